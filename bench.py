@@ -47,6 +47,7 @@ MALL_GATHER_GBS = 8600.0  # indexed rows served from the Infinity Cache (same gu
 BF16_MFMA_PEAK_TFLOPS = 2500.0   # dense bf16 MFMA peak (same guide; AMD's 5 PFLOP/s headline includes 2:1 sparsity)
 F32_MFMA_PEAK_TFLOPS = 157.0     # dense fp32 MFMA peak (same guide)
 L2_GATHER_GBS = 17800.0   # ... from an XCD's L2 (16.8-18.8 TB/s)
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: all arrays' data together (headers included, the files stay below 64 MB)
 
 # BASELINE.json configs[1..4]; c2 is the configuration the metric is quoted on
 CONFIGS = {
@@ -75,9 +76,14 @@ def parse():
     p.add_argument('--scaling', choices=['weak', 'strong'], default='strong',
                    help='world size > 1: strong = ONE graph cut across the ranks (BASELINE configs[3..4]), weak = one edge '
                         'block per rank (the union graph grows with the rank count)')
-    p.add_argument('--repeats', type=int, default=3,
-                   help='timed regions of --steps steps each (the contract\'s EXACTLY K steps inside the bracket): `value` is their median, '
-                        'the first region\'s figure is reported beside it')
+    p.add_argument('--repeats', type=int, default=1,
+                   help='timed regions of --steps steps each (the contract\'s EXACTLY K steps inside the bracket; the default, one region, '
+                        'times --steps steps in all): `value` is their median, the first region\'s figure is reported beside it')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps, write what the last timed step computed (loss, its terms, the embeddings, the updated '
+                        'parameters) as DIR/<name>.npy in float32, %d MB at most (a fixed sample of the rows of a larger array); '
+                        'every timed region starts from the same weights and random state, so runs with the same arguments are '
+                        'comparable array for array' % (DUMP_BUDGET_BYTES >> 20))
     p.add_argument('--launch-check', action='store_true',
                    help='only start the ranks, form the process group (gloo when there is no GPU) and report how many ranks '
                         'met; no compute (tests/test_distributed_cpu.py runs it on CPU)')
@@ -113,6 +119,8 @@ def parse():
     p.add_argument('--probe-steps', type=int, default=10)
     p.add_argument('--profile-steps', type=int, default=3, help='instrumented eager steps for the roofline figure')
     args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
     cfg = CONFIGS[args.config]
     for name, key in (('hidden', 'hidden'), ('n_bases', 'bases'), ('n_flows', 'flows'), ('gemm_precision', 'gemm')):
         if getattr(args, name) is None:
@@ -486,6 +494,32 @@ def rewarm(step_fn, seconds):
             break
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of ``arrays`` as out_dir/<name>.npy in float32, DUMP_BUDGET_BYTES in all.  Arrays are taken
+    smallest first, each up to an equal share of what is left; a larger one is written as a sample of its rows (dim 0; a 1-D array:
+    of its elements) picked by RandomState(0) and kept in row order -- the same rows for the same shapes in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items() if isinstance(v, torch.Tensor)}
+    left = DUMP_BUDGET_BYTES // 4          # float32 elements
+    written = {}
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].numel(), k))):
+        t = arrays[name].float()
+        share = left // (len(arrays) - i)
+        if t.numel() > share:
+            flat = t.dim() < 2
+            t = t.reshape(t.shape[0], -1) if t.dim() >= 2 and t[0].numel() <= share else t.reshape(-1, 1)
+            n_rows = max(1, share // t.shape[1])
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], n_rows, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            t = t.reshape(-1) if flat else t
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        left -= a.size
+        written[name] = list(a.shape)
+    print(f'[bench] --dump-outputs: {len(written)} arrays in {out_dir}', file=sys.stderr)
+    return written
+
+
 EXIT_NONFINITE_LOSS = 4
 EXIT_RANK_FAILED = 5           # a rank raised outside the recoverable places: it names itself and its phase on stderr, then leaves
 
@@ -626,6 +660,9 @@ def run_minibatch(args):
     Adam, recorded once and replayed as ONE hipGraph (gcn_vae_amd.graph_step); every replay draws a fresh batch.  Single GPU."""
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 or args.gpus > 1:
         raise SystemExit('bench.py --config mb is a single-GPU configuration (the sampled sub-graph is 20 000 edges)')
+    if args.dump_outputs:
+        raise SystemExit('bench.py --dump-outputs covers the full-graph configurations; --config mb draws a fresh batch per step '
+                         'from a sampler whose state its timed regions do not restore')
     sys.stdout.flush()
     saved_stdout = os.dup(1)
     os.dup2(2, 1)
@@ -841,6 +878,7 @@ def _main():
     pinned = [torch.zeros(200, dtype=torch.long).pin_memory() for _ in range(2)]
     pinned_evt, pinned_turn = [None, None], [0]
     one = torch.ones((), device=dev)        # d(loss)/d(loss): handed to backward instead of a ones_like fill per step
+    last = {}       # --dump-outputs: the tensors of the latest step_body (in a capture: the graph's static outputs)
 
     # ---- the two multi-GPU schemes.  Each mode = inputs + how the exchange is wired into the model ----------
     modes = {}
@@ -896,6 +934,8 @@ def _main():
         opt.zero_grad()
         embed = model(cur['g'], cur['node_id'], cur['etype'], cur['enorm'])
         loss, pred, kl, mmd = model.get_loss(cur['g'], embed, cur['samples'], cur['labels'])
+        if args.dump_outputs:      # held only when asked for: a live tensor changes what a capture's memory pool reuses
+            last.update(loss=loss, predict_loss=pred, kl=kl, mmd=mmd, embed=embed)
         loss.backward(gradient=one)
         if reducer is not None:
             reducer.finish()               # what backward could not start early, the waits, the 1/world scale
@@ -978,7 +1018,7 @@ def _main():
     # candidates = scheme x launch mode.  With collectives on the step the launch mode is part of the question: segments
     # remove the per-kernel host cost but add a graph launch per segment; "auto" measures instead of guessing.
     phase('warm-up, capture and probe of the partition schemes')
-    programs, probe = {}, {}
+    programs, probe, program_outs = {}, {}, {}
     auto = dist_on and args.partition == 'auto'
     # Every scheme / launch variant is warmed, captured and probed from the SAME initial weights and moments, and so are the timed
     # regions afterwards: the probes of `--partition auto` are dozens of updates, enough with IAF blocks to leave exp(alpha + mu) at
@@ -1026,6 +1066,7 @@ def _main():
                                                                                  '' if chunks == 2 else '/1-block',
                                                                                  '' if row_chunks == row_env else '/pipelined-%d' % row_chunks)
             programs[key] = (name,) + capture_current(sgm) + (chunks, row_chunks)
+            program_outs[key] = dict(last)
             if auto or len(modes) * len(variants) > 1:
                 k = max(1, args.probe_steps)
                 timed_run(1, programs[key][2])
@@ -1064,6 +1105,10 @@ def _main():
     # that ends on NaN weights is not a training measurement (the reference, under its global anomaly mode, would stop there:
     # kgvae/model.py:10).  The restore is outside the timed bracket; a non-finite final loss makes this program exit non-zero.
     snap = opt.snapshot()
+    # ... and from the same random state: the device RNG's {seed, tick} and the host draw of the MMD rows, which the
+    # time-bounded rewarm would otherwise leave at a different point in every run
+    rng = _ops.device_rng(dev)
+    rng_snap, pick_snap = rng.state.clone(), pick_rng.getstate()
     rewarm(run_step, args.rewarm_seconds if (cpu_rec is not None) else 0.0)
     for _ in range(args.warmup):
         loss = run_step()
@@ -1073,6 +1118,8 @@ def _main():
     for _rep in range(max(1, args.repeats)):
         phase(f'timed region {_rep + 1}')
         opt.restore(snap)
+        rng.state.copy_(rng_snap)
+        pick_rng.setstate(pick_snap)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -1102,6 +1149,11 @@ def _main():
         ec[rank] = cur['edges']
         dist.all_reduce(ec)
         edge_counts = [int(v) for v in ec.tolist()]
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before the roofline leg steps the model again
+        outs = dict(program_outs[chosen] if replay is not None else last)
+        outs.update(('param.' + k, p) for k, p in model.named_parameters())
+        dumped = dump_outputs(args.dump_outputs, outs)
 
     phase('roofline leg (instrumented eager steps)')
     # ---- roofline leg: the same step, eager, with HIP events around the K1 launches --------------
@@ -1208,6 +1260,8 @@ def _main():
         out['cpu_baseline'], out['parity_check'] = cpu_rec, parity_rec
         out['config']['k1_operands'] = 'bf16 (fp32 accumulate, fp32 rows in memory)' if k1_bf else 'f32'
         out['loss_is_finite'] = bool(np.isfinite(final_loss))
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if parity_rec is not None:
             out['parity_max_rel_err'] = parity_rec['parity_max_rel_err']
         sys.stdout.flush()
