@@ -382,6 +382,115 @@ __global__ __launch_bounds__(256) void k_rank_scores(const RankParams rp) {
     }
 }
 
+// ---- filtered rank count (the filtered MRR protocol): PASS 1 of k_rank_scores with a per-tile filter mask ----------------
+// tgt comes from k_rank_scores<0>; this kernel repeats the SAME k-ordered MFMA chain and epilogue arithmetic, so its raw count
+// equals gv_rank_scores' bit for bit, and in the same ballots drops the candidates listed in the query's filter range:
+//   count_filt[row] += #{ col != target[row], col not in filt_ent[filt_lo[row] .. filt_hi[row]) : logit > tgt (or NaN) } * 2 + ties
+// The filter of the 64 x 64 tile is a 64-bit word per row in LDS (bit j = column n0 + j is filtered), built before the MFMA loop:
+// two lower-bound searches per row for the window [n0, n0 + 64) of its sorted list, then the window's entries (<= 64 per row) set
+// bits one lane each.  A filtered NaN candidate counts nowhere: exclusion acts on the ballot of the very logit that is counted.
+struct RankFiltParams {
+    RankParams rp;           // rp.count = the raw count (may be NULL)
+    const int* filt_lo;
+    const int* filt_hi;
+    const int* filt_ent;
+    int n_ent;               // length of filt_ent: every range is clamped into it
+    int* count_filt;
+};
+
+__device__ __forceinline__ int lower_bound_i32(const int* a, int lo, int hi, int key) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltParams fp) {
+    constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1;
+    __shared__ float As[BK * LDA_S];
+    __shared__ float Bs[BK * LDB_S];
+    __shared__ unsigned long long fmask[BM];       // 512 B: the tile's filter, one word per row
+    __shared__ int win_lo[BM], win_hi[BM];         // each row's entries inside [n0, n0 + 64)
+    const RankParams& rp = fp.rp;
+    const GemmParams& p = rp.g;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    float ra[BM * BK / 256], rb[BN * BK / 256];
+    load_a<false, BM, BK>(p, m0, 0, p.k, ra);      // the first operand loads fly under the filter searches
+    load_b<true, BN, BK>(p, n0, 0, p.k, rb);
+
+    // filter window: thread t < 64 searches row t's list for n0, thread 64 + t for n0 + 64 (two waves, one search each)
+    if (threadIdx.x < 2 * BM) {
+        const int rl = threadIdx.x & (BM - 1), row = m0 + rl;
+        int lo = 0, hi = 0;
+        if (row < p.m) {
+            lo = min(max(fp.filt_lo[row], 0), fp.n_ent);
+            hi = min(max(fp.filt_hi[row], lo), fp.n_ent);
+        }
+        const int pos = lower_bound_i32(fp.filt_ent, lo, hi, threadIdx.x < BM ? n0 : n0 + BN);
+        if (threadIdx.x < BM) { win_lo[rl] = pos; fmask[rl] = 0ull; }
+        else win_hi[rl] = pos;
+    }
+    __syncthreads();
+    // the window's entries, staged cooperatively: wave w takes rows 16 w .. 16 w + 15, one entry per lane (a long list costs its
+    // window's entries only, never its length; an empty window -- most rows of most tiles -- costs one LDS read)
+    for (int i = 0; i < BM / 4; ++i) {
+        const int rl = wid * (BM / 4) + i;
+        const int a = win_lo[rl], cnt = win_hi[rl] - a;
+        for (int j = lane; j < cnt; j += 64) {
+            const unsigned bit = (unsigned)(fp.filt_ent[a + j] - n0);
+            if (bit < 64u) atomicOr(&fmask[rl], 1ull << bit);
+        }
+    }
+
+    for (int k0 = 0; k0 < p.k; k0 += BK) {
+        stage_a<false, BM, BK>(As, ra);
+        stage_b<true, BN, BK>(Bs, rb);
+        __syncthreads();
+        if (k0 + BK < p.k) {
+            load_a<false, BM, BK>(p, m0, k0 + BK, p.k, ra);
+            load_b<true, BN, BK>(p, n0, k0 + BK, p.k, rb);
+        }
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * LDA_S + wm + l31], Bs[(kk + lhi) * LDB_S + wn + l31],
+                                                       acc, 0, 0, 0);
+        __syncthreads();
+    }
+    const float bv = rp.bias ? *rp.bias : 0.f;
+    const int col = n0 + wn + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int rl = wm + (r & 3) + 8 * (r >> 2) + 4 * lhi, row = m0 + rl;
+        const bool in = row < p.m && col < p.n;
+        const float logit = acc[r] + bv;                        // the epilogue of k_rank_scores<1>, unchanged
+        const int tcol = row < p.m ? rp.target[row] : -1;
+        const float t = row < p.m ? rp.tgt[row] : 0.f;
+        const bool other = in && col != tcol;
+        const bool above = other && !(logit <= t);
+        const bool equal = other && logit == t;
+        const unsigned long long ma = __ballot(above), me = __ballot(equal);
+        if (l31 == 0 && row < p.m) {
+            const unsigned ha = (unsigned)(lhi ? (ma >> 32) : (ma & 0xffffffffull));
+            const unsigned he = (unsigned)(lhi ? (me >> 32) : (me & 0xffffffffull));
+            const unsigned keep = ~(unsigned)(fmask[rl] >> wn);    // this half-wave's 32 columns of the row's filter word
+            if (rp.count) {
+                const int c = 2 * __popc(ha) + __popc(he);
+                if (c) atomicAdd(rp.count + row, c);
+            }
+            const int cf = 2 * __popc(ha & keep) + __popc(he & keep);
+            if (cf) atomicAdd(fp.count_filt + row, cf);
+        }
+    }
+}
+
 // ---- relation-grouped products for dense per-relation weights (the `basis` regulariser) ----------------
 // With W_r = sum_b w_comp[r, b] V_b a full (in x out) matrix, a message is a 2*in*out-flop mat-vec: MFMA work.  Edges are
 // taken in BY-RELATION order (ops.RelationIndex.by_rel), so the messages of one relation are one GEMM whose A rows are
@@ -851,6 +960,36 @@ extern "C" int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e
     hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);
     hipLaunchKernelGGL(k_rank_scores<1>, grid, block, 0, st, rp);
     return launch_status("gv_rank_scores");
+}
+
+extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
+                                       int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_filtered: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count_filt, GV_ERR_NULL, "gv_rank_scores_filtered: NULL pointer");
+    GV_REQUIRE(filt_lo && filt_hi && filt_ent, GV_ERR_NULL, "gv_rank_scores_filtered: NULL filter pointer");
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_filtered: leading dimension too small");
+    RankFiltParams fp;
+    RankParams& rp = fp.rp;
+    GemmParams& p = rp.g;
+    p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
+    p.m = m; p.n = v; p.k = h; p.lda = ld_q; p.ldb = ld_e; p.ldc = v;
+    p.act = GV_ACT_NONE; p.accumulate = 0; p.split_k = 1; p.k_chunk = h;
+    p.vec_a = aligned16(q) && (ld_q % 4 == 0);
+    p.vec_b = aligned16(e) && (ld_e % 4 == 0);
+    p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
+    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
+    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent; fp.count_filt = count_filt;
+    hipStream_t st = (hipStream_t)stream;
+    if (count_raw && fill_words(count_raw, 0u, (size_t)m * sizeof(int), st) != hipSuccess)
+        return launch_status("gv_rank_scores_filtered(fill)");
+    if (fill_words(count_filt, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status("gv_rank_scores_filtered(fill)");
+    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
+    hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);           // tgt[row] = the target's logit
+    hipLaunchKernelGGL(k_rank_scores_filtered, grid, block, 0, st, fp);
+    return launch_status("gv_rank_scores_filtered");
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

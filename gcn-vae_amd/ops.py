@@ -558,6 +558,45 @@ def rank_scores(q, entities, target, bias=None):
     return count[:m].to(torch.float32) * 0.5
 
 
+def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=None):
+    """(raw, filtered) ranks of ``target[i]``, both as ``rank_scores`` returns them (0-based floats, x.5 under ties), from one
+    launch pair (gv_rank_scores_filtered).  The filtered rank leaves out the candidates ``filt_ent[filt_lo[i]:filt_hi[i]]`` --
+    entity ids sorted ascending and unique inside each range (ranking.FilterIndex builds them) -- whatever their score; ranges
+    may be empty, may hold the target and may be shared.  The raw rank equals ``rank_scores`` bit for bit."""
+    q, ld_q = _row_major(q, 'q')
+    entities, ld_e = _row_major(entities, 'entities')
+    if q.shape[1] != entities.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    m, v = q.shape[0], entities.shape[0]
+    target = target.reshape(-1)
+    if target.numel() != m:
+        raise ValueError('one target per query row')
+    filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+    if filt_lo.numel() != m or filt_hi.numel() != m:
+        raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+    n_ent = filt_ent.numel()
+    if n_ent >= 2 ** 31:
+        raise ValueError('filt_ent: more than 2**31 - 1 entries')
+    if m and (int(target.min()) < 0 or int(target.max()) >= v):
+        raise ValueError(f'targets must lie in [0, {v})')
+    if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
+        raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+    if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
+        raise ValueError(f'filtered entity ids must lie in [0, {v})')
+    i32 = dict(device=q.device, dtype=torch.int32)
+    tgt32 = target.to(**i32).contiguous()
+    lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+    ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    if bias is not None:
+        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
+    counts = torch.empty(2, max(m, 1), **i32)
+    lib.call('gv_rank_scores_filtered', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, ptr(ws), ptr(counts[0]), ptr(counts[1]), m, v, q.shape[1], lib.stream())
+    both = counts[:, :m].to(torch.float32) * 0.5
+    return both[0], both[1]
+
+
 def pick_split_k(m_out, n_out, k):
     """Reduction-heavy shapes (weight gradients: small output, K = nodes) need split-K to fill 256 CUs."""
     tiles = ((m_out + 63) // 64) * ((n_out + 63) // 64)

@@ -11,6 +11,11 @@ to leave the target inside the tie block.  Ties are counted explicitly: rank = #
 position in such a block; ranks are floats), and a NaN target score (diverged run) ranks LAST -- never the
 optimistic rank 1 that would make ``main`` keep a broken checkpoint as "best".
 ``perturb_and_get_rank_unfused`` keeps the materialised form (one GEMM + torch ops) as the in-repo cross-check.
+
+Filtered evaluation (the protocol of published FB15k-237 / WN18RR figures; the reference reports raw ranks only,
+kgvae/link_predict.py:7): a ``FilterIndex`` of the dataset's known triplets lists, per query, the OTHER true answers, and
+``ops.rank_scores_filtered`` (gv_rank_scores_filtered) leaves them out of the count in the same launch that gives the raw
+rank.  ``calc_filtered_mrr`` reports both.
 """
 import torch
 
@@ -66,6 +71,100 @@ def perturb_and_get_rank_unfused(embedding, w, a, r, b, test_size, batch_size=10
             print("batch {} / {}: MR : {:.6f} |  MRR : {:.6f}".format(idx, n_batch, rr.mean().item(),
                                                                       (1.0 / rr).mean().item()))
     return torch.cat(ranks)
+
+
+class FilterIndex:
+    """The known true answers of every (entity, relation) query in both directions, built once per dataset:
+      'o'  object query (s, r, ?):  key s * num_rels + r -> the sorted unique objects o with (s, r, o) known
+      's'  subject query (?, r, o): key o * num_rels + r -> the sorted unique subjects s with (s, r, o) known
+    Keys are int64 (num_nodes * num_rels passes 2**31 on large graphs).  Per direction ``keys[d]`` (int64) and ``ent[d]`` (int32)
+    are parallel arrays sorted by (key, entity): the answers of one key are a contiguous run of ``ent[d]``, which is exactly the
+    (filt_lo, filt_hi, filt_ent) form ``ops.rank_scores_filtered`` takes.  Built with torch ops on ``device`` (CPU works too)."""
+
+    def __init__(self, num_nodes, num_rels, *triplet_sets, device='cpu'):
+        self.num_nodes, self.num_rels, self.device = int(num_nodes), int(num_rels), torch.device(device)
+        parts = [torch.as_tensor(t).to(device=self.device, dtype=torch.long).reshape(-1, 3) for t in triplet_sets]
+        trip = torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.long, device=self.device)
+        if trip.numel() and (int(trip[:, [0, 2]].min()) < 0 or int(trip[:, [0, 2]].max()) >= self.num_nodes
+                             or int(trip[:, 1].min()) < 0 or int(trip[:, 1].max()) >= self.num_rels):
+            raise ValueError('triplets out of range of num_nodes / num_rels')
+        s, r, o = trip[:, 0], trip[:, 1], trip[:, 2]
+        self.keys, self.ent = {}, {}
+        for d, a, e in (('o', s, o), ('s', o, s)):
+            key = a * self.num_rels + r
+            order = torch.argsort(e, stable=True)
+            order = order[torch.argsort(key[order], stable=True)]           # by (key, entity)
+            k, x = key[order], e[order]
+            keep = torch.ones_like(k, dtype=torch.bool)
+            if k.numel() > 1:
+                keep[1:] = (k[1:] != k[:-1]) | (x[1:] != x[:-1])              # duplicate triplets once
+            self.keys[d], self.ent[d] = k[keep].contiguous(), x[keep].to(torch.int32).contiguous()
+        if max(self.ent['o'].numel(), 1) >= 2 ** 31:
+            raise ValueError('more than 2**31 - 1 distinct triplets')
+
+    def lookup(self, a, r, direction):
+        """(lo, hi): the range of ``ent[direction]`` holding the known answers of each query (a[i], r[i]), on ``a``'s device."""
+        keys = self.keys[direction]
+        q = a.to(device=self.device, dtype=torch.long) * self.num_rels + r.to(device=self.device, dtype=torch.long)
+        lo = torch.searchsorted(keys, q, right=False)
+        hi = torch.searchsorted(keys, q, right=True)
+        return lo.to(a.device), hi.to(a.device)
+
+    def entities(self, direction, device=None):
+        return self.ent[direction] if device is None else self.ent[direction].to(device)
+
+
+def perturb_and_get_rank_filtered(embedding, w, a, r, b, test_size, filter_index, direction, batch_size=100, all_batches=True,
+                                  flow_log_prob=None, verbose=False):
+    """(raw, filtered) ranks of ``b`` for the queries (a, r): ``perturb_and_get_rank`` with the known answers of each query left
+    out of the filtered count.  ``direction`` 'o' when ``b`` are objects (queries (s, r, ?)), 's' when they are subjects."""
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    emb = embedding.detach().contiguous()
+    wd = w.detach()
+    ent = filter_index.entities(direction, emb.device)
+    raw, filt = [], []
+    for lo in range(0, n, MAX_QUERY_ROWS):
+        hi = min(n, lo + MAX_QUERY_ROWS)
+        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
+        f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction)
+        rr, rf = ops.rank_scores_filtered(q, emb, b[lo:hi], f_lo, f_hi, ent, flow_log_prob)
+        raw.append(rr)
+        filt.append(rf)
+        if verbose:
+            x = 1.0 + torch.cat(filt).float()
+            print("rows {} / {}: MR (filtered) : {:.6f} |  MRR (filtered) : {:.6f}".format(hi, n, x.mean().item(),
+                                                                                          (1.0 / x).mean().item()))
+    if not raw:
+        empty = torch.zeros(0, dtype=torch.float32, device=emb.device)
+        return empty, empty.clone()
+    return torch.cat(raw), torch.cat(filt)
+
+
+def calc_filtered_mrr(embedding, w, test_triplets, filter_index, hits=[1, 3, 10], eval_bz=100, all_batches=True,
+                      flow_log_prob=None, verbose=True):
+    """Raw and filtered MRR / Hits@k over both directions, from one scorer launch pair per chunk of queries.  Returns
+    ``{'mrr_raw', 'mrr_filtered', 'hits_raw': {k: v}, 'hits_filtered': {k: v}}``; ``mrr_raw`` equals ``calc_mrr``'s value."""
+    with torch.no_grad():
+        test_triplets = test_triplets.to(embedding.device)
+        w = w.to(embedding.device)
+        if isinstance(flow_log_prob, torch.Tensor):
+            flow_log_prob = flow_log_prob.to(embedding.device)
+        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
+        n = test_triplets.shape[0]
+        raw_s, filt_s = perturb_and_get_rank_filtered(embedding, w, o, r, s, n, filter_index, 's', eval_bz, all_batches,
+                                                      flow_log_prob)
+        raw_o, filt_o = perturb_and_get_rank_filtered(embedding, w, s, r, o, n, filter_index, 'o', eval_bz, all_batches,
+                                                      flow_log_prob)
+        out = {}
+        for kind, ranks in (('raw', torch.cat([raw_s, raw_o]) + 1), ('filtered', torch.cat([filt_s, filt_o]) + 1)):
+            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
+            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
+        if verbose:
+            for kind in ('raw', 'filtered'):
+                print("MRR ({}): {:.6f}".format(kind, out['mrr_' + kind]))
+                for hit in hits:
+                    print("Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
+    return out
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

@@ -154,6 +154,9 @@ def main(args):
     adj_list, degrees = sampling.get_adj_and_degrees(num_nodes, train_data)
     optimizer = FlatAdam(model.parameters(), lr=args.lr, max_grad_norm=args.grad_norm)   # clip + Adam, one arena
     forward_time, backward_time, step_time = [], [], []
+    # --filtered-eval: the known triplets (train + valid + test) indexed once; model selection stays on the raw MRR
+    filters = ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev) \
+        if getattr(args, 'filtered_eval', False) else None
 
     if args.test_mode is True:
         print("\nstart testing:")
@@ -165,6 +168,10 @@ def main(args):
         print("Using best epoch: {}".format(checkpoint['epoch']))
         with torch.no_grad():
             embed = model(test_graph, test_node_id, test_rel, test_norm)
+        if filters is not None:
+            return ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
+                                             eval_bz=args.eval_batch_size, all_batches=True,
+                                             flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
         return ranking.calc_mrr(embed, model.w_relation, test_t, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
                                 all_batches=True, flow_log_prob=model.encoder.get_flow_log_prob())
 
@@ -242,8 +249,13 @@ def main(args):
             torch.save({'state_dict': host_state_dict(model), 'epoch': epoch}, args.model_state_file)
             with torch.no_grad():
                 embed = model(val_graph, val_node_id, val_rel, val_norm)
-            mrr = ranking.calc_mrr(embed, model.w_relation, valid_t, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
-                                   all_batches=False, flow_log_prob=model.encoder.get_flow_log_prob())
+            if filters is not None:
+                mrr = ranking.calc_filtered_mrr(embed, model.w_relation, valid_t, filters, hits=[1, 3, 10],
+                                                eval_bz=args.eval_batch_size, all_batches=False,
+                                                flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
+            else:
+                mrr = ranking.calc_mrr(embed, model.w_relation, valid_t, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
+                                       all_batches=False, flow_log_prob=model.encoder.get_flow_log_prob())
             if mrr < best_mrr:
                 torch.save({'state_dict': host_state_dict(model), 'epoch': epoch}, args.model_state_file + "_latest")
             else:
@@ -297,6 +309,9 @@ def build_parser():
     p.add_argument("--device-sampler", action="store_true",
                    help="prepare batches on the GPU (uniform sampler, torch's device RNG instead of numpy's: not the "
                         "reference's random stream, ~10x less host time per step)")
+    p.add_argument("--filtered-eval", action="store_true",
+                   help="also report filtered MRR and Hits@1/3/10 (the other known answers of a query -- train + valid + "
+                        "test -- left out of its rank); model selection stays on the raw MRR; not a reference flag")
     return p
 
 

@@ -520,6 +520,17 @@ int gv_made_row_bwd(const float* g_out, int n_layers, const gv_row_layer* layers
 int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias, float* tgt,
                    int* count, int m, int v, int h, void* stream);
 
+/* Filtered rank count (the filtered protocol of link-prediction MRR / Hits@k): the same scores, ties and NaN rules as
+ * gv_rank_scores, but the candidates listed for query i -- filt_ent[filt_lo[i] .. filt_hi[i]), entity ids sorted ascending and
+ * unique within the range -- count neither as better nor as equal (a listed NaN candidate included):
+ *   count_filt[i] = 2 * #{ j != t_i, j unlisted : logit[i, j] > logit[i, t_i] } + #{ j != t_i, j unlisted : logit equal }
+ * Ranges may be empty, may list the target, and may be shared by many queries; each is clamped into [0, n_filt_ent).
+ * count_raw (may be NULL) receives what gv_rank_scores would return, bit for bit, from the same launch.
+ * filt_lo / filt_hi int32 [m], filt_ent int32 [n_filt_ent]; tgt: m floats of workspace; counts int32 [m] (zeroed here). */
+int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                            const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
+                            int* count_raw, int* count_filt, int m, int v, int h, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.

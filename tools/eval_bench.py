@@ -2,7 +2,9 @@
 """Raw-MRR evaluation throughput: the whole FB15k-237 test split in both directions
 (2 x 20 466 queries against 14 541 entities, h = 200) through the fused rank-count scorer (gv_rank_scores) and through the
 materialised form (one GEMM per 100-query batch + torch sigmoid / gather / compare / sum -- what ranking.py did before).
-    python tools/eval_bench.py [--cpu-rows 200]     # --cpu-rows: also time the reference's (h, Eb, V) formulation on the host"""
+    python tools/eval_bench.py [--cpu-rows 200]     # --cpu-rows: also time the reference's (h, Eb, V) formulation on the host
+    python tools/eval_bench.py --filtered           # filtered ranks: raw only, raw + filtered in one launch pair, materialised torch
+--filtered takes the test split and the filter (train + valid + test) of the FB15k-237-synthetic dataset (Zipf-skewed lists)."""
 import argparse
 import os
 import sys
@@ -17,7 +19,10 @@ from gcn_vae_amd import ranking   # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cpu-rows', type=int, default=0)
+    ap.add_argument('--filtered', action='store_true')
     args = ap.parse_args()
+    if args.filtered:
+        return filtered_leg()
     gen = torch.Generator().manual_seed(0)
     v, h, n, n_rel = 14541, 200, 20466, 237
     emb = (torch.randn(v, h, generator=gen) * 0.3).cuda()
@@ -57,6 +62,78 @@ def main():
         dt = time.perf_counter() - t0
         print(f'host, reference formulation: {dt * 1e3:.1f} ms for {args.cpu_rows} queries -> '
               f'{dt / args.cpu_rows * 2 * n:.1f} s per full evaluation ({torch.get_num_threads()} threads)')
+
+
+def filtered_leg(chunk=4096, reps=5):
+    from gcn_vae_amd import data, ops
+    kg = data.load_data('FB15k-237-synthetic')
+    dev = torch.device('cuda')
+    t0 = time.perf_counter()
+    fi = ranking.FilterIndex(kg.num_nodes, kg.num_rels, kg.train, kg.valid, kg.test, device=dev)
+    torch.cuda.synchronize()
+    t_index = time.perf_counter() - t0
+    gen = torch.Generator().manual_seed(0)
+    v, h = kg.num_nodes, 200
+    emb = (torch.randn(v, h, generator=gen) * 0.3).to(dev)
+    w = torch.randn(kg.num_rels, h, generator=gen).to(dev)
+    trip = torch.from_numpy(kg.test).to(dev)
+    s, r, o = trip[:, 0], trip[:, 1], trip[:, 2]
+    n = trip.shape[0]
+    dirs = ((o, s, 's'), (s, o, 'o'))
+
+    def raw_only():
+        return [ranking.perturb_and_get_rank(emb, w, a, r, b, n) for a, b, _ in dirs]
+
+    def raw_and_filtered():
+        return [ranking.perturb_and_get_rank_filtered(emb, w, a, r, b, n, fi, d) for a, b, d in dirs]
+
+    def materialised():          # one GEMM per chunk of queries, the filter as a dense (chunk, V) mask, torch compare + sum
+        out = []
+        for a, b, d in dirs:
+            lo_all, hi_all = fi.lookup(a, r, d)
+            ent = fi.entities(d).long()
+            for c in range(0, n, chunk):
+                sl = slice(c, min(n, c + chunk))
+                q = ops.mul(emb[a[sl]].contiguous(), w[r[sl]].contiguous())
+                score = ops.gemm(q, emb, trans_b=True)
+                m = score.shape[0]
+                lo, hi = lo_all[sl], hi_all[sl]
+                lens = hi - lo
+                total = int(lens.sum())
+                keep = torch.ones_like(score, dtype=torch.bool)
+                if total:
+                    rows = torch.repeat_interleave(torch.arange(m, device=dev), lens)
+                    first = torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+                    idx = torch.repeat_interleave(lo, lens) + torch.arange(total, device=dev) - first
+                    keep[rows, ent[idx]] = False
+                t = b[sl].view(-1, 1)
+                keep.scatter_(1, t, False)
+                tgt = score.gather(1, t)
+                out.append(((~(score <= tgt)) & keep).sum(1).float() + 0.5 * ((score == tgt) & keep).sum(1).float())
+        return out
+
+    def timed(fn, k):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / k, out
+
+    t_raw, _ = timed(raw_only, reps)
+    t_both, both = timed(raw_and_filtered, reps)
+    t_mat, mat = timed(materialised, 2)
+    filt = torch.cat([f for _, f in both])
+    assert torch.equal(filt, torch.cat(mat)), 'fused filtered ranks differ from the materialised ones'
+    lens = torch.cat([torch.unique_consecutive(fi.keys[d], return_counts=True)[1] for d in 'so'])
+    print(f'filter index : {t_index * 1e3:8.2f} ms once ({fi.ent["o"].numel()} distinct triplets; list length mean '
+          f'{lens.float().mean():.2f}, max {int(lens.max())})')
+    print(f'raw only     : {t_raw * 1e3:8.2f} ms per full evaluation ({2 * n} queries x {v} entities, h = {h})')
+    print(f'raw+filtered : {t_both * 1e3:8.2f} ms  ({t_both / t_raw:.2f}x raw only)   filtered MRR '
+          f'{(1.0 / (filt + 1)).mean().item():.6f}')
+    print(f'materialised : {t_mat * 1e3:8.2f} ms (filtered only: GEMM + dense filter mask + torch compare / sum, '
+          f'{chunk}-query chunks)')
 
 
 if __name__ == '__main__':
