@@ -11,7 +11,10 @@
 // staging); the shapes on this path are skinny (K = N = 200..400, M = nodes), so the kernel is
 // sized for many small blocks rather than for a 256^2 pipeline.
 // split-K (grid.z) writes raw partial tiles to a workspace that a second kernel sums in order.
+#include <limits.h>
 #include <stdlib.h>
+
+#include <algorithm>
 
 #include "common.h"
 
@@ -487,6 +490,215 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
             }
             const int cf = 2 * __popc(ha & keep) + __popc(he & keep);
             if (cf) atomicAdd(fp.count_filt + row, cf);
+        }
+    }
+}
+
+// ---- top-k link prediction (gv_topk_scores): the rankers' score pass with a selection epilogue ----------------------------
+// logit[i, j] = q_i . e_j + bias comes from the SAME k-ordered MFMA chain as k_rank_scores (so it equals gv_gemm_f32 + bias bit
+// for bit); the score matrix is never stored.  Candidates are ordered by a 64-bit key, larger = better:
+//   key = ordered_u32(logit) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
+// a strict total order (ties on the logit by lower id); key 0 is "no candidate" and decodes to id -1, logit -inf.
+// Stage 1 (k_topk_span): a workgroup owns a 64-row query tile and sweeps a span of 64-column entity tiles in ascending order.  The
+// tile's logits go through LDS; wave w then takes rows 16 w .. 16 w + 15, one lane per column: a key that beats the row's running
+// threshold (its current k-th key) is inserted into the row's sorted list (LDS, k keys per row), one wave-wide shift per
+// survivor.  Once a list is warm almost nothing passes, so a tile costs a compare and a ballot per row.  Filtered columns get key 0
+// through a per-row cursor into the sorted filter list (the next listed id is kept in LDS: a window without entries reads
+// nothing).  The span's k keys per row go to the workspace.  Stage 2 (k_topk_merge): one wave per row merges the S span lists.
+struct TopkParams {
+    GemmParams g;                 // a = Q, b = E (stored [v, h]), m, n = v, k = h
+    const float* bias;
+    const int* filt_lo;           // NULL: no filter
+    const int* filt_hi;
+    const int* filt_ent;
+    int n_ent;                    // length of filt_ent: every range is clamped into it
+    int topk;                     // 1..128
+    int span_tiles;               // 64-column tiles per span (blockIdx.y = span)
+    int n_spans;
+    unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
+};
+
+constexpr int TOPK_MAX = 128;
+
+__device__ __forceinline__ unsigned long long topk_key(float x, int col) {
+    unsigned u = __float_as_uint(x);
+    if (x != x) u = 0u;
+    else {
+        if (u == 0x80000000u) u = 0u;
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    return ((unsigned long long)u << 32) | (unsigned)~col;
+}
+
+__device__ __forceinline__ float topk_key_logit(unsigned long long key) {
+    const unsigned o = (unsigned)(key >> 32);
+    if (key == 0ull) return -__builtin_huge_valf();
+    if (o == 0u) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// insert `key` into the wave's sorted (descending) list: lane l holds positions l + 64 j in a[j]; the last position falls off
+template <int NK>
+__device__ __forceinline__ void topk_insert(unsigned long long (&a)[NK], unsigned long long key, int lane) {
+    unsigned long long up[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) up[j] = __shfl(a[j], (lane + 63) & 63);     // lane l gets lane l - 1's (lane 0: lane 63's)
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const unsigned long long prev = lane ? up[j] : (j ? up[j - 1] : ~0ull);
+        a[j] = a[j] > key ? a[j] : (prev > key ? key : prev);
+    }
+}
+
+template <int NK>
+__device__ __forceinline__ void topk_insert_mask(unsigned long long (&a)[NK], unsigned long long keyv, unsigned long long sv, int lane) {
+    while (sv) {
+        const int c = __builtin_ctzll(sv);
+        sv &= sv - 1ull;
+        topk_insert<NK>(a, readlane_u64(keyv, c), lane);
+    }
+}
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
+    constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1, LDL = BN + 1;
+    __shared__ float As[BK * LDA_S];
+    __shared__ float Bs[BK * LDB_S];
+    __shared__ float Ls[BM * LDL];                 // the tile's logits, row-major
+    __shared__ unsigned long long thr[BM];         // each row's k-th key
+    __shared__ int cur[BM], fhi[BM], nxt[BM];      // filter cursor, range end, the id at the cursor (INT_MAX: none left)
+    __shared__ int fl[4][64];                      // per wave: column j of the row at hand is listed <=> fl[w][j] == tag
+    extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const GemmParams& p = tp.g;
+    const int k = tp.topk;
+    const int m0 = blockIdx.x * BM;
+    const int t_begin = blockIdx.y * tp.span_tiles;
+    const int t_end = min(t_begin + tp.span_tiles, (p.n + BN - 1) / BN);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const bool filtered = tp.filt_lo != nullptr;
+    float ra[BM * BK / 256], rb[BN * BK / 256];
+    if (t_begin < t_end) {
+        load_a<false, BM, BK>(p, m0, 0, p.k, ra);
+        load_b<true, BN, BK>(p, t_begin * BN, 0, p.k, rb);
+    }
+    for (int i = threadIdx.x; i < BM * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (threadIdx.x < BM) {
+        const int rl = threadIdx.x, row = m0 + rl;
+        thr[rl] = 0ull;
+        int lo = 0, hi = 0;
+        if (filtered && row < p.m) {
+            lo = min(max(tp.filt_lo[row], 0), tp.n_ent);
+            hi = min(max(tp.filt_hi[row], lo), tp.n_ent);
+            lo = lower_bound_i32(tp.filt_ent, lo, hi, t_begin * BN);
+        }
+        cur[rl] = lo; fhi[rl] = hi;
+        nxt[rl] = lo < hi ? tp.filt_ent[lo] : INT_MAX;
+    }
+    const float bv = tp.bias ? *tp.bias : 0.f;
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = t * BN;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int k0 = 0; k0 < p.k; k0 += BK) {                     // the MFMA chain of k_rank_scores, unchanged
+            stage_a<false, BM, BK>(As, ra);
+            stage_b<true, BN, BK>(Bs, rb);
+            __syncthreads();
+            if (k0 + BK < p.k) {
+                load_a<false, BM, BK>(p, m0, k0 + BK, p.k, ra);
+                load_b<true, BN, BK>(p, n0, k0 + BK, p.k, rb);
+            }
+#pragma unroll
+            for (int kk = 0; kk < BK; kk += 2)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * LDA_S + wm + l31], Bs[(kk + lhi) * LDB_S + wn + l31],
+                                                           acc, 0, 0, 0);
+            __syncthreads();
+        }
+        if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
+            load_a<false, BM, BK>(p, m0, 0, p.k, ra);
+            load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            Ls[(wm + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDL + wn + l31] = acc[r] + bv;
+        __syncthreads();                                           // (Ls is rewritten after the next tile's first barrier)
+
+        const int col = n0 + lane;
+        for (int i = 0; i < BM / 4; ++i) {
+            const int rl = wid * (BM / 4) + i;
+            if (m0 + rl >= p.m) break;
+            unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], col) : 0ull;
+            if (filtered && nxt[rl] < n0 + BN) {                  // this row lists ids inside the tile: mark them, advance the cursor
+                const int c0 = cur[rl], hi = fhi[rl], tag = (t - t_begin) * BM + rl + 1;
+                const int idx = c0 + lane;
+                const int ent = idx < hi ? tp.filt_ent[idx] : INT_MAX;
+                const bool win = ent < n0 + BN;
+                const int cnt = __popcll(__ballot(win));
+                const unsigned bit = (unsigned)(ent - n0);
+                if (win && bit < 64u) fl[wid][bit] = tag;
+                if (fl[wid][lane] == tag) key = 0ull;
+                const int c1 = c0 + cnt;
+                const int nx = cnt < 64 ? __shfl(ent, cnt) : (c1 < hi ? tp.filt_ent[c1] : INT_MAX);
+                if (lane == 0) { cur[rl] = c1; nxt[rl] = nx; }
+            }
+            const unsigned long long sv = __ballot(key > thr[rl]);
+            if (sv) {
+                unsigned long long a[NK];
+                unsigned long long* lst = lists + rl * k;
+#pragma unroll
+                for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? lst[lane + 64 * j] : 0ull;
+                topk_insert_mask<NK>(a, key, sv, lane);
+#pragma unroll
+                for (int j = 0; j < NK; ++j) {
+                    if (lane + 64 * j < k) lst[lane + 64 * j] = a[j];
+                    if (lane + 64 * j == k - 1) thr[rl] = a[j];
+                }
+            }
+        }
+    }
+    // each wave hands its own rows' lists on (written by this wave only: no barrier)
+    for (int i = 0; i < BM / 4; ++i) {
+        const int rl = wid * (BM / 4) + i, row = m0 + rl;
+        if (row >= p.m) break;
+        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
+        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// stage 2: one wave per row merges the n_spans sorted lists of k keys and decodes the first k
+template <int NK>
+__global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* part, int m, int n_spans, int k, int* out_ids,
+                                                    float* out_logits) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= m) return;
+    const unsigned long long* src = part + (size_t)row * n_spans * k;
+    unsigned long long a[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? src[lane + 64 * j] : 0ull;     // span 0 is sorted already
+    for (int s = 1; s < n_spans; ++s) {
+        const unsigned long long t = readlane_u64(a[(k - 1) >> 6], (k - 1) & 63);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            const unsigned long long key = lane + 64 * j < k ? src[(size_t)s * k + lane + 64 * j] : 0ull;
+            topk_insert_mask<NK>(a, key, __ballot(key > t), lane);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const int pos = lane + 64 * j;
+        if (pos < k) {
+            out_ids[(size_t)row * k + pos] = (int)~(unsigned)a[j];
+            out_logits[(size_t)row * k + pos] = topk_key_logit(a[j]);
         }
     }
 }
@@ -992,6 +1204,66 @@ extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e,
     return launch_status("gv_rank_scores_filtered");
 }
 
+
+// spans per query-row tile: about 4 workgroups per CU of the MI355X (256 CUs) at any m, each span at least 8 column tiles long so
+// the running lists warm up.  A fixed CU count keeps the workspace size a function of (m, v, k) alone.
+static void topk_spans(int m, int v, int* span_tiles, int* n_spans) {
+    const long long row_tiles = ((long long)m + 63) / 64, col_tiles = ((long long)v + 63) / 64;
+    long long s = (4 * 256 + row_tiles - 1) / row_tiles;
+    s = std::min(s, std::max(1LL, col_tiles / 8));
+    s = std::max(1LL, std::min(s, 64LL));
+    const long long per = (col_tiles + s - 1) / s;
+    *span_tiles = (int)per;
+    *n_spans = (int)((col_tiles + per - 1) / per);
+}
+
+extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
+    if (m <= 0 || v <= 0 || k < 1 || k > TOPK_MAX) return 0;
+    int span_tiles = 0, n_spans = 0;
+    topk_spans(m, v, &span_tiles, &n_spans);
+    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
+                              const int* filt_hi, const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits,
+                              void* workspace, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
+               n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores: leading dimension too small");
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores: NULL pointer");
+    TopkParams tp;
+    GemmParams& p = tp.g;
+    p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
+    p.m = m; p.n = v; p.k = h; p.lda = ld_q; p.ldb = ld_e; p.ldc = v;
+    p.act = GV_ACT_NONE; p.accumulate = 0; p.split_k = 1; p.k_chunk = h;
+    p.vec_a = aligned16(q) && (ld_q % 4 == 0);
+    p.vec_b = aligned16(e) && (ld_e % 4 == 0);
+    p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
+    tp.bias = bias;
+    tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
+    tp.topk = k;
+    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
+    tp.part = (unsigned long long*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 27 KiB static)
+    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
+    if (k <= 64) {
+        hipLaunchKernelGGL(k_topk_span<1>, grid, block, lds, st, tp);
+        hipLaunchKernelGGL(k_topk_merge<1>, mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out_ids, out_logits);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_topk_span<2>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
+                               "gv_topk_scores"))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_topk_span<2>, grid, block, lds, st, tp);
+        hipLaunchKernelGGL(k_topk_merge<2>, mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out_ids, out_logits);
+    }
+    return launch_status("gv_topk_scores");
+}
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,
                                 int out_feat, int transpose_w, const int32_t* tiles, int n_tiles, float* msg, void* stream) {
     GV_REQUIRE(num_rels > 0 && in_feat > 0 && out_feat > 0 && n_tiles >= 0, GV_ERR_SHAPE, "gv_rel_rows_gemm: bad sizes");

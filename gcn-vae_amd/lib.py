@@ -106,6 +106,8 @@ SIGNATURES = {
     'gv_rel_gradw_gemm': (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
     'gv_rank_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     'gv_rank_scores_filtered': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    'gv_topk_scores_workspace_bytes': (_L, [_I, _I, _I]),
+    'gv_topk_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -597,6 +597,61 @@ def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=N
     return both[0], both[1]
 
 
+TOPK_MAX = 128      # largest k gv_topk_scores takes
+
+
+def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The ``k`` best entities per query row under ``logit[i, j] = q[i] . entities[j] (+ bias)`` -- the logits ``rank_scores``
+    compares, bit for bit -- from one fused launch pair (gv_topk_scores) that never stores the score matrix.  With a filter
+    (``filt_lo``, ``filt_hi``, ``filt_ent`` as ``rank_scores_filtered`` takes them) the ids ``filt_ent[filt_lo[i]:filt_hi[i]]``
+    are no candidates of row i.  Order: logit descending, equal logits (-0 and +0 alike) by lower id, NaN after everything.
+    Returns ``(ids int64 (m, k), logits float32 (m, k))``; rows with fewer than k candidates are padded with id -1, logit -inf.
+    Logits are reported with -0 as +0 and every NaN as the one quiet NaN (``ranking.topk_from_scores`` does the same)."""
+    for name, t in (('q', q), ('entities', entities)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if q.shape[1] != entities.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    m, v, h = q.shape[0], entities.shape[0], q.shape[1]
+    if v < 1 or h < 1:
+        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    n_ent = 0
+    if all(given):
+        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+        if filt_lo.numel() != m or filt_hi.numel() != m:
+            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+        n_ent = filt_ent.numel()
+        if n_ent >= 2 ** 31:
+            raise ValueError('filt_ent: more than 2**31 - 1 entries')
+        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
+            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
+            raise ValueError(f'filtered entity ids must lie in [0, {v})')
+    q, ld_q = _row_major(q, 'q')
+    entities, ld_e = _row_major(entities, 'entities')
+    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids.long(), logits
+    lo32 = hi32 = ent32 = None
+    if all(given):
+        i32 = dict(device=q.device, dtype=torch.int32)
+        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    if bias is not None:
+        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_topk_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k,
+             ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
+    return ids.long(), logits
+
+
 def pick_split_k(m_out, n_out, k):
     """Reduction-heavy shapes (weight gradients: small output, K = nodes) need split-K to fill 256 CUs."""
     tiles = ((m_out + 63) // 64) * ((n_out + 63) // 64)

@@ -16,6 +16,10 @@ Filtered evaluation (the protocol of published FB15k-237 / WN18RR figures; the r
 kgvae/link_predict.py:7): a ``FilterIndex`` of the dataset's known triplets lists, per query, the OTHER true answers, and
 ``ops.rank_scores_filtered`` (gv_rank_scores_filtered) leaves them out of the count in the same launch that gives the raw
 rank.  ``calc_filtered_mrr`` reports both.
+
+Link prediction (what the reference's ``--generate`` demo did with an argmax, kgvae/utils.py:245-288): ``predict_topk`` returns
+the k best entities of each query, optionally filtered by a ``FilterIndex``, from ``ops.topk_scores`` (gv_topk_scores: the same
+logits, a selection epilogue instead of a count).  ``topk_from_scores`` states the order on a materialised score matrix.
 """
 import torch
 
@@ -165,6 +169,86 @@ def calc_filtered_mrr(embedding, w, test_triplets, filter_index, hits=[1, 3, 10]
                 for hit in hits:
                     print("Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
     return out
+
+
+def _listed_mask(filt_lo, filt_hi, filt_ent, m, v, device):
+    """Dense (m, v) bool: True where entity j is listed in row i's filter range."""
+    lo, hi, ent = (t.reshape(-1).to(device=device, dtype=torch.long) for t in (filt_lo, filt_hi, filt_ent))
+    lens = hi - lo
+    total = int(lens.sum()) if m else 0
+    mask = torch.zeros(m, v, dtype=torch.bool, device=device)
+    if total:
+        rows = torch.repeat_interleave(torch.arange(m, device=device), lens)
+        first = torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens)
+        idx = torch.repeat_interleave(lo, lens) + torch.arange(total, device=device) - first
+        mask[rows, ent[idx]] = True
+    return mask
+
+
+def topk_from_scores(score, k, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The top-k rule of ``ops.topk_scores`` on a materialised (m, v) logit matrix, in plain torch (any device): the ids listed
+    in ``filt_ent[filt_lo[i]:filt_hi[i]]`` are no candidates of row i; candidates go by logit descending, equal logits (-0 and
+    +0 alike) by lower id, NaN after every other value (-inf included) and by id among themselves.  Returns ``(ids int64 (m, k),
+    logits float32 (m, k))``, padded with id -1 / logit -inf past a row's last candidate; -0 is reported as +0 and every NaN
+    as the one quiet NaN."""
+    m, v = score.shape
+    k = int(k)
+    val = score.to(torch.float32) + 0.0                             # -0 -> +0
+    nan = torch.isnan(val)
+    val = torch.where(nan, torch.full_like(val, float('nan')), val)
+    tier = nan.to(torch.int8)                                       # 0 a number, 1 NaN, 2 no candidate
+    if filt_lo is not None:
+        tier = torch.where(_listed_mask(filt_lo, filt_hi, filt_ent, m, v, val.device), torch.full_like(tier, 2), tier)
+    by_logit = torch.argsort(torch.where(nan, torch.full_like(val, float('-inf')), val), dim=1, descending=True, stable=True)
+    order = by_logit.gather(1, torch.argsort(tier.gather(1, by_logit), dim=1, stable=True))[:, :k]
+    ids, logits = order.clone(), val.gather(1, order)
+    gone = tier.gather(1, order) == 2
+    ids[gone], logits[gone] = -1, float('-inf')
+    if order.shape[1] < k:
+        ids = torch.cat([ids, ids.new_full((m, k - order.shape[1]), -1)], 1)
+        logits = torch.cat([logits, logits.new_full((m, k - order.shape[1]), float('-inf'))], 1)
+    return ids, logits
+
+
+def _predict_topk(embedding, w, a, r, k, direction, filter_index, select):
+    if direction not in ('o', 's'):
+        raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
+    emb = embedding.detach().contiguous()
+    wd = w.detach()
+    ent = filter_index.entities(direction, emb.device) if filter_index is not None else None
+    ids, logits = [], []
+    for lo in range(0, a.shape[0], MAX_QUERY_ROWS):
+        hi = min(a.shape[0], lo + MAX_QUERY_ROWS)
+        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
+        f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction) if filter_index is not None else (None, None)
+        i, l = select(q, emb, f_lo, f_hi, ent)
+        ids.append(i)
+        logits.append(l)
+    if not ids:
+        return (torch.zeros(0, k, dtype=torch.int64, device=emb.device),
+                torch.zeros(0, k, dtype=torch.float32, device=emb.device))
+    return torch.cat(ids), torch.cat(logits)
+
+
+def predict_topk(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None):
+    """Link prediction: the ``k`` most likely entities of every query, ``direction`` 'o' for (a[i], r[i], ?) and 's' for
+    (?, r[i], a[i]), scored as ``perturb_and_get_rank`` scores them (q = e_a * w_r, logit = q . e_j + flow_log_prob).  With a
+    ``FilterIndex`` the query's known answers are left out (new facts only).  One fused launch pair per ``MAX_QUERY_ROWS``
+    queries (ops.topk_scores); returns ``(ids int64 (n, k), logits float32 (n, k))`` in the order of ``topk_from_scores``."""
+    def select(q, emb, f_lo, f_hi, ent):
+        return ops.topk_scores(q, emb, k, flow_log_prob, f_lo, f_hi, ent)
+    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select)
+
+
+def predict_topk_unfused(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None):
+    """``predict_topk`` from materialised logits (one GEMM + ``topk_from_scores`` per chunk): the in-repo cross-check and the
+    bench's baseline."""
+    def select(q, emb, f_lo, f_hi, ent):
+        score = ops.gemm(q, emb, trans_b=True, precision='f32')
+        if flow_log_prob is not None:
+            score = score + flow_log_prob
+        return topk_from_scores(score, k, f_lo, f_hi, ent)
+    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select)
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

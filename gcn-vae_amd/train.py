@@ -124,6 +124,24 @@ def _sync():
     torch.cuda.synchronize()
 
 
+def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=None):
+    """Top-k link predictions for both directions of every triplet, the known answers (``filter_index``) left out, as TSV:
+    ``direction  query_entity  relation  position  predicted_entity  logit`` -- 'o' lines answer (s, r, ?), 's' lines (?, r, o);
+    a query with fewer than k candidates ends in id -1, logit -inf.  Returns the number of lines written."""
+    n = 0
+    with torch.no_grad(), open(path, 'w') as f:
+        for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
+            r = triplets[:, 1]
+            ids, logits = ranking.predict_topk(embed, w, a, r, k, direction=d, filter_index=filter_index,
+                                               flow_log_prob=flow_log_prob)
+            a, r, ids, logits = a.tolist(), r.tolist(), ids.tolist(), logits.tolist()
+            for i in range(len(a)):
+                head = f"{d}\t{a[i]}\t{r[i]}\t"
+                f.writelines(f"{head}{p}\t{e}\t{x:.9g}\n" for p, (e, x) in enumerate(zip(ids[i], logits[i])))
+                n += len(ids[i])
+    return n
+
+
 def main(args):
     data = load_data(args.dataset)
     num_nodes, num_rels = data.num_nodes, data.num_rels
@@ -168,6 +186,13 @@ def main(args):
         print("Using best epoch: {}".format(checkpoint['epoch']))
         with torch.no_grad():
             embed = model(test_graph, test_node_id, test_rel, test_norm)
+        if getattr(args, 'predict_topk', 0) > 0:
+            known = filters if filters is not None else \
+                ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            n_lines = write_predictions(args.predict_out, embed, model.w_relation, test_t, args.predict_topk, known,
+                                        model.encoder.get_flow_log_prob())
+            print(f"wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to "
+                  f"{args.predict_out}")
         if filters is not None:
             return ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
                                              eval_bz=args.eval_batch_size, all_batches=True,
@@ -312,6 +337,11 @@ def build_parser():
     p.add_argument("--filtered-eval", action="store_true",
                    help="also report filtered MRR and Hits@1/3/10 (the other known answers of a query -- train + valid + "
                         "test -- left out of its rank); model selection stays on the raw MRR; not a reference flag")
+    p.add_argument("--predict-topk", type=int, default=0,
+                   help="with --test-mode: write the K most likely new entities of both directions of every test triplet "
+                        "(train + valid + test triplets filtered out) to --predict-out; 0 = off; not a reference flag")
+    p.add_argument("--predict-out", type=str, default="predictions.tsv",
+                   help="TSV of --predict-topk: direction, query entity, relation, position, predicted entity, logit")
     return p
 
 

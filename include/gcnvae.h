@@ -531,6 +531,21 @@ int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, 
                             const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
                             int* count_raw, int* count_filt, int m, int v, int h, void* stream);
 
+/* Top-k link prediction: for query i the k best entities under
+ *   logit[i, j] = q_i . e_j (+ *bias)        -- the scores gv_rank_scores compares, bit for bit (gv_gemm_f32 + bias)
+ * without storing the score matrix.  Candidates of row i: every j in [0, v), less filt_ent[filt_lo[i] .. filt_hi[i]) when a
+ * filter is given (the (lo, hi, ent) form of gv_rank_scores_filtered: ids sorted ascending and unique within a range; ranges may
+ * be empty or shared, and each is clamped into [0, n_filt_ent) on the device).  filt_lo / filt_hi / filt_ent all NULL: no filter.
+ * Order, a strict total one: logit descending; equal logits (-0 and +0 included) by lower id first; NaN logits after every other
+ * value (-inf included), among themselves by id.  out_ids int32 [m, k] / out_logits fp32 [m, k] row-major hold the first k
+ * candidates; a row with fewer than k candidates is padded with id -1, logit -inf.  Reported logits carry -0 as +0 and every
+ * NaN as the quiet NaN 0x7fc00000.  1 <= k <= 128; any m >= 0 (0: nothing launched), v >= 1, h >= 1.  workspace: at least
+ * gv_topk_scores_workspace_bytes(m, v, k) bytes, 8-byte aligned.  The result does not depend on the launch geometry. */
+int64_t gv_topk_scores_workspace_bytes(int m, int v, int k);
+int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo, const int* filt_hi,
+                   const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits, void* workspace, int m, int v,
+                   int h, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.

@@ -4,7 +4,9 @@
 materialised form (one GEMM per 100-query batch + torch sigmoid / gather / compare / sum -- what ranking.py did before).
     python tools/eval_bench.py [--cpu-rows 200]     # --cpu-rows: also time the reference's (h, Eb, V) formulation on the host
     python tools/eval_bench.py --filtered           # filtered ranks: raw only, raw + filtered in one launch pair, materialised torch
---filtered takes the test split and the filter (train + valid + test) of the FB15k-237-synthetic dataset (Zipf-skewed lists)."""
+    python tools/eval_bench.py --topk 10            # top-k link prediction: fused (filtered / unfiltered), materialised, raw ranker
+--filtered and --topk take the test split and the filter (train + valid + test) of the FB15k-237-synthetic dataset (Zipf-skewed
+lists)."""
 import argparse
 import os
 import sys
@@ -20,9 +22,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--cpu-rows', type=int, default=0)
     ap.add_argument('--filtered', action='store_true')
+    ap.add_argument('--topk', type=int, default=0)
     args = ap.parse_args()
     if args.filtered:
         return filtered_leg()
+    if args.topk:
+        return topk_leg(args.topk)
     gen = torch.Generator().manual_seed(0)
     v, h, n, n_rel = 14541, 200, 20466, 237
     emb = (torch.randn(v, h, generator=gen) * 0.3).cuda()
@@ -134,6 +139,53 @@ def filtered_leg(chunk=4096, reps=5):
           f'{(1.0 / (filt + 1)).mean().item():.6f}')
     print(f'materialised : {t_mat * 1e3:8.2f} ms (filtered only: GEMM + dense filter mask + torch compare / sum, '
           f'{chunk}-query chunks)')
+
+
+def topk_leg(k, reps=5):
+    """Top-k link prediction for both directions of the test split: fused with the filter, fused without, the materialised
+    path (ranking.predict_topk_unfused: GEMM + dense mask + two stable sorts) and, for scale, the raw-only fused ranker."""
+    from gcn_vae_amd import data
+    kg = data.load_data('FB15k-237-synthetic')
+    dev = torch.device('cuda')
+    fi = ranking.FilterIndex(kg.num_nodes, kg.num_rels, kg.train, kg.valid, kg.test, device=dev)
+    gen = torch.Generator().manual_seed(0)
+    v, h = kg.num_nodes, 200
+    emb = (torch.randn(v, h, generator=gen) * 0.3).to(dev)
+    w = torch.randn(kg.num_rels, h, generator=gen).to(dev)
+    trip = torch.from_numpy(kg.test).to(dev)
+    s, r, o = trip[:, 0], trip[:, 1], trip[:, 2]
+    n = trip.shape[0]
+    dirs = ((s, o, 'o'), (o, s, 's'))
+
+    def timed(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps, out
+
+    def fused(filt):
+        return [ranking.predict_topk(emb, w, a, r, k, d, fi if filt else None) for a, _, d in dirs]
+
+    def unfused(filt):
+        return [ranking.predict_topk_unfused(emb, w, a, r, k, d, fi if filt else None) for a, _, d in dirs]
+
+    t_ff, ff = timed(lambda: fused(True), reps)
+    t_fu, fu = timed(lambda: fused(False), reps)
+    t_uf, uf = timed(lambda: unfused(True), 2)
+    t_raw, _ = timed(lambda: [ranking.perturb_and_get_rank(emb, w, a, r, b, n) for a, b, _ in dirs], reps)
+    same_f = all(torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) for x, y in zip(ff, uf))
+    same_u = all(torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]) for x, y in zip(fu, unfused(False)))
+    flop = 2.0 * (2 * n) * v * h            # one MFMA pass over every (query, entity) pair
+    print(f'top-{k}: {2 * n} queries x {v} entities, h = {h}; fused == unfused: filtered {same_f}, unfiltered {same_u}')
+    print(f'fused, filtered     : {t_ff * 1e3:8.2f} ms  ({flop / t_ff / 1e12:.1f} TFLOP/s of the score pass)')
+    print(f'fused, unfiltered   : {t_fu * 1e3:8.2f} ms  ({flop / t_fu / 1e12:.1f} TFLOP/s)')
+    print(f'unfused, filtered   : {t_uf * 1e3:8.2f} ms  (GEMM + dense mask + two stable sorts; {t_uf / t_ff:.1f}x fused)')
+    print(f'raw ranker (fused)  : {t_raw * 1e3:8.2f} ms  (two MFMA passes; fused filtered top-{k} is {t_ff / t_raw:.2f}x this)')
+    if not (same_f and same_u):
+        raise SystemExit('fused top-k differs from the unfused path')
 
 
 if __name__ == '__main__':
