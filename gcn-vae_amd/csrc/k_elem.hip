@@ -426,9 +426,9 @@ using namespace gv;
 
 extern "C" int gv_rgcn_epilogue_fwd(const float* agg, const float* addend, int act, const uint8_t* keep,
                                     float keep_scale, float* out, int64_t n_rows, int n_cols, void* stream) {
-    GV_REQUIRE(agg && out, GV_ERR_NULL, "gv_rgcn_epilogue_fwd: NULL pointer");
     const int64_t n = n_rows * n_cols;
     if (n <= 0) return GV_OK;
+    GV_REQUIRE(agg && out, GV_ERR_NULL, "gv_rgcn_epilogue_fwd: NULL pointer");
     hipLaunchKernelGGL(k_epilogue_fwd, dim3(grid_for(n, 1024)), dim3(256), 0, GV_ST, agg, addend, act, keep,
                        keep_scale, out, n);
     return launch_status("gv_rgcn_epilogue_fwd");
@@ -437,9 +437,13 @@ extern "C" int gv_rgcn_epilogue_fwd(const float* agg, const float* addend, int a
 extern "C" int gv_rgcn_epilogue_bwd(const float* out, const float* grad_out, int act, const uint8_t* keep,
                                     float keep_scale, float* g, int64_t n_rows, int n_cols, float* colsum_part,
                                     void* stream) {
-    GV_REQUIRE(grad_out && g && (act == GV_ACT_NONE || out), GV_ERR_NULL, "gv_rgcn_epilogue_bwd: NULL pointer");
     const int64_t n = n_rows * n_cols;
-    if (n <= 0) return GV_OK;
+    if (n <= 0) {       // no rows: the column-sum partials are zeros (gv_colsum_finish reads all of them)
+        if (!colsum_part || n_cols <= 0) return GV_OK;
+        (void)hipMemsetAsync(colsum_part, 0, (size_t)EPI_SLICES * n_cols * sizeof(float), GV_ST);
+        return launch_status("gv_rgcn_epilogue_bwd(colsum, no rows)");
+    }
+    GV_REQUIRE(grad_out && g && (act == GV_ACT_NONE || out), GV_ERR_NULL, "gv_rgcn_epilogue_bwd: NULL pointer");
     if (colsum_part) {      // also write GV_EPILOGUE_COLSUM_SLICES row-slice partials of the column sums
         GV_REQUIRE(n_cols % 4 == 0 && n_cols <= 1024 && aligned16(grad_out) && aligned16(g) && (!out || aligned16(out)) &&
                        aligned16(colsum_part) && (!keep || (reinterpret_cast<uintptr_t>(keep) & 3u) == 0),

@@ -280,6 +280,14 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
         const float bv = (p.bias && p.split_k == 1) ? p.bias[col] : 0.f;
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
+            if (p.tmask && MT * NT > 1) {
+                // a block of several 64 x 64 tiles ran because one of them is wanted: the unwanted ones still hold zeros
+                const int ti = (m0 + wm + 32 * t) >> 6, tj = (n0 + wn + 32 * u) >> 6;
+                const int bit = ti * p.tmask_ld + tj;
+                if (ti * 64 < p.m && !((p.tmask[bit >> 6] >> (bit & 63)) & 1ull))
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[t][u][i] = 0.f;
+            }
             // accumulate: the 16 previous values of this tile column are requested TOGETHER (load, add, store per element in
             // source order makes the compiler wait for every load before the next: 16 round trips per tile)
             float old[16];
@@ -1032,7 +1040,7 @@ static int gemm_any(bool bf16, int trans_a, int trans_b, int m, int n, int k, co
                     const uint64_t* kmask = nullptr, const uint64_t* tmask = nullptr, int tiles_wanted = 0) {
     GV_REQUIRE(m >= 0 && n >= 0 && k >= 0, GV_ERR_SHAPE, "gv_gemm_f32: negative size");
     if (m == 0 || n == 0) return GV_OK;
-    GV_REQUIRE(a && b && c, GV_ERR_NULL, "gv_gemm_f32: NULL matrix");
+    GV_REQUIRE(c && (k == 0 || (a && b)), GV_ERR_NULL, "gv_gemm_f32: NULL matrix");      // k == 0: act(bias) (+ C), A and B unread
     GV_REQUIRE(lda >= (trans_a ? m : k) && ldb >= (trans_b ? k : n) && ldc >= n, GV_ERR_SHAPE,
                "gv_gemm_f32: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
     GV_REQUIRE(act == GV_ACT_NONE || act == GV_ACT_RELU, GV_ERR_SHAPE, "gv_gemm_f32: unknown act %d", act);
@@ -1307,7 +1315,7 @@ extern "C" int gv_colsum_finish(const float* part, int n, int n_slices, float* o
 
 extern "C" int gv_colsum(const float* x, const float* relu_mask, int64_t m, int n, int ld, float* out, float* workspace,
                          int accumulate, void* stream) {
-    GV_REQUIRE(x && out && workspace, GV_ERR_NULL, "gv_colsum: NULL pointer");
+    GV_REQUIRE((x || m == 0) && out && workspace, GV_ERR_NULL, "gv_colsum: NULL pointer");      // m == 0: sums of zero rows
     GV_REQUIRE(m >= 0 && n > 0 && ld >= n, GV_ERR_SHAPE, "gv_colsum: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int nsl = COLSUM_SLICES;     // workspace is sized for 64 slices

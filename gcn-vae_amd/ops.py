@@ -462,8 +462,20 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, out=None, 
     if out is None:
         out = torch.empty(m, n, dtype=torch.float32, device=a.device)
         accumulate = False
+    else:       # written through (pointer, out.stride(0)) only: a wrong shape, type or layout would be written out of bounds
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 2:
+            raise TypeError(f'out: expected a 2-D float32 tensor, got {getattr(out, "dtype", type(out).__name__)} '
+                            f'{tuple(getattr(out, "shape", ()))}')
+        if out.device != a.device or b.device != a.device:
+            raise ValueError(f'out / b must be on the device of a ({a.device}), got {out.device} / {b.device}')
+        if tuple(out.shape) != (m, n):
+            raise ValueError(f'out: expected shape {(m, n)}, got {tuple(out.shape)}')
+        if m * n and ((n > 1 and out.stride(1) != 1) or (m > 1 and out.stride(0) < n)):
+            raise ValueError(f'out: needs unit inner stride and a leading dimension >= {n}, got strides {out.stride()}')
     if bias is not None:
         _chk(bias, name='bias')
+        if bias.numel() != n or bias.device != a.device:
+            raise ValueError(f'bias: expected {n} values on {a.device}, got {bias.numel()} on {bias.device}')
     ws, ws_bytes = None, 0
     if split_k > 1:
         ws_bytes = int(lib.load().gv_gemm_workspace_bytes(m, n, k, split_k))
