@@ -67,6 +67,9 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
         self.rng_stream = ops.new_rng_stream()
         self._keep_next = None           # a mask the enclosing encoder drew for this call (one fused RNG launch)
         self.reduce_hook = None          # multi-GPU: sums the partial aggregate over the edge shards
+        # integer-id features with num_bases < num_rels: build each edge's row from the basis planes instead of the full
+        # (R, in_feat, out_feat) weight (ops.rel_graph_conv_basis_select); off = the materialised path
+        self.fused_basis_select = False
 
     def _keep_mask(self, n, device):
         p = self.dropout.p
@@ -130,6 +133,16 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
             # self-loop term a row of loop_weight (matmul_maybe_select)
             if self.reduce_hook is not None:
                 raise NotImplementedError('integer-id features are not wired into the multi-GPU edge sharding')
+            if not (self.fused_basis_select and self.num_bases < self.num_rels):
+                ops.check_select_weight_size(self.num_rels, self.in_feat, self.out_feat)     # before W is formed
+            if self.fused_basis_select and self.num_bases < self.num_rels:
+                h = ops.rel_graph_conv_basis_select(x, self.weight, self.w_comp, h_bias, loop_w, norm, gidx, ridx, act_id, keep,
+                                                    scale if keep is not None else 1.0)
+                if post_act is not None:
+                    h = post_act(h)
+                    if late_keep is not None:
+                        h = h * (late_keep.to(h.dtype) * scale)
+                return h
             flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)
             weight = ops.matmul(self.w_comp, flat) if self.num_bases < self.num_rels else flat
             h = ops.rel_graph_conv_select(x, weight.view(self.num_rels, self.in_feat, self.out_feat), h_bias, loop_w, norm,

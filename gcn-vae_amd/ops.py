@@ -1381,9 +1381,19 @@ def select_plan(gidx, ridx, ids, in_feat):
     return hit
 
 
+def check_select_weight_size(num_rels, in_feat, out_feat):
+    """The materialised integer-id path (W of num_rels x in_feat x out_feat elements, its gradient the same) is held to
+    2^31 elements: past that it was measured to train a different model (NOTES.md, entity classification at the AM size).
+    A basis layer with num_bases < num_rels takes the fused path instead (RelGraphConv.fused_basis_select)."""
+    if int(num_rels) * int(in_feat) * int(out_feat) >= 2 ** 31:
+        raise ValueError(f'the materialised basis weight would have {num_rels} x {in_feat} x {out_feat} >= 2^31 elements; '
+                         'use the fused basis select layer (RelGraphConv.fused_basis_select, num_bases < num_rels)')
+
+
 def rel_graph_conv_select(ids, w3, h_bias, loop_weight, norm, gidx, ridx, act=ACT_NONE, keep=None, keep_scale=1.0):
     """RelGraphConv('basis') with integer-id features: w3 is (R, in, out), ids int64 (N,)."""
     r, fin, fout = w3.shape
+    check_select_weight_size(r, fin, fout)
     plan = select_plan(gidx, ridx, ids, fin)
     loop_rows = embedding(loop_weight, ids.reshape(-1)) if loop_weight is not None else None
     return _RelGraphConvSelect.apply(w3.reshape(r * fin, fout), loop_rows, h_bias, norm, gidx, plan, act, keep, float(keep_scale))
@@ -1391,6 +1401,292 @@ def rel_graph_conv_select(ids, w3, h_bias, loop_weight, norm, gidx, ridx, act=AC
 
 def rel_graph_conv_dense(x, w3, h_bias, loop_weight, norm, gidx, ridx, act=ACT_NONE, keep=None, keep_scale=1.0):
     return _RelGraphConvDense.apply(x, w3, h_bias, loop_weight, norm, gidx, ridx, act, keep, float(keep_scale))
+
+
+# ------------------------------------------------------------------------------------------------
+# entity classification (kgvae/entity_classify.py): the basis integer-id input layer without W, and the softmax / CE head
+class _RelGraphConvBasisSelect(torch.autograd.Function):
+    """RelGraphConv('basis', num_bases < num_rels) on INTEGER-ID node features without forming W = w_comp @ V, which is
+    (R, rows, out) -- 17.7 GB at the AM dataset's size.  An edge's message is row id[src] of W_etype; the edges that share an
+    (id, relation) pair -- a run -- share that row, so gv_ec_basis_rows_fwd makes it once per run from the nb basis planes and the
+    1x1-block K1 aggregation sums the runs' rows into the destinations (x norm, + loop row + bias, activation, dropout), as
+    _RelGraphConvSelect does over the rows of a materialised W.  Backward: S = the same aggregation over the run <- destination
+    incidence, then gv_ec_basis_rows_bwd gives dV (only the ids that occur), and dcomp by relation in a fixed order; the
+    self-loop rows loop_weight[id] come back through the same aggregation over the id <- node incidence (not the embedding's
+    scatter-add: repeated ids would add in arrival order).  Every gradient has the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, v, comp, loop_weight, h_bias, norm, gidx, plan, act, keep, keep_scale):
+        v, comp = _chk(v, name='basis weight'), _chk(comp, name='w_comp')
+        nb, rows, fout = v.shape
+        r = comp.shape[0]
+        if comp.shape[1] != nb or r != plan['num_rels']:
+            raise ValueError(f'w_comp is {tuple(comp.shape)}, expected ({plan["num_rels"]}, {nb})')
+        n = gidx.num_nodes
+        coef = None if norm is None else norm.reshape(-1)
+        n_runs = plan['n_runs']
+        msg = torch.empty(max(n_runs, 1), fout, dtype=torch.float32, device=v.device)
+        lib.call('gv_ec_basis_rows_fwd', ptr(v), ptr(comp), ptr(plan['run_id']), ptr(plan['run_rel']), n_runs, fout, nb, r, rows,
+                 ptr(msg), lib.stream(), tag='ec_basis_fwd')
+        addend = None
+        if loop_weight is not None:
+            loop_weight = _chk(loop_weight, name='loop_weight')
+            if tuple(loop_weight.shape) != (rows, fout):
+                raise ValueError(f'loop_weight is {tuple(loop_weight.shape)}, expected ({rows}, {fout})')
+            loop_rows = torch.empty(n, fout, dtype=torch.float32, device=v.device)
+            lib.call('gv_gather_rows', ptr(loop_weight), ptr(plan['ids']), ptr(loop_rows), n, fout, lib.stream())
+            addend = loop_rows
+            if h_bias is not None:
+                addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
+                lib.call('gv_axpby', addend.numel(), None, 1.0, ptr(loop_rows), 1.0, ptr(addend), lib.stream())
+        elif h_bias is not None:
+            addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
+        ones = torch.ones(1, fout, dtype=torch.float32, device=v.device)
+        out = bdd_aggregate(gidx.by_dst.seg, plan['run_by_dst'], plan['zeros'], coef, gidx.by_dst.perm, msg, ones, fout, 1, 1,
+                            False, addend, act, keep, keep_scale)
+        ctx.save_for_backward(v, comp, coef, out if act == ACT_RELU else None, keep)
+        ctx.meta = (plan, act, keep_scale, h_bias is not None, loop_weight is not None)
+        ctx.direct = (_direct(v), _direct(comp), _direct(h_bias), _direct(loop_weight))
+        _stamp_direct(ctx)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        v, comp, coef, out, keep = ctx.saved_tensors
+        plan, act, keep_scale, has_bias, has_loop = ctx.meta
+        _verify_direct(ctx)
+        d_v, d_c, d_b, d_l = ctx.direct
+        nb, rows, fout = v.shape
+        r = comp.shape[0]
+        grad_bias = grad_v = grad_c = None
+        if has_bias and ctx.needs_input_grad[3]:
+            grad_bias = d_b if d_b is not None else torch.empty(fout, dtype=torch.float32, device=v.device)
+            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
+            if d_b is not None:
+                grad_bias = None
+        else:
+            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
+        want_v, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (want_v or want_c) and plan['n_runs'] > 0:
+            gi = plan['by_run']                      # destinations = runs, sources = node rows of g
+            ones = torch.ones(1, fout, dtype=torch.float32, device=g.device)
+            s = bdd_aggregate(gi.by_dst.seg, gi.nbr_by_dst, plan['zeros'], _coef_by_run(plan, coef), None, g, ones, fout, 1, 1)
+        else:
+            s = None
+        dv = dc = None
+        if want_v:
+            dv = d_v if d_v is not None else torch.zeros_like(v)
+        if want_c:
+            dc = d_c if d_c is not None else torch.zeros_like(comp)
+        if s is not None:
+            # a direct target is accumulated into (the arena is zeroed per step); a fresh zeros tensor is as well -- the kernel
+            # writes only the rows of ids that occur, so one accumulate flag serves both
+            q = torch.empty(plan['n_runs'] * nb if want_c else 0, dtype=torch.float32, device=g.device)
+            lib.call('gv_ec_basis_rows_bwd', ptr(v), ptr(comp), ptr(s), ptr(plan['run_id']), ptr(plan['run_rel']),
+                     ptr(plan['run_ptr']), plan['n_groups'], ptr(plan['q_pos']), ptr(plan['rel_ptr']), plan['n_runs'], fout, nb, r,
+                     rows, ptr(dv), ptr(q), ptr(dc), 1, lib.stream(), tag='ec_basis_bwd')
+        if want_v:
+            grad_v = None if d_v is not None else dv
+        if want_c:
+            grad_c = None if d_c is not None else dc
+        grad_loop = None
+        if has_loop and ctx.needs_input_grad[2]:
+            gi = plan['by_id']                       # destinations = loop_weight rows, sources = node rows of g
+            ones = torch.ones(1, fout, dtype=torch.float32, device=g.device)
+            grad_loop = bdd_aggregate(gi.by_dst.seg, gi.nbr_by_dst, plan['zeros_n'], None, None, g, ones, fout, 1, 1)
+            if d_l is not None:
+                lib.call('gv_axpby', grad_loop.numel(), None, 1.0, ptr(grad_loop), 1.0, ptr(d_l), lib.stream())
+                grad_loop = None
+        return grad_v, grad_c, grad_loop, grad_bias, None, None, None, None, None, None
+
+
+def _coef_by_run(plan, coef):
+    """The edge norms in the run <- destination graph's order; cached on the tensor's identity and version (the norm of a graph
+    is the same every epoch)."""
+    if coef is None:
+        return None
+    key = (coef.data_ptr(), coef._version, coef.numel())
+    hit = plan.get('coef_by_run')
+    if hit is None or hit[0] != key:          # the entry holds the tensor: its address cannot be recycled while cached
+        hit = plan['coef_by_run'] = (key, coef[plan['edge_of_by_run']].contiguous(), coef)
+    return hit[1]
+
+
+def basis_select_plan(gidx, ridx, ids, in_feat):
+    """Index of the fused basis row-select layer, once per (graph, relation types, ids): the distinct (id, relation) pairs of
+    the edges (runs, sorted by id then relation), each edge's run in by-destination order, the run <- destination graph of the
+    backward, the runs' id groups and their relation order.  No num_rels * in_feat < 2^31 limit: nothing is indexed by W row."""
+    cache = ridx.__dict__.setdefault('_basis_select', {})
+    key = (ids.data_ptr(), ids._version, ids.numel(), int(in_feat))
+    hit = cache.get(key)
+    if hit is None:
+        ids = ids.reshape(-1)
+        if ids.numel() != gidx.num_src_nodes:
+            raise ValueError(f'{ids.numel()} node ids for a graph of {gidx.num_src_nodes} nodes')
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= in_feat):
+            raise ValueError(f'integer node features must lie in [0, in_feat = {in_feat})')
+        if gidx.num_edges >= 2 ** 31:
+            raise ValueError('the fused basis select layer indexes edges with int32')
+        num_rels = int(ridx.num_rels)
+        dev = gidx.device
+        et = ridx.keepalive.reshape(-1).to(torch.int64)
+        pair = ids[gidx.src32.long()] * num_rels + et                    # caller's edge order
+        uniq, run_of = torch.unique(pair, sorted=True, return_inverse=True)
+        n_runs = int(uniq.numel())
+        run_id = torch.div(uniq, num_rels, rounding_mode='floor')
+        run_rel = (uniq - run_id * num_rels).to(torch.int32).contiguous()
+        starts = torch.ones(n_runs, dtype=torch.bool, device=dev)
+        if n_runs > 1:
+            starts[1:] = run_id[1:] != run_id[:-1]
+        run_ptr = torch.cat([torch.nonzero(starts).reshape(-1), torch.tensor([n_runs], device=dev)]).to(torch.int64).contiguous()
+        order_rel = torch.sort(run_rel, stable=True)[1]
+        q_pos = torch.empty(n_runs, dtype=torch.int64, device=dev)
+        q_pos[order_rel] = torch.arange(n_runs, device=dev)
+        rel_ptr = torch.zeros(num_rels + 1, dtype=torch.int64, device=dev)
+        rel_ptr[1:] = torch.cumsum(torch.bincount(run_rel.long(), minlength=num_rels), 0)
+        perm_d = gidx.by_dst.perm
+        run_by_dst = (run_of if perm_d is None else run_of[perm_d.long()]).to(torch.int32).contiguous()
+        by_run = GraphIndex(gidx.dst32.long(), run_of, max(n_runs, 1), num_src_nodes=gidx.num_nodes)
+        edge_of = torch.arange(gidx.num_edges, device=dev) if by_run.by_dst.perm is None else by_run.by_dst.perm.long()
+        nodes = torch.arange(ids.numel(), device=dev)
+        by_id = GraphIndex(nodes, ids, int(in_feat), num_src_nodes=ids.numel())      # loop_weight row <- node
+        hit = cache[key] = dict(num_rels=num_rels, n_runs=n_runs, n_groups=int(run_ptr.numel()) - 1,
+                                run_id=run_id.to(torch.int32).contiguous(), run_rel=run_rel, run_ptr=run_ptr, q_pos=q_pos,
+                                rel_ptr=rel_ptr, run_by_dst=run_by_dst, by_run=by_run, edge_of_by_run=edge_of,
+                                zeros=torch.zeros(max(gidx.num_edges, 1), dtype=torch.int32, device=dev), by_id=by_id,
+                                zeros_n=torch.zeros(max(ids.numel(), 1), dtype=torch.int32, device=dev),
+                                ids=ids.contiguous(), keep=ids)
+    return hit
+
+
+def rel_graph_conv_basis_select(ids, v, comp, h_bias, loop_weight, norm, gidx, ridx, act=ACT_NONE, keep=None, keep_scale=1.0):
+    """RelGraphConv('basis', nb < R) with integer-id features, W never formed: v is (nb, in, out), comp (R, nb), ids int64 (N,)."""
+    nb, fin, fout = v.shape
+    plan = basis_select_plan(gidx, ridx, ids, fin)
+    return _RelGraphConvBasisSelect.apply(v, comp, loop_weight, h_bias, norm, gidx, plan, act, keep, float(keep_scale))
+
+
+EC_HEAD_MAX_CLASSES = 64    # = GV_EC_HEAD_MAX_CLASSES (include/gcnvae.h)
+
+
+def _head_rows(h):
+    h = _chk(h, name='head rows')
+    if h.dim() != 2 or not 1 <= h.shape[1] <= EC_HEAD_MAX_CLASSES:
+        raise ValueError(f'head rows must be (N, C) with 1 <= C <= {EC_HEAD_MAX_CLASSES}, got {tuple(h.shape)}')
+    return h
+
+
+_head_plans = {}
+
+
+def head_plan(n, c, labels, sets, device=None):
+    """Row -> slot map of up to three DISJOINT index sets (train / validation / test) for gv_ec_head_*, validated once and cached
+    on the tensors' identity and version: int64 CUDA 1-D indices in [0, n), no index twice, labels int64 (n,) in [0, C) on the
+    indexed rows."""
+    if labels is None or not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise RuntimeError('labels: the gfx950 head needs a CUDA/ROCm int64 tensor')
+    if device is not None and labels.device != device:
+        raise RuntimeError(f'labels are on {labels.device}, the head rows on {device}')
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError(f'labels must be int64 of shape ({n},), got {labels.dtype} {tuple(labels.shape)}')
+    sets = list(sets) + [None] * (3 - len(sets))
+    if len(sets) != 3:
+        raise ValueError('at most three index sets (train, validation, test)')
+    key = (n, c, labels.data_ptr(), labels._version) + tuple(
+        (None if s is None else (s.data_ptr(), s._version, s.numel(), s.device)) for s in sets)
+    hit = _head_plans.get(key)
+    if hit is not None:
+        return hit
+    parts = []
+    for i, s in enumerate(sets):
+        if s is None:
+            s = torch.zeros(0, dtype=torch.int64, device=labels.device)
+        if not isinstance(s, torch.Tensor) or s.device != labels.device:
+            raise RuntimeError(f'index set {i}: must be a tensor on {labels.device}')
+        if s.dtype != torch.int64 or s.dim() != 1:
+            raise ValueError(f'index set {i}: expected 1-D int64, got {s.dtype} {tuple(s.shape)}')
+        if s.numel() and (int(s.min()) < 0 or int(s.max()) >= n):
+            raise ValueError(f'index set {i}: indices must lie in [0, {n})')
+        if s.numel() and (int(labels[s].min()) < 0 or int(labels[s].max()) >= c):
+            raise ValueError(f'index set {i}: labels must lie in [0, {c}) on the indexed rows')
+        parts.append(s)
+    cat = torch.cat(parts)
+    if torch.unique(cat).numel() != cat.numel():
+        raise ValueError('index sets must be free of duplicates and pairwise disjoint')
+    row_pos = torch.full((n,), -1, dtype=torch.int32, device=labels.device)
+    row_pos[cat] = torch.arange(cat.numel(), dtype=torch.int32, device=labels.device)
+    sizes = [p.numel() for p in parts]
+    off = torch.tensor([0, sizes[0], sizes[0] + sizes[1], sum(sizes)], dtype=torch.int64, device=labels.device)
+    if len(_head_plans) > 16:
+        _head_plans.clear()
+    hit = _head_plans[key] = dict(row_pos=row_pos, off=off, sizes=sizes, total=sum(sizes), keep=(labels, parts))
+    return hit
+
+
+class _ECHead(torch.autograd.Function):
+    """p = softmax(h) by rows and, over up to three index sets, the mean of F.cross_entropy(p, y) -- a second softmax, as the
+    reference trains (kgvae/entity_classify.py:104) -- and the number of rows whose argmax is the label: ONE row launch plus a
+    fixed-order finishing pass.  Backward: one row launch, each row's loss term through both softmaxes, plus grad_p."""
+
+    @staticmethod
+    def forward(ctx, h, labels, plan):
+        n, c = h.shape
+        p = torch.empty_like(h)
+        losses = torch.empty(3, dtype=torch.float32, device=h.device)
+        counts = torch.empty(3, dtype=torch.int32, device=h.device)
+        work = torch.empty(max(plan['total'], 1), dtype=torch.float32, device=h.device)
+        correct = torch.empty(max(plan['total'], 1), dtype=torch.int32, device=h.device)
+        lib.call('gv_ec_head_fwd', ptr(h), ptr(labels), ptr(plan['row_pos']), ptr(plan['off']), n, c, ptr(p), ptr(work),
+                 ptr(correct), ptr(losses), ptr(counts), lib.stream())
+        ctx.mark_non_differentiable(counts)
+        ctx.save_for_backward(p, labels)
+        ctx.plan = plan
+        return p, losses, counts
+
+    @staticmethod
+    def backward(ctx, gp, glosses, _gcounts):
+        p, labels = ctx.saved_tensors
+        plan = ctx.plan
+        n, c = p.shape
+        gp = None if gp is None else _chk(gp.contiguous(), name='grad p')
+        gl = None if glosses is None else _chk(glosses.contiguous(), name='grad losses')
+        dh = torch.empty_like(p)
+        lib.call('gv_ec_head_bwd', ptr(p), ptr(labels), ptr(plan['row_pos']), ptr(plan['off']), ptr(gl), ptr(gp), n, c, ptr(dh),
+                 lib.stream())
+        return dh, None, None
+
+
+class _SoftmaxRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h):
+        n, c = h.shape
+        p = torch.empty_like(h)
+        lib.call('gv_ec_head_fwd', ptr(h), None, None, None, n, c, ptr(p), None, None, None, None, lib.stream())
+        ctx.save_for_backward(p)
+        return p
+
+    @staticmethod
+    def backward(ctx, gp):
+        (p,) = ctx.saved_tensors
+        n, c = p.shape
+        dh = torch.empty_like(p)
+        lib.call('gv_ec_head_bwd', ptr(p), None, None, None, None, ptr(_chk(gp.contiguous(), name='grad p')), n, c, ptr(dh),
+                 lib.stream())
+        return dh
+
+
+def softmax_rows(h):
+    """softmax(h, dim=1) of (N, C <= 64) rows on the head kernel."""
+    return _SoftmaxRows.apply(_head_rows(h))
+
+
+def ec_head(h, labels, train_idx, val_idx=None, test_idx=None):
+    """The entity-classification head on the output layer's pre-softmax rows h (N, C <= 64):
+    returns (p, losses, counts) -- p = softmax(h) for every row; losses (3,) = F.cross_entropy(p[idx], labels[idx]) per set
+    (NaN for an empty set), differentiable; counts (3,) int32 = rows with argmax(p) == label.  Sets are int64 and disjoint."""
+    h = _head_rows(h)
+    plan = head_plan(h.shape[0], h.shape[1], labels, (train_idx, val_idx, test_idx), h.device)
+    return _ECHead.apply(h, labels, plan)
 
 
 class _RelGraphConvRows(torch.autograd.Function):

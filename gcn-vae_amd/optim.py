@@ -17,9 +17,19 @@ from .lib import ptr
 class FlatAdam:
     ALIGN = 64   # floats: keeps every parameter 256-B aligned for the 16-B vector paths of the kernels
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, total_multiple=1, moments=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, total_multiple=1, moments=True,
+                 weight_decay=0.0):
         """total_multiple: the arena length is rounded up to a multiple of it (a sharded optimiser cuts the arena into equal pieces);
-        moments=False: the caller keeps its own (smaller) moment arenas."""
+        moments=False: the caller keeps its own (smaller) moment arenas.
+        weight_decay: torch.optim.Adam's coupled L2 rule, g += weight_decay * p before the moments (one axpby over the arena;
+        at 0 nothing is launched).  The decay is added IN the gradient arena, so after step() each p.grad holds g + wd * p
+        (torch.optim.Adam leaves p.grad as it was) until the next zero_grad().  Not combined with max_grad_norm: clipping
+        would then see the decayed gradient."""
+        if weight_decay < 0.0:
+            raise ValueError(f'weight_decay must be >= 0, got {weight_decay}')
+        if weight_decay and max_grad_norm is not None:
+            raise ValueError('FlatAdam: weight_decay together with max_grad_norm is not supported')
+        self.weight_decay = float(weight_decay)
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError('FlatAdam: no trainable parameters')
@@ -114,6 +124,8 @@ class FlatAdam:
             self._clean = True
             return
         self.step_t += 1
+        if self.weight_decay:
+            lib.call('gv_axpby', self.total, None, self.weight_decay, ptr(self.flat_p), 1.0, ptr(self.flat_g), lib.stream())
         sumsq = None
         lib.call('gv_adam_step', ptr(self.flat_p), ptr(self.flat_g), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                  self.total, ptr(sumsq), float(self.max_grad_norm or 0.0), float(self.lr), float(self.betas[0]),

@@ -547,6 +547,39 @@ int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const flo
                    int h, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Entity classification (kgvae/entity_classify.py; csrc/k_ec.hip).  Deterministic: fixed summation orders, no float atomics.
+ *
+ * Basis-decomposed integer-id input layer without W = w_comp @ V.  A run k is one distinct (id, relation) pair of the edges,
+ * runs sorted by id then relation; run_ptr [n_groups + 1] (int64) cuts them into the groups of one id each.  V is (nb, rows, h)
+ * and comp (num_rels, nb), both fp32 row-major; offsets into V are 64-bit.
+ *   gv_ec_basis_rows_fwd : msg[k, :] = sum_b comp[run_rel[k], b] V[b, run_id[k], :]                 msg (n_runs, h)
+ *   gv_ec_basis_rows_bwd : given S (n_runs, h) -- the norm-weighted sum of the output gradient rows over each run's edges --
+ *     dv[b, id, :]   (+)= sum over the runs k of id  comp[run_rel[k], b] S[k, :]    (only the ids that occur are written)
+ *     q[q_pos[k], :]  = V[b, run_id[k], :] . S[k, :]  for every b                     (workspace, n_runs x nb)
+ *     dcomp[r, :]    (+)= sum of q rows rel_ptr[r] .. rel_ptr[r + 1]                  (q_pos puts the runs in relation order)
+ *   dv or dcomp may be NULL (that gradient is skipped); accumulate != 0 adds into them.
+ *
+ * Softmax / cross-entropy head (C <= GV_EC_HEAD_MAX_CLASSES columns):
+ *   gv_ec_head_fwd : p = softmax(h) by rows; for each row i with row_pos[i] >= 0 (int32 [n]; NULL: no sets)
+ *     term[row_pos[i]] = logsumexp(p_i) - p_i[labels[i]]   (F.cross_entropy on the probabilities, as the reference trains)
+ *     correct[row_pos[i]] = argmax(p_i) == labels[i]       (ties to the lowest column, as torch.argmax)
+ *   then one workgroup sums the three slices set_off[s] .. set_off[s + 1] (int64 [4]) in a fixed order:
+ *     loss[s] = mean term (NaN for an empty slice), count[s] = correct rows.
+ *   gv_ec_head_bwd : dh = p * (dp - <dp, p>) with dp = grad_p (NULL: 0) plus, for a row whose row_pos lies in slice s,
+ *     gloss[s] / |slice s| * (softmax(p_i) - onehot(labels[i])).  gloss: the 3 loss gradients (device); NULL: no loss term.
+ */
+#define GV_EC_HEAD_MAX_CLASSES 64
+int gv_ec_basis_rows_fwd(const float* v, const float* comp, const int32_t* run_id, const int32_t* run_rel, int64_t n_runs, int h,
+                         int nb, int num_rels, int64_t rows, float* msg, void* stream);
+int gv_ec_basis_rows_bwd(const float* v, const float* comp, const float* s, const int32_t* run_id, const int32_t* run_rel,
+                         const int64_t* run_ptr, int64_t n_groups, const int64_t* q_pos, const int64_t* rel_ptr, int64_t n_runs,
+                         int h, int nb, int num_rels, int64_t rows, float* dv, float* q, float* dcomp, int accumulate, void* stream);
+int gv_ec_head_fwd(const float* h, const int64_t* labels, const int32_t* row_pos, const int64_t* set_off, int64_t n, int c,
+                   float* p, float* term, int32_t* correct, float* loss, int32_t* count, void* stream);
+int gv_ec_head_bwd(const float* p, const int64_t* labels, const int32_t* row_pos, const int64_t* set_off, const float* gloss,
+                   const float* grad_p, int64_t n, int c, float* dh, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.
  * Replaces x@loop_weight (DGL RelGraphConv self loop), MaskedLinear (kgvae/flow_network.py:14-15)
