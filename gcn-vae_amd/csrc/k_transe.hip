@@ -1,0 +1,570 @@
+// TransE (Bordes et al. 2013; the OpenKE formulation of baselines/transe): negative sampling, the fused training step, the
+// ordered sparse SGD update and the filtered L1 / L2 ranker.  No float atomics anywhere: every sum has a fixed order, so a step
+// is bit-identical run to run and eager vs captured.  Row widths up to GV_TRANSE_MAX_DIM; a row is held by one wave, TE_C columns a lane.
+//
+// Sampler.  Positive b of a batch of B draws Philox(seed, tick) counter (b, stream, tick): word x picks the training triple
+// (multiply-shift onto [0, n_train)), word y the Bernoulli coin (head corrupted iff (y >> 8) * 2^-24 < p_head[r]).  Negative j of
+// positive b draws counter (b, stream + 0x10000 * (j + 1), tick), word x.  With a filter of k known answers out of V the word is
+// mapped onto [0, V - k) and then to the u-th entity NOT in the sorted known list (binary search on list[j] - j); k == V or no
+// filter: onto [0, V).  Layout (OpenKE): the B positives, then neg_ent blocks of B negatives.
+//
+// Step.  One wave per positive.  Every row is scored in OpenKE's 'normal' mode, ||(h + r) - t||_p, with h, r, t each passed through
+// F.normalize (x / max(||x||_2, 1e-12)) when norm_flag is set.  The positive's rows are gathered and normalised once; a negative
+// re-gathers only its corrupted side (the side whose id differs from the positive's; the tail when neither does).  Gradients of the
+// uncorrupted sides are accumulated in registers over the negatives in j order, then the positive; one gradient row is written per
+// occurrence: [h of b | t of b | corrupted side of (j, b)] for entities, [r of b] for relations.
+//
+// Ranker.  Distance of query q to entity j: ||q - n(E_j)||_p, summed over the columns in order with one accumulator
+// (p = 2: fmaf(d, d, acc), then sqrtf).  The fused ranker and gv_transe_distances share te_tile(), so their distances are the same bits.
+#include "common.h"
+
+namespace gv {
+
+#define GV_ST ((hipStream_t)stream)
+
+constexpr int TE_C = GV_TRANSE_MAX_DIM / WAVE;     // columns per lane
+constexpr float TE_EPS = 1e-12f;                    // F.normalize's eps
+
+__device__ __forceinline__ void te_load(const float* __restrict__ row, int dim, int lane, float (&x)[TE_C]) {
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) {
+        const int k = lane + c * WAVE;
+        x[c] = k < dim ? row[k] : 0.f;
+    }
+}
+
+// y = x / max(||x||_2, eps); returns ||x||_2 (the sum of squares in a fixed order)
+__device__ __forceinline__ float te_normalize(const float (&x)[TE_C], float (&y)[TE_C], bool on) {
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) ss = fmaf(x[c], x[c], ss);
+    const float n = sqrtf(wave_sum(ss));
+    const float den = fmaxf(n, TE_EPS);
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) y[c] = on ? x[c] / den : x[c];
+    return n;
+}
+
+// F.normalize backward: gx = (gy - y <y, gy>) / ||x|| where ||x|| >= eps, gy / eps below it
+__device__ __forceinline__ void te_normalize_bwd(const float (&y)[TE_C], float n, const float (&gy)[TE_C], float (&gx)[TE_C], bool on) {
+    if (!on) {
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = gy[c];
+        return;
+    }
+    if (n >= TE_EPS) {
+        float d = 0.f;
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) d = fmaf(y[c], gy[c], d);
+        d = wave_sum(d);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = (gy[c] - y[c] * d) / n;
+    } else {
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = gy[c] / TE_EPS;
+    }
+}
+
+// ||z||_p of z = (a + b) - c, and z itself
+__device__ __forceinline__ float te_dist(const float (&a)[TE_C], const float (&b)[TE_C], const float (&c)[TE_C], float (&z)[TE_C],
+                                         int p) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < TE_C; ++i) {
+        z[i] = (a[i] + b[i]) - c[i];
+        s = p == 1 ? s + fabsf(z[i]) : fmaf(z[i], z[i], s);
+    }
+    s = wave_sum(s);
+    return p == 1 ? s : sqrtf(s);
+}
+
+// dz = g * d||z||_p / dz: sign(z) for p = 1, z / ||z|| for p = 2; 0 at z = 0 (torch's norm backward)
+__device__ __forceinline__ void te_dist_bwd(const float (&z)[TE_C], float dist, float g, int p, float (&dz)[TE_C]) {
+#pragma unroll
+    for (int i = 0; i < TE_C; ++i) {
+        if (p == 1) dz[i] = z[i] > 0.f ? g : (z[i] < 0.f ? -g : 0.f);
+        else dz[i] = dist == 0.f ? 0.f : z[i] * (g / dist);
+    }
+}
+
+__device__ __forceinline__ void te_store(float* __restrict__ row, int dim, int lane, const float (&x)[TE_C]) {
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) {
+        const int k = lane + c * WAVE;
+        if (k < dim) row[k] = x[c];
+    }
+}
+
+// ---- sampler -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_transe_sample(const uint64_t* __restrict__ rng_state, uint32_t stream,
+                                                       const int32_t* __restrict__ train, int64_t n_train, int n_ent,
+                                                       const float* __restrict__ p_head, const int32_t* __restrict__ f_lo,
+                                                       const int32_t* __restrict__ f_hi, const int32_t* __restrict__ f_ent_o,
+                                                       const int32_t* __restrict__ f_ent_s, int B, int neg_ent,
+                                                       int32_t* __restrict__ bh, int32_t* __restrict__ br, int32_t* __restrict__ bt,
+                                                       uint32_t* __restrict__ draws) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const uint64_t seed = rng_state[0], tick = rng_state[1];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), t0 = (uint32_t)tick, t1 = (uint32_t)(tick >> 32);
+    const uint4 x = philox4x32_10(k0, k1, (uint32_t)b, stream, t0, t1);
+    const int64_t i = (int64_t)(((uint64_t)x.x * (uint64_t)n_train) >> 32);
+    const int h = train[3 * i], r = train[3 * i + 1], t = train[3 * i + 2];
+    const bool head = p_head ? (float)(x.y >> 8) * (1.f / 16777216.f) < p_head[r] : false;
+    bh[b] = h; br[b] = r; bt[b] = t;
+    if (draws) { draws[(int64_t)b * (neg_ent + 2)] = x.x; draws[(int64_t)b * (neg_ent + 2) + 1] = x.y; }
+    // the known answers of the corrupted side: heads of (?, r, t) when the head is replaced, tails of (h, r, ?) otherwise
+    int lo = 0, k = 0;
+    const int32_t* list = nullptr;
+    if (f_lo) {
+        const int64_t slot = 2 * i + (head ? 1 : 0);
+        lo = f_lo[slot];
+        k = f_hi[slot] - lo;
+        list = (head ? f_ent_s : f_ent_o) + lo;
+    }
+    const bool filt = list && k < n_ent;
+    const uint32_t range = filt ? (uint32_t)(n_ent - k) : (uint32_t)n_ent;
+    for (int j = 0; j < neg_ent; ++j) {
+        const uint32_t w = philox4x32_10(k0, k1, (uint32_t)b, stream + 0x10000u * (uint32_t)(j + 1), t0, t1).x;
+        if (draws) draws[(int64_t)b * (neg_ent + 2) + 2 + j] = w;
+        int u = (int)(((uint64_t)w * range) >> 32);
+        if (filt) {              // the u-th entity not in list[0, k): u + #{list[m] - m <= u}
+            int a = 0, z = k;
+            while (a < z) {
+                const int m = (a + z) >> 1;
+                if (list[m] - m <= u) a = m + 1;
+                else z = m;
+            }
+            u += a;
+        }
+        const int64_t o = (int64_t)B * (j + 1) + b;
+        bh[o] = head ? u : h;
+        br[o] = r;
+        bt[o] = head ? t : u;
+    }
+}
+
+// ---- fused step ----------------------------------------------------------------------------------
+struct TeStepArgs {
+    const float* ent;
+    const float* rel;
+    const int32_t* bh;
+    const int32_t* br;
+    const int32_t* bt;
+    int B, neg_ent, dim, p, norm;
+    float margin, adv_t, regul;
+    float* g_ent;       // (2B + neg_ent * B, dim)
+    float* g_rel;       // (B, dim)
+    float* loss_part;   // (B)
+    float* score;       // (B * (1 + neg_ent)) or NULL
+    int32_t* occ_ent;   // ((2 + neg_ent) B) entity id of each gradient row of g_ent, or NULL
+};
+
+__global__ __launch_bounds__(256) void k_transe_step(TeStepArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.B) return;
+    const int B = a.B, K = a.neg_ent, dim = a.dim, p = a.p;
+    const bool on = a.norm != 0, adv = a.adv_t > 0.f;
+    const int64_t N = (int64_t)B * (1 + K);
+    const int ph = a.bh[b], pr = a.br[b], pt = a.bt[b];
+    float xh[TE_C], xr[TE_C], xt[TE_C], yh[TE_C], yr[TE_C], yt[TE_C], z[TE_C];
+    te_load(a.ent + (int64_t)ph * dim, dim, lane, xh);
+    te_load(a.rel + (int64_t)pr * dim, dim, lane, xr);
+    te_load(a.ent + (int64_t)pt * dim, dim, lane, xt);
+    const float nh = te_normalize(xh, yh, on), nr = te_normalize(xr, yr, on), nt = te_normalize(xt, yt, on);
+    const float ps = te_dist(yh, yr, yt, z, p);
+    if (a.score && lane == 0) a.score[b] = ps;
+    if (a.occ_ent && lane == 0) { a.occ_ent[b] = ph; a.occ_ent[B + b] = pt; }
+    const float inv_bk = 1.f / (float)((int64_t)B * K);
+    // adversarial weights: softmax(-n * T) over the positive's negatives (first pass: the scores, their max and sum)
+    float wmax = -INFINITY, wsum = 0.f;
+    if (adv) {
+        for (int j = 0; j < K; ++j) {
+            const int64_t o = (int64_t)B * (j + 1) + b;
+            const int nhid = a.bh[o];
+            const bool head = nhid != ph;
+            float xc[TE_C], yc[TE_C];
+            te_load(a.ent + (int64_t)(head ? nhid : a.bt[o]) * dim, dim, lane, xc);
+            te_normalize(xc, yc, on);
+            const float ns = head ? te_dist(yc, yr, yt, z, p) : te_dist(yh, yr, yc, z, p);
+            const float v = -ns * a.adv_t;
+            const float m2 = fmaxf(wmax, v);
+            wsum = wsum * expf(wmax - m2) + expf(v - m2);
+            wmax = m2;
+        }
+    }
+    float gh[TE_C], gr[TE_C], gt[TE_C];
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) gh[c] = gr[c] = gt[c] = 0.f;
+    float gp = 0.f, loss = 0.f;
+    int n_head = 0;
+    for (int j = 0; j < K; ++j) {
+        const int64_t o = (int64_t)B * (j + 1) + b;
+        const int nhid = a.bh[o];
+        const bool head = nhid != ph;
+        const int cid = head ? nhid : a.bt[o];
+        n_head += head;
+        float xc[TE_C], yc[TE_C], dz[TE_C], gyc[TE_C], gxc[TE_C];
+        te_load(a.ent + (int64_t)cid * dim, dim, lane, xc);
+        const float nc = te_normalize(xc, yc, on);
+        const float ns = head ? te_dist(yc, yr, yt, z, p) : te_dist(yh, yr, yc, z, p);
+        if (a.score && lane == 0) a.score[o] = ns;
+        if (a.occ_ent && lane == 0) a.occ_ent[(int64_t)2 * B + (int64_t)j * B + b] = cid;
+        const float w = adv ? expf(-ns * a.adv_t - wmax) / wsum : inv_bk;
+        const float d = ps - ns, hinge = fmaxf(d, -a.margin);
+        loss += adv ? w * hinge : hinge;
+        // torch.max(x, -margin): the whole gradient to x above the margin, half of it at a tie
+        const float gd = (d > -a.margin ? 1.f : (d == -a.margin ? 0.5f : 0.f)) * (adv ? w / (float)B : inv_bk);
+        gp += gd;
+        te_dist_bwd(z, ns, -gd, p, dz);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) {
+            gr[c] += dz[c];
+            if (head) { gyc[c] = dz[c]; gt[c] -= dz[c]; }
+            else { gh[c] += dz[c]; gyc[c] = -dz[c]; }
+        }
+        te_normalize_bwd(yc, nc, gyc, gxc, on);
+        if (a.regul != 0.f) {
+            const float cr = a.regul * 2.f / (3.f * (float)N * (float)dim);
+#pragma unroll
+            for (int c = 0; c < TE_C; ++c) gxc[c] = fmaf(cr, xc[c], gxc[c]);
+        }
+        te_store(a.g_ent + ((int64_t)2 * B + (int64_t)j * B + b) * dim, dim, lane, gxc);
+    }
+    {   // the positive, last (z held the negatives' differences: the positive's is formed again, the same bits)
+        float zp[TE_C], dz[TE_C];
+        te_dist(yh, yr, yt, zp, p);
+        te_dist_bwd(zp, ps, gp, p, dz);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) { gh[c] += dz[c]; gr[c] += dz[c]; gt[c] -= dz[c]; }
+    }
+    float gx[TE_C];
+    const float cr = a.regul != 0.f ? a.regul * 2.f / (3.f * (float)N * (float)dim) : 0.f;
+    te_normalize_bwd(yh, nh, gh, gx, on);
+    if (cr != 0.f) {
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = fmaf(cr * (float)(1 + K - n_head), xh[c], gx[c]);
+    }
+    te_store(a.g_ent + (int64_t)b * dim, dim, lane, gx);
+    te_normalize_bwd(yt, nt, gt, gx, on);
+    if (cr != 0.f) {
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = fmaf(cr * (float)(1 + n_head), xt[c], gx[c]);
+    }
+    te_store(a.g_ent + ((int64_t)B + b) * dim, dim, lane, gx);
+    te_normalize_bwd(yr, nr, gr, gx, on);
+    if (cr != 0.f) {
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) gx[c] = fmaf(cr * (float)(1 + K), xr[c], gx[c]);
+    }
+    te_store(a.g_rel + (int64_t)b * dim, dim, lane, gx);
+    if (a.regul != 0.f) {   // this positive's share of regul_rate * (mean h^2 + mean t^2 + mean r^2) / 3 over the N rows
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c)
+            s += (float)(1 + K - n_head) * (xh[c] * xh[c]) + (float)(1 + n_head) * (xt[c] * xt[c]) + (float)(1 + K) * (xr[c] * xr[c]);
+        for (int j = 0; j < K; ++j) {
+            const int64_t o = (int64_t)B * (j + 1) + b;
+            const int nhid = a.bh[o];
+            float xc[TE_C];
+            te_load(a.ent + (int64_t)(nhid != ph ? nhid : a.bt[o]) * dim, dim, lane, xc);
+#pragma unroll
+            for (int c = 0; c < TE_C; ++c) s = fmaf(xc[c], xc[c], s);
+        }
+        loss = loss * (adv ? 1.f / (float)B : inv_bk) + a.regul * wave_sum(s) / (3.f * (float)N * (float)dim);
+    } else {
+        loss = loss * (adv ? 1.f / (float)B : inv_bk);
+    }
+    if (lane == 0) a.loss_part[b] = loss;
+}
+
+// ---- ordered reduction + SGD -----------------------------------------------------------------------
+// One wave per table row: the row's occurrences (perm[rowptr[s] .. rowptr[s+1])) summed in occurrence order, then p += -lr * g.
+// Rows without occurrences are not written.  The last block sums the loss partials (fixed order) into loss_out[0] and adds that
+// to the double epoch accumulator.
+__global__ __launch_bounds__(256) void k_transe_apply(float* __restrict__ ent, int n_ent, const float* __restrict__ g_ent,
+                                                      const int32_t* __restrict__ perm_e, const int32_t* __restrict__ rowptr_e,
+                                                      float* __restrict__ rel, int n_rel, const float* __restrict__ g_rel,
+                                                      const int32_t* __restrict__ perm_r, const int32_t* __restrict__ rowptr_r,
+                                                      int dim, float lr, const float* __restrict__ loss_part, int B, float margin,
+                                                      float* __restrict__ loss_out, double* __restrict__ epoch_acc, int row_blocks) {
+    const int lane = threadIdx.x & 63;
+    if ((int)blockIdx.x == row_blocks) {
+        if (threadIdx.x >= 64) return;
+        float s = 0.f;
+        for (int i = lane; i < B; i += 64) s += loss_part[i];
+        s = wave_sum(s) + margin;
+        if (lane == 0) {
+            loss_out[0] = s;
+            if (epoch_acc) epoch_acc[0] += (double)s;
+        }
+        return;
+    }
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    float* table;
+    const float* g;
+    const int32_t *perm, *rowptr;
+    int s;
+    if (w < n_ent) { table = ent; g = g_ent; perm = perm_e; rowptr = rowptr_e; s = w; }
+    else if (w < n_ent + n_rel) { table = rel; g = g_rel; perm = perm_r; rowptr = rowptr_r; s = w - n_ent; }
+    else return;
+    const int lo = rowptr[s], hi = rowptr[s + 1];
+    if (lo == hi) return;
+    for (int k = lane; k < dim; k += 64) {
+        float acc = 0.f;
+        for (int i = lo; i < hi; ++i) acc += g[(int64_t)perm[i] * dim + k];
+        float* q = table + (int64_t)s * dim + k;
+        *q = *q + (-lr) * acc;
+    }
+}
+
+// ---- queries and table normalisation ---------------------------------------------------------------
+// q[i] = n(ent[a[i]]) + n(rel[r[i]]) (tail queries) or n(ent[a[i]]) - n(rel[r[i]]) (head queries); with rel == NULL: q[i] = n(ent[i])
+__global__ __launch_bounds__(256) void k_transe_queries(const float* __restrict__ ent, const float* __restrict__ rel,
+                                                        const int32_t* __restrict__ ai, const int32_t* __restrict__ ri, int64_t m,
+                                                        int dim, int head, int norm, float* __restrict__ q) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= m) return;
+    float x[TE_C], y[TE_C];
+    te_load(ent + (int64_t)(rel ? ai[i] : i) * dim, dim, lane, x);
+    te_normalize(x, y, norm != 0);
+    if (rel) {
+        float xr[TE_C], yr[TE_C];
+        te_load(rel + (int64_t)ri[i] * dim, dim, lane, xr);
+        te_normalize(xr, yr, norm != 0);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) y[c] = head ? y[c] - yr[c] : y[c] + yr[c];
+    }
+    te_store(q + i * dim, dim, lane, y);
+}
+
+// ---- distances and the fused ranker --------------------------------------------------------------------
+constexpr int TE_TQ = 64, TE_TE = 64, TE_KC = 32;   // queries x entities per workgroup tile, columns per LDS stage
+
+__device__ __forceinline__ float te_pair_term(float acc, float a, float b, int p) {
+    const float d = a - b;
+    return p == 1 ? acc + fabsf(d) : fmaf(d, d, acc);
+}
+
+// acc[4][4] for queries q0 + 4 ty .. and entities e0 + 4 tx ..: the columns in order, one accumulator per pair
+__device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v, int dim, int p,
+                                        int64_t q0, int e0, float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4], float (&acc)[4][4]) {
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+    for (int k0 = 0; k0 < dim; k0 += TE_KC) {
+        __syncthreads();
+        for (int x = tid; x < TE_TQ * TE_KC; x += 256) {
+            const int row = x / TE_KC, k = x % TE_KC;
+            const int64_t qi = q0 + row;
+            qs[k][row] = (qi < m && k0 + k < dim) ? q[qi * dim + k0 + k] : 0.f;
+            const int ej = e0 + row;
+            es[k][row] = (ej < v && k0 + k < dim) ? en[(int64_t)ej * dim + k0 + k] : 0.f;
+        }
+        __syncthreads();
+        const int kn = min(TE_KC, dim - k0);
+        for (int k = 0; k < kn; ++k) {
+            const float4 qa = *reinterpret_cast<const float4*>(&qs[k][4 * ty]);
+            const float4 eb = *reinterpret_cast<const float4*>(&es[k][4 * tx]);
+            const float qv[4] = {qa.x, qa.y, qa.z, qa.w}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], p);
+        }
+    }
+    if (p == 2) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = sqrtf(acc[a][b]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_transe_distances(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v,
+                                                          int dim, int p, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    const int64_t q0 = (int64_t)blockIdx.x * TE_TQ;
+    const int e0 = blockIdx.y * TE_TE;
+    float acc[4][4];
+    te_tile(q, m, en, v, dim, p, q0, e0, qs, es, acc);
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int64_t qi = q0 + 4 * ty + a;
+            const int ej = e0 + 4 * tx + b;
+            if (qi < m && ej < v) out[qi * v + ej] = acc[a][b];
+        }
+}
+
+// counts[0][i] = 2 #better + #equal (raw), counts[1][i] the same over the entities not listed in f_ent[f_lo[i], f_hi[i]) -- the
+// rule of ranking.sort_and_rank on score = -distance: j != target is better when !(d_j >= d_target) (NaN on either side), equal
+// when d_j == d_target.  Block (x, y) takes query tile x and entity tiles y, y + gridDim.y, ...; integer atomics add the counts.
+__global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v,
+                                                     int dim, int p, const int32_t* __restrict__ target,
+                                                     const int32_t* __restrict__ f_lo, const int32_t* __restrict__ f_hi,
+                                                     const int32_t* __restrict__ f_ent, int32_t* __restrict__ raw,
+                                                     int32_t* __restrict__ filt) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    __shared__ float dt_s[TE_TQ];
+    __shared__ unsigned long long mask_s[TE_TQ];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int64_t q0 = (int64_t)blockIdx.x * TE_TQ;
+    if (tid < TE_TQ) {     // the target's distance, with te_tile's per-pair arithmetic
+        const int64_t qi = q0 + tid;
+        float acc = 0.f;
+        if (qi < m) {
+            const float* qr = q + qi * dim;
+            const float* er = en + (int64_t)target[qi] * dim;
+            for (int k = 0; k < dim; ++k) acc = te_pair_term(acc, qr[k], er[k], p);
+            if (p == 2) acc = sqrtf(acc);
+        }
+        dt_s[tid] = acc;
+    }
+    int cr[4] = {0, 0, 0, 0}, cf[4] = {0, 0, 0, 0};
+    const int n_tiles = (v + TE_TE - 1) / TE_TE;
+    for (int et = blockIdx.y; et < n_tiles; et += gridDim.y) {
+        const int e0 = et * TE_TE;
+        __syncthreads();
+        if (tid < TE_TQ) {
+            unsigned long long mk = 0;
+            const int64_t qi = q0 + tid;
+            if (f_lo && qi < m) {
+                int a = f_lo[qi], z = f_hi[qi];
+                while (a < z) {           // first listed id >= e0
+                    const int mid = (a + z) >> 1;
+                    if (f_ent[mid] < e0) a = mid + 1;
+                    else z = mid;
+                }
+                for (int x = a; x < f_hi[qi] && f_ent[x] < e0 + TE_TE; ++x) mk |= 1ull << (f_ent[x] - e0);
+            }
+            mask_s[tid] = mk;
+        }
+        float acc[4][4];
+        te_tile(q, m, en, v, dim, p, q0, e0, qs, es, acc);    // its first barrier publishes dt_s / mask_s
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int row = 4 * ty + a;
+            const int64_t qi = q0 + row;
+            if (qi >= m) continue;
+            const float dt = dt_s[row];
+            const unsigned long long mk = mask_s[row];
+            const int tg = target[qi];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int col = 4 * tx + b, ej = e0 + col;
+                if (ej >= v || ej == tg) continue;
+                const float d = acc[a][b];
+                const int c = !(d >= dt) ? 2 : (d == dt ? 1 : 0);
+                cr[a] += c;
+                if (!(mk >> col & 1ull)) cf[a] += c;
+            }
+        }
+    }
+    // the 16 lanes of a query row hold its partial counts: sum them, one atomic per query and kind
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        for (int off = 8; off >= 1; off >>= 1) {
+            cr[a] += __shfl_xor(cr[a], off, 16);
+            cf[a] += __shfl_xor(cf[a], off, 16);
+        }
+        const int64_t qi = q0 + 4 * ty + a;
+        if (tx == 0 && qi < m) {
+            atomicAdd(&raw[qi], cr[a]);
+            atomicAdd(&filt[qi], cf[a]);
+        }
+    }
+}
+
+}  // namespace gv
+
+using namespace gv;
+
+extern "C" int gv_transe_sample(const uint64_t* rng_state, uint32_t stream, const int32_t* train, int64_t n_train, int n_ent,
+                                const float* p_head, const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent_o,
+                                const int32_t* f_ent_s, int batch, int neg_ent, int32_t* bh, int32_t* br, int32_t* bt,
+                                uint32_t* draws, void* stream_) {
+    GV_REQUIRE(n_train > 0 && n_train < (1ll << 31) && n_ent > 0 && batch > 0 && neg_ent >= 0, GV_ERR_SHAPE,
+               "gv_transe_sample: n_train=%lld n_ent=%d batch=%d neg_ent=%d", (long long)n_train, n_ent, batch, neg_ent);
+    GV_REQUIRE((int64_t)batch * (1 + neg_ent) < (1ll << 31), GV_ERR_SHAPE, "gv_transe_sample: batch * (1 + neg_ent) >= 2^31");
+    GV_REQUIRE(rng_state && train && bh && br && bt, GV_ERR_NULL, "gv_transe_sample: NULL pointer");
+    GV_REQUIRE(!f_lo || (f_hi && f_ent_o && f_ent_s), GV_ERR_NULL, "gv_transe_sample: a filter needs f_lo, f_hi, f_ent_o, f_ent_s");
+    hipLaunchKernelGGL(k_transe_sample, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream_, rng_state, stream, train,
+                       n_train, n_ent, p_head, f_lo, f_hi, f_ent_o, f_ent_s, batch, neg_ent, bh, br, bt, draws);
+    return launch_status("gv_transe_sample");
+}
+
+extern "C" int gv_transe_step(const float* ent, const float* rel, const int32_t* bh, const int32_t* br, const int32_t* bt, int batch,
+                              int neg_ent, int dim, int p_norm, int norm_flag, float margin, float adv_temperature, float regul_rate,
+                              float* g_ent, float* g_rel, float* loss_part, float* score, int32_t* occ_ent, void* stream) {
+    GV_REQUIRE(batch > 0 && neg_ent > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_step: batch=%d neg_ent=%d dim=%d (1..%d) p_norm=%d (1 or 2)", batch, neg_ent, dim, GV_TRANSE_MAX_DIM, p_norm);
+    GV_REQUIRE((int64_t)batch * (2 + neg_ent) * dim < (1ll << 40), GV_ERR_SHAPE, "gv_transe_step: batch too large");
+    GV_REQUIRE(ent && rel && bh && br && bt && g_ent && g_rel && loss_part, GV_ERR_NULL, "gv_transe_step: NULL pointer");
+    TeStepArgs a{ent, rel, bh, br, bt, batch, neg_ent, dim, p_norm, norm_flag, margin, adv_temperature, regul_rate,
+                 g_ent, g_rel, loss_part, score, occ_ent};
+    hipLaunchKernelGGL(k_transe_step, dim3((batch + 3) / 4), dim3(256), 0, GV_ST, a);
+    return launch_status("gv_transe_step");
+}
+
+extern "C" int gv_transe_apply(float* ent, int n_ent, const float* g_ent, const int32_t* perm_e, const int32_t* rowptr_e, float* rel,
+                               int n_rel, const float* g_rel, const int32_t* perm_r, const int32_t* rowptr_r, int dim, float lr,
+                               const float* loss_part, int batch, float margin, float* loss_out, double* epoch_acc, void* stream) {
+    GV_REQUIRE(n_ent > 0 && n_rel > 0 && dim > 0 && batch > 0, GV_ERR_SHAPE, "gv_transe_apply: n_ent=%d n_rel=%d dim=%d batch=%d",
+               n_ent, n_rel, dim, batch);
+    GV_REQUIRE(ent && g_ent && perm_e && rowptr_e && rel && g_rel && perm_r && rowptr_r && loss_part && loss_out, GV_ERR_NULL,
+               "gv_transe_apply: NULL pointer");
+    const int row_blocks = (int)(((int64_t)n_ent + n_rel + 3) / 4);
+    hipLaunchKernelGGL(k_transe_apply, dim3(row_blocks + 1), dim3(256), 0, GV_ST, ent, n_ent, g_ent, perm_e, rowptr_e, rel, n_rel,
+                       g_rel, perm_r, rowptr_r, dim, lr, loss_part, batch, margin, loss_out, epoch_acc, row_blocks);
+    return launch_status("gv_transe_apply");
+}
+
+extern "C" int gv_transe_queries(const float* ent, const float* rel, const int32_t* a, const int32_t* r, int64_t m, int dim,
+                                 int head, int norm_flag, float* q, void* stream) {
+    GV_REQUIRE(m >= 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM, GV_ERR_SHAPE, "gv_transe_queries: m=%lld dim=%d (1..%d)", (long long)m,
+               dim, GV_TRANSE_MAX_DIM);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(ent && q && (!rel || (a && r)), GV_ERR_NULL, "gv_transe_queries: NULL pointer");
+    hipLaunchKernelGGL(k_transe_queries, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, GV_ST, ent, rel, a, r, m, dim, head, norm_flag, q);
+    return launch_status("gv_transe_queries");
+}
+
+extern "C" int gv_transe_distances(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, float* out, void* stream) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_distances: m=%lld v=%d dim=%d p_norm=%d", (long long)m, v, dim, p_norm);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && en && out, GV_ERR_NULL, "gv_transe_distances: NULL pointer");
+    hipLaunchKernelGGL(k_transe_distances, dim3((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)((v + TE_TE - 1) / TE_TE)), dim3(256),
+                       0, GV_ST, q, m, en, v, dim, p_norm, out);
+    return launch_status("gv_transe_distances");
+}
+
+extern "C" int gv_transe_rank_filtered(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
+                                       const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, int32_t* counts_raw,
+                                       int32_t* counts_filt, void* stream) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_rank_filtered: m=%lld v=%d dim=%d p_norm=%d", (long long)m, v, dim, p_norm);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && en && target && counts_raw && counts_filt, GV_ERR_NULL, "gv_transe_rank_filtered: NULL pointer");
+    GV_REQUIRE(!f_lo || (f_hi && f_ent), GV_ERR_NULL, "gv_transe_rank_filtered: a filter needs f_lo, f_hi and f_ent");
+    hipError_t e = fill_words(counts_raw, 0u, (size_t)m * 4, GV_ST);
+    if (e == hipSuccess) e = fill_words(counts_filt, 0u, (size_t)m * 4, GV_ST);
+    GV_REQUIRE(e == hipSuccess, (int)e, "gv_transe_rank_filtered: clearing the counts: %s", hipGetErrorString(e));
+    const int64_t q_tiles = (m + TE_TQ - 1) / TE_TQ;
+    const int e_tiles = (v + TE_TE - 1) / TE_TE;
+    int64_t split = (4 * (int64_t)current_device_cus() + q_tiles - 1) / q_tiles;
+    if (split > e_tiles) split = e_tiles;
+    if (split < 1) split = 1;
+    hipLaunchKernelGGL(k_transe_rank, dim3((unsigned)q_tiles, (unsigned)split), dim3(256), 0, GV_ST, q, m, en, v, dim, p_norm, target,
+                       f_lo, f_hi, f_ent, counts_raw, counts_filt);
+    return launch_status("gv_transe_rank_filtered");
+}

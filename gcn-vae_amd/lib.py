@@ -112,6 +112,12 @@ SIGNATURES = {
     'gv_ec_basis_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _I, _P]),
     'gv_ec_head_fwd': (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
     'gv_ec_head_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    'gv_transe_sample': (_I, [_P, ctypes.c_uint32, _P, _L, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'gv_transe_step': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
+    'gv_transe_apply': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _I, _F, _P, _P, _P]),
+    'gv_transe_queries': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
+    'gv_transe_distances': (_I, [_P, _L, _P, _I, _I, _I, _P, _P]),
+    'gv_transe_rank_filtered': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -2590,3 +2590,237 @@ def loss_head(z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, 
 from .made import *                                              # noqa: E402,F401,F403
 from .made import _ChainLayer, _RowLayer, _MADEForward, _MADEForwardBF16      # noqa: E402,F401
 from . import made                                               # noqa: E402,F401  (ops.made.<KNOB>)
+
+
+# ------------------------------------------------------------------------------------------------
+# TransE (transe.py): sampler, fused step, ordered SGD, queries, distances and the filtered ranker (k_transe.hip)
+# ------------------------------------------------------------------------------------------------
+TRANSE_MAX_DIM = 512      # = GV_TRANSE_MAX_DIM (include/gcnvae.h)
+
+
+def _i32(t, name, n=None):
+    t = _chk(t, torch.int32, name)
+    if not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f'{name}: expected a contiguous int32 tensor of {n} entries')
+    return t
+
+
+def _table(t, name):
+    t = _chk(t, name=name)
+    if t.dim() != 2 or not t.is_contiguous() or not 1 <= t.shape[1] <= TRANSE_MAX_DIM:
+        raise ValueError(f'{name}: expected a contiguous (rows, dim) float32 table with 1 <= dim <= {TRANSE_MAX_DIM}')
+    return t
+
+
+def _p_norm(p):
+    if p not in (1, 2):
+        raise ValueError(f'p_norm must be 1 or 2, got {p}')
+    return int(p)
+
+
+def transe_sample(rng_state, stream_id, train, n_ent, batch, neg_ent, p_head=None, filt=None, bh=None, br=None, bt=None,
+                  draws=None, check=True):
+    """(bh, br, bt) int32 of batch * (1 + neg_ent) rows in OpenKE's layout (gv_transe_sample).  ``train`` int32 (n, 3) on the device;
+    ``p_head`` float32 [num_rels] or None; ``filt`` = (f_lo, f_hi, f_ent_o, f_ent_s) as ``transe.TrainFilter`` holds them, or None.
+    ``check`` reads the triples and filter ranges back to validate them before the launch (pass False under capture, once the
+    same arrays have been checked)."""
+    train = _i32(train, 'train')
+    if train.dim() != 2 or train.shape[1] != 3 or train.shape[0] < 1:
+        raise ValueError('train: expected (n >= 1, 3) int32 triples')
+    batch, neg_ent, n_ent = int(batch), int(neg_ent), int(n_ent)
+    if batch < 1 or neg_ent < 0 or n_ent < 1:
+        raise ValueError(f'batch={batch} neg_ent={neg_ent} n_ent={n_ent}')
+    n = batch * (1 + neg_ent)
+    dev = train.device
+    bh = torch.empty(n, dtype=torch.int32, device=dev) if bh is None else _i32(bh, 'bh', n)
+    br = torch.empty(n, dtype=torch.int32, device=dev) if br is None else _i32(br, 'br', n)
+    bt = torch.empty(n, dtype=torch.int32, device=dev) if bt is None else _i32(bt, 'bt', n)
+    if p_head is not None:
+        p_head = _chk(p_head, name='p_head')
+    if check:        # reads the triples back (once per training set in DeviceTrainer; callers under capture pass check=False)
+        if int(train[:, [0, 2]].min()) < 0 or int(train[:, [0, 2]].max()) >= n_ent or int(train[:, 1].min()) < 0:
+            raise ValueError(f'train: entity ids must lie in [0, {n_ent}) and relation ids be >= 0')
+        if p_head is not None and int(train[:, 1].max()) >= p_head.numel():
+            raise ValueError(f'p_head: {p_head.numel()} entries, relation ids up to {int(train[:, 1].max())}')
+    f = [None] * 4
+    if filt is not None:
+        f = [_i32(filt[0], 'f_lo', 2 * train.shape[0]), _i32(filt[1], 'f_hi', 2 * train.shape[0]),
+             _i32(filt[2], 'f_ent_o'), _i32(filt[3], 'f_ent_s')]
+        if check and (int(f[0].min()) < 0 or bool((f[1] < f[0]).any())
+                      or int(f[1][0::2].max()) > f[2].numel() or int(f[1][1::2].max()) > f[3].numel()):
+            raise ValueError('filt: ranges must satisfy 0 <= f_lo <= f_hi <= len(f_ent_o / f_ent_s)')
+    rng_state = _chk(rng_state, torch.int64, 'rng_state')
+    if rng_state.numel() < 2 or rng_state.device != train.device:
+        raise ValueError('rng_state: the {seed, tick} int64 pair on the triples\' device')
+    if draws is not None:
+        draws = _chk(draws, torch.int32, 'draws')
+        if draws.numel() != batch * (neg_ent + 2):
+            raise ValueError('draws: batch * (neg_ent + 2) int32 entries')
+    lib.call('gv_transe_sample', ptr(rng_state), int(stream_id) & 0xFFFFFFFF, ptr(train), train.shape[0], n_ent, ptr(p_head),
+             *[ptr(x) for x in f], batch, neg_ent, ptr(bh), ptr(br), ptr(bt), ptr(draws), lib.stream())
+    return bh, br, bt
+
+
+def transe_step(ent, rel, bh, br, bt, batch, neg_ent, p_norm, norm_flag, margin, adv_temperature=None, regul_rate=0.0,
+                out=None, score=None, occ_ent=None, check=True):
+    """Forward, loss and backward of one batch in one launch (gv_transe_step).  Returns (g_ent (2 + neg_ent) * batch x dim,
+    g_rel batch x dim, loss_part [batch]): one gradient row per occurrence, the loss = loss_part.sum() + margin.  ``occ_ent``
+    (int32 [(2 + neg_ent) * batch], optional) receives the entity id of each g_ent row.  Every negative shares the positive's
+    relation and one of its entities (the sampler's layout): the side whose id differs from the positive's is the corrupted one."""
+    ent, rel = _table(ent, 'ent'), _table(rel, 'rel')
+    if ent.shape[1] != rel.shape[1]:
+        raise ValueError('ent / rel width mismatch')
+    batch, neg_ent = int(batch), int(neg_ent)
+    if batch < 1 or neg_ent < 1:
+        raise ValueError(f'batch={batch} neg_ent={neg_ent}: need at least one positive and one negative each')
+    n, dim = batch * (1 + neg_ent), ent.shape[1]
+    bh, br, bt = _i32(bh, 'bh', n), _i32(br, 'br', n), _i32(bt, 'bt', n)
+    if check:        # reads the ids back: callers under hipGraph capture pass check=False for ids made in range on the device
+        for name, t, hi in (('bh', bh, ent.shape[0]), ('bt', bt, ent.shape[0]), ('br', br, rel.shape[0])):
+            if int(t.min()) < 0 or int(t.max()) >= hi:
+                raise ValueError(f'{name}: ids must lie in [0, {hi})')
+    p_norm = _p_norm(p_norm)
+    if adv_temperature is not None and not adv_temperature > 0:
+        raise ValueError('adv_temperature must be > 0 (or None)')
+    if out is None:
+        out = (torch.empty((2 + neg_ent) * batch, dim, device=ent.device), torch.empty(batch, dim, device=ent.device),
+               torch.empty(batch, device=ent.device))
+    elif (tuple(_chk(out[0], name='g_ent').shape) != ((2 + neg_ent) * batch, dim) or tuple(_chk(out[1], name='g_rel').shape) != (batch, dim)
+          or _chk(out[2], name='loss_part').numel() != batch):
+        raise ValueError('out: (g_ent ((2 + neg_ent) batch, dim), g_rel (batch, dim), loss_part [batch])')
+    if score is not None:
+        score = _chk(score, name='score')
+        if score.numel() != n:
+            raise ValueError('score: batch * (1 + neg_ent) entries')
+    if occ_ent is not None:
+        occ_ent = _i32(occ_ent, 'occ_ent', (2 + neg_ent) * batch)
+    lib.call('gv_transe_step', ptr(ent), ptr(rel), ptr(bh), ptr(br), ptr(bt), batch, neg_ent, dim, p_norm, int(bool(norm_flag)),
+             float(margin), float(adv_temperature or 0.0), float(regul_rate), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(score),
+             ptr(occ_ent), lib.stream())
+    return out
+
+
+class TransEOrder:
+    """Buffers of the two occurrence orderings (entities, relations) gv_build_csr makes for the SGD launch, sized once (work
+    items and fix-ups are 4 int32 each, as indices.KGraph carves them)."""
+
+    def __init__(self, n_occ_e, n_ent, n_occ_r, n_rel, device, chunk=256):
+        from .indices import _index_caps, _index_workspace
+        self.parts = []
+        for n_occ, n_seg in ((n_occ_e, n_ent), (n_occ_r, n_rel)):
+            items_cap, fix_cap, _ = _index_caps(n_occ, n_seg, chunk)
+            i32 = dict(dtype=torch.int32, device=device)
+            self.parts.append(dict(n=n_occ, n_seg=n_seg, perm=torch.empty(n_occ, **i32), rowptr=torch.empty(n_seg + 1, **i32),
+                                   items=torch.empty(4 * items_cap, **i32), items_cap=items_cap, fix=torch.empty(4 * fix_cap, **i32),
+                                   fix_cap=fix_cap))
+        self.ws, self.ws_bytes = _index_workspace(device, max(n_occ_e, n_occ_r), max(n_ent, n_rel))
+        self.chunk = chunk
+
+    def build(self, keys_e, keys_r):
+        for p, keys in zip(self.parts, (keys_e, keys_r)):
+            lib.call('gv_build_csr', ptr(keys), p['n'], p['n_seg'], self.chunk, ptr(p['perm']), ptr(p['rowptr']), ptr(p['items']),
+                     p['items_cap'], ptr(p['fix']), p['fix_cap'], ptr(self.ws), self.ws_bytes, lib.stream())
+        return self.parts
+
+
+def transe_apply(ent, rel, g_ent, g_rel, order, lr, loss_part, margin, loss_out, epoch_acc=None):
+    """p += -lr * g on the touched rows of both tables, occurrences summed in order (gv_transe_apply); ``order`` = the two
+    ``TransEOrder`` parts after ``build``.  Writes loss_out[0] = loss_part.sum() + margin and adds it to epoch_acc (float64)."""
+    ent, rel = _table(ent, 'ent'), _table(rel, 'rel')
+    dim = ent.shape[1]
+    if rel.shape[1] != dim or ent.device != rel.device:
+        raise ValueError('ent / rel: same width and device')
+    pe, pr = order
+    g_ent, g_rel = _chk(g_ent, name='g_ent'), _chk(g_rel, name='g_rel')
+    if pe['n_seg'] != ent.shape[0] or pr['n_seg'] != rel.shape[0]:
+        raise ValueError(f'the orderings cover {pe["n_seg"]} entities / {pr["n_seg"]} relations, the tables hold '
+                         f'{ent.shape[0]} / {rel.shape[0]} rows')
+    if tuple(g_ent.shape) != (pe['n'], dim) or tuple(g_rel.shape) != (pr['n'], dim):
+        raise ValueError(f'g_ent {tuple(g_ent.shape)} / g_rel {tuple(g_rel.shape)}: expected ({pe["n"]}, {dim}) / ({pr["n"]}, {dim}), '
+                         'one row per ordered occurrence')
+    loss_part, loss_out = _chk(loss_part, name='loss_part'), _chk(loss_out, name='loss_out')
+    if loss_part.numel() < 1 or loss_out.numel() < 1:
+        raise ValueError('loss_part and loss_out need at least one entry')
+    for name, t in (('g_ent', g_ent), ('g_rel', g_rel), ('loss_part', loss_part), ('loss_out', loss_out)):
+        if t.device != ent.device:
+            raise ValueError(f'{name}: on {t.device}, the tables on {ent.device}')
+    if epoch_acc is not None:
+        epoch_acc = _chk(epoch_acc, torch.float64, 'epoch_acc')
+        if epoch_acc.numel() < 1 or epoch_acc.device != ent.device:
+            raise ValueError('epoch_acc: one float64 entry on the tables\' device')
+    lib.call('gv_transe_apply', ptr(ent), ent.shape[0], ptr(g_ent), ptr(pe['perm']), ptr(pe['rowptr']), ptr(rel), rel.shape[0],
+             ptr(g_rel), ptr(pr['perm']), ptr(pr['rowptr']), ent.shape[1], float(lr), ptr(loss_part), loss_part.numel(),
+             float(margin), ptr(loss_out), ptr(epoch_acc), lib.stream())
+
+
+def transe_queries(ent, rel=None, a=None, r=None, head=False, norm_flag=True):
+    """q[i] = n(ent[a[i]]) + n(rel[r[i]]) (tail queries), n(ent[a[i]]) - n(rel[r[i]]) (head queries); without ``rel`` the
+    normalised table n(ent) (gv_transe_queries)."""
+    ent = _table(ent, 'ent')
+    dim = ent.shape[1]
+    if rel is None:
+        m = ent.shape[0]
+    else:
+        rel = _table(rel, 'rel')
+        if rel.shape[1] != dim:
+            raise ValueError('ent / rel width mismatch')
+        a = a.to(device=ent.device, dtype=torch.int32).contiguous()
+        r = r.to(device=ent.device, dtype=torch.int32).contiguous()
+        m = a.numel()
+        if r.numel() != m:
+            raise ValueError('one relation per query')
+        if m and (int(a.min()) < 0 or int(a.max()) >= ent.shape[0] or int(r.min()) < 0 or int(r.max()) >= rel.shape[0]):
+            raise ValueError('query ids out of range')
+    q = torch.empty(m, dim, dtype=torch.float32, device=ent.device)
+    lib.call('gv_transe_queries', ptr(ent), ptr(rel), ptr(a), ptr(r), m, dim, int(bool(head)), int(bool(norm_flag)), ptr(q),
+             lib.stream())
+    return q
+
+
+def transe_distances(q, en, p_norm):
+    """(m, v) = ||q[i] - en[j]||_p, materialised (gv_transe_distances): the fused ranker's distances, bit for bit."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    p_norm = _p_norm(p_norm)
+    out = torch.empty(q.shape[0], en.shape[0], dtype=torch.float32, device=q.device)
+    lib.call('gv_transe_distances', ptr(q), q.shape[0], ptr(en), en.shape[0], q.shape[1], p_norm, ptr(out), lib.stream())
+    return out
+
+
+def transe_rank_filtered(q, en, target, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
+    """(raw, filtered) 0-based mid-ranks of ``target[i]`` under score = -||q[i] - en[j]||_p -- ``ranking.sort_and_rank`` on
+    ``transe_distances`` bit for bit -- without the distance matrix (gv_transe_rank_filtered).  The filter ranges are
+    ``rank_scores_filtered``'s; without them the filtered rank equals the raw one."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    p_norm = _p_norm(p_norm)
+    m, v = q.shape[0], en.shape[0]
+    target = target.reshape(-1)
+    if target.numel() != m:
+        raise ValueError('one target per query row')
+    if m and (int(target.min()) < 0 or int(target.max()) >= v):
+        raise ValueError(f'targets must lie in [0, {v})')
+    i32 = dict(device=q.device, dtype=torch.int32)
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    lo32 = hi32 = ent32 = None
+    if all(given):
+        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+        if filt_lo.numel() != m or filt_hi.numel() != m:
+            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+        n_ent = filt_ent.numel()
+        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
+            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
+            raise ValueError(f'filtered entity ids must lie in [0, {v})')
+        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    tgt32 = target.to(**i32).contiguous()
+    counts = torch.zeros(2, max(m, 1), **i32)
+    lib.call('gv_transe_rank_filtered', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
+             ptr(counts[0]), ptr(counts[1]), lib.stream())
+    both = counts[:, :m].to(torch.float32) * 0.5
+    return both[0], both[1]

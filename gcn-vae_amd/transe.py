@@ -1,0 +1,505 @@
+"""TransE, the baseline of Table 2 next to R-GCN and GCN-VAE (baselines/transe: OpenKE's TransE, MarginLoss, NegativeSampling,
+Trainer and main.py), trained and evaluated on the device.
+
+Model and loss keep the reference's semantics, class names and state-dict keys (``zero_const``, ``pi_const``,
+``ent_embeddings.weight``, ``rel_embeddings.weight``) and its xavier-uniform initialisation, so a seeded model starts from the
+reference's tables and a reference checkpoint loads.  Every training row is scored in OpenKE's 'normal' mode,
+``||n(h) + n(r) - n(t)||_p`` with ``n = F.normalize`` under ``norm_flag``; the loss is ``mean(max(p - n, -margin)) + margin``
+(self-adversarial: detached ``softmax(-n * T)`` weights summed over each positive's negatives) plus ``regul_rate`` times the mean
+of the squares of the raw batch rows.  The ``margin`` / ``epsilon`` model arguments (a different score, ``margin - d``, and a
+uniform init) are not used by main.py and are refused.
+
+Negative sampler (OpenKE's library is not part of the reference; this is the rule implemented):
+  * a batch of ``B = len(train) // nbatches`` positives is drawn uniformly with replacement (OpenKE's 'normal' mode) and
+    ``neg_ent`` negatives per positive, laid out as the B positives, then ``neg_ent`` blocks of B;
+  * with ``bern_flag`` the head is corrupted with probability ``tph / (tph + hpt)`` of the positive's relation (Wang et al. 2014;
+    tph: triples per distinct head, hpt: triples per distinct tail), the tail otherwise; without it always the tail;
+  * with ``filter_flag`` the replacement is uniform over the entities that form NO known training triple with the kept pair:
+    a draw ``u`` in ``[0, V - k)`` maps to the u-th entity absent from the k known answers of ``FilterIndex(train)``
+    (``nth_unlisted``); with ``k == V`` or without the filter the draw is uniform over all V entities;
+  * relations are never corrupted (``neg_rel = 0``).
+The draws are Philox4x32-10 keyed by the device RNG's {seed, tick} (include/gcnvae.h, gv_transe_sample), so a captured step
+samples anew at every replay.
+
+Device path (k_transe.hip): one sampler launch, one fused forward / loss / backward launch writing a gradient row per occurrence,
+two gv_build_csr orderings of the occurrences, and one launch that sums each touched row's occurrences in a fixed order and applies
+``p += -lr * g`` (rows without occurrences are not written, as torch's dense SGD leaves them).  No float atomics: a step is
+bit-identical run to run and eager vs captured.  The loss stays on the device; the per-epoch sum is read once per epoch.
+
+Evaluation: raw and filtered MRR, MR and Hits@1/3/10 over both directions, filter = train + valid + test.  Ranks are exactly
+``ranking.sort_and_rank(-distance, target)``: tail queries ``q = n(h) + n(r)``, head queries ``q = n(t) - n(r)``, both
+``||q - n(E_j)||_p`` (``h' + (r - t)`` and ``h' - (t - r)`` round alike), from ``ops.transe_rank_filtered``, which never stores
+the distance matrix.  The ``*_unfused`` functions are the plain-torch statement of the same rules: the in-repo cross-check and
+the bench's comparator, never a fallback.
+
+    python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
+"""
+import argparse
+import time
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .ranking import FilterIndex, _listed_mask, sort_and_rank
+
+
+# ------------------------------------------------------------------------------------------------
+# model and loss (the reference's modules)
+# ------------------------------------------------------------------------------------------------
+class BaseModule(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.zero_const = nn.Parameter(torch.Tensor([0]))
+        self.zero_const.requires_grad = False
+        self.pi_const = nn.Parameter(torch.Tensor([3.14159265358979323846]))
+        self.pi_const.requires_grad = False
+
+    def load_checkpoint(self, path):
+        self.load_state_dict(torch.load(path, map_location='cpu'))
+        self.eval()
+
+    def save_checkpoint(self, path):
+        torch.save(self.state_dict(), path)
+
+
+class TransE(BaseModule):
+    def __init__(self, ent_tot, rel_tot, dim=100, p_norm=1, norm_flag=True, margin=None, epsilon=None):
+        super().__init__()
+        if margin is not None or epsilon is not None:
+            raise ValueError('TransE(margin=..., epsilon=...) selects the reference\'s margin - d score and uniform init, which '
+                             'main.py never uses: not supported (pass the margin to MarginLoss)')
+        if p_norm not in (1, 2):
+            raise ValueError(f'p_norm must be 1 or 2, got {p_norm}')
+        self.ent_tot, self.rel_tot, self.dim, self.p_norm, self.norm_flag = ent_tot, rel_tot, dim, p_norm, norm_flag
+        self.margin, self.epsilon, self.margin_flag = None, None, False
+        self.ent_embeddings = nn.Embedding(ent_tot, dim)
+        self.rel_embeddings = nn.Embedding(rel_tot, dim)
+        nn.init.xavier_uniform_(self.ent_embeddings.weight.data)
+        nn.init.xavier_uniform_(self.rel_embeddings.weight.data)
+
+    def _calc(self, h, t, r, mode):
+        return score_rule(h, r, t, self.p_norm, self.norm_flag, mode)
+
+    def forward(self, data):
+        h = self.ent_embeddings(data['batch_h'])
+        t = self.ent_embeddings(data['batch_t'])
+        r = self.rel_embeddings(data['batch_r'])
+        return self._calc(h, t, r, data['mode'])
+
+    def regularization(self, data):
+        h = self.ent_embeddings(data['batch_h'])
+        t = self.ent_embeddings(data['batch_t'])
+        r = self.rel_embeddings(data['batch_r'])
+        return (torch.mean(h ** 2) + torch.mean(t ** 2) + torch.mean(r ** 2)) / 3
+
+    def predict(self, data):
+        return self.forward(data).cpu().data.numpy()
+
+
+def score_rule(h, r, t, p_norm, norm_flag, mode='normal'):
+    """The reference's TransE._calc in plain torch."""
+    if norm_flag:
+        h, r, t = F.normalize(h, 2, -1), F.normalize(r, 2, -1), F.normalize(t, 2, -1)
+    if mode != 'normal':
+        h = h.view(-1, r.shape[0], h.shape[-1])
+        t = t.view(-1, r.shape[0], t.shape[-1])
+        r = r.view(-1, r.shape[0], r.shape[-1])
+    score = h + (r - t) if mode == 'head_batch' else (h + r) - t
+    return torch.norm(score, p_norm, -1).flatten()
+
+
+class MarginLoss(BaseModule):
+    def __init__(self, adv_temperature=None, margin=6.0):
+        super().__init__()
+        self.margin = nn.Parameter(torch.Tensor([margin]))
+        self.margin.requires_grad = False
+        if adv_temperature is not None:
+            self.adv_temperature = nn.Parameter(torch.Tensor([adv_temperature]))
+            self.adv_temperature.requires_grad = False
+            self.adv_flag = True
+        else:
+            self.adv_flag = False
+
+    def get_weights(self, n_score):
+        return F.softmax(-n_score * self.adv_temperature, dim=-1).detach()
+
+    def forward(self, p_score, n_score):
+        if self.adv_flag:
+            return (self.get_weights(n_score) * torch.max(p_score - n_score, -self.margin)).sum(dim=-1).mean() + self.margin
+        return (torch.max(p_score - n_score, -self.margin)).mean() + self.margin
+
+
+class NegativeSampling(BaseModule):
+    def __init__(self, model=None, loss=None, batch_size=256, regul_rate=0.0):
+        super().__init__()
+        self.model, self.loss, self.batch_size, self.regul_rate = model, loss, batch_size, regul_rate
+
+    def _get_positive_score(self, score):
+        return score[:self.batch_size].view(-1, self.batch_size).permute(1, 0)
+
+    def _get_negative_score(self, score):
+        return score[self.batch_size:].view(-1, self.batch_size).permute(1, 0)
+
+    def forward(self, data):
+        score = self.model(data)
+        loss_res = self.loss(self._get_positive_score(score), self._get_negative_score(score))
+        if self.regul_rate != 0:
+            loss_res += self.regul_rate * self.model.regularization(data)
+        return loss_res
+
+
+def step_unfused(ent, rel, bh, br, bt, batch, p_norm, norm_flag, margin, adv_temperature=None, regul_rate=0.0):
+    """One training step's scores, loss and table gradients by torch autograd on (ent, rel) (any device): the reference's
+    NegativeSampling(TransE, MarginLoss) forward and backward.  Returns (score, loss, g_ent, g_rel)."""
+    e = ent.detach().clone().requires_grad_(True)
+    r = rel.detach().clone().requires_grad_(True)
+    bh, br, bt = (x.to(device=ent.device, dtype=torch.long) for x in (bh, br, bt))
+    score = score_rule(e[bh], r[br], e[bt], p_norm, norm_flag)
+    loss_fn = MarginLoss(adv_temperature, margin).to(ent.device)
+    p = score[:batch].view(-1, batch).permute(1, 0)
+    n = score[batch:].view(-1, batch).permute(1, 0)
+    loss = loss_fn(p, n)
+    if regul_rate != 0:
+        h_, t_, r_ = e[bh], e[bt], r[br]
+        loss = loss + regul_rate * ((torch.mean(h_ ** 2) + torch.mean(t_ ** 2) + torch.mean(r_ ** 2)) / 3)
+    loss.backward()
+    return score.detach(), loss.detach().reshape(()), e.grad, r.grad
+
+
+# ------------------------------------------------------------------------------------------------
+# negative sampling rules (host statements of gv_transe_sample)
+# ------------------------------------------------------------------------------------------------
+def bern_head_prob(train, num_rels):
+    """Per relation tph / (tph + hpt): the probability that the head is the corrupted side (OpenKE's bern mode)."""
+    t = torch.as_tensor(np.asarray(train), dtype=torch.long).reshape(-1, 3)
+    out = torch.full((num_rels,), 0.5, dtype=torch.float64)
+    for rr in torch.unique(t[:, 1]).tolist():
+        sel = t[t[:, 1] == rr]
+        n = float(sel.shape[0])
+        tph = n / float(torch.unique(sel[:, 0]).numel())
+        hpt = n / float(torch.unique(sel[:, 2]).numel())
+        out[rr] = tph / (tph + hpt)
+    return out.to(torch.float32)
+
+
+def nth_unlisted(listed, u):
+    """The u-th (0-based) integer >= 0 not in the sorted unique list ``listed``: u + #{j : listed[j] - j <= u} (binary search)."""
+    lo, hi = 0, len(listed)
+    while lo < hi:
+        m = (lo + hi) // 2
+        if int(listed[m]) - m <= u:
+            lo = m + 1
+        else:
+            hi = m
+    return u + lo
+
+
+def map_draw(word, n):
+    """A uint32 draw onto [0, n): multiply-shift (the sampler's rule)."""
+    return (int(word) * int(n)) >> 32
+
+
+class TrainFilter:
+    """The FilterIndex(train) runs of every training triple, both directions, as gv_transe_sample reads them: f_lo / f_hi
+    [2 n_train] (slot 2i: the known tails of (h, r); 2i + 1: the known heads of (t, r)) into ent['o'] / ent['s']."""
+
+    def __init__(self, train, num_nodes, num_rels, device):
+        train = torch.as_tensor(np.asarray(train), dtype=torch.long).reshape(-1, 3)
+        self.index = FilterIndex(num_nodes, num_rels, train)
+        lo_o, hi_o = self.index.lookup(train[:, 0], train[:, 1], 'o')
+        lo_s, hi_s = self.index.lookup(train[:, 2], train[:, 1], 's')
+        i32 = dict(dtype=torch.int32, device=device)
+        self.f_lo = torch.stack([lo_o, lo_s], 1).reshape(-1).to(**i32).contiguous()
+        self.f_hi = torch.stack([hi_o, hi_s], 1).reshape(-1).to(**i32).contiguous()
+        self.ent_o = self.index.entities('o', device).contiguous()
+        self.ent_s = self.index.entities('s', device).contiguous()
+
+    def tuple(self):
+        return (self.f_lo, self.f_hi, self.ent_o, self.ent_s)
+
+
+def sample_from_draws(draws, train, num_nodes, batch, neg_ent, p_head=None, train_filter=None):
+    """The batch gv_transe_sample makes from its raw words (``draws`` [batch, neg_ent + 2] uint32), restated on the host."""
+    train = np.asarray(train).reshape(-1, 3)
+    d = np.asarray(draws, dtype=np.int64) & 0xFFFFFFFF
+    n = batch * (1 + neg_ent)
+    bh, br, bt = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+    f_lo = f_hi = None
+    if train_filter is not None:
+        f_lo, f_hi = train_filter.f_lo.cpu().numpy(), train_filter.f_hi.cpu().numpy()
+        ents = {0: train_filter.ent_o.cpu().numpy(), 1: train_filter.ent_s.cpu().numpy()}
+    ph = None if p_head is None else np.asarray(p_head.cpu() if isinstance(p_head, torch.Tensor) else p_head, np.float32)
+    for b in range(batch):
+        i = map_draw(d[b, 0], len(train))
+        h, r, t = (int(x) for x in train[i])
+        head = bool(ph is not None and np.float32((d[b, 1] >> 8) * np.float32(1.0 / 16777216.0)) < ph[r])
+        bh[b], br[b], bt[b] = h, r, t
+        listed = None
+        if f_lo is not None:
+            slot = 2 * i + int(head)
+            listed = ents[int(head)][f_lo[slot]:f_hi[slot]]
+            if len(listed) >= num_nodes:
+                listed = None
+        for j in range(neg_ent):
+            w = d[b, 2 + j]
+            u = map_draw(w, num_nodes - (len(listed) if listed is not None else 0))
+            if listed is not None:
+                u = nth_unlisted(listed, u)
+            o = batch * (j + 1) + b
+            bh[o], br[o], bt[o] = (u, r, t) if head else (h, r, u)
+    return bh, br, bt
+
+
+# ------------------------------------------------------------------------------------------------
+# device trainer
+# ------------------------------------------------------------------------------------------------
+class DeviceTrainer:
+    """TransE training on the device: ``step()`` = sample + fused step + orderings + SGD, ``capture()`` records one step as a
+    hipGraph that ``step()`` then replays.  ``model``'s two embedding tables are updated in place."""
+
+    def __init__(self, model, train, nbatches=100, neg_ent=25, bern_flag=True, filter_flag=True, margin=5.0, alpha=1.0,
+                 adv_temperature=None, regul_rate=0.0, device='cuda'):
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.model = model
+        train = np.asarray(train).reshape(-1, 3)
+        self.n_train = len(train)
+        self.batch = self.n_train // nbatches
+        if self.batch < 1:
+            raise ValueError(f'{self.n_train} training triples cannot make {nbatches} batches')
+        self.nbatches, self.neg_ent = nbatches, neg_ent
+        self.margin, self.alpha, self.adv, self.regul = float(margin), float(alpha), adv_temperature, float(regul_rate)
+        self.ent, self.rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+        if self.ent.device != self.device:
+            raise ValueError('move the model to the device first')
+        if len(train) and (train[:, [0, 2]].min() < 0 or train[:, [0, 2]].max() >= model.ent_tot or train[:, 1].min() < 0
+                           or train[:, 1].max() >= model.rel_tot):
+            raise ValueError(f'training triples out of range of the model ({model.ent_tot} entities, {model.rel_tot} relations)')
+        self.train = torch.as_tensor(train, dtype=torch.int32).to(self.device).contiguous()
+        self.p_head = bern_head_prob(train, model.rel_tot).to(self.device) if bern_flag else None
+        self.filt = TrainFilter(train, model.ent_tot, model.rel_tot, self.device).tuple() if filter_flag else None
+        self.rng = ops.device_rng(self.device)
+        self.stream_id = ops.new_rng_stream()
+        B, K, dim = self.batch, neg_ent, model.dim
+        i32 = dict(dtype=torch.int32, device=self.device)
+        n = B * (1 + K)
+        self.bh, self.br, self.bt = (torch.empty(n, **i32) for _ in range(3))
+        self.grads = (torch.empty((2 + K) * B, dim, device=self.device), torch.empty(B, dim, device=self.device),
+                      torch.empty(B, device=self.device))
+        self.occ_ent = torch.empty((2 + K) * B, **i32)
+        self.order = ops.TransEOrder((2 + K) * B, model.ent_tot, B, model.rel_tot, self.device)
+        self.loss = torch.zeros(1, device=self.device)
+        self.epoch_loss = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self.graph = None
+
+    def _step(self):
+        B, K = self.batch, self.neg_ent
+        self.rng.tick()
+        # ids, relation shares and filter runs were validated once, at construction: no read-back inside the (captured) step
+        ops.transe_sample(self.rng.state, self.stream_id, self.train, self.model.ent_tot, B, K, self.p_head, self.filt,
+                          self.bh, self.br, self.bt, check=False)
+        g_ent, g_rel, part = ops.transe_step(self.ent, self.rel, self.bh, self.br, self.bt, B, K, self.model.p_norm,
+                                             self.model.norm_flag, self.margin, self.adv, self.regul, out=self.grads,
+                                             occ_ent=self.occ_ent, check=False)
+        order = self.order.build(self.occ_ent, self.br[:B])
+        ops.transe_apply(self.ent, self.rel, g_ent, g_rel, order, self.alpha, part, self.margin, self.loss, self.epoch_loss)
+
+    def capture(self):
+        """Record one step.  A warm-up step runs first, outside capture (library load, the orderings' first launches); the tables
+        and the RNG state are restored after it, so a captured run takes exactly the steps an eager run takes, with the same draws."""
+        saved = (self.ent.clone(), self.rel.clone(), self.rng.state.clone())
+        self._step()
+        self.ent.copy_(saved[0])
+        self.rel.copy_(saved[1])
+        self.rng.state.copy_(saved[2])
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._step()
+        return self
+
+    def step(self):
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._step()
+
+    def epoch(self):
+        """nbatches steps; returns the summed loss (read back once)."""
+        self.epoch_loss.zero_()
+        for _ in range(self.nbatches):
+            self.step()
+        return float(self.epoch_loss.item())
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation
+# ------------------------------------------------------------------------------------------------
+MAX_QUERY_ROWS = 16384      # queries per ranker launch
+
+
+def _summary(raw, filt, hits):
+    out = {}
+    for kind, ranks in (('raw', raw + 1), ('filtered', filt + 1)):
+        ranks = ranks.double()
+        out['mrr_' + kind] = torch.mean(1.0 / ranks).item()
+        out['mr_' + kind] = torch.mean(ranks).item()
+        out['hits_' + kind] = {h: torch.mean((ranks <= h).double()).item() for h in hits}
+    return out
+
+
+def rank_transe(ent, rel, triplets, p_norm, norm_flag, filter_index=None):
+    """(raw, filtered) 0-based ranks, head queries of every triplet then tail queries, from the fused ranker."""
+    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
+    en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
+    raws, filts = [], []
+    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
+        ent_f = filter_index.entities(d, ent.device) if filter_index is not None else None
+        for lo in range(0, a.numel(), MAX_QUERY_ROWS):
+            hi = min(a.numel(), lo + MAX_QUERY_ROWS)
+            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
+            f = (None, None, None)
+            if filter_index is not None:
+                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
+                f = (f_lo, f_hi, ent_f)
+            rr, rf = ops.transe_rank_filtered(q, en, b[lo:hi], p_norm, *f)
+            raws.append(rr)
+            filts.append(rf)
+    return torch.cat(raws), torch.cat(filts)
+
+
+def rank_transe_unfused(ent, rel, triplets, p_norm, norm_flag, filter_index=None, batch=32):
+    """``rank_transe`` in plain torch on materialised distances: the reference's head_batch / tail scores of every entity,
+    ``sort_and_rank(-distance)``'s rule, the filtered count over the entities the filter does not list."""
+    s, r, o = (triplets[:, i].to(ent.device).long() for i in range(3))
+    v = ent.shape[0]
+    raws, filts = [], []
+    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
+        for lo in range(0, a.numel(), batch):
+            hi = min(a.numel(), lo + batch)
+            m = hi - lo
+            cand = ent.unsqueeze(0).expand(m, v, ent.shape[1])
+            fix = ent[a[lo:hi]].unsqueeze(1).expand_as(cand)
+            rr = rel[r[lo:hi]].unsqueeze(1).expand_as(cand)
+            if norm_flag:
+                cand, fix, rr = F.normalize(cand, 2, -1), F.normalize(fix, 2, -1), F.normalize(rr, 2, -1)
+            diff = cand + (rr - fix) if head else (fix + rr) - cand
+            dist = torch.norm(diff, p_norm, -1)
+            raws.append(sort_and_rank(-dist, b[lo:hi]))
+            if filter_index is not None:
+                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
+                listed = _listed_mask(f_lo, f_hi, filter_index.entities(d), m, v, dist.device)
+                score, tgt = -dist, -dist.gather(1, b[lo:hi].view(-1, 1))
+                keep = ~listed
+                keep[torch.arange(m, device=dist.device), b[lo:hi]] = False
+                filts.append(((~(score <= tgt)) & keep).sum(1).float() + 0.5 * ((score == tgt) & keep).sum(1).float())
+            else:
+                filts.append(raws[-1])
+    return torch.cat(raws), torch.cat(filts)
+
+
+def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False, verbose=True):
+    """Raw MRR, MR and Hits@k over both directions, and the filtered ones when ``filter_index`` is given (a FilterIndex,
+    train + valid + test).  Returns {'mrr_raw', 'mr_raw', 'hits_raw': {k: v}} plus the same '_filtered' keys with a filter."""
+    with torch.no_grad():
+        ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+        triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
+        fn = rank_transe_unfused if unfused else rank_transe
+        raw, filt = fn(ent, rel, triplets, model.p_norm, model.norm_flag, filter_index)
+        out = _summary(raw, filt, hits)
+    kinds = ('raw', 'filtered') if filter_index is not None else ('raw',)
+    if filter_index is None:         # without a filter the "filtered" ranks are the raw ones: not reported
+        out = {k: v for k, v in out.items() if not k.endswith('_filtered')}
+    if verbose:
+        for kind in kinds:
+            print('MRR ({}): {:.6f} | MR ({}): {:.3f}'.format(kind, out['mrr_' + kind], kind, out['mr_' + kind]))
+            for h in hits:
+                print('Hits ({}) @ {}: {:.6f}'.format(kind, h, out['hits_' + kind][h]))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# CLI (baselines/transe/main.py's hyperparameters as defaults)
+# ------------------------------------------------------------------------------------------------
+def build_parser():
+    p = argparse.ArgumentParser(description='TransE baseline (OpenKE formulation) on the device')
+    p.add_argument('-d', '--dataset', type=str, required=True, help='dataset (data.load_data)')
+    p.add_argument('--gpu', type=int, default=0, help='device')
+    p.add_argument('--dim', type=int, default=200)
+    p.add_argument('--p-norm', type=int, default=1)
+    p.add_argument('--norm-flag', type=int, default=1)
+    p.add_argument('--margin', type=float, default=5.0)
+    p.add_argument('--nbatches', type=int, default=100)
+    p.add_argument('--neg-ent', type=int, default=25)
+    p.add_argument('--neg-rel', type=int, default=0)
+    p.add_argument('--bern-flag', type=int, default=1)
+    p.add_argument('--filter-flag', type=int, default=1)
+    p.add_argument('--train-times', type=int, default=1000)
+    p.add_argument('--alpha', type=float, default=1.0, help='SGD learning rate')
+    p.add_argument('--opt-method', type=str, default='sgd')
+    p.add_argument('--adv-temperature', type=float, default=None)
+    p.add_argument('--regul-rate', type=float, default=0.0)
+    p.add_argument('--seed', type=int, default=None)
+    p.add_argument('--checkpoint', type=str, default='transe.ckpt')
+    p.add_argument('--test-mode', action='store_true', help='load --checkpoint and evaluate only')
+    p.add_argument('--eval-every', type=int, default=0, help='evaluate on valid every N epochs (0: never)')
+    p.add_argument('--filtered-eval', action='store_true', help='report filtered ranks as well (filter: train + valid + test)')
+    p.add_argument('--graph-step', action='store_true', help='capture one step as a hipGraph and replay it')
+    return p
+
+
+def check_args(args):
+    if args.opt_method.lower() != 'sgd':
+        raise ValueError(f'--opt-method {args.opt_method}: only sgd is supported')
+    if args.neg_rel != 0:
+        raise ValueError('--neg-rel: relation corruption is not supported')
+    if args.p_norm not in (1, 2):
+        raise ValueError('--p-norm must be 1 or 2')
+    if args.adv_temperature is not None and not args.adv_temperature > 0:
+        raise ValueError('--adv-temperature must be > 0')
+    if not 1 <= args.dim <= ops.TRANSE_MAX_DIM:
+        raise ValueError(f'--dim must lie in [1, {ops.TRANSE_MAX_DIM}]')
+
+
+def main(args):
+    check_args(args)
+    from .data import load_data
+    if not torch.cuda.is_available():
+        raise RuntimeError('TransE training runs on a ROCm device (no CPU fallback)')
+    torch.cuda.set_device(args.gpu)
+    dev = torch.device('cuda', args.gpu)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+        np.random.seed(args.seed)
+    data = load_data(args.dataset)
+    model = TransE(data.num_nodes, data.num_rels, dim=args.dim, p_norm=args.p_norm, norm_flag=bool(args.norm_flag))
+    filt = None
+    if args.filtered_eval:
+        filt = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+    if not args.test_mode:
+        model = model.to(dev)
+        tr = DeviceTrainer(model, data.train, args.nbatches, args.neg_ent, bool(args.bern_flag), bool(args.filter_flag),
+                           args.margin, args.alpha, args.adv_temperature, args.regul_rate, dev)
+        if args.graph_step:
+            tr.capture()
+        print('Finish initializing...')
+        t0 = time.time()
+        for epoch in range(args.train_times):
+            res = tr.epoch()
+            print('Epoch %d | loss: %f' % (epoch, res))
+            if args.eval_every and (epoch + 1) % args.eval_every == 0 and len(data.valid):
+                evaluate(model, data.valid, filt)
+        torch.cuda.synchronize()
+        print('trained {} epochs in {:.2f} s'.format(args.train_times, time.time() - t0))
+        model.save_checkpoint(args.checkpoint)
+    model.load_checkpoint(args.checkpoint)
+    model = model.to(dev)
+    return evaluate(model, data.test, filt)
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

@@ -580,6 +580,41 @@ int gv_ec_head_bwd(const float* p, const int64_t* labels, const int32_t* row_pos
                    const float* grad_p, int64_t n, int c, float* dh, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TransE baseline (baselines/transe: OpenKE's TransE, MarginLoss, NegativeSampling; transe.py states the rules).
+ *   gv_transe_sample : batch positives drawn uniformly from train (int32 (n_train, 3)) and neg_ent negatives each, OpenKE's layout
+ *     (positives, then neg_ent blocks of batch), Philox keyed by rng_state {seed, tick} (device).  p_head [num_rels] (NULL: always the
+ *     tail) is the Bernoulli head share; f_lo / f_hi [2 n_train] (NULL: no filter) are the FilterIndex(train) runs of each training
+ *     triple, slot 2i the known tails of (h, r) in f_ent_o, slot 2i + 1 the known heads of (t, r) in f_ent_s.  draws (optional,
+ *     [batch, neg_ent + 2] uint32): the raw words (triple, coin, one per negative).
+ *   gv_transe_step : every row scored ||n(h) + n(r) - n(t)||_p; hinge max(p - n, -margin) (adv_temperature > 0: self-adversarial
+ *     weights), + regul_rate * regularisation; writes one gradient row per occurrence, g_ent [(2 + neg_ent) batch, dim] (h of b, t of
+ *     b, the corrupted side of negative (j, b) at 2 batch + j batch + b), g_rel [batch, dim], loss_part [batch] (loss = sum + margin)
+ *     and, optionally, score [batch (1 + neg_ent)] and occ_ent [(2 + neg_ent) batch], the entity id of each g_ent row.
+ *   gv_transe_apply : p += -lr * (sum of the row's occurrence gradients in perm order) for every row with occurrences (gv_build_csr
+ *     orderings of the occurrence ids: perm_*, rowptr_*); *loss_out = sum(loss_part) + margin, *epoch_acc (optional, double) += it.
+ *   gv_transe_queries : q[i] = n(ent[a[i]]) + n(rel[r[i]]) (head = 0) or n(ent[a[i]]) - n(rel[r[i]]) (head = 1); rel == NULL:
+ *     q[i] = n(ent[i]) (the normalised table).  n = F.normalize (eps 1e-12) when norm_flag, the identity otherwise.
+ *   gv_transe_distances : out [m, v] = ||q[i] - en[j]||_p, columns summed in order.
+ *   gv_transe_rank_filtered : counts_raw[i] = 2 #{j != target: !(d_j >= d_target)} + #{j != target: d_j == d_target}; counts_filt
+ *     the same over the j not in f_ent[f_lo[i], f_hi[i]) (NULL: no filter).  Distances are gv_transe_distances' bits. */
+#define GV_TRANSE_MAX_DIM 512
+int gv_transe_sample(const uint64_t* rng_state, uint32_t stream_id, const int32_t* train, int64_t n_train, int n_ent,
+                     const float* p_head, const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent_o, const int32_t* f_ent_s,
+                     int batch, int neg_ent, int32_t* bh, int32_t* br, int32_t* bt, uint32_t* draws, void* stream);
+int gv_transe_step(const float* ent, const float* rel, const int32_t* bh, const int32_t* br, const int32_t* bt, int batch, int neg_ent,
+                   int dim, int p_norm, int norm_flag, float margin, float adv_temperature, float regul_rate, float* g_ent,
+                   float* g_rel, float* loss_part, float* score, int32_t* occ_ent, void* stream);
+int gv_transe_apply(float* ent, int n_ent, const float* g_ent, const int32_t* perm_e, const int32_t* rowptr_e, float* rel, int n_rel,
+                    const float* g_rel, const int32_t* perm_r, const int32_t* rowptr_r, int dim, float lr, const float* loss_part,
+                    int batch, float margin, float* loss_out, double* epoch_acc, void* stream);
+int gv_transe_queries(const float* ent, const float* rel, const int32_t* a, const int32_t* r, int64_t m, int dim, int head,
+                      int norm_flag, float* q, void* stream);
+int gv_transe_distances(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, float* out, void* stream);
+int gv_transe_rank_filtered(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
+                            const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, int32_t* counts_raw, int32_t* counts_filt,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.
  * Replaces x@loop_weight (DGL RelGraphConv self loop), MaskedLinear (kgvae/flow_network.py:14-15)

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""TransE at FB15k-237-synthetic size with baselines/transe/main.py's hyperparameters (dim 200, L1, norm_flag, margin 5,
+nbatches 100, neg_ent 25, bern, filter, SGD alpha 1): µs per training step eager and graph-replayed, an epoch of 100 steps,
+raw + filtered evaluation of the test split, and the same for the plain-torch formulation of the reference on the same GPU
+(autograd + torch.optim.SGD on the fused sampler's batches; materialised distances + sort_and_rank).  Each case runs in a child
+process under a time limit and stops the bench at its first failure.
+
+    python tools/transe_bench.py [--steps 200] [--warmup 20] [--limit 600]
+
+Step bytes: algorithmic, counting the gathered rows (3 per positive + 1 per negative), the occurrence gradients written and read,
+and the touched table rows read and written once, against 8 TB/s.  Scorer: |a - b| terms at ~1.5 VALU instructions each against
+the 157 TFLOP/s fp32 vector rate (an estimate of the floor; the fraction reported is floor / measured)."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM, VALU = 8e12, 157e12
+
+
+def setup():
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.data import load_data
+    data = load_data('FB15k-237-synthetic')
+    torch.manual_seed(0)
+    model = transe.TransE(data.num_nodes, data.num_rels, dim=200, p_norm=1, norm_flag=True).cuda()
+    return data, model
+
+
+def timed(fn, n, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(n):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / n * 1e3      # us
+
+
+def case_step(steps, warmup):
+    from gcn_vae_amd import transe
+    data, model = setup()
+    tr = transe.DeviceTrainer(model, data.train, 100, 25, True, True, 5.0, 1.0)
+    eager = timed(tr.step, steps, warmup)
+    tr.capture()
+    graph = timed(tr.step, steps, warmup)
+    t0 = time.time()
+    loss = tr.epoch()
+    epoch_ms = (time.time() - t0) * 1e3
+    B, K, dim = tr.batch, 25, 200
+    rows = B * (3 + K)                                    # gathered rows
+    occ = (2 + K) * B + B                                 # gradient rows written, then read
+    touched = min(data.num_nodes, (2 + K) * B) + min(data.num_rels, B)
+    nbytes = 4 * dim * (rows + 2 * occ + 2 * touched)
+    return dict(step_eager_us=eager, step_graph_us=graph, epoch_ms=epoch_ms, epoch_loss=loss, batch=B,
+                step_bytes=nbytes, step_hbm_floor_us=nbytes / HBM * 1e6, hbm_fraction_graph=nbytes / HBM * 1e6 / graph)
+
+
+def case_eval(steps, warmup):
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.ranking import FilterIndex
+    data, model = setup()
+    fi = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device='cuda')
+    test = torch.as_tensor(np.asarray(data.test), dtype=torch.long)
+    ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+    fn = lambda: transe.rank_transe(ent, rel, test, 1, True, fi)  # noqa: E731
+    us = timed(fn, 3, 1)
+    terms = 2 * len(test) * data.num_nodes * 200
+    floor_us = terms * 1.5 / VALU * 1e6
+    out = transe.evaluate(model, test, fi, verbose=False)
+    return dict(eval_ms=us / 1e3, terms=terms, valu_floor_ms_estimate=floor_us / 1e3, valu_fraction=floor_us / us,
+                mrr_raw=out['mrr_raw'], mrr_filtered=out['mrr_filtered'])
+
+
+def case_torch_step(steps, warmup):
+    from gcn_vae_amd import transe
+    data, model = setup()
+    tr = transe.DeviceTrainer(model, data.train, 100, 25, True, True, 5.0, 1.0)
+    ns = transe.NegativeSampling(model, transe.MarginLoss(margin=5.0), batch_size=tr.batch).cuda()
+    opt = torch.optim.SGD(ns.parameters(), lr=1.0)
+    from gcn_vae_amd import ops
+
+    def step():
+        tr.rng.tick()
+        ops.transe_sample(tr.rng.state, tr.stream_id, tr.train, model.ent_tot, tr.batch, 25, tr.p_head, tr.filt, tr.bh, tr.br, tr.bt)
+        opt.zero_grad()
+        loss = ns({'batch_h': tr.bh.long(), 'batch_t': tr.bt.long(), 'batch_r': tr.br.long(), 'mode': 'normal'})
+        loss.backward()
+        opt.step()
+    return dict(torch_step_us=timed(step, min(steps, 100), warmup))
+
+
+def case_torch_eval(steps, warmup):
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.ranking import FilterIndex
+    data, model = setup()
+    fi = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device='cuda')
+    test = torch.as_tensor(np.asarray(data.test), dtype=torch.long)
+    ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+    us = timed(lambda: transe.rank_transe_unfused(ent, rel, test, 1, True, fi), 1, 0)
+    return dict(torch_eval_ms=us / 1e3)
+
+
+CASES = {'step': case_step, 'eval': case_eval, 'torch_step': case_torch_step, 'torch_eval': case_torch_eval}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--limit', type=int, default=600)
+    ap.add_argument('--case', default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.case:
+        print('RESULT ' + json.dumps(CASES[a.case](a.steps, a.warmup)))
+        return
+    res = {}
+    for name in CASES:
+        r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__), '--case', name,
+                            '--steps', str(a.steps), '--warmup', str(a.warmup)], capture_output=True, text=True, cwd=ROOT)
+        line = [x for x in r.stdout.splitlines() if x.startswith('RESULT ')]
+        if r.returncode != 0 or not line:
+            res[name] = dict(failed=r.returncode, tail=(r.stdout + r.stderr)[-1500:])
+            print(json.dumps(res[name]), file=sys.stderr)
+            break
+        res[name] = json.loads(line[0][7:])
+        print(name, json.dumps(res[name]), flush=True)
+    print(json.dumps(res))
+    sys.exit(1 if any('failed' in v for v in res.values()) else 0)
+
+
+if __name__ == '__main__':
+    main()
