@@ -7,6 +7,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--scaling strong|weak]
     python bench.py --config mb [--n-flows 3]          (the reference's mini-batch regime, one GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full      (the same line plus cpu_baseline, parity_check and roofline)
+
+A plain run does what its headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds
+what is measured or checked beside it: the CPU-oracle baseline and the parity leg (one HIP step held to the oracle's) before
+the timed steps, the instrumented eager steps of the roofline figures after them.
 
 Workloads (BASELINE.json configs, all seeded synthetics -- no dataset on disk, no network):
   c2 (default, configs[1]) FB15k-237-shaped: 14 541 entities, 237 relations = 474 directed edge types, 272 115 triplets
@@ -92,7 +97,10 @@ def parse():
     p.add_argument('--n-flows', type=int, default=None)
     p.add_argument('--gemm-precision', choices=['f32', 'bf16'], default=None,
                    help="bf16: dense products with bf16 operands / fp32 accumulation (configs[2]'s precision)")
-    p.add_argument('--no-check', action='store_true', help='skip the parity leg (one HIP step against the CPU oracle)')
+    p.add_argument('--full', action='store_true',
+                   help='also run the legs the headline does not need: CPU-oracle baseline + parity leg before the timed steps '
+                        '(one GPU), instrumented roofline steps after them; the options whose help starts with "--full:" refine these legs')
+    p.add_argument('--no-check', action='store_true', help='--full: skip the parity leg (one HIP step against the CPU oracle)')
     p.add_argument('--positives', type=int, default=20000)
     p.add_argument('--negative-sample', type=int, default=10)
     p.add_argument('--dropout', type=float, default=0.2)
@@ -102,12 +110,13 @@ def parse():
                         'hipGraph segments with the collectives launched eagerly between them)')
     p.add_argument('--no-segments', action='store_true',
                    help='world size > 1: launch every kernel eagerly instead of replaying hipGraph segments')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU-oracle baseline leg (and with it the parity leg)')
     p.add_argument('--rewarm-seconds', type=float, default=0.5,
-                   help='untimed steps for this long behind the CPU-baseline leg, in front of the --warmup steps (the GPU clocks drop while '
-                        'the CPU works; 0: none)')
+                   help='one GPU: untimed steps for this long in front of the --warmup steps, plain or --full (the GPU clocks drop '
+                        'while the CPU baseline of --full works; 0: none)')
     p.add_argument('--cpu-seconds', type=float, default=90.0,
-                   help='budget of the CPU-oracle baseline leg (the default covers 3 warm-up + 20 timed oracle steps of the default workload)')
+                   help='--full: budget of the CPU-oracle baseline leg (the default covers 3 warm-up + 20 timed oracle steps of the '
+                        'default workload)')
     p.add_argument('--force-dist', action='store_true', help='run the RCCL code path even at world size 1 (testing)')
     p.add_argument('--partition', choices=['auto', 'edge', 'row'], default='auto',
                    help='world size > 1: "edge" = edge-block sharding + all-reduce of node embeddings (north_star), "row" = '
@@ -117,7 +126,7 @@ def parse():
                    help='world size > 1: distributed.ShardedFlatAdam -- reduce-scatter of the gradient arena, clip + Adam on 1/N of '
                         'it per rank, all-gather of the updated parameters -- instead of the all-reduce + replicated update')
     p.add_argument('--probe-steps', type=int, default=10)
-    p.add_argument('--profile-steps', type=int, default=3, help='instrumented eager steps for the roofline figure')
+    p.add_argument('--profile-steps', type=int, default=3, help='--full: instrumented eager steps for the roofline figure')
     args = p.parse_args()
     if args.steps < 1:
         p.error('--steps must be at least 1')
@@ -479,10 +488,12 @@ def k4_records(ms, _ops):
 
 
 def rewarm(step_fn, seconds):
-    """Untimed steps for ``seconds`` of wall time (at most 500) BEFORE the contract's W warm-up steps: the CPU-oracle leg keeps the
-    GPU idle for ~25 s, its clocks drop, and W = 5 steps of a 1 ms step (5 ms) do not bring them back -- the first timed region of
-    the mini-batch configuration read 4.5 ms per step against 0.99 in the regions after it.  The weights are put back from the
-    snapshot before every timed region, so these steps leave no trace in what is timed."""
+    """Untimed steps for ``seconds`` of wall time (at most 500) BEFORE the contract's W warm-up steps: the CPU-oracle leg of --full
+    keeps the GPU idle for ~25 s, its clocks drop, and W = 5 steps of a 1 ms step (5 ms) do not bring them back -- the first timed
+    region of the mini-batch configuration read 4.5 ms per step against 0.99 in the regions after it.  A plain run takes these
+    steps as well: its timed steps then start from the same warm GPU as a --full run's.  Single-rank runs only (a time-bounded
+    loop would give the ranks different step counts, and the steps hold collectives).  The weights are put back from the snapshot
+    before every timed region, so these steps leave no trace in what is timed."""
     if seconds <= 0:
         return
     torch.cuda.synchronize()
@@ -698,7 +709,7 @@ def run_minibatch(args):
         for _ in range(3):
             step()
     cpu_rec = parity_rec = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # one batch of the synchronising sampler, BEFORE the timed steps (weights a few updates from their initialisation): the
         # oracle's step on it (reported baseline) and the HIP step held to it
         b = sm.sample(k, split, neg)
@@ -710,7 +721,7 @@ def run_minibatch(args):
             inputs = dict(g=b.g, node_id=b.node_id, etype=b.edge_type, enorm=b.edge_norm, samples=b.samples, labels=b.labels)
             parity_rec = parity_check(model, opt, inputs, ref, dev, args.gemm_precision == 'bf16')
     snap = opt.snapshot()          # every timed region starts from these weights and moments (see main())
-    rewarm(step, args.rewarm_seconds if (cpu_rec is not None) else 0.0)
+    rewarm(step, args.rewarm_seconds)
     for _ in range(args.warmup):
         out = step()
     regions = []
@@ -728,7 +739,7 @@ def run_minibatch(args):
     T = k * (neg + 1)
     # ---- K1 launch times of the same step, eager, HIP events (launch-latency regime: reported, not a roofline claim) ------
     detail, k4 = {}, {}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         opt.restore(snap)
         lib.TIMER = lib.KernelTimer()
         for _ in range(args.profile_steps):
@@ -1089,13 +1100,13 @@ def _main():
             return static_loss
         return step_body()
 
-    # The CPU oracle's step on this workload (the reported baseline) and the parity leg -- the HIP step held to it -- come BEFORE
-    # the timed steps: the weights are then a few updates from their initialisation.  (With IAF blocks a hundred more updates at
-    # lr 1e-3 let exp(alpha + mu) overflow in fp32 on these synthetic graphs -- in the oracle exactly as in the product; the
+    # --full: the CPU oracle's step on this workload (the reported baseline) and the parity leg -- the HIP step held to it -- come
+    # BEFORE the timed steps: the weights are then a few updates from their initialisation.  (With IAF blocks a hundred more updates
+    # at lr 1e-3 let exp(alpha + mu) overflow in fp32 on these synthetic graphs -- in the oracle exactly as in the product; the
     # reference, which switches torch's anomaly mode on globally, would stop there.)
     cpu_rec = parity_rec = None
     k1_bf = k1_bf16_mode(w, args, dev) if (rank == 0 and world == 1) else False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_rec, ref = cpu_baseline(w, model, args, args.cpu_seconds, k1_bf16=k1_bf)
         if not args.no_check:      # the timed workload, checked at its own size against the oracle (raises on failure)
             parity_rec = parity_check(model, opt, modes['edge'], ref, dev, args.gemm_precision == 'bf16')
@@ -1108,8 +1119,13 @@ def _main():
     # ... and from the same random state: the device RNG's {seed, tick} and the host draw of the MMD rows, which the
     # time-bounded rewarm would otherwise leave at a different point in every run
     rng = _ops.device_rng(dev)
+    if parity_rec is None and world == 1 and not (args.no_cpu_baseline or args.no_check):
+        # the parity leg's HIP step advances the device RNG by one tick (the start-of-forward tick of its embedding lookup; every
+        # draw of that step is overridden): a run without the leg takes the tick here, so that its timed regions draw the same
+        # dropout masks and noise as a --full run's
+        rng.tick()
     rng_snap, pick_snap = rng.state.clone(), pick_rng.getstate()
-    rewarm(run_step, args.rewarm_seconds if (cpu_rec is not None) else 0.0)
+    rewarm(run_step, args.rewarm_seconds if world == 1 else 0.0)
     for _ in range(args.warmup):
         loss = run_step()
     # EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks, --repeats times (every region starts
@@ -1156,10 +1172,10 @@ def _main():
         dumped = dump_outputs(args.dump_outputs, outs)
 
     phase('roofline leg (instrumented eager steps)')
-    # ---- roofline leg: the same step, eager, with HIP events around the K1 launches --------------
+    # ---- roofline leg (--full): the same step, eager, with HIP events around the K1 launches --------------
     roofline, detail, k4 = None, {}, {}
     per_rank_k1 = None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         opt.restore(snap)
         # every rank runs the instrumented steps (the collectives need all of them); each grades its OWN launches against
         # its OWN edge count, rank 0's detail goes into the line and all ranks' K1 GB/s into `k1_GBs_per_rank`

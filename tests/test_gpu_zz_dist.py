@@ -139,13 +139,13 @@ def test_bench_two_ranks_strong_scaling_one_graph(extra):
 def test_bench_starts_its_own_ranks_strong_scaling_by_default():
     """`python bench.py --gpus 2` with NO launcher (what the driver's contract line may be run as): bench.py starts the two
     ranks itself as a child torch.distributed.run job before touching the GPU, relays rank 0's JSON line and its exit code.
-    Defaults: ONE graph cut across the ranks (strong scaling), both schemes probed, K1 rates of every rank in the line;
-    with --repeats 3, three timed regions with their median.  (gloo: the two ranks share the box's one GPU.)"""
+    Defaults: ONE graph cut across the ranks (strong scaling), both schemes probed; with --full, K1 rates of every rank in the
+    line; with --repeats 3, three timed regions with their median.  (gloo: the two ranks share the box's one GPU.)"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', GV_DIST_BACKEND='gloo')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-           '--profile-steps', '2', '--positives', '2000', '--probe-steps', '2', '--repeats', '3']
+           '--full', '--profile-steps', '2', '--positives', '2000', '--probe-steps', '2', '--repeats', '3']
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:] + '\n' + out.stderr[-2500:])
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/r4
 # (c5: one oracle step on 50 M edges takes minutes on the host: no CPU leg; its parity is tests/test_gpu_configs.py)
 if [ "$what" = benches ] || [ "$what" = all ] || [ "$what" = c5 ]; then
 for spec in "c2:" "c3:--config c3" "mb:--config mb" "mb_flows3:--config mb --n-flows 3" "mb_flows3_bf16:--config mb --n-flows 3 --gemm-precision bf16" "c2_flows3_bf16:--n-flows 3 --gemm-precision bf16" "c4:--config c4" "c5:--config c5 --steps 5 --warmup 2 --no-cpu-baseline --no-check"; do
-  tag=${spec%%:*}; flags=${spec#*:}
+  tag=${spec%%:*}; flags="--full ${spec#*:}"
   if [ "$what" = c5 ] && [ "$tag" != c5 ]; then continue; fi
   echo "== bench $tag"; date +%T
   case "$flags" in *--steps*) st="";; *) st="--steps 20 --warmup 5";; esac

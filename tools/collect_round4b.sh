@@ -4,7 +4,7 @@
 set -e -o pipefail
 mkdir -p gpurun_out/r4b
 for spec in "c3:--config c3" "mb_flows3_bf16:--config mb --n-flows 3 --gemm-precision bf16" "c2_flows3_bf16:--n-flows 3 --gemm-precision bf16"; do
-  tag=${spec%%:*}; flags=${spec#*:}
+  tag=${spec%%:*}; flags="--full ${spec#*:}"
   echo "== bench $tag"; date +%T
   timeout -k 10 700 python bench.py $flags --steps 20 --warmup 5 > gpurun_out/r4b/bench_$tag.json 2> gpurun_out/r4b/bench_$tag.err || echo "rc=$? for $tag"
 done

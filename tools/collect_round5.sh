@@ -11,7 +11,7 @@ common="--no-cpu-baseline --no-check --profile-steps 0"
 steps="--steps 10 --warmup 3"; psteps="--steps 3 --warmup 2"
 if [ "$c" = c5 ]; then steps="--steps 3 --warmup 1"; psteps="--steps 2 --warmup 1"; fi
 echo "== $c: bench line"; date +%T
-timeout -k 10 900 python bench.py --config $c "$@" > "$out/bench_$c.json" 2> "$out/bench_$c.err" || echo "bench rc=$?"
+timeout -k 10 900 python bench.py --full --config $c "$@" > "$out/bench_$c.json" 2> "$out/bench_$c.err" || echo "bench rc=$?"
 for mode in instep serial; do
   echo "== $c: kernel trace ($mode)"; date +%T
   rm -rf /tmp/pp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the bench lines of the secondary regimes (mini-batch, flows, bf16): tools/collect_round5_lines.sh  -> gpurun_out/r5/bench_<tag>.json
 out=$PWD/gpurun_out/r5; mkdir -p "$out"
-run() { tag=$1; shift; echo "== $tag"; timeout -k 10 600 python bench.py "$@" > "$out/bench_$tag.json" 2> "$out/bench_$tag.err" || echo "bench $tag rc=$?"; }
+run() { tag=$1; shift; echo "== $tag"; timeout -k 10 600 python bench.py --full "$@" > "$out/bench_$tag.json" 2> "$out/bench_$tag.err" || echo "bench $tag rc=$?"; }
 run mb --config mb
 run mb_flows3 --config mb --n-flows 3
 run mb_flows3_bf16 --config mb --n-flows 3 --gemm-precision bf16

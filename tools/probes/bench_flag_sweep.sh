@@ -12,12 +12,12 @@ except Exception as e:
     print(tag, 'rc', rc, 'ERR', open(f'/tmp/e_{tag}.log').read()[-500:].replace('\n',' | '))
 PY
 }
-run c2f3 --n-flows 3
-run c2bf16 --gemm-precision bf16
-run c2f1bf16 --n-flows 1 --gemm-precision bf16
-run c4f3 --config c4 --n-flows 3
-run c4f3bf16 --config c4 --n-flows 3 --gemm-precision bf16
-run h100 --hidden 100
-run nograph --no-graph
-run mbf3 --config mb --n-flows 3
-run c3f32 --config c3 --gemm-precision f32
+run c2f3 --n-flows 3 --full
+run c2bf16 --gemm-precision bf16 --full
+run c2f1bf16 --n-flows 1 --gemm-precision bf16 --full
+run c4f3 --config c4 --n-flows 3 --full
+run c4f3bf16 --config c4 --n-flows 3 --gemm-precision bf16 --full
+run h100 --hidden 100 --full
+run nograph --no-graph --full
+run mbf3 --config mb --n-flows 3 --full
+run c3f32 --config c3 --gemm-precision f32 --full
