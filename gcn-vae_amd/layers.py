@@ -127,40 +127,36 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
             late_keep, keep = keep, None
         else:
             late_keep = None
+        keep_scale = scale if keep is not None else 1.0
         if int_ids:
             # integer-id features (kgvae/entity_classify.py:25-34, :63: features = arange(num_nodes) into a basis layer
             # with in_feat = num_nodes): a message is a ROW of the relation's matrix (DGL bmm_maybe_select), the
             # self-loop term a row of loop_weight (matmul_maybe_select)
             if self.reduce_hook is not None:
                 raise NotImplementedError('integer-id features are not wired into the multi-GPU edge sharding')
-            if not (self.fused_basis_select and self.num_bases < self.num_rels):
-                ops.check_select_weight_size(self.num_rels, self.in_feat, self.out_feat)     # before W is formed
             if self.fused_basis_select and self.num_bases < self.num_rels:
                 h = ops.rel_graph_conv_basis_select(x, self.weight, self.w_comp, h_bias, loop_w, norm, gidx, ridx, act_id, keep,
-                                                    scale if keep is not None else 1.0)
-                if post_act is not None:
-                    h = post_act(h)
-                    if late_keep is not None:
-                        h = h * (late_keep.to(h.dtype) * scale)
-                return h
-            flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)
-            weight = ops.matmul(self.w_comp, flat) if self.num_bases < self.num_rels else flat
-            h = ops.rel_graph_conv_select(x, weight.view(self.num_rels, self.in_feat, self.out_feat), h_bias, loop_w, norm,
-                                          gidx, ridx, act_id, keep, scale if keep is not None else 1.0)
+                                                    keep_scale)
+            else:
+                ops.check_select_weight_size(self.num_rels, self.in_feat, self.out_feat)     # before W is formed
+                flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)
+                weight = ops.matmul(self.w_comp, flat) if self.num_bases < self.num_rels else flat
+                h = ops.rel_graph_conv_select(x, weight.view(self.num_rels, self.in_feat, self.out_feat), h_bias, loop_w, norm,
+                                              gidx, ridx, act_id, keep, keep_scale)
         elif self.regularizer == 'bdd':
             h = ops.rel_graph_conv_bdd(x, self.weight, h_bias, loop_w, norm, gidx, ridx, self.num_bases, act_id, keep,
-                                       scale if keep is not None else 1.0, self.reduce_hook)
+                                       keep_scale, self.reduce_hook)
         else:
             # basis: W_r = sum_b w_comp[r, b] V_b (one MFMA GEMM), then a full (in x out) matrix per relation
             flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)
             weight = ops.matmul(self.w_comp, flat) if self.num_bases < self.num_rels else flat
             if self.reduce_hook is not None or os.environ.get('GV_BASIS_GENERIC', '0') == '1':
                 # edge-sharded multi-GPU hook / cross-check: the generic K1 kernels (one dense "block" per relation)
-                h = ops.rel_graph_conv_bdd(x, weight, h_bias, loop_w, norm, gidx, ridx, 1, act_id, keep,
-                                           scale if keep is not None else 1.0, self.reduce_hook)
+                h = ops.rel_graph_conv_bdd(x, weight, h_bias, loop_w, norm, gidx, ridx, 1, act_id, keep, keep_scale,
+                                           self.reduce_hook)
             else:
                 h = ops.rel_graph_conv_dense(x, weight.view(self.num_rels, self.in_feat, self.out_feat), h_bias, loop_w, norm,
-                                             gidx, ridx, act_id, keep, scale if keep is not None else 1.0)
+                                             gidx, ridx, act_id, keep, keep_scale)
         if post_act is not None:
             h = post_act(h)
             if late_keep is not None:

@@ -982,6 +982,146 @@ def embedding(table, ids, tick_rng=None, sole_consumer=False):
     return _Embedding.apply(table, ids, tick_rng)      # a real copy, as nn.Embedding returns
 
 
+# ---- the R-GCN layers' shared pieces: epilogue gradient, self-loop + bias addend, loop-weight and relation-weight gradients,
+# the edge norm in a launch's order, the packed bdd weights and the K1 choice of _RelGraphConvBdd
+def _epilogue_grad(out, grad_out, act, keep, keep_scale, want_bias, d_b):
+    """(g, grad_bias): g = dL/d(pre-epilogue rows); with ``want_bias`` the same pass yields the bias gradient (the column sums of
+    g), added into the optimiser's arena when the bias has a direct target ``d_b`` (grad_bias is then None)."""
+    if not want_bias:
+        return epilogue_bwd(out, grad_out, act, keep, keep_scale), None
+    grad_bias = d_b if d_b is not None else torch.empty(grad_out.shape[1], dtype=torch.float32, device=grad_out.device)
+    g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
+    return g, (None if d_b is not None else grad_bias)
+
+
+def _gemm_addend(x, loop_weight, h_bias, out_feat, loop_bf=None):
+    """The forward epilogue's addend: x @ loop_weight + h_bias (on the bf16 dense forms ``loop_bf`` when the caller has them),
+    h_bias broadcast to x's rows without a self loop, or None."""
+    if loop_weight is not None and loop_bf is not None:
+        return dense_bf16(x, loop_bf[0], loop_weight.shape[1], loop_weight.shape[0], bias=h_bias)
+    if loop_weight is not None:
+        return gemm(x, loop_weight, bias=h_bias)
+    if h_bias is not None:
+        return h_bias.unsqueeze(0).expand(x.shape[0], out_feat).contiguous()
+    return None
+
+
+def _row_addend(h_bias, loop_rows, n, out_feat):
+    """The addend of the integer-id layers: h_bias broadcast to n rows plus the gathered self-loop rows, or either alone, or None."""
+    if h_bias is None:
+        return loop_rows
+    addend = h_bias.unsqueeze(0).expand(n, out_feat).contiguous()
+    if loop_rows is not None:
+        lib.call('gv_axpby', addend.numel(), None, 1.0, ptr(loop_rows), 1.0, ptr(addend), lib.stream())
+    return addend
+
+
+def _loop_grads(x, g, loop_weight, d_l, want_loop, want_x, loop_bf=None):
+    """(grad_loop, gx_loop) of the self-loop term x @ loop_weight: the loop weight's gradient x^T g (added into its direct target
+    ``d_l`` when there is one, grad_loop then None) and g @ loop_weight^T (on the bf16 form of ``loop_bf`` when given)."""
+    if loop_weight is None:
+        return None, None
+    grad_loop = gx_loop = None
+    if want_loop:
+        grad_loop = gemm(x, g, trans_a=True, split_k=pick_split_k(x.shape[1], g.shape[1], x.shape[0]), out=d_l,
+                         accumulate=d_l is not None)
+        if d_l is not None:
+            grad_loop = None
+    if want_x:
+        if loop_bf is not None:
+            gx_loop = dense_bf16(g, loop_bf[1], loop_weight.shape[0], loop_weight.shape[1])
+        else:
+            gx_loop = gemm(g, loop_weight, trans_b=True)
+    return grad_loop, gx_loop
+
+
+def _coef_order(gidx, ridx, coef, side):
+    """(coef, coef_idx) of a launch over the by-source ('src') or by-relation ('rel') edge order: on static graphs the edge norm
+    cached in that order, read directly; on graphs indexed sync-free (rebuilt per batch) the norm read through the permutation."""
+    if gidx.sync_free or coef is None:
+        return coef, (gidx.by_src.perm if side == 'src' else ridx.by_rel.perm)
+    return (gidx.coef_in_src_order(coef) if side == 'src' else ridx.coef_in_rel_order(coef)), None
+
+
+def _relation_weight_grad(gidx, ridx, coef, x, g, nb, si, so, d_w):
+    """dL/dW of the bdd relation weights (added into the direct target ``d_w`` when there is one: None is returned then)."""
+    coef_r, idx_r = _coef_order(gidx, ridx, coef, 'rel')
+    grad_w = bdd_grad_weight(ridx.by_rel.seg, ridx.src_by_rel, ridx.dst_by_rel, coef_r, idx_r, x, g, nb, si, so, out=d_w,
+                             accumulate=d_w is not None)
+    return None if d_w is not None else grad_w
+
+
+def _bdd_weight_fwd(ctx, weight, nb, si, so, pk, pk_bwd):
+    """The forward K1 launch's weight operand (lane-packed with ``pk``).  When the backward-x launch packs too (``pk_bwd``) one
+    launch writes both layouts and the backward's copy is kept on ctx for _bdd_weight_bwd."""
+    ctx.w_bwd_packed = None
+    ctx.w_version = weight._version
+    if pk and pk_bwd:
+        w_fwd, ctx.w_bwd_packed = torch.empty_like(weight), torch.empty_like(weight)
+        lib.call('gv_rgcn_bdd_pack_weight_pair', ptr(weight), weight.shape[0], nb, si, so, ptr(w_fwd), ptr(ctx.w_bwd_packed),
+                 lib.stream())
+        return w_fwd
+    return pack_weight(weight, nb, si, so, False) if pk else weight
+
+
+def _bdd_weight_bwd(ctx, weight, nb, so, si):
+    """(weight operand, packed) of the backward-x per-row launch: the forward's copy while the weight is unchanged, else packed here."""
+    pk = si * so >= 8 and pack_supported(nb, so, si, True)
+    if ctx.w_bwd_packed is not None and weight._version == ctx.w_version:
+        return ctx.w_bwd_packed, pk
+    return (pack_weight(weight, nb, so, si, True) if pk else weight), pk
+
+
+def _bdd_k1(ctx, side, tl, gidx, ridx, coef, feat, weight, nb, bi, bo, plain_weight, addend, act=ACT_NONE, keep=None,
+            keep_scale=1.0, out=None, sharded=False):
+    """The K1 launch of _RelGraphConvBdd over one ordering: 'dst' = the forward (``bi`` x ``bo`` = si x so blocks), 'src' = the
+    backward w.r.t. x (so x si, transposed).  Precedence: relation phases (``tl``, the caller's PhaseOrder or None) > relation
+    groups (decided in the forward: ctx.grouped) > LDS-resident > relation runs > plain.  ``sharded``: the edge-sharded backward,
+    which takes the plain kernel (the forward's chunk loop stays with the forward).  ``plain_weight()`` gives the per-row kernels'
+    (weight, packed); ``addend()`` is called after any weight packing, in front of the launch.  The forward records the LDS
+    launch's operand precision on ctx.k1_bf for its backward."""
+    trans, r = side == 'src', weight.shape[0]
+    if tl is not None:
+        return bdd_aggregate_phases(tl, None if coef is None else tl.coef(coef), feat, pack_weight_phase(tl, weight, nb, bi, bo),
+                                    r, nb, bi, bo, addend(), act, keep, keep_scale, out=out)
+    seg = gidx.by_src.seg if trans else gidx.by_dst.seg
+    nbr, ety = (gidx.nbr_by_src, ridx.et_by_src) if trans else (gidx.nbr_by_dst, ridx.et_by_dst)
+
+    def coef_operands():
+        # the LDS and plain launches read the norm differently by direction: the forward in the caller's edge order through
+        # by_dst.perm; the backward, on static graphs, from the copy cached in by-source order
+        return _coef_order(gidx, ridx, coef, 'src') if trans else (coef, gidx.by_dst.perm)
+    # relation groups are decided once, in the forward (ctx.grouped), and the backward follows that decision; the backward asks
+    # for the LDS plan at the operand precision its forward chose (ctx.k1_bf), not at the current GEMM precision
+    lp = None if (ctx.grouped or sharded) else lds_plan(r, nb, bi, bo, bf=ctx.k1_bf if trans else None)
+    if lp is not None and lds_graph(gidx, side, lp[2]):       # few relation types: the whole table resident in LDS (csrc/k_lds.hip)
+        if not trans:
+            ctx.k1_bf = bool(lp[3])
+            if not torch.cuda.is_current_stream_capturing():
+                # the backward-x launch's list too, while a host read-back is still allowed: a step captured after this eager forward
+                # (a no-grad evaluation pass in front of the training capture) must not find it missing
+                lp_b = lds_plan(r, nb, bo, bi, bf=ctx.k1_bf)
+                if lp_b is not None:
+                    gidx.lds_order('src', lp_b[2])
+        c, c_idx = coef_operands()
+        return bdd_aggregate_lds(gidx.lds_order(side, lp[2]), nbr, ety, c, c_idx, feat,
+                                 pack_weight_lds(weight, nb, bi, bo, trans, lp), r, nb, bi, bo, trans, addend(), act, keep,
+                                 keep_scale, out=out, plan=lp)
+    w, pk = plain_weight()
+    if ctx.grouped:
+        seg_g, nbr_g, ety_g, perm = ridx.grouped_order(gidx, side)
+        coef_g = None if coef is None else ridx.grouped_coef(coef, side, perm)
+        return bdd_aggregate(seg_g, nbr_g, ety_g, coef_g, None, feat, w, nb, bi, bo, trans, addend(), act, keep, keep_scale,
+                             out=out, packed=pk)
+    if K1_REL_RUNS and not gidx.sync_free and not sharded:
+        nbr_r, et_r, _, coef_r = ridx.rel_sorted(gidx, side, coef)      # rows sorted by relation: weight reuse along runs
+        return bdd_aggregate(_k1_items(gidx, seg), nbr_r, et_r, coef_r, None, feat, w, nb, bi, bo, trans, addend(), act, keep,
+                             keep_scale, out=out, packed=pk)
+    c, c_idx = coef_operands()
+    return bdd_aggregate(_k1_items(gidx, seg), nbr, ety, c, c_idx, feat, w, nb, bi, bo, trans, addend(), act, keep, keep_scale,
+                         out=out, packed=pk)
+
+
 class _RelGraphConvBdd(torch.autograd.Function):
     """out = keep*scale*act( sum_e norm_e * blockdiag(W_{r_e}) x[src_e]  + x@loop_weight + h_bias ).
 
@@ -1005,62 +1145,22 @@ class _RelGraphConvBdd(torch.autograd.Function):
         tl = None
         if reduce_hook is None and use_phases(gidx, si, so, False, x.shape[0], in_feat):
             tl = ridx.phase_order(gidx, 'dst', num_bases, si, so)
-        ctx.tiles = tl is not None
         # lane-packed weights pay off once a block's weights span >= 32 B (measured: 2x4 / 4x2 blocks -24 % / -19 %,
         # 2x2 blocks +-0): pack per launch kind, a ~1.5 MB pass per layer
-        pk = not ctx.tiles and si * so >= 8 and pack_supported(num_bases, si, so, False)
+        pk = tl is None and si * so >= 8 and pack_supported(num_bases, si, so, False)
         bwd_phases = reduce_hook is None and use_phases(gidx, so, si, True, n, out_feat)
         pk_bwd = not bwd_phases and si * so >= 8 and pack_supported(num_bases, so, si, True)
-        ctx.w_bwd_packed = None
-        if pk and pk_bwd and ctx.needs_input_grad[0]:      # one launch writes both layouts; backward-x reuses its copy
-            w_fwd, ctx.w_bwd_packed = torch.empty_like(weight), torch.empty_like(weight)
-            lib.call('gv_rgcn_bdd_pack_weight_pair', ptr(weight), weight.shape[0], num_bases, si, so, ptr(w_fwd),
-                     ptr(ctx.w_bwd_packed), lib.stream())
-        else:
-            w_fwd = pack_weight(weight, num_bases, si, so, False) if pk else weight
-
+        w_fwd = _bdd_weight_fwd(ctx, weight, num_bases, si, so, pk, pk_bwd and ctx.needs_input_grad[0])
         ctx.loop_bf = dense_bf16_forms(loop_weight) if (loop_weight is not None and x.shape[0] >= 4096) else None
 
-        def self_loop_term():
-            if loop_weight is not None and ctx.loop_bf is not None:
-                return dense_bf16(x, ctx.loop_bf[0], loop_weight.shape[1], loop_weight.shape[0], bias=h_bias)
-            if loop_weight is not None:
-                return gemm(x, loop_weight, bias=h_bias)
-            if h_bias is not None:
-                return h_bias.unsqueeze(0).expand(n, out_feat).contiguous()
-            return None
+        def addend():
+            return _gemm_addend(x, loop_weight, h_bias, out_feat, ctx.loop_bf)
 
-        ctx.grouped = not ctx.tiles and reduce_hook is None and use_relation_groups(weight, gidx)
-        lp = lds_plan(weight.shape[0], num_bases, si, so) if (not ctx.tiles and not ctx.grouped and reduce_hook is None) else None
-        if lp is not None and not lds_graph(gidx, 'dst', lp[2]):
-            lp = None
-        ctx.k1_bf = bool(lp[3]) if lp is not None else False
-        if lp is not None and not torch.cuda.is_current_stream_capturing():
-            # the backward-x launch's list too, while a host read-back is still allowed: a step captured after this eager forward
-            # (a no-grad evaluation pass in front of the training capture) must not find it missing
-            lp_b = lds_plan(weight.shape[0], num_bases, so, si, bf=ctx.k1_bf)
-            if lp_b is not None:
-                gidx.lds_order('src', lp_b[2])
-        if lp is not None:       # few relation types: the whole table resident in LDS (csrc/k_lds.hip)
-            out = bdd_aggregate_lds(gidx.lds_order('dst', lp[2]), gidx.nbr_by_dst, ridx.et_by_dst, coef, gidx.by_dst.perm, x,
-                                    pack_weight_lds(weight, num_bases, si, so, False, lp), weight.shape[0], num_bases, si, so,
-                                    False, self_loop_term(), act, keep, keep_scale, plan=lp)
-        elif ctx.tiles:
-            out = bdd_aggregate_phases(tl, None if coef is None else tl.coef(coef), x,
-                                       pack_weight_phase(tl, weight, num_bases, si, so), weight.shape[0], num_bases, si, so,
-                                       self_loop_term(), act, keep, keep_scale)
-        elif ctx.grouped:
-            seg, nbr, ety, perm = ridx.grouped_order(gidx, 'dst')
-            coef_g = None if coef is None else ridx.grouped_coef(coef, 'dst', perm)
-            out = bdd_aggregate(seg, nbr, ety, coef_g, None, x, w_fwd, num_bases, si, so, False, self_loop_term(), act, keep,
-                                keep_scale, packed=pk)
-        elif reduce_hook is None and K1_REL_RUNS and not gidx.sync_free:
-            nbr_r, et_r, eid_r, coef_r = ridx.rel_sorted(gidx, 'dst', coef)      # rows sorted by relation: weight reuse along runs
-            out = bdd_aggregate(_k1_items(gidx, gidx.by_dst.seg), nbr_r, et_r, coef_r, None, x, w_fwd,
-                                num_bases, si, so, False, self_loop_term(), act, keep, keep_scale, packed=pk)
-        elif reduce_hook is None:
-            out = bdd_aggregate(_k1_items(gidx, gidx.by_dst.seg), gidx.nbr_by_dst, ridx.et_by_dst, coef, gidx.by_dst.perm, x, w_fwd,
-                                num_bases, si, so, False, self_loop_term(), act, keep, keep_scale, packed=pk)
+        ctx.grouped = tl is None and reduce_hook is None and use_relation_groups(weight, gidx)
+        ctx.k1_bf = False
+        if reduce_hook is None:
+            out = _bdd_k1(ctx, 'dst', tl, gidx, ridx, coef, x, weight, num_bases, si, so, lambda: (w_fwd, pk), addend, act, keep,
+                          keep_scale)
         else:
             # edge-sharded: aggregate the destination rows in DIST_FWD_CHUNKS blocks; the all-reduce of block c runs
             # on RCCL's stream while block c+1 is aggregated and, at the end, under the self-loop GEMM
@@ -1070,13 +1170,12 @@ class _RelGraphConvBdd(torch.autograd.Function):
                 bdd_aggregate(sub, gidx.nbr_by_dst, ridx.et_by_dst, coef, gidx.by_dst.perm, x, w_fwd, num_bases, si, so,
                               packed=pk, out=agg)
                 pending.append(reduce_hook(agg[r0:r1]))
-            addend = self_loop_term()
+            add = addend()
             for h in pending:
                 h.wait()
-            out = epilogue_fwd(agg, addend, act, keep, keep_scale)
+            out = epilogue_fwd(agg, add, act, keep, keep_scale)
         ctx.save_for_backward(x, weight, loop_weight, coef, out if act == ACT_RELU else None, keep)
         ctx.meta = (gidx, ridx, num_bases, si, so, act, keep_scale, h_bias is not None, reduce_hook)
-        ctx.w_version = weight._version
         ctx.direct = (_direct(weight), _direct(h_bias), _direct(loop_weight))
         _stamp_direct(ctx)
         # x is the embedding table itself (identity lookup) and this layer is its only consumer: dL/dx rows go straight
@@ -1091,20 +1190,12 @@ class _RelGraphConvBdd(torch.autograd.Function):
         gidx, ridx, nb, si, so, act, keep_scale, has_bias, reduce_hook = ctx.meta
         _verify_direct(ctx)
         d_w, d_b, d_l = ctx.direct
-        grad_bias = None
-        if has_bias and ctx.needs_input_grad[2]:         # bias gradient = column sums of g, from the same pass
-            grad_bias = d_b if d_b is not None else torch.empty(grad_out.shape[1], dtype=torch.float32, device=x.device)
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
-            if d_b is not None:
-                grad_bias = None
-        else:
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
+        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
         pending = None
         g_agg = g
         if reduce_hook is not None:      # gradient of this rank's partial aggregate = sum over ranks; overlapped below
             g_agg = copy_of(g)
             pending = reduce_hook(g_agg)
-        grad_loop = gx_loop = None
         # the layer's two weight gradients (stored straight into the optimiser's arena: nothing in this backward pass reads them)
         # on the side stream, beside the dL/dx path -- where that pays (RGCN_BWD_SIDE)
         side_w = reduce_hook is None and d_l is not None and d_w is not None and loop_weight is not None \
@@ -1113,88 +1204,43 @@ class _RelGraphConvBdd(torch.autograd.Function):
             with backward_side(True, x, g, g_agg, weight, coef, rgcn=True):
                 gw_first = rgcn_side_gradw_first(gidx.num_edges, x.shape[1])
                 if not gw_first:
-                    gemm(x, g, trans_a=True, split_k=pick_split_k(x.shape[1], g.shape[1], x.shape[0]), out=d_l, accumulate=True)
-                static = not gidx.sync_free and coef is not None
-                coef_r, idx_r = (ridx.coef_in_rel_order(coef), None) if static else (coef, ridx.by_rel.perm)
-                bdd_grad_weight(ridx.by_rel.seg, ridx.src_by_rel, ridx.dst_by_rel, coef_r, idx_r, x, g_agg, nb, si, so, out=d_w, accumulate=True)
+                    _loop_grads(x, g, loop_weight, d_l, True, False)
+                _relation_weight_grad(gidx, ridx, coef, x, g_agg, nb, si, so, d_w)
                 if gw_first:
-                    gemm(x, g, trans_a=True, split_k=pick_split_k(x.shape[1], g.shape[1], x.shape[0]), out=d_l, accumulate=True)
-        if loop_weight is not None:
-            if ctx.needs_input_grad[3] and not side_w:
-                # (on this stream, NOT ordered behind the side stream: d_l / d_w are this layer's own arena slices, which no
-                # other node of the pass writes -- a wait here serialises the flows' weight-gradient products with the R-GCN
-                # backward: WN18RR + 3 IAF 4.9 -> 5.2 ms when it was tried)
-                grad_loop = gemm(x, g, trans_a=True, split_k=pick_split_k(x.shape[1], g.shape[1], x.shape[0]),
-                                 out=d_l, accumulate=d_l is not None)
-                if d_l is not None:
-                    grad_loop = None
-            if ctx.needs_input_grad[0]:
-                if getattr(ctx, 'loop_bf', None) is not None:
-                    gx_loop = dense_bf16(g, ctx.loop_bf[1], loop_weight.shape[0], loop_weight.shape[1])
-                else:
-                    gx_loop = gemm(g, loop_weight, trans_b=True)
+                    _loop_grads(x, g, loop_weight, d_l, True, False)
+        # (the loop weight's gradient on this stream, NOT ordered behind the side stream: d_l / d_w are this layer's own arena
+        # slices, which no other node of the pass writes -- a wait here serialises the flows' weight-gradient products with the
+        # R-GCN backward: WN18RR + 3 IAF 4.9 -> 5.2 ms when it was tried)
+        grad_loop, gx_loop = _loop_grads(x, g, loop_weight, d_l, ctx.needs_input_grad[3] and not side_w, ctx.needs_input_grad[0],
+                                         ctx.loop_bf)
         if pending is not None:
             pending.wait()
         grad_x = None
-        tl = None
-        if reduce_hook is None and ctx.needs_input_grad[0] and use_phases(gidx, so, si, True, g_agg.shape[0], g_agg.shape[1]):
-            tl = ridx.phase_order(gidx, 'src', nb, so, si)
-        # dL/dx rows may be stored straight into the embedding table's gradient (identity lookup) -- but only while that
-        # buffer is known to be zero (fresh from zero_grad / step); a second backward before the next step, or another
-        # lookup of the table whose gradient landed first, must be added to, not erased
-        x_tgt = x_add = ctx.x_grad_target if ctx.needs_input_grad[0] else None
-        if x_tgt is not None:
-            if x_tgt.data_ptr() in GRAD_FRESH:
-                GRAD_FRESH.discard(x_tgt.data_ptr())
-                x_add = None
-            else:
-                x_tgt = None
-        if tl is not None:
-            grad_x = bdd_aggregate_phases(tl, None if coef is None else tl.coef(coef), g_agg,
-                                          pack_weight_phase(tl, weight, nb, so, si), weight.shape[0], nb, so, si, gx_loop,
-                                          out=x_tgt)
-        elif ctx.needs_input_grad[0] and not ctx.grouped and reduce_hook is None and \
-                lds_plan(weight.shape[0], nb, so, si, bf=ctx.k1_bf) is not None and \
-                lds_graph(gidx, 'src', lds_plan(weight.shape[0], nb, so, si, bf=ctx.k1_bf)[2]):
-            lp = lds_plan(weight.shape[0], nb, so, si, bf=ctx.k1_bf)
-            static = not gidx.sync_free and coef is not None
-            coef_s, idx_s = (gidx.coef_in_src_order(coef), None) if static else (coef, gidx.by_src.perm)
-            grad_x = bdd_aggregate_lds(gidx.lds_order('src', lp[2]), gidx.nbr_by_src, ridx.et_by_src, coef_s, idx_s, g_agg,
-                                       pack_weight_lds(weight, nb, so, si, True, lp), weight.shape[0], nb, so, si, True,
-                                       gx_loop, out=x_tgt, plan=lp)
-        elif ctx.needs_input_grad[0]:
-            pk = si * so >= 8 and pack_supported(nb, so, si, True)
-            if ctx.w_bwd_packed is not None and weight._version == ctx.w_version:
-                w_bwd = ctx.w_bwd_packed
-            else:
-                w_bwd = pack_weight(weight, nb, so, si, True) if pk else weight
-            # static graphs: the edge norm is cached in this launch's order; per-batch graphs read it through the index
-            static = not gidx.sync_free and coef is not None
-            if ctx.grouped:
-                seg, nbr, ety, perm = ridx.grouped_order(gidx, 'src')
-                coef_g = None if coef is None else ridx.grouped_coef_src(coef, perm)
-                grad_x = bdd_aggregate(seg, nbr, ety, coef_g, None, g_agg, w_bwd, nb, so, si, True, gx_loop, out=x_tgt, packed=pk)
-            elif K1_REL_RUNS and not gidx.sync_free and reduce_hook is None:
-                nbr_r, et_r, eid_r, coef_r = ridx.rel_sorted(gidx, 'src', coef)
-                grad_x = bdd_aggregate(_k1_items(gidx, gidx.by_src.seg), nbr_r, et_r, coef_r, None, g_agg,
-                                       w_bwd, nb, so, si, True, gx_loop, out=x_tgt, packed=pk)
-            else:
-                coef_s, idx_s = (gidx.coef_in_src_order(coef), None) if static else (coef, gidx.by_src.perm)
-                grad_x = bdd_aggregate(_k1_items(gidx, gidx.by_src.seg), gidx.nbr_by_src, ridx.et_by_src, coef_s, idx_s, g_agg,
-                                       w_bwd, nb, so, si, True, gx_loop, out=x_tgt, packed=pk)
-        if grad_x is not None and x_tgt is not None:
-            grad_x = None                                  # written in place
-        elif grad_x is not None and x_add is not None:     # the table's gradient already holds something: add
-            lib.call('gv_axpby', grad_x.numel(), None, 1.0, ptr(grad_x), 1.0, ptr(x_add), lib.stream())
-            grad_x = None
+        if ctx.needs_input_grad[0]:
+            # dL/dx rows may be stored straight into the embedding table's gradient (identity lookup) -- but only while that
+            # buffer is known to be zero (fresh from zero_grad / step); a second backward before the next step, or another
+            # lookup of the table whose gradient landed first, must be added to, not erased
+            x_tgt = x_add = ctx.x_grad_target
+            if x_tgt is not None:
+                if x_tgt.data_ptr() in GRAD_FRESH:
+                    GRAD_FRESH.discard(x_tgt.data_ptr())
+                    x_add = None
+                else:
+                    x_tgt = None
+            tl = None
+            if reduce_hook is None and use_phases(gidx, so, si, True, g_agg.shape[0], g_agg.shape[1]):
+                tl = ridx.phase_order(gidx, 'src', nb, so, si)
+            grad_x = _bdd_k1(ctx, 'src', tl, gidx, ridx, coef, g_agg, weight, nb, so, si,
+                             lambda: _bdd_weight_bwd(ctx, weight, nb, so, si), lambda: gx_loop, out=x_tgt,
+                             sharded=reduce_hook is not None)
+            if x_tgt is not None:
+                grad_x = None                                  # written in place
+            elif x_add is not None:     # the table's gradient already holds something: add
+                lib.call('gv_axpby', grad_x.numel(), None, 1.0, ptr(grad_x), 1.0, ptr(x_add), lib.stream())
+                grad_x = None
         grad_w = None
         if ctx.needs_input_grad[1] and not side_w:
-            static = not gidx.sync_free and coef is not None
-            coef_r, idx_r = (ridx.coef_in_rel_order(coef), None) if static else (coef, ridx.by_rel.perm)
-            grad_w = bdd_grad_weight(ridx.by_rel.seg, ridx.src_by_rel, ridx.dst_by_rel, coef_r, idx_r, x,
-                                     g_agg, nb, si, so, out=d_w, accumulate=d_w is not None)
-            if d_w is not None:
-                grad_w = None
+            grad_w = _relation_weight_grad(gidx, ridx, coef, x, g_agg, nb, si, so, d_w)
         return grad_x, grad_w, grad_bias, grad_loop, None, None, None, None, None, None, None, None
 
 
@@ -1239,17 +1285,13 @@ class _RelGraphConvDense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w3, h_bias, loop_weight, norm, gidx, ridx, act, keep, keep_scale):
         x, _ = _row_major(x, 'x')
-        n, fin = x.shape
+        fin = x.shape[1]
         r, fin_w, fout = w3.shape
         if fin_w != fin:
             raise ValueError(f'dense relation weights are {tuple(w3.shape)}, x has {fin} columns')
         coef = None if norm is None else norm.reshape(-1)
         tiles, n_tiles, pos_d, pos_s, zeros = ridx.dense_plan(gidx)
-        addend = None
-        if loop_weight is not None:
-            addend = gemm(x, loop_weight, bias=h_bias)
-        elif h_bias is not None:
-            addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
+        addend = _gemm_addend(x, loop_weight, h_bias, fout)
         msg = rel_rows_gemm(x, ridx.src_by_rel, w3, False, tiles, n_tiles, gidx.num_edges)
         ones = torch.ones(1, fout, dtype=torch.float32, device=x.device)
         out = bdd_aggregate(gidx.by_dst.seg, pos_d, zeros, coef, gidx.by_dst.perm, msg, ones, fout, 1, 1, False, addend, act,
@@ -1268,23 +1310,9 @@ class _RelGraphConvDense(torch.autograd.Function):
         d_b, d_l = ctx.direct
         r, fin, fout = w3.shape
         tiles, n_tiles, pos_d, pos_s, zeros = ridx.dense_plan(gidx)
-        grad_bias = grad_loop = grad_x = grad_w = None
-        if has_bias and ctx.needs_input_grad[2]:
-            grad_bias = d_b if d_b is not None else torch.empty(fout, dtype=torch.float32, device=x.device)
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
-            if d_b is not None:
-                grad_bias = None
-        else:
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
-        gx_loop = None
-        if loop_weight is not None:
-            if ctx.needs_input_grad[3]:
-                grad_loop = gemm(x, g, trans_a=True, split_k=pick_split_k(fin, fout, x.shape[0]), out=d_l,
-                                 accumulate=d_l is not None)
-                if d_l is not None:
-                    grad_loop = None
-            if ctx.needs_input_grad[0]:
-                gx_loop = gemm(g, loop_weight, trans_b=True)
+        grad_x = grad_w = None
+        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
+        grad_loop, gx_loop = _loop_grads(x, g, loop_weight, d_l, ctx.needs_input_grad[3], ctx.needs_input_grad[0])
         if ctx.needs_input_grad[0]:
             msg2 = rel_rows_gemm(g, ridx.dst_by_rel, w3, True, tiles, n_tiles, gidx.num_edges)
             ones = torch.ones(1, fin, dtype=torch.float32, device=x.device)
@@ -1315,14 +1343,7 @@ class _RelGraphConvSelect(torch.autograd.Function):
         wflat, _ = _row_major(wflat, 'relation rows')
         n, fout = gidx.num_nodes, wflat.shape[1]
         coef = None if norm is None else norm.reshape(-1)
-        addend = None
-        if h_bias is not None:
-            addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
-            if loop_rows is not None:
-                lib.call('gv_axpby', addend.numel(), None, 1.0, ptr(_chk(loop_rows.contiguous(), name='loop rows')), 1.0,
-                         ptr(addend), lib.stream())
-        elif loop_rows is not None:
-            addend = _chk(loop_rows.contiguous(), name='loop rows')
+        addend = _row_addend(h_bias, None if loop_rows is None else _chk(loop_rows.contiguous(), name='loop rows'), n, fout)
         ones = torch.ones(1, fout, dtype=torch.float32, device=wflat.device)
         out = bdd_aggregate(gidx.by_dst.seg, plan['row_by_dst'], plan['zeros'], coef, gidx.by_dst.perm, wflat, ones, fout, 1, 1,
                             False, addend, act, keep, keep_scale)
@@ -1337,15 +1358,7 @@ class _RelGraphConvSelect(torch.autograd.Function):
         coef, out, keep = ctx.saved_tensors
         plan, act, keep_scale, has_bias, has_loop, wshape = ctx.meta
         _verify_direct(ctx)
-        d_b = ctx.direct_b
-        grad_bias = None
-        if has_bias and ctx.needs_input_grad[2]:
-            grad_bias = d_b if d_b is not None else torch.empty(grad_out.shape[1], dtype=torch.float32, device=grad_out.device)
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
-            if d_b is not None:
-                grad_bias = None
-        else:
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
+        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], ctx.direct_b)
         grad_w = None
         if ctx.needs_input_grad[0]:
             gi = plan['by_row']                      # destinations = rows of W, sources = node rows of g
@@ -1428,19 +1441,14 @@ class _RelGraphConvBasisSelect(torch.autograd.Function):
         msg = torch.empty(max(n_runs, 1), fout, dtype=torch.float32, device=v.device)
         lib.call('gv_ec_basis_rows_fwd', ptr(v), ptr(comp), ptr(plan['run_id']), ptr(plan['run_rel']), n_runs, fout, nb, r, rows,
                  ptr(msg), lib.stream(), tag='ec_basis_fwd')
-        addend = None
+        loop_rows = None
         if loop_weight is not None:
             loop_weight = _chk(loop_weight, name='loop_weight')
             if tuple(loop_weight.shape) != (rows, fout):
                 raise ValueError(f'loop_weight is {tuple(loop_weight.shape)}, expected ({rows}, {fout})')
             loop_rows = torch.empty(n, fout, dtype=torch.float32, device=v.device)
             lib.call('gv_gather_rows', ptr(loop_weight), ptr(plan['ids']), ptr(loop_rows), n, fout, lib.stream())
-            addend = loop_rows
-            if h_bias is not None:
-                addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
-                lib.call('gv_axpby', addend.numel(), None, 1.0, ptr(loop_rows), 1.0, ptr(addend), lib.stream())
-        elif h_bias is not None:
-            addend = h_bias.unsqueeze(0).expand(n, fout).contiguous()
+        addend = _row_addend(h_bias, loop_rows, n, fout)
         ones = torch.ones(1, fout, dtype=torch.float32, device=v.device)
         out = bdd_aggregate(gidx.by_dst.seg, plan['run_by_dst'], plan['zeros'], coef, gidx.by_dst.perm, msg, ones, fout, 1, 1,
                             False, addend, act, keep, keep_scale)
@@ -1458,14 +1466,8 @@ class _RelGraphConvBasisSelect(torch.autograd.Function):
         d_v, d_c, d_b, d_l = ctx.direct
         nb, rows, fout = v.shape
         r = comp.shape[0]
-        grad_bias = grad_v = grad_c = None
-        if has_bias and ctx.needs_input_grad[3]:
-            grad_bias = d_b if d_b is not None else torch.empty(fout, dtype=torch.float32, device=v.device)
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
-            if d_b is not None:
-                grad_bias = None
-        else:
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
+        grad_v = grad_c = None
+        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[3], d_b)
         want_v, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if (want_v or want_c) and plan['n_runs'] > 0:
             gi = plan['by_run']                      # destinations = runs, sources = node rows of g
@@ -1735,19 +1737,8 @@ class _RelGraphConvRows(torch.autograd.Function):
             x_full, x_own = x, x[row0:row0 + c]
         pk = si * so >= 8 and pack_supported(num_bases, si, so, False)
         pk_bwd = si * so >= 8 and pack_supported(num_bases, so, si, True)
-        ctx.w_bwd_packed = None
-        if pk and pk_bwd:
-            w_fwd, ctx.w_bwd_packed = torch.empty_like(weight), torch.empty_like(weight)
-            lib.call('gv_rgcn_bdd_pack_weight_pair', ptr(weight), weight.shape[0], num_bases, si, so, ptr(w_fwd),
-                     ptr(ctx.w_bwd_packed), lib.stream())
-        else:
-            w_fwd = pack_weight(weight, num_bases, si, so, False) if pk else weight
-        addend = None
-        if c > 0:
-            if loop_weight is not None:
-                addend = gemm(x_own, loop_weight, bias=h_bias)
-            elif h_bias is not None:
-                addend = h_bias.unsqueeze(0).expand(c, out_feat).contiguous()
+        w_fwd = _bdd_weight_fwd(ctx, weight, num_bases, si, so, pk, pk_bwd)
+        addend = _gemm_addend(x_own, loop_weight, h_bias, out_feat) if c > 0 else None
         pad_output = pad_output or gather_output
         buf = torch.empty(slot if pad_output else c, out_feat, dtype=torch.float32, device=x.device)
         if pad_output and c < slot:
@@ -1775,7 +1766,6 @@ class _RelGraphConvRows(torch.autograd.Function):
         ctx.save_for_backward(x_full, weight, loop_weight, coef, out if act == ACT_RELU else None, keep)
         ctx.meta = (gidx, ridx, num_bases, si, so, act, keep_scale, h_bias is not None, part, gather_input)
         ctx.pipe = (bool(gather_output), bool(x_gathered))
-        ctx.w_version = weight._version
         ctx.direct = (_direct(weight), _direct(h_bias), _direct(loop_weight))
         _stamp_direct(ctx)
         return result
@@ -1792,7 +1782,6 @@ class _RelGraphConvRows(torch.autograd.Function):
         # (a gathered output's gradient is the consumer's reduce-scattered sums, valid in this rank's slot rows)
         grad_out = grad_out[row0:row0 + c] if gather_output else grad_out[:c]
         x_own = x_full[row0:row0 + c]
-        grad_bias = grad_loop = grad_w = None
         if c == 0:           # a rank without rows: contributes zeros to the exchange
             gfull = torch.zeros(total, in_feat, dtype=torch.float32, device=dev)
             if gather_input or x_gathered:
@@ -1805,23 +1794,12 @@ class _RelGraphConvRows(torch.autograd.Function):
                 part.reduce_scatter(own, gfull).wait()
                 return (own,) + (None,) * 15
             return (gfull,) + (None,) * 15
-        if has_bias and ctx.needs_input_grad[2]:
-            grad_bias = d_b if d_b is not None else torch.empty(grad_out.shape[1], dtype=torch.float32, device=dev)
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
-            if d_b is not None:
-                grad_bias = None
-        else:
-            g = epilogue_bwd(out, grad_out, act, keep, keep_scale)
+        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
         # K1^T first: its exchange then runs under the loop-weight products and the relation-weight gradient
         grad_x = pending = None
         if ctx.needs_input_grad[0]:
-            pk = si * so >= 8 and pack_supported(nb, so, si, True)
-            if ctx.w_bwd_packed is not None and weight._version == ctx.w_version:
-                w_bwd = ctx.w_bwd_packed
-            else:
-                w_bwd = pack_weight(weight, nb, so, si, True) if pk else weight
-            static = not gidx.sync_free and coef is not None
-            coef_s, idx_s = (gidx.coef_in_src_order(coef), None) if static else (coef, gidx.by_src.perm)
+            w_bwd, pk = _bdd_weight_bwd(ctx, weight, nb, so, si)
+            coef_s, idx_s = _coef_order(gidx, ridx, coef, 'src')
             own_sum = waits = None
             if x_gathered:
                 # block k = the same slot-row range of EVERY rank's slot: its partial sums are complete after its own launch and
@@ -1843,22 +1821,10 @@ class _RelGraphConvRows(torch.autograd.Function):
                 pending = part.reduce_scatter(grad_x, gfull)
             else:
                 grad_x = gfull
-        gx_loop = None
-        if loop_weight is not None:
-            if ctx.needs_input_grad[3]:
-                grad_loop = gemm(x_own, g, trans_a=True, split_k=pick_split_k(in_feat, g.shape[1], c), out=d_l,
-                                 accumulate=d_l is not None)
-                if d_l is not None:
-                    grad_loop = None
-            if ctx.needs_input_grad[0]:
-                gx_loop = gemm(g, loop_weight, trans_b=True)
+        grad_loop, gx_loop = _loop_grads(x_own, g, loop_weight, d_l, ctx.needs_input_grad[3], ctx.needs_input_grad[0])
+        grad_w = None
         if ctx.needs_input_grad[1]:
-            static = not gidx.sync_free and coef is not None
-            coef_r, idx_r = (ridx.coef_in_rel_order(coef), None) if static else (coef, ridx.by_rel.perm)
-            grad_w = bdd_grad_weight(ridx.by_rel.seg, ridx.src_by_rel, ridx.dst_by_rel, coef_r, idx_r, x_full, g, nb, si,
-                                     so, out=d_w, accumulate=d_w is not None)
-            if d_w is not None:
-                grad_w = None
+            grad_w = _relation_weight_grad(gidx, ridx, coef, x_full, g, nb, si, so, d_w)
         if pending is not None:
             pending.wait()
         if x_gathered and ctx.needs_input_grad[0]:
