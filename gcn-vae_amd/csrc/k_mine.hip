@@ -1,0 +1,411 @@
+// Whole-graph triplet mining (gv_mine_scores): every (s, r, o) of a DistMult decoder scored on the f32 MFMA, selected globally.
+//
+//   logit[s, r, o] = (E[s] * w[r]) . E[o] + bias
+//
+// bit for bit gv_gemm_f32(gv_mul(E, w[r]), E^T) + bias: one f32 multiply per subject element, the k-ordered
+// v_mfma_f32_32x32x2_f32 chain over k = 0 .. ceil16(h) - 1 (zeros past h, as the GEMM's 16-deep steps pad), one add.  The subject
+// side carries w[r]: (E[s] * w) . E[o] and (E[o] * w) . E[s] differ in rounding, so the s <-> o symmetry is not used.
+//
+// Loop order: a workgroup owns one 64 x 64 (subject tile, object tile) pair and walks the RELATIONS over it.  With ceil16(h) <= 240
+// both tiles of E are staged in LDS once (2 x 64 x 212 floats at h = 200) and a relation costs its 800-byte row of w; wider
+// tables are staged in 240-deep k-chunks per relation.  LDS rows hold the even k of a chunk, then the odd k: lane l of the MFMA
+// needs k = 2 j + (l >> 5) for consecutive j, so ONE ds_read_b128 per operand feeds four MFMAs (row pitch kc + 4 floats: the
+// 16 lanes of a b128 group fall on 16 distinct 16-byte slots).
+//
+// Candidates: all (s, r, o) with s, o < n, less the listed triplets (filter), less s == o (exclude_self), less NaN logits.  Each
+// has the ordered key of gv_topk_scores (sign-flip map, -0 -> +0, NaN -> 0 = never a candidate), larger = better.  Two epilogues:
+//   EMIT  key >= key_min: one wave-aggregated integer atomicAdd reserves slots on a 64-bit counter, (s, r, o, logit) go out as
+//         plain 16-byte vector stores while the slot is below the capacity; the counter keeps counting, so the host learns the
+//         true total.  Arrival order is arbitrary: the caller sorts.
+//   HIST  keys whose top prefix_bits equal `prefix` are binned by their next bin_bits into an LDS histogram that is flushed with
+//         integer atomics; the host walks 12 + 10 + 10 bits to the key of the K-th best candidate (at most three such passes).
+// The filter is applied before either: the (lo, hi, ent) ranges per key s * R + r are re-bucketed per tile pair first (count,
+// scan, fill: three small kernels, integer atomics), so a workgroup reads ITS listed triplets once into LDS and a relation
+// without one -- nearly all of them -- costs one LDS flag.  No float atomics anywhere.
+#include <limits.h>
+
+#include <algorithm>
+
+#include "common.h"
+
+namespace gv {
+
+typedef float mine_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int MINE_KC_MAX = 240;       // k per staged chunk (multiple of 16): 2 x 64 x 244 floats = 122 KiB of the 160
+constexpr int MINE_FL_CAP = 1024;      // listed triplets of a tile pair kept in LDS (the rest is read from memory)
+constexpr int MINE_HIST_BITS = 12;
+constexpr int MINE_REL_BITS = 19;      // packed filter entry: relation << 12 | local subject << 6 | local object
+
+struct MineParams {
+    const float* e;
+    const float* w;
+    const float* bias;
+    int n, h, num_rels, ld_e, ld_w;
+    int vec_e, vec_w;
+    int kc, n_chunks;                  // chunk depth (multiple of 16) and count; one chunk: the tiles stay in LDS
+    int rel_span;                      // relations per blockIdx.z
+    int exclude_self;
+    unsigned key_min;                  // EMIT
+    int prefix_bits, bin_bits;         // HIST
+    unsigned prefix;
+    const int* tile_ptr;               // [s_tiles * o_tiles + 1], NULL: no filter
+    const unsigned* tile_ent;
+    int4* out;
+    long long capacity;
+    unsigned long long* counter;
+    unsigned long long* hist;
+};
+
+// the key of gv_topk_scores' order (k_gemm.hip: topk_key), logit part
+__device__ __forceinline__ unsigned mine_key(float x) {
+    unsigned u = __float_as_uint(x);
+    if (x != x) return 0u;
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float mine_key_logit(unsigned o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// one 64-row tile of E, columns [k0, k0 + kc), into LDS: row pitch kc + 4, even k first, then odd k; zeros outside the table
+__device__ __forceinline__ void mine_stage_tile(float* dst, const float* e, int ld, bool vec, int row0, int n, int k0, int h, int kc) {
+    const int q4 = kc >> 2, pitch = kc + 4, half = kc >> 1;
+    for (int idx = threadIdx.x; idx < 64 * q4; idx += 256) {
+        const int rl = idx / q4, q = idx - rl * q4;
+        const int row = row0 + rl, k = k0 + 4 * q;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (row < n) {
+            const float* src = e + (size_t)row * ld + k;
+            if (vec && k + 3 < h) {
+                const float4 t = *reinterpret_cast<const float4*>(src);
+                v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = k + i < h ? src[i] : 0.f;
+            }
+        }
+        float* d = dst + rl * pitch + 2 * q;
+        *reinterpret_cast<float2*>(d) = make_float2(v[0], v[2]);
+        *reinterpret_cast<float2*>(d + half) = make_float2(v[1], v[3]);
+    }
+}
+
+// four floats of w[r] at k (zeros past h)
+__device__ __forceinline__ float4 mine_load_w(const MineParams& p, int r, int k) {
+    const float* src = p.w + (size_t)r * p.ld_w + k;
+    if (p.vec_w && k + 3 < p.h) return *reinterpret_cast<const float4*>(src);
+    float4 v;
+    v.x = k < p.h ? src[0] : 0.f;
+    v.y = k + 1 < p.h ? src[1] : 0.f;
+    v.z = k + 2 < p.h ? src[2] : 0.f;
+    v.w = k + 3 < p.h ? src[3] : 0.f;
+    return v;
+}
+
+__device__ __forceinline__ void mine_store_w(float* ws, int kc, int t, float4 v) {      // thread t holds k = 4 t .. 4 t + 3 of the chunk
+    *reinterpret_cast<float2*>(ws + 2 * t) = make_float2(v.x, v.z);
+    *reinterpret_cast<float2*>(ws + (kc >> 1) + 2 * t) = make_float2(v.y, v.w);
+}
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_mine(const MineParams p) {
+    extern __shared__ __attribute__((aligned(16))) float mine_smem[];
+    __shared__ unsigned long long fmask[3][64];          // the relation's listed objects per subject row, three relations in flight
+    __shared__ int fany[3];
+    __shared__ unsigned flist[MINE_FL_CAP];
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const int kc = p.kc, pitch = kc + 4, half = kc >> 1;
+    float* As = mine_smem;
+    float* Bs = As + 64 * pitch;
+    float* Ws = Bs + 64 * pitch;                         // [2][kc + 4]
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const int r0 = blockIdx.z * p.rel_span, r1 = min(r0 + p.rel_span, p.num_rels);
+    const bool resident = p.n_chunks == 1;
+    const bool diag = p.exclude_self && m0 == n0;
+    const float bv = p.bias ? *p.bias : 0.f;
+
+    int f_base = 0, f_cnt = 0;
+    if (p.tile_ptr) {
+        const int tile = blockIdx.y * gridDim.x + blockIdx.x;
+        f_base = p.tile_ptr[tile];
+        f_cnt = p.tile_ptr[tile + 1] - f_base;
+        for (int i = t; i < min(f_cnt, MINE_FL_CAP); i += 256) flist[i] = p.tile_ent[f_base + i];
+    }
+    if (t < 64) { fmask[0][t] = 0ull; fmask[1][t] = 0ull; fmask[2][t] = 0ull; }
+    if (t < 3) fany[t] = 0;
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
+    if (resident) {
+        mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, p.n, 0, p.h, kc);
+        mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, p.n, 0, p.h, kc);
+        if (t < (kc >> 2) && r0 < r1) mine_store_w(Ws, kc, t, mine_load_w(p, r0, 4 * t));
+    }
+    __syncthreads();
+
+    const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
+    const int shift = 32 - p.prefix_bits - p.bin_bits;
+    const unsigned bin_mask = (1u << p.bin_bits) - 1u;
+
+    for (int r = r0; r < r1; ++r) {
+        const int it = r - r0, fb = it % 3, wb = resident ? (it & 1) : 0;
+        // this relation's listed triplets -> fmask[fb]; the buffer of the relation after it is cleared (last read two relations ago)
+        if (t < 64) fmask[(it + 1) % 3][t] = 0ull;
+        if (t == 64) fany[(it + 1) % 3] = 0;
+        for (int i = t; i < f_cnt; i += 256) {
+            const unsigned ent = i < MINE_FL_CAP ? flist[i] : p.tile_ent[f_base + i];
+            if ((int)(ent >> 12) == r) {
+                atomicOr(&fmask[fb][(ent >> 6) & 63u], 1ull << (ent & 63u));
+                fany[fb] = 1;
+            }
+        }
+        float4 wnext = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool w_pre = resident && t < (kc >> 2) && r + 1 < r1;
+        if (w_pre) wnext = mine_load_w(p, r + 1, 4 * t);          // flies under the MFMA chain
+
+        mine_f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc;
+            if (!resident) {
+                __syncthreads();
+                mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, p.n, k0, p.h, kc);
+                mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, p.n, k0, p.h, kc);
+                if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
+                __syncthreads();
+            }
+            const int groups = (min(kc, p.h - k0) + 15) / 16 * 2;             // 8 k per group, whole 16-deep steps as the GEMM walks them
+            const float* wsb = Ws + wb * (kc + 4) + w_off;
+            // one wave per SIMD: the next group's three reads are issued before this group's MFMAs, or their latency is exposed
+            // every 256 cycles.  (The read past the last group lands in the row's / the buffer's four floats of padding: unused.)
+            float4 a_n = *reinterpret_cast<const float4*>(As + a_off);
+            float4 b_n = *reinterpret_cast<const float4*>(Bs + b_off);
+            float4 w_n = *reinterpret_cast<const float4*>(wsb);
+#pragma unroll 2
+            for (int g = 0; g < groups; ++g) {
+                const float4 a4 = a_n, b4 = b_n, w4 = w_n;
+                a_n = *reinterpret_cast<const float4*>(As + a_off + 4 * g + 4);
+                b_n = *reinterpret_cast<const float4*>(Bs + b_off + 4 * g + 4);
+                w_n = *reinterpret_cast<const float4*>(wsb + 4 * g + 4);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x * w4.x, b4.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y * w4.y, b4.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z * w4.z, b4.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w * w4.w, b4.w, acc, 0, 0, 0);
+            }
+        }
+        if (w_pre) mine_store_w(Ws + ((it + 1) & 1) * (kc + 4), kc, t, wnext);
+        __syncthreads();
+
+        // ---- epilogue: C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+        const int cl = wn + l31, col = n0 + cl;
+        unsigned key[16];
+        bool want = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
+            unsigned k = mine_key(acc[i] + bv);
+            if (m0 + rl >= p.n || col >= p.n || (diag && rl == cl)) k = 0u;
+            if (HIST) {
+                if (p.prefix_bits && (k >> (32 - p.prefix_bits)) != p.prefix) k = 0u;
+            } else {
+                if (k < p.key_min) k = 0u;
+            }
+            key[i] = k;
+            want = want || k != 0u;
+        }
+        if (__ballot(want) == 0ull) continue;                    // nearly every relation of nearly every tile in EMIT and refining HIST passes
+        const bool anyf = fany[fb] != 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
+            bool ok = key[i] != 0u;
+            if (anyf && ok) ok = !((fmask[fb][rl] >> cl) & 1ull);
+            if (HIST) {
+                if (ok) atomicAdd(&hist_s[(key[i] >> shift) & bin_mask], 1u);
+            } else {
+                const unsigned long long m = __ballot(ok);
+                if (m) {
+                    const int leader = __builtin_ctzll(m);
+                    unsigned long long base = 0ull;
+                    if (lane == leader) base = atomicAdd(p.counter, (unsigned long long)__popcll(m));
+                    const unsigned blo = (unsigned)__shfl((int)(unsigned)base, leader);
+                    const unsigned bhi = (unsigned)__shfl((int)(unsigned)(base >> 32), leader);
+                    base = ((unsigned long long)bhi << 32) | blo;
+                    if (ok) {
+                        const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+                        if (slot < (unsigned long long)p.capacity)
+                            p.out[slot] = make_int4(m0 + rl, r, col, __float_as_int(mine_key_logit(key[i])));
+                    }
+                }
+            }
+        }
+    }
+    if (HIST) {
+        __syncthreads();
+        for (int i = t; i <= (int)bin_mask; i += 256) {
+            const unsigned c = hist_s[i];
+            if (c) atomicAdd(p.hist + i, (unsigned long long)c);
+        }
+    }
+}
+
+// ---- the filter, re-bucketed per (subject tile, object tile): count, scan, fill ------------------------------------------
+struct MineFiltParams {
+    const int* lo;
+    const int* hi;
+    const int* ent;
+    int n_ent, n, num_rels, o_tiles;
+    int* cnt;                  // [tiles]: counts, then the fill cursors
+    int* ptr;                  // [tiles + 1]
+    unsigned* out;             // [n_ent]
+};
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_mine_filt(const MineFiltParams f) {
+    const long long keys = (long long)f.n * f.num_rels;
+    for (long long key = (long long)blockIdx.x * 256 + threadIdx.x; key < keys; key += (long long)gridDim.x * 256) {
+        const int lo = min(max(f.lo[key], 0), f.n_ent), hi = min(max(f.hi[key], lo), f.n_ent);
+        if (lo == hi) continue;
+        const int s = (int)(key / f.num_rels), r = (int)(key - (long long)s * f.num_rels);
+        for (int j = lo; j < hi; ++j) {
+            const int o = f.ent[j];
+            if (o < 0 || o >= f.n) continue;
+            const int tile = (s >> 6) * f.o_tiles + (o >> 6);
+            if (!FILL) atomicAdd(f.cnt + tile, 1);
+            else {
+                const int pos = atomicAdd(f.cnt + tile, 1);
+                if (pos >= 0 && pos < f.n_ent) f.out[pos] = ((unsigned)r << 12) | ((unsigned)(s & 63) << 6) | (unsigned)(o & 63);
+            }
+        }
+    }
+}
+
+// exclusive scan of the tile counts (one workgroup: a thread sums a contiguous slice, the slices are scanned in LDS)
+__global__ __launch_bounds__(1024) void k_mine_filt_scan(int* cnt, int* ptr, int tiles) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int per = (tiles + 1023) / 1024;
+    const int i0 = min(t * per, tiles), i1 = min(i0 + per, tiles);
+    int s = 0;
+    for (int i = i0; i < i1; ++i) s += cnt[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; }
+        ptr[tiles] = run;
+    }
+    __syncthreads();
+    int run = part[t];
+    for (int i = i0; i < i1; ++i) {
+        const int v = cnt[i];
+        ptr[i] = run;
+        cnt[i] = run;          // the fill cursor
+        run += v;
+    }
+}
+
+}  // namespace gv
+
+using namespace gv;
+
+static int64_t mine_align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+extern "C" int64_t gv_mine_scores_workspace_bytes(int n, int num_rels, int n_filt_ent) {
+    (void)num_rels;
+    if (n <= 0 || n_filt_ent < 0) return 0;
+    const int64_t tiles = (int64_t)((n + 63) / 64) * ((n + 63) / 64);
+    return mine_align16(tiles * 4) + mine_align16((tiles + 1) * 4) + mine_align16((int64_t)(n_filt_ent > 0 ? n_filt_ent : 1) * 4);
+}
+
+extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,
+                              const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                              uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                              uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels,
+                              int h, void* stream) {
+    GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_mine_scores: n=%d num_rels=%d h=%d n_filt_ent=%d",
+               n, num_rels, h, n_filt_ent);
+    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "gv_mine_scores: unknown mode %d", mode);
+    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_mine_scores: leading dimension too small (ld_e=%d ld_w=%d h=%d)", ld_e, ld_w, h);
+    GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "gv_mine_scores: n * num_rels = %lld reaches 2^31",
+               (long long)n * num_rels);
+    GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "gv_mine_scores: more than %d relations", 1 << MINE_REL_BITS);
+    GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "gv_mine_scores: n=%d: more than 2^31 tile pairs", n);
+    if (mode == GV_MINE_EMIT)
+        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "gv_mine_scores: capacity=%lld outside [0, 2^31)",
+                   (long long)capacity);
+    else
+        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
+                       (prefix >> prefix_bits) == 0u,
+                   GV_ERR_SHAPE, "gv_mine_scores: prefix_bits=%d prefix=%u bin_bits=%d out of range", prefix_bits, prefix, bin_bits);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_mine_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (n == 0) return GV_OK;
+    GV_REQUIRE(e && w, GV_ERR_NULL, "gv_mine_scores: NULL table");
+    if (mode == GV_MINE_EMIT) GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "gv_mine_scores: NULL output");
+    else GV_REQUIRE(hist, GV_ERR_NULL, "gv_mine_scores: NULL histogram");
+    const bool filtered = filt_lo != nullptr;
+    if (filtered) {
+        GV_REQUIRE(workspace, GV_ERR_NULL, "gv_mine_scores: a filter needs the workspace");
+        GV_REQUIRE(workspace_bytes >= gv_mine_scores_workspace_bytes(n, num_rels, n_filt_ent), GV_ERR_WORKSPACE,
+                   "gv_mine_scores: workspace %lld < %lld bytes", (long long)workspace_bytes,
+                   (long long)gv_mine_scores_workspace_bytes(n, num_rels, n_filt_ent));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles_1d = (n + 63) / 64;
+    const int tiles = tiles_1d * tiles_1d;
+
+    MineParams p{};
+    p.e = e; p.w = w; p.bias = bias;
+    p.n = n; p.h = h; p.num_rels = num_rels; p.ld_e = ld_e; p.ld_w = ld_w;
+    p.vec_e = aligned16(e) && (ld_e % 4 == 0);
+    p.vec_w = aligned16(w) && (ld_w % 4 == 0);
+    const int h16 = (h + 15) / 16 * 16;
+    p.kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
+    p.n_chunks = (h + p.kc - 1) / p.kc;
+    // relation spans: about four workgroups per CU of the MI355X when the table has few tiles (the result does not depend on it)
+    long long spans = (4LL * 256 + tiles - 1) / tiles;
+    spans = std::max(1LL, std::min(spans, (long long)num_rels));
+    p.rel_span = (int)((num_rels + spans - 1) / spans);
+    const int n_spans = (num_rels + p.rel_span - 1) / p.rel_span;
+    p.exclude_self = exclude_self ? 1 : 0;
+    p.key_min = key_min; p.prefix_bits = prefix_bits; p.bin_bits = bin_bits; p.prefix = prefix;
+    p.out = (int4*)out; p.capacity = capacity;
+    p.counter = (unsigned long long*)counter; p.hist = (unsigned long long*)hist;
+
+    if (filtered) {
+        char* ws = (char*)workspace;
+        MineFiltParams f{};
+        f.lo = filt_lo; f.hi = filt_hi; f.ent = filt_ent; f.n_ent = n_filt_ent; f.n = n; f.num_rels = num_rels; f.o_tiles = tiles_1d;
+        f.cnt = (int*)ws;
+        f.ptr = (int*)(ws + mine_align16((int64_t)tiles * 4));
+        f.out = (unsigned*)(ws + mine_align16((int64_t)tiles * 4) + mine_align16((int64_t)(tiles + 1) * 4));
+        if (fill_words(f.cnt, 0u, (size_t)tiles * 4, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
+        const long long keys = (long long)n * num_rels;
+        const unsigned fb = (unsigned)std::min<long long>((keys + 255) / 256, 65535);
+        hipLaunchKernelGGL(k_mine_filt<false>, dim3(fb), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(k_mine_filt_scan, dim3(1), dim3(1024), 0, st, f.cnt, f.ptr, tiles);
+        hipLaunchKernelGGL(k_mine_filt<true>, dim3(fb), dim3(256), 0, st, f);
+        p.tile_ptr = f.ptr; p.tile_ent = f.out;
+    }
+    const int lds = (2 * 64 * (p.kc + 4) + 2 * (p.kc + 4)) * (int)sizeof(float);
+    const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);
+    dim3 grid(tiles_1d, tiles_1d, n_spans), block(256);
+    if (mode == GV_MINE_EMIT) {
+        if (fill_words(counter, 0u, 8, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
+        static unsigned long long raised = 0;
+        if (!raise_dynamic_lds((const void*)k_mine<false>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_mine<false>, grid, block, lds, st, p);
+    } else {
+        if (fill_words(hist, 0u, (size_t)8 << bin_bits, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
+        static unsigned long long raised = 0;
+        if (!raise_dynamic_lds((const void*)k_mine<true>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_mine<true>, grid, block, lds, st, p);
+    }
+    return launch_status("gv_mine_scores");
+}

@@ -108,6 +108,9 @@ SIGNATURES = {
     'gv_rank_scores_filtered': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_topk_scores_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_topk_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    'gv_mine_scores_workspace_bytes': (_L, [_I, _I, _I]),
+    'gv_mine_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P, _P, _L,
+                            _I, _I, _I, _P]),
     'gv_ec_basis_rows_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P]),
     'gv_ec_basis_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _I, _P]),
     'gv_ec_head_fwd': (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),

@@ -664,6 +664,172 @@ def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=
     return ids.long(), logits
 
 
+MINE_MAX_RESULTS = 1 << 22      # default cap on the triplets one mining call may return (64 MiB of records)
+MINE_LEVELS = ((0, 12), (12, 10), (22, 10))      # (prefix bits, bin bits) of the histogram passes: 12 + 10 + 10 = the whole key
+
+
+class MineOverflow(RuntimeError):
+    """A mining run found more triplets than ``max_results`` allows; ``count`` is how many (nothing is truncated silently)."""
+
+    def __init__(self, count, max_results, what):
+        self.count, self.max_results = int(count), int(max_results)
+        super().__init__(f'{what}: {self.count} triplets, more than max_results={self.max_results}; raise the threshold or the cap')
+
+
+def mine_key(x):
+    """The ordered 32-bit key of a logit (host mirror of the kernels' sign-flip map): larger key = larger logit, -0 as +0,
+    NaN -> 0 (never a candidate)."""
+    import struct
+    x = float(x)
+    if x != x:
+        return 0
+    u = struct.unpack('<I', struct.pack('<f', x))[0]
+    if u == 0x80000000:
+        u = 0
+    return (~u & 0xffffffff) if u & 0x80000000 else (u | 0x80000000)
+
+
+def mine_order(triplets, logits, num_nodes, num_rels):
+    """Sort mined (triplets int64 (n, 3), logits (n,)) into the rule's total order: logit descending (-0 as +0), then (s, r, o)
+    ascending.  Any device."""
+    logits = logits.to(torch.float32) + 0.0
+    lin = (triplets[:, 0] * num_rels + triplets[:, 1]) * max(num_nodes, 1) + triplets[:, 2]
+    order = torch.argsort(lin, stable=True)
+    order = order[torch.argsort(logits[order], descending=True, stable=True)]
+    return triplets[order], logits[order]
+
+
+def mine_select(triplets, logits, k, max_results, num_nodes, num_rels):
+    """The top-K end of every mining route: from candidates that include everything at or above the K-th logit, the first K in
+    the total order and the number at or above the K-th logit's exact value (more than ``max_results`` of those: MineOverflow)."""
+    triplets, logits = mine_order(triplets, logits, num_nodes, num_rels)
+    n = logits.numel()
+    count = n if n <= k else int((logits >= logits[k - 1]).sum())
+    if count > max_results:
+        raise MineOverflow(count, max_results, f'top-{k}: the candidates at or above the K-th logit')
+    return triplets[:k], logits[:k], count
+
+
+def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                max_results=MINE_MAX_RESULTS):
+    """Mine ALL triplets of a DistMult decoder: ``logit[s, r, o] = (emb[s] * w[r]) . emb[o] (+ bias)``, bit for bit
+    ``gemm(mul(emb, w[r]), emb^T, precision='f32') + bias``, over every (s, r, o) -- less the triplets of the filter (key
+    ``s * R + r`` -> ``filt_ent[filt_lo[key]:filt_hi[key]]``), less s == o when ``exclude_self``, less NaN logits -- without
+    storing a score (gv_mine_scores: a workgroup keeps a subject and an object tile of ``emb`` in LDS and walks the relations).
+    ``threshold=t``: every candidate with logit >= t; ``k=K``: the K best.  Order: logit descending (-0 as +0), then (s, r, o).
+    Returns ``(triplets int64 (n, 3), logits float32 (n,), info)``; ``info['count']`` is the number of candidates at or above
+    the threshold (top-K: at or above the K-th logit), ``info['passes']`` the passes over the N x R x N product.  More than
+    ``max_results`` such candidates raise ``MineOverflow`` with the count.  Top-K finds its threshold with up to three
+    histogram passes over the ordered key's bits (12 + 10 + 10), then emits once."""
+    if (k is None) == (threshold is None):
+        raise ValueError('give exactly one of k and threshold')
+    for name, t in (('emb', emb), ('w', w)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if emb.shape[1] != w.shape[1]:
+        raise ValueError('emb / w width mismatch')
+    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
+    if num_rels < 1 or h < 1:
+        raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
+    if n * num_rels >= 2 ** 31:
+        raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
+    max_results = int(max_results)
+    if not 1 <= max_results < 2 ** 31:
+        raise ValueError(f'max_results must lie in [1, 2**31), got {max_results}')
+    if k is not None:
+        k = int(k)
+        if k < 1:
+            raise ValueError(f'k must be >= 1, got {k}')
+    else:
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError('threshold is NaN')
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev = emb.device
+    if w.device != dev:
+        raise ValueError(f'w must be on the device of emb ({dev})')
+    empty = (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev))
+    if n == 0:
+        return empty + ({'count': 0, 'passes': 0},)
+    lo32 = hi32 = ent32 = ws = None
+    n_ent, ws_bytes = 0, 0
+    if all(given):
+        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+        if filt_lo.numel() != n * num_rels or filt_hi.numel() != n * num_rels:
+            raise ValueError('one filter range (filt_lo, filt_hi) per key s * R + r')
+        n_ent = filt_ent.numel()
+        if n_ent >= 2 ** 31:
+            raise ValueError('filt_ent: more than 2**31 - 1 entries')
+        if int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any()):
+            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= n):
+            raise ValueError(f'filtered entity ids must lie in [0, {n})')
+        i32 = dict(device=dev, dtype=torch.int32)
+        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+        ws_bytes = int(lib.load().gv_mine_scores_workspace_bytes(n, num_rels, n_ent))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    if bias is not None:
+        bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
+        bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
+    info = {'count': 0, 'passes': 0}
+    words = torch.zeros(1 << MINE_LEVELS[0][1], dtype=torch.int64, device=dev)      # the counter / the histogram
+
+    def run(mode, key_min=0, prefix_bits=0, prefix=0, bin_bits=1, out=None, capacity=0):
+        lib.call('gv_mine_scores', ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+                 1 if exclude_self else 0, mode, key_min, prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words),
+                 ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+        info['passes'] += 1
+
+    def emit(key_min, capacity):
+        out = torch.empty(max(capacity, 1), 4, dtype=torch.int32, device=dev)
+        run(0, key_min=key_min, out=out, capacity=capacity)
+        count = int(words[0])
+        rec = out[:min(count, capacity)]
+        return count, rec[:, :3].long(), rec[:, 3].contiguous().view(torch.float32)
+
+    if k is None:
+        count, trip, logits = emit(mine_key(threshold), min(max_results, n * num_rels * n))
+        info['count'] = count
+        if count > max_results:
+            raise MineOverflow(count, max_results, f'threshold {threshold}')
+        return mine_order(trip, logits, n, num_rels) + (info,)
+
+    above, key_min = 0, None          # candidates strictly above the range being narrowed; the emission threshold once known
+    prefix = 0
+    for prefix_bits, bin_bits in MINE_LEVELS:
+        run(1, prefix_bits=prefix_bits, prefix=prefix, bin_bits=bin_bits)
+        hist = words[:1 << bin_bits].cpu().numpy()
+        total = int(hist.sum())
+        if prefix_bits == 0 and total <= k:           # fewer candidates than asked for: all of them
+            if total > max_results:
+                raise MineOverflow(total, max_results, f'top-{k}: all candidates')
+            if total == 0:
+                return empty + (info,)
+            key_min, edge = 1, total
+            break
+        tail = hist[::-1].cumsum()[::-1]              # tail[b] = candidates of this range in bins >= b
+        b = int((tail >= k - above).nonzero()[0].max())
+        prefix = (prefix << bin_bits) | b
+        above += int(tail[b]) - int(hist[b])
+        edge = above + int(hist[b])                   # what an emission at this bin's lower edge returns
+        shift = 32 - prefix_bits - bin_bits
+        if edge <= max_results or shift == 0:
+            key_min = prefix << shift
+            break
+    if edge > max_results:            # one exact logit value holds more candidates than may be returned
+        raise MineOverflow(edge, max_results, f'top-{k}: the candidates at or above the K-th logit')
+    count, trip, logits = emit(key_min, edge)
+    if count != edge:
+        raise RuntimeError(f'gv_mine_scores: the emission pass found {count} candidates where the histograms counted {edge}')
+    trip, logits, info['count'] = mine_select(trip, logits, k, max_results, n, num_rels)
+    return trip, logits, info
+
+
 def pick_split_k(m_out, n_out, k):
     """Reduction-heavy shapes (weight gradients: small output, K = nodes) need split-K to fill 256 CUs."""
     tiles = ((m_out + 63) // 64) * ((n_out + 63) // 64)

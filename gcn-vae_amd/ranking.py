@@ -20,6 +20,11 @@ rank.  ``calc_filtered_mrr`` reports both.
 Link prediction (what the reference's ``--generate`` demo did with an argmax, kgvae/utils.py:245-288): ``predict_topk`` returns
 the k best entities of each query, optionally filtered by a ``FilterIndex``, from ``ops.topk_scores`` (gv_topk_scores: the same
 logits, a selection epilogue instead of a count).  ``topk_from_scores`` states the order on a materialised score matrix.
+
+Completion (no query list: which triplets are missing from the graph?): ``mine_triplets`` selects globally among all N x R x N
+triplets -- the K most confident new ones, or all above a threshold -- from ``ops.mine_scores`` (gv_mine_scores: subject and
+object tiles of the entity table stay in LDS while the relations are walked over them).  ``mine_from_scores`` states the rule on
+a materialised (R, N, N) tensor; ``mine_triplets_unfused`` is the per-relation GEMM cross-check.
 """
 import torch
 
@@ -249,6 +254,148 @@ def predict_topk_unfused(embedding, w, a, r, k, direction='o', filter_index=None
             score = score + flow_log_prob
         return topk_from_scores(score, k, f_lo, f_hi, ent)
     return _predict_topk(embedding, w, a, r, k, direction, filter_index, select)
+
+
+MineOverflow = ops.MineOverflow
+
+
+def _mine_args(k, threshold, max_results):
+    if (k is None) == (threshold is None):
+        raise ValueError('give exactly one of k and threshold')
+    if k is not None and int(k) < 1:
+        raise ValueError(f'k must be >= 1, got {k}')
+    if threshold is not None and float(threshold) != float(threshold):
+        raise ValueError('threshold is NaN')
+    if int(max_results) < 1:
+        raise ValueError(f'max_results must be >= 1, got {max_results}')
+
+
+def mine_from_scores(score, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                     max_results=ops.MINE_MAX_RESULTS):
+    """The mining rule of ``ops.mine_scores`` on a materialised tensor ``score[r, s, o]`` (R, N, N), in plain torch (any device,
+    CPU included).  Candidates: every (s, r, o), less ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r),
+    less s == o when ``exclude_self``, less NaN logits.  Order, a strict total one: logit descending with -0 == +0, then
+    (s, r, o) ascending.  ``threshold=t`` selects every candidate with logit >= t, ``k=K`` the first K (fewer if fewer exist).
+    Returns ``(triplets int64 (n, 3), logits float32 (n,), info)`` in that order, -0 reported as +0; ``info['count']`` is the
+    number of candidates at or above the threshold (top-K: at or above the K-th logit's exact value; all, when fewer than K
+    exist).  More than ``max_results`` of those raise ``MineOverflow`` carrying the count: nothing is truncated silently."""
+    _mine_args(k, threshold, max_results)
+    num_rels, n = score.shape[0], score.shape[1]
+    val = score.to(torch.float32) + 0.0
+    cand = ~torch.isnan(val)
+    if exclude_self:
+        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
+    if filt_lo is not None and n:
+        listed = _listed_mask(filt_lo, filt_hi, filt_ent, n * num_rels, n, val.device)      # rows: key s * R + r
+        cand &= ~listed.view(n, num_rels, n).permute(1, 0, 2)
+    info = {'passes': 0}
+    if k is not None:
+        vals = val[cand]
+        if vals.numel() > int(k):
+            cand &= val >= torch.topk(vals, int(k)).values[-1]
+    else:
+        cand &= val >= float(threshold)
+    r, s, o = torch.nonzero(cand, as_tuple=True)
+    trip, logits = torch.stack([s, r, o], 1), val[cand]
+    if k is not None:
+        trip, logits, info['count'] = ops.mine_select(trip, logits, int(k), int(max_results), n, num_rels)
+        return trip, logits, info
+    info['count'] = int(logits.numel())
+    if info['count'] > int(max_results):
+        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
+    return ops.mine_order(trip, logits, n, num_rels) + (info,)
+
+
+def _mine_filter(filter_index, n, num_rels, device):
+    """(lo, hi, ent) of ALL N * R object-query keys s * R + r: one searchsorted over the index."""
+    if filter_index is None:
+        return None, None, None
+    if filter_index.num_nodes != n or filter_index.num_rels != num_rels:
+        raise ValueError(f'the FilterIndex is for {filter_index.num_nodes} entities / {filter_index.num_rels} relations, the tables '
+                         f'have {n} / {num_rels}')
+    a = torch.arange(n, device=device).repeat_interleave(num_rels)
+    r = torch.arange(num_rels, device=device).repeat(n)
+    lo, hi = filter_index.lookup(a, r, 'o')
+    return lo, hi, filter_index.entities('o', device)
+
+
+def _mine_bias(flow_log_prob, device):
+    if flow_log_prob is None:
+        return None
+    return torch.as_tensor(flow_log_prob, dtype=torch.float32).detach().to(device).reshape(1)
+
+
+def mine_triplets(embedding, w, *, k=None, threshold=None, filter_index=None, flow_log_prob=None, exclude_self=True,
+                  max_results=ops.MINE_MAX_RESULTS):
+    """Knowledge-graph completion: among ALL triplets (s, r, o), scored as every scorer here scores them (logit =
+    (e_s * w_r) . e_o + flow_log_prob), the ``k`` most confident ones or every one with logit >= ``threshold`` (a probability p
+    is the logit log(p / (1 - p))); with a ``FilterIndex`` the known triplets are left out (new facts only).  One fused sweep
+    per pass (ops.mine_scores); returns ``(triplets int64 (n, 3), logits float32 (n,), info)`` in the order of
+    ``mine_from_scores``, and raises ``MineOverflow`` rather than truncating."""
+    _mine_args(k, threshold, max_results)
+    emb = embedding.detach()
+    wd = w.detach().to(emb.device)
+    lo, hi, ent = _mine_filter(filter_index, emb.shape[0], wd.shape[0], emb.device)
+    return ops.mine_scores(emb, wd, threshold=threshold, k=k, bias=_mine_bias(flow_log_prob, emb.device), filt_lo=lo, filt_hi=hi,
+                           filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
+
+
+def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=None, flow_log_prob=None, exclude_self=True,
+                          max_results=ops.MINE_MAX_RESULTS):
+    """``mine_triplets`` from materialised logits, one relation at a time (``ops.mul`` + ``ops.gemm`` + torch selection, a running
+    K-th logit pruning the pool): the in-repo cross-check and the bench's baseline, never a fallback."""
+    _mine_args(k, threshold, max_results)
+    emb = embedding.detach().contiguous()
+    wd = w.detach().to(emb.device).contiguous()
+    n, num_rels = emb.shape[0], wd.shape[0]
+    lo, hi, ent = _mine_filter(filter_index, n, num_rels, emb.device)
+    bias = _mine_bias(flow_log_prob, emb.device)
+    k = None if k is None else int(k)
+    floor = None if k is not None else float(threshold)
+    pool_t, pool_v, held = [], [], 0
+    diag = torch.eye(n, dtype=torch.bool, device=emb.device) if exclude_self else None
+
+    def prune():
+        nonlocal pool_t, pool_v, held, floor
+        t, v = torch.cat(pool_t), torch.cat(pool_v)
+        if v.numel() > k:
+            floor = float(torch.topk(v, k).values[-1])
+            keep = v >= floor
+            t, v = t[keep], v[keep]
+        pool_t, pool_v, held = [t], [v], v.numel()
+
+    for r in range(num_rels):
+        val = ops.gemm(ops.mul(emb, wd[r].expand_as(emb).contiguous()), emb, trans_b=True, precision='f32')
+        if bias is not None:
+            val = val + bias
+        val = val + 0.0
+        cand = ~torch.isnan(val)
+        if diag is not None:
+            cand &= ~diag
+        if lo is not None:
+            cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], ent, n, n, emb.device)
+        if floor is not None:
+            cand &= val >= floor
+        if k is not None and floor is None:           # no bound yet: this relation's own K-th logit
+            vals = val[cand]
+            if vals.numel() > k:
+                cand &= val >= torch.topk(vals, k).values[-1]
+        s, o = torch.nonzero(cand, as_tuple=True)
+        pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
+        pool_v.append(val[cand])
+        held += s.numel()
+        if k is not None and held > max(4 * k, 1 << 20):
+            prune()
+    info = {'passes': num_rels}
+    trip = torch.cat(pool_t) if pool_t else torch.zeros(0, 3, dtype=torch.int64, device=emb.device)
+    logits = torch.cat(pool_v) if pool_v else torch.zeros(0, dtype=torch.float32, device=emb.device)
+    if k is not None:
+        trip, logits, info['count'] = ops.mine_select(trip, logits, int(k), int(max_results), n, num_rels)
+        return trip, logits, info
+    info['count'] = int(logits.numel())
+    if info['count'] > int(max_results):
+        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
+    return ops.mine_order(trip, logits, n, num_rels) + (info,)
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

@@ -142,7 +142,48 @@ def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=N
     return n
 
 
+def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None):
+    """Knowledge-graph completion as TSV, ``s  r  o  rank  logit``: the new triplets (``filter_index``: the known ones left out,
+    s != o) that ``ranking.mine_triplets`` selects among ALL N x R x N -- the ``k`` most confident and / or those whose
+    probability sigmoid(logit) reaches ``threshold`` -- best first.  Returns the number of lines written."""
+    with torch.no_grad():
+        if k:
+            trip, logits, _ = ranking.mine_triplets(embed, w, k=k, filter_index=filter_index, flow_log_prob=flow_log_prob)
+            if threshold is not None:
+                keep = logits >= _logit_of(threshold)
+                trip, logits = trip[keep], logits[keep]
+        else:
+            trip, logits, _ = ranking.mine_triplets(embed, w, threshold=_logit_of(threshold), filter_index=filter_index,
+                                                    flow_log_prob=flow_log_prob)
+    return _write_triplets(path, trip, logits)
+
+
+def _logit_of(p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f'a probability lies in [0, 1], got {p}')
+    return float('-inf') if p == 0.0 else float('inf') if p == 1.0 else float(np.log(p / (1.0 - p)))
+
+
+def _write_triplets(path, trip, logits):
+    with open(path, 'w') as f:
+        f.writelines(f"{s}\t{r}\t{o}\t{i}\t{x:.9g}\n" for i, ((s, r, o), x) in enumerate(zip(trip.tolist(), logits.tolist())))
+    return trip.shape[0]
+
+
+def check_args(args):
+    """Flag combinations that are refused before anything is loaded."""
+    wants = [f for f, on in (('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
+                             ('--complete-threshold', getattr(args, 'complete_threshold', None) is not None),
+                             ('--sample-graph', getattr(args, 'sample_graph', 0) > 0)) if on]
+    if wants and args.test_mode is not True:
+        raise ValueError(f"{' / '.join(wants)} decode a trained checkpoint: pass --test-mode True (and --model-state-file)")
+    if getattr(args, 'complete_threshold', None) is not None:
+        _logit_of(args.complete_threshold)
+
+
 def main(args):
+    check_args(args)
     data = load_data(args.dataset)
     num_nodes, num_rels = data.num_nodes, data.num_rels
     train_data, valid_data, test_data = data.train, data.valid, data.test
@@ -193,6 +234,18 @@ def main(args):
                                         model.encoder.get_flow_log_prob())
             print(f"wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to "
                   f"{args.predict_out}")
+        if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
+            known = filters if filters is not None else \
+                ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            n_lines = write_completions(args.complete_out, embed, model.w_relation, known, k=args.complete_topk or None,
+                                        threshold=args.complete_threshold, flow_log_prob=model.encoder.get_flow_log_prob())
+            print(f"wrote {n_lines} new triplets (all {num_nodes} x {num_rels} x {num_nodes} scored, known triplets filtered) to "
+                  f"{args.complete_out}")
+        if getattr(args, 'sample_graph', 0) > 0:
+            from . import generate
+            _, trip, logits = generate.sample_graph(model, args.sample_graph, k=args.sample_topk)
+            print(f"wrote {_write_triplets(args.sample_out, trip, logits)} triplets of a graph decoded from {args.sample_graph} "
+                  f"prior samples to {args.sample_out}")
         if filters is not None:
             return ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
                                              eval_bz=args.eval_batch_size, all_batches=True,
@@ -342,6 +395,20 @@ def build_parser():
                         "(train + valid + test triplets filtered out) to --predict-out; 0 = off; not a reference flag")
     p.add_argument("--predict-out", type=str, default="predictions.tsv",
                    help="TSV of --predict-topk: direction, query entity, relation, position, predicted entity, logit")
+    p.add_argument("--complete-topk", type=int, default=0,
+                   help="with --test-mode: score ALL triplets (s, r, o) and write the K most confident NEW ones (train + valid + "
+                        "test triplets and s == o left out) to --complete-out; 0 = off; not a reference flag")
+    p.add_argument("--complete-threshold", type=float, default=None,
+                   help="with --test-mode: write every new triplet whose probability reaches P (with --complete-topk: the K best, "
+                        "cut at P) to --complete-out")
+    p.add_argument("--complete-out", type=str, default="completions.tsv",
+                   help="TSV of --complete-topk / --complete-threshold: subject, relation, object, rank, logit")
+    p.add_argument("--sample-graph", type=int, default=0,
+                   help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
+                        "confident triplets among them to --sample-out; 0 = off")
+    p.add_argument("--sample-topk", type=int, default=1000, help="triplets kept by --sample-graph")
+    p.add_argument("--sample-out", type=str, default="sampled_graph.tsv",
+                   help="TSV of --sample-graph: subject, relation, object, rank, logit")
     return p
 
 

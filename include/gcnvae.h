@@ -546,6 +546,30 @@ int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const flo
                    const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits, void* workspace, int m, int v,
                    int h, void* stream);
 
+/* Whole-graph triplet mining (csrc/k_mine.hip): every triplet of a DistMult decoder scored and selected globally, for the
+ * entity table e (n, h) and the relation rows w (num_rels, h), both fp32 row-major:
+ *   logit[s, r, o] = (e[s] * w[r]) . e[o] (+ *bias)
+ * bit for bit gv_gemm_f32(gv_mul(e, w[r]), e^T) + bias (one f32 multiply per element, the k-ordered f32 MFMA chain, one add), so
+ * the subject side carries w[r] and the s <-> o symmetry is not used.  Candidates: all (s, r, o), less the triplets of the filter
+ * -- key s * num_rels + r -> filt_ent[filt_lo[key] .. filt_hi[key]), ranges clamped into [0, n_filt_ent); all three NULL: no
+ * filter --, less s == o when exclude_self, less NaN logits.  A candidate's key is ordered_u32(logit), the sign-flip map of
+ * gv_topk_scores: -0 -> +0, then a negative float's bits inverted and a non-negative one's sign bit set, so that a larger key is
+ * a larger logit; key 0 is NaN only.  One call is one pass over the n * num_rels * n product:
+ *   GV_MINE_EMIT  every candidate with key >= key_min is written as four int32 (s, r, o, bits of the logit with -0 as +0) to
+ *                 out [capacity][4] (16-byte aligned) in arbitrary order; *counter (uint64, zeroed here) ends as the number of
+ *                 such candidates, which may exceed the capacity: records past it are counted and not written.
+ *   GV_MINE_HIST  hist [1 << bin_bits] (uint64, zeroed here): among the candidates whose top prefix_bits key bits equal
+ *                 `prefix` (prefix_bits 0: all), the count per value of the next bin_bits key bits.  1 <= bin_bits <= 12.
+ * The unused mode's arguments are ignored.  workspace (only with a filter): gv_mine_scores_workspace_bytes(n, num_rels,
+ * n_filt_ent) bytes, 16-byte aligned.  n * num_rels < 2^31, num_rels <= 2^19, any h >= 1 and ld >= h; n == 0: nothing is
+ * launched.  Integer atomics on the counter and the histograms only; the result does not depend on the launch geometry. */
+enum { GV_MINE_EMIT = 0, GV_MINE_HIST = 1 };
+int64_t gv_mine_scores_workspace_bytes(int n, int num_rels, int n_filt_ent);
+int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,
+                   const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode, uint32_t key_min,
+                   int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity, uint64_t* counter,
+                   uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Entity classification (kgvae/entity_classify.py; csrc/k_ec.hip).  Deterministic: fixed summation orders, no float atomics.
  *
