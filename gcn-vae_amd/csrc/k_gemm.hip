@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "k_topk.h"
 
 namespace gv {
 
@@ -409,15 +410,6 @@ struct RankFiltParams {
     int* count_filt;
 };
 
-__device__ __forceinline__ int lower_bound_i32(const int* a, int lo, int hi, int key) {
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltParams fp) {
     constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1;
     __shared__ float As[BK * LDA_S];
@@ -513,6 +505,7 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
 // survivor.  Once a list is warm almost nothing passes, so a tile costs a compare and a ballot per row.  Filtered columns get key 0
 // through a per-row cursor into the sorted filter list (the next listed id is kept in LDS: a window without entries reads
 // nothing).  The span's k keys per row go to the workspace.  Stage 2 (k_topk_merge): one wave per row merges the S span lists.
+// Key, list, cursor and merge live in k_topk.h, which gv_transe_topk (k_transe.hip) shares.
 struct TopkParams {
     GemmParams g;                 // a = Q, b = E (stored [v, h]), m, n = v, k = h
     const float* bias;
@@ -525,53 +518,6 @@ struct TopkParams {
     int n_spans;
     unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
 };
-
-constexpr int TOPK_MAX = 128;
-
-__device__ __forceinline__ unsigned long long topk_key(float x, int col) {
-    unsigned u = __float_as_uint(x);
-    if (x != x) u = 0u;
-    else {
-        if (u == 0x80000000u) u = 0u;
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((unsigned long long)u << 32) | (unsigned)~col;
-}
-
-__device__ __forceinline__ float topk_key_logit(unsigned long long key) {
-    const unsigned o = (unsigned)(key >> 32);
-    if (key == 0ull) return -__builtin_huge_valf();
-    if (o == 0u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x, int lane) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// insert `key` into the wave's sorted (descending) list: lane l holds positions l + 64 j in a[j]; the last position falls off
-template <int NK>
-__device__ __forceinline__ void topk_insert(unsigned long long (&a)[NK], unsigned long long key, int lane) {
-    unsigned long long up[NK];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) up[j] = __shfl(a[j], (lane + 63) & 63);     // lane l gets lane l - 1's (lane 0: lane 63's)
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        const unsigned long long prev = lane ? up[j] : (j ? up[j - 1] : ~0ull);
-        a[j] = a[j] > key ? a[j] : (prev > key ? key : prev);
-    }
-}
-
-template <int NK>
-__device__ __forceinline__ void topk_insert_mask(unsigned long long (&a)[NK], unsigned long long keyv, unsigned long long sv, int lane) {
-    while (sv) {
-        const int c = __builtin_ctzll(sv);
-        sv &= sv - 1ull;
-        topk_insert<NK>(a, readlane_u64(keyv, c), lane);
-    }
-}
 
 template <int NK>
 __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
@@ -602,14 +548,8 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
     if (threadIdx.x < BM) {
         const int rl = threadIdx.x, row = m0 + rl;
         thr[rl] = 0ull;
-        int lo = 0, hi = 0;
-        if (filtered && row < p.m) {
-            lo = min(max(tp.filt_lo[row], 0), tp.n_ent);
-            hi = min(max(tp.filt_hi[row], lo), tp.n_ent);
-            lo = lower_bound_i32(tp.filt_ent, lo, hi, t_begin * BN);
-        }
-        cur[rl] = lo; fhi[rl] = hi;
-        nxt[rl] = lo < hi ? tp.filt_ent[lo] : INT_MAX;
+        topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && row < p.m, row, t_begin * BN, &cur[rl], &fhi[rl],
+                          &nxt[rl]);
     }
     const float bv = tp.bias ? *tp.bias : 0.f;
 
@@ -646,32 +586,10 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
             const int rl = wid * (BM / 4) + i;
             if (m0 + rl >= p.m) break;
             unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], col) : 0ull;
-            if (filtered && nxt[rl] < n0 + BN) {                  // this row lists ids inside the tile: mark them, advance the cursor
-                const int c0 = cur[rl], hi = fhi[rl], tag = (t - t_begin) * BM + rl + 1;
-                const int idx = c0 + lane;
-                const int ent = idx < hi ? tp.filt_ent[idx] : INT_MAX;
-                const bool win = ent < n0 + BN;
-                const int cnt = __popcll(__ballot(win));
-                const unsigned bit = (unsigned)(ent - n0);
-                if (win && bit < 64u) fl[wid][bit] = tag;
-                if (fl[wid][lane] == tag) key = 0ull;
-                const int c1 = c0 + cnt;
-                const int nx = cnt < 64 ? __shfl(ent, cnt) : (c1 < hi ? tp.filt_ent[c1] : INT_MAX);
-                if (lane == 0) { cur[rl] = c1; nxt[rl] = nx; }
-            }
-            const unsigned long long sv = __ballot(key > thr[rl]);
-            if (sv) {
-                unsigned long long a[NK];
-                unsigned long long* lst = lists + rl * k;
-#pragma unroll
-                for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? lst[lane + 64 * j] : 0ull;
-                topk_insert_mask<NK>(a, key, sv, lane);
-#pragma unroll
-                for (int j = 0; j < NK; ++j) {
-                    if (lane + 64 * j < k) lst[lane + 64 * j] = a[j];
-                    if (lane + 64 * j == k - 1) thr[rl] = a[j];
-                }
-            }
+            if (filtered && nxt[rl] < n0 + BN &&                  // this row lists ids inside the tile: mark them, advance the cursor
+                topk_filter_window(tp.filt_ent, n0, (t - t_begin) * BM + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
+                key = 0ull;
+            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
         }
     }
     // each wave hands its own rows' lists on (written by this wave only: no barrier)
@@ -680,34 +598,6 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
         if (row >= p.m) break;
         unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
         for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
-    }
-}
-
-// stage 2: one wave per row merges the n_spans sorted lists of k keys and decodes the first k
-template <int NK>
-__global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* part, int m, int n_spans, int k, int* out_ids,
-                                                    float* out_logits) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= m) return;
-    const unsigned long long* src = part + (size_t)row * n_spans * k;
-    unsigned long long a[NK];
-#pragma unroll
-    for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? src[lane + 64 * j] : 0ull;     // span 0 is sorted already
-    for (int s = 1; s < n_spans; ++s) {
-        const unsigned long long t = readlane_u64(a[(k - 1) >> 6], (k - 1) & 63);
-#pragma unroll
-        for (int j = 0; j < NK; ++j) {
-            const unsigned long long key = lane + 64 * j < k ? src[(size_t)s * k + lane + 64 * j] : 0ull;
-            topk_insert_mask<NK>(a, key, __ballot(key > t), lane);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < NK; ++j) {
-        const int pos = lane + 64 * j;
-        if (pos < k) {
-            out_ids[(size_t)row * k + pos] = (int)~(unsigned)a[j];
-            out_logits[(size_t)row * k + pos] = topk_key_logit(a[j]);
-        }
     }
 }
 
@@ -1213,18 +1103,6 @@ extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e,
 }
 
 
-// spans per query-row tile: about 4 workgroups per CU of the MI355X (256 CUs) at any m, each span at least 8 column tiles long so
-// the running lists warm up.  A fixed CU count keeps the workspace size a function of (m, v, k) alone.
-static void topk_spans(int m, int v, int* span_tiles, int* n_spans) {
-    const long long row_tiles = ((long long)m + 63) / 64, col_tiles = ((long long)v + 63) / 64;
-    long long s = (4 * 256 + row_tiles - 1) / row_tiles;
-    s = std::min(s, std::max(1LL, col_tiles / 8));
-    s = std::max(1LL, std::min(s, 64LL));
-    const long long per = (col_tiles + s - 1) / s;
-    *span_tiles = (int)per;
-    *n_spans = (int)((col_tiles + per - 1) / per);
-}
-
 extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
     if (m <= 0 || v <= 0 || k < 1 || k > TOPK_MAX) return 0;
     int span_tiles = 0, n_spans = 0;
@@ -1259,16 +1137,17 @@ extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e
     hipStream_t st = (hipStream_t)stream;
     const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 27 KiB static)
     dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
+    const TopkLogitOut out{out_ids, out_logits};
     if (k <= 64) {
         hipLaunchKernelGGL(k_topk_span<1>, grid, block, lds, st, tp);
-        hipLaunchKernelGGL(k_topk_merge<1>, mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out_ids, out_logits);
+        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
     } else {
         static unsigned long long lds_raised = 0;
         if (!raise_dynamic_lds((const void*)k_topk_span<2>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
                                "gv_topk_scores"))
             return GV_ERR_SHAPE;
         hipLaunchKernelGGL(k_topk_span<2>, grid, block, lds, st, tp);
-        hipLaunchKernelGGL(k_topk_merge<2>, mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out_ids, out_logits);
+        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
     }
     return launch_status("gv_topk_scores");
 }

@@ -1,0 +1,174 @@
+// Top-k selection shared by gv_topk_scores (k_gemm.hip: MFMA logits) and gv_transe_topk (k_transe.hip: L1 / L2 distances): the
+// ordered 64-bit key, the per-row sorted list with its wave-wide insert, the cursor over a row's sorted filter list, the span
+// geometry and the merge of the spans' lists.  The two kernels differ in how a 64 x 64 tile of values is made, not in how the
+// best k of a row are kept.
+//
+// Candidates are ordered by a 64-bit key, larger = better:
+//   key = ordered_u32(value) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
+// a strict total order (ties on the value by lower id); key 0 is "no candidate" and decodes to id -1, value -inf.
+#pragma once
+#include <limits.h>
+
+#include <algorithm>
+
+#include "common.h"
+
+namespace gv {
+
+constexpr int TOPK_MAX = 128;
+
+__device__ __forceinline__ unsigned long long topk_key(float x, int col) {
+    unsigned u = __float_as_uint(x);
+    if (x != x) u = 0u;
+    else {
+        if (u == 0x80000000u) u = 0u;
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    return ((unsigned long long)u << 32) | (unsigned)~col;
+}
+
+__device__ __forceinline__ float topk_key_logit(unsigned long long key) {
+    const unsigned o = (unsigned)(key >> 32);
+    if (key == 0ull) return -__builtin_huge_valf();
+    if (o == 0u) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__device__ __forceinline__ int topk_key_id(unsigned long long key) { return (int)~(unsigned)key; }
+
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x, int lane) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// insert `key` into the wave's sorted (descending) list: lane l holds positions l + 64 j in a[j]; the last position falls off
+template <int NK>
+__device__ __forceinline__ void topk_insert(unsigned long long (&a)[NK], unsigned long long key, int lane) {
+    unsigned long long up[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) up[j] = __shfl(a[j], (lane + 63) & 63);     // lane l gets lane l - 1's (lane 0: lane 63's)
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const unsigned long long prev = lane ? up[j] : (j ? up[j - 1] : ~0ull);
+        a[j] = a[j] > key ? a[j] : (prev > key ? key : prev);
+    }
+}
+
+template <int NK>
+__device__ __forceinline__ void topk_insert_mask(unsigned long long (&a)[NK], unsigned long long keyv, unsigned long long sv, int lane) {
+    while (sv) {
+        const int c = __builtin_ctzll(sv);
+        sv &= sv - 1ull;
+        topk_insert<NK>(a, readlane_u64(keyv, c), lane);
+    }
+}
+
+__device__ __forceinline__ int lower_bound_i32(const int* a, int lo, int hi, int key) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ---- the filter cursor of one query row (state in LDS, one entry per row of the workgroup's tile) ------------------------
+// cur: the position in filt_ent of the first listed id not yet passed, fhi: the row's range end, nxt: the id at the cursor
+// (INT_MAX: none left), so that a window without listed ids reads nothing from memory.
+__device__ __forceinline__ void topk_filter_begin(const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_ent, bool live,
+                                                  long long row, int first_col, int* cur, int* fhi, int* nxt) {
+    int lo = 0, hi = 0;
+    if (live) {
+        lo = min(max(filt_lo[row], 0), n_ent);
+        hi = min(max(filt_hi[row], lo), n_ent);
+        lo = lower_bound_i32(filt_ent, lo, hi, first_col);
+    }
+    *cur = lo; *fhi = hi;
+    *nxt = lo < hi ? filt_ent[lo] : INT_MAX;
+}
+
+// One wave, one lane per column of the window [n0, n0 + 64) of a row whose cursor says it lists ids inside the window: marks the
+// listed columns in the wave's flag words (flw[j] == tag <=> column j of the row at hand is listed; tags are unique per row and
+// window, so the flags are never cleared), advances the cursor past the window and returns whether this lane's column is listed.
+__device__ __forceinline__ bool topk_filter_window(const int* filt_ent, int n0, int tag, int lane, int* cur, const int* fhi, int* nxt,
+                                                   int* flw) {
+    const int c0 = *cur, hi = *fhi;
+    const int idx = c0 + lane;
+    const int ent = idx < hi ? filt_ent[idx] : INT_MAX;
+    const bool win = ent < n0 + 64;
+    const int cnt = __popcll(__ballot(win));
+    const unsigned bit = (unsigned)(ent - n0);
+    if (win && bit < 64u) flw[bit] = tag;
+    const bool listed = flw[lane] == tag;
+    const int c1 = c0 + cnt;
+    const int nx = cnt < 64 ? __shfl(ent, cnt) : (c1 < hi ? filt_ent[c1] : INT_MAX);
+    if (lane == 0) { *cur = c1; *nxt = nx; }
+    return listed;
+}
+
+// One wave: the lanes' keys that beat the row's k-th key (*thr) go into the row's sorted list lst[0, k) (LDS), *thr follows.
+template <int NK>
+__device__ __forceinline__ void topk_list_update(unsigned long long key, unsigned long long* lst, unsigned long long* thr, int k,
+                                                 int lane) {
+    const unsigned long long sv = __ballot(key > *thr);
+    if (sv) {
+        unsigned long long a[NK];
+#pragma unroll
+        for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? lst[lane + 64 * j] : 0ull;
+        topk_insert_mask<NK>(a, key, sv, lane);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            if (lane + 64 * j < k) lst[lane + 64 * j] = a[j];
+            if (lane + 64 * j == k - 1) *thr = a[j];
+        }
+    }
+}
+
+// ---- stage 2: one wave per row merges the n_spans sorted lists of k keys and hands the first k to `out` --------------------
+// Out::put(i, key) decodes key into entry i of the (m, k) outputs.
+struct TopkLogitOut {
+    int* ids;
+    float* logits;
+    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
+        ids[i] = topk_key_id(key);
+        logits[i] = topk_key_logit(key);
+    }
+};
+
+template <int NK, class Out>
+__global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* part, int m, int n_spans, int k, const Out out) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= m) return;
+    const unsigned long long* src = part + (size_t)row * n_spans * k;
+    unsigned long long a[NK];
+#pragma unroll
+    for (int j = 0; j < NK; ++j) a[j] = lane + 64 * j < k ? src[lane + 64 * j] : 0ull;     // span 0 is sorted already
+    for (int s = 1; s < n_spans; ++s) {
+        const unsigned long long t = readlane_u64(a[(k - 1) >> 6], (k - 1) & 63);
+#pragma unroll
+        for (int j = 0; j < NK; ++j) {
+            const unsigned long long key = lane + 64 * j < k ? src[(size_t)s * k + lane + 64 * j] : 0ull;
+            topk_insert_mask<NK>(a, key, __ballot(key > t), lane);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NK; ++j) {
+        const int pos = lane + 64 * j;
+        if (pos < k) out.put((size_t)row * k + pos, a[j]);
+    }
+}
+
+// spans per query-row tile: about 4 workgroups per CU of the MI355X (256 CUs) at any m, each span at least 8 column tiles long so
+// the running lists warm up.  A fixed CU count keeps the workspace size a function of (m, v, k) alone.
+inline void topk_spans(long long m, int v, int* span_tiles, int* n_spans) {
+    const long long row_tiles = (m + 63) / 64, col_tiles = ((long long)v + 63) / 64;
+    long long s = (4 * 256 + row_tiles - 1) / row_tiles;
+    s = std::min(s, std::max(1LL, col_tiles / 8));
+    s = std::max(1LL, std::min(s, 64LL));
+    const long long per = (col_tiles + s - 1) / s;
+    *span_tiles = (int)per;
+    *n_spans = (int)((col_tiles + per - 1) / per);
+}
+
+}  // namespace gv

@@ -15,8 +15,13 @@
 // occurrence: [h of b | t of b | corrupted side of (j, b)] for entities, [r of b] for relations.
 //
 // Ranker.  Distance of query q to entity j: ||q - n(E_j)||_p, summed over the columns in order with one accumulator
-// (p = 2: fmaf(d, d, acc), then sqrtf).  The fused ranker and gv_transe_distances share te_tile(), so their distances are the same bits.
+// (p = 2: fmaf(d, d, acc), then sqrtf).  The fused ranker, gv_transe_topk and gv_transe_distances share te_tile(), so their
+// distances are the same bits.
+//
+// Top-k (gv_transe_topk).  te_tile()'s distances with the selection of gv_topk_scores (k_topk.h) on the key of -distance: smaller
+// distance first, ties by lower id, NaN last; the distance matrix is never stored.
 #include "common.h"
+#include "k_topk.h"
 
 namespace gv {
 
@@ -484,6 +489,94 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
     }
 }
 
+
+// ---- fused top-k: te_tile() + the selection epilogue of gv_topk_scores ------------------------------------------------------------
+// Workgroup (x, y) owns query tile x and sweeps span y of 64-entity tiles in ascending id order.  The 16 distances a lane holds
+// after te_tile() go through LDS (ds) into one lane per column: wave w takes rows 16 w .. 16 w + 15, keys the column's distance as
+// topk_key(-d, id) -- larger key = smaller distance, ties by lower id, NaN below every number -- and inserts what beats the row's
+// running k-th key into the row's sorted LDS list.  Columns past v and listed ids get key 0 (no candidate).  The span's lists go to
+// the workspace; k_topk_merge<NK, TeDistOut> merges them, one wave per row.  Nothing depends on the span count: every span list is
+// the exact best k of its columns under a strict total order, and so is the merge.
+struct TeTopkParams {
+    const float* q;
+    const float* en;
+    const int32_t* filt_lo;       // NULL: no filter
+    const int32_t* filt_hi;
+    const int32_t* filt_ent;
+    int64_t m;
+    int v, dim, p;
+    int n_ent;                    // length of filt_ent: every range is clamped into it
+    int topk;                     // 1..TOPK_MAX
+    int span_tiles, n_spans;
+    unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
+};
+
+constexpr int TE_LDD = TE_TE + 4;      // row stride of the distance tile: float4 stores stay 16-byte aligned
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    __shared__ __attribute__((aligned(16))) float ds[TE_TQ * TE_LDD];     // the tile's distances, row-major
+    __shared__ unsigned long long thr[TE_TQ];                             // each row's k-th key
+    __shared__ int cur[TE_TQ], fhi[TE_TQ], nxt[TE_TQ];                    // filter cursor (k_topk.h)
+    __shared__ int fl[4][64];
+    extern __shared__ unsigned long long lists[];                         // [TE_TQ][topk]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, tx = tid & 15, ty = tid >> 4;
+    const int k = tp.topk;
+    const int64_t q0 = (int64_t)blockIdx.x * TE_TQ;
+    const int t_begin = blockIdx.y * tp.span_tiles;
+    const int t_end = min(t_begin + tp.span_tiles, (tp.v + TE_TE - 1) / TE_TE);
+    const bool filtered = tp.filt_lo != nullptr;
+    for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (tid < TE_TQ) {
+        thr[tid] = 0ull;
+        topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && q0 + tid < tp.m, q0 + tid, t_begin * TE_TE,
+                          &cur[tid], &fhi[tid], &nxt[tid]);
+    }
+    for (int t = t_begin; t < t_end; ++t) {
+        const int e0 = t * TE_TE;
+        float acc[4][4];
+        // te_tile's first barrier publishes the set-up above and ends the last tile's reads of ds
+        te_tile(tp.q, tp.m, tp.en, tp.v, tp.dim, tp.p, q0, e0, qs, es, acc);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
+        __syncthreads();
+        const int col = e0 + lane;
+        for (int i = 0; i < TE_TQ / 4; ++i) {
+            const int rl = wid * (TE_TQ / 4) + i;
+            if (q0 + rl >= tp.m) break;
+            unsigned long long key = col < tp.v ? topk_key(-ds[rl * TE_LDD + lane], col) : 0ull;
+            if (filtered && nxt[rl] < e0 + TE_TE &&
+                topk_filter_window(tp.filt_ent, e0, (t - t_begin) * TE_TQ + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
+                key = 0ull;
+            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
+        }
+    }
+    // each wave hands its own rows' lists on (written by this wave only: no barrier)
+    for (int i = 0; i < TE_TQ / 4; ++i) {
+        const int rl = wid * (TE_TQ / 4) + i;
+        const int64_t row = q0 + rl;
+        if (row >= tp.m) break;
+        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
+        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// the key of -distance back to the distance: key 0 (no candidate) -> id -1, +inf; zero -> +0; NaN -> the one quiet NaN
+struct TeDistOut {
+    int64_t* ids;
+    float* dist;
+    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
+        ids[i] = (int64_t)topk_key_id(key);
+        const float x = topk_key_logit(key);                 // -distance, never -0
+        const unsigned b = __float_as_uint(x) ^ 0x80000000u;
+        dist[i] = x != x ? x : __uint_as_float(b == 0x80000000u ? 0u : b);
+    }
+};
+
 }  // namespace gv
 
 using namespace gv;
@@ -567,4 +660,46 @@ extern "C" int gv_transe_rank_filtered(const float* q, int64_t m, const float* e
     hipLaunchKernelGGL(k_transe_rank, dim3((unsigned)q_tiles, (unsigned)split), dim3(256), 0, GV_ST, q, m, en, v, dim, p_norm, target,
                        f_lo, f_hi, f_ent, counts_raw, counts_filt);
     return launch_status("gv_transe_rank_filtered");
+}
+
+extern "C" int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k) {
+    if (m <= 0 || m >= (1ll << 31) || v <= 0 || k < 1 || k > TOPK_MAX) return 0;
+    int span_tiles = 0, n_spans = 0;
+    topk_spans(m, v, &span_tiles, &n_spans);
+    return m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+extern "C" int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
+                              const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int k, int64_t* out_ids,
+                              float* out_dist, void* workspace, void* stream) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) &&
+                   n_filt_ent >= 0,
+               GV_ERR_SHAPE, "gv_transe_topk: m=%lld v=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", (long long)m, v, dim,
+               GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_transe_topk: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_transe_topk: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && en && out_ids && out_dist && workspace, GV_ERR_NULL, "gv_transe_topk: NULL pointer");
+    TeTopkParams tp{q, en, filt_lo, filt_hi, filt_ent, m, v, dim, p_norm, n_filt_ent, k, 0, 0, (unsigned long long*)workspace};
+    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
+    const int lds = TE_TQ * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 36 KiB static)
+    const dim3 grid((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), block(256), mgrid((unsigned)((m + 3) / 4));
+    const TeDistOut out{out_ids, out_dist};
+    if (k <= 64) {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_transe_topk_span<1>, TE_TQ * 64 * (int)sizeof(unsigned long long), lds_raised,
+                               "gv_transe_topk"))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_transe_topk_span<1>, grid, block, lds, GV_ST, tp);
+        hipLaunchKernelGGL((k_topk_merge<1, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_transe_topk_span<2>, TE_TQ * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
+                               "gv_transe_topk"))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_transe_topk_span<2>, grid, block, lds, GV_ST, tp);
+        hipLaunchKernelGGL((k_topk_merge<2, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
+    }
+    return launch_status("gv_transe_topk");
 }

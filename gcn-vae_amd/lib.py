@@ -121,6 +121,8 @@ SIGNATURES = {
     'gv_transe_queries': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     'gv_transe_distances': (_I, [_P, _L, _P, _I, _I, _I, _P, _P]),
     'gv_transe_rank_filtered': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    'gv_transe_topk_workspace_bytes': (_L, [_L, _I, _I]),
+    'gv_transe_topk': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -2956,3 +2956,51 @@ def transe_rank_filtered(q, en, target, p_norm, filt_lo=None, filt_hi=None, filt
              ptr(counts[0]), ptr(counts[1]), lib.stream())
     both = counts[:, :m].to(torch.float32) * 0.5
     return both[0], both[1]
+
+
+def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The ``k`` nearest entities of every query row under ``||q[i] - en[j]||_p`` -- ``transe_distances``' distances bit for bit
+    -- from one fused launch pair (gv_transe_topk) that never stores the distance matrix.  With a filter (as
+    ``transe_rank_filtered`` takes it) the ids ``filt_ent[filt_lo[i]:filt_hi[i]]`` are no candidates of row i.  Order: distance
+    ascending, equal distances by lower id, NaN after everything (+inf included).  Returns ``(ids int64 (m, k), dist float32
+    (m, k))``; rows with fewer than k candidates are padded with id -1, distance +inf.  A zero distance is reported as +0 and
+    every NaN as the one quiet NaN (``transe.topk_from_distances`` does the same)."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    if q.device != en.device:
+        raise ValueError(f'q on {q.device}, entities on {en.device}')
+    p_norm = _p_norm(p_norm)
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    m, v = q.shape[0], en.shape[0]
+    if v < 1:
+        raise ValueError('need at least one entity')
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    i32 = dict(device=q.device, dtype=torch.int32)
+    lo32 = hi32 = ent32 = None
+    n_ent = 0
+    if all(given):
+        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+        if filt_lo.numel() != m or filt_hi.numel() != m:
+            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+        n_ent = filt_ent.numel()
+        if n_ent >= 2 ** 31:
+            raise ValueError('filt_ent: more than 2**31 - 1 entries')
+        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
+            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
+            raise ValueError(f'filtered entity ids must lie in [0, {v})')
+        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    ids = torch.empty(m, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids, dist
+    ws = torch.empty(int(lib.load().gv_transe_topk_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_transe_topk', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k, ptr(ids),
+             ptr(dist), ptr(ws), lib.stream())
+    return ids, dist

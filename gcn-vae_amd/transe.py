@@ -32,7 +32,14 @@ Evaluation: raw and filtered MRR, MR and Hits@1/3/10 over both directions, filte
 the distance matrix.  The ``*_unfused`` functions are the plain-torch statement of the same rules: the in-repo cross-check and
 the bench's comparator, never a fallback.
 
+Link prediction: ``predict_topk`` names the ``k`` nearest entities of every query, (a, r, ?) or (?, r, a), with the query's known
+answers left out when a ``FilterIndex`` is given -- the same queries, table and distances as the ranker, selected by
+``ops.transe_topk`` (gv_transe_topk) without the distance matrix.  ``topk_from_distances`` states the order on a materialised
+matrix: distance ascending, ties by lower id, NaN last.  ``--predict-topk K --predict-out FILE`` writes both directions of the
+test split (filter: train + valid + test) in train.py's prediction TSV layout, the distance in place of the logit.
+
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
+    python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
 """
 import argparse
 import time
@@ -43,7 +50,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ranking import FilterIndex, _listed_mask, sort_and_rank
+from .ranking import FilterIndex, _listed_mask, sort_and_rank, topk_from_scores
 
 
 # ------------------------------------------------------------------------------------------------
@@ -423,6 +430,91 @@ def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False,
 
 
 # ------------------------------------------------------------------------------------------------
+# link prediction
+# ------------------------------------------------------------------------------------------------
+def topk_from_distances(dist, k, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The top-k rule of ``ops.transe_topk`` on a materialised (m, v) distance matrix, in plain torch (any device):
+    ``ranking.topk_from_scores(-dist, ...)`` -- smaller distance first, equal distances by lower id, NaN after every number (+inf
+    included) and by id among themselves, the ids in ``filt_ent[filt_lo[i]:filt_hi[i]]`` no candidates of row i.  Returns
+    ``(ids int64 (m, k), dist float32 (m, k))`` padded with id -1 / distance +inf; a reported distance is the matrix entry's bit
+    pattern, except that a zero is +0 and every NaN the one quiet NaN."""
+    ids, neg = topk_from_scores(-dist.to(torch.float32), k, filt_lo, filt_hi, filt_ent)
+    out = 0.0 - neg                                                   # -(+0) would be -0; 0 - (+0) is +0
+    return ids, torch.where(torch.isnan(out), torch.full_like(out, float('nan')), out)
+
+
+def _tables(model_or_tables):
+    if isinstance(model_or_tables, TransE):
+        m = model_or_tables
+        return m.ent_embeddings.weight.data, m.rel_embeddings.weight.data, m.p_norm, m.norm_flag
+    ent, rel, p_norm, norm_flag = model_or_tables
+    return ent.detach(), rel.detach(), p_norm, norm_flag
+
+
+def _predict_topk(model_or_tables, a, r, k, direction, filter_index, select):
+    if direction not in ('o', 's'):
+        raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
+    ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+    k = int(k)
+    a, r = a.to(ent.device), r.to(ent.device)
+    en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
+    ent_f = filter_index.entities(direction, ent.device) if filter_index is not None else None
+    ids, dist = [], []
+    for lo in range(0, a.numel(), MAX_QUERY_ROWS):
+        hi = min(a.numel(), lo + MAX_QUERY_ROWS)
+        q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=direction == 's', norm_flag=norm_flag)
+        f = (None, None, None)
+        if filter_index is not None:
+            f = (*filter_index.lookup(a[lo:hi], r[lo:hi], direction), ent_f)
+        i, d = select(q, en, p_norm, f)
+        ids.append(i)
+        dist.append(d)
+    if not ids:
+        return (torch.zeros(0, k, dtype=torch.int64, device=ent.device), torch.zeros(0, k, dtype=torch.float32, device=ent.device))
+    return torch.cat(ids), torch.cat(dist)
+
+
+def predict_topk(model_or_tables, a, r, k, direction='o', filter_index=None):
+    """Link prediction: the ``k`` nearest entities of every query, ``direction`` 'o' for (a[i], r[i], ?) with
+    ``q = n(a) + n(r)`` and 's' for (?, r[i], a[i]) with ``q = n(a) - n(r)``, at distance ``||q - n(E_j)||_p`` -- the queries and
+    distances of ``rank_transe``.  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``.  With a
+    ``FilterIndex`` the query's known answers are left out (new facts only).  One fused launch pair per ``MAX_QUERY_ROWS``
+    queries (ops.transe_topk); returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of ``topk_from_distances``."""
+    with torch.no_grad():
+        return _predict_topk(model_or_tables, a, r, k, direction, filter_index,
+                             lambda q, en, p, f: ops.transe_topk(q, en, k, p, *f))
+
+
+def predict_topk_unfused(model_or_tables, a, r, k, direction='o', filter_index=None):
+    """``predict_topk`` from materialised distances (``ops.transe_distances`` + ``topk_from_distances`` per chunk): the in-repo
+    cross-check and the bench's comparator, never a fallback."""
+    with torch.no_grad():
+        return _predict_topk(model_or_tables, a, r, k, direction, filter_index,
+                             lambda q, en, p, f: topk_from_distances(ops.transe_distances(q, en, p), k, *f))
+
+
+def write_predictions(path, model_or_tables, triplets, k, filter_index):
+    """Top-k link predictions for both directions of every triplet, the known answers (``filter_index``) left out, as TSV in
+    train.py's layout: ``direction  query_entity  relation  position  predicted_entity  distance`` -- 'o' lines answer (s, r, ?),
+    's' lines (?, r, o); a query with fewer than k candidates ends in id -1, distance inf.  Returns the number of lines written."""
+    triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
+    n = 0
+    with open(path, 'w') as f:
+        for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
+            r = triplets[:, 1]
+            ids, dist = predict_topk(model_or_tables, a, r, k, direction=d, filter_index=filter_index)
+            n += _write_rows(f, d, a.tolist(), r.tolist(), ids.tolist(), dist.tolist())
+    return n
+
+
+def _write_rows(f, direction, a, r, ids, values):
+    for i in range(len(a)):
+        head = f"{direction}\t{a[i]}\t{r[i]}\t"
+        f.writelines(f"{head}{p}\t{e}\t{x:.9g}\n" for p, (e, x) in enumerate(zip(ids[i], values[i])))
+    return sum(len(row) for row in ids)
+
+
+# ------------------------------------------------------------------------------------------------
 # CLI (baselines/transe/main.py's hyperparameters as defaults)
 # ------------------------------------------------------------------------------------------------
 def build_parser():
@@ -449,6 +541,11 @@ def build_parser():
     p.add_argument('--eval-every', type=int, default=0, help='evaluate on valid every N epochs (0: never)')
     p.add_argument('--filtered-eval', action='store_true', help='report filtered ranks as well (filter: train + valid + test)')
     p.add_argument('--graph-step', action='store_true', help='capture one step as a hipGraph and replay it')
+    p.add_argument('--predict-topk', type=int, default=None,
+                   help='after the final evaluation write the K (1..128) nearest new entities of both directions of every test '
+                        'triplet (train + valid + test triplets filtered out) to --predict-out')
+    p.add_argument('--predict-out', type=str, default='transe_predictions.tsv',
+                   help='TSV written by --predict-topk: direction, query entity, relation, position, entity, distance')
     return p
 
 
@@ -463,6 +560,9 @@ def check_args(args):
         raise ValueError('--adv-temperature must be > 0')
     if not 1 <= args.dim <= ops.TRANSE_MAX_DIM:
         raise ValueError(f'--dim must lie in [1, {ops.TRANSE_MAX_DIM}]')
+    k = getattr(args, 'predict_topk', None)
+    if k is not None and not 1 <= k <= ops.TOPK_MAX:
+        raise ValueError(f'--predict-topk must lie in [1, {ops.TOPK_MAX}], got {k}')
 
 
 def main(args):
@@ -498,7 +598,12 @@ def main(args):
         model.save_checkpoint(args.checkpoint)
     model.load_checkpoint(args.checkpoint)
     model = model.to(dev)
-    return evaluate(model, data.test, filt)
+    out = evaluate(model, data.test, filt)
+    if args.predict_topk is not None:
+        known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        n_lines = write_predictions(args.predict_out, model, data.test, args.predict_topk, known)
+        print(f'wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to {args.predict_out}')
+    return out
 
 
 if __name__ == '__main__':

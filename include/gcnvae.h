@@ -620,7 +620,14 @@ int gv_ec_head_bwd(const float* p, const int64_t* labels, const int32_t* row_pos
  *     q[i] = n(ent[i]) (the normalised table).  n = F.normalize (eps 1e-12) when norm_flag, the identity otherwise.
  *   gv_transe_distances : out [m, v] = ||q[i] - en[j]||_p, columns summed in order.
  *   gv_transe_rank_filtered : counts_raw[i] = 2 #{j != target: !(d_j >= d_target)} + #{j != target: d_j == d_target}; counts_filt
- *     the same over the j not in f_ent[f_lo[i], f_hi[i]) (NULL: no filter).  Distances are gv_transe_distances' bits. */
+ *     the same over the j not in f_ent[f_lo[i], f_hi[i]) (NULL: no filter).  Distances are gv_transe_distances' bits.
+ *   gv_transe_topk : the k (1..128) nearest entities of every query row, the distance matrix never stored: out_ids / out_dist [m, k],
+ *     smaller distance first, equal distances by lower id, NaN distances after every number (+inf included) and by id among
+ *     themselves; the ids in filt_ent[filt_lo[i], filt_hi[i]) (ranges clamped into [0, n_filt_ent]; all three NULL: no filter) are
+ *     no candidates of row i.  Rows with fewer than k candidates end in id -1, distance +inf.  A reported distance is
+ *     gv_transe_distances' bit pattern of that pair, a zero as +0 and every NaN as the one quiet NaN (0x7fc00000).  q as
+ *     gv_transe_queries writes it, en as gv_transe_rank_filtered takes it; workspace of gv_transe_topk_workspace_bytes(m, v, k)
+ *     bytes, 8-byte aligned.  The result does not depend on the launch geometry. */
 #define GV_TRANSE_MAX_DIM 512
 int gv_transe_sample(const uint64_t* rng_state, uint32_t stream_id, const int32_t* train, int64_t n_train, int n_ent,
                      const float* p_head, const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent_o, const int32_t* f_ent_s,
@@ -637,6 +644,10 @@ int gv_transe_distances(const float* q, int64_t m, const float* en, int v, int d
 int gv_transe_rank_filtered(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
                             const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, int32_t* counts_raw, int32_t* counts_filt,
                             void* stream);
+int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k);
+int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
+                   const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int k, int64_t* out_ids, float* out_dist,
+                   void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):

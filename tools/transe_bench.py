@@ -6,6 +6,12 @@ raw + filtered evaluation of the test split, and the same for the plain-torch fo
 process under a time limit and stops the bench at its first failure.
 
     python tools/transe_bench.py [--steps 200] [--warmup 20] [--limit 600]
+    python tools/transe_bench.py --topk [--out profiles/transe_topk/bench.json]
+
+--topk runs the link-prediction leg alone: both directions of the test split (40 932 queries), filter = train + valid + test,
+L1 and L2, k = 10 and 100; per configuration predict_topk (fused), predict_topk_unfused (materialised distances + sort) and
+rank_transe on the same queries (the bare distance sweep with a counting epilogue).  Each is warmed up once and timed over
+--topk-repeats synchronised runs; the median and the minimum are reported, in ms.
 
 Step bytes: algorithmic, counting the gathered rows (3 per positive + 1 per negative), the occurrence gradients written and read,
 and the touched table rows read and written once, against 8 TB/s.  Scorer: |a - b| terms at ~1.5 VALU instructions each against
@@ -111,6 +117,44 @@ def case_torch_eval(steps, warmup):
     return dict(torch_eval_ms=us / 1e3)
 
 
+def _repeat_ms(fn, repeats):
+    fn()                                                  # warm-up: library load, allocator, LDS attribute
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        out.append(s.elapsed_time(e))
+    return dict(median_ms=float(np.median(out)), min_ms=float(min(out)), runs=[round(x, 3) for x in out])
+
+
+def case_topk(steps, warmup, repeats=5):
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.ranking import FilterIndex
+    data, model = setup()
+    fi = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device='cuda')
+    test = torch.as_tensor(np.asarray(data.test), dtype=torch.long).cuda()
+    ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+    s, r, o = test[:, 0], test[:, 1], test[:, 2]
+    res = dict(queries=2 * len(test), entities=data.num_nodes, dim=200, repeats=repeats)
+    for p in (1, 2):
+        tables = (ent, rel, p, True)
+
+        def both(fn, k):
+            fn(tables, s, r, k, direction='o', filter_index=fi)
+            fn(tables, o, r, k, direction='s', filter_index=fi)
+        res[f'rank_p{p}'] = _repeat_ms(lambda: transe.rank_transe(ent, rel, test, p, True, fi), repeats)
+        for k in (10, 100):
+            fused = _repeat_ms(lambda: both(transe.predict_topk, k), repeats)
+            unfused = _repeat_ms(lambda: both(transe.predict_topk_unfused, k), max(2, repeats // 2))
+            res[f'p{p}_k{k}'] = dict(fused=fused, unfused=unfused, unfused_over_fused=unfused['median_ms'] / fused['median_ms'],
+                                     fused_over_rank=fused['median_ms'] / res[f'rank_p{p}']['median_ms'])
+    return res
+
+
 CASES = {'step': case_step, 'eval': case_eval, 'torch_step': case_torch_step, 'torch_eval': case_torch_eval}
 
 
@@ -120,7 +164,27 @@ def main():
     ap.add_argument('--warmup', type=int, default=20)
     ap.add_argument('--limit', type=int, default=600)
     ap.add_argument('--case', default=None, help=argparse.SUPPRESS)
+    ap.add_argument('--topk', action='store_true', help='run the link-prediction leg alone')
+    ap.add_argument('--topk-repeats', type=int, default=5)
+    ap.add_argument('--out', default=None, help='with --topk: also write the JSON result to this file')
     a = ap.parse_args()
+    if a.case == 'topk':
+        print('RESULT ' + json.dumps(case_topk(a.steps, a.warmup, a.topk_repeats)))
+        return
+    if a.topk:
+        r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__), '--case', 'topk',
+                            '--topk-repeats', str(a.topk_repeats)], capture_output=True, text=True, cwd=ROOT)
+        line = [x for x in r.stdout.splitlines() if x.startswith('RESULT ')]
+        if r.returncode != 0 or not line:
+            print(json.dumps(dict(failed=r.returncode, tail=(r.stdout + r.stderr)[-1500:])), file=sys.stderr)
+            sys.exit(1)
+        text = json.dumps(json.loads(line[0][7:]), indent=1)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write(text + '\n')
+        return
     if a.case:
         print('RESULT ' + json.dumps(CASES[a.case](a.steps, a.warmup)))
         return
