@@ -408,13 +408,23 @@ struct RankFiltParams {
     const int* filt_ent;
     int n_ent;               // length of filt_ent: every range is clamped into it
     int* count_filt;
+    // CAND only (gv_rank_scores_constrained): per-query candidate sets, bit j & 31 of word j >> 5 of row cand_set[row] of `cand`
+    const uint32_t* cand;    // [n_sets, ld_cand]
+    const int* cand_set;     // one set id per query; outside [0, n_sets) = the empty set
+    int ld_cand, n_sets;
+    int* count_raw_c;
+    int* count_filt_c;       // NULL (as count_filt, filt_lo) when no filter is given
 };
 
+// CAND: the type-constrained protocol on top.  The tile's 64 columns are two words of the row's set, loaded once per row and
+// tile into LDS next to the filter word (the second word guarded: an odd word count has none for the last tile) and ANDed into
+// the same ballots, so the constrained counts see the very logits of the unconstrained ones.  The filter is optional there.
+template <bool CAND>
 __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltParams fp) {
     constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1;
     __shared__ float As[BK * LDA_S];
     __shared__ float Bs[BK * LDB_S];
-    __shared__ unsigned long long fmask[BM];       // 512 B: the tile's filter, one word per row
+    __shared__ unsigned long long fmask[CAND ? 2 * BM : BM];       // 512 B: the tile's filter, one word per row (CAND: + the set's)
     __shared__ int win_lo[BM], win_hi[BM];         // each row's entries inside [n0, n0 + 64)
     const RankParams& rp = fp.rp;
     const GemmParams& p = rp.g;
@@ -430,16 +440,28 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
     load_b<true, BN, BK>(p, n0, 0, p.k, rb);
 
     // filter window: thread t < 64 searches row t's list for n0, thread 64 + t for n0 + 64 (two waves, one search each)
+    const bool filtered = !CAND || fp.filt_lo != nullptr;
     if (threadIdx.x < 2 * BM) {
         const int rl = threadIdx.x & (BM - 1), row = m0 + rl;
         int lo = 0, hi = 0;
-        if (row < p.m) {
+        if (row < p.m && filtered) {
             lo = min(max(fp.filt_lo[row], 0), fp.n_ent);
             hi = min(max(fp.filt_hi[row], lo), fp.n_ent);
         }
         const int pos = lower_bound_i32(fp.filt_ent, lo, hi, threadIdx.x < BM ? n0 : n0 + BN);
         if (threadIdx.x < BM) { win_lo[rl] = pos; fmask[rl] = 0ull; }
         else win_hi[rl] = pos;
+    } else if (CAND && threadIdx.x < 3 * BM) {     // the third wave: row t's two set words for columns [n0, n0 + 64)
+        const int rl = threadIdx.x & (BM - 1), row = m0 + rl;
+        const int set = row < p.m ? fp.cand_set[row] : -1;
+        unsigned long long cw = 0ull;
+        if ((unsigned)set < (unsigned)fp.n_sets) {
+            const uint32_t* words = fp.cand + (size_t)set * fp.ld_cand;
+            const int w0 = n0 >> 5;                // n0 < v, so w0 < ceil(v / 32) <= ld_cand
+            cw = words[w0];
+            if (w0 + 1 < (p.n + 31) >> 5) cw |= (unsigned long long)words[w0 + 1] << 32;     // never past the set's last used word
+        }
+        fmask[BM + rl] = cw;
     }
     __syncthreads();
     // the window's entries, staged cooperatively: wave w takes rows 16 w .. 16 w + 15, one entry per lane (a long list costs its
@@ -488,8 +510,19 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
                 const int c = 2 * __popc(ha) + __popc(he);
                 if (c) atomicAdd(rp.count + row, c);
             }
-            const int cf = 2 * __popc(ha & keep) + __popc(he & keep);
-            if (cf) atomicAdd(fp.count_filt + row, cf);
+            if (!CAND || fp.count_filt) {
+                const int cf = 2 * __popc(ha & keep) + __popc(he & keep);
+                if (cf) atomicAdd(fp.count_filt + row, cf);
+            }
+            if (CAND) {      // `in` has dropped the columns >= v already, whatever the set's padding bits hold
+                const unsigned member = (unsigned)(fmask[BM + rl] >> wn);
+                const int cc = 2 * __popc(ha & member) + __popc(he & member);
+                if (cc) atomicAdd(fp.count_raw_c + row, cc);
+                if (fp.count_filt_c) {
+                    const int cfc = 2 * __popc(ha & keep & member) + __popc(he & keep & member);
+                    if (cfc) atomicAdd(fp.count_filt_c + row, cfc);
+                }
+            }
         }
     }
 }
@@ -517,9 +550,10 @@ struct TopkParams {
     int span_tiles;               // 64-column tiles per span (blockIdx.y = span)
     int n_spans;
     unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
+    TopkCand cs;                  // CAND only (gv_topk_scores_constrained)
 };
 
-template <int NK>
+template <int NK, bool CAND>
 __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
     constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1, LDL = BN + 1;
     __shared__ float As[BK * LDA_S];
@@ -552,9 +586,11 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
                           &nxt[rl]);
     }
     const float bv = tp.bias ? *tp.bias : 0.f;
+    const uint32_t* cand_row = CAND ? topk_cand_row(tp.cs, m0 + wid * (BM / 4), p.m, lane) : nullptr;
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * BN;
+        const unsigned cand_w = CAND ? topk_cand_word(cand_row, n0, p.n, lane) : 0u;     // lands under the MFMA chain
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -589,6 +625,7 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
             if (filtered && nxt[rl] < n0 + BN &&                  // this row lists ids inside the tile: mark them, advance the cursor
                 topk_filter_window(tp.filt_ent, n0, (t - t_begin) * BM + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
                 key = 0ull;
+            if (CAND && !topk_cand_member(cand_w, i, lane)) key = 0ull;
             topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
         }
     }
@@ -1072,15 +1109,12 @@ extern "C" int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e
     return launch_status("gv_rank_scores");
 }
 
-extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
-                                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
-                                       int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_filtered: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count_filt, GV_ERR_NULL, "gv_rank_scores_filtered: NULL pointer");
-    GV_REQUIRE(filt_lo && filt_hi && filt_ent, GV_ERR_NULL, "gv_rank_scores_filtered: NULL filter pointer");
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_filtered: leading dimension too small");
+// gv_rank_scores_filtered, and with `cand` its type-constrained form (the filter optional there)
+static int rank_filtered_any(const char* name, const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                             const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
+                             int ld_cand, int n_sets, const int* cand_set, float* tgt, int* count_raw, int* count_filt,
+                             int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
+    const bool constrained = cand != nullptr;
     RankFiltParams fp;
     RankParams& rp = fp.rp;
     GemmParams& p = rp.g;
@@ -1092,16 +1126,52 @@ extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e,
     p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
     rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
     fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent; fp.count_filt = count_filt;
+    fp.cand = cand; fp.cand_set = cand_set; fp.ld_cand = ld_cand; fp.n_sets = n_sets;
+    fp.count_raw_c = count_raw_c; fp.count_filt_c = count_filt_c;
     hipStream_t st = (hipStream_t)stream;
-    if (count_raw && fill_words(count_raw, 0u, (size_t)m * sizeof(int), st) != hipSuccess)
-        return launch_status("gv_rank_scores_filtered(fill)");
-    if (fill_words(count_filt, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status("gv_rank_scores_filtered(fill)");
+    for (int* c : {count_raw, count_filt, count_raw_c, count_filt_c})
+        if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status(name);
     dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
     hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);           // tgt[row] = the target's logit
-    hipLaunchKernelGGL(k_rank_scores_filtered, grid, block, 0, st, fp);
-    return launch_status("gv_rank_scores_filtered");
+    if (constrained) hipLaunchKernelGGL(k_rank_scores_filtered<true>, grid, block, 0, st, fp);
+    else hipLaunchKernelGGL(k_rank_scores_filtered<false>, grid, block, 0, st, fp);
+    return launch_status(name);
 }
 
+extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
+                                       int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_filtered: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count_filt, GV_ERR_NULL, "gv_rank_scores_filtered: NULL pointer");
+    GV_REQUIRE(filt_lo && filt_hi && filt_ent, GV_ERR_NULL, "gv_rank_scores_filtered: NULL filter pointer");
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_filtered: leading dimension too small");
+    return rank_filtered_any("gv_rank_scores_filtered", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, nullptr,
+                             0, 0, nullptr, tgt, count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
+}
+
+extern "C" int gv_rank_scores_constrained(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                                          const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                                          const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, float* tgt,
+                                          int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h,
+                                          void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_constrained: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_rank_scores_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_constrained: leading dimension too small");
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_rank_scores_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_rank_scores_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count_raw && count_raw_c, GV_ERR_NULL, "gv_rank_scores_constrained: NULL pointer");
+    GV_REQUIRE(!filt_lo || (count_filt && count_filt_c), GV_ERR_NULL, "gv_rank_scores_constrained: a filter needs both filtered counts");
+    const bool f = filt_lo != nullptr;        // without a filter the two filtered counts are not written
+    return rank_filtered_any("gv_rank_scores_constrained", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, cand,
+                             ld_cand, n_sets, cand_set, tgt, count_raw, f ? count_filt : nullptr, count_raw_c,
+                             f ? count_filt_c : nullptr, m, v, h, stream);
+}
 
 extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
     if (m <= 0 || v <= 0 || k < 1 || k > TOPK_MAX) return 0;
@@ -1110,17 +1180,11 @@ extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
     return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
 }
 
-extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
-                              const int* filt_hi, const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits,
-                              void* workspace, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
-               n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores: leading dimension too small");
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores: NULL pointer");
+// the launches of gv_topk_scores, and with cs.cand of its type-constrained form
+template <bool CAND>
+static int topk_scores_launch(const char* name, const float* q, int ld_q, const float* e, int ld_e, const float* bias,
+                              const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
+                              int* out_ids, float* out_logits, void* workspace, int m, int v, int h, void* stream) {
     TopkParams tp;
     GemmParams& p = tp.g;
     p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
@@ -1134,23 +1198,58 @@ extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e
     tp.topk = k;
     topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
     tp.part = (unsigned long long*)workspace;
+    tp.cs = cs;
     hipStream_t st = (hipStream_t)stream;
     const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 27 KiB static)
     dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
     const TopkLogitOut out{out_ids, out_logits};
     if (k <= 64) {
-        hipLaunchKernelGGL(k_topk_span<1>, grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_span<1, CAND>), grid, block, lds, st, tp);
         hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
     } else {
         static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_topk_span<2>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
-                               "gv_topk_scores"))
+        if (!raise_dynamic_lds((const void*)k_topk_span<2, CAND>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised, name))
             return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_topk_span<2>, grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_span<2, CAND>), grid, block, lds, st, tp);
         hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
     }
-    return launch_status("gv_topk_scores");
+    return launch_status(name);
 }
+
+extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
+                              const int* filt_hi, const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits,
+                              void* workspace, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
+               n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores: leading dimension too small");
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores: NULL pointer");
+    return topk_scores_launch<false>("gv_topk_scores", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
+                                     out_ids, out_logits, workspace, m, v, h, stream);
+}
+
+extern "C" int gv_topk_scores_constrained(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
+                                          const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand,
+                                          int n_sets, const int32_t* cand_set, int k, int* out_ids, float* out_logits,
+                                          void* workspace, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_constrained: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_topk_scores_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores_constrained: leading dimension too small");
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_topk_scores_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_topk_scores_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores_constrained: NULL pointer");
+    return topk_scores_launch<true>("gv_topk_scores_constrained", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                                    TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_logits, workspace, m, v, h, stream);
+}
+
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,
                                 int out_feat, int transpose_w, const int32_t* tiles, int n_tiles, float* msg, void* stream) {
     GV_REQUIRE(num_rels > 0 && in_feat > 0 && out_feat > 0 && n_tiles >= 0, GV_ERR_SHAPE, "gv_rel_rows_gemm: bad sizes");

@@ -125,6 +125,36 @@ __device__ __forceinline__ void topk_list_update(unsigned long long key, unsigne
     }
 }
 
+// ---- per-query candidate sets (the type-constrained top-k) -----------------------------------------------------------------
+// Entity j is bit j & 31 of word j >> 5 of row cand_set[query] of `cand` ([n_sets, ld_cand]); a set id outside [0, n_sets) is the
+// empty set.  A wave owns 16 consecutive query rows, so the two words a 64-column tile needs of each row are 32 words: lane l < 32
+// keeps word (l >> 4) of row (l & 15) in a register -- loaded before the tile's arithmetic, read back by readlane when the row's
+// turn comes -- and the span kernels' LDS stays as it is.  The second word is guarded by the used word count ceil(v / 32), not by
+// ld_cand: an odd count has none for the last tile, and a row's padding words are never read.
+struct TopkCand {
+    const uint32_t* cand;
+    const int* cand_set;
+    int ld_cand, n_sets;
+};
+
+__device__ __forceinline__ const uint32_t* topk_cand_row(const TopkCand& cs, long long first_row, long long m, int lane) {
+    const long long row = first_row + (lane & 15);
+    const int set = (lane < 32 && row < m) ? cs.cand_set[row] : -1;
+    return (unsigned)set < (unsigned)cs.n_sets ? cs.cand + (size_t)set * cs.ld_cand : nullptr;
+}
+
+__device__ __forceinline__ unsigned topk_cand_word(const uint32_t* row_words, int n0, int v, int lane) {
+    const int w = (n0 >> 5) + ((lane >> 4) & 1);
+    return (row_words && w < (v + 31) >> 5) ? row_words[w] : 0u;      // never past the set's last used word
+}
+
+// is column `lane` of the tile a member of the set of the wave's i-th row (i wave-uniform, 0..15)?
+__device__ __forceinline__ bool topk_cand_member(unsigned word, int i, int lane) {
+    const unsigned w0 = (unsigned)__builtin_amdgcn_readlane((int)word, i);
+    const unsigned w1 = (unsigned)__builtin_amdgcn_readlane((int)word, 16 + i);
+    return ((lane < 32 ? w0 : w1) >> (lane & 31)) & 1u;
+}
+
 // ---- stage 2: one wave per row merges the n_spans sorted lists of k keys and hands the first k to `out` --------------------
 // Out::put(i, key) decodes key into entry i of the (m, k) outputs.
 struct TopkLogitOut {

@@ -412,15 +412,20 @@ __global__ __launch_bounds__(256) void k_transe_distances(const float* __restric
 // counts[0][i] = 2 #better + #equal (raw), counts[1][i] the same over the entities not listed in f_ent[f_lo[i], f_hi[i]) -- the
 // rule of ranking.sort_and_rank on score = -distance: j != target is better when !(d_j >= d_target) (NaN on either side), equal
 // when d_j == d_target.  Block (x, y) takes query tile x and entity tiles y, y + gridDim.y, ...; integer atomics add the counts.
+// CAND (gv_transe_rank_constrained): raw_c / filt_c are the same counts over the members of the query's candidate set only (TopkCand,
+// k_topk.h).  The tile's two set words sit in LDS next to the filter word, loaded by the second wave while the first builds the
+// filter word; without a filter (f_lo NULL) neither filtered count is written.
+template <bool CAND>
 __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v,
                                                      int dim, int p, const int32_t* __restrict__ target,
                                                      const int32_t* __restrict__ f_lo, const int32_t* __restrict__ f_hi,
                                                      const int32_t* __restrict__ f_ent, int32_t* __restrict__ raw,
-                                                     int32_t* __restrict__ filt) {
+                                                     int32_t* __restrict__ filt, const TopkCand cs, int32_t* __restrict__ raw_c,
+                                                     int32_t* __restrict__ filt_c) {
     __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
     __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
     __shared__ float dt_s[TE_TQ];
-    __shared__ unsigned long long mask_s[TE_TQ];
+    __shared__ unsigned long long mask_s[CAND ? 2 * TE_TQ : TE_TQ];       // the tile's filter word per row (CAND: + the set's)
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int64_t q0 = (int64_t)blockIdx.x * TE_TQ;
     if (tid < TE_TQ) {     // the target's distance, with te_tile's per-pair arithmetic
@@ -434,7 +439,7 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
         }
         dt_s[tid] = acc;
     }
-    int cr[4] = {0, 0, 0, 0}, cf[4] = {0, 0, 0, 0};
+    int cr[4] = {0, 0, 0, 0}, cf[4] = {0, 0, 0, 0}, crc[4] = {0, 0, 0, 0}, cfc[4] = {0, 0, 0, 0};
     const int n_tiles = (v + TE_TE - 1) / TE_TE;
     for (int et = blockIdx.y; et < n_tiles; et += gridDim.y) {
         const int e0 = et * TE_TE;
@@ -452,6 +457,17 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
                 for (int x = a; x < f_hi[qi] && f_ent[x] < e0 + TE_TE; ++x) mk |= 1ull << (f_ent[x] - e0);
             }
             mask_s[tid] = mk;
+        } else if (CAND && tid < 2 * TE_TQ) {
+            const int64_t qi = q0 + tid - TE_TQ;
+            const int set = qi < m ? cs.cand_set[qi] : -1;
+            unsigned long long cw = 0;
+            if ((unsigned)set < (unsigned)cs.n_sets) {
+                const uint32_t* words = cs.cand + (size_t)set * cs.ld_cand;
+                const int w0 = e0 >> 5;            // e0 < v, so w0 < ceil(v / 32) <= ld_cand
+                cw = words[w0];
+                if (w0 + 1 < (v + 31) >> 5) cw |= (unsigned long long)words[w0 + 1] << 32;     // never past the last used word
+            }
+            mask_s[tid] = cw;
         }
         float acc[4][4];
         te_tile(q, m, en, v, dim, p, q0, e0, qs, es, acc);    // its first barrier publishes dt_s / mask_s
@@ -471,6 +487,10 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
                 const int c = !(d >= dt) ? 2 : (d == dt ? 1 : 0);
                 cr[a] += c;
                 if (!(mk >> col & 1ull)) cf[a] += c;
+                if (CAND && (mask_s[TE_TQ + row] >> col & 1ull)) {
+                    crc[a] += c;
+                    if (!(mk >> col & 1ull)) cfc[a] += c;
+                }
             }
         }
     }
@@ -480,11 +500,19 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
         for (int off = 8; off >= 1; off >>= 1) {
             cr[a] += __shfl_xor(cr[a], off, 16);
             cf[a] += __shfl_xor(cf[a], off, 16);
+            if (CAND) {
+                crc[a] += __shfl_xor(crc[a], off, 16);
+                cfc[a] += __shfl_xor(cfc[a], off, 16);
+            }
         }
         const int64_t qi = q0 + 4 * ty + a;
         if (tx == 0 && qi < m) {
             atomicAdd(&raw[qi], cr[a]);
-            atomicAdd(&filt[qi], cf[a]);
+            if (!CAND || f_lo) atomicAdd(&filt[qi], cf[a]);
+            if (CAND) {
+                atomicAdd(&raw_c[qi], crc[a]);
+                if (f_lo) atomicAdd(&filt_c[qi], cfc[a]);
+            }
         }
     }
 }
@@ -509,11 +537,12 @@ struct TeTopkParams {
     int topk;                     // 1..TOPK_MAX
     int span_tiles, n_spans;
     unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
+    TopkCand cs;                  // CAND only (gv_transe_topk_constrained): non-members get key 0 as well
 };
 
 constexpr int TE_LDD = TE_TE + 4;      // row stride of the distance tile: float4 stores stay 16-byte aligned
 
-template <int NK>
+template <int NK, bool CAND>
 __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp) {
     __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
     __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
@@ -535,8 +564,10 @@ __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp)
         topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && q0 + tid < tp.m, q0 + tid, t_begin * TE_TE,
                           &cur[tid], &fhi[tid], &nxt[tid]);
     }
+    const uint32_t* cand_row = CAND ? topk_cand_row(tp.cs, q0 + wid * (TE_TQ / 4), tp.m, lane) : nullptr;
     for (int t = t_begin; t < t_end; ++t) {
         const int e0 = t * TE_TE;
+        const unsigned cand_w = CAND ? topk_cand_word(cand_row, e0, tp.v, lane) : 0u;      // lands under te_tile
         float acc[4][4];
         // te_tile's first barrier publishes the set-up above and ends the last tile's reads of ds
         te_tile(tp.q, tp.m, tp.en, tp.v, tp.dim, tp.p, q0, e0, qs, es, acc);
@@ -552,6 +583,7 @@ __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp)
             if (filtered && nxt[rl] < e0 + TE_TE &&
                 topk_filter_window(tp.filt_ent, e0, (t - t_begin) * TE_TQ + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
                 key = 0ull;
+            if (CAND && !topk_cand_member(cand_w, i, lane)) key = 0ull;
             topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
         }
     }
@@ -641,6 +673,29 @@ extern "C" int gv_transe_distances(const float* q, int64_t m, const float* en, i
     return launch_status("gv_transe_distances");
 }
 
+// gv_transe_rank_filtered, and with cs.cand its type-constrained form
+static int transe_rank_any(const char* name, const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
+                           const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, const TopkCand& cs, int32_t* counts_raw,
+                           int32_t* counts_filt, int32_t* counts_raw_c, int32_t* counts_filt_c, void* stream) {
+    hipError_t e = hipSuccess;
+    for (int32_t* c : {counts_raw, counts_filt, counts_raw_c, counts_filt_c})
+        if (c && e == hipSuccess) e = fill_words(c, 0u, (size_t)m * 4, GV_ST);
+    GV_REQUIRE(e == hipSuccess, (int)e, "%s: clearing the counts: %s", name, hipGetErrorString(e));
+    const int64_t q_tiles = (m + TE_TQ - 1) / TE_TQ;
+    const int e_tiles = (v + TE_TE - 1) / TE_TE;
+    int64_t split = (4 * (int64_t)current_device_cus() + q_tiles - 1) / q_tiles;
+    if (split > e_tiles) split = e_tiles;
+    if (split < 1) split = 1;
+    const dim3 grid((unsigned)q_tiles, (unsigned)split), block(256);
+    if (cs.cand)
+        hipLaunchKernelGGL(k_transe_rank<true>, grid, block, 0, GV_ST, q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, counts_raw,
+                           counts_filt, cs, counts_raw_c, counts_filt_c);
+    else
+        hipLaunchKernelGGL(k_transe_rank<false>, grid, block, 0, GV_ST, q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, counts_raw,
+                           counts_filt, cs, counts_raw_c, counts_filt_c);
+    return launch_status(name);
+}
+
 extern "C" int gv_transe_rank_filtered(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
                                        const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, int32_t* counts_raw,
                                        int32_t* counts_filt, void* stream) {
@@ -649,17 +704,28 @@ extern "C" int gv_transe_rank_filtered(const float* q, int64_t m, const float* e
     if (m == 0) return GV_OK;
     GV_REQUIRE(q && en && target && counts_raw && counts_filt, GV_ERR_NULL, "gv_transe_rank_filtered: NULL pointer");
     GV_REQUIRE(!f_lo || (f_hi && f_ent), GV_ERR_NULL, "gv_transe_rank_filtered: a filter needs f_lo, f_hi and f_ent");
-    hipError_t e = fill_words(counts_raw, 0u, (size_t)m * 4, GV_ST);
-    if (e == hipSuccess) e = fill_words(counts_filt, 0u, (size_t)m * 4, GV_ST);
-    GV_REQUIRE(e == hipSuccess, (int)e, "gv_transe_rank_filtered: clearing the counts: %s", hipGetErrorString(e));
-    const int64_t q_tiles = (m + TE_TQ - 1) / TE_TQ;
-    const int e_tiles = (v + TE_TE - 1) / TE_TE;
-    int64_t split = (4 * (int64_t)current_device_cus() + q_tiles - 1) / q_tiles;
-    if (split > e_tiles) split = e_tiles;
-    if (split < 1) split = 1;
-    hipLaunchKernelGGL(k_transe_rank, dim3((unsigned)q_tiles, (unsigned)split), dim3(256), 0, GV_ST, q, m, en, v, dim, p_norm, target,
-                       f_lo, f_hi, f_ent, counts_raw, counts_filt);
-    return launch_status("gv_transe_rank_filtered");
+    return transe_rank_any("gv_transe_rank_filtered", q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, TopkCand{}, counts_raw,
+                           counts_filt, nullptr, nullptr, stream);
+}
+
+extern "C" int gv_transe_rank_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
+                                          const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, const uint32_t* cand,
+                                          int ld_cand, int n_sets, const int32_t* cand_set, int32_t* counts_raw, int32_t* counts_filt,
+                                          int32_t* counts_raw_c, int32_t* counts_filt_c, void* stream) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_rank_constrained: m=%lld v=%d dim=%d p_norm=%d", (long long)m, v, dim, p_norm);
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_transe_rank_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE((f_lo && f_hi && f_ent) || (!f_lo && !f_hi && !f_ent), GV_ERR_NULL,
+               "gv_transe_rank_constrained: f_lo / f_hi / f_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_transe_rank_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && en && target && counts_raw && counts_raw_c, GV_ERR_NULL, "gv_transe_rank_constrained: NULL pointer");
+    GV_REQUIRE(!f_lo || (counts_filt && counts_filt_c), GV_ERR_NULL, "gv_transe_rank_constrained: a filter needs both filtered counts");
+    const bool f = f_lo != nullptr;           // without a filter the two filtered counts are not written
+    return transe_rank_any("gv_transe_rank_constrained", q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent,
+                           TopkCand{cand, cand_set, ld_cand, n_sets}, counts_raw, f ? counts_filt : nullptr, counts_raw_c,
+                           f ? counts_filt_c : nullptr, stream);
 }
 
 extern "C" int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k) {
@@ -667,6 +733,33 @@ extern "C" int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k) {
     int span_tiles = 0, n_spans = 0;
     topk_spans(m, v, &span_tiles, &n_spans);
     return m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+// the launches of gv_transe_topk, and with cs.cand of its type-constrained form
+template <bool CAND>
+static int transe_topk_launch(const char* name, const float* q, int64_t m, const float* en, int v, int dim, int p_norm,
+                              const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                              const TopkCand& cs, int k, int64_t* out_ids, float* out_dist, void* workspace, void* stream) {
+    TeTopkParams tp{q, en, filt_lo, filt_hi, filt_ent, m, v, dim, p_norm, n_filt_ent, k, 0, 0, (unsigned long long*)workspace, cs};
+    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
+    const int lds = TE_TQ * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 36 KiB static)
+    const dim3 grid((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), block(256), mgrid((unsigned)((m + 3) / 4));
+    const TeDistOut out{out_ids, out_dist};
+    if (k <= 64) {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_transe_topk_span<1, CAND>, TE_TQ * 64 * (int)sizeof(unsigned long long), lds_raised, name))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_transe_topk_span<1, CAND>), grid, block, lds, GV_ST, tp);
+        hipLaunchKernelGGL((k_topk_merge<1, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_transe_topk_span<2, CAND>, TE_TQ * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
+                               name))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_transe_topk_span<2, CAND>), grid, block, lds, GV_ST, tp);
+        hipLaunchKernelGGL((k_topk_merge<2, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
+    }
+    return launch_status(name);
 }
 
 extern "C" int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
@@ -681,25 +774,26 @@ extern "C" int gv_transe_topk(const float* q, int64_t m, const float* en, int v,
                "gv_transe_topk: filt_lo / filt_hi / filt_ent must be all given or all NULL");
     if (m == 0) return GV_OK;
     GV_REQUIRE(q && en && out_ids && out_dist && workspace, GV_ERR_NULL, "gv_transe_topk: NULL pointer");
-    TeTopkParams tp{q, en, filt_lo, filt_hi, filt_ent, m, v, dim, p_norm, n_filt_ent, k, 0, 0, (unsigned long long*)workspace};
-    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
-    const int lds = TE_TQ * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 36 KiB static)
-    const dim3 grid((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), block(256), mgrid((unsigned)((m + 3) / 4));
-    const TeDistOut out{out_ids, out_dist};
-    if (k <= 64) {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_transe_topk_span<1>, TE_TQ * 64 * (int)sizeof(unsigned long long), lds_raised,
-                               "gv_transe_topk"))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_transe_topk_span<1>, grid, block, lds, GV_ST, tp);
-        hipLaunchKernelGGL((k_topk_merge<1, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_transe_topk_span<2>, TE_TQ * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
-                               "gv_transe_topk"))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_transe_topk_span<2>, grid, block, lds, GV_ST, tp);
-        hipLaunchKernelGGL((k_topk_merge<2, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
-    }
-    return launch_status("gv_transe_topk");
+    return transe_topk_launch<false>("gv_transe_topk", q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
+                                     out_ids, out_dist, workspace, stream);
+}
+
+extern "C" int gv_transe_topk_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm,
+                                          const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                          const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, int k,
+                                          int64_t* out_ids, float* out_dist, void* workspace, void* stream) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) &&
+                   n_filt_ent >= 0,
+               GV_ERR_SHAPE, "gv_transe_topk_constrained: m=%lld v=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", (long long)m, v,
+               dim, GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_transe_topk_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_transe_topk_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_transe_topk_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_transe_topk_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && en && out_ids && out_dist && workspace, GV_ERR_NULL, "gv_transe_topk_constrained: NULL pointer");
+    return transe_topk_launch<true>("gv_transe_topk_constrained", q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                                    TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_dist, workspace, stream);
 }

@@ -108,6 +108,8 @@ SIGNATURES = {
     'gv_rank_scores_filtered': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_topk_scores_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_topk_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    'gv_rank_scores_constrained': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'gv_topk_scores_constrained': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_mine_scores_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_mine_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P, _P, _L,
                             _I, _I, _I, _P]),
@@ -123,6 +125,8 @@ SIGNATURES = {
     'gv_transe_rank_filtered': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     'gv_transe_topk_workspace_bytes': (_L, [_L, _I, _I]),
     'gv_transe_topk': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    'gv_transe_rank_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'gv_transe_topk_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

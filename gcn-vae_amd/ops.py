@@ -570,6 +570,28 @@ def rank_scores(q, entities, target, bias=None):
     return count[:m].to(torch.float32) * 0.5
 
 
+def _filter_args(filt_lo, filt_hi, filt_ent, m, v, device):
+    """The checks of ``rank_scores_filtered`` on an optional filter: (lo32, hi32, ent32, n_ent), all None / 0 without one."""
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    if not all(given):
+        return None, None, None, 0
+    filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+    if filt_lo.numel() != m or filt_hi.numel() != m:
+        raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+    n_ent = filt_ent.numel()
+    if n_ent >= 2 ** 31:
+        raise ValueError('filt_ent: more than 2**31 - 1 entries')
+    if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
+        raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+    if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
+        raise ValueError(f'filtered entity ids must lie in [0, {v})')
+    i32 = dict(device=device, dtype=torch.int32)
+    ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    return filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous(), ent32, n_ent
+
+
 def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=None):
     """(raw, filtered) ranks of ``target[i]``, both as ``rank_scores`` returns them (0-based floats, x.5 under ties), from one
     launch pair (gv_rank_scores_filtered).  The filtered rank leaves out the candidates ``filt_ent[filt_lo[i]:filt_hi[i]]`` --
@@ -583,22 +605,13 @@ def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=N
     target = target.reshape(-1)
     if target.numel() != m:
         raise ValueError('one target per query row')
-    filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
-    if filt_lo.numel() != m or filt_hi.numel() != m:
-        raise ValueError('one filter range (filt_lo, filt_hi) per query row')
-    n_ent = filt_ent.numel()
-    if n_ent >= 2 ** 31:
-        raise ValueError('filt_ent: more than 2**31 - 1 entries')
+    if filt_lo is None or filt_hi is None or filt_ent is None:
+        raise ValueError('rank_scores_filtered needs filt_lo, filt_hi and filt_ent')
     if m and (int(target.min()) < 0 or int(target.max()) >= v):
         raise ValueError(f'targets must lie in [0, {v})')
-    if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
-        raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
-    if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
-        raise ValueError(f'filtered entity ids must lie in [0, {v})')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     i32 = dict(device=q.device, dtype=torch.int32)
     tgt32 = target.to(**i32).contiguous()
-    lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
-    ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
     if bias is not None:
         bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
     ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
@@ -630,37 +643,101 @@ def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=
     k = int(k)
     if not 1 <= k <= TOPK_MAX:
         raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
-    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
-    if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
-    n_ent = 0
-    if all(given):
-        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
-        if filt_lo.numel() != m or filt_hi.numel() != m:
-            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
-        n_ent = filt_ent.numel()
-        if n_ent >= 2 ** 31:
-            raise ValueError('filt_ent: more than 2**31 - 1 entries')
-        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
-            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
-        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
-            raise ValueError(f'filtered entity ids must lie in [0, {v})')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     q, ld_q = _row_major(q, 'q')
     entities, ld_e = _row_major(entities, 'entities')
     ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
     logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
     if m == 0:
         return ids.long(), logits
-    lo32 = hi32 = ent32 = None
-    if all(given):
-        i32 = dict(device=q.device, dtype=torch.int32)
-        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
-        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
     if bias is not None:
         bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
     ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
     lib.call('gv_topk_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k,
              ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
+    return ids.long(), logits
+
+
+def _cand_args(cand, cand_set, m, v, device):
+    """A candidate bitmask (``ranking.TypeConstraint.words``: (n_sets, >= ceil(v / 32)) int32 or uint32, entity j = bit j & 31
+    of word j >> 5; a view with a longer row stride is taken as it is) and one set id per query row: (words, ld_cand, n_sets,
+    set32).  Set ids are NOT range-checked: an id outside [0, n_sets) is the empty set, on the device too."""
+    if not isinstance(cand, torch.Tensor) or not cand.is_cuda or cand.device != device:
+        raise RuntimeError('cand: the gfx950 path needs a CUDA/ROCm tensor on the queries\' device; there is no CPU fallback')
+    if cand.dtype not in (torch.int32, torch.uint32) or cand.dim() != 2:
+        raise TypeError(f'cand: expected a 2-D int32 / uint32 bitmask, got {cand.dtype} {tuple(cand.shape)}')
+    n_sets, w = cand.shape
+    if n_sets < 1 or w < (v + 31) // 32:
+        raise ValueError(f'cand: need at least one set and ceil({v} / 32) = {(v + 31) // 32} words per set, got {tuple(cand.shape)}')
+    if cand.stride(1) != 1 or (n_sets > 1 and cand.stride(0) < w):
+        cand = cand.contiguous()
+    cand_set = cand_set.reshape(-1)
+    if cand_set.numel() != m:
+        raise ValueError('one candidate set id per query row')
+    return cand, (cand.stride(0) if n_sets > 1 else w), n_sets, cand_set.to(device=device, dtype=torch.int32).contiguous()
+
+
+def rank_scores_constrained(q, entities, target, cand, cand_set, filt_lo=None, filt_hi=None, filt_ent=None, bias=None):
+    """(raw, filtered, raw_constrained, filtered_constrained) ranks of ``target[i]``, as ``rank_scores_filtered`` returns them,
+    from one launch pair (gv_rank_scores_constrained).  The constrained ranks count only the candidates whose bit is set in
+    row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``); the target itself is never counted, member or not, and an
+    empty or out-of-range set gives rank 0.  The first two equal ``rank_scores_filtered`` bit for bit.  Without a filter the two
+    filtered ranks are None."""
+    q, ld_q = _row_major(q, 'q')
+    entities, ld_e = _row_major(entities, 'entities')
+    if q.shape[1] != entities.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    m, v = q.shape[0], entities.shape[0]
+    target = target.reshape(-1)
+    if target.numel() != m:
+        raise ValueError('one target per query row')
+    if m and (int(target.min()) < 0 or int(target.max()) >= v):
+        raise ValueError(f'targets must lie in [0, {v})')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    i32 = dict(device=q.device, dtype=torch.int32)
+    tgt32 = target.to(**i32).contiguous()
+    if bias is not None:
+        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
+    counts = torch.zeros(4, max(m, 1), **i32)
+    filt = lo32 is not None
+    lib.call('gv_rank_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), ptr(ws), ptr(counts[0]), ptr(counts[1]) if filt else None,
+             ptr(counts[2]), ptr(counts[3]) if filt else None, m, v, q.shape[1], lib.stream())
+    r = counts[:, :m].to(torch.float32) * 0.5
+    return r[0], (r[1] if filt else None), r[2], (r[3] if filt else None)
+
+
+def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """``topk_scores`` among the members of a per-query candidate set only (gv_topk_scores_constrained): the candidates of row i
+    are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``), less the filter-listed
+    ids.  Order, ties, NaN and padding are ``topk_scores``'; a set with fewer than k members pads, an out-of-range set id gives
+    an all-padding row."""
+    for name, t in (('q', q), ('entities', entities)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if q.shape[1] != entities.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    m, v, h = q.shape[0], entities.shape[0], q.shape[1]
+    if v < 1 or h < 1:
+        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    q, ld_q = _row_major(q, 'q')
+    entities, ld_e = _row_major(entities, 'entities')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids.long(), logits
+    if bias is not None:
+        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_topk_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+             ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
     return ids.long(), logits
 
 
@@ -2935,21 +3012,7 @@ def transe_rank_filtered(q, en, target, p_norm, filt_lo=None, filt_hi=None, filt
     if m and (int(target.min()) < 0 or int(target.max()) >= v):
         raise ValueError(f'targets must lie in [0, {v})')
     i32 = dict(device=q.device, dtype=torch.int32)
-    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
-    if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
-    lo32 = hi32 = ent32 = None
-    if all(given):
-        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
-        if filt_lo.numel() != m or filt_hi.numel() != m:
-            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
-        n_ent = filt_ent.numel()
-        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
-            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
-        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
-            raise ValueError(f'filtered entity ids must lie in [0, {v})')
-        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
-        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     tgt32 = target.to(**i32).contiguous()
     counts = torch.zeros(2, max(m, 1), **i32)
     lib.call('gv_transe_rank_filtered', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
@@ -2977,25 +3040,7 @@ def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     m, v = q.shape[0], en.shape[0]
     if v < 1:
         raise ValueError('need at least one entity')
-    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
-    if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
-    i32 = dict(device=q.device, dtype=torch.int32)
-    lo32 = hi32 = ent32 = None
-    n_ent = 0
-    if all(given):
-        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
-        if filt_lo.numel() != m or filt_hi.numel() != m:
-            raise ValueError('one filter range (filt_lo, filt_hi) per query row')
-        n_ent = filt_ent.numel()
-        if n_ent >= 2 ** 31:
-            raise ValueError('filt_ent: more than 2**31 - 1 entries')
-        if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
-            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
-        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
-            raise ValueError(f'filtered entity ids must lie in [0, {v})')
-        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
-        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     ids = torch.empty(m, k, dtype=torch.int64, device=q.device)
     dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
     if m == 0:
@@ -3003,4 +3048,60 @@ def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     ws = torch.empty(int(lib.load().gv_transe_topk_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
     lib.call('gv_transe_topk', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k, ptr(ids),
              ptr(dist), ptr(ws), lib.stream())
+    return ids, dist
+
+
+def transe_rank_constrained(q, en, target, p_norm, cand, cand_set, filt_lo=None, filt_hi=None, filt_ent=None):
+    """(raw, filtered, raw_constrained, filtered_constrained) 0-based mid-ranks of ``target[i]`` under score =
+    -||q[i] - en[j]||_p (gv_transe_rank_constrained): ``transe_rank_filtered``'s two, bit for bit, and the same over the members
+    of row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it).  Without a filter the two filtered
+    ranks are None."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    p_norm = _p_norm(p_norm)
+    m, v = q.shape[0], en.shape[0]
+    target = target.reshape(-1)
+    if target.numel() != m:
+        raise ValueError('one target per query row')
+    if m and (int(target.min()) < 0 or int(target.max()) >= v):
+        raise ValueError(f'targets must lie in [0, {v})')
+    lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    i32 = dict(device=q.device, dtype=torch.int32)
+    tgt32 = target.to(**i32).contiguous()
+    counts = torch.zeros(4, max(m, 1), **i32)
+    filt = lo32 is not None
+    lib.call('gv_transe_rank_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
+             ptr(cand), ld_cand, n_sets, ptr(set32), ptr(counts[0]), ptr(counts[1]) if filt else None, ptr(counts[2]),
+             ptr(counts[3]) if filt else None, lib.stream())
+    r = counts[:, :m].to(torch.float32) * 0.5
+    return r[0], (r[1] if filt else None), r[2], (r[3] if filt else None)
+
+
+def transe_topk_constrained(q, en, k, p_norm, cand, cand_set, filt_lo=None, filt_hi=None, filt_ent=None):
+    """``transe_topk`` among the members of a per-query candidate set only (gv_transe_topk_constrained): the candidates of row i
+    are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it),
+    less the filter-listed ids.  Order and padding are ``transe_topk``'s."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    if q.device != en.device:
+        raise ValueError(f'q on {q.device}, entities on {en.device}')
+    p_norm = _p_norm(p_norm)
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    m, v = q.shape[0], en.shape[0]
+    if v < 1:
+        raise ValueError('need at least one entity')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    ids = torch.empty(m, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids, dist
+    ws = torch.empty(int(lib.load().gv_transe_topk_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_transe_topk_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+             ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(dist), ptr(ws), lib.stream())
     return ids, dist

@@ -21,6 +21,12 @@ Link prediction (what the reference's ``--generate`` demo did with an argmax, kg
 the k best entities of each query, optionally filtered by a ``FilterIndex``, from ``ops.topk_scores`` (gv_topk_scores: the same
 logits, a selection epilogue instead of a count).  ``topk_from_scores`` states the order on a materialised score matrix.
 
+Type-constrained evaluation and prediction (the second protocol of the reference's baseline tester,
+baselines/transe/tester.py:70-91): a ``TypeConstraint`` holds, per relation and side, the bitmask of the entities seen there;
+``ops.rank_scores_constrained`` ranks the target among those only -- raw, filtered and both constrained counts from one launch
+pair -- and ``predict_topk(type_constraint=...)`` proposes members only.  ``rank_from_scores_constrained`` and
+``topk_from_scores(cand=...)`` state the rules on a materialised score matrix.
+
 Completion (no query list: which triplets are missing from the graph?): ``mine_triplets`` selects globally among all N x R x N
 triplets -- the K most confident new ones, or all above a threshold -- from ``ops.mine_scores`` (gv_mine_scores: subject and
 object tiles of the entity table stay in LDS while the relations are walked over them).  ``mine_from_scores`` states the rule on
@@ -123,6 +129,136 @@ class FilterIndex:
         return self.ent[direction] if device is None else self.ent[direction].to(device)
 
 
+class TypeConstraint:
+    """Per relation and side, the set of entities seen there in the given triplet sets, as one bitmask:
+      set r             (direction 'o'): the entities seen as OBJECT of relation r   -- the candidates of a query (s, r, ?)
+      set num_rels + r  (direction 's'): the entities seen as SUBJECT of relation r  -- the candidates of a query (?, r, o)
+    ``words`` is int32 (2 * num_rels, W), W = ceil(num_nodes / 32): entity j is bit j & 31 of word j >> 5; bits at positions
+    >= num_nodes are zero.  ``sizes`` (int64 [2 * num_rels]) counts the members.  Built with torch ops on ``device``."""
+
+    def __init__(self, num_nodes, num_rels, *triplet_sets, device='cpu'):
+        self.num_nodes, self.num_rels, self.device = int(num_nodes), int(num_rels), torch.device(device)
+        parts = [torch.as_tensor(t).to(device=self.device, dtype=torch.long).reshape(-1, 3) for t in triplet_sets]
+        trip = torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.long, device=self.device)
+        if trip.numel() and (int(trip[:, [0, 2]].min()) < 0 or int(trip[:, [0, 2]].max()) >= self.num_nodes
+                             or int(trip[:, 1].min()) < 0 or int(trip[:, 1].max()) >= self.num_rels):
+            raise ValueError('triplets out of range of num_nodes / num_rels')
+        s, r, o = trip[:, 0], trip[:, 1], trip[:, 2]
+        n_sets, n_words = 2 * self.num_rels, (self.num_nodes + 31) // 32
+        # distinct (set, entity) pairs: each is one bit, so summing the bits of a word is OR-ing them
+        pair = torch.unique(torch.cat([r * self.num_nodes + o, (self.num_rels + r) * self.num_nodes + s]))
+        set_id, ent = pair // max(self.num_nodes, 1), pair % max(self.num_nodes, 1)
+        words = torch.zeros(n_sets * n_words, dtype=torch.long, device=self.device)
+        words.index_add_(0, set_id * n_words + (ent >> 5), torch.ones_like(ent) << (ent & 31))
+        words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)          # the uint32 bit pattern, held as int32
+        self.words = words.to(torch.int32).view(n_sets, n_words).contiguous()
+        self.sizes = torch.bincount(set_id, minlength=n_sets)
+
+    def set_ids(self, r, direction):
+        """int32 set id of each relation ``r[i]``: r for 'o' (object candidates), num_rels + r for 's' (subject candidates)."""
+        if direction not in ('o', 's'):
+            raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
+        r = torch.as_tensor(r)
+        return (r + (self.num_rels if direction == 's' else 0)).to(torch.int32)
+
+    def mask(self, set_ids, device=None):
+        """Dense (m, num_nodes) bool of the members of each listed set; an id outside [0, 2 * num_rels) is the empty set."""
+        ids = torch.as_tensor(set_ids).to(device=self.device, dtype=torch.long).reshape(-1)
+        ok = (ids >= 0) & (ids < self.words.shape[0])
+        rows = self.words[ids.clamp(0, max(self.words.shape[0] - 1, 0))] if self.words.shape[0] else self.words.new_zeros(ids.numel(), 0)
+        ent = torch.arange(self.num_nodes, device=self.device)
+        dense = ((rows[:, ent >> 5] >> (ent & 31)) & 1).bool() & ok.view(-1, 1)
+        return dense if device is None else dense.to(device)
+
+    def contains(self, r, entities, direction):
+        """bool: is ``entities[i]`` a member of the ``direction`` set of relation ``r[i]``?  (On ``entities``' device.)"""
+        entities = torch.as_tensor(entities)
+        e = entities.to(device=self.device, dtype=torch.long)
+        ids = self.set_ids(torch.as_tensor(r).to(self.device), direction).long()
+        if e.numel() and (int(e.min()) < 0 or int(e.max()) >= self.num_nodes or int(ids.min()) < 0
+                          or int(ids.max()) >= self.words.shape[0]):
+            raise ValueError('entities / relations out of range of num_nodes / num_rels')
+        return (((self.words[ids, e >> 5] >> (e & 31)) & 1).bool()).to(entities.device)
+
+
+def rank_from_scores_constrained(score, target, cand_mask, listed_mask=None):
+    """The rule of ``ops.rank_scores_constrained`` on a materialised (m, v) logit matrix, in plain torch (any device):
+    ``sort_and_rank``'s predicates (NaN never optimistic, ties half) counted over four candidate pools, the target left out of
+    every one whether or not it is a member: all entities; those not in ``listed_mask``; the members of ``cand_mask``; the
+    members not listed.  Both masks are dense (m, v) bools.  Returns (raw, filtered, raw_constrained, filtered_constrained),
+    0-based float mid-ranks; the two filtered ones are None without ``listed_mask``."""
+    tgt = score.gather(1, target.view(-1, 1))
+    other = torch.ones_like(score, dtype=torch.bool).scatter_(1, target.view(-1, 1), False)
+    better, equal = (~(score <= tgt)) & other, (score == tgt) & other
+
+    def rank(pool):
+        return (better & pool).sum(dim=1).float() + 0.5 * (equal & pool).sum(dim=1).float()
+    cand_mask = cand_mask.to(score.device)
+    if listed_mask is None:
+        return rank(other), None, rank(cand_mask), None
+    keep = ~listed_mask.to(score.device)
+    return rank(other), rank(keep), rank(cand_mask), rank(cand_mask & keep)
+
+
+def perturb_and_get_rank_constrained(embedding, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
+                                     all_batches=True, flow_log_prob=None):
+    """(raw, filtered, raw_constrained, filtered_constrained) ranks of ``b`` for the queries (a, r):
+    ``perturb_and_get_rank_filtered`` plus the ranks among the ``direction`` type set of each query's relation only.
+    ``filter_index`` may be None: the two filtered ranks are then None."""
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    emb = embedding.detach().contiguous()
+    wd = w.detach()
+    ent = filter_index.entities(direction, emb.device) if filter_index is not None else None
+    words = type_constraint.words.to(emb.device)
+    out = [[], [], [], []]
+    for lo in range(0, n, MAX_QUERY_ROWS):
+        hi = min(n, lo + MAX_QUERY_ROWS)
+        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
+        f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction) if filter_index is not None else (None, None)
+        ranks = ops.rank_scores_constrained(q, emb, b[lo:hi], words, type_constraint.set_ids(r[lo:hi], direction), f_lo, f_hi, ent,
+                                            flow_log_prob)
+        for acc, x in zip(out, ranks):
+            acc.append(x)
+    if not out[0]:
+        out = [[torch.zeros(0, dtype=torch.float32, device=emb.device)] for _ in out]
+        if filter_index is None:
+            out[1] = out[3] = [None]
+    return tuple(None if x[0] is None else torch.cat(x) for x in out)
+
+
+CONSTRAINED_KINDS = ('raw', 'filtered', 'raw_constrained', 'filtered_constrained')
+
+
+def calc_constrained_mrr(embedding, w, test_triplets, filter_index, type_constraint, hits=[1, 3, 10], eval_bz=100,
+                         all_batches=True, flow_log_prob=None, verbose=True):
+    """The four-way report of the type-constrained protocol over both directions: ``mrr_<kind>`` and ``hits_<kind>: {k: v}`` for
+    raw, filtered, raw_constrained and filtered_constrained.  The first two equal ``calc_filtered_mrr``'s values."""
+    with torch.no_grad():
+        test_triplets = test_triplets.to(embedding.device)
+        w = w.to(embedding.device)
+        if isinstance(flow_log_prob, torch.Tensor):
+            flow_log_prob = flow_log_prob.to(embedding.device)
+        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
+        n = test_triplets.shape[0]
+        by_s = perturb_and_get_rank_constrained(embedding, w, o, r, s, n, filter_index, type_constraint, 's', eval_bz, all_batches,
+                                                flow_log_prob)
+        by_o = perturb_and_get_rank_constrained(embedding, w, s, r, o, n, filter_index, type_constraint, 'o', eval_bz, all_batches,
+                                                flow_log_prob)
+        out = {}
+        for kind, rs, ro in zip(CONSTRAINED_KINDS, by_s, by_o):
+            if rs is None:                                    # no filter_index: the two filtered kinds are not reported
+                continue
+            ranks = torch.cat([rs, ro]) + 1
+            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
+            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
+        if verbose:
+            for kind in (k for k in CONSTRAINED_KINDS if 'mrr_' + k in out):
+                print("MRR ({}): {:.6f}".format(kind, out['mrr_' + kind]))
+                for hit in hits:
+                    print("Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
+    return out
+
+
 def perturb_and_get_rank_filtered(embedding, w, a, r, b, test_size, filter_index, direction, batch_size=100, all_batches=True,
                                   flow_log_prob=None, verbose=False):
     """(raw, filtered) ranks of ``b`` for the queries (a, r): ``perturb_and_get_rank`` with the known answers of each query left
@@ -190,9 +326,10 @@ def _listed_mask(filt_lo, filt_hi, filt_ent, m, v, device):
     return mask
 
 
-def topk_from_scores(score, k, filt_lo=None, filt_hi=None, filt_ent=None):
+def topk_from_scores(score, k, filt_lo=None, filt_hi=None, filt_ent=None, cand=None):
     """The top-k rule of ``ops.topk_scores`` on a materialised (m, v) logit matrix, in plain torch (any device): the ids listed
-    in ``filt_ent[filt_lo[i]:filt_hi[i]]`` are no candidates of row i; candidates go by logit descending, equal logits (-0 and
+    in ``filt_ent[filt_lo[i]:filt_hi[i]]`` are no candidates of row i, nor are the columns where ``cand`` -- a dense (m, v) bool
+    of allowed columns, the rule of ``ops.topk_scores_constrained`` -- is False; candidates go by logit descending, equal logits (-0 and
     +0 alike) by lower id, NaN after every other value (-inf included) and by id among themselves.  Returns ``(ids int64 (m, k),
     logits float32 (m, k))``, padded with id -1 / logit -inf past a row's last candidate; -0 is reported as +0 and every NaN
     as the one quiet NaN."""
@@ -204,6 +341,8 @@ def topk_from_scores(score, k, filt_lo=None, filt_hi=None, filt_ent=None):
     tier = nan.to(torch.int8)                                       # 0 a number, 1 NaN, 2 no candidate
     if filt_lo is not None:
         tier = torch.where(_listed_mask(filt_lo, filt_hi, filt_ent, m, v, val.device), torch.full_like(tier, 2), tier)
+    if cand is not None:
+        tier = torch.where(cand.to(val.device), tier, torch.full_like(tier, 2))
     by_logit = torch.argsort(torch.where(nan, torch.full_like(val, float('-inf')), val), dim=1, descending=True, stable=True)
     order = by_logit.gather(1, torch.argsort(tier.gather(1, by_logit), dim=1, stable=True))[:, :k]
     ids, logits = order.clone(), val.gather(1, order)
@@ -215,7 +354,7 @@ def topk_from_scores(score, k, filt_lo=None, filt_hi=None, filt_ent=None):
     return ids, logits
 
 
-def _predict_topk(embedding, w, a, r, k, direction, filter_index, select):
+def _predict_topk(embedding, w, a, r, k, direction, filter_index, select, type_constraint=None):
     if direction not in ('o', 's'):
         raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
     emb = embedding.detach().contiguous()
@@ -226,7 +365,10 @@ def _predict_topk(embedding, w, a, r, k, direction, filter_index, select):
         hi = min(a.shape[0], lo + MAX_QUERY_ROWS)
         q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
         f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction) if filter_index is not None else (None, None)
-        i, l = select(q, emb, f_lo, f_hi, ent)
+        if type_constraint is None:
+            i, l = select(q, emb, f_lo, f_hi, ent)
+        else:
+            i, l = select(q, emb, f_lo, f_hi, ent, type_constraint.set_ids(r[lo:hi], direction))
         ids.append(i)
         logits.append(l)
     if not ids:
@@ -235,25 +377,31 @@ def _predict_topk(embedding, w, a, r, k, direction, filter_index, select):
     return torch.cat(ids), torch.cat(logits)
 
 
-def predict_topk(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None):
+def predict_topk(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None, type_constraint=None):
     """Link prediction: the ``k`` most likely entities of every query, ``direction`` 'o' for (a[i], r[i], ?) and 's' for
     (?, r[i], a[i]), scored as ``perturb_and_get_rank`` scores them (q = e_a * w_r, logit = q . e_j + flow_log_prob).  With a
     ``FilterIndex`` the query's known answers are left out (new facts only).  One fused launch pair per ``MAX_QUERY_ROWS``
-    queries (ops.topk_scores); returns ``(ids int64 (n, k), logits float32 (n, k))`` in the order of ``topk_from_scores``."""
-    def select(q, emb, f_lo, f_hi, ent):
-        return ops.topk_scores(q, emb, k, flow_log_prob, f_lo, f_hi, ent)
-    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select)
+    queries (ops.topk_scores); returns ``(ids int64 (n, k), logits float32 (n, k))`` in the order of ``topk_from_scores``.
+    With a ``TypeConstraint`` only the members of the relation's ``direction`` type set are proposed
+    (ops.topk_scores_constrained); rows with fewer than k such candidates are padded."""
+    words = type_constraint.words.to(embedding.device) if type_constraint is not None else None
+
+    def select(q, emb, f_lo, f_hi, ent, sets=None):
+        if sets is None:
+            return ops.topk_scores(q, emb, k, flow_log_prob, f_lo, f_hi, ent)
+        return ops.topk_scores_constrained(q, emb, k, words, sets, flow_log_prob, f_lo, f_hi, ent)
+    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select, type_constraint)
 
 
-def predict_topk_unfused(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None):
+def predict_topk_unfused(embedding, w, a, r, k, direction='o', filter_index=None, flow_log_prob=None, type_constraint=None):
     """``predict_topk`` from materialised logits (one GEMM + ``topk_from_scores`` per chunk): the in-repo cross-check and the
     bench's baseline."""
-    def select(q, emb, f_lo, f_hi, ent):
+    def select(q, emb, f_lo, f_hi, ent, sets=None):
         score = ops.gemm(q, emb, trans_b=True, precision='f32')
         if flow_log_prob is not None:
             score = score + flow_log_prob
-        return topk_from_scores(score, k, f_lo, f_hi, ent)
-    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select)
+        return topk_from_scores(score, k, f_lo, f_hi, ent, None if sets is None else type_constraint.mask(sets, score.device))
+    return _predict_topk(embedding, w, a, r, k, direction, filter_index, select, type_constraint)
 
 
 MineOverflow = ops.MineOverflow

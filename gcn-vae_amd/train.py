@@ -124,16 +124,18 @@ def _sync():
     torch.cuda.synchronize()
 
 
-def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=None):
+def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=None, type_constraint=None):
     """Top-k link predictions for both directions of every triplet, the known answers (``filter_index``) left out, as TSV:
     ``direction  query_entity  relation  position  predicted_entity  logit`` -- 'o' lines answer (s, r, ?), 's' lines (?, r, o);
-    a query with fewer than k candidates ends in id -1, logit -inf.  Returns the number of lines written."""
+    a query with fewer than k candidates ends in id -1, logit -inf.  With a ``type_constraint`` (ranking.TypeConstraint) only
+    members of the relation's type set on that side are written.  Returns the number of lines written."""
     n = 0
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
     with torch.no_grad(), open(path, 'w') as f:
         for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
             r = triplets[:, 1]
             ids, logits = ranking.predict_topk(embed, w, a, r, k, direction=d, filter_index=filter_index,
-                                               flow_log_prob=flow_log_prob)
+                                               flow_log_prob=flow_log_prob, **constrained)
             a, r, ids, logits = a.tolist(), r.tolist(), ids.tolist(), logits.tolist()
             for i in range(len(a)):
                 head = f"{d}\t{a[i]}\t{r[i]}\t"
@@ -180,6 +182,13 @@ def check_args(args):
         raise ValueError(f"{' / '.join(wants)} decode a trained checkpoint: pass --test-mode True (and --model-state-file)")
     if getattr(args, 'complete_threshold', None) is not None:
         _logit_of(args.complete_threshold)
+    if getattr(args, 'type_constrain', False):
+        if args.test_mode is not True:
+            raise ValueError('--type-constrain reports on / predicts from a trained checkpoint: pass --test-mode True '
+                             '(and --model-state-file)')
+        if not getattr(args, 'filtered_eval', False):
+            raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, '
+                             'filtered_constrained')
 
 
 def main(args):
@@ -219,6 +228,9 @@ def main(args):
 
     if args.test_mode is True:
         print("\nstart testing:")
+        # --type-constrain: per relation and side, the entities seen there in train + valid + test
+        types = ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev) \
+            if getattr(args, 'type_constrain', False) else None
         checkpoint = torch.load(args.model_state_file, map_location=dev)
         test_t = torch.as_tensor(test_data, dtype=torch.long, device=dev)
         test_graph, test_node_id, test_rel, test_norm = graph_inputs(test_data)
@@ -231,7 +243,7 @@ def main(args):
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             n_lines = write_predictions(args.predict_out, embed, model.w_relation, test_t, args.predict_topk, known,
-                                        model.encoder.get_flow_log_prob())
+                                        model.encoder.get_flow_log_prob(), types)
             print(f"wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to "
                   f"{args.predict_out}")
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
@@ -246,6 +258,10 @@ def main(args):
             _, trip, logits = generate.sample_graph(model, args.sample_graph, k=args.sample_topk)
             print(f"wrote {_write_triplets(args.sample_out, trip, logits)} triplets of a graph decoded from {args.sample_graph} "
                   f"prior samples to {args.sample_out}")
+        if types is not None:
+            return ranking.calc_constrained_mrr(embed, model.w_relation, test_t, filters, types, hits=[1, 3, 10],
+                                                eval_bz=args.eval_batch_size, all_batches=True,
+                                                flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
         if filters is not None:
             return ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
                                              eval_bz=args.eval_batch_size, all_batches=True,
@@ -390,6 +406,10 @@ def build_parser():
     p.add_argument("--filtered-eval", action="store_true",
                    help="also report filtered MRR and Hits@1/3/10 (the other known answers of a query -- train + valid + "
                         "test -- left out of its rank); model selection stays on the raw MRR; not a reference flag")
+    p.add_argument("--type-constrain", action="store_true",
+                   help="with --test-mode and --filtered-eval: the type-constrained protocol (candidates: the entities seen on "
+                        "that side of the relation in train + valid + test); the report is raw, filtered, raw_constrained and "
+                        "filtered_constrained, and --predict-topk writes such entities only; not a reference flag")
     p.add_argument("--predict-topk", type=int, default=0,
                    help="with --test-mode: write the K most likely new entities of both directions of every test triplet "
                         "(train + valid + test triplets filtered out) to --predict-out; 0 = off; not a reference flag")

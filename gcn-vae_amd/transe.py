@@ -50,7 +50,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ranking import FilterIndex, _listed_mask, sort_and_rank, topk_from_scores
+from .ranking import FilterIndex, TypeConstraint, _listed_mask, rank_from_scores_constrained, sort_and_rank, topk_from_scores
 
 
 # ------------------------------------------------------------------------------------------------
@@ -349,9 +349,9 @@ class DeviceTrainer:
 MAX_QUERY_ROWS = 16384      # queries per ranker launch
 
 
-def _summary(raw, filt, hits):
+def _summary(raw, filt, hits, suffix=''):
     out = {}
-    for kind, ranks in (('raw', raw + 1), ('filtered', filt + 1)):
+    for kind, ranks in (('raw' + suffix, raw + 1), ('filtered' + suffix, filt + 1)):
         ranks = ranks.double()
         out['mrr_' + kind] = torch.mean(1.0 / ranks).item()
         out['mr_' + kind] = torch.mean(ranks).item()
@@ -409,18 +409,74 @@ def rank_transe_unfused(ent, rel, triplets, p_norm, norm_flag, filter_index=None
     return torch.cat(raws), torch.cat(filts)
 
 
-def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False, verbose=True):
+def rank_transe_constrained(ent, rel, triplets, p_norm, norm_flag, type_constraint, filter_index=None):
+    """(raw, filtered, raw_constrained, filtered_constrained) 0-based ranks in ``rank_transe``'s order (head queries of every
+    triplet, then tail queries) from the fused ranker: the constrained ranks count the members of the relation's type set only
+    (``ranking.TypeConstraint``: subjects of r for a head query, objects of r for a tail query).  Without a filter the two
+    filtered ones equal their unfiltered twins, as ``rank_transe``'s do."""
+    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
+    en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
+    words = type_constraint.words.to(ent.device)
+    out = [[], [], [], []]
+    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
+        ent_f = filter_index.entities(d, ent.device) if filter_index is not None else None
+        for lo in range(0, a.numel(), MAX_QUERY_ROWS):
+            hi = min(a.numel(), lo + MAX_QUERY_ROWS)
+            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
+            f = (None, None, None)
+            if filter_index is not None:
+                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
+                f = (f_lo, f_hi, ent_f)
+            rr, rf, rc, rfc = ops.transe_rank_constrained(q, en, b[lo:hi], p_norm, words, type_constraint.set_ids(r[lo:hi], d), *f)
+            for acc, x in zip(out, (rr, rr if rf is None else rf, rc, rc if rfc is None else rfc)):
+                acc.append(x)
+    return tuple(torch.cat(x) for x in out)
+
+
+def rank_transe_constrained_unfused(ent, rel, triplets, p_norm, norm_flag, type_constraint, filter_index=None, batch=1024):
+    """``rank_transe_constrained`` on materialised distances: ``ranking.rank_from_scores_constrained`` on
+    ``-ops.transe_distances`` -- the bits the fused ranker compares -- chunk by chunk."""
+    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
+    en = ops.transe_queries(ent, norm_flag=norm_flag)
+    v = ent.shape[0]
+    out = [[], [], [], []]
+    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
+        for lo in range(0, a.numel(), batch):
+            hi = min(a.numel(), lo + batch)
+            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
+            listed = None
+            if filter_index is not None:
+                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
+                listed = _listed_mask(f_lo, f_hi, filter_index.entities(d), hi - lo, v, ent.device)
+            cand = type_constraint.mask(type_constraint.set_ids(r[lo:hi], d), ent.device)
+            rr, rf, rc, rfc = rank_from_scores_constrained(-ops.transe_distances(q, en, p_norm), b[lo:hi].long(), cand, listed)
+            for acc, x in zip(out, (rr, rr if rf is None else rf, rc, rc if rfc is None else rfc)):
+                acc.append(x)
+    return tuple(torch.cat(x) for x in out)
+
+
+def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False, verbose=True, type_constraint=None):
     """Raw MRR, MR and Hits@k over both directions, and the filtered ones when ``filter_index`` is given (a FilterIndex,
-    train + valid + test).  Returns {'mrr_raw', 'mr_raw', 'hits_raw': {k: v}} plus the same '_filtered' keys with a filter."""
+    train + valid + test).  Returns {'mrr_raw', 'mr_raw', 'hits_raw': {k: v}} plus the same '_filtered' keys with a filter.
+    With a ``type_constraint`` (ranking.TypeConstraint) the type-constrained protocol is reported too: '_raw_constrained' keys,
+    and '_filtered_constrained' ones with a filter."""
     with torch.no_grad():
         ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
         triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
-        fn = rank_transe_unfused if unfused else rank_transe
-        raw, filt = fn(ent, rel, triplets, model.p_norm, model.norm_flag, filter_index)
-        out = _summary(raw, filt, hits)
+        if type_constraint is None:
+            fn = rank_transe_unfused if unfused else rank_transe
+            raw, filt = fn(ent, rel, triplets, model.p_norm, model.norm_flag, filter_index)
+            out = _summary(raw, filt, hits)
+        else:
+            fn = rank_transe_constrained_unfused if unfused else rank_transe_constrained
+            raw, filt, raw_c, filt_c = fn(ent, rel, triplets, model.p_norm, model.norm_flag, type_constraint, filter_index)
+            out = _summary(raw, filt, hits)
+            out.update(_summary(raw_c, filt_c, hits, '_constrained'))
     kinds = ('raw', 'filtered') if filter_index is not None else ('raw',)
+    if type_constraint is not None:
+        kinds = kinds + tuple(k + '_constrained' for k in kinds)
     if filter_index is None:         # without a filter the "filtered" ranks are the raw ones: not reported
-        out = {k: v for k, v in out.items() if not k.endswith('_filtered')}
+        out = {k: v for k, v in out.items() if '_filtered' not in k}
     if verbose:
         for kind in kinds:
             print('MRR ({}): {:.6f} | MR ({}): {:.3f}'.format(kind, out['mrr_' + kind], kind, out['mr_' + kind]))
@@ -432,13 +488,14 @@ def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False,
 # ------------------------------------------------------------------------------------------------
 # link prediction
 # ------------------------------------------------------------------------------------------------
-def topk_from_distances(dist, k, filt_lo=None, filt_hi=None, filt_ent=None):
+def topk_from_distances(dist, k, filt_lo=None, filt_hi=None, filt_ent=None, cand=None):
     """The top-k rule of ``ops.transe_topk`` on a materialised (m, v) distance matrix, in plain torch (any device):
     ``ranking.topk_from_scores(-dist, ...)`` -- smaller distance first, equal distances by lower id, NaN after every number (+inf
-    included) and by id among themselves, the ids in ``filt_ent[filt_lo[i]:filt_hi[i]]`` no candidates of row i.  Returns
+    included) and by id among themselves, the ids in ``filt_ent[filt_lo[i]:filt_hi[i]]`` no candidates of row i, nor the columns
+    where ``cand`` (a dense (m, v) bool of allowed columns, the rule of ``ops.transe_topk_constrained``) is False.  Returns
     ``(ids int64 (m, k), dist float32 (m, k))`` padded with id -1 / distance +inf; a reported distance is the matrix entry's bit
     pattern, except that a zero is +0 and every NaN the one quiet NaN."""
-    ids, neg = topk_from_scores(-dist.to(torch.float32), k, filt_lo, filt_hi, filt_ent)
+    ids, neg = topk_from_scores(-dist.to(torch.float32), k, filt_lo, filt_hi, filt_ent, cand)
     out = 0.0 - neg                                                   # -(+0) would be -0; 0 - (+0) is +0
     return ids, torch.where(torch.isnan(out), torch.full_like(out, float('nan')), out)
 
@@ -451,7 +508,7 @@ def _tables(model_or_tables):
     return ent.detach(), rel.detach(), p_norm, norm_flag
 
 
-def _predict_topk(model_or_tables, a, r, k, direction, filter_index, select):
+def _predict_topk(model_or_tables, a, r, k, direction, filter_index, select, type_constraint=None):
     if direction not in ('o', 's'):
         raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
     ent, rel, p_norm, norm_flag = _tables(model_or_tables)
@@ -466,7 +523,10 @@ def _predict_topk(model_or_tables, a, r, k, direction, filter_index, select):
         f = (None, None, None)
         if filter_index is not None:
             f = (*filter_index.lookup(a[lo:hi], r[lo:hi], direction), ent_f)
-        i, d = select(q, en, p_norm, f)
+        if type_constraint is None:
+            i, d = select(q, en, p_norm, f)
+        else:
+            i, d = select(q, en, p_norm, f, type_constraint.set_ids(r[lo:hi], direction))
         ids.append(i)
         dist.append(d)
     if not ids:
@@ -474,35 +534,44 @@ def _predict_topk(model_or_tables, a, r, k, direction, filter_index, select):
     return torch.cat(ids), torch.cat(dist)
 
 
-def predict_topk(model_or_tables, a, r, k, direction='o', filter_index=None):
+def predict_topk(model_or_tables, a, r, k, direction='o', filter_index=None, type_constraint=None):
     """Link prediction: the ``k`` nearest entities of every query, ``direction`` 'o' for (a[i], r[i], ?) with
     ``q = n(a) + n(r)`` and 's' for (?, r[i], a[i]) with ``q = n(a) - n(r)``, at distance ``||q - n(E_j)||_p`` -- the queries and
     distances of ``rank_transe``.  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``.  With a
     ``FilterIndex`` the query's known answers are left out (new facts only).  One fused launch pair per ``MAX_QUERY_ROWS``
-    queries (ops.transe_topk); returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of ``topk_from_distances``."""
+    queries (ops.transe_topk); returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of ``topk_from_distances``.
+    With a ``ranking.TypeConstraint`` only the members of the relation's ``direction`` type set are proposed
+    (ops.transe_topk_constrained)."""
     with torch.no_grad():
+        if type_constraint is None:
+            return _predict_topk(model_or_tables, a, r, k, direction, filter_index,
+                                 lambda q, en, p, f: ops.transe_topk(q, en, k, p, *f))
+        words = type_constraint.words.to(_tables(model_or_tables)[0].device)
         return _predict_topk(model_or_tables, a, r, k, direction, filter_index,
-                             lambda q, en, p, f: ops.transe_topk(q, en, k, p, *f))
+                             lambda q, en, p, f, sets: ops.transe_topk_constrained(q, en, k, p, words, sets, *f), type_constraint)
 
 
-def predict_topk_unfused(model_or_tables, a, r, k, direction='o', filter_index=None):
+def predict_topk_unfused(model_or_tables, a, r, k, direction='o', filter_index=None, type_constraint=None):
     """``predict_topk`` from materialised distances (``ops.transe_distances`` + ``topk_from_distances`` per chunk): the in-repo
     cross-check and the bench's comparator, never a fallback."""
     with torch.no_grad():
-        return _predict_topk(model_or_tables, a, r, k, direction, filter_index,
-                             lambda q, en, p, f: topk_from_distances(ops.transe_distances(q, en, p), k, *f))
+        def select(q, en, p, f, sets=None):
+            cand = None if sets is None else type_constraint.mask(sets, q.device)
+            return topk_from_distances(ops.transe_distances(q, en, p), k, *f, cand)
+        return _predict_topk(model_or_tables, a, r, k, direction, filter_index, select, type_constraint)
 
 
-def write_predictions(path, model_or_tables, triplets, k, filter_index):
+def write_predictions(path, model_or_tables, triplets, k, filter_index, type_constraint=None):
     """Top-k link predictions for both directions of every triplet, the known answers (``filter_index``) left out, as TSV in
     train.py's layout: ``direction  query_entity  relation  position  predicted_entity  distance`` -- 'o' lines answer (s, r, ?),
-    's' lines (?, r, o); a query with fewer than k candidates ends in id -1, distance inf.  Returns the number of lines written."""
+    's' lines (?, r, o); a query with fewer than k candidates ends in id -1, distance inf.  With a ``type_constraint`` only members of the
+    relation's type set on that side are written.  Returns the number of lines written."""
     triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
     n = 0
     with open(path, 'w') as f:
         for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
             r = triplets[:, 1]
-            ids, dist = predict_topk(model_or_tables, a, r, k, direction=d, filter_index=filter_index)
+            ids, dist = predict_topk(model_or_tables, a, r, k, direction=d, filter_index=filter_index, type_constraint=type_constraint)
             n += _write_rows(f, d, a.tolist(), r.tolist(), ids.tolist(), dist.tolist())
     return n
 
@@ -540,6 +609,10 @@ def build_parser():
     p.add_argument('--test-mode', action='store_true', help='load --checkpoint and evaluate only')
     p.add_argument('--eval-every', type=int, default=0, help='evaluate on valid every N epochs (0: never)')
     p.add_argument('--filtered-eval', action='store_true', help='report filtered ranks as well (filter: train + valid + test)')
+    p.add_argument('--type-constrain', action='store_true',
+                   help='type-constrained protocol (candidates: the entities seen on that side of the relation in train + valid + '
+                        'test): with --filtered-eval the evaluation reports raw, filtered, raw_constrained and '
+                        'filtered_constrained; with --predict-topk only such entities are written')
     p.add_argument('--graph-step', action='store_true', help='capture one step as a hipGraph and replay it')
     p.add_argument('--predict-topk', type=int, default=None,
                    help='after the final evaluation write the K (1..128) nearest new entities of both directions of every test '
@@ -563,6 +636,8 @@ def check_args(args):
     k = getattr(args, 'predict_topk', None)
     if k is not None and not 1 <= k <= ops.TOPK_MAX:
         raise ValueError(f'--predict-topk must lie in [1, {ops.TOPK_MAX}], got {k}')
+    if getattr(args, 'type_constrain', False) and not getattr(args, 'filtered_eval', False):
+        raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, filtered_constrained')
 
 
 def main(args):
@@ -580,6 +655,9 @@ def main(args):
     filt = None
     if args.filtered_eval:
         filt = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+    types = None
+    if args.type_constrain:
+        types = TypeConstraint(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
     if not args.test_mode:
         model = model.to(dev)
         tr = DeviceTrainer(model, data.train, args.nbatches, args.neg_ent, bool(args.bern_flag), bool(args.filter_flag),
@@ -598,10 +676,10 @@ def main(args):
         model.save_checkpoint(args.checkpoint)
     model.load_checkpoint(args.checkpoint)
     model = model.to(dev)
-    out = evaluate(model, data.test, filt)
+    out = evaluate(model, data.test, filt, type_constraint=types)
     if args.predict_topk is not None:
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
-        n_lines = write_predictions(args.predict_out, model, data.test, args.predict_topk, known)
+        n_lines = write_predictions(args.predict_out, model, data.test, args.predict_topk, known, types)
         print(f'wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to {args.predict_out}')
     return out
 

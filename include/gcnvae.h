@@ -546,6 +546,25 @@ int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const flo
                    const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits, void* workspace, int m, int v,
                    int h, void* stream);
 
+/* Type-constrained ranking and top-k: gv_rank_scores_filtered / gv_topk_scores with a per-query candidate set on top.  The sets
+ * are rows of a bitmask cand [n_sets, ld_cand] (uint32, ld_cand >= ceil(v / 32) words per row): entity j is bit j & 31 of word
+ * j >> 5; bits at positions >= v are ignored.  cand_set int32 [m] names the set of each query; an id outside [0, n_sets) is the
+ * empty set.  All the rules of the unconstrained entry points hold (scores, ties, NaN, filter ranges, padding, workspace).
+ *   gv_rank_scores_constrained : count_raw / count_filt are gv_rank_scores_filtered's, bit for bit; count_raw_c / count_filt_c
+ *     count, of the same candidates j != t_i, only the members of set cand_set[i] (the target is never counted, member or not;
+ *     an empty set gives 0).  The filter is all or none: with filt_lo / filt_hi / filt_ent NULL the two filtered counts are not
+ *     written (and may be NULL).  The four counts come from the same ballots of one launch pair.
+ *   gv_topk_scores_constrained : the candidates of row i are the members of set cand_set[i], less the listed ids when a filter is
+ *     given; workspace of gv_topk_scores_workspace_bytes(m, v, k) bytes. */
+int gv_rank_scores_constrained(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                               const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
+                               int ld_cand, int n_sets, const int32_t* cand_set, float* tgt, int* count_raw, int* count_filt,
+                               int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream);
+int gv_topk_scores_constrained(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
+                               const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand, int n_sets,
+                               const int32_t* cand_set, int k, int* out_ids, float* out_logits, void* workspace, int m, int v, int h,
+                               void* stream);
+
 /* Whole-graph triplet mining (csrc/k_mine.hip): every triplet of a DistMult decoder scored and selected globally, for the
  * entity table e (n, h) and the relation rows w (num_rels, h), both fp32 row-major:
  *   logit[s, r, o] = (e[s] * w[r]) . e[o] (+ *bias)
@@ -627,7 +646,11 @@ int gv_ec_head_bwd(const float* p, const int64_t* labels, const int32_t* row_pos
  *     no candidates of row i.  Rows with fewer than k candidates end in id -1, distance +inf.  A reported distance is
  *     gv_transe_distances' bit pattern of that pair, a zero as +0 and every NaN as the one quiet NaN (0x7fc00000).  q as
  *     gv_transe_queries writes it, en as gv_transe_rank_filtered takes it; workspace of gv_transe_topk_workspace_bytes(m, v, k)
- *     bytes, 8-byte aligned.  The result does not depend on the launch geometry. */
+ *     bytes, 8-byte aligned.  The result does not depend on the launch geometry.
+ *   gv_transe_rank_constrained / gv_transe_topk_constrained : the two above with the per-query candidate sets of
+ *     gv_rank_scores_constrained (cand [n_sets, ld_cand], cand_set [m]): counts_raw / counts_filt are gv_transe_rank_filtered's,
+ *     counts_raw_c / counts_filt_c the same over the set's members; without a filter the two filtered counts are not written.  The
+ *     top-k's candidates are the set's members less the listed ids; workspace as gv_transe_topk. */
 #define GV_TRANSE_MAX_DIM 512
 int gv_transe_sample(const uint64_t* rng_state, uint32_t stream_id, const int32_t* train, int64_t n_train, int n_ent,
                      const float* p_head, const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent_o, const int32_t* f_ent_s,
@@ -648,6 +671,14 @@ int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k);
 int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
                    const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int k, int64_t* out_ids, float* out_dist,
                    void* workspace, void* stream);
+int gv_transe_rank_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
+                               const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, const uint32_t* cand, int ld_cand,
+                               int n_sets, const int32_t* cand_set, int32_t* counts_raw, int32_t* counts_filt, int32_t* counts_raw_c,
+                               int32_t* counts_filt_c, void* stream);
+int gv_transe_topk_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
+                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand,
+                               int n_sets, const int32_t* cand_set, int k, int64_t* out_ids, float* out_dist, void* workspace,
+                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
