@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 from gcn_vae_amd import ops, transe
 from gcn_vae_amd.ranking import FilterIndex, sort_and_rank
@@ -245,11 +246,14 @@ def test_fused_ranks_equal_sort_and_rank_on_distances(p_norm, head):
     ref_f = ((~(sc <= tg)) & keep).sum(1).float() + 0.5 * ((sc == tg) & keep).sum(1).float()
     assert torch.equal(filt, ref_f)
     assert bool((filt <= raw).all())
-    # distances within a float64 bound of the same formula
-    q64 = ops.transe_queries(ent, rel, a, r, head=head).double()
-    d64 = torch.cdist(q64, en.double(), p=p_norm)
+    # distances within a float64 bound of the same formula, queries and table formed in float64 from the HOST tables (the
+    # device's normalised queries are part of what is checked)
+    e64, r64 = F.normalize(ent.cpu().double(), 2, -1), F.normalize(rel.cpu().double(), 2, -1)
+    q64 = e64[a.cpu()] - r64[r.cpu()] if head else e64[a.cpu()] + r64[r.cpu()]
+    d64 = torch.cdist(q64, e64, p=p_norm, compute_mode='donot_use_mm_for_euclid_dist')
     fin = torch.isfinite(d64)
-    assert bool(((dist.double() - d64).abs()[fin] <= 1e-5 * (d64[fin] + 1)).all())
+    assert int(fin.sum()) > 0.9 * fin.numel()
+    assert bool(((dist.cpu().double() - d64).abs()[fin] <= 1e-5 * (d64[fin] + 1)).all())
 
 
 def test_full_size_fused_agrees_with_unfused():
