@@ -1129,6 +1129,225 @@ __global__ __launch_bounds__(256) void k_prior_sample_bwd(const float* z_pre, co
     }
 }
 
+// ---- DistMult + BCE forward that also sums the relation gradient (gv_distmult_bce_fwd_grad) ------------------------------
+// The by-relation sweep of the weight gradient (k_gradw_fast<1,1,4,U>'s geometry: one wave per (relation, slice, slot) item, a
+// lane on four consecutive columns, U triplets' rows in flight) reads the same e_s, e_o rows the scorer reads, and
+// delta_t = sigmoid(x_t) - y_t needs nothing but the score: one pass forms p = e_s*e_o, x = sum_c p_c w_c (w_r's four columns
+// stay in registers over the item), delta, and acc += delta*p.  The unscaled row sum goes to u[r] (unsplit item) or the item's
+// partial slot; gv_distmult_grad_finish scales by the upstream gradient, which does not exist yet when this runs.
+// The grid is red_blocks(T, 16) workgroups, the partial count gv_loss_combine sums, whatever the item count: workgroup b
+// takes the item quads b, b + grid, ...  (grid % 8 == 0 whenever the list has XCD windows, so a quad keeps its XCD).
+struct DmFusedParams {
+    const int4* items;
+    int n_items;
+    const int* rel_s;
+    const int* rel_o;
+    const int* rel_tid;
+    const float* e;
+    int ld_e;
+    const float* w;
+    int ld_w;
+    const float* labels;
+    const float* bias;
+    const int* pos3;
+    float* score;
+    float* delta;        // pos3: [2T] in entity-incidence order; else [T] in triplet order
+    float* u;            // [num_rels][h]
+    float* partial;      // [n_slots][h]
+    float* part;         // [2 * DM_PART]: BCE partials, then the delta partials
+    int h;
+};
+
+constexpr int DM_PART = RED_BLOCKS;
+
+__device__ __forceinline__ int dm_rl_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+
+template <int U>
+__global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedParams a) {
+    __shared__ float sm[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool active = lane * 4 < a.h;
+    const int c0 = active ? lane * 4 : 0;
+    const float bv = a.bias ? *a.bias : 0.f;
+    const float* __restrict__ ebase = a.e + c0;
+    float lsum = 0.f, dsum = 0.f;          // per lane: the triplets whose scalars this lane finishes
+    // x (wave-uniform) of one triplet from its lane products, delta, and the row sum
+    auto triplet = [&](const float (&xs)[4], const float (&xo)[4], const float (&wr)[4], float y, float (&acc)[4], float& x,
+                       float& d) {
+        float p[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) p[i] = active ? xs[i] * xo[i] : 0.f;
+        float dot = p[0] * wr[0];
+        dot = fmaf(p[1], wr[1], dot);
+        dot = fmaf(p[2], wr[2], dot);
+        dot = fmaf(p[3], wr[3], dot);
+        x = wave_sum(dot) + bv;
+        d = 1.f / (1.f + expf(-x)) - y;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaf(d, p[i], acc[i]);
+    };
+    for (int quad = blockIdx.x; quad * 4 < a.n_items; quad += gridDim.x) {
+        const int item = __builtin_amdgcn_readfirstlane(quad * 4 + wv);
+        if (item >= a.n_items) continue;
+        const int4 it = a.items[item];
+        if (it.x < 0) continue;                 // unused tail entry of an upper-bound-sized item list
+        if (it.w >= 0 && !a.partial) continue;   // split item without a partial buffer: never dereference NULL
+        float wr[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};
+        if (active) load_vec<4>(a.w + (size_t)it.x * a.ld_w + c0, wr);
+        for (int e0 = it.y; e0 < it.z; e0 += 64) {
+            const int cnt = min(64, it.z - e0);
+            int my_s = 0, my_o = 0, my_t = 0;
+            float my_y = 0.f, my_x = 0.f, my_d = 0.f;
+            if (lane < cnt) {
+                my_s = a.rel_s[e0 + lane];
+                my_o = a.rel_o[e0 + lane];
+                my_t = a.rel_tid[e0 + lane];
+                my_y = a.labels[my_t];
+            }
+            int j = 0;
+            for (; j + U <= cnt; j += U) {
+                float xs[U][4], xo[U][4];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int s = dm_rl_i(my_s, j + u), o = dm_rl_i(my_o, j + u);
+                    if (active) {
+                        load_vec<4>(ebase + (size_t)s * a.ld_e, xs[u]);
+                        load_vec<4>(ebase + (size_t)o * a.ld_e, xo[u]);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    float x, d;
+                    triplet(xs[u], xo[u], wr, rl_bcast_f(my_y, j + u), acc, x, d);
+                    if (lane == j + u) { my_x = x; my_d = d; }
+                }
+            }
+            for (; j < cnt; ++j) {
+                float xs[4], xo[4], x, d;
+                const int s = dm_rl_i(my_s, j), o = dm_rl_i(my_o, j);
+                if (active) {
+                    load_vec<4>(ebase + (size_t)s * a.ld_e, xs);
+                    load_vec<4>(ebase + (size_t)o * a.ld_e, xo);
+                }
+                triplet(xs, xo, wr, rl_bcast_f(my_y, j), acc, x, d);
+                if (lane == j) { my_x = x; my_d = d; }
+            }
+            if (lane < cnt) {       // the batch's scalars, one triplet per lane
+                a.score[my_t] = my_x;
+                if (a.pos3) {
+                    a.delta[a.pos3[3 * (size_t)my_t]] = my_d;
+                    a.delta[a.pos3[3 * (size_t)my_t + 1]] = my_d;
+                } else {
+                    a.delta[my_t] = my_d;
+                }
+                lsum += fmaxf(my_x, 0.f) - my_x * my_y + log1pf(expf(-fabsf(my_x)));
+                dsum += my_d;
+            }
+        }
+        if (active) store_vec<4>((it.w >= 0 ? a.partial + (size_t)it.w * a.h : a.u + (size_t)it.x * a.h) + c0, acc);
+    }
+    const float lt = block_sum_256(lsum, sm);
+    const float dt = block_sum_256(dsum, sm);
+    if (threadIdx.x == 0) {
+        a.part[blockIdx.x] = lt;
+        a.part[DM_PART + blockIdx.x] = dt;
+    }
+}
+
+// The backward's one launch behind it, the blocks dealt by range:
+//   [0, nb_rows)          relation rows, 64 lanes x 4 columns per wave, 4 rows per block:
+//                         g_w[r] (+)= (g/T) * (u[r], or the ordered sum of r's slots) + g * reg_scale * w[r]
+//   [nb_rows, +nb_coef)   d_out[i] = (g/T) * delta[i]
+//   last block (bias)     dbias = (g/T) * sum of the delta partials, in index order
+// A row is split exactly when it has more than `chunk` triplets; its slots are found through the fix list.
+struct DmFinishParams {
+    const float* gloss;
+    const float* u;
+    const float* partial;
+    const int4* fix;
+    int n_fix;
+    const int* rowptr;
+    int chunk, num_rels, h;
+    const float* w;
+    int ld_w;
+    float reg_scale;
+    float* g_w;
+    int ld_gw, accumulate;
+    const float* delta;
+    float* d_out;
+    int64_t n_coef;
+    const float* part;
+    int n_part;
+    float* dbias;
+    int64_t t;
+    int nb_rows, nb_coef;
+};
+
+__global__ __launch_bounds__(256) void k_distmult_grad_finish(const DmFinishParams a) {
+    __shared__ float sm[4];
+    const float g = a.gloss ? *a.gloss : 1.f;
+    const float gt = g / (float)a.t;
+    const int b = blockIdx.x;
+    if (b < a.nb_rows) {
+        const int lane = threadIdx.x & 63;
+        const int n_rows = a.num_rels + a.n_fix;          // rows first (split ones skipped), then the fix entries
+        const int row = b * 4 + (threadIdx.x >> 6);
+        if (row >= n_rows || lane * 4 >= a.h) return;
+        const int c0 = lane * 4;
+        int r;
+        float acc[4];
+        if (row < a.num_rels) {
+            r = row;
+            if (a.rowptr[r + 1] - a.rowptr[r] > a.chunk) return;      // split: the fix entry's wave writes it
+            load_vec<4>(a.u + (size_t)r * a.h + c0, acc);
+        } else {
+            const int4 f = a.fix[row - a.num_rels];
+            if (f.x < 0) return;                  // unused tail entry of an upper-bound-sized fix list
+            r = f.x;
+            // ordered slot sum: four interleaved chains, then a fixed combine (as the grad-W fix-up)
+            const float4* __restrict__ p = reinterpret_cast<const float4*>(a.partial + (size_t)f.y * a.h + c0);
+            const size_t stride = (size_t)(a.h >> 2);
+            float4 s[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            int k = 0;
+            for (; k + 4 <= f.z; k += 4) {
+                float4 v[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = p[(size_t)(k + i) * stride];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { s[i].x += v[i].x; s[i].y += v[i].y; s[i].z += v[i].z; s[i].w += v[i].w; }
+            }
+            for (; k < f.z; ++k) {
+                const float4 v = p[(size_t)k * stride];
+                s[0].x += v.x; s[0].y += v.y; s[0].z += v.z; s[0].w += v.w;
+            }
+            acc[0] = (s[0].x + s[1].x) + (s[2].x + s[3].x);
+            acc[1] = (s[0].y + s[1].y) + (s[2].y + s[3].y);
+            acc[2] = (s[0].z + s[1].z) + (s[2].z + s[3].z);
+            acc[3] = (s[0].w + s[1].w) + (s[2].w + s[3].w);
+        }
+        float wr[4], out[4];
+        load_vec<4>(a.w + (size_t)r * a.ld_w + c0, wr);
+        float* o = a.g_w + (size_t)r * a.ld_gw + c0;
+        if (a.accumulate) load_vec<4>(o, out);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float v = fmaf(gt, acc[i], g * a.reg_scale * wr[i]);
+            out[i] = a.accumulate ? out[i] + v : v;
+        }
+        store_vec<4>(o, out);
+    } else if (b < a.nb_rows + a.nb_coef) {
+        for (int64_t i = (int64_t)(b - a.nb_rows) * 256 + threadIdx.x; i < a.n_coef; i += (int64_t)a.nb_coef * 256)
+            a.d_out[i] = gt * a.delta[i];
+    } else {
+        float acc = 0.f;
+        for (int i = threadIdx.x; i < a.n_part; i += 256) acc += a.part[DM_PART + i];
+        const float tot = block_sum_256(acc, sm);
+        if (threadIdx.x == 0) *a.dbias = gt * tot;
+    }
+}
+
 constexpr int KL_SLICES = 256;      // row slices of the mixture-gradient partial sums
 constexpr int KL_FUSED_KT = 16;     // (also the 16-lane group that carries one row's responsibilities)     // the fused backward keeps 4*KT floats per lane: k <= 16 (the reference's mog_k is 10)
 
@@ -1453,4 +1672,46 @@ extern "C" int gv_prior_sample_bwd(const float* z_pre, const float* eps, const f
     GV_REQUIRE(s > 0 && k > 0 && h > 0, GV_ERR_SHAPE, "gv_prior_sample_bwd: bad shape");
     hipLaunchKernelGGL(k_prior_sample_bwd, dim3((k * h + 255) / 256), dim3(256), 0, GV_ST, z_pre, eps, g, gz_pre, accumulate, s, k, h);
     return launch_status("gv_prior_sample_bwd");
+}
+
+extern "C" int gv_distmult_bce_fwd_grad(const int32_t* items, int n_items, const int32_t* rel_s, const int32_t* rel_o,
+                                        const int32_t* rel_tid, const float* embed, int ld_e, const float* w_rel, int ld_w,
+                                        const float* labels, const float* bias, const int32_t* pos3, float* score,
+                                        float* delta, float* u, float* partial, float* workspace, int64_t t, int h,
+                                        void* stream) {
+    GV_REQUIRE(items && rel_s && rel_o && rel_tid && embed && w_rel && labels && score && delta && u && workspace,
+               GV_ERR_NULL, "gv_distmult_bce_fwd_grad: NULL pointer");
+    GV_REQUIRE(t > 0 && t < (1ll << 30) && n_items > 0, GV_ERR_SHAPE, "gv_distmult_bce_fwd_grad: t=%lld n_items=%d",
+               (long long)t, n_items);
+    GV_REQUIRE(h > 0 && h <= 256 && h % 4 == 0 && ld_e >= h && ld_w >= h && ld_e % 4 == 0 && ld_w % 4 == 0, GV_ERR_SHAPE,
+               "gv_distmult_bce_fwd_grad: h=%d (ld %d, %d): the fused sweep covers h <= 256, h %% 4 == 0", h, ld_e, ld_w);
+    GV_REQUIRE(aligned16(embed) && aligned16(w_rel) && aligned16(u) && aligned16(partial), GV_ERR_ALIGN,
+               "gv_distmult_bce_fwd_grad: 16-B alignment required");
+    DmFusedParams p{(const int4*)items, n_items, rel_s, rel_o, rel_tid, embed, ld_e, w_rel, ld_w, labels, bias, pos3,
+                    score, delta, u, partial, workspace, h};
+    hipLaunchKernelGGL(k_distmult_bce_fwd_grad<8>, dim3(red_blocks(t, 16)), dim3(256), 0, GV_ST, p);
+    return launch_status("gv_distmult_bce_fwd_grad");
+}
+
+extern "C" int gv_distmult_grad_finish(const float* gloss, const float* u, const float* partial, const int32_t* fix,
+                                       int n_fix, const int32_t* rowptr, int chunk, int num_rels, int h,
+                                       const float* w_rel, int ld_w, float reg_scale, float* grad_w, int ld_gw,
+                                       int accumulate, const float* delta, float* d_out, int64_t n_coef,
+                                       const float* workspace, float* dbias, int64_t t, void* stream) {
+    GV_REQUIRE(u && rowptr && w_rel && grad_w && delta && d_out, GV_ERR_NULL, "gv_distmult_grad_finish: NULL pointer");
+    GV_REQUIRE(n_fix == 0 || (fix && partial), GV_ERR_NULL, "gv_distmult_grad_finish: split rows need fix + partial");
+    GV_REQUIRE(!dbias || workspace, GV_ERR_NULL, "gv_distmult_grad_finish: dbias needs the forward's workspace");
+    GV_REQUIRE(t > 0 && n_coef > 0 && n_fix >= 0 && num_rels > 0 && chunk > 0, GV_ERR_SHAPE,
+               "gv_distmult_grad_finish: t=%lld n_coef=%lld n_fix=%d num_rels=%d chunk=%d", (long long)t, (long long)n_coef,
+               n_fix, num_rels, chunk);
+    GV_REQUIRE(h > 0 && h <= 256 && h % 4 == 0 && ld_w >= h && ld_gw >= h && ld_w % 4 == 0 && ld_gw % 4 == 0, GV_ERR_SHAPE,
+               "gv_distmult_grad_finish: h=%d (ld %d, %d): h <= 256, h %% 4 == 0", h, ld_w, ld_gw);
+    GV_REQUIRE(aligned16(u) && aligned16(partial) && aligned16(w_rel) && aligned16(grad_w), GV_ERR_ALIGN,
+               "gv_distmult_grad_finish: 16-B alignment required");
+    DmFinishParams p{gloss, u, partial, (const int4*)fix, n_fix, rowptr, chunk, num_rels, h, w_rel, ld_w, reg_scale, grad_w,
+                     ld_gw, accumulate, delta, d_out, n_coef, workspace, red_blocks(t, 16), dbias, t, 0, 0};
+    p.nb_rows = (num_rels + n_fix + 3) / 4;
+    p.nb_coef = red_blocks(n_coef, 1024);
+    hipLaunchKernelGGL(k_distmult_grad_finish, dim3(p.nb_rows + p.nb_coef + (dbias ? 1 : 0)), dim3(256), 0, GV_ST, p);
+    return launch_status("gv_distmult_grad_finish");
 }

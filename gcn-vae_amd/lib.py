@@ -137,6 +137,8 @@ SIGNATURES = {
     'gv_reparam_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     'gv_distmult_bce_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     'gv_bce_grad': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    'gv_distmult_bce_fwd_grad': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    'gv_distmult_grad_finish': (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _I, _F, _P, _I, _I, _P, _P, _L, _P, _P, _L, _P]),
     'gv_mean_sq': (_I, [_P, _L, _F, _P, _P, _I, _P]),
     'gv_mean_sq2': (_I, [_P, _L, _F, _P, _L, _F, _P, _P, _P, _L, _P]),
     'gv_axpby': (_I, [_L, _P, _F, _P, _F, _P, _P]),

@@ -2281,12 +2281,52 @@ def reparam(h2, eps, z_pre=None):
     return z, m, v
 
 
+# The DistMult head's forward in by-relation order, summing the relation gradient on the way (gv_distmult_bce_fwd_grad), and the
+# backward's one finishing launch (gv_distmult_grad_finish) in place of gv_bce_grad + the 1x1 grad-W launches + the regulariser's
+# axpby.  GV_DISTMULT_FUSED=0: the separate sweeps.
+DISTMULT_FUSED = _os.environ.get('GV_DISTMULT_FUSED', '1') == '1'
+
+
+def distmult_fused_ok(embed, ld_e, w_rel, ld_w):
+    """THE shape rule of the fused DistMult sweep: a wave's 64 lanes hold four consecutive columns each (h <= 256, h % 4 == 0,
+    16-B aligned rows).  Everything else (h = 500 of BASELINE configs[3] among it) keeps the three separate sweeps."""
+    h = embed.shape[1]
+    return (DISTMULT_FUSED and h % 4 == 0 and h <= 256 and ld_e % 4 == 0 and ld_w % 4 == 0
+            and embed.data_ptr() % 16 == 0 and w_rel.data_ptr() % 16 == 0)
+
+
+def _distmult_fused_fwd(embed, ld_e, w_rel, ld_w, labels, bias, tidx, score, ws):
+    """Launch the fused forward; returns what the finishing launch needs: (delta, u, partial).  ``ws``: 2048 floats."""
+    seg, T, h = tidx.rel, tidx.T, embed.shape[1]
+    _check_items(seg)
+    f32 = dict(dtype=torch.float32, device=embed.device)
+    delta = torch.empty(2 * T if tidx.pos3 is not None else T, **f32)
+    u = torch.empty(w_rel.shape[0], h, **f32)
+    partial = torch.empty(seg.n_slots, h, **f32) if seg.n_fix > 0 else None
+    lib.call('gv_distmult_bce_fwd_grad', ptr(seg.items), seg.n_items, ptr(tidx.rel_s), ptr(tidx.rel_o), ptr(tidx.rel_tid),
+             ptr(embed), ld_e, ptr(w_rel), ld_w, ptr(labels), ptr(bias), ptr(tidx.pos3), ptr(score), ptr(delta), ptr(u),
+             ptr(partial), ptr(ws), T, h, lib.stream())
+    return delta, u, partial
+
+
+def _distmult_fused_finish(fused, gloss, tidx, w_rel, ld_w, reg_scale, g_w, accumulate, ws, dbias):
+    """g_w (+)= (g/T) * relation row sums + g * reg_scale * w_rel, *dbias, and the returned coefficients (g/T) * delta (a fresh
+    buffer: a second backward over a retained graph scales the forward's delta again, not its own output)."""
+    delta, u, partial = fused
+    seg = tidx.rel
+    d_out = torch.empty_like(delta)
+    lib.call('gv_distmult_grad_finish', ptr(gloss), ptr(u), ptr(partial), ptr(seg.fix), seg.n_fix, ptr(seg.rowptr), seg.chunk,
+             w_rel.shape[0], w_rel.shape[1], ptr(w_rel), ld_w, float(reg_scale), ptr(g_w), g_w.stride(0), 1 if accumulate else 0,
+             ptr(delta), ptr(d_out), delta.numel(), ptr(ws), ptr(dbias), tidx.T, lib.stream())
+    return d_out
+
+
 class _DistMultBCE(torch.autograd.Function):
     """(loss, score) of the DistMult scorer with BCE-with-logits (mean); ``bias`` = flow_log_prob or None.
     ``gscore`` handed to backward (from users of ``score``) is added to the BCE gradient."""
 
     @staticmethod
-    def forward(ctx, embed, w_rel, bias, labels, tidx):
+    def forward(ctx, embed, w_rel, bias, labels, tidx, grad_mode=True):
         ctx.set_materialize_grads(False)
         embed, ld_e = _row_major(embed, 'embed')
         w_rel, ld_w = _row_major(w_rel, 'w_relation')
@@ -2296,25 +2336,40 @@ class _DistMultBCE(torch.autograd.Function):
             raise ValueError('labels / triplets length mismatch')
         score = torch.empty(T, dtype=torch.float32, device=embed.device)
         loss = torch.empty((), dtype=torch.float32, device=embed.device)
-        ws = torch.empty(1024, dtype=torch.float32, device=embed.device)
-        lib.call('gv_distmult_bce_fwd', ptr(embed), ld_e, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order),
-                 ptr(labels), ptr(bias), ptr(score), ptr(loss), ptr(ws), T, h, lib.stream())
+        ws = torch.empty(2048, dtype=torch.float32, device=embed.device)
+        ctx.fused = None
+        # (grad_mode: the caller's torch.is_grad_enabled() -- inside forward it is always off)
+        if grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and distmult_fused_ok(embed, ld_e, w_rel, ld_w):
+            ctx.fused = _distmult_fused_fwd(embed, ld_e, w_rel, ld_w, labels, bias, tidx, score, ws)
+            lib.call('gv_loss_combine', ptr(ws), T, None, 0, 0, None, 0, h, 0, None, 0, 0, 0.0, 0.0, 0.0, None, ptr(loss), None,
+                     lib.stream())
+        else:
+            lib.call('gv_distmult_bce_fwd', ptr(embed), ld_e, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order),
+                     ptr(labels), ptr(bias), ptr(score), ptr(loss), ptr(ws), T, h, lib.stream())
         ctx.save_for_backward(embed, w_rel, labels, score)
-        ctx.tidx, ctx.has_bias = tidx, bias is not None
+        ctx.tidx, ctx.has_bias, ctx.ws, ctx.ld_w = tidx, bias is not None, ws, ld_w
         ctx.mark_non_differentiable(score)
         return loss, score
 
     @staticmethod
     def backward(ctx, gloss, _gscore):
         if gloss is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         embed, w_rel, labels, score = ctx.saved_tensors
         tidx = ctx.tidx
         T, h = tidx.T, embed.shape[1]
         dev = embed.device
         gloss = _chk(gloss.reshape(1).contiguous(), name='gloss')
-        dscore = torch.empty(T, dtype=torch.float32, device=dev)
         dbias = torch.empty((), dtype=torch.float32, device=dev) if ctx.has_bias else None
+        if ctx.fused is not None:
+            g_w = torch.empty_like(w_rel)
+            d_inc = _distmult_fused_finish(ctx.fused, gloss, tidx, w_rel, ctx.ld_w, 0.0, g_w, False, ctx.ws, dbias)
+            g_embed = None
+            if ctx.needs_input_grad[0]:
+                g_embed = bdd_aggregate(tidx.inc, tidx.inc_other, tidx.inc_rel, d_inc,
+                                        None if tidx.pos3 is not None else tidx.inc_tid, embed, w_rel, h, 1, 1)
+            return g_embed, (g_w if ctx.needs_input_grad[1] else None), dbias, None, None, None
+        dscore = torch.empty(T, dtype=torch.float32, device=dev)
         ws = torch.empty(1024, dtype=torch.float32, device=dev)
         lib.call('gv_bce_grad', ptr(score), ptr(labels), ptr(gloss), ptr(dscore), None, None, None, ptr(dbias), ptr(ws), T,
                  lib.stream())
@@ -2324,11 +2379,11 @@ class _DistMultBCE(torch.autograd.Function):
                                     h, 1, 1)
         if ctx.needs_input_grad[1]:
             g_w = bdd_grad_weight(tidx.rel, tidx.rel_s, tidx.rel_o, dscore, tidx.rel_tid, embed, embed, h, 1, 1)
-        return g_embed, g_w, dbias, None, None
+        return g_embed, g_w, dbias, None, None, None
 
 
 def distmult_bce(embed, w_rel, bias, labels, tidx):
-    return _DistMultBCE.apply(embed, w_rel, bias, labels, tidx)
+    return _DistMultBCE.apply(embed, w_rel, bias, labels, tidx, torch.is_grad_enabled())
 
 
 class _DistMultScore(torch.autograd.Function):
@@ -2644,7 +2699,7 @@ class _LossHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, reg_w, kl_w, mmd_w, score_bias,
-                embed_rows=None, rows_dev=None, kl_link=None):
+                embed_rows=None, rows_dev=None, kl_link=None, grad_mode=True):
         z, ld_z = _row_major(z, 'embed')
         if rows_dev is not None:          # static-shape batch: rows [*rows_dev, n) of z are padding (include/gcnvae.h, rows_dev)
             rows_dev = _chk(rows_dev.reshape(-1), torch.int32, 'rows_dev')
@@ -2659,7 +2714,7 @@ class _LossHead(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         scal = torch.empty(4, **f32)                 # pred, reg, kl, mmd (each written before it is read)
         pred, reg, kl, mmd = scal[0:1], scal[1:2], scal[2:3], scal[3:4]
-        ws, ws2 = torch.empty(1024, **f32), torch.empty(1024, **f32)
+        ws, ws2 = torch.empty(2048, **f32), torch.empty(1024, **f32)
         score = torch.empty(T, **f32)
         loss = torch.empty((), **f32)
         bias = flp if (score_bias and flp is not None) else None
@@ -2696,8 +2751,15 @@ class _LossHead(torch.autograd.Function):
         lib.call('gv_mean_sq2', ptr(z), z.numel(), 1.0 / z_count, ptr(w_rel), w_rel.numel(), 1.0 / w_rel.numel(), None,
                  ptr(ws2), ptr(rows_dev), n, st)
         # DistMult scorer + BCE (three 800-B row gathers per triplet: the bandwidth-bound part)
-        lib.call('gv_distmult_bce_fwd', ptr(z), ld_z, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order), ptr(labels),
-                 ptr(bias), ptr(score), None, ptr(ws), T, h, st)
+        # (with a backward to come and a width the fused sweep covers: in by-relation order, the relation gradient's sums with it)
+        ctx.fused = None
+        # (grad_mode: the caller's torch.is_grad_enabled() -- inside forward it is always off)
+        if grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and distmult_fused_ok(z, ld_z, w_rel, ld_w):
+            ctx.fused = _distmult_fused_fwd(z, ld_z, w_rel, ld_w, labels, bias, tidx, score, ws)
+            ctx.ws = ws
+        else:
+            lib.call('gv_distmult_bce_fwd', ptr(z), ld_z, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order), ptr(labels),
+                     ptr(bias), ptr(score), None, ptr(ws), T, h, st)
         lib.call('gv_loss_combine', ptr(ws), T, ptr(ws2), z.numel(), w_rel.numel(), ptr(wsk) if kl_w > 0 else None, n, h,
                  (z_pre.shape[0] // 2) if kl_w > 0 else 0, ptr(wsm) if mmd_w > 0 else None,
                  z_pri.shape[0] if mmd_w > 0 else 0, pick.numel() if mmd_w > 0 else 0, float(reg_w), float(kl_w),
@@ -2717,7 +2779,7 @@ class _LossHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gp, _gk, _gm):
         if g is None:
-            return (None,) * 17
+            return (None,) * 18
         z, z_mean, z_sigma, w_rel, z_pre, resp, z_pri, z_post, pick, labels, score, wsk, rows_dev = ctx.saved_tensors
         z_count = ctx.z_count
         tidx, reg_w, kl_w, mmd_w, has_bias, flp_in_kl = ctx.meta
@@ -2725,9 +2787,10 @@ class _LossHead(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         g = _chk(g.reshape(1).contiguous(), name='gloss')
         # every buffer a side branch writes is allocated here, before the forks
-        dscore = torch.empty(T, **f32)
-        dbias = torch.empty((), **f32) if has_bias else None      # (written by gv_bce_grad's ordered final sum: no fill)
-        ws = torch.empty(1024, **f32)
+        fused = ctx.fused
+        dscore = torch.empty(T, **f32) if fused is None else None
+        dbias = torch.empty((), **f32) if has_bias else None      # (written by an ordered final sum: no fill)
+        ws = torch.empty(1024, **f32) if fused is None else None
         link = ctx.kl_link
         gz = torch.empty_like(z) if link is None else None
         gm = gv = gzp = d_zp = g_pri = g_post = None
@@ -2764,16 +2827,21 @@ class _LossHead(torch.autograd.Function):
                 lib.call('gv_mmd_bwd', ptr(z_pri), ptr(z), ptr(pick), z_pri.shape[0], pick.numel(), h, ptr(g), mmd_w,
                          ptr(g_pri), ptr(gz), s1)
         # main: dL/dscore, then the relation-side gradient (does not need gz)
-        if tidx.pos3 is not None:      # dL/dscore also lands in the two launches' own orders
-            d_inc, d_rel, idx_inc, idx_rel = torch.empty(2 * T, **f32), torch.empty(T, **f32), None, None
+        if fused is not None:          # the forward summed the relation rows: scale them, add the regulariser, scale delta
+            d_inc = _distmult_fused_finish(fused, g, tidx, w_rel, h, 2.0 * reg_w / w_rel.numel(), g_w, d_w is not None, ctx.ws,
+                                           dbias)
+            idx_inc = None if tidx.pos3 is not None else tidx.inc_tid
         else:
-            d_inc, d_rel, idx_inc, idx_rel = dscore, dscore, tidx.inc_tid, tidx.rel_tid
-        lib.call('gv_bce_grad', ptr(score), ptr(labels), ptr(g), ptr(dscore), ptr(tidx.pos3),
-                 ptr(d_inc) if tidx.pos3 is not None else None, ptr(d_rel) if tidx.pos3 is not None else None,
-                 ptr(dbias), ptr(ws), T, st)
-        bdd_grad_weight(tidx.rel, tidx.rel_s, tidx.rel_o, d_rel, idx_rel, z, z, h, 1, 1, out=g_w,
-                        accumulate=d_w is not None)
-        lib.call('gv_axpby', w_rel.numel(), ptr(g), 2.0 * reg_w / w_rel.numel(), ptr(w_rel), 1.0, ptr(g_w), st)
+            if tidx.pos3 is not None:      # dL/dscore also lands in the two launches' own orders
+                d_inc, d_rel, idx_inc, idx_rel = torch.empty(2 * T, **f32), torch.empty(T, **f32), None, None
+            else:
+                d_inc, d_rel, idx_inc, idx_rel = dscore, dscore, tidx.inc_tid, tidx.rel_tid
+            lib.call('gv_bce_grad', ptr(score), ptr(labels), ptr(g), ptr(dscore), ptr(tidx.pos3),
+                     ptr(d_inc) if tidx.pos3 is not None else None, ptr(d_rel) if tidx.pos3 is not None else None,
+                     ptr(dbias), ptr(ws), T, st)
+            bdd_grad_weight(tidx.rel, tidx.rel_s, tidx.rel_o, d_rel, idx_rel, z, z, h, 1, 1, out=g_w,
+                            accumulate=d_w is not None)
+            lib.call('gv_axpby', w_rel.numel(), ptr(g), 2.0 * reg_w / w_rel.numel(), ptr(w_rel), 1.0, ptr(g_w), st)
         join(1)
         g_z = bdd_aggregate(indices.largest_first(tidx.inc) if indices.K1_ITEMS_LARGEST_FIRST else tidx.inc, tidx.inc_other, tidx.inc_rel,
                             d_inc, idx_inc, z, w_rel, h, 1, 1, addend=gz)
@@ -2784,13 +2852,14 @@ class _LossHead(torch.autograd.Function):
             lib.call('gv_lincomb4', ptr(dbias) if has_bias else None, 1.0, ptr(g) if flp_in_kl else None, kl_w, None, 0.0,
                      None, 0.0, ptr(g_flp), st)
         return (g_z, gm, gv, (None if d_w is not None else g_w), (None if d_zp is not None else gzp), g_flp, g_pri, None,
-                None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None)
 
 
 def loss_head(z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, reg_w, kl_w, mmd_w, score_bias,
               embed_rows=None, rows_dev=None):
     return _LossHead.apply(z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, float(reg_w), float(kl_w),
-                           float(mmd_w), bool(score_bias), embed_rows, rows_dev, getattr(z, '_gv_kl_link', None))
+                           float(mmd_w), bool(score_bias), embed_rows, rows_dev, getattr(z, '_gv_kl_link', None),
+                           torch.is_grad_enabled())
 
 
 # ------------------------------------------------------------------------------------------------

@@ -775,6 +775,28 @@ int gv_bce_grad(const float* score, const float* labels, const float* gloss, flo
  * the two K1 launches of the DistMult backward: dscore_t is then also written to dscore_inc / dscore_rel at those
  * positions, and the launches take their edge coefficient without a coef_idx indirection. */
 
+/* The same forward in BY-RELATION order, summing the relation gradient on the way (h <= 256, h % 4 == 0, 16-B aligned rows):
+ * one wave per work item of the by-relation triplet list (items int32 [n_items][4] = relation, begin, end, slot or -1, as
+ * gv_rgcn_bdd_grad_weight takes them; rel_s / rel_o / rel_tid int32 [T] = subject, object, triplet id by position).
+ *   score[t] as above;  delta_t = sigmoid(score_t) - label_t, written to delta[pos3[t][0]] and delta[pos3[t][1]] (pos3 given:
+ *   delta is [2T], the entity-incidence order) or to delta[t];  u[r] = sum_t delta_t e[s_t] * e[o_t] over an unsplit item,
+ *   partial[slot] for a split one (u: [num_rels][h], partial: [n_slots][h], may be NULL when no item has a slot).
+ * workspace: 2048 floats -- the BCE partial sums where gv_loss_combine (or a sum over red = min(1024, ceil(T / 16)) entries,
+ * times 1/T) expects them, and from entry 1024 on as many partial sums of delta.
+ * gv_distmult_grad_finish is the backward's one launch behind it (gloss: device scalar, NULL = 1):
+ *   grad_w[r] (+)= (gloss/T) * (u[r], or the ordered sum of r's slots: fix int32 [n_fix][4] = row, first slot, slots, 0)
+ *                 + gloss * reg_scale * w_rel[r]          (rowptr int32 [num_rels + 1] and chunk: the list's; accumulate: +=)
+ *   d_out[i] = (gloss/T) * delta[i], i < n_coef (a fresh buffer: delta stays as the forward left it)
+ *   *dbias = (gloss/T) * sum_t delta_t   (dbias optional; workspace = the forward's) */
+int gv_distmult_bce_fwd_grad(const int32_t* items, int n_items, const int32_t* rel_s, const int32_t* rel_o,
+                             const int32_t* rel_tid, const float* embed, int ld_e, const float* w_rel, int ld_w,
+                             const float* labels, const float* bias, const int32_t* pos3, float* score, float* delta,
+                             float* u, float* partial, float* workspace, int64_t t, int h, void* stream);
+int gv_distmult_grad_finish(const float* gloss, const float* u, const float* partial, const int32_t* fix, int n_fix,
+                            const int32_t* rowptr, int chunk, int num_rels, int h, const float* w_rel, int ld_w,
+                            float reg_scale, float* grad_w, int ld_gw, int accumulate, const float* delta, float* d_out,
+                            int64_t n_coef, const float* workspace, float* dbias, int64_t t, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K6  fused reductions
  *   gv_mean_sq : *out (+)= scale * sum(x^2)            (regularization_loss, kgvae/link_predict.py:68-69)
