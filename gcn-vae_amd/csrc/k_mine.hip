@@ -22,20 +22,14 @@
 // The filter is applied before either: the (lo, hi, ent) ranges per key s * R + r are re-bucketed per tile pair first (count,
 // scan, fill: three small kernels, integer atomics), so a workgroup reads ITS listed triplets once into LDS and a relation
 // without one -- nearly all of them -- costs one LDS flag.  No float atomics anywhere.
-#include <limits.h>
-
-#include <algorithm>
-
 #include "common.h"
+#include "k_mine.h"
 
 namespace gv {
 
 typedef float mine_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MINE_KC_MAX = 240;       // k per staged chunk (multiple of 16): 2 x 64 x 244 floats = 122 KiB of the 160
-constexpr int MINE_FL_CAP = 1024;      // listed triplets of a tile pair kept in LDS (the rest is read from memory)
-constexpr int MINE_HIST_BITS = 12;
-constexpr int MINE_REL_BITS = 19;      // packed filter entry: relation << 12 | local subject << 6 | local object
 
 struct MineParams {
     const float* e;
@@ -56,18 +50,6 @@ struct MineParams {
     unsigned long long* counter;
     unsigned long long* hist;
 };
-
-// the key of gv_topk_scores' order (k_gemm.hip: topk_key), logit part
-__device__ __forceinline__ unsigned mine_key(float x) {
-    unsigned u = __float_as_uint(x);
-    if (x != x) return 0u;
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float mine_key_logit(unsigned o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 
 // one 64-row tile of E, columns [k0, k0 + kc), into LDS: row pitch kc + 4, even k first, then odd k; zeros outside the table
 __device__ __forceinline__ void mine_stage_tile(float* dst, const float* e, int ld, bool vec, int row0, int n, int k0, int h, int kc) {
@@ -129,13 +111,8 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     const bool diag = p.exclude_self && m0 == n0;
     const float bv = p.bias ? *p.bias : 0.f;
 
-    int f_base = 0, f_cnt = 0;
-    if (p.tile_ptr) {
-        const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-        f_base = p.tile_ptr[tile];
-        f_cnt = p.tile_ptr[tile + 1] - f_base;
-        for (int i = t; i < min(f_cnt, MINE_FL_CAP); i += 256) flist[i] = p.tile_ent[f_base + i];
-    }
+    int f_base, f_cnt;
+    mine_filter_load(p.tile_ptr, p.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, t, &f_base, &f_cnt);
     if (t < 64) { fmask[0][t] = 0ull; fmask[1][t] = 0ull; fmask[2][t] = 0ull; }
     if (t < 3) fany[t] = 0;
     if (HIST)
@@ -156,13 +133,7 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
         // this relation's listed triplets -> fmask[fb]; the buffer of the relation after it is cleared (last read two relations ago)
         if (t < 64) fmask[(it + 1) % 3][t] = 0ull;
         if (t == 64) fany[(it + 1) % 3] = 0;
-        for (int i = t; i < f_cnt; i += 256) {
-            const unsigned ent = i < MINE_FL_CAP ? flist[i] : p.tile_ent[f_base + i];
-            if ((int)(ent >> 12) == r) {
-                atomicOr(&fmask[fb][(ent >> 6) & 63u], 1ull << (ent & 63u));
-                fany[fb] = 1;
-            }
-        }
+        mine_filter_relation(flist, p.tile_ent, f_base, f_cnt, r, t, fmask[fb], &fany[fb]);
         float4 wnext = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool w_pre = resident && t < (kc >> 2) && r + 1 < r1;
         if (w_pre) wnext = mine_load_w(p, r + 1, 4 * t);          // flies under the MFMA chain
@@ -228,85 +199,13 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
             if (HIST) {
                 if (ok) atomicAdd(&hist_s[(key[i] >> shift) & bin_mask], 1u);
             } else {
-                const unsigned long long m = __ballot(ok);
-                if (m) {
-                    const int leader = __builtin_ctzll(m);
-                    unsigned long long base = 0ull;
-                    if (lane == leader) base = atomicAdd(p.counter, (unsigned long long)__popcll(m));
-                    const unsigned blo = (unsigned)__shfl((int)(unsigned)base, leader);
-                    const unsigned bhi = (unsigned)__shfl((int)(unsigned)(base >> 32), leader);
-                    base = ((unsigned long long)bhi << 32) | blo;
-                    if (ok) {
-                        const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-                        if (slot < (unsigned long long)p.capacity)
-                            p.out[slot] = make_int4(m0 + rl, r, col, __float_as_int(mine_key_logit(key[i])));
-                    }
-                }
+                mine_emit(ok, lane, m0 + rl, r, col, __float_as_int(mine_key_logit(key[i])), p.out, p.capacity, p.counter);
             }
         }
     }
     if (HIST) {
         __syncthreads();
-        for (int i = t; i <= (int)bin_mask; i += 256) {
-            const unsigned c = hist_s[i];
-            if (c) atomicAdd(p.hist + i, (unsigned long long)c);
-        }
-    }
-}
-
-// ---- the filter, re-bucketed per (subject tile, object tile): count, scan, fill ------------------------------------------
-struct MineFiltParams {
-    const int* lo;
-    const int* hi;
-    const int* ent;
-    int n_ent, n, num_rels, o_tiles;
-    int* cnt;                  // [tiles]: counts, then the fill cursors
-    int* ptr;                  // [tiles + 1]
-    unsigned* out;             // [n_ent]
-};
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_mine_filt(const MineFiltParams f) {
-    const long long keys = (long long)f.n * f.num_rels;
-    for (long long key = (long long)blockIdx.x * 256 + threadIdx.x; key < keys; key += (long long)gridDim.x * 256) {
-        const int lo = min(max(f.lo[key], 0), f.n_ent), hi = min(max(f.hi[key], lo), f.n_ent);
-        if (lo == hi) continue;
-        const int s = (int)(key / f.num_rels), r = (int)(key - (long long)s * f.num_rels);
-        for (int j = lo; j < hi; ++j) {
-            const int o = f.ent[j];
-            if (o < 0 || o >= f.n) continue;
-            const int tile = (s >> 6) * f.o_tiles + (o >> 6);
-            if (!FILL) atomicAdd(f.cnt + tile, 1);
-            else {
-                const int pos = atomicAdd(f.cnt + tile, 1);
-                if (pos >= 0 && pos < f.n_ent) f.out[pos] = ((unsigned)r << 12) | ((unsigned)(s & 63) << 6) | (unsigned)(o & 63);
-            }
-        }
-    }
-}
-
-// exclusive scan of the tile counts (one workgroup: a thread sums a contiguous slice, the slices are scanned in LDS)
-__global__ __launch_bounds__(1024) void k_mine_filt_scan(int* cnt, int* ptr, int tiles) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (tiles + 1023) / 1024;
-    const int i0 = min(t * per, tiles), i1 = min(i0 + per, tiles);
-    int s = 0;
-    for (int i = i0; i < i1; ++i) s += cnt[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        ptr[tiles] = run;
-    }
-    __syncthreads();
-    int run = part[t];
-    for (int i = i0; i < i1; ++i) {
-        const int v = cnt[i];
-        ptr[i] = run;
-        cnt[i] = run;          // the fill cursor
-        run += v;
+        mine_hist_flush(hist_s, p.hist, bin_mask, t);
     }
 }
 
@@ -314,13 +213,9 @@ __global__ __launch_bounds__(1024) void k_mine_filt_scan(int* cnt, int* ptr, int
 
 using namespace gv;
 
-static int64_t mine_align16(int64_t b) { return (b + 15) / 16 * 16; }
-
 extern "C" int64_t gv_mine_scores_workspace_bytes(int n, int num_rels, int n_filt_ent) {
     (void)num_rels;
-    if (n <= 0 || n_filt_ent < 0) return 0;
-    const int64_t tiles = (int64_t)((n + 63) / 64) * ((n + 63) / 64);
-    return mine_align16(tiles * 4) + mine_align16((tiles + 1) * 4) + mine_align16((int64_t)(n_filt_ent > 0 ? n_filt_ent : 1) * 4);
+    return mine_filter_workspace_bytes(n, n_filt_ent);
 }
 
 extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,
@@ -378,21 +273,8 @@ extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w
     p.out = (int4*)out; p.capacity = capacity;
     p.counter = (unsigned long long*)counter; p.hist = (unsigned long long*)hist;
 
-    if (filtered) {
-        char* ws = (char*)workspace;
-        MineFiltParams f{};
-        f.lo = filt_lo; f.hi = filt_hi; f.ent = filt_ent; f.n_ent = n_filt_ent; f.n = n; f.num_rels = num_rels; f.o_tiles = tiles_1d;
-        f.cnt = (int*)ws;
-        f.ptr = (int*)(ws + mine_align16((int64_t)tiles * 4));
-        f.out = (unsigned*)(ws + mine_align16((int64_t)tiles * 4) + mine_align16((int64_t)(tiles + 1) * 4));
-        if (fill_words(f.cnt, 0u, (size_t)tiles * 4, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
-        const long long keys = (long long)n * num_rels;
-        const unsigned fb = (unsigned)std::min<long long>((keys + 255) / 256, 65535);
-        hipLaunchKernelGGL(k_mine_filt<false>, dim3(fb), dim3(256), 0, st, f);
-        hipLaunchKernelGGL(k_mine_filt_scan, dim3(1), dim3(1024), 0, st, f.cnt, f.ptr, tiles);
-        hipLaunchKernelGGL(k_mine_filt<true>, dim3(fb), dim3(256), 0, st, f);
-        p.tile_ptr = f.ptr; p.tile_ent = f.out;
-    }
+    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &p.tile_ptr, &p.tile_ent))
+        return launch_status("gv_mine_scores(fill)");
     const int lds = (2 * 64 * (p.kc + 4) + 2 * (p.kc + 4)) * (int)sizeof(float);
     const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);
     dim3 grid(tiles_1d, tiles_1d, n_spans), block(256);

@@ -22,6 +22,7 @@
 // distance first, ties by lower id, NaN last; the distance matrix is never stored.
 #include "common.h"
 #include "k_topk.h"
+#include "k_transe.h"
 
 namespace gv {
 
@@ -346,12 +347,7 @@ __global__ __launch_bounds__(256) void k_transe_queries(const float* __restrict_
 }
 
 // ---- distances and the fused ranker --------------------------------------------------------------------
-constexpr int TE_TQ = 64, TE_TE = 64, TE_KC = 32;   // queries x entities per workgroup tile, columns per LDS stage
-
-__device__ __forceinline__ float te_pair_term(float acc, float a, float b, int p) {
-    const float d = a - b;
-    return p == 1 ? acc + fabsf(d) : fmaf(d, d, acc);
-}
+constexpr int TE_KC = 32;   // columns per LDS stage of a TE_TQ x TE_TE tile (k_transe.h, with te_pair_term)
 
 // acc[4][4] for queries q0 + 4 ty .. and entities e0 + 4 tx ..: the columns in order, one accumulator per pair
 __device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v, int dim, int p,

@@ -1,0 +1,277 @@
+// Whole-graph triplet mining for TransE (gv_transe_mine): every (s, r, o) of the normalised tables en (n, dim), rn (R, dim)
+//
+//   q[c] = en[s][c] + rn[r][c]          d[s, r, o] = ||q - en[o]||_p
+//
+// bit for bit gv_transe_distances on the query rows of gv_transe_queries (head = 0): one f32 add per subject element, then
+// te_pair_term (k_transe.h) over the columns in order into ONE accumulator per pair, sqrtf for p = 2.  L1 has no matrix form and the
+// L2 identity |q|^2 + |e|^2 - 2 q.e rounds differently, so this is vector-ALU work: 4 x 4 pairs a lane, as te_tile.
+//
+// Loop order: a workgroup owns one 64 x 64 (subject tile, object tile) pair and walks the RELATIONS over it.  Up to TM_KC_MAX columns
+// both tiles of en sit in LDS, column-major ([k][64 + 4]: a lane's four subjects and four objects are one 16-byte read each), staged
+// once; a relation then costs its dim-float row of rn, added to the subject side on the fly.  The two tiles fill most of the LDS, so
+// a compute unit holds ONE workgroup: it is 1 024 threads, four groups of 256 that each take every fourth relation of the span over
+// the same two tiles (four waves a SIMD: with one, every LDS read's latency showed -- 1.28 s a sweep against 0.26 s of arithmetic).
+// Wider tables are staged in TM_KC_MAX-column chunks per round of four relations; the 16 accumulators live across the chunks of a
+// relation, so the summation order is the same.
+//
+// Partial sums only grow (every term is >= 0 and f32 addition is monotone), so once every pair of a wave is past the distance the
+// pass still cares about -- the emission threshold, or the upper edge of the histogram prefix -- the wave leaves the column loop
+// (checked every TM_CHECK columns; NaN never compares greater, so NaN pairs run to the end and are dropped by their key).  What a
+// pair's key is compared with is unchanged, so the result is too.
+//
+// Candidates, keys (ordered_u32(-d): larger = nearer, 0 = NaN only), the filter and the EMIT / HIST epilogues are those of
+// gv_mine_scores (k_mine.h); a record's fourth word is the bits of d itself (never -0: the sums start at +0 and add |.| or squares).
+#include "common.h"
+#include "k_mine.h"
+#include "k_transe.h"
+
+namespace gv {
+
+constexpr int TM_LD = TE_TQ + 4;        // LDS row pitch of a column of 64 rows
+constexpr int TM_KC_MAX = 224;          // columns per staged chunk: (2 x 68 + 4) x 224 floats = 123 KiB (+ 22 KiB static) of the 160
+constexpr int TM_CHECK = 32;            // columns between two looks at the partial sums
+constexpr int TM_GROUPS = 4;            // groups of 256 threads on one tile pair, each walking its own relations
+constexpr int TM_THREADS = 256 * TM_GROUPS;
+
+struct TeMineParams {
+    const float* en;
+    const float* rn;
+    int n, dim, num_rels;
+    int kc, n_chunks;                  // chunk width and count; one chunk: the tiles stay in LDS
+    int rel_span;                      // relations per blockIdx.z
+    int exclude_self;
+    unsigned key_min;                  // EMIT
+    int prefix_bits, bin_bits;         // HIST
+    unsigned prefix;
+    const int* tile_ptr;               // [s_tiles * o_tiles + 1], NULL: no filter
+    const unsigned* tile_ent;
+    int4* out;
+    long long capacity;
+    unsigned long long* counter;
+    unsigned long long* hist;
+};
+
+// columns [k0, k0 + kn) of rows row0 .. row0 + 63 of en into dst [kn][TM_LD]; zeros past the table
+__device__ __forceinline__ void tm_stage(float* dst, const float* __restrict__ en, int row0, int n, int dim, int k0, int kn) {
+    for (int x = threadIdx.x; x < TE_TQ * kn; x += TM_THREADS) {
+        const int row = x / kn, k = x - row * kn;
+        dst[k * TM_LD + row] = row0 + row < n ? en[(size_t)(row0 + row) * dim + k0 + k] : 0.f;
+    }
+}
+
+template <int P, bool HIST>
+__global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p) {
+    extern __shared__ __attribute__((aligned(16))) float tm_smem[];
+    __shared__ unsigned long long fmask[TM_GROUPS][64];  // a group's relation: its listed objects per subject row
+    __shared__ int fany[TM_GROUPS];
+    __shared__ unsigned flist[MINE_FL_CAP];
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const int kc = p.kc;
+    float* As = tm_smem;                                 // [kc][TM_LD] subjects
+    float* Bs = As + kc * TM_LD;                         // [kc][TM_LD] objects
+    const int t = threadIdx.x, g = t >> 8, tl = t & 255, lane = t & 63, tx = tl & 15, ty = tl >> 4;
+    float* Rs = Bs + kc * TM_LD + g * kc;                // [TM_GROUPS][kc] each group's relation row
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const int r0 = blockIdx.z * p.rel_span, r1 = min(r0 + p.rel_span, p.num_rels);
+    const bool resident = p.n_chunks == 1;
+    const bool diag = p.exclude_self && m0 == n0;
+
+    // the largest distance this pass looks at: keys below kmin are dropped by the epilogue whatever their value
+    const unsigned kmin = HIST ? (p.prefix_bits ? p.prefix << (32 - p.prefix_bits) : 0u) : p.key_min;
+    float bound = INFINITY;                              // in the accumulator's unit: the distance, or (p = 2) its square, rounded up
+    if (kmin > 0x007fffffu) {                            // above the key of +inf
+        const float dmax = -mine_key_logit(kmin);
+        // p = 2: a few ulps above dmax^2, and never in the subnormals, so that acc > bound implies sqrtf(acc) > dmax
+        bound = P == 1 || dmax < 0.f ? dmax : fmaxf(dmax * dmax * 1.000001f, 1e-30f);
+    }
+
+    int f_base, f_cnt;
+    mine_filter_load(p.tile_ptr, p.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, tl, &f_base, &f_cnt);   // every group: the same words
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += TM_THREADS) hist_s[i] = 0u;
+    if (resident) {
+        tm_stage(As, p.en, m0, p.n, p.dim, 0, p.dim);
+        tm_stage(Bs, p.en, n0, p.n, p.dim, 0, p.dim);
+    }
+    const int shift = 32 - p.prefix_bits - p.bin_bits;
+    const unsigned bin_mask = (1u << p.bin_bits) - 1u;
+    const float* a_ptr = As + 4 * ty;
+    const float* b_ptr = Bs + 4 * tx;
+
+    // group g takes relations r0 + g, r0 + g + TM_GROUPS, ...; every group makes every round's barriers, with or without a relation
+    for (int rb = r0; rb < r1; rb += TM_GROUPS) {
+        const int r = rb + g;
+        const bool live = r < r1;
+        __syncthreads();                                 // the last round's reads of Rs and fmask are over
+        if (tl < 64) fmask[g][tl] = 0ull;
+        if (tl == 64) fany[g] = 0;
+        if (resident && live)
+            for (int k = tl; k < p.dim; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k];
+        __syncthreads();
+        if (live) mine_filter_relation(flist, p.tile_ent, f_base, f_cnt, r, tl, fmask[g], &fany[g]);
+
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        bool past = !live;                               // wave-uniform: every pair of the wave is beyond the bound
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc, kn = min(kc, p.dim - k0);
+            if (!resident) {
+                __syncthreads();
+                tm_stage(As, p.en, m0, p.n, p.dim, k0, kn);
+                tm_stage(Bs, p.en, n0, p.n, p.dim, k0, kn);
+                if (live)
+                    for (int k = tl; k < kn; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
+                __syncthreads();
+            }
+            for (int kb = 0; kb < kn && !past; kb += TM_CHECK) {
+                const int ke = min(kb + TM_CHECK, kn);
+#pragma unroll 4
+                for (int k = kb; k < ke; ++k) {
+                    const float4 qa = *reinterpret_cast<const float4*>(a_ptr + k * TM_LD);
+                    const float4 eb = *reinterpret_cast<const float4*>(b_ptr + k * TM_LD);
+                    const float rv = Rs[k];
+                    const float qv[4] = {qa.x + rv, qa.y + rv, qa.z + rv, qa.w + rv}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], P);
+                }
+                bool all_past = true;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) all_past = all_past && acc[a][b] > bound;
+                past = __all(all_past) != 0;
+            }
+        }
+        __syncthreads();                                 // fmask / fany of this round are complete
+
+        // ---- epilogue: lane (tx, ty) holds subjects 4 ty + a, objects 4 tx + b
+        unsigned key[4][4];
+        bool want = false;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (P == 2) acc[a][b] = sqrtf(acc[a][b]);
+                const int rl = 4 * ty + a, cl = 4 * tx + b;
+                unsigned k = mine_key(-acc[a][b]);
+                if (!live || m0 + rl >= p.n || n0 + cl >= p.n || (diag && rl == cl)) k = 0u;
+                if (HIST) {
+                    if (p.prefix_bits && (k >> (32 - p.prefix_bits)) != p.prefix) k = 0u;
+                } else {
+                    if (k < p.key_min) k = 0u;
+                }
+                key[a][b] = k;
+                want = want || k != 0u;
+            }
+        if (__ballot(want) == 0ull) continue;            // nearly every relation of nearly every tile in EMIT and refining HIST passes
+        const bool anyf = fany[g] != 0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int rl = 4 * ty + a, cl = 4 * tx + b;
+                bool ok = key[a][b] != 0u;
+                if (anyf && ok) ok = !((fmask[g][rl] >> cl) & 1ull);
+                if (HIST) {
+                    if (ok) atomicAdd(&hist_s[(key[a][b] >> shift) & bin_mask], 1u);
+                } else {
+                    mine_emit(ok, lane, m0 + rl, r, n0 + cl, __float_as_int(acc[a][b]), p.out, p.capacity, p.counter);
+                }
+            }
+    }
+    if (HIST) {
+        __syncthreads();
+        if (t < 256) mine_hist_flush(hist_s, p.hist, bin_mask, t);
+    }
+}
+
+template <int P, bool HIST>
+static int tm_launch(const TeMineParams& p, dim3 grid, int lds, int lds_max, hipStream_t st) {
+    static unsigned long long raised = 0;
+    if (!raise_dynamic_lds((const void*)k_transe_mine<P, HIST>, lds_max, raised, "gv_transe_mine")) return GV_ERR_SHAPE;
+    hipLaunchKernelGGL((k_transe_mine<P, HIST>), grid, dim3(TM_THREADS), lds, st, p);
+    return launch_status("gv_transe_mine");
+}
+
+}  // namespace gv
+
+using namespace gv;
+
+extern "C" int64_t gv_transe_mine_workspace_bytes(int n, int num_rels, int n_filt_ent) {
+    (void)num_rels;
+    return mine_filter_workspace_bytes(n, n_filt_ent);
+}
+
+extern "C" int gv_transe_mine(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* filt_lo,
+                              const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                              uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                              uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes, void* stream) {
+    GV_REQUIRE(n >= 0 && num_rels > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_transe_mine: n=%d num_rels=%d n_filt_ent=%d", n, num_rels,
+               n_filt_ent);
+    GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_mine: dim=%d (1..%d) p_norm=%d (1 or 2)", dim, GV_TRANSE_MAX_DIM, p_norm);
+    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "gv_transe_mine: unknown mode %d", mode);
+    GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "gv_transe_mine: n * num_rels = %lld reaches 2^31",
+               (long long)n * num_rels);
+    GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "gv_transe_mine: more than %d relations", 1 << MINE_REL_BITS);
+    GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "gv_transe_mine: n=%d: more than 2^31 tile pairs", n);
+    if (mode == GV_MINE_EMIT)
+        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "gv_transe_mine: capacity=%lld outside [0, 2^31)",
+                   (long long)capacity);
+    else
+        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
+                       (prefix >> prefix_bits) == 0u,
+                   GV_ERR_SHAPE, "gv_transe_mine: prefix_bits=%d prefix=%u bin_bits=%d out of range", prefix_bits, prefix, bin_bits);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_transe_mine: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (n == 0) return GV_OK;
+    GV_REQUIRE(en && rn, GV_ERR_NULL, "gv_transe_mine: NULL table");
+    if (mode == GV_MINE_EMIT) {
+        GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "gv_transe_mine: NULL output");
+        GV_REQUIRE(aligned16(out), GV_ERR_SHAPE, "gv_transe_mine: out is not 16-byte aligned");
+    } else {
+        GV_REQUIRE(hist, GV_ERR_NULL, "gv_transe_mine: NULL histogram");
+    }
+    const bool filtered = filt_lo != nullptr;
+    if (filtered) {
+        GV_REQUIRE(workspace, GV_ERR_NULL, "gv_transe_mine: a filter needs the workspace");
+        GV_REQUIRE(aligned16(workspace), GV_ERR_WORKSPACE, "gv_transe_mine: the workspace is not 16-byte aligned");
+        GV_REQUIRE(workspace_bytes >= gv_transe_mine_workspace_bytes(n, num_rels, n_filt_ent), GV_ERR_WORKSPACE,
+                   "gv_transe_mine: workspace %lld < %lld bytes", (long long)workspace_bytes,
+                   (long long)gv_transe_mine_workspace_bytes(n, num_rels, n_filt_ent));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles_1d = (n + 63) / 64;
+    const int tiles = tiles_1d * tiles_1d;
+
+    TeMineParams p{};
+    p.en = en; p.rn = rn; p.n = n; p.dim = dim; p.num_rels = num_rels;
+    p.kc = std::min(dim, TM_KC_MAX);
+    p.n_chunks = (dim + p.kc - 1) / p.kc;
+    // relation spans: about four workgroups per CU of the MI355X when the table has few tiles (the result does not depend on it)
+    long long spans = (4LL * 256 + tiles - 1) / tiles;
+    spans = std::max(1LL, std::min(spans, (long long)num_rels));
+    p.rel_span = (int)((num_rels + spans - 1) / spans);
+    const int n_spans = (num_rels + p.rel_span - 1) / p.rel_span;
+    p.exclude_self = exclude_self ? 1 : 0;
+    p.key_min = key_min; p.prefix_bits = prefix_bits; p.bin_bits = bin_bits; p.prefix = prefix;
+    p.out = (int4*)out; p.capacity = capacity;
+    p.counter = (unsigned long long*)counter; p.hist = (unsigned long long*)hist;
+
+    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &p.tile_ptr, &p.tile_ent))
+        return launch_status("gv_transe_mine(fill)");
+    const int lds = (2 * TM_LD + TM_GROUPS) * p.kc * (int)sizeof(float);
+    const int lds_max = (2 * TM_LD + TM_GROUPS) * TM_KC_MAX * (int)sizeof(float);
+    const dim3 grid(tiles_1d, tiles_1d, n_spans);
+    if (mode == GV_MINE_EMIT) {
+        if (fill_words(counter, 0u, 8, st) != hipSuccess) return launch_status("gv_transe_mine(fill)");
+        return p_norm == 1 ? tm_launch<1, false>(p, grid, lds, lds_max, st) : tm_launch<2, false>(p, grid, lds, lds_max, st);
+    }
+    if (fill_words(hist, 0u, (size_t)8 << bin_bits, st) != hipSuccess) return launch_status("gv_transe_mine(fill)");
+    return p_norm == 1 ? tm_launch<1, true>(p, grid, lds, lds_max, st) : tm_launch<2, true>(p, grid, lds, lds_max, st);
+}

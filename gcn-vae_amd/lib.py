@@ -127,6 +127,9 @@ SIGNATURES = {
     'gv_transe_topk': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     'gv_transe_rank_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     'gv_transe_topk_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'gv_transe_mine_workspace_bytes': (_L, [_I, _I, _I]),
+    'gv_transe_mine': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P,
+                            _P, _L, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -766,25 +766,126 @@ def mine_key(x):
     return (~u & 0xffffffff) if u & 0x80000000 else (u | 0x80000000)
 
 
-def mine_order(triplets, logits, num_nodes, num_rels):
+def mine_order(triplets, logits, num_nodes, num_rels, ascending=False):
     """Sort mined (triplets int64 (n, 3), logits (n,)) into the rule's total order: logit descending (-0 as +0), then (s, r, o)
-    ascending.  Any device."""
+    ascending.  ``ascending``: the values are distances, smallest first (gv_transe_mine's order).  Any device."""
     logits = logits.to(torch.float32) + 0.0
     lin = (triplets[:, 0] * num_rels + triplets[:, 1]) * max(num_nodes, 1) + triplets[:, 2]
     order = torch.argsort(lin, stable=True)
-    order = order[torch.argsort(logits[order], descending=True, stable=True)]
+    order = order[torch.argsort(logits[order], descending=not ascending, stable=True)]
     return triplets[order], logits[order]
 
 
-def mine_select(triplets, logits, k, max_results, num_nodes, num_rels):
+def mine_select(triplets, logits, k, max_results, num_nodes, num_rels, ascending=False):
     """The top-K end of every mining route: from candidates that include everything at or above the K-th logit, the first K in
-    the total order and the number at or above the K-th logit's exact value (more than ``max_results`` of those: MineOverflow)."""
-    triplets, logits = mine_order(triplets, logits, num_nodes, num_rels)
+    the total order and the number at or above the K-th logit's exact value (more than ``max_results`` of those: MineOverflow).
+    ``ascending``: distances, the K smallest and the number at or below the K-th."""
+    triplets, logits = mine_order(triplets, logits, num_nodes, num_rels, ascending)
     n = logits.numel()
-    count = n if n <= k else int((logits >= logits[k - 1]).sum())
+    count = n if n <= k else int((logits <= logits[k - 1]).sum() if ascending else (logits >= logits[k - 1]).sum())
     if count > max_results:
-        raise MineOverflow(count, max_results, f'top-{k}: the candidates at or above the K-th logit')
+        what = 'at or below the K-th distance' if ascending else 'at or above the K-th logit'
+        raise MineOverflow(count, max_results, f'top-{k}: the candidates {what}')
     return triplets[:k], logits[:k], count
+
+
+def _mine_args(k, threshold, max_results):
+    """(k, threshold, max_results) of a mining call, checked: exactly one of k >= 1 and a threshold that is not NaN."""
+    if (k is None) == (threshold is None):
+        raise ValueError('give exactly one of k and threshold')
+    max_results = int(max_results)
+    if not 1 <= max_results < 2 ** 31:
+        raise ValueError(f'max_results must lie in [1, 2**31), got {max_results}')
+    if k is not None:
+        k = int(k)
+        if k < 1:
+            raise ValueError(f'k must be >= 1, got {k}')
+    else:
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError('threshold is NaN')
+    return k, threshold, max_results
+
+
+def _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev, workspace_bytes):
+    """The filter of a mining call as the kernels take it: (lo32, hi32, ent32, n_ent, workspace, workspace bytes), all None / 0
+    without one.  ``workspace_bytes``: the entry point that sizes the re-bucketed filter."""
+    if filt_lo is None:
+        return None, None, None, 0, None, 0
+    filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
+    if filt_lo.numel() != n * num_rels or filt_hi.numel() != n * num_rels:
+        raise ValueError('one filter range (filt_lo, filt_hi) per key s * R + r')
+    n_ent = filt_ent.numel()
+    if n_ent >= 2 ** 31:
+        raise ValueError('filt_ent: more than 2**31 - 1 entries')
+    if int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any()):
+        raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
+    if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= n):
+        raise ValueError(f'filtered entity ids must lie in [0, {n})')
+    i32 = dict(device=dev, dtype=torch.int32)
+    lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
+    ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
+    ws_bytes = int(workspace_bytes(n, num_rels, n_ent))
+    return lo32, hi32, ent32, n_ent, torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _mine_drive(launch, dev, n, num_rels, k, threshold, threshold_key, max_results, ascending, name):
+    """What both miners do around their kernel: a threshold run is one emission at ``threshold_key``; top-K walks the histogram
+    levels (12 + 10 + 10 key bits) to the key of the K-th best candidate, then emits once.  ``launch(mode, key_min, prefix_bits,
+    prefix, bin_bits, out, capacity, words)`` is one pass of the kernel, ``words`` its counter / histogram; a record's fourth
+    word is the value (the logit, or the distance when ``ascending``).  Returns ``(triplets, values, info)`` in the rule's order."""
+    edge_of = 'at or below the K-th distance' if ascending else 'at or above the K-th logit'
+    info = {'count': 0, 'passes': 0}
+    words = torch.zeros(1 << MINE_LEVELS[0][1], dtype=torch.int64, device=dev)      # the counter / the histogram
+    empty = (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev))
+
+    def run(mode, key_min=0, prefix_bits=0, prefix=0, bin_bits=1, out=None, capacity=0):
+        launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words)
+        info['passes'] += 1
+
+    def emit(key_min, capacity):
+        out = torch.empty(max(capacity, 1), 4, dtype=torch.int32, device=dev)
+        run(0, key_min=key_min, out=out, capacity=capacity)
+        count = int(words[0])
+        rec = out[:min(count, capacity)]
+        return count, rec[:, :3].long(), rec[:, 3].contiguous().view(torch.float32)
+
+    if k is None:
+        count, trip, logits = emit(threshold_key, min(max_results, n * num_rels * n))
+        info['count'] = count
+        if count > max_results:
+            raise MineOverflow(count, max_results, f'threshold {threshold}')
+        return mine_order(trip, logits, n, num_rels, ascending) + (info,)
+
+    above, key_min = 0, None          # candidates strictly above the range being narrowed; the emission threshold once known
+    prefix = 0
+    for prefix_bits, bin_bits in MINE_LEVELS:
+        run(1, prefix_bits=prefix_bits, prefix=prefix, bin_bits=bin_bits)
+        hist = words[:1 << bin_bits].cpu().numpy()
+        total = int(hist.sum())
+        if prefix_bits == 0 and total <= k:           # fewer candidates than asked for: all of them
+            if total > max_results:
+                raise MineOverflow(total, max_results, f'top-{k}: all candidates')
+            if total == 0:
+                return empty + (info,)
+            key_min, edge = 1, total
+            break
+        tail = hist[::-1].cumsum()[::-1]              # tail[b] = candidates of this range in bins >= b
+        b = int((tail >= k - above).nonzero()[0].max())
+        prefix = (prefix << bin_bits) | b
+        above += int(tail[b]) - int(hist[b])
+        edge = above + int(hist[b])                   # what an emission at this bin's lower edge returns
+        shift = 32 - prefix_bits - bin_bits
+        if edge <= max_results or shift == 0:
+            key_min = prefix << shift
+            break
+    if edge > max_results:            # one exact value holds more candidates than may be returned
+        raise MineOverflow(edge, max_results, f'top-{k}: the candidates {edge_of}')
+    count, trip, logits = emit(key_min, edge)
+    if count != edge:
+        raise RuntimeError(f'{name}: the emission pass found {count} candidates where the histograms counted {edge}')
+    trip, logits, info['count'] = mine_select(trip, logits, k, max_results, n, num_rels, ascending)
+    return trip, logits, info
 
 
 def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
@@ -810,17 +911,7 @@ def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt
         raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
     if n * num_rels >= 2 ** 31:
         raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
-    max_results = int(max_results)
-    if not 1 <= max_results < 2 ** 31:
-        raise ValueError(f'max_results must lie in [1, 2**31), got {max_results}')
-    if k is not None:
-        k = int(k)
-        if k < 1:
-            raise ValueError(f'k must be >= 1, got {k}')
-    else:
-        threshold = float(threshold)
-        if threshold != threshold:
-            raise ValueError('threshold is NaN')
+    k, threshold, max_results = _mine_args(k, threshold, max_results)
     given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
     if any(given) and not all(given):
         raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
@@ -829,82 +920,22 @@ def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt
     dev = emb.device
     if w.device != dev:
         raise ValueError(f'w must be on the device of emb ({dev})')
-    empty = (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev))
     if n == 0:
-        return empty + ({'count': 0, 'passes': 0},)
-    lo32 = hi32 = ent32 = ws = None
-    n_ent, ws_bytes = 0, 0
-    if all(given):
-        filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
-        if filt_lo.numel() != n * num_rels or filt_hi.numel() != n * num_rels:
-            raise ValueError('one filter range (filt_lo, filt_hi) per key s * R + r')
-        n_ent = filt_ent.numel()
-        if n_ent >= 2 ** 31:
-            raise ValueError('filt_ent: more than 2**31 - 1 entries')
-        if int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any()):
-            raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
-        if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= n):
-            raise ValueError(f'filtered entity ids must lie in [0, {n})')
-        i32 = dict(device=dev, dtype=torch.int32)
-        lo32, hi32 = filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous()
-        ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
-        ws_bytes = int(lib.load().gv_mine_scores_workspace_bytes(n, num_rels, n_ent))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        return (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                {'count': 0, 'passes': 0})
+    lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
+                                                               lib.load().gv_mine_scores_workspace_bytes)
     if bias is not None:
         bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
         bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
-    info = {'count': 0, 'passes': 0}
-    words = torch.zeros(1 << MINE_LEVELS[0][1], dtype=torch.int64, device=dev)      # the counter / the histogram
 
-    def run(mode, key_min=0, prefix_bits=0, prefix=0, bin_bits=1, out=None, capacity=0):
+    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
         lib.call('gv_mine_scores', ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
                  1 if exclude_self else 0, mode, key_min, prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words),
                  ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
-        info['passes'] += 1
 
-    def emit(key_min, capacity):
-        out = torch.empty(max(capacity, 1), 4, dtype=torch.int32, device=dev)
-        run(0, key_min=key_min, out=out, capacity=capacity)
-        count = int(words[0])
-        rec = out[:min(count, capacity)]
-        return count, rec[:, :3].long(), rec[:, 3].contiguous().view(torch.float32)
-
-    if k is None:
-        count, trip, logits = emit(mine_key(threshold), min(max_results, n * num_rels * n))
-        info['count'] = count
-        if count > max_results:
-            raise MineOverflow(count, max_results, f'threshold {threshold}')
-        return mine_order(trip, logits, n, num_rels) + (info,)
-
-    above, key_min = 0, None          # candidates strictly above the range being narrowed; the emission threshold once known
-    prefix = 0
-    for prefix_bits, bin_bits in MINE_LEVELS:
-        run(1, prefix_bits=prefix_bits, prefix=prefix, bin_bits=bin_bits)
-        hist = words[:1 << bin_bits].cpu().numpy()
-        total = int(hist.sum())
-        if prefix_bits == 0 and total <= k:           # fewer candidates than asked for: all of them
-            if total > max_results:
-                raise MineOverflow(total, max_results, f'top-{k}: all candidates')
-            if total == 0:
-                return empty + (info,)
-            key_min, edge = 1, total
-            break
-        tail = hist[::-1].cumsum()[::-1]              # tail[b] = candidates of this range in bins >= b
-        b = int((tail >= k - above).nonzero()[0].max())
-        prefix = (prefix << bin_bits) | b
-        above += int(tail[b]) - int(hist[b])
-        edge = above + int(hist[b])                   # what an emission at this bin's lower edge returns
-        shift = 32 - prefix_bits - bin_bits
-        if edge <= max_results or shift == 0:
-            key_min = prefix << shift
-            break
-    if edge > max_results:            # one exact logit value holds more candidates than may be returned
-        raise MineOverflow(edge, max_results, f'top-{k}: the candidates at or above the K-th logit')
-    count, trip, logits = emit(key_min, edge)
-    if count != edge:
-        raise RuntimeError(f'gv_mine_scores: the emission pass found {count} candidates where the histograms counted {edge}')
-    trip, logits, info['count'] = mine_select(trip, logits, k, max_results, n, num_rels)
-    return trip, logits, info
+    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
+                       'gv_mine_scores')
 
 
 def pick_split_k(m_out, n_out, k):
@@ -3174,3 +3205,48 @@ def transe_topk_constrained(q, en, k, p_norm, cand, cand_set, filt_lo=None, filt
     lib.call('gv_transe_topk_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
              ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(dist), ptr(ws), lib.stream())
     return ids, dist
+
+
+def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                max_results=MINE_MAX_RESULTS):
+    """Mine ALL triplets of a TransE model: ``d[s, r, o] = ||(en[s] + rn[r]) - en[o]||_p`` over every (s, r, o), bit for bit
+    ``transe_distances`` on the tail queries ``transe_queries`` makes of (s, r); ``en`` / ``rn`` are the normalised tables
+    (``transe_queries(table, norm_flag=...)``).  Candidates: every triplet, less the filter's (key ``s * R + r`` ->
+    ``filt_ent[filt_lo[key]:filt_hi[key]]``), less s == o when ``exclude_self``, less NaN distances (+inf is one) -- without storing
+    a distance (gv_transe_mine: a workgroup keeps a subject and an object tile of ``en`` in LDS and walks the relations).
+    ``threshold=t``: every candidate with d <= t (a negative t: none); ``k=K``: the K nearest.  Order: distance ascending, then
+    (s, r, o).  Returns ``(triplets int64 (n, 3), distances float32 (n,), info)``; ``info['count']``, ``info['passes']`` and
+    ``MineOverflow`` as in ``mine_scores``, with "at or below the distance" for "at or above the logit"."""
+    k, threshold, max_results = _mine_args(k, threshold, max_results)
+    for name, t in (('en', en), ('rn', rn)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
+    if en.shape[1] != rn.shape[1]:
+        raise ValueError('en / rn width mismatch')
+    p_norm = _p_norm(p_norm)
+    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
+    if num_rels < 1:
+        raise ValueError('need at least one relation')
+    if n * num_rels >= 2 ** 31:
+        raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    dev = en.device
+    if rn.device != dev:
+        raise ValueError(f'rn must be on the device of en ({dev})')
+    if n == 0:
+        return (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                {'count': 0, 'passes': 0})
+    lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
+                                                               lib.load().gv_transe_mine_workspace_bytes)
+
+    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
+        lib.call('gv_transe_mine', ptr(en), ptr(rn), n, num_rels, dim, p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+                 1 if exclude_self else 0, mode, key_min, prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words),
+                 ptr(ws), ws_bytes, lib.stream())
+
+    # d <= t is key(-d) >= key(-t); t = -0 keys as +0, the key of every zero distance
+    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(-threshold), max_results, True,
+                       'gv_transe_mine')

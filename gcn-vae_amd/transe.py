@@ -38,6 +38,12 @@ answers left out when a ``FilterIndex`` is given -- the same queries, table and 
 matrix: distance ascending, ties by lower id, NaN last.  ``--predict-topk K --predict-out FILE`` writes both directions of the
 test split (filter: train + valid + test) in train.py's prediction TSV layout, the distance in place of the logit.
 
+Completion: ``mine_triplets`` selects among ALL N x R x N triplets the K nearest new ones, or all within a distance -- the
+distances of ``predict_topk(direction='o')``, the reference's 'normal' mode (h + r) - t -- from ``ops.transe_mine``
+(gv_transe_mine: subject and object tiles of the normalised table stay in LDS while the relations are walked over them).
+``mine_from_distances`` states the rule on a materialised (R, N, N) tensor; ``mine_triplets_unfused`` is the per-relation
+cross-check.  ``--complete-topk K`` / ``--complete-threshold D`` write them to ``--complete-out`` in train.py's layout.
+
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
 """
@@ -50,7 +56,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ranking import FilterIndex, TypeConstraint, _listed_mask, rank_from_scores_constrained, sort_and_rank, topk_from_scores
+from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, rank_from_scores_constrained,
+                      sort_and_rank, topk_from_scores)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -584,6 +591,143 @@ def _write_rows(f, direction, a, r, ids, values):
 
 
 # ------------------------------------------------------------------------------------------------
+# completion: the whole graph's nearest new triplets
+# ------------------------------------------------------------------------------------------------
+def mine_from_distances(dist, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                        max_results=ops.MINE_MAX_RESULTS):
+    """The mining rule of ``ops.transe_mine`` on a materialised tensor ``dist[r, s, o]`` (R, N, N), in plain torch (any device,
+    CPU included): the counterpart of ``ranking.mine_from_scores``.  Candidates: every (s, r, o), less
+    ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r), less s == o when ``exclude_self``, less NaN
+    distances (+inf is a candidate).  Order, a strict total one: distance ascending, then (s, r, o) ascending.  ``threshold=t``
+    selects every candidate with d <= t, ``k=K`` the first K (fewer if fewer exist).  Returns ``(triplets int64 (n, 3), distances
+    float32 (n,), info)`` in that order; ``info['count']`` is the number of candidates at or below the threshold (top-K: at or
+    below the K-th distance's exact value; all, when fewer than K exist).  More than ``max_results`` of those raise
+    ``MineOverflow`` carrying the count: nothing is truncated silently."""
+    _mine_args(k, threshold, max_results)
+    num_rels, n = dist.shape[0], dist.shape[1]
+    val = dist.to(torch.float32) + 0.0
+    cand = ~torch.isnan(val)
+    if exclude_self:
+        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
+    if filt_lo is not None and n:
+        listed = _listed_mask(filt_lo, filt_hi, filt_ent, n * num_rels, n, val.device)      # rows: key s * R + r
+        cand &= ~listed.view(n, num_rels, n).permute(1, 0, 2)
+    info = {'passes': 0}
+    if k is not None:
+        vals = val[cand]
+        if vals.numel() > int(k):
+            cand &= val <= torch.topk(vals, int(k), largest=False).values[-1]
+    else:
+        cand &= val <= float(threshold)
+    r, s, o = torch.nonzero(cand, as_tuple=True)
+    trip, d = torch.stack([s, r, o], 1), val[cand]
+    if k is not None:
+        trip, d, info['count'] = ops.mine_select(trip, d, int(k), int(max_results), n, num_rels, ascending=True)
+        return trip, d, info
+    info['count'] = int(d.numel())
+    if info['count'] > int(max_results):
+        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
+    return ops.mine_order(trip, d, n, num_rels, ascending=True) + (info,)
+
+
+def mine_triplets(model_or_tables, *, k=None, threshold=None, filter_index=None, exclude_self=True,
+                  max_results=ops.MINE_MAX_RESULTS):
+    """Knowledge-graph completion: among ALL triplets (s, r, o), at the distance ``||n(E_s) + n(R_r) - n(E_o)||_p`` of
+    ``predict_topk(direction='o')``, the ``k`` nearest ones or every one with distance <= ``threshold``; with a ``FilterIndex`` the
+    known triplets are left out (new facts only).  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``.  One
+    fused sweep per pass (ops.transe_mine); returns ``(triplets int64 (n, 3), distances float32 (n,), info)`` in the order of
+    ``mine_from_distances``, and raises ``MineOverflow`` rather than truncating."""
+    _mine_args(k, threshold, max_results)
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+        rel = rel.to(ent.device)
+        lo, hi, f_ent = _mine_filter(filter_index, ent.shape[0], rel.shape[0], ent.device)
+        if ent.shape[0] == 0:
+            en, rn = ent.contiguous(), rel.contiguous()
+        else:
+            en = ops.transe_queries(ent.contiguous(), norm_flag=norm_flag)             # the normalised tables, once
+            rn = ops.transe_queries(rel.contiguous(), norm_flag=norm_flag)
+        return ops.transe_mine(en, rn, p_norm, k=k, threshold=threshold, filt_lo=lo, filt_hi=hi, filt_ent=f_ent,
+                               exclude_self=exclude_self, max_results=max_results)
+
+
+def mine_triplets_unfused(model_or_tables, *, k=None, threshold=None, filter_index=None, exclude_self=True,
+                          max_results=ops.MINE_MAX_RESULTS):
+    """``mine_triplets`` from materialised distances, one relation at a time (``ops.transe_queries`` + ``ops.transe_distances`` +
+    torch selection, a running K-th distance pruning the pool): the in-repo cross-check and the bench's comparator, never a
+    fallback."""
+    _mine_args(k, threshold, max_results)
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+        ent, rel = ent.contiguous(), rel.to(ent.device).contiguous()
+        n, num_rels = ent.shape[0], rel.shape[0]
+        dev = ent.device
+        lo, hi, f_ent = _mine_filter(filter_index, n, num_rels, dev)
+        k = None if k is None else int(k)
+        ceil = None if k is not None else float(threshold)
+        pool_t, pool_v, held = [], [], 0
+        diag = torch.eye(n, dtype=torch.bool, device=dev) if exclude_self else None
+        subjects = torch.arange(n, device=dev)
+        en = ops.transe_queries(ent, norm_flag=norm_flag) if n else ent
+
+        def prune():
+            nonlocal pool_t, pool_v, held, ceil
+            t, v = torch.cat(pool_t), torch.cat(pool_v)
+            if v.numel() > k:
+                ceil = float(torch.topk(v, k, largest=False).values[-1])
+                keep = v <= ceil
+                t, v = t[keep], v[keep]
+            pool_t, pool_v, held = [t], [v], v.numel()
+
+        for r in range(num_rels if n else 0):
+            q = ops.transe_queries(ent, rel, subjects, torch.full_like(subjects, r), head=False, norm_flag=norm_flag)
+            val = ops.transe_distances(q, en, p_norm)
+            cand = ~torch.isnan(val)
+            if diag is not None:
+                cand &= ~diag
+            if lo is not None:
+                cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], f_ent, n, n, dev)
+            if ceil is not None:
+                cand &= val <= ceil
+            if k is not None and ceil is None:            # no bound yet: this relation's own K-th distance
+                vals = val[cand]
+                if vals.numel() > k:
+                    cand &= val <= torch.topk(vals, k, largest=False).values[-1]
+            s, o = torch.nonzero(cand, as_tuple=True)
+            pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
+            pool_v.append(val[cand])
+            held += s.numel()
+            if k is not None and held > max(4 * k, 1 << 20):
+                prune()
+        info = {'passes': num_rels}
+        trip = torch.cat(pool_t) if pool_t else torch.zeros(0, 3, dtype=torch.int64, device=dev)
+        d = torch.cat(pool_v) if pool_v else torch.zeros(0, dtype=torch.float32, device=dev)
+        if k is not None:
+            trip, d, info['count'] = ops.mine_select(trip, d, int(k), int(max_results), n, num_rels, ascending=True)
+            return trip, d, info
+        info['count'] = int(d.numel())
+        if info['count'] > int(max_results):
+            raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
+        return ops.mine_order(trip, d, n, num_rels, ascending=True) + (info,)
+
+
+def write_completions(path, model_or_tables, filter_index, k=None, threshold=None):
+    """The whole graph's nearest new triplets (``mine_triplets``: the ``k`` nearest, cut at distance ``threshold`` when both are
+    given; the known triplets and s == o left out) as TSV in train.py's completion layout: ``subject  relation  object  rank
+    distance``.  Returns the number of lines written."""
+    if k is not None:
+        trip, dist, _ = mine_triplets(model_or_tables, k=k, filter_index=filter_index)
+        if threshold is not None:
+            keep = dist <= float(threshold)
+            trip, dist = trip[keep], dist[keep]
+    else:
+        trip, dist, _ = mine_triplets(model_or_tables, threshold=threshold, filter_index=filter_index)
+    with open(path, 'w') as f:
+        f.writelines(f"{s}\t{r}\t{o}\t{i}\t{x:.9g}\n" for i, ((s, r, o), x) in enumerate(zip(trip.tolist(), dist.tolist())))
+    return int(dist.numel())
+
+
+# ------------------------------------------------------------------------------------------------
 # CLI (baselines/transe/main.py's hyperparameters as defaults)
 # ------------------------------------------------------------------------------------------------
 def build_parser():
@@ -619,6 +763,13 @@ def build_parser():
                         'triplet (train + valid + test triplets filtered out) to --predict-out')
     p.add_argument('--predict-out', type=str, default='transe_predictions.tsv',
                    help='TSV written by --predict-topk: direction, query entity, relation, position, entity, distance')
+    p.add_argument('--complete-topk', type=int, default=None,
+                   help='after the final evaluation write the K nearest new triplets among ALL entities x relations x entities '
+                        '(train + valid + test triplets and s == o left out) to --complete-out')
+    p.add_argument('--complete-threshold', type=float, default=None,
+                   help='as --complete-topk, every new triplet within distance D; with both, the K nearest cut at D')
+    p.add_argument('--complete-out', type=str, default='transe_completions.tsv',
+                   help='TSV written by --complete-topk / --complete-threshold: subject, relation, object, rank, distance')
     return p
 
 
@@ -636,6 +787,12 @@ def check_args(args):
     k = getattr(args, 'predict_topk', None)
     if k is not None and not 1 <= k <= ops.TOPK_MAX:
         raise ValueError(f'--predict-topk must lie in [1, {ops.TOPK_MAX}], got {k}')
+    ck = getattr(args, 'complete_topk', None)
+    if ck is not None and ck < 1:
+        raise ValueError(f'--complete-topk must be >= 1, got {ck}')
+    cd = getattr(args, 'complete_threshold', None)
+    if cd is not None and cd != cd:
+        raise ValueError('--complete-threshold is NaN')
     if getattr(args, 'type_constrain', False) and not getattr(args, 'filtered_eval', False):
         raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, filtered_constrained')
 
@@ -681,6 +838,10 @@ def main(args):
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
         n_lines = write_predictions(args.predict_out, model, data.test, args.predict_topk, known, types)
         print(f'wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to {args.predict_out}')
+    if args.complete_topk is not None or args.complete_threshold is not None:
+        known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        n_lines = write_completions(args.complete_out, model, known, args.complete_topk, args.complete_threshold)
+        print(f'wrote {n_lines} completions (nearest new triplets of the whole graph, known triplets filtered) to {args.complete_out}')
     return out
 
 

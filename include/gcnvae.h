@@ -680,6 +680,23 @@ int gv_transe_topk_constrained(const float* q, int64_t m, const float* en, int v
                                int n_sets, const int32_t* cand_set, int k, int64_t* out_ids, float* out_dist, void* workspace,
                                void* stream);
 
+/* Whole-graph triplet mining for TransE (csrc/k_transe_mine.hip): every (s, r, o) of the dense tables en (n, dim) and rn (num_rels,
+ * dim), both as gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
+ *   q[c] = en[s][c] + rn[r][c]      d[s, r, o] = ||q - en[o]||_p
+ * bit for bit gv_transe_distances on the row gv_transe_queries (head = 0) makes of (s, r) -- the reference's 'normal' mode
+ * (h + r) - t; the head-batch form rounds differently and is not mined.  Candidates: all (s, r, o), less the triplets of the filter
+ * (key s * num_rels + r, exactly as gv_mine_scores; all three NULL: no filter), less s == o when exclude_self, less NaN distances
+ * (+inf is a candidate).  A candidate's key is ordered_u32(-d), the map of gv_transe_topk: a larger key is a nearer triplet, key 0 is
+ * NaN only.  The modes, their arguments and the workspace are those of gv_mine_scores; a GV_MINE_EMIT record is (s, r, o, bits of d),
+ * d never -0.  1 <= dim <= GV_TRANSE_MAX_DIM, p_norm 1 or 2, n * num_rels < 2^31, num_rels <= 2^19, 1 <= bin_bits <= 12, out and
+ * workspace 16-byte aligned; everything is checked on the host before any launch, and n == 0 launches nothing.  Integer atomics on
+ * the counter and the histograms only; the result does not depend on the launch geometry. */
+int64_t gv_transe_mine_workspace_bytes(int n, int num_rels, int n_filt_ent);
+int gv_transe_mine(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* filt_lo,
+                   const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode, uint32_t key_min,
+                   int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.

@@ -7,11 +7,18 @@ process under a time limit and stops the bench at its first failure.
 
     python tools/transe_bench.py [--steps 200] [--warmup 20] [--limit 600]
     python tools/transe_bench.py --topk [--out profiles/transe_topk/bench.json]
+    python tools/transe_bench.py --mine [--out profiles/transe_mine/bench.json]
 
 --topk runs the link-prediction leg alone: both directions of the test split (40 932 queries), filter = train + valid + test,
 L1 and L2, k = 10 and 100; per configuration predict_topk (fused), predict_topk_unfused (materialised distances + sort) and
 rank_transe on the same queries (the bare distance sweep with a counting epilogue).  Each is warmed up once and timed over
 --topk-repeats synchronised runs; the median and the minimum are reported, in ms.
+
+--mine runs the completion leg alone: the 100 000 nearest new triplets of ALL 14 541 x 237 x 14 541, train + valid + test
+filtered, dim 200 with L1 and L2 and dim 500 with L1 and L2: mine_triplets (fused) against mine_triplets_unfused (per-relation
+materialised distances + torch selection) in the same process, each warmed up once, medians of --mine-repeats (unfused: half as
+many) synchronised runs; the two results are asserted bit-equal.  At dim 200 predict_topk(k = 128) over all N x R queries is timed
+once as well -- it answers another question (the best 128 per query, not the global K).
 
 Step bytes: algorithmic, counting the gathered rows (3 per positive + 1 per negative), the occurrence gradients written and read,
 and the touched table rows read and written once, against 8 TB/s.  Scorer: |a - b| terms at ~1.5 VALU instructions each against
@@ -155,7 +162,68 @@ def case_topk(steps, warmup, repeats=5):
     return res
 
 
-CASES = {'step': case_step, 'eval': case_eval, 'torch_step': case_torch_step, 'torch_eval': case_torch_eval}
+def case_mine(steps, warmup, repeats=3):
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.data import load_data
+    from gcn_vae_amd.ranking import FilterIndex
+    data = load_data('FB15k-237-synthetic')
+    fi = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device='cuda')
+    n, num_rels, k = data.num_nodes, data.num_rels, 100000
+    res = dict(entities=n, relations=num_rels, k=k, repeats=repeats)
+
+    def say(*a):
+        print(*a, file=sys.stderr, flush=True)
+    for dim in (200, 500):
+        torch.manual_seed(0)
+        model = transe.TransE(n, num_rels, dim=dim, p_norm=1, norm_flag=True).cuda()
+        ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+        for p in (1, 2):
+            tables = (ent, rel, p, True)
+            got = transe.mine_triplets(tables, k=k, filter_index=fi)
+            want = transe.mine_triplets_unfused(tables, k=k, filter_index=fi)
+            assert got[0].shape == (k, 3) and torch.equal(got[0], want[0]) and got[2]['count'] == want[2]['count']
+            assert torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
+            fused = _repeat_ms(lambda: transe.mine_triplets(tables, k=k, filter_index=fi), repeats)
+            unfused = _repeat_ms(lambda: transe.mine_triplets_unfused(tables, k=k, filter_index=fi), max(1, repeats // 2))
+            # the distance sweep alone: n * R * n pairs of dim terms, two vector operations each, per pass
+            floor_ms = 2.0 * n * num_rels * n * dim / (VALU / 2) * 1e3
+            out = dict(fused=fused, unfused=unfused, unfused_over_fused=unfused['median_ms'] / fused['median_ms'],
+                       passes=got[2]['passes'], count=got[2]['count'], bit_equal=True, farthest=float(got[1][-1]),
+                       pass_floor_ms=floor_ms, floor_over_fused_pass=floor_ms * got[2]['passes'] / fused['median_ms'])
+            say(f'dim {dim} p {p}', json.dumps(out))
+            if dim == 200:
+                a = torch.arange(n, device='cuda').repeat_interleave(num_rels)
+                r = torch.arange(num_rels, device='cuda').repeat(n)
+                torch.cuda.synchronize()
+                t0 = time.time()
+                transe.predict_topk(tables, a, r, 128, direction='o', filter_index=fi)
+                torch.cuda.synchronize()
+                out['predict_topk_128_all_queries_ms'] = (time.time() - t0) * 1e3
+                say(f'dim {dim} p {p} predict_topk over {a.numel()} queries: {out["predict_topk_128_all_queries_ms"]:.0f} ms')
+            res[f'dim{dim}_p{p}'] = out
+    return res
+
+
+def case_mine_trace(steps, warmup):
+    """What ``rocprofv3 --kernel-trace --stats -- python tools/transe_bench.py --case mine_trace`` profiles: the fused top-K route
+    alone, dim 200, L1 then L2, a warm-up and two runs each."""
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.data import load_data
+    from gcn_vae_amd.ranking import FilterIndex
+    data = load_data('FB15k-237-synthetic')
+    fi = FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device='cuda')
+    torch.manual_seed(0)
+    model = transe.TransE(data.num_nodes, data.num_rels, dim=200, p_norm=1, norm_flag=True).cuda()
+    ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+    passes = {}
+    for p in (1, 2):
+        for _ in range(3):
+            passes[f'p{p}'] = transe.mine_triplets((ent, rel, p, True), k=100000, filter_index=fi)[2]['passes']
+    torch.cuda.synchronize()
+    return dict(runs_per_norm=3, passes=passes)
+
+
+CASES = {'mine_trace': case_mine_trace, 'step': case_step, 'eval': case_eval, 'torch_step': case_torch_step, 'torch_eval': case_torch_eval}
 
 
 def main():
@@ -166,17 +234,25 @@ def main():
     ap.add_argument('--case', default=None, help=argparse.SUPPRESS)
     ap.add_argument('--topk', action='store_true', help='run the link-prediction leg alone')
     ap.add_argument('--topk-repeats', type=int, default=5)
-    ap.add_argument('--out', default=None, help='with --topk: also write the JSON result to this file')
+    ap.add_argument('--mine', action='store_true', help='run the completion leg alone')
+    ap.add_argument('--mine-repeats', type=int, default=3)
+    ap.add_argument('--out', default=None, help='with --topk / --mine: also write the JSON result to this file')
     a = ap.parse_args()
+    if a.case == 'mine':
+        print('RESULT ' + json.dumps(case_mine(a.steps, a.warmup, a.mine_repeats)))
+        return
     if a.case == 'topk':
         print('RESULT ' + json.dumps(case_topk(a.steps, a.warmup, a.topk_repeats)))
         return
-    if a.topk:
-        r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__), '--case', 'topk',
-                            '--topk-repeats', str(a.topk_repeats)], capture_output=True, text=True, cwd=ROOT)
+    if a.topk or a.mine:
+        leg = ['--case', 'topk', '--topk-repeats', str(a.topk_repeats)] if a.topk else ['--case', 'mine', '--mine-repeats',
+                                                                                           str(a.mine_repeats)]
+        # the mining leg reports each configuration on stderr as it finishes
+        r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__)] + leg,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE if a.topk else None, text=True, cwd=ROOT)
         line = [x for x in r.stdout.splitlines() if x.startswith('RESULT ')]
         if r.returncode != 0 or not line:
-            print(json.dumps(dict(failed=r.returncode, tail=(r.stdout + r.stderr)[-1500:])), file=sys.stderr)
+            print(json.dumps(dict(failed=r.returncode, tail=(r.stdout + (r.stderr or ''))[-1500:])), file=sys.stderr)
             sys.exit(1)
         text = json.dumps(json.loads(line[0][7:]), indent=1)
         print(text)
@@ -189,7 +265,7 @@ def main():
         print('RESULT ' + json.dumps(CASES[a.case](a.steps, a.warmup)))
         return
     res = {}
-    for name in CASES:
+    for name in ('step', 'eval', 'torch_step', 'torch_eval'):
         r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__), '--case', name,
                             '--steps', str(a.steps), '--warmup', str(a.warmup)], capture_output=True, text=True, cwd=ROOT)
         line = [x for x in r.stdout.splitlines() if x.startswith('RESULT ')]
