@@ -325,6 +325,132 @@ __global__ __launch_bounds__(256) void k_transe_apply(float* __restrict__ ent, i
     }
 }
 
+// ---- ordered reduction + torch.optim rule ----------------------------------------------------------
+// k_transe_apply's work split, order of summation and loss block; the rule applied to the row's summed g is torch.optim's SGD,
+// Adagrad, Adadelta or Adam at torch's defaults, with the coupled L2 decay g += wd * p first.  Dense semantics: under Adadelta,
+// Adam or any wd != 0 every row of both tables is updated (an untouched row has g = 0: its moments still move it, its averages
+// decay, it shrinks); under SGD / Adagrad at wd == 0 an untouched row is the identity and is not written.  The step number t
+// (1-based, int64 on the device) is only read: something ahead of this launch advances it.  The scalars that depend on t are
+// formed in double from the double hyper-parameters, as torch forms them in Python floats, and rounded to float once.
+struct TeOptArgs {
+    float* ent;
+    float* rel;
+    float* s1_ent;              // Adagrad: sum; Adadelta: square_avg; Adam: exp_avg
+    float* s2_ent;              // Adadelta: acc_delta; Adam: exp_avg_sq
+    float* s1_rel;
+    float* s2_rel;
+    const float* g_ent;
+    const float* g_rel;
+    const int32_t* perm_e;
+    const int32_t* rowptr_e;
+    const int32_t* perm_r;
+    const int32_t* rowptr_r;
+    const int64_t* step_t;
+    const float* loss_part;
+    float* loss_out;
+    double* epoch_acc;
+    double lr, wd, lr_decay;
+    int n_ent, n_rel, dim, method, B, row_blocks;
+    float margin;
+};
+
+constexpr double TE_ADADELTA_RHO = 0.9, TE_ADADELTA_EPS = 1e-6, TE_ADAGRAD_EPS = 1e-10;
+constexpr double TE_ADAM_B1 = 0.9, TE_ADAM_B2 = 0.999, TE_ADAM_EPS = 1e-8;
+
+__global__ __launch_bounds__(256) void k_transe_apply_opt(const TeOptArgs a) {
+    const int lane = threadIdx.x & 63;
+    if ((int)blockIdx.x == a.row_blocks) {
+        if (threadIdx.x >= 64) return;
+        float s = 0.f;
+        for (int i = lane; i < a.B; i += 64) s += a.loss_part[i];
+        s = wave_sum(s) + a.margin;
+        if (lane == 0) {
+            a.loss_out[0] = s;
+            if (a.epoch_acc) a.epoch_acc[0] += (double)s;
+        }
+        return;
+    }
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    float *table, *s1, *s2;
+    const float* g;
+    const int32_t *perm, *rowptr;
+    int s;
+    if (w < a.n_ent) { table = a.ent; s1 = a.s1_ent; s2 = a.s2_ent; g = a.g_ent; perm = a.perm_e; rowptr = a.rowptr_e; s = w; }
+    else if (w < a.n_ent + a.n_rel) {
+        table = a.rel; s1 = a.s1_rel; s2 = a.s2_rel; g = a.g_rel; perm = a.perm_r; rowptr = a.rowptr_r; s = w - a.n_ent;
+    } else return;
+    const int method = a.method, dim = a.dim;
+    const bool decay = a.wd != 0.0;
+    const int lo = rowptr[s], hi = rowptr[s + 1];
+    if (lo == hi && !decay && (method == GV_TRANSE_OPT_SGD || method == GV_TRANSE_OPT_ADAGRAD)) return;
+    const float wd = (float)a.wd, lr = (float)a.lr;
+    // per-step scalars (wave-uniform): Adagrad's clr; Adam's lr / bc1 and sqrt(bc2)
+    float c0 = 0.f, c1 = 0.f;
+    if (method == GV_TRANSE_OPT_ADAGRAD) {
+        c0 = (float)(a.lr / (1.0 + (double)(a.step_t[0] - 1) * a.lr_decay));
+    } else if (method == GV_TRANSE_OPT_ADAM) {
+        const double t = (double)a.step_t[0];
+        c0 = (float)(a.lr / (1.0 - pow(TE_ADAM_B1, t)));
+        c1 = (float)sqrt(1.0 - pow(TE_ADAM_B2, t));
+    }
+    // every column's sum runs over the occurrences in perm order from 0, as k_transe_apply's does (the same bits); the row's
+    // columns are summed side by side and four occurrences are fetched at a time, so a long run waits for a quarter of its
+    // occurrences' two dependent loads (perm, then the gradient row) instead of for each one once per 64 columns
+    float acc[TE_C];
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) acc[c] = 0.f;
+    int i = lo;
+    for (; i + 4 <= hi; i += 4) {
+        const int32_t o0 = perm[i], o1 = perm[i + 1], o2 = perm[i + 2], o3 = perm[i + 3];
+        float x0[TE_C], x1[TE_C], x2[TE_C], x3[TE_C];
+        te_load(g + (int64_t)o0 * dim, dim, lane, x0);
+        te_load(g + (int64_t)o1 * dim, dim, lane, x1);
+        te_load(g + (int64_t)o2 * dim, dim, lane, x2);
+        te_load(g + (int64_t)o3 * dim, dim, lane, x3);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) acc[c] = (((acc[c] + x0[c]) + x1[c]) + x2[c]) + x3[c];
+    }
+    for (; i < hi; ++i) {
+        float x0[TE_C];
+        te_load(g + (int64_t)perm[i] * dim, dim, lane, x0);
+#pragma unroll
+        for (int c = 0; c < TE_C; ++c) acc[c] += x0[c];
+    }
+    const int64_t base = (int64_t)s * dim;
+#pragma unroll
+    for (int c = 0; c < TE_C; ++c) {
+        const int k = lane + c * WAVE;
+        if (k >= dim) continue;
+        float* q = table + base + k;
+        const float p = *q;
+        float gk = acc[c];
+        if (decay) gk = gk + wd * p;
+        if (method == GV_TRANSE_OPT_SGD) {
+            *q = p + (-lr) * gk;
+        } else if (method == GV_TRANSE_OPT_ADAGRAD) {
+            const float sum = s1[base + k] + gk * gk;
+            s1[base + k] = sum;
+            *q = p - c0 * gk / (sqrtf(sum) + (float)TE_ADAGRAD_EPS);
+        } else if (method == GV_TRANSE_OPT_ADADELTA) {
+            const float rho = (float)TE_ADADELTA_RHO, one_rho = (float)(1.0 - TE_ADADELTA_RHO), eps = (float)TE_ADADELTA_EPS;
+            const float sq = rho * s1[base + k] + one_rho * (gk * gk);
+            const float ad = s2[base + k];
+            const float d = sqrtf(ad + eps) / sqrtf(sq + eps) * gk;
+            s1[base + k] = sq;
+            s2[base + k] = rho * ad + one_rho * (d * d);
+            *q = p - lr * d;
+        } else {
+            const float w1 = (float)(1.0 - TE_ADAM_B1), b2 = (float)TE_ADAM_B2, w2 = (float)(1.0 - TE_ADAM_B2);
+            const float m0 = s1[base + k];
+            const float m = m0 + w1 * (gk - m0);
+            const float v = b2 * s2[base + k] + w2 * (gk * gk);
+            s1[base + k] = m;
+            s2[base + k] = v;
+            *q = p - c0 * m / (sqrtf(v) / c1 + (float)TE_ADAM_EPS);
+        }
+    }
+}
+
 // ---- queries and table normalisation ---------------------------------------------------------------
 // q[i] = n(ent[a[i]]) + n(rel[r[i]]) (tail queries) or n(ent[a[i]]) - n(rel[r[i]]) (head queries); with rel == NULL: q[i] = n(ent[i])
 __global__ __launch_bounds__(256) void k_transe_queries(const float* __restrict__ ent, const float* __restrict__ rel,
@@ -647,6 +773,32 @@ extern "C" int gv_transe_apply(float* ent, int n_ent, const float* g_ent, const 
     hipLaunchKernelGGL(k_transe_apply, dim3(row_blocks + 1), dim3(256), 0, GV_ST, ent, n_ent, g_ent, perm_e, rowptr_e, rel, n_rel,
                        g_rel, perm_r, rowptr_r, dim, lr, loss_part, batch, margin, loss_out, epoch_acc, row_blocks);
     return launch_status("gv_transe_apply");
+}
+
+extern "C" int gv_transe_apply_opt(float* ent, int n_ent, const float* g_ent, const int32_t* perm_e, const int32_t* rowptr_e,
+                                   float* rel, int n_rel, const float* g_rel, const int32_t* perm_r, const int32_t* rowptr_r, int dim,
+                                   int method, double lr, double weight_decay, double lr_decay, float* s1_ent, float* s2_ent,
+                                   float* s1_rel, float* s2_rel, const int64_t* step_t, const float* loss_part, int batch,
+                                   float margin, float* loss_out, double* epoch_acc, void* stream) {
+    GV_REQUIRE(n_ent > 0 && n_rel > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && batch > 0 && (int64_t)n_ent + n_rel < (1ll << 31) - 4,
+               GV_ERR_SHAPE, "gv_transe_apply_opt: n_ent=%d n_rel=%d dim=%d (1..%d) batch=%d", n_ent, n_rel, dim, GV_TRANSE_MAX_DIM, batch);
+    GV_REQUIRE(method >= GV_TRANSE_OPT_SGD && method <= GV_TRANSE_OPT_ADAM, GV_ERR_SHAPE,
+               "gv_transe_apply_opt: method=%d (0 sgd, 1 adagrad, 2 adadelta, 3 adam)", method);
+    GV_REQUIRE(lr >= 0.0 && weight_decay >= 0.0 && lr_decay >= 0.0, GV_ERR_SHAPE,
+               "gv_transe_apply_opt: lr=%g weight_decay=%g lr_decay=%g must all be >= 0", lr, weight_decay, lr_decay);
+    GV_REQUIRE(ent && g_ent && perm_e && rowptr_e && rel && g_rel && perm_r && rowptr_r && loss_part && loss_out, GV_ERR_NULL,
+               "gv_transe_apply_opt: NULL pointer");
+    GV_REQUIRE(method == GV_TRANSE_OPT_SGD || (s1_ent && s1_rel), GV_ERR_NULL, "gv_transe_apply_opt: method %d needs s1_ent and s1_rel",
+               method);
+    GV_REQUIRE(method < GV_TRANSE_OPT_ADADELTA || (s2_ent && s2_rel), GV_ERR_NULL,
+               "gv_transe_apply_opt: method %d needs s2_ent and s2_rel", method);
+    GV_REQUIRE((method != GV_TRANSE_OPT_ADAGRAD && method != GV_TRANSE_OPT_ADAM) || step_t, GV_ERR_NULL,
+               "gv_transe_apply_opt: method %d needs step_t", method);
+    const int row_blocks = (int)(((int64_t)n_ent + n_rel + 3) / 4);
+    TeOptArgs a{ent, rel, s1_ent, s2_ent, s1_rel, s2_rel, g_ent, g_rel, perm_e, rowptr_e, perm_r, rowptr_r, step_t, loss_part, loss_out,
+                epoch_acc, lr, weight_decay, lr_decay, n_ent, n_rel, dim, method, batch, row_blocks, margin};
+    hipLaunchKernelGGL(k_transe_apply_opt, dim3(row_blocks + 1), dim3(256), 0, GV_ST, a);
+    return launch_status("gv_transe_apply_opt");
 }
 
 extern "C" int gv_transe_queries(const float* ent, const float* rel, const int32_t* a, const int32_t* r, int64_t m, int dim,

@@ -120,6 +120,8 @@ SIGNATURES = {
     'gv_transe_sample': (_I, [_P, ctypes.c_uint32, _P, _L, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     'gv_transe_step': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     'gv_transe_apply': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _F, _P, _I, _F, _P, _P, _P]),
+    'gv_transe_apply_opt': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 _P, _P, _P, _P, _P, _P, _I, _F, _P, _P, _P]),
     'gv_transe_queries': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _P, _P]),
     'gv_transe_distances': (_I, [_P, _L, _P, _I, _I, _I, _P, _P]),
     'gv_transe_rank_filtered': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -3062,6 +3062,97 @@ def transe_apply(ent, rel, g_ent, g_rel, order, lr, loss_part, margin, loss_out,
              float(margin), ptr(loss_out), ptr(epoch_acc), lib.stream())
 
 
+TRANSE_OPT_METHODS = {'sgd': 0, 'adagrad': 1, 'adadelta': 2, 'adam': 3}      # = GV_TRANSE_OPT_* (include/gcnvae.h)
+
+
+class TransEOptState:
+    """What ``transe_apply_opt`` keeps between steps: two float32 arrays per table, shaped like the table (``ent`` / ``rel``:
+    pairs (s1, s2) -- Adagrad: s1 = sum; Adadelta: square_avg, acc_delta; Adam: exp_avg, exp_avg_sq; SGD: unused), and ``t``, the
+    number of steps taken, int64 [1] on the device."""
+
+    def __init__(self, n_ent, n_rel, dim, device):
+        self.ent = (torch.zeros(n_ent, dim, device=device), torch.zeros(n_ent, dim, device=device))
+        self.rel = (torch.zeros(n_rel, dim, device=device), torch.zeros(n_rel, dim, device=device))
+        self.t = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def tensors(self):
+        return (*self.ent, *self.rel, self.t)
+
+    def zero_(self):
+        for x in self.tensors():
+            x.zero_()
+        return self
+
+    def snapshot(self):
+        """Copies of the four arrays and the step number (device tensors): what ``restore`` puts back."""
+        return tuple(x.clone() for x in self.tensors())
+
+    def restore(self, snap):
+        """Put a ``snapshot`` back IN PLACE (every address stays what a captured step recorded)."""
+        for x, s in zip(self.tensors(), snap):
+            x.copy_(s)
+        return self
+
+
+def transe_apply_opt(ent, rel, g_ent, g_rel, order, method, lr, loss_part, margin, loss_out, epoch_acc=None, *, state,
+                     weight_decay=0.0, lr_decay=0.0):
+    """One optimiser step on both tables from the occurrence gradients, summed in order as ``transe_apply`` sums them
+    (gv_transe_apply_opt): ``method`` 'sgd' | 'adagrad' | 'adadelta' | 'adam' (case-insensitive) is the rule of torch.optim at
+    torch's defaults with the coupled ``weight_decay``; ``lr_decay`` is Adagrad's.  ``state`` (a ``TransEOptState``) is updated in
+    place: its step number ``t`` is advanced by one on the stream first (a captured replay advances it too), then one launch
+    reads it.  Under Adadelta, Adam or a non-zero weight_decay every row of both tables is updated (torch's dense semantics);
+    otherwise rows without occurrences are not written.  Writes loss_out / epoch_acc as ``transe_apply`` does."""
+    code = TRANSE_OPT_METHODS.get(method.lower()) if isinstance(method, str) else None
+    if code is None:
+        raise ValueError(f'method {method!r}: expected one of {sorted(TRANSE_OPT_METHODS)}')
+    lr, weight_decay, lr_decay = float(lr), float(weight_decay), float(lr_decay)
+    for name, x in (('lr', lr), ('weight_decay', weight_decay), ('lr_decay', lr_decay)):
+        if not x >= 0.0:
+            raise ValueError(f'{name} must be >= 0, got {x}')
+    if lr_decay != 0.0 and code != TRANSE_OPT_METHODS['adagrad']:
+        raise ValueError('lr_decay is Adagrad\'s: pass 0 with any other method')
+    if not isinstance(state, TransEOptState):
+        raise TypeError('state: a TransEOptState')
+    for name, pair, table in (('state.ent', state.ent, ent), ('state.rel', state.rel, rel)):
+        for i, x in enumerate(pair):
+            if tuple(x.shape) != tuple(table.shape):
+                raise ValueError(f'{name}[{i}]: shape {tuple(x.shape)}, the table {tuple(table.shape)}')
+    ent, rel = _table(ent, 'ent'), _table(rel, 'rel')
+    dim = ent.shape[1]
+    if rel.shape[1] != dim or ent.device != rel.device:
+        raise ValueError('ent / rel: same width and device')
+    pe, pr = order
+    g_ent, g_rel = _chk(g_ent, name='g_ent'), _chk(g_rel, name='g_rel')
+    if pe['n_seg'] != ent.shape[0] or pr['n_seg'] != rel.shape[0]:
+        raise ValueError(f'the orderings cover {pe["n_seg"]} entities / {pr["n_seg"]} relations, the tables hold '
+                         f'{ent.shape[0]} / {rel.shape[0]} rows')
+    if tuple(g_ent.shape) != (pe['n'], dim) or tuple(g_rel.shape) != (pr['n'], dim):
+        raise ValueError(f'g_ent {tuple(g_ent.shape)} / g_rel {tuple(g_rel.shape)}: expected ({pe["n"]}, {dim}) / ({pr["n"]}, {dim}), '
+                         'one row per ordered occurrence')
+    loss_part, loss_out = _chk(loss_part, name='loss_part'), _chk(loss_out, name='loss_out')
+    if loss_part.numel() < 1 or loss_out.numel() < 1:
+        raise ValueError('loss_part and loss_out need at least one entry')
+    for name, pair in (('state.ent', state.ent), ('state.rel', state.rel)):
+        for i, x in enumerate(pair):
+            _chk(x, name=f'{name}[{i}]')
+    t = _chk(state.t, torch.int64, 'state.t')
+    if t.numel() != 1:
+        raise ValueError('state.t: one int64 entry')
+    for name, x in (('g_ent', g_ent), ('g_rel', g_rel), ('loss_part', loss_part), ('loss_out', loss_out), ('state.ent', state.ent[0]),
+                    ('state.ent', state.ent[1]), ('state.rel', state.rel[0]), ('state.rel', state.rel[1]), ('state.t', t)):
+        if x.device != ent.device:
+            raise ValueError(f'{name}: on {x.device}, the tables on {ent.device}')
+    if epoch_acc is not None:
+        epoch_acc = _chk(epoch_acc, torch.float64, 'epoch_acc')
+        if epoch_acc.numel() < 1 or epoch_acc.device != ent.device:
+            raise ValueError('epoch_acc: one float64 entry on the tables\' device')
+    t.add_(1)         # on the stream, ahead of the launch that reads it: part of a captured step
+    lib.call('gv_transe_apply_opt', ptr(ent), ent.shape[0], ptr(g_ent), ptr(pe['perm']), ptr(pe['rowptr']), ptr(rel), rel.shape[0],
+             ptr(g_rel), ptr(pr['perm']), ptr(pr['rowptr']), dim, code, lr, weight_decay, lr_decay, ptr(state.ent[0]),
+             ptr(state.ent[1]), ptr(state.rel[0]), ptr(state.rel[1]), ptr(t), ptr(loss_part), loss_part.numel(), float(margin),
+             ptr(loss_out), ptr(epoch_acc), lib.stream())
+
+
 def transe_queries(ent, rel=None, a=None, r=None, head=False, norm_flag=True):
     """q[i] = n(ent[a[i]]) + n(rel[r[i]]) (tail queries), n(ent[a[i]]) - n(rel[r[i]]) (head queries); without ``rel`` the
     normalised table n(ent) (gv_transe_queries)."""

@@ -26,6 +26,16 @@ two gv_build_csr orderings of the occurrences, and one launch that sums each tou
 ``p += -lr * g`` (rows without occurrences are not written, as torch's dense SGD leaves them).  No float atomics: a step is
 bit-identical run to run and eager vs captured.  The loss stays on the device; the per-epoch sum is read once per epoch.
 
+Optimisers: the reference Trainer's ``opt_method`` / ``alpha`` / ``weight_decay`` / ``lr_decay`` (torch.optim's SGD, Adagrad,
+Adadelta, Adam at torch's defaults) are ``DeviceTrainer(opt_method=..., weight_decay=..., lr_decay=...)`` and the CLI's
+``--optimizer`` / ``--weight-decay`` / ``--lr-decay`` (``--opt-method`` itself stays at sgd).  Plain SGD keeps the launch above;
+every other choice replaces it by ``ops.transe_apply_opt`` (gv_transe_apply_opt): the same ordered per-row sum, then the chosen
+rule, with the state (two arrays per table, ``ops.TransEOptState``) and the step number on the device -- the step number is
+advanced on the stream inside the step, so a captured graph's replays see it grow.  Semantics are torch's dense ones: Adadelta,
+Adam and any weight decay update every row of both tables at every step, SGD and Adagrad without decay only the touched rows.
+``apply_unfused`` states the update with ``index_add_`` and a real ``torch.optim`` step.  Checkpoints are the model's state dict,
+as in the reference: the optimiser state is not saved, and a resumed run starts it from zero.
+
 Evaluation: raw and filtered MRR, MR and Hits@1/3/10 over both directions, filter = train + valid + test.  Ranks are exactly
 ``ranking.sort_and_rank(-distance, target)``: tail queries ``q = n(h) + n(r)``, head queries ``q = n(t) - n(r)``, both
 ``||q - n(E_j)||_p`` (``h' + (r - t)`` and ``h' - (t - r)`` round alike), from ``ops.transe_rank_filtered``, which never stores
@@ -46,6 +56,7 @@ cross-check.  ``--complete-topk K`` / ``--complete-threshold D`` write them to `
 
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
+    python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --optimizer adam --alpha 0.001 --graph-step
 """
 import argparse
 import time
@@ -270,12 +281,54 @@ def sample_from_draws(draws, train, num_nodes, batch, neg_ent, p_head=None, trai
 # ------------------------------------------------------------------------------------------------
 # device trainer
 # ------------------------------------------------------------------------------------------------
+OPT_METHODS = ('sgd', 'adagrad', 'adadelta', 'adam')
+
+
+def make_optimizer(params, opt_method='sgd', alpha=1.0, weight_decay=0.0, lr_decay=0.0):
+    """The ``torch.optim`` optimiser the reference's Trainer builds from ``opt_method`` (case-insensitive), ``alpha``,
+    ``weight_decay`` and, for Adagrad only, ``lr_decay``; everything else at torch's defaults.  What ``apply_unfused`` steps."""
+    name = str(opt_method).lower()
+    if name == 'adagrad':
+        return torch.optim.Adagrad(params, lr=alpha, lr_decay=lr_decay, weight_decay=weight_decay)
+    if name == 'adadelta':
+        return torch.optim.Adadelta(params, lr=alpha, weight_decay=weight_decay)
+    if name == 'adam':
+        return torch.optim.Adam(params, lr=alpha, weight_decay=weight_decay)
+    if name == 'sgd':
+        return torch.optim.SGD(params, lr=alpha, weight_decay=weight_decay)
+    raise ValueError(f'opt_method {opt_method!r}: expected one of {OPT_METHODS}')
+
+
+def apply_unfused(ent, rel, g_ent_rows, occ_ent, g_rel_rows, occ_rel, optimizer):
+    """The update of ``ops.transe_apply_opt`` in plain torch (any device, any dtype): the occurrence rows are ``index_add_``-ed
+    into dense gradients of the two tables (row i of ``g_ent_rows`` belongs to entity ``occ_ent[i]``, row i of ``g_rel_rows`` to
+    relation ``occ_rel[i]``) and ``optimizer`` -- a ``torch.optim`` optimiser over ``[ent, rel]``, e.g. ``make_optimizer`` --
+    takes one step.  The tables are updated in place.  The cross-check and the bench's comparator, never a fallback."""
+    for table, rows, occ in ((ent, g_ent_rows, occ_ent), (rel, g_rel_rows, occ_rel)):
+        occ = occ.to(device=table.device, dtype=torch.long)
+        table.grad = torch.zeros_like(table).index_add_(0, occ, rows.to(device=table.device, dtype=table.dtype))
+    optimizer.step()
+    return ent, rel
+
+
 class DeviceTrainer:
-    """TransE training on the device: ``step()`` = sample + fused step + orderings + SGD, ``capture()`` records one step as a
-    hipGraph that ``step()`` then replays.  ``model``'s two embedding tables are updated in place."""
+    """TransE training on the device: ``step()`` = sample + fused step + orderings + optimiser update, ``capture()`` records one
+    step as a hipGraph that ``step()`` then replays.  ``model``'s two embedding tables are updated in place.  ``opt_method``
+    ('sgd', 'adagrad', 'adadelta', 'adam', case-insensitive), ``weight_decay`` and ``lr_decay`` (Adagrad only) are the reference
+    Trainer's; ``alpha`` is the learning rate of every method.  The optimiser state (``opt_state``) lives on the device."""
 
     def __init__(self, model, train, nbatches=100, neg_ent=25, bern_flag=True, filter_flag=True, margin=5.0, alpha=1.0,
-                 adv_temperature=None, regul_rate=0.0, device='cuda'):
+                 adv_temperature=None, regul_rate=0.0, device='cuda', opt_method='sgd', weight_decay=0.0, lr_decay=0.0):
+        self.opt_method = str(opt_method).lower()
+        if self.opt_method not in OPT_METHODS:
+            raise ValueError(f'opt_method {opt_method!r}: expected one of {OPT_METHODS}')
+        self.weight_decay, self.lr_decay = float(weight_decay), float(lr_decay)
+        if not self.weight_decay >= 0 or not self.lr_decay >= 0:
+            raise ValueError(f'weight_decay={weight_decay} lr_decay={lr_decay}: both must be >= 0')
+        if (self.opt_method != 'sgd' or self.weight_decay != 0) and not float(alpha) >= 0:
+            raise ValueError(f'alpha={alpha}: must be >= 0 with opt_method {self.opt_method!r} / weight_decay')
+        if self.lr_decay != 0 and self.opt_method != 'adagrad':
+            raise ValueError('lr_decay is Adagrad\'s (the reference passes it to no other optimiser)')
         self.device = torch.device(device)
         if self.device.type == 'cuda' and self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
@@ -308,6 +361,10 @@ class DeviceTrainer:
         self.order = ops.TransEOrder((2 + K) * B, model.ent_tot, B, model.rel_tot, self.device)
         self.loss = torch.zeros(1, device=self.device)
         self.epoch_loss = torch.zeros(1, dtype=torch.float64, device=self.device)
+        # plain SGD keeps gv_transe_apply (and its bits); everything else goes through gv_transe_apply_opt with this state
+        self.opt_state = None
+        if self.opt_method != 'sgd' or self.weight_decay != 0:
+            self.opt_state = ops.TransEOptState(model.ent_tot, model.rel_tot, dim, self.device)
         self.graph = None
 
     def _step(self):
@@ -320,16 +377,25 @@ class DeviceTrainer:
                                              self.model.norm_flag, self.margin, self.adv, self.regul, out=self.grads,
                                              occ_ent=self.occ_ent, check=False)
         order = self.order.build(self.occ_ent, self.br[:B])
-        ops.transe_apply(self.ent, self.rel, g_ent, g_rel, order, self.alpha, part, self.margin, self.loss, self.epoch_loss)
+        if self.opt_state is None:
+            ops.transe_apply(self.ent, self.rel, g_ent, g_rel, order, self.alpha, part, self.margin, self.loss, self.epoch_loss)
+        else:
+            ops.transe_apply_opt(self.ent, self.rel, g_ent, g_rel, order, self.opt_method, self.alpha, part, self.margin, self.loss,
+                                 self.epoch_loss, state=self.opt_state, weight_decay=self.weight_decay, lr_decay=self.lr_decay)
 
     def capture(self):
-        """Record one step.  A warm-up step runs first, outside capture (library load, the orderings' first launches); the tables
-        and the RNG state are restored after it, so a captured run takes exactly the steps an eager run takes, with the same draws."""
+        """Record one step.  A warm-up step runs first, outside capture (library load, the orderings' first launches); the tables,
+        the RNG state and the optimiser state with its step number are restored after it, so a captured run takes exactly the
+        steps an eager run takes, with the same draws.  The step number is advanced on the stream inside the step, so every
+        replay sees the next one."""
         saved = (self.ent.clone(), self.rel.clone(), self.rng.state.clone())
+        opt_saved = self.opt_state.snapshot() if self.opt_state is not None else None
         self._step()
         self.ent.copy_(saved[0])
         self.rel.copy_(saved[1])
         self.rng.state.copy_(saved[2])
+        if opt_saved is not None:
+            self.opt_state.restore(opt_saved)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
@@ -744,8 +810,12 @@ def build_parser():
     p.add_argument('--bern-flag', type=int, default=1)
     p.add_argument('--filter-flag', type=int, default=1)
     p.add_argument('--train-times', type=int, default=1000)
-    p.add_argument('--alpha', type=float, default=1.0, help='SGD learning rate')
-    p.add_argument('--opt-method', type=str, default='sgd')
+    p.add_argument('--alpha', type=float, default=1.0, help='learning rate (of every --optimizer)')
+    p.add_argument('--opt-method', type=str, default='sgd', help='kept at sgd: choose the optimiser with --optimizer')
+    p.add_argument('--optimizer', type=str, default='sgd',
+                   help='sgd, adagrad, adadelta or adam (case-insensitive): the torch.optim rule at torch\'s defaults, on the device')
+    p.add_argument('--weight-decay', type=float, default=0.0, help='coupled L2 decay, g += weight_decay * p (every row, every step)')
+    p.add_argument('--lr-decay', type=float, default=0.0, help='Adagrad\'s learning-rate decay (with --optimizer adagrad only)')
     p.add_argument('--adv-temperature', type=float, default=None)
     p.add_argument('--regul-rate', type=float, default=0.0)
     p.add_argument('--seed', type=int, default=None)
@@ -775,7 +845,20 @@ def build_parser():
 
 def check_args(args):
     if args.opt_method.lower() != 'sgd':
-        raise ValueError(f'--opt-method {args.opt_method}: only sgd is supported')
+        raise ValueError(f'--opt-method {args.opt_method}: only sgd is supported here; choose the optimiser with --optimizer '
+                         f'{{{",".join(OPT_METHODS)}}}')
+    opt = str(getattr(args, 'optimizer', 'sgd')).lower()
+    if opt not in OPT_METHODS:
+        raise ValueError(f'--optimizer {args.optimizer}: expected one of {", ".join(OPT_METHODS)}')
+    wd, ld = getattr(args, 'weight_decay', 0.0), getattr(args, 'lr_decay', 0.0)
+    if not wd >= 0:
+        raise ValueError(f'--weight-decay must be >= 0, got {wd}')
+    if not ld >= 0:
+        raise ValueError(f'--lr-decay must be >= 0, got {ld}')
+    if ld != 0 and opt != 'adagrad':
+        raise ValueError('--lr-decay is Adagrad\'s learning-rate decay: it needs --optimizer adagrad')
+    if (opt != 'sgd' or wd != 0) and not args.alpha >= 0:
+        raise ValueError(f'--alpha must be >= 0 with --optimizer {opt} / --weight-decay, got {args.alpha}')
     if args.neg_rel != 0:
         raise ValueError('--neg-rel: relation corruption is not supported')
     if args.p_norm not in (1, 2):
@@ -818,7 +901,9 @@ def main(args):
     if not args.test_mode:
         model = model.to(dev)
         tr = DeviceTrainer(model, data.train, args.nbatches, args.neg_ent, bool(args.bern_flag), bool(args.filter_flag),
-                           args.margin, args.alpha, args.adv_temperature, args.regul_rate, dev)
+                           args.margin, args.alpha, args.adv_temperature, args.regul_rate, dev,
+                           opt_method=getattr(args, 'optimizer', 'sgd'), weight_decay=getattr(args, 'weight_decay', 0.0),
+                           lr_decay=getattr(args, 'lr_decay', 0.0))
         if args.graph_step:
             tr.capture()
         print('Finish initializing...')

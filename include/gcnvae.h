@@ -635,6 +635,21 @@ int gv_ec_head_bwd(const float* p, const int64_t* labels, const int32_t* row_pos
  *     and, optionally, score [batch (1 + neg_ent)] and occ_ent [(2 + neg_ent) batch], the entity id of each g_ent row.
  *   gv_transe_apply : p += -lr * (sum of the row's occurrence gradients in perm order) for every row with occurrences (gv_build_csr
  *     orderings of the occurrence ids: perm_*, rowptr_*); *loss_out = sum(loss_part) + margin, *epoch_acc (optional, double) += it.
+ *   gv_transe_apply_opt : gv_transe_apply's launch (one wave per table row, the row's occurrence gradients summed in perm order, the
+ *     same loss_out / epoch_acc) with the rule of torch.optim at torch's defaults applied to the summed g, chosen by method
+ *     (GV_TRANSE_OPT_*), after the coupled decay g += weight_decay * p:
+ *       SGD      : p -= lr * g                     (weight_decay == 0: gv_transe_apply's bits)
+ *       ADAGRAD  : s1 += g * g; p -= clr * g / (sqrt(s1) + 1e-10), clr = lr / (1 + (t - 1) * lr_decay)
+ *       ADADELTA : s1 = 0.9 s1 + 0.1 g * g; d = sqrt(s2 + 1e-6) / sqrt(s1 + 1e-6) * g; s2 = 0.9 s2 + 0.1 d * d; p -= lr * d
+ *       ADAM     : s1 += 0.1 (g - s1); s2 = 0.999 s2 + 0.001 g * g; p -= (lr / bc1) * s1 / (sqrt(s2) / sqrt(bc2) + 1e-8),
+ *                  bc1 = 1 - 0.9^t, bc2 = 1 - 0.999^t
+ *     s1_* / s2_* are float32 state arrays shaped like their table (SGD: none read; ADAGRAD: s1 only), zero before the first step.
+ *     *step_t (int64, device) is the 1-based number of THIS step: the caller advances it ahead of the launch (on the stream, so
+ *     that a captured graph's replays see it grow); the kernel only reads it (ADAGRAD, ADAM).  clr, lr / bc1 and sqrt(bc2) are
+ *     formed in double and rounded to float once.  Dense semantics: under ADADELTA, ADAM or weight_decay != 0 every row of both
+ *     tables is updated at every step (a row without occurrences has g = 0); under SGD / ADAGRAD at weight_decay == 0 such a row
+ *     is the identity and is not written.  lr, weight_decay and lr_decay must be >= 0, 1 <= dim <= GV_TRANSE_MAX_DIM (the row's
+ *     columns are summed side by side, GV_TRANSE_MAX_DIM / 64 a lane, four occurrences fetched at a time).
  *   gv_transe_queries : q[i] = n(ent[a[i]]) + n(rel[r[i]]) (head = 0) or n(ent[a[i]]) - n(rel[r[i]]) (head = 1); rel == NULL:
  *     q[i] = n(ent[i]) (the normalised table).  n = F.normalize (eps 1e-12) when norm_flag, the identity otherwise.
  *   gv_transe_distances : out [m, v] = ||q[i] - en[j]||_p, columns summed in order.
@@ -661,6 +676,15 @@ int gv_transe_step(const float* ent, const float* rel, const int32_t* bh, const 
 int gv_transe_apply(float* ent, int n_ent, const float* g_ent, const int32_t* perm_e, const int32_t* rowptr_e, float* rel, int n_rel,
                     const float* g_rel, const int32_t* perm_r, const int32_t* rowptr_r, int dim, float lr, const float* loss_part,
                     int batch, float margin, float* loss_out, double* epoch_acc, void* stream);
+#define GV_TRANSE_OPT_SGD 0
+#define GV_TRANSE_OPT_ADAGRAD 1
+#define GV_TRANSE_OPT_ADADELTA 2
+#define GV_TRANSE_OPT_ADAM 3
+int gv_transe_apply_opt(float* ent, int n_ent, const float* g_ent, const int32_t* perm_e, const int32_t* rowptr_e, float* rel,
+                        int n_rel, const float* g_rel, const int32_t* perm_r, const int32_t* rowptr_r, int dim, int method, double lr,
+                        double weight_decay, double lr_decay, float* s1_ent, float* s2_ent, float* s1_rel, float* s2_rel,
+                        const int64_t* step_t, const float* loss_part, int batch, float margin, float* loss_out, double* epoch_acc,
+                        void* stream);
 int gv_transe_queries(const float* ent, const float* rel, const int32_t* a, const int32_t* r, int64_t m, int dim, int head,
                       int norm_flag, float* q, void* stream);
 int gv_transe_distances(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, float* out, void* stream);

@@ -20,6 +20,13 @@ materialised distances + torch selection) in the same process, each warmed up on
 many) synchronised runs; the two results are asserted bit-equal.  At dim 200 predict_topk(k = 128) over all N x R queries is timed
 once as well -- it answers another question (the best 128 per query, not the global K).
 
+--opt runs the optimiser leg alone (python tools/transe_bench.py --opt [--out profiles/transe_opt/bench.json]): the whole step at
+the workload above with SGD, Adagrad, Adadelta and Adam, eager and captured, the four interleaved over --opt-rounds rounds of
+--steps steps in one process (medians and minima in µs, and each method over SGD); then the update alone on one batch's
+occurrence rows: ops.transe_apply_opt against transe.apply_unfused (index_add_ + torch.optim on the same device and rows) and
+against plain SGD's ops.transe_apply.  Its bytes are an upper estimate: the occurrence rows read once, plus every table and state
+array read and written once (all rows for Adadelta / Adam, the touched rows otherwise), against 8 TB/s.
+
 Step bytes: algorithmic, counting the gathered rows (3 per positive + 1 per negative), the occurrence gradients written and read,
 and the touched table rows read and written once, against 8 TB/s.  Scorer: |a - b| terms at ~1.5 VALU instructions each against
 the 157 TFLOP/s fp32 vector rate (an estimate of the floor; the fraction reported is floor / measured)."""
@@ -204,6 +211,72 @@ def case_mine(steps, warmup, repeats=3):
     return res
 
 
+OPT_ALPHA = {'sgd': 1.0, 'adagrad': 0.1, 'adadelta': 1.0, 'adam': 1e-3}
+
+
+def _rounds(fns, n, warmup, rounds):
+    """{name: {median_us, min_us, runs}} of ``timed`` over ``rounds`` interleaved rounds (every function once per round)."""
+    out = {k: [] for k in fns}
+    for r in range(rounds):
+        for k, fn in fns.items():
+            out[k].append(timed(fn, n, warmup if r == 0 else 3))
+    return {k: dict(median_us=float(np.median(v)), min_us=float(min(v)), runs=[round(x, 2) for x in v]) for k, v in out.items()}
+
+
+def case_opt(steps, warmup, rounds=5):
+    """The optimiser leg: the whole training step per method (eager, then captured), the methods interleaved round by round in
+    one process next to plain SGD; then the update alone on one batch's occurrence rows -- ops.transe_apply_opt against
+    transe.apply_unfused (index_add_ + torch.optim, same device, same rows) and against plain SGD's ops.transe_apply."""
+    from gcn_vae_amd import ops, transe
+    data, _ = setup()
+    methods = ('sgd', 'adagrad', 'adadelta', 'adam')
+    trainers = {}
+    for m in methods:
+        torch.manual_seed(0)
+        model = transe.TransE(data.num_nodes, data.num_rels, dim=200, p_norm=1, norm_flag=True).cuda()
+        trainers[m] = transe.DeviceTrainer(model, data.train, 100, 25, True, True, 5.0, OPT_ALPHA[m], opt_method=m)
+    tr = trainers['sgd']
+    B, K, dim = tr.batch, 25, 200
+    rows = data.num_nodes + data.num_rels
+    res = dict(batch=B, neg_ent=K, dim=dim, table_rows=rows, steps=steps, rounds=rounds, alpha=OPT_ALPHA,
+               step_eager=_rounds({m: t.step for m, t in trainers.items()}, steps, warmup, rounds))
+    for t in trainers.values():
+        t.capture()
+    res['step_graph'] = _rounds({m: t.step for m, t in trainers.items()}, steps, warmup, rounds)
+    for kind in ('step_eager', 'step_graph'):
+        for m in methods:
+            res[kind][m]['over_sgd'] = res[kind][m]['median_us'] / res[kind]['sgd']['median_us']
+    # the update alone, on the occurrence rows the SGD trainer's last step left in its buffers
+    torch.cuda.synchronize()
+    g_ent, g_rel, part = tr.grads
+    parts = tr.order.parts
+    occ_e, occ_r = tr.occ_ent.long(), tr.br[:B].long()
+    loss = torch.zeros(1, device='cuda')
+    fns = {}
+    keep = []
+    for m in methods:
+        ent, rel = tr.ent.clone(), tr.rel.clone()
+        state = ops.TransEOptState(ent.shape[0], rel.shape[0], dim, ent.device)
+        fns[m + '_fused'] = (lambda m=m, ent=ent, rel=rel, state=state:
+                             ops.transe_apply_opt(ent, rel, g_ent, g_rel, parts, m, OPT_ALPHA[m], part, 5.0, loss, state=state))
+        ent2, rel2 = tr.ent.clone(), tr.rel.clone()
+        opt = transe.make_optimizer([ent2, rel2], m, OPT_ALPHA[m])
+        fns[m + '_unfused'] = (lambda ent2=ent2, rel2=rel2, opt=opt: transe.apply_unfused(ent2, rel2, g_ent, occ_e, g_rel, occ_r, opt))
+        keep.append((ent, rel, state, ent2, rel2, opt))
+    ent0, rel0 = tr.ent.clone(), tr.rel.clone()
+    fns['sgd_transe_apply'] = lambda: ops.transe_apply(ent0, rel0, g_ent, g_rel, parts, 1.0, part, 5.0, loss)
+    res['apply'] = _rounds(fns, steps, warmup, rounds)
+    for m in methods:
+        f, u = res['apply'][m + '_fused'], res['apply'][m + '_unfused']
+        arrays = {'sgd': 0, 'adagrad': 4, 'adadelta': 6, 'adam': 6}[m]       # table + state arrays, each read and written
+        dense = m in ('adadelta', 'adam')
+        nbytes = 4 * dim * ((2 + K) * B + B) + (4 * dim * rows * arrays if dense else
+                                                 4 * dim * (min(data.num_nodes, (2 + K) * B) + min(data.num_rels, B)) * max(arrays, 2))
+        res['apply'][m] = dict(unfused_over_fused=u['median_us'] / f['median_us'], bytes_upper=nbytes,
+                               hbm_floor_us=nbytes / HBM * 1e6, hbm_fraction=nbytes / HBM * 1e6 / f['median_us'])
+    return res
+
+
 def case_mine_trace(steps, warmup):
     """What ``rocprofv3 --kernel-trace --stats -- python tools/transe_bench.py --case mine_trace`` profiles: the fused top-K route
     alone, dim 200, L1 then L2, a warm-up and two runs each."""
@@ -236,7 +309,9 @@ def main():
     ap.add_argument('--topk-repeats', type=int, default=5)
     ap.add_argument('--mine', action='store_true', help='run the completion leg alone')
     ap.add_argument('--mine-repeats', type=int, default=3)
-    ap.add_argument('--out', default=None, help='with --topk / --mine: also write the JSON result to this file')
+    ap.add_argument('--opt', action='store_true', help='run the optimiser leg alone')
+    ap.add_argument('--opt-rounds', type=int, default=5)
+    ap.add_argument('--out', default=None, help='with --topk / --mine / --opt: also write the JSON result to this file')
     a = ap.parse_args()
     if a.case == 'mine':
         print('RESULT ' + json.dumps(case_mine(a.steps, a.warmup, a.mine_repeats)))
@@ -244,9 +319,14 @@ def main():
     if a.case == 'topk':
         print('RESULT ' + json.dumps(case_topk(a.steps, a.warmup, a.topk_repeats)))
         return
-    if a.topk or a.mine:
+    if a.case == 'opt':
+        print('RESULT ' + json.dumps(case_opt(a.steps, a.warmup, a.opt_rounds)))
+        return
+    if a.topk or a.mine or a.opt:
         leg = ['--case', 'topk', '--topk-repeats', str(a.topk_repeats)] if a.topk else ['--case', 'mine', '--mine-repeats',
                                                                                            str(a.mine_repeats)]
+        if a.opt:
+            leg = ['--case', 'opt', '--opt-rounds', str(a.opt_rounds), '--steps', str(a.steps), '--warmup', str(a.warmup)]
         # the mining leg reports each configuration on stderr as it finishes
         r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__)] + leg,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE if a.topk else None, text=True, cwd=ROOT)
