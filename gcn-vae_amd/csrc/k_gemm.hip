@@ -321,13 +321,44 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
     }
 }
 
+// ---- the 64 x 64 score tile of the entity queries: acc = Q[m0 .., :] @ E[n0 .., :]^T -------------------------------------------
+// The rankers and the top-k scorer all take their logits from here, and it runs the SAME k-ordered fp32 MFMA chain as
+// k_gemm_f32<false, true, 1, 1, 16>: a target's logit is bit-identical to the element a later pass recomputes, every count equals
+// the one taken on a materialised score matrix, and top-k logits equal gv_gemm_f32 + bias.  The caller has issued the loads of
+// the first k-chunk into ra / rb (so they fly under whatever it does first); the later chunks' loads fly under the MFMAs here.
+constexpr int SC_BM = 64, SC_BN = 64, SC_BK = 16, SC_LDA = SC_BM + 1, SC_LDB = SC_BN + 1;
+
+__device__ __forceinline__ f32x16 score_tile(const GemmParams& p, int m0, int n0, float (&ra)[SC_BM * SC_BK / 256],
+                                             float (&rb)[SC_BN * SC_BK / 256], float* As, float* Bs) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int k0 = 0; k0 < p.k; k0 += SC_BK) {
+        stage_a<false, SC_BM, SC_BK>(As, ra);
+        stage_b<true, SC_BN, SC_BK>(Bs, rb);
+        __syncthreads();
+        if (k0 + SC_BK < p.k) {
+            load_a<false, SC_BM, SC_BK>(p, m0, k0 + SC_BK, p.k, ra);
+            load_b<true, SC_BN, SC_BK>(p, n0, k0 + SC_BK, p.k, rb);
+        }
+#pragma unroll
+        for (int kk = 0; kk < SC_BK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * SC_LDA + wm + l31], Bs[(kk + lhi) * SC_LDB + wn + l31],
+                                                       acc, 0, 0, 0);
+        __syncthreads();
+    }
+    return acc;
+}
+
 // ---- evaluation scorer with a rank-count epilogue (perturb_and_get_rank, kgvae/utils.py:180-221) ----
 // S = Q (m x h) @ E^T (E: v x h), prob = sigmoid(S + *bias).  The reference materialises an (h, Eb, V) tensor, sorts every
 // row and looks the target up; here the probabilities never leave the registers:
-//   PASS 0  tgt[row]    = prob[row, target[row]]                      (written by the one lane that owns that element)
-//   PASS 1  count[row] += #{ col != target[row] : prob[row, col] > tgt[row] }   (wave ballots, one int atomic per 32 columns)
-// Both passes run the SAME k-ordered fp32 MFMA chain as k_gemm_f32<false, true, 1, 1, 16>, so tgt is bit-identical to the
-// element the second pass recomputes and the count equals the one taken on a materialised score matrix.
+//   PASS 0  tgt[row]    = logit[row, target[row]]                     (written by the one lane that owns that element)
+//   PASS 1  count[row] += #{ col != target[row] : logit[row, col] > tgt[row] }   (wave ballots, one int atomic per 32 columns)
+// Both passes take the logit from score_tile, so tgt is bit-identical to the element the second pass recomputes.
 struct RankParams {
     GemmParams g;            // a = Q, b = E (stored [v, h]), m, n = v, k = h
     const int* target;
@@ -336,67 +367,62 @@ struct RankParams {
     int* count;
 };
 
+// This half-wave's ballots for the 32 columns it holds of `row`: bit j of `above` / `equal` = the candidate in column
+// (col - l31) + j beats / ties with the row's target.  Ranked on the LOGIT: monotone with the reference's sigmoid
+// (kgvae/utils.py:208) but free of its saturation, where every candidate ties at 1.0f.  A count is 2 * #above + #equal, i.e. twice
+// the mid-rank under ties; a candidate that is NaN, or any candidate when the target itself is NaN, counts as above (never
+// optimistic).  The target's own column and everything outside the matrix vote nowhere.
+struct RankVotes {
+    unsigned above, equal;
+};
+
+// (a row is never negative: indexed unsigned, an access costs no sign extension)
+__device__ __forceinline__ RankVotes rank_votes(const RankParams& rp, float logit, int row, int col, int lhi) {
+    const bool live = row < rp.g.m;
+    const int tcol = live ? rp.target[(unsigned)row] : -1;
+    const float t = live ? rp.tgt[(unsigned)row] : 0.f;
+    const bool other = live && col < rp.g.n && col != tcol;
+    const bool above = other && !(logit <= t);          // greater, or either side NaN
+    const bool equal = other && logit == t;
+    const unsigned long long ma = __ballot(above), me = __ballot(equal);
+    return {(unsigned)(lhi ? (ma >> 32) : (ma & 0xffffffffull)), (unsigned)(lhi ? (me >> 32) : (me & 0xffffffffull))};
+}
+
+__device__ __forceinline__ void rank_count_add(int* count, int row, unsigned above, unsigned equal) {
+    const int c = 2 * __popc(above) + __popc(equal);
+    if (c) atomicAdd(count + (unsigned)row, c);
+}
+
 template <int PASS>
 __global__ __launch_bounds__(256) void k_rank_scores(const RankParams rp) {
-    constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1;
-    __shared__ float As[BK * LDA_S];
-    __shared__ float Bs[BK * LDB_S];
+    __shared__ float As[SC_BK * SC_LDA];
+    __shared__ float Bs[SC_BK * SC_LDB];
     const GemmParams& p = rp.g;
-    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int m0 = blockIdx.y * SC_BM, n0 = blockIdx.x * SC_BN;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
     const int l31 = lane & 31, lhi = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float ra[BM * BK / 256], rb[BN * BK / 256];
-    load_a<false, BM, BK>(p, m0, 0, p.k, ra);
-    load_b<true, BN, BK>(p, n0, 0, p.k, rb);
-    for (int k0 = 0; k0 < p.k; k0 += BK) {
-        stage_a<false, BM, BK>(As, ra);
-        stage_b<true, BN, BK>(Bs, rb);
-        __syncthreads();
-        if (k0 + BK < p.k) {
-            load_a<false, BM, BK>(p, m0, k0 + BK, p.k, ra);
-            load_b<true, BN, BK>(p, n0, k0 + BK, p.k, rb);
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * LDA_S + wm + l31], Bs[(kk + lhi) * LDB_S + wn + l31],
-                                                       acc, 0, 0, 0);
-        __syncthreads();
-    }
+    float ra[SC_BM * SC_BK / 256], rb[SC_BN * SC_BK / 256];
+    load_a<false, SC_BM, SC_BK>(p, m0, 0, p.k, ra);
+    load_b<true, SC_BN, SC_BK>(p, n0, 0, p.k, rb);
+    const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
     const float bv = rp.bias ? *rp.bias : 0.f;
-    const int col = n0 + wn + l31;
+    const int col = n0 + (wid & 1) * 32 + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-        const bool in = row < p.m && col < p.n;
-        // ranked on the LOGIT: monotone with the reference's sigmoid (kgvae/utils.py:208) but free of its saturation,
-        // where every candidate ties at 1.0f.  count = 2 * #better + #equal, i.e. twice the mid-rank under ties; a
-        // candidate that is NaN, or any candidate when the target itself is NaN, counts as better (never optimistic).
+        const int row = m0 + (wid >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
         const float logit = acc[r] + bv;
-        const int tcol = row < p.m ? rp.target[row] : -1;
         if (PASS == 0) {
-            if (in && col == tcol) rp.tgt[row] = logit;
+            if (row < p.m && col < p.n && col == rp.target[row]) rp.tgt[row] = logit;
         } else {
-            const float t = row < p.m ? rp.tgt[row] : 0.f;
-            const bool other = in && col != tcol;
-            const bool above = other && !(logit <= t);          // greater, or either side NaN
-            const bool equal = other && logit == t;
-            const unsigned long long ma = __ballot(above), me = __ballot(equal);
-            if (l31 == 0 && row < p.m) {
-                const int c = 2 * __popc((unsigned)(lhi ? (ma >> 32) : (ma & 0xffffffffull))) +
-                              __popc((unsigned)(lhi ? (me >> 32) : (me & 0xffffffffull)));
-                if (c) atomicAdd(rp.count + row, c);
-            }
+            const RankVotes vt = rank_votes(rp, logit, row, col, lhi);
+            if (l31 == 0 && row < p.m) rank_count_add(rp.count, row, vt.above, vt.equal);
         }
     }
 }
 
-// ---- filtered rank count (the filtered MRR protocol): PASS 1 of k_rank_scores with a per-tile filter mask ----------------
-// tgt comes from k_rank_scores<0>; this kernel repeats the SAME k-ordered MFMA chain and epilogue arithmetic, so its raw count
-// equals gv_rank_scores' bit for bit, and in the same ballots drops the candidates listed in the query's filter range:
+// ---- the rank counts: raw, filtered (the filtered MRR protocol) and type-constrained, from one pass over the scores ------------
+// tgt comes from k_rank_scores<0>; every count is taken from the ballots of k_rank_scores<1> (rank_votes) on the same logits, so the
+// raw count equals gv_rank_scores' bit for bit, and the filtered one drops the candidates listed in the query's filter range:
 //   count_filt[row] += #{ col != target[row], col not in filt_ent[filt_lo[row] .. filt_hi[row]) : logit > tgt (or NaN) } * 2 + ties
 // The filter of the 64 x 64 tile is a 64-bit word per row in LDS (bit j = column n0 + j is filtered), built before the MFMA loop:
 // two lower-bound searches per row for the window [n0, n0 + 64) of its sorted list, then the window's entries (<= 64 per row) set
@@ -408,22 +434,19 @@ struct RankFiltParams {
     const int* filt_ent;
     int n_ent;               // length of filt_ent: every range is clamped into it
     int* count_filt;
-    // CAND only (gv_rank_scores_constrained): per-query candidate sets, bit j & 31 of word j >> 5 of row cand_set[row] of `cand`
-    const uint32_t* cand;    // [n_sets, ld_cand]
-    const int* cand_set;     // one set id per query; outside [0, n_sets) = the empty set
-    int ld_cand, n_sets;
+    TopkCand cs;             // CAND only (gv_rank_scores_constrained)
     int* count_raw_c;
     int* count_filt_c;       // NULL (as count_filt, filt_lo) when no filter is given
 };
 
-// CAND: the type-constrained protocol on top.  The tile's 64 columns are two words of the row's set, loaded once per row and
-// tile into LDS next to the filter word (the second word guarded: an odd word count has none for the last tile) and ANDed into
-// the same ballots, so the constrained counts see the very logits of the unconstrained ones.  The filter is optional there.
+// CAND: the type-constrained protocol on top.  The tile's 64 columns are two words of the row's set (topk_cand_pair), loaded once
+// per row and tile into LDS next to the filter word and ANDed into the same ballots, so the constrained counts see the very logits
+// of the unconstrained ones.  The filter is optional there.
 template <bool CAND>
 __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltParams fp) {
-    constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1;
-    __shared__ float As[BK * LDA_S];
-    __shared__ float Bs[BK * LDB_S];
+    constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK;
+    __shared__ float As[BK * SC_LDA];
+    __shared__ float Bs[BK * SC_LDB];
     __shared__ unsigned long long fmask[CAND ? 2 * BM : BM];       // 512 B: the tile's filter, one word per row (CAND: + the set's)
     __shared__ int win_lo[BM], win_hi[BM];         // each row's entries inside [n0, n0 + 64)
     const RankParams& rp = fp.rp;
@@ -432,9 +455,6 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
     const int l31 = lane & 31, lhi = lane >> 5;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     float ra[BM * BK / 256], rb[BN * BK / 256];
     load_a<false, BM, BK>(p, m0, 0, p.k, ra);      // the first operand loads fly under the filter searches
     load_b<true, BN, BK>(p, n0, 0, p.k, rb);
@@ -452,16 +472,8 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
         if (threadIdx.x < BM) { win_lo[rl] = pos; fmask[rl] = 0ull; }
         else win_hi[rl] = pos;
     } else if (CAND && threadIdx.x < 3 * BM) {     // the third wave: row t's two set words for columns [n0, n0 + 64)
-        const int rl = threadIdx.x & (BM - 1), row = m0 + rl;
-        const int set = row < p.m ? fp.cand_set[row] : -1;
-        unsigned long long cw = 0ull;
-        if ((unsigned)set < (unsigned)fp.n_sets) {
-            const uint32_t* words = fp.cand + (size_t)set * fp.ld_cand;
-            const int w0 = n0 >> 5;                // n0 < v, so w0 < ceil(v / 32) <= ld_cand
-            cw = words[w0];
-            if (w0 + 1 < (p.n + 31) >> 5) cw |= (unsigned long long)words[w0 + 1] << 32;     // never past the set's last used word
-        }
-        fmask[BM + rl] = cw;
+        const int rl = threadIdx.x & (BM - 1);
+        fmask[BM + rl] = topk_cand_pair(fp.cs, m0 + rl, p.m, n0, p.n);
     }
     __syncthreads();
     // the window's entries, staged cooperatively: wave w takes rows 16 w .. 16 w + 15, one entry per lane (a long list costs its
@@ -475,60 +487,28 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
         }
     }
 
-    for (int k0 = 0; k0 < p.k; k0 += BK) {
-        stage_a<false, BM, BK>(As, ra);
-        stage_b<true, BN, BK>(Bs, rb);
-        __syncthreads();
-        if (k0 + BK < p.k) {
-            load_a<false, BM, BK>(p, m0, k0 + BK, p.k, ra);
-            load_b<true, BN, BK>(p, n0, k0 + BK, p.k, rb);
-        }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * LDA_S + wm + l31], Bs[(kk + lhi) * LDB_S + wn + l31],
-                                                       acc, 0, 0, 0);
-        __syncthreads();
-    }
+    const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
     const float bv = rp.bias ? *rp.bias : 0.f;
     const int col = n0 + wn + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rl = wm + (r & 3) + 8 * (r >> 2) + 4 * lhi, row = m0 + rl;
-        const bool in = row < p.m && col < p.n;
-        const float logit = acc[r] + bv;                        // the epilogue of k_rank_scores<1>, unchanged
-        const int tcol = row < p.m ? rp.target[row] : -1;
-        const float t = row < p.m ? rp.tgt[row] : 0.f;
-        const bool other = in && col != tcol;
-        const bool above = other && !(logit <= t);
-        const bool equal = other && logit == t;
-        const unsigned long long ma = __ballot(above), me = __ballot(equal);
+        const RankVotes vt = rank_votes(rp, acc[r] + bv, row, col, lhi);
         if (l31 == 0 && row < p.m) {
-            const unsigned ha = (unsigned)(lhi ? (ma >> 32) : (ma & 0xffffffffull));
-            const unsigned he = (unsigned)(lhi ? (me >> 32) : (me & 0xffffffffull));
             const unsigned keep = ~(unsigned)(fmask[rl] >> wn);    // this half-wave's 32 columns of the row's filter word
-            if (rp.count) {
-                const int c = 2 * __popc(ha) + __popc(he);
-                if (c) atomicAdd(rp.count + row, c);
-            }
-            if (!CAND || fp.count_filt) {
-                const int cf = 2 * __popc(ha & keep) + __popc(he & keep);
-                if (cf) atomicAdd(fp.count_filt + row, cf);
-            }
-            if (CAND) {      // `in` has dropped the columns >= v already, whatever the set's padding bits hold
+            if (rp.count) rank_count_add(rp.count, row, vt.above, vt.equal);
+            if (!CAND || fp.count_filt) rank_count_add(fp.count_filt, row, vt.above & keep, vt.equal & keep);
+            if (CAND) {      // the votes have dropped the columns >= v already, whatever the set's padding bits hold
                 const unsigned member = (unsigned)(fmask[BM + rl] >> wn);
-                const int cc = 2 * __popc(ha & member) + __popc(he & member);
-                if (cc) atomicAdd(fp.count_raw_c + row, cc);
-                if (fp.count_filt_c) {
-                    const int cfc = 2 * __popc(ha & keep & member) + __popc(he & keep & member);
-                    if (cfc) atomicAdd(fp.count_filt_c + row, cfc);
-                }
+                rank_count_add(fp.count_raw_c, row, vt.above & member, vt.equal & member);
+                if (fp.count_filt_c) rank_count_add(fp.count_filt_c, row, vt.above & keep & member, vt.equal & keep & member);
             }
         }
     }
 }
 
 // ---- top-k link prediction (gv_topk_scores): the rankers' score pass with a selection epilogue ----------------------------
-// logit[i, j] = q_i . e_j + bias comes from the SAME k-ordered MFMA chain as k_rank_scores (so it equals gv_gemm_f32 + bias bit
+// logit[i, j] = q_i . e_j + bias comes from score_tile, as the rankers' does (so it equals gv_gemm_f32 + bias bit
 // for bit); the score matrix is never stored.  Candidates are ordered by a 64-bit key, larger = better:
 //   key = ordered_u32(logit) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
 // a strict total order (ties on the logit by lower id); key 0 is "no candidate" and decodes to id -1, logit -inf.
@@ -555,9 +535,9 @@ struct TopkParams {
 
 template <int NK, bool CAND>
 __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
-    constexpr int BM = 64, BN = 64, BK = 16, LDA_S = BM + 1, LDB_S = BN + 1, LDL = BN + 1;
-    __shared__ float As[BK * LDA_S];
-    __shared__ float Bs[BK * LDB_S];
+    constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1;
+    __shared__ float As[BK * SC_LDA];
+    __shared__ float Bs[BK * SC_LDB];
     __shared__ float Ls[BM * LDL];                 // the tile's logits, row-major
     __shared__ unsigned long long thr[BM];         // each row's k-th key
     __shared__ int cur[BM], fhi[BM], nxt[BM];      // filter cursor, range end, the id at the cursor (INT_MAX: none left)
@@ -591,23 +571,7 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * BN;
         const unsigned cand_w = CAND ? topk_cand_word(cand_row, n0, p.n, lane) : 0u;     // lands under the MFMA chain
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        for (int k0 = 0; k0 < p.k; k0 += BK) {                     // the MFMA chain of k_rank_scores, unchanged
-            stage_a<false, BM, BK>(As, ra);
-            stage_b<true, BN, BK>(Bs, rb);
-            __syncthreads();
-            if (k0 + BK < p.k) {
-                load_a<false, BM, BK>(p, m0, k0 + BK, p.k, ra);
-                load_b<true, BN, BK>(p, n0, k0 + BK, p.k, rb);
-            }
-#pragma unroll
-            for (int kk = 0; kk < BK; kk += 2)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * LDA_S + wm + l31], Bs[(kk + lhi) * LDB_S + wn + l31],
-                                                           acc, 0, 0, 0);
-            __syncthreads();
-        }
+        const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
         if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
             load_a<false, BM, BK>(p, m0, 0, p.k, ra);
             load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
@@ -1086,56 +1050,49 @@ extern "C" int gv_gemm_bf16(int trans_a, int trans_b, int m, int n, int k, const
                     workspace, workspace_bytes, stream);
 }
 
-extern "C" int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
-                              float* tgt, int* count, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0, GV_ERR_SHAPE, "gv_rank_scores: m=%d v=%d h=%d", m, v, h);
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count, GV_ERR_NULL, "gv_rank_scores: NULL pointer");
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores: leading dimension too small");
-    RankParams rp;
-    GemmParams& p = rp.g;
+// the product behind every entity query: S = Q (m x h) @ E^T (E stored [v, h]), nothing stored, no epilogue
+static GemmParams score_gemm_params(const float* q, int ld_q, const float* e, int ld_e, int m, int v, int h) {
+    GemmParams p;
     p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
     p.m = m; p.n = v; p.k = h; p.lda = ld_q; p.ldb = ld_e; p.ldc = v;
     p.act = GV_ACT_NONE; p.accumulate = 0; p.split_k = 1; p.k_chunk = h;
     p.vec_a = aligned16(q) && (ld_q % 4 == 0);
     p.vec_b = aligned16(e) && (ld_e % 4 == 0);
     p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
-    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count;
-    hipStream_t st = (hipStream_t)stream;
-    if (fill_words(count, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status("gv_rank_scores(fill)");
-    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
-    hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);
-    hipLaunchKernelGGL(k_rank_scores<1>, grid, block, 0, st, rp);
-    return launch_status("gv_rank_scores");
+    return p;
 }
 
-// gv_rank_scores_filtered, and with `cand` its type-constrained form (the filter optional there)
-static int rank_filtered_any(const char* name, const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
-                             const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
-                             int ld_cand, int n_sets, const int* cand_set, float* tgt, int* count_raw, int* count_filt,
-                             int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
-    const bool constrained = cand != nullptr;
+// the launches of the three rankers: gv_rank_scores (count_filt NULL: the raw count alone, no filter word to build),
+// gv_rank_scores_filtered and, with cs.cand, its type-constrained form (the filter optional there)
+static int rank_launch(const char* name, const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, float* tgt,
+                       int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
     RankFiltParams fp;
     RankParams& rp = fp.rp;
-    GemmParams& p = rp.g;
-    p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
-    p.m = m; p.n = v; p.k = h; p.lda = ld_q; p.ldb = ld_e; p.ldc = v;
-    p.act = GV_ACT_NONE; p.accumulate = 0; p.split_k = 1; p.k_chunk = h;
-    p.vec_a = aligned16(q) && (ld_q % 4 == 0);
-    p.vec_b = aligned16(e) && (ld_e % 4 == 0);
-    p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
+    rp.g = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
     rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
     fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent; fp.count_filt = count_filt;
-    fp.cand = cand; fp.cand_set = cand_set; fp.ld_cand = ld_cand; fp.n_sets = n_sets;
+    fp.cs = cs;
     fp.count_raw_c = count_raw_c; fp.count_filt_c = count_filt_c;
     hipStream_t st = (hipStream_t)stream;
     for (int* c : {count_raw, count_filt, count_raw_c, count_filt_c})
         if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status(name);
     dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
     hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);           // tgt[row] = the target's logit
-    if (constrained) hipLaunchKernelGGL(k_rank_scores_filtered<true>, grid, block, 0, st, fp);
+    if (!count_filt && !cs.cand) hipLaunchKernelGGL(k_rank_scores<1>, grid, block, 0, st, rp);
+    else if (cs.cand) hipLaunchKernelGGL(k_rank_scores_filtered<true>, grid, block, 0, st, fp);
     else hipLaunchKernelGGL(k_rank_scores_filtered<false>, grid, block, 0, st, fp);
     return launch_status(name);
+}
+
+extern "C" int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
+                              float* tgt, int* count, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0, GV_ERR_SHAPE, "gv_rank_scores: m=%d v=%d h=%d", m, v, h);
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count, GV_ERR_NULL, "gv_rank_scores: NULL pointer");
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores: leading dimension too small");
+    return rank_launch("gv_rank_scores", q, ld_q, e, ld_e, target, bias, nullptr, nullptr, nullptr, 0, TopkCand{}, tgt, count, nullptr,
+                       nullptr, nullptr, m, v, h, stream);
 }
 
 extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
@@ -1147,8 +1104,8 @@ extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e,
     GV_REQUIRE(q && e && target && tgt && count_filt, GV_ERR_NULL, "gv_rank_scores_filtered: NULL pointer");
     GV_REQUIRE(filt_lo && filt_hi && filt_ent, GV_ERR_NULL, "gv_rank_scores_filtered: NULL filter pointer");
     GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_filtered: leading dimension too small");
-    return rank_filtered_any("gv_rank_scores_filtered", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, nullptr,
-                             0, 0, nullptr, tgt, count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
+    return rank_launch("gv_rank_scores_filtered", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, tgt,
+                       count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
 }
 
 extern "C" int gv_rank_scores_constrained(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
@@ -1168,9 +1125,9 @@ extern "C" int gv_rank_scores_constrained(const float* q, int ld_q, const float*
     GV_REQUIRE(q && e && target && tgt && count_raw && count_raw_c, GV_ERR_NULL, "gv_rank_scores_constrained: NULL pointer");
     GV_REQUIRE(!filt_lo || (count_filt && count_filt_c), GV_ERR_NULL, "gv_rank_scores_constrained: a filter needs both filtered counts");
     const bool f = filt_lo != nullptr;        // without a filter the two filtered counts are not written
-    return rank_filtered_any("gv_rank_scores_constrained", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, cand,
-                             ld_cand, n_sets, cand_set, tgt, count_raw, f ? count_filt : nullptr, count_raw_c,
-                             f ? count_filt_c : nullptr, m, v, h, stream);
+    return rank_launch("gv_rank_scores_constrained", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                       TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, f ? count_filt : nullptr, count_raw_c,
+                       f ? count_filt_c : nullptr, m, v, h, stream);
 }
 
 extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
@@ -1186,13 +1143,7 @@ static int topk_scores_launch(const char* name, const float* q, int ld_q, const 
                               const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
                               int* out_ids, float* out_logits, void* workspace, int m, int v, int h, void* stream) {
     TopkParams tp;
-    GemmParams& p = tp.g;
-    p.a = q; p.b = e; p.c = nullptr; p.bias = nullptr; p.a_mask = nullptr; p.ws = nullptr;
-    p.m = m; p.n = v; p.k = h; p.lda = ld_q; p.ldb = ld_e; p.ldc = v;
-    p.act = GV_ACT_NONE; p.accumulate = 0; p.split_k = 1; p.k_chunk = h;
-    p.vec_a = aligned16(q) && (ld_q % 4 == 0);
-    p.vec_b = aligned16(e) && (ld_e % 4 == 0);
-    p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = 0; p.tmask_wanted = 0;
+    tp.g = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
     tp.bias = bias;
     tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
     tp.topk = k;

@@ -155,6 +155,18 @@ __device__ __forceinline__ bool topk_cand_member(unsigned word, int i, int lane)
     return ((lane < 32 ? w0 : w1) >> (lane & 31)) & 1u;
 }
 
+// The rankers keep a row's two words for the 64-column tile at n0 in LDS instead (one thread per row): both at once, the second
+// under the same guard.  n0 < v, so the first word lies inside ceil(v / 32) <= ld_cand.
+__device__ __forceinline__ unsigned long long topk_cand_pair(const TopkCand& cs, long long row, long long m, int n0, int v) {
+    const int set = row < m ? cs.cand_set[row] : -1;
+    if ((unsigned)set >= (unsigned)cs.n_sets) return 0ull;
+    const uint32_t* words = cs.cand + (size_t)set * cs.ld_cand;
+    const int w0 = n0 >> 5;
+    unsigned long long cw = words[w0];
+    if (w0 + 1 < (v + 31) >> 5) cw |= (unsigned long long)words[w0 + 1] << 32;     // never past the set's last used word
+    return cw;
+}
+
 // ---- stage 2: one wave per row merges the n_spans sorted lists of k keys and hands the first k to `out` --------------------
 // Out::put(i, key) decodes key into entry i of the (m, k) outputs.
 struct TopkLogitOut {

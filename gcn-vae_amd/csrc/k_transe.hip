@@ -580,16 +580,7 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
             }
             mask_s[tid] = mk;
         } else if (CAND && tid < 2 * TE_TQ) {
-            const int64_t qi = q0 + tid - TE_TQ;
-            const int set = qi < m ? cs.cand_set[qi] : -1;
-            unsigned long long cw = 0;
-            if ((unsigned)set < (unsigned)cs.n_sets) {
-                const uint32_t* words = cs.cand + (size_t)set * cs.ld_cand;
-                const int w0 = e0 >> 5;            // e0 < v, so w0 < ceil(v / 32) <= ld_cand
-                cw = words[w0];
-                if (w0 + 1 < (v + 31) >> 5) cw |= (unsigned long long)words[w0 + 1] << 32;     // never past the last used word
-            }
-            mask_s[tid] = cw;
+            mask_s[tid] = topk_cand_pair(cs, q0 + tid - TE_TQ, m, e0, v);
         }
         float acc[4][4];
         te_tile(q, m, en, v, dim, p, q0, e0, qs, es, acc);    // its first barrier publishes dt_s / mask_s

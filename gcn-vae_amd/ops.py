@@ -550,24 +550,53 @@ def rank_scores(q, entities, target, bias=None):
     the number of OTHER entities with a strictly larger logit plus HALF the number that tie with it (gv_rank_scores:
     MFMA tiles with a rank-count epilogue; the (m, V) score matrix is never stored).  Logits, not sigmoid outputs: same
     order, no saturation ties.  A NaN target score ranks last."""
+    q, ld_q, entities, ld_e = _score_operands(q, entities)
+    m, v = q.shape[0], entities.shape[0]
+    tgt32 = _target_args(target, m, v, q.device)
+    bias = _bias_arg(bias)
+    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
+    counts = torch.empty(1, max(m, 1), dtype=torch.int32, device=q.device)
+    lib.call('gv_rank_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(ws), ptr(counts), m, v,
+             q.shape[1], lib.stream())
+    return _ranks(counts, m)[0]
+
+
+def _score_operands(q, entities):
+    """The two operands of a DistMult ranking query, row-major and of one width: (q, ld_q, entities, ld_e)."""
     q, ld_q = _row_major(q, 'q')
     entities, ld_e = _row_major(entities, 'entities')
     if q.shape[1] != entities.shape[1]:
         raise ValueError('q / entities width mismatch')
-    m, v = q.shape[0], entities.shape[0]
+    return q, ld_q, entities, ld_e
+
+
+def _target_args(target, m, v, device):
+    """One target entity per query row, inside [0, v): int32 on the queries' device."""
     target = target.reshape(-1)
     if target.numel() != m:
         raise ValueError('one target per query row')
     if m and (int(target.min()) < 0 or int(target.max()) >= v):
         raise ValueError(f'targets must lie in [0, {v})')
-    tgt32 = target.to(device=q.device, dtype=torch.int32).contiguous()
-    if bias is not None:
-        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
-    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    count = torch.empty(max(m, 1), dtype=torch.int32, device=q.device)
-    lib.call('gv_rank_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(ws), ptr(count), m, v,
-             q.shape[1], lib.stream())
-    return count[:m].to(torch.float32) * 0.5
+    return target.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _topk_arg(k):
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    return k
+
+
+def _bias_arg(bias):
+    """The scorers' optional scalar bias as the one-element float32 tensor the entries read."""
+    return None if bias is None else _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+
+
+def _ranks(counts, m, filt=True):
+    """Ranks from a (1, 2 or 4, >= m) buffer of counts 2 #better + #equal: one float tensor per row of the buffer.  The odd rows
+    are the filtered counts, which the entries leave unwritten when no filter was given (``filt`` False): None for those."""
+    r = counts[:, :m].to(torch.float32) * 0.5
+    return tuple(r[i] if filt or i % 2 == 0 else None for i in range(r.shape[0]))
 
 
 def _filter_args(filt_lo, filt_hi, filt_ent, m, v, device):
@@ -597,32 +626,35 @@ def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=N
     launch pair (gv_rank_scores_filtered).  The filtered rank leaves out the candidates ``filt_ent[filt_lo[i]:filt_hi[i]]`` --
     entity ids sorted ascending and unique inside each range (ranking.FilterIndex builds them) -- whatever their score; ranges
     may be empty, may hold the target and may be shared.  The raw rank equals ``rank_scores`` bit for bit."""
-    q, ld_q = _row_major(q, 'q')
-    entities, ld_e = _row_major(entities, 'entities')
-    if q.shape[1] != entities.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, ld_q, entities, ld_e = _score_operands(q, entities)
     m, v = q.shape[0], entities.shape[0]
-    target = target.reshape(-1)
-    if target.numel() != m:
-        raise ValueError('one target per query row')
-    if filt_lo is None or filt_hi is None or filt_ent is None:
+    # (a wrong number of targets is reported ahead of a missing filter, a target out of range after it)
+    if target.numel() == m and (filt_lo is None or filt_hi is None or filt_ent is None):
         raise ValueError('rank_scores_filtered needs filt_lo, filt_hi and filt_ent')
-    if m and (int(target.min()) < 0 or int(target.max()) >= v):
-        raise ValueError(f'targets must lie in [0, {v})')
+    tgt32 = _target_args(target, m, v, q.device)
     lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    i32 = dict(device=q.device, dtype=torch.int32)
-    tgt32 = target.to(**i32).contiguous()
-    if bias is not None:
-        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    bias = _bias_arg(bias)
     ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.empty(2, max(m, 1), **i32)
+    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=q.device)
     lib.call('gv_rank_scores_filtered', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
              ptr(ent32), n_ent, ptr(ws), ptr(counts[0]), ptr(counts[1]), m, v, q.shape[1], lib.stream())
-    both = counts[:, :m].to(torch.float32) * 0.5
-    return both[0], both[1]
+    return _ranks(counts, m)
 
 
 TOPK_MAX = 128      # largest k gv_topk_scores takes
+
+
+def _topk_operands(q, entities):
+    """The shape checks of ``topk_scores`` on its two operands, ahead of any look at their device: (m, v, h)."""
+    for name, t in (('q', q), ('entities', entities)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if q.shape[1] != entities.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    m, v, h = q.shape[0], entities.shape[0], q.shape[1]
+    if v < 1 or h < 1:
+        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
+    return m, v, h
 
 
 def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -632,17 +664,8 @@ def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=
     are no candidates of row i.  Order: logit descending, equal logits (-0 and +0 alike) by lower id, NaN after everything.
     Returns ``(ids int64 (m, k), logits float32 (m, k))``; rows with fewer than k candidates are padded with id -1, logit -inf.
     Logits are reported with -0 as +0 and every NaN as the one quiet NaN (``ranking.topk_from_scores`` does the same)."""
-    for name, t in (('q', q), ('entities', entities)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise TypeError(f'{name}: expected a 2-D tensor')
-    if q.shape[1] != entities.shape[1]:
-        raise ValueError('q / entities width mismatch')
-    m, v, h = q.shape[0], entities.shape[0], q.shape[1]
-    if v < 1 or h < 1:
-        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
-    k = int(k)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    m, v, h = _topk_operands(q, entities)
+    k = _topk_arg(k)
     lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     q, ld_q = _row_major(q, 'q')
     entities, ld_e = _row_major(entities, 'entities')
@@ -650,8 +673,7 @@ def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=
     logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
     if m == 0:
         return ids.long(), logits
-    if bias is not None:
-        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    bias = _bias_arg(bias)
     ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
     lib.call('gv_topk_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k,
              ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
@@ -683,30 +705,19 @@ def rank_scores_constrained(q, entities, target, cand, cand_set, filt_lo=None, f
     row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``); the target itself is never counted, member or not, and an
     empty or out-of-range set gives rank 0.  The first two equal ``rank_scores_filtered`` bit for bit.  Without a filter the two
     filtered ranks are None."""
-    q, ld_q = _row_major(q, 'q')
-    entities, ld_e = _row_major(entities, 'entities')
-    if q.shape[1] != entities.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, ld_q, entities, ld_e = _score_operands(q, entities)
     m, v = q.shape[0], entities.shape[0]
-    target = target.reshape(-1)
-    if target.numel() != m:
-        raise ValueError('one target per query row')
-    if m and (int(target.min()) < 0 or int(target.max()) >= v):
-        raise ValueError(f'targets must lie in [0, {v})')
+    tgt32 = _target_args(target, m, v, q.device)
     lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    i32 = dict(device=q.device, dtype=torch.int32)
-    tgt32 = target.to(**i32).contiguous()
-    if bias is not None:
-        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    bias = _bias_arg(bias)
     ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.zeros(4, max(m, 1), **i32)
+    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
     filt = lo32 is not None
     lib.call('gv_rank_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
              ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), ptr(ws), ptr(counts[0]), ptr(counts[1]) if filt else None,
              ptr(counts[2]), ptr(counts[3]) if filt else None, m, v, q.shape[1], lib.stream())
-    r = counts[:, :m].to(torch.float32) * 0.5
-    return r[0], (r[1] if filt else None), r[2], (r[3] if filt else None)
+    return _ranks(counts, m, filt)
 
 
 def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -714,17 +725,8 @@ def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=N
     are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``), less the filter-listed
     ids.  Order, ties, NaN and padding are ``topk_scores``'; a set with fewer than k members pads, an out-of-range set id gives
     an all-padding row."""
-    for name, t in (('q', q), ('entities', entities)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise TypeError(f'{name}: expected a 2-D tensor')
-    if q.shape[1] != entities.shape[1]:
-        raise ValueError('q / entities width mismatch')
-    m, v, h = q.shape[0], entities.shape[0], q.shape[1]
-    if v < 1 or h < 1:
-        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
-    k = int(k)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    m, v, h = _topk_operands(q, entities)
+    k = _topk_arg(k)
     q, ld_q = _row_major(q, 'q')
     entities, ld_e = _row_major(entities, 'entities')
     lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
@@ -733,8 +735,7 @@ def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=N
     logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
     if m == 0:
         return ids.long(), logits
-    if bias is not None:
-        bias = _chk(bias.reshape(1).to(torch.float32).contiguous(), name='bias')
+    bias = _bias_arg(bias)
     ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
     lib.call('gv_topk_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
              ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
@@ -3188,28 +3189,27 @@ def transe_distances(q, en, p_norm):
     return out
 
 
+def _transe_operands(q, en):
+    """The two tables of a TransE query, of one width."""
+    q, en = _table(q, 'q'), _table(en, 'entities')
+    if q.shape[1] != en.shape[1]:
+        raise ValueError('q / entities width mismatch')
+    return q, en
+
+
 def transe_rank_filtered(q, en, target, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     """(raw, filtered) 0-based mid-ranks of ``target[i]`` under score = -||q[i] - en[j]||_p -- ``ranking.sort_and_rank`` on
     ``transe_distances`` bit for bit -- without the distance matrix (gv_transe_rank_filtered).  The filter ranges are
     ``rank_scores_filtered``'s; without them the filtered rank equals the raw one."""
-    q, en = _table(q, 'q'), _table(en, 'entities')
-    if q.shape[1] != en.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, en = _transe_operands(q, en)
     p_norm = _p_norm(p_norm)
     m, v = q.shape[0], en.shape[0]
-    target = target.reshape(-1)
-    if target.numel() != m:
-        raise ValueError('one target per query row')
-    if m and (int(target.min()) < 0 or int(target.max()) >= v):
-        raise ValueError(f'targets must lie in [0, {v})')
-    i32 = dict(device=q.device, dtype=torch.int32)
+    tgt32 = _target_args(target, m, v, q.device)
     lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    tgt32 = target.to(**i32).contiguous()
-    counts = torch.zeros(2, max(m, 1), **i32)
+    counts = torch.zeros(2, max(m, 1), dtype=torch.int32, device=q.device)
     lib.call('gv_transe_rank_filtered', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
              ptr(counts[0]), ptr(counts[1]), lib.stream())
-    both = counts[:, :m].to(torch.float32) * 0.5
-    return both[0], both[1]
+    return _ranks(counts, m)
 
 
 def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -3219,15 +3219,11 @@ def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     ascending, equal distances by lower id, NaN after everything (+inf included).  Returns ``(ids int64 (m, k), dist float32
     (m, k))``; rows with fewer than k candidates are padded with id -1, distance +inf.  A zero distance is reported as +0 and
     every NaN as the one quiet NaN (``transe.topk_from_distances`` does the same)."""
-    q, en = _table(q, 'q'), _table(en, 'entities')
-    if q.shape[1] != en.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, en = _transe_operands(q, en)
     if q.device != en.device:
         raise ValueError(f'q on {q.device}, entities on {en.device}')
     p_norm = _p_norm(p_norm)
-    k = int(k)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    k = _topk_arg(k)
     m, v = q.shape[0], en.shape[0]
     if v < 1:
         raise ValueError('need at least one entity')
@@ -3247,42 +3243,29 @@ def transe_rank_constrained(q, en, target, p_norm, cand, cand_set, filt_lo=None,
     -||q[i] - en[j]||_p (gv_transe_rank_constrained): ``transe_rank_filtered``'s two, bit for bit, and the same over the members
     of row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it).  Without a filter the two filtered
     ranks are None."""
-    q, en = _table(q, 'q'), _table(en, 'entities')
-    if q.shape[1] != en.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, en = _transe_operands(q, en)
     p_norm = _p_norm(p_norm)
     m, v = q.shape[0], en.shape[0]
-    target = target.reshape(-1)
-    if target.numel() != m:
-        raise ValueError('one target per query row')
-    if m and (int(target.min()) < 0 or int(target.max()) >= v):
-        raise ValueError(f'targets must lie in [0, {v})')
+    tgt32 = _target_args(target, m, v, q.device)
     lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
     cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    i32 = dict(device=q.device, dtype=torch.int32)
-    tgt32 = target.to(**i32).contiguous()
-    counts = torch.zeros(4, max(m, 1), **i32)
+    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
     filt = lo32 is not None
     lib.call('gv_transe_rank_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
              ptr(cand), ld_cand, n_sets, ptr(set32), ptr(counts[0]), ptr(counts[1]) if filt else None, ptr(counts[2]),
              ptr(counts[3]) if filt else None, lib.stream())
-    r = counts[:, :m].to(torch.float32) * 0.5
-    return r[0], (r[1] if filt else None), r[2], (r[3] if filt else None)
+    return _ranks(counts, m, filt)
 
 
 def transe_topk_constrained(q, en, k, p_norm, cand, cand_set, filt_lo=None, filt_hi=None, filt_ent=None):
     """``transe_topk`` among the members of a per-query candidate set only (gv_transe_topk_constrained): the candidates of row i
     are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it),
     less the filter-listed ids.  Order and padding are ``transe_topk``'s."""
-    q, en = _table(q, 'q'), _table(en, 'entities')
-    if q.shape[1] != en.shape[1]:
-        raise ValueError('q / entities width mismatch')
+    q, en = _transe_operands(q, en)
     if q.device != en.device:
         raise ValueError(f'q on {q.device}, entities on {en.device}')
     p_norm = _p_norm(p_norm)
-    k = int(k)
-    if not 1 <= k <= TOPK_MAX:
-        raise ValueError(f'k must lie in [1, {TOPK_MAX}], got {k}')
+    k = _topk_arg(k)
     m, v = q.shape[0], en.shape[0]
     if v < 1:
         raise ValueError('need at least one entity')
