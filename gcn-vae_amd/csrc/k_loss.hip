@@ -1130,11 +1130,11 @@ __global__ __launch_bounds__(256) void k_prior_sample_bwd(const float* z_pre, co
 }
 
 // ---- DistMult + BCE forward that also sums the relation gradient (gv_distmult_bce_fwd_grad) ------------------------------
-// The by-relation sweep of the weight gradient (k_gradw_fast<1,1,4,U>'s geometry: one wave per (relation, slice, slot) item, a
-// lane on four consecutive columns, U triplets' rows in flight) reads the same e_s, e_o rows the scorer reads, and
-// delta_t = sigmoid(x_t) - y_t needs nothing but the score: one pass forms p = e_s*e_o, x = sum_c p_c w_c (w_r's four columns
-// stay in registers over the item), delta, and acc += delta*p.  The unscaled row sum goes to u[r] (unsplit item) or the item's
-// partial slot; gv_distmult_grad_finish scales by the upstream gradient, which does not exist yet when this runs.
+// The by-relation sweep of the weight gradient (k_gradw_fast<1,1,4,U>'s item list: one wave per (relation, slice, slot) item)
+// reads the same e_s, e_o rows the scorer reads, and delta_t = sigmoid(x_t) - y_t needs nothing but the score: one pass forms
+// p = e_s*e_o, x = sum_c p_c w_c (w_r's columns stay in registers over the item), delta, and acc += delta*p.  The unscaled row
+// sum goes to u[r] (unsplit item) or the item's partial slot; gv_distmult_grad_finish scales by the upstream gradient, which
+// does not exist yet when this runs.
 // The grid is red_blocks(T, 16) workgroups, the partial count gv_loss_combine sums, whatever the item count: workgroup b
 // takes the item quads b, b + grid, ...  (grid % 8 == 0 whenever the list has XCD windows, so a quad keeps its XCD).
 struct DmFusedParams {
@@ -1160,79 +1160,105 @@ struct DmFusedParams {
 
 constexpr int DM_PART = RED_BLOCKS;
 
-__device__ __forceinline__ int dm_rl_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+// Layout (k_kl_fwd_v5's): a DPP row of 16 lanes holds one triplet, lane l16 of it the float4 columns 4*(l16 + 16 g), g < 4, so
+// a wave instruction serves four triplets and a dot product ends inside the row.
+// A wave keeps its 64-triplet batch as (s, o, label, score) entries in LDS: batch lane j fills entry j, step k = 0..15 serves
+// the triplets 4k + rw in row rw (DM_U steps' rows in flight) and leaves their scores there, and the batch lanes finish the
+// scalars (delta for the entity side, the BCE term) once per batch.  A row past the batch's end shadows the batch's last
+// triplet with delta = 0.
+// Summation order.  Score: each lane chains its columns in ascending order (groups g = 0..3, four columns each), then the row
+// butterfly of row16_sum.  Relation row: triplets == q (mod 4) of a batch accumulate in row q in list order; at the item's end
+// the four rows are added as (0 + 1) + (2 + 3) and row 0 stores.
+__device__ __forceinline__ float dm_perm_f(int src_lane, float v) {
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane << 2, __float_as_int(v)));
+}
+__device__ __forceinline__ float dm_delta(float x, float y) { return 1.f / (1.f + expf(-x)) - y; }
 
-template <int U>
+// Steps in flight, on the MI355X at T = 220 000, h = 200: 1 / 2 / 3 -> 95 / 127 / 161 registers, 36.6 / 35.4 / 38.7 us (NOTES.md).
+constexpr int DM_U = 2;
+
 __global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedParams a) {
+    constexpr int U = DM_U;
     __shared__ float sm[4];
+    __shared__ int4 tb[4][64];          // a wave's batch: (s, o, label, score) of batch lane j
+    __shared__ float sums[2][256];      // per thread: BCE terms and deltas of the triplets whose scalars it finishes
+    constexpr int G = 4;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const bool active = lane * 4 < a.h;
-    const int c0 = active ? lane * 4 : 0;
+    const int l16 = lane & 15, rw = lane >> 4;
+    bool on[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) on[g] = 4 * (l16 + 16 * g) < a.h;
     const float bv = a.bias ? *a.bias : 0.f;
-    const float* __restrict__ ebase = a.e + c0;
-    float lsum = 0.f, dsum = 0.f;          // per lane: the triplets whose scalars this lane finishes
-    // x (wave-uniform) of one triplet from its lane products, delta, and the row sum
-    auto triplet = [&](const float (&xs)[4], const float (&xo)[4], const float (&wr)[4], float y, float (&acc)[4], float& x,
-                       float& d) {
-        float p[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) p[i] = active ? xs[i] * xo[i] : 0.f;
-        float dot = p[0] * wr[0];
-        dot = fmaf(p[1], wr[1], dot);
-        dot = fmaf(p[2], wr[2], dot);
-        dot = fmaf(p[3], wr[3], dot);
-        x = wave_sum(dot) + bv;
-        d = 1.f / (1.f + expf(-x)) - y;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fmaf(d, p[i], acc[i]);
-    };
+    const float* __restrict__ ebase = a.e + 4 * l16;
+    sums[0][threadIdx.x] = sums[1][threadIdx.x] = 0.f;
     for (int quad = blockIdx.x; quad * 4 < a.n_items; quad += gridDim.x) {
         const int item = __builtin_amdgcn_readfirstlane(quad * 4 + wv);
         if (item >= a.n_items) continue;
         const int4 it = a.items[item];
         if (it.x < 0) continue;                 // unused tail entry of an upper-bound-sized item list
         if (it.w >= 0 && !a.partial) continue;   // split item without a partial buffer: never dereference NULL
-        float wr[4] = {0.f, 0.f, 0.f, 0.f}, acc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (active) load_vec<4>(a.w + (size_t)it.x * a.ld_w + c0, wr);
+        float4 wr[G], acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            wr[g] = acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (on[g]) wr[g] = *reinterpret_cast<const float4*>(a.w + (size_t)it.x * a.ld_w + 4 * l16 + 64 * g);
+        }
         for (int e0 = it.y; e0 < it.z; e0 += 64) {
             const int cnt = min(64, it.z - e0);
-            int my_s = 0, my_o = 0, my_t = 0;
-            float my_y = 0.f, my_x = 0.f, my_d = 0.f;
-            if (lane < cnt) {
-                my_s = a.rel_s[e0 + lane];
-                my_o = a.rel_o[e0 + lane];
-                my_t = a.rel_tid[e0 + lane];
-                my_y = a.labels[my_t];
-            }
-            int j = 0;
-            for (; j + U <= cnt; j += U) {
-                float xs[U][4], xo[U][4];
+            if (lane < cnt)
+                tb[wv][lane] = make_int4(a.rel_s[e0 + lane], a.rel_o[e0 + lane],
+                                         __float_as_int(a.labels[a.rel_tid[e0 + lane]]), 0);
+            __builtin_amdgcn_wave_barrier();       // (a wave's LDS accesses execute in order: nothing to wait for)
+            for (int j = 0; j < cnt; j += 4 * U) {
+                int2 so[U];
+                float4 xs[U][G], xo[U][G];
+#pragma unroll
+                for (int u = 0; u < U; ++u) so[u] = *reinterpret_cast<const int2*>(&tb[wv][min(j + 4 * u + rw, cnt - 1)]);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const int s = dm_rl_i(my_s, j + u), o = dm_rl_i(my_o, j + u);
-                    if (active) {
-                        load_vec<4>(ebase + (size_t)s * a.ld_e, xs[u]);
-                        load_vec<4>(ebase + (size_t)o * a.ld_e, xo[u]);
+                    const float* ps = ebase + (size_t)so[u].x * a.ld_e;
+                    const float* po = ebase + (size_t)so[u].y * a.ld_e;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        if (on[g]) {
+                            xs[u][g] = *reinterpret_cast<const float4*>(ps + 64 * g);
+                            xo[u][g] = *reinterpret_cast<const float4*>(po + 64 * g);
+                        }
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    float x, d;
-                    triplet(xs[u], xo[u], wr, rl_bcast_f(my_y, j + u), acc, x, d);
-                    if (lane == j + u) { my_x = x; my_d = d; }
+                    float4 (&p)[G] = xs[u];          // the products take the subject row's registers
+                    const int t = j + 4 * u + rw;    // < 64
+                    const float y = __int_as_float(tb[wv][min(t, cnt - 1)].z);      // (lands behind the dot product's chain)
+                    float dot = 0.f;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        p[g].x *= xo[u][g].x; p[g].y *= xo[u][g].y; p[g].z *= xo[u][g].z; p[g].w *= xo[u][g].w;
+                        float c = fmaf(p[g].x, wr[g].x, dot);
+                        c = fmaf(p[g].y, wr[g].y, c);
+                        c = fmaf(p[g].z, wr[g].z, c);
+                        c = fmaf(p[g].w, wr[g].w, c);
+                        dot = on[g] ? c : dot;          // a group past h leaves the chain as it was
+                    }
+                    const float x = row16_sum(dot) + bv;
+                    const float d = t < cnt ? dm_delta(x, y) : 0.f;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {       // (lanes of a group past h carry values that are never stored)
+                        acc[g].x = fmaf(d, p[g].x, acc[g].x);
+                        acc[g].y = fmaf(d, p[g].y, acc[g].y);
+                        acc[g].z = fmaf(d, p[g].z, acc[g].z);
+                        acc[g].w = fmaf(d, p[g].w, acc[g].w);
+                    }
+                    if (l16 == 0 && t < cnt) tb[wv][t].w = __float_as_int(x);
+                    __builtin_amdgcn_sched_barrier(0);   // one step's products at a time: two steps stay inside 128 registers
                 }
             }
-            for (; j < cnt; ++j) {
-                float xs[4], xo[4], x, d;
-                const int s = dm_rl_i(my_s, j), o = dm_rl_i(my_o, j);
-                if (active) {
-                    load_vec<4>(ebase + (size_t)s * a.ld_e, xs);
-                    load_vec<4>(ebase + (size_t)o * a.ld_e, xo);
-                }
-                triplet(xs, xo, wr, rl_bcast_f(my_y, j), acc, x, d);
-                if (lane == j) { my_x = x; my_d = d; }
-            }
+            __builtin_amdgcn_wave_barrier();
             if (lane < cnt) {       // the batch's scalars, one triplet per lane
+                const float my_y = __int_as_float(tb[wv][lane].z), my_x = __int_as_float(tb[wv][lane].w);
+                const int my_t = a.rel_tid[e0 + lane];       // (read again: one register fewer over the step loop)
+                const float my_d = dm_delta(my_x, my_y);
                 a.score[my_t] = my_x;
                 if (a.pos3) {
                     a.delta[a.pos3[3 * (size_t)my_t]] = my_d;
@@ -1240,14 +1266,25 @@ __global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedPara
                 } else {
                     a.delta[my_t] = my_d;
                 }
-                lsum += fmaxf(my_x, 0.f) - my_x * my_y + log1pf(expf(-fabsf(my_x)));
-                dsum += my_d;
+                sums[0][threadIdx.x] += fmaxf(my_x, 0.f) - my_x * my_y + log1pf(expf(-fabsf(my_x)));
+                sums[1][threadIdx.x] += my_d;
             }
+            __builtin_amdgcn_wave_barrier();
         }
-        if (active) store_vec<4>((it.w >= 0 ? a.partial + (size_t)it.w * a.h : a.u + (size_t)it.x * a.h) + c0, acc);
+        float* out = (it.w >= 0 ? a.partial + (size_t)it.w * a.h : a.u + (size_t)it.x * a.h) + 4 * l16;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            float v[4] = {acc[g].x, acc[g].y, acc[g].z, acc[g].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                v[i] += dm_perm_f(lane ^ 16, v[i]);       // rows 0, 1: 0 + 1; rows 2, 3: 2 + 3
+                v[i] += dm_perm_f(lane ^ 32, v[i]);       // row 0: (0 + 1) + (2 + 3)
+            }
+            if (rw == 0 && on[g]) store_vec<4>(out + 64 * g, v);
+        }
     }
-    const float lt = block_sum_256(lsum, sm);
-    const float dt = block_sum_256(dsum, sm);
+    const float lt = block_sum_256(sums[0][threadIdx.x], sm);
+    const float dt = block_sum_256(sums[1][threadIdx.x], sm);
     if (threadIdx.x == 0) {
         a.part[blockIdx.x] = lt;
         a.part[DM_PART + blockIdx.x] = dt;
@@ -1689,7 +1726,7 @@ extern "C" int gv_distmult_bce_fwd_grad(const int32_t* items, int n_items, const
                "gv_distmult_bce_fwd_grad: 16-B alignment required");
     DmFusedParams p{(const int4*)items, n_items, rel_s, rel_o, rel_tid, embed, ld_e, w_rel, ld_w, labels, bias, pos3,
                     score, delta, u, partial, workspace, h};
-    hipLaunchKernelGGL(k_distmult_bce_fwd_grad<8>, dim3(red_blocks(t, 16)), dim3(256), 0, GV_ST, p);
+    hipLaunchKernelGGL(k_distmult_bce_fwd_grad, dim3(red_blocks(t, 16)), dim3(256), 0, GV_ST, p);
     return launch_status("gv_distmult_bce_fwd_grad");
 }
 

@@ -2320,7 +2320,7 @@ DISTMULT_FUSED = _os.environ.get('GV_DISTMULT_FUSED', '1') == '1'
 
 
 def distmult_fused_ok(embed, ld_e, w_rel, ld_w):
-    """THE shape rule of the fused DistMult sweep: a wave's 64 lanes hold four consecutive columns each (h <= 256, h % 4 == 0,
+    """THE shape rule of the fused DistMult sweep: a triplet's 16 lanes hold up to four float4 columns each (h <= 256, h % 4 == 0,
     16-B aligned rows).  Everything else (h = 500 of BASELINE configs[3] among it) keeps the three separate sweeps."""
     h = embed.shape[1]
     return (DISTMULT_FUSED and h % 4 == 0 and h <= 256 and ld_e % 4 == 0 and ld_w % 4 == 0
