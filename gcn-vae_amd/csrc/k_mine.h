@@ -1,12 +1,24 @@
-// What the whole-graph miners share (gv_mine_scores in k_mine.hip, gv_transe_mine in k_transe_mine.hip): the ordered key, the
-// filter re-bucketed per (subject tile, object tile) -- count, scan, fill: three small kernels, integer atomics -- the per-relation
-// filter words of a 64 x 64 tile pair, and the EMIT / HIST epilogues.  A workgroup of either miner is 256 threads on one 64 x 64 tile
-// pair; a candidate is (local row rl, local column cl) of it.
+// What the whole-graph miners share (gv_mine_scores in k_mine.hip, gv_transe_mine in k_transe_mine.hip): everything about SELECTING
+// candidates.  A workgroup of either miner is 256 threads (or groups of 256) on one 64 x 64 (subject tile, object tile) pair; a
+// candidate is (local row rl, local column cl) of it under relation r, with a value the kernel computed its own way.
+//
+// Candidates: all (s, r, o) with s, o < n, less the listed triplets (filter), less s == o (exclude_self), less NaN values.  Each
+// has the ordered key of gv_topk_scores (sign-flip map, -0 -> +0, NaN -> 0 = never a candidate), larger = better; a distance d keys
+// as -d.  A kernel zeroes the keys of candidates outside the table or on an excluded diagonal (that depends on its layout), then:
+//   mine_gate  drops the keys this pass does not look at.
+//       EMIT  key >= key_min stays.
+//       HIST  keys whose top prefix_bits equal `prefix` stay.
+//   __ballot   a wave with no key left skips the rest: nearly every relation of nearly every tile in EMIT and refining HIST passes.
+//   mine_take  the filter, then
+//       EMIT  one wave-aggregated integer atomicAdd reserves slots on a 64-bit counter, (s, r, o, value bits) go out as plain
+//             16-byte vector stores while the slot is below the capacity; the counter keeps counting, so the host learns the true
+//             total.  Arrival order is arbitrary: the caller sorts.
+//       HIST  the key's next bin_bits index an LDS histogram that is flushed with integer atomics (mine_hist_flush); the host
+//             walks 12 + 10 + 10 bits to the key of the K-th best candidate (at most three such passes).
+// The filter: the (lo, hi, ent) ranges per key s * R + r are re-bucketed per tile pair first (mine_prepare), so a workgroup reads
+// ITS listed triplets once into LDS (mine_filter_load) and a relation without one -- nearly all of them -- costs one LDS flag
+// (mine_filter_relation).  No float atomics anywhere.
 #pragma once
-#include <limits.h>
-
-#include <algorithm>
-
 #include "common.h"
 
 namespace gv {
@@ -27,91 +39,35 @@ __device__ __forceinline__ float mine_key_logit(unsigned o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-// ---- the filter, re-bucketed per (subject tile, object tile): count, scan, fill ------------------------------------------
-struct MineFiltParams {
-    const int* lo;
-    const int* hi;
-    const int* ent;
-    int n_ent, n, num_rels, o_tiles;
-    int* cnt;                  // [tiles]: counts, then the fill cursors
-    int* ptr;                  // [tiles + 1]
-    unsigned* out;             // [n_ent]
+// ---- what a pass selects, as both kernels' parameter structs embed it ---------------------------------------------------------
+struct MineSelect {
+    int n, num_rels;
+    int rel_span;                      // relations per blockIdx.z
+    int exclude_self;
+    unsigned key_min;                  // EMIT
+    int prefix_bits, bin_bits;         // HIST
+    unsigned prefix;
+    const int* tile_ptr;               // [s_tiles * o_tiles + 1], NULL: no filter
+    const unsigned* tile_ent;
+    int4* out;
+    long long capacity;
+    unsigned long long* counter;
+    unsigned long long* hist;
 };
 
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_mine_filt(const MineFiltParams f) {
-    const long long keys = (long long)f.n * f.num_rels;
-    for (long long key = (long long)blockIdx.x * 256 + threadIdx.x; key < keys; key += (long long)gridDim.x * 256) {
-        const int lo = min(max(f.lo[key], 0), f.n_ent), hi = min(max(f.hi[key], lo), f.n_ent);
-        if (lo == hi) continue;
-        const int s = (int)(key / f.num_rels), r = (int)(key - (long long)s * f.num_rels);
-        for (int j = lo; j < hi; ++j) {
-            const int o = f.ent[j];
-            if (o < 0 || o >= f.n) continue;
-            const int tile = (s >> 6) * f.o_tiles + (o >> 6);
-            if (!FILL) atomicAdd(f.cnt + tile, 1);
-            else {
-                const int pos = atomicAdd(f.cnt + tile, 1);
-                if (pos >= 0 && pos < f.n_ent) f.out[pos] = ((unsigned)r << 12) | ((unsigned)(s & 63) << 6) | (unsigned)(o & 63);
-            }
-        }
-    }
-}
-
-// exclusive scan of the tile counts (one workgroup: a thread sums a contiguous slice, the slices are scanned in LDS)
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_mine_filt_scan(int* cnt, int* ptr, int tiles) {
-    __shared__ int part[THREADS];
-    const int t = threadIdx.x;
-    const int per = (tiles + THREADS - 1) / THREADS;
-    const int i0 = min(t * per, tiles), i1 = min(i0 + per, tiles);
-    int s = 0;
-    for (int i = i0; i < i1; ++i) s += cnt[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int run = 0;
-        for (int i = 0; i < THREADS; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        ptr[tiles] = run;
-    }
-    __syncthreads();
-    int run = part[t];
-    for (int i = i0; i < i1; ++i) {
-        const int v = cnt[i];
-        ptr[i] = run;
-        cnt[i] = run;          // the fill cursor
-        run += v;
-    }
-}
-
-inline int64_t mine_align16(int64_t b) { return (b + 15) / 16 * 16; }
-
+// ---- host side, compiled once (k_mine.hip) -----------------------------------------------------------------------------------
 // bytes of the re-bucketed filter of an n-entity table with n_filt_ent listed objects (0 for an empty table)
-inline int64_t mine_filter_workspace_bytes(int n, int n_filt_ent) {
-    if (n <= 0 || n_filt_ent < 0) return 0;
-    const int64_t tiles = (int64_t)((n + 63) / 64) * ((n + 63) / 64);
-    return mine_align16(tiles * 4) + mine_align16((tiles + 1) * 4) + mine_align16((int64_t)(n_filt_ent > 0 ? n_filt_ent : 1) * 4);
-}
+int64_t mine_filter_workspace_bytes(int n, int n_filt_ent);
 
-// the three launches; *tile_ptr [tiles + 1] and *tile_ent then point into the workspace.  false: a launch could not be queued.
-inline bool mine_filter_rebucket(const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int n,
-                                 int num_rels, void* workspace, hipStream_t st, const int** tile_ptr, const unsigned** tile_ent) {
-    const int tiles_1d = (n + 63) / 64, tiles = tiles_1d * tiles_1d;
-    char* ws = (char*)workspace;
-    MineFiltParams f{};
-    f.lo = filt_lo; f.hi = filt_hi; f.ent = filt_ent; f.n_ent = n_filt_ent; f.n = n; f.num_rels = num_rels; f.o_tiles = tiles_1d;
-    f.cnt = (int*)ws;
-    f.ptr = (int*)(ws + mine_align16((int64_t)tiles * 4));
-    f.out = (unsigned*)(ws + mine_align16((int64_t)tiles * 4) + mine_align16((int64_t)(tiles + 1) * 4));
-    if (fill_words(f.cnt, 0u, (size_t)tiles * 4, st) != hipSuccess) return false;
-    const long long keys = (long long)n * num_rels;
-    const unsigned fb = (unsigned)std::min<long long>((keys + 255) / 256, 65535);
-    hipLaunchKernelGGL(k_mine_filt<false>, dim3(fb), dim3(256), 0, st, f);
-    hipLaunchKernelGGL(k_mine_filt_scan<1024>, dim3(1), dim3(1024), 0, st, f.cnt, f.ptr, tiles);
-    hipLaunchKernelGGL(k_mine_filt<true>, dim3(fb), dim3(256), 0, st, f);
-    *tile_ptr = f.ptr; *tile_ent = f.out;
-    return true;
-}
+// What both entries do before their launch, `who` being the entry's name in every message: the checks of the arguments they share,
+// *sel filled (rel_span: about four workgroups per CU of the MI355X when the table has few tiles; the result does not depend on
+// it), the filter re-bucketed per tile pair into the workspace (count, scan, fill: three small kernels, integer atomics), the
+// counter (EMIT) or the histogram (HIST) cleared, *grid = (object tiles, subject tiles, relation spans).  GV_OK: launch, unless
+// n == 0 (nothing was queued, nothing is to be done).
+int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
+                 hipStream_t st, MineSelect* sel, dim3* grid);
 
 // ---- device side: a workgroup's share of the re-bucketed filter ---------------------------------------------------------------
 // its range of tile_ent, the first MINE_FL_CAP entries copied into flist (visible after the caller's next barrier)
@@ -137,7 +93,18 @@ __device__ __forceinline__ void mine_filter_relation(const unsigned* flist, cons
     }
 }
 
-// ---- device side: the two epilogues -------------------------------------------------------------------------------------------
+// ---- device side: gate, take, flush ------------------------------------------------------------------------------------------
+// the key when this pass looks at it, else 0
+template <bool HIST>
+__device__ __forceinline__ unsigned mine_gate(unsigned key, const MineSelect& sel) {
+    if (HIST) {
+        if (sel.prefix_bits && (key >> (32 - sel.prefix_bits)) != sel.prefix) key = 0u;
+    } else {
+        if (key < sel.key_min) key = 0u;
+    }
+    return key;
+}
+
 // EMIT, called by every lane of a wave together: one wave-aggregated integer atomicAdd reserves the slots of the lanes with `ok`,
 // (s, r, o, value bits) go out as one 16-byte store while the slot is below the capacity; the counter keeps counting.
 __device__ __forceinline__ void mine_emit(bool ok, int lane, int s, int r, int o, int value_bits, int4* out, long long capacity,
@@ -157,11 +124,26 @@ __device__ __forceinline__ void mine_emit(bool ok, int lane, int s, int r, int o
     }
 }
 
+// One gated key of candidate (rl, cl) of tile pair (m0, n0) under relation r, called by every lane of a wave together (key 0: this
+// lane has none): dropped when the relation's mask lists it (`listed`: the relation has listed triplets in this tile pair), else
+// counted in hist_s or emitted with value_bits.
+template <bool HIST>
+__device__ __forceinline__ void mine_take(unsigned key, int value_bits, int rl, int cl, int m0, int n0, int r, int lane, bool listed,
+                                          const unsigned long long* mask, unsigned* hist_s, const MineSelect& sel) {
+    bool ok = key != 0u;
+    if (listed && ok) ok = !((mask[rl] >> cl) & 1ull);
+    if (HIST) {
+        if (ok) atomicAdd(&hist_s[(key >> (32 - sel.prefix_bits - sel.bin_bits)) & ((1u << sel.bin_bits) - 1u)], 1u);
+    } else {
+        mine_emit(ok, lane, m0 + rl, r, n0 + cl, value_bits, sel.out, sel.capacity, sel.counter);
+    }
+}
+
 // HIST: the workgroup's LDS histogram into the global one (after a barrier)
-__device__ __forceinline__ void mine_hist_flush(const unsigned* hist_s, unsigned long long* hist, unsigned bin_mask, int t) {
-    for (int i = t; i <= (int)bin_mask; i += 256) {
+__device__ __forceinline__ void mine_hist_flush(const unsigned* hist_s, const MineSelect& sel, int t) {
+    for (int i = t; i < (1 << sel.bin_bits); i += 256) {
         const unsigned c = hist_s[i];
-        if (c) atomicAdd(hist + i, (unsigned long long)c);
+        if (c) atomicAdd(sel.hist + i, (unsigned long long)c);
     }
 }
 

@@ -12,16 +12,13 @@
 // needs k = 2 j + (l >> 5) for consecutive j, so ONE ds_read_b128 per operand feeds four MFMAs (row pitch kc + 4 floats: the
 // 16 lanes of a b128 group fall on 16 distinct 16-byte slots).
 //
-// Candidates: all (s, r, o) with s, o < n, less the listed triplets (filter), less s == o (exclude_self), less NaN logits.  Each
-// has the ordered key of gv_topk_scores (sign-flip map, -0 -> +0, NaN -> 0 = never a candidate), larger = better.  Two epilogues:
-//   EMIT  key >= key_min: one wave-aggregated integer atomicAdd reserves slots on a 64-bit counter, (s, r, o, logit) go out as
-//         plain 16-byte vector stores while the slot is below the capacity; the counter keeps counting, so the host learns the
-//         true total.  Arrival order is arbitrary: the caller sorts.
-//   HIST  keys whose top prefix_bits equal `prefix` are binned by their next bin_bits into an LDS histogram that is flushed with
-//         integer atomics; the host walks 12 + 10 + 10 bits to the key of the K-th best candidate (at most three such passes).
-// The filter is applied before either: the (lo, hi, ent) ranges per key s * R + r are re-bucketed per tile pair first (count,
-// scan, fill: three small kernels, integer atomics), so a workgroup reads ITS listed triplets once into LDS and a relation
-// without one -- nearly all of them -- costs one LDS flag.  No float atomics anywhere.
+// Candidates, keys, the filter and the EMIT / HIST epilogues: k_mine.h, which both miners share; a record's fourth word is the logit
+// (mine_key_logit of its key: -0 as +0).  This file is also the one home of what the two entries do on the host before their
+// launch (mine_prepare) and of the three small kernels that re-bucket the filter.
+#include <limits.h>
+
+#include <algorithm>
+
 #include "common.h"
 #include "k_mine.h"
 
@@ -35,20 +32,10 @@ struct MineParams {
     const float* e;
     const float* w;
     const float* bias;
-    int n, h, num_rels, ld_e, ld_w;
+    int h, ld_e, ld_w;
     int vec_e, vec_w;
     int kc, n_chunks;                  // chunk depth (multiple of 16) and count; one chunk: the tiles stay in LDS
-    int rel_span;                      // relations per blockIdx.z
-    int exclude_self;
-    unsigned key_min;                  // EMIT
-    int prefix_bits, bin_bits;         // HIST
-    unsigned prefix;
-    const int* tile_ptr;               // [s_tiles * o_tiles + 1], NULL: no filter
-    const unsigned* tile_ent;
-    int4* out;
-    long long capacity;
-    unsigned long long* counter;
-    unsigned long long* hist;
+    MineSelect sel;
 };
 
 // one 64-row tile of E, columns [k0, k0 + kc), into LDS: row pitch kc + 4, even k first, then odd k; zeros outside the table
@@ -106,34 +93,34 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    const int r0 = blockIdx.z * p.rel_span, r1 = min(r0 + p.rel_span, p.num_rels);
+    const MineSelect& sel = p.sel;
+    const int n = sel.n;
+    const int r0 = blockIdx.z * sel.rel_span, r1 = min(r0 + sel.rel_span, sel.num_rels);
     const bool resident = p.n_chunks == 1;
-    const bool diag = p.exclude_self && m0 == n0;
+    const bool diag = sel.exclude_self && m0 == n0;
     const float bv = p.bias ? *p.bias : 0.f;
 
     int f_base, f_cnt;
-    mine_filter_load(p.tile_ptr, p.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, t, &f_base, &f_cnt);
+    mine_filter_load(sel.tile_ptr, sel.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, t, &f_base, &f_cnt);
     if (t < 64) { fmask[0][t] = 0ull; fmask[1][t] = 0ull; fmask[2][t] = 0ull; }
     if (t < 3) fany[t] = 0;
     if (HIST)
         for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
     if (resident) {
-        mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, p.n, 0, p.h, kc);
-        mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, p.n, 0, p.h, kc);
+        mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, n, 0, p.h, kc);
+        mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, n, 0, p.h, kc);
         if (t < (kc >> 2) && r0 < r1) mine_store_w(Ws, kc, t, mine_load_w(p, r0, 4 * t));
     }
     __syncthreads();
 
     const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
-    const int shift = 32 - p.prefix_bits - p.bin_bits;
-    const unsigned bin_mask = (1u << p.bin_bits) - 1u;
 
     for (int r = r0; r < r1; ++r) {
         const int it = r - r0, fb = it % 3, wb = resident ? (it & 1) : 0;
         // this relation's listed triplets -> fmask[fb]; the buffer of the relation after it is cleared (last read two relations ago)
         if (t < 64) fmask[(it + 1) % 3][t] = 0ull;
         if (t == 64) fany[(it + 1) % 3] = 0;
-        mine_filter_relation(flist, p.tile_ent, f_base, f_cnt, r, t, fmask[fb], &fany[fb]);
+        mine_filter_relation(flist, sel.tile_ent, f_base, f_cnt, r, t, fmask[fb], &fany[fb]);
         float4 wnext = make_float4(0.f, 0.f, 0.f, 0.f);
         const bool w_pre = resident && t < (kc >> 2) && r + 1 < r1;
         if (w_pre) wnext = mine_load_w(p, r + 1, 4 * t);          // flies under the MFMA chain
@@ -145,8 +132,8 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
             const int k0 = c * kc;
             if (!resident) {
                 __syncthreads();
-                mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, p.n, k0, p.h, kc);
-                mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, p.n, k0, p.h, kc);
+                mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, n, k0, p.h, kc);
+                mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, n, k0, p.h, kc);
                 if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
                 __syncthreads();
             }
@@ -172,41 +159,170 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
         if (w_pre) mine_store_w(Ws + ((it + 1) & 1) * (kc + 4), kc, t, wnext);
         __syncthreads();
 
-        // ---- epilogue: C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-        const int cl = wn + l31, col = n0 + cl;
+        // ---- epilogue (k_mine.h): C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+        const int cl = wn + l31;
         unsigned key[16];
         bool want = false;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
             unsigned k = mine_key(acc[i] + bv);
-            if (m0 + rl >= p.n || col >= p.n || (diag && rl == cl)) k = 0u;
-            if (HIST) {
-                if (p.prefix_bits && (k >> (32 - p.prefix_bits)) != p.prefix) k = 0u;
-            } else {
-                if (k < p.key_min) k = 0u;
-            }
-            key[i] = k;
-            want = want || k != 0u;
+            if (m0 + rl >= n || n0 + cl >= n || (diag && rl == cl)) k = 0u;
+            key[i] = mine_gate<HIST>(k, sel);
+            want = want || key[i] != 0u;
         }
-        if (__ballot(want) == 0ull) continue;                    // nearly every relation of nearly every tile in EMIT and refining HIST passes
-        const bool anyf = fany[fb] != 0;
+        if (__ballot(want) == 0ull) continue;
+        const bool listed = fany[fb] != 0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
-            bool ok = key[i] != 0u;
-            if (anyf && ok) ok = !((fmask[fb][rl] >> cl) & 1ull);
-            if (HIST) {
-                if (ok) atomicAdd(&hist_s[(key[i] >> shift) & bin_mask], 1u);
-            } else {
-                mine_emit(ok, lane, m0 + rl, r, col, __float_as_int(mine_key_logit(key[i])), p.out, p.capacity, p.counter);
-            }
+            mine_take<HIST>(key[i], __float_as_int(mine_key_logit(key[i])), rl, cl, m0, n0, r, lane, listed, fmask[fb], hist_s, sel);
         }
     }
     if (HIST) {
         __syncthreads();
-        mine_hist_flush(hist_s, p.hist, bin_mask, t);
+        mine_hist_flush(hist_s, sel, t);
     }
+}
+
+// ---- the filter, re-bucketed per (subject tile, object tile): count, scan, fill ------------------------------------------
+struct MineFiltParams {
+    const int* lo;
+    const int* hi;
+    const int* ent;
+    int n_ent, n, num_rels, o_tiles;
+    int* cnt;                  // [tiles]: counts, then the fill cursors
+    int* ptr;                  // [tiles + 1]
+    unsigned* out;             // [n_ent]
+};
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_mine_filt(const MineFiltParams f) {
+    const long long keys = (long long)f.n * f.num_rels;
+    for (long long key = (long long)blockIdx.x * 256 + threadIdx.x; key < keys; key += (long long)gridDim.x * 256) {
+        const int lo = min(max(f.lo[key], 0), f.n_ent), hi = min(max(f.hi[key], lo), f.n_ent);
+        if (lo == hi) continue;
+        const int s = (int)(key / f.num_rels), r = (int)(key - (long long)s * f.num_rels);
+        for (int j = lo; j < hi; ++j) {
+            const int o = f.ent[j];
+            if (o < 0 || o >= f.n) continue;
+            const int tile = (s >> 6) * f.o_tiles + (o >> 6);
+            if (!FILL) atomicAdd(f.cnt + tile, 1);
+            else {
+                const int pos = atomicAdd(f.cnt + tile, 1);
+                if (pos >= 0 && pos < f.n_ent) f.out[pos] = ((unsigned)r << 12) | ((unsigned)(s & 63) << 6) | (unsigned)(o & 63);
+            }
+        }
+    }
+}
+
+// exclusive scan of the tile counts (one workgroup: a thread sums a contiguous slice, the slices are scanned in LDS)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_mine_filt_scan(int* cnt, int* ptr, int tiles) {
+    __shared__ int part[THREADS];
+    const int t = threadIdx.x;
+    const int per = (tiles + THREADS - 1) / THREADS;
+    const int i0 = min(t * per, tiles), i1 = min(i0 + per, tiles);
+    int s = 0;
+    for (int i = i0; i < i1; ++i) s += cnt[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int i = 0; i < THREADS; ++i) { const int v = part[i]; part[i] = run; run += v; }
+        ptr[tiles] = run;
+    }
+    __syncthreads();
+    int run = part[t];
+    for (int i = i0; i < i1; ++i) {
+        const int v = cnt[i];
+        ptr[i] = run;
+        cnt[i] = run;          // the fill cursor
+        run += v;
+    }
+}
+
+static int64_t mine_align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+int64_t mine_filter_workspace_bytes(int n, int n_filt_ent) {
+    if (n <= 0 || n_filt_ent < 0) return 0;
+    const int64_t tiles = (int64_t)((n + 63) / 64) * ((n + 63) / 64);
+    return mine_align16(tiles * 4) + mine_align16((tiles + 1) * 4) + mine_align16((int64_t)(n_filt_ent > 0 ? n_filt_ent : 1) * 4);
+}
+
+// the three launches; *tile_ptr [tiles + 1] and *tile_ent then point into the workspace.  false: a launch could not be queued.
+static bool mine_filter_rebucket(const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int n,
+                                 int num_rels, void* workspace, hipStream_t st, const int** tile_ptr, const unsigned** tile_ent) {
+    const int tiles_1d = (n + 63) / 64, tiles = tiles_1d * tiles_1d;
+    char* ws = (char*)workspace;
+    MineFiltParams f{};
+    f.lo = filt_lo; f.hi = filt_hi; f.ent = filt_ent; f.n_ent = n_filt_ent; f.n = n; f.num_rels = num_rels; f.o_tiles = tiles_1d;
+    f.cnt = (int*)ws;
+    f.ptr = (int*)(ws + mine_align16((int64_t)tiles * 4));
+    f.out = (unsigned*)(ws + mine_align16((int64_t)tiles * 4) + mine_align16((int64_t)(tiles + 1) * 4));
+    if (fill_words(f.cnt, 0u, (size_t)tiles * 4, st) != hipSuccess) return false;
+    const long long keys = (long long)n * num_rels;
+    const unsigned fb = (unsigned)std::min<long long>((keys + 255) / 256, 65535);
+    hipLaunchKernelGGL(k_mine_filt<false>, dim3(fb), dim3(256), 0, st, f);
+    hipLaunchKernelGGL(k_mine_filt_scan<1024>, dim3(1), dim3(1024), 0, st, f.cnt, f.ptr, tiles);
+    hipLaunchKernelGGL(k_mine_filt<true>, dim3(fb), dim3(256), 0, st, f);
+    *tile_ptr = f.ptr; *tile_ent = f.out;
+    return true;
+}
+
+int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
+                 hipStream_t st, MineSelect* sel, dim3* grid) {
+    GV_REQUIRE(n >= 0 && num_rels > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: n=%d num_rels=%d n_filt_ent=%d", who, n, num_rels,
+               n_filt_ent);
+    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "%s: unknown mode %d", who, mode);
+    GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "%s: n * num_rels = %lld reaches 2^31", who,
+               (long long)n * num_rels);
+    GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "%s: more than %d relations", who, 1 << MINE_REL_BITS);
+    GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "%s: n=%d: more than 2^31 tile pairs", who, n);
+    if (mode == GV_MINE_EMIT)
+        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "%s: capacity=%lld outside [0, 2^31)", who, (long long)capacity);
+    else
+        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
+                       (prefix >> prefix_bits) == 0u,
+                   GV_ERR_SHAPE, "%s: prefix_bits=%d prefix=%u bin_bits=%d out of range", who, prefix_bits, prefix, bin_bits);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "%s: filt_lo / filt_hi / filt_ent must be all given or all NULL", who);
+    if (n == 0) return GV_OK;
+    if (mode == GV_MINE_EMIT) {
+        GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "%s: NULL output", who);
+        GV_REQUIRE(aligned16(out), GV_ERR_SHAPE, "%s: out is not 16-byte aligned", who);        // int4 records
+    } else {
+        GV_REQUIRE(hist, GV_ERR_NULL, "%s: NULL histogram", who);
+    }
+    const bool filtered = filt_lo != nullptr;
+    if (filtered) {
+        GV_REQUIRE(workspace, GV_ERR_NULL, "%s: a filter needs the workspace", who);
+        GV_REQUIRE(aligned16(workspace), GV_ERR_WORKSPACE, "%s: the workspace is not 16-byte aligned", who);
+        GV_REQUIRE(workspace_bytes >= mine_filter_workspace_bytes(n, n_filt_ent), GV_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes",
+                   who, (long long)workspace_bytes, (long long)mine_filter_workspace_bytes(n, n_filt_ent));
+    }
+    const int tiles_1d = (n + 63) / 64;
+    const int tiles = tiles_1d * tiles_1d;
+    long long spans = (4LL * 256 + tiles - 1) / tiles;
+    spans = std::max(1LL, std::min(spans, (long long)num_rels));
+    *sel = MineSelect{};
+    sel->n = n; sel->num_rels = num_rels;
+    sel->rel_span = (int)((num_rels + spans - 1) / spans);
+    sel->exclude_self = exclude_self ? 1 : 0;
+    sel->key_min = key_min; sel->prefix_bits = prefix_bits; sel->bin_bits = bin_bits; sel->prefix = prefix;
+    sel->out = (int4*)out; sel->capacity = capacity;
+    sel->counter = (unsigned long long*)counter; sel->hist = (unsigned long long*)hist;
+    *grid = dim3(tiles_1d, tiles_1d, (num_rels + sel->rel_span - 1) / sel->rel_span);
+
+    char fill[64];
+    snprintf(fill, sizeof fill, "%s(fill)", who);
+    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &sel->tile_ptr, &sel->tile_ent))
+        return launch_status(fill);
+    const bool emit = mode == GV_MINE_EMIT;
+    if (fill_words(emit ? (void*)counter : (void*)hist, 0u, emit ? 8 : (size_t)8 << bin_bits, st) != hipSuccess) return launch_status(fill);
+    return GV_OK;
 }
 
 }  // namespace gv
@@ -225,69 +341,31 @@ extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w
                               int h, void* stream) {
     GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_mine_scores: n=%d num_rels=%d h=%d n_filt_ent=%d",
                n, num_rels, h, n_filt_ent);
-    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "gv_mine_scores: unknown mode %d", mode);
     GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_mine_scores: leading dimension too small (ld_e=%d ld_w=%d h=%d)", ld_e, ld_w, h);
-    GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "gv_mine_scores: n * num_rels = %lld reaches 2^31",
-               (long long)n * num_rels);
-    GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "gv_mine_scores: more than %d relations", 1 << MINE_REL_BITS);
-    GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "gv_mine_scores: n=%d: more than 2^31 tile pairs", n);
-    if (mode == GV_MINE_EMIT)
-        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "gv_mine_scores: capacity=%lld outside [0, 2^31)",
-                   (long long)capacity);
-    else
-        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
-                       (prefix >> prefix_bits) == 0u,
-                   GV_ERR_SHAPE, "gv_mine_scores: prefix_bits=%d prefix=%u bin_bits=%d out of range", prefix_bits, prefix, bin_bits);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_mine_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    if (n == 0) return GV_OK;
-    GV_REQUIRE(e && w, GV_ERR_NULL, "gv_mine_scores: NULL table");
-    if (mode == GV_MINE_EMIT) GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "gv_mine_scores: NULL output");
-    else GV_REQUIRE(hist, GV_ERR_NULL, "gv_mine_scores: NULL histogram");
-    const bool filtered = filt_lo != nullptr;
-    if (filtered) {
-        GV_REQUIRE(workspace, GV_ERR_NULL, "gv_mine_scores: a filter needs the workspace");
-        GV_REQUIRE(workspace_bytes >= gv_mine_scores_workspace_bytes(n, num_rels, n_filt_ent), GV_ERR_WORKSPACE,
-                   "gv_mine_scores: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                   (long long)gv_mine_scores_workspace_bytes(n, num_rels, n_filt_ent));
-    }
+    GV_REQUIRE(n == 0 || (e && w), GV_ERR_NULL, "gv_mine_scores: NULL table");
     hipStream_t st = (hipStream_t)stream;
-    const int tiles_1d = (n + 63) / 64;
-    const int tiles = tiles_1d * tiles_1d;
-
     MineParams p{};
+    dim3 grid;
+    const int rc = mine_prepare("gv_mine_scores", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
+                                prefix_bits, prefix, bin_bits, out, capacity, counter, hist, workspace, workspace_bytes, st, &p.sel, &grid);
+    if (rc != GV_OK || n == 0) return rc;
     p.e = e; p.w = w; p.bias = bias;
-    p.n = n; p.h = h; p.num_rels = num_rels; p.ld_e = ld_e; p.ld_w = ld_w;
+    p.h = h; p.ld_e = ld_e; p.ld_w = ld_w;
     p.vec_e = aligned16(e) && (ld_e % 4 == 0);
     p.vec_w = aligned16(w) && (ld_w % 4 == 0);
     const int h16 = (h + 15) / 16 * 16;
     p.kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
     p.n_chunks = (h + p.kc - 1) / p.kc;
-    // relation spans: about four workgroups per CU of the MI355X when the table has few tiles (the result does not depend on it)
-    long long spans = (4LL * 256 + tiles - 1) / tiles;
-    spans = std::max(1LL, std::min(spans, (long long)num_rels));
-    p.rel_span = (int)((num_rels + spans - 1) / spans);
-    const int n_spans = (num_rels + p.rel_span - 1) / p.rel_span;
-    p.exclude_self = exclude_self ? 1 : 0;
-    p.key_min = key_min; p.prefix_bits = prefix_bits; p.bin_bits = bin_bits; p.prefix = prefix;
-    p.out = (int4*)out; p.capacity = capacity;
-    p.counter = (unsigned long long*)counter; p.hist = (unsigned long long*)hist;
-
-    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &p.tile_ptr, &p.tile_ent))
-        return launch_status("gv_mine_scores(fill)");
     const int lds = (2 * 64 * (p.kc + 4) + 2 * (p.kc + 4)) * (int)sizeof(float);
     const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);
-    dim3 grid(tiles_1d, tiles_1d, n_spans), block(256);
     if (mode == GV_MINE_EMIT) {
-        if (fill_words(counter, 0u, 8, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
         static unsigned long long raised = 0;
         if (!raise_dynamic_lds((const void*)k_mine<false>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine<false>, grid, block, lds, st, p);
+        hipLaunchKernelGGL(k_mine<false>, grid, dim3(256), lds, st, p);
     } else {
-        if (fill_words(hist, 0u, (size_t)8 << bin_bits, st) != hipSuccess) return launch_status("gv_mine_scores(fill)");
         static unsigned long long raised = 0;
         if (!raise_dynamic_lds((const void*)k_mine<true>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine<true>, grid, block, lds, st, p);
+        hipLaunchKernelGGL(k_mine<true>, grid, dim3(256), lds, st, p);
     }
     return launch_status("gv_mine_scores");
 }

@@ -19,8 +19,11 @@
 // (checked every TM_CHECK columns; NaN never compares greater, so NaN pairs run to the end and are dropped by their key).  What a
 // pair's key is compared with is unchanged, so the result is too.
 //
-// Candidates, keys (ordered_u32(-d): larger = nearer, 0 = NaN only), the filter and the EMIT / HIST epilogues are those of
-// gv_mine_scores (k_mine.h); a record's fourth word is the bits of d itself (never -0: the sums start at +0 and add |.| or squares).
+// Candidates, keys (those of -d: larger = nearer, 0 = NaN only), the filter and the EMIT / HIST epilogues: k_mine.h, which both
+// miners share, as they share the host set-up before the launch (mine_prepare, k_mine.hip); a record's fourth word is the bits of d
+// itself (never -0: the sums start at +0 and add |.| or squares).
+#include <algorithm>
+
 #include "common.h"
 #include "k_mine.h"
 #include "k_transe.h"
@@ -36,19 +39,9 @@ constexpr int TM_THREADS = 256 * TM_GROUPS;
 struct TeMineParams {
     const float* en;
     const float* rn;
-    int n, dim, num_rels;
+    int dim;
     int kc, n_chunks;                  // chunk width and count; one chunk: the tiles stay in LDS
-    int rel_span;                      // relations per blockIdx.z
-    int exclude_self;
-    unsigned key_min;                  // EMIT
-    int prefix_bits, bin_bits;         // HIST
-    unsigned prefix;
-    const int* tile_ptr;               // [s_tiles * o_tiles + 1], NULL: no filter
-    const unsigned* tile_ent;
-    int4* out;
-    long long capacity;
-    unsigned long long* counter;
-    unsigned long long* hist;
+    MineSelect sel;
 };
 
 // columns [k0, k0 + kn) of rows row0 .. row0 + 63 of en into dst [kn][TM_LD]; zeros past the table
@@ -72,12 +65,14 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     const int t = threadIdx.x, g = t >> 8, tl = t & 255, lane = t & 63, tx = tl & 15, ty = tl >> 4;
     float* Rs = Bs + kc * TM_LD + g * kc;                // [TM_GROUPS][kc] each group's relation row
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
-    const int r0 = blockIdx.z * p.rel_span, r1 = min(r0 + p.rel_span, p.num_rels);
+    const MineSelect& sel = p.sel;
+    const int n = sel.n;
+    const int r0 = blockIdx.z * sel.rel_span, r1 = min(r0 + sel.rel_span, sel.num_rels);
     const bool resident = p.n_chunks == 1;
-    const bool diag = p.exclude_self && m0 == n0;
+    const bool diag = sel.exclude_self && m0 == n0;
 
     // the largest distance this pass looks at: keys below kmin are dropped by the epilogue whatever their value
-    const unsigned kmin = HIST ? (p.prefix_bits ? p.prefix << (32 - p.prefix_bits) : 0u) : p.key_min;
+    const unsigned kmin = HIST ? (sel.prefix_bits ? sel.prefix << (32 - sel.prefix_bits) : 0u) : sel.key_min;
     float bound = INFINITY;                              // in the accumulator's unit: the distance, or (p = 2) its square, rounded up
     if (kmin > 0x007fffffu) {                            // above the key of +inf
         const float dmax = -mine_key_logit(kmin);
@@ -86,15 +81,13 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     }
 
     int f_base, f_cnt;
-    mine_filter_load(p.tile_ptr, p.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, tl, &f_base, &f_cnt);   // every group: the same words
+    mine_filter_load(sel.tile_ptr, sel.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, tl, &f_base, &f_cnt);   // every group: the same words
     if (HIST)
         for (int i = t; i < (1 << MINE_HIST_BITS); i += TM_THREADS) hist_s[i] = 0u;
     if (resident) {
-        tm_stage(As, p.en, m0, p.n, p.dim, 0, p.dim);
-        tm_stage(Bs, p.en, n0, p.n, p.dim, 0, p.dim);
+        tm_stage(As, p.en, m0, n, p.dim, 0, p.dim);
+        tm_stage(Bs, p.en, n0, n, p.dim, 0, p.dim);
     }
-    const int shift = 32 - p.prefix_bits - p.bin_bits;
-    const unsigned bin_mask = (1u << p.bin_bits) - 1u;
     const float* a_ptr = As + 4 * ty;
     const float* b_ptr = Bs + 4 * tx;
 
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
         if (resident && live)
             for (int k = tl; k < p.dim; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k];
         __syncthreads();
-        if (live) mine_filter_relation(flist, p.tile_ent, f_base, f_cnt, r, tl, fmask[g], &fany[g]);
+        if (live) mine_filter_relation(flist, sel.tile_ent, f_base, f_cnt, r, tl, fmask[g], &fany[g]);
 
         float acc[4][4];
 #pragma unroll
@@ -120,8 +113,8 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
             const int k0 = c * kc, kn = min(kc, p.dim - k0);
             if (!resident) {
                 __syncthreads();
-                tm_stage(As, p.en, m0, p.n, p.dim, k0, kn);
-                tm_stage(Bs, p.en, n0, p.n, p.dim, k0, kn);
+                tm_stage(As, p.en, m0, n, p.dim, k0, kn);
+                tm_stage(Bs, p.en, n0, n, p.dim, k0, kn);
                 if (live)
                     for (int k = tl; k < kn; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
                 __syncthreads();
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
         }
         __syncthreads();                                 // fmask / fany of this round are complete
 
-        // ---- epilogue: lane (tx, ty) holds subjects 4 ty + a, objects 4 tx + b
+        // ---- epilogue (k_mine.h): lane (tx, ty) holds subjects 4 ty + a, objects 4 tx + b
         unsigned key[4][4];
         bool want = false;
 #pragma unroll
@@ -159,34 +152,21 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
                 if (P == 2) acc[a][b] = sqrtf(acc[a][b]);
                 const int rl = 4 * ty + a, cl = 4 * tx + b;
                 unsigned k = mine_key(-acc[a][b]);
-                if (!live || m0 + rl >= p.n || n0 + cl >= p.n || (diag && rl == cl)) k = 0u;
-                if (HIST) {
-                    if (p.prefix_bits && (k >> (32 - p.prefix_bits)) != p.prefix) k = 0u;
-                } else {
-                    if (k < p.key_min) k = 0u;
-                }
-                key[a][b] = k;
-                want = want || k != 0u;
+                if (!live || m0 + rl >= n || n0 + cl >= n || (diag && rl == cl)) k = 0u;
+                key[a][b] = mine_gate<HIST>(k, sel);
+                want = want || key[a][b] != 0u;
             }
-        if (__ballot(want) == 0ull) continue;            // nearly every relation of nearly every tile in EMIT and refining HIST passes
-        const bool anyf = fany[g] != 0;
+        if (__ballot(want) == 0ull) continue;
+        const bool listed = fany[g] != 0;
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int rl = 4 * ty + a, cl = 4 * tx + b;
-                bool ok = key[a][b] != 0u;
-                if (anyf && ok) ok = !((fmask[g][rl] >> cl) & 1ull);
-                if (HIST) {
-                    if (ok) atomicAdd(&hist_s[(key[a][b] >> shift) & bin_mask], 1u);
-                } else {
-                    mine_emit(ok, lane, m0 + rl, r, n0 + cl, __float_as_int(acc[a][b]), p.out, p.capacity, p.counter);
-                }
-            }
+            for (int b = 0; b < 4; ++b)
+                mine_take<HIST>(key[a][b], __float_as_int(acc[a][b]), 4 * ty + a, 4 * tx + b, m0, n0, r, lane, listed, fmask[g], hist_s, sel);
     }
     if (HIST) {
         __syncthreads();
-        if (t < 256) mine_hist_flush(hist_s, p.hist, bin_mask, t);
+        if (t < 256) mine_hist_flush(hist_s, sel, t);
     }
 }
 
@@ -211,67 +191,20 @@ extern "C" int gv_transe_mine(const float* en, const float* rn, int n, int num_r
                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
                               uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                               uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes, void* stream) {
-    GV_REQUIRE(n >= 0 && num_rels > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_transe_mine: n=%d num_rels=%d n_filt_ent=%d", n, num_rels,
-               n_filt_ent);
     GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
                "gv_transe_mine: dim=%d (1..%d) p_norm=%d (1 or 2)", dim, GV_TRANSE_MAX_DIM, p_norm);
-    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "gv_transe_mine: unknown mode %d", mode);
-    GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "gv_transe_mine: n * num_rels = %lld reaches 2^31",
-               (long long)n * num_rels);
-    GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "gv_transe_mine: more than %d relations", 1 << MINE_REL_BITS);
-    GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "gv_transe_mine: n=%d: more than 2^31 tile pairs", n);
-    if (mode == GV_MINE_EMIT)
-        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "gv_transe_mine: capacity=%lld outside [0, 2^31)",
-                   (long long)capacity);
-    else
-        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
-                       (prefix >> prefix_bits) == 0u,
-                   GV_ERR_SHAPE, "gv_transe_mine: prefix_bits=%d prefix=%u bin_bits=%d out of range", prefix_bits, prefix, bin_bits);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_transe_mine: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    if (n == 0) return GV_OK;
-    GV_REQUIRE(en && rn, GV_ERR_NULL, "gv_transe_mine: NULL table");
-    if (mode == GV_MINE_EMIT) {
-        GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "gv_transe_mine: NULL output");
-        GV_REQUIRE(aligned16(out), GV_ERR_SHAPE, "gv_transe_mine: out is not 16-byte aligned");
-    } else {
-        GV_REQUIRE(hist, GV_ERR_NULL, "gv_transe_mine: NULL histogram");
-    }
-    const bool filtered = filt_lo != nullptr;
-    if (filtered) {
-        GV_REQUIRE(workspace, GV_ERR_NULL, "gv_transe_mine: a filter needs the workspace");
-        GV_REQUIRE(aligned16(workspace), GV_ERR_WORKSPACE, "gv_transe_mine: the workspace is not 16-byte aligned");
-        GV_REQUIRE(workspace_bytes >= gv_transe_mine_workspace_bytes(n, num_rels, n_filt_ent), GV_ERR_WORKSPACE,
-                   "gv_transe_mine: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                   (long long)gv_transe_mine_workspace_bytes(n, num_rels, n_filt_ent));
-    }
+    GV_REQUIRE(n <= 0 || (en && rn), GV_ERR_NULL, "gv_transe_mine: NULL table");
     hipStream_t st = (hipStream_t)stream;
-    const int tiles_1d = (n + 63) / 64;
-    const int tiles = tiles_1d * tiles_1d;
-
     TeMineParams p{};
-    p.en = en; p.rn = rn; p.n = n; p.dim = dim; p.num_rels = num_rels;
+    dim3 grid;
+    const int rc = mine_prepare("gv_transe_mine", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
+                                prefix_bits, prefix, bin_bits, out, capacity, counter, hist, workspace, workspace_bytes, st, &p.sel, &grid);
+    if (rc != GV_OK || n == 0) return rc;
+    p.en = en; p.rn = rn; p.dim = dim;
     p.kc = std::min(dim, TM_KC_MAX);
     p.n_chunks = (dim + p.kc - 1) / p.kc;
-    // relation spans: about four workgroups per CU of the MI355X when the table has few tiles (the result does not depend on it)
-    long long spans = (4LL * 256 + tiles - 1) / tiles;
-    spans = std::max(1LL, std::min(spans, (long long)num_rels));
-    p.rel_span = (int)((num_rels + spans - 1) / spans);
-    const int n_spans = (num_rels + p.rel_span - 1) / p.rel_span;
-    p.exclude_self = exclude_self ? 1 : 0;
-    p.key_min = key_min; p.prefix_bits = prefix_bits; p.bin_bits = bin_bits; p.prefix = prefix;
-    p.out = (int4*)out; p.capacity = capacity;
-    p.counter = (unsigned long long*)counter; p.hist = (unsigned long long*)hist;
-
-    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &p.tile_ptr, &p.tile_ent))
-        return launch_status("gv_transe_mine(fill)");
     const int lds = (2 * TM_LD + TM_GROUPS) * p.kc * (int)sizeof(float);
     const int lds_max = (2 * TM_LD + TM_GROUPS) * TM_KC_MAX * (int)sizeof(float);
-    const dim3 grid(tiles_1d, tiles_1d, n_spans);
-    if (mode == GV_MINE_EMIT) {
-        if (fill_words(counter, 0u, 8, st) != hipSuccess) return launch_status("gv_transe_mine(fill)");
-        return p_norm == 1 ? tm_launch<1, false>(p, grid, lds, lds_max, st) : tm_launch<2, false>(p, grid, lds, lds_max, st);
-    }
-    if (fill_words(hist, 0u, (size_t)8 << bin_bits, st) != hipSuccess) return launch_status("gv_transe_mine(fill)");
+    if (mode == GV_MINE_EMIT) return p_norm == 1 ? tm_launch<1, false>(p, grid, lds, lds_max, st) : tm_launch<2, false>(p, grid, lds, lds_max, st);
     return p_norm == 1 ? tm_launch<1, true>(p, grid, lds, lds_max, st) : tm_launch<2, true>(p, grid, lds, lds_max, st);
 }

@@ -808,6 +808,43 @@ def _mine_args(k, threshold, max_results):
     return k, threshold, max_results
 
 
+def _mine_tables(a, name_a, b, name_b, prepare=None):
+    """The two tables of a mining call, checked: 2-D tensors, each through ``prepare(t, name)`` when the wrapper vets its tables this
+    early, of one width."""
+    for name, t in ((name_a, a), (name_b, b)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if prepare is not None:
+        a, b = prepare(a, name_a), prepare(b, name_b)
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f'{name_a} / {name_b} width mismatch')
+    return a, b
+
+
+def _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=None):
+    """``N * R`` below 2**31 and the filter given whole or not at all; between the two, where ``mine_scores`` has always made them,
+    the checks of ``args`` = (k, threshold, max_results), which are returned checked."""
+    if n * num_rels >= 2 ** 31:
+        raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
+    if args is not None:
+        args = _mine_args(*args)
+    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    return args
+
+
+def _mine_device(a, name_a, b, name_b):
+    """(the device both tables are on, the empty result when there is no entity or else None)"""
+    dev = a.device
+    if b.device != dev:
+        raise ValueError(f'{name_b} must be on the device of {name_a} ({dev})')
+    if a.shape[0]:
+        return dev, None
+    return dev, (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+                 {'count': 0, 'passes': 0})
+
+
 def _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev, workspace_bytes):
     """The filter of a mining call as the kernels take it: (lo32, hi32, ent32, n_ent, workspace, workspace bytes), all None / 0
     without one.  ``workspace_bytes``: the entry point that sizes the re-bucketed filter."""
@@ -902,28 +939,16 @@ def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt
     histogram passes over the ordered key's bits (12 + 10 + 10), then emits once."""
     if (k is None) == (threshold is None):
         raise ValueError('give exactly one of k and threshold')
-    for name, t in (('emb', emb), ('w', w)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise TypeError(f'{name}: expected a 2-D tensor')
-    if emb.shape[1] != w.shape[1]:
-        raise ValueError('emb / w width mismatch')
+    _mine_tables(emb, 'emb', w, 'w')
     n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
     if num_rels < 1 or h < 1:
         raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
-    if n * num_rels >= 2 ** 31:
-        raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
-    k, threshold, max_results = _mine_args(k, threshold, max_results)
-    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
-    if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+    k, threshold, max_results = _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=(k, threshold, max_results))
     emb, ld_e = _row_major(emb, 'emb')
     w, ld_w = _row_major(w, 'w')
-    dev = emb.device
-    if w.device != dev:
-        raise ValueError(f'w must be on the device of emb ({dev})')
-    if n == 0:
-        return (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
-                {'count': 0, 'passes': 0})
+    dev, nothing = _mine_device(emb, 'emb', w, 'w')
+    if nothing is not None:
+        return nothing
     lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
                                                                lib.load().gv_mine_scores_workspace_bytes)
     if bias is not None:
@@ -3292,27 +3317,15 @@ def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi
     (s, r, o).  Returns ``(triplets int64 (n, 3), distances float32 (n,), info)``; ``info['count']``, ``info['passes']`` and
     ``MineOverflow`` as in ``mine_scores``, with "at or below the distance" for "at or above the logit"."""
     k, threshold, max_results = _mine_args(k, threshold, max_results)
-    for name, t in (('en', en), ('rn', rn)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise TypeError(f'{name}: expected a 2-D tensor')
-    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
-    if en.shape[1] != rn.shape[1]:
-        raise ValueError('en / rn width mismatch')
+    en, rn = _mine_tables(en, 'en', rn, 'rn', prepare=lambda t, name: _table(t.contiguous(), name))
     p_norm = _p_norm(p_norm)
     n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
     if num_rels < 1:
         raise ValueError('need at least one relation')
-    if n * num_rels >= 2 ** 31:
-        raise ValueError(f'N * R = {n * num_rels} reaches 2**31')
-    given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
-    if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
-    dev = en.device
-    if rn.device != dev:
-        raise ValueError(f'rn must be on the device of en ({dev})')
-    if n == 0:
-        return (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
-                {'count': 0, 'passes': 0})
+    _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    dev, nothing = _mine_device(en, 'en', rn, 'rn')
+    if nothing is not None:
+        return nothing
     lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
                                                                lib.load().gv_transe_mine_workspace_bytes)
 

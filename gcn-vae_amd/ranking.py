@@ -418,6 +418,41 @@ def _mine_args(k, threshold, max_results):
         raise ValueError(f'max_results must be >= 1, got {max_results}')
 
 
+def _mine_from_values(val, ascending, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                     max_results=ops.MINE_MAX_RESULTS):
+    """The mining rule, once, on a materialised tensor ``val[r, s, o]`` (R, N, N) in plain torch: logits, largest first, or
+    (``ascending``) distances, smallest first.  ``mine_from_scores`` and ``transe.mine_from_distances`` state it for each."""
+    _mine_args(k, threshold, max_results)
+    num_rels, n = val.shape[0], val.shape[1]
+    val = val.to(torch.float32) + 0.0
+    within = torch.le if ascending else torch.ge          # at the bound or better
+    cand = ~torch.isnan(val)
+    if exclude_self:
+        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
+    if filt_lo is not None and n:
+        listed = _listed_mask(filt_lo, filt_hi, filt_ent, n * num_rels, n, val.device)      # rows: key s * R + r
+        cand &= ~listed.view(n, num_rels, n).permute(1, 0, 2)
+    if k is not None:
+        vals = val[cand]
+        if vals.numel() > int(k):
+            cand &= within(val, torch.topk(vals, int(k), largest=not ascending).values[-1])
+    else:
+        cand &= within(val, float(threshold))
+    r, s, o = torch.nonzero(cand, as_tuple=True)
+    return _mine_finish(torch.stack([s, r, o], 1), val[cand], {'passes': 0}, k, threshold, max_results, n, num_rels, ascending)
+
+
+def _mine_finish(trip, values, info, k, threshold, max_results, n, num_rels, ascending):
+    """The end of both host routes: the candidates at the bound or better into the rule's order, counted, capped."""
+    if k is not None:
+        trip, values, info['count'] = ops.mine_select(trip, values, int(k), int(max_results), n, num_rels, ascending)
+        return trip, values, info
+    info['count'] = int(values.numel())
+    if info['count'] > int(max_results):
+        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
+    return ops.mine_order(trip, values, n, num_rels, ascending) + (info,)
+
+
 def mine_from_scores(score, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
                      max_results=ops.MINE_MAX_RESULTS):
     """The mining rule of ``ops.mine_scores`` on a materialised tensor ``score[r, s, o]`` (R, N, N), in plain torch (any device,
@@ -427,31 +462,8 @@ def mine_from_scores(score, *, k=None, threshold=None, filt_lo=None, filt_hi=Non
     Returns ``(triplets int64 (n, 3), logits float32 (n,), info)`` in that order, -0 reported as +0; ``info['count']`` is the
     number of candidates at or above the threshold (top-K: at or above the K-th logit's exact value; all, when fewer than K
     exist).  More than ``max_results`` of those raise ``MineOverflow`` carrying the count: nothing is truncated silently."""
-    _mine_args(k, threshold, max_results)
-    num_rels, n = score.shape[0], score.shape[1]
-    val = score.to(torch.float32) + 0.0
-    cand = ~torch.isnan(val)
-    if exclude_self:
-        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
-    if filt_lo is not None and n:
-        listed = _listed_mask(filt_lo, filt_hi, filt_ent, n * num_rels, n, val.device)      # rows: key s * R + r
-        cand &= ~listed.view(n, num_rels, n).permute(1, 0, 2)
-    info = {'passes': 0}
-    if k is not None:
-        vals = val[cand]
-        if vals.numel() > int(k):
-            cand &= val >= torch.topk(vals, int(k)).values[-1]
-    else:
-        cand &= val >= float(threshold)
-    r, s, o = torch.nonzero(cand, as_tuple=True)
-    trip, logits = torch.stack([s, r, o], 1), val[cand]
-    if k is not None:
-        trip, logits, info['count'] = ops.mine_select(trip, logits, int(k), int(max_results), n, num_rels)
-        return trip, logits, info
-    info['count'] = int(logits.numel())
-    if info['count'] > int(max_results):
-        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
-    return ops.mine_order(trip, logits, n, num_rels) + (info,)
+    return _mine_from_values(score, False, k=k, threshold=threshold, filt_lo=filt_lo, filt_hi=filt_hi, filt_ent=filt_ent,
+                            exclude_self=exclude_self, max_results=max_results)
 
 
 def _mine_filter(filter_index, n, num_rels, device):
@@ -488,6 +500,50 @@ def mine_triplets(embedding, w, *, k=None, threshold=None, filter_index=None, fl
                            filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
 
 
+def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, filt, exclude_self, max_results):
+    """The unfused route of both models, one relation at a time: ``values_of(r)`` is relation r's (N, N) values (logits, or
+    distances when ``ascending``), ``filt`` the (lo, hi, ent) of ``_mine_filter``; torch selection, a running K-th value pruning
+    the pool."""
+    lo, hi, ent = filt
+    k = None if k is None else int(k)
+    bound = None if k is not None else float(threshold)
+    within = torch.le if ascending else torch.ge          # at the bound or better
+    pool_t, pool_v, held = [], [], 0
+    diag = torch.eye(n, dtype=torch.bool, device=device) if exclude_self else None
+
+    def prune():
+        nonlocal pool_t, pool_v, held, bound
+        t, v = torch.cat(pool_t), torch.cat(pool_v)
+        if v.numel() > k:
+            bound = float(torch.topk(v, k, largest=not ascending).values[-1])
+            keep = within(v, bound)
+            t, v = t[keep], v[keep]
+        pool_t, pool_v, held = [t], [v], v.numel()
+
+    for r in range(num_rels if n else 0):
+        val = values_of(r)
+        cand = ~torch.isnan(val)
+        if diag is not None:
+            cand &= ~diag
+        if lo is not None:
+            cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], ent, n, n, device)
+        if bound is not None:
+            cand &= within(val, bound)
+        if k is not None and bound is None:           # no bound yet: this relation's own K-th value
+            vals = val[cand]
+            if vals.numel() > k:
+                cand &= within(val, torch.topk(vals, k, largest=not ascending).values[-1])
+        s, o = torch.nonzero(cand, as_tuple=True)
+        pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
+        pool_v.append(val[cand])
+        held += s.numel()
+        if k is not None and held > max(4 * k, 1 << 20):
+            prune()
+    trip = torch.cat(pool_t) if pool_t else torch.zeros(0, 3, dtype=torch.int64, device=device)
+    values = torch.cat(pool_v) if pool_v else torch.zeros(0, dtype=torch.float32, device=device)
+    return _mine_finish(trip, values, {'passes': num_rels}, k, threshold, max_results, n, num_rels, ascending)
+
+
 def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=None, flow_log_prob=None, exclude_self=True,
                           max_results=ops.MINE_MAX_RESULTS):
     """``mine_triplets`` from materialised logits, one relation at a time (``ops.mul`` + ``ops.gemm`` + torch selection, a running
@@ -496,54 +552,17 @@ def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=
     emb = embedding.detach().contiguous()
     wd = w.detach().to(emb.device).contiguous()
     n, num_rels = emb.shape[0], wd.shape[0]
-    lo, hi, ent = _mine_filter(filter_index, n, num_rels, emb.device)
+    filt = _mine_filter(filter_index, n, num_rels, emb.device)
     bias = _mine_bias(flow_log_prob, emb.device)
-    k = None if k is None else int(k)
-    floor = None if k is not None else float(threshold)
-    pool_t, pool_v, held = [], [], 0
-    diag = torch.eye(n, dtype=torch.bool, device=emb.device) if exclude_self else None
 
-    def prune():
-        nonlocal pool_t, pool_v, held, floor
-        t, v = torch.cat(pool_t), torch.cat(pool_v)
-        if v.numel() > k:
-            floor = float(torch.topk(v, k).values[-1])
-            keep = v >= floor
-            t, v = t[keep], v[keep]
-        pool_t, pool_v, held = [t], [v], v.numel()
-
-    for r in range(num_rels):
+    def logits_of(r):
         val = ops.gemm(ops.mul(emb, wd[r].expand_as(emb).contiguous()), emb, trans_b=True, precision='f32')
         if bias is not None:
             val = val + bias
-        val = val + 0.0
-        cand = ~torch.isnan(val)
-        if diag is not None:
-            cand &= ~diag
-        if lo is not None:
-            cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], ent, n, n, emb.device)
-        if floor is not None:
-            cand &= val >= floor
-        if k is not None and floor is None:           # no bound yet: this relation's own K-th logit
-            vals = val[cand]
-            if vals.numel() > k:
-                cand &= val >= torch.topk(vals, k).values[-1]
-        s, o = torch.nonzero(cand, as_tuple=True)
-        pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
-        pool_v.append(val[cand])
-        held += s.numel()
-        if k is not None and held > max(4 * k, 1 << 20):
-            prune()
-    info = {'passes': num_rels}
-    trip = torch.cat(pool_t) if pool_t else torch.zeros(0, 3, dtype=torch.int64, device=emb.device)
-    logits = torch.cat(pool_v) if pool_v else torch.zeros(0, dtype=torch.float32, device=emb.device)
-    if k is not None:
-        trip, logits, info['count'] = ops.mine_select(trip, logits, int(k), int(max_results), n, num_rels)
-        return trip, logits, info
-    info['count'] = int(logits.numel())
-    if info['count'] > int(max_results):
-        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
-    return ops.mine_order(trip, logits, n, num_rels) + (info,)
+        return val + 0.0
+
+    return _mine_unfused(logits_of, False, n, num_rels, emb.device, k=k, threshold=threshold, filt=filt, exclude_self=exclude_self,
+                        max_results=max_results)
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

@@ -67,8 +67,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, rank_from_scores_constrained,
-                      sort_and_rank, topk_from_scores)
+from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_unfused,
+                      rank_from_scores_constrained, sort_and_rank, topk_from_scores)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -669,31 +669,8 @@ def mine_from_distances(dist, *, k=None, threshold=None, filt_lo=None, filt_hi=N
     float32 (n,), info)`` in that order; ``info['count']`` is the number of candidates at or below the threshold (top-K: at or
     below the K-th distance's exact value; all, when fewer than K exist).  More than ``max_results`` of those raise
     ``MineOverflow`` carrying the count: nothing is truncated silently."""
-    _mine_args(k, threshold, max_results)
-    num_rels, n = dist.shape[0], dist.shape[1]
-    val = dist.to(torch.float32) + 0.0
-    cand = ~torch.isnan(val)
-    if exclude_self:
-        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
-    if filt_lo is not None and n:
-        listed = _listed_mask(filt_lo, filt_hi, filt_ent, n * num_rels, n, val.device)      # rows: key s * R + r
-        cand &= ~listed.view(n, num_rels, n).permute(1, 0, 2)
-    info = {'passes': 0}
-    if k is not None:
-        vals = val[cand]
-        if vals.numel() > int(k):
-            cand &= val <= torch.topk(vals, int(k), largest=False).values[-1]
-    else:
-        cand &= val <= float(threshold)
-    r, s, o = torch.nonzero(cand, as_tuple=True)
-    trip, d = torch.stack([s, r, o], 1), val[cand]
-    if k is not None:
-        trip, d, info['count'] = ops.mine_select(trip, d, int(k), int(max_results), n, num_rels, ascending=True)
-        return trip, d, info
-    info['count'] = int(d.numel())
-    if info['count'] > int(max_results):
-        raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
-    return ops.mine_order(trip, d, n, num_rels, ascending=True) + (info,)
+    return _mine_from_values(dist, True, k=k, threshold=threshold, filt_lo=filt_lo, filt_hi=filt_hi, filt_ent=filt_ent,
+                            exclude_self=exclude_self, max_results=max_results)
 
 
 def mine_triplets(model_or_tables, *, k=None, threshold=None, filter_index=None, exclude_self=True,
@@ -727,54 +704,16 @@ def mine_triplets_unfused(model_or_tables, *, k=None, threshold=None, filter_ind
         ent, rel, p_norm, norm_flag = _tables(model_or_tables)
         ent, rel = ent.contiguous(), rel.to(ent.device).contiguous()
         n, num_rels = ent.shape[0], rel.shape[0]
-        dev = ent.device
-        lo, hi, f_ent = _mine_filter(filter_index, n, num_rels, dev)
-        k = None if k is None else int(k)
-        ceil = None if k is not None else float(threshold)
-        pool_t, pool_v, held = [], [], 0
-        diag = torch.eye(n, dtype=torch.bool, device=dev) if exclude_self else None
-        subjects = torch.arange(n, device=dev)
+        filt = _mine_filter(filter_index, n, num_rels, ent.device)
+        subjects = torch.arange(n, device=ent.device)
         en = ops.transe_queries(ent, norm_flag=norm_flag) if n else ent
 
-        def prune():
-            nonlocal pool_t, pool_v, held, ceil
-            t, v = torch.cat(pool_t), torch.cat(pool_v)
-            if v.numel() > k:
-                ceil = float(torch.topk(v, k, largest=False).values[-1])
-                keep = v <= ceil
-                t, v = t[keep], v[keep]
-            pool_t, pool_v, held = [t], [v], v.numel()
-
-        for r in range(num_rels if n else 0):
+        def distances_of(r):
             q = ops.transe_queries(ent, rel, subjects, torch.full_like(subjects, r), head=False, norm_flag=norm_flag)
-            val = ops.transe_distances(q, en, p_norm)
-            cand = ~torch.isnan(val)
-            if diag is not None:
-                cand &= ~diag
-            if lo is not None:
-                cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], f_ent, n, n, dev)
-            if ceil is not None:
-                cand &= val <= ceil
-            if k is not None and ceil is None:            # no bound yet: this relation's own K-th distance
-                vals = val[cand]
-                if vals.numel() > k:
-                    cand &= val <= torch.topk(vals, k, largest=False).values[-1]
-            s, o = torch.nonzero(cand, as_tuple=True)
-            pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
-            pool_v.append(val[cand])
-            held += s.numel()
-            if k is not None and held > max(4 * k, 1 << 20):
-                prune()
-        info = {'passes': num_rels}
-        trip = torch.cat(pool_t) if pool_t else torch.zeros(0, 3, dtype=torch.int64, device=dev)
-        d = torch.cat(pool_v) if pool_v else torch.zeros(0, dtype=torch.float32, device=dev)
-        if k is not None:
-            trip, d, info['count'] = ops.mine_select(trip, d, int(k), int(max_results), n, num_rels, ascending=True)
-            return trip, d, info
-        info['count'] = int(d.numel())
-        if info['count'] > int(max_results):
-            raise MineOverflow(info['count'], max_results, f'threshold {float(threshold)}')
-        return ops.mine_order(trip, d, n, num_rels, ascending=True) + (info,)
+            return ops.transe_distances(q, en, p_norm)
+
+        return _mine_unfused(distances_of, True, n, num_rels, ent.device, k=k, threshold=threshold, filt=filt,
+                            exclude_self=exclude_self, max_results=max_results)
 
 
 def write_completions(path, model_or_tables, filter_index, k=None, threshold=None):

@@ -581,7 +581,8 @@ int gv_topk_scores_constrained(const float* q, int ld_q, const float* e, int ld_
  *                 `prefix` (prefix_bits 0: all), the count per value of the next bin_bits key bits.  1 <= bin_bits <= 12.
  * The unused mode's arguments are ignored.  workspace (only with a filter): gv_mine_scores_workspace_bytes(n, num_rels,
  * n_filt_ent) bytes, 16-byte aligned.  n * num_rels < 2^31, num_rels <= 2^19, any h >= 1 and ld >= h; n == 0: nothing is
- * launched.  Integer atomics on the counter and the histograms only; the result does not depend on the launch geometry. */
+ * launched.  An out (GV_MINE_EMIT) or a workspace (with a filter) that is not 16-byte aligned is refused before any launch, as
+ * gv_transe_mine refuses it.  Integer atomics on the counter and the histograms only; the result does not depend on the launch geometry. */
 enum { GV_MINE_EMIT = 0, GV_MINE_HIST = 1 };
 int64_t gv_mine_scores_workspace_bytes(int n, int num_rels, int n_filt_ent);
 int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from mine_cases import _lists, _same
+
 pytestmark = pytest.mark.gpu
 
 
@@ -27,39 +29,6 @@ def _materialise(ops, ent, rel, p, norm_flag):
     s = torch.arange(n, device='cuda')
     return torch.stack([ops.transe_distances(ops.transe_queries(ent, rel, s, torch.full_like(s, r), head=False, norm_flag=norm_flag),
                                              en, p) for r in range(rel.shape[0])])
-
-
-def _same(a, b):
-    """Bit-for-bit equality of (triplets, distances) and of the reported counts."""
-    return (torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
-            and a[2]['count'] == b[2]['count'])
-
-
-def _lists(keys, v, gen, dense):
-    """Sorted unique object lists per key s * R + r, packed into (lo, hi, ent): empty, few, straddling a 64-column tile edge, a
-    whole 64-column window, all but two.  ``dense``: every key gets a kind in turn, otherwise most keys stay empty."""
-    cycle = ['empty', 'few', 'straddle', 'window', 'long', 'few', 'empty']
-    sparse = {0: 'few', 3: 'few', 7: 'straddle', 13: 'window', 29: 'long'}
-    out = []
-    for i in range(keys):
-        kind = cycle[i % len(cycle)] if dense else sparse.get(i % 41, 'empty')
-        if kind == 'empty':
-            e = np.zeros(0, dtype=np.int64)
-        elif kind == 'few':
-            e = np.unique(torch.randint(0, v, (5,), generator=gen).numpy())
-        elif kind == 'straddle':
-            c = 64 * int(torch.randint(1, max(2, v // 64), (1,), generator=gen))
-            e = np.arange(max(0, min(v, c) - 3), min(v, c + 3))
-        elif kind == 'window':
-            c = 64 * int(torch.randint(0, max(1, v // 64), (1,), generator=gen))
-            e = np.arange(c, min(v, c + 64))
-        else:
-            e = np.sort(torch.randperm(v, generator=gen)[:max(0, v - 2)].numpy())
-        out.append(e)
-    lens = np.array([len(e) for e in out], dtype=np.int64)
-    hi = np.cumsum(lens)
-    ent = np.concatenate(out) if lens.sum() else np.zeros(0, dtype=np.int64)
-    return torch.from_numpy(hi - lens).cuda(), torch.from_numpy(hi).cuda(), torch.from_numpy(ent).cuda()
 
 
 def _tables(n, dim, num_rels, seed, scale=0.5):

@@ -2,56 +2,13 @@
 loop), the argument checks of gv_mine_scores (nothing is launched), and the command-line surface."""
 import ctypes
 import functools
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
-
-def _key(x):
-    """Order key of a logit under the rule: descending, -0 == +0."""
-    return -(x + 0.0)
-
-
-def brute_force(score, k=None, threshold=None, filt=None, exclude_self=True):
-    """Every candidate of score[r, s, o] in the rule's total order, by three Python loops; ``filt`` a set of (s, r, o)."""
-    num_rels, n = score.shape[0], score.shape[1]
-    cands = []
-    for s in range(n):
-        for r in range(num_rels):
-            for o in range(n):
-                x = float(score[r, s, o])
-                if math.isnan(x) or (exclude_self and s == o) or (filt and (s, r, o) in filt):
-                    continue
-                cands.append((_key(x), s, r, o, x + 0.0))
-    cands.sort(key=lambda c: c[:4])
-    if threshold is not None:
-        cands = [c for c in cands if c[4] >= threshold]
-        count = len(cands)
-    else:
-        count = len(cands) if len(cands) <= k else sum(1 for c in cands if c[4] >= cands[k - 1][4])
-        cands = cands[:k]
-    trip = torch.tensor([c[1:4] for c in cands], dtype=torch.int64).reshape(-1, 3)
-    logits = torch.tensor([c[4] for c in cands], dtype=torch.float32)
-    return trip, logits, count
-
-
-def filter_arrays(filt, n, num_rels):
-    """(lo, hi, ent) over the keys s * R + r of a set of (s, r, o)."""
-    lists = [[] for _ in range(n * num_rels)]
-    for s, r, o in sorted(filt):
-        lists[s * num_rels + r].append(o)
-    lens = np.array([len(x) for x in lists], dtype=np.int64)
-    hi = np.cumsum(lens)
-    ent = np.array([o for x in lists for o in x], dtype=np.int64)
-    return torch.from_numpy(hi - lens), torch.from_numpy(hi), torch.from_numpy(ent)
-
-
-def same(got, want):
-    return (torch.equal(got[0], want[0]) and torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
-            and got[2]['count'] == want[2])
+from mine_cases import brute_force, filter_arrays, same
 
 
 def scores(n, num_rels, h, seed, special=True):
@@ -79,13 +36,13 @@ def test_mine_from_scores_equals_the_triple_loop(n, num_rels, seed, exclude_self
                                                         torch.randint(0, n, (2 * n,), generator=gen))}
     for f in (None, filt):
         arrays = dict(zip(('filt_lo', 'filt_hi', 'filt_ent'), filter_arrays(f, n, num_rels))) if f else {}
-        total = brute_force(score, k=10 ** 9, filt=f, exclude_self=exclude_self)[2]
+        total = brute_force(score, False, k=10 ** 9, filt=f, exclude_self=exclude_self)[2]
         for k in (1, 2, 5, 17, max(total, 1), total + 7):          # the last: K larger than the number of candidates
             got = ranking.mine_from_scores(score, k=k, exclude_self=exclude_self, **arrays)
-            assert same(got, brute_force(score, k=k, filt=f, exclude_self=exclude_self))
+            assert same(got, brute_force(score, False, k=k, filt=f, exclude_self=exclude_self))
         for t in (float('inf'), float('-inf'), 0.0, -0.0, 0.7, -1.3):
             got = ranking.mine_from_scores(score, threshold=t, exclude_self=exclude_self, **arrays)
-            assert same(got, brute_force(score, threshold=t, filt=f, exclude_self=exclude_self))
+            assert same(got, brute_force(score, False, threshold=t, filt=f, exclude_self=exclude_self))
         everything = ranking.mine_from_scores(score, threshold=float('-inf'), exclude_self=exclude_self, **arrays)
         assert everything[0].shape[0] == total and not bool(torch.isnan(everything[1]).any())      # all but NaN
 
@@ -114,7 +71,7 @@ def test_the_rule_on_a_hand_made_tensor():
 def test_both_overflow_errors_carry_the_true_count():
     from gcn_vae_amd import ranking
     score = scores(10, 2, 4, 7, special=False)
-    want = brute_force(score, threshold=-0.5)[2]
+    want = brute_force(score, False, threshold=-0.5)[2]
     assert want > 5
     with pytest.raises(ranking.MineOverflow) as err:
         ranking.mine_from_scores(score, threshold=-0.5, max_results=want - 1)
@@ -172,11 +129,13 @@ def test_entry_points_are_exported_and_check_their_arguments():
     assert call(e=None) != 0 and 'NULL' in lib.last_error()
     assert call(w=None) != 0 and 'NULL' in lib.last_error()
     assert call(out=None) != 0 and 'NULL' in lib.last_error()
+    assert call(out=ctypes.c_void_p(8)) != 0 and 'aligned' in lib.last_error()
     assert call(counter=None) != 0 and 'NULL' in lib.last_error()
     assert call(mode=1, hist=None) != 0 and 'NULL' in lib.last_error()
     assert call(lo=one) != 0 and 'filt' in lib.last_error()                       # the three filter arrays come together
     assert call(lo=one, hi=one, ent=one, n_ent=5) != 0 and 'workspace' in lib.last_error()
     assert call(lo=one, hi=one, ent=one, n_ent=5, ws=one, ws_bytes=8) != 0 and 'workspace' in lib.last_error()
+    assert call(lo=one, hi=one, ent=one, n_ent=5, ws=ctypes.c_void_p(24), ws_bytes=1 << 20) != 0 and 'aligned' in lib.last_error()
     assert call(ld_e=7) != 0 and 'leading dimension' in lib.last_error()
     assert call(ld_w=7) != 0 and 'leading dimension' in lib.last_error()
     assert call(n=2 ** 20, num_rels=2 ** 11) != 0 and '2^31' in lib.last_error()
@@ -193,6 +152,7 @@ def test_entry_points_are_exported_and_check_their_arguments():
     assert l.gv_mine_scores_workspace_bytes(0, 3, 5) == 0
     fb = l.gv_mine_scores_workspace_bytes(14541, 237, 310116)
     assert fb >= (2 * 228 * 228 + 1 + 310116) * 4 and fb % 16 == 0
+    assert fb == l.gv_transe_mine_workspace_bytes(14541, 237, 310116)              # one re-bucketed filter for both miners
 
 
 def test_the_wrappers_refuse_host_tensors_and_bad_arguments():

@@ -1,52 +1,13 @@
 """Whole-graph TransE mining, the parts that need no GPU: the rule itself (transe.mine_from_distances against a triple Python
 loop), the argument checks of gv_transe_mine (nothing is launched), and the command-line surface."""
 import ctypes
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
-
-def brute_force(dist, k=None, threshold=None, filt=None, exclude_self=True):
-    """Every candidate of dist[r, s, o] in the rule's total order (distance ascending, then s, r, o), by three Python loops;
-    ``filt`` a set of (s, r, o)."""
-    num_rels, n = dist.shape[0], dist.shape[1]
-    cands = []
-    for s in range(n):
-        for r in range(num_rels):
-            for o in range(n):
-                x = float(dist[r, s, o])
-                if math.isnan(x) or (exclude_self and s == o) or (filt and (s, r, o) in filt):
-                    continue
-                cands.append((x, s, r, o))
-    cands.sort()
-    if threshold is not None:
-        cands = [c for c in cands if c[0] <= threshold]
-        count = len(cands)
-    else:
-        count = len(cands) if len(cands) <= k else sum(1 for c in cands if c[0] <= cands[k - 1][0])
-        cands = cands[:k]
-    trip = torch.tensor([c[1:] for c in cands], dtype=torch.int64).reshape(-1, 3)
-    d = torch.tensor([c[0] for c in cands], dtype=torch.float32)
-    return trip, d, count
-
-
-def filter_arrays(filt, n, num_rels):
-    """(lo, hi, ent) over the keys s * R + r of a set of (s, r, o)."""
-    lists = [[] for _ in range(n * num_rels)]
-    for s, r, o in sorted(filt):
-        lists[s * num_rels + r].append(o)
-    lens = np.array([len(x) for x in lists], dtype=np.int64)
-    hi = np.cumsum(lens)
-    ent = np.array([o for x in lists for o in x], dtype=np.int64)
-    return torch.from_numpy(hi - lens), torch.from_numpy(hi), torch.from_numpy(ent)
-
-
-def same(got, want):
-    return (torch.equal(got[0], want[0]) and torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
-            and got[2]['count'] == want[2])
+from mine_cases import brute_force, filter_arrays, same
 
 
 def distances(n, num_rels, seed):
@@ -78,13 +39,13 @@ def test_mine_from_distances_equals_the_triple_loop(n, num_rels, seed, exclude_s
                                                         torch.randint(0, n, (2 * n,), generator=gen))}
     for f in (None, filt):
         arrays = dict(zip(('filt_lo', 'filt_hi', 'filt_ent'), filter_arrays(f, n, num_rels))) if f else {}
-        total = brute_force(dist, k=10 ** 9, filt=f, exclude_self=exclude_self)[2]
+        total = brute_force(dist, True, k=10 ** 9, filt=f, exclude_self=exclude_self)[2]
         for k in (1, 2, 5, 17, max(total, 1), total + 7):          # the last: K larger than the number of candidates
             got = transe.mine_from_distances(dist, k=k, exclude_self=exclude_self, **arrays)
-            assert same(got, brute_force(dist, k=k, filt=f, exclude_self=exclude_self)), k
+            assert same(got, brute_force(dist, True, k=k, filt=f, exclude_self=exclude_self)), k
         for t in (float('inf'), 0.0, -0.0, -1.0, 1.5, 2.0, 3.25):
             got = transe.mine_from_distances(dist, threshold=t, exclude_self=exclude_self, **arrays)
-            assert same(got, brute_force(dist, threshold=t, filt=f, exclude_self=exclude_self)), t
+            assert same(got, brute_force(dist, True, threshold=t, filt=f, exclude_self=exclude_self)), t
         assert transe.mine_from_distances(dist, threshold=-1.0, exclude_self=exclude_self, **arrays)[0].shape == (0, 3)
         everything = transe.mine_from_distances(dist, threshold=float('inf'), exclude_self=exclude_self, **arrays)
         assert everything[0].shape[0] == total and not bool(torch.isnan(everything[1]).any())      # all but NaN, +inf included
@@ -115,7 +76,7 @@ def test_the_rule_on_a_hand_made_tensor():
 def test_both_overflow_errors_carry_the_true_count():
     from gcn_vae_amd import ops, transe
     dist = torch.rand(2, 10, 10, generator=torch.Generator().manual_seed(7))
-    want = brute_force(dist, threshold=0.4)[2]
+    want = brute_force(dist, True, threshold=0.4)[2]
     assert want > 5
     with pytest.raises(transe.MineOverflow) as err:
         transe.mine_from_distances(dist, threshold=0.4, max_results=want - 1)
