@@ -353,6 +353,51 @@ __device__ __forceinline__ f32x16 score_tile(const GemmParams& p, int m0, int n0
     return acc;
 }
 
+// ---- the Monte-Carlo posterior-predictive tile (gv_rank_scores_mc, gv_topk_scores_mc): a loop over samples around score_tile ----
+// Sample s has its own query matrix at q + s * q_stride and its own entity table at e + s * e_stride (the leading dimensions are
+// shared) and an optional bias[s]; logit_s comes from score_tile unchanged, and
+//   pbar[i, j] = (sum over s ascending of sig(logit_s[i, j] + bias[s])) * (1.0f / S)
+// stays in 16 registers per lane from the MFMA accumulator to the caller's vote or selection.
+struct McSamples {
+    long long q_stride, e_stride;      // elements between consecutive samples' Q / E
+    int n_samples;                     // 0: not a Monte-Carlo launch
+    float inv_s;                       // 1.0f / n_samples (exact for a power of two: the same sample twice gives the sample's value)
+};
+
+// sig(x) = 1 / (1 + exp(-x)), as v_rcp_f32(1.0f + __expf(-x)): two quarter-rate instructions, no IEEE divide sequence.  The ONE form
+// every pass and entry point of the MC scorers uses, so a target's probability is bit-identical wherever it is recomputed.
+// +inf -> 1, -inf -> 0 (exp overflows to +inf, whose reciprocal is +0), NaN -> NaN: a NaN in any sample makes pbar NaN.
+__device__ __forceinline__ float mc_sig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+// The caller has issued sample 0's first k-chunk of tile (m0, n0) into ra / rb.  Under each sample's epilogue (16 exp + 16 rcp per
+// lane) the next sample's first k-chunk is already in flight; under the last one, sample 0's of the tile at n0_next (< 0: none).
+__device__ __forceinline__ f32x16 mc_pbar_tile(const GemmParams& g, const McSamples& mc, const float* bias, int m0, int n0,
+                                               int n0_next, float (&ra)[SC_BM * SC_BK / 256], float (&rb)[SC_BN * SC_BK / 256],
+                                               float* As, float* Bs) {
+    f32x16 sum;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sum[i] = 0.f;
+    GemmParams p = g;
+    for (int s = 0; s < mc.n_samples; ++s) {
+        const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
+        const float bv = bias ? bias[s] : 0.f;
+        if (s + 1 < mc.n_samples) {
+            p.a += mc.q_stride;
+            p.b += mc.e_stride;
+            load_a<false, SC_BM, SC_BK>(p, m0, 0, p.k, ra);
+            load_b<true, SC_BN, SC_BK>(p, n0, 0, p.k, rb);
+        } else if (n0_next >= 0) {
+            load_a<false, SC_BM, SC_BK>(g, m0, 0, g.k, ra);
+            load_b<true, SC_BN, SC_BK>(g, n0_next, 0, g.k, rb);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sum[i] += mc_sig(acc[i] + bv);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sum[i] *= mc.inv_s;
+    return sum;
+}
+
 // ---- evaluation scorer with a rank-count epilogue (perturb_and_get_rank, kgvae/utils.py:180-221) ----
 // S = Q (m x h) @ E^T (E: v x h), prob = sigmoid(S + *bias).  The reference materialises an (h, Eb, V) tensor, sorts every
 // row and looks the target up; here the probabilities never leave the registers:
@@ -437,13 +482,19 @@ struct RankFiltParams {
     TopkCand cs;             // CAND only (gv_rank_scores_constrained)
     int* count_raw_c;
     int* count_filt_c;       // NULL (as count_filt, filt_lo) when no filter is given
+    McSamples mc;            // MC only (gv_rank_scores_mc): rp.bias then holds one value per sample
 };
 
 // CAND: the type-constrained protocol on top.  The tile's 64 columns are two words of the row's set (topk_cand_pair), loaded once
 // per row and tile into LDS next to the filter word and ANDed into the same ballots, so the constrained counts see the very logits
 // of the unconstrained ones.  The filter is optional there.
-template <bool CAND>
-__global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltParams fp) {
+// MC: the posterior-predictive ranker (gv_rank_scores_mc).  The value that votes is pbar from mc_pbar_tile instead of the logit --
+// bounded, so it CAN saturate: candidates whose every sample rounds to 1.0f tie with such a target and share the mid-rank -- and
+// rp.tgt comes from k_rank_target_mc, which runs the same sample loop.  Filter, ballots and counts are the ones above; the filter
+// is optional (raw count only without one).  Its 16 extra accumulators are held inside the single-sample rankers' 8 waves / SIMD
+// (waves_per_eu: 64 registers; the single-sample instantiations keep the default and their code).
+template <bool CAND, bool MC = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 8 : 1))) void k_rank_scores_filtered(const RankFiltParams fp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK;
     __shared__ float As[BK * SC_LDA];
     __shared__ float Bs[BK * SC_LDB];
@@ -460,7 +511,7 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
     load_b<true, BN, BK>(p, n0, 0, p.k, rb);
 
     // filter window: thread t < 64 searches row t's list for n0, thread 64 + t for n0 + 64 (two waves, one search each)
-    const bool filtered = !CAND || fp.filt_lo != nullptr;
+    const bool filtered = (!CAND && !MC) || fp.filt_lo != nullptr;
     if (threadIdx.x < 2 * BM) {
         const int rl = threadIdx.x & (BM - 1), row = m0 + rl;
         int lo = 0, hi = 0;
@@ -487,23 +538,56 @@ __global__ __launch_bounds__(256) void k_rank_scores_filtered(const RankFiltPara
         }
     }
 
-    const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
-    const float bv = rp.bias ? *rp.bias : 0.f;
+    f32x16 acc;
+    float bv = 0.f;
+    if constexpr (MC) {
+        acc = mc_pbar_tile(p, fp.mc, rp.bias, m0, n0, -1, ra, rb, As, Bs);
+    } else {
+        acc = score_tile(p, m0, n0, ra, rb, As, Bs);
+        bv = rp.bias ? *rp.bias : 0.f;
+    }
     const int col = n0 + wn + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rl = wm + (r & 3) + 8 * (r >> 2) + 4 * lhi, row = m0 + rl;
-        const RankVotes vt = rank_votes(rp, acc[r] + bv, row, col, lhi);
+        const RankVotes vt = rank_votes(rp, MC ? acc[r] : acc[r] + bv, row, col, lhi);
         if (l31 == 0 && row < p.m) {
             const unsigned keep = ~(unsigned)(fmask[rl] >> wn);    // this half-wave's 32 columns of the row's filter word
             if (rp.count) rank_count_add(rp.count, row, vt.above, vt.equal);
-            if (!CAND || fp.count_filt) rank_count_add(fp.count_filt, row, vt.above & keep, vt.equal & keep);
+            if ((!CAND && !MC) || fp.count_filt) rank_count_add(fp.count_filt, row, vt.above & keep, vt.equal & keep);
             if (CAND) {      // the votes have dropped the columns >= v already, whatever the set's padding bits hold
                 const unsigned member = (unsigned)(fmask[BM + rl] >> wn);
                 rank_count_add(fp.count_raw_c, row, vt.above & member, vt.equal & member);
                 if (fp.count_filt_c) rank_count_add(fp.count_filt_c, row, vt.above & keep & member, vt.equal & keep & member);
             }
         }
+    }
+}
+
+// The first pass of gv_rank_scores_mc: tgt[row] = pbar[row, target[row]], from the same sample loop the second pass runs, so the
+// element is recomputed there bit for bit.  A workgroup reads its 64 targets first and leaves when none falls in its 64 columns:
+// of the whole grid, at most 64 workgroups per row tile do any arithmetic.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_rank_target_mc(const RankFiltParams fp) {
+    __shared__ float As[SC_BK * SC_LDA];
+    __shared__ float Bs[SC_BK * SC_LDB];
+    const RankParams& rp = fp.rp;
+    const GemmParams& p = rp.g;
+    const int m0 = blockIdx.y * SC_BM, n0 = blockIdx.x * SC_BN;
+    bool mine = false;
+    if (threadIdx.x < SC_BM && m0 + (int)threadIdx.x < p.m)
+        mine = (unsigned)(rp.target[m0 + threadIdx.x] - n0) < (unsigned)SC_BN;
+    if (!__syncthreads_or(mine)) return;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    float ra[SC_BM * SC_BK / 256], rb[SC_BN * SC_BK / 256];
+    load_a<false, SC_BM, SC_BK>(p, m0, 0, p.k, ra);
+    load_b<true, SC_BN, SC_BK>(p, n0, 0, p.k, rb);
+    const f32x16 pbar = mc_pbar_tile(p, fp.mc, rp.bias, m0, n0, -1, ra, rb, As, Bs);
+    const int col = n0 + (wid & 1) * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + (wid >> 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+        if (row < p.m && col < p.n && col == rp.target[row]) rp.tgt[row] = pbar[r];
     }
 }
 
@@ -531,10 +615,13 @@ struct TopkParams {
     int n_spans;
     unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
     TopkCand cs;                  // CAND only (gv_topk_scores_constrained)
+    McSamples mc;                 // MC only (gv_topk_scores_mc): bias then holds one value per sample
 };
 
-template <int NK, bool CAND>
-__global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
+// MC: the key's value is pbar from mc_pbar_tile (the very values gv_rank_scores_mc votes on) instead of the logit; held to the
+// 5 waves / SIMD of the single-sample scorer (which its LDS allows at most anyway).
+template <int NK, bool CAND, bool MC = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 5 : 1))) void k_topk_span(const TopkParams tp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1;
     __shared__ float As[BK * SC_LDA];
     __shared__ float Bs[BK * SC_LDB];
@@ -565,20 +652,25 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
         topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && row < p.m, row, t_begin * BN, &cur[rl], &fhi[rl],
                           &nxt[rl]);
     }
-    const float bv = tp.bias ? *tp.bias : 0.f;
+    const float bv = (!MC && tp.bias) ? *tp.bias : 0.f;
     const uint32_t* cand_row = CAND ? topk_cand_row(tp.cs, m0 + wid * (BM / 4), p.m, lane) : nullptr;
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * BN;
         const unsigned cand_w = CAND ? topk_cand_word(cand_row, n0, p.n, lane) : 0u;     // lands under the MFMA chain
-        const f32x16 acc = score_tile(p, m0, n0, ra, rb, As, Bs);
-        if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
-            load_a<false, BM, BK>(p, m0, 0, p.k, ra);
-            load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+        f32x16 acc;
+        if constexpr (MC) {                                        // (the next tile's first operands are requested in there)
+            acc = mc_pbar_tile(p, tp.mc, tp.bias, m0, n0, t + 1 < t_end ? n0 + BN : -1, ra, rb, As, Bs);
+        } else {
+            acc = score_tile(p, m0, n0, ra, rb, As, Bs);
+            if (t + 1 < t_end) {                                   // the next tile's first operands fly under the selection
+                load_a<false, BM, BK>(p, m0, 0, p.k, ra);
+                load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+            }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            Ls[(wm + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDL + wn + l31] = acc[r] + bv;
+            Ls[(wm + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDL + wn + l31] = MC ? acc[r] : acc[r] + bv;
         __syncthreads();                                           // (Ls is rewritten after the next tile's first barrier)
 
         const int col = n0 + lane;
@@ -600,6 +692,41 @@ __global__ __launch_bounds__(256) void k_topk_span(const TopkParams tp) {
         unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
         for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
     }
+}
+
+// ---- the spread of a selected pair's probability over the samples (gv_pair_prob_std_mc) ----------------------------------
+// One thread per pair (i, ids[i, c]): p_s = sig(q_s[i] . e_s[id] + bias[s]) with the dot a plain ascending-k fmaf chain from 0 -- NOT
+// the tile's MFMA chain, so p_s may differ from the tile's value in the last bits -- then the two-pass population standard
+// deviation in fp32: mean = (sum p_s) / S, std = sqrt((sum (p_s - mean)^2) / S), the p_s recomputed for the second pass (the same
+// chain, bit for bit; nothing is stored, S is unbounded).  A padding id (< 0, or >= v) gives 0; S = 1 gives p - p = 0 exactly.
+__global__ __launch_bounds__(256) void k_pair_prob_std_mc(const float* q, int ld_q, const float* e, int ld_e, const McSamples mc,
+                                                         const float* bias, const int* ids, float* out_std, long long pairs, int k,
+                                                         int v, int h) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= pairs) return;
+    const int id = ids[i];
+    if ((unsigned)id >= (unsigned)v) {
+        out_std[i] = 0.f;
+        return;
+    }
+    const float* qr = q + (i / k) * ld_q;
+    const float* er = e + (long long)id * ld_e;
+    auto prob = [&](int s) {
+        const float* a = qr + s * mc.q_stride;
+        const float* b = er + s * mc.e_stride;
+        float dot = 0.f;
+        for (int j = 0; j < h; ++j) dot = fmaf(a[j], b[j], dot);
+        return mc_sig(dot + (bias ? bias[s] : 0.f));
+    };
+    float sum = 0.f;
+    for (int s = 0; s < mc.n_samples; ++s) sum += prob(s);
+    const float mean = sum / (float)mc.n_samples;
+    float dev = 0.f;
+    for (int s = 0; s < mc.n_samples; ++s) {
+        const float d = prob(s) - mean;
+        dev = fmaf(d, d, dev);
+    }
+    out_std[i] = sqrtf(dev / (float)mc.n_samples);
 }
 
 // ---- relation-grouped products for dense per-relation weights (the `basis` regulariser) ----------------
@@ -1199,6 +1326,108 @@ extern "C" int gv_topk_scores_constrained(const float* q, int ld_q, const float*
     GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores_constrained: NULL pointer");
     return topk_scores_launch<true>("gv_topk_scores_constrained", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_logits, workspace, m, v, h, stream);
+}
+
+// ---- Monte-Carlo posterior-predictive ranking and top-k (gv_rank_scores_mc, gv_topk_scores_mc, gv_pair_prob_std_mc) -----------
+// the sample geometry shared by the three entries: n_samples >= 1, and with more than one sample each stride spans its matrix
+static int mc_samples_args(const char* name, const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                           int n_samples, int m, int v, int h, McSamples* mc) {
+    GV_REQUIRE(n_samples >= 1, GV_ERR_SHAPE, "%s: n_samples=%d", name, n_samples);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "%s: leading dimension too small", name);
+    GV_REQUIRE(n_samples == 1 || (q_stride >= (int64_t)(m > 0 ? m - 1 : 0) * ld_q + h && e_stride >= (int64_t)(v - 1) * ld_e + h),
+               GV_ERR_SHAPE, "%s: sample stride shorter than the rows it spans (q_stride=%lld e_stride=%lld)", name,
+               (long long)q_stride, (long long)e_stride);
+    mc->q_stride = n_samples > 1 ? q_stride : 0;
+    mc->e_stride = n_samples > 1 ? e_stride : 0;
+    mc->n_samples = n_samples;
+    mc->inv_s = 1.0f / (float)n_samples;
+    return GV_OK;
+}
+
+// score_gemm_params for sample 0; the 16-byte loads need every sample's base aligned
+static GemmParams mc_gemm_params(const float* q, int ld_q, const float* e, int ld_e, const McSamples& mc, int m, int v, int h) {
+    GemmParams p = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
+    p.vec_a = p.vec_a && mc.q_stride % 4 == 0;
+    p.vec_b = p.vec_b && mc.e_stride % 4 == 0;
+    return p;
+}
+
+extern "C" int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                 const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                                 int n_filt_ent, float* tgt, int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_mc: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
+               n_filt_ent);
+    RankFiltParams fp{};
+    const int rc = mc_samples_args("gv_rank_scores_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &fp.mc);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_rank_scores_mc: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count_raw, GV_ERR_NULL, "gv_rank_scores_mc: NULL pointer");
+    GV_REQUIRE(!filt_lo || count_filt, GV_ERR_NULL, "gv_rank_scores_mc: a filter needs count_filt");
+    RankParams& rp = fp.rp;
+    rp.g = mc_gemm_params(q, ld_q, e, ld_e, fp.mc, m, v, h);
+    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
+    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent;
+    fp.count_filt = filt_lo ? count_filt : nullptr;          // without a filter the filtered count is not written
+    hipStream_t st = (hipStream_t)stream;
+    for (int* c : {count_raw, fp.count_filt})
+        if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status("gv_rank_scores_mc");
+    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
+    hipLaunchKernelGGL(k_rank_target_mc, grid, block, 0, st, fp);                        // tgt[row] = the target's pbar
+    hipLaunchKernelGGL((k_rank_scores_filtered<false, true>), grid, block, 0, st, fp);
+    return launch_status("gv_rank_scores_mc");
+}
+
+extern "C" int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                 const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int k,
+                                 int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_mc: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
+               n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_mc: k=%d outside [1, %d]", k, TOPK_MAX);
+    TopkParams tp{};
+    const int rc = mc_samples_args("gv_topk_scores_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &tp.mc);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_topk_scores_mc: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && out_ids && out_prob && workspace, GV_ERR_NULL, "gv_topk_scores_mc: NULL pointer");
+    tp.g = mc_gemm_params(q, ld_q, e, ld_e, tp.mc, m, v, h);
+    tp.bias = bias;
+    tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
+    tp.topk = k;
+    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
+    tp.part = (unsigned long long*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int lds = 64 * k * (int)sizeof(unsigned long long);
+    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
+    const TopkLogitOut out{out_ids, out_prob};
+    if (k <= 64) {
+        hipLaunchKernelGGL((k_topk_span<1, false, true>), grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_topk_span<2, false, true>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
+                               "gv_topk_scores_mc"))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_topk_span<2, false, true>), grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
+    }
+    return launch_status("gv_topk_scores_mc");
+}
+
+extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                   const float* bias, const int* ids, int k, float* out_std, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && k >= 1, GV_ERR_SHAPE, "gv_pair_prob_std_mc: m=%d v=%d h=%d k=%d", m, v, h, k);
+    McSamples mc;
+    const int rc = mc_samples_args("gv_pair_prob_std_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc);
+    if (rc != GV_OK) return rc;
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && ids && out_std, GV_ERR_NULL, "gv_pair_prob_std_mc: NULL pointer");
+    const long long pairs = (long long)m * k;
+    hipLaunchKernelGGL(k_pair_prob_std_mc, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, ld_q, e, ld_e,
+                       mc, bias, ids, out_std, pairs, k, v, h);
+    return launch_status("gv_pair_prob_std_mc");
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

@@ -263,6 +263,51 @@ class KGVAE(ops.StayOnDevice, nn.Module):
                     self.flow_log_prob = (log_det_sum.reshape(-1) * live).sum() / rows
         return z
 
+    def posterior_samples(self, g, h, r, norm, n_samples, seed=None):
+        """``n_samples`` draws of the latents from q(z | graph) for the Monte-Carlo posterior predictive (ranking.calc_mc_mrr,
+        ranking.predict_topk_mc): the embedding and the two R-GCN layers run ONCE, the reparameterisation and the flows once per
+        sample on the one layer-2 output.  Returns ``(z float32 (S, N, h_dim), flow_log_probs float32 (S,) or None without
+        flows)``.  The noise comes from a ``torch.Generator`` on the module's device seeded with ``seed`` (None: a fresh random
+        seed) and is drawn sample by sample, so the same seed gives the same z bit for bit and the first S samples do not depend
+        on how many follow.  Eval mode only (dropout off); ``eps_override`` is not consulted; ``z_mean`` / ``z_sigma`` /
+        ``flow_log_prob`` are left as a ``forward`` would have left them after the last sample."""
+        n_samples = int(n_samples)
+        if n_samples < 1:
+            raise ValueError(f'posterior_samples: n_samples must be >= 1, got {n_samples}')
+        if self.training:
+            raise RuntimeError('posterior_samples needs eval mode (the layers\' dropout would differ between the samples\' one '
+                               'shared pass and a forward): call .eval() first')
+        if self.row_part is not None:
+            raise NotImplementedError('posterior_samples under a destination-row partition (multi-GPU) is not supported')
+        h, r, norm = ops.to_module_device(self.z_pre, h, r, norm)
+        self.node_id = h.squeeze()
+        dev = self.z_pre.device
+        gen = torch.Generator(device=dev)
+        if seed is None:
+            gen.seed()
+        else:
+            gen.manual_seed(int(seed))
+        with torch.no_grad():
+            x = self.input_layer(g, h, r, norm)
+            x = self.rconv_layer_1(g, x, r, norm)
+            h2 = self.rconv_layer_2(g, x, r, norm)
+            n = h2.shape[0]
+            z = torch.empty(n_samples, n, self.h_dim, dtype=torch.float32, device=dev)
+            flps = torch.empty(n_samples, dtype=torch.float32, device=dev) if self.n_flows > 0 else None
+            self.flow_log_prob = None
+            self._z_pri_flowed = None
+            for s in range(n_samples):
+                eps = torch.randn(n, self.h_dim, generator=gen, dtype=torch.float32, device=dev)
+                zs, self.z_mean, self.z_sigma = ops.reparam(h2, eps)
+                if self.n_flows > 0:
+                    zs, flp = self._apply_flows(zs, want_mean=True)
+                    if flp.dim() != 0:       # (more than 8 blocks: the per-row sum came back)
+                        flp = torch.mean(flp.view(-1, 1))
+                    self.flow_log_prob = flp
+                    flps[s] = flp
+                z[s].copy_(zs)
+        return z, flps
+
 
 class BaseRGCN(ops.StayOnDevice, nn.Module):
     def __init__(self, num_nodes, h_dim, out_dim, num_rels, num_bases, num_hidden_layers=1, dropout=0,

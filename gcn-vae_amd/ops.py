@@ -742,7 +742,93 @@ def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=N
     return ids.long(), logits
 
 
-MINE_MAX_RESULTS = 1 << 22      # default cap on the triplets one mining call may return (64 MiB of records)
+def _mc_operands(q, entities):
+    """The two sample stacks of a Monte-Carlo query -- q (S, m, h), entities (S, v, h) -- checked for shape ahead of any look at
+    their device, then as contiguous float32: (q, entities, S, m, v, h)."""
+    for name, t in (('q', q), ('entities', entities)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise TypeError(f'{name}: expected a 3-D (samples, rows, width) tensor')
+    if q.shape[0] != entities.shape[0] or q.shape[0] < 1:
+        raise ValueError(f'q / entities need the same number of samples, at least one ({q.shape[0]} vs {entities.shape[0]})')
+    if q.shape[2] != entities.shape[2]:
+        raise ValueError('q / entities width mismatch')
+    (s, m, h), v = q.shape, entities.shape[1]
+    if v < 1 or h < 1:
+        raise ValueError(f'need at least one entity and width >= 1 (v={v}, h={h})')
+    q, entities = _chk(q.contiguous(), name='q'), _chk(entities.contiguous(), name='entities')
+    if entities.device != q.device:
+        raise ValueError(f'entities must be on the device of q ({q.device}), got {entities.device}')
+    return q, entities, s, m, v, h
+
+
+def _mc_bias_arg(bias, s, device):
+    """The MC scorers' optional per-sample bias (each draw's flow_log_prob): float32 (S,) on the queries' device."""
+    if bias is None:
+        return None
+    bias = bias.reshape(-1)
+    if bias.numel() != s:
+        raise ValueError(f'bias: one value per sample ({s}), got {bias.numel()}')
+    return _chk(bias.to(device=device, dtype=torch.float32).contiguous(), name='bias')
+
+
+def rank_scores_mc(q, entities, target, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """Posterior-predictive ranks from S samples (gv_rank_scores_mc): ``q`` (S, m, h) and ``entities`` (S, v, h) hold one query
+    matrix and one entity table per sample, ``bias`` (S,) optionally each draw's flow_log_prob.  The value ranked is
+    ``pbar[i, j] = mean_s sigmoid(q[s, i] . entities[s, j] + bias[s])``, never stored; ranks follow ``rank_scores_filtered``'s
+    rules (0-based floats, x.5 under ties -- pbar saturates, so ties are real --, NaN never optimistic).  Returns ``(raw,
+    filtered, tgt)``: ``filtered`` is None without a filter, ``tgt`` (m,) is the target's own pbar."""
+    q, entities, s, m, v, h = _mc_operands(q, entities)
+    tgt32 = _target_args(target, m, v, q.device)
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    bias = _mc_bias_arg(bias, s, q.device)
+    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
+    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=q.device)
+    filt = lo32 is not None
+    lib.call('gv_rank_scores_mc', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, ptr(tgt), ptr(counts[0]), ptr(counts[1]) if filt else None, m, v, h, lib.stream())
+    raw, filtered = _ranks(counts, m, filt)
+    return raw, filtered, tgt[:m]
+
+
+def topk_scores_mc(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The ``k`` most probable entities per query row under ``rank_scores_mc``'s pbar -- the very values it ranks, bit for bit --
+    from one fused launch pair (gv_topk_scores_mc).  Filter, order (pbar descending, ties by lower id, NaN last) and padding (id
+    -1, value -inf) are ``topk_scores``'.  Returns ``(ids int64 (m, k), prob_mean float32 (m, k))``."""
+    q, entities, s, m, v, h = _mc_operands(q, entities)
+    k = _topk_arg(k)
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    prob = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids.long(), prob
+    bias = _mc_bias_arg(bias, s, q.device)
+    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_topk_scores_mc', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+             k, ptr(ids), ptr(prob), ptr(ws), m, v, h, lib.stream())
+    return ids.long(), prob
+
+
+def pair_prob_std_mc(q, entities, ids, bias=None):
+    """Population standard deviation over the samples of ``sigmoid(q[s, i] . entities[s, ids[i, c]] + bias[s])`` for every
+    selected pair (gv_pair_prob_std_mc; two-pass in fp32, the dot a plain fmaf chain): float32 (m, k).  Padding ids (-1) give
+    0, one sample gives exactly 0."""
+    q, entities, s, m, v, h = _mc_operands(q, entities)
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.shape[0] != m or ids.shape[1] < 1:
+        raise ValueError(f'ids: expected ({m}, k >= 1) entity ids, one row per query')
+    if ids.numel() and int(ids.max()) >= v:
+        raise ValueError(f'ids must lie below {v} (negative: padding)')
+    k = ids.shape[1]
+    std = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return std
+    bias = _mc_bias_arg(bias, s, q.device)
+    ids32 = ids.to(device=q.device, dtype=torch.int32).contiguous()
+    lib.call('gv_pair_prob_std_mc', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(bias), ptr(ids32), k, ptr(std), m, v, h,
+             lib.stream())
+    return std
+
+
+MINE_MAX_RESULTS = 1 << 22     # default cap on the triplets one mining call may return (64 MiB of records)
 MINE_LEVELS = ((0, 12), (12, 10), (22, 10))      # (prefix bits, bin bits) of the histogram passes: 12 + 10 + 10 = the whole key
 
 

@@ -31,6 +31,13 @@ Completion (no query list: which triplets are missing from the graph?): ``mine_t
 triplets -- the K most confident new ones, or all above a threshold -- from ``ops.mine_scores`` (gv_mine_scores: subject and
 object tiles of the entity table stay in LDS while the relations are walked over them).  ``mine_from_scores`` states the rule on
 a materialised (R, N, N) tensor; ``mine_triplets_unfused`` is the per-relation GEMM cross-check.
+
+Monte-Carlo posterior predictive (the encoder is variational: one draw of the latents gives one of many possible rankings):
+with S samples from ``KGVAE.posterior_samples``, ``calc_mc_mrr`` ranks and ``predict_topk_mc`` selects on
+``pbar = mean_s sigmoid(logit_s)`` -- ``ops.rank_scores_mc`` / ``ops.topk_scores_mc`` loop over the samples around the same
+score tile and keep pbar in registers -- and ``predict_topk_mc`` adds each proposal's spread over the samples.  pbar is a
+probability, so it saturates and ties are real; they share the mid-rank.  ``mc_mean_prob`` / ``mc_ranks_from_probs`` state the
+rule on materialised values; the ``*_mc_unfused`` routes are the per-sample GEMM cross-check.
 """
 import torch
 
@@ -402,6 +409,195 @@ def predict_topk_unfused(embedding, w, a, r, k, direction='o', filter_index=None
             score = score + flow_log_prob
         return topk_from_scores(score, k, f_lo, f_hi, ent, None if sets is None else type_constraint.mask(sets, score.device))
     return _predict_topk(embedding, w, a, r, k, direction, filter_index, select, type_constraint)
+
+
+# ---- Monte-Carlo posterior-predictive ranking and top-k --------------------------------------------------------------------
+MC_STACK_ROWS = 4096        # queries per MC launch: bounds the (S, rows, h) query stack
+MC_UNFUSED_ROWS = 1024      # queries per chunk of the materialised cross-check: bounds its (rows, v) matrices
+
+
+def mc_mean_prob(z, w, a, r, flow_log_probs=None):
+    """The posterior-predictive probability on materialised values, in the tensors' dtype (any device):
+    ``pbar[i, j] = (sum_s sigmoid((z[s, a_i] * w[r_i]) . z[s, j] + flow_log_probs[s])) / S`` for the samples ``z`` (S, N, h),
+    summed in ascending s.  Returns (len(a), N)."""
+    total = None
+    for s in range(z.shape[0]):
+        logit = (z[s][a] * w[r]) @ z[s].T
+        if flow_log_probs is not None:
+            logit = logit + flow_log_probs[s]
+        p = torch.sigmoid(logit)
+        total = p if total is None else total + p
+    return total / z.shape[0]
+
+
+def mc_ranks_from_probs(pbar, target, listed_mask=None):
+    """The rank rule of ``ops.rank_scores_mc`` on a materialised (m, v) matrix of probabilities: ``sort_and_rank``'s predicates
+    (a NaN candidate or a NaN target counts as better, ties count half), the target itself left out; the filtered rank also
+    leaves out the candidates of ``listed_mask`` (dense (m, v) bool), NaN ones included.  Returns ``(raw, filtered)``, 0-based
+    float mid-ranks; ``filtered`` is None without a mask."""
+    t = target.view(-1, 1).to(pbar.device)
+    tgt = pbar.gather(1, t)
+    other = torch.ones_like(pbar, dtype=torch.bool).scatter_(1, t, False)
+    better, equal = (~(pbar <= tgt)) & other, (pbar == tgt) & other
+
+    def rank(pool):
+        return (better & pool).sum(dim=1).float() + 0.5 * (equal & pool).sum(dim=1).float()
+    return rank(other), (None if listed_mask is None else rank(~listed_mask.to(pbar.device)))
+
+
+def _mc_args(z, w, flow_log_probs):
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] < 1:
+        raise ValueError('z: expected the (S, N, h) samples of KGVAE.posterior_samples, S >= 1')
+    z = z.detach().contiguous()
+    flp = None
+    if flow_log_probs is not None:
+        flp = torch.as_tensor(flow_log_probs).detach().reshape(-1).to(device=z.device, dtype=torch.float32)
+        if flp.numel() != z.shape[0]:
+            raise ValueError(f'flow_log_probs: one value per sample ({z.shape[0]}), got {flp.numel()}')
+    return z, w.detach().to(z.device), flp
+
+
+def _mc_queries(z, w, a, r):
+    """Q_s = z_s[a] * w[r] for every sample, as one (S, rows, h) stack."""
+    return ops.mul(z[:, a].contiguous(), w[r].unsqueeze(0).expand(z.shape[0], -1, -1).contiguous())
+
+
+def _mc_pbar_unfused(z, w, a, r, flp):
+    """pbar of a chunk of queries from one fp32 GEMM per sample (ops.gemm) + torch: (rows, N) float32."""
+    total = None
+    for s in range(z.shape[0]):
+        score = ops.gemm(ops.mul(z[s][a].contiguous(), w[r].contiguous()), z[s], trans_b=True, precision='f32')
+        if flp is not None:
+            score = score + flp[s]
+        p = torch.sigmoid(score)
+        total = p if total is None else total + p
+    return total * (1.0 / z.shape[0])
+
+
+def _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, fused):
+    ent = filter_index.entities(direction, z.device) if filter_index is not None else None
+    raw, filt = [], []
+    step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
+    for lo in range(0, n, step):
+        sl = slice(lo, min(n, lo + step))
+        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+        if fused:
+            rr, rf, _ = ops.rank_scores_mc(_mc_queries(z, w, a[sl], r[sl]), z, b[sl], flp, f_lo, f_hi, ent)
+        else:
+            pbar = _mc_pbar_unfused(z, w, a[sl], r[sl], flp)
+            listed = None if ent is None else _listed_mask(f_lo, f_hi, ent, pbar.shape[0], pbar.shape[1], pbar.device)
+            rr, rf = mc_ranks_from_probs(pbar, b[sl], listed)
+        raw.append(rr)
+        filt.append(rf)
+    if not raw:
+        empty = torch.zeros(0, dtype=torch.float32, device=z.device)
+        return empty, (empty.clone() if filter_index is not None else None)
+    return torch.cat(raw), (torch.cat(filt) if filter_index is not None else None)
+
+
+def perturb_and_get_rank_mc(z, w, a, r, b, test_size, filter_index=None, direction='o', batch_size=100, all_batches=True,
+                            flow_log_probs=None):
+    """(raw, filtered) posterior-predictive ranks of ``b`` for the queries (a, r) under the samples ``z`` (S, N, h): one fused
+    launch pair per ``MC_STACK_ROWS`` queries (ops.rank_scores_mc).  ``filtered`` is None without a ``filter_index``."""
+    z, w, flp = _mc_args(z, w, flow_log_probs)
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    return _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, True)
+
+
+def perturb_and_get_rank_mc_unfused(z, w, a, r, b, test_size, filter_index=None, direction='o', batch_size=100, all_batches=True,
+                                    flow_log_probs=None):
+    """``perturb_and_get_rank_mc`` from materialised probabilities (S GEMMs, sigmoids and a running sum per chunk, then
+    ``mc_ranks_from_probs``): the in-repo cross-check and the bench's baseline."""
+    z, w, flp = _mc_args(z, w, flow_log_probs)
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    return _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, False)
+
+
+def _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, fused):
+    with torch.no_grad():
+        z, w, flp = _mc_args(z, w, flow_log_probs)
+        test_triplets = test_triplets.to(z.device)
+        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
+        n = test_triplets.shape[0]
+        n = min(n, eval_bz) if all_batches is False else n
+        raw_s, filt_s = _perturb_and_get_rank_mc(z, w, o, r, s, n, filter_index, 's', flp, fused)
+        raw_o, filt_o = _perturb_and_get_rank_mc(z, w, s, r, o, n, filter_index, 'o', flp, fused)
+        kinds = [('raw', torch.cat([raw_s, raw_o]) + 1)]
+        if filter_index is not None:
+            kinds.append(('filtered', torch.cat([filt_s, filt_o]) + 1))
+        out = {'n_samples': int(z.shape[0])}
+        for kind, ranks in kinds:
+            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
+            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
+        if verbose:
+            for kind, _ in kinds:
+                print("MC MRR ({}, {} samples): {:.6f}".format(kind, out['n_samples'], out['mrr_' + kind]))
+                for hit in hits:
+                    print("MC Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
+    return out
+
+
+def calc_mc_mrr(z, w, test_triplets, filter_index=None, flow_log_probs=None, hits=[1, 3, 10], eval_bz=100, all_batches=True,
+                verbose=True):
+    """Posterior-predictive MRR / Hits@k over both directions from the samples ``z`` (S, N, h) of ``KGVAE.posterior_samples``
+    (``flow_log_probs``: its second result): every test triplet is ranked on ``pbar = mean_s sigmoid(logit_s)``.  Returns
+    ``{'mrr_raw', 'hits_raw': {k: v}, 'n_samples'}`` and with a ``FilterIndex`` also ``'mrr_filtered'``, ``'hits_filtered'``, in
+    the shape of ``calc_filtered_mrr``'s result.  For a fixed seed of the samples the figures are reproducible."""
+    return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, True)
+
+
+def calc_mc_mrr_unfused(z, w, test_triplets, filter_index=None, flow_log_probs=None, hits=[1, 3, 10], eval_bz=100,
+                        all_batches=True, verbose=True):
+    """``calc_mc_mrr`` on the materialised route (``perturb_and_get_rank_mc_unfused``)."""
+    return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, False)
+
+
+def _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, fused):
+    if direction not in ('o', 's'):
+        raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
+    z, w, flp = _mc_args(z, w, flow_log_probs)
+    ent = filter_index.entities(direction, z.device) if filter_index is not None else None
+    ids, mean, std = [], [], []
+    step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
+    for lo in range(0, a.shape[0], step):
+        sl = slice(lo, min(a.shape[0], lo + step))
+        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+        if fused:
+            q = _mc_queries(z, w, a[sl], r[sl])
+            i, p = ops.topk_scores_mc(q, z, k, flp, f_lo, f_hi, ent)
+            sd = ops.pair_prob_std_mc(q, z, i, flp)
+        else:
+            i, p = topk_from_scores(_mc_pbar_unfused(z, w, a[sl], r[sl], flp), k, f_lo, f_hi, ent)
+            pick = i.clamp(min=0)
+            ps = []
+            for s in range(z.shape[0]):        # the selected pairs' probability in every sample, from the same GEMMs
+                score = ops.gemm(ops.mul(z[s][a[sl]].contiguous(), w[r[sl]].contiguous()), z[s], trans_b=True, precision='f32')
+                ps.append(torch.sigmoid(score if flp is None else score + flp[s]).gather(1, pick))
+            sd = torch.stack(ps).std(dim=0, unbiased=False)
+            sd[i < 0] = 0.0
+        ids.append(i)
+        mean.append(p)
+        std.append(sd)
+    if not ids:
+        f32 = dict(dtype=torch.float32, device=z.device)
+        return torch.zeros(0, k, dtype=torch.int64, device=z.device), torch.zeros(0, k, **f32), torch.zeros(0, k, **f32)
+    return torch.cat(ids), torch.cat(mean), torch.cat(std)
+
+
+def predict_topk_mc(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None):
+    """Posterior-predictive link prediction from the samples ``z`` (S, N, h): the ``k`` entities of highest
+    ``pbar = mean_s sigmoid(logit_s)`` for every query (``direction`` and ``filter_index`` as ``predict_topk`` takes them), and
+    how sure the model is of each: returns ``(ids int64 (n, k), prob_mean float32 (n, k), prob_std float32 (n, k))``,
+    ``prob_std`` the population standard deviation of the pair's probability over the samples.  Rows with fewer than k
+    candidates are padded with id -1, mean -inf, std 0.  One fused launch pair plus the spread kernel per ``MC_STACK_ROWS``
+    queries (ops.topk_scores_mc, ops.pair_prob_std_mc)."""
+    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, True)
+
+
+def predict_topk_mc_unfused(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None):
+    """``predict_topk_mc`` from materialised probabilities (S GEMMs per chunk + ``topk_from_scores``): the in-repo cross-check
+    and the bench's baseline."""
+    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, False)
 
 
 MineOverflow = ops.MineOverflow

@@ -144,6 +144,25 @@ def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=N
     return n
 
 
+def write_mc_predictions(path, z, w, triplets, k, filter_index, flow_log_probs=None):
+    """``write_predictions`` under the posterior predictive of the samples ``z`` (S, N, h) (ranking.predict_topk_mc), as TSV:
+    ``direction  query_entity  relation  position  predicted_entity  prob_mean  prob_std`` -- the mean and the population standard
+    deviation over the samples of the pair's probability; a query with fewer than k candidates ends in id -1, mean -inf, std 0.
+    Returns the number of lines written."""
+    n = 0
+    with torch.no_grad(), open(path, 'w') as f:
+        for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
+            r = triplets[:, 1]
+            ids, mean, std = ranking.predict_topk_mc(z, w, a, r, k, direction=d, filter_index=filter_index,
+                                                     flow_log_probs=flow_log_probs)
+            a, r, ids, mean, std = a.tolist(), r.tolist(), ids.tolist(), mean.tolist(), std.tolist()
+            for i in range(len(a)):
+                head = f"{d}\t{a[i]}\t{r[i]}\t"
+                f.writelines(f"{head}{p}\t{e}\t{x:.9g}\t{y:.9g}\n" for p, (e, x, y) in enumerate(zip(ids[i], mean[i], std[i])))
+                n += len(ids[i])
+    return n
+
+
 def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None):
     """Knowledge-graph completion as TSV, ``s  r  o  rank  logit``: the new triplets (``filter_index``: the known ones left out,
     s != o) that ``ranking.mine_triplets`` selects among ALL N x R x N -- the ``k`` most confident and / or those whose
@@ -189,6 +208,18 @@ def check_args(args):
         if not getattr(args, 'filtered_eval', False):
             raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, '
                              'filtered_constrained')
+    if getattr(args, 'mc_samples', 0) < 0:
+        raise ValueError(f'--mc-samples counts posterior samples: 0 (off) or more, got {args.mc_samples}')
+    if getattr(args, 'mc_samples', 0) > 0:
+        if args.test_mode is not True:
+            raise ValueError('--mc-samples reports on / predicts from a trained checkpoint: pass --test-mode True '
+                             '(and --model-state-file)')
+        if args.model_class != 'KGVAE':
+            raise ValueError('--mc-samples needs --model-class KGVAE: the RGCN encoder is deterministic, it has no posterior '
+                             'to sample')
+        if getattr(args, 'type_constrain', False):
+            raise ValueError('--mc-samples with --type-constrain is not supported: the posterior-predictive ranker has no '
+                             'type-constrained form yet')
 
 
 def main(args):
@@ -259,15 +290,30 @@ def main(args):
             print(f"wrote {_write_triplets(args.sample_out, trip, logits)} triplets of a graph decoded from {args.sample_graph} "
                   f"prior samples to {args.sample_out}")
         if types is not None:
-            return ranking.calc_constrained_mrr(embed, model.w_relation, test_t, filters, types, hits=[1, 3, 10],
-                                                eval_bz=args.eval_batch_size, all_batches=True,
-                                                flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
-        if filters is not None:
-            return ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
-                                             eval_bz=args.eval_batch_size, all_batches=True,
-                                             flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
-        return ranking.calc_mrr(embed, model.w_relation, test_t, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
-                                all_batches=True, flow_log_prob=model.encoder.get_flow_log_prob())
+            mrr = ranking.calc_constrained_mrr(embed, model.w_relation, test_t, filters, types, hits=[1, 3, 10],
+                                               eval_bz=args.eval_batch_size, all_batches=True,
+                                               flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
+        elif filters is not None:
+            mrr = ranking.calc_filtered_mrr(embed, model.w_relation, test_t, filters, hits=[1, 3, 10],
+                                            eval_bz=args.eval_batch_size, all_batches=True,
+                                            flow_log_prob=model.encoder.get_flow_log_prob())['mrr_raw']
+        else:
+            mrr = ranking.calc_mrr(embed, model.w_relation, test_t, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
+                                   all_batches=True, flow_log_prob=model.encoder.get_flow_log_prob())
+        if getattr(args, 'mc_samples', 0) > 0:
+            # the posterior predictive, after everything the single draw reports: S seeded samples of the latents, one encoder pass
+            z, flps = model.encoder.posterior_samples(test_graph, test_node_id, test_rel, test_norm, args.mc_samples,
+                                                      seed=args.mc_seed)
+            print(f"\nMonte-Carlo posterior predictive: {args.mc_samples} samples, seed {args.mc_seed}")
+            ranking.calc_mc_mrr(z, model.w_relation, test_t, filters, flps, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
+                                all_batches=True)
+            if getattr(args, 'predict_topk', 0) > 0:
+                known = filters if filters is not None else \
+                    ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+                n_lines = write_mc_predictions(args.mc_predict_out, z, model.w_relation, test_t, args.predict_topk, known, flps)
+                print(f"wrote {n_lines} posterior-predictive predictions (top {args.predict_topk}, both directions, known "
+                      f"triplets filtered, mean and spread over {args.mc_samples} samples) to {args.mc_predict_out}")
+        return mrr
 
     print("start training...")
     epoch, best_mrr = 0, 0
@@ -415,6 +461,14 @@ def build_parser():
                         "(train + valid + test triplets filtered out) to --predict-out; 0 = off; not a reference flag")
     p.add_argument("--predict-out", type=str, default="predictions.tsv",
                    help="TSV of --predict-topk: direction, query entity, relation, position, predicted entity, logit")
+    p.add_argument("--mc-samples", type=int, default=0,
+                   help="with --test-mode (KGVAE): after the usual report, rank on the Monte-Carlo posterior predictive -- the "
+                        "mean over S seeded posterior samples of the triplet probability -- raw, and filtered under "
+                        "--filtered-eval; with --predict-topk also write --mc-predict-out; 0 = off; not a reference flag")
+    p.add_argument("--mc-seed", type=int, default=0, help="seed of the --mc-samples posterior samples")
+    p.add_argument("--mc-predict-out", type=str, default="mc_predictions.tsv",
+                   help="TSV of --mc-samples with --predict-topk: direction, query entity, relation, position, predicted entity, "
+                        "mean and standard deviation over the samples of its probability")
     p.add_argument("--complete-topk", type=int, default=0,
                    help="with --test-mode: score ALL triplets (s, r, o) and write the K most confident NEW ones (train + valid + "
                         "test triplets and s == o left out) to --complete-out; 0 = off; not a reference flag")

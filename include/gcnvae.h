@@ -565,6 +565,36 @@ int gv_topk_scores_constrained(const float* q, int ld_q, const float* e, int ld_
                                const int32_t* cand_set, int k, int* out_ids, float* out_logits, void* workspace, int m, int v, int h,
                                void* stream);
 
+/* Monte-Carlo posterior-predictive ranking and top-k for a variational encoder: S posterior samples instead of one draw.
+ * Sample s has a query matrix Q_s (m, h) at q + s * q_stride and an entity table E_s (v, h) at e + s * e_stride (strides in
+ * elements; the leading dimensions ld_q / ld_e are shared by the samples) and an optional bias[s] (that draw's flow_log_prob;
+ * bias NULL: none).  With
+ *   logit_s[i, j] = Q_s[i] . E_s[j] + bias[s]          -- gv_gemm_f32 + bias bit for bit, as the single-sample entries' logits
+ *   sig(x)        = v_rcp_f32(1.0f + __expf(-x))       -- +inf -> 1, -inf -> 0, NaN -> NaN
+ *   pbar[i, j]    = (sum over s = 0 .. S-1 ascending of sig(logit_s[i, j])) * (1.0f / S)      -- fp32; NaN in any sample -> NaN
+ * the value that is ranked / selected is pbar, which never leaves the registers.  pbar is bounded, so unlike a logit it can
+ * saturate: candidates whose every sample rounds to 1.0f tie (mid-rank in the ranker, lower id first in the top-k).
+ * n_samples >= 1; with n_samples > 1, q_stride >= (m - 1) * ld_q + h and e_stride >= (v - 1) * ld_e + h.
+ *   gv_rank_scores_mc : the counts of gv_rank_scores_filtered taken on pbar -- 2 * #above + #equal, a NaN candidate or a NaN target
+ *     counts as above, the target's own column and the listed candidates do not vote.  filt_lo / filt_hi / filt_ent all NULL: the
+ *     raw count alone (count_filt is not written and may be NULL).  tgt: m floats of workspace, receives pbar[i, target[i]];
+ *     count_raw / count_filt int32 [m] (zeroed here).
+ *   gv_topk_scores_mc : gv_topk_scores with pbar as the key's value: same order (value descending, ties by lower id, NaN last),
+ *     same filter, same padding (id -1, value -inf), 1 <= k <= 128, workspace of gv_topk_scores_workspace_bytes(m, v, k) bytes.
+ *     out_prob [m, k] holds the very values gv_rank_scores_mc votes on.
+ *   gv_pair_prob_std_mc : for every pair (i, ids[i * k + c]) the population standard deviation over the samples of sig(logit_s),
+ *     two-pass (mean, then deviations) in fp32.  Here the logit is a plain ascending-k fmaf dot, NOT the tile's MFMA chain: the
+ *     mean behind it may differ from out_prob in the last bits.  An id outside [0, v) (the padding id -1) gives 0; S = 1 gives
+ *     exactly 0.  ids int32 [m, k], out_std fp32 [m, k]. */
+int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                      const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                      int n_filt_ent, float* tgt, int* count_raw, int* count_filt, int m, int v, int h, void* stream);
+int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                      const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int k,
+                      int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream);
+int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                        const float* bias, const int* ids, int k, float* out_std, int m, int v, int h, void* stream);
+
 /* Whole-graph triplet mining (csrc/k_mine.hip): every triplet of a DistMult decoder scored and selected globally, for the
  * entity table e (n, h) and the relation rows w (num_rels, h), both fp32 row-major:
  *   logit[s, r, o] = (e[s] * w[r]) . e[o] (+ *bias)
