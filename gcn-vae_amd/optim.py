@@ -7,6 +7,14 @@ the norm from the partials in a fixed order and clearing the gradient it has con
 per-tensor / foreach kernel sets, and every address is static -- the step is hipGraph-capturable.
 Numerics follow ``torch.nn.utils.clip_grad_norm_`` (coefficient min(1, max_norm / (norm + 1e-6))) and
 ``torch.optim.Adam`` (bias correction, eps added outside the square root).
+
+The C ABI takes lr, the betas, eps and max_norm as ``float``: the kernel is a self-consistent Adam on the float32-rounded values,
+and beta2 = float32(0.999) = 0.99900001287 makes ``exp_avg_sq`` 1.3e-5 (relative) smaller than torch's with the double 0.999; the
+tests' references take the rounded values.  ``grad_norm()`` is the norm BEFORE the clip, as ``clip_grad_norm_`` returns it.
+Non-finite gradients (pinned by tests/test_gpu_flat_adam.py, not endorsed): ``grad_norm()`` turns non-finite, which is what a driver
+should look at.  With a NaN the clip coefficient is fminf(1, NaN) = 1: the step runs UNCLIPPED, the NaN poisons its own element
+(parameter and both moments) and no other, where torch's clip multiplies every gradient by NaN and loses every parameter.  With
+an inf the coefficient is 0, as torch's: the element itself becomes inf * 0 = NaN and every other sees a zero gradient.
 """
 import torch
 
