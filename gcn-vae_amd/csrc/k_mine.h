@@ -18,6 +18,12 @@
 // The filter: the (lo, hi, ent) ranges per key s * R + r are re-bucketed per tile pair first (mine_prepare), so a workgroup reads
 // ITS listed triplets once into LDS (mine_filter_load) and a relation without one -- nearly all of them -- costs one LDS flag
 // (mine_filter_relation).  No float atomics anywhere.
+//
+// The type-constrained miners (gv_mine_scores_typed, gv_transe_mine_typed) walk the transposed order -- a workgroup owns relation
+// r, one 64-row tile of r's SUBJECT member list and a span of 64-row tiles of r's OBJECT member list, rows gathered through the
+// member ids -- and share the same keys, gate, ballot, emission and histogram (mine_put); what differs is where a candidate's ids
+// come from (the member lists, MineTyped) and the filter: gathered tiles do not fit the per-tile-pair buckets, so a workgroup reads
+// the (lo, hi, ent) ranges of its 64 subjects directly (mine_typed_filter).
 #pragma once
 #include "common.h"
 
@@ -55,12 +61,39 @@ struct MineSelect {
     unsigned long long* hist;
 };
 
+// ---- the member lists and the work units of the type-constrained miners ----------------------------------------------------------
+struct MineTyped {
+    const long long* set_ptr;          // [2 R + 1]: set r = the objects of r, set R + r = its subjects (ranking.TypeConstraint)
+    const int* set_ids;                // each set's members, ascending
+    const int4* units;                 // (r, subject tile, first object tile, end object tile), tiles of 64 members
+    const int* filt_lo;                // the filter as given: key s * R + r -> filt_ent[lo:hi], ascending; NULL: none
+    const int* filt_hi;
+    const int* filt_ent;
+    int n_filt_ent;
+};
+
 // ---- host side, compiled once (k_mine.hip) -----------------------------------------------------------------------------------
 // bytes of the re-bucketed filter of an n-entity table with n_filt_ent listed objects (0 for an empty table)
 int64_t mine_filter_workspace_bytes(int n, int n_filt_ent);
 
-// What both entries do before their launch, `who` being the entry's name in every message: the checks of the arguments they share,
-// *sel filled (rel_span: about four workgroups per CU of the MI355X when the table has few tiles; the result does not depend on
+// What all four entries check alike, `who` being the entry's name in every message: sizes, mode, the capacity or the histogram
+// level, the filter given whole or not at all and (n > 0) the outputs of the mode; *sel filled but for rel_span and the filter.
+int mine_select_args(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                     int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                     int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, MineSelect* sel);
+
+// the counter (EMIT) or the histogram (HIST) cleared on the stream
+int mine_clear(const char* who, int mode, int bin_bits, uint64_t* counter, uint64_t* hist, hipStream_t st);
+
+// What the two type-constrained entries do before their launch: mine_select_args, the checks of the member lists and the unit list,
+// *ty filled, the counter or the histogram cleared.  GV_OK: launch n_units workgroups, unless n == 0 or n_units == 0.
+int mine_typed_prepare(const char* who, int n, int num_rels, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units,
+                       int64_t n_units, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                       int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out,
+                       int64_t capacity, uint64_t* counter, uint64_t* hist, hipStream_t st, MineSelect* sel, MineTyped* ty);
+
+// What the two whole-graph entries do before their launch: mine_select_args, then
+// *sel completed (rel_span: about four workgroups per CU of the MI355X when the table has few tiles; the result does not depend on
 // it), the filter re-bucketed per tile pair into the workspace (count, scan, fill: three small kernels, integer atomics), the
 // counter (EMIT) or the histogram (HIST) cleared, *grid = (object tiles, subject tiles, relation spans).  GV_OK: launch, unless
 // n == 0 (nothing was queued, nothing is to be done).
@@ -124,6 +157,18 @@ __device__ __forceinline__ void mine_emit(bool ok, int lane, int s, int r, int o
     }
 }
 
+// One gated key of candidate (s, r, o), called by every lane of a wave together (`ok` false: this lane has none to put): counted in
+// hist_s or emitted with value_bits.
+template <bool HIST>
+__device__ __forceinline__ void mine_put(bool ok, unsigned key, int value_bits, int s, int r, int o, int lane, unsigned* hist_s,
+                                         const MineSelect& sel) {
+    if (HIST) {
+        if (ok) atomicAdd(&hist_s[(key >> (32 - sel.prefix_bits - sel.bin_bits)) & ((1u << sel.bin_bits) - 1u)], 1u);
+    } else {
+        mine_emit(ok, lane, s, r, o, value_bits, sel.out, sel.capacity, sel.counter);
+    }
+}
+
 // One gated key of candidate (rl, cl) of tile pair (m0, n0) under relation r, called by every lane of a wave together (key 0: this
 // lane has none): dropped when the relation's mask lists it (`listed`: the relation has listed triplets in this tile pair), else
 // counted in hist_s or emitted with value_bits.
@@ -132,10 +177,47 @@ __device__ __forceinline__ void mine_take(unsigned key, int value_bits, int rl, 
                                           const unsigned long long* mask, unsigned* hist_s, const MineSelect& sel) {
     bool ok = key != 0u;
     if (listed && ok) ok = !((mask[rl] >> cl) & 1ull);
-    if (HIST) {
-        if (ok) atomicAdd(&hist_s[(key >> (32 - sel.prefix_bits - sel.bin_bits)) & ((1u << sel.bin_bits) - 1u)], 1u);
-    } else {
-        mine_emit(ok, lane, m0 + rl, r, n0 + cl, value_bits, sel.out, sel.capacity, sel.counter);
+    mine_put<HIST>(ok, key, value_bits, m0 + rl, r, n0 + cl, lane, hist_s, sel);
+}
+
+// ---- device side: the type-constrained miners' tiles -----------------------------------------------------------------------------
+// the member ids of 64-row tile `tile` of set `set` into ids_s [64] (-1 past the list's end or for an id outside the table, which
+// then is no candidate and gathers nothing), by the threads with 0 <= tl < 64
+__device__ __forceinline__ void mine_typed_ids(const MineTyped& ty, int set, int tile, int n, int tl, int* ids_s) {
+    if (tl < 64) {
+        const long long at = ty.set_ptr[set] + (long long)tile * 64 + tl;
+        int id = -1;
+        if (tile >= 0 && at < ty.set_ptr[set + 1]) id = ty.set_ids[at];
+        ids_s[tl] = (unsigned)id < (unsigned)n ? id : -1;
+    }
+}
+
+// The listed objects of relation r per subject row of a gathered tile pair -> mask [64] (zeroed before, behind a barrier), by 256
+// threads tl, four per row.  The tile's object ids are ascending, so a row's listed objects inside their range are one window of its
+// sorted list: found by bisection, walked, each entry looked up among the 64 ids in LDS.  A row without a list costs its two loads.
+__device__ __forceinline__ void mine_typed_filter(const MineTyped& ty, int num_rels, int r, const int* sid_s, const int* oid_s, int tl,
+                                                  unsigned long long* mask) {
+    if (!ty.filt_lo) return;
+    const int row = tl >> 2, s = sid_s[row];
+    if (s < 0 || oid_s[0] < 0) return;
+    const long long key = (long long)s * num_rels + r;
+    const int lo = min(max(ty.filt_lo[key], 0), ty.n_filt_ent), hi = min(max(ty.filt_hi[key], lo), ty.n_filt_ent);
+    if (lo == hi) return;
+    int cnt = 64;                                        // the tile's live columns: a prefix
+    if (oid_s[63] < 0) {
+        int a = 0, b = 63;                               // oid_s[a] >= 0 > oid_s[b]
+        while (b - a > 1) { const int m = (a + b) >> 1; if (oid_s[m] >= 0) a = m; else b = m; }
+        cnt = b;
+    }
+    const int o_min = oid_s[0], o_max = oid_s[cnt - 1];
+    int a = lo, b = hi;                                  // the first entry >= o_min
+    while (a < b) { const int m = (a + b) >> 1; if (ty.filt_ent[m] < o_min) a = m + 1; else b = m; }
+    for (int j = a + (tl & 3); j < hi; j += 4) {
+        const int e = ty.filt_ent[j];
+        if (e > o_max) break;
+        int x = 0, y = cnt;                              // the first column with id >= e
+        while (x < y) { const int m = (x + y) >> 1; if (oid_s[m] < e) x = m + 1; else y = m; }
+        if (x < cnt && oid_s[x] == e) atomicOr(&mask[row], 1ull << x);
     }
 }
 

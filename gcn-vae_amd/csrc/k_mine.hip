@@ -13,8 +13,9 @@
 // 16 lanes of a b128 group fall on 16 distinct 16-byte slots).
 //
 // Candidates, keys, the filter and the EMIT / HIST epilogues: k_mine.h, which both miners share; a record's fourth word is the logit
-// (mine_key_logit of its key: -0 as +0).  This file is also the one home of what the two entries do on the host before their
-// launch (mine_prepare) and of the three small kernels that re-bucket the filter.
+// (mine_key_logit of its key: -0 as +0).  This file is also the one home of what the mining entries do on the host before their
+// launch (mine_select_args, mine_prepare, mine_typed_prepare), of the three small kernels that re-bucket the filter, and of the
+// type-constrained sweep gv_mine_scores_typed (k_mine_typed, further down), which walks the transposed order.
 #include <limits.h>
 
 #include <algorithm>
@@ -270,10 +271,9 @@ static bool mine_filter_rebucket(const int32_t* filt_lo, const int32_t* filt_hi,
     return true;
 }
 
-int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
-                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
-                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
-                 hipStream_t st, MineSelect* sel, dim3* grid) {
+int mine_select_args(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                     int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                     int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, MineSelect* sel) {
     GV_REQUIRE(n >= 0 && num_rels > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: n=%d num_rels=%d n_filt_ent=%d", who, n, num_rels,
                n_filt_ent);
     GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "%s: unknown mode %d", who, mode);
@@ -289,6 +289,13 @@ int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, c
                    GV_ERR_SHAPE, "%s: prefix_bits=%d prefix=%u bin_bits=%d out of range", who, prefix_bits, prefix, bin_bits);
     GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
                "%s: filt_lo / filt_hi / filt_ent must be all given or all NULL", who);
+    *sel = MineSelect{};
+    sel->n = n; sel->num_rels = num_rels;
+    sel->rel_span = num_rels;
+    sel->exclude_self = exclude_self ? 1 : 0;
+    sel->key_min = key_min; sel->prefix_bits = prefix_bits; sel->bin_bits = bin_bits; sel->prefix = prefix;
+    sel->out = (int4*)out; sel->capacity = capacity;
+    sel->counter = (unsigned long long*)counter; sel->hist = (unsigned long long*)hist;
     if (n == 0) return GV_OK;
     if (mode == GV_MINE_EMIT) {
         GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "%s: NULL output", who);
@@ -296,6 +303,24 @@ int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, c
     } else {
         GV_REQUIRE(hist, GV_ERR_NULL, "%s: NULL histogram", who);
     }
+    return GV_OK;
+}
+
+int mine_clear(const char* who, int mode, int bin_bits, uint64_t* counter, uint64_t* hist, hipStream_t st) {
+    char fill[64];
+    snprintf(fill, sizeof fill, "%s(fill)", who);
+    const bool emit = mode == GV_MINE_EMIT;
+    if (fill_words(emit ? (void*)counter : (void*)hist, 0u, emit ? 8 : (size_t)8 << bin_bits, st) != hipSuccess) return launch_status(fill);
+    return GV_OK;
+}
+
+int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
+                 hipStream_t st, MineSelect* sel, dim3* grid) {
+    const int rc = mine_select_args(who, n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
+                                    prefix, bin_bits, out, capacity, counter, hist, sel);
+    if (rc != GV_OK || n == 0) return rc;
     const bool filtered = filt_lo != nullptr;
     if (filtered) {
         GV_REQUIRE(workspace, GV_ERR_NULL, "%s: a filter needs the workspace", who);
@@ -307,22 +332,161 @@ int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, c
     const int tiles = tiles_1d * tiles_1d;
     long long spans = (4LL * 256 + tiles - 1) / tiles;
     spans = std::max(1LL, std::min(spans, (long long)num_rels));
-    *sel = MineSelect{};
-    sel->n = n; sel->num_rels = num_rels;
     sel->rel_span = (int)((num_rels + spans - 1) / spans);
-    sel->exclude_self = exclude_self ? 1 : 0;
-    sel->key_min = key_min; sel->prefix_bits = prefix_bits; sel->bin_bits = bin_bits; sel->prefix = prefix;
-    sel->out = (int4*)out; sel->capacity = capacity;
-    sel->counter = (unsigned long long*)counter; sel->hist = (unsigned long long*)hist;
     *grid = dim3(tiles_1d, tiles_1d, (num_rels + sel->rel_span - 1) / sel->rel_span);
 
-    char fill[64];
-    snprintf(fill, sizeof fill, "%s(fill)", who);
-    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &sel->tile_ptr, &sel->tile_ent))
+    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &sel->tile_ptr, &sel->tile_ent)) {
+        char fill[64];
+        snprintf(fill, sizeof fill, "%s(fill)", who);
         return launch_status(fill);
-    const bool emit = mode == GV_MINE_EMIT;
-    if (fill_words(emit ? (void*)counter : (void*)hist, 0u, emit ? 8 : (size_t)8 << bin_bits, st) != hipSuccess) return launch_status(fill);
-    return GV_OK;
+    }
+    return mine_clear(who, mode, bin_bits, counter, hist, st);
+}
+
+int mine_typed_prepare(const char* who, int n, int num_rels, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units,
+                       int64_t n_units, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                       int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out,
+                       int64_t capacity, uint64_t* counter, uint64_t* hist, hipStream_t st, MineSelect* sel, MineTyped* ty) {
+    const int rc = mine_select_args(who, n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
+                                    prefix, bin_bits, out, capacity, counter, hist, sel);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE(n_units >= 0 && n_units <= INT_MAX, GV_ERR_SHAPE, "%s: n_units=%lld outside [0, 2^31)", who, (long long)n_units);
+    if (n == 0) return GV_OK;
+    GV_REQUIRE(n_units == 0 || (set_ptr && set_ids && units), GV_ERR_NULL, "%s: NULL member lists or unit list", who);
+    GV_REQUIRE(aligned16(units), GV_ERR_SHAPE, "%s: units is not 16-byte aligned", who);          // int4 records
+    *ty = MineTyped{};
+    ty->set_ptr = (const long long*)set_ptr; ty->set_ids = set_ids; ty->units = (const int4*)units;
+    ty->filt_lo = filt_lo; ty->filt_hi = filt_hi; ty->filt_ent = filt_ent; ty->n_filt_ent = n_filt_ent;
+    return mine_clear(who, mode, bin_bits, counter, hist, st);
+}
+
+// ---- the type-constrained sweep (gv_mine_scores_typed) -----------------------------------------------------------------------------
+// Loop order, transposed: a workgroup owns one unit = (relation r, one 64-row tile of r's subject members, a span of 64-row tiles
+// of r's object members).  Rows of E are GATHERED through the member ids into the LDS layout of k_mine; the subject tile and w[r]
+// are staged once per unit while the table fits one chunk, an object tile once per tile pair (no other relation could reuse it: its
+// rows belong to r's list).  The arithmetic per pair is k_mine's: (E[s] * w[r]) in f32, the k-ordered 32x32x2 chain over ceil16(h),
+// + bias; so a surviving triplet's logit is the unconstrained miner's, bit for bit.
+__device__ __forceinline__ void mine_stage_gather(float* dst, const float* e, int ld, bool vec, const int* ids_s, int k0, int h, int kc) {
+    const int q4 = kc >> 2, pitch = kc + 4, half = kc >> 1;
+    for (int idx = threadIdx.x; idx < 64 * q4; idx += 256) {
+        const int rl = idx / q4, q = idx - rl * q4;
+        const int row = ids_s[rl], k = k0 + 4 * q;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (row >= 0) {
+            const float* src = e + (size_t)row * ld + k;
+            if (vec && k + 3 < h) {
+                const float4 t = *reinterpret_cast<const float4*>(src);
+                v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = k + i < h ? src[i] : 0.f;
+            }
+        }
+        float* d = dst + rl * pitch + 2 * q;
+        *reinterpret_cast<float2*>(d) = make_float2(v[0], v[2]);
+        *reinterpret_cast<float2*>(d + half) = make_float2(v[1], v[3]);
+    }
+}
+
+struct MineTypedParams {
+    MineParams p;
+    MineTyped ty;
+};
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
+    extern __shared__ __attribute__((aligned(16))) float mine_smem[];
+    __shared__ unsigned long long fmask[64];             // the tile pair's listed objects per subject row
+    __shared__ int sid_s[64], oid_s[64];                 // the tiles' entity ids, -1 past the lists
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const MineParams& p = tp.p;
+    const MineTyped& ty = tp.ty;
+    const MineSelect& sel = p.sel;
+    const int kc = p.kc, pitch = kc + 4, half = kc >> 1;
+    float* As = mine_smem;
+    float* Bs = As + 64 * pitch;
+    float* Ws = Bs + 64 * pitch;                         // [kc + 4]
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int4 unit = ty.units[blockIdx.x];
+    const int r = unit.x;
+    if (r < 0 || r >= sel.num_rels) return;              // uniform: not a unit
+    const bool resident = p.n_chunks == 1;
+    const float bv = p.bias ? *p.bias : 0.f;
+
+    mine_typed_ids(ty, sel.num_rels + r, unit.y, sel.n, t, sid_s);
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
+    __syncthreads();
+    if (resident) {
+        mine_stage_gather(As, p.e, p.ld_e, p.vec_e, sid_s, 0, p.h, kc);
+        if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, 4 * t));
+    }
+    const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
+
+    for (int ot = unit.z; ot < unit.w; ++ot) {
+        __syncthreads();                                 // the last tile's reads of Bs, oid_s and fmask are over
+        mine_typed_ids(ty, r, ot, sel.n, t, oid_s);
+        if (t < 64) fmask[t] = 0ull;
+        __syncthreads();
+        mine_typed_filter(ty, sel.num_rels, r, sid_s, oid_s, t, fmask);
+
+        mine_f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc;
+            if (c > 0) __syncthreads();
+            if (!resident) {
+                mine_stage_gather(As, p.e, p.ld_e, p.vec_e, sid_s, k0, p.h, kc);
+                if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
+            }
+            mine_stage_gather(Bs, p.e, p.ld_e, p.vec_e, oid_s, k0, p.h, kc);
+            __syncthreads();
+            const int groups = (min(kc, p.h - k0) + 15) / 16 * 2;             // as k_mine: whole 16-deep steps
+            const float* wsb = Ws + w_off;
+            float4 a_n = *reinterpret_cast<const float4*>(As + a_off);
+            float4 b_n = *reinterpret_cast<const float4*>(Bs + b_off);
+            float4 w_n = *reinterpret_cast<const float4*>(wsb);
+#pragma unroll 2
+            for (int g = 0; g < groups; ++g) {
+                const float4 a4 = a_n, b4 = b_n, w4 = w_n;
+                a_n = *reinterpret_cast<const float4*>(As + a_off + 4 * g + 4);
+                b_n = *reinterpret_cast<const float4*>(Bs + b_off + 4 * g + 4);
+                w_n = *reinterpret_cast<const float4*>(wsb + 4 * g + 4);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x * w4.x, b4.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y * w4.y, b4.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z * w4.z, b4.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w * w4.w, b4.w, acc, 0, 0, 0);
+            }
+        }
+
+        // ---- epilogue (k_mine.h), ids through the member lists; fmask is complete: a barrier followed the filter's atomics
+        const int cl = wn + l31, o = oid_s[cl];
+        unsigned key[16];
+        bool want = false;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi, s = sid_s[rl];
+            unsigned k = mine_key(acc[i] + bv);
+            if (s < 0 || o < 0 || (sel.exclude_self && s == o)) k = 0u;
+            key[i] = mine_gate<HIST>(k, sel);
+            want = want || key[i] != 0u;
+        }
+        if (__ballot(want) != 0ull) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
+                const bool ok = key[i] != 0u && !((fmask[rl] >> cl) & 1ull);
+                mine_put<HIST>(ok, key[i], __float_as_int(mine_key_logit(key[i])), sid_s[rl], r, o, lane, hist_s, sel);
+            }
+        }
+    }
+    if (HIST) {
+        __syncthreads();
+        mine_hist_flush(hist_s, sel, t);
+    }
 }
 
 }  // namespace gv
@@ -368,4 +532,42 @@ extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w
         hipLaunchKernelGGL(k_mine<true>, grid, dim3(256), lds, st, p);
     }
     return launch_status("gv_mine_scores");
+}
+
+extern "C" int gv_mine_scores_typed(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int64_t* set_ptr,
+                                    const int32_t* set_ids, const int32_t* units, int64_t n_units, const int32_t* filt_lo,
+                                    const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                                    uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                                    uint64_t* counter, uint64_t* hist, int n, int num_rels, int h, void* stream) {
+    GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE,
+               "gv_mine_scores_typed: n=%d num_rels=%d h=%d n_filt_ent=%d", n, num_rels, h, n_filt_ent);
+    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_mine_scores_typed: leading dimension too small (ld_e=%d ld_w=%d h=%d)", ld_e,
+               ld_w, h);
+    GV_REQUIRE(n == 0 || (e && w), GV_ERR_NULL, "gv_mine_scores_typed: NULL table");
+    hipStream_t st = (hipStream_t)stream;
+    MineTypedParams tp{};
+    MineParams& p = tp.p;
+    const int rc = mine_typed_prepare("gv_mine_scores_typed", n, num_rels, set_ptr, set_ids, units, n_units, filt_lo, filt_hi, filt_ent,
+                                      n_filt_ent, exclude_self, mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, counter, hist,
+                                      st, &p.sel, &tp.ty);
+    if (rc != GV_OK || n == 0 || n_units == 0) return rc;
+    p.e = e; p.w = w; p.bias = bias;
+    p.h = h; p.ld_e = ld_e; p.ld_w = ld_w;
+    p.vec_e = aligned16(e) && (ld_e % 4 == 0);
+    p.vec_w = aligned16(w) && (ld_w % 4 == 0);
+    const int h16 = (h + 15) / 16 * 16;
+    p.kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
+    p.n_chunks = (h + p.kc - 1) / p.kc;
+    const int lds = (2 * 64 + 1) * (p.kc + 4) * (int)sizeof(float);
+    const int lds_max = (2 * 64 + 1) * (MINE_KC_MAX + 4) * (int)sizeof(float);
+    if (mode == GV_MINE_EMIT) {
+        static unsigned long long raised = 0;
+        if (!raise_dynamic_lds((const void*)k_mine_typed<false>, lds_max, raised, "gv_mine_scores_typed")) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_mine_typed<false>, dim3((unsigned)n_units), dim3(256), lds, st, tp);
+    } else {
+        static unsigned long long raised = 0;
+        if (!raise_dynamic_lds((const void*)k_mine_typed<true>, lds_max, raised, "gv_mine_scores_typed")) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_mine_typed<true>, dim3((unsigned)n_units), dim3(256), lds, st, tp);
+    }
+    return launch_status("gv_mine_scores_typed");
 }

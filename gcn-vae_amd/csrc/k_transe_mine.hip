@@ -52,6 +52,19 @@ __device__ __forceinline__ void tm_stage(float* dst, const float* __restrict__ e
     }
 }
 
+// the largest accumulator value this pass looks at: keys below kmin are dropped by the epilogue whatever their value
+template <int P, bool HIST>
+__device__ __forceinline__ float tm_bound(const MineSelect& sel) {
+    const unsigned kmin = HIST ? (sel.prefix_bits ? sel.prefix << (32 - sel.prefix_bits) : 0u) : sel.key_min;
+    float bound = INFINITY;                              // in the accumulator's unit: the distance, or (p = 2) its square, rounded up
+    if (kmin > 0x007fffffu) {                            // above the key of +inf
+        const float dmax = -mine_key_logit(kmin);
+        // p = 2: a few ulps above dmax^2, and never in the subnormals, so that acc > bound implies sqrtf(acc) > dmax
+        bound = P == 1 || dmax < 0.f ? dmax : fmaxf(dmax * dmax * 1.000001f, 1e-30f);
+    }
+    return bound;
+}
+
 template <int P, bool HIST>
 __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p) {
     extern __shared__ __attribute__((aligned(16))) float tm_smem[];
@@ -71,14 +84,7 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     const bool resident = p.n_chunks == 1;
     const bool diag = sel.exclude_self && m0 == n0;
 
-    // the largest distance this pass looks at: keys below kmin are dropped by the epilogue whatever their value
-    const unsigned kmin = HIST ? (sel.prefix_bits ? sel.prefix << (32 - sel.prefix_bits) : 0u) : sel.key_min;
-    float bound = INFINITY;                              // in the accumulator's unit: the distance, or (p = 2) its square, rounded up
-    if (kmin > 0x007fffffu) {                            // above the key of +inf
-        const float dmax = -mine_key_logit(kmin);
-        // p = 2: a few ulps above dmax^2, and never in the subnormals, so that acc > bound implies sqrtf(acc) > dmax
-        bound = P == 1 || dmax < 0.f ? dmax : fmaxf(dmax * dmax * 1.000001f, 1e-30f);
-    }
+    const float bound = tm_bound<P, HIST>(sel);
 
     int f_base, f_cnt;
     mine_filter_load(sel.tile_ptr, sel.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, tl, &f_base, &f_cnt);   // every group: the same words
@@ -178,6 +184,140 @@ static int tm_launch(const TeMineParams& p, dim3 grid, int lds, int lds_max, hip
     return launch_status("gv_transe_mine");
 }
 
+// ---- the type-constrained sweep (gv_transe_mine_typed) -----------------------------------------------------------------------------
+// Loop order, transposed (k_mine.h): a workgroup owns one unit = (relation r, one 64-row tile of r's subject members, a span of
+// 64-row tiles of r's object members), rows gathered through the member ids.  No second relation can reuse an object tile (its rows
+// are r's list), so the four groups of 256 threads that k_transe_mine spreads over four relations here take four OBJECT tiles of
+// the span against the one subject tile and the one row of rn: five tiles at a time, in TMT_KC-column chunks (5 x 68 x 64 floats =
+// 85 KiB + 20 KiB static: one workgroup of 16 waves a compute unit, the occupancy of k_transe_mine).  The 16 accumulators live
+// across a pair's chunks and te_pair_term walks the columns in order, so a distance is k_transe_mine's bit for bit; the monotone
+// early exit is kept per wave, and a round whose every wave is past the bound stops staging chunks.
+constexpr int TMT_KC = 64;
+
+struct TeMineTypedParams {
+    TeMineParams p;
+    MineTyped ty;
+};
+
+// columns [k0, k0 + kn) of the rows ids_s[0 .. 63] of en into dst [kn][TM_LD] by `threads` threads tl; zeros for id -1
+__device__ __forceinline__ void tm_stage_gather(float* dst, const float* __restrict__ en, const int* ids_s, int dim, int k0, int kn,
+                                                int tl, int threads) {
+    for (int x = tl; x < TE_TQ * kn; x += threads) {
+        const int row = x / kn, k = x - row * kn, id = ids_s[row];
+        dst[k * TM_LD + row] = id >= 0 ? en[(size_t)id * dim + k0 + k] : 0.f;
+    }
+}
+
+template <int P, bool HIST>
+__global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed(const TeMineTypedParams tp) {
+    extern __shared__ __attribute__((aligned(16))) float tm_smem[];
+    __shared__ unsigned long long fmask[TM_GROUPS][64];  // a group's object tile: its listed objects per subject row
+    __shared__ int sid_s[64], oid_s[TM_GROUPS][64];      // the tiles' entity ids, -1 past the lists
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const TeMineParams& p = tp.p;
+    const MineTyped& ty = tp.ty;
+    const MineSelect& sel = p.sel;
+    const int kc = p.kc;
+    const int t = threadIdx.x, g = t >> 8, tl = t & 255, lane = t & 63, tx = tl & 15, ty4 = tl >> 4;
+    float* As = tm_smem;                                 // [kc][TM_LD] subjects
+    float* Bs = As + (1 + g) * kc * TM_LD;               // [TM_GROUPS][kc][TM_LD] each group's objects
+    float* Rs = As + (1 + TM_GROUPS) * kc * TM_LD;       // [kc] the relation's row
+    const int4 unit = ty.units[blockIdx.x];
+    const int r = unit.x;
+    if (r < 0 || r >= sel.num_rels) return;              // uniform: not a unit
+    const float bound = tm_bound<P, HIST>(sel);
+
+    mine_typed_ids(ty, sel.num_rels + r, unit.y, sel.n, t, sid_s);
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += TM_THREADS) hist_s[i] = 0u;
+    const float* a_ptr = As + 4 * ty4;
+    const float* b_ptr = Bs + 4 * tx;
+
+    // group g takes object tiles unit.z + g, unit.z + g + TM_GROUPS, ...; every group makes every round's barriers
+    for (int ob = unit.z; ob < unit.w; ob += TM_GROUPS) {
+        const int ot = ob + g;
+        const bool live = ot < unit.w;
+        __syncthreads();                                 // the last round's reads of oid_s and fmask are over; sid_s is there
+        mine_typed_ids(ty, r, live ? ot : -1, sel.n, tl, oid_s[g]);
+        if (tl < 64) fmask[g][tl] = 0ull;
+        __syncthreads();
+        if (live) mine_typed_filter(ty, sel.num_rels, r, sid_s, oid_s[g], tl, fmask[g]);
+
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        bool past = !live;                               // wave-uniform: every pair of the wave is beyond the bound
+        for (int k0 = 0; k0 < p.dim; k0 += kc) {
+            const int kn = min(kc, p.dim - k0);
+            if (__syncthreads_and(past)) break;          // the last chunk's reads are over; nothing left to look at: uniform
+            tm_stage_gather(As, p.en, sid_s, p.dim, k0, kn, t, TM_THREADS);
+            if (live) tm_stage_gather(Bs, p.en, oid_s[g], p.dim, k0, kn, tl, 256);
+            for (int k = t; k < kn; k += TM_THREADS) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
+            __syncthreads();
+            for (int kb = 0; kb < kn && !past; kb += TM_CHECK) {
+                const int ke = min(kb + TM_CHECK, kn);
+#pragma unroll 4
+                for (int k = kb; k < ke; ++k) {
+                    const float4 qa = *reinterpret_cast<const float4*>(a_ptr + k * TM_LD);
+                    const float4 eb = *reinterpret_cast<const float4*>(b_ptr + k * TM_LD);
+                    const float rv = Rs[k];
+                    const float qv[4] = {qa.x + rv, qa.y + rv, qa.z + rv, qa.w + rv}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+                    for (int a = 0; a < 4; ++a)
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], P);
+                }
+                bool all_past = true;
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) all_past = all_past && acc[a][b] > bound;
+                past = __all(all_past) != 0;
+            }
+        }
+        __syncthreads();                                 // fmask of this round is complete
+
+        // ---- epilogue (k_mine.h): lane (tx, ty4) holds subjects 4 ty4 + a, objects 4 tx + b, ids through the member lists
+        unsigned key[4][4];
+        bool want = false;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if (P == 2) acc[a][b] = sqrtf(acc[a][b]);
+                const int s = sid_s[4 * ty4 + a], o = oid_s[g][4 * tx + b];
+                unsigned k = mine_key(-acc[a][b]);
+                if (!live || s < 0 || o < 0 || (sel.exclude_self && s == o)) k = 0u;
+                key[a][b] = mine_gate<HIST>(k, sel);
+                want = want || key[a][b] != 0u;
+            }
+        if (__ballot(want) == 0ull) continue;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int rl = 4 * ty4 + a, cl = 4 * tx + b;
+                const bool ok = key[a][b] != 0u && !((fmask[g][rl] >> cl) & 1ull);
+                mine_put<HIST>(ok, key[a][b], __float_as_int(acc[a][b]), sid_s[rl], r, oid_s[g][cl], lane, hist_s, sel);
+            }
+    }
+    if (HIST) {
+        __syncthreads();
+        if (t < 256) mine_hist_flush(hist_s, sel, t);
+    }
+}
+
+template <int P, bool HIST>
+static int tmt_launch(const TeMineTypedParams& tp, unsigned n_units, int lds, hipStream_t st) {
+    static unsigned long long raised = 0;
+    const int lds_max = ((1 + TM_GROUPS) * TM_LD + 1) * TMT_KC * (int)sizeof(float);
+    if (!raise_dynamic_lds((const void*)k_transe_mine_typed<P, HIST>, lds_max, raised, "gv_transe_mine_typed")) return GV_ERR_SHAPE;
+    hipLaunchKernelGGL((k_transe_mine_typed<P, HIST>), dim3(n_units), dim3(TM_THREADS), lds, st, tp);
+    return launch_status("gv_transe_mine_typed");
+}
+
 }  // namespace gv
 
 using namespace gv;
@@ -207,4 +347,28 @@ extern "C" int gv_transe_mine(const float* en, const float* rn, int n, int num_r
     const int lds_max = (2 * TM_LD + TM_GROUPS) * TM_KC_MAX * (int)sizeof(float);
     if (mode == GV_MINE_EMIT) return p_norm == 1 ? tm_launch<1, false>(p, grid, lds, lds_max, st) : tm_launch<2, false>(p, grid, lds, lds_max, st);
     return p_norm == 1 ? tm_launch<1, true>(p, grid, lds, lds_max, st) : tm_launch<2, true>(p, grid, lds, lds_max, st);
+}
+
+extern "C" int gv_transe_mine_typed(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int64_t* set_ptr,
+                                    const int32_t* set_ids, const int32_t* units, int64_t n_units, const int32_t* filt_lo,
+                                    const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                                    uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                                    uint64_t* counter, uint64_t* hist, void* stream) {
+    GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "gv_transe_mine_typed: dim=%d (1..%d) p_norm=%d (1 or 2)", dim, GV_TRANSE_MAX_DIM, p_norm);
+    GV_REQUIRE(n <= 0 || (en && rn), GV_ERR_NULL, "gv_transe_mine_typed: NULL table");
+    hipStream_t st = (hipStream_t)stream;
+    TeMineTypedParams tp{};
+    TeMineParams& p = tp.p;
+    const int rc = mine_typed_prepare("gv_transe_mine_typed", n, num_rels, set_ptr, set_ids, units, n_units, filt_lo, filt_hi, filt_ent,
+                                      n_filt_ent, exclude_self, mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, counter, hist,
+                                      st, &p.sel, &tp.ty);
+    if (rc != GV_OK || n == 0 || n_units == 0) return rc;
+    p.en = en; p.rn = rn; p.dim = dim;
+    p.kc = std::min(dim, TMT_KC);
+    p.n_chunks = (dim + p.kc - 1) / p.kc;
+    const int lds = ((1 + TM_GROUPS) * TM_LD + 1) * p.kc * (int)sizeof(float);
+    const unsigned nu = (unsigned)n_units;
+    if (mode == GV_MINE_EMIT) return p_norm == 1 ? tmt_launch<1, false>(tp, nu, lds, st) : tmt_launch<2, false>(tp, nu, lds, st);
+    return p_norm == 1 ? tmt_launch<1, true>(tp, nu, lds, st) : tmt_launch<2, true>(tp, nu, lds, st);
 }

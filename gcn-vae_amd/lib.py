@@ -116,6 +116,8 @@ SIGNATURES = {
     'gv_mine_scores_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_mine_scores': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P, _P, _L,
                             _I, _I, _I, _P]),
+    'gv_mine_scores_typed': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I,
+                                  _P, _L, _P, _P, _I, _I, _I, _P]),
     'gv_ec_basis_rows_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P]),
     'gv_ec_basis_rows_bwd': (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _I, _P]),
     'gv_ec_head_fwd': (_I, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
@@ -135,6 +137,8 @@ SIGNATURES = {
     'gv_transe_mine_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_transe_mine': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P,
                             _P, _L, _P]),
+    'gv_transe_mine_typed': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32,
+                                  _I, _P, _L, _P, _P, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -925,10 +925,12 @@ def _mine_device(a, name_a, b, name_b):
     dev = a.device
     if b.device != dev:
         raise ValueError(f'{name_b} must be on the device of {name_a} ({dev})')
-    if a.shape[0]:
-        return dev, None
-    return dev, (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
-                 {'count': 0, 'passes': 0})
+    return dev, (None if a.shape[0] else _mine_empty(dev))
+
+
+def _mine_empty(dev):
+    return (torch.zeros(0, 3, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.float32, device=dev),
+            {'count': 0, 'passes': 0})
 
 
 def _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev, workspace_bytes):
@@ -1048,6 +1050,114 @@ def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt
 
     return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
                        'gv_mine_scores')
+
+
+MINE_TYPED_SPAN = 8            # object tiles a unit of the typed sweeps takes at most against one staged subject tile
+MINE_TYPED_FILL = 1024         # units wanted before tiles are grouped at all: four workgroups for each of the MI355X's 256 CUs
+
+
+def mine_typed_plan(ptr, num_rels, span=None, multiple=1):
+    """The unit list of the type-constrained sweeps from the member lists' sizes, with torch ops on ``ptr``'s device (a CPU tensor
+    works): int32 (U, 4) rows ``(r, subject tile, first object tile, end object tile)`` over 64-member tiles of relation r's
+    subject list (set ``num_rels + r``) and object list (set ``r``), every tile pair in exactly one unit.  ``span`` object tiles a
+    unit (the last of a row of units fewer); None: ``MINE_TYPED_SPAN`` when that still leaves ``MINE_TYPED_FILL`` units, else as
+    many as do, at least ``multiple`` and a multiple of it (the TransE kernel takes four object tiles at a time).  The result of a
+    sweep does not depend on it.  More than 2**31 - 1 units: ValueError."""
+    sizes = (ptr[1:] - ptr[:-1]).to(torch.int64)
+    n_o, n_s = sizes[:num_rels], sizes[num_rels:]
+    s_tiles, o_tiles = (n_s + 63) // 64, (n_o + 63) // 64
+    if span is None:
+        pairs = int((s_tiles * o_tiles).sum())
+        span = min(MINE_TYPED_SPAN, max(1, pairs // MINE_TYPED_FILL))
+        span = max(multiple, span // multiple * multiple)
+    span = int(span)
+    if span < 1:
+        raise ValueError(f'span must be >= 1, got {span}')
+    groups = (o_tiles + span - 1) // span
+    per_r = s_tiles * groups
+    total = int(per_r.sum())
+    if total > 2 ** 31 - 1:
+        raise ValueError(f'the type-constrained sweep has {total} units, more than 2**31 - 1')
+    rel = torch.repeat_interleave(torch.arange(num_rels, device=ptr.device), per_r)
+    local = torch.arange(total, device=ptr.device) - (torch.cumsum(per_r, 0) - per_r)[rel]
+    g = groups[rel].clamp(min=1)
+    first = (local % g) * span
+    units = torch.stack([rel, local // g, first, torch.minimum(first + span, o_tiles[rel])], 1)
+    return units.to(torch.int32).contiguous()
+
+
+def _mine_typed_members(ptr, ids, n, num_rels):
+    """The member lists of a typed mining call, checked with torch ops where they are (a bad id would be an out-of-bounds gather, so
+    none reaches a launch): ``ptr`` int64 [2 R + 1] from 0, non-decreasing, ending at ``ids.numel()``; every id in [0, n); every
+    set strictly ascending (a tile's object ids are searched by bisection).  ValueError otherwise."""
+    for name, t in (('ptr', ptr), ('ids', ids)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f'{name}: expected a 1-D int32 / int64 tensor')
+    if ptr.numel() != 2 * num_rels + 1:
+        raise ValueError(f'ptr: expected {2 * num_rels + 1} entries (2 R + 1), got {ptr.numel()}')
+    if ids.device != ptr.device:
+        raise ValueError('ptr and ids must be on one device')
+    ptr = ptr.to(torch.int64)
+    if int(ptr[0]) != 0 or bool((ptr[1:] < ptr[:-1]).any()) or int(ptr[-1]) != ids.numel():
+        raise ValueError(f'ptr must start at 0, be non-decreasing and end at ids.numel() = {ids.numel()}')
+    if ids.numel() >= 2 ** 31:
+        raise ValueError('ids: more than 2**31 - 1 members')
+    if ids.numel():
+        if int(ids.min()) < 0 or int(ids.max()) >= n:
+            raise ValueError(f'member ids must lie in [0, {n})')
+        starts = torch.zeros(ids.numel() + 1, dtype=torch.bool, device=ids.device)
+        starts[ptr] = True
+        if bool(((ids[1:] <= ids[:-1]) & ~starts[1:-1]).any()):
+            raise ValueError('the members of every set must be strictly ascending')
+    return ptr.contiguous(), ids.to(torch.int32).contiguous()
+
+
+def _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev):
+    """``_mine_filter_args`` for the typed sweeps, which read the ranges as given and need each key's listed objects ascending."""
+    lo32, hi32, ent32, n_ent, _, _ = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev, lambda *a: 0)
+    if n_ent > 1:
+        starts = torch.zeros(n_ent + 1, dtype=torch.bool, device=dev)
+        starts[lo32.long()] = True
+        if bool(((ent32[1:] < ent32[:-1]) & ~starts[1:-1]).any()):
+            raise ValueError('the listed objects of every key must be ascending')
+    return lo32, hi32, ent32, n_ent
+
+
+def mine_scores_typed(emb, w, set_ptr, set_ids, *, threshold=None, k=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                      exclude_self=True, max_results=MINE_MAX_RESULTS, span=None):
+    """``mine_scores`` among the TYPE-CORRECT triplets only: ``s`` a member of set ``R + r``, ``o`` a member of set ``r``, the sets
+    given as lists (``set_ptr`` int64 [2 R + 1], ``set_ids``: ``ranking.TypeConstraint.members``).  Everything else -- logits bit for bit,
+    filter, ``exclude_self``, NaN, order, ``info``, ``MineOverflow`` -- is ``mine_scores``'.  gv_mine_scores_typed walks the
+    transposed order: a workgroup takes a relation, a 64-member tile of its subject list and ``span`` tiles of its object list
+    (``mine_typed_plan``; the result does not depend on ``span``), rows gathered through the ids.  An empty plan returns the
+    empty result without a launch."""
+    _mine_tables(emb, 'emb', w, 'w')
+    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
+    if num_rels < 1 or h < 1:
+        raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
+    k, threshold, max_results = _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=(k, threshold, max_results))
+    set_ptr, set_ids = _mine_typed_members(set_ptr, set_ids, n, num_rels)
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev, nothing = _mine_device(emb, 'emb', w, 'w')
+    if nothing is not None:
+        return nothing
+    set_ptr, set_ids = set_ptr.to(dev), set_ids.to(dev)
+    units = mine_typed_plan(set_ptr, num_rels, span)
+    if units.shape[0] == 0:
+        return _mine_empty(dev)
+    lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
+    if bias is not None:
+        bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
+        bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
+
+    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
+        lib.call('gv_mine_scores_typed', ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(set_ptr), ptr(set_ids), ptr(units),
+                 units.shape[0], ptr(lo32), ptr(hi32), ptr(ent32), n_ent, 1 if exclude_self else 0, mode, key_min,
+                 prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), n, num_rels, h, lib.stream())
+
+    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
+                       'gv_mine_scores_typed')
 
 
 def pick_split_k(m_out, n_out, k):
@@ -3423,3 +3533,40 @@ def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi
     # d <= t is key(-d) >= key(-t); t = -0 keys as +0, the key of every zero distance
     return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(-threshold), max_results, True,
                        'gv_transe_mine')
+
+
+def transe_mine_typed(en, rn, p_norm, set_ptr, set_ids, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                      exclude_self=True, max_results=MINE_MAX_RESULTS, span=None):
+    """``transe_mine`` among the TYPE-CORRECT triplets only: ``s`` a member of set ``R + r``, ``o`` a member of set ``r``, the sets
+    given as lists (``set_ptr`` int64 [2 R + 1], ``set_ids``: ``ranking.TypeConstraint.members``), checked as ``mine_scores_typed``
+    checks them.  Distances bit for bit, filter, ``exclude_self``, NaN, order, ``info`` and ``MineOverflow`` are ``transe_mine``'s.
+    gv_transe_mine_typed: a workgroup takes a relation, a 64-member tile of its subject list and ``span`` tiles of its object list,
+    four at a time (``mine_typed_plan``; the result does not depend on ``span``).  An empty plan returns the empty result without
+    a launch."""
+    k, threshold, max_results = _mine_args(k, threshold, max_results)
+    for name, t in (('en', en), ('rn', rn)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    set_ptr, set_ids = _mine_typed_members(set_ptr, set_ids, en.shape[0], rn.shape[0])
+    en, rn = _mine_tables(en, 'en', rn, 'rn', prepare=lambda t, name: _table(t.contiguous(), name))
+    p_norm = _p_norm(p_norm)
+    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
+    if num_rels < 1:
+        raise ValueError('need at least one relation')
+    _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    dev, nothing = _mine_device(en, 'en', rn, 'rn')
+    if nothing is not None:
+        return nothing
+    set_ptr, set_ids = set_ptr.to(dev), set_ids.to(dev)
+    units = mine_typed_plan(set_ptr, num_rels, span, multiple=4)
+    if units.shape[0] == 0:
+        return _mine_empty(dev)
+    lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
+
+    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
+        lib.call('gv_transe_mine_typed', ptr(en), ptr(rn), n, num_rels, dim, p_norm, ptr(set_ptr), ptr(set_ids), ptr(units),
+                 units.shape[0], ptr(lo32), ptr(hi32), ptr(ent32), n_ent, 1 if exclude_self else 0, mode, key_min, prefix_bits,
+                 prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), lib.stream())
+
+    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(-threshold), max_results, True,
+                       'gv_transe_mine_typed')

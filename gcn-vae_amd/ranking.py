@@ -177,6 +177,15 @@ class TypeConstraint:
         dense = ((rows[:, ent >> 5] >> (ent & 31)) & 1).bool() & ok.view(-1, 1)
         return dense if device is None else dense.to(device)
 
+    def members(self, device=None):
+        """Every set as a list: ``(ptr int64 [2 * num_rels + 1], ids int32 [total])``, set j's members ascending in
+        ``ids[ptr[j]:ptr[j + 1]]`` -- the form the type-constrained miners take (``ops.mine_scores_typed``).  Torch ops on ``words``."""
+        dense = self.mask(torch.arange(self.words.shape[0], device=self.device))
+        ptr = torch.zeros(dense.shape[0] + 1, dtype=torch.int64, device=self.device)
+        ptr[1:] = torch.cumsum(dense.sum(1), 0)
+        ids = torch.nonzero(dense)[:, 1].to(torch.int32).contiguous()          # row-major: by set, then ascending entity
+        return (ptr, ids) if device is None else (ptr.to(device), ids.to(device))
+
     def contains(self, r, entities, direction):
         """bool: is ``entities[i]`` a member of the ``direction`` set of relation ``r[i]``?  (On ``entities``' device.)"""
         entities = torch.as_tensor(entities)
@@ -615,14 +624,21 @@ def _mine_args(k, threshold, max_results):
 
 
 def _mine_from_values(val, ascending, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
-                     max_results=ops.MINE_MAX_RESULTS):
+                     max_results=ops.MINE_MAX_RESULTS, cand_subj=None, cand_obj=None):
     """The mining rule, once, on a materialised tensor ``val[r, s, o]`` (R, N, N) in plain torch: logits, largest first, or
-    (``ascending``) distances, smallest first.  ``mine_from_scores`` and ``transe.mine_from_distances`` state it for each."""
+    (``ascending``) distances, smallest first.  ``mine_from_scores`` and ``transe.mine_from_distances`` state it for each.
+    ``cand_subj`` / ``cand_obj`` (dense bool (R, N), each optional): the typed rule -- (s, r, o) is a candidate only when
+    ``cand_subj[r, s]`` and ``cand_obj[r, o]``; everything else is unchanged."""
     _mine_args(k, threshold, max_results)
     num_rels, n = val.shape[0], val.shape[1]
     val = val.to(torch.float32) + 0.0
     within = torch.le if ascending else torch.ge          # at the bound or better
     cand = ~torch.isnan(val)
+    for name, side, shape in (('cand_subj', cand_subj, (num_rels, n, 1)), ('cand_obj', cand_obj, (num_rels, 1, n))):
+        if side is not None:
+            if side.dtype != torch.bool or tuple(side.shape) != (num_rels, n):
+                raise ValueError(f'{name}: expected a bool ({num_rels}, {n}) mask')
+            cand &= side.to(val.device).view(shape)
     if exclude_self:
         cand &= ~torch.eye(n, dtype=torch.bool, device=val.device).unsqueeze(0)
     if filt_lo is not None and n:
@@ -650,16 +666,18 @@ def _mine_finish(trip, values, info, k, threshold, max_results, n, num_rels, asc
 
 
 def mine_from_scores(score, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
-                     max_results=ops.MINE_MAX_RESULTS):
+                     max_results=ops.MINE_MAX_RESULTS, cand_subj=None, cand_obj=None):
     """The mining rule of ``ops.mine_scores`` on a materialised tensor ``score[r, s, o]`` (R, N, N), in plain torch (any device,
     CPU included).  Candidates: every (s, r, o), less ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r),
     less s == o when ``exclude_self``, less NaN logits.  Order, a strict total one: logit descending with -0 == +0, then
     (s, r, o) ascending.  ``threshold=t`` selects every candidate with logit >= t, ``k=K`` the first K (fewer if fewer exist).
     Returns ``(triplets int64 (n, 3), logits float32 (n,), info)`` in that order, -0 reported as +0; ``info['count']`` is the
     number of candidates at or above the threshold (top-K: at or above the K-th logit's exact value; all, when fewer than K
-    exist).  More than ``max_results`` of those raise ``MineOverflow`` carrying the count: nothing is truncated silently."""
+    exist).  More than ``max_results`` of those raise ``MineOverflow`` carrying the count: nothing is truncated silently.
+    ``cand_subj`` / ``cand_obj`` (bool (R, N)): the typed rule of ``ops.mine_scores_typed``, s among ``cand_subj[r]`` and o among
+    ``cand_obj[r]`` (``TypeConstraint.mask`` of sets R + r and r)."""
     return _mine_from_values(score, False, k=k, threshold=threshold, filt_lo=filt_lo, filt_hi=filt_hi, filt_ent=filt_ent,
-                            exclude_self=exclude_self, max_results=max_results)
+                            exclude_self=exclude_self, max_results=max_results, cand_subj=cand_subj, cand_obj=cand_obj)
 
 
 def _mine_filter(filter_index, n, num_rels, device):
@@ -675,6 +693,14 @@ def _mine_filter(filter_index, n, num_rels, device):
     return lo, hi, filter_index.entities('o', device)
 
 
+def _mine_members(type_constraint, n, num_rels, device):
+    """(ptr, ids) of ``TypeConstraint.members`` on ``device`` for tables of these sizes."""
+    if type_constraint.num_nodes != n or type_constraint.num_rels != num_rels:
+        raise ValueError(f'the TypeConstraint is for {type_constraint.num_nodes} entities / {type_constraint.num_rels} relations, the '
+                         f'tables have {n} / {num_rels}')
+    return type_constraint.members(device)
+
+
 def _mine_bias(flow_log_prob, device):
     if flow_log_prob is None:
         return None
@@ -682,30 +708,40 @@ def _mine_bias(flow_log_prob, device):
 
 
 def mine_triplets(embedding, w, *, k=None, threshold=None, filter_index=None, flow_log_prob=None, exclude_self=True,
-                  max_results=ops.MINE_MAX_RESULTS):
+                  max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
     """Knowledge-graph completion: among ALL triplets (s, r, o), scored as every scorer here scores them (logit =
     (e_s * w_r) . e_o + flow_log_prob), the ``k`` most confident ones or every one with logit >= ``threshold`` (a probability p
     is the logit log(p / (1 - p))); with a ``FilterIndex`` the known triplets are left out (new facts only).  One fused sweep
     per pass (ops.mine_scores); returns ``(triplets int64 (n, 3), logits float32 (n,), info)`` in the order of
-    ``mine_from_scores``, and raises ``MineOverflow`` rather than truncating."""
+    ``mine_from_scores``, and raises ``MineOverflow`` rather than truncating.  With a ``type_constraint`` (TypeConstraint) only
+    type-correct triplets are candidates -- s seen as subject of r, o seen as object of r -- at the same logits, from the sweep
+    over each relation's member lists (ops.mine_scores_typed)."""
     _mine_args(k, threshold, max_results)
     emb = embedding.detach()
     wd = w.detach().to(emb.device)
     lo, hi, ent = _mine_filter(filter_index, emb.shape[0], wd.shape[0], emb.device)
+    if type_constraint is not None:
+        set_ptr, set_ids = _mine_members(type_constraint, emb.shape[0], wd.shape[0], emb.device)
+        return ops.mine_scores_typed(emb, wd, set_ptr, set_ids, threshold=threshold, k=k, bias=_mine_bias(flow_log_prob, emb.device),
+                                     filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
     return ops.mine_scores(emb, wd, threshold=threshold, k=k, bias=_mine_bias(flow_log_prob, emb.device), filt_lo=lo, filt_hi=hi,
                            filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
 
 
-def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, filt, exclude_self, max_results):
+def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, filt, exclude_self, max_results, members=None):
     """The unfused route of both models, one relation at a time: ``values_of(r)`` is relation r's (N, N) values (logits, or
     distances when ``ascending``), ``filt`` the (lo, hi, ent) of ``_mine_filter``; torch selection, a running K-th value pruning
-    the pool."""
+    the pool.  With ``members`` = (ptr, ids) of ``TypeConstraint.members`` the typed route: ``values_of(r, subj, obj)`` is the
+    (|subj|, |obj|) block of relation r's member lists, selected the same way, local indices mapped back through the lists."""
     lo, hi, ent = filt
     k = None if k is None else int(k)
     bound = None if k is not None else float(threshold)
     within = torch.le if ascending else torch.ge          # at the bound or better
     pool_t, pool_v, held = [], [], 0
-    diag = torch.eye(n, dtype=torch.bool, device=device) if exclude_self else None
+    typed = members is not None
+    diag = torch.eye(n, dtype=torch.bool, device=device) if exclude_self and not typed else None
+    if typed:
+        set_ptr, set_ids = members[0].tolist(), members[1].to(device).long()
 
     def prune():
         nonlocal pool_t, pool_v, held, bound
@@ -717,12 +753,23 @@ def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, fi
         pool_t, pool_v, held = [t], [v], v.numel()
 
     for r in range(num_rels if n else 0):
-        val = values_of(r)
+        if typed:
+            subj, obj = set_ids[set_ptr[num_rels + r]:set_ptr[num_rels + r + 1]], set_ids[set_ptr[r]:set_ptr[r + 1]]
+            if not subj.numel() or not obj.numel():
+                continue
+            val = values_of(r, subj, obj)
+            f_lo, f_hi = (lo[r::num_rels][subj], hi[r::num_rels][subj]) if lo is not None else (None, None)
+        else:
+            val = values_of(r)
+            f_lo, f_hi = (lo[r::num_rels], hi[r::num_rels]) if lo is not None else (None, None)
         cand = ~torch.isnan(val)
         if diag is not None:
             cand &= ~diag
+        elif exclude_self:
+            cand &= subj.view(-1, 1) != obj.view(1, -1)
         if lo is not None:
-            cand &= ~_listed_mask(lo[r::num_rels], hi[r::num_rels], ent, n, n, device)
+            listed = _listed_mask(f_lo, f_hi, ent, val.shape[0], n, device)
+            cand &= ~(listed[:, obj] if typed else listed)
         if bound is not None:
             cand &= within(val, bound)
         if k is not None and bound is None:           # no bound yet: this relation's own K-th value
@@ -730,6 +777,8 @@ def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, fi
             if vals.numel() > k:
                 cand &= within(val, torch.topk(vals, k, largest=not ascending).values[-1])
         s, o = torch.nonzero(cand, as_tuple=True)
+        if typed:
+            s, o = subj[s], obj[o]
         pool_t.append(torch.stack([s, torch.full_like(s, r), o], 1))
         pool_v.append(val[cand])
         held += s.numel()
@@ -741,24 +790,27 @@ def _mine_unfused(values_of, ascending, n, num_rels, device, *, k, threshold, fi
 
 
 def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=None, flow_log_prob=None, exclude_self=True,
-                          max_results=ops.MINE_MAX_RESULTS):
+                          max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
     """``mine_triplets`` from materialised logits, one relation at a time (``ops.mul`` + ``ops.gemm`` + torch selection, a running
-    K-th logit pruning the pool): the in-repo cross-check and the bench's baseline, never a fallback."""
+    K-th logit pruning the pool): the in-repo cross-check and the bench's baseline, never a fallback.  With a ``type_constraint``
+    the relation's subject and object members are ``index_select``-ed first and the GEMM is (|subjects|, h) x (h, |objects|)."""
     _mine_args(k, threshold, max_results)
     emb = embedding.detach().contiguous()
     wd = w.detach().to(emb.device).contiguous()
     n, num_rels = emb.shape[0], wd.shape[0]
     filt = _mine_filter(filter_index, n, num_rels, emb.device)
     bias = _mine_bias(flow_log_prob, emb.device)
+    members = None if type_constraint is None else _mine_members(type_constraint, n, num_rels, emb.device)
 
-    def logits_of(r):
-        val = ops.gemm(ops.mul(emb, wd[r].expand_as(emb).contiguous()), emb, trans_b=True, precision='f32')
+    def logits_of(r, subj=None, obj=None):
+        a, b = (emb, emb) if subj is None else (emb.index_select(0, subj), emb.index_select(0, obj))
+        val = ops.gemm(ops.mul(a, wd[r].expand_as(a).contiguous()), b, trans_b=True, precision='f32')
         if bias is not None:
             val = val + bias
         return val + 0.0
 
     return _mine_unfused(logits_of, False, n, num_rels, emb.device, k=k, threshold=threshold, filt=filt, exclude_self=exclude_self,
-                        max_results=max_results)
+                        max_results=max_results, members=members)
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

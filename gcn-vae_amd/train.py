@@ -163,19 +163,21 @@ def write_mc_predictions(path, z, w, triplets, k, filter_index, flow_log_probs=N
     return n
 
 
-def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None):
+def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None, type_constraint=None):
     """Knowledge-graph completion as TSV, ``s  r  o  rank  logit``: the new triplets (``filter_index``: the known ones left out,
     s != o) that ``ranking.mine_triplets`` selects among ALL N x R x N -- the ``k`` most confident and / or those whose
-    probability sigmoid(logit) reaches ``threshold`` -- best first.  Returns the number of lines written."""
+    probability sigmoid(logit) reaches ``threshold`` -- best first; with a ``type_constraint`` among the type-correct ones only.
+    Returns the number of lines written."""
     with torch.no_grad():
         if k:
-            trip, logits, _ = ranking.mine_triplets(embed, w, k=k, filter_index=filter_index, flow_log_prob=flow_log_prob)
+            trip, logits, _ = ranking.mine_triplets(embed, w, k=k, filter_index=filter_index, flow_log_prob=flow_log_prob,
+                                                    type_constraint=type_constraint)
             if threshold is not None:
                 keep = logits >= _logit_of(threshold)
                 trip, logits = trip[keep], logits[keep]
         else:
             trip, logits, _ = ranking.mine_triplets(embed, w, threshold=_logit_of(threshold), filter_index=filter_index,
-                                                    flow_log_prob=flow_log_prob)
+                                                    flow_log_prob=flow_log_prob, type_constraint=type_constraint)
     return _write_triplets(path, trip, logits)
 
 
@@ -201,6 +203,9 @@ def check_args(args):
         raise ValueError(f"{' / '.join(wants)} decode a trained checkpoint: pass --test-mode True (and --model-state-file)")
     if getattr(args, 'complete_threshold', None) is not None:
         _logit_of(args.complete_threshold)
+    if getattr(args, 'complete_typed', False) and not (getattr(args, 'complete_topk', 0) > 0
+                                                      or getattr(args, 'complete_threshold', None) is not None):
+        raise ValueError('--complete-typed restricts the completions: it needs --complete-topk or --complete-threshold')
     if getattr(args, 'type_constrain', False):
         if args.test_mode is not True:
             raise ValueError('--type-constrain reports on / predicts from a trained checkpoint: pass --test-mode True '
@@ -280,10 +285,15 @@ def main(args):
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            typed = None
+            if getattr(args, 'complete_typed', False):
+                typed = types if types is not None else \
+                    ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             n_lines = write_completions(args.complete_out, embed, model.w_relation, known, k=args.complete_topk or None,
-                                        threshold=args.complete_threshold, flow_log_prob=model.encoder.get_flow_log_prob())
-            print(f"wrote {n_lines} new triplets (all {num_nodes} x {num_rels} x {num_nodes} scored, known triplets filtered) to "
-                  f"{args.complete_out}")
+                                        threshold=args.complete_threshold, flow_log_prob=model.encoder.get_flow_log_prob(),
+                                        type_constraint=typed)
+            scored = "the type-correct triplets" if typed is not None else f"all {num_nodes} x {num_rels} x {num_nodes}"
+            print(f"wrote {n_lines} new triplets ({scored} scored, known triplets filtered) to {args.complete_out}")
         if getattr(args, 'sample_graph', 0) > 0:
             from . import generate
             _, trip, logits = generate.sample_graph(model, args.sample_graph, k=args.sample_topk)
@@ -455,7 +465,9 @@ def build_parser():
     p.add_argument("--type-constrain", action="store_true",
                    help="with --test-mode and --filtered-eval: the type-constrained protocol (candidates: the entities seen on "
                         "that side of the relation in train + valid + test); the report is raw, filtered, raw_constrained and "
-                        "filtered_constrained, and --predict-topk writes such entities only; not a reference flag")
+                        "filtered_constrained, and --predict-topk writes such entities only; --complete-topk / "
+                        "--complete-threshold are not touched and keep writing unconstrained completions (see --complete-typed); "
+                        "not a reference flag")
     p.add_argument("--predict-topk", type=int, default=0,
                    help="with --test-mode: write the K most likely new entities of both directions of every test triplet "
                         "(train + valid + test triplets filtered out) to --predict-out; 0 = off; not a reference flag")
@@ -477,6 +489,9 @@ def build_parser():
                         "cut at P) to --complete-out")
     p.add_argument("--complete-out", type=str, default="completions.tsv",
                    help="TSV of --complete-topk / --complete-threshold: subject, relation, object, rank, logit")
+    p.add_argument("--complete-typed", action="store_true",
+                   help="with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as "
+                        "subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval")
     p.add_argument("--sample-graph", type=int, default=0,
                    help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
                         "confident triplets among them to --sample-out; 0 = off")

@@ -52,7 +52,9 @@ Completion: ``mine_triplets`` selects among ALL N x R x N triplets the K nearest
 distances of ``predict_topk(direction='o')``, the reference's 'normal' mode (h + r) - t -- from ``ops.transe_mine``
 (gv_transe_mine: subject and object tiles of the normalised table stay in LDS while the relations are walked over them).
 ``mine_from_distances`` states the rule on a materialised (R, N, N) tensor; ``mine_triplets_unfused`` is the per-relation
-cross-check.  ``--complete-topk K`` / ``--complete-threshold D`` write them to ``--complete-out`` in train.py's layout.
+cross-check.  ``--complete-topk K`` / ``--complete-threshold D`` write them to ``--complete-out`` in train.py's layout.  With a
+``type_constraint`` (``--complete-typed``) only type-correct triplets are mined, by ``ops.transe_mine_typed``
+(gv_transe_mine_typed: by relation, over that relation's subject and object member lists).
 
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
@@ -67,7 +69,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_unfused,
+from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
+                      _mine_unfused,
                       rank_from_scores_constrained, sort_and_rank, topk_from_scores)
 
 
@@ -660,7 +663,7 @@ def _write_rows(f, direction, a, r, ids, values):
 # completion: the whole graph's nearest new triplets
 # ------------------------------------------------------------------------------------------------
 def mine_from_distances(dist, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
-                        max_results=ops.MINE_MAX_RESULTS):
+                        max_results=ops.MINE_MAX_RESULTS, cand_subj=None, cand_obj=None):
     """The mining rule of ``ops.transe_mine`` on a materialised tensor ``dist[r, s, o]`` (R, N, N), in plain torch (any device,
     CPU included): the counterpart of ``ranking.mine_from_scores``.  Candidates: every (s, r, o), less
     ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r), less s == o when ``exclude_self``, less NaN
@@ -668,18 +671,21 @@ def mine_from_distances(dist, *, k=None, threshold=None, filt_lo=None, filt_hi=N
     selects every candidate with d <= t, ``k=K`` the first K (fewer if fewer exist).  Returns ``(triplets int64 (n, 3), distances
     float32 (n,), info)`` in that order; ``info['count']`` is the number of candidates at or below the threshold (top-K: at or
     below the K-th distance's exact value; all, when fewer than K exist).  More than ``max_results`` of those raise
-    ``MineOverflow`` carrying the count: nothing is truncated silently."""
+    ``MineOverflow`` carrying the count: nothing is truncated silently.  ``cand_subj`` / ``cand_obj`` (bool (R, N)): the typed rule
+    of ``ops.transe_mine_typed``, as in ``ranking.mine_from_scores``."""
     return _mine_from_values(dist, True, k=k, threshold=threshold, filt_lo=filt_lo, filt_hi=filt_hi, filt_ent=filt_ent,
-                            exclude_self=exclude_self, max_results=max_results)
+                            exclude_self=exclude_self, max_results=max_results, cand_subj=cand_subj, cand_obj=cand_obj)
 
 
 def mine_triplets(model_or_tables, *, k=None, threshold=None, filter_index=None, exclude_self=True,
-                  max_results=ops.MINE_MAX_RESULTS):
+                  max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
     """Knowledge-graph completion: among ALL triplets (s, r, o), at the distance ``||n(E_s) + n(R_r) - n(E_o)||_p`` of
     ``predict_topk(direction='o')``, the ``k`` nearest ones or every one with distance <= ``threshold``; with a ``FilterIndex`` the
     known triplets are left out (new facts only).  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``.  One
     fused sweep per pass (ops.transe_mine); returns ``(triplets int64 (n, 3), distances float32 (n,), info)`` in the order of
-    ``mine_from_distances``, and raises ``MineOverflow`` rather than truncating."""
+    ``mine_from_distances``, and raises ``MineOverflow`` rather than truncating.  With a ``type_constraint`` (TypeConstraint) only
+    type-correct triplets are candidates -- s seen as subject of r, o seen as object of r -- at the same distances, from the sweep
+    over each relation's member lists (ops.transe_mine_typed)."""
     _mine_args(k, threshold, max_results)
     with torch.no_grad():
         ent, rel, p_norm, norm_flag = _tables(model_or_tables)
@@ -690,43 +696,49 @@ def mine_triplets(model_or_tables, *, k=None, threshold=None, filter_index=None,
         else:
             en = ops.transe_queries(ent.contiguous(), norm_flag=norm_flag)             # the normalised tables, once
             rn = ops.transe_queries(rel.contiguous(), norm_flag=norm_flag)
+        if type_constraint is not None:
+            set_ptr, set_ids = _mine_members(type_constraint, ent.shape[0], rel.shape[0], ent.device)
+            return ops.transe_mine_typed(en, rn, p_norm, set_ptr, set_ids, k=k, threshold=threshold, filt_lo=lo, filt_hi=hi,
+                                         filt_ent=f_ent, exclude_self=exclude_self, max_results=max_results)
         return ops.transe_mine(en, rn, p_norm, k=k, threshold=threshold, filt_lo=lo, filt_hi=hi, filt_ent=f_ent,
                                exclude_self=exclude_self, max_results=max_results)
 
 
 def mine_triplets_unfused(model_or_tables, *, k=None, threshold=None, filter_index=None, exclude_self=True,
-                          max_results=ops.MINE_MAX_RESULTS):
+                          max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
     """``mine_triplets`` from materialised distances, one relation at a time (``ops.transe_queries`` + ``ops.transe_distances`` +
     torch selection, a running K-th distance pruning the pool): the in-repo cross-check and the bench's comparator, never a
-    fallback."""
+    fallback.  With a ``type_constraint`` the queries are the relation's subject members and the table its object members."""
     _mine_args(k, threshold, max_results)
     with torch.no_grad():
         ent, rel, p_norm, norm_flag = _tables(model_or_tables)
         ent, rel = ent.contiguous(), rel.to(ent.device).contiguous()
         n, num_rels = ent.shape[0], rel.shape[0]
         filt = _mine_filter(filter_index, n, num_rels, ent.device)
+        members = None if type_constraint is None else _mine_members(type_constraint, n, num_rels, ent.device)
         subjects = torch.arange(n, device=ent.device)
         en = ops.transe_queries(ent, norm_flag=norm_flag) if n else ent
 
-        def distances_of(r):
-            q = ops.transe_queries(ent, rel, subjects, torch.full_like(subjects, r), head=False, norm_flag=norm_flag)
-            return ops.transe_distances(q, en, p_norm)
+        def distances_of(r, subj=None, obj=None):
+            a = subjects if subj is None else subj
+            q = ops.transe_queries(ent, rel, a, torch.full_like(a, r), head=False, norm_flag=norm_flag)
+            return ops.transe_distances(q, en if obj is None else en.index_select(0, obj), p_norm)
 
         return _mine_unfused(distances_of, True, n, num_rels, ent.device, k=k, threshold=threshold, filt=filt,
-                            exclude_self=exclude_self, max_results=max_results)
+                            exclude_self=exclude_self, max_results=max_results, members=members)
 
 
-def write_completions(path, model_or_tables, filter_index, k=None, threshold=None):
+def write_completions(path, model_or_tables, filter_index, k=None, threshold=None, type_constraint=None):
     """The whole graph's nearest new triplets (``mine_triplets``: the ``k`` nearest, cut at distance ``threshold`` when both are
-    given; the known triplets and s == o left out) as TSV in train.py's completion layout: ``subject  relation  object  rank
-    distance``.  Returns the number of lines written."""
+    given; the known triplets and s == o left out; with a ``type_constraint`` type-correct triplets only) as TSV in train.py's
+    completion layout: ``subject  relation  object  rank  distance``.  Returns the number of lines written."""
     if k is not None:
-        trip, dist, _ = mine_triplets(model_or_tables, k=k, filter_index=filter_index)
+        trip, dist, _ = mine_triplets(model_or_tables, k=k, filter_index=filter_index, type_constraint=type_constraint)
         if threshold is not None:
             keep = dist <= float(threshold)
             trip, dist = trip[keep], dist[keep]
     else:
-        trip, dist, _ = mine_triplets(model_or_tables, threshold=threshold, filter_index=filter_index)
+        trip, dist, _ = mine_triplets(model_or_tables, threshold=threshold, filter_index=filter_index, type_constraint=type_constraint)
     with open(path, 'w') as f:
         f.writelines(f"{s}\t{r}\t{o}\t{i}\t{x:.9g}\n" for i, ((s, r, o), x) in enumerate(zip(trip.tolist(), dist.tolist())))
     return int(dist.numel())
@@ -765,7 +777,8 @@ def build_parser():
     p.add_argument('--type-constrain', action='store_true',
                    help='type-constrained protocol (candidates: the entities seen on that side of the relation in train + valid + '
                         'test): with --filtered-eval the evaluation reports raw, filtered, raw_constrained and '
-                        'filtered_constrained; with --predict-topk only such entities are written')
+                        'filtered_constrained; with --predict-topk only such entities are written.  It does not touch '
+                        '--complete-topk / --complete-threshold, which keep writing unconstrained completions: see --complete-typed')
     p.add_argument('--graph-step', action='store_true', help='capture one step as a hipGraph and replay it')
     p.add_argument('--predict-topk', type=int, default=None,
                    help='after the final evaluation write the K (1..128) nearest new entities of both directions of every test '
@@ -779,6 +792,9 @@ def build_parser():
                    help='as --complete-topk, every new triplet within distance D; with both, the K nearest cut at D')
     p.add_argument('--complete-out', type=str, default='transe_completions.tsv',
                    help='TSV written by --complete-topk / --complete-threshold: subject, relation, object, rank, distance')
+    p.add_argument('--complete-typed', action='store_true',
+                   help='with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as '
+                        'subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval')
     return p
 
 
@@ -815,6 +831,8 @@ def check_args(args):
     cd = getattr(args, 'complete_threshold', None)
     if cd is not None and cd != cd:
         raise ValueError('--complete-threshold is NaN')
+    if getattr(args, 'complete_typed', False) and ck is None and cd is None:
+        raise ValueError('--complete-typed restricts the completions: it needs --complete-topk or --complete-threshold')
     if getattr(args, 'type_constrain', False) and not getattr(args, 'filtered_eval', False):
         raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, filtered_constrained')
 
@@ -864,8 +882,13 @@ def main(args):
         print(f'wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to {args.predict_out}')
     if args.complete_topk is not None or args.complete_threshold is not None:
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
-        n_lines = write_completions(args.complete_out, model, known, args.complete_topk, args.complete_threshold)
-        print(f'wrote {n_lines} completions (nearest new triplets of the whole graph, known triplets filtered) to {args.complete_out}')
+        typed = None
+        if getattr(args, 'complete_typed', False):
+            typed = types if types is not None else \
+                TypeConstraint(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        n_lines = write_completions(args.complete_out, model, known, args.complete_topk, args.complete_threshold, typed)
+        print(f'wrote {n_lines} completions (nearest new {"type-correct " if typed is not None else ""}triplets of the whole graph, '
+              f'known triplets filtered) to {args.complete_out}')
     return out
 
 

@@ -620,6 +620,23 @@ int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w, const flo
                    int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity, uint64_t* counter,
                    uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
 
+/* Type-constrained whole-graph mining (csrc/k_mine.hip): gv_mine_scores with the candidates further restricted to the type-correct
+ * triplets -- s a member of set num_rels + r (the subjects of r), o a member of set r (its objects), the numbering of the
+ * gv_*_constrained entries.  Each set is a list: set_ptr [2 * num_rels + 1] (int64, non-decreasing from 0) ranges over set_ids
+ * (int32), every set's members strictly ascending and in [0, n).  The sweep walks `units` [n_units][4] (int32, 16-byte aligned):
+ * (r, a 64-member tile of r's subject list, the first and the end of a span of 64-member tiles of r's object list); the units must
+ * cover every tile pair of every relation once -- how the object tiles are grouped into spans does not change the result.  Rows are
+ * gathered through the ids, the arithmetic per pair is gv_mine_scores', so a surviving triplet's logit is the unconstrained
+ * miner's bit for bit; keys, modes, records, counter and histograms are its too.  The filter is read as given (no workspace): the
+ * listed objects of every key must be ascending.  The pointers' CONTENTS are device memory and are not checked here (an id outside
+ * [0, n) is treated as no member); everything else is checked on the host before any launch.  0 <= n_units < 2^31; n == 0 or
+ * n_units == 0: nothing is launched beyond clearing the counter / histogram (n > 0).  Integer atomics only. */
+int gv_mine_scores_typed(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int64_t* set_ptr,
+                         const int32_t* set_ids, const int32_t* units, int64_t n_units, const int32_t* filt_lo,
+                         const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                         uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                         uint64_t* counter, uint64_t* hist, int n, int num_rels, int h, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Entity classification (kgvae/entity_classify.py; csrc/k_ec.hip).  Deterministic: fixed summation orders, no float atomics.
  *
@@ -751,6 +768,15 @@ int gv_transe_mine(const float* en, const float* rn, int n, int num_rels, int di
                    const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode, uint32_t key_min,
                    int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist,
                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Type-constrained whole-graph mining for TransE (csrc/k_transe_mine.hip): gv_transe_mine with the candidates restricted to the
+ * type-correct triplets; member lists, units, filter and checks exactly as gv_mine_scores_typed, tables, distances, keys and
+ * records exactly as gv_transe_mine (a surviving triplet's distance is the unconstrained miner's bit for bit). */
+int gv_transe_mine_typed(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int64_t* set_ptr,
+                         const int32_t* set_ids, const int32_t* units, int64_t n_units, const int32_t* filt_lo,
+                         const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                         uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
+                         uint64_t* counter, uint64_t* hist, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
