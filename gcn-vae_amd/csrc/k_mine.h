@@ -1,15 +1,17 @@
-// What the whole-graph miners share (gv_mine_scores in k_mine.hip, gv_transe_mine in k_transe_mine.hip): everything about SELECTING
-// candidates.  A workgroup of either miner is 256 threads (or groups of 256) on one 64 x 64 (subject tile, object tile) pair; a
-// candidate is (local row rl, local column cl) of it under relation r, with a value the kernel computed its own way.
+// What the four mining sweeps share (gv_mine_scores / gv_mine_scores_typed in k_mine.hip, gv_transe_mine / gv_transe_mine_typed in
+// k_transe_mine.hip): everything about SELECTING candidates.  A workgroup of a whole-graph sweep is 256 threads (or groups of 256)
+// on one 64 x 64 (subject tile, object tile) pair of the table, walking the relations; a candidate is (local row rl, local column
+// cl) of it under relation r, with a value the kernel computed its own way.
 //
 // Candidates: all (s, r, o) with s, o < n, less the listed triplets (filter), less s == o (exclude_self), less NaN values.  Each
 // has the ordered key of gv_topk_scores (sign-flip map, -0 -> +0, NaN -> 0 = never a candidate), larger = better; a distance d keys
-// as -d.  A kernel zeroes the keys of candidates outside the table or on an excluded diagonal (that depends on its layout), then:
-//   mine_gate  drops the keys this pass does not look at.
+// as -d.  A lane hands its 16 keys to mine_select16 with where each candidate sits, (rl, cl), and who it is, (s, o); that
+//   zeroes    the keys of candidates with an id outside [0, n) (outside the table; -1 past a list) or with s == o when excluded;
+//   mine_gate drops the keys this pass does not look at.
 //       EMIT  key >= key_min stays.
 //       HIST  keys whose top prefix_bits equal `prefix` stay.
-//   __ballot   a wave with no key left skips the rest: nearly every relation of nearly every tile in EMIT and refining HIST passes.
-//   mine_take  the filter, then
+//   __ballot  a wave with no key left skips the rest: nearly every relation of nearly every tile in EMIT and refining HIST passes.
+//   filter    a key whose bit cl of mask[rl] is set is dropped; then mine_put:
 //       EMIT  one wave-aggregated integer atomicAdd reserves slots on a 64-bit counter, (s, r, o, value bits) go out as plain
 //             16-byte vector stores while the slot is below the capacity; the counter keeps counting, so the host learns the true
 //             total.  Arrival order is arbitrary: the caller sorts.
@@ -19,11 +21,13 @@
 // ITS listed triplets once into LDS (mine_filter_load) and a relation without one -- nearly all of them -- costs one LDS flag
 // (mine_filter_relation).  No float atomics anywhere.
 //
-// The type-constrained miners (gv_mine_scores_typed, gv_transe_mine_typed) walk the transposed order -- a workgroup owns relation
-// r, one 64-row tile of r's SUBJECT member list and a span of 64-row tiles of r's OBJECT member list, rows gathered through the
-// member ids -- and share the same keys, gate, ballot, emission and histogram (mine_put); what differs is where a candidate's ids
-// come from (the member lists, MineTyped) and the filter: gathered tiles do not fit the per-tile-pair buckets, so a workgroup reads
-// the (lo, hi, ent) ranges of its 64 subjects directly (mine_typed_filter).
+// The type-constrained sweeps walk the transposed order -- a workgroup owns relation r, one 64-row tile of r's SUBJECT member list
+// and a span of 64-row tiles of r's OBJECT member list, rows gathered through the member ids.  What differs for selection is
+// where a candidate's ids come from (the member lists, MineTyped) and the filter: gathered tiles do not fit the per-tile-pair
+// buckets, so a workgroup reads the (lo, hi, ent) ranges of its 64 subjects directly (mine_typed_filter).
+//
+// Host side: an entry states its selection arguments once, as a MineCall; mine_prepare / mine_typed_prepare check them and queue
+// what precedes the sweep, mine_launch raises the kernel's LDS limit and launches it.
 #pragma once
 #include "common.h"
 
@@ -45,7 +49,7 @@ __device__ __forceinline__ float mine_key_logit(unsigned o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-// ---- what a pass selects, as both kernels' parameter structs embed it ---------------------------------------------------------
+// ---- what a pass selects, as every kernel's parameter struct embeds it ---------------------------------------------------------
 struct MineSelect {
     int n, num_rels;
     int rel_span;                      // relations per blockIdx.z
@@ -76,31 +80,50 @@ struct MineTyped {
 // bytes of the re-bucketed filter of an n-entity table with n_filt_ent listed objects (0 for an empty table)
 int64_t mine_filter_workspace_bytes(int n, int n_filt_ent);
 
-// What all four entries check alike, `who` being the entry's name in every message: sizes, mode, the capacity or the histogram
-// level, the filter given whole or not at all and (n > 0) the outputs of the mode; *sel filled but for rel_span and the filter.
-int mine_select_args(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
-                     int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
-                     int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, MineSelect* sel);
+// the selection arguments every mining entry takes, as it was given them; `who` is the entry's name in every message
+struct MineCall {
+    const char* who;
+    int n, num_rels;
+    const int32_t* filt_lo;
+    const int32_t* filt_hi;
+    const int32_t* filt_ent;
+    int n_filt_ent, exclude_self, mode;
+    uint32_t key_min;
+    int prefix_bits;
+    uint32_t prefix;
+    int bin_bits;
+    int32_t* out;
+    int64_t capacity;
+    uint64_t* counter;
+    uint64_t* hist;
+    hipStream_t st;
+};
 
-// the counter (EMIT) or the histogram (HIST) cleared on the stream
-int mine_clear(const char* who, int mode, int bin_bits, uint64_t* counter, uint64_t* hist, hipStream_t st);
+// What all four entries check alike: sizes, mode, the capacity or the histogram level, the filter given whole or not at all and
+// (n > 0) the outputs of the mode; *sel filled but for rel_span and the filter.
+int mine_select_args(const MineCall& c, MineSelect* sel);
 
 // What the two type-constrained entries do before their launch: mine_select_args, the checks of the member lists and the unit list,
-// *ty filled, the counter or the histogram cleared.  GV_OK: launch n_units workgroups, unless n == 0 or n_units == 0.
-int mine_typed_prepare(const char* who, int n, int num_rels, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units,
-                       int64_t n_units, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
-                       int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out,
-                       int64_t capacity, uint64_t* counter, uint64_t* hist, hipStream_t st, MineSelect* sel, MineTyped* ty);
+// *ty filled, the counter (EMIT) or the histogram (HIST) cleared on the stream.  GV_OK: launch n_units workgroups, unless n == 0 or
+// n_units == 0.
+int mine_typed_prepare(const MineCall& c, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                       MineSelect* sel, MineTyped* ty);
 
 // What the two whole-graph entries do before their launch: mine_select_args, then
 // *sel completed (rel_span: about four workgroups per CU of the MI355X when the table has few tiles; the result does not depend on
 // it), the filter re-bucketed per tile pair into the workspace (count, scan, fill: three small kernels, integer atomics), the
-// counter (EMIT) or the histogram (HIST) cleared, *grid = (object tiles, subject tiles, relation spans).  GV_OK: launch, unless
-// n == 0 (nothing was queued, nothing is to be done).
-int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
-                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
-                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
-                 hipStream_t st, MineSelect* sel, dim3* grid);
+// counter or the histogram cleared, *grid = (object tiles, subject tiles, relation spans).  GV_OK: launch, unless n == 0 (nothing
+// was queued, nothing is to be done).
+int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid);
+
+// one sweep's launch: the kernel's dynamic-LDS limit raised to lds_max once per device (one flag per kernel instantiation)
+template <auto KERNEL, class Params>
+static int mine_launch(const Params& p, dim3 grid, int threads, int lds, int lds_max, const MineCall& c) {
+    static unsigned long long raised = 0;
+    if (!raise_dynamic_lds((const void*)KERNEL, lds_max, raised, c.who)) return GV_ERR_SHAPE;
+    hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, c.st, p);
+    return launch_status(c.who);
+}
 
 // ---- device side: a workgroup's share of the re-bucketed filter ---------------------------------------------------------------
 // its range of tile_ent, the first MINE_FL_CAP entries copied into flist (visible after the caller's next barrier)
@@ -126,7 +149,7 @@ __device__ __forceinline__ void mine_filter_relation(const unsigned* flist, cons
     }
 }
 
-// ---- device side: gate, take, flush ------------------------------------------------------------------------------------------
+// ---- device side: gate, put, the epilogue, flush ------------------------------------------------------------------------------------------
 // the key when this pass looks at it, else 0
 template <bool HIST>
 __device__ __forceinline__ unsigned mine_gate(unsigned key, const MineSelect& sel) {
@@ -169,15 +192,37 @@ __device__ __forceinline__ void mine_put(bool ok, unsigned key, int value_bits, 
     }
 }
 
-// One gated key of candidate (rl, cl) of tile pair (m0, n0) under relation r, called by every lane of a wave together (key 0: this
-// lane has none): dropped when the relation's mask lists it (`listed`: the relation has listed triplets in this tile pair), else
-// counted in hist_s or emitted with value_bits.
-template <bool HIST>
-__device__ __forceinline__ void mine_take(unsigned key, int value_bits, int rl, int cl, int m0, int n0, int r, int lane, bool listed,
-                                          const unsigned long long* mask, unsigned* hist_s, const MineSelect& sel) {
-    bool ok = key != 0u;
-    if (listed && ok) ok = !((mask[rl] >> cl) & 1ull);
-    mine_put<HIST>(ok, key, value_bits, m0 + rl, r, n0 + cl, lane, hist_s, sel);
+// The epilogue of the sweeps (k_transe_mine writes the same rule out: see there), called by every lane of a wave together with its 16 candidates under relation r: key_of(i) is
+// candidate i's key, where(i) the candidate as (rl, cl, s, o) -- its place in the tile pair and its entity ids -- and
+// bits(i, key) its value as the record carries it.  No candidate: an id outside [0, n) (outside the table; -1 past a member list),
+// s == o when `exclude` (exclude_self, and the tile pair can hold such a pair: off the diagonal of the whole-graph sweeps the 16
+// comparisons are skipped), or `live` false (the wave's group has no relation / no tile this round).  `listed`: mask [64] may hold
+// a bit (false: the relation has no listed triplet here, the mask is not read).
+// Contract with the callables: key_of(i) is called exactly once per candidate, in the first loop, and bits(i, .) only after it
+// (tm_epilogue takes its square root in key_of).  Constraint on the spelling: `live` is tested FIRST and a dead group is said
+// through `live`, not through ids of -1 -- tested last it becomes control flow that costs the TransE kernels 28 VGPRs and
+// scratch (profiles/mine_shared/resources.txt); recompile to assembly and compare with that table after any change here.
+template <bool HIST, class KeyOf, class Where, class Bits>
+__device__ __forceinline__ void mine_select16(bool live, bool exclude, KeyOf key_of, Where where, Bits bits, int r, bool listed,
+                                              const unsigned long long* mask, int lane, unsigned* hist_s, const MineSelect& sel) {
+    unsigned key[16];
+    bool want = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        key[i] = key_of(i);
+        const int4 c = where(i);
+        if (!live || (unsigned)c.z >= (unsigned)sel.n || (unsigned)c.w >= (unsigned)sel.n || (exclude && c.z == c.w)) key[i] = 0u;
+        key[i] = mine_gate<HIST>(key[i], sel);
+        want = want || key[i] != 0u;
+    }
+    if (__ballot(want) == 0ull) return;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int4 c = where(i);
+        bool ok = key[i] != 0u;
+        if (listed && ok) ok = !((mask[c.x] >> c.y) & 1ull);
+        mine_put<HIST>(ok, key[i], bits(i, key[i]), c.z, r, c.w, lane, hist_s, sel);
+    }
 }
 
 // ---- device side: the type-constrained miners' tiles -----------------------------------------------------------------------------

@@ -12,10 +12,13 @@
 // needs k = 2 j + (l >> 5) for consecutive j, so ONE ds_read_b128 per operand feeds four MFMAs (row pitch kc + 4 floats: the
 // 16 lanes of a b128 group fall on 16 distinct 16-byte slots).
 //
-// Candidates, keys, the filter and the EMIT / HIST epilogues: k_mine.h, which both miners share; a record's fourth word is the logit
-// (mine_key_logit of its key: -0 as +0).  This file is also the one home of what the mining entries do on the host before their
-// launch (mine_select_args, mine_prepare, mine_typed_prepare), of the three small kernels that re-bucket the filter, and of the
-// type-constrained sweep gv_mine_scores_typed (k_mine_typed, further down), which walks the transposed order.
+// The type-constrained sweep gv_mine_scores_typed (k_mine_typed, further down) walks the transposed order over gathered rows.  The
+// two kernels own their loop order, barriers and staging schedule and share the rest: mine_stage_rows (one stager, the row source
+// a callable), mine_mfma_chunk (the arithmetic of a staged chunk, so a logit is the same whichever sweep computed it), mine_epilogue
+// (bias, keys, then the selection of k_mine.h: candidates, gate, filter, EMIT / HIST; a record's fourth word is the logit,
+// mine_key_logit of its key: -0 as +0) and, on the host, mine_params and mine_launch.  This file is also the one home of what every
+// mining entry does on the host before its launch (mine_select_args, mine_prepare, mine_typed_prepare on a MineCall) and of the
+// three small kernels that re-bucket the filter.
 #include <limits.h>
 
 #include <algorithm>
@@ -39,14 +42,16 @@ struct MineParams {
     MineSelect sel;
 };
 
-// one 64-row tile of E, columns [k0, k0 + kc), into LDS: row pitch kc + 4, even k first, then odd k; zeros outside the table
-__device__ __forceinline__ void mine_stage_tile(float* dst, const float* e, int ld, bool vec, int row0, int n, int k0, int h, int kc) {
+// 64 rows of E, columns [k0, k0 + kc), into LDS: row pitch kc + 4, even k first, then odd k.  Local row rl is table row row_of(rl),
+// or zeros when that is outside [0, n) (past the table's end; -1 past a member list).
+template <class RowOf>
+__device__ __forceinline__ void mine_stage_rows(float* dst, const float* e, int ld, bool vec, RowOf row_of, int n, int k0, int h, int kc) {
     const int q4 = kc >> 2, pitch = kc + 4, half = kc >> 1;
     for (int idx = threadIdx.x; idx < 64 * q4; idx += 256) {
         const int rl = idx / q4, q = idx - rl * q4;
-        const int row = row0 + rl, k = k0 + 4 * q;
+        const int row = row_of(rl), k = k0 + 4 * q;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (row < n) {
+        if ((unsigned)row < (unsigned)n) {
             const float* src = e + (size_t)row * ld + k;
             if (vec && k + 3 < h) {
                 const float4 t = *reinterpret_cast<const float4*>(src);
@@ -79,6 +84,49 @@ __device__ __forceinline__ void mine_store_w(float* ws, int kc, int t, float4 v)
     *reinterpret_cast<float2*>(ws + (kc >> 1) + 2 * t) = make_float2(v.y, v.w);
 }
 
+// One staged chunk into a wave's 32 x 32 accumulators: `groups` groups of 8 k from the lane's a (subject row), b (object row) and w
+// positions in LDS, (a * w) in f32 on the subject side, the k-ordered MFMA chain.  Both sweeps run their arithmetic here, so a
+// logit does not depend on which of them computed it.  (acc goes in and out by value: by reference it costs k_mine<HIST> 4 VGPRs.)
+__device__ __forceinline__ mine_f32x16 mine_mfma_chunk(mine_f32x16 acc, const float* a, const float* b, const float* w, int groups) {
+    // one wave per SIMD: the next group's three reads are issued before this group's MFMAs, or their latency is exposed
+    // every 256 cycles.  (The read past the last group lands in the row's / the buffer's four floats of padding: unused.)
+    float4 a_n = *reinterpret_cast<const float4*>(a);
+    float4 b_n = *reinterpret_cast<const float4*>(b);
+    float4 w_n = *reinterpret_cast<const float4*>(w);
+#pragma unroll 2
+    for (int g = 0; g < groups; ++g) {
+        const float4 a4 = a_n, b4 = b_n, w4 = w_n;
+        a_n = *reinterpret_cast<const float4*>(a + 4 * g + 4);
+        b_n = *reinterpret_cast<const float4*>(b + 4 * g + 4);
+        w_n = *reinterpret_cast<const float4*>(w + 4 * g + 4);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x * w4.x, b4.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y * w4.y, b4.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z * w4.z, b4.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w * w4.w, b4.w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// 8 k per group, whole 16-deep steps as the GEMM walks them
+__device__ __forceinline__ int mine_groups(int kc, int h, int k0) { return (min(kc, h - k0) + 15) / 16 * 2; }
+
+// The epilogue (k_mine.h: mine_select16) of a wave's 32 x 32 block at (wm, wn) of the tile pair, C/D map of the 32x32 MFMA: col =
+// lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  ids_of(rl, cl) is the candidate's (s, o), an id outside [0, n) for
+// none, `exclude` whether s == o is to be dropped and can occur here; a record's value is the logit of its key.
+template <bool HIST, class IdsOf>
+__device__ __forceinline__ void mine_epilogue(mine_f32x16 acc, float bv, int wm, int wn, int lane, bool exclude, IdsOf ids_of, int r,
+                                              bool listed, const unsigned long long* mask, unsigned* hist_s, const MineSelect& sel) {
+    const int cl = wn + (lane & 31), lhi = lane >> 5;
+    mine_select16<HIST>(
+        true, exclude, [&](int i) { return mine_key(acc[i] + bv); },
+        [&](int i) {
+            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
+            const int2 so = ids_of(rl, cl);
+            return make_int4(rl, cl, so.x, so.y);
+        },
+        [](int, unsigned k) { return __float_as_int(mine_key_logit(k)); }, r, listed, mask, lane, hist_s, sel);
+}
+
 template <bool HIST>
 __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     extern __shared__ __attribute__((aligned(16))) float mine_smem[];
@@ -98,8 +146,9 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     const int n = sel.n;
     const int r0 = blockIdx.z * sel.rel_span, r1 = min(r0 + sel.rel_span, sel.num_rels);
     const bool resident = p.n_chunks == 1;
-    const bool diag = sel.exclude_self && m0 == n0;
     const float bv = p.bias ? *p.bias : 0.f;
+    const auto s_row = [=](int rl) { return m0 + rl; };                   // table rows of the tiles' local rows, >= n past the table
+    const auto o_row = [=](int cl) { return n0 + cl; };
 
     int f_base, f_cnt;
     mine_filter_load(sel.tile_ptr, sel.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, t, &f_base, &f_cnt);
@@ -108,8 +157,8 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     if (HIST)
         for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
     if (resident) {
-        mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, n, 0, p.h, kc);
-        mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, n, 0, p.h, kc);
+        mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, 0, p.h, kc);
+        mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, sel.n, 0, p.h, kc);
         if (t < (kc >> 2) && r0 < r1) mine_store_w(Ws, kc, t, mine_load_w(p, r0, 4 * t));
     }
     __syncthreads();
@@ -133,52 +182,20 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
             const int k0 = c * kc;
             if (!resident) {
                 __syncthreads();
-                mine_stage_tile(As, p.e, p.ld_e, p.vec_e, m0, n, k0, p.h, kc);
-                mine_stage_tile(Bs, p.e, p.ld_e, p.vec_e, n0, n, k0, p.h, kc);
+                mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, k0, p.h, kc);
+                mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, sel.n, k0, p.h, kc);
                 if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
                 __syncthreads();
             }
-            const int groups = (min(kc, p.h - k0) + 15) / 16 * 2;             // 8 k per group, whole 16-deep steps as the GEMM walks them
-            const float* wsb = Ws + wb * (kc + 4) + w_off;
-            // one wave per SIMD: the next group's three reads are issued before this group's MFMAs, or their latency is exposed
-            // every 256 cycles.  (The read past the last group lands in the row's / the buffer's four floats of padding: unused.)
-            float4 a_n = *reinterpret_cast<const float4*>(As + a_off);
-            float4 b_n = *reinterpret_cast<const float4*>(Bs + b_off);
-            float4 w_n = *reinterpret_cast<const float4*>(wsb);
-#pragma unroll 2
-            for (int g = 0; g < groups; ++g) {
-                const float4 a4 = a_n, b4 = b_n, w4 = w_n;
-                a_n = *reinterpret_cast<const float4*>(As + a_off + 4 * g + 4);
-                b_n = *reinterpret_cast<const float4*>(Bs + b_off + 4 * g + 4);
-                w_n = *reinterpret_cast<const float4*>(wsb + 4 * g + 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x * w4.x, b4.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y * w4.y, b4.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z * w4.z, b4.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w * w4.w, b4.w, acc, 0, 0, 0);
-            }
+            acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + wb * (kc + 4) + w_off, mine_groups(kc, p.h, k0));
         }
         if (w_pre) mine_store_w(Ws + ((it + 1) & 1) * (kc + 4), kc, t, wnext);
         __syncthreads();
 
-        // ---- epilogue (k_mine.h): C/D map of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-        const int cl = wn + l31;
-        unsigned key[16];
-        bool want = false;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
-            unsigned k = mine_key(acc[i] + bv);
-            if (m0 + rl >= n || n0 + cl >= n || (diag && rl == cl)) k = 0u;
-            key[i] = mine_gate<HIST>(k, sel);
-            want = want || key[i] != 0u;
-        }
-        if (__ballot(want) == 0ull) continue;
-        const bool listed = fany[fb] != 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
-            mine_take<HIST>(key[i], __float_as_int(mine_key_logit(key[i])), rl, cl, m0, n0, r, lane, listed, fmask[fb], hist_s, sel);
-        }
+        // positional ids.  An id is >= n outside the table, and s == o exactly when the tiles coincide and rl == cl (m0, n0 are
+        // multiples of 64 and rl, cl < 64): the predicate m0 + rl >= n || n0 + cl >= n || (exclude_self && m0 == n0 && rl == cl).
+        mine_epilogue<HIST>(acc, bv, wm, wn, lane, sel.exclude_self && m0 == n0,
+                            [&](int rl, int cl) { return make_int2(s_row(rl), o_row(cl)); }, r, fany[fb] != 0, fmask[fb], hist_s, sel);
     }
     if (HIST) {
         __syncthreads();
@@ -271,62 +288,66 @@ static bool mine_filter_rebucket(const int32_t* filt_lo, const int32_t* filt_hi,
     return true;
 }
 
-int mine_select_args(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
-                     int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
-                     int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, MineSelect* sel) {
-    GV_REQUIRE(n >= 0 && num_rels > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: n=%d num_rels=%d n_filt_ent=%d", who, n, num_rels,
-               n_filt_ent);
-    GV_REQUIRE(mode == GV_MINE_EMIT || mode == GV_MINE_HIST, GV_ERR_SHAPE, "%s: unknown mode %d", who, mode);
+int mine_select_args(const MineCall& c, MineSelect* sel) {
+    const char* who = c.who;
+    const int n = c.n, num_rels = c.num_rels;
+    GV_REQUIRE(n >= 0 && num_rels > 0 && c.n_filt_ent >= 0, GV_ERR_SHAPE, "%s: n=%d num_rels=%d n_filt_ent=%d", who, n, num_rels,
+               c.n_filt_ent);
+    GV_REQUIRE(c.mode == GV_MINE_EMIT || c.mode == GV_MINE_HIST, GV_ERR_SHAPE, "%s: unknown mode %d", who, c.mode);
     GV_REQUIRE((long long)n * num_rels < (1LL << 31), GV_ERR_SHAPE, "%s: n * num_rels = %lld reaches 2^31", who,
                (long long)n * num_rels);
     GV_REQUIRE(num_rels <= (1 << MINE_REL_BITS), GV_ERR_SHAPE, "%s: more than %d relations", who, 1 << MINE_REL_BITS);
     GV_REQUIRE((n + 63) / 64 <= 46340, GV_ERR_SHAPE, "%s: n=%d: more than 2^31 tile pairs", who, n);
-    if (mode == GV_MINE_EMIT)
-        GV_REQUIRE(capacity >= 0 && capacity <= INT_MAX, GV_ERR_SHAPE, "%s: capacity=%lld outside [0, 2^31)", who, (long long)capacity);
+    if (c.mode == GV_MINE_EMIT)
+        GV_REQUIRE(c.capacity >= 0 && c.capacity <= INT_MAX, GV_ERR_SHAPE, "%s: capacity=%lld outside [0, 2^31)", who,
+                   (long long)c.capacity);
     else
-        GV_REQUIRE(bin_bits >= 1 && bin_bits <= MINE_HIST_BITS && prefix_bits >= 0 && prefix_bits + bin_bits <= 32 &&
-                       (prefix >> prefix_bits) == 0u,
-                   GV_ERR_SHAPE, "%s: prefix_bits=%d prefix=%u bin_bits=%d out of range", who, prefix_bits, prefix, bin_bits);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+        GV_REQUIRE(c.bin_bits >= 1 && c.bin_bits <= MINE_HIST_BITS && c.prefix_bits >= 0 && c.prefix_bits + c.bin_bits <= 32 &&
+                       (c.prefix >> c.prefix_bits) == 0u,
+                   GV_ERR_SHAPE, "%s: prefix_bits=%d prefix=%u bin_bits=%d out of range", who, c.prefix_bits, c.prefix, c.bin_bits);
+    GV_REQUIRE((c.filt_lo && c.filt_hi && c.filt_ent) || (!c.filt_lo && !c.filt_hi && !c.filt_ent), GV_ERR_NULL,
                "%s: filt_lo / filt_hi / filt_ent must be all given or all NULL", who);
     *sel = MineSelect{};
     sel->n = n; sel->num_rels = num_rels;
     sel->rel_span = num_rels;
-    sel->exclude_self = exclude_self ? 1 : 0;
-    sel->key_min = key_min; sel->prefix_bits = prefix_bits; sel->bin_bits = bin_bits; sel->prefix = prefix;
-    sel->out = (int4*)out; sel->capacity = capacity;
-    sel->counter = (unsigned long long*)counter; sel->hist = (unsigned long long*)hist;
+    sel->exclude_self = c.exclude_self ? 1 : 0;
+    sel->key_min = c.key_min; sel->prefix_bits = c.prefix_bits; sel->bin_bits = c.bin_bits; sel->prefix = c.prefix;
+    sel->out = (int4*)c.out; sel->capacity = c.capacity;
+    sel->counter = (unsigned long long*)c.counter; sel->hist = (unsigned long long*)c.hist;
     if (n == 0) return GV_OK;
-    if (mode == GV_MINE_EMIT) {
-        GV_REQUIRE(counter && (out || capacity == 0), GV_ERR_NULL, "%s: NULL output", who);
-        GV_REQUIRE(aligned16(out), GV_ERR_SHAPE, "%s: out is not 16-byte aligned", who);        // int4 records
+    if (c.mode == GV_MINE_EMIT) {
+        GV_REQUIRE(c.counter && (c.out || c.capacity == 0), GV_ERR_NULL, "%s: NULL output", who);
+        GV_REQUIRE(aligned16(c.out), GV_ERR_SHAPE, "%s: out is not 16-byte aligned", who);        // int4 records
     } else {
-        GV_REQUIRE(hist, GV_ERR_NULL, "%s: NULL histogram", who);
+        GV_REQUIRE(c.hist, GV_ERR_NULL, "%s: NULL histogram", who);
     }
     return GV_OK;
 }
 
-int mine_clear(const char* who, int mode, int bin_bits, uint64_t* counter, uint64_t* hist, hipStream_t st) {
+static int mine_fill_status(const MineCall& c) {
     char fill[64];
-    snprintf(fill, sizeof fill, "%s(fill)", who);
-    const bool emit = mode == GV_MINE_EMIT;
-    if (fill_words(emit ? (void*)counter : (void*)hist, 0u, emit ? 8 : (size_t)8 << bin_bits, st) != hipSuccess) return launch_status(fill);
+    snprintf(fill, sizeof fill, "%s(fill)", c.who);
+    return launch_status(fill);
+}
+
+// the counter (EMIT) or the histogram (HIST) cleared on the stream
+static int mine_clear(const MineCall& c) {
+    const bool emit = c.mode == GV_MINE_EMIT;
+    if (fill_words(emit ? (void*)c.counter : (void*)c.hist, 0u, emit ? 8 : (size_t)8 << c.bin_bits, c.st) != hipSuccess)
+        return mine_fill_status(c);
     return GV_OK;
 }
 
-int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
-                 int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
-                 int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes,
-                 hipStream_t st, MineSelect* sel, dim3* grid) {
-    const int rc = mine_select_args(who, n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
-                                    prefix, bin_bits, out, capacity, counter, hist, sel);
+int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid) {
+    const int rc = mine_select_args(c, sel);
+    const int n = c.n, num_rels = c.num_rels;
     if (rc != GV_OK || n == 0) return rc;
-    const bool filtered = filt_lo != nullptr;
+    const bool filtered = c.filt_lo != nullptr;
     if (filtered) {
-        GV_REQUIRE(workspace, GV_ERR_NULL, "%s: a filter needs the workspace", who);
-        GV_REQUIRE(aligned16(workspace), GV_ERR_WORKSPACE, "%s: the workspace is not 16-byte aligned", who);
-        GV_REQUIRE(workspace_bytes >= mine_filter_workspace_bytes(n, n_filt_ent), GV_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes",
-                   who, (long long)workspace_bytes, (long long)mine_filter_workspace_bytes(n, n_filt_ent));
+        GV_REQUIRE(workspace, GV_ERR_NULL, "%s: a filter needs the workspace", c.who);
+        GV_REQUIRE(aligned16(workspace), GV_ERR_WORKSPACE, "%s: the workspace is not 16-byte aligned", c.who);
+        GV_REQUIRE(workspace_bytes >= mine_filter_workspace_bytes(n, c.n_filt_ent), GV_ERR_WORKSPACE, "%s: workspace %lld < %lld bytes",
+                   c.who, (long long)workspace_bytes, (long long)mine_filter_workspace_bytes(n, c.n_filt_ent));
     }
     const int tiles_1d = (n + 63) / 64;
     const int tiles = tiles_1d * tiles_1d;
@@ -335,59 +356,49 @@ int mine_prepare(const char* who, int n, int num_rels, const int32_t* filt_lo, c
     sel->rel_span = (int)((num_rels + spans - 1) / spans);
     *grid = dim3(tiles_1d, tiles_1d, (num_rels + sel->rel_span - 1) / sel->rel_span);
 
-    if (filtered && !mine_filter_rebucket(filt_lo, filt_hi, filt_ent, n_filt_ent, n, num_rels, workspace, st, &sel->tile_ptr, &sel->tile_ent)) {
-        char fill[64];
-        snprintf(fill, sizeof fill, "%s(fill)", who);
-        return launch_status(fill);
-    }
-    return mine_clear(who, mode, bin_bits, counter, hist, st);
+    if (filtered && !mine_filter_rebucket(c.filt_lo, c.filt_hi, c.filt_ent, c.n_filt_ent, n, num_rels, workspace, c.st, &sel->tile_ptr,
+                                          &sel->tile_ent))
+        return mine_fill_status(c);
+    return mine_clear(c);
 }
 
-int mine_typed_prepare(const char* who, int n, int num_rels, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units,
-                       int64_t n_units, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
-                       int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out,
-                       int64_t capacity, uint64_t* counter, uint64_t* hist, hipStream_t st, MineSelect* sel, MineTyped* ty) {
-    const int rc = mine_select_args(who, n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
-                                    prefix, bin_bits, out, capacity, counter, hist, sel);
+int mine_typed_prepare(const MineCall& c, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                       MineSelect* sel, MineTyped* ty) {
+    const int rc = mine_select_args(c, sel);
     if (rc != GV_OK) return rc;
-    GV_REQUIRE(n_units >= 0 && n_units <= INT_MAX, GV_ERR_SHAPE, "%s: n_units=%lld outside [0, 2^31)", who, (long long)n_units);
-    if (n == 0) return GV_OK;
-    GV_REQUIRE(n_units == 0 || (set_ptr && set_ids && units), GV_ERR_NULL, "%s: NULL member lists or unit list", who);
-    GV_REQUIRE(aligned16(units), GV_ERR_SHAPE, "%s: units is not 16-byte aligned", who);          // int4 records
+    GV_REQUIRE(n_units >= 0 && n_units <= INT_MAX, GV_ERR_SHAPE, "%s: n_units=%lld outside [0, 2^31)", c.who, (long long)n_units);
+    if (c.n == 0) return GV_OK;
+    GV_REQUIRE(n_units == 0 || (set_ptr && set_ids && units), GV_ERR_NULL, "%s: NULL member lists or unit list", c.who);
+    GV_REQUIRE(aligned16(units), GV_ERR_SHAPE, "%s: units is not 16-byte aligned", c.who);          // int4 records
     *ty = MineTyped{};
     ty->set_ptr = (const long long*)set_ptr; ty->set_ids = set_ids; ty->units = (const int4*)units;
-    ty->filt_lo = filt_lo; ty->filt_hi = filt_hi; ty->filt_ent = filt_ent; ty->n_filt_ent = n_filt_ent;
-    return mine_clear(who, mode, bin_bits, counter, hist, st);
+    ty->filt_lo = c.filt_lo; ty->filt_hi = c.filt_hi; ty->filt_ent = c.filt_ent; ty->n_filt_ent = c.n_filt_ent;
+    return mine_clear(c);
+}
+
+// What both DistMult entries check of their tables; then *p filled but for the selection.
+static int mine_params(const char* who, const float* e, int ld_e, const float* w, int ld_w, const float* bias, int n, int num_rels, int h,
+                       int n_filt_ent, MineParams* p) {
+    GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: n=%d num_rels=%d h=%d n_filt_ent=%d", who, n,
+               num_rels, h, n_filt_ent);
+    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "%s: leading dimension too small (ld_e=%d ld_w=%d h=%d)", who, ld_e, ld_w, h);
+    GV_REQUIRE(n == 0 || (e && w), GV_ERR_NULL, "%s: NULL table", who);
+    p->e = e; p->w = w; p->bias = bias;
+    p->h = h; p->ld_e = ld_e; p->ld_w = ld_w;
+    p->vec_e = aligned16(e) && (ld_e % 4 == 0);
+    p->vec_w = aligned16(w) && (ld_w % 4 == 0);
+    const int h16 = (h + 15) / 16 * 16;
+    p->kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
+    p->n_chunks = (h + p->kc - 1) / p->kc;
+    return GV_OK;
 }
 
 // ---- the type-constrained sweep (gv_mine_scores_typed) -----------------------------------------------------------------------------
 // Loop order, transposed: a workgroup owns one unit = (relation r, one 64-row tile of r's subject members, a span of 64-row tiles
-// of r's object members).  Rows of E are GATHERED through the member ids into the LDS layout of k_mine; the subject tile and w[r]
-// are staged once per unit while the table fits one chunk, an object tile once per tile pair (no other relation could reuse it: its
-// rows belong to r's list).  The arithmetic per pair is k_mine's: (E[s] * w[r]) in f32, the k-ordered 32x32x2 chain over ceil16(h),
-// + bias; so a surviving triplet's logit is the unconstrained miner's, bit for bit.
-__device__ __forceinline__ void mine_stage_gather(float* dst, const float* e, int ld, bool vec, const int* ids_s, int k0, int h, int kc) {
-    const int q4 = kc >> 2, pitch = kc + 4, half = kc >> 1;
-    for (int idx = threadIdx.x; idx < 64 * q4; idx += 256) {
-        const int rl = idx / q4, q = idx - rl * q4;
-        const int row = ids_s[rl], k = k0 + 4 * q;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (row >= 0) {
-            const float* src = e + (size_t)row * ld + k;
-            if (vec && k + 3 < h) {
-                const float4 t = *reinterpret_cast<const float4*>(src);
-                v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = k + i < h ? src[i] : 0.f;
-            }
-        }
-        float* d = dst + rl * pitch + 2 * q;
-        *reinterpret_cast<float2*>(d) = make_float2(v[0], v[2]);
-        *reinterpret_cast<float2*>(d + half) = make_float2(v[1], v[3]);
-    }
-}
-
+// of r's object members).  Rows of E are GATHERED through the member ids (mine_stage_rows) into the same LDS layout; the subject tile
+// and w[r] are staged once per unit while the table fits one chunk, an object tile once per tile pair (no other relation could
+// reuse it: its rows belong to r's list).  The arithmetic per pair is mine_mfma_chunk and mine_epilogue, the very code k_mine runs,
+// so a surviving triplet's logit is the unconstrained miner's, bit for bit.
 struct MineTypedParams {
     MineParams p;
     MineTyped ty;
@@ -409,6 +420,8 @@ __global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
     const int l31 = lane & 31, lhi = lane >> 5;
+    const auto s_row = [&](int rl) { return sid_s[rl]; };                 // table rows of the tiles' local rows: the member ids
+    const auto o_row = [&](int cl) { return oid_s[cl]; };
     const int4 unit = ty.units[blockIdx.x];
     const int r = unit.x;
     if (r < 0 || r >= sel.num_rels) return;              // uniform: not a unit
@@ -420,7 +433,7 @@ __global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
         for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
     __syncthreads();
     if (resident) {
-        mine_stage_gather(As, p.e, p.ld_e, p.vec_e, sid_s, 0, p.h, kc);
+        mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, 0, p.h, kc);
         if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, 4 * t));
     }
     const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
@@ -439,49 +452,18 @@ __global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
             const int k0 = c * kc;
             if (c > 0) __syncthreads();
             if (!resident) {
-                mine_stage_gather(As, p.e, p.ld_e, p.vec_e, sid_s, k0, p.h, kc);
+                mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, k0, p.h, kc);
                 if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
             }
-            mine_stage_gather(Bs, p.e, p.ld_e, p.vec_e, oid_s, k0, p.h, kc);
+            mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, sel.n, k0, p.h, kc);
             __syncthreads();
-            const int groups = (min(kc, p.h - k0) + 15) / 16 * 2;             // as k_mine: whole 16-deep steps
-            const float* wsb = Ws + w_off;
-            float4 a_n = *reinterpret_cast<const float4*>(As + a_off);
-            float4 b_n = *reinterpret_cast<const float4*>(Bs + b_off);
-            float4 w_n = *reinterpret_cast<const float4*>(wsb);
-#pragma unroll 2
-            for (int g = 0; g < groups; ++g) {
-                const float4 a4 = a_n, b4 = b_n, w4 = w_n;
-                a_n = *reinterpret_cast<const float4*>(As + a_off + 4 * g + 4);
-                b_n = *reinterpret_cast<const float4*>(Bs + b_off + 4 * g + 4);
-                w_n = *reinterpret_cast<const float4*>(wsb + 4 * g + 4);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x * w4.x, b4.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y * w4.y, b4.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z * w4.z, b4.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w * w4.w, b4.w, acc, 0, 0, 0);
-            }
+            acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + w_off, mine_groups(kc, p.h, k0));
         }
 
-        // ---- epilogue (k_mine.h), ids through the member lists; fmask is complete: a barrier followed the filter's atomics
-        const int cl = wn + l31, o = oid_s[cl];
-        unsigned key[16];
-        bool want = false;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi, s = sid_s[rl];
-            unsigned k = mine_key(acc[i] + bv);
-            if (s < 0 || o < 0 || (sel.exclude_self && s == o)) k = 0u;
-            key[i] = mine_gate<HIST>(k, sel);
-            want = want || key[i] != 0u;
-        }
-        if (__ballot(want) != 0ull) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int rl = wm + (i & 3) + 8 * (i >> 2) + 4 * lhi;
-                const bool ok = key[i] != 0u && !((fmask[rl] >> cl) & 1ull);
-                mine_put<HIST>(ok, key[i], __float_as_int(mine_key_logit(key[i])), sid_s[rl], r, o, lane, hist_s, sel);
-            }
-        }
+        // ids through the member lists, -1 past them; fmask is complete (a barrier followed the filter's atomics) and always read
+        const int o = oid_s[wn + l31];
+        mine_epilogue<HIST>(acc, bv, wm, wn, lane, sel.exclude_self != 0, [&](int rl, int) { return make_int2(sid_s[rl], o); }, r, true,
+                            fmask, hist_s, sel);
     }
     if (HIST) {
         __syncthreads();
@@ -503,35 +485,17 @@ extern "C" int gv_mine_scores(const float* e, int ld_e, const float* w, int ld_w
                               uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                               uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels,
                               int h, void* stream) {
-    GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_mine_scores: n=%d num_rels=%d h=%d n_filt_ent=%d",
-               n, num_rels, h, n_filt_ent);
-    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_mine_scores: leading dimension too small (ld_e=%d ld_w=%d h=%d)", ld_e, ld_w, h);
-    GV_REQUIRE(n == 0 || (e && w), GV_ERR_NULL, "gv_mine_scores: NULL table");
-    hipStream_t st = (hipStream_t)stream;
+    const MineCall c{"gv_mine_scores", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
+                     prefix, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
     MineParams p{};
     dim3 grid;
-    const int rc = mine_prepare("gv_mine_scores", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
-                                prefix_bits, prefix, bin_bits, out, capacity, counter, hist, workspace, workspace_bytes, st, &p.sel, &grid);
+    int rc = mine_params(c.who, e, ld_e, w, ld_w, bias, n, num_rels, h, n_filt_ent, &p);
+    if (rc == GV_OK) rc = mine_prepare(c, workspace, workspace_bytes, &p.sel, &grid);
     if (rc != GV_OK || n == 0) return rc;
-    p.e = e; p.w = w; p.bias = bias;
-    p.h = h; p.ld_e = ld_e; p.ld_w = ld_w;
-    p.vec_e = aligned16(e) && (ld_e % 4 == 0);
-    p.vec_w = aligned16(w) && (ld_w % 4 == 0);
-    const int h16 = (h + 15) / 16 * 16;
-    p.kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
-    p.n_chunks = (h + p.kc - 1) / p.kc;
     const int lds = (2 * 64 * (p.kc + 4) + 2 * (p.kc + 4)) * (int)sizeof(float);
     const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);
-    if (mode == GV_MINE_EMIT) {
-        static unsigned long long raised = 0;
-        if (!raise_dynamic_lds((const void*)k_mine<false>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine<false>, grid, dim3(256), lds, st, p);
-    } else {
-        static unsigned long long raised = 0;
-        if (!raise_dynamic_lds((const void*)k_mine<true>, lds_max, raised, "gv_mine_scores")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine<true>, grid, dim3(256), lds, st, p);
-    }
-    return launch_status("gv_mine_scores");
+    return mode == GV_MINE_EMIT ? mine_launch<k_mine<false>>(p, grid, 256, lds, lds_max, c)
+                                : mine_launch<k_mine<true>>(p, grid, 256, lds, lds_max, c);
 }
 
 extern "C" int gv_mine_scores_typed(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int64_t* set_ptr,
@@ -539,35 +503,15 @@ extern "C" int gv_mine_scores_typed(const float* e, int ld_e, const float* w, in
                                     const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
                                     uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                                     uint64_t* counter, uint64_t* hist, int n, int num_rels, int h, void* stream) {
-    GV_REQUIRE(n >= 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE,
-               "gv_mine_scores_typed: n=%d num_rels=%d h=%d n_filt_ent=%d", n, num_rels, h, n_filt_ent);
-    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_mine_scores_typed: leading dimension too small (ld_e=%d ld_w=%d h=%d)", ld_e,
-               ld_w, h);
-    GV_REQUIRE(n == 0 || (e && w), GV_ERR_NULL, "gv_mine_scores_typed: NULL table");
-    hipStream_t st = (hipStream_t)stream;
+    const MineCall c{"gv_mine_scores_typed", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
+                     prefix_bits, prefix, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
     MineTypedParams tp{};
-    MineParams& p = tp.p;
-    const int rc = mine_typed_prepare("gv_mine_scores_typed", n, num_rels, set_ptr, set_ids, units, n_units, filt_lo, filt_hi, filt_ent,
-                                      n_filt_ent, exclude_self, mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, counter, hist,
-                                      st, &p.sel, &tp.ty);
+    int rc = mine_params(c.who, e, ld_e, w, ld_w, bias, n, num_rels, h, n_filt_ent, &tp.p);
+    if (rc == GV_OK) rc = mine_typed_prepare(c, set_ptr, set_ids, units, n_units, &tp.p.sel, &tp.ty);
     if (rc != GV_OK || n == 0 || n_units == 0) return rc;
-    p.e = e; p.w = w; p.bias = bias;
-    p.h = h; p.ld_e = ld_e; p.ld_w = ld_w;
-    p.vec_e = aligned16(e) && (ld_e % 4 == 0);
-    p.vec_w = aligned16(w) && (ld_w % 4 == 0);
-    const int h16 = (h + 15) / 16 * 16;
-    p.kc = h16 <= MINE_KC_MAX ? h16 : MINE_KC_MAX;
-    p.n_chunks = (h + p.kc - 1) / p.kc;
-    const int lds = (2 * 64 + 1) * (p.kc + 4) * (int)sizeof(float);
+    const int lds = (2 * 64 + 1) * (tp.p.kc + 4) * (int)sizeof(float);
     const int lds_max = (2 * 64 + 1) * (MINE_KC_MAX + 4) * (int)sizeof(float);
-    if (mode == GV_MINE_EMIT) {
-        static unsigned long long raised = 0;
-        if (!raise_dynamic_lds((const void*)k_mine_typed<false>, lds_max, raised, "gv_mine_scores_typed")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine_typed<false>, dim3((unsigned)n_units), dim3(256), lds, st, tp);
-    } else {
-        static unsigned long long raised = 0;
-        if (!raise_dynamic_lds((const void*)k_mine_typed<true>, lds_max, raised, "gv_mine_scores_typed")) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_mine_typed<true>, dim3((unsigned)n_units), dim3(256), lds, st, tp);
-    }
-    return launch_status("gv_mine_scores_typed");
+    const dim3 grid((unsigned)n_units);
+    return mode == GV_MINE_EMIT ? mine_launch<k_mine_typed<false>>(tp, grid, 256, lds, lds_max, c)
+                                : mine_launch<k_mine_typed<true>>(tp, grid, 256, lds, lds_max, c);
 }

@@ -19,9 +19,14 @@
 // (checked every TM_CHECK columns; NaN never compares greater, so NaN pairs run to the end and are dropped by their key).  What a
 // pair's key is compared with is unchanged, so the result is too.
 //
-// Candidates, keys (those of -d: larger = nearer, 0 = NaN only), the filter and the EMIT / HIST epilogues: k_mine.h, which both
-// miners share, as they share the host set-up before the launch (mine_prepare, k_mine.hip); a record's fourth word is the bits of d
-// itself (never -0: the sums start at +0 and add |.| or squares).
+// The type-constrained sweep gv_transe_mine_typed (k_transe_mine_typed, further down) walks the transposed order over gathered rows.
+// The two kernels own their loop order, barriers and LDS layout and share the rest: tm_stage_rows (one stager, the row source a
+// callable), tm_bound and tm_columns (the column loop with its early exit, so a distance is the same whichever sweep computed it),
+// the selection rule of k_mine.h (keys of -d: larger = nearer, 0 = NaN only; candidates, gate, filter, EMIT / HIST: through
+// tm_epilogue and mine_select16 in the typed kernel, written out in k_transe_mine, which is two VGPRs and 1 % of an L2 top-K run
+// better off that way) and, on the host, tm_params and what every mining entry does before its launch (MineCall, mine_prepare /
+// mine_typed_prepare, mine_launch: k_mine.h, k_mine.hip).  A record's fourth word is the bits of d itself (never -0: the sums start
+// at +0 and add |.| or squares).
 #include <algorithm>
 
 #include "common.h"
@@ -44,11 +49,14 @@ struct TeMineParams {
     MineSelect sel;
 };
 
-// columns [k0, k0 + kn) of rows row0 .. row0 + 63 of en into dst [kn][TM_LD]; zeros past the table
-__device__ __forceinline__ void tm_stage(float* dst, const float* __restrict__ en, int row0, int n, int dim, int k0, int kn) {
-    for (int x = threadIdx.x; x < TE_TQ * kn; x += TM_THREADS) {
-        const int row = x / kn, k = x - row * kn;
-        dst[k * TM_LD + row] = row0 + row < n ? en[(size_t)(row0 + row) * dim + k0 + k] : 0.f;
+// columns [k0, k0 + kn) of 64 rows of en into dst [kn][TM_LD] by `threads` threads tl: local row `row` is table row row_of(row), or
+// zeros when that is outside [0, n) (past the table's end; -1 past a member list)
+template <class RowOf>
+__device__ __forceinline__ void tm_stage_rows(float* dst, const float* __restrict__ en, RowOf row_of, int n, int dim, int k0, int kn,
+                                              int tl, int threads) {
+    for (int x = tl; x < TE_TQ * kn; x += threads) {
+        const int row = x / kn, k = x - row * kn, id = row_of(row);
+        dst[k * TM_LD + row] = (unsigned)id < (unsigned)n ? en[(size_t)id * dim + k0 + k] : 0.f;
     }
 }
 
@@ -63,6 +71,56 @@ __device__ __forceinline__ float tm_bound(const MineSelect& sel) {
         bound = P == 1 || dmax < 0.f ? dmax : fmaxf(dmax * dmax * 1.000001f, 1e-30f);
     }
     return bound;
+}
+
+// kn staged columns into a lane's 4 x 4 accumulators: subjects a_ptr[k * TM_LD + 0 .. 3] + Rs[k] against objects b_ptr[k * TM_LD +
+// 0 .. 3], te_pair_term in column order.  Both sweeps run their arithmetic here, so a distance does not depend on which of them
+// computed it.  `past` (wave-uniform) is set once every pair of the wave is beyond `bound`, looked at every TM_CHECK columns; a
+// wave that comes in past does nothing.
+template <int P>
+__device__ __forceinline__ void tm_columns(float (&acc)[4][4], const float* a_ptr, const float* b_ptr, const float* Rs, int kn, float bound,
+                                           bool& past) {
+    for (int kb = 0; kb < kn && !past; kb += TM_CHECK) {
+        const int ke = min(kb + TM_CHECK, kn);
+#pragma unroll 4
+        for (int k = kb; k < ke; ++k) {
+            const float4 qa = *reinterpret_cast<const float4*>(a_ptr + k * TM_LD);
+            const float4 eb = *reinterpret_cast<const float4*>(b_ptr + k * TM_LD);
+            const float rv = Rs[k];
+            const float qv[4] = {qa.x + rv, qa.y + rv, qa.z + rv, qa.w + rv}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], P);
+        }
+        bool all_past = true;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) all_past = all_past && acc[a][b] > bound;
+        past = __all(all_past) != 0;
+    }
+}
+
+// The typed kernel's epilogue (k_mine.h: mine_select16) for lane (tx, ty), which holds local rows 4 ty + a and columns 4 tx + b of the tile pair:
+// sqrtf for p = 2, the key of -d.  ids_of(rl, cl) is the candidate's (s, o), an id outside [0, n) for none; `live` false: the
+// lane's group has nothing this round; `exclude`: s == o is to be dropped and can occur here.  A record's value is d itself.
+template <int P, bool HIST, class IdsOf>
+__device__ __forceinline__ void tm_epilogue(float (&acc)[4][4], bool live, bool exclude, int tx, int ty, int lane, IdsOf ids_of, int r,
+                                            bool listed, const unsigned long long* mask, unsigned* hist_s, const MineSelect& sel) {
+    mine_select16<HIST>(
+        live, exclude,
+        [&](int i) {
+            float& d = acc[i >> 2][i & 3];
+            if (P == 2) d = sqrtf(d);
+            return mine_key(-d);
+        },
+        [&](int i) {
+            const int rl = 4 * ty + (i >> 2), cl = 4 * tx + (i & 3);
+            const int2 so = ids_of(rl, cl);
+            return make_int4(rl, cl, so.x, so.y);
+        },
+        [&](int i, unsigned) { return __float_as_int(acc[i >> 2][i & 3]); }, r, listed, mask, lane, hist_s, sel);
 }
 
 template <int P, bool HIST>
@@ -83,7 +141,8 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     const int r0 = blockIdx.z * sel.rel_span, r1 = min(r0 + sel.rel_span, sel.num_rels);
     const bool resident = p.n_chunks == 1;
     const bool diag = sel.exclude_self && m0 == n0;
-
+    const auto s_row = [=](int rl) { return m0 + rl; };                   // table rows of the tiles' local rows, >= n past the table
+    const auto o_row = [=](int cl) { return n0 + cl; };
     const float bound = tm_bound<P, HIST>(sel);
 
     int f_base, f_cnt;
@@ -91,8 +150,8 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     if (HIST)
         for (int i = t; i < (1 << MINE_HIST_BITS); i += TM_THREADS) hist_s[i] = 0u;
     if (resident) {
-        tm_stage(As, p.en, m0, n, p.dim, 0, p.dim);
-        tm_stage(Bs, p.en, n0, n, p.dim, 0, p.dim);
+        tm_stage_rows(As, p.en, s_row, n, p.dim, 0, p.dim, t, TM_THREADS);
+        tm_stage_rows(Bs, p.en, o_row, n, p.dim, 0, p.dim, t, TM_THREADS);
     }
     const float* a_ptr = As + 4 * ty;
     const float* b_ptr = Bs + 4 * tx;
@@ -119,36 +178,19 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
             const int k0 = c * kc, kn = min(kc, p.dim - k0);
             if (!resident) {
                 __syncthreads();
-                tm_stage(As, p.en, m0, n, p.dim, k0, kn);
-                tm_stage(Bs, p.en, n0, n, p.dim, k0, kn);
+                tm_stage_rows(As, p.en, s_row, n, p.dim, k0, kn, t, TM_THREADS);
+                tm_stage_rows(Bs, p.en, o_row, n, p.dim, k0, kn, t, TM_THREADS);
                 if (live)
                     for (int k = tl; k < kn; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
                 __syncthreads();
             }
-            for (int kb = 0; kb < kn && !past; kb += TM_CHECK) {
-                const int ke = min(kb + TM_CHECK, kn);
-#pragma unroll 4
-                for (int k = kb; k < ke; ++k) {
-                    const float4 qa = *reinterpret_cast<const float4*>(a_ptr + k * TM_LD);
-                    const float4 eb = *reinterpret_cast<const float4*>(b_ptr + k * TM_LD);
-                    const float rv = Rs[k];
-                    const float qv[4] = {qa.x + rv, qa.y + rv, qa.z + rv, qa.w + rv}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], P);
-                }
-                bool all_past = true;
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) all_past = all_past && acc[a][b] > bound;
-                past = __all(all_past) != 0;
-            }
+            tm_columns<P>(acc, a_ptr, b_ptr, Rs, kn, bound, past);
         }
         __syncthreads();                                 // fmask / fany of this round are complete
 
-        // ---- epilogue (k_mine.h): lane (tx, ty) holds subjects 4 ty + a, objects 4 tx + b
+        // ---- epilogue, this kernel's own: lane (tx, ty) holds subjects 4 ty + a, objects 4 tx + b.  It is the rule of mine_select16
+        // (k_mine.h) with positional ids, written out: through mine_select16 this kernel took two more VGPRs for p = 1 and an L2
+        // top-K run 1 % longer (profiles/mine_shared).  Change the two together.
         unsigned key[4][4];
         bool want = false;
 #pragma unroll
@@ -167,21 +209,17 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b)
-                mine_take<HIST>(key[a][b], __float_as_int(acc[a][b]), 4 * ty + a, 4 * tx + b, m0, n0, r, lane, listed, fmask[g], hist_s, sel);
+            for (int b = 0; b < 4; ++b) {
+                const int rl = 4 * ty + a, cl = 4 * tx + b;
+                bool ok = key[a][b] != 0u;
+                if (listed && ok) ok = !((fmask[g][rl] >> cl) & 1ull);
+                mine_put<HIST>(ok, key[a][b], __float_as_int(acc[a][b]), m0 + rl, r, n0 + cl, lane, hist_s, sel);
+            }
     }
     if (HIST) {
         __syncthreads();
         if (t < 256) mine_hist_flush(hist_s, sel, t);
     }
-}
-
-template <int P, bool HIST>
-static int tm_launch(const TeMineParams& p, dim3 grid, int lds, int lds_max, hipStream_t st) {
-    static unsigned long long raised = 0;
-    if (!raise_dynamic_lds((const void*)k_transe_mine<P, HIST>, lds_max, raised, "gv_transe_mine")) return GV_ERR_SHAPE;
-    hipLaunchKernelGGL((k_transe_mine<P, HIST>), grid, dim3(TM_THREADS), lds, st, p);
-    return launch_status("gv_transe_mine");
 }
 
 // ---- the type-constrained sweep (gv_transe_mine_typed) -----------------------------------------------------------------------------
@@ -190,7 +228,7 @@ static int tm_launch(const TeMineParams& p, dim3 grid, int lds, int lds_max, hip
 // are r's list), so the four groups of 256 threads that k_transe_mine spreads over four relations here take four OBJECT tiles of
 // the span against the one subject tile and the one row of rn: five tiles at a time, in TMT_KC-column chunks (5 x 68 x 64 floats =
 // 85 KiB + 20 KiB static: one workgroup of 16 waves a compute unit, the occupancy of k_transe_mine).  The 16 accumulators live
-// across a pair's chunks and te_pair_term walks the columns in order, so a distance is k_transe_mine's bit for bit; the monotone
+// across a pair's chunks and tm_columns walks the columns in order, so a distance is k_transe_mine's bit for bit; the monotone
 // early exit is kept per wave, and a round whose every wave is past the bound stops staging chunks.
 constexpr int TMT_KC = 64;
 
@@ -198,15 +236,6 @@ struct TeMineTypedParams {
     TeMineParams p;
     MineTyped ty;
 };
-
-// columns [k0, k0 + kn) of the rows ids_s[0 .. 63] of en into dst [kn][TM_LD] by `threads` threads tl; zeros for id -1
-__device__ __forceinline__ void tm_stage_gather(float* dst, const float* __restrict__ en, const int* ids_s, int dim, int k0, int kn,
-                                                int tl, int threads) {
-    for (int x = tl; x < TE_TQ * kn; x += threads) {
-        const int row = x / kn, k = x - row * kn, id = ids_s[row];
-        dst[k * TM_LD + row] = id >= 0 ? en[(size_t)id * dim + k0 + k] : 0.f;
-    }
-}
 
 template <int P, bool HIST>
 __global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed(const TeMineTypedParams tp) {
@@ -252,56 +281,17 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed(const TeMineTy
         for (int k0 = 0; k0 < p.dim; k0 += kc) {
             const int kn = min(kc, p.dim - k0);
             if (__syncthreads_and(past)) break;          // the last chunk's reads are over; nothing left to look at: uniform
-            tm_stage_gather(As, p.en, sid_s, p.dim, k0, kn, t, TM_THREADS);
-            if (live) tm_stage_gather(Bs, p.en, oid_s[g], p.dim, k0, kn, tl, 256);
+            tm_stage_rows(As, p.en, [&](int row) { return sid_s[row]; }, sel.n, p.dim, k0, kn, t, TM_THREADS);
+            if (live) tm_stage_rows(Bs, p.en, [&](int row) { return oid_s[g][row]; }, sel.n, p.dim, k0, kn, tl, 256);
             for (int k = t; k < kn; k += TM_THREADS) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
             __syncthreads();
-            for (int kb = 0; kb < kn && !past; kb += TM_CHECK) {
-                const int ke = min(kb + TM_CHECK, kn);
-#pragma unroll 4
-                for (int k = kb; k < ke; ++k) {
-                    const float4 qa = *reinterpret_cast<const float4*>(a_ptr + k * TM_LD);
-                    const float4 eb = *reinterpret_cast<const float4*>(b_ptr + k * TM_LD);
-                    const float rv = Rs[k];
-                    const float qv[4] = {qa.x + rv, qa.y + rv, qa.z + rv, qa.w + rv}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
-#pragma unroll
-                    for (int a = 0; a < 4; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], P);
-                }
-                bool all_past = true;
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) all_past = all_past && acc[a][b] > bound;
-                past = __all(all_past) != 0;
-            }
+            tm_columns<P>(acc, a_ptr, b_ptr, Rs, kn, bound, past);
         }
         __syncthreads();                                 // fmask of this round is complete
 
-        // ---- epilogue (k_mine.h): lane (tx, ty4) holds subjects 4 ty4 + a, objects 4 tx + b, ids through the member lists
-        unsigned key[4][4];
-        bool want = false;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                if (P == 2) acc[a][b] = sqrtf(acc[a][b]);
-                const int s = sid_s[4 * ty4 + a], o = oid_s[g][4 * tx + b];
-                unsigned k = mine_key(-acc[a][b]);
-                if (!live || s < 0 || o < 0 || (sel.exclude_self && s == o)) k = 0u;
-                key[a][b] = mine_gate<HIST>(k, sel);
-                want = want || key[a][b] != 0u;
-            }
-        if (__ballot(want) == 0ull) continue;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int rl = 4 * ty4 + a, cl = 4 * tx + b;
-                const bool ok = key[a][b] != 0u && !((fmask[g][rl] >> cl) & 1ull);
-                mine_put<HIST>(ok, key[a][b], __float_as_int(acc[a][b]), sid_s[rl], r, oid_s[g][cl], lane, hist_s, sel);
-            }
+        // ids through the member lists, -1 past them and for a group without a tile; fmask is always read
+        tm_epilogue<P, HIST>(acc, live, sel.exclude_self != 0, tx, ty4, lane,
+                             [&](int rl, int cl) { return make_int2(sid_s[rl], oid_s[g][cl]); }, r, true, fmask[g], hist_s, sel);
     }
     if (HIST) {
         __syncthreads();
@@ -309,13 +299,15 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed(const TeMineTy
     }
 }
 
-template <int P, bool HIST>
-static int tmt_launch(const TeMineTypedParams& tp, unsigned n_units, int lds, hipStream_t st) {
-    static unsigned long long raised = 0;
-    const int lds_max = ((1 + TM_GROUPS) * TM_LD + 1) * TMT_KC * (int)sizeof(float);
-    if (!raise_dynamic_lds((const void*)k_transe_mine_typed<P, HIST>, lds_max, raised, "gv_transe_mine_typed")) return GV_ERR_SHAPE;
-    hipLaunchKernelGGL((k_transe_mine_typed<P, HIST>), dim3(n_units), dim3(TM_THREADS), lds, st, tp);
-    return launch_status("gv_transe_mine_typed");
+// What both entries check of their tables and the norm; then *p filled but for the selection, in chunks of at most kc_max columns.
+static int tm_params(const char* who, const float* en, const float* rn, int n, int dim, int p_norm, int kc_max, TeMineParams* p) {
+    GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE, "%s: dim=%d (1..%d) p_norm=%d (1 or 2)",
+               who, dim, GV_TRANSE_MAX_DIM, p_norm);
+    GV_REQUIRE(n <= 0 || (en && rn), GV_ERR_NULL, "%s: NULL table", who);
+    p->en = en; p->rn = rn; p->dim = dim;
+    p->kc = std::min(dim, kc_max);
+    p->n_chunks = (dim + p->kc - 1) / p->kc;
+    return GV_OK;
 }
 
 }  // namespace gv
@@ -331,22 +323,20 @@ extern "C" int gv_transe_mine(const float* en, const float* rn, int n, int num_r
                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
                               uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                               uint64_t* counter, uint64_t* hist, void* workspace, int64_t workspace_bytes, void* stream) {
-    GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
-               "gv_transe_mine: dim=%d (1..%d) p_norm=%d (1 or 2)", dim, GV_TRANSE_MAX_DIM, p_norm);
-    GV_REQUIRE(n <= 0 || (en && rn), GV_ERR_NULL, "gv_transe_mine: NULL table");
-    hipStream_t st = (hipStream_t)stream;
+    const MineCall c{"gv_transe_mine", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min, prefix_bits,
+                     prefix, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
     TeMineParams p{};
     dim3 grid;
-    const int rc = mine_prepare("gv_transe_mine", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
-                                prefix_bits, prefix, bin_bits, out, capacity, counter, hist, workspace, workspace_bytes, st, &p.sel, &grid);
+    int rc = tm_params(c.who, en, rn, n, dim, p_norm, TM_KC_MAX, &p);
+    if (rc == GV_OK) rc = mine_prepare(c, workspace, workspace_bytes, &p.sel, &grid);
     if (rc != GV_OK || n == 0) return rc;
-    p.en = en; p.rn = rn; p.dim = dim;
-    p.kc = std::min(dim, TM_KC_MAX);
-    p.n_chunks = (dim + p.kc - 1) / p.kc;
     const int lds = (2 * TM_LD + TM_GROUPS) * p.kc * (int)sizeof(float);
     const int lds_max = (2 * TM_LD + TM_GROUPS) * TM_KC_MAX * (int)sizeof(float);
-    if (mode == GV_MINE_EMIT) return p_norm == 1 ? tm_launch<1, false>(p, grid, lds, lds_max, st) : tm_launch<2, false>(p, grid, lds, lds_max, st);
-    return p_norm == 1 ? tm_launch<1, true>(p, grid, lds, lds_max, st) : tm_launch<2, true>(p, grid, lds, lds_max, st);
+    if (mode == GV_MINE_EMIT)
+        return p_norm == 1 ? mine_launch<k_transe_mine<1, false>>(p, grid, TM_THREADS, lds, lds_max, c)
+                           : mine_launch<k_transe_mine<2, false>>(p, grid, TM_THREADS, lds, lds_max, c);
+    return p_norm == 1 ? mine_launch<k_transe_mine<1, true>>(p, grid, TM_THREADS, lds, lds_max, c)
+                       : mine_launch<k_transe_mine<2, true>>(p, grid, TM_THREADS, lds, lds_max, c);
 }
 
 extern "C" int gv_transe_mine_typed(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int64_t* set_ptr,
@@ -354,21 +344,18 @@ extern "C" int gv_transe_mine_typed(const float* en, const float* rn, int n, int
                                     const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
                                     uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                                     uint64_t* counter, uint64_t* hist, void* stream) {
-    GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
-               "gv_transe_mine_typed: dim=%d (1..%d) p_norm=%d (1 or 2)", dim, GV_TRANSE_MAX_DIM, p_norm);
-    GV_REQUIRE(n <= 0 || (en && rn), GV_ERR_NULL, "gv_transe_mine_typed: NULL table");
-    hipStream_t st = (hipStream_t)stream;
+    const MineCall c{"gv_transe_mine_typed", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
+                     prefix_bits, prefix, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
     TeMineTypedParams tp{};
-    TeMineParams& p = tp.p;
-    const int rc = mine_typed_prepare("gv_transe_mine_typed", n, num_rels, set_ptr, set_ids, units, n_units, filt_lo, filt_hi, filt_ent,
-                                      n_filt_ent, exclude_self, mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, counter, hist,
-                                      st, &p.sel, &tp.ty);
+    int rc = tm_params(c.who, en, rn, n, dim, p_norm, TMT_KC, &tp.p);
+    if (rc == GV_OK) rc = mine_typed_prepare(c, set_ptr, set_ids, units, n_units, &tp.p.sel, &tp.ty);
     if (rc != GV_OK || n == 0 || n_units == 0) return rc;
-    p.en = en; p.rn = rn; p.dim = dim;
-    p.kc = std::min(dim, TMT_KC);
-    p.n_chunks = (dim + p.kc - 1) / p.kc;
-    const int lds = ((1 + TM_GROUPS) * TM_LD + 1) * p.kc * (int)sizeof(float);
-    const unsigned nu = (unsigned)n_units;
-    if (mode == GV_MINE_EMIT) return p_norm == 1 ? tmt_launch<1, false>(tp, nu, lds, st) : tmt_launch<2, false>(tp, nu, lds, st);
-    return p_norm == 1 ? tmt_launch<1, true>(tp, nu, lds, st) : tmt_launch<2, true>(tp, nu, lds, st);
+    const int lds = ((1 + TM_GROUPS) * TM_LD + 1) * tp.p.kc * (int)sizeof(float);
+    const int lds_max = ((1 + TM_GROUPS) * TM_LD + 1) * TMT_KC * (int)sizeof(float);
+    const dim3 grid((unsigned)n_units);
+    if (mode == GV_MINE_EMIT)
+        return p_norm == 1 ? mine_launch<k_transe_mine_typed<1, false>>(tp, grid, TM_THREADS, lds, lds_max, c)
+                           : mine_launch<k_transe_mine_typed<2, false>>(tp, grid, TM_THREADS, lds, lds_max, c);
+    return p_norm == 1 ? mine_launch<k_transe_mine_typed<1, true>>(tp, grid, TM_THREADS, lds, lds_max, c)
+                       : mine_launch<k_transe_mine_typed<2, true>>(tp, grid, TM_THREADS, lds, lds_max, c);
 }

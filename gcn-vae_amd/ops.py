@@ -1027,29 +1027,59 @@ def mine_scores(emb, w, *, threshold=None, k=None, bias=None, filt_lo=None, filt
     histogram passes over the ordered key's bits (12 + 10 + 10), then emits once."""
     if (k is None) == (threshold is None):
         raise ValueError('give exactly one of k and threshold')
+    return _mine_scores('gv_mine_scores', emb, w, None, threshold, k, bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results)
+
+
+def _mine_lists(members, multiple, filt, n, num_rels, dev, workspace_bytes):
+    """What a sweep's entry point takes besides its tables and the selection, as ``(lists, workspace, held)`` in the C order:
+    ``lists`` = ``[set_ptr, set_ids, units, n_units,] filt_lo, filt_hi, filt_ent, n_filt_ent`` (the bracketed four for a typed
+    sweep: the checked ``members`` = (set_ptr, set_ids, span) moved to ``dev`` and their unit plan; ``filt`` = (lo, hi, ent)),
+    ``workspace`` = ``workspace, workspace_bytes`` for a whole-graph sweep's re-bucketed filter (sized by ``workspace_bytes``),
+    () for a typed one.  Both hold raw addresses: ``held`` is the tensors behind them, which the caller keeps until its last
+    launch.  None: the typed plan is empty."""
+    if members is None:
+        lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(*filt, n, num_rels, dev, workspace_bytes)
+        held, sets, after = (ws,), (), (ptr(ws), ws_bytes)
+    else:
+        set_ptr, set_ids = members[0].to(dev), members[1].to(dev)
+        units = mine_typed_plan(set_ptr, num_rels, members[2], multiple=multiple)
+        if units.shape[0] == 0:
+            return None
+        lo32, hi32, ent32, n_ent = _mine_typed_filter_args(*filt, n, num_rels, dev)
+        held, sets, after = (set_ptr, set_ids, units), (ptr(set_ptr), ptr(set_ids), ptr(units), units.shape[0]), ()
+    return sets + (ptr(lo32), ptr(hi32), ptr(ent32), n_ent), after, held + (lo32, hi32, ent32)
+
+
+def _mine_scores(entry, emb, w, members, threshold, k, bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
+    """``mine_scores`` (``members`` None) and ``mine_scores_typed`` (``members`` = (set_ptr, set_ids, span)): one set of checks, one
+    launch; the typed sweep adds its member lists and unit list and reads the filter as given, the whole-graph one re-buckets it
+    into a workspace."""
     _mine_tables(emb, 'emb', w, 'w')
     n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
     if num_rels < 1 or h < 1:
         raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
     k, threshold, max_results = _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=(k, threshold, max_results))
+    if members is not None:
+        members = _mine_typed_members(members[0], members[1], n, num_rels) + (members[2],)
     emb, ld_e = _row_major(emb, 'emb')
     w, ld_w = _row_major(w, 'w')
     dev, nothing = _mine_device(emb, 'emb', w, 'w')
     if nothing is not None:
         return nothing
-    lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
-                                                               lib.load().gv_mine_scores_workspace_bytes)
+    lists = _mine_lists(members, 1, (filt_lo, filt_hi, filt_ent), n, num_rels, dev, lib.load().gv_mine_scores_workspace_bytes)
+    if lists is None:
+        return _mine_empty(dev)
+    lists, workspace, _held = lists      # _held: the tensors behind the addresses, alive until this frame returns
     if bias is not None:
         bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
         bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
 
     def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
-        lib.call('gv_mine_scores', ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-                 1 if exclude_self else 0, mode, key_min, prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words),
-                 ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+        lib.call(entry, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), *lists, 1 if exclude_self else 0, mode, key_min, prefix_bits,
+                 prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), *workspace, n, num_rels, h, lib.stream())
 
     return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
-                       'gv_mine_scores')
+                       entry)
 
 
 MINE_TYPED_SPAN = 8            # object tiles a unit of the typed sweeps takes at most against one staged subject tile (DESIGN.md 4d-2)
@@ -1131,33 +1161,8 @@ def mine_scores_typed(emb, w, set_ptr, set_ids, *, threshold=None, k=None, bias=
     transposed order: a workgroup takes a relation, a 64-member tile of its subject list and ``span`` tiles of its object list
     (``mine_typed_plan``; the result does not depend on ``span``), rows gathered through the ids.  An empty plan returns the
     empty result without a launch."""
-    _mine_tables(emb, 'emb', w, 'w')
-    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
-    if num_rels < 1 or h < 1:
-        raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
-    k, threshold, max_results = _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=(k, threshold, max_results))
-    set_ptr, set_ids = _mine_typed_members(set_ptr, set_ids, n, num_rels)
-    emb, ld_e = _row_major(emb, 'emb')
-    w, ld_w = _row_major(w, 'w')
-    dev, nothing = _mine_device(emb, 'emb', w, 'w')
-    if nothing is not None:
-        return nothing
-    set_ptr, set_ids = set_ptr.to(dev), set_ids.to(dev)
-    units = mine_typed_plan(set_ptr, num_rels, span)
-    if units.shape[0] == 0:
-        return _mine_empty(dev)
-    lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
-    if bias is not None:
-        bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
-        bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
-
-    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
-        lib.call('gv_mine_scores_typed', ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(set_ptr), ptr(set_ids), ptr(units),
-                 units.shape[0], ptr(lo32), ptr(hi32), ptr(ent32), n_ent, 1 if exclude_self else 0, mode, key_min,
-                 prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), n, num_rels, h, lib.stream())
-
-    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
-                       'gv_mine_scores_typed')
+    return _mine_scores('gv_mine_scores_typed', emb, w, (set_ptr, set_ids, span), threshold, k, bias, filt_lo, filt_hi, filt_ent,
+                        exclude_self, max_results)
 
 
 def pick_split_k(m_out, n_out, k):
@@ -3512,7 +3517,18 @@ def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi
     ``threshold=t``: every candidate with d <= t (a negative t: none); ``k=K``: the K nearest.  Order: distance ascending, then
     (s, r, o).  Returns ``(triplets int64 (n, 3), distances float32 (n,), info)``; ``info['count']``, ``info['passes']`` and
     ``MineOverflow`` as in ``mine_scores``, with "at or below the distance" for "at or above the logit"."""
+    return _transe_mine('gv_transe_mine', en, rn, p_norm, None, k, threshold, filt_lo, filt_hi, filt_ent, exclude_self, max_results)
+
+
+def _transe_mine(entry, en, rn, p_norm, members, k, threshold, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
+    """``transe_mine`` (``members`` None) and ``transe_mine_typed`` (``members`` = (set_ptr, set_ids, span)), as ``_mine_scores`` is
+    both DistMult miners; the member lists are checked before the tables are made contiguous."""
     k, threshold, max_results = _mine_args(k, threshold, max_results)
+    if members is not None:
+        for name, t in (('en', en), ('rn', rn)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2:
+                raise TypeError(f'{name}: expected a 2-D tensor')
+        members = _mine_typed_members(members[0], members[1], en.shape[0], rn.shape[0]) + (members[2],)
     en, rn = _mine_tables(en, 'en', rn, 'rn', prepare=lambda t, name: _table(t.contiguous(), name))
     p_norm = _p_norm(p_norm)
     n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
@@ -3522,17 +3538,18 @@ def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi
     dev, nothing = _mine_device(en, 'en', rn, 'rn')
     if nothing is not None:
         return nothing
-    lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
-                                                               lib.load().gv_transe_mine_workspace_bytes)
+    lists = _mine_lists(members, 4, (filt_lo, filt_hi, filt_ent), n, num_rels, dev, lib.load().gv_transe_mine_workspace_bytes)
+    if lists is None:
+        return _mine_empty(dev)
+    lists, workspace, _held = lists      # _held: the tensors behind the addresses, alive until this frame returns
 
     def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
-        lib.call('gv_transe_mine', ptr(en), ptr(rn), n, num_rels, dim, p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-                 1 if exclude_self else 0, mode, key_min, prefix_bits, prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words),
-                 ptr(ws), ws_bytes, lib.stream())
+        lib.call(entry, ptr(en), ptr(rn), n, num_rels, dim, p_norm, *lists, 1 if exclude_self else 0, mode, key_min, prefix_bits,
+                 prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), *workspace, lib.stream())
 
     # d <= t is key(-d) >= key(-t); t = -0 keys as +0, the key of every zero distance
     return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(-threshold), max_results, True,
-                       'gv_transe_mine')
+                       entry)
 
 
 def transe_mine_typed(en, rn, p_norm, set_ptr, set_ids, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None,
@@ -3543,30 +3560,5 @@ def transe_mine_typed(en, rn, p_norm, set_ptr, set_ids, *, k=None, threshold=Non
     gv_transe_mine_typed: a workgroup takes a relation, a 64-member tile of its subject list and ``span`` tiles of its object list,
     four at a time (``mine_typed_plan``; the result does not depend on ``span``).  An empty plan returns the empty result without
     a launch."""
-    k, threshold, max_results = _mine_args(k, threshold, max_results)
-    for name, t in (('en', en), ('rn', rn)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise TypeError(f'{name}: expected a 2-D tensor')
-    set_ptr, set_ids = _mine_typed_members(set_ptr, set_ids, en.shape[0], rn.shape[0])
-    en, rn = _mine_tables(en, 'en', rn, 'rn', prepare=lambda t, name: _table(t.contiguous(), name))
-    p_norm = _p_norm(p_norm)
-    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
-    if num_rels < 1:
-        raise ValueError('need at least one relation')
-    _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
-    dev, nothing = _mine_device(en, 'en', rn, 'rn')
-    if nothing is not None:
-        return nothing
-    set_ptr, set_ids = set_ptr.to(dev), set_ids.to(dev)
-    units = mine_typed_plan(set_ptr, num_rels, span, multiple=4)
-    if units.shape[0] == 0:
-        return _mine_empty(dev)
-    lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
-
-    def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
-        lib.call('gv_transe_mine_typed', ptr(en), ptr(rn), n, num_rels, dim, p_norm, ptr(set_ptr), ptr(set_ids), ptr(units),
-                 units.shape[0], ptr(lo32), ptr(hi32), ptr(ent32), n_ent, 1 if exclude_self else 0, mode, key_min, prefix_bits,
-                 prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), lib.stream())
-
-    return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(-threshold), max_results, True,
-                       'gv_transe_mine_typed')
+    return _transe_mine('gv_transe_mine_typed', en, rn, p_norm, (set_ptr, set_ids, span), k, threshold, filt_lo, filt_hi, filt_ent,
+                        exclude_self, max_results)
