@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "k_mc.h"
 #include "k_topk.h"
 
 namespace gv {
@@ -364,10 +365,7 @@ struct McSamples {
     float inv_s;                       // 1.0f / n_samples (exact for a power of two: the same sample twice gives the sample's value)
 };
 
-// sig(x) = 1 / (1 + exp(-x)), as v_rcp_f32(1.0f + __expf(-x)): two quarter-rate instructions, no IEEE divide sequence.  The ONE form
-// every pass and entry point of the MC scorers uses, so a target's probability is bit-identical wherever it is recomputed.
-// +inf -> 1, -inf -> 0 (exp overflows to +inf, whose reciprocal is +0), NaN -> NaN: a NaN in any sample makes pbar NaN.
-__device__ __forceinline__ float mc_sig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// (sig is mc_sig of k_mc.h, the one form the typed MC miner of k_mine.hip uses too.)
 
 // The caller has issued sample 0's first k-chunk of tile (m0, n0) into ra / rb.  Under each sample's epilogue (16 exp + 16 rcp per
 // lane) the next sample's first k-chunk is already in flight; under the last one, sample 0's of the tile at n0_next (< 0: none).

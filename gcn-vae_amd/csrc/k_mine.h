@@ -1,5 +1,5 @@
-// What the four mining sweeps share (gv_mine_scores / gv_mine_scores_typed in k_mine.hip, gv_transe_mine / gv_transe_mine_typed in
-// k_transe_mine.hip): everything about SELECTING candidates.  A workgroup of a whole-graph sweep is 256 threads (or groups of 256)
+// What the mining sweeps share (gv_mine_scores / gv_mine_scores_typed and its Monte-Carlo form gv_mine_scores_typed_mc in k_mine.hip,
+// gv_transe_mine / gv_transe_mine_typed in k_transe_mine.hip): everything about SELECTING candidates.  A workgroup of a whole-graph sweep is 256 threads (or groups of 256)
 // on one 64 x 64 (subject tile, object tile) pair of the table, walking the relations; a candidate is (local row rl, local column
 // cl) of it under relation r, with a value the kernel computed its own way.
 //

@@ -22,8 +22,10 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <utility>
 
 #include "common.h"
+#include "k_mc.h"
 #include "k_mine.h"
 
 namespace gv {
@@ -471,6 +473,187 @@ __global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
     }
 }
 
+// ---- the type-constrained sweep on the Monte-Carlo posterior predictive (gv_mine_scores_typed_mc) -----------------------------------
+// k_mine_typed with S entity tables: sample s reads e + s * e_stride (shared ld_e), the one w, bias[s].  The value selected is
+//   pbar = (sum over s ascending of mc_sig(logit_s + bias[s])) * (1.0f / S)
+// with logit_s from mine_mfma_chunk unchanged, so pbar is gv_topk_scores_mc's out_prob for the query (s, r) at entity o, bit for bit.
+// Loop order: the SAMPLE loop is outside the unit's object tiles.  A unit's span is walked in groups of MINE_MC_SPAN tiles; per
+// (group, sample) the subject tile is staged once and per (object tile, sample) the object tile once -- the single-sample
+// kernel's staging count per sample -- while one 16-register pbar accumulator per tile of the group stays live across the samples
+// (one wave per SIMD: the register file is otherwise nearly empty).  On the resident path the next object tile of a sample is
+// gathered into registers (mine_fetch_rows) before this tile's MFMA chain and written to LDS behind it.  The accumulators are indexed by a compile-time tile number (mine_each)
+// only, a group's missing tiles are predicated off.  Filter, ids and mine_epilogue run per tile after the last sample; w[r] does
+// not depend on the sample and stays staged per unit on the resident path.  The chunked path stages both tiles per (tile, sample,
+// chunk): it works, it is not fast.
+constexpr int MINE_MC_SPAN = 8;        // object tiles whose pbar a workgroup holds in registers at once (= ops.MINE_TYPED_SPAN)
+constexpr int MINE_FETCH_MAX = (64 * (MINE_KC_MAX / 4) + 255) / 256;      // 16-byte pieces of a staged tile per thread, at most
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>), in order: the tile loops of k_mine_typed_mc written out, so that
+// the per-tile accumulators are indexed by constants whatever the loop unroller's size limit makes of a body this large (as a
+// `#pragma unroll` loop the accumulators went to scratch once the register gather was added).
+template <class F, int... J>
+__device__ __forceinline__ void mine_each(F&& f, std::integer_sequence<int, J...>) {
+    (f(std::integral_constant<int, J>{}), ...);
+}
+
+// mine_stage_rows in two halves -- a thread's pieces of a tile's rows into registers, and from there into the LDS layout -- so that
+// the NEXT object tile's gather is in flight under the MFMA chain of this one (all loads issued together, no LDS touched).
+template <class RowOf>
+__device__ __forceinline__ void mine_fetch_rows(float4 (&v)[MINE_FETCH_MAX], const float* e, int ld, bool vec, RowOf row_of, int n, int h,
+                                                int kc) {
+    const int q4 = kc >> 2;
+#pragma unroll
+    for (int i = 0; i < MINE_FETCH_MAX; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < 64 * q4) {
+            const int rl = idx / q4, k = 4 * (idx - rl * q4);
+            const int row = row_of(rl);
+            if ((unsigned)row < (unsigned)n) {
+                const float* src = e + (size_t)row * ld + k;
+                if (vec && k + 3 < h) {
+                    v[i] = *reinterpret_cast<const float4*>(src);
+                } else {
+                    v[i].x = k < h ? src[0] : 0.f;
+                    v[i].y = k + 1 < h ? src[1] : 0.f;
+                    v[i].z = k + 2 < h ? src[2] : 0.f;
+                    v[i].w = k + 3 < h ? src[3] : 0.f;
+                }
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void mine_commit_rows(float* dst, const float4 (&v)[MINE_FETCH_MAX], int kc) {
+    const int q4 = kc >> 2, pitch = kc + 4, half = kc >> 1;
+#pragma unroll
+    for (int i = 0; i < MINE_FETCH_MAX; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        if (idx < 64 * q4) {
+            const int rl = idx / q4, q = idx - rl * q4;
+            float* d = dst + rl * pitch + 2 * q;
+            *reinterpret_cast<float2*>(d) = make_float2(v[i].x, v[i].z);
+            *reinterpret_cast<float2*>(d + half) = make_float2(v[i].y, v[i].w);
+        }
+    }
+}
+
+struct MineTypedMcParams {
+    MineParams p;                      // p.bias: one value per sample, or NULL
+    MineTyped ty;
+    long long e_stride;                // elements between consecutive samples' tables
+    int n_samples;
+    float inv_s;                       // 1.0f / n_samples
+};
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_mine_typed_mc(const MineTypedMcParams tp) {
+    extern __shared__ __attribute__((aligned(16))) float mine_smem[];
+    __shared__ unsigned long long fmask[64];             // the tile pair's listed objects per subject row
+    __shared__ int sid_s[64], oid_s[MINE_MC_SPAN][64];   // the subject tile's and the group's object tiles' entity ids, -1 past the lists
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const MineParams& p = tp.p;
+    const MineTyped& ty = tp.ty;
+    const MineSelect& sel = p.sel;
+    const int kc = p.kc, pitch = kc + 4, half = kc >> 1;
+    float* As = mine_smem;
+    float* Bs = As + 64 * pitch;
+    float* Ws = Bs + 64 * pitch;                         // [kc + 4]
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const auto s_row = [&](int rl) { return sid_s[rl]; };
+    const int4 unit = ty.units[blockIdx.x];
+    const int r = unit.x;
+    if (r < 0 || r >= sel.num_rels) return;              // uniform: not a unit
+    const bool resident = p.n_chunks == 1;
+
+    mine_typed_ids(ty, sel.num_rels + r, unit.y, sel.n, t, sid_s);
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
+    if (resident && t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, 4 * t));
+    const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
+
+    for (int og = unit.z; og < unit.w; og += MINE_MC_SPAN) {
+        __syncthreads();                                 // the last group's reads of oid_s are over (and sid_s is written)
+        for (int j = wid; j < MINE_MC_SPAN; j += 4)      // a tile past the span's end: all -1
+            mine_typed_ids(ty, r, og + j < unit.w ? og + j : -1, sel.n, lane, oid_s[j]);
+
+        mine_f32x16 pbar[MINE_MC_SPAN];
+#pragma unroll
+        for (int j = 0; j < MINE_MC_SPAN; ++j)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) pbar[j][i] = 0.f;
+
+        for (int s = 0; s < tp.n_samples; ++s) {
+            const float* es = p.e + (long long)s * tp.e_stride;
+            const float bv = p.bias ? p.bias[s] : 0.f;
+            mine_each([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if (og + j < unit.w) {                   // uniform
+                    const auto o_row = [&](int cl) { return oid_s[j][cl]; };
+                    mine_f32x16 acc;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                    if (resident) {
+                        // tile 0 of a sample is staged directly with the subject tile; every later tile was gathered into registers
+                        // under the chain of the tile before it and committed behind that chain's barrier
+                        if (j == 0) {
+                            __syncthreads();             // the last chain's reads of As / Bs are over, oid_s is written
+                            mine_stage_rows(As, es, p.ld_e, p.vec_e, s_row, sel.n, 0, p.h, kc);
+                            mine_stage_rows(Bs, es, p.ld_e, p.vec_e, o_row, sel.n, 0, p.h, kc);
+                        }
+                        __syncthreads();
+                        const bool more = j + 1 < MINE_MC_SPAN && og + j + 1 < unit.w;      // uniform
+                        float4 next[MINE_FETCH_MAX];
+                        if (more)
+                            mine_fetch_rows(next, es, p.ld_e, p.vec_e, [&](int cl) { return oid_s[j + 1 < MINE_MC_SPAN ? j + 1 : j][cl]; },
+                                            sel.n, p.h, kc);
+                        acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + w_off, mine_groups(kc, p.h, 0));
+                        if (more) {
+                            __syncthreads();             // every wave's reads of Bs are over
+                            mine_commit_rows(Bs, next, kc);
+                        }
+                    } else {
+                        for (int c = 0; c < p.n_chunks; ++c) {
+                            const int k0 = c * kc;
+                            __syncthreads();             // the last chain's reads of As / Bs / Ws are over, oid_s is written
+                            mine_stage_rows(As, es, p.ld_e, p.vec_e, s_row, sel.n, k0, p.h, kc);
+                            if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
+                            mine_stage_rows(Bs, es, p.ld_e, p.vec_e, o_row, sel.n, k0, p.h, kc);
+                            __syncthreads();
+                            acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + w_off, mine_groups(kc, p.h, k0));
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) pbar[j][i] += mc_sig(acc[i] + bv);
+                }
+            }, std::make_integer_sequence<int, MINE_MC_SPAN>{});
+        }
+
+        mine_each([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (og + j < unit.w) {                       // uniform
+                __syncthreads();                         // the last tile's reads of fmask are over
+                if (t < 64) fmask[t] = 0ull;
+                __syncthreads();
+                mine_typed_filter(ty, sel.num_rels, r, sid_s, oid_s[j], t, fmask);
+                __syncthreads();                         // fmask is complete
+#pragma unroll
+                for (int i = 0; i < 16; ++i) pbar[j][i] *= tp.inv_s;
+                // the key is pbar's (never -0: a sum of sigmoids), the record's fourth word its bits
+                const int o = oid_s[j][wn + l31];
+                mine_epilogue<HIST>(pbar[j], 0.f, wm, wn, lane, sel.exclude_self != 0, [&](int rl, int) { return make_int2(sid_s[rl], o); },
+                                    r, true, fmask, hist_s, sel);
+            }
+        }, std::make_integer_sequence<int, MINE_MC_SPAN>{});
+    }
+    if (HIST) {
+        __syncthreads();
+        mine_hist_flush(hist_s, sel, t);
+    }
+}
+
 }  // namespace gv
 
 using namespace gv;
@@ -514,4 +697,31 @@ extern "C" int gv_mine_scores_typed(const float* e, int ld_e, const float* w, in
     const dim3 grid((unsigned)n_units);
     return mode == GV_MINE_EMIT ? mine_launch<k_mine_typed<false>>(tp, grid, 256, lds, lds_max, c)
                                 : mine_launch<k_mine_typed<true>>(tp, grid, 256, lds, lds_max, c);
+}
+
+extern "C" int gv_mine_scores_typed_mc(const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w, int ld_w,
+                                       const float* bias, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units,
+                                       int64_t n_units, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                                       int n_filt_ent, int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix,
+                                       int bin_bits, int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, int n,
+                                       int num_rels, int h, void* stream) {
+    const MineCall c{"gv_mine_scores_typed_mc", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, key_min,
+                     prefix_bits, prefix, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
+    MineTypedMcParams tp{};
+    int rc = mine_params(c.who, e, ld_e, w, ld_w, bias, n, num_rels, h, n_filt_ent, &tp.p);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE(n_samples >= 1, GV_ERR_SHAPE, "%s: n_samples=%d", c.who, n_samples);
+    GV_REQUIRE(n_samples == 1 || e_stride >= (int64_t)(n > 0 ? n - 1 : 0) * ld_e + h, GV_ERR_SHAPE,
+               "%s: sample stride shorter than the rows it spans (e_stride=%lld)", c.who, (long long)e_stride);
+    tp.e_stride = n_samples > 1 ? e_stride : 0;
+    tp.n_samples = n_samples;
+    tp.inv_s = 1.0f / (float)n_samples;
+    tp.p.vec_e = tp.p.vec_e && tp.e_stride % 4 == 0;     // the 16-byte loads need every sample's base aligned
+    rc = mine_typed_prepare(c, set_ptr, set_ids, units, n_units, &tp.p.sel, &tp.ty);
+    if (rc != GV_OK || n == 0 || n_units == 0) return rc;
+    const int lds = (2 * 64 + 1) * (tp.p.kc + 4) * (int)sizeof(float);
+    const int lds_max = (2 * 64 + 1) * (MINE_KC_MAX + 4) * (int)sizeof(float);
+    const dim3 grid((unsigned)n_units);
+    return mode == GV_MINE_EMIT ? mine_launch<k_mine_typed_mc<false>>(tp, grid, 256, lds, lds_max, c)
+                                : mine_launch<k_mine_typed_mc<true>>(tp, grid, 256, lds, lds_max, c);
 }

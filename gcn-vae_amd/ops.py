@@ -1050,32 +1050,60 @@ def _mine_lists(members, multiple, filt, n, num_rels, dev, workspace_bytes):
     return sets + (ptr(lo32), ptr(hi32), ptr(ent32), n_ent), after, held + (lo32, hi32, ent32)
 
 
-def _mine_scores(entry, emb, w, members, threshold, k, bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
-    """``mine_scores`` (``members`` None) and ``mine_scores_typed`` (``members`` = (set_ptr, set_ids, span)): one set of checks, one
-    launch; the typed sweep adds its member lists and unit list and reads the filter as given, the whole-graph one re-buckets it
-    into a workspace."""
-    _mine_tables(emb, 'emb', w, 'w')
-    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
+def _mine_sample_stack(z, name):
+    """The (S, N, h) sample stack of a Monte-Carlo mining call as the kernel reads it: float32 on the GPU with unit inner stride,
+    rows ``ld >= h`` apart and samples a stride apart that spans a whole table (kept as given when it already is, else made
+    contiguous).  Returns (tensor, ld, sample stride in elements -- 0 for one sample)."""
+    if not z.is_cuda:
+        raise RuntimeError(f'{name}: the gfx950 path needs a CUDA/ROCm tensor; there is no CPU fallback')
+    if z.dtype != torch.float32:
+        raise TypeError(f'{name}: expected float32, got {z.dtype}')
+    s, n, h = z.shape
+    ld = z.stride(1) if n > 1 else h
+    if (h > 1 and z.stride(2) != 1) or ld < h or (s > 1 and z.stride(0) < (n - 1) * ld + h):
+        z, ld = z.contiguous(), h
+    return z, ld, (z.stride(0) if s > 1 else 0)
+
+
+def _mine_scores(entry, emb, w, members, threshold, k, bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results, mc=False):
+    """``mine_scores`` (``members`` None), ``mine_scores_typed`` (``members`` = (set_ptr, set_ids, span)) and, with ``mc``,
+    ``mine_scores_typed_mc`` (``emb`` the (S, N, h) sample stack, ``bias`` one value per sample, the threshold a probability):
+    one set of checks, one launch; the typed sweeps add their member lists and unit list and read the filter as given, the
+    whole-graph one re-buckets it into a workspace."""
+    n_samples = None
+    if mc:
+        if not isinstance(emb, torch.Tensor) or emb.dim() != 3 or emb.shape[0] < 1:
+            raise TypeError('z: expected a 3-D (samples, entities, width) tensor with at least one sample')
+        n_samples = emb.shape[0]
+    _mine_tables(emb[0] if mc else emb, 'z[s]' if mc else 'emb', w, 'w')
+    n, num_rels, h = emb.shape[-2], w.shape[0], emb.shape[-1]
     if num_rels < 1 or h < 1:
         raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
     k, threshold, max_results = _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent, args=(k, threshold, max_results))
     if members is not None:
         members = _mine_typed_members(members[0], members[1], n, num_rels) + (members[2],)
-    emb, ld_e = _row_major(emb, 'emb')
+    if n_samples is None:
+        emb, ld_e = _row_major(emb, 'emb')
+        tables = (ld_e,)
+    else:
+        emb, ld_e, e_stride = _mine_sample_stack(emb, 'z')
+        tables = (ld_e, e_stride, n_samples)
     w, ld_w = _row_major(w, 'w')
-    dev, nothing = _mine_device(emb, 'emb', w, 'w')
+    dev, nothing = _mine_device(emb if n_samples is None else emb[0], 'emb', w, 'w')
     if nothing is not None:
         return nothing
     lists = _mine_lists(members, 1, (filt_lo, filt_hi, filt_ent), n, num_rels, dev, lib.load().gv_mine_scores_workspace_bytes)
     if lists is None:
         return _mine_empty(dev)
     lists, workspace, _held = lists      # _held: the tensors behind the addresses, alive until this frame returns
-    if bias is not None:
+    if bias is not None and n_samples is not None:
+        bias = _mc_bias_arg(torch.as_tensor(bias).detach(), n_samples, dev)
+    elif bias is not None:
         bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
         bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
 
     def launch(mode, key_min, prefix_bits, prefix, bin_bits, out, capacity, words):
-        lib.call(entry, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), *lists, 1 if exclude_self else 0, mode, key_min, prefix_bits,
+        lib.call(entry, ptr(emb), *tables, ptr(w), ld_w, ptr(bias), *lists, 1 if exclude_self else 0, mode, key_min, prefix_bits,
                  prefix, bin_bits, ptr(out), capacity, ptr(words), ptr(words), *workspace, n, num_rels, h, lib.stream())
 
     return _mine_drive(launch, dev, n, num_rels, k, threshold, None if k is not None else mine_key(threshold), max_results, False,
@@ -1163,6 +1191,22 @@ def mine_scores_typed(emb, w, set_ptr, set_ids, *, threshold=None, k=None, bias=
     empty result without a launch."""
     return _mine_scores('gv_mine_scores_typed', emb, w, (set_ptr, set_ids, span), threshold, k, bias, filt_lo, filt_hi, filt_ent,
                         exclude_self, max_results)
+
+
+def mine_scores_typed_mc(z, w, set_ptr, set_ids, *, threshold=None, k=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                         exclude_self=True, max_results=MINE_MAX_RESULTS, span=None):
+    """``mine_scores_typed`` on the Monte-Carlo posterior predictive of S samples: ``z`` (S, N, h) holds one entity table per
+    sample (unit inner stride; row and sample strides are kept), ``w`` the one relation table, ``bias`` (S,) optionally each
+    draw's flow_log_prob.  The value selected is ``pbar[s, r, o] = mean_s sigmoid((z_s[s] * w[r]) . z_s[o] + bias[s])``, summed in
+    ascending sample order and never stored: bit for bit the ``prob_mean`` ``topk_scores_mc`` returns for the query
+    ``mul(z_s[s], w[r])`` at entity o (gv_mine_scores_typed_mc: the sample loop runs outside a unit's object tiles, one pbar
+    accumulator per tile in registers).  ``threshold`` is a PROBABILITY compared with pbar; order: pbar descending, then
+    (s, r, o) ascending; a NaN in any sample makes the triplet no candidate.  Member lists, filter, ``exclude_self``, ``span``,
+    ``info`` and ``MineOverflow`` are ``mine_scores_typed``'.  pbar saturates: candidates whose every sample rounds to 1.0f
+    tie, and when the tie at the K-th value holds more than ``max_results`` candidates the call raises ``MineOverflow`` with the
+    count, as the rule says for any tie.  Returns ``(triplets int64 (n, 3), probs float32 (n,), info)``."""
+    return _mine_scores('gv_mine_scores_typed_mc', z, w, (set_ptr, set_ids, span), threshold, k, bias, filt_lo, filt_hi, filt_ent,
+                        exclude_self, max_results, mc=True)
 
 
 def pick_split_k(m_out, n_out, k):

@@ -813,6 +813,82 @@ def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=
                         max_results=max_results, members=members)
 
 
+# ---- type-correct completions on the Monte-Carlo posterior predictive ---------------------------------------------------------
+MC_MINE_STACK_BYTES = 64 << 20      # bytes of the (S, chunk, h) query stack behind the spread of the mined triplets
+
+
+def mine_from_probs(pbar, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                    max_results=ops.MINE_MAX_RESULTS, cand_subj=None, cand_obj=None):
+    """The mining rule of ``ops.mine_scores_typed_mc`` on a materialised tensor of posterior-predictive probabilities
+    ``pbar[r, s, o]`` (R, N, N), in plain torch: ``mine_from_scores``' rule with the probability as the value -- candidates less
+    the listed, less s == o, less NaN; pbar descending, then (s, r, o) ascending; ``threshold`` a probability; ``count`` and
+    ``MineOverflow`` at the exact K-th value, which for a saturated pbar (1.0f) is a real tie."""
+    return _mine_from_values(pbar, False, k=k, threshold=threshold, filt_lo=filt_lo, filt_hi=filt_hi, filt_ent=filt_ent,
+                             exclude_self=exclude_self, max_results=max_results, cand_subj=cand_subj, cand_obj=cand_obj)
+
+
+def _mine_mc_setup(z, w, k, threshold, max_results, filter_index, flow_log_probs, type_constraint):
+    _mine_args(k, threshold, max_results)
+    if type_constraint is None:
+        raise ValueError('mine_triplets_mc needs a type_constraint: only the sweep over the relations\' member lists has a '
+                         'Monte-Carlo form.  The unconstrained sweep keeps its two tiles of ONE table in LDS across all '
+                         'relations; looping it over samples would restage both per (relation, sample), so it was not built')
+    z, wd, flp = _mc_args(z, w, flow_log_probs)
+    n, num_rels = z.shape[1], wd.shape[0]
+    return z, wd, flp, n, num_rels, _mine_filter(filter_index, n, num_rels, z.device), _mine_members(type_constraint, n, num_rels,
+                                                                                                    z.device)
+
+
+def mine_triplets_mc(z, w, *, k=None, threshold=None, filter_index=None, flow_log_probs=None, exclude_self=True,
+                     max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
+    """Type-correct knowledge-graph completion on the posterior predictive of the samples ``z`` (S, N, h) of
+    ``KGVAE.posterior_samples`` (``flow_log_probs``: its second result): among the type-correct triplets (``type_constraint``,
+    required) the ``k`` of highest ``pbar = mean_s sigmoid(logit_s)`` or every one with pbar >= ``threshold`` (a probability),
+    the known ones of ``filter_index`` left out.  One fused sweep per pass (ops.mine_scores_typed_mc); for a fixed seed of the
+    samples the result is reproducible.  Returns ``(triplets int64 (n, 3), probs float32 (n,), std float32 (n,), info)`` in the
+    order of ``mine_from_probs``; ``std`` is the population standard deviation over the samples of each returned triplet's
+    probability (ops.pair_prob_std_mc, fed in chunks whose query stack stays under ``MC_MINE_STACK_BYTES``).  Raises
+    ``MineOverflow`` rather than truncating -- also when a saturated tie at pbar == 1.0f exceeds ``max_results``."""
+    z, wd, flp, n, num_rels, (lo, hi, ent), (set_ptr, set_ids) = _mine_mc_setup(z, w, k, threshold, max_results, filter_index,
+                                                                                flow_log_probs, type_constraint)
+    trip, probs, info = ops.mine_scores_typed_mc(z, wd, set_ptr, set_ids, threshold=threshold, k=k, bias=flp, filt_lo=lo, filt_hi=hi,
+                                                 filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
+    rows = max(1, MC_MINE_STACK_BYTES // (z.shape[0] * z.shape[2] * 4))
+    std = [ops.pair_prob_std_mc(_mc_queries(z, wd, trip[i:i + rows, 0], trip[i:i + rows, 1]), z, trip[i:i + rows, 2:3], flp)[:, 0]
+           for i in range(0, trip.shape[0], rows)]
+    return trip, probs, (torch.cat(std) if std else torch.zeros(0, dtype=torch.float32, device=z.device)), info
+
+
+def mine_triplets_mc_unfused(z, w, *, k=None, threshold=None, filter_index=None, flow_log_probs=None, exclude_self=True,
+                             max_results=ops.MINE_MAX_RESULTS, type_constraint=None):
+    """``mine_triplets_mc`` from materialised probabilities, one relation at a time: per sample the relation's subject and object
+    members are ``index_select``-ed, ``ops.mul`` + ``ops.gemm`` give the block of logits, torch the sigmoid and the running mean;
+    then torch selection with a running K-th value (``_mine_unfused``).  The spread comes from the selected triplets' per-sample
+    probabilities in torch.  The in-repo cross-check and the bench's comparator, never a fallback."""
+    z, wd, flp, n, num_rels, filt, members = _mine_mc_setup(z, w, k, threshold, max_results, filter_index, flow_log_probs,
+                                                            type_constraint)
+    wd = wd.contiguous()
+    n_samples = z.shape[0]
+
+    def pbar_of(r, subj, obj):
+        total = None
+        for s in range(n_samples):
+            a, b = z[s].index_select(0, subj), z[s].index_select(0, obj)
+            logit = ops.gemm(ops.mul(a, wd[r].expand_as(a).contiguous()), b, trans_b=True, precision='f32')
+            p = torch.sigmoid(logit if flp is None else logit + flp[s])
+            total = p if total is None else total + p
+        return total * (1.0 / n_samples)
+
+    trip, probs, info = _mine_unfused(pbar_of, False, n, num_rels, z.device, k=k, threshold=threshold, filt=filt,
+                                      exclude_self=exclude_self, max_results=max_results, members=members)
+    std, rows = [], max(1, MC_MINE_STACK_BYTES // (n_samples * z.shape[2] * 4))
+    for i in range(0, trip.shape[0], rows):
+        s_, r_, o_ = trip[i:i + rows].unbind(1)
+        logit = (z[:, s_] * wd[r_] * z[:, o_]).sum(-1)
+        std.append(torch.sigmoid(logit if flp is None else logit + flp.view(-1, 1)).std(dim=0, unbiased=False))
+    return trip, probs, (torch.cat(std) if std else torch.zeros(0, dtype=torch.float32, device=z.device)), info
+
+
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,
              verbose=True):
     with torch.no_grad():

@@ -181,6 +181,25 @@ def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow
     return _write_triplets(path, trip, logits)
 
 
+def write_mc_completions(path, z, w, filter_index, type_constraint, k=None, threshold=None, flow_log_probs=None):
+    """``write_completions`` under the posterior predictive of the samples ``z`` (S, N, h), among the type-correct triplets
+    (ranking.mine_triplets_mc), as TSV: ``s  r  o  rank  prob_mean  prob_std`` -- the first four columns are those of
+    ``write_completions`` (the two files join on s, r, o; the rank here counts from 1), the last two the mean and the population
+    standard deviation over the samples of the triplet's probability.  ``k`` the most probable and / or those whose mean probability reaches ``threshold``, best first.  Returns the
+    number of lines written."""
+    with torch.no_grad():
+        sel = dict(k=k) if k else dict(threshold=float(threshold))
+        trip, mean, std, _ = ranking.mine_triplets_mc(z, w, filter_index=filter_index, flow_log_probs=flow_log_probs,
+                                                      type_constraint=type_constraint, **sel)
+        if k and threshold is not None:
+            keep = mean >= float(threshold)
+            trip, mean, std = trip[keep], mean[keep], std[keep]
+    with open(path, 'w') as f:
+        f.writelines(f"{s}\t{r}\t{o}\t{i}\t{x:.9g}\t{y:.9g}\n"
+                     for i, ((s, r, o), x, y) in enumerate(zip(trip.tolist(), mean.tolist(), std.tolist()), 1))
+    return trip.shape[0]
+
+
 def _logit_of(p):
     p = float(p)
     if not 0.0 <= p <= 1.0:
@@ -225,6 +244,13 @@ def check_args(args):
         if getattr(args, 'type_constrain', False):
             raise ValueError('--mc-samples with --type-constrain is not supported: the posterior-predictive ranker has no '
                              'type-constrained form yet')
+    if getattr(args, 'mc_complete', False):
+        if not getattr(args, 'mc_samples', 0) > 0:
+            raise ValueError('--mc-complete mines on the posterior predictive: it needs --mc-samples S > 0')
+        if not getattr(args, 'complete_typed', False):
+            raise ValueError('--mc-complete needs --complete-typed: only the sweep over the type-correct triplets has a '
+                             'Monte-Carlo form')
+        # (--complete-typed without --complete-topk / --complete-threshold was refused above: a selection is given)
 
 
 def main(args):
@@ -323,6 +349,15 @@ def main(args):
                 n_lines = write_mc_predictions(args.mc_predict_out, z, model.w_relation, test_t, args.predict_topk, known, flps)
                 print(f"wrote {n_lines} posterior-predictive predictions (top {args.predict_topk}, both directions, known "
                       f"triplets filtered, mean and spread over {args.mc_samples} samples) to {args.mc_predict_out}")
+            if getattr(args, 'mc_complete', False):
+                known = filters if filters is not None else \
+                    ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+                typed = types if types is not None else \
+                    ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+                n_lines = write_mc_completions(args.mc_complete_out, z, model.w_relation, known, typed, k=args.complete_topk or None,
+                                               threshold=args.complete_threshold, flow_log_probs=flps)
+                print(f"wrote {n_lines} new type-correct triplets (known triplets filtered, mean and spread over "
+                      f"{args.mc_samples} samples) to {args.mc_complete_out}")
         return mrr
 
     print("start training...")
@@ -492,6 +527,14 @@ def build_parser():
     p.add_argument("--complete-typed", action="store_true",
                    help="with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as "
                         "subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval")
+    p.add_argument("--mc-complete", action="store_true",
+                   help="with --mc-samples, --complete-typed and --complete-topk / --complete-threshold: also mine the type-correct "
+                        "completions on the posterior predictive (the mean over the samples of the triplet probability; the "
+                        "threshold is compared with that mean) and write them to --mc-complete-out; reproducible for a fixed "
+                        "--mc-seed")
+    p.add_argument("--mc-complete-out", type=str, default="mc_completions.tsv",
+                   help="TSV of --mc-complete: subject, relation, object, rank (the columns of --complete-out), then the mean and "
+                        "the standard deviation over the samples of the triplet's probability")
     p.add_argument("--sample-graph", type=int, default=0,
                    help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
                         "confident triplets among them to --sample-out; 0 = off")

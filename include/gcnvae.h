@@ -637,6 +637,23 @@ int gv_mine_scores_typed(const float* e, int ld_e, const float* w, int ld_w, con
                          uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                          uint64_t* counter, uint64_t* hist, int n, int num_rels, int h, void* stream);
 
+/* Type-constrained mining on the Monte-Carlo posterior predictive (csrc/k_mine.hip): gv_mine_scores_typed with n_samples entity
+ * tables.  Sample s reads e + s * e_stride (elements; the leading dimension ld_e is shared), the one w, and bias[s] when bias is
+ * given (n_samples floats).  The value that is selected is
+ *   pbar[s_, r, o] = (sum over s ascending of sig(logit_s[s_, r, o] + bias[s])) * (1.0f / n_samples)
+ * with logit_s the arithmetic of gv_mine_scores on table s and sig the sigmoid of the gv_*_mc scorers, so pbar is bit for bit
+ * gv_topk_scores_mc's out_prob of the query e_s[s_] * w[r] at entity o.  The key is ordered_u32(pbar), a record is (s, r, o, bits of
+ * pbar); a NaN in any sample makes the triplet no candidate.  pbar is bounded and saturates: candidates whose every sample rounds
+ * to 1.0f share one key.  Member lists, units, filter, exclude_self, modes, counter, histograms and every check are those of
+ * gv_mine_scores_typed; in addition n_samples >= 1 and, with n_samples > 1, e_stride >= (n - 1) * ld_e + h, both refused before
+ * any launch.  Integer atomics only; the result does not depend on the spans or the launch geometry. */
+int gv_mine_scores_typed_mc(const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w, int ld_w, const float* bias,
+                            const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                            const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                            int exclude_self, int mode, uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits,
+                            int32_t* out, int64_t capacity, uint64_t* counter, uint64_t* hist, int n, int num_rels, int h,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Entity classification (kgvae/entity_classify.py; csrc/k_ec.hip).  Deterministic: fixed summation orders, no float atomics.
  *
