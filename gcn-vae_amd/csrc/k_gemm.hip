@@ -477,10 +477,10 @@ struct RankFiltParams {
     const int* filt_ent;
     int n_ent;               // length of filt_ent: every range is clamped into it
     int* count_filt;
-    TopkCand cs;             // CAND only (gv_rank_scores_constrained)
+    TopkCand cs;             // CAND only (gv_rank_scores_constrained, gv_rank_scores_mc_constrained)
     int* count_raw_c;
     int* count_filt_c;       // NULL (as count_filt, filt_lo) when no filter is given
-    McSamples mc;            // MC only (gv_rank_scores_mc): rp.bias then holds one value per sample
+    McSamples mc;            // MC only (gv_rank_scores_mc, gv_rank_scores_mc_constrained): rp.bias then holds one value per sample
 };
 
 // CAND: the type-constrained protocol on top.  The tile's 64 columns are two words of the row's set (topk_cand_pair), loaded once
@@ -491,6 +491,8 @@ struct RankFiltParams {
 // rp.tgt comes from k_rank_target_mc, which runs the same sample loop.  Filter, ballots and counts are the ones above; the filter
 // is optional (raw count only without one).  Its 16 extra accumulators are held inside the single-sample rankers' 8 waves / SIMD
 // (waves_per_eu: 64 registers; the single-sample instantiations keep the default and their code).
+// CAND and MC together (gv_rank_scores_mc_constrained): all four counts vote on the one pbar; the set words are in LDS before the
+// sample loop starts, so the constraint holds no register across it and the budget is the MC ranker's.
 template <bool CAND, bool MC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 8 : 1))) void k_rank_scores_filtered(const RankFiltParams fp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK;
@@ -612,12 +614,14 @@ struct TopkParams {
     int span_tiles;               // 64-column tiles per span (blockIdx.y = span)
     int n_spans;
     unsigned long long* part;     // [m][n_spans][topk] keys, each span's list sorted descending
-    TopkCand cs;                  // CAND only (gv_topk_scores_constrained)
-    McSamples mc;                 // MC only (gv_topk_scores_mc): bias then holds one value per sample
+    TopkCand cs;                  // CAND only (gv_topk_scores_constrained, gv_topk_scores_mc_constrained)
+    McSamples mc;                 // MC only (gv_topk_scores_mc, gv_topk_scores_mc_constrained): bias then holds one value per sample
 };
 
 // MC: the key's value is pbar from mc_pbar_tile (the very values gv_rank_scores_mc votes on) instead of the logit; held to the
-// 5 waves / SIMD of the single-sample scorer (which its LDS allows at most anyway).
+// 5 waves / SIMD of the single-sample scorer (which its LDS allows at most anyway).  With CAND on top (gv_topk_scores_mc_constrained)
+// the tile's set word is requested ahead of the sample loop; cand_row is the one value the 96-register ceiling sends to scratch,
+// reloaded once per column tile outside the sample loop.
 template <int NK, bool CAND, bool MC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 5 : 1))) void k_topk_span(const TopkParams tp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1;
@@ -1350,6 +1354,29 @@ static GemmParams mc_gemm_params(const float* q, int ld_q, const float* e, int l
     return p;
 }
 
+// the launches of gv_rank_scores_mc and, with cs.cand, of its type-constrained form: pass 0 is shared (the target's pbar does not
+// depend on the set), pass 1 votes all its counts on the one pbar of mc_pbar_tile
+static int rank_mc_launch(const char* name, RankFiltParams& fp, const float* q, int ld_q, const float* e, int ld_e, const int* target,
+                          const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                          const TopkCand& cs, float* tgt, int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m,
+                          int v, int h, void* stream) {
+    RankParams& rp = fp.rp;
+    rp.g = mc_gemm_params(q, ld_q, e, ld_e, fp.mc, m, v, h);
+    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
+    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent;
+    fp.count_filt = filt_lo ? count_filt : nullptr;          // without a filter the filtered counts are not written
+    fp.cs = cs;
+    fp.count_raw_c = count_raw_c; fp.count_filt_c = filt_lo ? count_filt_c : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    for (int* c : {count_raw, fp.count_filt, fp.count_raw_c, fp.count_filt_c})
+        if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status(name);
+    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
+    hipLaunchKernelGGL(k_rank_target_mc, grid, block, 0, st, fp);                        // tgt[row] = the target's pbar
+    if (cs.cand) hipLaunchKernelGGL((k_rank_scores_filtered<true, true>), grid, block, 0, st, fp);
+    else hipLaunchKernelGGL((k_rank_scores_filtered<false, true>), grid, block, 0, st, fp);
+    return launch_status(name);
+}
+
 extern "C" int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
                                  const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
                                  int n_filt_ent, float* tgt, int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
@@ -1363,18 +1390,62 @@ extern "C" int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, con
     if (m == 0) return GV_OK;
     GV_REQUIRE(q && e && target && tgt && count_raw, GV_ERR_NULL, "gv_rank_scores_mc: NULL pointer");
     GV_REQUIRE(!filt_lo || count_filt, GV_ERR_NULL, "gv_rank_scores_mc: a filter needs count_filt");
-    RankParams& rp = fp.rp;
-    rp.g = mc_gemm_params(q, ld_q, e, ld_e, fp.mc, m, v, h);
-    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
-    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent;
-    fp.count_filt = filt_lo ? count_filt : nullptr;          // without a filter the filtered count is not written
+    return rank_mc_launch("gv_rank_scores_mc", fp, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{},
+                          tgt, count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
+}
+
+extern "C" int gv_rank_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                                             int n_samples, const int* target, const float* bias, const int* filt_lo,
+                                             const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
+                                             int ld_cand, int n_sets, const int32_t* cand_set, float* tgt, int* count_raw,
+                                             int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_mc_constrained: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    RankFiltParams fp{};
+    const int rc = mc_samples_args("gv_rank_scores_mc_constrained", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &fp.mc);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_rank_scores_mc_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_rank_scores_mc_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_rank_scores_mc_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && target && tgt && count_raw && count_raw_c, GV_ERR_NULL, "gv_rank_scores_mc_constrained: NULL pointer");
+    GV_REQUIRE(!filt_lo || (count_filt && count_filt_c), GV_ERR_NULL,
+               "gv_rank_scores_mc_constrained: a filter needs both filtered counts");
+    return rank_mc_launch("gv_rank_scores_mc_constrained", fp, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                          TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, count_filt, count_raw_c, count_filt_c, m, v, h,
+                          stream);
+}
+
+// the launches of gv_topk_scores_mc, and with cs.cand of its type-constrained form
+template <bool CAND>
+static int topk_mc_launch(const char* name, TopkParams& tp, const float* q, int ld_q, const float* e, int ld_e, const float* bias,
+                          const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
+                          int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream) {
+    tp.g = mc_gemm_params(q, ld_q, e, ld_e, tp.mc, m, v, h);
+    tp.bias = bias;
+    tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
+    tp.topk = k;
+    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
+    tp.part = (unsigned long long*)workspace;
+    tp.cs = cs;
     hipStream_t st = (hipStream_t)stream;
-    for (int* c : {count_raw, fp.count_filt})
-        if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status("gv_rank_scores_mc");
-    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
-    hipLaunchKernelGGL(k_rank_target_mc, grid, block, 0, st, fp);                        // tgt[row] = the target's pbar
-    hipLaunchKernelGGL((k_rank_scores_filtered<false, true>), grid, block, 0, st, fp);
-    return launch_status("gv_rank_scores_mc");
+    const int lds = 64 * k * (int)sizeof(unsigned long long);
+    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
+    const TopkLogitOut out{out_ids, out_prob};
+    if (k <= 64) {
+        hipLaunchKernelGGL((k_topk_span<1, CAND, true>), grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_topk_span<2, CAND, true>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
+                               name))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_topk_span<2, CAND, true>), grid, block, lds, st, tp);
+        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
+    }
+    return launch_status(name);
 }
 
 extern "C" int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
@@ -1390,28 +1461,30 @@ extern "C" int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, con
                "gv_topk_scores_mc: filt_lo / filt_hi / filt_ent must be all given or all NULL");
     if (m == 0) return GV_OK;
     GV_REQUIRE(q && e && out_ids && out_prob && workspace, GV_ERR_NULL, "gv_topk_scores_mc: NULL pointer");
-    tp.g = mc_gemm_params(q, ld_q, e, ld_e, tp.mc, m, v, h);
-    tp.bias = bias;
-    tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
-    tp.topk = k;
-    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
-    tp.part = (unsigned long long*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const int lds = 64 * k * (int)sizeof(unsigned long long);
-    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
-    const TopkLogitOut out{out_ids, out_prob};
-    if (k <= 64) {
-        hipLaunchKernelGGL((k_topk_span<1, false, true>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_topk_span<2, false, true>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
-                               "gv_topk_scores_mc"))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_topk_span<2, false, true>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    }
-    return launch_status("gv_topk_scores_mc");
+    return topk_mc_launch<false>("gv_topk_scores_mc", tp, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
+                                 out_ids, out_prob, workspace, m, v, h, stream);
+}
+
+extern "C" int gv_topk_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                                             int n_samples, const float* bias, const int* filt_lo, const int* filt_hi,
+                                             const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand, int n_sets,
+                                             const int32_t* cand_set, int k, int* out_ids, float* out_prob, void* workspace, int m,
+                                             int v, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: m=%d v=%d h=%d n_filt_ent=%d",
+               m, v, h, n_filt_ent);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
+    TopkParams tp{};
+    const int rc = mc_samples_args("gv_topk_scores_mc_constrained", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &tp.mc);
+    if (rc != GV_OK) return rc;
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: n_sets=%d ld_cand=%d (>= %d)",
+               n_sets, ld_cand, (v + 31) / 32);
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_topk_scores_mc_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_topk_scores_mc_constrained: NULL cand / cand_set");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(q && e && out_ids && out_prob && workspace, GV_ERR_NULL, "gv_topk_scores_mc_constrained: NULL pointer");
+    return topk_mc_launch<true>("gv_topk_scores_mc_constrained", tp, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                                TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_prob, workspace, m, v, h, stream);
 }
 
 extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,

@@ -808,6 +808,48 @@ def topk_scores_mc(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_e
     return ids.long(), prob
 
 
+def rank_scores_mc_constrained(q, entities, target, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """The type-constrained protocol on ``rank_scores_mc``'s pbar (gv_rank_scores_mc_constrained): returns ``(raw, filtered,
+    raw_constrained, filtered_constrained, tgt)``.  ``raw``, ``filtered`` and ``tgt`` equal ``rank_scores_mc``'s bit for bit; the
+    constrained ranks count, on the same pbar, only the members of row ``cand_set[i]`` of the bitmask ``cand`` (see
+    ``_cand_args``): the target is never counted, member or not, and an empty or out-of-range set gives rank 0.  Without a filter
+    the two filtered ranks are None."""
+    q, entities, s, m, v, h = _mc_operands(q, entities)
+    tgt32 = _target_args(target, m, v, q.device)
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    bias = _mc_bias_arg(bias, s, q.device)
+    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
+    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
+    filt = lo32 is not None
+    if m == 0:                                  # (an empty stack has no sample stride to give)
+        return _ranks(counts, 0, filt) + (tgt[:0],)
+    lib.call('gv_rank_scores_mc_constrained', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(tgt32), ptr(bias), ptr(lo32),
+             ptr(hi32), ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), ptr(tgt), ptr(counts[0]),
+             ptr(counts[1]) if filt else None, ptr(counts[2]), ptr(counts[3]) if filt else None, m, v, h, lib.stream())
+    return _ranks(counts, m, filt) + (tgt[:m],)
+
+
+def topk_scores_mc_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
+    """``topk_scores_mc`` among the members of a per-query candidate set only (gv_topk_scores_mc_constrained): the candidates of
+    row i are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``), less the
+    filter-listed ids; the values are ``rank_scores_mc_constrained``'s pbar, bit for bit.  A set with fewer than k members pads
+    (id -1, value -inf), an out-of-range set id gives an all-padding row.  Returns ``(ids int64 (m, k), prob_mean float32 (m, k))``."""
+    q, entities, s, m, v, h = _mc_operands(q, entities)
+    k = _topk_arg(k)
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
+    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
+    prob = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if m == 0:
+        return ids.long(), prob
+    bias = _mc_bias_arg(bias, s, q.device)
+    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
+    lib.call('gv_topk_scores_mc_constrained', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(prob), ptr(ws), m, v, h, lib.stream())
+    return ids.long(), prob
+
+
 def pair_prob_std_mc(q, entities, ids, bias=None):
     """Population standard deviation over the samples of ``sigmoid(q[s, i] . entities[s, ids[i, c]] + bias[s])`` for every
     selected pair (gv_pair_prob_std_mc; two-pass in fp32, the dot a plain fmaf chain): float32 (m, k).  Padding ids (-1) give

@@ -561,22 +561,114 @@ def calc_mc_mrr_unfused(z, w, test_triplets, filter_index=None, flow_log_probs=N
     return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, False)
 
 
-def _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, fused):
+def _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, fused):
+    ent = filter_index.entities(direction, z.device) if filter_index is not None else None
+    words = type_constraint.words.to(z.device) if fused else None
+    out = [[], [], [], []]
+    step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
+    for lo in range(0, n, step):
+        sl = slice(lo, min(n, lo + step))
+        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+        sets = type_constraint.set_ids(r[sl], direction)
+        if fused:
+            ranks = ops.rank_scores_mc_constrained(_mc_queries(z, w, a[sl], r[sl]), z, b[sl], words, sets, flp, f_lo, f_hi, ent)[:4]
+        else:
+            pbar = _mc_pbar_unfused(z, w, a[sl], r[sl], flp)
+            listed = None if ent is None else _listed_mask(f_lo, f_hi, ent, pbar.shape[0], pbar.shape[1], pbar.device)
+            ranks = rank_from_scores_constrained(pbar, b[sl].to(pbar.device), type_constraint.mask(sets, pbar.device), listed)
+        for acc, x in zip(out, ranks):
+            acc.append(x)
+    if not out[0]:
+        out = [[torch.zeros(0, dtype=torch.float32, device=z.device)] for _ in out]
+        if filter_index is None:
+            out[1] = out[3] = [None]
+    return tuple(None if x[0] is None else torch.cat(x) for x in out)
+
+
+def perturb_and_get_rank_mc_constrained(z, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
+                                        all_batches=True, flow_log_probs=None):
+    """(raw, filtered, raw_constrained, filtered_constrained) posterior-predictive ranks of ``b`` for the queries (a, r) under the
+    samples ``z`` (S, N, h): ``perturb_and_get_rank_mc`` plus the ranks among the ``direction`` type set of each query's relation
+    only, all four on the same pbar (ops.rank_scores_mc_constrained, one fused launch pair per ``MC_STACK_ROWS`` queries).
+    ``filter_index`` may be None: the two filtered ranks are then None."""
+    z, w, flp = _mc_args(z, w, flow_log_probs)
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    return _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, True)
+
+
+def perturb_and_get_rank_mc_constrained_unfused(z, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
+                                                all_batches=True, flow_log_probs=None):
+    """``perturb_and_get_rank_mc_constrained`` from materialised probabilities (``_mc_pbar_unfused``, then
+    ``rank_from_scores_constrained`` applied to pbar -- its predicates are the MC rule already): the in-repo cross-check and the
+    bench's baseline."""
+    z, w, flp = _mc_args(z, w, flow_log_probs)
+    n = min(test_size, batch_size) if all_batches is False else test_size
+    return _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, False)
+
+
+def _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches, verbose,
+                             fused):
+    with torch.no_grad():
+        z, w, flp = _mc_args(z, w, flow_log_probs)
+        test_triplets = test_triplets.to(z.device)
+        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
+        n = test_triplets.shape[0]
+        n = min(n, eval_bz) if all_batches is False else n
+        by_s = _perturb_and_get_rank_mc_constrained(z, w, o, r, s, n, filter_index, type_constraint, 's', flp, fused)
+        by_o = _perturb_and_get_rank_mc_constrained(z, w, s, r, o, n, filter_index, type_constraint, 'o', flp, fused)
+        out = {'n_samples': int(z.shape[0])}
+        for kind, rs, ro in zip(CONSTRAINED_KINDS, by_s, by_o):
+            if rs is None:                                    # no filter_index: the two filtered kinds are not reported
+                continue
+            ranks = torch.cat([rs, ro]) + 1
+            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
+            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
+        if verbose:
+            for kind in (k for k in CONSTRAINED_KINDS if 'mrr_' + k in out):
+                print("MC MRR ({}, {} samples): {:.6f}".format(kind, out['n_samples'], out['mrr_' + kind]))
+                for hit in hits:
+                    print("MC Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
+    return out
+
+
+def calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs=None, hits=[1, 3, 10], eval_bz=100,
+                            all_batches=True, verbose=True):
+    """The four-way report of the type-constrained protocol on the posterior predictive, over both directions: ``n_samples`` and
+    ``mrr_<kind>`` / ``hits_<kind>: {k: v}`` for the kinds of ``CONSTRAINED_KINDS`` (the filtered ones only with a
+    ``FilterIndex``).  Every kind ranks on ``calc_mc_mrr``'s pbar: the raw and filtered figures equal its values."""
+    return _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches,
+                                    verbose, True)
+
+
+def calc_mc_constrained_mrr_unfused(z, w, test_triplets, filter_index, type_constraint, flow_log_probs=None, hits=[1, 3, 10],
+                                    eval_bz=100, all_batches=True, verbose=True):
+    """``calc_mc_constrained_mrr`` on the materialised route (``perturb_and_get_rank_mc_constrained_unfused``)."""
+    return _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches,
+                                    verbose, False)
+
+
+def _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, fused, type_constraint=None):
     if direction not in ('o', 's'):
         raise ValueError("direction is 'o' (queries (a, r, ?)) or 's' (queries (?, r, a))")
     z, w, flp = _mc_args(z, w, flow_log_probs)
     ent = filter_index.entities(direction, z.device) if filter_index is not None else None
+    words = type_constraint.words.to(z.device) if fused and type_constraint is not None else None
     ids, mean, std = [], [], []
     step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
     for lo in range(0, a.shape[0], step):
         sl = slice(lo, min(a.shape[0], lo + step))
         f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+        sets = type_constraint.set_ids(r[sl], direction) if type_constraint is not None else None
         if fused:
             q = _mc_queries(z, w, a[sl], r[sl])
-            i, p = ops.topk_scores_mc(q, z, k, flp, f_lo, f_hi, ent)
+            if sets is None:
+                i, p = ops.topk_scores_mc(q, z, k, flp, f_lo, f_hi, ent)
+            else:
+                i, p = ops.topk_scores_mc_constrained(q, z, k, words, sets, flp, f_lo, f_hi, ent)
             sd = ops.pair_prob_std_mc(q, z, i, flp)
         else:
-            i, p = topk_from_scores(_mc_pbar_unfused(z, w, a[sl], r[sl], flp), k, f_lo, f_hi, ent)
+            pbar = _mc_pbar_unfused(z, w, a[sl], r[sl], flp)
+            i, p = topk_from_scores(pbar, k, f_lo, f_hi, ent, cand=None if sets is None else type_constraint.mask(sets, pbar.device))
             pick = i.clamp(min=0)
             ps = []
             for s in range(z.shape[0]):        # the selected pairs' probability in every sample, from the same GEMMs
@@ -593,20 +685,21 @@ def _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, fus
     return torch.cat(ids), torch.cat(mean), torch.cat(std)
 
 
-def predict_topk_mc(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None):
+def predict_topk_mc(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None, type_constraint=None):
     """Posterior-predictive link prediction from the samples ``z`` (S, N, h): the ``k`` entities of highest
     ``pbar = mean_s sigmoid(logit_s)`` for every query (``direction`` and ``filter_index`` as ``predict_topk`` takes them), and
     how sure the model is of each: returns ``(ids int64 (n, k), prob_mean float32 (n, k), prob_std float32 (n, k))``,
     ``prob_std`` the population standard deviation of the pair's probability over the samples.  Rows with fewer than k
     candidates are padded with id -1, mean -inf, std 0.  One fused launch pair plus the spread kernel per ``MC_STACK_ROWS``
-    queries (ops.topk_scores_mc, ops.pair_prob_std_mc)."""
-    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, True)
+    queries (ops.topk_scores_mc, ops.pair_prob_std_mc).  With a ``TypeConstraint`` only the members of the relation's
+    ``direction`` type set are proposed (ops.topk_scores_mc_constrained); the spread is computed as before, on the selected ids."""
+    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, True, type_constraint)
 
 
-def predict_topk_mc_unfused(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None):
+def predict_topk_mc_unfused(z, w, a, r, k, direction='o', filter_index=None, flow_log_probs=None, type_constraint=None):
     """``predict_topk_mc`` from materialised probabilities (S GEMMs per chunk + ``topk_from_scores``): the in-repo cross-check
     and the bench's baseline."""
-    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, False)
+    return _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, False, type_constraint)
 
 
 MineOverflow = ops.MineOverflow

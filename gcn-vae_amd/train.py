@@ -144,17 +144,19 @@ def write_predictions(path, embed, w, triplets, k, filter_index, flow_log_prob=N
     return n
 
 
-def write_mc_predictions(path, z, w, triplets, k, filter_index, flow_log_probs=None):
+def write_mc_predictions(path, z, w, triplets, k, filter_index, flow_log_probs=None, type_constraint=None):
     """``write_predictions`` under the posterior predictive of the samples ``z`` (S, N, h) (ranking.predict_topk_mc), as TSV:
     ``direction  query_entity  relation  position  predicted_entity  prob_mean  prob_std`` -- the mean and the population standard
     deviation over the samples of the pair's probability; a query with fewer than k candidates ends in id -1, mean -inf, std 0.
+    With a ``type_constraint`` (ranking.TypeConstraint) only members of the relation's type set on that side are written.
     Returns the number of lines written."""
     n = 0
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
     with torch.no_grad(), open(path, 'w') as f:
         for d, a in (('o', triplets[:, 0]), ('s', triplets[:, 2])):
             r = triplets[:, 1]
             ids, mean, std = ranking.predict_topk_mc(z, w, a, r, k, direction=d, filter_index=filter_index,
-                                                     flow_log_probs=flow_log_probs)
+                                                     flow_log_probs=flow_log_probs, **constrained)
             a, r, ids, mean, std = a.tolist(), r.tolist(), ids.tolist(), mean.tolist(), std.tolist()
             for i in range(len(a)):
                 head = f"{d}\t{a[i]}\t{r[i]}\t"
@@ -242,8 +244,14 @@ def check_args(args):
             raise ValueError('--mc-samples needs --model-class KGVAE: the RGCN encoder is deterministic, it has no posterior '
                              'to sample')
         if getattr(args, 'type_constrain', False):
-            raise ValueError('--mc-samples with --type-constrain is not supported: the posterior-predictive ranker has no '
-                             'type-constrained form yet')
+            raise ValueError('--mc-samples with --type-constrain is not supported: --type-constrain reports on the single draw; '
+                             'the type-constrained posterior-predictive report is --mc-type-constrain')
+    if getattr(args, 'mc_type_constrain', False):
+        if not getattr(args, 'mc_samples', 0) > 0:
+            raise ValueError('--mc-type-constrain constrains the posterior-predictive report: it needs --mc-samples S > 0')
+        if not getattr(args, 'filtered_eval', False):
+            raise ValueError('--mc-type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, '
+                             'filtered_constrained')
     if getattr(args, 'mc_complete', False):
         if not getattr(args, 'mc_samples', 0) > 0:
             raise ValueError('--mc-complete mines on the posterior predictive: it needs --mc-samples S > 0')
@@ -341,14 +349,23 @@ def main(args):
             z, flps = model.encoder.posterior_samples(test_graph, test_node_id, test_rel, test_norm, args.mc_samples,
                                                       seed=args.mc_seed)
             print(f"\nMonte-Carlo posterior predictive: {args.mc_samples} samples, seed {args.mc_seed}")
-            ranking.calc_mc_mrr(z, model.w_relation, test_t, filters, flps, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
-                                all_batches=True)
+            # --mc-type-constrain: the sets of --type-constrain (train + valid + test), applied to the posterior predictive
+            mc_types = ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev) \
+                if getattr(args, 'mc_type_constrain', False) else None
+            if mc_types is not None:
+                ranking.calc_mc_constrained_mrr(z, model.w_relation, test_t, filters, mc_types, flps, hits=[1, 3, 10],
+                                                eval_bz=args.eval_batch_size, all_batches=True)
+            else:
+                ranking.calc_mc_mrr(z, model.w_relation, test_t, filters, flps, hits=[1, 3, 10], eval_bz=args.eval_batch_size,
+                                    all_batches=True)
             if getattr(args, 'predict_topk', 0) > 0:
                 known = filters if filters is not None else \
                     ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
-                n_lines = write_mc_predictions(args.mc_predict_out, z, model.w_relation, test_t, args.predict_topk, known, flps)
+                n_lines = write_mc_predictions(args.mc_predict_out, z, model.w_relation, test_t, args.predict_topk, known, flps,
+                                               mc_types)
+                typed_note = ", type-correct entities only" if mc_types is not None else ""
                 print(f"wrote {n_lines} posterior-predictive predictions (top {args.predict_topk}, both directions, known "
-                      f"triplets filtered, mean and spread over {args.mc_samples} samples) to {args.mc_predict_out}")
+                      f"triplets filtered{typed_note}, mean and spread over {args.mc_samples} samples) to {args.mc_predict_out}")
             if getattr(args, 'mc_complete', False):
                 known = filters if filters is not None else \
                     ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -527,6 +544,11 @@ def build_parser():
     p.add_argument("--complete-typed", action="store_true",
                    help="with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as "
                         "subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval")
+    p.add_argument("--mc-type-constrain", action="store_true",
+                   help="with --mc-samples and --filtered-eval: the type-constrained protocol on the posterior predictive -- the MC "
+                        "report becomes raw / filtered / raw_constrained / filtered_constrained, and --mc-predict-out proposes "
+                        "only entities seen on that side of the relation in train + valid + test; reproducible for a fixed "
+                        "--mc-seed (--type-constrain itself stays a single-draw report)")
     p.add_argument("--mc-complete", action="store_true",
                    help="with --mc-samples, --complete-typed and --complete-topk / --complete-threshold: also mine the type-correct "
                         "completions on the posterior predictive (the mean over the samples of the triplet probability; the "

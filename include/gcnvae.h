@@ -595,6 +595,28 @@ int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e
 int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
                         const float* bias, const int* ids, int k, float* out_std, int m, int v, int h, void* stream);
 
+/* The type-constrained protocol on the posterior predictive: the two entries above with the per-query candidate sets of
+ * gv_rank_scores_constrained on top (cand [n_sets, ld_cand], ld_cand >= ceil(v / 32), n_sets >= 1, cand_set int32 [m]; bits at
+ * positions >= v are ignored, a set id outside [0, n_sets) is the empty set and is never dereferenced).  Sample geometry, one
+ * bias per sample, the all-or-none filter, ties, NaN, saturation and padding are the parents'; every value voted on or selected is
+ * the pbar of gv_rank_scores_mc, bit for bit.
+ *   gv_rank_scores_mc_constrained : tgt, count_raw and count_filt are gv_rank_scores_mc's, bit for bit (the target's pbar does not
+ *     depend on the set: the first launch is shared).  count_raw_c / count_filt_c count, of the same candidates j != t_i and on
+ *     the same pbar, only the members of set cand_set[i]; the target is never counted, member or not, and an empty set gives 0.
+ *     Without a filter the two filtered counts are not written (and may be NULL).  Counts int32 [m], zeroed here.
+ *   gv_topk_scores_mc_constrained : the candidates of row i are the members of set cand_set[i], less the listed ids when a filter
+ *     is given; a set with fewer than k such members pads with id -1, value -inf.  Workspace of
+ *     gv_topk_scores_workspace_bytes(m, v, k) bytes. */
+int gv_rank_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                  const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                                  int n_filt_ent, const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, float* tgt,
+                                  int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h,
+                                  void* stream);
+int gv_topk_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                  const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                                  const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, int k, int* out_ids,
+                                  float* out_prob, void* workspace, int m, int v, int h, void* stream);
+
 /* Whole-graph triplet mining (csrc/k_mine.hip): every triplet of a DistMult decoder scored and selected globally, for the
  * entity table e (n, h) and the relation rows w (num_rels, h), both fp32 row-major:
  *   logit[s, r, o] = (e[s] * w[r]) . e[o] (+ *bias)
