@@ -25,6 +25,8 @@ __global__ __launch_bounds__(256) void k_final_sum(const float* part, int n, flo
     if (threadIdx.x == 0) *out = accumulate ? *out + scale * tot : scale * tot;
 }
 
+constexpr int LOSS_COMBINE_XSQ_MAX = 65536;   // = GV_LOSS_COMBINE_WREL_MAX: 16 float4 loads per thread of the one 1 024-thread block
+
 // the four loss terms' final sums and their weighted combination in one block:
 //   scal = {s0*sum(p0), s1*sum(p1), s2*sum(p2), s3*sum(p3)},  loss = scal[0] + w1*scal[1] + w2*scal[2] + w3*scal[3]
 __global__ __launch_bounds__(256) void k_loss_combine(const float* p0, int n0, float s0, const float* p1, int n1, float s1,
@@ -45,6 +47,59 @@ __global__ __launch_bounds__(256) void k_loss_combine(const float* p0, int n0, f
         term[j] = ss[j] * block_sum_256(acc, sm);
     }
     if (threadIdx.x == 0) {
+        if (scal) { scal[0] = term[0]; scal[1] = term[1]; scal[2] = term[2]; scal[3] = term[3]; }
+        float v = term[0];
+        if (p1) v += w1 * term[1];
+        if (p2) v += w2 * term[2];
+        if (p3) v += w3 * term[3];
+        *loss = v;
+    }
+}
+
+// k_loss_combine that also sums xsq^2 (the relation table's half of the regulariser: term 1 += s_xsq * sum xsq^2) in its one
+// block.  The block is 1 024 threads so that the whole table is ONE round of loads: a thread issues its <= LOSS_COMBINE_XSQ_Q
+// float4 loads together and then multiplies (a loop of dependent round trips in a single block is what a launch costs).  The four
+// partial-sum terms are added by the first 256 threads exactly as k_loss_combine adds them (the other waves add zeros).
+constexpr int LOSS_COMBINE_XSQ_Q = LOSS_COMBINE_XSQ_MAX / 4 / 1024;
+__global__ __launch_bounds__(1024) void k_loss_combine_xsq(const float* p0, int n0, float s0, const float* p1, int n1, float s1,
+                                                           const float* p2, int n2, float s2, const float* p3, int n3, float s3,
+                                                           float w1, float w2, float w3, float* scal, float* loss,
+                                                           const float4* xsq, int n_xsq4, float s_xsq) {
+    __shared__ float sm[5][16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float4 x[LOSS_COMBINE_XSQ_Q];
+#pragma unroll
+    for (int q = 0; q < LOSS_COMBINE_XSQ_Q; ++q) {
+        const int i = threadIdx.x + 1024 * q;
+        x[q] = i < n_xsq4 ? xsq[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float* ps[4] = {p0, p1, p2, p3};
+    const int ns[4] = {n0, n1, n2, n3};
+    float acc[5];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        acc[j] = 0.f;
+        if (ps[j] && threadIdx.x < 256)
+            for (int i = threadIdx.x; i < ns[j]; i += 256) acc[j] += ps[j][i];
+    }
+    acc[4] = 0.f;
+#pragma unroll
+    for (int q = 0; q < LOSS_COMBINE_XSQ_Q; ++q)
+        acc[4] = fmaf(x[q].x, x[q].x, fmaf(x[q].y, x[q].y, fmaf(x[q].z, x[q].z, fmaf(x[q].w, x[q].w, acc[4]))));
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const float t = wave_sum(acc[j]);
+        if (lane == 0) sm[j][w] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float ss[4] = {s0, s1, s2, s3};
+        float term[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) term[j] = ss[j] * (sm[j][0] + sm[j][1] + sm[j][2] + sm[j][3]);      // (waves 4 .. 15 hold zeros)
+        float tx = 0.f;
+        for (int q = 0; q < 16; ++q) tx += sm[4][q];
+        term[1] += s_xsq * tx;
         if (scal) { scal[0] = term[0]; scal[1] = term[1]; scal[2] = term[2]; scal[3] = term[3]; }
         float v = term[0];
         if (p1) v += w1 * term[1];
@@ -186,13 +241,24 @@ __global__ __launch_bounds__(256) void k_kl_mix(const float* z_pre, int k, int h
 
 constexpr int KL_KMAX = 64;   // mixture components (lane j keeps component j's log-density)
 
+// sum z^2 of a KL forward block (the embedding regulariser's forward riding on the sweep that makes z): the lanes' shares are
+// summed per wave in the DPP order of wave_sum, then over the four waves in wave order, one partial per block -- the same fixed
+// wave -> block order as the KL partials, no atomics.  `wsum` is the block's 4-float scratch (reused: barrier first).
+__device__ __forceinline__ void kl_zsq_block(float zsq, float* wsum, float* zsq_part) {
+    zsq = wave_sum(zsq);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = zsq;
+    __syncthreads();
+    if (threadIdx.x == 0) zsq_part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // one wave per node; mixture table staged in LDS once per block; CPL = columns per lane (h <= 64*CPL)
 template <int CPL>
 __global__ __launch_bounds__(256) void k_kl_fwd(const float* z, const float* m, int ld_m, const float* v,
                                                 const float* mix, const float* flp, float* resp, float* part,
                                                 int64_t n, int h, int k, const int* rows_dev, const float* h2 = nullptr,
                                                 const float* eps = nullptr, float* z_out = nullptr, float* v_out = nullptr,
-                                                float* m_out = nullptr) {
+                                                float* m_out = nullptr, float* zsq_part = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float wsum[4];
     if (rows_dev) n = *rows_dev;               // rows beyond it are padding of a static-shape batch
@@ -217,6 +283,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd(const float* z, const float* m, 
     const float fl = flp ? *flp : 0.f;
     const float logk = logf((float)k);
     float my_terms = 0.f;                       // lane 0 of each wave: sum of its nodes' terms, in node order
+    float zsq = 0.f;                            // fused reparameterisation: this lane's share of sum z^2 (the regulariser's forward)
     for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (int64_t)gridDim.x * 4) {
         float zz[CPL];
         float a = 0.f;
@@ -230,6 +297,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd(const float* z, const float* m, 
                     mm = h2[r * 2 * h + c];
                     vv = softplus_t(h2[r * 2 * h + h + c]) + 1e-8f;
                     zz[i] = mm + eps[r * h + c] * sqrtf(vv);
+                    zsq = fmaf(zz[i], zz[i], zsq);
                     z_out[r * h + c] = zz[i];
                     v_out[r * h + c] = vv;
                     if (m_out) m_out[r * h + c] = mm;
@@ -266,6 +334,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd(const float* z, const float* m, 
     if (lane == 0) wsum[threadIdx.x >> 6] = my_terms;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (zsq_part) kl_zsq_block(zsq, wsum, zsq_part);
 }
 
 // The same pass with a lane owning FOUR CONSECUTIVE columns per group (h % 4 == 0, G = ceil(h / 256) groups): 16-B loads and
@@ -277,7 +346,7 @@ template <int G>
 __global__ __launch_bounds__(256) void k_kl_fwd_v4(const float* z, const float* m, int ld_m, const float* v,
                                                    const float* mix, const float* flp, float* resp, float* part,
                                                    int64_t n, int h, int k, const int* rows_dev, const float* h2,
-                                                   const float* eps, float* z_out, float* v_out, float* m_out) {
+                                                   const float* eps, float* z_out, float* v_out, float* m_out, float* zsq_part) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float wsum[4];
     __shared__ float lconst[KL_KMAX];
@@ -296,7 +365,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v4(const float* z, const float* 
     const int lane = threadIdx.x & 63;
     const float fl = flp ? *flp : 0.f;
     const float logk = logf((float)k);
-    float my_terms = 0.f;
+    float my_terms = 0.f, zsq = 0.f;
     bool on[G];
     int col[G];
 #pragma unroll
@@ -324,6 +393,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v4(const float* z, const float* 
                     vv[i] = softplus_t(raw[i]) + 1e-8f;
                     zz[g][i] = mm[i] + ee[i] * sqrtf(vv[i]);
                 }
+                zsq = fmaf(zz[g][0], zz[g][0], fmaf(zz[g][1], zz[g][1], fmaf(zz[g][2], zz[g][2], fmaf(zz[g][3], zz[g][3], zsq))));
                 *reinterpret_cast<float4*>(z_out + r * h + col[g]) = make_float4(zz[g][0], zz[g][1], zz[g][2], zz[g][3]);
                 *reinterpret_cast<float4*>(v_out + r * h + col[g]) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                 if (m_out) *reinterpret_cast<float4*>(m_out + r * h + col[g]) = m4;
@@ -368,6 +438,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v4(const float* z, const float* 
     if (lane == 0) wsum[threadIdx.x >> 6] = my_terms;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (zsq_part) kl_zsq_block(zsq, wsum, zsq_part);
 }
 
 // FOUR NODES PER WAVE (h <= 64 G, h % 4 == 0, k <= 16): a row of 16 lanes owns one node, lane l of the row the float4 columns
@@ -390,7 +461,7 @@ template <int G>
 __global__ __launch_bounds__(256) void k_kl_fwd_v5(const float* z, const float* m, int ld_m, const float* v,
                                                    const float* mix, const float* flp, float* resp, float* part,
                                                    int64_t n, int h, int k, const int* rows_dev, const float* h2,
-                                                   const float* eps, float* z_out, float* v_out, float* m_out) {
+                                                   const float* eps, float* z_out, float* v_out, float* m_out, float* zsq_part) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float wsum[4];
     __shared__ float lconst[KL_KMAX];
@@ -417,6 +488,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v5(const float* z, const float* 
         on[g] = col[g] < h;
     }
     float my_terms = 0.f;                       // every lane of a row: the sum of the row's nodes' terms, in node order
+    float zsq = 0.f;                            // fused reparameterisation: this lane's share of sum z^2 over the live rows
     for (int64_t base = (int64_t)blockIdx.x * 16 + wv * 4; base < n; base += (int64_t)gridDim.x * 16) {      // (wave-uniform)
         const bool live = base + rw < n;
         const int64_t r = live ? base + rw : n - 1;      // rows past the end shadow the last node: uniform control flow, no effects
@@ -440,6 +512,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v5(const float* z, const float* 
                     zz[g][i] = mm[i] + ee[i] * sqrtf(vv[i]);
                 }
                 if (live) {
+                    zsq = fmaf(zz[g][0], zz[g][0], fmaf(zz[g][1], zz[g][1], fmaf(zz[g][2], zz[g][2], fmaf(zz[g][3], zz[g][3], zsq))));
                     *reinterpret_cast<float4*>(z_out + r * h + col[g]) = make_float4(zz[g][0], zz[g][1], zz[g][2], zz[g][3]);
                     *reinterpret_cast<float4*>(v_out + r * h + col[g]) = make_float4(vv[0], vv[1], vv[2], vv[3]);
                     if (m_out) *reinterpret_cast<float4*>(m_out + r * h + col[g]) = m4;
@@ -486,6 +559,7 @@ __global__ __launch_bounds__(256) void k_kl_fwd_v5(const float* z, const float* 
     if (lane == 0) wsum[wv] = t;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (zsq_part) kl_zsq_block(zsq, wsum, zsq_part);
 }
 
 // per-node gradients gz, gm, gv (scaled by *gkl / n)
@@ -636,13 +710,19 @@ __global__ __launch_bounds__(256) void k_kl_bwd_fused(const float* z, const floa
 // and the mixture table comes from LDS.  Grid = KL_SLICES workgroups of 8 waves that interleave the slice's rows, two rows in
 // flight per wave; the waves' 2 k partial sums are combined through LDS two components at a time, in wave order.  Per element the
 // same expressions; a slice's rows are summed in another (fixed) order.
+// On the gh2 path the sweep can also do the work of the epilogue gradient of the layer that made h2 (`keep` / `bias_cols`: that
+// layer has no activation): the two stored quads become keep ? value * keep_scale : 0 -- k_epilogue_bwd_colsum's expression on
+// the same fp32 value, so the rows are the bits that pass would write -- and with `bias_cols` their column sums over the slice's
+// rows (the bias gradient's partials) are reduced over the waves in one more round of `red` and written behind the slice's
+// 2 k h mixture partials; `pstride` is a slice's length in `part` (2 k h, or (2 k + 2) h with bias_cols).
 constexpr int KLB_WAVES = 8, KLB_KR = 2;
 template <int KT>
 __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z, const float* m, int ld_m, const float* v, const float* mix,
                                                                   const float* resp, const float* gkl, float gscale, float z_extra,
                                                                   float* gz, float* gm, float* gv, float* part, int64_t n, int h, int k,
                                                                   const int* rows_dev, const float* h2, const float* eps,
-                                                                  const float* gz_up, float* gh2) {
+                                                                  const float* gz_up, float* gh2, const uint8_t* keep,
+                                                                  float keep_scale, int bias_cols, int pstride) {
     extern __shared__ __attribute__((aligned(16))) float4 sm4[];      // [2][k * h / 4] (mu_j, 1/(2 v_j)), then red[2 KR][waves][64]
     const int64_t n_real = rows_dev ? (int64_t)*rows_dev : n;
     const float refit = (float)n / (float)n_real;
@@ -665,6 +745,7 @@ __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z,
     for (int j = 0; j < KT; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) { amu[j][i] = 0.f; av[j][i] = 0.f; }
+    float bs0[4] = {0.f, 0.f, 0.f, 0.f}, bs1[4] = {0.f, 0.f, 0.f, 0.f};      // column sums of the stored gh2 quads (bias_cols)
     __syncthreads();
     constexpr int RU = 2;
     for (int64_t rb = r0 + w; rb < r1; rb += KLB_WAVES * RU) {
@@ -675,10 +756,12 @@ __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z,
             if ((lane & 15) < k && (lane >> 4) < RU && rr < r1 && rr < n_real) rv = resp[rr * k + (lane & 15)];
         }
         float zz[RU][4], mm[RU][4], vv[RU][4], rawv[RU][4], ee[RU][4], gu[RU][4];
+        uchar4 kp0[RU], kp1[RU];
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int64_t r = rb + KLB_WAVES * u;
             float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f), m4 = z4, v4 = make_float4(1.f, 1.f, 1.f, 1.f), r4 = z4, e4 = z4, g4 = z4;
+            kp0[u] = kp1[u] = make_uchar4(1, 1, 1, 1);
             if (ok && r < r1) {
                 z4 = *reinterpret_cast<const float4*>(z + r * h + col);
                 m4 = *reinterpret_cast<const float4*>(m + r * ld_m + col);
@@ -687,6 +770,10 @@ __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z,
                     r4 = *reinterpret_cast<const float4*>(h2 + r * 2 * h + h + col);
                     e4 = *reinterpret_cast<const float4*>(eps + r * h + col);
                     if (gz_up) g4 = *reinterpret_cast<const float4*>(gz_up + r * h + col);
+                    if (keep) {
+                        kp0[u] = *reinterpret_cast<const uchar4*>(keep + r * 2 * h + col);
+                        kp1[u] = *reinterpret_cast<const uchar4*>(keep + r * 2 * h + h + col);
+                    }
                 }
             }
             zz[u][0] = z4.x; zz[u][1] = z4.y; zz[u][2] = z4.z; zz[u][3] = z4.w;
@@ -748,6 +835,16 @@ __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z,
                     }
                 }
                 if (gh2) {
+                    if (keep) {
+                        const unsigned char k0[4] = {kp0[u].x, kp0[u].y, kp0[u].z, kp0[u].w}, k1[4] = {kp1[u].x, kp1[u].y, kp1[u].z, kp1[u].w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            o0[i] = k0[i] ? o0[i] * keep_scale : 0.f;
+                            o1[i] = k1[i] ? o1[i] * keep_scale : 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { bs0[i] += o0[i]; bs1[i] += o1[i]; }
                     *reinterpret_cast<float4*>(gh2 + r * 2 * h + col) = make_float4(o0[0], o0[1], o0[2], o0[3]);
                     *reinterpret_cast<float4*>(gh2 + r * 2 * h + h + col) = make_float4(o1[0], o1[1], o1[2], o1[3]);
                 } else {
@@ -784,7 +881,22 @@ __global__ __launch_bounds__(64 * KLB_WAVES) void k_kl_bwd_cols4(const float* z,
             } else {
                 o = make_float4(-t.x, -t.y, -t.z, -t.w);
             }
-            *reinterpret_cast<float4*>(part + ((size_t)blockIdx.y * 2 * k + (kind ? k : 0) + j) * h + col) = o;
+            *reinterpret_cast<float4*>(part + (size_t)blockIdx.y * pstride + (size_t)((kind ? k : 0) + j) * h + col) = o;
+        }
+    }
+    if (bias_cols) {       // one more round: entry 0 = the mean columns' sums, entry 1 = the raw-sigma columns'; waves 0 and 1 add them in wave order
+        __syncthreads();
+        red[(0 * KLB_WAVES + w) * 64 + lane] = make_float4(bs0[0], bs0[1], bs0[2], bs0[3]);
+        red[(1 * KLB_WAVES + w) * 64 + lane] = make_float4(bs1[0], bs1[1], bs1[2], bs1[3]);
+        __syncthreads();
+        if (w < 2 && ok) {
+            float4 t = red[(w * KLB_WAVES) * 64 + lane];
+#pragma unroll
+            for (int q = 1; q < KLB_WAVES; ++q) {
+                const float4 x = red[(w * KLB_WAVES + q) * 64 + lane];
+                t.x += x.x; t.y += x.y; t.z += x.z; t.w += x.w;
+            }
+            *reinterpret_cast<float4*>(part + (size_t)blockIdx.y * pstride + (size_t)2 * k * h + (w ? h : 0) + col) = t;
         }
     }
 }
@@ -832,14 +944,21 @@ __global__ __launch_bounds__(256) void k_kl_bwd_mix_part(const float* z, const f
     }
 }
 
+// g_bias (optional): a slice of `part` is followed by the 2 h column sums k_kl_bwd_cols4 left with bias_cols; they are finished in
+// the same launch by the same slice sum -- no cg factor, no softplus chain -- and written or added into g_bias [2 h].
 __global__ __launch_bounds__(1024) void k_kl_bwd_mix_final(const float* part, const float* z_pre, const float* gkl,
                                                            float gscale, float* g_zpre, int accumulate, int64_t n, int h,
-                                                           int k, int nsl, const int* rows_dev) {
+                                                           int k, int nsl, const int* rows_dev, float* g_bias = nullptr,
+                                                           int accumulate_bias = 0) {
     __shared__ float sm[64][16];
-    const int total = 2 * k * h, kh = k * h;
+    const int kh = k * h, total = 2 * kh + (g_bias ? 2 * h : 0);
     const int i = blockIdx.x * 16 + (threadIdx.x & 15);
     float acc = sum_slices_16x64(part, total, nsl, i, sm);     // slices added in a fixed order
     if ((threadIdx.x >> 4) != 0 || i >= total) return;
+    if (i >= 2 * kh) {
+        g_bias[i - 2 * kh] = accumulate_bias ? g_bias[i - 2 * kh] + acc : acc;
+        return;
+    }
     const float cg = gscale * (gkl ? *gkl : 1.f) / (float)(rows_dev ? (int64_t)*rows_dev : n);
     if (i >= kh) {  // chain through v_j = softplus(raw) + 1e-8
         const float raw = z_pre[i];
@@ -1473,15 +1592,19 @@ extern "C" int gv_mean_sq2(const float* x1, int64_t n1, float scale1, const floa
     return launch_status("gv_mean_sq2");
 }
 
+// workspace layout (floats): mix[3 k h] | KL partials [RED_BLOCKS] | slice partials [KL_SLICES][(2 k + 2) h] | sum z^2 partials [RED_BLOCKS]
+// (the slice partials are [KL_SLICES][2 k h] from the region's start unless the bias columns ride along: gv_reparam_kl_bwd_fold)
+static size_t kl_zsq_offset(int h, int k) { return 3 * (size_t)k * h + RED_BLOCKS + (size_t)KL_SLICES * (2 * k + 2) * h; }
+
 extern "C" int64_t gv_kl_workspace_bytes(int64_t n, int h, int k) {
     (void)n;
-    return (int64_t)sizeof(float) * (3 * (int64_t)k * h + RED_BLOCKS + (int64_t)KL_SLICES * 2 * k * h);
+    return (int64_t)sizeof(float) * (int64_t)(kl_zsq_offset(h, k) + RED_BLOCKS);
 }
 
 // the float4-column form where rows are 16-B aligned (h % 4 == 0, every operand 16-B aligned; GV_KL_V4=0 keeps the per-lane form)
 static bool kl_fwd_v4(int nb, size_t lds, hipStream_t st, const float* z, const float* m, int ld_m, const float* v, const float* mix,
                       const float* flp, float* resp, float* part, int64_t n, int h, int k, const int* rows_dev, const float* h2,
-                      const float* eps, float* z_out, float* v_out, float* m_out) {
+                      const float* eps, float* z_out, float* v_out, float* m_out, float* zsq_part) {
     static const int env = getenv("GV_KL_V4") ? atoi(getenv("GV_KL_V4")) : 1;
     const bool al = aligned16(mix) && (!z || aligned16(z)) && (!m || (aligned16(m) && ld_m % 4 == 0)) && (!v || aligned16(v)) &&
                     (!h2 || aligned16(h2)) && (!eps || aligned16(eps)) && (!z_out || aligned16(z_out)) && (!v_out || aligned16(v_out)) &&
@@ -1492,13 +1615,13 @@ static bool kl_fwd_v4(int nb, size_t lds, hipStream_t st, const float* z, const 
     if (v5 && h <= (v5 == 2 ? 512 : 256) && k <= 16) {
         if (h <= 256)
             hipLaunchKernelGGL(k_kl_fwd_v5<4>, dim3(nb), dim3(256), lds, st, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, h2,
-                               eps, z_out, v_out, m_out);
+                               eps, z_out, v_out, m_out, zsq_part);
         else
             hipLaunchKernelGGL(k_kl_fwd_v5<8>, dim3(nb), dim3(256), lds, st, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, h2,
-                               eps, z_out, v_out, m_out);
+                               eps, z_out, v_out, m_out, zsq_part);
         return true;
     }
-#define GV_KL_V4(G_) hipLaunchKernelGGL(k_kl_fwd_v4<G_>, dim3(nb), dim3(256), lds, st, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, h2, eps, z_out, v_out, m_out)
+#define GV_KL_V4(G_) hipLaunchKernelGGL(k_kl_fwd_v4<G_>, dim3(nb), dim3(256), lds, st, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, h2, eps, z_out, v_out, m_out, zsq_part)
     if (h <= 256) GV_KL_V4(1);
     else if (h <= 512) GV_KL_V4(2);
     else GV_KL_V4(4);
@@ -1521,7 +1644,7 @@ extern "C" int gv_kl_fwd(const float* z, const float* m, int ld_m, const float* 
     const int nb = kl_blocks(n);
     GV_REQUIRE(h <= 1024, GV_ERR_SHAPE, "gv_kl_fwd: h=%d > 1024 unsupported", h);
 #define GV_KL_FWD(CPL_) hipLaunchKernelGGL(k_kl_fwd<CPL_>, dim3(nb), dim3(256), lds, GV_ST, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev)
-    if (kl_fwd_v4(nb, lds, GV_ST, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, nullptr, nullptr, nullptr, nullptr, nullptr)) {}
+    if (kl_fwd_v4(nb, lds, GV_ST, z, m, ld_m, v, mix, flp, resp, part, n, h, k, rows_dev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) {}
     else if (h <= 64) GV_KL_FWD(1);
     else if (h <= 128) GV_KL_FWD(2);
     else if (h <= 256) GV_KL_FWD(4);
@@ -1536,18 +1659,21 @@ extern "C" int gv_kl_fwd(const float* z, const float* m, int ld_m, const float* 
 // the float4-column backward where rows are 16-B aligned (GV_KL_BWD_V4=0 keeps the lane-per-column form)
 static bool kl_bwd_cols4(hipStream_t st, const float* z, const float* m, int ld_m, const float* v, const float* mix, const float* resp,
                          const float* gkl, float gscale, float z_extra, float* gz, float* gm, float* gv, float* part, int64_t n, int h,
-                         int k, const int* rows_dev, const float* h2, const float* eps, const float* gz_up, float* gh2) {
+                         int k, const int* rows_dev, const float* h2, const float* eps, const float* gz_up, float* gh2,
+                         const uint8_t* keep = nullptr, float keep_scale = 1.f, bool bias_cols = false) {
     static const int env = getenv("GV_KL_BWD_V4") ? atoi(getenv("GV_KL_BWD_V4")) : 1;
     const bool al = aligned16(z) && aligned16(m) && ld_m % 4 == 0 && aligned16(v) && aligned16(mix) && aligned16(part) &&
                     (!gz || aligned16(gz)) && (!gm || aligned16(gm)) && (!gv || aligned16(gv)) && (!h2 || aligned16(h2)) &&
-                    (!eps || aligned16(eps)) && (!gz_up || aligned16(gz_up)) && (!gh2 || aligned16(gh2));
+                    (!eps || aligned16(eps)) && (!gz_up || aligned16(gz_up)) && (!gh2 || aligned16(gh2)) &&
+                    (!keep || (uintptr_t)keep % 4 == 0);
     if (!env || h % 4 != 0 || h > 1024 || k > 10 || !al) return false;      // (a 16-component instance spills: k > 10 keeps the other form)
     const size_t lds = ((size_t)2 * k * h / 4 + (size_t)2 * KLB_KR * KLB_WAVES * 64) * sizeof(float4);
     if (lds > 128 * 1024) return false;
     static unsigned long long lds_done = 0;
     if (lds > 64 * 1024 && !raise_dynamic_lds((const void*)k_kl_bwd_cols4<10>, 128 * 1024, lds_done, "gv_kl_bwd")) return false;
 #define GV_KLB(KT_) hipLaunchKernelGGL(k_kl_bwd_cols4<KT_>, dim3((h + 255) / 256, KL_SLICES), dim3(64 * KLB_WAVES), lds, st, z, m, ld_m, v, mix, resp, gkl, \
-                                       gscale, z_extra, gz, gm, gv, part, n, h, k, rows_dev, h2, eps, gz_up, gh2)
+                                       gscale, z_extra, gz, gm, gv, part, n, h, k, rows_dev, h2, eps, gz_up, gh2, keep, keep_scale, \
+                                       bias_cols ? 1 : 0, (2 * k + (bias_cols ? 2 : 0)) * h)
     GV_KLB(10);
 #undef GV_KLB
     return true;
@@ -1595,14 +1721,15 @@ extern "C" int gv_reparam_kl_fwd(const float* h2, const float* eps, const float*
     GV_REQUIRE(lds <= 64 * 1024, GV_ERR_SHAPE, "gv_reparam_kl_fwd: mixture table %zu B exceeds the 64 KiB LDS budget", lds);
     float* mix = workspace;
     float* part = workspace + 3 * (size_t)k * h;
+    float* zsq_part = workspace + kl_zsq_offset(h, k);      // sum z^2 per block, for gv_loss_combine_fold
     hipLaunchKernelGGL(k_kl_mix, dim3((k * h + 255) / 256), dim3(256), 0, GV_ST, z_pre, k, h, mix);
     const int nb = kl_blocks(n);
     const float* none = nullptr;
     const int* no_rows = nullptr;
 #define GV_RKL_FWD(CPL_)                                                                                                       \
     hipLaunchKernelGGL(k_kl_fwd<CPL_>, dim3(nb), dim3(256), lds, GV_ST, none, none, h, none, (const float*)mix, none, resp, part, n, h, \
-                       k, no_rows, h2, eps, z, v, m_out)
-    if (kl_fwd_v4(nb, lds, GV_ST, none, none, h, none, mix, none, resp, part, n, h, k, no_rows, h2, eps, z, v, m_out)) {}
+                       k, no_rows, h2, eps, z, v, m_out, zsq_part)
+    if (kl_fwd_v4(nb, lds, GV_ST, none, none, h, none, mix, none, resp, part, n, h, k, no_rows, h2, eps, z, v, m_out, zsq_part)) {}
     else if (h <= 64) GV_RKL_FWD(1);
     else if (h <= 128) GV_RKL_FWD(2);
     else if (h <= 256) GV_RKL_FWD(4);
@@ -1630,6 +1757,32 @@ extern "C" int gv_reparam_kl_bwd(const float* z, const float* h2, const float* v
     hipLaunchKernelGGL(k_kl_bwd_mix_final, dim3((2 * k * h + 15) / 16), dim3(1024), 0, GV_ST, (const float*)part, z_pre, gkl, gscale,
                        g_zpre, accumulate_zpre, n, h, k, KL_SLICES, no_rows);
     return launch_status("gv_reparam_kl_bwd");
+}
+
+// gv_reparam_kl_bwd that also does the epilogue gradient of the layer that made h2 (no activation; k_kl_bwd_cols4): gh2 rows
+// masked by keep / keep_scale before they are stored, their column sums (that layer's bias gradient) finished by the launch
+// that finishes g_zpre.  Only the float4-column form takes the fold: where it refuses, this call fails and launches nothing.
+extern "C" int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                                      const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up,
+                                      float* gh2, float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale,
+                                      float* g_bias, int accumulate_bias, float* workspace, int64_t n, int h, int k,
+                                      void* stream) {
+    GV_REQUIRE(z && h2 && v && eps && z_pre && resp && gh2 && g_zpre && workspace, GV_ERR_NULL,
+               "gv_reparam_kl_bwd_fold: NULL pointer");
+    GV_REQUIRE(n > 0 && h > 0 && k > 0 && k <= KL_FUSED_KT, GV_ERR_SHAPE, "gv_reparam_kl_bwd_fold: n=%lld h=%d k=%d (k <= %d)",
+               (long long)n, h, k, KL_FUSED_KT);
+    float* mix = workspace;
+    float* part = workspace + 3 * (size_t)k * h + RED_BLOCKS;
+    float* none = nullptr;
+    const int* no_rows = nullptr;
+    const int cols = (2 * k + (g_bias ? 2 : 0)) * h;
+    GV_REQUIRE(kl_bwd_cols4(GV_ST, z, h2, 2 * h, v, mix, resp, gkl, gscale, z_extra, none, none, none, part, n, h, k, no_rows, h2, eps,
+                            gz_up, gh2, keep, keep_scale, g_bias != nullptr),
+               GV_ERR_SHAPE, "gv_reparam_kl_bwd_fold: h=%d k=%d or an unaligned operand: only the float4-column backward "
+               "(h %% 4 == 0, k <= 10, 16-B rows) folds the epilogue gradient", h, k);
+    hipLaunchKernelGGL(k_kl_bwd_mix_final, dim3((cols + 15) / 16), dim3(1024), 0, GV_ST, (const float*)part, z_pre, gkl, gscale,
+                       g_zpre, accumulate_zpre, n, h, k, KL_SLICES, no_rows, g_bias, accumulate_bias);
+    return launch_status("gv_reparam_kl_bwd_fold");
 }
 
 __global__ void k_lincomb(const float* a0, float c0, const float* a1, float c1, const float* a2, float c2, const float* a3,
@@ -1681,6 +1834,25 @@ extern "C" int gv_loss_combine(const float* ws_pred, int64_t t, const float* ws_
                        n2, ws_kl ? 1.f / (float)n_nodes : 0.f, ws_mmd, n3, 1.f, reg_w, kl_w, mmd_w, scal, loss, rows_dev,
                        (float)n_nodes);
     return launch_status("gv_loss_combine");
+}
+
+// gv_loss_combine on the hand-off route: the regulariser's z half comes from the sum z^2 partials gv_reparam_kl_fwd left in ws_kl,
+// its relation half is summed from w_rel itself by the combine block (no gv_mean_sq2 launch).
+extern "C" int gv_loss_combine_fold(const float* ws_pred, int64_t t, const float* w_rel, int64_t n_embed, int64_t n_wrel,
+                                    const float* ws_kl, int64_t n_nodes, int h, int k, const float* ws_mmd, int sx, int sy,
+                                    float reg_w, float kl_w, float mmd_w, float* scal, float* loss, void* stream) {
+    GV_REQUIRE(ws_pred && loss && w_rel && ws_kl, GV_ERR_NULL, "gv_loss_combine_fold: NULL pointer");
+    GV_REQUIRE(t > 0 && n_embed > 0 && n_nodes > 0 && h > 0 && k > 0, GV_ERR_SHAPE, "gv_loss_combine_fold: t=%lld n_embed=%lld",
+               (long long)t, (long long)n_embed);
+    GV_REQUIRE(n_wrel > 0 && n_wrel <= LOSS_COMBINE_XSQ_MAX && n_wrel % 4 == 0, GV_ERR_SHAPE,
+               "gv_loss_combine_fold: n_wrel=%lld (one block sums at most %d elements, a multiple of 4; other tables keep gv_mean_sq2)",
+               (long long)n_wrel, LOSS_COMBINE_XSQ_MAX);
+    GV_REQUIRE(aligned16(w_rel), GV_ERR_ALIGN, "gv_loss_combine_fold: w_rel must be 16-B aligned");
+    const int n0 = red_blocks(t, 16), n2 = kl_blocks(n_nodes), n3 = ws_mmd ? sx + sy : 0;
+    hipLaunchKernelGGL(k_loss_combine_xsq, dim3(1), dim3(1024), 0, GV_ST, ws_pred, n0, 1.f / (float)t, ws_kl + kl_zsq_offset(h, k), n2,
+                       1.f / (float)n_embed, ws_kl + 3 * (size_t)k * h, n2, 1.f / (float)n_nodes, ws_mmd, n3, 1.f, reg_w, kl_w, mmd_w,
+                       scal, loss, (const float4*)w_rel, (int)(n_wrel / 4), 1.f / (float)n_wrel);
+    return launch_status("gv_loss_combine_fold");
 }
 
 extern "C" int gv_mmd_bwd(const float* x, const float* y, const int64_t* y_index, int sx, int sy, int h, const float* gmmd,

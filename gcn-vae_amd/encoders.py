@@ -243,11 +243,13 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         h = self.rconv_layer_1(g, h, r, norm)
         if self.grad_reducer is not None:     # layer 2 onwards is final once dL/dh1 exists: its arena suffix reduces under layer 1's backward
             h = self.grad_reducer.milestone(h, next(self.rconv_layer_2.parameters()))
-        h = self.rconv_layer_2(g, h, r, norm)
         # no flow between z and the KL term: the KL forward pass rides on the reparameterisation's sweep over the rows, and
-        # its backward is chained through the reparameterisation's (ops.reparam); with flows the two stay separate
+        # its backward is chained through the reparameterisation's (ops.reparam); with flows the two stay separate.  h2 has
+        # exactly one consumer here, so layer 2's epilogue gradient may ride on that backward too (ops.EpilogueLink)
         fuse_kl = self.training and self.n_flows == 0 and self.fuse_kl_with_reparam
-        z, self.z_mean, self.z_sigma = ops.reparam(h, eps, self.z_pre.squeeze(0) if fuse_kl else None)
+        h = self.rconv_layer_2(g, h, r, norm, sole_consumer=fuse_kl)
+        z, self.z_mean, self.z_sigma = ops.reparam(h, eps, self.z_pre.squeeze(0) if fuse_kl else None,
+                                                   getattr(h, '_gv_epi_link', None) if fuse_kl else None)
         self._z_pri_flowed = None
         if self.n_flows > 0:
             # flow_log_prob = mean over the rows that exist (a static-shape batch: the device count) of the blocks' summed log-dets

@@ -112,7 +112,9 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
                                        part, act_id, keep, scale if keep is not None else 1.0, gather_input, pad_output,
                                        gather_output, x_gathered)
 
-    def forward(self, g, x, etypes, norm=None):
+    def forward(self, g, x, etypes, norm=None, sole_consumer=False):
+        """``sole_consumer``: the caller passes the output to one node only and that node takes ``out._gv_epi_link``
+        (ops.EpilogueLink; KGVAE.forward -> ops.reparam): offered by the bdd layer without activation."""
         x, etypes, norm = ops.to_module_device(self.weight, x, etypes, norm)
         int_ids = x.dtype == torch.int64 and x.dim() == 1
         if int_ids and self.regularizer == 'bdd':
@@ -145,7 +147,8 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
                                               gidx, ridx, act_id, keep, keep_scale)
         elif self.regularizer == 'bdd':
             h = ops.rel_graph_conv_bdd(x, self.weight, h_bias, loop_w, norm, gidx, ridx, self.num_bases, act_id, keep,
-                                       keep_scale, self.reduce_hook)
+                                       keep_scale, self.reduce_hook,
+                                       sole_consumer=sole_consumer and post_act is None and late_keep is None)
         else:
             # basis: W_r = sum_b w_comp[r, b] V_b (one MFMA GEMM), then a full (in x out) matrix per relation
             flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)

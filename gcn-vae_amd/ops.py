@@ -1721,7 +1721,7 @@ class _RelGraphConvBdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep, keep_scale,
-                reduce_hook):
+                reduce_hook, link_box=None):
         x, _ = _row_major(x, 'x')
         n, in_feat = x.shape
         si = in_feat // num_bases
@@ -1769,6 +1769,11 @@ class _RelGraphConvBdd(torch.autograd.Function):
         # into the table's gradient (zero at this point of the step: the optimiser cleared it, nothing else adds to it)
         tgt = getattr(x, '_gv_grad_target', None)
         ctx.x_grad_target = tgt if (tgt is not None and reduce_hook is None and tuple(tgt.shape) == tuple(x.shape)) else None
+        # a caller that knows the output's one consumer asks for the epilogue hand-off (EpilogueLink): no activation, one GPU
+        ctx.epi_link = None
+        if link_box is not None and act == ACT_NONE and reduce_hook is None:
+            ctx.epi_link = link_box[0] = EpilogueLink(keep, keep_scale, h_bias is not None and ctx.needs_input_grad[2],
+                                                      ctx.direct[1], out_feat)
         return out
 
     @staticmethod
@@ -1777,7 +1782,11 @@ class _RelGraphConvBdd(torch.autograd.Function):
         gidx, ridx, nb, si, so, act, keep_scale, has_bias, reduce_hook = ctx.meta
         _verify_direct(ctx)
         d_w, d_b, d_l = ctx.direct
-        g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
+        folded = ctx.epi_link.take(grad_out) if ctx.epi_link is not None else None
+        if folded is not None:          # the consumer's backward wrote these rows masked and summed the bias gradient
+            g, grad_bias = folded
+        else:
+            g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
         pending = None
         g_agg = g
         if reduce_hook is not None:      # gradient of this rank's partial aggregate = sum over ranks; overlapped below
@@ -1828,7 +1837,7 @@ class _RelGraphConvBdd(torch.autograd.Function):
         grad_w = None
         if ctx.needs_input_grad[1] and not side_w:
             grad_w = _relation_weight_grad(gidx, ridx, coef, x, g_agg, nb, si, so, d_w)
-        return grad_x, grad_w, grad_bias, grad_loop, None, None, None, None, None, None, None, None
+        return grad_x, grad_w, grad_bias, grad_loop, None, None, None, None, None, None, None, None, None
 
 
 K1_REL_RUNS = _os.environ.get('GV_K1_REL_RUNS', '1') == '1'     # static graphs: rows sorted by relation (weight reuse along runs)
@@ -1846,9 +1855,17 @@ def use_relation_groups(weight, gidx):
 
 
 def rel_graph_conv_bdd(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act=ACT_NONE, keep=None,
-                       keep_scale=1.0, reduce_hook=None):
-    return _RelGraphConvBdd.apply(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep,
-                                  float(keep_scale), reduce_hook)
+                       keep_scale=1.0, reduce_hook=None, sole_consumer=False):
+    """``sole_consumer``: the caller hands the output to exactly one node that accepts an EpilogueLink (ops.reparam); the output
+    then carries the hand-off (``out._gv_epi_link``) when the layer can offer one."""
+    if not (sole_consumer and KL_SEAM_FOLD):
+        return _RelGraphConvBdd.apply(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep,
+                                      float(keep_scale), reduce_hook, None)
+    box = [None]
+    out = _RelGraphConvBdd.apply(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep, float(keep_scale),
+                                 reduce_hook, box)
+    out._gv_epi_link = box[0]
+    return out
 
 
 def rel_rows_gemm(feat, rows, w3, transpose_w, tiles, n_tiles, n_edges):
@@ -2553,6 +2570,63 @@ class KLLink:
 
 
 FUSE_REPARAM_KL = _os.environ.get('GV_FUSE_REPARAM_KL', '1') == '1'
+# The seam between the encoder's last layer and the loss head, on the hand-off route above: sum z^2 from the KL forward sweep
+# (no gv_mean_sq2 launch) and that layer's epilogue gradient + bias sums from the KL backward sweep (no gv_rgcn_epilogue_bwd /
+# gv_colsum_finish launches).  GV_KL_SEAM_FOLD=0: the three separate launches.
+KL_SEAM_FOLD = _os.environ.get('GV_KL_SEAM_FOLD', '1') == '1'
+LOSS_COMBINE_WREL_MAX = 65536      # = GV_LOSS_COMBINE_WREL_MAX (include/gcnvae.h): the combine block sums a relation table up to this size
+KL_BWD_COLS4_KMAX = 10             # components the float4-column KL backward holds in registers (csrc/k_loss.hip, kl_bwd_cols4)
+
+
+class EpilogueLink:
+    """Hand-off between an R-GCN layer WITHOUT activation and the reparameterisation node that is the ONLY consumer of its output
+    h2 (KGVAE.forward knows that): the layer's forward leaves its keep mask, keep scale and bias-gradient target here; the
+    reparameterisation's backward may then write dL/dh2 already masked and sum the bias gradient in the same sweep
+    (gv_reparam_kl_bwd_fold).  It records the buffer it returned in ``buf``; the layer's backward skips its own epilogue
+    gradient only for that very buffer."""
+    __slots__ = ('keep', 'keep_scale', 'want_bias', 'bias_target', 'n_bias', '_gv_direct_epoch', 'buf', 'buf_version', 'grad_bias')
+
+    def __init__(self, keep, keep_scale, want_bias, bias_target, n_bias):
+        self.keep, self.keep_scale = keep, float(keep_scale)
+        self.want_bias, self.bias_target, self.n_bias = bool(want_bias), bias_target, int(n_bias)
+        _stamp_direct(self)               # bias_target is a slice of the optimiser arena as it stood in the layer's forward
+        self.buf = self.grad_bias = None
+        self.buf_version = 0
+
+    def record(self, buf, grad_bias):
+        self.buf, self.buf_version, self.grad_bias = buf, buf._version, grad_bias
+
+    def take(self, grad_out):
+        """The layer's backward: None when nothing was folded; (g, grad_bias) when ``grad_out`` is the folded buffer, untouched;
+        raises when the fold happened but another gradient was added to h2's (the mask cannot be undone)."""
+        buf, version, grad_bias = self.buf, self.buf_version, self.grad_bias
+        self.buf = self.grad_bias = None
+        if buf is None:
+            return None
+        if (grad_out is None or grad_out.data_ptr() != buf.data_ptr() or tuple(grad_out.shape) != tuple(buf.shape)
+                or grad_out.dtype != buf.dtype or not grad_out.is_contiguous() or grad_out._version != version):
+            raise RuntimeError('the layer-2 epilogue gradient was folded into the KL backward (ops.EpilogueLink), but the gradient '
+                               'arriving at the layer is not that buffer: something else consumed the layer output as well and '
+                               'its gradient was added unmasked.  Only hand an EpilogueLink to ops.reparam when it is the sole '
+                               'consumer (GV_KL_SEAM_FOLD=0 turns the fold off)')
+        return grad_out, grad_bias
+
+
+def kl_seam_fold_ok(epi, gm, gv, h, k, tensors=()):
+    """THE rule of the KL backward's epilogue fold (decided in _Reparam.backward, at run time): a link from the layer, no other
+    consumer of z_mean / z_sigma (their gradients would be added to dL/dh2 after the mask), and the float4-column backward's own
+    conditions -- h % 4 == 0, h <= 1024, k <= 10 components (their mixture table then fits the LDS), 16-B aligned operands (the
+    keep mask 4-B) -- because the lane-per-column form does not carry the fold."""
+    if epi is None or not KL_SEAM_FOLD or gm is not None or gv is not None:
+        return False
+    if _os.environ.get('GV_KL_BWD_V4', '1') == '0' or h % 4 != 0 or h > 1024 or not 1 <= k <= KL_BWD_COLS4_KMAX:
+        return False
+    if epi.keep is not None and (epi.keep.data_ptr() % 4 != 0 or not epi.keep.is_contiguous()
+                                 or tuple(epi.keep.shape)[-1] != 2 * h or epi.keep.dtype != torch.uint8):
+        return False
+    if epi.want_bias and epi.n_bias != 2 * h:
+        return False
+    return all(t is None or t.data_ptr() % 16 == 0 for t in tensors)
 
 
 class _Reparam(torch.autograd.Function):
@@ -2560,7 +2634,7 @@ class _Reparam(torch.autograd.Function):
     With ``z_pre`` (the mixture prior's parameters, (2k, h)) the KL forward pass over the same rows rides along."""
 
     @staticmethod
-    def forward(ctx, h2, eps, z_pre, link_box):
+    def forward(ctx, h2, eps, z_pre, link_box, epi_link=None):
         ctx.set_materialize_grads(False)
         h2 = _chk(h2.contiguous(), name='h2')
         n, h = h2.shape[0], h2.shape[1] // 2
@@ -2569,6 +2643,7 @@ class _Reparam(torch.autograd.Function):
         v = torch.empty_like(z)
         m = torch.empty_like(z)
         ctx.link = None
+        ctx.epi_link = epi_link if z_pre is not None else None
         if z_pre is not None:
             z_pre = _chk(z_pre.contiguous(), name='z_pre')
             k = z_pre.shape[0] // 2
@@ -2585,17 +2660,35 @@ class _Reparam(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gz, gm, gv):
-        link = ctx.link
+        link, epi = ctx.link, ctx.epi_link
+        if epi is not None:
+            epi.buf = epi.grad_bias = None                 # nothing folded yet in this backward pass
         if link is not None and link.gkl is not None:      # the loss head left KL's backward to this node
             h2, eps, v, z, z_pre = ctx.saved_tensors
             n, h = v.shape
+            k = z_pre.shape[0] // 2
             gz = None if gz is None else _chk(gz.contiguous(), name='gz')
             d_zp = _direct_flat(z_pre)
             gzp = d_zp if d_zp is not None else torch.empty_like(z_pre)
             gh2 = torch.empty_like(h2)
+            if kl_seam_fold_ok(epi, gm, gv, h, k, (z, h2, v, eps, link.resp, link.ws, gz, gh2)):
+                # the producing layer's epilogue gradient rides along: gh2 leaves masked, its column sums are the bias gradient
+                g_bias = d_b = None
+                if epi.want_bias:
+                    d_b = epi.bias_target
+                    if d_b is not None:
+                        _verify_direct(epi)                # the arena slice resolved in the LAYER's forward
+                    g_bias = d_b if d_b is not None else torch.empty(2 * h, dtype=torch.float32, device=h2.device)
+                lib.call('gv_reparam_kl_bwd_fold', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp), ptr(link.gkl),
+                         float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), 1 if d_zp is not None else 0,
+                         ptr(epi.keep), epi.keep_scale, ptr(g_bias), 1 if d_b is not None else 0, ptr(link.ws), n, h, k,
+                         lib.stream())
+                link.gkl = None
+                epi.record(gh2, None if d_b is not None else g_bias)
+                return gh2, None, (None if d_zp is not None else gzp), None, None
             lib.call('gv_reparam_kl_bwd', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp), ptr(link.gkl),
                      float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), 1 if d_zp is not None else 0,
-                     ptr(link.ws), n, h, z_pre.shape[0] // 2, lib.stream())
+                     ptr(link.ws), n, h, k, lib.stream())
             link.gkl = None
             if gm is not None or gv is not None:       # z_mean / z_sigma have another consumer (a second loss head, a user's own term)
                 extra = torch.empty_like(h2)
@@ -2603,7 +2696,7 @@ class _Reparam(torch.autograd.Function):
                 gv = None if gv is None else _chk(gv.contiguous(), name='gv')
                 lib.call('gv_reparam_bwd', ptr(h2), ptr(eps), ptr(v), None, ptr(gm), ptr(gv), ptr(extra), n, h, lib.stream())
                 gh2 += extra
-            return gh2, None, (None if d_zp is not None else gzp), None
+            return gh2, None, (None if d_zp is not None else gzp), None, None
         h2, eps, v = ctx.saved_tensors[:3]
         n, h = v.shape
         gz = None if gz is None else _chk(gz.contiguous(), name='gz')
@@ -2611,16 +2704,17 @@ class _Reparam(torch.autograd.Function):
         gv = None if gv is None else _chk(gv.contiguous(), name='gv')
         gh2 = torch.empty_like(h2)
         lib.call('gv_reparam_bwd', ptr(h2), ptr(eps), ptr(v), ptr(gz), ptr(gm), ptr(gv), ptr(gh2), n, h, lib.stream())
-        return gh2, None, None, None
+        return gh2, None, None, None, None
 
 
-def reparam(h2, eps, z_pre=None):
+def reparam(h2, eps, z_pre=None, epi_link=None):
     """``z_pre``: when the caller knows that the loss head will evaluate KL(z) against this mixture with no flow in between,
-    the KL forward pass is done in the same sweep; the returned z then carries the hand-off (``z._gv_kl_link``)."""
+    the KL forward pass is done in the same sweep; the returned z then carries the hand-off (``z._gv_kl_link``).
+    ``epi_link``: the EpilogueLink of the layer that made ``h2``, from a caller that knows this node is h2's ONLY consumer."""
     if z_pre is None or not FUSE_REPARAM_KL:
-        return _Reparam.apply(h2, eps, None, None)
+        return _Reparam.apply(h2, eps, None, None, None)
     box = [None]
-    z, m, v = _Reparam.apply(h2, eps, z_pre, box)
+    z, m, v = _Reparam.apply(h2, eps, z_pre, box, epi_link if KL_SEAM_FOLD else None)
     z._gv_kl_link = box[0]
     return z, m, v
 
@@ -3092,8 +3186,12 @@ class _LossHead(torch.autograd.Function):
         # embed_rows: the regulariser's mean runs over that many rows (the rest of z are all-zero padding rows of the
         # multi-GPU row partition)
         z_count = z.numel() if embed_rows is None else int(embed_rows) * h
-        lib.call('gv_mean_sq2', ptr(z), z.numel(), 1.0 / z_count, ptr(w_rel), w_rel.numel(), 1.0 / w_rel.numel(), None,
-                 ptr(ws2), ptr(rows_dev), n, st)
+        # on the hand-off route the KL sweep that made z left sum z^2 in its workspace, and the combine launch sums w_rel^2 itself
+        reg_fold = (link is not None and KL_SEAM_FOLD and w_rel.numel() <= LOSS_COMBINE_WREL_MAX and w_rel.numel() % 4 == 0
+                    and w_rel.data_ptr() % 16 == 0)
+        if not reg_fold:
+            lib.call('gv_mean_sq2', ptr(z), z.numel(), 1.0 / z_count, ptr(w_rel), w_rel.numel(), 1.0 / w_rel.numel(), None,
+                     ptr(ws2), ptr(rows_dev), n, st)
         # DistMult scorer + BCE (three 800-B row gathers per triplet: the bandwidth-bound part)
         # (with a backward to come and a width the fused sweep covers: in by-relation order, the relation gradient's sums with it)
         ctx.fused = None
@@ -3104,10 +3202,15 @@ class _LossHead(torch.autograd.Function):
         else:
             lib.call('gv_distmult_bce_fwd', ptr(z), ld_z, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order), ptr(labels),
                      ptr(bias), ptr(score), None, ptr(ws), T, h, st)
-        lib.call('gv_loss_combine', ptr(ws), T, ptr(ws2), z.numel(), w_rel.numel(), ptr(wsk) if kl_w > 0 else None, n, h,
-                 (z_pre.shape[0] // 2) if kl_w > 0 else 0, ptr(wsm) if mmd_w > 0 else None,
-                 z_pri.shape[0] if mmd_w > 0 else 0, pick.numel() if mmd_w > 0 else 0, float(reg_w), float(kl_w),
-                 float(mmd_w), ptr(scal), ptr(loss), ptr(rows_dev), st)
+        if reg_fold:
+            lib.call('gv_loss_combine_fold', ptr(ws), T, ptr(w_rel), z.numel(), w_rel.numel(), ptr(wsk), n, h, z_pre.shape[0] // 2,
+                     ptr(wsm) if mmd_w > 0 else None, z_pri.shape[0] if mmd_w > 0 else 0, pick.numel() if mmd_w > 0 else 0,
+                     float(reg_w), float(kl_w), float(mmd_w), ptr(scal), ptr(loss), st)
+        else:
+            lib.call('gv_loss_combine', ptr(ws), T, ptr(ws2), z.numel(), w_rel.numel(), ptr(wsk) if kl_w > 0 else None, n, h,
+                     (z_pre.shape[0] // 2) if kl_w > 0 else 0, ptr(wsm) if mmd_w > 0 else None,
+                     z_pri.shape[0] if mmd_w > 0 else 0, pick.numel() if mmd_w > 0 else 0, float(reg_w), float(kl_w),
+                     float(mmd_w), ptr(scal), ptr(loss), ptr(rows_dev), st)
         ctx.save_for_backward(z, z_mean if kl_w > 0 else None, z_sigma if kl_w > 0 else None, w_rel,
                               z_pre if kl_w > 0 else None, resp, z_pri if mmd_w > 0 else None, z_post,
                               pick if mmd_w > 0 else None, labels, score, wsk, rows_dev)

@@ -975,6 +975,27 @@ int gv_reparam_kl_fwd(const float* h2, const float* eps, const float* z_pre, flo
 int gv_reparam_kl_bwd(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre, const float* resp,
                       const float* gkl, float gscale, float z_extra, const float* gz_up, float* gh2, float* g_zpre,
                       int accumulate_zpre, float* workspace, int64_t n, int h, int k, void* stream);
+/* The seam between the layer that made h2 and the loss head (one consumer of h2, that layer without activation):
+ *   gv_reparam_kl_fwd also leaves sum z^2, one partial per block of its sweep, at the end of `workspace`;
+ *   gv_loss_combine_fold = gv_loss_combine that takes the regulariser's z half from those partials (scaled by 1 / n_embed) and
+ *                       sums w_rel^2 itself in its one block (scaled by 1 / n_wrel; n_wrel <= GV_LOSS_COMBINE_WREL_MAX and a
+ *                       multiple of 4, w_rel 16-B aligned; other tables keep gv_mean_sq2 + gv_loss_combine): scal[1] = mean z^2 + mean w_rel^2 as before, no
+ *                       gv_mean_sq2 launch; ws_kl must be the workspace gv_reparam_kl_fwd filled for these n_nodes, h, k;
+ *   gv_reparam_kl_bwd_fold = gv_reparam_kl_bwd followed by that layer's gv_rgcn_epilogue_bwd + gv_colsum_finish in the same two
+ *                       launches: gh2 = keep ? gh2 * keep_scale : 0 before it is stored (keep: uint8 [n, 2h], 4-B aligned, or
+ *                       NULL = no dropout: rows unmasked) -- the rows are bit for bit what the separate pass writes -- and
+ *                       g_bias [2h] (optional) = the column sums of the stored rows, overwritten or, with accumulate_bias,
+ *                       added to; summed per row slice and then over the slices in a fixed order.  Needs h % 4 == 0,
+ *                       k <= 10 and 16-B aligned operands (the float4-column backward); otherwise it fails with GV_ERR_SHAPE
+ *                       and launches nothing: the caller decides beforehand (ops.kl_seam_fold_ok). */
+#define GV_LOSS_COMBINE_WREL_MAX 65536
+int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                           const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up, float* gh2,
+                           float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale, float* g_bias,
+                           int accumulate_bias, float* workspace, int64_t n, int h, int k, void* stream);
+int gv_loss_combine_fold(const float* ws_pred, int64_t t, const float* w_rel, int64_t n_embed, int64_t n_wrel,
+                         const float* ws_kl, int64_t n_nodes, int h, int k, const float* ws_mmd, int sx, int sy, float reg_w,
+                         float kl_w, float mmd_w, float* scal /* 4 floats, optional */, float* loss, void* stream);
 /* upstream gradient = gscale * (*gkl); gz additionally receives (*gkl) * z_extra * z (the embedding regulariser's
  * gradient, kgvae/link_predict.py:68-69, folded into the same pass); accumulate_zpre adds into g_zpre; mix_ready = 1 when `workspace` is the one
  * gv_kl_fwd filled for the same z_pre (skips recomputing the mixture table).  With rows_dev: padding rows get zero gz / gm / gv
