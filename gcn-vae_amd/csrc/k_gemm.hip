@@ -354,6 +354,35 @@ __device__ __forceinline__ f32x16 score_tile(const GemmParams& p, int m0, int n0
     return acc;
 }
 
+// score_tile_with: score_tile with the query rows supplied by the caller -- load_a_chunk(k0, ra) fills ra with this thread's share
+// of Q[m0 .., k0 ..] in load_a's layout (gv_entity_topk_scores gathers and scales them on the way).  The same staging, the same
+// chain; score_tile keeps its own spelling because routing it through here moves instructions in the rankers' and selectors' code.
+template <class LoadA>
+__device__ __forceinline__ f32x16 score_tile_with(const GemmParams& p, LoadA load_a_chunk, int n0, float (&ra)[SC_BM * SC_BK / 256],
+                                                  float (&rb)[SC_BN * SC_BK / 256], float* As, float* Bs) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int k0 = 0; k0 < p.k; k0 += SC_BK) {
+        stage_a<false, SC_BM, SC_BK>(As, ra);
+        stage_b<true, SC_BN, SC_BK>(Bs, rb);
+        __syncthreads();
+        if (k0 + SC_BK < p.k) {
+            load_a_chunk(k0 + SC_BK, ra);
+            load_b<true, SC_BN, SC_BK>(p, n0, k0 + SC_BK, p.k, rb);
+        }
+#pragma unroll
+        for (int kk = 0; kk < SC_BK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * SC_LDA + wm + l31], Bs[(kk + lhi) * SC_LDB + wn + l31],
+                                                       acc, 0, 0, 0);
+        __syncthreads();
+    }
+    return acc;
+}
+
 // ---- the Monte-Carlo posterior-predictive tile (gv_rank_scores_mc, gv_topk_scores_mc): a loop over samples around score_tile ----
 // Sample s has its own query matrix at q + s * q_stride and its own entity table at e + s * e_stride (the leading dimensions are
 // shared) and an optional bias[s]; logit_s comes from score_tile unchanged, and
@@ -692,6 +721,140 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 5 : 1)
         const int rl = wid * (BM / 4) + i, row = m0 + rl;
         if (row >= p.m) break;
         unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
+        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// ---- per-entity completion (gv_entity_topk_scores): one list per query entity over ALL relations -------------------------------
+// Query row i is entity a = ents[i]; its candidates are the pairs (r, x), logit = (E[a] * w[r]) . E[x] + bias -- k_topk_span with
+// the relations walked INSIDE the row's list, so neither an (entity x relation) query matrix nor m * R * k intermediate results
+// exist.  The columns of a row are the sequence of (relation, 64-column tile) pairs, r-major: tile t = r * col_tiles + ct, candidate
+// id = r * N + x (< 2^31), so the ordered key of k_topk.h already says "logit, then relation, then entity".  A workgroup owns a
+// 64-row tile of query entities and a contiguous span of that sequence.  The query operand is made while it is staged: a thread's
+// four floats of E[a] (gathered through ents) times the same four of w[r], one f32 multiply each -- the value gv_mul stores --
+// and goes through score_tile's K-chunked staging, so LDS is k_topk_span's (27 KiB + the lists) at any width and k = 128 fits
+// beside it.  At the first tile of a relation (and of the span) the 64 rows' filter cursors are re-opened on key a * R + r.
+struct EntityTopkParams {
+    GemmParams g;                 // b = E (stored [N, h]), m, n = N, k = h; a is not read
+    const int* ents;              // [m] query entities; an id outside [0, N) is a row without candidates
+    const float* w;               // [R, ld_w]
+    int ld_w, vec_a;              // vec_a: four floats of a row of E and of w may be read as one
+    int num_rels, exclude_self;
+    const float* bias;
+    const int* filt_lo;           // key a * R + r; NULL: no filter
+    const int* filt_hi;
+    const int* filt_ent;
+    int n_ent;
+    int topk;
+    int span_tiles, n_spans;      // (relation, column tile) pairs per span (blockIdx.y = span)
+    unsigned long long* part;     // [m][n_spans][topk]
+};
+
+struct EntityTopkOut {
+    int* rel;
+    int* ent;
+    float* logits;
+    int n;
+    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
+        const int id = topk_key_id(key);
+        rel[i] = id < 0 ? -1 : id / n;
+        ent[i] = id < 0 ? -1 : id % n;
+        logits[i] = topk_key_logit(key);
+    }
+};
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams ep) {
+    constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256;
+    __shared__ float As[BK * SC_LDA];
+    __shared__ float Bs[BK * SC_LDB];
+    __shared__ float Ls[BM * LDL];
+    __shared__ unsigned long long thr[BM];
+    __shared__ int cur[BM], fhi[BM], nxt[BM];
+    __shared__ int fl[4][64];
+    __shared__ int ent_s[BM];                      // the rows' entities (-1: no such row)
+    extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const GemmParams& p = ep.g;
+    const int k = ep.topk;
+    const int m0 = blockIdx.x * BM;
+    const int col_tiles = (p.n + BN - 1) / BN;
+    const int t_begin = blockIdx.y * ep.span_tiles;
+    const int t_end = min(t_begin + ep.span_tiles, ep.num_rels * col_tiles);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const bool filtered = ep.filt_lo != nullptr;
+
+    // this thread's share of the query operand: row threadIdx.x / 4 of the tile, APT floats from column (threadIdx.x % 4) * APT on
+    const int a_row = m0 + threadIdx.x / (BK / APT), a_col = (threadIdx.x % (BK / APT)) * APT;
+    const int a_ent = a_row < p.m ? ep.ents[a_row] : -1;
+    const bool a_ok = (unsigned)a_ent < (unsigned)p.n;
+    const float* a_src = p.b + (a_ok ? (size_t)a_ent * p.ldb : 0) + a_col;
+    const float* w_src = ep.w + a_col;             // + r * ld_w
+    auto load_q = [&](int k0, float (&r)[APT]) {
+        float wv[APT];
+        load_run<APT>(a_src + k0, a_col + k0, p.k, a_ok, ep.vec_a, r, 0);
+        load_run<APT>(w_src + k0, a_col + k0, p.k, a_ok, ep.vec_a, wv, 0);
+#pragma unroll
+        for (int i = 0; i < APT; ++i) r[i] *= wv[i];
+    };
+
+    int r = t_begin / col_tiles, ct = t_begin - r * col_tiles;
+    float ra[APT], rb[BN * BK / 256];
+    if (t_begin < t_end) {
+        w_src += (size_t)r * ep.ld_w;
+        load_q(0, ra);
+        load_b<true, BN, BK>(p, ct * BN, 0, p.k, rb);
+    }
+    for (int i = threadIdx.x; i < BM * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (threadIdx.x < BM) {
+        const int row = m0 + threadIdx.x;
+        const int a = row < p.m ? ep.ents[row] : -1;
+        ent_s[threadIdx.x] = (unsigned)a < (unsigned)p.n ? a : -1;
+        thr[threadIdx.x] = 0ull;
+    }
+    const float bv = ep.bias ? *ep.bias : 0.f;
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = ct * BN;
+        const f32x16 acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
+        const bool opens = ct == 0 || t == t_begin;                // the relation's (or the span's) first tile
+        const int r_now = r;
+        if (++ct == col_tiles) { ct = 0; ++r; w_src += ep.ld_w; }
+        if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
+            load_q(0, ra);
+            load_b<true, BN, BK>(p, ct * BN, 0, p.k, rb);
+        }
+        // (every wave is past score_tile's last barrier: nobody still reads the previous relation's cursors, or Ls)
+        if (opens && threadIdx.x < BM) {
+            const int rl = threadIdx.x, a = ent_s[rl];
+            topk_filter_begin(ep.filt_lo, ep.filt_hi, ep.filt_ent, ep.n_ent, filtered && a >= 0, (long long)a * ep.num_rels + r_now, n0,
+                              &cur[rl], &fhi[rl], &nxt[rl]);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Ls[(wm + (i & 3) + 8 * (i >> 2) + 4 * lhi) * LDL + wn + l31] = acc[i] + bv;
+        __syncthreads();
+
+        const int col = n0 + lane;
+        for (int i = 0; i < BM / 4; ++i) {
+            const int rl = wid * (BM / 4) + i;
+            if (m0 + rl >= p.m) break;
+            const int a = ent_s[rl];
+            if (a < 0) continue;
+            unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], r_now * p.n + col) : 0ull;
+            if (filtered && nxt[rl] < n0 + BN &&
+                topk_filter_window(ep.filt_ent, n0, (int)((unsigned)(t - t_begin) * BM + rl + 1u), lane, &cur[rl], &fhi[rl], &nxt[rl],
+                                   fl[wid]))
+                key = 0ull;
+            if (ep.exclude_self && col == a) key = 0ull;
+            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
+        }
+    }
+    for (int i = 0; i < BM / 4; ++i) {
+        const int rl = wid * (BM / 4) + i, row = m0 + rl;
+        if (row >= p.m) break;
+        unsigned long long* dst = ep.part + ((size_t)row * ep.n_spans + blockIdx.y) * k;
         for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
     }
 }
@@ -1328,6 +1491,74 @@ extern "C" int gv_topk_scores_constrained(const float* q, int ld_q, const float*
     GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores_constrained: NULL pointer");
     return topk_scores_launch<true>("gv_topk_scores_constrained", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_logits, workspace, m, v, h, stream);
+}
+
+// ---- per-entity completion (gv_entity_topk_scores) ------------------------------------------------------------------------------
+// spans of the R * ceil(N / 64) (relation, column tile) pairs: topk_spans' rule, up to 256 spans so that a single query entity
+// still fills the chip (its one row tile is all the parallelism there is besides)
+static void entity_topk_spans(long long m, int n, int num_rels, int* span_tiles, int* n_spans) {
+    topk_spans_of(m, (long long)num_rels * (((long long)n + 63) / 64), 256, span_tiles, n_spans);
+}
+
+extern "C" int64_t gv_entity_topk_scores_workspace_bytes(int m, int n, int num_rels, int k) {
+    if (m <= 0 || n <= 0 || num_rels <= 0 || (long long)n * num_rels > INT_MAX || k < 1 || k > TOPK_MAX) return 0;
+    int span_tiles = 0, n_spans = 0;
+    entity_topk_spans(m, n, num_rels, &span_tiles, &n_spans);
+    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                                     const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int exclude_self,
+                                     int k, int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
+                                     int64_t workspace_bytes, int n, int num_rels, int h, void* stream) {
+    const char* name = "gv_entity_topk_scores";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE,
+               "gv_entity_topk_scores: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", m, n, num_rels, h, n_filt_ent);
+    GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "gv_entity_topk_scores: n * num_rels = %lld does not fit 31 bits",
+               (long long)n * num_rels);
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_entity_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "gv_entity_topk_scores: span_tiles=%d (0: the library's rule)", span_tiles);
+    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_entity_topk_scores: leading dimension too small");
+    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
+               "gv_entity_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    if (m == 0) return GV_OK;
+    GV_REQUIRE(ents && e && w && out_rel && out_ent && out_logits && workspace, GV_ERR_NULL, "gv_entity_topk_scores: NULL pointer");
+    EntityTopkParams ep;
+    ep.g = score_gemm_params(nullptr, ld_e, e, ld_e, m, n, h);
+    ep.ents = ents; ep.w = w; ep.ld_w = ld_w;
+    ep.vec_a = ep.g.vec_b && aligned16(w) && (ld_w % 4 == 0);
+    ep.num_rels = num_rels; ep.exclude_self = exclude_self != 0;
+    ep.bias = bias;
+    ep.filt_lo = filt_lo; ep.filt_hi = filt_hi; ep.filt_ent = filt_ent; ep.n_ent = n_filt_ent;
+    ep.topk = k;
+    const long long tiles = (long long)num_rels * (((long long)n + 63) / 64);
+    if (span_tiles > 0) {
+        ep.span_tiles = (int)std::min<long long>(span_tiles, tiles);
+        ep.n_spans = (int)((tiles + ep.span_tiles - 1) / ep.span_tiles);
+    } else {
+        entity_topk_spans(m, n, num_rels, &ep.span_tiles, &ep.n_spans);
+    }
+    GV_REQUIRE(ep.n_spans <= 65535, GV_ERR_SHAPE, "gv_entity_topk_scores: span_tiles=%d gives %d spans (at most 65535)", span_tiles,
+               ep.n_spans);
+    const int64_t need = (int64_t)m * ep.n_spans * k * (int64_t)sizeof(unsigned long long);
+    GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "gv_entity_topk_scores: workspace of %lld bytes, %lld needed",
+               (long long)workspace_bytes, (long long)need);
+    ep.part = (unsigned long long*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 28 KiB static)
+    dim3 grid((m + 63) / 64, ep.n_spans), block(256), mgrid((m + 3) / 4);
+    const EntityTopkOut out{out_rel, out_ent, out_logits, n};
+    if (k <= 64) {
+        hipLaunchKernelGGL((k_entity_topk_span<1>), grid, block, lds, st, ep);
+        hipLaunchKernelGGL((k_topk_merge<1, EntityTopkOut>), mgrid, block, 0, st, ep.part, m, ep.n_spans, k, out);
+    } else {
+        static unsigned long long lds_raised = 0;
+        if (!raise_dynamic_lds((const void*)k_entity_topk_span<2>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised, name))
+            return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_entity_topk_span<2>), grid, block, lds, st, ep);
+        hipLaunchKernelGGL((k_topk_merge<2, EntityTopkOut>), mgrid, block, 0, st, ep.part, m, ep.n_spans, k, out);
+    }
+    return launch_status(name);
 }
 
 // ---- Monte-Carlo posterior-predictive ranking and top-k (gv_rank_scores_mc, gv_topk_scores_mc, gv_pair_prob_std_mc) -----------

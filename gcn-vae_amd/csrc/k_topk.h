@@ -203,14 +203,19 @@ __global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* pa
 
 // spans per query-row tile: about 4 workgroups per CU of the MI355X (256 CUs) at any m, each span at least 8 column tiles long so
 // the running lists warm up.  A fixed CU count keeps the workspace size a function of (m, v, k) alone.
-inline void topk_spans(long long m, int v, int* span_tiles, int* n_spans) {
-    const long long row_tiles = (m + 63) / 64, col_tiles = ((long long)v + 63) / 64;
+// topk_spans_of: the same rule on a sequence of `col_tiles` tiles, at most `max_spans` of them per row tile (what stage 2 walks).
+inline void topk_spans_of(long long m, long long col_tiles, long long max_spans, int* span_tiles, int* n_spans) {
+    const long long row_tiles = (m + 63) / 64;
     long long s = (4 * 256 + row_tiles - 1) / row_tiles;
     s = std::min(s, std::max(1LL, col_tiles / 8));
-    s = std::max(1LL, std::min(s, 64LL));
+    s = std::max(1LL, std::min(s, max_spans));
     const long long per = (col_tiles + s - 1) / s;
     *span_tiles = (int)per;
     *n_spans = (int)((col_tiles + per - 1) / per);
+}
+
+inline void topk_spans(long long m, int v, int* span_tiles, int* n_spans) {
+    topk_spans_of(m, ((long long)v + 63) / 64, 64, span_tiles, n_spans);
 }
 
 }  // namespace gv

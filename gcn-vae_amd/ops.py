@@ -742,6 +742,63 @@ def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=N
     return ids.long(), logits
 
 
+def _entity_topk_operands(ents, emb, w):
+    """The shape checks of ``entity_topk_scores`` on its operands, ahead of any look at their device: (m, n, num_rels, h)."""
+    for name, t in (('emb', emb), ('w', w)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    if not isinstance(ents, torch.Tensor) or ents.dim() != 1 or ents.is_floating_point() or ents.dtype == torch.bool:
+        raise TypeError('ents: expected a 1-D integer tensor of entity ids')
+    if emb.shape[1] != w.shape[1]:
+        raise ValueError('emb / w width mismatch')
+    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
+    if n < 1 or num_rels < 1 or h < 1:
+        raise ValueError(f'need at least one entity, one relation and width >= 1 (n={n}, num_rels={num_rels}, h={h})')
+    if n * num_rels >= 2 ** 31:
+        raise ValueError(f'n * num_rels = {n * num_rels} does not fit 31 bits: a candidate (r, x) is the id r * n + x')
+    return ents.numel(), n, num_rels, h
+
+
+def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
+    """Per-entity completion: for every query entity ``a = ents[i]`` the ``k`` best pairs (r, x) over ALL relations under
+    ``logit[i, r, x] = (emb[a] * w[r]) . emb[x] (+ bias)`` -- bit for bit ``gemm(mul(emb[a], w[r]), emb^T, precision='f32') + bias``,
+    the logits ``topk_scores`` and ``mine_scores`` select on -- from one fused launch pair (gv_entity_topk_scores) that keeps one
+    sorted list per entity while the relations are walked: no (entity x relation) query matrix, no per-relation results.  With
+    a filter (one range per key ``a * R + r``, N * R of them: ``ranking._mine_filter`` builds it) the ids
+    ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R + r]]`` are no candidates under relation r, nor is ``x == a`` with
+    ``exclude_self``.  Order: logit descending (-0 and +0 alike), then relation, then entity ascending; NaN after everything.
+    ``ents`` may repeat and need not be sorted.  ``span``: (relation, 64-column tile) pairs per workgroup instead of the library's
+    rule -- the result does not depend on it.  Returns ``(rel int64 (m, k), ent int64 (m, k), logits float32 (m, k))``, padded
+    with -1 / -1 / -inf past a row's last candidate; -0 is reported as +0 and every NaN as the one quiet NaN."""
+    m, n, num_rels, h = _entity_topk_operands(ents, emb, w)
+    k = _topk_arg(k)
+    if span is not None and int(span) < 1:
+        raise ValueError(f'span counts (relation, column tile) pairs per workgroup: at least 1, got {span}')
+    if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
+        raise ValueError(f'query entities must lie in [0, {n})')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, n * num_rels, n, emb.device)
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev = emb.device
+    rel = torch.empty(m, k, dtype=torch.int32, device=dev)
+    ent = torch.empty(m, k, dtype=torch.int32, device=dev)
+    logits = torch.empty(m, k, dtype=torch.float32, device=dev)
+    if m == 0:
+        return rel.long(), ent.long(), logits
+    ents32 = ents.to(device=dev, dtype=torch.int32).contiguous()
+    bias = _bias_arg(bias)
+    if span is None:
+        span_tiles, ws_bytes = 0, int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
+    else:
+        tiles = num_rels * ((n + 63) // 64)
+        span_tiles = min(int(span), tiles)
+        ws_bytes = m * ((tiles + span_tiles - 1) // span_tiles) * k * 8
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_entity_topk_scores', ptr(ents32), m, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+             int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(logits), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+    return rel.long(), ent.long(), logits
+
+
 def _mc_operands(q, entities):
     """The two sample stacks of a Monte-Carlo query -- q (S, m, h), entities (S, v, h) -- checked for shape ahead of any look at
     their device, then as contiguous float32: (q, entities, S, m, v, h)."""

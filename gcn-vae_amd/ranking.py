@@ -32,6 +32,12 @@ triplets -- the K most confident new ones, or all above a threshold -- from ``op
 object tiles of the entity table stay in LDS while the relations are walked over them).  ``mine_from_scores`` states the rule on
 a materialised (R, N, N) tensor; ``mine_triplets_unfused`` is the per-relation GEMM cross-check.
 
+Per-entity completion (what is this entity missing? -- the question of the reference's ``--generate`` ego-net demo,
+kgvae/utils.py:224-288): ``complete_entities`` returns each entity's k best new facts over ALL relations at once, the entity as
+subject or as object, from ``ops.entity_topk_scores`` (gv_entity_topk_scores: one sorted list per entity while the relations are
+walked, at ``predict_topk``'s logits).  ``complete_entities_from_scores`` states the rule on a materialised (m, R, N) tensor;
+``complete_entities_unfused`` is the per-relation GEMM cross-check.
+
 Monte-Carlo posterior predictive (the encoder is variational: one draw of the latents gives one of many possible rankings):
 with S samples from ``KGVAE.posterior_samples``, ``calc_mc_mrr`` ranks and ``predict_topk_mc`` selects on
 ``pbar = mean_s sigmoid(logit_s)`` -- ``ops.rank_scores_mc`` / ``ops.topk_scores_mc`` loop over the samples around the same
@@ -773,8 +779,9 @@ def mine_from_scores(score, *, k=None, threshold=None, filt_lo=None, filt_hi=Non
                             exclude_self=exclude_self, max_results=max_results, cand_subj=cand_subj, cand_obj=cand_obj)
 
 
-def _mine_filter(filter_index, n, num_rels, device):
-    """(lo, hi, ent) of ALL N * R object-query keys s * R + r: one searchsorted over the index."""
+def _mine_filter(filter_index, n, num_rels, device, direction='o'):
+    """(lo, hi, ent) of ALL N * R object-query keys s * R + r: one searchsorted over the index (``direction`` 's': the subject-query
+    keys o * R + r and their known subjects)."""
     if filter_index is None:
         return None, None, None
     if filter_index.num_nodes != n or filter_index.num_rels != num_rels:
@@ -782,8 +789,8 @@ def _mine_filter(filter_index, n, num_rels, device):
                          f'have {n} / {num_rels}')
     a = torch.arange(n, device=device).repeat_interleave(num_rels)
     r = torch.arange(num_rels, device=device).repeat(n)
-    lo, hi = filter_index.lookup(a, r, 'o')
-    return lo, hi, filter_index.entities('o', device)
+    lo, hi = filter_index.lookup(a, r, direction)
+    return lo, hi, filter_index.entities(direction, device)
 
 
 def _mine_members(type_constraint, n, num_rels, device):
@@ -904,6 +911,84 @@ def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=
 
     return _mine_unfused(logits_of, False, n, num_rels, emb.device, k=k, threshold=threshold, filt=filt, exclude_self=exclude_self,
                         max_results=max_results, members=members)
+
+
+# ---- per-entity completion: what is this entity missing? ------------------------------------------------------------------------
+COMPLETE_UNFUSED_ELEMS = 1 << 26      # logits per chunk of the materialised cross-check: bounds its (rows, R, N) tensor
+
+
+def complete_entities_from_scores(score, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True):
+    """The rule of ``ops.entity_topk_scores`` on a materialised (m, R, N) logit tensor, in plain torch (any device): row i belongs
+    to entity ``entities[i]``, its candidates are all (r, x) less the ids ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R + r]]``
+    under relation r (the dense per-key ranges of ``_mine_filter``) and less ``x == a`` with ``exclude_self``; they go by logit
+    descending, equal logits (-0 and +0 alike) by relation, then by entity, NaN after every other value.  Returns ``(rel int64
+    (m, k), other int64 (m, k), logits float32 (m, k))``, padded with -1 / -1 / -inf; -0 is reported as +0 and every NaN as the
+    one quiet NaN.  ``topk_from_scores`` on the (m, R * N) view: the id r * N + x already says relation first, then entity."""
+    m, num_rels, n = score.shape
+    ents = torch.as_tensor(entities, dtype=torch.long, device=score.device).reshape(-1)
+    if ents.numel() != m:
+        raise ValueError('one query entity per row of the score tensor')
+    allowed = torch.ones(m, num_rels, n, dtype=torch.bool, device=score.device)
+    if filt_lo is not None:
+        keys = (ents.view(-1, 1) * num_rels + torch.arange(num_rels, device=score.device)).reshape(-1)
+        lo, hi = filt_lo.reshape(-1).to(score.device)[keys], filt_hi.reshape(-1).to(score.device)[keys]
+        allowed &= ~_listed_mask(lo, hi, filt_ent.to(score.device), m * num_rels, n, score.device).view(m, num_rels, n)
+    if exclude_self and m:
+        allowed[torch.arange(m, device=score.device), :, ents] = False
+    ids, logits = topk_from_scores(score.reshape(m, num_rels * n), k, cand=allowed.view(m, num_rels * n))
+    gone = ids < 0
+    return torch.where(gone, ids, ids // n), torch.where(gone, ids, ids % n), logits
+
+
+def _complete_args(embedding, w, entities, k, side, filter_index):
+    """What the two routes of ``complete_entities`` check and prepare alike: (emb, w, entities, k, (lo, hi, ent))."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    k = ops._topk_arg(k)
+    emb = embedding.detach()
+    wd = w.detach().to(emb.device)
+    ents = torch.as_tensor(entities, device=emb.device).reshape(-1)
+    ops._entity_topk_operands(ents, emb, wd)
+    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
+    filt = _mine_filter(filter_index, emb.shape[0], wd.shape[0], emb.device, 'o' if side == 's' else 's')
+    return emb, wd, ents, k, filt
+
+
+def complete_entities(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True):
+    """What is this entity missing?  For every entity ``a`` of ``entities`` (any order, repeats allowed) the ``k`` most likely new
+    facts around it over ALL relations at once: ``side='s'`` the facts (a, r, x), ``side='o'`` the facts (x, r, a), scored as
+    ``predict_topk`` scores the queries (a, r) in that direction (logit = (e_a * w_r) . e_x + flow_log_prob: the query entity's row
+    carries w_r on both sides).  With a ``FilterIndex`` the known facts are left out -- direction 'o' for ``side='s'``, 's' for
+    ``side='o'`` -- and with ``exclude_self`` the loops (a, r, a).  One fused launch pair (ops.entity_topk_scores) keeps one list
+    per entity while the relations are walked.  Returns ``(rel int64 (m, k), other int64 (m, k), logits float32 (m, k))`` in the
+    order of ``complete_entities_from_scores``: best first, ties by relation, then by entity; rows with fewer than k candidates
+    end in -1 / -1 / -inf.  1 <= k <= 128."""
+    emb, wd, ents, k, (lo, hi, ent) = _complete_args(embedding, w, entities, k, side, filter_index)
+    return ops.entity_topk_scores(ents, emb, wd, k, _mine_bias(flow_log_prob, emb.device), lo, hi, ent, exclude_self)
+
+
+def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True):
+    """``complete_entities`` from materialised logits: per relation ``ops.mul`` + ``ops.gemm`` into a (rows, R, N) tensor, then
+    ``complete_entities_from_scores``, ``COMPLETE_UNFUSED_ELEMS`` logits at a time.  The in-repo cross-check and the bench's
+    baseline, never a fallback."""
+    emb, wd, ents, k, (lo, hi, ent) = _complete_args(embedding, w, entities, k, side, filter_index)
+    emb, wd = emb.contiguous(), wd.contiguous()
+    n, num_rels = emb.shape[0], wd.shape[0]
+    bias = _mine_bias(flow_log_prob, emb.device)
+    rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
+    out = []
+    for at in range(0, ents.numel(), rows):
+        part = ents[at:at + rows].long()
+        ea = emb[part].contiguous()
+        score = torch.stack([ops.gemm(ops.mul(ea, wd[r].expand_as(ea).contiguous()), emb, trans_b=True, precision='f32')
+                             for r in range(num_rels)], dim=1)
+        if bias is not None:
+            score = score + bias
+        out.append(complete_entities_from_scores(score, part, k, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self))
+    if not out:
+        z = torch.zeros(0, k, dtype=torch.int64, device=emb.device)
+        return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=emb.device)
+    return tuple(torch.cat(t) for t in zip(*out))
 
 
 # ---- type-correct completions on the Monte-Carlo posterior predictive ---------------------------------------------------------

@@ -13,6 +13,7 @@ Differences from the reference, all forced by its own crashes or by the device:
   * ``--gpu`` must name a ROCm device: there is no CPU path.
 """
 import argparse
+import os
 import time
 
 import numpy as np
@@ -165,6 +166,52 @@ def write_mc_predictions(path, z, w, triplets, k, filter_index, flow_log_probs=N
     return n
 
 
+PROFILE_ROWS = 4096      # entities per ranking.complete_entities call of write_entity_profiles (bounds the host-side lists)
+
+
+def profile_entities_arg(spec, num_nodes):
+    """The entities of ``--profile-entities``: None is every entity, else comma-separated ids or the path of a file with one id
+    per line (blank lines skipped).  Ids are kept as given, in order, repeats included; one outside [0, num_nodes) is refused."""
+    if spec is None:
+        return list(range(num_nodes))
+    if os.path.isfile(spec):
+        with open(spec) as f:
+            fields = [line.strip() for line in f if line.strip()]
+    else:
+        fields = [x.strip() for x in spec.split(',') if x.strip()]
+    try:
+        ids = [int(x) for x in fields]
+    except ValueError:
+        raise ValueError(f'--profile-entities takes comma-separated entity ids or a file with one id per line, got {spec!r}') from None
+    bad = [i for i in ids if not 0 <= i < num_nodes]
+    if bad:
+        raise ValueError(f'--profile-entities: entity {bad[0]} lies outside [0, {num_nodes})')
+    return ids
+
+
+def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None):
+    """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  logit  probability``: for every entity of
+    ``entities`` its ``k`` most likely new facts over all relations (ranking.complete_entities; ``filter_index``: the known ones
+    left out, as are loops), best first with the rank counted from 1 -- the 's' lines are the facts (entity, relation, other),
+    then the 'o' lines the facts (other, relation, entity).  An entity with fewer than k candidates has fewer lines.  Returns the
+    number of lines written."""
+    n_lines = 0
+    ents = torch.as_tensor(entities, dtype=torch.long, device=embed.device).reshape(-1)
+    with torch.no_grad(), open(path, 'w') as f:
+        for side in ('s', 'o'):
+            for at in range(0, ents.numel(), PROFILE_ROWS):
+                part = ents[at:at + PROFILE_ROWS]
+                rel, other, logits = ranking.complete_entities(embed, w, part, k, side=side, filter_index=filter_index,
+                                                               flow_log_prob=flow_log_prob)
+                prob = torch.sigmoid(logits)
+                for a, rs, xs, ls, ps in zip(part.tolist(), rel.tolist(), other.tolist(), logits.tolist(), prob.tolist()):
+                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{l:.9g}\t{p:.9g}\n"
+                             for i, (r, x, l, p) in enumerate(zip(rs, xs, ls, ps), 1) if r >= 0]
+                    f.writelines(lines)
+                    n_lines += len(lines)
+    return n_lines
+
+
 def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None, type_constraint=None):
     """Knowledge-graph completion as TSV, ``s  r  o  rank  logit``: the new triplets (``filter_index``: the known ones left out,
     s != o) that ``ranking.mine_triplets`` selects among ALL N x R x N -- the ``k`` most confident and / or those whose
@@ -217,7 +264,10 @@ def _write_triplets(path, trip, logits):
 
 def check_args(args):
     """Flag combinations that are refused before anything is loaded."""
-    wants = [f for f, on in (('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
+    if not 0 <= getattr(args, 'profile_topk', 0) <= ops.TOPK_MAX:
+        raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
+    wants = [f for f, on in (('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
+                             ('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
                              ('--complete-threshold', getattr(args, 'complete_threshold', None) is not None),
                              ('--sample-graph', getattr(args, 'sample_graph', 0) > 0)) if on]
     if wants and args.test_mode is not True:
@@ -316,6 +366,14 @@ def main(args):
                                         model.encoder.get_flow_log_prob(), types)
             print(f"wrote {n_lines} predictions (top {args.predict_topk}, both directions, known triplets filtered) to "
                   f"{args.predict_out}")
+        if getattr(args, 'profile_topk', 0) > 0:
+            known = filters if filters is not None else \
+                ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            who = profile_entities_arg(getattr(args, 'profile_entities', None), num_nodes)
+            n_lines = write_entity_profiles(args.profile_out, embed, model.w_relation, who, args.profile_topk, known,
+                                            model.encoder.get_flow_log_prob())
+            print(f"wrote {n_lines} new facts around {len(who)} entities (top {args.profile_topk} over all relations, as subject "
+                  f"and as object, known triplets filtered) to {args.profile_out}")
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -557,6 +615,16 @@ def build_parser():
     p.add_argument("--mc-complete-out", type=str, default="mc_completions.tsv",
                    help="TSV of --mc-complete: subject, relation, object, rank (the columns of --complete-out), then the mean and "
                         "the standard deviation over the samples of the triplet's probability")
+    p.add_argument("--profile-topk", type=int, default=0,
+                   help="with --test-mode: for every entity of --profile-entities write its K most likely NEW facts over all "
+                        "relations at once, the entity as subject and as object (train + valid + test triplets and loops left "
+                        "out), to --profile-out; 1..128, 0 = off; not a reference flag")
+    p.add_argument("--profile-entities", type=str, default=None,
+                   help="the entities of --profile-topk: comma-separated ids, or a file with one id per line; default: every "
+                        "entity")
+    p.add_argument("--profile-out", type=str, default="profiles.tsv",
+                   help="TSV of --profile-topk: entity, side (s: the entity is the subject, o: the object), relation, other "
+                        "entity, rank from 1, logit, probability")
     p.add_argument("--sample-graph", type=int, default=0,
                    help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
                         "confident triplets among them to --sample-out; 0 = off")

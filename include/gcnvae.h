@@ -565,6 +565,28 @@ int gv_topk_scores_constrained(const float* q, int ld_q, const float* e, int ld_
                                const int32_t* cand_set, int k, int* out_ids, float* out_logits, void* workspace, int m, int v, int h,
                                void* stream);
 
+/* Per-entity completion: for each of m query entities a = ents[i] the k best pairs (r, x), r in [0, num_rels), x in [0, n), under
+ *   logit[i, r, x] = (e[a] * w[r]) . e[x] (+ *bias)     -- gv_gemm_f32(gv_mul(e[a], w[r]), e^T) + bias bit for bit, the value
+ *                                                          gv_topk_scores and gv_mine_scores produce
+ * in one list per entity: neither the (entity x relation) query matrix nor per-relation results are stored.  e (n, h) and
+ * w (num_rels, h) row-major fp32, ents int32 [m] (may repeat, any order; an id outside [0, n) gives an all-padding row).
+ * No candidates: the ids filt_ent[filt_lo[a * num_rels + r] .. filt_hi[a * num_rels + r]) of relation r -- the (lo, hi, ent) form
+ * of gv_topk_scores with one range per key a * num_rels + r (n * num_rels of them), each clamped into [0, n_filt_ent); all three
+ * NULL: no filter -- and x == a when exclude_self is set.
+ * Order, a strict total one: the key ordered_u32(logit) << 32 | ~(r * n + x) of gv_topk_scores, i.e. logit descending, then
+ * relation ascending, then entity ascending; NaN after every number; -0 reported as +0, every NaN as the quiet NaN 0x7fc00000.
+ * out_rel / out_ent int32 [m, k], out_logits fp32 [m, k]; a row with fewer than k candidates is padded with -1 / -1 / -inf.
+ * 1 <= k <= 128, n * num_rels < 2^31 (refused otherwise), any m >= 0 (0: nothing launched).  A workgroup owns 64 query entities
+ * and span_tiles consecutive (relation, 64-column tile) pairs of the r-major sequence; span_tiles = 0 takes the library's rule,
+ * for which gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k) sizes the workspace; with span_tiles > 0 the caller provides
+ * m * ceil(num_rels * ceil(n / 64) / span_tiles) * k * 8 bytes.  workspace_bytes is checked against what the launch needs.  The
+ * result does not depend on span_tiles.  Integer arithmetic only outside the scores; no atomics. */
+int64_t gv_entity_topk_scores_workspace_bytes(int m, int n, int num_rels, int k);
+int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                          const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int exclude_self, int k,
+                          int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
+                          int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+
 /* Monte-Carlo posterior-predictive ranking and top-k for a variational encoder: S posterior samples instead of one draw.
  * Sample s has a query matrix Q_s (m, h) at q + s * q_stride and an entity table E_s (v, h) at e + s * e_stride (strides in
  * elements; the leading dimensions ld_q / ld_e are shared by the samples) and an optional bias[s] (that draw's flow_log_prob;

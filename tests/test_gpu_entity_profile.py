@@ -1,0 +1,204 @@
+"""Per-entity completion on the GPU (gv_entity_topk_scores / ops.entity_topk_scores / ranking.complete_entities): the fused route
+against the materialised one (per relation ops.mul + ops.gemm, ordered by ranking.complete_entities_from_scores) and against the
+merge over relations of ranking.predict_topk -- ids equal, logit bits equal; ops.gemm itself is held to float64 by
+tests/test_gpu_gemm.py, so there is no tolerance here.  pytest -m gpu."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(150, 3, 20), (70, 7, 37), (200, 1, 200), (130, 5, 260)]      # (N, R, h): N % 64 != 0; h % 4 != 0, h % 16 != 0; h of 17 k-chunks
+FLP = 0.37
+
+
+def _same(a, b):
+    """Bit-for-bit equality of (rel, other, logits) triples."""
+    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
+
+
+@functools.lru_cache(maxsize=None)
+def _tables(n, num_rels, h):
+    gen = torch.Generator().manual_seed(n * 31 + num_rels * 7 + h)
+    emb = (torch.randn(n, h, generator=gen) * 0.5).cuda()
+    w = torch.randn(num_rels, h, generator=gen).cuda()
+    trip = torch.stack([torch.randint(0, n, (n * num_rels // 2,), generator=gen),
+                        torch.randint(0, num_rels, (n * num_rels // 2,), generator=gen),
+                        torch.randint(0, n, (n * num_rels // 2,), generator=gen)], 1)
+    perm = torch.randperm(n, generator=gen)
+    return emb, w, trip, perm
+
+
+def _entities(perm, m):
+    """m query entities: out of order, and with a repeat as soon as there are three."""
+    ents = perm[:m].clone()
+    if m >= 3:
+        ents[m // 2] = ents[0]
+    return ents.cuda()
+
+
+@pytest.mark.parametrize('flp', [None, FLP])
+@pytest.mark.parametrize('filtered', [False, True])
+@pytest.mark.parametrize('side', ['s', 'o'])
+@pytest.mark.parametrize('n,num_rels,h', SHAPES)
+def test_fused_equals_unfused_exactly(n, num_rels, h, side, filtered, flp):
+    from gcn_vae_amd import ranking
+    emb, w, trip, perm = _tables(n, num_rels, h)
+    fi = ranking.FilterIndex(n, num_rels, trip, device='cuda') if filtered else None
+    bias = None if flp is None else torch.tensor(flp, device='cuda')
+    for m in (1, 64, 65, n):
+        ents = _entities(perm, m)
+        for k in (1, 10, 128):
+            got = ranking.complete_entities(emb, w, ents, k, side=side, filter_index=fi, flow_log_prob=bias)
+            want = ranking.complete_entities_unfused(emb, w, ents, k, side=side, filter_index=fi, flow_log_prob=bias)
+            assert got[0].shape == (m, k) and got[0].dtype == torch.int64 and got[2].dtype == torch.float32
+            assert _same(got, want), (m, k)
+    # the list is new facts only: no known triplet, no loop
+    if filtered:
+        rel, other, _ = got
+        a = ents.view(-1, 1).expand_as(rel)
+        s, o = (a, other) if side == 's' else (other, a)
+        known = {tuple(t) for t in trip.tolist()}
+        listed = {t for t in zip(s.flatten().tolist(), rel.flatten().tolist(), o.flatten().tolist()) if t[1] >= 0}
+        assert not (listed & known) and all(x != y for x, _, y in listed)
+
+
+@pytest.mark.parametrize('side', ['s', 'o'])
+@pytest.mark.parametrize('n,num_rels,h', SHAPES)
+def test_fused_equals_the_merge_of_predict_topk(n, num_rels, h, side):
+    """The bit-for-bit claim against the existing entry point: per relation ranking.predict_topk gives each query's k best, and
+    their merge by (logit, r, x) is the entity's list (exclude_self off: predict_topk keeps the loops)."""
+    from gcn_vae_amd import ranking
+    emb, w, trip, perm = _tables(n, num_rels, h)
+    fi = ranking.FilterIndex(n, num_rels, trip, device='cuda')
+    ents, k = _entities(perm, 65), 10
+    bias = torch.tensor(FLP, device='cuda')
+    pool = torch.zeros(65, num_rels, n, device='cuda')
+    given = torch.zeros(65, num_rels, n, dtype=torch.bool, device='cuda')
+    for r in range(num_rels):
+        ids, logits = ranking.predict_topk(emb, w, ents, torch.full_like(ents, r), k, direction='o' if side == 's' else 's',
+                                           filter_index=fi, flow_log_prob=bias)
+        live = ids >= 0
+        rows = torch.arange(65, device='cuda').view(-1, 1).expand_as(ids)
+        pool[rows[live], r, ids[live]] = logits[live]
+        given[rows[live], r, ids[live]] = True
+    want_ids, want_logits = ranking.topk_from_scores(pool.view(65, -1), k, cand=given.view(65, -1))
+    got = ranking.complete_entities(emb, w, ents, k, side=side, filter_index=fi, flow_log_prob=bias, exclude_self=False)
+    assert torch.equal(got[0] * n + got[1], want_ids) and torch.equal(got[2].view(torch.int32), want_logits.view(torch.int32))
+
+
+def _dyadic_case():
+    """Small-integer tables: every logit is an exact integer, relations 0 and 2 are the same row of w (equal logits across
+    relations), entities 3 and 90 the same row of emb (equal logits inside a relation, 64-column tiles apart)."""
+    gen = torch.Generator().manual_seed(5)
+    n, num_rels, h = 150, 4, 6
+    emb = torch.randint(-2, 3, (n, h), generator=gen).float()
+    emb[90] = emb[3]
+    w = torch.randint(-1, 2, (num_rels, h), generator=gen).float()
+    w[2] = w[0]
+    score = torch.einsum('ah,rh,xh->arx', emb.double(), w.double(), emb.double()).float()      # exact: integers below 2^24
+    return emb.cuda(), w.cuda(), score
+
+
+@pytest.mark.parametrize('span', [None, 1, 2, 5, 12])
+def test_dyadic_tables_tie_across_relations_and_span_boundaries(span):
+    """N = 150 is three column tiles, so the 12 (relation, tile) pairs are cut into 1, 3, 6 and 12 spans by the override (span = 5
+    cuts inside relations 1 and 3); the library's own rule gives one span here.  The order must be the rule's in every cut."""
+    from gcn_vae_amd import ops, ranking
+    emb, w, score = _dyadic_case()
+    ents = torch.tensor([7, 3, 149, 90, 3, 64, 0], device='cuda')
+    for k in (1, 10, 128):
+        for excl in (True, False):
+            want = ranking.complete_entities_from_scores(score[ents.cpu()], ents.cpu(), k, exclude_self=excl)
+            got = ops.entity_topk_scores(ents, emb, w, k, exclude_self=excl, span=span)
+            assert _same(tuple(t.cpu() for t in got), want), (k, excl)
+    rel = got[0].cpu()
+    assert (want[2][:, :-1] == want[2][:, 1:]).any() and len(rel.unique()) == 4      # ties are there, every relation shows up
+
+
+@pytest.mark.parametrize('n,num_rels,h,k', [(150, 3, 20, 10), (130, 5, 260, 128), (70, 7, 37, 128)])
+def test_result_does_not_depend_on_the_span_geometry(n, num_rels, h, k):
+    from gcn_vae_amd import ops, ranking
+    emb, w, trip, perm = _tables(n, num_rels, h)
+    lo, hi, ent = ranking._mine_filter(ranking.FilterIndex(n, num_rels, trip, device='cuda'), n, num_rels, emb.device)
+    ents = _entities(perm, 65)
+    base = ops.entity_topk_scores(ents, emb, w, k, None, lo, hi, ent)
+    for span in (1, 2, 4, 7, 10 ** 6):
+        assert _same(ops.entity_topk_scores(ents, emb, w, k, None, lo, hi, ent, span=span), base), span
+
+
+def test_padding_past_the_last_candidate():
+    from gcn_vae_amd import ranking
+    gen = torch.Generator().manual_seed(3)
+    emb, w = torch.randn(5, 9, generator=gen).cuda(), torch.randn(1, 9, generator=gen).cuda()
+    ents = torch.arange(5, device='cuda')
+    rel, other, logits = ranking.complete_entities(emb, w, ents, 10)                 # 4 candidates each: the loops are out
+    assert (rel[:, :4] == 0).all() and (rel[:, 4:] == -1).all() and (other[:, 4:] == -1).all()
+    assert torch.isinf(logits[:, 4:]).all() and (logits[:, 4:] < 0).all()
+    assert all(sorted(other[i, :4].tolist()) == [x for x in range(5) if x != i] for i in range(5))
+    assert _same((rel, other, logits), ranking.complete_entities_unfused(emb, w, ents, 10))
+    rel, _, _ = ranking.complete_entities(emb, w, ents, 10, exclude_self=False)
+    assert (rel[:, :5] == 0).all() and (rel[:, 5:] == -1).all()
+    empty = ranking.complete_entities(emb, w, ents[:0], 10)
+    assert empty[0].shape == (0, 10) and empty[2].shape == (0, 10)
+
+
+def test_a_relation_whose_filter_lists_every_entity_contributes_nothing():
+    from gcn_vae_amd import ranking
+    n, num_rels, h = 150, 3, 20
+    emb, w, _, perm = _tables(n, num_rels, h)
+    everybody = torch.cartesian_prod(torch.arange(n), torch.tensor([1]), torch.arange(n))      # every (s, 1, o)
+    fi = ranking.FilterIndex(n, num_rels, everybody, device='cuda')
+    ents = _entities(perm, 70)
+    for side in ('s', 'o'):
+        got = ranking.complete_entities(emb, w, ents, 128, side=side, filter_index=fi)
+        assert not (got[0] == 1).any() and (got[0] >= 0).all()
+        assert _same(got, ranking.complete_entities_unfused(emb, w, ents, 128, side=side, filter_index=fi))
+
+
+def test_cli_writes_the_entity_profiles(tmp_path, monkeypatch):
+    from gcn_vae_amd import ranking, train
+    from gcn_vae_amd.encoders import KGVAE
+    spec = 'synthetic:60:4:400:40:40'
+    kg = __import__('gcn_vae_amd.data', fromlist=['load_data']).load_data(spec)
+    torch.manual_seed(0)
+    net = train.LinkPredict(KGVAE, kg.num_nodes, 16, kg.num_rels, num_bases=4, num_hidden_layers=1, dropout=0.0,
+                            use_cuda=True, reg_param=0.01, kl_param=1e-3, mmd_param=0.0, k=4, n_flows=2).cuda()
+    ckpt, out = str(tmp_path / 'm.pth'), str(tmp_path / 'profiles.tsv')
+    torch.save({'state_dict': train.host_state_dict(net), 'epoch': 0}, ckpt)
+    seen = []
+    real = ranking.complete_entities
+
+    def spy(*args, **kwargs):
+        res = real(*args, **kwargs)
+        seen.append((kwargs['side'], args[2].tolist(), res))
+        return res
+    monkeypatch.setattr(ranking, 'complete_entities', spy)
+    who, k = [3, 59, 3, 0], 5
+    args = train.build_parser().parse_args(['-d', spec, '--gpu', '0', '--n-hidden', '16', '--n-bases', '4', '--n-layers', '1',
+                                            '--mog-k', '4', '--n-flows', '2', '--test-mode', 'True', '--model-state-file', ckpt,
+                                            '--profile-topk', str(k), '--profile-entities', ','.join(map(str, who)),
+                                            '--profile-out', out])
+    train.main(args)
+    rows = [line.rstrip('\n').split('\t') for line in open(out)]
+    assert [s for s, _, _ in seen] == ['s', 'o'] and all(e == who for _, e, _ in seen)
+    padding = sum(int((res[0] < 0).sum()) for _, _, res in seen)
+    assert len(rows) == 2 * len(who) * k - padding and all(len(row) == 7 for row in rows)
+    known = {tuple(x) for x in np.concatenate([kg.train, kg.valid, kg.test]).tolist()}
+    at = 0
+    for side, ents, res in seen:
+        rel, other, logits = (t.cpu() for t in res)
+        for i, a in enumerate(ents):
+            for j in range(k):
+                if rel[i, j] < 0:
+                    continue
+                ent, sd, r, x, rank, logit, prob = rows[at]
+                at += 1
+                assert (int(ent), sd, int(r), int(x), int(rank)) == (a, side, int(rel[i, j]), int(other[i, j]), j + 1)
+                assert np.float32(logit) == logits[i, j].numpy()                      # nine digits give the float32 back
+                assert abs(float(prob) - torch.sigmoid(logits[i, j]).item()) < 1e-6
+                fact = (a, int(r), int(x)) if side == 's' else (int(x), int(r), a)
+                assert fact not in known and int(x) != a
+    assert at == len(rows)
