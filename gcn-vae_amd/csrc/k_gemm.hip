@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "k_mc.h"
+#include "k_query_args.h"
 #include "k_topk.h"
 
 namespace gv {
@@ -1354,49 +1355,84 @@ static GemmParams score_gemm_params(const float* q, int ld_q, const float* e, in
     return p;
 }
 
-// the launches of the three rankers: gv_rank_scores (count_filt NULL: the raw count alone, no filter word to build),
-// gv_rank_scores_filtered and, with cs.cand, its type-constrained form (the filter optional there)
-static int rank_launch(const char* name, const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
-                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, float* tgt,
-                       int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
-    RankFiltParams fp;
+// ---- Monte-Carlo posterior-predictive ranking and top-k (gv_rank_scores_mc, gv_topk_scores_mc, gv_pair_prob_std_mc) -----------
+// the sample geometry shared by the three entries: n_samples >= 1, and with more than one sample each stride spans its matrix
+static int mc_samples_args(const char* name, const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                           int n_samples, int m, int v, int h, McSamples* mc) {
+    GV_REQUIRE(n_samples >= 1, GV_ERR_SHAPE, "%s: n_samples=%d", name, n_samples);
+    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "%s: leading dimension too small", name);
+    GV_REQUIRE(n_samples == 1 || (q_stride >= (int64_t)(m > 0 ? m - 1 : 0) * ld_q + h && e_stride >= (int64_t)(v - 1) * ld_e + h),
+               GV_ERR_SHAPE, "%s: sample stride shorter than the rows it spans (q_stride=%lld e_stride=%lld)", name,
+               (long long)q_stride, (long long)e_stride);
+    mc->q_stride = n_samples > 1 ? q_stride : 0;
+    mc->e_stride = n_samples > 1 ? e_stride : 0;
+    mc->n_samples = n_samples;
+    mc->inv_s = 1.0f / (float)n_samples;
+    return GV_OK;
+}
+
+// score_gemm_params for sample 0; the 16-byte loads need every sample's base aligned (no samples: strides 0, score_gemm_params')
+static GemmParams mc_gemm_params(const float* q, int ld_q, const float* e, int ld_e, const McSamples& mc, int m, int v, int h) {
+    GemmParams p = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
+    p.vec_a = p.vec_a && mc.q_stride % 4 == 0;
+    p.vec_b = p.vec_b && mc.e_stride % 4 == 0;
+    return p;
+}
+
+// The launches of every ranker; mc.n_samples == 0: not Monte-Carlo.  Pass 0 writes tgt[row], the target's logit or pbar (it does not
+// depend on filter or set); pass 1 votes all its counts on the one value.  Without a filter the filtered counts are not written.
+// Single-sample: gv_rank_scores (no filter, no set) runs the raw count alone, with no filter word to build.
+static int rank_launch(const char* name, const McSamples& mc, const float* q, int ld_q, const float* e, int ld_e, const int* target,
+                       const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                       const TopkCand& cs, float* tgt, int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m,
+                       int v, int h, void* stream) {
+    RankFiltParams fp{};
     RankParams& rp = fp.rp;
-    rp.g = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
+    fp.mc = mc;
+    rp.g = mc_gemm_params(q, ld_q, e, ld_e, mc, m, v, h);
     rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
-    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent; fp.count_filt = count_filt;
+    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent;
+    fp.count_filt = filt_lo ? count_filt : nullptr;
     fp.cs = cs;
-    fp.count_raw_c = count_raw_c; fp.count_filt_c = count_filt_c;
+    fp.count_raw_c = count_raw_c; fp.count_filt_c = filt_lo ? count_filt_c : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    for (int* c : {count_raw, count_filt, count_raw_c, count_filt_c})
+    for (int* c : {count_raw, fp.count_filt, fp.count_raw_c, fp.count_filt_c})
         if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status(name);
     dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
-    hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);           // tgt[row] = the target's logit
-    if (!count_filt && !cs.cand) hipLaunchKernelGGL(k_rank_scores<1>, grid, block, 0, st, rp);
-    else if (cs.cand) hipLaunchKernelGGL(k_rank_scores_filtered<true>, grid, block, 0, st, fp);
-    else hipLaunchKernelGGL(k_rank_scores_filtered<false>, grid, block, 0, st, fp);
+    if (mc.n_samples) {
+        hipLaunchKernelGGL(k_rank_target_mc, grid, block, 0, st, fp);
+        if (cs.cand) hipLaunchKernelGGL((k_rank_scores_filtered<true, true>), grid, block, 0, st, fp);
+        else hipLaunchKernelGGL((k_rank_scores_filtered<false, true>), grid, block, 0, st, fp);
+    } else {
+        hipLaunchKernelGGL(k_rank_scores<0>, grid, block, 0, st, rp);
+        if (!fp.count_filt && !cs.cand) hipLaunchKernelGGL(k_rank_scores<1>, grid, block, 0, st, rp);
+        else if (cs.cand) hipLaunchKernelGGL(k_rank_scores_filtered<true>, grid, block, 0, st, fp);
+        else hipLaunchKernelGGL(k_rank_scores_filtered<false>, grid, block, 0, st, fp);
+    }
     return launch_status(name);
 }
 
 extern "C" int gv_rank_scores(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
                               float* tgt, int* count, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0, GV_ERR_SHAPE, "gv_rank_scores: m=%d v=%d h=%d", m, v, h);
+    const char* name = "gv_rank_scores";
+    GV_CHECK(query_sizes(name, m, v, h));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count, GV_ERR_NULL, "gv_rank_scores: NULL pointer");
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores: leading dimension too small");
-    return rank_launch("gv_rank_scores", q, ld_q, e, ld_e, target, bias, nullptr, nullptr, nullptr, 0, TopkCand{}, tgt, count, nullptr,
+    GV_CHECK(query_pointers(name, q && e && target && tgt && count));
+    GV_CHECK(query_leading(name, ld_q, ld_e, h));
+    return rank_launch(name, McSamples{}, q, ld_q, e, ld_e, target, bias, nullptr, nullptr, nullptr, 0, TopkCand{}, tgt, count, nullptr,
                        nullptr, nullptr, m, v, h, stream);
 }
 
 extern "C" int gv_rank_scores_filtered(const float* q, int ld_q, const float* e, int ld_e, const int* target, const float* bias,
                                        const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, float* tgt,
                                        int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_filtered: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
+    const char* name = "gv_rank_scores_filtered";
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count_filt, GV_ERR_NULL, "gv_rank_scores_filtered: NULL pointer");
+    GV_CHECK(query_pointers(name, q && e && target && tgt && count_filt));
     GV_REQUIRE(filt_lo && filt_hi && filt_ent, GV_ERR_NULL, "gv_rank_scores_filtered: NULL filter pointer");
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_filtered: leading dimension too small");
-    return rank_launch("gv_rank_scores_filtered", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, tgt,
+    GV_CHECK(query_leading(name, ld_q, ld_e, h));
+    return rank_launch(name, McSamples{}, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, tgt,
                        count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
 }
 
@@ -1405,21 +1441,51 @@ extern "C" int gv_rank_scores_constrained(const float* q, int ld_q, const float*
                                           const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, float* tgt,
                                           int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h,
                                           void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_constrained: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_rank_scores_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_rank_scores_constrained: leading dimension too small");
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_rank_scores_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_rank_scores_constrained: NULL cand / cand_set");
+    const char* name = "gv_rank_scores_constrained";
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_leading(name, ld_q, ld_e, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count_raw && count_raw_c, GV_ERR_NULL, "gv_rank_scores_constrained: NULL pointer");
-    GV_REQUIRE(!filt_lo || (count_filt && count_filt_c), GV_ERR_NULL, "gv_rank_scores_constrained: a filter needs both filtered counts");
-    const bool f = filt_lo != nullptr;        // without a filter the two filtered counts are not written
-    return rank_launch("gv_rank_scores_constrained", q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
-                       TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, f ? count_filt : nullptr, count_raw_c,
-                       f ? count_filt_c : nullptr, m, v, h, stream);
+    GV_CHECK(query_pointers(name, q && e && target && tgt && count_raw && count_raw_c));
+    GV_CHECK(query_filter_needs(name, filt_lo, count_filt && count_filt_c, "both filtered counts"));
+    return rank_launch(name, McSamples{}, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                       TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, count_filt, count_raw_c, count_filt_c, m, v, h, stream);
+}
+
+extern "C" int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                 const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                                 int n_filt_ent, float* tgt, int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
+    const char* name = "gv_rank_scores_mc";
+    McSamples mc;
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(mc_samples_args(name, q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, q && e && target && tgt && count_raw));
+    GV_CHECK(query_filter_needs(name, filt_lo, count_filt, "count_filt"));
+    return rank_launch(name, mc, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, tgt, count_raw,
+                       count_filt, nullptr, nullptr, m, v, h, stream);
+}
+
+extern "C" int gv_rank_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                                             int n_samples, const int* target, const float* bias, const int* filt_lo,
+                                             const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
+                                             int ld_cand, int n_sets, const int32_t* cand_set, float* tgt, int* count_raw,
+                                             int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
+    const char* name = "gv_rank_scores_mc_constrained";
+    McSamples mc;
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(mc_samples_args(name, q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, q && e && target && tgt && count_raw && count_raw_c));
+    GV_CHECK(query_filter_needs(name, filt_lo, count_filt && count_filt_c, "both filtered counts"));
+    return rank_launch(name, mc, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                       TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, count_filt, count_raw_c, count_filt_c, m, v, h, stream);
 }
 
 extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
@@ -1429,48 +1495,36 @@ extern "C" int64_t gv_topk_scores_workspace_bytes(int m, int v, int k) {
     return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
 }
 
-// the launches of gv_topk_scores, and with cs.cand of its type-constrained form
-template <bool CAND>
-static int topk_scores_launch(const char* name, const float* q, int ld_q, const float* e, int ld_e, const float* bias,
-                              const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
-                              int* out_ids, float* out_logits, void* workspace, int m, int v, int h, void* stream) {
-    TopkParams tp;
-    tp.g = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
+// the launches of gv_topk_scores and its forms: CAND with cs.cand, MC with mc.n_samples > 0 (the running lists: <= 64 KiB of LDS
+// beside 27 KiB static, so only k > 64 needs the limit raised)
+template <bool CAND, bool MC>
+static int topk_launch(const char* name, const McSamples& mc, const float* q, int ld_q, const float* e, int ld_e, const float* bias,
+                       const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
+                       int* out_ids, float* out_values, void* workspace, int m, int v, int h, void* stream) {
+    TopkParams tp{};
+    tp.mc = mc;
+    tp.g = mc_gemm_params(q, ld_q, e, ld_e, mc, m, v, h);
     tp.bias = bias;
     tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
     tp.topk = k;
     topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
     tp.part = (unsigned long long*)workspace;
     tp.cs = cs;
-    hipStream_t st = (hipStream_t)stream;
-    const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 27 KiB static)
-    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
-    const TopkLogitOut out{out_ids, out_logits};
-    if (k <= 64) {
-        hipLaunchKernelGGL((k_topk_span<1, CAND>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_topk_span<2, CAND>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised, name))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_topk_span<2, CAND>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    }
-    return launch_status(name);
+    return topk_span_merge<k_topk_span<1, CAND, MC>, k_topk_span<2, CAND, MC>, false, 64>(
+        name, dim3((m + 63) / 64, tp.n_spans), tp, tp.part, m, tp.n_spans, k, TopkLogitOut{out_ids, out_values}, (hipStream_t)stream);
 }
 
 extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
                               const int* filt_hi, const int* filt_ent, int n_filt_ent, int k, int* out_ids, float* out_logits,
                               void* workspace, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
-               n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores: leading dimension too small");
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    const char* name = "gv_topk_scores";
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(query_leading(name, ld_q, ld_e, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores: NULL pointer");
-    return topk_scores_launch<false>("gv_topk_scores", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
+    GV_CHECK(query_pointers(name, q && e && out_ids && out_logits && workspace));
+    return topk_launch<false, false>(name, McSamples{}, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
                                      out_ids, out_logits, workspace, m, v, h, stream);
 }
 
@@ -1478,19 +1532,65 @@ extern "C" int gv_topk_scores_constrained(const float* q, int ld_q, const float*
                                           const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand,
                                           int n_sets, const int32_t* cand_set, int k, int* out_ids, float* out_logits,
                                           void* workspace, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_constrained: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_topk_scores_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "gv_topk_scores_constrained: leading dimension too small");
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_topk_scores_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_topk_scores_constrained: NULL cand / cand_set");
+    const char* name = "gv_topk_scores_constrained";
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_leading(name, ld_q, ld_e, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && out_ids && out_logits && workspace, GV_ERR_NULL, "gv_topk_scores_constrained: NULL pointer");
-    return topk_scores_launch<true>("gv_topk_scores_constrained", q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+    GV_CHECK(query_pointers(name, q && e && out_ids && out_logits && workspace));
+    return topk_launch<true, false>(name, McSamples{}, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_logits, workspace, m, v, h, stream);
+}
+
+extern "C" int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                 const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int k,
+                                 int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream) {
+    const char* name = "gv_topk_scores_mc";
+    McSamples mc;
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(mc_samples_args(name, q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, q && e && out_ids && out_prob && workspace));
+    return topk_launch<false, true>(name, mc, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k, out_ids,
+                                    out_prob, workspace, m, v, h, stream);
+}
+
+extern "C" int gv_topk_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
+                                             int n_samples, const float* bias, const int* filt_lo, const int* filt_hi,
+                                             const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand, int n_sets,
+                                             const int32_t* cand_set, int k, int* out_ids, float* out_prob, void* workspace, int m,
+                                             int v, int h, void* stream) {
+    const char* name = "gv_topk_scores_mc_constrained";
+    McSamples mc;
+    GV_CHECK(query_sizes(name, m, v, h, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(mc_samples_args(name, q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, q && e && out_ids && out_prob && workspace));
+    return topk_launch<true, true>(name, mc, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                                   TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_prob, workspace, m, v, h, stream);
+}
+
+extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                   const float* bias, const int* ids, int k, float* out_std, int m, int v, int h, void* stream) {
+    const char* name = "gv_pair_prob_std_mc";
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && k >= 1, GV_ERR_SHAPE, "gv_pair_prob_std_mc: m=%d v=%d h=%d k=%d", m, v, h, k);
+    McSamples mc;
+    GV_CHECK(mc_samples_args(name, q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, q && e && ids && out_std));
+    const long long pairs = (long long)m * k;
+    hipLaunchKernelGGL(k_pair_prob_std_mc, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, ld_q, e, ld_e,
+                       mc, bias, ids, out_std, pairs, k, v, h);
+    return launch_status(name);
 }
 
 // ---- per-entity completion (gv_entity_topk_scores) ------------------------------------------------------------------------------
@@ -1516,13 +1616,12 @@ extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e,
                "gv_entity_topk_scores: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", m, n, num_rels, h, n_filt_ent);
     GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "gv_entity_topk_scores: n * num_rels = %lld does not fit 31 bits",
                (long long)n * num_rels);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_entity_topk_scores: k=%d outside [1, %d]", k, TOPK_MAX);
+    GV_CHECK(query_k(name, k));
     GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "gv_entity_topk_scores: span_tiles=%d (0: the library's rule)", span_tiles);
-    GV_REQUIRE(ld_e >= h && ld_w >= h, GV_ERR_SHAPE, "gv_entity_topk_scores: leading dimension too small");
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_entity_topk_scores: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(ents && e && w && out_rel && out_ent && out_logits && workspace, GV_ERR_NULL, "gv_entity_topk_scores: NULL pointer");
+    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_logits && workspace));
     EntityTopkParams ep;
     ep.g = score_gemm_params(nullptr, ld_e, e, ld_e, m, n, h);
     ep.ents = ents; ep.w = w; ep.ld_w = ld_w;
@@ -1544,192 +1643,9 @@ extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e,
     GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "gv_entity_topk_scores: workspace of %lld bytes, %lld needed",
                (long long)workspace_bytes, (long long)need);
     ep.part = (unsigned long long*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const int lds = 64 * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 28 KiB static)
-    dim3 grid((m + 63) / 64, ep.n_spans), block(256), mgrid((m + 3) / 4);
-    const EntityTopkOut out{out_rel, out_ent, out_logits, n};
-    if (k <= 64) {
-        hipLaunchKernelGGL((k_entity_topk_span<1>), grid, block, lds, st, ep);
-        hipLaunchKernelGGL((k_topk_merge<1, EntityTopkOut>), mgrid, block, 0, st, ep.part, m, ep.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_entity_topk_span<2>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised, name))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_entity_topk_span<2>), grid, block, lds, st, ep);
-        hipLaunchKernelGGL((k_topk_merge<2, EntityTopkOut>), mgrid, block, 0, st, ep.part, m, ep.n_spans, k, out);
-    }
-    return launch_status(name);
-}
-
-// ---- Monte-Carlo posterior-predictive ranking and top-k (gv_rank_scores_mc, gv_topk_scores_mc, gv_pair_prob_std_mc) -----------
-// the sample geometry shared by the three entries: n_samples >= 1, and with more than one sample each stride spans its matrix
-static int mc_samples_args(const char* name, const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
-                           int n_samples, int m, int v, int h, McSamples* mc) {
-    GV_REQUIRE(n_samples >= 1, GV_ERR_SHAPE, "%s: n_samples=%d", name, n_samples);
-    GV_REQUIRE(ld_q >= h && ld_e >= h, GV_ERR_SHAPE, "%s: leading dimension too small", name);
-    GV_REQUIRE(n_samples == 1 || (q_stride >= (int64_t)(m > 0 ? m - 1 : 0) * ld_q + h && e_stride >= (int64_t)(v - 1) * ld_e + h),
-               GV_ERR_SHAPE, "%s: sample stride shorter than the rows it spans (q_stride=%lld e_stride=%lld)", name,
-               (long long)q_stride, (long long)e_stride);
-    mc->q_stride = n_samples > 1 ? q_stride : 0;
-    mc->e_stride = n_samples > 1 ? e_stride : 0;
-    mc->n_samples = n_samples;
-    mc->inv_s = 1.0f / (float)n_samples;
-    return GV_OK;
-}
-
-// score_gemm_params for sample 0; the 16-byte loads need every sample's base aligned
-static GemmParams mc_gemm_params(const float* q, int ld_q, const float* e, int ld_e, const McSamples& mc, int m, int v, int h) {
-    GemmParams p = score_gemm_params(q, ld_q, e, ld_e, m, v, h);
-    p.vec_a = p.vec_a && mc.q_stride % 4 == 0;
-    p.vec_b = p.vec_b && mc.e_stride % 4 == 0;
-    return p;
-}
-
-// the launches of gv_rank_scores_mc and, with cs.cand, of its type-constrained form: pass 0 is shared (the target's pbar does not
-// depend on the set), pass 1 votes all its counts on the one pbar of mc_pbar_tile
-static int rank_mc_launch(const char* name, RankFiltParams& fp, const float* q, int ld_q, const float* e, int ld_e, const int* target,
-                          const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
-                          const TopkCand& cs, float* tgt, int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int m,
-                          int v, int h, void* stream) {
-    RankParams& rp = fp.rp;
-    rp.g = mc_gemm_params(q, ld_q, e, ld_e, fp.mc, m, v, h);
-    rp.target = target; rp.bias = bias; rp.tgt = tgt; rp.count = count_raw;
-    fp.filt_lo = filt_lo; fp.filt_hi = filt_hi; fp.filt_ent = filt_ent; fp.n_ent = n_filt_ent;
-    fp.count_filt = filt_lo ? count_filt : nullptr;          // without a filter the filtered counts are not written
-    fp.cs = cs;
-    fp.count_raw_c = count_raw_c; fp.count_filt_c = filt_lo ? count_filt_c : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    for (int* c : {count_raw, fp.count_filt, fp.count_raw_c, fp.count_filt_c})
-        if (c && fill_words(c, 0u, (size_t)m * sizeof(int), st) != hipSuccess) return launch_status(name);
-    dim3 grid((v + 63) / 64, (m + 63) / 64), block(256);
-    hipLaunchKernelGGL(k_rank_target_mc, grid, block, 0, st, fp);                        // tgt[row] = the target's pbar
-    if (cs.cand) hipLaunchKernelGGL((k_rank_scores_filtered<true, true>), grid, block, 0, st, fp);
-    else hipLaunchKernelGGL((k_rank_scores_filtered<false, true>), grid, block, 0, st, fp);
-    return launch_status(name);
-}
-
-extern "C" int gv_rank_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
-                                 const int* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
-                                 int n_filt_ent, float* tgt, int* count_raw, int* count_filt, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_mc: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
-               n_filt_ent);
-    RankFiltParams fp{};
-    const int rc = mc_samples_args("gv_rank_scores_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &fp.mc);
-    if (rc != GV_OK) return rc;
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_rank_scores_mc: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count_raw, GV_ERR_NULL, "gv_rank_scores_mc: NULL pointer");
-    GV_REQUIRE(!filt_lo || count_filt, GV_ERR_NULL, "gv_rank_scores_mc: a filter needs count_filt");
-    return rank_mc_launch("gv_rank_scores_mc", fp, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{},
-                          tgt, count_raw, count_filt, nullptr, nullptr, m, v, h, stream);
-}
-
-extern "C" int gv_rank_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
-                                             int n_samples, const int* target, const float* bias, const int* filt_lo,
-                                             const int* filt_hi, const int* filt_ent, int n_filt_ent, const uint32_t* cand,
-                                             int ld_cand, int n_sets, const int32_t* cand_set, float* tgt, int* count_raw,
-                                             int* count_filt, int* count_raw_c, int* count_filt_c, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_rank_scores_mc_constrained: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
-    RankFiltParams fp{};
-    const int rc = mc_samples_args("gv_rank_scores_mc_constrained", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &fp.mc);
-    if (rc != GV_OK) return rc;
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_rank_scores_mc_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_rank_scores_mc_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_rank_scores_mc_constrained: NULL cand / cand_set");
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && target && tgt && count_raw && count_raw_c, GV_ERR_NULL, "gv_rank_scores_mc_constrained: NULL pointer");
-    GV_REQUIRE(!filt_lo || (count_filt && count_filt_c), GV_ERR_NULL,
-               "gv_rank_scores_mc_constrained: a filter needs both filtered counts");
-    return rank_mc_launch("gv_rank_scores_mc_constrained", fp, q, ld_q, e, ld_e, target, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
-                          TopkCand{cand, cand_set, ld_cand, n_sets}, tgt, count_raw, count_filt, count_raw_c, count_filt_c, m, v, h,
-                          stream);
-}
-
-// the launches of gv_topk_scores_mc, and with cs.cand of its type-constrained form
-template <bool CAND>
-static int topk_mc_launch(const char* name, TopkParams& tp, const float* q, int ld_q, const float* e, int ld_e, const float* bias,
-                          const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const TopkCand& cs, int k,
-                          int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream) {
-    tp.g = mc_gemm_params(q, ld_q, e, ld_e, tp.mc, m, v, h);
-    tp.bias = bias;
-    tp.filt_lo = filt_lo; tp.filt_hi = filt_hi; tp.filt_ent = filt_ent; tp.n_ent = n_filt_ent;
-    tp.topk = k;
-    topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
-    tp.part = (unsigned long long*)workspace;
-    tp.cs = cs;
-    hipStream_t st = (hipStream_t)stream;
-    const int lds = 64 * k * (int)sizeof(unsigned long long);
-    dim3 grid((m + 63) / 64, tp.n_spans), block(256), mgrid((m + 3) / 4);
-    const TopkLogitOut out{out_ids, out_prob};
-    if (k <= 64) {
-        hipLaunchKernelGGL((k_topk_span<1, CAND, true>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<1, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_topk_span<2, CAND, true>, 64 * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
-                               name))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_topk_span<2, CAND, true>), grid, block, lds, st, tp);
-        hipLaunchKernelGGL((k_topk_merge<2, TopkLogitOut>), mgrid, block, 0, st, tp.part, m, tp.n_spans, k, out);
-    }
-    return launch_status(name);
-}
-
-extern "C" int gv_topk_scores_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
-                                 const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int k,
-                                 int* out_ids, float* out_prob, void* workspace, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_mc: m=%d v=%d h=%d n_filt_ent=%d", m, v, h,
-               n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_mc: k=%d outside [1, %d]", k, TOPK_MAX);
-    TopkParams tp{};
-    const int rc = mc_samples_args("gv_topk_scores_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &tp.mc);
-    if (rc != GV_OK) return rc;
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_topk_scores_mc: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && out_ids && out_prob && workspace, GV_ERR_NULL, "gv_topk_scores_mc: NULL pointer");
-    return topk_mc_launch<false>("gv_topk_scores_mc", tp, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
-                                 out_ids, out_prob, workspace, m, v, h, stream);
-}
-
-extern "C" int gv_topk_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride,
-                                             int n_samples, const float* bias, const int* filt_lo, const int* filt_hi,
-                                             const int* filt_ent, int n_filt_ent, const uint32_t* cand, int ld_cand, int n_sets,
-                                             const int32_t* cand_set, int k, int* out_ids, float* out_prob, void* workspace, int m,
-                                             int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: m=%d v=%d h=%d n_filt_ent=%d",
-               m, v, h, n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
-    TopkParams tp{};
-    const int rc = mc_samples_args("gv_topk_scores_mc_constrained", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &tp.mc);
-    if (rc != GV_OK) return rc;
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_topk_scores_mc_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_topk_scores_mc_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_topk_scores_mc_constrained: NULL cand / cand_set");
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && out_ids && out_prob && workspace, GV_ERR_NULL, "gv_topk_scores_mc_constrained: NULL pointer");
-    return topk_mc_launch<true>("gv_topk_scores_mc_constrained", tp, q, ld_q, e, ld_e, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
-                                TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_prob, workspace, m, v, h, stream);
-}
-
-extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, const float* e, int ld_e, int64_t e_stride, int n_samples,
-                                   const float* bias, const int* ids, int k, float* out_std, int m, int v, int h, void* stream) {
-    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && k >= 1, GV_ERR_SHAPE, "gv_pair_prob_std_mc: m=%d v=%d h=%d k=%d", m, v, h, k);
-    McSamples mc;
-    const int rc = mc_samples_args("gv_pair_prob_std_mc", q, ld_q, q_stride, e, ld_e, e_stride, n_samples, m, v, h, &mc);
-    if (rc != GV_OK) return rc;
-    if (m == 0) return GV_OK;
-    GV_REQUIRE(q && e && ids && out_std, GV_ERR_NULL, "gv_pair_prob_std_mc: NULL pointer");
-    const long long pairs = (long long)m * k;
-    hipLaunchKernelGGL(k_pair_prob_std_mc, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, ld_q, e, ld_e,
-                       mc, bias, ids, out_std, pairs, k, v, h);
-    return launch_status("gv_pair_prob_std_mc");
+    return topk_span_merge<k_entity_topk_span<1>, k_entity_topk_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
+        name, dim3((m + 63) / 64, ep.n_spans), ep, ep.part, m, ep.n_spans, k, EntityTopkOut{out_rel, out_ent, out_logits, n},
+        (hipStream_t)stream);
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

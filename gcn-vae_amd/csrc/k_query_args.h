@@ -1,0 +1,66 @@
+// The argument checks the entity-query entries share (host only): gv_rank_scores* / gv_topk_scores* / gv_entity_topk_scores
+// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* (k_transe.hip).  One function per group of arguments; each takes the entry's
+// name, sets the library's error text and returns the code, GV_OK when the group is fine.  An entry lists its groups in the order
+// in which it reports them -- tests/test_query_entries_host.py pins every text and, with two faults at once, that order -- then
+// returns for m == 0, then asks for its own pointers.
+#pragma once
+#include "common.h"
+#include "k_topk.h"
+
+#define GV_CHECK(call)                 \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != GV_OK) return rc_;  \
+    } while (0)
+
+namespace gv {
+
+inline int query_sizes(const char* name, int m, int v, int h) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0, GV_ERR_SHAPE, "%s: m=%d v=%d h=%d", name, m, v, h);
+    return GV_OK;
+}
+
+inline int query_sizes(const char* name, int m, int v, int h, int n_filt_ent) {
+    GV_REQUIRE(m >= 0 && v > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: m=%d v=%d h=%d n_filt_ent=%d", name, m, v, h, n_filt_ent);
+    return GV_OK;
+}
+
+inline int query_k(const char* name, int k) {
+    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "%s: k=%d outside [1, %d]", name, k, TOPK_MAX);
+    return GV_OK;
+}
+
+inline int query_leading(const char* name, int ld_a, int ld_b, int h) {
+    GV_REQUIRE(ld_a >= h && ld_b >= h, GV_ERR_SHAPE, "%s: leading dimension too small", name);
+    return GV_OK;
+}
+
+// the filter's three arrays come together or not at all (`names`: how the entry spells them)
+inline int query_filter(const char* name, const void* lo, const void* hi, const void* ent, const char* names = "filt_lo / filt_hi / filt_ent") {
+    GV_REQUIRE((lo && hi && ent) || (!lo && !hi && !ent), GV_ERR_NULL, "%s: %s must be all given or all NULL", name, names);
+    return GV_OK;
+}
+
+// the candidate sets: their geometry, and -- reported after the filter -- their two arrays
+inline int query_cand_shape(const char* name, int n_sets, int ld_cand, int v) {
+    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "%s: n_sets=%d ld_cand=%d (>= %d)", name, n_sets, ld_cand, (v + 31) / 32);
+    return GV_OK;
+}
+
+inline int query_cand_given(const char* name, const void* cand, const void* cand_set) {
+    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "%s: NULL cand / cand_set", name);
+    return GV_OK;
+}
+
+inline int query_pointers(const char* name, bool all_given) {
+    GV_REQUIRE(all_given, GV_ERR_NULL, "%s: NULL pointer", name);
+    return GV_OK;
+}
+
+// what comes with a filter: somewhere to count what it leaves (`what`: count_filt, or both filtered counts)
+inline int query_filter_needs(const char* name, const void* filt_lo, bool given, const char* what) {
+    GV_REQUIRE(!filt_lo || given, GV_ERR_NULL, "%s: a filter needs %s", name, what);
+    return GV_OK;
+}
+
+}  // namespace gv

@@ -1,6 +1,6 @@
 // Top-k selection shared by gv_topk_scores (k_gemm.hip: MFMA logits) and gv_transe_topk (k_transe.hip: L1 / L2 distances): the
 // ordered 64-bit key, the per-row sorted list with its wave-wide insert, the cursor over a row's sorted filter list, the span
-// geometry and the merge of the spans' lists.  The two kernels differ in how a 64 x 64 tile of values is made, not in how the
+// geometry, the merge of the spans' lists and the host's launch of the pair.  The two kernels differ in how a 64 x 64 tile of values is made, not in how the
 // best k of a row are kept.
 //
 // Candidates are ordered by a 64-bit key, larger = better:
@@ -199,6 +199,28 @@ __global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* pa
         const int pos = lane + 64 * j;
         if (pos < k) out.put((size_t)row * k + pos, a[j]);
     }
+}
+
+// The launch pair of every top-k entry: the span kernel -- Span1 (NK = 1) up to k = 64, Span2 (NK = 2) beyond -- then k_topk_merge.
+// ROWS: query rows per span tile (ROWS * k keys of dynamic LDS); RAISE1: the NK = 1 kernel's static LDS leaves less than ROWS * 64
+// keys under the default limit, so it is raised for both.  One device mask per span kernel: the statics below belong to one
+// instantiation of this template, i.e. to one kernel pair.
+template <auto Span1, auto Span2, bool RAISE1, int ROWS, class Params, class Out>
+int topk_span_merge(const char* name, dim3 grid, const Params& p, unsigned long long* part, int m, int n_spans, int k, const Out& out,
+                    hipStream_t st) {
+    constexpr int KEY = (int)sizeof(unsigned long long);
+    const dim3 block(256), mgrid((unsigned)((m + 3) / 4));
+    static unsigned long long raised1 = 0, raised2 = 0;
+    if (k <= 64) {
+        if (RAISE1 && !raise_dynamic_lds((const void*)Span1, ROWS * 64 * KEY, raised1, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(Span1, grid, block, ROWS * k * KEY, st, p);
+        hipLaunchKernelGGL((k_topk_merge<1, Out>), mgrid, block, 0, st, part, m, n_spans, k, out);
+    } else {
+        if (!raise_dynamic_lds((const void*)Span2, ROWS * TOPK_MAX * KEY, raised2, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(Span2, grid, block, ROWS * k * KEY, st, p);
+        hipLaunchKernelGGL((k_topk_merge<2, Out>), mgrid, block, 0, st, part, m, n_spans, k, out);
+    }
+    return launch_status(name);
 }
 
 // spans per query-row tile: about 4 workgroups per CU of the MI355X (256 CUs) at any m, each span at least 8 column tiles long so

@@ -21,6 +21,7 @@
 // Top-k (gv_transe_topk).  te_tile()'s distances with the selection of gv_topk_scores (k_topk.h) on the key of -distance: smaller
 // distance first, ties by lower id, NaN last; the distance matrix is never stored.
 #include "common.h"
+#include "k_query_args.h"
 #include "k_topk.h"
 #include "k_transe.h"
 
@@ -835,36 +836,39 @@ static int transe_rank_any(const char* name, const float* q, int64_t m, const fl
     return launch_status(name);
 }
 
+static int transe_rank_sizes(const char* name, int64_t m, int v, int dim, int p_norm) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
+               "%s: m=%lld v=%d dim=%d p_norm=%d", name, (long long)m, v, dim, p_norm);
+    return GV_OK;
+}
+
 extern "C" int gv_transe_rank_filtered(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
                                        const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, int32_t* counts_raw,
                                        int32_t* counts_filt, void* stream) {
-    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
-               "gv_transe_rank_filtered: m=%lld v=%d dim=%d p_norm=%d", (long long)m, v, dim, p_norm);
+    const char* name = "gv_transe_rank_filtered";
+    GV_CHECK(transe_rank_sizes(name, m, v, dim, p_norm));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && en && target && counts_raw && counts_filt, GV_ERR_NULL, "gv_transe_rank_filtered: NULL pointer");
-    GV_REQUIRE(!f_lo || (f_hi && f_ent), GV_ERR_NULL, "gv_transe_rank_filtered: a filter needs f_lo, f_hi and f_ent");
-    return transe_rank_any("gv_transe_rank_filtered", q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, TopkCand{}, counts_raw,
-                           counts_filt, nullptr, nullptr, stream);
+    GV_CHECK(query_pointers(name, q && en && target && counts_raw && counts_filt));
+    GV_CHECK(query_filter_needs(name, f_lo, f_hi && f_ent, "f_lo, f_hi and f_ent"));
+    return transe_rank_any(name, q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, TopkCand{}, counts_raw, counts_filt, nullptr,
+                           nullptr, stream);
 }
 
 extern "C" int gv_transe_rank_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* target,
                                           const int32_t* f_lo, const int32_t* f_hi, const int32_t* f_ent, const uint32_t* cand,
                                           int ld_cand, int n_sets, const int32_t* cand_set, int32_t* counts_raw, int32_t* counts_filt,
                                           int32_t* counts_raw_c, int32_t* counts_filt_c, void* stream) {
-    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE,
-               "gv_transe_rank_constrained: m=%lld v=%d dim=%d p_norm=%d", (long long)m, v, dim, p_norm);
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_transe_rank_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE((f_lo && f_hi && f_ent) || (!f_lo && !f_hi && !f_ent), GV_ERR_NULL,
-               "gv_transe_rank_constrained: f_lo / f_hi / f_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_transe_rank_constrained: NULL cand / cand_set");
+    const char* name = "gv_transe_rank_constrained";
+    GV_CHECK(transe_rank_sizes(name, m, v, dim, p_norm));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_filter(name, f_lo, f_hi, f_ent, "f_lo / f_hi / f_ent"));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && en && target && counts_raw && counts_raw_c, GV_ERR_NULL, "gv_transe_rank_constrained: NULL pointer");
-    GV_REQUIRE(!f_lo || (counts_filt && counts_filt_c), GV_ERR_NULL, "gv_transe_rank_constrained: a filter needs both filtered counts");
+    GV_CHECK(query_pointers(name, q && en && target && counts_raw && counts_raw_c));
+    GV_CHECK(query_filter_needs(name, f_lo, counts_filt && counts_filt_c, "both filtered counts"));
     const bool f = f_lo != nullptr;           // without a filter the two filtered counts are not written
-    return transe_rank_any("gv_transe_rank_constrained", q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent,
-                           TopkCand{cand, cand_set, ld_cand, n_sets}, counts_raw, f ? counts_filt : nullptr, counts_raw_c,
-                           f ? counts_filt_c : nullptr, stream);
+    return transe_rank_any(name, q, m, en, v, dim, p_norm, target, f_lo, f_hi, f_ent, TopkCand{cand, cand_set, ld_cand, n_sets},
+                           counts_raw, f ? counts_filt : nullptr, counts_raw_c, f ? counts_filt_c : nullptr, stream);
 }
 
 extern "C" int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k) {
@@ -874,65 +878,52 @@ extern "C" int64_t gv_transe_topk_workspace_bytes(int64_t m, int v, int k) {
     return m * n_spans * k * (int64_t)sizeof(unsigned long long);
 }
 
-// the launches of gv_transe_topk, and with cs.cand of its type-constrained form
+static int transe_topk_sizes(const char* name, int64_t m, int v, int dim, int p_norm, int n_filt_ent) {
+    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) &&
+                   n_filt_ent >= 0,
+               GV_ERR_SHAPE, "%s: m=%lld v=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", name, (long long)m, v, dim,
+               GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
+    return GV_OK;
+}
+
+// the launches of gv_transe_topk, and with cs.cand of its type-constrained form (the running lists: <= 64 KiB of LDS beside 36 KiB
+// static, so the limit is raised for either NK)
 template <bool CAND>
 static int transe_topk_launch(const char* name, const float* q, int64_t m, const float* en, int v, int dim, int p_norm,
                               const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
                               const TopkCand& cs, int k, int64_t* out_ids, float* out_dist, void* workspace, void* stream) {
     TeTopkParams tp{q, en, filt_lo, filt_hi, filt_ent, m, v, dim, p_norm, n_filt_ent, k, 0, 0, (unsigned long long*)workspace, cs};
     topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
-    const int lds = TE_TQ * k * (int)sizeof(unsigned long long);      // the running lists: <= 64 KiB (+ 36 KiB static)
-    const dim3 grid((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), block(256), mgrid((unsigned)((m + 3) / 4));
-    const TeDistOut out{out_ids, out_dist};
-    if (k <= 64) {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_transe_topk_span<1, CAND>, TE_TQ * 64 * (int)sizeof(unsigned long long), lds_raised, name))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_transe_topk_span<1, CAND>), grid, block, lds, GV_ST, tp);
-        hipLaunchKernelGGL((k_topk_merge<1, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
-    } else {
-        static unsigned long long lds_raised = 0;
-        if (!raise_dynamic_lds((const void*)k_transe_topk_span<2, CAND>, TE_TQ * TOPK_MAX * (int)sizeof(unsigned long long), lds_raised,
-                               name))
-            return GV_ERR_SHAPE;
-        hipLaunchKernelGGL((k_transe_topk_span<2, CAND>), grid, block, lds, GV_ST, tp);
-        hipLaunchKernelGGL((k_topk_merge<2, TeDistOut>), mgrid, block, 0, GV_ST, tp.part, (int)m, tp.n_spans, k, out);
-    }
-    return launch_status(name);
+    return topk_span_merge<k_transe_topk_span<1, CAND>, k_transe_topk_span<2, CAND>, true, TE_TQ>(
+        name, dim3((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), tp, tp.part, (int)m, tp.n_spans, k,
+        TeDistOut{out_ids, out_dist}, GV_ST);
 }
 
 extern "C" int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int k, int64_t* out_ids,
                               float* out_dist, void* workspace, void* stream) {
-    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) &&
-                   n_filt_ent >= 0,
-               GV_ERR_SHAPE, "gv_transe_topk: m=%lld v=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", (long long)m, v, dim,
-               GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_transe_topk: k=%d outside [1, %d]", k, TOPK_MAX);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_transe_topk: filt_lo / filt_hi / filt_ent must be all given or all NULL");
+    const char* name = "gv_transe_topk";
+    GV_CHECK(transe_topk_sizes(name, m, v, dim, p_norm, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && en && out_ids && out_dist && workspace, GV_ERR_NULL, "gv_transe_topk: NULL pointer");
-    return transe_topk_launch<false>("gv_transe_topk", q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k,
-                                     out_ids, out_dist, workspace, stream);
+    GV_CHECK(query_pointers(name, q && en && out_ids && out_dist && workspace));
+    return transe_topk_launch<false>(name, q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent, TopkCand{}, k, out_ids,
+                                     out_dist, workspace, stream);
 }
 
 extern "C" int gv_transe_topk_constrained(const float* q, int64_t m, const float* en, int v, int dim, int p_norm,
                                           const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
                                           const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, int k,
                                           int64_t* out_ids, float* out_dist, void* workspace, void* stream) {
-    GV_REQUIRE(m >= 0 && m < (1ll << 31) && v > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) &&
-                   n_filt_ent >= 0,
-               GV_ERR_SHAPE, "gv_transe_topk_constrained: m=%lld v=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", (long long)m, v,
-               dim, GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
-    GV_REQUIRE(k >= 1 && k <= TOPK_MAX, GV_ERR_SHAPE, "gv_transe_topk_constrained: k=%d outside [1, %d]", k, TOPK_MAX);
-    GV_REQUIRE(n_sets >= 1 && ld_cand >= (v + 31) / 32, GV_ERR_SHAPE, "gv_transe_topk_constrained: n_sets=%d ld_cand=%d (>= %d)",
-               n_sets, ld_cand, (v + 31) / 32);
-    GV_REQUIRE((filt_lo && filt_hi && filt_ent) || (!filt_lo && !filt_hi && !filt_ent), GV_ERR_NULL,
-               "gv_transe_topk_constrained: filt_lo / filt_hi / filt_ent must be all given or all NULL");
-    GV_REQUIRE(cand && cand_set, GV_ERR_NULL, "gv_transe_topk_constrained: NULL cand / cand_set");
+    const char* name = "gv_transe_topk_constrained";
+    GV_CHECK(transe_topk_sizes(name, m, v, dim, p_norm, n_filt_ent));
+    GV_CHECK(query_k(name, k));
+    GV_CHECK(query_cand_shape(name, n_sets, ld_cand, v));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    GV_CHECK(query_cand_given(name, cand, cand_set));
     if (m == 0) return GV_OK;
-    GV_REQUIRE(q && en && out_ids && out_dist && workspace, GV_ERR_NULL, "gv_transe_topk_constrained: NULL pointer");
-    return transe_topk_launch<true>("gv_transe_topk_constrained", q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent,
+    GV_CHECK(query_pointers(name, q && en && out_ids && out_dist && workspace));
+    return transe_topk_launch<true>(name, q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent,
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_dist, workspace, stream);
 }

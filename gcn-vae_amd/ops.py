@@ -550,15 +550,40 @@ def rank_scores(q, entities, target, bias=None):
     the number of OTHER entities with a strictly larger logit plus HALF the number that tie with it (gv_rank_scores:
     MFMA tiles with a rank-count epilogue; the (m, V) score matrix is never stored).  Logits, not sigmoid outputs: same
     order, no saturation ties.  A NaN target score ranks last."""
-    q, ld_q, entities, ld_e = _score_operands(q, entities)
-    m, v = q.shape[0], entities.shape[0]
-    tgt32 = _target_args(target, m, v, q.device)
-    bias = _bias_arg(bias)
-    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.empty(1, max(m, 1), dtype=torch.int32, device=q.device)
-    lib.call('gv_rank_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(ws), ptr(counts), m, v,
-             q.shape[1], lib.stream())
-    return _ranks(counts, m)[0]
+    return _rank_scores('gv_rank_scores', q, entities, target, bias, None)[0][0]
+
+
+def _rank_scores(entry, q, entities, target, bias, filt, cand=None, mc=False):
+    """The five ``rank_scores*`` wrappers: the operands' checks, the target, the filter (``filt``: (filt_lo, filt_hi, filt_ent), each
+    possibly None; None: the entry takes no filter), the candidate sets (``cand``: (cand, cand_set) or None), the bias, the buffers
+    and the call.  ``mc``: q / entities are sample stacks (``_mc_operands``).  Returns (one rank tensor per count the entry takes --
+    raw, filtered, raw_constrained, filtered_constrained; None for a filtered one without a filter --, the targets' own values).
+    The counts are not cleared here: the entry zeroes every count array it is given, and a row it is not given comes back as None."""
+    if mc:
+        q, entities, s, m, v, h = _mc_operands(q, entities)
+        operands = (ptr(q), h, m * h, ptr(entities), h, v * h, s)
+    else:
+        q, ld_q, entities, ld_e = _score_operands(q, entities)
+        (m, h), v = q.shape, entities.shape[0]
+        operands = (ptr(q), ld_q, ptr(entities), ld_e)
+    dev = q.device
+    # (a wrong number of targets is reported ahead of a missing filter, a target out of range after it)
+    if entry == 'gv_rank_scores_filtered' and target.numel() == m and any(t is None for t in filt):
+        raise ValueError('rank_scores_filtered needs filt_lo, filt_hi and filt_ent')
+    tgt32 = _target_args(target, m, v, dev)
+    lo32, hi32, ent32, n_ent = _filter_args(*(filt or (None, None, None)), m, v, dev)
+    sets = () if cand is None else _cand_args(*cand, m, v, dev)
+    bias = _mc_bias_arg(bias, s, dev) if mc else _bias_arg(bias)
+    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=dev)
+    counts = torch.empty((1 if filt is None else 2) * (1 if cand is None else 2), max(m, 1), dtype=torch.int32, device=dev)
+    given = lo32 is not None
+    if m == 0 and mc and cand is not None:      # (an empty stack has no sample stride to give)
+        return _ranks(counts, 0, given), tgt[:0]
+    filter_args = () if filt is None else (ptr(lo32), ptr(hi32), ptr(ent32), n_ent)
+    set_args = () if cand is None else (ptr(sets[0]), sets[1], sets[2], ptr(sets[3]))
+    count_args = [ptr(c) if given or i % 2 == 0 else None for i, c in enumerate(counts)]
+    lib.call(entry, *operands, ptr(tgt32), ptr(bias), *filter_args, *set_args, ptr(tgt), *count_args, m, v, h, lib.stream())
+    return _ranks(counts, m, given), tgt[:m]
 
 
 def _score_operands(q, entities):
@@ -626,19 +651,7 @@ def rank_scores_filtered(q, entities, target, filt_lo, filt_hi, filt_ent, bias=N
     launch pair (gv_rank_scores_filtered).  The filtered rank leaves out the candidates ``filt_ent[filt_lo[i]:filt_hi[i]]`` --
     entity ids sorted ascending and unique inside each range (ranking.FilterIndex builds them) -- whatever their score; ranges
     may be empty, may hold the target and may be shared.  The raw rank equals ``rank_scores`` bit for bit."""
-    q, ld_q, entities, ld_e = _score_operands(q, entities)
-    m, v = q.shape[0], entities.shape[0]
-    # (a wrong number of targets is reported ahead of a missing filter, a target out of range after it)
-    if target.numel() == m and (filt_lo is None or filt_hi is None or filt_ent is None):
-        raise ValueError('rank_scores_filtered needs filt_lo, filt_hi and filt_ent')
-    tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    bias = _bias_arg(bias)
-    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=q.device)
-    lib.call('gv_rank_scores_filtered', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, ptr(ws), ptr(counts[0]), ptr(counts[1]), m, v, q.shape[1], lib.stream())
-    return _ranks(counts, m)
+    return _rank_scores('gv_rank_scores_filtered', q, entities, target, bias, (filt_lo, filt_hi, filt_ent))[0]
 
 
 TOPK_MAX = 128      # largest k gv_topk_scores takes
@@ -664,20 +677,39 @@ def topk_scores(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=
     are no candidates of row i.  Order: logit descending, equal logits (-0 and +0 alike) by lower id, NaN after everything.
     Returns ``(ids int64 (m, k), logits float32 (m, k))``; rows with fewer than k candidates are padded with id -1, logit -inf.
     Logits are reported with -0 as +0 and every NaN as the one quiet NaN (``ranking.topk_from_scores`` does the same)."""
-    m, v, h = _topk_operands(q, entities)
+    return _topk_scores('gv_topk_scores', q, entities, k, bias, (filt_lo, filt_hi, filt_ent))
+
+
+def _topk_scores(entry, q, entities, k, bias, filt, cand=None, mc=False):
+    """The four ``topk_scores*`` wrappers, with ``_rank_scores``' arguments: the checks, the outputs, the workspace and the call.
+    Returns (ids int64 (m, k), values float32 (m, k))."""
+    if mc:
+        q, entities, s, m, v, h = _mc_operands(q, entities)
+    else:
+        m, v, h = _topk_operands(q, entities)
     k = _topk_arg(k)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    q, ld_q = _row_major(q, 'q')
-    entities, ld_e = _row_major(entities, 'entities')
-    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
-    logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
+    if cand is None:                            # topk_scores reports a bad filter ahead of a CPU tensor, the constrained form after it
+        lo32, hi32, ent32, n_ent = _filter_args(*filt, m, v, q.device)
+    if mc:
+        operands = (ptr(q), h, m * h, ptr(entities), h, v * h, s)
+    else:
+        q, ld_q = _row_major(q, 'q')
+        entities, ld_e = _row_major(entities, 'entities')
+        operands = (ptr(q), ld_q, ptr(entities), ld_e)
+    dev = q.device
+    if cand is not None:
+        lo32, hi32, ent32, n_ent = _filter_args(*filt, m, v, dev)
+        words, ld_cand, n_sets, set32 = _cand_args(*cand, m, v, dev)
+    ids = torch.empty(m, k, dtype=torch.int32, device=dev)
+    values = torch.empty(m, k, dtype=torch.float32, device=dev)
     if m == 0:
-        return ids.long(), logits
-    bias = _bias_arg(bias)
-    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_topk_scores', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k,
-             ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
-    return ids.long(), logits
+        return ids.long(), values
+    bias = _mc_bias_arg(bias, s, dev) if mc else _bias_arg(bias)
+    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=dev)
+    set_args = () if cand is None else (ptr(words), ld_cand, n_sets, ptr(set32))
+    lib.call(entry, *operands, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, *set_args, k, ptr(ids), ptr(values), ptr(ws), m, v, h,
+             lib.stream())
+    return ids.long(), values
 
 
 def _cand_args(cand, cand_set, m, v, device):
@@ -705,19 +737,7 @@ def rank_scores_constrained(q, entities, target, cand, cand_set, filt_lo=None, f
     row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``); the target itself is never counted, member or not, and an
     empty or out-of-range set gives rank 0.  The first two equal ``rank_scores_filtered`` bit for bit.  Without a filter the two
     filtered ranks are None."""
-    q, ld_q, entities, ld_e = _score_operands(q, entities)
-    m, v = q.shape[0], entities.shape[0]
-    tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    bias = _bias_arg(bias)
-    ws = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
-    filt = lo32 is not None
-    lib.call('gv_rank_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), ptr(ws), ptr(counts[0]), ptr(counts[1]) if filt else None,
-             ptr(counts[2]), ptr(counts[3]) if filt else None, m, v, q.shape[1], lib.stream())
-    return _ranks(counts, m, filt)
+    return _rank_scores('gv_rank_scores_constrained', q, entities, target, bias, (filt_lo, filt_hi, filt_ent), (cand, cand_set))[0]
 
 
 def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -725,21 +745,7 @@ def topk_scores_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=N
     are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``), less the filter-listed
     ids.  Order, ties, NaN and padding are ``topk_scores``'; a set with fewer than k members pads, an out-of-range set id gives
     an all-padding row."""
-    m, v, h = _topk_operands(q, entities)
-    k = _topk_arg(k)
-    q, ld_q = _row_major(q, 'q')
-    entities, ld_e = _row_major(entities, 'entities')
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
-    logits = torch.empty(m, k, dtype=torch.float32, device=q.device)
-    if m == 0:
-        return ids.long(), logits
-    bias = _bias_arg(bias)
-    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_topk_scores_constrained', ptr(q), ld_q, ptr(entities), ld_e, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-             ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(logits), ptr(ws), m, v, h, lib.stream())
-    return ids.long(), logits
+    return _topk_scores('gv_topk_scores_constrained', q, entities, k, bias, (filt_lo, filt_hi, filt_ent), (cand, cand_set))
 
 
 def _entity_topk_operands(ents, emb, w):
@@ -834,35 +840,15 @@ def rank_scores_mc(q, entities, target, bias=None, filt_lo=None, filt_hi=None, f
     ``pbar[i, j] = mean_s sigmoid(q[s, i] . entities[s, j] + bias[s])``, never stored; ranks follow ``rank_scores_filtered``'s
     rules (0-based floats, x.5 under ties -- pbar saturates, so ties are real --, NaN never optimistic).  Returns ``(raw,
     filtered, tgt)``: ``filtered`` is None without a filter, ``tgt`` (m,) is the target's own pbar."""
-    q, entities, s, m, v, h = _mc_operands(q, entities)
-    tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    bias = _mc_bias_arg(bias, s, q.device)
-    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=q.device)
-    filt = lo32 is not None
-    lib.call('gv_rank_scores_mc', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(tgt32), ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, ptr(tgt), ptr(counts[0]), ptr(counts[1]) if filt else None, m, v, h, lib.stream())
-    raw, filtered = _ranks(counts, m, filt)
-    return raw, filtered, tgt[:m]
+    (raw, filtered), tgt = _rank_scores('gv_rank_scores_mc', q, entities, target, bias, (filt_lo, filt_hi, filt_ent), mc=True)
+    return raw, filtered, tgt
 
 
 def topk_scores_mc(q, entities, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
     """The ``k`` most probable entities per query row under ``rank_scores_mc``'s pbar -- the very values it ranks, bit for bit --
     from one fused launch pair (gv_topk_scores_mc).  Filter, order (pbar descending, ties by lower id, NaN last) and padding (id
     -1, value -inf) are ``topk_scores``'.  Returns ``(ids int64 (m, k), prob_mean float32 (m, k))``."""
-    q, entities, s, m, v, h = _mc_operands(q, entities)
-    k = _topk_arg(k)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
-    prob = torch.empty(m, k, dtype=torch.float32, device=q.device)
-    if m == 0:
-        return ids.long(), prob
-    bias = _mc_bias_arg(bias, s, q.device)
-    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_topk_scores_mc', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-             k, ptr(ids), ptr(prob), ptr(ws), m, v, h, lib.stream())
-    return ids.long(), prob
+    return _topk_scores('gv_topk_scores_mc', q, entities, k, bias, (filt_lo, filt_hi, filt_ent), mc=True)
 
 
 def rank_scores_mc_constrained(q, entities, target, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -871,20 +857,9 @@ def rank_scores_mc_constrained(q, entities, target, cand, cand_set, bias=None, f
     constrained ranks count, on the same pbar, only the members of row ``cand_set[i]`` of the bitmask ``cand`` (see
     ``_cand_args``): the target is never counted, member or not, and an empty or out-of-range set gives rank 0.  Without a filter
     the two filtered ranks are None."""
-    q, entities, s, m, v, h = _mc_operands(q, entities)
-    tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    bias = _mc_bias_arg(bias, s, q.device)
-    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=q.device)
-    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
-    filt = lo32 is not None
-    if m == 0:                                  # (an empty stack has no sample stride to give)
-        return _ranks(counts, 0, filt) + (tgt[:0],)
-    lib.call('gv_rank_scores_mc_constrained', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(tgt32), ptr(bias), ptr(lo32),
-             ptr(hi32), ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), ptr(tgt), ptr(counts[0]),
-             ptr(counts[1]) if filt else None, ptr(counts[2]), ptr(counts[3]) if filt else None, m, v, h, lib.stream())
-    return _ranks(counts, m, filt) + (tgt[:m],)
+    ranks, tgt = _rank_scores('gv_rank_scores_mc_constrained', q, entities, target, bias, (filt_lo, filt_hi, filt_ent), (cand, cand_set),
+                              mc=True)
+    return ranks + (tgt,)
 
 
 def topk_scores_mc_constrained(q, entities, k, cand, cand_set, bias=None, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -892,19 +867,7 @@ def topk_scores_mc_constrained(q, entities, k, cand, cand_set, bias=None, filt_l
     row i are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (see ``_cand_args``), less the
     filter-listed ids; the values are ``rank_scores_mc_constrained``'s pbar, bit for bit.  A set with fewer than k members pads
     (id -1, value -inf), an out-of-range set id gives an all-padding row.  Returns ``(ids int64 (m, k), prob_mean float32 (m, k))``."""
-    q, entities, s, m, v, h = _mc_operands(q, entities)
-    k = _topk_arg(k)
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    ids = torch.empty(m, k, dtype=torch.int32, device=q.device)
-    prob = torch.empty(m, k, dtype=torch.float32, device=q.device)
-    if m == 0:
-        return ids.long(), prob
-    bias = _mc_bias_arg(bias, s, q.device)
-    ws = torch.empty(int(lib.load().gv_topk_scores_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_topk_scores_mc_constrained', ptr(q), h, m * h, ptr(entities), h, v * h, s, ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(prob), ptr(ws), m, v, h, lib.stream())
-    return ids.long(), prob
+    return _topk_scores('gv_topk_scores_mc_constrained', q, entities, k, bias, (filt_lo, filt_hi, filt_ent), (cand, cand_set), mc=True)
 
 
 def pair_prob_std_mc(q, entities, ids, bias=None):
