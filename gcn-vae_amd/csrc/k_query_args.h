@@ -1,5 +1,5 @@
 // The argument checks the entity-query entries share (host only): gv_rank_scores* / gv_topk_scores* / gv_entity_topk_scores
-// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* (k_transe.hip).  One function per group of arguments; each takes the entry's
+// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk (k_transe.hip).  One function per group of arguments; each takes the entry's
 // name, sets the library's error text and returns the code, GV_OK when the group is fine.  An entry lists its groups in the order
 // in which it reports them -- tests/test_query_entries_host.py pins every text and, with two faults at once, that order -- then
 // returns for m == 0, then asks for its own pointers.

@@ -20,6 +20,9 @@
 //
 // Top-k (gv_transe_topk).  te_tile()'s distances with the selection of gv_topk_scores (k_topk.h) on the key of -distance: smaller
 // distance first, ties by lower id, NaN last; the distance matrix is never stored.
+//
+// Per-entity completion (gv_transe_entity_topk).  The same tile and selection with the relations walked inside a query entity's list:
+// the query row en[a] +- rn[r] is formed while it is staged (te_tile_with), the candidate id is r * N + x.
 #include "common.h"
 #include "k_query_args.h"
 #include "k_topk.h"
@@ -476,9 +479,12 @@ __global__ __launch_bounds__(256) void k_transe_queries(const float* __restrict_
 // ---- distances and the fused ranker --------------------------------------------------------------------
 constexpr int TE_KC = 32;   // columns per LDS stage of a TE_TQ x TE_TE tile (k_transe.h, with te_pair_term)
 
-// acc[4][4] for queries q0 + 4 ty .. and entities e0 + 4 tx ..: the columns in order, one accumulator per pair
-__device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v, int dim, int p,
-                                        int64_t q0, int e0, float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4], float (&acc)[4][4]) {
+// acc[4][4] for the tile's query rows 4 ty .. and entities e0 + 4 tx ..: the columns in order, one accumulator per pair.
+// q_at(row, c): column c of the tile's query row `row` as it is staged (0 past the last row or column) -- te_tile reads a stored
+// query matrix, gv_transe_entity_topk forms the row on the way.
+template <class QAt>
+__device__ __forceinline__ void te_tile_with(QAt q_at, const float* __restrict__ en, int v, int dim, int p, int e0,
+                                             float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4], float (&acc)[4][4]) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -488,8 +494,7 @@ __device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, 
         __syncthreads();
         for (int x = tid; x < TE_TQ * TE_KC; x += 256) {
             const int row = x / TE_KC, k = x % TE_KC;
-            const int64_t qi = q0 + row;
-            qs[k][row] = (qi < m && k0 + k < dim) ? q[qi * dim + k0 + k] : 0.f;
+            qs[k][row] = q_at(row, k0 + k);
             const int ej = e0 + row;
             es[k][row] = (ej < v && k0 + k < dim) ? en[(int64_t)ej * dim + k0 + k] : 0.f;
         }
@@ -511,6 +516,17 @@ __device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, 
 #pragma unroll
             for (int b = 0; b < 4; ++b) acc[a][b] = sqrtf(acc[a][b]);
     }
+}
+
+// the tile of rows q0 .. of a stored query matrix q (m, dim)
+__device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v, int dim, int p,
+                                        int64_t q0, int e0, float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4], float (&acc)[4][4]) {
+    te_tile_with(
+        [&](int row, int c) {
+            const int64_t qi = q0 + row;
+            return (qi < m && c < dim) ? q[qi * dim + c] : 0.f;
+        },
+        en, v, dim, p, e0, qs, es, acc);
 }
 
 __global__ __launch_bounds__(256) void k_transe_distances(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v,
@@ -711,15 +727,130 @@ __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp)
     }
 }
 
-// the key of -distance back to the distance: key 0 (no candidate) -> id -1, +inf; zero -> +0; NaN -> the one quiet NaN
+// the key of -distance back to the distance: key 0 (no candidate) -> +inf; zero -> +0; NaN -> the one quiet NaN
+__device__ __forceinline__ float te_key_dist(unsigned long long key) {
+    const float x = topk_key_logit(key);                 // -distance, never -0
+    const unsigned b = __float_as_uint(x) ^ 0x80000000u;
+    return x != x ? x : __uint_as_float(b == 0x80000000u ? 0u : b);
+}
+
+// (key 0 -> id -1)
 struct TeDistOut {
     int64_t* ids;
     float* dist;
     __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
         ids[i] = (int64_t)topk_key_id(key);
-        const float x = topk_key_logit(key);                 // -distance, never -0
-        const unsigned b = __float_as_uint(x) ^ 0x80000000u;
-        dist[i] = x != x ? x : __uint_as_float(b == 0x80000000u ? 0u : b);
+        dist[i] = te_key_dist(key);
+    }
+};
+
+// ---- per-entity completion (gv_transe_entity_topk): one list per query entity over ALL relations ---------------------------------
+// Query row i is entity a = ents[i]; its candidates are the pairs (r, x) at distance ||(en[a] +- rn[r]) - en[x]||_p -- k_transe_topk_span
+// with the relations walked INSIDE the row's list, as k_entity_topk_span (k_gemm.hip) does for DistMult: neither an (entity x
+// relation) query matrix nor m * R * k intermediate results exist.  The columns of a row are the sequence of (relation, 64-entity
+// tile) pairs, r-major: tile t = r * col_tiles + ct, candidate id = r * N + x (< 2^31), so the ordered key says "distance, then
+// relation, then entity".  A workgroup owns a 64-row tile of query entities and a contiguous span of that sequence.  The query row is
+// made while te_tile_with stages it: en[a][c] + rn[r][c] (head: -), one f32 add each -- the value k_transe_queries stores -- so the
+// distances are gv_transe_distances' bits.  At the first tile of a relation (and of the span) the 64 rows' filter cursors are
+// re-opened on key a * R + r.
+struct TeEntityTopkParams {
+    const float* en;              // [n, dim]
+    const float* rn;              // [num_rels, dim]
+    const int32_t* ents;          // [m] query entities; an id outside [0, n) is a row without candidates
+    const int32_t* filt_lo;       // key a * R + r; NULL: no filter
+    const int32_t* filt_hi;
+    const int32_t* filt_ent;
+    int m, n, num_rels, dim, p, head, exclude_self;
+    int n_ent;                    // length of filt_ent: every range is clamped into it
+    int topk;                     // 1..TOPK_MAX
+    int span_tiles, n_spans;      // (relation, entity tile) pairs per span (blockIdx.y = span)
+    unsigned long long* part;     // [m][n_spans][topk]
+};
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_transe_entity_topk_span(const TeEntityTopkParams tp) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    __shared__ __attribute__((aligned(16))) float ds[TE_TQ * TE_LDD];     // the tile's distances, row-major
+    __shared__ unsigned long long thr[TE_TQ];                             // each row's k-th key
+    __shared__ int cur[TE_TQ], fhi[TE_TQ], nxt[TE_TQ];                    // filter cursor (k_topk.h)
+    __shared__ int fl[4][64];
+    __shared__ int ent_s[TE_TQ];                                          // the rows' entities (-1: no such row)
+    extern __shared__ unsigned long long lists[];                         // [TE_TQ][topk]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, tx = tid & 15, ty = tid >> 4;
+    const int k = tp.topk, dim = tp.dim;
+    const int m0 = blockIdx.x * TE_TQ;
+    const int col_tiles = (tp.n + TE_TE - 1) / TE_TE;
+    const int t_begin = blockIdx.y * tp.span_tiles;
+    const int t_end = min(t_begin + tp.span_tiles, tp.num_rels * col_tiles);
+    const bool filtered = tp.filt_lo != nullptr, head = tp.head != 0;
+    for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (tid < TE_TQ) {
+        const int a = m0 + tid < tp.m ? tp.ents[m0 + tid] : -1;
+        ent_s[tid] = (unsigned)a < (unsigned)tp.n ? a : -1;
+        thr[tid] = 0ull;
+    }
+    int r = t_begin / col_tiles, ct = t_begin - r * col_tiles;
+    for (int t = t_begin; t < t_end; ++t) {
+        const int e0 = ct * TE_TE, r_now = r;
+        const bool opens = ct == 0 || t == t_begin;                // the relation's (or the span's) first tile
+        if (++ct == col_tiles) { ct = 0; ++r; }
+        const float* __restrict__ rr = tp.rn + (size_t)r_now * dim;
+        float acc[4][4];
+        // te_tile_with's first barrier publishes the set-up above and ends the last tile's reads of ds and of the cursors
+        te_tile_with(
+            [&](int row, int c) {
+                const int a = ent_s[row];
+                if (a < 0 || c >= dim) return 0.f;
+                const float x = tp.en[(size_t)a * dim + c], y = rr[c];
+                return head ? x - y : x + y;
+            },
+            tp.en, tp.n, dim, tp.p, e0, qs, es, acc);
+        if (opens && tid < TE_TQ) {
+            const int a = ent_s[tid];
+            topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && a >= 0, (long long)a * tp.num_rels + r_now, e0,
+                              &cur[tid], &fhi[tid], &nxt[tid]);
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
+        __syncthreads();
+        const int col = e0 + lane;
+        for (int i = 0; i < TE_TQ / 4; ++i) {
+            const int rl = wid * (TE_TQ / 4) + i;
+            if (m0 + rl >= tp.m) break;
+            const int a = ent_s[rl];
+            if (a < 0) continue;
+            unsigned long long key = col < tp.n ? topk_key(-ds[rl * TE_LDD + lane], r_now * tp.n + col) : 0ull;
+            if (filtered && nxt[rl] < e0 + TE_TE &&
+                topk_filter_window(tp.filt_ent, e0, (int)((unsigned)(t - t_begin) * TE_TQ + rl + 1u), lane, &cur[rl], &fhi[rl], &nxt[rl],
+                                   fl[wid]))
+                key = 0ull;
+            if (tp.exclude_self && col == a) key = 0ull;
+            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
+        }
+    }
+    // each wave hands its own rows' lists on (written by this wave only: no barrier)
+    for (int i = 0; i < TE_TQ / 4; ++i) {
+        const int rl = wid * (TE_TQ / 4) + i, row = m0 + rl;
+        if (row >= tp.m) break;
+        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
+        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// TeDistOut with the candidate id r * n + x taken apart
+struct TeEntityDistOut {
+    int64_t* rel;
+    int64_t* ent;
+    float* dist;
+    int n;
+    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
+        const int id = topk_key_id(key);
+        rel[i] = id < 0 ? -1 : id / n;
+        ent[i] = id < 0 ? -1 : id % n;
+        dist[i] = te_key_dist(key);
     }
 };
 
@@ -926,4 +1057,52 @@ extern "C" int gv_transe_topk_constrained(const float* q, int64_t m, const float
     GV_CHECK(query_pointers(name, q && en && out_ids && out_dist && workspace));
     return transe_topk_launch<true>(name, q, m, en, v, dim, p_norm, filt_lo, filt_hi, filt_ent, n_filt_ent,
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_dist, workspace, stream);
+}
+
+// ---- per-entity completion (gv_transe_entity_topk) -------------------------------------------------------------------------------
+// spans of the R * ceil(N / 64) (relation, entity tile) pairs: span_tiles of them each when the caller says so, else topk_spans'
+// rule with up to 256 spans, so that a single query entity still fills the chip (gv_entity_topk_scores' geometry)
+static void transe_entity_topk_spans(int m, int n, int num_rels, int span_tiles, int* per, int* n_spans) {
+    const long long tiles = (long long)num_rels * (((long long)n + TE_TE - 1) / TE_TE);
+    if (span_tiles > 0) {
+        *per = (int)std::min<long long>(span_tiles, tiles);
+        *n_spans = (int)((tiles + *per - 1) / *per);
+    } else {
+        topk_spans_of(m, tiles, 256, per, n_spans);
+    }
+}
+
+extern "C" int64_t gv_transe_entity_topk_workspace_bytes(int m, int n, int num_rels, int k, int span_tiles) {
+    if (m <= 0 || n <= 0 || num_rels <= 0 || (long long)n * num_rels > INT_MAX || k < 1 || k > TOPK_MAX || span_tiles < 0) return 0;
+    int per = 0, n_spans = 0;
+    transe_entity_topk_spans(m, n, num_rels, span_tiles, &per, &n_spans);
+    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+extern "C" int gv_transe_entity_topk(const int32_t* ents, int m, const float* en, const float* rn, int n, int num_rels, int dim, int head,
+                                     int p_norm, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                                     int n_filt_ent, int exclude_self, int k, int span_tiles, int64_t* out_rel, int64_t* out_ent,
+                                     float* out_dist, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* name = "gv_transe_entity_topk";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) && n_filt_ent >= 0,
+               GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", name, m, n, num_rels, dim,
+               GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
+    GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "%s: n * num_rels = %lld does not fit 31 bits", name,
+               (long long)n * num_rels);
+    GV_CHECK(query_k(name, k));
+    GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "%s: span_tiles=%d (0: the library's rule)", name, span_tiles);
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, ents && en && rn && out_rel && out_ent && out_dist && workspace));
+    TeEntityTopkParams tp{en, rn, ents, filt_lo, filt_hi, filt_ent, m, n, num_rels, dim, p_norm, head != 0, exclude_self != 0,
+                          n_filt_ent, k, 0, 0, (unsigned long long*)workspace};
+    transe_entity_topk_spans(m, n, num_rels, span_tiles, &tp.span_tiles, &tp.n_spans);
+    GV_REQUIRE(tp.n_spans <= 65535, GV_ERR_SHAPE, "%s: span_tiles=%d gives %d spans (at most 65535)", name, span_tiles, tp.n_spans);
+    const int64_t need = (int64_t)m * tp.n_spans * k * (int64_t)sizeof(unsigned long long);
+    GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed", name, (long long)workspace_bytes,
+               (long long)need);
+    // (<= 64 KiB of lists beside 37 KiB static: the limit is raised for either NK)
+    return topk_span_merge<k_transe_entity_topk_span<1>, k_transe_entity_topk_span<2>, true, TE_TQ>(
+        name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), tp, tp.part, m, tp.n_spans, k,
+        TeEntityDistOut{out_rel, out_ent, out_dist, n}, GV_ST);
 }

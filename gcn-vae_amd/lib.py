@@ -142,6 +142,8 @@ SIGNATURES = {
     'gv_transe_topk': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     'gv_transe_rank_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     'gv_transe_topk_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'gv_transe_entity_topk_workspace_bytes': (_L, [_I, _I, _I, _I, _I]),
+    'gv_transe_entity_topk': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
     'gv_transe_mine_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_transe_mine': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P,
                             _P, _L, _P]),

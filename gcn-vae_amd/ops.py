@@ -3716,6 +3716,46 @@ def transe_topk_constrained(q, en, k, p_norm, cand, cand_set, filt_lo=None, filt
     return ids, dist
 
 
+def transe_entity_topk(ents, en, rn, k, p_norm, head=False, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
+    """Per-entity completion for TransE: for every query entity ``a = ents[i]`` the ``k`` nearest pairs (r, x) over ALL relations
+    under ``d[i, r, x] = ||(en[a] + rn[r]) - en[x]||_p`` (``head``: ``en[a] - rn[r]``, the facts (x, r, a)) -- bit for bit
+    ``transe_distances(transe_queries(ent, rel, a, r, head), en, p_norm)``, the distances ``transe_topk`` selects on -- from one
+    fused launch pair (gv_transe_entity_topk) that keeps one sorted list per entity while the relations are walked: no (entity x
+    relation) query matrix, no per-relation results.  ``en`` / ``rn`` are the normalised tables (``transe_queries(table,
+    norm_flag=...)``).  With a filter (one range per key ``a * R + r``, N * R of them: ``ranking._mine_filter`` builds it) the ids
+    ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R + r]]`` are no candidates under relation r, nor is ``x == a`` with
+    ``exclude_self``.  Order: distance ascending, then relation, then entity ascending; NaN after everything (+inf included).
+    ``ents`` may repeat and need not be sorted.  ``span``: (relation, 64-entity tile) pairs per workgroup instead of the library's
+    rule -- the result does not depend on it.  Returns ``(rel int64 (m, k), other int64 (m, k), dist float32 (m, k))``, padded
+    with -1 / -1 / +inf past a row's last candidate; a zero distance is reported as +0 and every NaN as the one quiet NaN."""
+    m, n, num_rels, dim = _entity_topk_operands(ents, en, rn)
+    k = _topk_arg(k)
+    p_norm = _p_norm(p_norm)
+    if dim > TRANSE_MAX_DIM:
+        raise ValueError(f'en / rn: width {dim} above {TRANSE_MAX_DIM}')
+    if span is not None and int(span) < 1:
+        raise ValueError(f'span counts (relation, entity tile) pairs per workgroup: at least 1, got {span}')
+    if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
+        raise ValueError(f'query entities must lie in [0, {n})')
+    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, n * num_rels, n, en.device)
+    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
+    dev = en.device
+    if rn.device != dev:
+        raise ValueError(f'en on {dev}, rn on {rn.device}')
+    rel = torch.empty(m, k, dtype=torch.int64, device=dev)
+    other = torch.empty(m, k, dtype=torch.int64, device=dev)
+    dist = torch.empty(m, k, dtype=torch.float32, device=dev)
+    if m == 0:
+        return rel, other, dist
+    ents32 = ents.to(device=dev, dtype=torch.int32).contiguous()
+    span_tiles = 0 if span is None else min(int(span), num_rels * ((n + 63) // 64))
+    ws_bytes = int(lib.load().gv_transe_entity_topk_workspace_bytes(m, n, num_rels, k, span_tiles))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_transe_entity_topk', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
+    return rel, other, dist
+
+
 def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
                 max_results=MINE_MAX_RESULTS):
     """Mine ALL triplets of a TransE model: ``d[s, r, o] = ||(en[s] + rn[r]) - en[o]||_p`` over every (s, r, o), bit for bit

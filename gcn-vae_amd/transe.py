@@ -56,6 +56,13 @@ cross-check.  ``--complete-topk K`` / ``--complete-threshold D`` write them to `
 ``type_constraint`` (``--complete-typed``) only type-correct triplets are mined, by ``ops.transe_mine_typed``
 (gv_transe_mine_typed: by relation, over that relation's subject and object member lists).
 
+Per-entity completion: ``complete_entities`` answers "what is this entity missing?" -- an entity's ``k`` nearest new facts over
+ALL relations, as subject (``side='s'``) or as object (``side='o'``), at ``predict_topk``'s distances, from ``ops.transe_entity_topk``
+(gv_transe_entity_topk: one sorted list per entity while the relations are walked; no (entity x relation) query matrix).
+``complete_entities_from_distances`` states the rule on a materialised (m, R, N) tensor; ``complete_entities_unfused`` is the
+per-relation cross-check.  ``--profile-topk K --profile-entities IDS|FILE --profile-out FILE`` write both sides in train.py's
+profile layout, the distance in place of the logit and probability.
+
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --optimizer adam --alpha 0.001 --graph-step
@@ -70,8 +77,9 @@ import torch.nn.functional as F
 
 from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
-                      _mine_unfused,
+                      _mine_unfused, complete_entities_from_scores,
                       rank_from_scores_constrained, sort_and_rank, topk_from_scores)
+from .train import PROFILE_ROWS, profile_entities_arg
 
 
 # ------------------------------------------------------------------------------------------------
@@ -745,6 +753,101 @@ def write_completions(path, model_or_tables, filter_index, k=None, threshold=Non
 
 
 # ------------------------------------------------------------------------------------------------
+# per-entity completion: what is this entity missing?
+# ------------------------------------------------------------------------------------------------
+COMPLETE_UNFUSED_ELEMS = 1 << 26      # distances per chunk of the materialised cross-check: bounds its (rows, R, N) tensor
+
+
+def complete_entities_from_distances(dist, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True):
+    """The rule of ``ops.transe_entity_topk`` on a materialised (m, R, N) distance tensor, in plain torch (any device): row i
+    belongs to entity ``entities[i]``, its candidates are all (r, x) less the ids ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R +
+    r]]`` under relation r (the dense per-key ranges of ``_mine_filter``) and less ``x == a`` with ``exclude_self``; they go by
+    distance ascending, equal distances by relation, then by entity, NaN after every number (+inf included).  Returns ``(rel int64
+    (m, k), other int64 (m, k), dist float32 (m, k))``, padded with -1 / -1 / +inf; a zero is reported as +0 and every NaN as the
+    one quiet NaN.  ``topk_from_distances`` on the (m, R * N) view under the allowed mask of
+    ``ranking.complete_entities_from_scores``: the id r * N + x already says relation first, then entity."""
+    rel, other, neg = complete_entities_from_scores(-dist.to(torch.float32), entities, k, filt_lo=filt_lo, filt_hi=filt_hi,
+                                                    filt_ent=filt_ent, exclude_self=exclude_self)
+    out = 0.0 - neg                                                   # -(+0) would be -0; 0 - (+0) is +0
+    return rel, other, torch.where(torch.isnan(out), torch.full_like(out, float('nan')), out)
+
+
+def _complete_args(model_or_tables, entities, k, side, filter_index):
+    """What the two routes of ``complete_entities`` check and prepare alike: (ent, rel, p_norm, norm_flag, entities, k, (lo, hi,
+    ent))."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    k = ops._topk_arg(k)
+    ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+    rel = rel.to(ent.device)
+    ents = torch.as_tensor(entities, device=ent.device).reshape(-1)
+    ops._entity_topk_operands(ents, ent, rel)
+    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
+    filt = _mine_filter(filter_index, ent.shape[0], rel.shape[0], ent.device, 'o' if side == 's' else 's')
+    return ent.contiguous(), rel.contiguous(), ops._p_norm(p_norm), norm_flag, ents, k, filt
+
+
+def complete_entities(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True):
+    """What is this entity missing?  For every entity ``a`` of ``entities`` (any order, repeats allowed) the ``k`` nearest new
+    facts around it over ALL relations at once: ``side='s'`` the facts (a, r, x) at ``||n(a) + n(r) - n(x)||_p``, ``side='o'`` the
+    facts (x, r, a) at ``||n(a) - n(r) - n(x)||_p`` -- the distances of ``predict_topk`` on the queries (a, r) in direction 'o' /
+    's', bit for bit.  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``.  With a ``FilterIndex`` the known
+    facts are left out -- direction 'o' for ``side='s'``, 's' for ``side='o'`` -- and with ``exclude_self`` the loops (a, r, a).
+    The normalised tables are built once and one fused launch pair (ops.transe_entity_topk) keeps one list per entity while the
+    relations are walked.  Returns ``(rel int64 (m, k), other int64 (m, k), dist float32 (m, k))`` in the order of
+    ``complete_entities_from_distances``: nearest first, ties by relation, then by entity; rows with fewer than k candidates end
+    in -1 / -1 / +inf.  1 <= k <= 128."""
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag, ents, k, (lo, hi, f_ent) = _complete_args(model_or_tables, entities, k, side, filter_index)
+        en = ops.transe_queries(ent, norm_flag=norm_flag)                 # the normalised tables, once
+        rn = ops.transe_queries(rel, norm_flag=norm_flag)
+        return ops.transe_entity_topk(ents, en, rn, k, p_norm, side == 'o', lo, hi, f_ent, exclude_self)
+
+
+def complete_entities_unfused(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True):
+    """``complete_entities`` from materialised distances: per relation ``ops.transe_queries`` + ``ops.transe_distances`` into a
+    (rows, R, N) tensor, then ``complete_entities_from_distances``, ``COMPLETE_UNFUSED_ELEMS`` distances at a time.  The in-repo
+    cross-check and the bench's comparator, never a fallback."""
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag, ents, k, (lo, hi, f_ent) = _complete_args(model_or_tables, entities, k, side, filter_index)
+        n, num_rels = ent.shape[0], rel.shape[0]
+        en = ops.transe_queries(ent, norm_flag=norm_flag)
+        rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
+        out = []
+        for at in range(0, ents.numel(), rows):
+            part = ents[at:at + rows].long()
+            dist = torch.stack([ops.transe_distances(ops.transe_queries(ent, rel, part, torch.full_like(part, r), head=side == 'o',
+                                                                        norm_flag=norm_flag), en, p_norm)
+                                for r in range(num_rels)], dim=1)
+            out.append(complete_entities_from_distances(dist, part, k, filt_lo=lo, filt_hi=hi, filt_ent=f_ent,
+                                                        exclude_self=exclude_self))
+        if not out:
+            z = torch.zeros(0, k, dtype=torch.int64, device=ent.device)
+            return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=ent.device)
+        return tuple(torch.cat(t) for t in zip(*out))
+
+
+def write_entity_profiles(path, model_or_tables, entities, k, filter_index):
+    """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  distance``: for every entity of ``entities`` its
+    ``k`` nearest new facts over all relations (``complete_entities``; ``filter_index``: the known ones left out, as are loops),
+    nearest first with the rank counted from 1 -- the 's' lines are the facts (entity, relation, other), then the 'o' lines the
+    facts (other, relation, entity).  The first five columns are those of train.py's ``profiles.tsv``: the two files join on them.
+    An entity with fewer than k candidates has fewer lines.  Returns the number of lines written."""
+    n_lines = 0
+    ents = torch.as_tensor(entities, dtype=torch.long).reshape(-1)
+    with open(path, 'w') as f:
+        for side in ('s', 'o'):
+            for at in range(0, ents.numel(), PROFILE_ROWS):
+                part = ents[at:at + PROFILE_ROWS]
+                rel, other, dist = complete_entities(model_or_tables, part, k, side=side, filter_index=filter_index)
+                for a, rs, xs, ds in zip(part.tolist(), rel.tolist(), other.tolist(), dist.tolist()):
+                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{d:.9g}\n" for i, (r, x, d) in enumerate(zip(rs, xs, ds), 1) if r >= 0]
+                    f.writelines(lines)
+                    n_lines += len(lines)
+    return n_lines
+
+
+# ------------------------------------------------------------------------------------------------
 # CLI (baselines/transe/main.py's hyperparameters as defaults)
 # ------------------------------------------------------------------------------------------------
 def build_parser():
@@ -795,6 +898,15 @@ def build_parser():
     p.add_argument('--complete-typed', action='store_true',
                    help='with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as '
                         'subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval')
+    p.add_argument('--profile-topk', type=int, default=0,
+                   help='after the final evaluation write, for every entity of --profile-entities, its K nearest NEW facts over all '
+                        'relations, as subject and as object (train + valid + test triplets and loops left out), to --profile-out; '
+                        '1..128, 0 = off')
+    p.add_argument('--profile-entities', type=str, default=None,
+                   help='the entities of --profile-topk: comma-separated ids, or a file with one id per line; default: every entity')
+    p.add_argument('--profile-out', type=str, default='transe_profiles.tsv',
+                   help='TSV written by --profile-topk: entity, side (s: the entity is the subject, o: the object), relation, other '
+                        'entity, rank (from 1), distance; the first five columns are those of train.py\'s --profile-out')
     return p
 
 
@@ -835,6 +947,8 @@ def check_args(args):
         raise ValueError('--complete-typed restricts the completions: it needs --complete-topk or --complete-threshold')
     if getattr(args, 'type_constrain', False) and not getattr(args, 'filtered_eval', False):
         raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, filtered_constrained')
+    if not 0 <= getattr(args, 'profile_topk', 0) <= ops.TOPK_MAX:
+        raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
 
 
 def main(args):
@@ -848,6 +962,9 @@ def main(args):
         torch.manual_seed(args.seed)
         np.random.seed(args.seed)
     data = load_data(args.dataset)
+    who = None
+    if getattr(args, 'profile_topk', 0) > 0:         # a bad id is refused before any training
+        who = profile_entities_arg(getattr(args, 'profile_entities', None), data.num_nodes)
     model = TransE(data.num_nodes, data.num_rels, dim=args.dim, p_norm=args.p_norm, norm_flag=bool(args.norm_flag))
     filt = None
     if args.filtered_eval:
@@ -889,6 +1006,11 @@ def main(args):
         n_lines = write_completions(args.complete_out, model, known, args.complete_topk, args.complete_threshold, typed)
         print(f'wrote {n_lines} completions (nearest new {"type-correct " if typed is not None else ""}triplets of the whole graph, '
               f'known triplets filtered) to {args.complete_out}')
+    if who is not None:
+        known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        n_lines = write_entity_profiles(args.profile_out, model, who, args.profile_topk, known)
+        print(f'wrote {n_lines} new facts around {len(who)} entities (nearest {args.profile_topk} over all relations, as subject and '
+              f'as object, known triplets filtered) to {args.profile_out}')
     return out
 
 

@@ -813,6 +813,29 @@ int gv_transe_topk_constrained(const float* q, int64_t m, const float* en, int v
                                int n_sets, const int32_t* cand_set, int k, int64_t* out_ids, float* out_dist, void* workspace,
                                void* stream);
 
+/* Per-entity completion for TransE (csrc/k_transe.hip): for every query entity a = ents[i] the k nearest pairs (r, x) over ALL
+ * relations, gv_entity_topk_scores with distances for logits.  en (n, dim) and rn (num_rels, dim) are the dense tables as
+ * gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
+ *   head = 0: q[c] = en[a][c] + rn[r][c], the facts (a, r, x)      head = 1: q[c] = en[a][c] - rn[r][c], the facts (x, r, a)
+ *   d[i, r, x] = ||q - en[x]||_p
+ * bit for bit gv_transe_distances on the row gv_transe_queries makes of (a, r, head): the query row is formed while it is staged,
+ * so neither the (entity x relation) query matrix nor per-relation results are stored.  ents int32 [m] (may repeat, any order; an
+ * id outside [0, n) gives an all-padding row).  No candidates: the ids filt_ent[filt_lo[a * num_rels + r] .. filt_hi[a * num_rels
+ * + r]) of relation r (one range per key, n * num_rels of them, each clamped into [0, n_filt_ent]; all three NULL: no filter) and
+ * x == a when exclude_self is set.  Order, a strict total one: the key ordered_u32(-d) << 32 | ~(r * n + x) of gv_transe_topk, i.e.
+ * distance ascending, then relation ascending, then entity ascending; NaN after every number (+inf included).  out_rel / out_ent
+ * int64 [m, k], out_dist fp32 [m, k]; a row with fewer than k candidates is padded with -1 / -1 / +inf; a zero distance is +0 and
+ * every NaN the quiet NaN 0x7fc00000.  1 <= k <= 128, 1 <= dim <= GV_TRANSE_MAX_DIM, p_norm 1 or 2, n * num_rels < 2^31 (refused
+ * otherwise), any m >= 0 (0: nothing launched).  A workgroup owns 64 query entities and span_tiles consecutive (relation, 64-entity
+ * tile) pairs of the r-major sequence; span_tiles = 0 takes the library's rule.  gv_transe_entity_topk_workspace_bytes(m, n,
+ * num_rels, k, span_tiles) = m * n_spans * k * 8 sizes the workspace (0 for sizes the entry refuses); workspace_bytes is checked
+ * against it.  The result does not depend on span_tiles.  No atomics. */
+int64_t gv_transe_entity_topk_workspace_bytes(int m, int n, int num_rels, int k, int span_tiles);
+int gv_transe_entity_topk(const int32_t* ents, int m, const float* en, const float* rn, int n, int num_rels, int dim, int head,
+                          int p_norm, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                          int exclude_self, int k, int span_tiles, int64_t* out_rel, int64_t* out_ent, float* out_dist,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Whole-graph triplet mining for TransE (csrc/k_transe_mine.hip): every (s, r, o) of the dense tables en (n, dim) and rn (num_rels,
  * dim), both as gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
  *   q[c] = en[s][c] + rn[r][c]      d[s, r, o] = ||q - en[o]||_p

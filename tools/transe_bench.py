@@ -8,6 +8,7 @@ process under a time limit and stops the bench at its first failure.
     python tools/transe_bench.py [--steps 200] [--warmup 20] [--limit 600]
     python tools/transe_bench.py --topk [--out profiles/transe_topk/bench.json]
     python tools/transe_bench.py --mine [--out profiles/transe_mine/bench.json]
+    python tools/transe_bench.py --profile [--profile-shapes fb,wn18rr,fb-dim500] [--out profiles/transe_profile/bench.json]
 
 --topk runs the link-prediction leg alone: both directions of the test split (40 932 queries), filter = train + valid + test,
 L1 and L2, k = 10 and 100; per configuration predict_topk (fused), predict_topk_unfused (materialised distances + sort) and
@@ -19,6 +20,12 @@ filtered, dim 200 with L1 and L2 and dim 500 with L1 and L2: mine_triplets (fuse
 materialised distances + torch selection) in the same process, each warmed up once, medians of --mine-repeats (unfused: half as
 many) synchronised runs; the two results are asserted bit-equal.  At dim 200 predict_topk(k = 128) over all N x R queries is timed
 once as well -- it answers another question (the best 128 per query, not the global K).
+
+--profile runs the per-entity completion leg alone: an entity's k nearest new facts over all relations (side 's', train + valid +
+test filtered, loops kept as predict_topk keeps them), FB15k-237 and WN18RR sizes, dim 200, L1 and L2, k = 10 and 100, for every
+entity and for a single one: complete_entities (fused) against predict_topk over all m x R queries + a torch merge, and against
+complete_entities_unfused -- on the all-entities set measured on 256 entities and scaled, which the JSON says.  All three in one
+process, each warmed up once, medians of --profile-repeats synchronised runs; the answers are asserted bit-equal.
 
 --opt runs the optimiser leg alone (python tools/transe_bench.py --opt [--out profiles/transe_opt/bench.json]): the whole step at
 the workload above with SGD, Adagrad, Adadelta and Adam, eager and captured, the four interleaved over --opt-rounds rounds of
@@ -211,6 +218,92 @@ def case_mine(steps, warmup, repeats=3):
     return res
 
 
+PROFILE_SHAPES = {'fb': ('FB15k-237-synthetic', 200), 'wn18rr': ('WN18RR-synthetic', 200), 'fb-dim500': ('FB15k-237-synthetic', 500)}
+
+
+def _merge_over_relations(ids, dist, m, num_rels, n, k):
+    """(m * R, k) answers of the queries (a, r), a-major, into each entity's k nearest (r, x): by distance, then relation, then
+    entity (the tables here give no NaN; padding is +inf with the id past every candidate's)."""
+    cid = torch.arange(num_rels, device=ids.device).view(1, num_rels, 1) * n + ids.view(m, num_rels, k)
+    cid = torch.where(ids.view(m, num_rels, k) < 0, torch.full_like(cid, num_rels * n), cid).view(m, num_rels * k)
+    by_id = torch.argsort(cid, dim=1, stable=True)
+    d = dist.view(m, num_rels * k).gather(1, by_id)
+    order = by_id.gather(1, torch.argsort(d, dim=1, stable=True)[:, :k])
+    best, d = cid.gather(1, order), dist.view(m, num_rels * k).gather(1, order)
+    gone = best >= num_rels * n
+    return torch.where(gone, -1, best // n), torch.where(gone, -1, best % n), d
+
+
+def case_profile(steps, warmup, repeats=3, shapes='fb,wn18rr', chunk=2048, unfused_entities=256):
+    """The per-entity completion leg: transe.complete_entities (fused) against (a) transe.predict_topk over all m * R queries of the
+    entities, ``chunk`` entities at a time, + a torch merge over each entity's R x k answers, and (b) transe.complete_entities_unfused
+    -- on the all-entities set measured on the first ``unfused_entities`` entities and scaled by m / that (both recorded)."""
+    from gcn_vae_amd import transe
+    from gcn_vae_amd.data import load_data
+    from gcn_vae_amd.ranking import FilterIndex
+
+    def say(*a):
+        print(*a, file=sys.stderr, flush=True)
+
+    def same(a, b):
+        return all(torch.equal(x, y) for x, y in zip(a[:2], b[:2])) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
+    res = dict(unit='ms; each route warmed up once, then the median of synchronised timed runs, all in one process', repeats=repeats,
+               side='s', exclude_self=False, shapes={})
+    for shape in shapes.split(','):
+        name, dim = PROFILE_SHAPES[shape]
+        data = load_data(name)
+        n, num_rels = data.num_nodes, data.num_rels
+        fi = FilterIndex(n, num_rels, data.train, data.valid, data.test, device='cuda')
+        torch.manual_seed(0)
+        model = transe.TransE(n, num_rels, dim=dim, p_norm=1, norm_flag=True).cuda()
+        ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+        rels = torch.arange(num_rels, device='cuda')
+        cases = []
+        for p in (1, 2):
+            tables = (ent, rel, p, True)
+            for query, ents in (('all', torch.arange(n, device='cuda')), ('single', torch.tensor([n // 2], device='cuda'))):
+                m = ents.numel()
+                sample = ents[:min(m, unfused_entities)]
+                for k in (10, 100):
+                    kw = dict(side='s', filter_index=fi, exclude_self=False)         # predict_topk keeps the loops
+
+                    def fused():
+                        return transe.complete_entities(tables, ents, k, **kw)
+
+                    def per_query():
+                        out = []
+                        for at in range(0, m, chunk):
+                            part = ents[at:at + chunk]
+                            ids, dist = transe.predict_topk(tables, part.repeat_interleave(num_rels), rels.repeat(part.numel()), k,
+                                                            direction='o', filter_index=fi)
+                            out.append(_merge_over_relations(ids, dist, part.numel(), num_rels, n, k))
+                        return tuple(torch.cat(t) for t in zip(*out))
+
+                    def unfused():
+                        return transe.complete_entities_unfused(tables, sample, k, **kw)
+
+                    got = fused()
+                    eq_q, eq_u = same(got, per_query()), same(tuple(t[:sample.numel()] for t in got), unfused())
+                    t_f = _repeat_ms(fused, repeats)
+                    t_q = _repeat_ms(per_query, max(1, repeats - 1) if query == 'all' else repeats)
+                    t_u = _repeat_ms(unfused, max(1, repeats - 1))
+                    scale = m / sample.numel()
+                    case = dict(p_norm=p, query=query, entities=m, k=k, fused=t_f, per_query=t_q,
+                                per_query_over_fused=t_q['median_ms'] / t_f['median_ms'], unfused_entities=sample.numel(),
+                                unfused_measured=t_u, unfused_ms_scaled=t_u['median_ms'] * scale,
+                                unfused_over_fused=t_u['median_ms'] * scale / t_f['median_ms'], equal_per_query=eq_q,
+                                equal_unfused=eq_u)
+                    say(f"{shape} L{p} {query:6s} k={k:3d}: fused {t_f['median_ms']:9.2f} ms | predict_topk + merge "
+                        f"{t_q['median_ms']:9.2f} ms ({case['per_query_over_fused']:.2f}x) | unfused {case['unfused_ms_scaled']:10.2f} ms "
+                        f"({case['unfused_over_fused']:.2f}x, measured on {sample.numel()} entities) | equal: {eq_q} {eq_u}")
+                    if not (eq_q and eq_u):
+                        raise SystemExit('the fused route differs from a cross-check route')
+                    cases.append(case)
+        res['shapes'][shape] = dict(dataset=name, entities=n, relations=num_rels, dim=dim, filter_triplets=int(fi.ent['o'].numel()),
+                                    cases=cases)
+    return res
+
+
 OPT_ALPHA = {'sgd': 1.0, 'adagrad': 0.1, 'adadelta': 1.0, 'adam': 1e-3}
 
 
@@ -311,7 +404,11 @@ def main():
     ap.add_argument('--mine-repeats', type=int, default=3)
     ap.add_argument('--opt', action='store_true', help='run the optimiser leg alone')
     ap.add_argument('--opt-rounds', type=int, default=5)
-    ap.add_argument('--out', default=None, help='with --topk / --mine / --opt: also write the JSON result to this file')
+    ap.add_argument('--profile', action='store_true', help='run the per-entity completion leg alone')
+    ap.add_argument('--profile-repeats', type=int, default=3)
+    ap.add_argument('--profile-shapes', default='fb,wn18rr', help=f'comma list of {sorted(PROFILE_SHAPES)}')
+    ap.add_argument('--out', default=None, help='with --topk / --mine / --opt / --profile: also write the JSON result to this file '
+                                                '(--profile: profiles/transe_profile/bench.json unless given)')
     a = ap.parse_args()
     if a.case == 'mine':
         print('RESULT ' + json.dumps(case_mine(a.steps, a.warmup, a.mine_repeats)))
@@ -322,12 +419,19 @@ def main():
     if a.case == 'opt':
         print('RESULT ' + json.dumps(case_opt(a.steps, a.warmup, a.opt_rounds)))
         return
-    if a.topk or a.mine or a.opt:
+    if a.case == 'profile':
+        print('RESULT ' + json.dumps(case_profile(a.steps, a.warmup, a.profile_repeats, a.profile_shapes)))
+        return
+    if a.profile and a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'transe_profile', 'bench.json')
+    if a.topk or a.mine or a.opt or a.profile:
         leg = ['--case', 'topk', '--topk-repeats', str(a.topk_repeats)] if a.topk else ['--case', 'mine', '--mine-repeats',
                                                                                            str(a.mine_repeats)]
         if a.opt:
             leg = ['--case', 'opt', '--opt-rounds', str(a.opt_rounds), '--steps', str(a.steps), '--warmup', str(a.warmup)]
-        # the mining leg reports each configuration on stderr as it finishes
+        if a.profile:
+            leg = ['--case', 'profile', '--profile-repeats', str(a.profile_repeats), '--profile-shapes', a.profile_shapes]
+        # the mining and the profile legs report each configuration on stderr as it finishes
         r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__)] + leg,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE if a.topk else None, text=True, cwd=ROOT)
         line = [x for x in r.stdout.splitlines() if x.startswith('RESULT ')]
