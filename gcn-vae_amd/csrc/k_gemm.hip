@@ -632,7 +632,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
 // survivor.  Once a list is warm almost nothing passes, so a tile costs a compare and a ballot per row.  Filtered columns get key 0
 // through a per-row cursor into the sorted filter list (the next listed id is kept in LDS: a window without entries reads
 // nothing).  The span's k keys per row go to the workspace.  Stage 2 (k_topk_merge): one wave per row merges the S span lists.
-// Key, list, cursor and merge live in k_topk.h, which gv_transe_topk (k_transe.hip) shares.
+// Key, list, cursor, the epilogue's set-up / row loop / hand-on (topk_span_*) and the merge live in k_topk.h, which the other three
+// span kernels share; a kernel keeps the making of its tile and, as lambdas, the row's cursor set-up and the row's key.
 struct TopkParams {
     GemmParams g;                 // a = Q, b = E (stored [v, h]), m, n = v, k = h
     const float* bias;
@@ -676,14 +677,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 5 : 1)
         load_a<false, BM, BK>(p, m0, 0, p.k, ra);
         load_b<true, BN, BK>(p, t_begin * BN, 0, p.k, rb);
     }
-    for (int i = threadIdx.x; i < BM * k; i += 256) lists[i] = 0ull;
-    fl[wid][lane] = 0;
-    if (threadIdx.x < BM) {
-        const int rl = threadIdx.x, row = m0 + rl;
-        thr[rl] = 0ull;
+    topk_span_clear<BM>(lists, k, fl, thr, lane, wid, [&](int rl) {
+        const int row = m0 + rl;
         topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && row < p.m, row, t_begin * BN, &cur[rl], &fhi[rl],
                           &nxt[rl]);
-    }
+    });
     const float bv = (!MC && tp.bias) ? *tp.bias : 0.f;
     const uint32_t* cand_row = CAND ? topk_cand_row(tp.cs, m0 + wid * (BM / 4), p.m, lane) : nullptr;
 
@@ -706,24 +704,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 5 : 1)
         __syncthreads();                                           // (Ls is rewritten after the next tile's first barrier)
 
         const int col = n0 + lane;
-        for (int i = 0; i < BM / 4; ++i) {
-            const int rl = wid * (BM / 4) + i;
-            if (m0 + rl >= p.m) break;
+        topk_span_select<NK, BM>(m0, p.m, lists, thr, k, lane, wid, [&](int rl, int i) {
             unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], col) : 0ull;
             if (filtered && nxt[rl] < n0 + BN &&                  // this row lists ids inside the tile: mark them, advance the cursor
                 topk_filter_window(tp.filt_ent, n0, (t - t_begin) * BM + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
                 key = 0ull;
             if (CAND && !topk_cand_member(cand_w, i, lane)) key = 0ull;
-            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
-        }
+            return key;
+        });
     }
-    // each wave hands its own rows' lists on (written by this wave only: no barrier)
-    for (int i = 0; i < BM / 4; ++i) {
-        const int rl = wid * (BM / 4) + i, row = m0 + rl;
-        if (row >= p.m) break;
-        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
-        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
-    }
+    topk_span_hand_on<BM>(m0, p.m, lists, k, tp.part, tp.n_spans, lane, wid);
 }
 
 // ---- per-entity completion (gv_entity_topk_scores): one list per query entity over ALL relations -------------------------------
@@ -749,19 +739,6 @@ struct EntityTopkParams {
     int topk;
     int span_tiles, n_spans;      // (relation, column tile) pairs per span (blockIdx.y = span)
     unsigned long long* part;     // [m][n_spans][topk]
-};
-
-struct EntityTopkOut {
-    int* rel;
-    int* ent;
-    float* logits;
-    int n;
-    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
-        const int id = topk_key_id(key);
-        rel[i] = id < 0 ? -1 : id / n;
-        ent[i] = id < 0 ? -1 : id % n;
-        logits[i] = topk_key_logit(key);
-    }
 };
 
 template <int NK>
@@ -800,64 +777,44 @@ __global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams
         for (int i = 0; i < APT; ++i) r[i] *= wv[i];
     };
 
-    int r = t_begin / col_tiles, ct = t_begin - r * col_tiles;
+    TopkPairWalk walk(t_begin, col_tiles);
     float ra[APT], rb[BN * BK / 256];
     if (t_begin < t_end) {
-        w_src += (size_t)r * ep.ld_w;
+        w_src += (size_t)walk.r * ep.ld_w;
         load_q(0, ra);
-        load_b<true, BN, BK>(p, ct * BN, 0, p.k, rb);
+        load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
     }
-    for (int i = threadIdx.x; i < BM * k; i += 256) lists[i] = 0ull;
-    fl[wid][lane] = 0;
-    if (threadIdx.x < BM) {
-        const int row = m0 + threadIdx.x;
-        const int a = row < p.m ? ep.ents[row] : -1;
-        ent_s[threadIdx.x] = (unsigned)a < (unsigned)p.n ? a : -1;
-        thr[threadIdx.x] = 0ull;
-    }
+    topk_span_clear<BM>(lists, k, fl, thr, lane, wid, [&](int rl) { topk_pair_entity(ep.ents, m0, rl, p.m, p.n, ent_s); });
     const float bv = ep.bias ? *ep.bias : 0.f;
 
     for (int t = t_begin; t < t_end; ++t) {
-        const int n0 = ct * BN;
+        const int n0 = walk.ct * BN;
         const f32x16 acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
-        const bool opens = ct == 0 || t == t_begin;                // the relation's (or the span's) first tile
-        const int r_now = r;
-        if (++ct == col_tiles) { ct = 0; ++r; w_src += ep.ld_w; }
+        const TopkPairTile tile = walk.step(col_tiles, t == t_begin);
+        if (walk.r != tile.r) w_src += ep.ld_w;
         if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
             load_q(0, ra);
-            load_b<true, BN, BK>(p, ct * BN, 0, p.k, rb);
+            load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
         }
         // (every wave is past score_tile's last barrier: nobody still reads the previous relation's cursors, or Ls)
-        if (opens && threadIdx.x < BM) {
-            const int rl = threadIdx.x, a = ent_s[rl];
-            topk_filter_begin(ep.filt_lo, ep.filt_hi, ep.filt_ent, ep.n_ent, filtered && a >= 0, (long long)a * ep.num_rels + r_now, n0,
-                              &cur[rl], &fhi[rl], &nxt[rl]);
-        }
+        if (tile.opens && threadIdx.x < BM)
+            topk_pair_reopen(ep.filt_lo, ep.filt_hi, ep.filt_ent, ep.n_ent, ent_s, ep.num_rels, tile, cur, fhi, nxt);
 #pragma unroll
         for (int i = 0; i < 16; ++i) Ls[(wm + (i & 3) + 8 * (i >> 2) + 4 * lhi) * LDL + wn + l31] = acc[i] + bv;
         __syncthreads();
 
         const int col = n0 + lane;
-        for (int i = 0; i < BM / 4; ++i) {
-            const int rl = wid * (BM / 4) + i;
-            if (m0 + rl >= p.m) break;
+        topk_span_select<NK, BM>(m0, p.m, lists, thr, k, lane, wid, [&](int rl, int) {
             const int a = ent_s[rl];
-            if (a < 0) continue;
-            unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], r_now * p.n + col) : 0ull;
+            unsigned long long key = col < p.n ? topk_key(Ls[rl * LDL + lane], tile.r * p.n + col) : 0ull;
             if (filtered && nxt[rl] < n0 + BN &&
                 topk_filter_window(ep.filt_ent, n0, (int)((unsigned)(t - t_begin) * BM + rl + 1u), lane, &cur[rl], &fhi[rl], &nxt[rl],
                                    fl[wid]))
                 key = 0ull;
-            if (ep.exclude_self && col == a) key = 0ull;
-            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
-        }
+            return ep.exclude_self && col == a ? 0ull : key;
+        }, [&](int rl) { return ent_s[rl] >= 0; });
     }
-    for (int i = 0; i < BM / 4; ++i) {
-        const int rl = wid * (BM / 4) + i, row = m0 + rl;
-        if (row >= p.m) break;
-        unsigned long long* dst = ep.part + ((size_t)row * ep.n_spans + blockIdx.y) * k;
-        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
-    }
+    topk_span_hand_on<BM>(m0, p.m, lists, k, ep.part, ep.n_spans, lane, wid);
 }
 
 // ---- the spread of a selected pair's probability over the samples (gv_pair_prob_std_mc) ----------------------------------
@@ -1511,7 +1468,7 @@ static int topk_launch(const char* name, const McSamples& mc, const float* q, in
     tp.part = (unsigned long long*)workspace;
     tp.cs = cs;
     return topk_span_merge<k_topk_span<1, CAND, MC>, k_topk_span<2, CAND, MC>, false, 64>(
-        name, dim3((m + 63) / 64, tp.n_spans), tp, tp.part, m, tp.n_spans, k, TopkLogitOut{out_ids, out_values}, (hipStream_t)stream);
+        name, dim3((m + 63) / 64, tp.n_spans), tp, tp.part, m, tp.n_spans, k, TopkOut<int, topk_key_logit>{out_ids, out_values}, (hipStream_t)stream);
 }
 
 extern "C" int gv_topk_scores(const float* q, int ld_q, const float* e, int ld_e, const float* bias, const int* filt_lo,
@@ -1593,18 +1550,9 @@ extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, c
     return launch_status(name);
 }
 
-// ---- per-entity completion (gv_entity_topk_scores) ------------------------------------------------------------------------------
-// spans of the R * ceil(N / 64) (relation, column tile) pairs: topk_spans' rule, up to 256 spans so that a single query entity
-// still fills the chip (its one row tile is all the parallelism there is besides)
-static void entity_topk_spans(long long m, int n, int num_rels, int* span_tiles, int* n_spans) {
-    topk_spans_of(m, (long long)num_rels * (((long long)n + 63) / 64), 256, span_tiles, n_spans);
-}
-
+// ---- per-entity completion (gv_entity_topk_scores): the spans and their checks are entity_query_* of k_query_args.h ------------
 extern "C" int64_t gv_entity_topk_scores_workspace_bytes(int m, int n, int num_rels, int k) {
-    if (m <= 0 || n <= 0 || num_rels <= 0 || (long long)n * num_rels > INT_MAX || k < 1 || k > TOPK_MAX) return 0;
-    int span_tiles = 0, n_spans = 0;
-    entity_topk_spans(m, n, num_rels, &span_tiles, &n_spans);
-    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+    return entity_query_workspace_bytes(m, n, num_rels, k, 0);      // (the library's rule: a caller's span_tiles sizes its own)
 }
 
 extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
@@ -1614,10 +1562,7 @@ extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e,
     const char* name = "gv_entity_topk_scores";
     GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE,
                "gv_entity_topk_scores: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", m, n, num_rels, h, n_filt_ent);
-    GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "gv_entity_topk_scores: n * num_rels = %lld does not fit 31 bits",
-               (long long)n * num_rels);
-    GV_CHECK(query_k(name, k));
-    GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "gv_entity_topk_scores: span_tiles=%d (0: the library's rule)", span_tiles);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
     GV_CHECK(query_leading(name, ld_e, ld_w, h));
     GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
     if (m == 0) return GV_OK;
@@ -1630,21 +1575,11 @@ extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e,
     ep.bias = bias;
     ep.filt_lo = filt_lo; ep.filt_hi = filt_hi; ep.filt_ent = filt_ent; ep.n_ent = n_filt_ent;
     ep.topk = k;
-    const long long tiles = (long long)num_rels * (((long long)n + 63) / 64);
-    if (span_tiles > 0) {
-        ep.span_tiles = (int)std::min<long long>(span_tiles, tiles);
-        ep.n_spans = (int)((tiles + ep.span_tiles - 1) / ep.span_tiles);
-    } else {
-        entity_topk_spans(m, n, num_rels, &ep.span_tiles, &ep.n_spans);
-    }
-    GV_REQUIRE(ep.n_spans <= 65535, GV_ERR_SHAPE, "gv_entity_topk_scores: span_tiles=%d gives %d spans (at most 65535)", span_tiles,
-               ep.n_spans);
-    const int64_t need = (int64_t)m * ep.n_spans * k * (int64_t)sizeof(unsigned long long);
-    GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "gv_entity_topk_scores: workspace of %lld bytes, %lld needed",
-               (long long)workspace_bytes, (long long)need);
+    entity_query_spans(m, n, num_rels, span_tiles, &ep.span_tiles, &ep.n_spans);
+    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, ep.n_spans, workspace_bytes));
     ep.part = (unsigned long long*)workspace;
     return topk_span_merge<k_entity_topk_span<1>, k_entity_topk_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
-        name, dim3((m + 63) / 64, ep.n_spans), ep, ep.part, m, ep.n_spans, k, EntityTopkOut{out_rel, out_ent, out_logits, n},
+        name, dim3((m + 63) / 64, ep.n_spans), ep, ep.part, m, ep.n_spans, k, TopkPairOut<int, topk_key_logit>{out_rel, out_ent, out_logits, n},
         (hipStream_t)stream);
 }
 

@@ -63,4 +63,44 @@ inline int query_filter_needs(const char* name, const void* filt_lo, bool given,
     return GV_OK;
 }
 
+// ---- the per-entity queries (gv_entity_topk_scores, gv_transe_entity_topk) -------------------------------------------------------
+// spans of the R * ceil(N / 64) (relation, 64-column tile) pairs: span_tiles of them each when the caller says so (> 0), else
+// topk_spans' rule with up to 256 spans, so that a single query entity still fills the chip (its one row tile is all the
+// parallelism there is besides)
+inline void entity_query_spans(long long m, int n, int num_rels, int span_tiles, int* per, int* n_spans) {
+    const long long tiles = (long long)num_rels * (((long long)n + 63) / 64);
+    if (span_tiles > 0) {
+        *per = (int)std::min<long long>(span_tiles, tiles);
+        *n_spans = (int)((tiles + *per - 1) / *per);
+    } else {
+        topk_spans_of(m, tiles, 256, per, n_spans);
+    }
+}
+
+// what gv_*_workspace_bytes answer: the spans' lists, 0 for sizes the entry refuses
+inline int64_t entity_query_workspace_bytes(int m, int n, int num_rels, int k, int span_tiles) {
+    if (m <= 0 || n <= 0 || num_rels <= 0 || (long long)n * num_rels > INT_MAX || k < 1 || k > TOPK_MAX || span_tiles < 0) return 0;
+    int per = 0, n_spans = 0;
+    entity_query_spans(m, n, num_rels, span_tiles, &per, &n_spans);
+    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+// what follows an entry's own sizes: a candidate (r, x) is the id r * n + x of a key; k; the caller's span
+inline int entity_query_shape(const char* name, int n, int num_rels, int k, int span_tiles) {
+    GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "%s: n * num_rels = %lld does not fit 31 bits", name,
+               (long long)n * num_rels);
+    GV_CHECK(query_k(name, k));
+    GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "%s: span_tiles=%d (0: the library's rule)", name, span_tiles);
+    return GV_OK;
+}
+
+// the spans are a grid dimension; the workspace holds every span's lists
+inline int entity_query_workspace(const char* name, int m, int k, int span_tiles, int n_spans, int64_t workspace_bytes) {
+    GV_REQUIRE(n_spans <= 65535, GV_ERR_SHAPE, "%s: span_tiles=%d gives %d spans (at most 65535)", name, span_tiles, n_spans);
+    const int64_t need = (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+    GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed", name, (long long)workspace_bytes,
+               (long long)need);
+    return GV_OK;
+}
+
 }  // namespace gv

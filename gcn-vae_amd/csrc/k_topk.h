@@ -1,7 +1,9 @@
-// Top-k selection shared by gv_topk_scores (k_gemm.hip: MFMA logits) and gv_transe_topk (k_transe.hip: L1 / L2 distances): the
-// ordered 64-bit key, the per-row sorted list with its wave-wide insert, the cursor over a row's sorted filter list, the span
-// geometry, the merge of the spans' lists and the host's launch of the pair.  The two kernels differ in how a 64 x 64 tile of values is made, not in how the
-// best k of a row are kept.
+// Top-k selection shared by the four span kernels -- k_topk_span, k_entity_topk_span (k_gemm.hip: MFMA logits) and
+// k_transe_topk_span, k_transe_entity_topk_span (k_transe.hip: L1 / L2 distances): the ordered 64-bit key, the per-row sorted list
+// with its wave-wide insert, the cursor over a row's sorted filter list, the selection epilogue (set-up, the wave's row loop, the
+// hand-on of the lists), the per-entity kernels' walk over (relation, column tile) pairs, the span geometry, the merge of the spans'
+// lists with its two output decoders and the host's launch of the pair.  The kernels differ in how a 64 x 64 tile of values is
+// made, not in how the best k of a row are kept.
 //
 // Candidates are ordered by a 64-bit key, larger = better:
 //   key = ordered_u32(value) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
@@ -167,14 +169,110 @@ __device__ __forceinline__ unsigned long long topk_cand_pair(const TopkCand& cs,
     return cw;
 }
 
+// ---- stage 1's selection epilogue: what the four span kernels do around their own tile of values ---------------------------
+// A span kernel is 256 threads on a ROWS-row query tile: it declares the LDS state itself (lists [ROWS][k], thr [ROWS], the
+// cursor's cur / fhi / nxt [ROWS], fl [4][64]) and hands it to these pieces by pointer.  Wave w owns rows w * ROWS / 4 onwards.
+// set-up, every thread: empty lists (key 0), no flag set, each row's k-th key 0 -- and row_setup(rl), what else thread rl < ROWS
+// prepares for its row.  The tile's first barrier publishes it.  (k_transe_entity_topk_span keeps its own copy: see there.)
+template <int ROWS, class RowSetup>
+__device__ __forceinline__ void topk_span_clear(unsigned long long* lists, int k, int (*fl)[64], unsigned long long* thr, int lane,
+                                                int wid, RowSetup&& row_setup) {
+    for (int i = threadIdx.x; i < ROWS * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (threadIdx.x < ROWS) {
+        thr[threadIdx.x] = 0ull;
+        row_setup((int)threadIdx.x);
+    }
+}
+
+struct TopkEveryRow {
+    __device__ __forceinline__ bool operator()(int) const { return true; }
+};
+
+// The wave's rows of the tile at hand, one lane per column: row_key(rl, i) is the lane's key of tile row rl (the wave's i-th) --
+// the kernel's own value read, id, filter window and drop rule -- and what beats the row's k-th key goes into the row's list.  A
+// row that row_live(rl) denies is passed over (a per-entity row without an entity); rows from m on (row0 + rl) end the loop.
+template <int NK, int ROWS, class Idx, class RowKey, class RowLive = TopkEveryRow>
+__device__ __forceinline__ void topk_span_select(Idx row0, Idx m, unsigned long long* lists, unsigned long long* thr, int k,
+                                                 int lane, int wid, RowKey&& row_key, RowLive&& row_live = RowLive{}) {
+    for (int i = 0; i < ROWS / 4; ++i) {
+        const int rl = wid * (ROWS / 4) + i;
+        if (row0 + rl >= m) break;
+        if (!row_live(rl)) continue;
+        topk_list_update<NK>(row_key(rl, i), lists + rl * k, &thr[rl], k, lane);
+    }
+}
+
+// the hand-on: each wave copies its own rows' lists to part[row][span][k] (written by this wave only: no barrier)
+template <int ROWS, class Idx>
+__device__ __forceinline__ void topk_span_hand_on(Idx row0, Idx m, const unsigned long long* lists, int k, unsigned long long* part,
+                                                  int n_spans, int lane, int wid) {
+    for (int i = 0; i < ROWS / 4; ++i) {
+        const int rl = wid * (ROWS / 4) + i;
+        const Idx row = row0 + rl;
+        if (row >= m) break;
+        unsigned long long* dst = part + ((size_t)row * n_spans + blockIdx.y) * k;
+        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// ---- the per-entity kernels' columns: the sequence of (relation, 64-column tile) pairs, r-major -------------------------------
+// Tile t = r * col_tiles + ct, candidate id = r * N + x.  A span starts at tile t_begin.
+struct TopkPairTile {
+    int r, c0;      // the tile's relation and first column
+    bool opens;     // the relation's (or the span's) first tile: the rows' filter cursors are re-opened
+};
+
+struct TopkPairWalk {
+    int r, ct;      // the NEXT tile's relation and column tile
+    __device__ __forceinline__ TopkPairWalk(int t_begin, int col_tiles) : r(t_begin / col_tiles), ct(t_begin - r * col_tiles) {}
+    // the pair at hand; the walk moves on to the next one (`first`: t == t_begin)
+    __device__ __forceinline__ TopkPairTile step(int col_tiles, bool first) {
+        const TopkPairTile now{r, ct * 64, ct == 0 || first};
+        if (++ct == col_tiles) { ct = 0; ++r; }
+        return now;
+    }
+};
+
+// set-up, thread rl < ROWS: the row's entity into ent_s (-1: no such row, or an id outside [0, n))
+__device__ __forceinline__ void topk_pair_entity(const int* ents, int row0, int rl, int m, int n, int* ent_s) {
+    const int a = row0 + rl < m ? ents[row0 + rl] : -1;
+    ent_s[rl] = (unsigned)a < (unsigned)n ? a : -1;
+}
+
+// at a tile that `opens`, thread rl < ROWS: the row's cursor on the list of key a * R + r, from the tile's first column on.  The
+// caller places this where no wave still reads the previous relation's cursors (each kernel says where that is).
+__device__ __forceinline__ void topk_pair_reopen(const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_ent, const int* ent_s,
+                                                 int num_rels, const TopkPairTile& tile, int* cur, int* fhi, int* nxt) {
+    const int rl = threadIdx.x, a = ent_s[rl];
+    topk_filter_begin(filt_lo, filt_hi, filt_ent, n_ent, filt_lo != nullptr && a >= 0, (long long)a * num_rels + tile.r, tile.c0,
+                      &cur[rl], &fhi[rl], &nxt[rl]);
+}
+
 // ---- stage 2: one wave per row merges the n_spans sorted lists of k keys and hands the first k to `out` --------------------
-// Out::put(i, key) decodes key into entry i of the (m, k) outputs.
-struct TopkLogitOut {
-    int* ids;
-    float* logits;
+// Out::put(i, key) decodes key into entry i of the (m, k) outputs.  Id: the outputs' integer type; Value: the key's value back
+// (topk_key_logit, or te_key_dist of k_transe.hip for a key made of -distance).
+template <class Id, float (*Value)(unsigned long long)>
+struct TopkOut {                     // id / value
+    Id* ids;
+    float* values;
     __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
-        ids[i] = topk_key_id(key);
-        logits[i] = topk_key_logit(key);
+        ids[i] = (Id)topk_key_id(key);
+        values[i] = Value(key);
+    }
+};
+
+template <class Id, float (*Value)(unsigned long long)>
+struct TopkPairOut {                 // relation / entity / value: the candidate id r * n + x taken apart (key 0 -> -1 / -1)
+    Id* rel;
+    Id* ent;
+    float* values;
+    int n;
+    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
+        const int id = topk_key_id(key);
+        rel[i] = id < 0 ? -1 : id / n;
+        ent[i] = id < 0 ? -1 : id % n;
+        values[i] = Value(key);
     }
 };
 

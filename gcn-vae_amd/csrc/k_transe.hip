@@ -653,8 +653,9 @@ __global__ __launch_bounds__(256) void k_transe_rank(const float* __restrict__ q
 // after te_tile() go through LDS (ds) into one lane per column: wave w takes rows 16 w .. 16 w + 15, keys the column's distance as
 // topk_key(-d, id) -- larger key = smaller distance, ties by lower id, NaN below every number -- and inserts what beats the row's
 // running k-th key into the row's sorted LDS list.  Columns past v and listed ids get key 0 (no candidate).  The span's lists go to
-// the workspace; k_topk_merge<NK, TeDistOut> merges them, one wave per row.  Nothing depends on the span count: every span list is
-// the exact best k of its columns under a strict total order, and so is the merge.
+// the workspace; k_topk_merge merges them, one wave per row, and TopkOut<int64_t, te_key_dist> decodes.  Nothing depends on the span
+// count: every span list is the exact best k of its columns under a strict total order, and so is the merge.  Set-up, row loop and
+// hand-on are topk_span_clear / topk_span_select / topk_span_hand_on of k_topk.h; the lambdas below are what is this kernel's own.
 struct TeTopkParams {
     const float* q;
     const float* en;
@@ -687,13 +688,10 @@ __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp)
     const int t_begin = blockIdx.y * tp.span_tiles;
     const int t_end = min(t_begin + tp.span_tiles, (tp.v + TE_TE - 1) / TE_TE);
     const bool filtered = tp.filt_lo != nullptr;
-    for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
-    fl[wid][lane] = 0;
-    if (tid < TE_TQ) {
-        thr[tid] = 0ull;
-        topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && q0 + tid < tp.m, q0 + tid, t_begin * TE_TE,
-                          &cur[tid], &fhi[tid], &nxt[tid]);
-    }
+    topk_span_clear<TE_TQ>(lists, k, fl, thr, lane, wid, [&](int rl) {
+        topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && q0 + rl < tp.m, q0 + rl, t_begin * TE_TE,
+                          &cur[rl], &fhi[rl], &nxt[rl]);
+    });
     const uint32_t* cand_row = CAND ? topk_cand_row(tp.cs, q0 + wid * (TE_TQ / 4), tp.m, lane) : nullptr;
     for (int t = t_begin; t < t_end; ++t) {
         const int e0 = t * TE_TE;
@@ -706,25 +704,16 @@ __global__ __launch_bounds__(256) void k_transe_topk_span(const TeTopkParams tp)
             *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
         __syncthreads();
         const int col = e0 + lane;
-        for (int i = 0; i < TE_TQ / 4; ++i) {
-            const int rl = wid * (TE_TQ / 4) + i;
-            if (q0 + rl >= tp.m) break;
+        topk_span_select<NK, TE_TQ>(q0, tp.m, lists, thr, k, lane, wid, [&](int rl, int i) {
             unsigned long long key = col < tp.v ? topk_key(-ds[rl * TE_LDD + lane], col) : 0ull;
             if (filtered && nxt[rl] < e0 + TE_TE &&
                 topk_filter_window(tp.filt_ent, e0, (t - t_begin) * TE_TQ + rl + 1, lane, &cur[rl], &fhi[rl], &nxt[rl], fl[wid]))
                 key = 0ull;
             if (CAND && !topk_cand_member(cand_w, i, lane)) key = 0ull;
-            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
-        }
+            return key;
+        });
     }
-    // each wave hands its own rows' lists on (written by this wave only: no barrier)
-    for (int i = 0; i < TE_TQ / 4; ++i) {
-        const int rl = wid * (TE_TQ / 4) + i;
-        const int64_t row = q0 + rl;
-        if (row >= tp.m) break;
-        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
-        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
-    }
+    topk_span_hand_on<TE_TQ>(q0, tp.m, lists, k, tp.part, tp.n_spans, lane, wid);
 }
 
 // the key of -distance back to the distance: key 0 (no candidate) -> +inf; zero -> +0; NaN -> the one quiet NaN
@@ -733,16 +722,6 @@ __device__ __forceinline__ float te_key_dist(unsigned long long key) {
     const unsigned b = __float_as_uint(x) ^ 0x80000000u;
     return x != x ? x : __uint_as_float(b == 0x80000000u ? 0u : b);
 }
-
-// (key 0 -> id -1)
-struct TeDistOut {
-    int64_t* ids;
-    float* dist;
-    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
-        ids[i] = (int64_t)topk_key_id(key);
-        dist[i] = te_key_dist(key);
-    }
-};
 
 // ---- per-entity completion (gv_transe_entity_topk): one list per query entity over ALL relations ---------------------------------
 // Query row i is entity a = ents[i]; its candidates are the pairs (r, x) at distance ||(en[a] +- rn[r]) - en[x]||_p -- k_transe_topk_span
@@ -784,19 +763,19 @@ __global__ __launch_bounds__(256) void k_transe_entity_topk_span(const TeEntityT
     const int t_begin = blockIdx.y * tp.span_tiles;
     const int t_end = min(t_begin + tp.span_tiles, tp.num_rels * col_tiles);
     const bool filtered = tp.filt_lo != nullptr, head = tp.head != 0;
+    // topk_span_clear's lines with the threshold cleared AFTER the entity's fetch: through the shared set-up (threshold first) the
+    // kernel is one instruction shorter, its loops sit 4 bytes earlier and the fused route measured 1.7 - 3.2 % slower (NOTES.md)
     for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
     fl[wid][lane] = 0;
     if (tid < TE_TQ) {
-        const int a = m0 + tid < tp.m ? tp.ents[m0 + tid] : -1;
-        ent_s[tid] = (unsigned)a < (unsigned)tp.n ? a : -1;
+        topk_pair_entity(tp.ents, m0, tid, tp.m, tp.n, ent_s);
         thr[tid] = 0ull;
     }
-    int r = t_begin / col_tiles, ct = t_begin - r * col_tiles;
+    TopkPairWalk walk(t_begin, col_tiles);
     for (int t = t_begin; t < t_end; ++t) {
-        const int e0 = ct * TE_TE, r_now = r;
-        const bool opens = ct == 0 || t == t_begin;                // the relation's (or the span's) first tile
-        if (++ct == col_tiles) { ct = 0; ++r; }
-        const float* __restrict__ rr = tp.rn + (size_t)r_now * dim;
+        const TopkPairTile tile = walk.step(col_tiles, t == t_begin);
+        const int e0 = tile.c0;
+        const float* __restrict__ rr = tp.rn + (size_t)tile.r * dim;
         float acc[4][4];
         // te_tile_with's first barrier publishes the set-up above and ends the last tile's reads of ds and of the cursors
         te_tile_with(
@@ -807,52 +786,26 @@ __global__ __launch_bounds__(256) void k_transe_entity_topk_span(const TeEntityT
                 return head ? x - y : x + y;
             },
             tp.en, tp.n, dim, tp.p, e0, qs, es, acc);
-        if (opens && tid < TE_TQ) {
-            const int a = ent_s[tid];
-            topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && a >= 0, (long long)a * tp.num_rels + r_now, e0,
-                              &cur[tid], &fhi[tid], &nxt[tid]);
-        }
+        // (every wave is past te_tile_with's last barrier: nobody still reads the previous relation's cursors)
+        if (tile.opens && tid < TE_TQ)
+            topk_pair_reopen(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, ent_s, tp.num_rels, tile, cur, fhi, nxt);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
             *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
         __syncthreads();
         const int col = e0 + lane;
-        for (int i = 0; i < TE_TQ / 4; ++i) {
-            const int rl = wid * (TE_TQ / 4) + i;
-            if (m0 + rl >= tp.m) break;
+        topk_span_select<NK, TE_TQ>(m0, tp.m, lists, thr, k, lane, wid, [&](int rl, int) {
             const int a = ent_s[rl];
-            if (a < 0) continue;
-            unsigned long long key = col < tp.n ? topk_key(-ds[rl * TE_LDD + lane], r_now * tp.n + col) : 0ull;
+            unsigned long long key = col < tp.n ? topk_key(-ds[rl * TE_LDD + lane], tile.r * tp.n + col) : 0ull;
             if (filtered && nxt[rl] < e0 + TE_TE &&
                 topk_filter_window(tp.filt_ent, e0, (int)((unsigned)(t - t_begin) * TE_TQ + rl + 1u), lane, &cur[rl], &fhi[rl], &nxt[rl],
                                    fl[wid]))
                 key = 0ull;
-            if (tp.exclude_self && col == a) key = 0ull;
-            topk_list_update<NK>(key, lists + rl * k, &thr[rl], k, lane);
-        }
+            return tp.exclude_self && col == a ? 0ull : key;
+        }, [&](int rl) { return ent_s[rl] >= 0; });
     }
-    // each wave hands its own rows' lists on (written by this wave only: no barrier)
-    for (int i = 0; i < TE_TQ / 4; ++i) {
-        const int rl = wid * (TE_TQ / 4) + i, row = m0 + rl;
-        if (row >= tp.m) break;
-        unsigned long long* dst = tp.part + ((size_t)row * tp.n_spans + blockIdx.y) * k;
-        for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
-    }
+    topk_span_hand_on<TE_TQ>(m0, tp.m, lists, k, tp.part, tp.n_spans, lane, wid);
 }
-
-// TeDistOut with the candidate id r * n + x taken apart
-struct TeEntityDistOut {
-    int64_t* rel;
-    int64_t* ent;
-    float* dist;
-    int n;
-    __device__ __forceinline__ void put(size_t i, unsigned long long key) const {
-        const int id = topk_key_id(key);
-        rel[i] = id < 0 ? -1 : id / n;
-        ent[i] = id < 0 ? -1 : id % n;
-        dist[i] = te_key_dist(key);
-    }
-};
 
 }  // namespace gv
 
@@ -1027,7 +980,7 @@ static int transe_topk_launch(const char* name, const float* q, int64_t m, const
     topk_spans(m, v, &tp.span_tiles, &tp.n_spans);
     return topk_span_merge<k_transe_topk_span<1, CAND>, k_transe_topk_span<2, CAND>, true, TE_TQ>(
         name, dim3((unsigned)((m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), tp, tp.part, (int)m, tp.n_spans, k,
-        TeDistOut{out_ids, out_dist}, GV_ST);
+        TopkOut<int64_t, te_key_dist>{out_ids, out_dist}, GV_ST);
 }
 
 extern "C" int gv_transe_topk(const float* q, int64_t m, const float* en, int v, int dim, int p_norm, const int32_t* filt_lo,
@@ -1059,24 +1012,11 @@ extern "C" int gv_transe_topk_constrained(const float* q, int64_t m, const float
                                     TopkCand{cand, cand_set, ld_cand, n_sets}, k, out_ids, out_dist, workspace, stream);
 }
 
-// ---- per-entity completion (gv_transe_entity_topk) -------------------------------------------------------------------------------
-// spans of the R * ceil(N / 64) (relation, entity tile) pairs: span_tiles of them each when the caller says so, else topk_spans'
-// rule with up to 256 spans, so that a single query entity still fills the chip (gv_entity_topk_scores' geometry)
-static void transe_entity_topk_spans(int m, int n, int num_rels, int span_tiles, int* per, int* n_spans) {
-    const long long tiles = (long long)num_rels * (((long long)n + TE_TE - 1) / TE_TE);
-    if (span_tiles > 0) {
-        *per = (int)std::min<long long>(span_tiles, tiles);
-        *n_spans = (int)((tiles + *per - 1) / *per);
-    } else {
-        topk_spans_of(m, tiles, 256, per, n_spans);
-    }
-}
+// ---- per-entity completion (gv_transe_entity_topk): gv_entity_topk_scores' geometry, entity_query_* of k_query_args.h ----------
+static_assert(TE_TQ == 64 && TE_TE == 64, "the span helpers of k_topk.h and entity_query_spans count 64 x 64 tiles");
 
 extern "C" int64_t gv_transe_entity_topk_workspace_bytes(int m, int n, int num_rels, int k, int span_tiles) {
-    if (m <= 0 || n <= 0 || num_rels <= 0 || (long long)n * num_rels > INT_MAX || k < 1 || k > TOPK_MAX || span_tiles < 0) return 0;
-    int per = 0, n_spans = 0;
-    transe_entity_topk_spans(m, n, num_rels, span_tiles, &per, &n_spans);
-    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+    return entity_query_workspace_bytes(m, n, num_rels, k, span_tiles);
 }
 
 extern "C" int gv_transe_entity_topk(const int32_t* ents, int m, const float* en, const float* rn, int n, int num_rels, int dim, int head,
@@ -1087,22 +1027,16 @@ extern "C" int gv_transe_entity_topk(const int32_t* ents, int m, const float* en
     GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) && n_filt_ent >= 0,
                GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", name, m, n, num_rels, dim,
                GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
-    GV_REQUIRE((long long)n * num_rels <= INT_MAX, GV_ERR_SHAPE, "%s: n * num_rels = %lld does not fit 31 bits", name,
-               (long long)n * num_rels);
-    GV_CHECK(query_k(name, k));
-    GV_REQUIRE(span_tiles >= 0, GV_ERR_SHAPE, "%s: span_tiles=%d (0: the library's rule)", name, span_tiles);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
     GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
     if (m == 0) return GV_OK;
     GV_CHECK(query_pointers(name, ents && en && rn && out_rel && out_ent && out_dist && workspace));
     TeEntityTopkParams tp{en, rn, ents, filt_lo, filt_hi, filt_ent, m, n, num_rels, dim, p_norm, head != 0, exclude_self != 0,
                           n_filt_ent, k, 0, 0, (unsigned long long*)workspace};
-    transe_entity_topk_spans(m, n, num_rels, span_tiles, &tp.span_tiles, &tp.n_spans);
-    GV_REQUIRE(tp.n_spans <= 65535, GV_ERR_SHAPE, "%s: span_tiles=%d gives %d spans (at most 65535)", name, span_tiles, tp.n_spans);
-    const int64_t need = (int64_t)m * tp.n_spans * k * (int64_t)sizeof(unsigned long long);
-    GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed", name, (long long)workspace_bytes,
-               (long long)need);
+    entity_query_spans(m, n, num_rels, span_tiles, &tp.span_tiles, &tp.n_spans);
+    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, tp.n_spans, workspace_bytes));
     // (<= 64 KiB of lists beside 37 KiB static: the limit is raised for either NK)
     return topk_span_merge<k_transe_entity_topk_span<1>, k_transe_entity_topk_span<2>, true, TE_TQ>(
         name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), tp, tp.part, m, tp.n_spans, k,
-        TeEntityDistOut{out_rel, out_ent, out_dist, n}, GV_ST);
+        TopkPairOut<int64_t, te_key_dist>{out_rel, out_ent, out_dist, n}, GV_ST);
 }

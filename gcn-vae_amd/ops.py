@@ -765,6 +765,20 @@ def _entity_topk_operands(ents, emb, w):
     return ents.numel(), n, num_rels, h
 
 
+def _entity_topk_args(ents, span, tile, filt, m, n, num_rels, k, id_dtype, device):
+    """What the two per-entity wrappers do once the operands' shapes and k stand: the checks of ``span`` (``tile``: how the wrapper
+    calls a tile), of the query entities' range and of the filter over the N * R keys, then the outputs.  Returns (``_filter_args``'
+    tuple, (rel, ent, values), ents32, span_tiles) -- span_tiles 0 is the library's rule, else ``span`` held to the number of pairs."""
+    if span is not None and int(span) < 1:
+        raise ValueError(f'span counts (relation, {tile} tile) pairs per workgroup: at least 1, got {span}')
+    if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
+        raise ValueError(f'query entities must lie in [0, {n})')
+    filt32 = _filter_args(*filt, n * num_rels, n, device)
+    outs = tuple(torch.empty(m, k, dtype=t, device=device) for t in (id_dtype, id_dtype, torch.float32))
+    span_tiles = 0 if span is None else min(int(span), num_rels * ((n + 63) // 64))
+    return filt32, outs, ents.to(device=device, dtype=torch.int32).contiguous(), span_tiles
+
+
 def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
     """Per-entity completion: for every query entity ``a = ents[i]`` the ``k`` best pairs (r, x) over ALL relations under
     ``logit[i, r, x] = (emb[a] * w[r]) . emb[x] (+ bias)`` -- bit for bit ``gemm(mul(emb[a], w[r]), emb^T, precision='f32') + bias``,
@@ -778,27 +792,19 @@ def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, f
     with -1 / -1 / -inf past a row's last candidate; -0 is reported as +0 and every NaN as the one quiet NaN."""
     m, n, num_rels, h = _entity_topk_operands(ents, emb, w)
     k = _topk_arg(k)
-    if span is not None and int(span) < 1:
-        raise ValueError(f'span counts (relation, column tile) pairs per workgroup: at least 1, got {span}')
-    if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
-        raise ValueError(f'query entities must lie in [0, {n})')
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, n * num_rels, n, emb.device)
+    (lo32, hi32, ent32, n_ent), (rel, ent, logits), ents32, span_tiles = _entity_topk_args(
+        ents, span, 'column', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, emb.device)
     emb, ld_e = _row_major(emb, 'emb')
     w, ld_w = _row_major(w, 'w')
     dev = emb.device
-    rel = torch.empty(m, k, dtype=torch.int32, device=dev)
-    ent = torch.empty(m, k, dtype=torch.int32, device=dev)
-    logits = torch.empty(m, k, dtype=torch.float32, device=dev)
     if m == 0:
         return rel.long(), ent.long(), logits
-    ents32 = ents.to(device=dev, dtype=torch.int32).contiguous()
     bias = _bias_arg(bias)
-    if span is None:
-        span_tiles, ws_bytes = 0, int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
-    else:
+    if span_tiles:      # gv_entity_topk_scores_workspace_bytes takes no span_tiles (the ABI stays): a given span's lists are sized here
         tiles = num_rels * ((n + 63) // 64)
-        span_tiles = min(int(span), tiles)
         ws_bytes = m * ((tiles + span_tiles - 1) // span_tiles) * k * 8
+    else:
+        ws_bytes = int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     lib.call('gv_entity_topk_scores', ptr(ents32), m, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
              int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(logits), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
@@ -3636,15 +3642,25 @@ def transe_rank_filtered(q, en, target, p_norm, filt_lo=None, filt_hi=None, filt
     """(raw, filtered) 0-based mid-ranks of ``target[i]`` under score = -||q[i] - en[j]||_p -- ``ranking.sort_and_rank`` on
     ``transe_distances`` bit for bit -- without the distance matrix (gv_transe_rank_filtered).  The filter ranges are
     ``rank_scores_filtered``'s; without them the filtered rank equals the raw one."""
+    return _transe_rank('gv_transe_rank_filtered', q, en, target, p_norm, (filt_lo, filt_hi, filt_ent))
+
+
+def _transe_rank(entry, q, en, target, p_norm, filt, cand=None):
+    """The two ``transe_rank_*`` wrappers, with ``_rank_scores``' ``filt`` and ``cand``: the checks, the counts and the call.  One
+    rank tensor per count the entry takes; the constrained entry leaves the filtered ones unwritten without a filter (None)."""
     q, en = _transe_operands(q, en)
     p_norm = _p_norm(p_norm)
     m, v = q.shape[0], en.shape[0]
     tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    counts = torch.zeros(2, max(m, 1), dtype=torch.int32, device=q.device)
-    lib.call('gv_transe_rank_filtered', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
-             ptr(counts[0]), ptr(counts[1]), lib.stream())
-    return _ranks(counts, m)
+    lo32, hi32, ent32, _ = _filter_args(*filt, m, v, q.device)
+    sets = () if cand is None else _cand_args(*cand, m, v, q.device)
+    counts = torch.zeros(2 if cand is None else 4, max(m, 1), dtype=torch.int32, device=q.device)
+    given = cand is None or lo32 is not None
+    set_args = () if cand is None else (ptr(sets[0]), sets[1], sets[2], ptr(sets[3]))
+    count_args = [ptr(c) if given or i % 2 == 0 else None for i, c in enumerate(counts)]
+    lib.call(entry, ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32), *set_args, *count_args,
+             lib.stream())
+    return _ranks(counts, m, given)
 
 
 def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
@@ -3654,6 +3670,12 @@ def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     ascending, equal distances by lower id, NaN after everything (+inf included).  Returns ``(ids int64 (m, k), dist float32
     (m, k))``; rows with fewer than k candidates are padded with id -1, distance +inf.  A zero distance is reported as +0 and
     every NaN as the one quiet NaN (``transe.topk_from_distances`` does the same)."""
+    return _transe_topk('gv_transe_topk', q, en, k, p_norm, (filt_lo, filt_hi, filt_ent))
+
+
+def _transe_topk(entry, q, en, k, p_norm, filt, cand=None):
+    """The two ``transe_topk*`` wrappers, with ``_transe_rank``'s arguments: the checks, the outputs, the workspace and the call.
+    Returns (ids int64 (m, k), dist float32 (m, k))."""
     q, en = _transe_operands(q, en)
     if q.device != en.device:
         raise ValueError(f'q on {q.device}, entities on {en.device}')
@@ -3662,13 +3684,15 @@ def transe_topk(q, en, k, p_norm, filt_lo=None, filt_hi=None, filt_ent=None):
     m, v = q.shape[0], en.shape[0]
     if v < 1:
         raise ValueError('need at least one entity')
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
+    lo32, hi32, ent32, n_ent = _filter_args(*filt, m, v, q.device)
+    sets = () if cand is None else _cand_args(*cand, m, v, q.device)
     ids = torch.empty(m, k, dtype=torch.int64, device=q.device)
     dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
     if m == 0:
         return ids, dist
     ws = torch.empty(int(lib.load().gv_transe_topk_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_transe_topk', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent, k, ptr(ids),
+    set_args = () if cand is None else (ptr(sets[0]), sets[1], sets[2], ptr(sets[3]))
+    lib.call(entry, ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent, *set_args, k, ptr(ids),
              ptr(dist), ptr(ws), lib.stream())
     return ids, dist
 
@@ -3678,42 +3702,14 @@ def transe_rank_constrained(q, en, target, p_norm, cand, cand_set, filt_lo=None,
     -||q[i] - en[j]||_p (gv_transe_rank_constrained): ``transe_rank_filtered``'s two, bit for bit, and the same over the members
     of row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it).  Without a filter the two filtered
     ranks are None."""
-    q, en = _transe_operands(q, en)
-    p_norm = _p_norm(p_norm)
-    m, v = q.shape[0], en.shape[0]
-    tgt32 = _target_args(target, m, v, q.device)
-    lo32, hi32, ent32, _ = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    counts = torch.zeros(4, max(m, 1), dtype=torch.int32, device=q.device)
-    filt = lo32 is not None
-    lib.call('gv_transe_rank_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(tgt32), ptr(lo32), ptr(hi32), ptr(ent32),
-             ptr(cand), ld_cand, n_sets, ptr(set32), ptr(counts[0]), ptr(counts[1]) if filt else None, ptr(counts[2]),
-             ptr(counts[3]) if filt else None, lib.stream())
-    return _ranks(counts, m, filt)
+    return _transe_rank('gv_transe_rank_constrained', q, en, target, p_norm, (filt_lo, filt_hi, filt_ent), (cand, cand_set))
 
 
 def transe_topk_constrained(q, en, k, p_norm, cand, cand_set, filt_lo=None, filt_hi=None, filt_ent=None):
     """``transe_topk`` among the members of a per-query candidate set only (gv_transe_topk_constrained): the candidates of row i
     are the entities whose bit is set in row ``cand_set[i]`` of the bitmask ``cand`` (as ``rank_scores_constrained`` takes it),
     less the filter-listed ids.  Order and padding are ``transe_topk``'s."""
-    q, en = _transe_operands(q, en)
-    if q.device != en.device:
-        raise ValueError(f'q on {q.device}, entities on {en.device}')
-    p_norm = _p_norm(p_norm)
-    k = _topk_arg(k)
-    m, v = q.shape[0], en.shape[0]
-    if v < 1:
-        raise ValueError('need at least one entity')
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, m, v, q.device)
-    cand, ld_cand, n_sets, set32 = _cand_args(cand, cand_set, m, v, q.device)
-    ids = torch.empty(m, k, dtype=torch.int64, device=q.device)
-    dist = torch.empty(m, k, dtype=torch.float32, device=q.device)
-    if m == 0:
-        return ids, dist
-    ws = torch.empty(int(lib.load().gv_transe_topk_workspace_bytes(m, v, k)), dtype=torch.uint8, device=q.device)
-    lib.call('gv_transe_topk_constrained', ptr(q), m, ptr(en), v, q.shape[1], p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-             ptr(cand), ld_cand, n_sets, ptr(set32), k, ptr(ids), ptr(dist), ptr(ws), lib.stream())
-    return ids, dist
+    return _transe_topk('gv_transe_topk_constrained', q, en, k, p_norm, (filt_lo, filt_hi, filt_ent), (cand, cand_set))
 
 
 def transe_entity_topk(ents, en, rn, k, p_norm, head=False, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
@@ -3733,22 +3729,14 @@ def transe_entity_topk(ents, en, rn, k, p_norm, head=False, filt_lo=None, filt_h
     p_norm = _p_norm(p_norm)
     if dim > TRANSE_MAX_DIM:
         raise ValueError(f'en / rn: width {dim} above {TRANSE_MAX_DIM}')
-    if span is not None and int(span) < 1:
-        raise ValueError(f'span counts (relation, entity tile) pairs per workgroup: at least 1, got {span}')
-    if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
-        raise ValueError(f'query entities must lie in [0, {n})')
-    lo32, hi32, ent32, n_ent = _filter_args(filt_lo, filt_hi, filt_ent, n * num_rels, n, en.device)
+    (lo32, hi32, ent32, n_ent), (rel, other, dist), ents32, span_tiles = _entity_topk_args(
+        ents, span, 'entity', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int64, en.device)
     en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
     dev = en.device
     if rn.device != dev:
         raise ValueError(f'en on {dev}, rn on {rn.device}')
-    rel = torch.empty(m, k, dtype=torch.int64, device=dev)
-    other = torch.empty(m, k, dtype=torch.int64, device=dev)
-    dist = torch.empty(m, k, dtype=torch.float32, device=dev)
     if m == 0:
         return rel, other, dist
-    ents32 = ents.to(device=dev, dtype=torch.int32).contiguous()
-    span_tiles = 0 if span is None else min(int(span), num_rels * ((n + 63) // 64))
     ws_bytes = int(lib.load().gv_transe_entity_topk_workspace_bytes(m, n, num_rels, k, span_tiles))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     lib.call('gv_transe_entity_topk', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32),
