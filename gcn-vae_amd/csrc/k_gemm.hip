@@ -384,6 +384,36 @@ __device__ __forceinline__ f32x16 score_tile_with(const GemmParams& p, LoadA loa
     return acc;
 }
 
+// score_tile_gather: score_tile_with with the entity rows supplied by the caller as well -- load_b_chunk(k0, rb) fills rb with this
+// thread's share of the tile's 64 entity rows in load_b's layout (gv_entity_topk_scores_typed gathers them through member ids).
+// The same staging, the same chain: a gathered row's logits are the bits score_tile gives that row.
+template <class LoadA, class LoadB>
+__device__ __forceinline__ f32x16 score_tile_gather(const GemmParams& p, LoadA load_a_chunk, LoadB load_b_chunk,
+                                                    float (&ra)[SC_BM * SC_BK / 256], float (&rb)[SC_BN * SC_BK / 256], float* As,
+                                                    float* Bs) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int k0 = 0; k0 < p.k; k0 += SC_BK) {
+        stage_a<false, SC_BM, SC_BK>(As, ra);
+        stage_b<true, SC_BN, SC_BK>(Bs, rb);
+        __syncthreads();
+        if (k0 + SC_BK < p.k) {
+            load_a_chunk(k0 + SC_BK, ra);
+            load_b_chunk(k0 + SC_BK, rb);
+        }
+#pragma unroll
+        for (int kk = 0; kk < SC_BK; kk += 2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[(kk + lhi) * SC_LDA + wm + l31], Bs[(kk + lhi) * SC_LDB + wn + l31],
+                                                       acc, 0, 0, 0);
+        __syncthreads();
+    }
+    return acc;
+}
+
 // ---- the Monte-Carlo posterior-predictive tile (gv_rank_scores_mc, gv_topk_scores_mc): a loop over samples around score_tile ----
 // Sample s has its own query matrix at q + s * q_stride and its own entity table at e + s * e_stride (the leading dimensions are
 // shared) and an optional bias[s]; logit_s comes from score_tile unchanged, and
@@ -813,6 +843,135 @@ __global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams
                 key = 0ull;
             return ep.exclude_self && col == a ? 0ull : key;
         }, [&](int rl) { return ent_s[rl] >= 0; });
+    }
+    topk_span_hand_on<BM>(m0, p.m, lists, k, ep.part, ep.n_spans, lane, wid);
+}
+
+// ---- per-entity completion among TYPE-CORRECT facts (gv_entity_topk_scores_typed) -----------------------------------------------
+// k_entity_topk_span with a row's columns taken from the relations' candidate member lists instead of the whole table: the r-major
+// sequence of (relation, 64-member tile of set cand_base + r) pairs, sum_r ceil(|C_r| / 64) tiles (TopkTyped, k_topk.h).  A
+// workgroup finds its span's first relation by bisection on tile_ptr and walks forward.  The entity operand is GATHERED through
+// the tile's 64 ids -- kept in LDS, three buffers deep: the tile at hand (its selection reads them), the next one (its first
+// operands are requested under the selection) and the one a slower wave may still be selecting on -- and goes through the same
+// k-chunks as score_tile (score_tile_gather), so a candidate's logit is the untyped kernel's, bit for bit.  The candidate id is
+// r * N + ids[slot]; the lists ascend, so the key's order is the rule's.  At a relation's (or the span's) first tile thread rl < 64
+// decides whether its entity is a member of the query-side set of r (bisection of that list) -- a row that is not is passed over
+// -- and re-opens the row's filter cursor at the tile's first id.  The filter of a gathered tile is topk_typed_filter_window: it
+// assumes neither that listed ids are members nor that fewer than 64 of them lie between two members.
+struct EntityTopkTypedParams {
+    EntityTopkParams e;           // span_tiles / n_spans count tiles of the member lists
+    TopkTyped ty;
+};
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_entity_topk_typed_span(const EntityTopkTypedParams tp) {
+    constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256, BPT = BN * BK / 256;
+    __shared__ float As[BK * SC_LDA];
+    __shared__ float Bs[BK * SC_LDB];
+    __shared__ float Ls[BM * LDL];
+    __shared__ unsigned long long thr[BM];
+    __shared__ int cur[BM], fhi[BM], nxt[BM];
+    __shared__ int fl[4][64];
+    __shared__ int ent_s[BM];                      // the rows' entities (-1: no such row)
+    __shared__ int live_s[BM];                     // the row's entity is on the query side of the relation at hand
+    __shared__ int ids_s[3][BN];                   // the member ids of the tile at hand, the next and the previous one (-1: none)
+    extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const EntityTopkParams& ep = tp.e;
+    const TopkTyped& ty = tp.ty;
+    const GemmParams& p = ep.g;
+    const int k = ep.topk, num_rels = ep.num_rels;
+    const int m0 = blockIdx.x * BM;
+    const int t_begin = blockIdx.y * ep.span_tiles;
+    const int t_end = min(t_begin + ep.span_tiles, ty.n_tiles);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const bool filtered = ep.filt_lo != nullptr;
+
+    // this thread's share of the query operand, as k_entity_topk_span forms it
+    const int a_row = m0 + threadIdx.x / (BK / APT), a_col = (threadIdx.x % (BK / APT)) * APT;
+    const int a_ent = a_row < p.m ? ep.ents[a_row] : -1;
+    const bool a_ok = (unsigned)a_ent < (unsigned)p.n;
+    const float* a_src = p.b + (a_ok ? (size_t)a_ent * p.ldb : 0) + a_col;
+    const float* w_src = ep.w + a_col;             // + r * ld_w
+    auto load_q = [&](int k0, float (&r)[APT]) {
+        float wv[APT];
+        load_run<APT>(a_src + k0, a_col + k0, p.k, a_ok, ep.vec_a, r, 0);
+        load_run<APT>(w_src + k0, a_col + k0, p.k, a_ok, ep.vec_a, wv, 0);
+#pragma unroll
+        for (int i = 0; i < APT; ++i) r[i] *= wv[i];
+    };
+    // ... and of the entity operand: row threadIdx.x / 4 of the tile is table row ids[threadIdx.x / 4], load_b's columns
+    const int b_slot = threadIdx.x / (BK / BPT), b_col = (threadIdx.x % (BK / BPT)) * BPT;
+    const float* b_src = p.b + b_col;
+    bool b_ok = false;
+    auto gather_from = [&](const int* ids) {
+        const int id = ids[b_slot];
+        b_ok = id >= 0;
+        b_src = p.b + (b_ok ? (size_t)id * p.ldb : 0) + b_col;
+    };
+    auto load_e = [&](int k0, float (&r)[BPT]) { load_run<BPT>(b_src + k0, b_col + k0, p.k, b_ok, p.vec_b, r, 0); };
+
+    TopkTypedTile tile{};
+    if (t_begin < t_end) {
+        tile = topk_typed_seek(ty, num_rels, t_begin);
+        if (threadIdx.x < BN) ids_s[0][threadIdx.x] = topk_typed_id(ty, tile, p.n, threadIdx.x);
+    }
+    topk_span_clear<BM>(lists, k, fl, thr, lane, wid, [&](int rl) { topk_pair_entity(ep.ents, m0, rl, p.m, p.n, ent_s); });
+    __syncthreads();                               // the first tile's ids, ahead of the first gather
+    float ra[APT], rb[BPT];
+    if (t_begin < t_end) {
+        w_src = ep.w + (size_t)tile.r * ep.ld_w + a_col;
+        gather_from(ids_s[0]);
+        load_q(0, ra);
+        load_e(0, rb);
+    }
+    const float bv = ep.bias ? *ep.bias : 0.f;
+
+    int buf = 0;
+    for (int t = t_begin; t < t_end; ++t) {
+        const bool more = t + 1 < t_end;
+        const int nbuf = buf == 2 ? 0 : buf + 1;
+        TopkTypedTile next = tile;
+        if (more) {
+            // the next tile's ids: its buffer was last read by the selection two tiles back, which every wave left before this
+            // wave passed the previous tile's barriers; the barriers below publish it
+            next = topk_typed_next(ty, num_rels, tile, t);
+            if (threadIdx.x < BN) ids_s[nbuf][threadIdx.x] = topk_typed_id(ty, next, p.n, threadIdx.x);
+        }
+        const f32x16 acc = score_tile_gather(p, load_q, load_e, ra, rb, As, Bs);
+        if (more) {                                                // the next tile's first operands fly under the selection
+            w_src = ep.w + (size_t)next.r * ep.ld_w + a_col;
+            gather_from(ids_s[nbuf]);
+            load_q(0, ra);
+            load_e(0, rb);
+        }
+        const int* ids = ids_s[buf];
+        // (every wave is past the tile's last barrier: nobody still reads the previous relation's cursors or flags, or Ls)
+        if ((tile.ct == 0 || t == t_begin) && threadIdx.x < BM) {
+            const int rl = threadIdx.x, a = ent_s[rl];
+            const bool live = a >= 0 && topk_typed_member(ty, num_rels, tile.r, a);
+            live_s[rl] = live;
+            topk_filter_begin(ep.filt_lo, ep.filt_hi, ep.filt_ent, ep.n_ent, filtered && live, (long long)a * num_rels + tile.r,
+                              max(ids[0], 0), &cur[rl], &fhi[rl], &nxt[rl]);
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Ls[(wm + (i & 3) + 8 * (i >> 2) + 4 * lhi) * LDL + wn + l31] = acc[i] + bv;
+        __syncthreads();
+
+        const int cnt = max(tile.live(), 1);
+        const int x = ids[lane], id_max = ids[cnt - 1];
+        topk_span_select<NK, BM>(m0, p.m, lists, thr, k, lane, wid, [&](int rl, int) {
+            const int a = ent_s[rl];
+            unsigned long long key = x >= 0 ? topk_key(Ls[rl * LDL + lane], tile.r * p.n + x) : 0ull;
+            if (filtered && nxt[rl] <= id_max &&
+                topk_typed_filter_window(ep.filt_ent, ids, cnt, id_max, (int)((unsigned)(t - t_begin) * BM + rl + 1u), lane, &cur[rl],
+                                         &fhi[rl], &nxt[rl], fl[wid]))
+                key = 0ull;
+            return ep.exclude_self && x == a ? 0ull : key;
+        }, [&](int rl) { return live_s[rl] != 0; });
+        tile = next;
+        buf = nbuf;
     }
     topk_span_hand_on<BM>(m0, p.m, lists, k, ep.part, ep.n_spans, lane, wid);
 }
@@ -1581,6 +1740,46 @@ extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e,
     return topk_span_merge<k_entity_topk_span<1>, k_entity_topk_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
         name, dim3((m + 63) / 64, ep.n_spans), ep, ep.part, m, ep.n_spans, k, TopkPairOut<int, topk_key_logit>{out_rel, out_ent, out_logits, n},
         (hipStream_t)stream);
+}
+
+// ---- per-entity completion among type-correct facts (gv_entity_topk_scores_typed): spans of the member lists' tiles ---------------
+extern "C" int64_t gv_entity_topk_scores_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles) {
+    return entity_typed_workspace_bytes(m, n_tiles, k, span_tiles);
+}
+
+extern "C" int gv_entity_topk_scores_typed(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                                           const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                                           const int64_t* set_ptr, const int32_t* set_ids, const int32_t* tile_ptr, int n_tiles,
+                                           int cand_base, int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent,
+                                           float* out_logits, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h,
+                                           void* stream) {
+    const char* name = "gv_entity_topk_scores_typed";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", name,
+               m, n, num_rels, h, n_filt_ent);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
+    GV_CHECK(entity_typed_shape(name, num_rels, n_tiles, cand_base));
+    GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_logits && workspace));
+    GV_CHECK(entity_typed_given(name, set_ptr, set_ids, tile_ptr, n_tiles));
+    EntityTopkTypedParams tp;
+    EntityTopkParams& ep = tp.e;
+    ep.g = score_gemm_params(nullptr, ld_e, e, ld_e, m, n, h);
+    ep.ents = ents; ep.w = w; ep.ld_w = ld_w;
+    ep.vec_a = ep.g.vec_b && aligned16(w) && (ld_w % 4 == 0);
+    ep.num_rels = num_rels; ep.exclude_self = exclude_self != 0;
+    ep.bias = bias;
+    ep.filt_lo = filt_lo; ep.filt_hi = filt_hi; ep.filt_ent = filt_ent; ep.n_ent = n_filt_ent;
+    ep.topk = k;
+    entity_typed_spans(m, n_tiles, span_tiles, &ep.span_tiles, &ep.n_spans);
+    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, ep.n_spans, workspace_bytes));
+    ep.part = (unsigned long long*)workspace;
+    tp.ty = TopkTyped{(const long long*)set_ptr, set_ids, tile_ptr, cand_base, n_tiles};
+    const TopkPairOut<int, topk_key_logit> out{out_rel, out_ent, out_logits, n};
+    if (n_tiles == 0) return topk_all_padding(name, ep.part, m, k, out, (hipStream_t)stream);
+    return topk_span_merge<k_entity_topk_typed_span<1>, k_entity_topk_typed_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
+        name, dim3((m + 63) / 64, ep.n_spans), tp, ep.part, m, ep.n_spans, k, out, (hipStream_t)stream);
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

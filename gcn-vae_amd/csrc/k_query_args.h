@@ -1,5 +1,5 @@
-// The argument checks the entity-query entries share (host only): gv_rank_scores* / gv_topk_scores* / gv_entity_topk_scores
-// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk (k_transe.hip).  One function per group of arguments; each takes the entry's
+// The argument checks the entity-query entries share (host only): gv_rank_scores* / gv_topk_scores* / gv_entity_topk_scores{,_typed}
+// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk{,_typed} (k_transe.hip).  One function per group of arguments; each takes the entry's
 // name, sets the library's error text and returns the code, GV_OK when the group is fine.  An entry lists its groups in the order
 // in which it reports them -- tests/test_query_entries_host.py pins every text and, with two faults at once, that order -- then
 // returns for m == 0, then asks for its own pointers.
@@ -100,6 +100,42 @@ inline int entity_query_workspace(const char* name, int m, int k, int span_tiles
     const int64_t need = (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
     GV_REQUIRE(workspace_bytes >= need, GV_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed", name, (long long)workspace_bytes,
                (long long)need);
+    return GV_OK;
+}
+
+// ---- the type-constrained per-entity queries (gv_entity_topk_scores_typed, gv_transe_entity_topk_typed) ---------------------------
+// spans of the n_tiles (relation, 64-member tile) pairs of the candidate lists, by entity_query_spans' rule; no tile at all is one
+// span of padding (nothing is walked: the merge decodes empty lists)
+inline void entity_typed_spans(long long m, int n_tiles, int span_tiles, int* per, int* n_spans) {
+    if (n_tiles <= 0) {
+        *per = 1; *n_spans = 1;
+    } else if (span_tiles > 0) {
+        *per = std::min(span_tiles, n_tiles);
+        *n_spans = (n_tiles + *per - 1) / *per;
+    } else {
+        topk_spans_of(m, n_tiles, 256, per, n_spans);
+    }
+}
+
+// what gv_*_typed_workspace_bytes answer: the spans' lists, m * n_spans * k keys, 0 for sizes the entry refuses
+inline int64_t entity_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles) {
+    if (m <= 0 || n_tiles < 0 || k < 1 || k > TOPK_MAX || span_tiles < 0) return 0;
+    int per = 0, n_spans = 0;
+    entity_typed_spans(m, n_tiles, span_tiles, &per, &n_spans);
+    return (int64_t)m * n_spans * k * (int64_t)sizeof(unsigned long long);
+}
+
+// what follows entity_query_shape: the tile count and which side holds the candidates
+inline int entity_typed_shape(const char* name, int num_rels, int n_tiles, int cand_base) {
+    GV_REQUIRE(n_tiles >= 0, GV_ERR_SHAPE, "%s: n_tiles=%d", name, n_tiles);
+    GV_REQUIRE(cand_base == 0 || cand_base == num_rels, GV_ERR_SHAPE, "%s: cand_base=%d (0: the objects of r are the candidates, %d: its subjects)",
+               name, cand_base, num_rels);
+    return GV_OK;
+}
+
+// the member lists and the tile prefix (set_ids may be NULL when no set has a member: then there is no tile either)
+inline int entity_typed_given(const char* name, const void* set_ptr, const void* set_ids, const void* tile_ptr, int n_tiles) {
+    GV_REQUIRE(set_ptr && tile_ptr && (set_ids || n_tiles == 0), GV_ERR_NULL, "%s: NULL set_ptr / set_ids / tile_ptr", name);
     return GV_OK;
 }
 

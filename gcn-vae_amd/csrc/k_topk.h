@@ -4,6 +4,8 @@
 // hand-on of the lists), the per-entity kernels' walk over (relation, column tile) pairs, the span geometry, the merge of the spans'
 // lists with its two output decoders and the host's launch of the pair.  The kernels differ in how a 64 x 64 tile of values is
 // made, not in how the best k of a row are kept.
+// The two type-constrained per-entity kernels (k_entity_topk_typed_span, k_transe_entity_topk_typed_span) share all of it but the
+// filter window, and their columns -- tiles of the relations' member lists -- are the TopkTyped pieces below.
 //
 // Candidates are ordered by a 64-bit key, larger = better:
 //   key = ordered_u32(value) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
@@ -249,6 +251,107 @@ __device__ __forceinline__ void topk_pair_reopen(const int* filt_lo, const int* 
                       &cur[rl], &fhi[rl], &nxt[rl]);
 }
 
+// ---- the TYPED per-entity kernels' columns: (relation, 64-member tile of the relation's candidate list) pairs, r-major ---------
+// (k_entity_topk_typed_span, k_transe_entity_topk_typed_span.)  The sets are ranking.TypeConstraint.members: set j's members ascending
+// in set_ids[set_ptr[j] : set_ptr[j + 1]], 2 R sets.  Relation r's candidates are set cand_base + r, and a query entity has
+// candidates under r only as a member of set R - cand_base + r (cand_base 0: objects wanted, the entity a subject; R: the other way
+// round).  tile_ptr [R + 1] is the prefix of ceil(|candidates of r| / 64): tile t belongs to the relation r with tile_ptr[r] <= t <
+// tile_ptr[r + 1].  A slot past the list's end, or an id outside [0, n), is -1: it gathers nothing and gets key 0.
+struct TopkTyped {
+    const long long* set_ptr;     // [2 R + 1]
+    const int* set_ids;
+    const int* tile_ptr;          // [R + 1], tile_ptr[R] = n_tiles
+    int cand_base, n_tiles;
+};
+
+struct TopkTypedTile {
+    int r, ct;                    // the tile's relation, its index in the relation's candidate list
+    int t_end;                    // tile_ptr[r + 1]: the relation's tiles end here
+    long long base, len;          // the candidate list: set_ids[base : base + len]
+    __device__ __forceinline__ int live() const { return (int)min(64ll, len - 64ll * ct); }     // the tile's slots that hold a member
+};
+
+__device__ __forceinline__ void topk_typed_relation(const TopkTyped& ty, int r, TopkTypedTile* tile) {
+    tile->r = r; tile->ct = 0;
+    tile->t_end = ty.tile_ptr[r + 1];
+    tile->base = ty.set_ptr[ty.cand_base + r];
+    tile->len = ty.set_ptr[ty.cand_base + r + 1] - tile->base;
+}
+
+// tile t < n_tiles: its relation by bisection on tile_ptr (the last r with tile_ptr[r] <= t: relations without a tile are passed)
+__device__ __forceinline__ TopkTypedTile topk_typed_seek(const TopkTyped& ty, int num_rels, int t) {
+    int lo = 0, hi = num_rels;                           // the first r in (0, R] with tile_ptr[r] > t
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (ty.tile_ptr[mid + 1] > t) hi = mid;
+        else lo = mid + 1;
+    }
+    TopkTypedTile tile;
+    topk_typed_relation(ty, min(lo, num_rels - 1), &tile);
+    tile.ct = t - ty.tile_ptr[tile.r];
+    return tile;
+}
+
+// tile t's successor, tile t + 1 (< n_tiles)
+__device__ __forceinline__ TopkTypedTile topk_typed_next(const TopkTyped& ty, int num_rels, const TopkTypedTile& now, int t) {
+    TopkTypedTile nx = now;
+    ++nx.ct;
+    if (t + 1 >= now.t_end) {
+        int r = now.r + 1;
+        while (r < num_rels - 1 && ty.tile_ptr[r + 1] <= t + 1) ++r;
+        topk_typed_relation(ty, r, &nx);
+    }
+    return nx;
+}
+
+// the tile's 64 member ids, one per thread tl < 64
+__device__ __forceinline__ int topk_typed_id(const TopkTyped& ty, const TopkTypedTile& tile, int n, int tl) {
+    const long long at = 64ll * tile.ct + tl;
+    const int id = (tile.ct >= 0 && at < tile.len) ? ty.set_ids[tile.base + at] : -1;
+    return (unsigned)id < (unsigned)n ? id : -1;
+}
+
+// is entity a (>= 0) a member of the QUERY-side set of relation r?  (bisection of that set's ascending list)
+__device__ __forceinline__ bool topk_typed_member(const TopkTyped& ty, int num_rels, int r, int a) {
+    const int set = num_rels - ty.cand_base + r;
+    const long long lo = ty.set_ptr[set], hi = ty.set_ptr[set + 1];
+    long long x = lo, y = hi;
+    while (x < y) {
+        const long long mid = x + ((y - x) >> 1);
+        if (ty.set_ids[mid] < a) x = mid + 1;
+        else y = mid;
+    }
+    return x < hi && ty.set_ids[x] == a;
+}
+
+// The filter of a gathered tile.  One wave, a row whose cursor says that its next listed id is <= the tile's last member id_max:
+// every listed id up to id_max is taken off the cursor, 64 at a time -- however many of them lie between two members, and member
+// or not -- and looked up among the tile's `cnt` ascending ids (LDS) by bisection; a hit marks its slot in the wave's flag words
+// (flw[j] == tag <=> slot j is listed; tags are unique per row and tile, so the flags are never cleared).  Returns whether this
+// lane's slot is listed.
+__device__ __forceinline__ bool topk_typed_filter_window(const int* filt_ent, const int* ids, int cnt, int id_max, int tag, int lane,
+                                                         int* cur, const int* fhi, int* nxt, int* flw) {
+    int c = *cur;
+    const int hi = *fhi;
+    int nx;
+    for (;;) {
+        const int idx = c + lane;
+        const int ent = idx < hi ? filt_ent[idx] : INT_MAX;
+        const bool win = ent <= id_max;
+        const int got = __popcll(__ballot(win));
+        if (win) {
+            int x = 0, y = cnt;                          // the first slot with id >= ent
+            while (x < y) { const int mid = (x + y) >> 1; if (ids[mid] < ent) x = mid + 1; else y = mid; }
+            if (x < cnt && ids[x] == ent) flw[x] = tag;
+        }
+        c += got;
+        if (got < 64) { nx = __shfl(ent, got); break; }
+    }
+    const bool listed = flw[lane] == tag;
+    if (lane == 0) { *cur = c; *nxt = nx; }
+    return listed;
+}
+
 // ---- stage 2: one wave per row merges the n_spans sorted lists of k keys and hands the first k to `out` --------------------
 // Out::put(i, key) decodes key into entry i of the (m, k) outputs.  Id: the outputs' integer type; Value: the key's value back
 // (topk_key_logit, or te_key_dist of k_transe.hip for a key made of -distance).
@@ -318,6 +421,21 @@ int topk_span_merge(const char* name, dim3 grid, const Params& p, unsigned long 
         hipLaunchKernelGGL(Span2, grid, block, ROWS * k * KEY, st, p);
         hipLaunchKernelGGL((k_topk_merge<2, Out>), mgrid, block, 0, st, part, m, n_spans, k, out);
     }
+    return launch_status(name);
+}
+
+// No column to walk (a typed query whose candidate lists are all empty): the m * k keys of one span of empty lists, then the merge
+// alone, which decodes them to the outputs' padding.
+template <class Out>
+int topk_all_padding(const char* name, unsigned long long* part, int m, int k, const Out& out, hipStream_t st) {
+    const hipError_t e = fill_words(part, 0u, (size_t)m * k * sizeof(unsigned long long), st);
+    if (e != hipSuccess) {
+        set_error("%s: %s", name, hipGetErrorString(e));
+        return (int)e;
+    }
+    const dim3 block(256), mgrid((unsigned)((m + 3) / 4));
+    if (k <= 64) hipLaunchKernelGGL((k_topk_merge<1, Out>), mgrid, block, 0, st, part, m, 1, k, out);
+    else hipLaunchKernelGGL((k_topk_merge<2, Out>), mgrid, block, 0, st, part, m, 1, k, out);
     return launch_status(name);
 }
 

@@ -518,6 +518,44 @@ __device__ __forceinline__ void te_tile_with(QAt q_at, const float* __restrict__
     }
 }
 
+// te_tile_with with the tile's entity rows supplied by the caller as well: e_at(row, c) is column c of the tile's entity row `row` as
+// it is staged (0 for a row that holds none, or past the last column) -- gv_transe_entity_topk_typed gathers the rows through member
+// ids.  The same staging, the same column order, the same per-pair chain: a gathered row's distances are te_tile's bits.
+template <class QAt, class EAt>
+__device__ __forceinline__ void te_tile_gather(QAt q_at, EAt e_at, int dim, int p, float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4],
+                                               float (&acc)[4][4]) {
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+    for (int k0 = 0; k0 < dim; k0 += TE_KC) {
+        __syncthreads();
+        for (int x = tid; x < TE_TQ * TE_KC; x += 256) {
+            const int row = x / TE_KC, k = x % TE_KC;
+            qs[k][row] = q_at(row, k0 + k);
+            es[k][row] = e_at(row, k0 + k);
+        }
+        __syncthreads();
+        const int kn = min(TE_KC, dim - k0);
+        for (int k = 0; k < kn; ++k) {
+            const float4 qa = *reinterpret_cast<const float4*>(&qs[k][4 * ty]);
+            const float4 eb = *reinterpret_cast<const float4*>(&es[k][4 * tx]);
+            const float qv[4] = {qa.x, qa.y, qa.z, qa.w}, ev[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[a][b] = te_pair_term(acc[a][b], qv[a], ev[b], p);
+        }
+    }
+    if (p == 2) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = sqrtf(acc[a][b]);
+    }
+}
+
 // the tile of rows q0 .. of a stored query matrix q (m, dim)
 __device__ __forceinline__ void te_tile(const float* __restrict__ q, int64_t m, const float* __restrict__ en, int v, int dim, int p,
                                         int64_t q0, int e0, float (*qs)[TE_TQ + 4], float (*es)[TE_TE + 4], float (&acc)[4][4]) {
@@ -807,6 +845,101 @@ __global__ __launch_bounds__(256) void k_transe_entity_topk_span(const TeEntityT
     topk_span_hand_on<TE_TQ>(m0, tp.m, lists, k, tp.part, tp.n_spans, lane, wid);
 }
 
+// ---- per-entity completion among TYPE-CORRECT facts (gv_transe_entity_topk_typed) -------------------------------------------------
+// k_transe_entity_topk_span with a row's columns taken from the relations' candidate member lists (TopkTyped, k_topk.h), as
+// k_entity_topk_typed_span (k_gemm.hip) does for DistMult: the r-major sequence of (relation, 64-member tile of set cand_base + r)
+// pairs.  The tile's entity rows are gathered through its 64 ids (te_tile_gather: the same columns in the same order, so the
+// distances are the untyped kernel's bits); the ids sit in LDS, two buffers deep -- a slower wave may still select on the previous
+// tile's -- and thread tl < 64 requests the NEXT tile's id a tile ahead, so the load flies under the distances.  Row liveness (the
+// entity a member of the query-side set of r), the filter cursor at the tile's first id and the gathered tile's filter are the
+// DistMult kernel's.
+struct TeEntityTopkTypedParams {
+    TeEntityTopkParams e;         // span_tiles / n_spans count tiles of the member lists
+    TopkTyped ty;
+};
+
+template <int NK>
+__global__ __launch_bounds__(256) void k_transe_entity_topk_typed_span(const TeEntityTopkTypedParams pp) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    __shared__ __attribute__((aligned(16))) float ds[TE_TQ * TE_LDD];     // the tile's distances, row-major
+    __shared__ unsigned long long thr[TE_TQ];
+    __shared__ int cur[TE_TQ], fhi[TE_TQ], nxt[TE_TQ];
+    __shared__ int fl[4][64];
+    __shared__ int ent_s[TE_TQ];                                          // the rows' entities (-1: no such row)
+    __shared__ int live_s[TE_TQ];                                         // the row's entity is on the query side of the relation at hand
+    __shared__ int ids_s[2][TE_TE];                                       // the member ids of the tile at hand and of the previous one
+    extern __shared__ unsigned long long lists[];                         // [TE_TQ][topk]
+    const TeEntityTopkParams& tp = pp.e;
+    const TopkTyped& ty = pp.ty;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, tx = tid & 15, ty4 = tid >> 4;
+    const int k = tp.topk, dim = tp.dim, num_rels = tp.num_rels;
+    const int m0 = blockIdx.x * TE_TQ;
+    const int t_begin = blockIdx.y * tp.span_tiles;
+    const int t_end = min(t_begin + tp.span_tiles, ty.n_tiles);
+    const bool filtered = tp.filt_lo != nullptr, head = tp.head != 0;
+    TopkTypedTile tile{};
+    int my_id = -1;                                                       // thread tl < 64: slot tl of the tile about to be staged
+    if (t_begin < t_end) {
+        tile = topk_typed_seek(ty, num_rels, t_begin);
+        if (tid < TE_TE) my_id = topk_typed_id(ty, tile, tp.n, tid);
+    }
+    topk_span_clear<TE_TQ>(lists, k, fl, thr, lane, wid, [&](int rl) { topk_pair_entity(tp.ents, m0, rl, tp.m, tp.n, ent_s); });
+    int buf = 0;
+    for (int t = t_begin; t < t_end; ++t) {
+        // this buffer was last read by the selection two tiles back, which every wave left before this wave passed the previous
+        // tile's barriers; te_tile_gather's first barrier publishes it (and the set-up above)
+        int* ids = ids_s[buf];
+        if (tid < TE_TE) ids[tid] = my_id;
+        TopkTypedTile next = tile;
+        if (t + 1 < t_end) {
+            next = topk_typed_next(ty, num_rels, tile, t);
+            if (tid < TE_TE) my_id = topk_typed_id(ty, next, tp.n, tid);
+        }
+        const float* __restrict__ rr = tp.rn + (size_t)tile.r * dim;
+        float acc[4][4];
+        te_tile_gather(
+            [&](int row, int c) {
+                const int a = ent_s[row];
+                if (a < 0 || c >= dim) return 0.f;
+                const float x = tp.en[(size_t)a * dim + c], y = rr[c];
+                return head ? x - y : x + y;
+            },
+            [&](int row, int c) {
+                const int id = ids[row];
+                return (id >= 0 && c < dim) ? tp.en[(size_t)id * dim + c] : 0.f;
+            },
+            dim, tp.p, qs, es, acc);
+        // (every wave is past the tile's last barrier: nobody still reads the previous relation's cursors or flags)
+        if ((tile.ct == 0 || t == t_begin) && tid < TE_TQ) {
+            const int a = ent_s[tid];
+            const bool live = a >= 0 && topk_typed_member(ty, num_rels, tile.r, a);
+            live_s[tid] = live;
+            topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_ent, tp.n_ent, filtered && live, (long long)a * num_rels + tile.r,
+                              max(ids[0], 0), &cur[tid], &fhi[tid], &nxt[tid]);
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            *reinterpret_cast<float4*>(&ds[(4 * ty4 + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
+        __syncthreads();
+        const int cnt = max(tile.live(), 1);
+        const int x = ids[lane], id_max = ids[cnt - 1];
+        topk_span_select<NK, TE_TQ>(m0, tp.m, lists, thr, k, lane, wid, [&](int rl, int) {
+            const int a = ent_s[rl];
+            unsigned long long key = x >= 0 ? topk_key(-ds[rl * TE_LDD + lane], tile.r * tp.n + x) : 0ull;
+            if (filtered && nxt[rl] <= id_max &&
+                topk_typed_filter_window(tp.filt_ent, ids, cnt, id_max, (int)((unsigned)(t - t_begin) * TE_TQ + rl + 1u), lane, &cur[rl],
+                                         &fhi[rl], &nxt[rl], fl[wid]))
+                key = 0ull;
+            return tp.exclude_self && x == a ? 0ull : key;
+        }, [&](int rl) { return live_s[rl] != 0; });
+        tile = next;
+        buf ^= 1;
+    }
+    if (t_begin >= t_end) __syncthreads();                                // a span without a tile: the set-up's lists, published
+    topk_span_hand_on<TE_TQ>(m0, tp.m, lists, k, tp.part, tp.n_spans, lane, wid);
+}
+
 }  // namespace gv
 
 using namespace gv;
@@ -1039,4 +1172,37 @@ extern "C" int gv_transe_entity_topk(const int32_t* ents, int m, const float* en
     return topk_span_merge<k_transe_entity_topk_span<1>, k_transe_entity_topk_span<2>, true, TE_TQ>(
         name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), tp, tp.part, m, tp.n_spans, k,
         TopkPairOut<int64_t, te_key_dist>{out_rel, out_ent, out_dist, n}, GV_ST);
+}
+
+// ---- per-entity completion among type-correct facts (gv_transe_entity_topk_typed): spans of the member lists' tiles ----------------
+extern "C" int64_t gv_transe_entity_topk_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles) {
+    return entity_typed_workspace_bytes(m, n_tiles, k, span_tiles);
+}
+
+extern "C" int gv_transe_entity_topk_typed(const int32_t* ents, int m, const float* en, const float* rn, int n, int num_rels, int dim,
+                                           int head, int p_norm, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent,
+                                           int n_filt_ent, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* tile_ptr,
+                                           int n_tiles, int cand_base, int exclude_self, int k, int span_tiles, int64_t* out_rel,
+                                           int64_t* out_ent, float* out_dist, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* name = "gv_transe_entity_topk_typed";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) && n_filt_ent >= 0,
+               GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_ent=%d", name, m, n, num_rels, dim,
+               GV_TRANSE_MAX_DIM, p_norm, n_filt_ent);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
+    GV_CHECK(entity_typed_shape(name, num_rels, n_tiles, cand_base));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, ents && en && rn && out_rel && out_ent && out_dist && workspace));
+    GV_CHECK(entity_typed_given(name, set_ptr, set_ids, tile_ptr, n_tiles));
+    TeEntityTopkTypedParams pp{TeEntityTopkParams{en, rn, ents, filt_lo, filt_hi, filt_ent, m, n, num_rels, dim, p_norm, head != 0,
+                                                  exclude_self != 0, n_filt_ent, k, 0, 0, (unsigned long long*)workspace},
+                               TopkTyped{(const long long*)set_ptr, set_ids, tile_ptr, cand_base, n_tiles}};
+    TeEntityTopkParams& tp = pp.e;
+    entity_typed_spans(m, n_tiles, span_tiles, &tp.span_tiles, &tp.n_spans);
+    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, tp.n_spans, workspace_bytes));
+    const TopkPairOut<int64_t, te_key_dist> out{out_rel, out_ent, out_dist, n};
+    if (n_tiles == 0) return topk_all_padding(name, tp.part, m, k, out, GV_ST);
+    // (<= 64 KiB of lists beside 38 KiB static: the limit is raised for either NK)
+    return topk_span_merge<k_transe_entity_topk_typed_span<1>, k_transe_entity_topk_typed_span<2>, true, TE_TQ>(
+        name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), pp, tp.part, m, tp.n_spans, k, out, GV_ST);
 }

@@ -112,6 +112,9 @@ SIGNATURES = {
     'gv_topk_scores_constrained': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_entity_topk_scores_workspace_bytes': (_L, [_I, _I, _I, _I]),
     'gv_entity_topk_scores': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    'gv_entity_topk_scores_typed_workspace_bytes': (_L, [_I, _I, _I, _I]),
+    'gv_entity_topk_scores_typed': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I,
+                                         _I, _I, _P]),
     'gv_rank_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_topk_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_pair_prob_std_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
@@ -144,6 +147,9 @@ SIGNATURES = {
     'gv_transe_topk_constrained': (_I, [_P, _L, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P]),
     'gv_transe_entity_topk_workspace_bytes': (_L, [_I, _I, _I, _I, _I]),
     'gv_transe_entity_topk': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    'gv_transe_entity_topk_typed_workspace_bytes': (_L, [_I, _I, _I, _I]),
+    'gv_transe_entity_topk_typed': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P,
+                                         _L, _P]),
     'gv_transe_mine_workspace_bytes': (_L, [_I, _I, _I]),
     'gv_transe_mine': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I, _P, _L, _P, _P,
                             _P, _L, _P]),

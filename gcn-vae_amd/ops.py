@@ -811,6 +811,70 @@ def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, f
     return rel.long(), ent.long(), logits
 
 
+def entity_typed_plan(set_ptr, num_rels, side='s'):
+    """The columns of the type-constrained per-entity sweeps from the member lists' sizes, with torch ops on ``set_ptr``'s device
+    (a CPU tensor works): ``(tile_ptr int32 [R + 1], n_tiles, cand_base)``.  ``side='s'`` (facts (a, r, x)): the candidates of
+    relation r are its objects, set ``cand_base + r`` with ``cand_base = 0``; ``side='o'`` (facts (x, r, a)): its subjects,
+    ``cand_base = R``.  ``tile_ptr`` is the prefix of ``ceil(|candidates of r| / 64)`` -- a row's columns are the r-major sequence
+    of (relation, 64-member tile) pairs -- and ``n_tiles = tile_ptr[R]``, read back with one sync.  2**31 tiles or more:
+    ValueError."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: the candidates are objects) or 'o' (as object: subjects)")
+    cand_base = 0 if side == 's' else num_rels
+    sizes = (set_ptr[1:] - set_ptr[:-1]).to(torch.int64)[cand_base:cand_base + num_rels]
+    tile_ptr = torch.zeros(num_rels + 1, dtype=torch.int64, device=set_ptr.device)
+    tile_ptr[1:] = torch.cumsum((sizes + 63) // 64, 0)
+    n_tiles = int(tile_ptr[-1])
+    if n_tiles >= 2 ** 31:
+        raise ValueError(f'the candidate lists have {n_tiles} tiles of 64 members, more than 2**31 - 1')
+    return tile_ptr.to(torch.int32).contiguous(), n_tiles, cand_base
+
+
+def _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, device):
+    """What the two typed per-entity wrappers add to ``_entity_topk_args``: the member lists checked (``_mine_typed_members``) and
+    on the tables' device, the plan, and ``span`` held to the number of tiles.  Returns (ptr64, ids32, tile_ptr, n_tiles, cand_base,
+    span_tiles)."""
+    for name, t in (('set_ptr', set_ptr), ('set_ids', set_ids)):
+        if not isinstance(t, torch.Tensor) or t.device != device:
+            raise RuntimeError(f'{name}: the gfx950 path needs a CUDA/ROCm tensor on the tables\' device; there is no CPU fallback')
+    ptr64, ids32 = _mine_typed_members(set_ptr, set_ids, n, num_rels)
+    tile_ptr, n_tiles, cand_base = entity_typed_plan(ptr64, num_rels, side)
+    if not ids32.numel():
+        ids32 = torch.zeros(1, dtype=torch.int32, device=device)
+    span_tiles = 0 if span is None else max(1, min(int(span), n_tiles))
+    return ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles
+
+
+def entity_topk_scores_typed(ents, emb, w, k, set_ptr, set_ids, side='s', bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                             exclude_self=True, span=None):
+    """``entity_topk_scores`` among the TYPE-CORRECT facts only (gv_entity_topk_scores_typed).  The sets are given as lists
+    (``set_ptr`` int64 [2 R + 1], ``set_ids``: ``ranking.TypeConstraint.members``, set r = the objects of r, set R + r its
+    subjects).  ``side='s'``: the facts (a, r, x) with a among r's subjects and x among its objects -- the filter is the object
+    queries'; ``side='o'``: the facts (x, r, a) with a among r's objects and x among its subjects -- the filter is the subject
+    queries'.  The logit is ``entity_topk_scores``' either way (the query entity's row carries w[r]), bit for bit, and so are
+    order, ties, NaN, -0, padding and the outputs; the filter is independent of the sets.  One fused launch pair walks the
+    relations' candidate lists, 64 members a tile, rows gathered through the ids: ``sum_r ceil(|C_r| / 64)`` column tiles per
+    64-entity row tile instead of ``R * ceil(N / 64)``.  An entity on the query side of no relation gets an all-padding row.
+    ``span``: (relation, 64-member tile) pairs per workgroup instead of the library's rule -- the result does not depend on it."""
+    m, n, num_rels, h = _entity_topk_operands(ents, emb, w)
+    k = _topk_arg(k)
+    (lo32, hi32, ent32, n_ent), (rel, ent, logits), ents32, _ = _entity_topk_args(
+        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, emb.device)
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev = emb.device
+    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, dev)
+    if m == 0:
+        return rel.long(), ent.long(), logits
+    bias = _bias_arg(bias)
+    ws_bytes = int(lib.load().gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_entity_topk_scores_typed', ptr(ents32), m, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32),
+             n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k, span_tiles, ptr(rel),
+             ptr(ent), ptr(logits), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+    return rel.long(), ent.long(), logits
+
+
 def _mc_operands(q, entities):
     """The two sample stacks of a Monte-Carlo query -- q (S, m, h), entities (S, v, h) -- checked for shape ahead of any look at
     their device, then as contiguous float32: (q, entities, S, m, v, h)."""
@@ -3741,6 +3805,38 @@ def transe_entity_topk(ents, en, rn, k, p_norm, head=False, filt_lo=None, filt_h
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     lib.call('gv_transe_entity_topk', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32),
              ptr(ent32), n_ent, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
+    return rel, other, dist
+
+
+def transe_entity_topk_typed(ents, en, rn, k, p_norm, set_ptr, set_ids, head=False, filt_lo=None, filt_hi=None, filt_ent=None,
+                             exclude_self=True, span=None):
+    """``transe_entity_topk`` among the TYPE-CORRECT facts only (gv_transe_entity_topk_typed), with the member lists of
+    ``entity_topk_scores_typed``.  ``head=False``: the facts (a, r, x) at ``||en[a] + rn[r] - en[x]||_p``, a among r's subjects
+    and x among its objects; ``head=True``: the facts (x, r, a) at ``||en[a] - rn[r] - en[x]||_p``, a among r's objects and x
+    among its subjects.  The distances bit for bit, order, ties, NaN, padding and the outputs are ``transe_entity_topk``'s; the
+    filter is independent of the sets.  One fused launch pair walks the relations' candidate lists, 64 members a tile.  An entity
+    on the query side of no relation gets an all-padding row.  ``span``: (relation, 64-member tile) pairs per workgroup -- the
+    result does not depend on it."""
+    m, n, num_rels, dim = _entity_topk_operands(ents, en, rn)
+    k = _topk_arg(k)
+    p_norm = _p_norm(p_norm)
+    if dim > TRANSE_MAX_DIM:
+        raise ValueError(f'en / rn: width {dim} above {TRANSE_MAX_DIM}')
+    (lo32, hi32, ent32, n_ent), (rel, other, dist), ents32, _ = _entity_topk_args(
+        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int64, en.device)
+    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
+    dev = en.device
+    if rn.device != dev:
+        raise ValueError(f'en on {dev}, rn on {rn.device}')
+    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, 'o' if head else 's', span, n,
+                                                                                     num_rels, dev)
+    if m == 0:
+        return rel, other, dist
+    ws_bytes = int(lib.load().gv_transe_entity_topk_typed_workspace_bytes(m, n_tiles, k, span_tiles))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_transe_entity_topk_typed', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32),
+             ptr(hi32), ptr(ent32), n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k,
+             span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
     return rel, other, dist
 
 

@@ -793,11 +793,16 @@ def _mine_filter(filter_index, n, num_rels, device, direction='o'):
     return lo, hi, filter_index.entities(direction, device)
 
 
-def _mine_members(type_constraint, n, num_rels, device):
-    """(ptr, ids) of ``TypeConstraint.members`` on ``device`` for tables of these sizes."""
+def _mine_members_sizes(type_constraint, n, num_rels):
+    """A ``TypeConstraint`` built for other sizes than the tables' is refused."""
     if type_constraint.num_nodes != n or type_constraint.num_rels != num_rels:
         raise ValueError(f'the TypeConstraint is for {type_constraint.num_nodes} entities / {type_constraint.num_rels} relations, the '
                          f'tables have {n} / {num_rels}')
+
+
+def _mine_members(type_constraint, n, num_rels, device):
+    """(ptr, ids) of ``TypeConstraint.members`` on ``device`` for tables of these sizes."""
+    _mine_members_sizes(type_constraint, n, num_rels)
     return type_constraint.members(device)
 
 
@@ -917,18 +922,31 @@ def mine_triplets_unfused(embedding, w, *, k=None, threshold=None, filter_index=
 COMPLETE_UNFUSED_ELEMS = 1 << 26      # logits per chunk of the materialised cross-check: bounds its (rows, R, N) tensor
 
 
-def complete_entities_from_scores(score, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True):
+def complete_entities_from_scores(score, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                                  cand_query=None, cand_other=None):
     """The rule of ``ops.entity_topk_scores`` on a materialised (m, R, N) logit tensor, in plain torch (any device): row i belongs
     to entity ``entities[i]``, its candidates are all (r, x) less the ids ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R + r]]``
     under relation r (the dense per-key ranges of ``_mine_filter``) and less ``x == a`` with ``exclude_self``; they go by logit
     descending, equal logits (-0 and +0 alike) by relation, then by entity, NaN after every other value.  Returns ``(rel int64
     (m, k), other int64 (m, k), logits float32 (m, k))``, padded with -1 / -1 / -inf; -0 is reported as +0 and every NaN as the
-    one quiet NaN.  ``topk_from_scores`` on the (m, R * N) view: the id r * N + x already says relation first, then entity."""
+    one quiet NaN.  ``topk_from_scores`` on the (m, R * N) view: the id r * N + x already says relation first, then entity.
+    ``cand_query`` / ``cand_other`` (bool (R, N), given together): the typed rule of ``ops.entity_topk_scores_typed`` -- (r, x) is
+    a candidate of entity a only with ``cand_query[r, a]`` and ``cand_other[r, x]`` (``complete_masks`` makes them of a
+    ``TypeConstraint``); an entity outside [0, N) then has no candidate at all."""
     m, num_rels, n = score.shape
     ents = torch.as_tensor(entities, dtype=torch.long, device=score.device).reshape(-1)
     if ents.numel() != m:
         raise ValueError('one query entity per row of the score tensor')
     allowed = torch.ones(m, num_rels, n, dtype=torch.bool, device=score.device)
+    if (cand_query is None) != (cand_other is None):
+        raise ValueError('cand_query and cand_other are given together or not at all')
+    if cand_query is not None:
+        cq, co = (torch.as_tensor(c, dtype=torch.bool, device=score.device) for c in (cand_query, cand_other))
+        if tuple(cq.shape) != (num_rels, n) or tuple(co.shape) != (num_rels, n):
+            raise ValueError(f'cand_query / cand_other: expected bool ({num_rels}, {n})')
+        inside = (ents >= 0) & (ents < n)
+        ents = ents.clamp(0, n - 1)                  # an entity outside the table: every candidate is denied here
+        allowed &= (cq[:, ents].t() & inside.view(-1, 1)).view(m, num_rels, 1) & co.view(1, num_rels, n)
     if filt_lo is not None:
         keys = (ents.view(-1, 1) * num_rels + torch.arange(num_rels, device=score.device)).reshape(-1)
         lo, hi = filt_lo.reshape(-1).to(score.device)[keys], filt_hi.reshape(-1).to(score.device)[keys]
@@ -938,6 +956,40 @@ def complete_entities_from_scores(score, entities, k, *, filt_lo=None, filt_hi=N
     ids, logits = topk_from_scores(score.reshape(m, num_rels * n), k, cand=allowed.view(m, num_rels * n))
     gone = ids < 0
     return torch.where(gone, ids, ids // n), torch.where(gone, ids, ids % n), logits
+
+
+class _Unconstrained:
+    """The default of ``complete_entities(type_constraint=)``: no constraint was given."""
+
+    def __repr__(self):
+        return 'UNCONSTRAINED'
+
+
+UNCONSTRAINED = _Unconstrained()
+
+
+def _complete_constraint(type_constraint):
+    """The ``type_constraint`` argument of the per-entity routes: None when it was left at its default ``UNCONSTRAINED``, else the
+    ``TypeConstraint`` given.  Anything else is a TypeError -- an explicit None too: the unconstrained call is the one that does not
+    name the argument, as it was before the argument existed."""
+    if type_constraint is UNCONSTRAINED:
+        return None
+    if not isinstance(type_constraint, TypeConstraint):
+        raise TypeError(f'type_constraint: expected a ranking.TypeConstraint, got {type(type_constraint).__name__} (leave the argument '
+                        f'out for the unconstrained call)')
+    return type_constraint
+
+
+def complete_masks(type_constraint, side, device=None):
+    """``(cand_query, cand_other)``, bool (R, N) each, of a ``TypeConstraint`` for per-entity completion on ``side``: 's' (facts
+    (a, r, x)) asks a among the subjects of r (set R + r) and x among its objects (set r); 'o' (facts (x, r, a)) the other way
+    round -- ``mine_triplets(type_constraint=)``'s definition of type-correct, seen from one entity."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    num_rels = type_constraint.num_rels
+    obj = type_constraint.mask(torch.arange(num_rels), device)
+    subj = type_constraint.mask(torch.arange(num_rels, 2 * num_rels), device)
+    return (subj, obj) if side == 's' else (obj, subj)
 
 
 def _complete_args(embedding, w, entities, k, side, filter_index):
@@ -954,7 +1006,8 @@ def _complete_args(embedding, w, entities, k, side, filter_index):
     return emb, wd, ents, k, filt
 
 
-def complete_entities(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True):
+def complete_entities(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True,
+                      type_constraint=UNCONSTRAINED):
     """What is this entity missing?  For every entity ``a`` of ``entities`` (any order, repeats allowed) the ``k`` most likely new
     facts around it over ALL relations at once: ``side='s'`` the facts (a, r, x), ``side='o'`` the facts (x, r, a), scored as
     ``predict_topk`` scores the queries (a, r) in that direction (logit = (e_a * w_r) . e_x + flow_log_prob: the query entity's row
@@ -962,18 +1015,33 @@ def complete_entities(embedding, w, entities, k, *, side='s', filter_index=None,
     ``side='o'`` -- and with ``exclude_self`` the loops (a, r, a).  One fused launch pair (ops.entity_topk_scores) keeps one list
     per entity while the relations are walked.  Returns ``(rel int64 (m, k), other int64 (m, k), logits float32 (m, k))`` in the
     order of ``complete_entities_from_scores``: best first, ties by relation, then by entity; rows with fewer than k candidates
-    end in -1 / -1 / -inf.  1 <= k <= 128."""
+    end in -1 / -1 / -inf.  1 <= k <= 128.  With a ``type_constraint`` (TypeConstraint) only type-correct facts are candidates --
+    the entity seen on its side of r and the other entity seen on the other side, ``mine_triplets(type_constraint=)``'s rule --
+    at the same logits, from the sweep over the relations' member lists (ops.entity_topk_scores_typed); the filter and the
+    constraint are independent and may come from different triplet sets.  An entity on its side of no relation gets an
+    all-padding row.  The unconstrained call leaves the argument out; an explicit None is a TypeError."""
+    type_constraint = _complete_constraint(type_constraint)
     emb, wd, ents, k, (lo, hi, ent) = _complete_args(embedding, w, entities, k, side, filter_index)
+    if type_constraint is not None:
+        set_ptr, set_ids = _mine_members(type_constraint, emb.shape[0], wd.shape[0], emb.device)
+        return ops.entity_topk_scores_typed(ents, emb, wd, k, set_ptr, set_ids, side, _mine_bias(flow_log_prob, emb.device), lo, hi, ent,
+                                            exclude_self)
     return ops.entity_topk_scores(ents, emb, wd, k, _mine_bias(flow_log_prob, emb.device), lo, hi, ent, exclude_self)
 
 
-def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True):
+def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True,
+                              type_constraint=UNCONSTRAINED):
     """``complete_entities`` from materialised logits: per relation ``ops.mul`` + ``ops.gemm`` into a (rows, R, N) tensor, then
     ``complete_entities_from_scores``, ``COMPLETE_UNFUSED_ELEMS`` logits at a time.  The in-repo cross-check and the bench's
-    baseline, never a fallback."""
+    baseline, never a fallback.  With a ``type_constraint`` the same logits under the masks of ``complete_masks``."""
+    type_constraint = _complete_constraint(type_constraint)
     emb, wd, ents, k, (lo, hi, ent) = _complete_args(embedding, w, entities, k, side, filter_index)
     emb, wd = emb.contiguous(), wd.contiguous()
     n, num_rels = emb.shape[0], wd.shape[0]
+    masks = {}
+    if type_constraint is not None:
+        _mine_members_sizes(type_constraint, n, num_rels)
+        masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, emb.device)))
     bias = _mine_bias(flow_log_prob, emb.device)
     rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
     out = []
@@ -984,7 +1052,8 @@ def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_ind
                              for r in range(num_rels)], dim=1)
         if bias is not None:
             score = score + bias
-        out.append(complete_entities_from_scores(score, part, k, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self))
+        out.append(complete_entities_from_scores(score, part, k, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self,
+                                                 **masks))
     if not out:
         z = torch.zeros(0, k, dtype=torch.int64, device=emb.device)
         return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=emb.device)

@@ -189,20 +189,22 @@ def profile_entities_arg(spec, num_nodes):
     return ids
 
 
-def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None):
+def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None, type_constraint=None):
     """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  logit  probability``: for every entity of
     ``entities`` its ``k`` most likely new facts over all relations (ranking.complete_entities; ``filter_index``: the known ones
     left out, as are loops), best first with the rank counted from 1 -- the 's' lines are the facts (entity, relation, other),
-    then the 'o' lines the facts (other, relation, entity).  An entity with fewer than k candidates has fewer lines.  Returns the
-    number of lines written."""
+    then the 'o' lines the facts (other, relation, entity).  An entity with fewer than k candidates has fewer lines.  With a
+    ``type_constraint`` (ranking.TypeConstraint) only type-correct facts are written, in the same columns.  Returns the number of
+    lines written."""
     n_lines = 0
     ents = torch.as_tensor(entities, dtype=torch.long, device=embed.device).reshape(-1)
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
     with torch.no_grad(), open(path, 'w') as f:
         for side in ('s', 'o'):
             for at in range(0, ents.numel(), PROFILE_ROWS):
                 part = ents[at:at + PROFILE_ROWS]
                 rel, other, logits = ranking.complete_entities(embed, w, part, k, side=side, filter_index=filter_index,
-                                                               flow_log_prob=flow_log_prob)
+                                                               flow_log_prob=flow_log_prob, **constrained)
                 prob = torch.sigmoid(logits)
                 for a, rs, xs, ls, ps in zip(part.tolist(), rel.tolist(), other.tolist(), logits.tolist(), prob.tolist()):
                     lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{l:.9g}\t{p:.9g}\n"
@@ -266,6 +268,8 @@ def check_args(args):
     """Flag combinations that are refused before anything is loaded."""
     if not 0 <= getattr(args, 'profile_topk', 0) <= ops.TOPK_MAX:
         raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
+    if getattr(args, 'profile_typed', False) and not getattr(args, 'profile_topk', 0) > 0:
+        raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
     wants = [f for f, on in (('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
                              ('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
                              ('--complete-threshold', getattr(args, 'complete_threshold', None) is not None),
@@ -370,10 +374,14 @@ def main(args):
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             who = profile_entities_arg(getattr(args, 'profile_entities', None), num_nodes)
+            typed = None
+            if getattr(args, 'profile_typed', False):      # (--type-constrain's sets are the same ones, when it is given as well)
+                typed = types if types is not None else \
+                    ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             n_lines = write_entity_profiles(args.profile_out, embed, model.w_relation, who, args.profile_topk, known,
-                                            model.encoder.get_flow_log_prob())
-            print(f"wrote {n_lines} new facts around {len(who)} entities (top {args.profile_topk} over all relations, as subject "
-                  f"and as object, known triplets filtered) to {args.profile_out}")
+                                            model.encoder.get_flow_log_prob(), typed)
+            print(f"wrote {n_lines} new {'type-correct ' if typed is not None else ''}facts around {len(who)} entities (top "
+                  f"{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}")
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -625,6 +633,10 @@ def build_parser():
     p.add_argument("--profile-out", type=str, default="profiles.tsv",
                    help="TSV of --profile-topk: entity, side (s: the entity is the subject, o: the object), relation, other "
                         "entity, rank from 1, logit, probability")
+    p.add_argument("--profile-typed", action="store_true",
+                   help="with --profile-topk: write type-correct facts only (the entity seen on its side of the relation, the other "
+                        "entity seen on the other side, in train + valid + test); the same columns; --type-constrain does not "
+                        "constrain profiles")
     p.add_argument("--sample-graph", type=int, default=0,
                    help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
                         "confident triplets among them to --sample-out; 0 = off")

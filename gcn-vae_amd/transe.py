@@ -61,7 +61,9 @@ ALL relations, as subject (``side='s'``) or as object (``side='o'``), at ``predi
 (gv_transe_entity_topk: one sorted list per entity while the relations are walked; no (entity x relation) query matrix).
 ``complete_entities_from_distances`` states the rule on a materialised (m, R, N) tensor; ``complete_entities_unfused`` is the
 per-relation cross-check.  ``--profile-topk K --profile-entities IDS|FILE --profile-out FILE`` write both sides in train.py's
-profile layout, the distance in place of the logit and probability.
+profile layout, the distance in place of the logit and probability.  With a ``type_constraint`` (``--profile-typed``) only
+type-correct facts are candidates, from ``ops.transe_entity_topk_typed`` (gv_transe_entity_topk_typed: the relations' candidate
+member lists are walked, rows gathered through the ids).
 
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
@@ -77,7 +79,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
-                      _mine_unfused, complete_entities_from_scores,
+                      UNCONSTRAINED, _complete_constraint, _mine_members_sizes, _mine_unfused, complete_entities_from_scores,
+                      complete_masks,
                       rank_from_scores_constrained, sort_and_rank, topk_from_scores)
 from .train import PROFILE_ROWS, profile_entities_arg
 
@@ -758,16 +761,19 @@ def write_completions(path, model_or_tables, filter_index, k=None, threshold=Non
 COMPLETE_UNFUSED_ELEMS = 1 << 26      # distances per chunk of the materialised cross-check: bounds its (rows, R, N) tensor
 
 
-def complete_entities_from_distances(dist, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True):
+def complete_entities_from_distances(dist, entities, k, *, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                                     cand_query=None, cand_other=None):
     """The rule of ``ops.transe_entity_topk`` on a materialised (m, R, N) distance tensor, in plain torch (any device): row i
     belongs to entity ``entities[i]``, its candidates are all (r, x) less the ids ``filt_ent[filt_lo[a * R + r]:filt_hi[a * R +
     r]]`` under relation r (the dense per-key ranges of ``_mine_filter``) and less ``x == a`` with ``exclude_self``; they go by
     distance ascending, equal distances by relation, then by entity, NaN after every number (+inf included).  Returns ``(rel int64
     (m, k), other int64 (m, k), dist float32 (m, k))``, padded with -1 / -1 / +inf; a zero is reported as +0 and every NaN as the
     one quiet NaN.  ``topk_from_distances`` on the (m, R * N) view under the allowed mask of
-    ``ranking.complete_entities_from_scores``: the id r * N + x already says relation first, then entity."""
+    ``ranking.complete_entities_from_scores``: the id r * N + x already says relation first, then entity.  ``cand_query`` /
+    ``cand_other`` (bool (R, N), ``ranking.complete_masks``): the typed rule of ``ops.transe_entity_topk_typed``, as there."""
     rel, other, neg = complete_entities_from_scores(-dist.to(torch.float32), entities, k, filt_lo=filt_lo, filt_hi=filt_hi,
-                                                    filt_ent=filt_ent, exclude_self=exclude_self)
+                                                    filt_ent=filt_ent, exclude_self=exclude_self, cand_query=cand_query,
+                                                    cand_other=cand_other)
     out = 0.0 - neg                                                   # -(+0) would be -0; 0 - (+0) is +0
     return rel, other, torch.where(torch.isnan(out), torch.full_like(out, float('nan')), out)
 
@@ -787,7 +793,7 @@ def _complete_args(model_or_tables, entities, k, side, filter_index):
     return ent.contiguous(), rel.contiguous(), ops._p_norm(p_norm), norm_flag, ents, k, filt
 
 
-def complete_entities(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True):
+def complete_entities(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True, type_constraint=UNCONSTRAINED):
     """What is this entity missing?  For every entity ``a`` of ``entities`` (any order, repeats allowed) the ``k`` nearest new
     facts around it over ALL relations at once: ``side='s'`` the facts (a, r, x) at ``||n(a) + n(r) - n(x)||_p``, ``side='o'`` the
     facts (x, r, a) at ``||n(a) - n(r) - n(x)||_p`` -- the distances of ``predict_topk`` on the queries (a, r) in direction 'o' /
@@ -796,21 +802,36 @@ def complete_entities(model_or_tables, entities, k, *, side='s', filter_index=No
     The normalised tables are built once and one fused launch pair (ops.transe_entity_topk) keeps one list per entity while the
     relations are walked.  Returns ``(rel int64 (m, k), other int64 (m, k), dist float32 (m, k))`` in the order of
     ``complete_entities_from_distances``: nearest first, ties by relation, then by entity; rows with fewer than k candidates end
-    in -1 / -1 / +inf.  1 <= k <= 128."""
+    in -1 / -1 / +inf.  1 <= k <= 128.  With a ``type_constraint`` (TypeConstraint) only type-correct facts are candidates -- the
+    entity seen on its side of r and the other entity seen on the other side, ``mine_triplets(type_constraint=)``'s rule -- at the
+    same distances, from the sweep over the relations' member lists (ops.transe_entity_topk_typed); the filter and the constraint
+    are independent.  An entity on its side of no relation gets an all-padding row.  The unconstrained call leaves the argument
+    out; an explicit None is a TypeError, as in ``ranking.complete_entities``."""
+    type_constraint = _complete_constraint(type_constraint)
     with torch.no_grad():
         ent, rel, p_norm, norm_flag, ents, k, (lo, hi, f_ent) = _complete_args(model_or_tables, entities, k, side, filter_index)
+        members = None if type_constraint is None else _mine_members(type_constraint, ent.shape[0], rel.shape[0], ent.device)
         en = ops.transe_queries(ent, norm_flag=norm_flag)                 # the normalised tables, once
         rn = ops.transe_queries(rel, norm_flag=norm_flag)
+        if members is not None:
+            return ops.transe_entity_topk_typed(ents, en, rn, k, p_norm, members[0], members[1], side == 'o', lo, hi, f_ent, exclude_self)
         return ops.transe_entity_topk(ents, en, rn, k, p_norm, side == 'o', lo, hi, f_ent, exclude_self)
 
 
-def complete_entities_unfused(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True):
+def complete_entities_unfused(model_or_tables, entities, k, *, side='s', filter_index=None, exclude_self=True,
+                              type_constraint=UNCONSTRAINED):
     """``complete_entities`` from materialised distances: per relation ``ops.transe_queries`` + ``ops.transe_distances`` into a
     (rows, R, N) tensor, then ``complete_entities_from_distances``, ``COMPLETE_UNFUSED_ELEMS`` distances at a time.  The in-repo
-    cross-check and the bench's comparator, never a fallback."""
+    cross-check and the bench's comparator, never a fallback.  With a ``type_constraint`` the same distances under the masks of
+    ``ranking.complete_masks``."""
+    type_constraint = _complete_constraint(type_constraint)
     with torch.no_grad():
         ent, rel, p_norm, norm_flag, ents, k, (lo, hi, f_ent) = _complete_args(model_or_tables, entities, k, side, filter_index)
         n, num_rels = ent.shape[0], rel.shape[0]
+        masks = {}
+        if type_constraint is not None:
+            _mine_members_sizes(type_constraint, n, num_rels)
+            masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, ent.device)))
         en = ops.transe_queries(ent, norm_flag=norm_flag)
         rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
         out = []
@@ -820,26 +841,28 @@ def complete_entities_unfused(model_or_tables, entities, k, *, side='s', filter_
                                                                         norm_flag=norm_flag), en, p_norm)
                                 for r in range(num_rels)], dim=1)
             out.append(complete_entities_from_distances(dist, part, k, filt_lo=lo, filt_hi=hi, filt_ent=f_ent,
-                                                        exclude_self=exclude_self))
+                                                        exclude_self=exclude_self, **masks))
         if not out:
             z = torch.zeros(0, k, dtype=torch.int64, device=ent.device)
             return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=ent.device)
         return tuple(torch.cat(t) for t in zip(*out))
 
 
-def write_entity_profiles(path, model_or_tables, entities, k, filter_index):
+def write_entity_profiles(path, model_or_tables, entities, k, filter_index, type_constraint=None):
     """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  distance``: for every entity of ``entities`` its
     ``k`` nearest new facts over all relations (``complete_entities``; ``filter_index``: the known ones left out, as are loops),
     nearest first with the rank counted from 1 -- the 's' lines are the facts (entity, relation, other), then the 'o' lines the
     facts (other, relation, entity).  The first five columns are those of train.py's ``profiles.tsv``: the two files join on them.
-    An entity with fewer than k candidates has fewer lines.  Returns the number of lines written."""
+    An entity with fewer than k candidates has fewer lines.  With a ``type_constraint`` (ranking.TypeConstraint) only type-correct
+    facts are written, in the same columns.  Returns the number of lines written."""
     n_lines = 0
     ents = torch.as_tensor(entities, dtype=torch.long).reshape(-1)
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
     with open(path, 'w') as f:
         for side in ('s', 'o'):
             for at in range(0, ents.numel(), PROFILE_ROWS):
                 part = ents[at:at + PROFILE_ROWS]
-                rel, other, dist = complete_entities(model_or_tables, part, k, side=side, filter_index=filter_index)
+                rel, other, dist = complete_entities(model_or_tables, part, k, side=side, filter_index=filter_index, **constrained)
                 for a, rs, xs, ds in zip(part.tolist(), rel.tolist(), other.tolist(), dist.tolist()):
                     lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{d:.9g}\n" for i, (r, x, d) in enumerate(zip(rs, xs, ds), 1) if r >= 0]
                     f.writelines(lines)
@@ -907,6 +930,10 @@ def build_parser():
     p.add_argument('--profile-out', type=str, default='transe_profiles.tsv',
                    help='TSV written by --profile-topk: entity, side (s: the entity is the subject, o: the object), relation, other '
                         'entity, rank (from 1), distance; the first five columns are those of train.py\'s --profile-out')
+    p.add_argument('--profile-typed', action='store_true',
+                   help='with --profile-topk: write type-correct facts only (the entity seen on its side of the relation, the other '
+                        'entity seen on the other side, in train + valid + test); the same columns; --type-constrain does not '
+                        'constrain profiles')
     return p
 
 
@@ -949,6 +976,8 @@ def check_args(args):
         raise ValueError('--type-constrain needs --filtered-eval: the report is raw, filtered, raw_constrained, filtered_constrained')
     if not 0 <= getattr(args, 'profile_topk', 0) <= ops.TOPK_MAX:
         raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
+    if getattr(args, 'profile_typed', False) and not getattr(args, 'profile_topk', 0) > 0:
+        raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
 
 
 def main(args):
@@ -1008,9 +1037,13 @@ def main(args):
               f'known triplets filtered) to {args.complete_out}')
     if who is not None:
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
-        n_lines = write_entity_profiles(args.profile_out, model, who, args.profile_topk, known)
-        print(f'wrote {n_lines} new facts around {len(who)} entities (nearest {args.profile_topk} over all relations, as subject and '
-              f'as object, known triplets filtered) to {args.profile_out}')
+        typed = None
+        if getattr(args, 'profile_typed', False):
+            typed = types if types is not None else \
+                TypeConstraint(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        n_lines = write_entity_profiles(args.profile_out, model, who, args.profile_topk, known, typed)
+        print(f'wrote {n_lines} new {"type-correct " if typed is not None else ""}facts around {len(who)} entities (nearest '
+              f'{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}')
     return out
 
 

@@ -587,6 +587,26 @@ int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, 
                           int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
                           int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
 
+/* gv_entity_topk_scores among the TYPE-CORRECT facts only: a query entity's candidates under relation r are the members of set
+ * cand_base + r, and only when the entity itself is a member of set num_rels - cand_base + r (it has no candidate under r
+ * otherwise).  The sets are gv_mine_scores_typed's: set_ptr int64 [2 num_rels + 1] from 0, non-decreasing, set j's members
+ * set_ids[set_ptr[j] .. set_ptr[j + 1]) int32, strictly ascending, each in [0, n) -- set r = the entities seen as object of
+ * relation r, set num_rels + r = those seen as its subject (ranking.TypeConstraint.members).  cand_base = 0: the facts (a, r, x), a
+ * among r's subjects and x among its objects; cand_base = num_rels: the facts (x, r, a) the other way round (any other value is
+ * refused).  tile_ptr int32 [num_rels + 1] is the prefix of ceil(|set cand_base + r| / 64) over r, n_tiles = tile_ptr[num_rels]: a
+ * row's columns are the r-major sequence of (relation, 64-member tile) pairs, and span_tiles counts those.  Everything else --
+ * the logits bit for bit, the filter (independent of the sets: a listed id need not be a member), exclude_self, order, ties, NaN,
+ * -0, padding, the outputs, 1 <= k <= 128, n * num_rels < 2^31 -- is gv_entity_topk_scores'.  An entity that is on the query side
+ * of no relation, or outside [0, n), gives an all-padding row; m = 0 launches nothing, n_tiles = 0 writes padding without walking
+ * anything.  gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles) = m * n_spans * k * 8 (0 for sizes the entry
+ * refuses); workspace_bytes is checked against it.  The result does not depend on span_tiles.  No atomics. */
+int64_t gv_entity_topk_scores_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles);
+int gv_entity_topk_scores_typed(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                                const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, const int64_t* set_ptr,
+                                const int32_t* set_ids, const int32_t* tile_ptr, int n_tiles, int cand_base, int exclude_self, int k,
+                                int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
+                                int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+
 /* Monte-Carlo posterior-predictive ranking and top-k for a variational encoder: S posterior samples instead of one draw.
  * Sample s has a query matrix Q_s (m, h) at q + s * q_stride and an entity table E_s (v, h) at e + s * e_stride (strides in
  * elements; the leading dimensions ld_q / ld_e are shared by the samples) and an optional bias[s] (that draw's flow_log_prob;
@@ -835,6 +855,17 @@ int gv_transe_entity_topk(const int32_t* ents, int m, const float* en, const flo
                           int p_norm, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
                           int exclude_self, int k, int span_tiles, int64_t* out_rel, int64_t* out_ent, float* out_dist,
                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/* gv_transe_entity_topk among the TYPE-CORRECT facts only, with the member lists, tile_ptr / n_tiles and cand_base of
+ * gv_entity_topk_scores_typed (head = 0 goes with cand_base = 0, head = 1 with cand_base = num_rels; the entry does not tie them).
+ * The distances bit for bit, the filter, exclude_self, order, padding and outputs are gv_transe_entity_topk's; span_tiles counts
+ * (relation, 64-member tile) pairs; gv_transe_entity_topk_typed_workspace_bytes(m, n_tiles, k, span_tiles) = m * n_spans * k * 8. */
+int64_t gv_transe_entity_topk_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles);
+int gv_transe_entity_topk_typed(const int32_t* ents, int m, const float* en, const float* rn, int n, int num_rels, int dim, int head,
+                                int p_norm, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                const int64_t* set_ptr, const int32_t* set_ids, const int32_t* tile_ptr, int n_tiles, int cand_base,
+                                int exclude_self, int k, int span_tiles, int64_t* out_rel, int64_t* out_ent, float* out_dist,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Whole-graph triplet mining for TransE (csrc/k_transe_mine.hip): every (s, r, o) of the dense tables en (n, dim) and rn (num_rels,
  * dim), both as gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
