@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "k_mc.h"
@@ -771,8 +772,24 @@ struct EntityTopkParams {
     unsigned long long* part;     // [m][n_spans][topk]
 };
 
-template <int NK>
-__global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams ep) {
+// MC (gv_entity_topk_scores_mc): the samples beside the parent's parameters, which keep their layout; e.bias then holds one value
+// per sample
+struct EntityTopkMcParams {
+    EntityTopkParams e;
+    McSamples mc;
+};
+
+__device__ __forceinline__ const EntityTopkParams& entity_topk_params(const EntityTopkParams& pp) { return pp; }
+__device__ __forceinline__ const EntityTopkParams& entity_topk_params(const EntityTopkMcParams& pp) { return pp.e; }
+
+// MC: the key's value is pbar -- mc_pbar_tile's arithmetic around score_tile_with, sample s reading the table at b + s * e_stride
+// for the query rows E_s[a] and the candidate rows alike, the one w shared -- written to Ls and selected ONCE per tile; the walk,
+// the cursors and the selection never see a sample.  Under each sample's sigmoids the next sample's first k-chunk is in flight,
+// under the last one's the next tile's sample-0 chunk.  The samples come in a wrapper struct and the single-sample branch keeps
+// the parent's statements spelled out (no helper shared with the MC branch): either a longer EntityTopkParams or a shared lambda
+// costs the single-sample kernel two registers and its fifth wave; the typed kernel below does the same.
+template <int NK, bool MC = false>
+__global__ __launch_bounds__(256) void k_entity_topk_span(const std::conditional_t<MC, EntityTopkMcParams, EntityTopkParams> pp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256;
     __shared__ float As[BK * SC_LDA];
     __shared__ float Bs[BK * SC_LDB];
@@ -782,6 +799,7 @@ __global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams
     __shared__ int fl[4][64];
     __shared__ int ent_s[BM];                      // the rows' entities (-1: no such row)
     extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const EntityTopkParams& ep = entity_topk_params(pp);
     const GemmParams& p = ep.g;
     const int k = ep.topk;
     const int m0 = blockIdx.x * BM;
@@ -797,7 +815,7 @@ __global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams
     const int a_row = m0 + threadIdx.x / (BK / APT), a_col = (threadIdx.x % (BK / APT)) * APT;
     const int a_ent = a_row < p.m ? ep.ents[a_row] : -1;
     const bool a_ok = (unsigned)a_ent < (unsigned)p.n;
-    const float* a_src = p.b + (a_ok ? (size_t)a_ent * p.ldb : 0) + a_col;
+    const float* a_src = p.b + (a_ok ? (size_t)a_ent * p.ldb : 0) + a_col;     // (MC: of the sample at hand)
     const float* w_src = ep.w + a_col;             // + r * ld_w
     auto load_q = [&](int k0, float (&r)[APT]) {
         float wv[APT];
@@ -815,16 +833,47 @@ __global__ __launch_bounds__(256) void k_entity_topk_span(const EntityTopkParams
         load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
     }
     topk_span_clear<BM>(lists, k, fl, thr, lane, wid, [&](int rl) { topk_pair_entity(ep.ents, m0, rl, p.m, p.n, ent_s); });
-    const float bv = ep.bias ? *ep.bias : 0.f;
+    const float bv = (!MC && ep.bias) ? *ep.bias : 0.f;
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = walk.ct * BN;
-        const f32x16 acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
-        const TopkPairTile tile = walk.step(col_tiles, t == t_begin);
-        if (walk.r != tile.r) w_src += ep.ld_w;
-        if (t + 1 < t_end) {                                       // the next tile's first operands fly under the selection
-            load_q(0, ra);
-            load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
+        f32x16 acc;
+        TopkPairTile tile;
+        if constexpr (MC) {
+            const McSamples& mc = pp.mc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            GemmParams ps = p;                                     // b: the table of the sample at hand
+            for (int s = 0; s < mc.n_samples; ++s) {
+                const f32x16 lg = score_tile_with(ps, load_q, n0, ra, rb, As, Bs);
+                const float bs = ep.bias ? ep.bias[s] : 0.f;
+                if (s + 1 < mc.n_samples) {                        // the next sample's first operands fly under the sigmoids
+                    a_src += mc.e_stride;
+                    ps.b += mc.e_stride;
+                    load_q(0, ra);
+                    load_b<true, BN, BK>(ps, n0, 0, p.k, rb);
+                } else {                                           // ... under the last one's, the next tile's of sample 0
+                    a_src -= (long long)s * mc.e_stride;
+                    tile = walk.step(col_tiles, t == t_begin);
+                    if (walk.r != tile.r) w_src += ep.ld_w;
+                    if (t + 1 < t_end) {
+                        load_q(0, ra);
+                        load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] += mc_sig(lg[i] + bs);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] *= mc.inv_s;
+        } else {
+            acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
+            tile = walk.step(col_tiles, t == t_begin);
+            if (walk.r != tile.r) w_src += ep.ld_w;
+            if (t + 1 < t_end) {                                   // the next tile's first operands fly under the selection
+                load_q(0, ra);
+                load_b<true, BN, BK>(p, walk.ct * BN, 0, p.k, rb);
+            }
         }
         // (every wave is past score_tile's last barrier: nobody still reads the previous relation's cursors, or Ls)
         if (tile.opens && threadIdx.x < BM)
@@ -863,8 +912,19 @@ struct EntityTopkTypedParams {
     TopkTyped ty;
 };
 
-template <int NK>
-__global__ __launch_bounds__(256) void k_entity_topk_typed_span(const EntityTopkTypedParams tp) {
+struct EntityTopkTypedMcParams {  // MC (gv_entity_topk_scores_typed_mc), as EntityTopkMcParams
+    EntityTopkTypedParams t;
+    McSamples mc;
+};
+
+__device__ __forceinline__ const EntityTopkTypedParams& entity_topk_params(const EntityTopkTypedParams& pp) { return pp; }
+__device__ __forceinline__ const EntityTopkTypedParams& entity_topk_params(const EntityTopkTypedMcParams& pp) { return pp.t; }
+
+// MC: k_entity_topk_span's sample loop around score_tile_gather -- the gathered member rows and the query rows both read at
+// + s * e_stride -- with the membership test, the id buffers and the filter window outside it.
+template <int NK, bool MC = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC ? 4 : 1))) void k_entity_topk_typed_span(
+    const std::conditional_t<MC, EntityTopkTypedMcParams, EntityTopkTypedParams> pp) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256, BPT = BN * BK / 256;
     __shared__ float As[BK * SC_LDA];
     __shared__ float Bs[BK * SC_LDB];
@@ -876,6 +936,7 @@ __global__ __launch_bounds__(256) void k_entity_topk_typed_span(const EntityTopk
     __shared__ int live_s[BM];                     // the row's entity is on the query side of the relation at hand
     __shared__ int ids_s[3][BN];                   // the member ids of the tile at hand, the next and the previous one (-1: none)
     extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const EntityTopkTypedParams& tp = entity_topk_params(pp);
     const EntityTopkParams& ep = tp.e;
     const TopkTyped& ty = tp.ty;
     const GemmParams& p = ep.g;
@@ -926,7 +987,7 @@ __global__ __launch_bounds__(256) void k_entity_topk_typed_span(const EntityTopk
         load_q(0, ra);
         load_e(0, rb);
     }
-    const float bv = ep.bias ? *ep.bias : 0.f;
+    const float bv = (!MC && ep.bias) ? *ep.bias : 0.f;
 
     int buf = 0;
     for (int t = t_begin; t < t_end; ++t) {
@@ -939,12 +1000,41 @@ __global__ __launch_bounds__(256) void k_entity_topk_typed_span(const EntityTopk
             next = topk_typed_next(ty, num_rels, tile, t);
             if (threadIdx.x < BN) ids_s[nbuf][threadIdx.x] = topk_typed_id(ty, next, p.n, threadIdx.x);
         }
-        const f32x16 acc = score_tile_gather(p, load_q, load_e, ra, rb, As, Bs);
-        if (more) {                                                // the next tile's first operands fly under the selection
-            w_src = ep.w + (size_t)next.r * ep.ld_w + a_col;
-            gather_from(ids_s[nbuf]);
-            load_q(0, ra);
-            load_e(0, rb);
+        f32x16 acc;
+        if constexpr (MC) {
+            const McSamples& mc = pp.mc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            for (int s = 0; s < mc.n_samples; ++s) {
+                const f32x16 lg = score_tile_gather(p, load_q, load_e, ra, rb, As, Bs);
+                const float bs = ep.bias ? ep.bias[s] : 0.f;
+                if (s + 1 < mc.n_samples) {                        // the next sample's first operands fly under the sigmoids
+                    a_src += mc.e_stride;
+                    b_src += mc.e_stride;
+                    load_q(0, ra);
+                    load_e(0, rb);
+                } else {                                           // ... under the last one's, the next tile's of sample 0
+                    a_src -= (long long)s * mc.e_stride;
+                    if (more) {                                    // (gather_from starts over from sample 0's table)
+                        w_src = ep.w + (size_t)next.r * ep.ld_w + a_col;
+                        gather_from(ids_s[nbuf]);
+                        load_q(0, ra);
+                        load_e(0, rb);
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] += mc_sig(lg[i] + bs);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] *= mc.inv_s;
+        } else {
+            acc = score_tile_gather(p, load_q, load_e, ra, rb, As, Bs);
+            if (more) {                                            // the next tile's first operands fly under the selection
+                w_src = ep.w + (size_t)next.r * ep.ld_w + a_col;
+                gather_from(ids_s[nbuf]);
+                load_q(0, ra);
+                load_e(0, rb);
+            }
         }
         const int* ids = ids_s[buf];
         // (every wave is past the tile's last barrier: nobody still reads the previous relation's cursors or flags, or Ls)
@@ -1709,42 +1799,123 @@ extern "C" int gv_pair_prob_std_mc(const float* q, int ld_q, int64_t q_stride, c
     return launch_status(name);
 }
 
-// ---- per-entity completion (gv_entity_topk_scores): the spans and their checks are entity_query_* of k_query_args.h ------------
+// ---- per-entity completion (gv_entity_topk_scores{,_mc}): the spans and their checks are entity_query_* of k_query_args.h -------
 extern "C" int64_t gv_entity_topk_scores_workspace_bytes(int m, int n, int num_rels, int k) {
     return entity_query_workspace_bytes(m, n, num_rels, k, 0);      // (the library's rule: a caller's span_tiles sizes its own)
 }
 
-extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
-                                     const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int exclude_self,
-                                     int k, int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
-                                     int64_t workspace_bytes, int n, int num_rels, int h, void* stream) {
-    const char* name = "gv_entity_topk_scores";
-    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE,
-               "gv_entity_topk_scores: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", m, n, num_rels, h, n_filt_ent);
-    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
+// the sample geometry of the two Monte-Carlo per-entity entries, reported where the parents report their leading dimensions:
+// n_samples >= 1, and with more than one sample the stride spans the table (mc_samples_args without a query stack)
+static int entity_mc_samples_args(const char* name, int ld_e, int ld_w, int64_t e_stride, int n_samples, int n, int h, McSamples* mc) {
+    GV_REQUIRE(n_samples >= 1, GV_ERR_SHAPE, "%s: n_samples=%d", name, n_samples);
     GV_CHECK(query_leading(name, ld_e, ld_w, h));
-    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
-    if (m == 0) return GV_OK;
-    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_logits && workspace));
-    EntityTopkParams ep;
-    ep.g = score_gemm_params(nullptr, ld_e, e, ld_e, m, n, h);
+    GV_REQUIRE(n_samples == 1 || e_stride >= (int64_t)(n - 1) * ld_e + h, GV_ERR_SHAPE,
+               "%s: sample stride shorter than the table it spans (e_stride=%lld)", name, (long long)e_stride);
+    mc->q_stride = 0;
+    mc->e_stride = n_samples > 1 ? e_stride : 0;
+    mc->n_samples = n_samples;
+    mc->inv_s = 1.0f / (float)n_samples;
+    return GV_OK;
+}
+
+// the parent's parameters inside an entry's own (the MC forms carry the samples beside them)
+static EntityTopkParams& entity_topk_host_params(EntityTopkParams& pp, const McSamples&) { return pp; }
+static EntityTopkParams& entity_topk_host_params(EntityTopkMcParams& pp, const McSamples& mc) { pp.mc = mc; return pp.e; }
+static EntityTopkTypedParams& entity_topk_host_params(EntityTopkTypedParams& pp, const McSamples&) { return pp; }
+static EntityTopkTypedParams& entity_topk_host_params(EntityTopkTypedMcParams& pp, const McSamples& mc) { pp.mc = mc; return pp.t; }
+
+// what the four per-entity entries put into EntityTopkParams alike (mc.n_samples == 0: not Monte-Carlo); the spans follow
+static void entity_topk_fill(EntityTopkParams& ep, const McSamples& mc, const int32_t* ents, int m, const float* e, int ld_e,
+                             const float* w, int ld_w, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                             int n_filt_ent, int exclude_self, int k, int n, int num_rels, int h) {
+    ep.g = mc_gemm_params(nullptr, ld_e, e, ld_e, mc, m, n, h);     // (the 16-byte loads need every sample's table aligned)
     ep.ents = ents; ep.w = w; ep.ld_w = ld_w;
     ep.vec_a = ep.g.vec_b && aligned16(w) && (ld_w % 4 == 0);
     ep.num_rels = num_rels; ep.exclude_self = exclude_self != 0;
     ep.bias = bias;
     ep.filt_lo = filt_lo; ep.filt_hi = filt_hi; ep.filt_ent = filt_ent; ep.n_ent = n_filt_ent;
     ep.topk = k;
+}
+
+template <bool MC>
+static int entity_topk_entry(const char* name, const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                             const float* w, int ld_w, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                             int n_filt_ent, int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent,
+                             float* out_values, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", name,
+               m, n, num_rels, h, n_filt_ent);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
+    McSamples mc{};
+    if constexpr (MC) GV_CHECK(entity_mc_samples_args(name, ld_e, ld_w, e_stride, n_samples, n, h, &mc));
+    else GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_values && workspace));
+    std::conditional_t<MC, EntityTopkMcParams, EntityTopkParams> pp;
+    EntityTopkParams& ep = entity_topk_host_params(pp, mc);
+    entity_topk_fill(ep, mc, ents, m, e, ld_e, w, ld_w, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, k, n, num_rels, h);
     entity_query_spans(m, n, num_rels, span_tiles, &ep.span_tiles, &ep.n_spans);
     GV_CHECK(entity_query_workspace(name, m, k, span_tiles, ep.n_spans, workspace_bytes));
     ep.part = (unsigned long long*)workspace;
-    return topk_span_merge<k_entity_topk_span<1>, k_entity_topk_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
-        name, dim3((m + 63) / 64, ep.n_spans), ep, ep.part, m, ep.n_spans, k, TopkPairOut<int, topk_key_logit>{out_rel, out_ent, out_logits, n},
+    return topk_span_merge<k_entity_topk_span<1, MC>, k_entity_topk_span<2, MC>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
+        name, dim3((m + 63) / 64, ep.n_spans), pp, ep.part, m, ep.n_spans, k, TopkPairOut<int, topk_key_logit>{out_rel, out_ent, out_values, n},
         (hipStream_t)stream);
 }
 
-// ---- per-entity completion among type-correct facts (gv_entity_topk_scores_typed): spans of the member lists' tiles ---------------
+extern "C" int gv_entity_topk_scores(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                                     const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent, int exclude_self,
+                                     int k, int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
+                                     int64_t workspace_bytes, int n, int num_rels, int h, void* stream) {
+    return entity_topk_entry<false>("gv_entity_topk_scores", ents, m, e, ld_e, 0, 0, w, ld_w, bias, filt_lo, filt_hi, filt_ent, n_filt_ent,
+                                    exclude_self, k, span_tiles, out_rel, out_ent, out_logits, workspace, workspace_bytes, n, num_rels, h,
+                                    stream);
+}
+
+extern "C" int gv_entity_topk_scores_mc(const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w,
+                                        int ld_w, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                                        int n_filt_ent, int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent,
+                                        float* out_prob, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h,
+                                        void* stream) {
+    return entity_topk_entry<true>("gv_entity_topk_scores_mc", ents, m, e, ld_e, e_stride, n_samples, w, ld_w, bias, filt_lo, filt_hi,
+                                   filt_ent, n_filt_ent, exclude_self, k, span_tiles, out_rel, out_ent, out_prob, workspace,
+                                   workspace_bytes, n, num_rels, h, stream);
+}
+
+// ---- per-entity completion among type-correct facts (gv_entity_topk_scores_typed{,_mc}): spans of the member lists' tiles --------
 extern "C" int64_t gv_entity_topk_scores_typed_workspace_bytes(int m, int n_tiles, int k, int span_tiles) {
     return entity_typed_workspace_bytes(m, n_tiles, k, span_tiles);
+}
+
+template <bool MC>
+static int entity_topk_typed_entry(const char* name, const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                   const float* w, int ld_w, const float* bias, const int* filt_lo, const int* filt_hi,
+                                   const int* filt_ent, int n_filt_ent, const int64_t* set_ptr, const int32_t* set_ids,
+                                   const int32_t* tile_ptr, int n_tiles, int cand_base, int exclude_self, int k, int span_tiles,
+                                   int32_t* out_rel, int32_t* out_ent, float* out_values, void* workspace, int64_t workspace_bytes, int n,
+                                   int num_rels, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", name,
+               m, n, num_rels, h, n_filt_ent);
+    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
+    GV_CHECK(entity_typed_shape(name, num_rels, n_tiles, cand_base));
+    McSamples mc{};
+    if constexpr (MC) GV_CHECK(entity_mc_samples_args(name, ld_e, ld_w, e_stride, n_samples, n, h, &mc));
+    else GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
+    if (m == 0) return GV_OK;
+    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_values && workspace));
+    GV_CHECK(entity_typed_given(name, set_ptr, set_ids, tile_ptr, n_tiles));
+    std::conditional_t<MC, EntityTopkTypedMcParams, EntityTopkTypedParams> pp;
+    EntityTopkTypedParams& tp = entity_topk_host_params(pp, mc);
+    EntityTopkParams& ep = tp.e;
+    entity_topk_fill(ep, mc, ents, m, e, ld_e, w, ld_w, bias, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, k, n, num_rels, h);
+    entity_typed_spans(m, n_tiles, span_tiles, &ep.span_tiles, &ep.n_spans);
+    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, ep.n_spans, workspace_bytes));
+    ep.part = (unsigned long long*)workspace;
+    tp.ty = TopkTyped{(const long long*)set_ptr, set_ids, tile_ptr, cand_base, n_tiles};
+    const TopkPairOut<int, topk_key_logit> out{out_rel, out_ent, out_values, n};
+    if (n_tiles == 0) return topk_all_padding(name, ep.part, m, k, out, (hipStream_t)stream);
+    return topk_span_merge<k_entity_topk_typed_span<1, MC>, k_entity_topk_typed_span<2, MC>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
+        name, dim3((m + 63) / 64, ep.n_spans), pp, ep.part, m, ep.n_spans, k, out, (hipStream_t)stream);
 }
 
 extern "C" int gv_entity_topk_scores_typed(const int32_t* ents, int m, const float* e, int ld_e, const float* w, int ld_w, const float* bias,
@@ -1753,33 +1924,20 @@ extern "C" int gv_entity_topk_scores_typed(const int32_t* ents, int m, const flo
                                            int cand_base, int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent,
                                            float* out_logits, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h,
                                            void* stream) {
-    const char* name = "gv_entity_topk_scores_typed";
-    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_ent >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_ent=%d", name,
-               m, n, num_rels, h, n_filt_ent);
-    GV_CHECK(entity_query_shape(name, n, num_rels, k, span_tiles));
-    GV_CHECK(entity_typed_shape(name, num_rels, n_tiles, cand_base));
-    GV_CHECK(query_leading(name, ld_e, ld_w, h));
-    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_ent));
-    if (m == 0) return GV_OK;
-    GV_CHECK(query_pointers(name, ents && e && w && out_rel && out_ent && out_logits && workspace));
-    GV_CHECK(entity_typed_given(name, set_ptr, set_ids, tile_ptr, n_tiles));
-    EntityTopkTypedParams tp;
-    EntityTopkParams& ep = tp.e;
-    ep.g = score_gemm_params(nullptr, ld_e, e, ld_e, m, n, h);
-    ep.ents = ents; ep.w = w; ep.ld_w = ld_w;
-    ep.vec_a = ep.g.vec_b && aligned16(w) && (ld_w % 4 == 0);
-    ep.num_rels = num_rels; ep.exclude_self = exclude_self != 0;
-    ep.bias = bias;
-    ep.filt_lo = filt_lo; ep.filt_hi = filt_hi; ep.filt_ent = filt_ent; ep.n_ent = n_filt_ent;
-    ep.topk = k;
-    entity_typed_spans(m, n_tiles, span_tiles, &ep.span_tiles, &ep.n_spans);
-    GV_CHECK(entity_query_workspace(name, m, k, span_tiles, ep.n_spans, workspace_bytes));
-    ep.part = (unsigned long long*)workspace;
-    tp.ty = TopkTyped{(const long long*)set_ptr, set_ids, tile_ptr, cand_base, n_tiles};
-    const TopkPairOut<int, topk_key_logit> out{out_rel, out_ent, out_logits, n};
-    if (n_tiles == 0) return topk_all_padding(name, ep.part, m, k, out, (hipStream_t)stream);
-    return topk_span_merge<k_entity_topk_typed_span<1>, k_entity_topk_typed_span<2>, false, 64>(      // (<= 64 KiB of lists + 28 KiB static)
-        name, dim3((m + 63) / 64, ep.n_spans), tp, ep.part, m, ep.n_spans, k, out, (hipStream_t)stream);
+    return entity_topk_typed_entry<false>("gv_entity_topk_scores_typed", ents, m, e, ld_e, 0, 0, w, ld_w, bias, filt_lo, filt_hi, filt_ent,
+                                          n_filt_ent, set_ptr, set_ids, tile_ptr, n_tiles, cand_base, exclude_self, k, span_tiles, out_rel,
+                                          out_ent, out_logits, workspace, workspace_bytes, n, num_rels, h, stream);
+}
+
+extern "C" int gv_entity_topk_scores_typed_mc(const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples,
+                                              const float* w, int ld_w, const float* bias, const int* filt_lo, const int* filt_hi,
+                                              const int* filt_ent, int n_filt_ent, const int64_t* set_ptr, const int32_t* set_ids,
+                                              const int32_t* tile_ptr, int n_tiles, int cand_base, int exclude_self, int k,
+                                              int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_prob, void* workspace,
+                                              int64_t workspace_bytes, int n, int num_rels, int h, void* stream) {
+    return entity_topk_typed_entry<true>("gv_entity_topk_scores_typed_mc", ents, m, e, ld_e, e_stride, n_samples, w, ld_w, bias, filt_lo,
+                                         filt_hi, filt_ent, n_filt_ent, set_ptr, set_ids, tile_ptr, n_tiles, cand_base, exclude_self, k,
+                                         span_tiles, out_rel, out_ent, out_prob, workspace, workspace_bytes, n, num_rels, h, stream);
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

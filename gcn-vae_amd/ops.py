@@ -940,6 +940,71 @@ def topk_scores_mc_constrained(q, entities, k, cand, cand_set, bias=None, filt_l
     return _topk_scores('gv_topk_scores_mc_constrained', q, entities, k, bias, (filt_lo, filt_hi, filt_ent), (cand, cand_set), mc=True)
 
 
+def _entity_topk_mc_operands(ents, z, w):
+    """The shape checks of the Monte-Carlo per-entity wrappers, ahead of any look at the tensors' device: ``z`` an (S, N, h) stack
+    with at least one sample, then ``_entity_topk_operands`` on a sample.  Returns (S, m, n, num_rels, h)."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] < 1:
+        raise TypeError('z: expected a 3-D (samples, entities, width) tensor with at least one sample')
+    return (z.shape[0],) + _entity_topk_operands(ents, z[0], w)
+
+
+def entity_topk_scores_mc(ents, z, w, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
+    """``entity_topk_scores`` on the Monte-Carlo posterior predictive of S samples (gv_entity_topk_scores_mc): ``z`` (S, N, h) holds
+    one entity table per sample (unit inner stride; row and sample strides are kept when they span their rows / table), ``w`` the
+    one relation table, ``bias`` (S,) optionally each draw's flow_log_prob.  The value selected is
+    ``pbar[i, r, x] = mean_s sigmoid((z_s[a] * w[r]) . z_s[x] + bias[s])``, summed in ascending sample order in registers and
+    selected once per (relation, column tile): bit for bit the ``prob_mean`` ``topk_scores_mc`` returns for the query
+    ``mul(z_s[a], w[r])`` at entity x.  Filter, ``exclude_self``, ``span`` and padding (-1 / -1 / -inf) are ``entity_topk_scores``';
+    order: pbar descending, then relation, then entity ascending -- pbar saturates, so candidates whose every sample rounds to
+    1.0f are a real tie, broken by (r, x); a NaN in any sample gives NaN, after everything.  Returns ``(rel int64 (m, k), ent int64
+    (m, k), prob_mean float32 (m, k))``."""
+    s, m, n, num_rels, h = _entity_topk_mc_operands(ents, z, w)
+    k = _topk_arg(k)
+    (lo32, hi32, ent32, n_ent), (rel, ent, prob), ents32, span_tiles = _entity_topk_args(
+        ents, span, 'column', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, z.device)
+    z, ld_e, e_stride = _mine_sample_stack(z, 'z')
+    w, ld_w = _row_major(w, 'w')
+    dev = z.device
+    if m == 0:
+        return rel.long(), ent.long(), prob
+    bias = _mc_bias_arg(bias, s, dev)
+    if span_tiles:      # (a given span's lists are sized here, as entity_topk_scores does)
+        tiles = num_rels * ((n + 63) // 64)
+        ws_bytes = m * ((tiles + span_tiles - 1) // span_tiles) * k * 8
+    else:
+        ws_bytes = int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_entity_topk_scores_mc', ptr(ents32), m, ptr(z), ld_e, e_stride, s, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(prob), ptr(ws), ws_bytes, n, num_rels, h,
+             lib.stream())
+    return rel.long(), ent.long(), prob
+
+
+def entity_topk_scores_typed_mc(ents, z, w, k, set_ptr, set_ids, side='s', bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                                exclude_self=True, span=None):
+    """``entity_topk_scores_mc`` among the TYPE-CORRECT facts only (gv_entity_topk_scores_typed_mc): the member lists, ``side`` and
+    ``span`` of ``entity_topk_scores_typed``, the samples, ``bias`` (S,), pbar, order, ties, NaN and padding of
+    ``entity_topk_scores_mc`` -- a candidate's pbar is the untyped sweep's, bit for bit.  Returns ``(rel int64 (m, k), ent int64
+    (m, k), prob_mean float32 (m, k))``."""
+    s, m, n, num_rels, h = _entity_topk_mc_operands(ents, z, w)
+    k = _topk_arg(k)
+    (lo32, hi32, ent32, n_ent), (rel, ent, prob), ents32, _ = _entity_topk_args(
+        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, z.device)
+    z, ld_e, e_stride = _mine_sample_stack(z, 'z')
+    w, ld_w = _row_major(w, 'w')
+    dev = z.device
+    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, dev)
+    if m == 0:
+        return rel.long(), ent.long(), prob
+    bias = _mc_bias_arg(bias, s, dev)
+    ws_bytes = int(lib.load().gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call('gv_entity_topk_scores_typed_mc', ptr(ents32), m, ptr(z), ld_e, e_stride, s, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32),
+             ptr(ent32), n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k, span_tiles,
+             ptr(rel), ptr(ent), ptr(prob), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+    return rel.long(), ent.long(), prob
+
+
 def pair_prob_std_mc(q, entities, ids, bias=None):
     """Population standard deviation over the samples of ``sigmoid(q[s, i] . entities[s, ids[i, c]] + bias[s])`` for every
     selected pair (gv_pair_prob_std_mc; two-pass in fp32, the dot a plain fmaf chain): float32 (m, k).  Padding ids (-1) give

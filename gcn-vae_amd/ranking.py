@@ -43,7 +43,11 @@ with S samples from ``KGVAE.posterior_samples``, ``calc_mc_mrr`` ranks and ``pre
 ``pbar = mean_s sigmoid(logit_s)`` -- ``ops.rank_scores_mc`` / ``ops.topk_scores_mc`` loop over the samples around the same
 score tile and keep pbar in registers -- and ``predict_topk_mc`` adds each proposal's spread over the samples.  pbar is a
 probability, so it saturates and ties are real; they share the mid-rank.  ``mc_mean_prob`` / ``mc_ranks_from_probs`` state the
-rule on materialised values; the ``*_mc_unfused`` routes are the per-sample GEMM cross-check.
+rule on materialised values; the ``*_mc_unfused`` routes are the per-sample GEMM cross-check.  ``mine_triplets_mc`` mines the
+type-correct triplets on pbar, and ``complete_entities_mc`` is per-entity completion on it, typed or not
+(``ops.entity_topk_scores_mc`` / ``ops.entity_topk_scores_typed_mc``: the sample loop inside each (relation, tile), one selection
+per tile), with the mean and the spread of every returned fact; ``complete_entities_mc_from_probs`` states its rule on
+materialised probabilities and ``complete_entities_mc_unfused`` is the cross-check.
 """
 import torch
 
@@ -1134,6 +1138,103 @@ def mine_triplets_mc_unfused(z, w, *, k=None, threshold=None, filter_index=None,
         logit = (z[:, s_] * wd[r_] * z[:, o_]).sum(-1)
         std.append(torch.sigmoid(logit if flp is None else logit + flp.view(-1, 1)).std(dim=0, unbiased=False))
     return trip, probs, (torch.cat(std) if std else torch.zeros(0, dtype=torch.float32, device=z.device)), info
+
+
+# ---- per-entity completion on the Monte-Carlo posterior predictive, typed or not -------------------------------------------------
+def _complete_mc_args(z, w, entities, k, side, filter_index, flow_log_probs):
+    """What the two routes of ``complete_entities_mc`` check and prepare alike: (z, w, flp, entities, k, (lo, hi, ent))."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    k = ops._topk_arg(k)
+    z, wd, flp = _mc_args(z, w, flow_log_probs)
+    ents = torch.as_tensor(entities, device=z.device).reshape(-1)
+    ops._entity_topk_mc_operands(ents, z, wd)
+    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
+    filt = _mine_filter(filter_index, z.shape[1], wd.shape[0], z.device, 'o' if side == 's' else 's')
+    return z, wd, flp, ents, k, filt
+
+
+def _complete_mc_rows(z):
+    """Returned facts per chunk of the spread's query stack: its (S, rows, h) floats stay under ``MC_MINE_STACK_BYTES``."""
+    return max(1, MC_MINE_STACK_BYTES // (z.shape[0] * z.shape[2] * 4))
+
+
+def complete_entities_mc(z, w, entities, k, *, side='s', filter_index=None, flow_log_probs=None, exclude_self=True,
+                         type_constraint=UNCONSTRAINED):
+    """``complete_entities`` on the posterior predictive of the samples ``z`` (S, N, h) of ``KGVAE.posterior_samples``
+    (``flow_log_probs``: its second result): each entity's ``k`` new facts of highest ``pbar = mean_s sigmoid(logit_s)`` over ALL
+    relations, reproducible for a fixed seed of the samples.  Sides, the filter's direction, ``exclude_self`` and the constraint
+    (left out: unconstrained; an explicit None is a TypeError) are ``complete_entities``'.  One fused launch pair
+    (ops.entity_topk_scores_mc, or ops.entity_topk_scores_typed_mc with a ``type_constraint``) loops the samples around each score
+    tile and selects once per tile.  Returns ``(rel int64 (m, k), other int64 (m, k), prob_mean float32 (m, k), prob_std float32
+    (m, k))``: pbar descending, ties -- real ones, pbar saturates -- by relation, then by entity; rows with fewer than k
+    candidates end in -1 / -1 / -inf / 0.  ``prob_std`` is the population standard deviation over the samples of each returned
+    fact's probability (ops.pair_prob_std_mc, fed as ``mine_triplets_mc`` feeds it, in chunks whose query stack stays under
+    ``MC_MINE_STACK_BYTES``)."""
+    type_constraint = _complete_constraint(type_constraint)
+    z, wd, flp, ents, k, (lo, hi, ent) = _complete_mc_args(z, w, entities, k, side, filter_index, flow_log_probs)
+    if type_constraint is not None:
+        set_ptr, set_ids = _mine_members(type_constraint, z.shape[1], wd.shape[0], z.device)
+        rel, other, mean = ops.entity_topk_scores_typed_mc(ents, z, wd, k, set_ptr, set_ids, side, flp, lo, hi, ent, exclude_self)
+    else:
+        rel, other, mean = ops.entity_topk_scores_mc(ents, z, wd, k, flp, lo, hi, ent, exclude_self)
+    # the spread: one query row (a, r) per returned fact, its one candidate the other entity; a padding slot (other -1) gives 0
+    a = ents.long().view(-1, 1).expand(-1, k).reshape(-1)
+    r, x = rel.reshape(-1).clamp(min=0), other.reshape(-1, 1)
+    rows = _complete_mc_rows(z)
+    std = [ops.pair_prob_std_mc(_mc_queries(z, wd, a[i:i + rows], r[i:i + rows]), z, x[i:i + rows], flp)[:, 0]
+           for i in range(0, a.numel(), rows)]
+    std = torch.cat(std) if std else torch.zeros(0, dtype=torch.float32, device=z.device)
+    return rel, other, mean, std.view(-1, k)
+
+
+def complete_entities_mc_from_probs(pbar, probs, entities, k, **rule):
+    """The host rule of ``complete_entities_mc_unfused`` on materialised values (any device): ``pbar`` (m, R, N) the mean
+    probabilities, ``probs`` (S, m, R, N) the per-sample ones; ``complete_entities_from_scores`` (``rule``: its filter, ``exclude_self``
+    and masks) selects on pbar, and the spread is the population standard deviation of the selected facts' per-sample
+    probabilities, 0 in the padding slots.  Returns ``(rel, other, prob_mean, prob_std)``."""
+    rel, other, mean = complete_entities_from_scores(pbar, entities, k, **rule)
+    m, num_rels, n = pbar.shape
+    gone = rel < 0
+    flat = (rel.clamp(min=0) * n + other.clamp(min=0)).unsqueeze(0).expand(probs.shape[0], -1, -1)
+    picked = probs.reshape(probs.shape[0], m, num_rels * n).gather(2, flat)
+    std = picked.std(dim=0, unbiased=False).to(torch.float32)
+    return rel, other, mean, torch.where(gone, torch.zeros_like(std), std)
+
+
+def complete_entities_mc_unfused(z, w, entities, k, *, side='s', filter_index=None, flow_log_probs=None, exclude_self=True,
+                                 type_constraint=UNCONSTRAINED):
+    """``complete_entities_mc`` from materialised probabilities: per sample and relation ``ops.mul`` + ``ops.gemm`` give the logits,
+    torch the sigmoid and the running mean, then ``complete_entities_from_scores`` on the (rows, R, N) probabilities,
+    ``COMPLETE_UNFUSED_ELEMS`` values per sample at a time; the spread comes from the selected facts' per-sample probabilities
+    (``complete_entities_mc_from_probs``).  The in-repo cross-check and the bench's comparator, never a fallback."""
+    type_constraint = _complete_constraint(type_constraint)
+    z, wd, flp, ents, k, (lo, hi, ent) = _complete_mc_args(z, w, entities, k, side, filter_index, flow_log_probs)
+    wd = wd.contiguous()
+    n_samples, n, num_rels = z.shape[0], z.shape[1], wd.shape[0]
+    masks = {}
+    if type_constraint is not None:
+        _mine_members_sizes(type_constraint, n, num_rels)
+        masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, z.device)))
+    rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels * (n_samples + 1)))
+    out = []
+    for at in range(0, ents.numel(), rows):
+        part = ents[at:at + rows].long()
+        probs, total = [], None
+        for s in range(n_samples):
+            ea = z[s][part].contiguous()
+            logit = torch.stack([ops.gemm(ops.mul(ea, wd[r].expand_as(ea).contiguous()), z[s], trans_b=True, precision='f32')
+                                 for r in range(num_rels)], dim=1)
+            p = torch.sigmoid(logit if flp is None else logit + flp[s])
+            probs.append(p)
+            total = p if total is None else total + p
+        out.append(complete_entities_mc_from_probs(total * (1.0 / n_samples), torch.stack(probs), part, k, filt_lo=lo, filt_hi=hi,
+                                                   filt_ent=ent, exclude_self=exclude_self, **masks))
+    if not out:
+        i64 = torch.zeros(0, k, dtype=torch.int64, device=z.device)
+        f32 = torch.zeros(0, k, dtype=torch.float32, device=z.device)
+        return i64, i64.clone(), f32, f32.clone()
+    return tuple(torch.cat(t) for t in zip(*out))
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

@@ -214,6 +214,29 @@ def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_pr
     return n_lines
 
 
+def write_mc_entity_profiles(path, z, w, entities, k, filter_index, flow_log_probs=None, type_constraint=None):
+    """``write_entity_profiles`` under the posterior predictive of the samples ``z`` (S, N, h) (ranking.complete_entities_mc), as
+    TSV: ``entity  side  relation  other_entity  rank  prob_mean  prob_std`` -- the first five columns are those of
+    ``write_entity_profiles`` (the two files join on them), the last two the mean and the population standard deviation over the
+    samples of the fact's probability; best mean first, the rank counted from 1.  With a ``type_constraint``
+    (ranking.TypeConstraint) only type-correct facts are written.  Returns the number of lines written."""
+    n_lines = 0
+    ents = torch.as_tensor(entities, dtype=torch.long, device=z.device).reshape(-1)
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    with torch.no_grad(), open(path, 'w') as f:
+        for side in ('s', 'o'):
+            for at in range(0, ents.numel(), PROFILE_ROWS):
+                part = ents[at:at + PROFILE_ROWS]
+                rel, other, mean, std = ranking.complete_entities_mc(z, w, part, k, side=side, filter_index=filter_index,
+                                                                     flow_log_probs=flow_log_probs, **constrained)
+                for a, rs, xs, ms, ds in zip(part.tolist(), rel.tolist(), other.tolist(), mean.tolist(), std.tolist()):
+                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{p:.9g}\t{d:.9g}\n"
+                             for i, (r, x, p, d) in enumerate(zip(rs, xs, ms, ds), 1) if r >= 0]
+                    f.writelines(lines)
+                    n_lines += len(lines)
+    return n_lines
+
+
 def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None, type_constraint=None):
     """Knowledge-graph completion as TSV, ``s  r  o  rank  logit``: the new triplets (``filter_index``: the known ones left out,
     s != o) that ``ranking.mine_triplets`` selects among ALL N x R x N -- the ``k`` most confident and / or those whose
@@ -313,6 +336,11 @@ def check_args(args):
             raise ValueError('--mc-complete needs --complete-typed: only the sweep over the type-correct triplets has a '
                              'Monte-Carlo form')
         # (--complete-typed without --complete-topk / --complete-threshold was refused above: a selection is given)
+    if getattr(args, 'mc_profile', False):
+        if not getattr(args, 'mc_samples', 0) > 0:
+            raise ValueError('--mc-profile profiles the entities on the posterior predictive: it needs --mc-samples S > 0')
+        if not getattr(args, 'profile_topk', 0) > 0:
+            raise ValueError('--mc-profile writes the posterior-predictive form of the profiles: it needs --profile-topk K > 0')
 
 
 def main(args):
@@ -441,6 +469,18 @@ def main(args):
                                                threshold=args.complete_threshold, flow_log_probs=flps)
                 print(f"wrote {n_lines} new type-correct triplets (known triplets filtered, mean and spread over "
                       f"{args.mc_samples} samples) to {args.mc_complete_out}")
+            if getattr(args, 'mc_profile', False):
+                known = filters if filters is not None else \
+                    ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+                who = profile_entities_arg(getattr(args, 'profile_entities', None), num_nodes)
+                typed = None
+                if getattr(args, 'profile_typed', False):
+                    typed = types if types is not None else \
+                        ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+                n_lines = write_mc_entity_profiles(args.mc_profile_out, z, model.w_relation, who, args.profile_topk, known, flps, typed)
+                print(f"wrote {n_lines} new {'type-correct ' if typed is not None else ''}facts around {len(who)} entities (top "
+                      f"{args.profile_topk} over all relations, as subject and as object, known triplets filtered, mean and spread "
+                      f"over {args.mc_samples} samples) to {args.mc_profile_out}")
         return mrr
 
     print("start training...")
@@ -637,6 +677,13 @@ def build_parser():
                    help="with --profile-topk: write type-correct facts only (the entity seen on its side of the relation, the other "
                         "entity seen on the other side, in train + valid + test); the same columns; --type-constrain does not "
                         "constrain profiles")
+    p.add_argument("--mc-profile", action="store_true",
+                   help="with --mc-samples and --profile-topk: also write the profiles on the posterior predictive (each entity's K "
+                        "new facts of highest mean probability over the samples, with the spread) to --mc-profile-out; honours "
+                        "--profile-entities and --profile-typed; reproducible for a fixed --mc-seed")
+    p.add_argument("--mc-profile-out", type=str, default="mc_profiles.tsv",
+                   help="TSV of --mc-profile: entity, side, relation, other entity, rank from 1 (the columns of --profile-out), then "
+                        "the mean and the standard deviation over the samples of the fact's probability")
     p.add_argument("--sample-graph", type=int, default=0,
                    help="with --test-mode: draw M node latents from the prior (KGVAE.sample_z) and write the --sample-topk most "
                         "confident triplets among them to --sample-out; 0 = off")

@@ -659,6 +659,31 @@ int gv_topk_scores_mc_constrained(const float* q, int ld_q, int64_t q_stride, co
                                   const uint32_t* cand, int ld_cand, int n_sets, const int32_t* cand_set, int k, int* out_ids,
                                   float* out_prob, void* workspace, int m, int v, int h, void* stream);
 
+/* Per-entity completion on the posterior predictive: gv_entity_topk_scores and gv_entity_topk_scores_typed with S samples of
+ * the entity table instead of one.  Sample s is the table E_s (n, h) at e + s * e_stride (elements; ld_e is shared), read for the
+ * query rows E_s[a] and for the candidate rows alike; the one w (num_rels, h) is shared by the samples; bias NULL or [n_samples],
+ * that draw's flow_log_prob.  The value selected is
+ *   pbar[i, r, x] = (sum over s = 0 .. S-1 ascending of sig(logit_s[i, r, x] + bias[s])) * (1.0f / S)
+ * with logit_s gv_entity_topk_scores' logit on table s and sig as above -- bit for bit the out_prob of gv_topk_scores_mc for the
+ * query rows E_s[a] * w[r] at entity x, for both sides -- summed in registers and selected once per (relation, tile).
+ * Order: the parents' key on pbar, i.e. pbar descending, then relation ascending, then entity ascending.  pbar saturates:
+ * candidates whose every sample rounds to 1.0f are a real tie, broken by (r, x).  A NaN in any sample gives NaN, which sorts
+ * after every number (reported as 0x7fc00000), as in gv_topk_scores_mc.  Padding is -1 / -1 / -inf.  1 <= k <= 128 and
+ * n * num_rels < 2^31 (refused otherwise); n_samples >= 1 and, with n_samples > 1, e_stride >= (n - 1) * ld_e + h (refused
+ * otherwise, before any launch).  ents, the filter, exclude_self, span_tiles, the member lists, tile_ptr, n_tiles and cand_base
+ * are the parents'; an entity outside [0, n) and a member id of -1 are dereferenced in no sample.  The workspaces are the
+ * parents': gv_entity_topk_scores_workspace_bytes / gv_entity_topk_scores_typed_workspace_bytes.  The result does not depend on
+ * span_tiles.  No atomics; no float arithmetic outside the scores. */
+int gv_entity_topk_scores_mc(const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w,
+                             int ld_w, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent, int n_filt_ent,
+                             int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_prob,
+                             void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+int gv_entity_topk_scores_typed_mc(const int32_t* ents, int m, const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w,
+                                   int ld_w, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_ent,
+                                   int n_filt_ent, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* tile_ptr, int n_tiles,
+                                   int cand_base, int exclude_self, int k, int span_tiles, int32_t* out_rel, int32_t* out_ent,
+                                   float* out_prob, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+
 /* Whole-graph triplet mining (csrc/k_mine.hip): every triplet of a DistMult decoder scored and selected globally, for the
  * entity table e (n, h) and the relation rows w (num_rels, h), both fp32 row-major:
  *   logit[s, r, o] = (e[s] * w[r]) . e[o] (+ *bias)
