@@ -766,17 +766,62 @@ def _entity_topk_operands(ents, emb, w):
 
 
 def _entity_topk_args(ents, span, tile, filt, m, n, num_rels, k, id_dtype, device):
-    """What the two per-entity wrappers do once the operands' shapes and k stand: the checks of ``span`` (``tile``: how the wrapper
+    """What the per-entity wrappers do once the operands' shapes and k stand: the checks of ``span`` (``tile``: how the wrapper
     calls a tile), of the query entities' range and of the filter over the N * R keys, then the outputs.  Returns (``_filter_args``'
-    tuple, (rel, ent, values), ents32, span_tiles) -- span_tiles 0 is the library's rule, else ``span`` held to the number of pairs."""
+    tuple, (rel, ent, values), ents32)."""
     if span is not None and int(span) < 1:
         raise ValueError(f'span counts (relation, {tile} tile) pairs per workgroup: at least 1, got {span}')
     if m and (int(ents.min()) < 0 or int(ents.max()) >= n):
         raise ValueError(f'query entities must lie in [0, {n})')
     filt32 = _filter_args(*filt, n * num_rels, n, device)
     outs = tuple(torch.empty(m, k, dtype=t, device=device) for t in (id_dtype, id_dtype, torch.float32))
-    span_tiles = 0 if span is None else min(int(span), num_rels * ((n + 63) // 64))
-    return filt32, outs, ents.to(device=device, dtype=torch.int32).contiguous(), span_tiles
+    return filt32, outs, ents.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _entity_span_tiles(span, n_tiles):
+    """The ``span_tiles`` an entry is handed: 0 is the library's rule, else ``span`` (checked: >= 1) held to the row's tiles."""
+    return 0 if span is None else max(1, min(int(span), n_tiles))
+
+
+def _entity_topk(entry, ents, table, w, k, bias, filt, exclude_self, span, typed=None, mc=False):
+    """The four ``entity_topk_scores*`` wrappers, in the style of ``_topk_scores``: the checks in their one order, the outputs, the
+    workspace and the call.  ``filt``: (filt_lo, filt_hi, filt_ent); ``typed``: (set_ptr, set_ids, side) for the sweeps over the
+    member lists, else None; ``mc``: ``table`` is the (S, N, h) sample stack and ``bias`` holds one value per sample.  Returns (rel
+    int64 (m, k), ent int64 (m, k), values float32 (m, k))."""
+    if mc:
+        s, m, n, num_rels, h = _entity_topk_mc_operands(ents, table, w)
+    else:
+        m, n, num_rels, h = _entity_topk_operands(ents, table, w)
+    k = _topk_arg(k)
+    (lo32, hi32, ent32, n_ent), (rel, ent, values), ents32 = _entity_topk_args(
+        ents, span, 'column' if typed is None else 'member', filt, m, n, num_rels, k, torch.int32, table.device)
+    if mc:
+        table, ld_e, e_stride = _mine_sample_stack(table, 'z')
+        tables = (ptr(table), ld_e, e_stride, s)
+    else:
+        table, ld_e = _row_major(table, 'emb')
+        tables = (ptr(table), ld_e)
+    w, ld_w = _row_major(w, 'w')
+    dev = table.device
+    if typed is None:
+        n_tiles, lists = num_rels * ((n + 63) // 64), ()
+        span_tiles = _entity_span_tiles(span, n_tiles)
+    else:
+        ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(*typed, span, n, num_rels, dev)
+        lists = (ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base)
+    if m == 0:
+        return rel.long(), ent.long(), values
+    bias = _mc_bias_arg(bias, s, dev) if mc else _bias_arg(bias)
+    if typed is not None:
+        ws_bytes = int(lib.load().gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles))
+    elif span_tiles:    # gv_entity_topk_scores_workspace_bytes takes no span_tiles (the ABI stays): a given span's lists are sized here
+        ws_bytes = m * ((n_tiles + span_tiles - 1) // span_tiles) * k * 8
+    else:
+        ws_bytes = int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call(entry, ptr(ents32), m, *tables, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent, *lists,
+             int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(values), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
+    return rel.long(), ent.long(), values
 
 
 def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True, span=None):
@@ -790,25 +835,7 @@ def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, f
     ``ents`` may repeat and need not be sorted.  ``span``: (relation, 64-column tile) pairs per workgroup instead of the library's
     rule -- the result does not depend on it.  Returns ``(rel int64 (m, k), ent int64 (m, k), logits float32 (m, k))``, padded
     with -1 / -1 / -inf past a row's last candidate; -0 is reported as +0 and every NaN as the one quiet NaN."""
-    m, n, num_rels, h = _entity_topk_operands(ents, emb, w)
-    k = _topk_arg(k)
-    (lo32, hi32, ent32, n_ent), (rel, ent, logits), ents32, span_tiles = _entity_topk_args(
-        ents, span, 'column', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, emb.device)
-    emb, ld_e = _row_major(emb, 'emb')
-    w, ld_w = _row_major(w, 'w')
-    dev = emb.device
-    if m == 0:
-        return rel.long(), ent.long(), logits
-    bias = _bias_arg(bias)
-    if span_tiles:      # gv_entity_topk_scores_workspace_bytes takes no span_tiles (the ABI stays): a given span's lists are sized here
-        tiles = num_rels * ((n + 63) // 64)
-        ws_bytes = m * ((tiles + span_tiles - 1) // span_tiles) * k * 8
-    else:
-        ws_bytes = int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_entity_topk_scores', ptr(ents32), m, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
-             int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(logits), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
-    return rel.long(), ent.long(), logits
+    return _entity_topk('gv_entity_topk_scores', ents, emb, w, k, bias, (filt_lo, filt_hi, filt_ent), exclude_self, span)
 
 
 def entity_typed_plan(set_ptr, num_rels, side='s'):
@@ -841,8 +868,7 @@ def _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, device):
     tile_ptr, n_tiles, cand_base = entity_typed_plan(ptr64, num_rels, side)
     if not ids32.numel():
         ids32 = torch.zeros(1, dtype=torch.int32, device=device)
-    span_tiles = 0 if span is None else max(1, min(int(span), n_tiles))
-    return ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles
+    return ptr64, ids32, tile_ptr, n_tiles, cand_base, _entity_span_tiles(span, n_tiles)
 
 
 def entity_topk_scores_typed(ents, emb, w, k, set_ptr, set_ids, side='s', bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
@@ -856,23 +882,8 @@ def entity_topk_scores_typed(ents, emb, w, k, set_ptr, set_ids, side='s', bias=N
     relations' candidate lists, 64 members a tile, rows gathered through the ids: ``sum_r ceil(|C_r| / 64)`` column tiles per
     64-entity row tile instead of ``R * ceil(N / 64)``.  An entity on the query side of no relation gets an all-padding row.
     ``span``: (relation, 64-member tile) pairs per workgroup instead of the library's rule -- the result does not depend on it."""
-    m, n, num_rels, h = _entity_topk_operands(ents, emb, w)
-    k = _topk_arg(k)
-    (lo32, hi32, ent32, n_ent), (rel, ent, logits), ents32, _ = _entity_topk_args(
-        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, emb.device)
-    emb, ld_e = _row_major(emb, 'emb')
-    w, ld_w = _row_major(w, 'w')
-    dev = emb.device
-    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, dev)
-    if m == 0:
-        return rel.long(), ent.long(), logits
-    bias = _bias_arg(bias)
-    ws_bytes = int(lib.load().gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_entity_topk_scores_typed', ptr(ents32), m, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32), ptr(ent32),
-             n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k, span_tiles, ptr(rel),
-             ptr(ent), ptr(logits), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
-    return rel.long(), ent.long(), logits
+    return _entity_topk('gv_entity_topk_scores_typed', ents, emb, w, k, bias, (filt_lo, filt_hi, filt_ent), exclude_self, span,
+                        (set_ptr, set_ids, side))
 
 
 def _mc_operands(q, entities):
@@ -958,26 +969,7 @@ def entity_topk_scores_mc(ents, z, w, k, bias=None, filt_lo=None, filt_hi=None, 
     order: pbar descending, then relation, then entity ascending -- pbar saturates, so candidates whose every sample rounds to
     1.0f are a real tie, broken by (r, x); a NaN in any sample gives NaN, after everything.  Returns ``(rel int64 (m, k), ent int64
     (m, k), prob_mean float32 (m, k))``."""
-    s, m, n, num_rels, h = _entity_topk_mc_operands(ents, z, w)
-    k = _topk_arg(k)
-    (lo32, hi32, ent32, n_ent), (rel, ent, prob), ents32, span_tiles = _entity_topk_args(
-        ents, span, 'column', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, z.device)
-    z, ld_e, e_stride = _mine_sample_stack(z, 'z')
-    w, ld_w = _row_major(w, 'w')
-    dev = z.device
-    if m == 0:
-        return rel.long(), ent.long(), prob
-    bias = _mc_bias_arg(bias, s, dev)
-    if span_tiles:      # (a given span's lists are sized here, as entity_topk_scores does)
-        tiles = num_rels * ((n + 63) // 64)
-        ws_bytes = m * ((tiles + span_tiles - 1) // span_tiles) * k * 8
-    else:
-        ws_bytes = int(lib.load().gv_entity_topk_scores_workspace_bytes(m, n, num_rels, k))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_entity_topk_scores_mc', ptr(ents32), m, ptr(z), ld_e, e_stride, s, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(ent), ptr(prob), ptr(ws), ws_bytes, n, num_rels, h,
-             lib.stream())
-    return rel.long(), ent.long(), prob
+    return _entity_topk('gv_entity_topk_scores_mc', ents, z, w, k, bias, (filt_lo, filt_hi, filt_ent), exclude_self, span, mc=True)
 
 
 def entity_topk_scores_typed_mc(ents, z, w, k, set_ptr, set_ids, side='s', bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
@@ -986,23 +978,8 @@ def entity_topk_scores_typed_mc(ents, z, w, k, set_ptr, set_ids, side='s', bias=
     ``span`` of ``entity_topk_scores_typed``, the samples, ``bias`` (S,), pbar, order, ties, NaN and padding of
     ``entity_topk_scores_mc`` -- a candidate's pbar is the untyped sweep's, bit for bit.  Returns ``(rel int64 (m, k), ent int64
     (m, k), prob_mean float32 (m, k))``."""
-    s, m, n, num_rels, h = _entity_topk_mc_operands(ents, z, w)
-    k = _topk_arg(k)
-    (lo32, hi32, ent32, n_ent), (rel, ent, prob), ents32, _ = _entity_topk_args(
-        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int32, z.device)
-    z, ld_e, e_stride = _mine_sample_stack(z, 'z')
-    w, ld_w = _row_major(w, 'w')
-    dev = z.device
-    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, side, span, n, num_rels, dev)
-    if m == 0:
-        return rel.long(), ent.long(), prob
-    bias = _mc_bias_arg(bias, s, dev)
-    ws_bytes = int(lib.load().gv_entity_topk_scores_typed_workspace_bytes(m, n_tiles, k, span_tiles))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_entity_topk_scores_typed_mc', ptr(ents32), m, ptr(z), ld_e, e_stride, s, ptr(w), ld_w, ptr(bias), ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k, span_tiles,
-             ptr(rel), ptr(ent), ptr(prob), ptr(ws), ws_bytes, n, num_rels, h, lib.stream())
-    return rel.long(), ent.long(), prob
+    return _entity_topk('gv_entity_topk_scores_typed_mc', ents, z, w, k, bias, (filt_lo, filt_hi, filt_ent), exclude_self, span,
+                        (set_ptr, set_ids, side), mc=True)
 
 
 def pair_prob_std_mc(q, entities, ids, bias=None):
@@ -3853,24 +3830,7 @@ def transe_entity_topk(ents, en, rn, k, p_norm, head=False, filt_lo=None, filt_h
     ``ents`` may repeat and need not be sorted.  ``span``: (relation, 64-entity tile) pairs per workgroup instead of the library's
     rule -- the result does not depend on it.  Returns ``(rel int64 (m, k), other int64 (m, k), dist float32 (m, k))``, padded
     with -1 / -1 / +inf past a row's last candidate; a zero distance is reported as +0 and every NaN as the one quiet NaN."""
-    m, n, num_rels, dim = _entity_topk_operands(ents, en, rn)
-    k = _topk_arg(k)
-    p_norm = _p_norm(p_norm)
-    if dim > TRANSE_MAX_DIM:
-        raise ValueError(f'en / rn: width {dim} above {TRANSE_MAX_DIM}')
-    (lo32, hi32, ent32, n_ent), (rel, other, dist), ents32, span_tiles = _entity_topk_args(
-        ents, span, 'entity', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int64, en.device)
-    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
-    dev = en.device
-    if rn.device != dev:
-        raise ValueError(f'en on {dev}, rn on {rn.device}')
-    if m == 0:
-        return rel, other, dist
-    ws_bytes = int(lib.load().gv_transe_entity_topk_workspace_bytes(m, n, num_rels, k, span_tiles))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_transe_entity_topk', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32),
-             ptr(ent32), n_ent, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
-    return rel, other, dist
+    return _transe_entity_topk('gv_transe_entity_topk', ents, en, rn, k, p_norm, head, (filt_lo, filt_hi, filt_ent), exclude_self, span)
 
 
 def transe_entity_topk_typed(ents, en, rn, k, p_norm, set_ptr, set_ids, head=False, filt_lo=None, filt_hi=None, filt_ent=None,
@@ -3882,26 +3842,38 @@ def transe_entity_topk_typed(ents, en, rn, k, p_norm, set_ptr, set_ids, head=Fal
     filter is independent of the sets.  One fused launch pair walks the relations' candidate lists, 64 members a tile.  An entity
     on the query side of no relation gets an all-padding row.  ``span``: (relation, 64-member tile) pairs per workgroup -- the
     result does not depend on it."""
+    return _transe_entity_topk('gv_transe_entity_topk_typed', ents, en, rn, k, p_norm, head, (filt_lo, filt_hi, filt_ent), exclude_self,
+                               span, (set_ptr, set_ids, 'o' if head else 's'))
+
+
+def _transe_entity_topk(entry, ents, en, rn, k, p_norm, head, filt, exclude_self, span, typed=None):
+    """The two ``transe_entity_topk*`` wrappers, with ``_entity_topk``'s ``filt`` and ``typed``: the checks in their one order, the
+    outputs, the workspace and the call.  Returns (rel int64 (m, k), other int64 (m, k), dist float32 (m, k))."""
     m, n, num_rels, dim = _entity_topk_operands(ents, en, rn)
     k = _topk_arg(k)
     p_norm = _p_norm(p_norm)
     if dim > TRANSE_MAX_DIM:
         raise ValueError(f'en / rn: width {dim} above {TRANSE_MAX_DIM}')
-    (lo32, hi32, ent32, n_ent), (rel, other, dist), ents32, _ = _entity_topk_args(
-        ents, span, 'member', (filt_lo, filt_hi, filt_ent), m, n, num_rels, k, torch.int64, en.device)
+    (lo32, hi32, ent32, n_ent), (rel, other, dist), ents32 = _entity_topk_args(
+        ents, span, 'entity' if typed is None else 'member', filt, m, n, num_rels, k, torch.int64, en.device)
     en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
     dev = en.device
     if rn.device != dev:
         raise ValueError(f'en on {dev}, rn on {rn.device}')
-    ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(set_ptr, set_ids, 'o' if head else 's', span, n,
-                                                                                     num_rels, dev)
+    if typed is None:
+        span_tiles, lists = _entity_span_tiles(span, num_rels * ((n + 63) // 64)), ()
+    else:
+        ptr64, ids32, tile_ptr, n_tiles, cand_base, span_tiles = _entity_topk_typed_args(*typed, span, n, num_rels, dev)
+        lists = (ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base)
     if m == 0:
         return rel, other, dist
-    ws_bytes = int(lib.load().gv_transe_entity_topk_typed_workspace_bytes(m, n_tiles, k, span_tiles))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    lib.call('gv_transe_entity_topk_typed', ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32),
-             ptr(hi32), ptr(ent32), n_ent, ptr(ptr64), ptr(ids32), ptr(tile_ptr), n_tiles, cand_base, int(bool(exclude_self)), k,
-             span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
+    if typed is None:
+        ws_bytes = int(lib.load().gv_transe_entity_topk_workspace_bytes(m, n, num_rels, k, span_tiles))
+    else:
+        ws_bytes = int(lib.load().gv_transe_entity_topk_typed_workspace_bytes(m, n_tiles, k, span_tiles))
+    ws =torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    lib.call(entry, ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+             *lists, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
     return rel, other, dist
 
 

@@ -984,12 +984,17 @@ def _complete_constraint(type_constraint):
     return type_constraint
 
 
+def _complete_side(side):
+    """The one refusal of a per-entity route's ``side``."""
+    if side not in ('s', 'o'):
+        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+
+
 def complete_masks(type_constraint, side, device=None):
     """``(cand_query, cand_other)``, bool (R, N) each, of a ``TypeConstraint`` for per-entity completion on ``side``: 's' (facts
     (a, r, x)) asks a among the subjects of r (set R + r) and x among its objects (set r); 'o' (facts (x, r, a)) the other way
     round -- ``mine_triplets(type_constraint=)``'s definition of type-correct, seen from one entity."""
-    if side not in ('s', 'o'):
-        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    _complete_side(side)
     num_rels = type_constraint.num_rels
     obj = type_constraint.mask(torch.arange(num_rels), device)
     subj = type_constraint.mask(torch.arange(num_rels, 2 * num_rels), device)
@@ -998,16 +1003,41 @@ def complete_masks(type_constraint, side, device=None):
 
 def _complete_args(embedding, w, entities, k, side, filter_index):
     """What the two routes of ``complete_entities`` check and prepare alike: (emb, w, entities, k, (lo, hi, ent))."""
-    if side not in ('s', 'o'):
-        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    _complete_side(side)
     k = ops._topk_arg(k)
     emb = embedding.detach()
     wd = w.detach().to(emb.device)
-    ents = torch.as_tensor(entities, device=emb.device).reshape(-1)
-    ops._entity_topk_operands(ents, emb, wd)
-    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
-    filt = _mine_filter(filter_index, emb.shape[0], wd.shape[0], emb.device, 'o' if side == 's' else 's')
+    ents, filt = _complete_queries(emb, wd, entities, side, filter_index)
     return emb, wd, ents, k, filt
+
+
+def _complete_queries(table, w, entities, side, filter_index, mc=False):
+    """The second half of every per-entity route's preparation, once side and k stand and the model's tables are at hand (``mc``:
+    ``table`` is the sample stack): the entities on the tables' device, checked with the operands' shapes, and the filter.  Returns
+    (entities, (lo, hi, ent))."""
+    ents = torch.as_tensor(entities, device=table.device).reshape(-1)
+    (ops._entity_topk_mc_operands if mc else ops._entity_topk_operands)(ents, table, w)
+    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
+    return ents, _mine_filter(filter_index, table.shape[-2], w.shape[0], table.device, 'o' if side == 's' else 's')
+
+
+def _complete_mask_args(type_constraint, side, n, num_rels, device):
+    """The typed rule of the ``*_unfused`` routes as the keywords by which ``complete_entities_from_scores`` takes it: the masks of
+    ``complete_masks``, refused when the constraint was built for other sizes than the tables'; {} without a constraint."""
+    if type_constraint is None:
+        return {}
+    _mine_members_sizes(type_constraint, n, num_rels)
+    return dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, device)))
+
+
+def _complete_unfused(chunk, ents, rows, k, n_values=1):
+    """The chunk loop of the three ``*_unfused`` routes: ``chunk(part)`` is (rel, other, values...) of ``rows`` entities at a time
+    (int64 ids), the results concatenated; without entities the empty result, int64 / int64 and ``n_values`` float32 (0, k)."""
+    out = [chunk(ents[at:at + rows].long()) for at in range(0, ents.numel(), rows)]
+    if not out:
+        i64 = torch.zeros(0, k, dtype=torch.int64, device=ents.device)
+        return (i64, i64.clone()) + tuple(torch.zeros(0, k, dtype=torch.float32, device=ents.device) for _ in range(n_values))
+    return tuple(torch.cat(t) for t in zip(*out))
 
 
 def complete_entities(embedding, w, entities, k, *, side='s', filter_index=None, flow_log_prob=None, exclude_self=True,
@@ -1042,26 +1072,18 @@ def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_ind
     emb, wd, ents, k, (lo, hi, ent) = _complete_args(embedding, w, entities, k, side, filter_index)
     emb, wd = emb.contiguous(), wd.contiguous()
     n, num_rels = emb.shape[0], wd.shape[0]
-    masks = {}
-    if type_constraint is not None:
-        _mine_members_sizes(type_constraint, n, num_rels)
-        masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, emb.device)))
+    masks = _complete_mask_args(type_constraint, side, n, num_rels, emb.device)
     bias = _mine_bias(flow_log_prob, emb.device)
-    rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
-    out = []
-    for at in range(0, ents.numel(), rows):
-        part = ents[at:at + rows].long()
+
+    def chunk(part):
         ea = emb[part].contiguous()
         score = torch.stack([ops.gemm(ops.mul(ea, wd[r].expand_as(ea).contiguous()), emb, trans_b=True, precision='f32')
                              for r in range(num_rels)], dim=1)
         if bias is not None:
             score = score + bias
-        out.append(complete_entities_from_scores(score, part, k, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self,
-                                                 **masks))
-    if not out:
-        z = torch.zeros(0, k, dtype=torch.int64, device=emb.device)
-        return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=emb.device)
-    return tuple(torch.cat(t) for t in zip(*out))
+        return complete_entities_from_scores(score, part, k, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self, **masks)
+
+    return _complete_unfused(chunk, ents, max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels)), k)
 
 
 # ---- type-correct completions on the Monte-Carlo posterior predictive ---------------------------------------------------------
@@ -1143,14 +1165,10 @@ def mine_triplets_mc_unfused(z, w, *, k=None, threshold=None, filter_index=None,
 # ---- per-entity completion on the Monte-Carlo posterior predictive, typed or not -------------------------------------------------
 def _complete_mc_args(z, w, entities, k, side, filter_index, flow_log_probs):
     """What the two routes of ``complete_entities_mc`` check and prepare alike: (z, w, flp, entities, k, (lo, hi, ent))."""
-    if side not in ('s', 'o'):
-        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    _complete_side(side)
     k = ops._topk_arg(k)
     z, wd, flp = _mc_args(z, w, flow_log_probs)
-    ents = torch.as_tensor(entities, device=z.device).reshape(-1)
-    ops._entity_topk_mc_operands(ents, z, wd)
-    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
-    filt = _mine_filter(filter_index, z.shape[1], wd.shape[0], z.device, 'o' if side == 's' else 's')
+    ents, filt = _complete_queries(z, wd, entities, side, filter_index, mc=True)
     return z, wd, flp, ents, k, filt
 
 
@@ -1212,14 +1230,9 @@ def complete_entities_mc_unfused(z, w, entities, k, *, side='s', filter_index=No
     z, wd, flp, ents, k, (lo, hi, ent) = _complete_mc_args(z, w, entities, k, side, filter_index, flow_log_probs)
     wd = wd.contiguous()
     n_samples, n, num_rels = z.shape[0], z.shape[1], wd.shape[0]
-    masks = {}
-    if type_constraint is not None:
-        _mine_members_sizes(type_constraint, n, num_rels)
-        masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, z.device)))
-    rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels * (n_samples + 1)))
-    out = []
-    for at in range(0, ents.numel(), rows):
-        part = ents[at:at + rows].long()
+    masks = _complete_mask_args(type_constraint, side, n, num_rels, z.device)
+
+    def chunk(part):
         probs, total = [], None
         for s in range(n_samples):
             ea = z[s][part].contiguous()
@@ -1228,13 +1241,10 @@ def complete_entities_mc_unfused(z, w, entities, k, *, side='s', filter_index=No
             p = torch.sigmoid(logit if flp is None else logit + flp[s])
             probs.append(p)
             total = p if total is None else total + p
-        out.append(complete_entities_mc_from_probs(total * (1.0 / n_samples), torch.stack(probs), part, k, filt_lo=lo, filt_hi=hi,
-                                                   filt_ent=ent, exclude_self=exclude_self, **masks))
-    if not out:
-        i64 = torch.zeros(0, k, dtype=torch.int64, device=z.device)
-        f32 = torch.zeros(0, k, dtype=torch.float32, device=z.device)
-        return i64, i64.clone(), f32, f32.clone()
-    return tuple(torch.cat(t) for t in zip(*out))
+        return complete_entities_mc_from_probs(total * (1.0 / n_samples), torch.stack(probs), part, k, filt_lo=lo, filt_hi=hi,
+                                               filt_ent=ent, exclude_self=exclude_self, **masks)
+
+    return _complete_unfused(chunk, ents, max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels * (n_samples + 1))), k, n_values=2)
 
 
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,

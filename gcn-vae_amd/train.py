@@ -189,6 +189,32 @@ def profile_entities_arg(spec, num_nodes):
     return ids
 
 
+def profile_lines(side, entities, rel, other, *value_columns):
+    """The lines of a per-entity TSV for one side, ``entity  side  relation  other_entity  rank  value...``: one per returned fact
+    of every entity of ``entities`` (``rel``, ``other`` and each value column are its (m, k) results, best first), the rank counted
+    from 1, the padding slots (relation < 0) left out, every value column as ``:.9g``."""
+    lines = []
+    for a, rs, xs, *vs in zip(torch.as_tensor(entities).tolist(), rel.tolist(), other.tolist(), *(v.tolist() for v in value_columns)):
+        lines += [f"{a}\t{side}\t{r}\t{x}\t{i}\t" + '\t'.join(f"{v:.9g}" for v in values) + '\n'
+                  for i, (r, x, *values) in enumerate(zip(rs, xs, *vs), 1) if r >= 0]
+    return lines
+
+
+def write_profile_lines(path, entities, route, rows=PROFILE_ROWS):
+    """The loop of the profile writers (this file's two and transe.py's): the 's' lines of every entity, then the 'o' lines,
+    ``rows`` entities per call of ``route(part, side)`` -> ``(rel, other, *value_columns)``, as ``profile_lines`` formats them.
+    Returns the number of lines written."""
+    n_lines = 0
+    with torch.no_grad(), open(path, 'w') as f:
+        for side in ('s', 'o'):
+            for at in range(0, entities.numel(), rows):
+                part = entities[at:at + rows]
+                lines = profile_lines(side, part, *route(part, side))
+                f.writelines(lines)
+                n_lines += len(lines)
+    return n_lines
+
+
 def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None, type_constraint=None):
     """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  logit  probability``: for every entity of
     ``entities`` its ``k`` most likely new facts over all relations (ranking.complete_entities; ``filter_index``: the known ones
@@ -196,22 +222,14 @@ def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_pr
     then the 'o' lines the facts (other, relation, entity).  An entity with fewer than k candidates has fewer lines.  With a
     ``type_constraint`` (ranking.TypeConstraint) only type-correct facts are written, in the same columns.  Returns the number of
     lines written."""
-    n_lines = 0
-    ents = torch.as_tensor(entities, dtype=torch.long, device=embed.device).reshape(-1)
     constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
-    with torch.no_grad(), open(path, 'w') as f:
-        for side in ('s', 'o'):
-            for at in range(0, ents.numel(), PROFILE_ROWS):
-                part = ents[at:at + PROFILE_ROWS]
-                rel, other, logits = ranking.complete_entities(embed, w, part, k, side=side, filter_index=filter_index,
-                                                               flow_log_prob=flow_log_prob, **constrained)
-                prob = torch.sigmoid(logits)
-                for a, rs, xs, ls, ps in zip(part.tolist(), rel.tolist(), other.tolist(), logits.tolist(), prob.tolist()):
-                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{l:.9g}\t{p:.9g}\n"
-                             for i, (r, x, l, p) in enumerate(zip(rs, xs, ls, ps), 1) if r >= 0]
-                    f.writelines(lines)
-                    n_lines += len(lines)
-    return n_lines
+
+    def route(part, side):
+        rel, other, logits = ranking.complete_entities(embed, w, part, k, side=side, filter_index=filter_index,
+                                                       flow_log_prob=flow_log_prob, **constrained)
+        return rel, other, logits, torch.sigmoid(logits)
+
+    return write_profile_lines(path, torch.as_tensor(entities, dtype=torch.long, device=embed.device).reshape(-1), route)
 
 
 def write_mc_entity_profiles(path, z, w, entities, k, filter_index, flow_log_probs=None, type_constraint=None):
@@ -220,21 +238,13 @@ def write_mc_entity_profiles(path, z, w, entities, k, filter_index, flow_log_pro
     ``write_entity_profiles`` (the two files join on them), the last two the mean and the population standard deviation over the
     samples of the fact's probability; best mean first, the rank counted from 1.  With a ``type_constraint``
     (ranking.TypeConstraint) only type-correct facts are written.  Returns the number of lines written."""
-    n_lines = 0
-    ents = torch.as_tensor(entities, dtype=torch.long, device=z.device).reshape(-1)
     constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
-    with torch.no_grad(), open(path, 'w') as f:
-        for side in ('s', 'o'):
-            for at in range(0, ents.numel(), PROFILE_ROWS):
-                part = ents[at:at + PROFILE_ROWS]
-                rel, other, mean, std = ranking.complete_entities_mc(z, w, part, k, side=side, filter_index=filter_index,
-                                                                     flow_log_probs=flow_log_probs, **constrained)
-                for a, rs, xs, ms, ds in zip(part.tolist(), rel.tolist(), other.tolist(), mean.tolist(), std.tolist()):
-                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{p:.9g}\t{d:.9g}\n"
-                             for i, (r, x, p, d) in enumerate(zip(rs, xs, ms, ds), 1) if r >= 0]
-                    f.writelines(lines)
-                    n_lines += len(lines)
-    return n_lines
+
+    def route(part, side):                      # (rel, other, mean, std): the value columns as they come
+        return ranking.complete_entities_mc(z, w, part, k, side=side, filter_index=filter_index, flow_log_probs=flow_log_probs,
+                                            **constrained)
+
+    return write_profile_lines(path, torch.as_tensor(entities, dtype=torch.long, device=z.device).reshape(-1), route)
 
 
 def write_completions(path, embed, w, filter_index, k=None, threshold=None, flow_log_prob=None, type_constraint=None):

@@ -79,10 +79,9 @@ import torch.nn.functional as F
 
 from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
-                      UNCONSTRAINED, _complete_constraint, _mine_members_sizes, _mine_unfused, complete_entities_from_scores,
-                      complete_masks,
-                      rank_from_scores_constrained, sort_and_rank, topk_from_scores)
-from .train import PROFILE_ROWS, profile_entities_arg
+                      UNCONSTRAINED, _complete_constraint, _complete_mask_args, _complete_queries, _complete_side, _complete_unfused,
+                      _mine_unfused, complete_entities_from_scores, rank_from_scores_constrained, sort_and_rank, topk_from_scores)
+from .train import profile_entities_arg, write_profile_lines
 
 
 # ------------------------------------------------------------------------------------------------
@@ -781,15 +780,11 @@ def complete_entities_from_distances(dist, entities, k, *, filt_lo=None, filt_hi
 def _complete_args(model_or_tables, entities, k, side, filter_index):
     """What the two routes of ``complete_entities`` check and prepare alike: (ent, rel, p_norm, norm_flag, entities, k, (lo, hi,
     ent))."""
-    if side not in ('s', 'o'):
-        raise ValueError("side is 's' (the entity as subject: new facts (a, r, x)) or 'o' (as object: new facts (x, r, a))")
+    _complete_side(side)
     k = ops._topk_arg(k)
     ent, rel, p_norm, norm_flag = _tables(model_or_tables)
     rel = rel.to(ent.device)
-    ents = torch.as_tensor(entities, device=ent.device).reshape(-1)
-    ops._entity_topk_operands(ents, ent, rel)
-    # the entity as subject asks for objects: the filter of the object queries (a, r, ?), and the other way round
-    filt = _mine_filter(filter_index, ent.shape[0], rel.shape[0], ent.device, 'o' if side == 's' else 's')
+    ents, filt = _complete_queries(ent, rel, entities, side, filter_index)
     return ent.contiguous(), rel.contiguous(), ops._p_norm(p_norm), norm_flag, ents, k, filt
 
 
@@ -828,24 +823,17 @@ def complete_entities_unfused(model_or_tables, entities, k, *, side='s', filter_
     with torch.no_grad():
         ent, rel, p_norm, norm_flag, ents, k, (lo, hi, f_ent) = _complete_args(model_or_tables, entities, k, side, filter_index)
         n, num_rels = ent.shape[0], rel.shape[0]
-        masks = {}
-        if type_constraint is not None:
-            _mine_members_sizes(type_constraint, n, num_rels)
-            masks = dict(zip(('cand_query', 'cand_other'), complete_masks(type_constraint, side, ent.device)))
+        masks = _complete_mask_args(type_constraint, side, n, num_rels, ent.device)
         en = ops.transe_queries(ent, norm_flag=norm_flag)
-        rows = max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels))
-        out = []
-        for at in range(0, ents.numel(), rows):
-            part = ents[at:at + rows].long()
+
+        def chunk(part):
             dist = torch.stack([ops.transe_distances(ops.transe_queries(ent, rel, part, torch.full_like(part, r), head=side == 'o',
                                                                         norm_flag=norm_flag), en, p_norm)
                                 for r in range(num_rels)], dim=1)
-            out.append(complete_entities_from_distances(dist, part, k, filt_lo=lo, filt_hi=hi, filt_ent=f_ent,
-                                                        exclude_self=exclude_self, **masks))
-        if not out:
-            z = torch.zeros(0, k, dtype=torch.int64, device=ent.device)
-            return z, z.clone(), torch.zeros(0, k, dtype=torch.float32, device=ent.device)
-        return tuple(torch.cat(t) for t in zip(*out))
+            return complete_entities_from_distances(dist, part, k, filt_lo=lo, filt_hi=hi, filt_ent=f_ent, exclude_self=exclude_self,
+                                                    **masks)
+
+        return _complete_unfused(chunk, ents, max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels)), k)
 
 
 def write_entity_profiles(path, model_or_tables, entities, k, filter_index, type_constraint=None):
@@ -855,19 +843,10 @@ def write_entity_profiles(path, model_or_tables, entities, k, filter_index, type
     facts (other, relation, entity).  The first five columns are those of train.py's ``profiles.tsv``: the two files join on them.
     An entity with fewer than k candidates has fewer lines.  With a ``type_constraint`` (ranking.TypeConstraint) only type-correct
     facts are written, in the same columns.  Returns the number of lines written."""
-    n_lines = 0
-    ents = torch.as_tensor(entities, dtype=torch.long).reshape(-1)
     constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
-    with open(path, 'w') as f:
-        for side in ('s', 'o'):
-            for at in range(0, ents.numel(), PROFILE_ROWS):
-                part = ents[at:at + PROFILE_ROWS]
-                rel, other, dist = complete_entities(model_or_tables, part, k, side=side, filter_index=filter_index, **constrained)
-                for a, rs, xs, ds in zip(part.tolist(), rel.tolist(), other.tolist(), dist.tolist()):
-                    lines = [f"{a}\t{side}\t{r}\t{x}\t{i}\t{d:.9g}\n" for i, (r, x, d) in enumerate(zip(rs, xs, ds), 1) if r >= 0]
-                    f.writelines(lines)
-                    n_lines += len(lines)
-    return n_lines
+    return write_profile_lines(path, torch.as_tensor(entities, dtype=torch.long).reshape(-1),
+                               lambda part, side: complete_entities(model_or_tables, part, k, side=side, filter_index=filter_index,
+                                                                    **constrained))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -8,15 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+from entity_typed_cases import entities as _entities, same as _same
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(150, 3, 20), (70, 7, 37), (200, 1, 200), (130, 5, 260)]      # (N, R, h): N % 64 != 0; h % 4 != 0, h % 16 != 0; h of 17 k-chunks
 FLP = 0.37
-
-
-def _same(a, b):
-    """Bit-for-bit equality of (rel, other, logits) triples."""
-    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
 
 
 @functools.lru_cache(maxsize=None)
@@ -29,14 +26,6 @@ def _tables(n, num_rels, h):
                         torch.randint(0, n, (n * num_rels // 2,), generator=gen)], 1)
     perm = torch.randperm(n, generator=gen)
     return emb, w, trip, perm
-
-
-def _entities(perm, m):
-    """m query entities: out of order, and with a repeat as soon as there are three."""
-    ents = perm[:m].clone()
-    if m >= 3:
-        ents[m // 2] = ents[0]
-    return ents.cuda()
 
 
 @pytest.mark.parametrize('flp', [None, FLP])

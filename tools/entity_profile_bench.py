@@ -14,33 +14,16 @@ The filter is the synthetic dataset's train + valid + test triplets.  Writes --o
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gcn_vae_amd import data, ranking   # noqa: E402
+from entity_bench_common import SHAPES as WIDTH_200, merge_all_queries, same, time_routes   # noqa: E402
 
-SHAPES = {'fb': ('FB15k-237-synthetic', 200), 'wn18rr': ('WN18RR-synthetic', 200), 'fb-h500': ('FB15k-237-synthetic', 500)}
-
-
-def same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a[:2], b[:2])) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
-
-
-def merge_over_relations(ids, logits, m, num_rels, n, k):
-    """(m * R, k) answers of the queries (a, r), a-major, into each entity's k best (r, x): by logit, then relation, then entity."""
-    cid = torch.arange(num_rels, device=ids.device).view(1, num_rels, 1) * n + ids.view(m, num_rels, k)
-    cid = torch.where(ids.view(m, num_rels, k) < 0, torch.full_like(cid, num_rels * n), cid).view(m, num_rels * k)
-    by_id = torch.argsort(cid, dim=1, stable=True)
-    lg = logits.view(m, num_rels * k).gather(1, by_id)
-    order = by_id.gather(1, torch.argsort(lg, dim=1, descending=True, stable=True)[:, :k])
-    best, lg = cid.gather(1, order), logits.view(m, num_rels * k).gather(1, order)
-    gone = best >= num_rels * n
-    return torch.where(gone, -1, best // n), torch.where(gone, -1, best % n), lg
+SHAPES = {**WIDTH_200, 'fb-h500': ('FB15k-237-synthetic', 500)}
 
 
 def bench_shape(shape, ks, reps, chunk, unfused_entities, trace_leg):
@@ -69,7 +52,7 @@ def bench_shape(shape, ks, reps, chunk, unfused_entities, trace_leg):
                     part = ents[at:at + chunk]
                     ids, logits = ranking.predict_topk(emb, w, part.repeat_interleave(num_rels), rels.repeat(part.numel()), k,
                                                        direction='o', filter_index=fi, flow_log_prob=kw['flow_log_prob'])
-                    out.append(merge_over_relations(ids, logits, part.numel(), num_rels, n, k))
+                    out.append(merge_all_queries(ids, logits, part.numel(), n, num_rels, k, False))
                 return tuple(torch.cat(t) for t in zip(*out))
 
             def unfused():
@@ -81,18 +64,7 @@ def bench_shape(shape, ks, reps, chunk, unfused_entities, trace_leg):
                         fused()
                     torch.cuda.synchronize()
                 continue
-            routes = [('fused', fused), ('per_query', per_query), ('unfused', unfused)]
-            outs = {nm: fn() for nm, fn in routes}                     # warm-up of every route
-            torch.cuda.synchronize()
-            times = {nm: [] for nm, _ in routes}
-            for _ in range(reps):                                       # alternated
-                for nm, fn in routes:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    fn()
-                    torch.cuda.synchronize()
-                    times[nm].append(time.perf_counter() - t0)
-            med = {nm: statistics.median(v) * 1e3 for nm, v in times.items()}
+            outs, med = time_routes([('fused', fused), ('per_query', per_query), ('unfused', unfused)], reps)
             case = dict(query=query, entities=m, k=k, fused_ms=med['fused'], per_query_ms=med['per_query'],
                         per_query_over_fused=med['per_query'] / med['fused'], unfused_entities=sample.numel(),
                         unfused_ms_measured=med['unfused'], unfused_ms_scaled=med['unfused'] * m / sample.numel(),

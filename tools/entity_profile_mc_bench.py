@@ -21,7 +21,6 @@ all-entities set: they are written as "not measured".  Writes profiles/entity_pr
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -29,25 +28,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gcn_vae_amd import data, ops, ranking   # noqa: E402
-from entity_profile_typed_bench import SHAPES, merge_member_queries   # noqa: E402
+from entity_bench_common import SHAPES, merge_member_queries, same, time_routes   # noqa: E402
 
 NOT_MEASURED = 'not measured'
-
-
-def time_routes(routes, reps):
-    outs = {nm: fn() for nm, fn in routes}                                   # warm-up of every route
-    torch.cuda.synchronize()
-    times = {nm: [] for nm, _ in routes}
-    for _ in range(reps):                                                    # alternated
-        for nm, fn in routes:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            times[nm].append(time.perf_counter() - t0)
-    return outs, {nm: statistics.median(v) * 1e3 for nm, v in times.items()}
 
 
 def bench_shape(shape, samples, ks, reps, chunk, unfused_entities, max_seconds, queries):
@@ -120,8 +104,7 @@ def bench_shape(shape, samples, ks, reps, chunk, unfused_entities, max_seconds, 
                                 single_sample_per_call_ms=med['single'] / s, fused_mean_per_sample_ms=med['fused_mean'] / s,
                                 single_over_fused_mean=med['single'] / med['fused_mean'])
                     if 'per_query' in med:
-                        equal = all(torch.equal(x, y) for x, y in zip(outs['fused'][:2], outs['per_query'][:2])) and \
-                            torch.equal(outs['fused'][2].view(torch.int32), outs['per_query'][2].view(torch.int32))
+                        equal = same(outs['fused'], outs['per_query'])
                         case.update(per_query_ms=med['per_query'], per_query_over_fused=med['per_query'] / med['fused'],
                                     equal_per_query=equal, unfused_entities=sample.numel(), unfused_ms_measured=med['unfused'],
                                     unfused_ms_scaled=med['unfused'] * scale, unfused_over_fused=med['unfused'] * scale / med['fused'])

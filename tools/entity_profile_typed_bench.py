@@ -18,63 +18,16 @@ profiles/entity_profile_typed/bench.json (DistMult) and profiles/transe_profile_
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gcn_vae_amd import data, ops, ranking, transe   # noqa: E402
+from entity_bench_common import SHAPES, merge_member_queries, same, time_routes   # noqa: E402
 
-SHAPES = {'fb': ('FB15k-237-synthetic', 200), 'wn18rr': ('WN18RR-synthetic', 200)}
 OUT = {'distmult': os.path.join('entity_profile_typed', 'bench.json'), 'transe': os.path.join('transe_profile_typed', 'bench.json')}
-
-
-def same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a[:2], b[:2])) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
-
-
-def merge_member_queries(rows, rels, ids, values, m, n, num_rels, k, ascending):
-    """The (Q, k) answers of the member queries (rows[q], rels[q]) -- row-major, relations ascending inside a row -- into each
-    entity's k best (r, x): by value, then relation, then entity.  Padded to the largest number of relations an entity has."""
-    dev = ids.device
-    count = torch.bincount(rows, minlength=m)
-    width = int(count.max()) if rows.numel() else 0
-    gone_id = num_rels * n
-    worst = float('inf') if ascending else float('-inf')
-    cid = torch.full((m, max(width, 1), k), gone_id, dtype=torch.long, device=dev)
-    val = torch.full((m, max(width, 1), k), worst, dtype=torch.float32, device=dev)
-    if rows.numel():
-        slot = torch.arange(rows.numel(), device=dev) - (torch.cumsum(count, 0) - count)[rows]
-        cid[rows, slot] = torch.where(ids < 0, torch.full_like(ids, gone_id), rels.view(-1, 1) * n + ids)
-        val[rows, slot] = values
-    cid, val = cid.view(m, -1), val.view(m, -1)
-    by_id = torch.argsort(cid, dim=1, stable=True)
-    order = by_id.gather(1, torch.argsort(val.gather(1, by_id), dim=1, descending=not ascending, stable=True)[:, :k])
-    if order.shape[1] < k:                                                   # fewer than k slots in all: pad
-        pad = torch.zeros(m, k - order.shape[1], dtype=torch.long, device=dev)
-        best = torch.cat([cid.gather(1, order), pad + gone_id], 1)
-        out = torch.cat([val.gather(1, order), pad.float() + worst], 1)
-    else:
-        best, out = cid.gather(1, order), val.gather(1, order)
-    gone = best >= gone_id
-    return torch.where(gone, -1, best // n), torch.where(gone, -1, best % n), torch.where(gone, torch.full_like(out, worst), out)
-
-
-def time_routes(routes, reps):
-    outs = {nm: fn() for nm, fn in routes}                                   # warm-up of every route
-    torch.cuda.synchronize()
-    times = {nm: [] for nm, _ in routes}
-    for _ in range(reps):                                                    # alternated
-        for nm, fn in routes:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            times[nm].append(time.perf_counter() - t0)
-    return outs, {nm: statistics.median(v) * 1e3 for nm, v in times.items()}
 
 
 def bench_shape(model, shape, ks, reps, chunk, unfused_entities):

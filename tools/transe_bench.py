@@ -221,19 +221,6 @@ def case_mine(steps, warmup, repeats=3):
 PROFILE_SHAPES = {'fb': ('FB15k-237-synthetic', 200), 'wn18rr': ('WN18RR-synthetic', 200), 'fb-dim500': ('FB15k-237-synthetic', 500)}
 
 
-def _merge_over_relations(ids, dist, m, num_rels, n, k):
-    """(m * R, k) answers of the queries (a, r), a-major, into each entity's k nearest (r, x): by distance, then relation, then
-    entity (the tables here give no NaN; padding is +inf with the id past every candidate's)."""
-    cid = torch.arange(num_rels, device=ids.device).view(1, num_rels, 1) * n + ids.view(m, num_rels, k)
-    cid = torch.where(ids.view(m, num_rels, k) < 0, torch.full_like(cid, num_rels * n), cid).view(m, num_rels * k)
-    by_id = torch.argsort(cid, dim=1, stable=True)
-    d = dist.view(m, num_rels * k).gather(1, by_id)
-    order = by_id.gather(1, torch.argsort(d, dim=1, stable=True)[:, :k])
-    best, d = cid.gather(1, order), dist.view(m, num_rels * k).gather(1, order)
-    gone = best >= num_rels * n
-    return torch.where(gone, -1, best // n), torch.where(gone, -1, best % n), d
-
-
 def case_profile(steps, warmup, repeats=3, shapes='fb,wn18rr', chunk=2048, unfused_entities=256):
     """The per-entity completion leg: transe.complete_entities (fused) against (a) transe.predict_topk over all m * R queries of the
     entities, ``chunk`` entities at a time, + a torch merge over each entity's R x k answers, and (b) transe.complete_entities_unfused
@@ -241,12 +228,11 @@ def case_profile(steps, warmup, repeats=3, shapes='fb,wn18rr', chunk=2048, unfus
     from gcn_vae_amd import transe
     from gcn_vae_amd.data import load_data
     from gcn_vae_amd.ranking import FilterIndex
+    from entity_bench_common import merge_all_queries, same
 
     def say(*a):
         print(*a, file=sys.stderr, flush=True)
 
-    def same(a, b):
-        return all(torch.equal(x, y) for x, y in zip(a[:2], b[:2])) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
     res = dict(unit='ms; each route warmed up once, then the median of synchronised timed runs, all in one process', repeats=repeats,
                side='s', exclude_self=False, shapes={})
     for shape in shapes.split(','):
@@ -276,7 +262,7 @@ def case_profile(steps, warmup, repeats=3, shapes='fb,wn18rr', chunk=2048, unfus
                             part = ents[at:at + chunk]
                             ids, dist = transe.predict_topk(tables, part.repeat_interleave(num_rels), rels.repeat(part.numel()), k,
                                                             direction='o', filter_index=fi)
-                            out.append(_merge_over_relations(ids, dist, part.numel(), num_rels, n, k))
+                            out.append(merge_all_queries(ids, dist, part.numel(), n, num_rels, k, True))
                         return tuple(torch.cat(t) for t in zip(*out))
 
                     def unfused():
