@@ -54,55 +54,99 @@ import torch
 from . import ops
 
 
+def mid_ranks(value, target, listed_mask=None, cand_mask=None):
+    """The rank rule, once, on a materialised (m, v) matrix of values, higher is better (logits, probabilities, -distances), in
+    plain torch: a candidate is better when ``~(value <= tgt)`` -- a NaN candidate or a NaN target never ranks the target well --,
+    ties count half and the target itself is left out of every pool, member or not.  The pools: all entities; those not in
+    ``listed_mask``; the members of ``cand_mask``; the members not listed (both masks dense (m, v) bools on ``value``'s device).
+    Returns (raw, filtered, raw_constrained, filtered_constrained), 0-based float mid-ranks, None where a pool's mask is missing."""
+    tgt = value.gather(1, target.view(-1, 1))
+    other = torch.ones_like(value, dtype=torch.bool).scatter_(1, target.view(-1, 1), False)
+    better, equal = (~(value <= tgt)) & other, (value == tgt) & other
+
+    def rank(pool=None):
+        b, e = (better, equal) if pool is None else (better & pool, equal & pool)
+        return b.sum(dim=1).float() + 0.5 * e.sum(dim=1).float()
+    keep = None if listed_mask is None else ~listed_mask
+    return (rank(), None if keep is None else rank(keep), None if cand_mask is None else rank(cand_mask),
+            None if keep is None or cand_mask is None else rank(cand_mask & keep))
+
+
 def sort_and_rank(score, target):
     """0-based mid-rank of ``target`` in every row of a materialised (logit) score matrix; NaN never ranks well."""
-    tgt = score.gather(1, target.view(-1, 1))
-    other = torch.ones_like(score, dtype=torch.bool).scatter_(1, target.view(-1, 1), False)
-    better = (~(score <= tgt)) & other
-    equal = (score == tgt) & other
-    return better.sum(dim=1).float() + 0.5 * equal.sum(dim=1).float()
+    return mid_ranks(score, target)[0]
 
 
 MAX_QUERY_ROWS = 16384      # queries per gv_rank_scores launch (bounds the (rows, h) query matrix, nothing else)
+
+
+def _n_ranked(test_size, batch_size, all_batches):
+    """How many queries a protocol ranks: all of them, or with ``all_batches=False`` the first batch only."""
+    return min(test_size, batch_size) if all_batches is False else test_size
+
+
+def _rank_chunks(n, step, a, r, b, filter_index, direction, device, n_kinds, rank_chunk, progress=None):
+    """The chunk loop of every rank driver, once: the first ``n`` queries (a, r) with targets ``b`` go ``step`` at a time through
+    ``rank_chunk(a, r, b, f_lo, f_hi, ent)`` -- the chunk's slices and its filter ranges into ``ent``, all three None without a
+    ``filter_index`` --, which returns the chunk's ``n_kinds`` ranks in ``CONSTRAINED_KINDS``' order.  Returns one tensor per kind
+    (empty float32 on ``device`` when there is nothing to rank); a filtered kind is None when the protocol has no filter.
+    ``progress(hi, chunks)``, when given, is called after every chunk with the per-kind lists so far."""
+    ent = filter_index.entities(direction, device) if filter_index is not None else None
+    chunks = [[] for _ in range(n_kinds)]
+    for lo in range(0, n, step):
+        sl = slice(lo, min(n, lo + step))
+        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+        for acc, x in zip(chunks, rank_chunk(a[sl], r[sl], b[sl], f_lo, f_hi, ent)):
+            acc.append(x)
+        if progress is not None:
+            progress(sl.stop, chunks)
+    out = []
+    for kind, x in enumerate(chunks):
+        if filter_index is None and kind % 2:                 # a filtered kind of a protocol without a filter
+            out.append(None)
+        else:
+            out.append(torch.cat(x) if x else torch.zeros(0, dtype=torch.float32, device=device))
+    return tuple(out)
+
+
+def _print_progress(head, label, ranks):
+    x = 1.0 + torch.cat(ranks).float()
+    print("{}: MR{} : {:.6f} |  MRR{} : {:.6f}".format(head, label, x.mean().item(), label, (1.0 / x).mean().item()))
+
+
+def _queries(emb, w, a, r):
+    """q = e_a * w_r of a chunk of queries."""
+    return ops.mul(emb[a].contiguous(), w[r].contiguous())
 
 
 def perturb_and_get_rank(embedding, w, a, r, b, test_size, batch_size=100, all_batches=True, flow_log_prob=None,
                          verbose=False):
     """Ranks of ``b`` for the queries (a, r).  ``batch_size`` only matters with ``all_batches=False`` (the reference's
     quick validation scores the first batch only, kgvae/utils.py:183-186): the fused scorer has no (h, Eb, V) tensor to bound."""
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    emb = embedding.detach().contiguous()
-    wd = w.detach()
-    ranks = []
-    for lo in range(0, n, MAX_QUERY_ROWS):
-        hi = min(n, lo + MAX_QUERY_ROWS)
-        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
-        ranks.append(ops.rank_scores(q, emb, b[lo:hi], flow_log_prob))
-        if verbose:
-            rr = 1.0 + torch.cat(ranks).float()
-            print("rows {} / {}: MR : {:.6f} |  MRR : {:.6f}".format(hi, n, rr.mean().item(), (1.0 / rr).mean().item()))
-    return torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.float32, device=emb.device)
+    n = _n_ranked(test_size, batch_size, all_batches)
+    emb, wd = embedding.detach().contiguous(), w.detach()
+
+    def rank_chunk(a, r, b, f_lo, f_hi, ent):
+        return (ops.rank_scores(_queries(emb, wd, a, r), emb, b, flow_log_prob),)
+    progress = (lambda hi, chunks: _print_progress("rows {} / {}".format(hi, n), "", chunks[0])) if verbose else None
+    return _rank_chunks(n, MAX_QUERY_ROWS, a, r, b, None, None, emb.device, 1, rank_chunk, progress)[0]
 
 
 def perturb_and_get_rank_unfused(embedding, w, a, r, b, test_size, batch_size=100, all_batches=True, flow_log_prob=None,
                                  verbose=False):
-    n_batch = (test_size + batch_size - 1) // batch_size
-    if all_batches is False:
-        n_batch = 1
-    ranks = []
-    emb = embedding.detach().contiguous()
-    for idx in range(n_batch):
-        lo, hi = idx * batch_size, min(test_size, (idx + 1) * batch_size)
-        emb_ar = ops.mul(emb[a[lo:hi]].contiguous(), w.detach()[r[lo:hi]].contiguous())
-        score = ops.gemm(emb_ar, emb, trans_b=True)                       # (Eb, V)
+    n = _n_ranked(test_size, batch_size, all_batches)
+    emb, wd = embedding.detach().contiguous(), w.detach()
+
+    def rank_chunk(a, r, b, f_lo, f_hi, ent):
+        score = ops.gemm(_queries(emb, wd, a, r), emb, trans_b=True)                  # (Eb, V)
         if flow_log_prob is not None:
             score = score + flow_log_prob
-        ranks.append(sort_and_rank(score, b[lo:hi]))              # on the logits (see the module docstring)
-        if verbose:
-            rr = 1.0 + torch.cat(ranks).float()
-            print("batch {} / {}: MR : {:.6f} |  MRR : {:.6f}".format(idx, n_batch, rr.mean().item(),
-                                                                      (1.0 / rr).mean().item()))
-    return torch.cat(ranks)
+        return (sort_and_rank(score, b),)                         # on the logits (see the module docstring)
+    n_batch = (n + batch_size - 1) // batch_size
+    progress = None
+    if verbose:
+        progress = lambda hi, chunks: _print_progress("batch {} / {}".format((hi - 1) // batch_size, n_batch), "", chunks[0])
+    return _rank_chunks(n, batch_size, a, r, b, None, None, emb.device, 1, rank_chunk, progress)[0]
 
 
 class FilterIndex:
@@ -213,17 +257,7 @@ def rank_from_scores_constrained(score, target, cand_mask, listed_mask=None):
     every one whether or not it is a member: all entities; those not in ``listed_mask``; the members of ``cand_mask``; the
     members not listed.  Both masks are dense (m, v) bools.  Returns (raw, filtered, raw_constrained, filtered_constrained),
     0-based float mid-ranks; the two filtered ones are None without ``listed_mask``."""
-    tgt = score.gather(1, target.view(-1, 1))
-    other = torch.ones_like(score, dtype=torch.bool).scatter_(1, target.view(-1, 1), False)
-    better, equal = (~(score <= tgt)) & other, (score == tgt) & other
-
-    def rank(pool):
-        return (better & pool).sum(dim=1).float() + 0.5 * (equal & pool).sum(dim=1).float()
-    cand_mask = cand_mask.to(score.device)
-    if listed_mask is None:
-        return rank(other), None, rank(cand_mask), None
-    keep = ~listed_mask.to(score.device)
-    return rank(other), rank(keep), rank(cand_mask), rank(cand_mask & keep)
+    return mid_ranks(score, target, None if listed_mask is None else listed_mask.to(score.device), cand_mask.to(score.device))
 
 
 def perturb_and_get_rank_constrained(embedding, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
@@ -231,28 +265,55 @@ def perturb_and_get_rank_constrained(embedding, w, a, r, b, test_size, filter_in
     """(raw, filtered, raw_constrained, filtered_constrained) ranks of ``b`` for the queries (a, r):
     ``perturb_and_get_rank_filtered`` plus the ranks among the ``direction`` type set of each query's relation only.
     ``filter_index`` may be None: the two filtered ranks are then None."""
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    emb = embedding.detach().contiguous()
-    wd = w.detach()
-    ent = filter_index.entities(direction, emb.device) if filter_index is not None else None
+    n = _n_ranked(test_size, batch_size, all_batches)
+    emb, wd = embedding.detach().contiguous(), w.detach()
     words = type_constraint.words.to(emb.device)
-    out = [[], [], [], []]
-    for lo in range(0, n, MAX_QUERY_ROWS):
-        hi = min(n, lo + MAX_QUERY_ROWS)
-        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
-        f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction) if filter_index is not None else (None, None)
-        ranks = ops.rank_scores_constrained(q, emb, b[lo:hi], words, type_constraint.set_ids(r[lo:hi], direction), f_lo, f_hi, ent,
-                                            flow_log_prob)
-        for acc, x in zip(out, ranks):
-            acc.append(x)
-    if not out[0]:
-        out = [[torch.zeros(0, dtype=torch.float32, device=emb.device)] for _ in out]
-        if filter_index is None:
-            out[1] = out[3] = [None]
-    return tuple(None if x[0] is None else torch.cat(x) for x in out)
+
+    def rank_chunk(a, r, b, f_lo, f_hi, ent):
+        return ops.rank_scores_constrained(_queries(emb, wd, a, r), emb, b, words, type_constraint.set_ids(r, direction), f_lo, f_hi,
+                                           ent, flow_log_prob)
+    return _rank_chunks(n, MAX_QUERY_ROWS, a, r, b, filter_index, direction, emb.device, 4, rank_chunk)
 
 
 CONSTRAINED_KINDS = ('raw', 'filtered', 'raw_constrained', 'filtered_constrained')
+MRR_LINES = ("MRR ({0}): {1:.6f}", "Hits ({0}) @ {1}: {2:.6f}")
+MC_MRR_LINES = ("MC MRR ({0}, {n_samples} samples): {1:.6f}", "MC Hits ({0}) @ {1}: {2:.6f}")
+
+
+def _on_device(embedding, w, flow_log_prob):
+    """The reference validates with the model "on the CPU" (kgvae/link_predict.py:239-251): whatever side the caller's tensors
+    are on, the scorer runs where the embedding is."""
+    if isinstance(flow_log_prob, torch.Tensor):
+        flow_log_prob = flow_log_prob.to(embedding.device)
+    return w.to(embedding.device), flow_log_prob
+
+
+def _both_directions(table, test_triplets, eval_bz, all_batches, rank):
+    """The two query sets of a test split, on ``table``'s device: ``rank(a, r, b, n, direction)`` for the subjects given
+    (o, r), then for the objects given (s, r); ``n`` is already cut to the first batch with ``all_batches=False``."""
+    test_triplets = test_triplets.to(table.device)
+    s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
+    n = _n_ranked(test_triplets.shape[0], eval_bz, all_batches)
+    return rank(o, r, s, n, 's'), rank(s, r, o, n, 'o')
+
+
+def _report(by_s, by_o, kinds, hits, verbose, lines, lead={}):
+    """MRR and Hits@k of every kind over both directions: ``by_s`` / ``by_o`` hold the 0-based ranks of the first ``len(by_s)``
+    of ``kinds``, one tensor each (None: not reported).  Returns ``lead``'s entries, then ``mrr_<kind>`` and
+    ``hits_<kind>: {k: v}``; ``verbose`` prints them with the two format strings ``lines``."""
+    out = dict(lead)
+    for kind, rs, ro in zip(kinds, by_s, by_o):
+        if rs is None:                                    # no filter_index: the filtered kinds are not reported
+            continue
+        ranks = torch.cat([rs, ro]) + 1
+        out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
+        out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
+    if verbose:
+        for kind in (k for k in kinds if 'mrr_' + k in out):
+            print(lines[0].format(kind, out['mrr_' + kind], **lead))
+            for hit in hits:
+                print(lines[1].format(kind, hit, out['hits_' + kind][hit]))
+    return out
 
 
 def calc_constrained_mrr(embedding, w, test_triplets, filter_index, type_constraint, hits=[1, 3, 10], eval_bz=100,
@@ -260,55 +321,24 @@ def calc_constrained_mrr(embedding, w, test_triplets, filter_index, type_constra
     """The four-way report of the type-constrained protocol over both directions: ``mrr_<kind>`` and ``hits_<kind>: {k: v}`` for
     raw, filtered, raw_constrained and filtered_constrained.  The first two equal ``calc_filtered_mrr``'s values."""
     with torch.no_grad():
-        test_triplets = test_triplets.to(embedding.device)
-        w = w.to(embedding.device)
-        if isinstance(flow_log_prob, torch.Tensor):
-            flow_log_prob = flow_log_prob.to(embedding.device)
-        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
-        n = test_triplets.shape[0]
-        by_s = perturb_and_get_rank_constrained(embedding, w, o, r, s, n, filter_index, type_constraint, 's', eval_bz, all_batches,
-                                                flow_log_prob)
-        by_o = perturb_and_get_rank_constrained(embedding, w, s, r, o, n, filter_index, type_constraint, 'o', eval_bz, all_batches,
-                                                flow_log_prob)
-        out = {}
-        for kind, rs, ro in zip(CONSTRAINED_KINDS, by_s, by_o):
-            if rs is None:                                    # no filter_index: the two filtered kinds are not reported
-                continue
-            ranks = torch.cat([rs, ro]) + 1
-            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
-            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
-        if verbose:
-            for kind in (k for k in CONSTRAINED_KINDS if 'mrr_' + k in out):
-                print("MRR ({}): {:.6f}".format(kind, out['mrr_' + kind]))
-                for hit in hits:
-                    print("Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
-    return out
+        w, flow_log_prob = _on_device(embedding, w, flow_log_prob)
+        by_s, by_o = _both_directions(embedding, test_triplets, eval_bz, all_batches, lambda a, r, b, n, d:
+                                      perturb_and_get_rank_constrained(embedding, w, a, r, b, n, filter_index, type_constraint, d,
+                                                                       eval_bz, all_batches, flow_log_prob))
+        return _report(by_s, by_o, CONSTRAINED_KINDS, hits, verbose, MRR_LINES)
 
 
 def perturb_and_get_rank_filtered(embedding, w, a, r, b, test_size, filter_index, direction, batch_size=100, all_batches=True,
                                   flow_log_prob=None, verbose=False):
     """(raw, filtered) ranks of ``b`` for the queries (a, r): ``perturb_and_get_rank`` with the known answers of each query left
     out of the filtered count.  ``direction`` 'o' when ``b`` are objects (queries (s, r, ?)), 's' when they are subjects."""
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    emb = embedding.detach().contiguous()
-    wd = w.detach()
-    ent = filter_index.entities(direction, emb.device)
-    raw, filt = [], []
-    for lo in range(0, n, MAX_QUERY_ROWS):
-        hi = min(n, lo + MAX_QUERY_ROWS)
-        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
-        f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction)
-        rr, rf = ops.rank_scores_filtered(q, emb, b[lo:hi], f_lo, f_hi, ent, flow_log_prob)
-        raw.append(rr)
-        filt.append(rf)
-        if verbose:
-            x = 1.0 + torch.cat(filt).float()
-            print("rows {} / {}: MR (filtered) : {:.6f} |  MRR (filtered) : {:.6f}".format(hi, n, x.mean().item(),
-                                                                                          (1.0 / x).mean().item()))
-    if not raw:
-        empty = torch.zeros(0, dtype=torch.float32, device=emb.device)
-        return empty, empty.clone()
-    return torch.cat(raw), torch.cat(filt)
+    n = _n_ranked(test_size, batch_size, all_batches)
+    emb, wd = embedding.detach().contiguous(), w.detach()
+
+    def rank_chunk(a, r, b, f_lo, f_hi, ent):
+        return ops.rank_scores_filtered(_queries(emb, wd, a, r), emb, b, f_lo, f_hi, ent, flow_log_prob)
+    progress = (lambda hi, chunks: _print_progress("rows {} / {}".format(hi, n), " (filtered)", chunks[1])) if verbose else None
+    return _rank_chunks(n, MAX_QUERY_ROWS, a, r, b, filter_index, direction, emb.device, 2, rank_chunk, progress)
 
 
 def calc_filtered_mrr(embedding, w, test_triplets, filter_index, hits=[1, 3, 10], eval_bz=100, all_batches=True,
@@ -316,26 +346,11 @@ def calc_filtered_mrr(embedding, w, test_triplets, filter_index, hits=[1, 3, 10]
     """Raw and filtered MRR / Hits@k over both directions, from one scorer launch pair per chunk of queries.  Returns
     ``{'mrr_raw', 'mrr_filtered', 'hits_raw': {k: v}, 'hits_filtered': {k: v}}``; ``mrr_raw`` equals ``calc_mrr``'s value."""
     with torch.no_grad():
-        test_triplets = test_triplets.to(embedding.device)
-        w = w.to(embedding.device)
-        if isinstance(flow_log_prob, torch.Tensor):
-            flow_log_prob = flow_log_prob.to(embedding.device)
-        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
-        n = test_triplets.shape[0]
-        raw_s, filt_s = perturb_and_get_rank_filtered(embedding, w, o, r, s, n, filter_index, 's', eval_bz, all_batches,
-                                                      flow_log_prob)
-        raw_o, filt_o = perturb_and_get_rank_filtered(embedding, w, s, r, o, n, filter_index, 'o', eval_bz, all_batches,
-                                                      flow_log_prob)
-        out = {}
-        for kind, ranks in (('raw', torch.cat([raw_s, raw_o]) + 1), ('filtered', torch.cat([filt_s, filt_o]) + 1)):
-            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
-            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
-        if verbose:
-            for kind in ('raw', 'filtered'):
-                print("MRR ({}): {:.6f}".format(kind, out['mrr_' + kind]))
-                for hit in hits:
-                    print("Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
-    return out
+        w, flow_log_prob = _on_device(embedding, w, flow_log_prob)
+        by_s, by_o = _both_directions(embedding, test_triplets, eval_bz, all_batches, lambda a, r, b, n, d:
+                                      perturb_and_get_rank_filtered(embedding, w, a, r, b, n, filter_index, d, eval_bz, all_batches,
+                                                                    flow_log_prob))
+        return _report(by_s, by_o, CONSTRAINED_KINDS[:2], hits, verbose, MRR_LINES)
 
 
 def _listed_mask(filt_lo, filt_hi, filt_ent, m, v, device):
@@ -389,7 +404,7 @@ def _predict_topk(embedding, w, a, r, k, direction, filter_index, select, type_c
     ids, logits = [], []
     for lo in range(0, a.shape[0], MAX_QUERY_ROWS):
         hi = min(a.shape[0], lo + MAX_QUERY_ROWS)
-        q = ops.mul(emb[a[lo:hi]].contiguous(), wd[r[lo:hi]].contiguous())
+        q = _queries(emb, wd, a[lo:hi], r[lo:hi])
         f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], direction) if filter_index is not None else (None, None)
         if type_constraint is None:
             i, l = select(q, emb, f_lo, f_hi, ent)
@@ -454,14 +469,7 @@ def mc_ranks_from_probs(pbar, target, listed_mask=None):
     (a NaN candidate or a NaN target counts as better, ties count half), the target itself left out; the filtered rank also
     leaves out the candidates of ``listed_mask`` (dense (m, v) bool), NaN ones included.  Returns ``(raw, filtered)``, 0-based
     float mid-ranks; ``filtered`` is None without a mask."""
-    t = target.view(-1, 1).to(pbar.device)
-    tgt = pbar.gather(1, t)
-    other = torch.ones_like(pbar, dtype=torch.bool).scatter_(1, t, False)
-    better, equal = (~(pbar <= tgt)) & other, (pbar == tgt) & other
-
-    def rank(pool):
-        return (better & pool).sum(dim=1).float() + 0.5 * (equal & pool).sum(dim=1).float()
-    return rank(other), (None if listed_mask is None else rank(~listed_mask.to(pbar.device)))
+    return mid_ranks(pbar, target.to(pbar.device), None if listed_mask is None else listed_mask.to(pbar.device))[:2]
 
 
 def _mc_args(z, w, flow_log_probs):
@@ -493,25 +501,23 @@ def _mc_pbar_unfused(z, w, a, r, flp):
     return total * (1.0 / z.shape[0])
 
 
-def _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, fused):
-    ent = filter_index.entities(direction, z.device) if filter_index is not None else None
-    raw, filt = [], []
-    step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
-    for lo in range(0, n, step):
-        sl = slice(lo, min(n, lo + step))
-        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
+def _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, fused, type_constraint=None):
+    """The Monte-Carlo rank driver, fused or materialised: (raw, filtered), or with a ``type_constraint`` the four kinds."""
+    words = type_constraint.words.to(z.device) if fused and type_constraint is not None else None
+
+    def rank_chunk(a, r, b, f_lo, f_hi, ent):
+        sets = type_constraint.set_ids(r, direction) if type_constraint is not None else None
         if fused:
-            rr, rf, _ = ops.rank_scores_mc(_mc_queries(z, w, a[sl], r[sl]), z, b[sl], flp, f_lo, f_hi, ent)
-        else:
-            pbar = _mc_pbar_unfused(z, w, a[sl], r[sl], flp)
-            listed = None if ent is None else _listed_mask(f_lo, f_hi, ent, pbar.shape[0], pbar.shape[1], pbar.device)
-            rr, rf = mc_ranks_from_probs(pbar, b[sl], listed)
-        raw.append(rr)
-        filt.append(rf)
-    if not raw:
-        empty = torch.zeros(0, dtype=torch.float32, device=z.device)
-        return empty, (empty.clone() if filter_index is not None else None)
-    return torch.cat(raw), (torch.cat(filt) if filter_index is not None else None)
+            if sets is None:
+                return ops.rank_scores_mc(_mc_queries(z, w, a, r), z, b, flp, f_lo, f_hi, ent)[:2]
+            return ops.rank_scores_mc_constrained(_mc_queries(z, w, a, r), z, b, words, sets, flp, f_lo, f_hi, ent)[:4]
+        pbar = _mc_pbar_unfused(z, w, a, r, flp)
+        listed = None if ent is None else _listed_mask(f_lo, f_hi, ent, pbar.shape[0], pbar.shape[1], pbar.device)
+        if sets is None:
+            return mc_ranks_from_probs(pbar, b, listed)
+        return rank_from_scores_constrained(pbar, b.to(pbar.device), type_constraint.mask(sets, pbar.device), listed)
+    return _rank_chunks(n, MC_STACK_ROWS if fused else MC_UNFUSED_ROWS, a, r, b, filter_index, direction, z.device,
+                        2 if type_constraint is None else 4, rank_chunk)
 
 
 def perturb_and_get_rank_mc(z, w, a, r, b, test_size, filter_index=None, direction='o', batch_size=100, all_batches=True,
@@ -519,8 +525,7 @@ def perturb_and_get_rank_mc(z, w, a, r, b, test_size, filter_index=None, directi
     """(raw, filtered) posterior-predictive ranks of ``b`` for the queries (a, r) under the samples ``z`` (S, N, h): one fused
     launch pair per ``MC_STACK_ROWS`` queries (ops.rank_scores_mc).  ``filtered`` is None without a ``filter_index``."""
     z, w, flp = _mc_args(z, w, flow_log_probs)
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    return _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, True)
+    return _perturb_and_get_rank_mc(z, w, a, r, b, _n_ranked(test_size, batch_size, all_batches), filter_index, direction, flp, True)
 
 
 def perturb_and_get_rank_mc_unfused(z, w, a, r, b, test_size, filter_index=None, direction='o', batch_size=100, all_batches=True,
@@ -528,32 +533,15 @@ def perturb_and_get_rank_mc_unfused(z, w, a, r, b, test_size, filter_index=None,
     """``perturb_and_get_rank_mc`` from materialised probabilities (S GEMMs, sigmoids and a running sum per chunk, then
     ``mc_ranks_from_probs``): the in-repo cross-check and the bench's baseline."""
     z, w, flp = _mc_args(z, w, flow_log_probs)
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    return _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, direction, flp, False)
+    return _perturb_and_get_rank_mc(z, w, a, r, b, _n_ranked(test_size, batch_size, all_batches), filter_index, direction, flp, False)
 
 
-def _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, fused):
+def _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, fused, type_constraint=None):
     with torch.no_grad():
         z, w, flp = _mc_args(z, w, flow_log_probs)
-        test_triplets = test_triplets.to(z.device)
-        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
-        n = test_triplets.shape[0]
-        n = min(n, eval_bz) if all_batches is False else n
-        raw_s, filt_s = _perturb_and_get_rank_mc(z, w, o, r, s, n, filter_index, 's', flp, fused)
-        raw_o, filt_o = _perturb_and_get_rank_mc(z, w, s, r, o, n, filter_index, 'o', flp, fused)
-        kinds = [('raw', torch.cat([raw_s, raw_o]) + 1)]
-        if filter_index is not None:
-            kinds.append(('filtered', torch.cat([filt_s, filt_o]) + 1))
-        out = {'n_samples': int(z.shape[0])}
-        for kind, ranks in kinds:
-            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
-            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
-        if verbose:
-            for kind, _ in kinds:
-                print("MC MRR ({}, {} samples): {:.6f}".format(kind, out['n_samples'], out['mrr_' + kind]))
-                for hit in hits:
-                    print("MC Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
-    return out
+        by_s, by_o = _both_directions(z, test_triplets, eval_bz, all_batches, lambda a, r, b, n, d:
+                                      _perturb_and_get_rank_mc(z, w, a, r, b, n, filter_index, d, flp, fused, type_constraint))
+        return _report(by_s, by_o, CONSTRAINED_KINDS, hits, verbose, MC_MRR_LINES, {'n_samples': int(z.shape[0])})
 
 
 def calc_mc_mrr(z, w, test_triplets, filter_index=None, flow_log_probs=None, hits=[1, 3, 10], eval_bz=100, all_batches=True,
@@ -571,30 +559,6 @@ def calc_mc_mrr_unfused(z, w, test_triplets, filter_index=None, flow_log_probs=N
     return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, False)
 
 
-def _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, fused):
-    ent = filter_index.entities(direction, z.device) if filter_index is not None else None
-    words = type_constraint.words.to(z.device) if fused else None
-    out = [[], [], [], []]
-    step = MC_STACK_ROWS if fused else MC_UNFUSED_ROWS
-    for lo in range(0, n, step):
-        sl = slice(lo, min(n, lo + step))
-        f_lo, f_hi = filter_index.lookup(a[sl], r[sl], direction) if filter_index is not None else (None, None)
-        sets = type_constraint.set_ids(r[sl], direction)
-        if fused:
-            ranks = ops.rank_scores_mc_constrained(_mc_queries(z, w, a[sl], r[sl]), z, b[sl], words, sets, flp, f_lo, f_hi, ent)[:4]
-        else:
-            pbar = _mc_pbar_unfused(z, w, a[sl], r[sl], flp)
-            listed = None if ent is None else _listed_mask(f_lo, f_hi, ent, pbar.shape[0], pbar.shape[1], pbar.device)
-            ranks = rank_from_scores_constrained(pbar, b[sl].to(pbar.device), type_constraint.mask(sets, pbar.device), listed)
-        for acc, x in zip(out, ranks):
-            acc.append(x)
-    if not out[0]:
-        out = [[torch.zeros(0, dtype=torch.float32, device=z.device)] for _ in out]
-        if filter_index is None:
-            out[1] = out[3] = [None]
-    return tuple(None if x[0] is None else torch.cat(x) for x in out)
-
-
 def perturb_and_get_rank_mc_constrained(z, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
                                         all_batches=True, flow_log_probs=None):
     """(raw, filtered, raw_constrained, filtered_constrained) posterior-predictive ranks of ``b`` for the queries (a, r) under the
@@ -602,8 +566,8 @@ def perturb_and_get_rank_mc_constrained(z, w, a, r, b, test_size, filter_index, 
     only, all four on the same pbar (ops.rank_scores_mc_constrained, one fused launch pair per ``MC_STACK_ROWS`` queries).
     ``filter_index`` may be None: the two filtered ranks are then None."""
     z, w, flp = _mc_args(z, w, flow_log_probs)
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    return _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, True)
+    return _perturb_and_get_rank_mc(z, w, a, r, b, _n_ranked(test_size, batch_size, all_batches), filter_index, direction, flp, True,
+                                    type_constraint)
 
 
 def perturb_and_get_rank_mc_constrained_unfused(z, w, a, r, b, test_size, filter_index, type_constraint, direction, batch_size=100,
@@ -612,33 +576,8 @@ def perturb_and_get_rank_mc_constrained_unfused(z, w, a, r, b, test_size, filter
     ``rank_from_scores_constrained`` applied to pbar -- its predicates are the MC rule already): the in-repo cross-check and the
     bench's baseline."""
     z, w, flp = _mc_args(z, w, flow_log_probs)
-    n = min(test_size, batch_size) if all_batches is False else test_size
-    return _perturb_and_get_rank_mc_constrained(z, w, a, r, b, n, filter_index, type_constraint, direction, flp, False)
-
-
-def _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches, verbose,
-                             fused):
-    with torch.no_grad():
-        z, w, flp = _mc_args(z, w, flow_log_probs)
-        test_triplets = test_triplets.to(z.device)
-        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
-        n = test_triplets.shape[0]
-        n = min(n, eval_bz) if all_batches is False else n
-        by_s = _perturb_and_get_rank_mc_constrained(z, w, o, r, s, n, filter_index, type_constraint, 's', flp, fused)
-        by_o = _perturb_and_get_rank_mc_constrained(z, w, s, r, o, n, filter_index, type_constraint, 'o', flp, fused)
-        out = {'n_samples': int(z.shape[0])}
-        for kind, rs, ro in zip(CONSTRAINED_KINDS, by_s, by_o):
-            if rs is None:                                    # no filter_index: the two filtered kinds are not reported
-                continue
-            ranks = torch.cat([rs, ro]) + 1
-            out['mrr_' + kind] = torch.mean(1.0 / ranks.float()).item()
-            out['hits_' + kind] = {hit: torch.mean((ranks <= hit).float()).item() for hit in hits}
-        if verbose:
-            for kind in (k for k in CONSTRAINED_KINDS if 'mrr_' + k in out):
-                print("MC MRR ({}, {} samples): {:.6f}".format(kind, out['n_samples'], out['mrr_' + kind]))
-                for hit in hits:
-                    print("MC Hits ({}) @ {}: {:.6f}".format(kind, hit, out['hits_' + kind][hit]))
-    return out
+    return _perturb_and_get_rank_mc(z, w, a, r, b, _n_ranked(test_size, batch_size, all_batches), filter_index, direction, flp, False,
+                                    type_constraint)
 
 
 def calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs=None, hits=[1, 3, 10], eval_bz=100,
@@ -646,15 +585,13 @@ def calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, 
     """The four-way report of the type-constrained protocol on the posterior predictive, over both directions: ``n_samples`` and
     ``mrr_<kind>`` / ``hits_<kind>: {k: v}`` for the kinds of ``CONSTRAINED_KINDS`` (the filtered ones only with a
     ``FilterIndex``).  Every kind ranks on ``calc_mc_mrr``'s pbar: the raw and filtered figures equal its values."""
-    return _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches,
-                                    verbose, True)
+    return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, True, type_constraint)
 
 
 def calc_mc_constrained_mrr_unfused(z, w, test_triplets, filter_index, type_constraint, flow_log_probs=None, hits=[1, 3, 10],
                                     eval_bz=100, all_batches=True, verbose=True):
     """``calc_mc_constrained_mrr`` on the materialised route (``perturb_and_get_rank_mc_constrained_unfused``)."""
-    return _calc_mc_constrained_mrr(z, w, test_triplets, filter_index, type_constraint, flow_log_probs, hits, eval_bz, all_batches,
-                                    verbose, False)
+    return _calc_mc_mrr(z, w, test_triplets, filter_index, flow_log_probs, hits, eval_bz, all_batches, verbose, False, type_constraint)
 
 
 def _predict_topk_mc(z, w, a, r, k, direction, filter_index, flow_log_probs, fused, type_constraint=None):
@@ -1250,20 +1187,8 @@ def complete_entities_mc_unfused(z, w, entities, k, *, side='s', filter_index=No
 def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True, flow_log_prob=None,
              verbose=True):
     with torch.no_grad():
-        # the reference validates with the model "on the CPU" (kgvae/link_predict.py:239-251): whatever side the caller's
-        # tensors are on, the scorer runs where the embedding is
-        test_triplets = test_triplets.to(embedding.device)
-        w = w.to(embedding.device)
-        if isinstance(flow_log_prob, torch.Tensor):
-            flow_log_prob = flow_log_prob.to(embedding.device)
-        s, r, o = test_triplets[:, 0], test_triplets[:, 1], test_triplets[:, 2]
-        n = test_triplets.shape[0]
-        ranks_s = perturb_and_get_rank(embedding, w, o, r, s, n, eval_bz, all_batches, flow_log_prob)
-        ranks_o = perturb_and_get_rank(embedding, w, s, r, o, n, eval_bz, all_batches, flow_log_prob)
-        ranks = torch.cat([ranks_s, ranks_o]) + 1
-        mrr = torch.mean(1.0 / ranks.float())
-        if verbose:
-            print("MRR (raw): {:.6f}".format(mrr.item()))
-            for hit in hits:
-                print("Hits (raw) @ {}: {:.6f}".format(hit, torch.mean((ranks <= hit).float()).item()))
-    return mrr.item()
+        w, flow_log_prob = _on_device(embedding, w, flow_log_prob)
+        by_s, by_o = _both_directions(embedding, test_triplets, eval_bz, all_batches, lambda a, r, b, n, d:
+                                      (perturb_and_get_rank(embedding, w, a, r, b, n, eval_bz, all_batches, flow_log_prob),))
+        # Hits@k are printed, never returned: not computed when nothing is printed
+        return _report(by_s, by_o, CONSTRAINED_KINDS[:1], hits if verbose else (), verbose, MRR_LINES)['mrr_raw']

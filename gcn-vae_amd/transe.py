@@ -80,7 +80,7 @@ import torch.nn.functional as F
 from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
                       UNCONSTRAINED, _complete_constraint, _complete_mask_args, _complete_queries, _complete_side, _complete_unfused,
-                      _mine_unfused, complete_entities_from_scores, rank_from_scores_constrained, sort_and_rank, topk_from_scores)
+                      _mine_unfused, complete_entities_from_scores, mid_ranks, rank_from_scores_constrained, topk_from_scores)
 from .train import profile_entities_arg, write_profile_lines
 
 
@@ -445,54 +445,50 @@ def _summary(raw, filt, hits, suffix=''):
     return out
 
 
-def rank_transe(ent, rel, triplets, p_norm, norm_flag, filter_index=None):
-    """(raw, filtered) 0-based ranks, head queries of every triplet then tail queries, from the fused ranker."""
-    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
-    en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
-    raws, filts = [], []
+def _rank_directions(ent, triplets, step, filter_index, n_kinds, rank_chunk):
+    """The direction x chunk loop of the four rankers, once: all head queries (?, r, o), then all tail queries (s, r, ?), ``step``
+    at a time through ``rank_chunk(head, direction, a, r, b, filt)`` -- ``filt`` the chunk's ``(filt_lo, filt_hi, filt_ent)``, three
+    None without a ``filter_index`` --, which returns the chunk's ``n_kinds`` ranks, raw and filtered alternating.  A filtered one
+    that comes back None (no filter) is its unfiltered twin."""
+    s, r, o = (triplets[:, i].to(ent.device).long() for i in range(3))
+    out = [[] for _ in range(n_kinds)]
     for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
         ent_f = filter_index.entities(d, ent.device) if filter_index is not None else None
-        for lo in range(0, a.numel(), MAX_QUERY_ROWS):
-            hi = min(a.numel(), lo + MAX_QUERY_ROWS)
-            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
-            f = (None, None, None)
-            if filter_index is not None:
-                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
-                f = (f_lo, f_hi, ent_f)
-            rr, rf = ops.transe_rank_filtered(q, en, b[lo:hi], p_norm, *f)
-            raws.append(rr)
-            filts.append(rf)
-    return torch.cat(raws), torch.cat(filts)
+        for lo in range(0, a.numel(), step):
+            sl = slice(lo, min(a.numel(), lo + step))
+            filt = (*filter_index.lookup(a[sl], r[sl], d), ent_f) if filter_index is not None else (None, None, None)
+            ranks = rank_chunk(head, d, a[sl], r[sl], b[sl], filt)
+            for i, acc in enumerate(out):
+                acc.append(ranks[i - 1] if ranks[i] is None else ranks[i])
+    return tuple(torch.cat(x) for x in out)
+
+
+def rank_transe(ent, rel, triplets, p_norm, norm_flag, filter_index=None):
+    """(raw, filtered) 0-based ranks, head queries of every triplet then tail queries, from the fused ranker."""
+    en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
+
+    def rank_chunk(head, d, a, r, b, filt):
+        q = ops.transe_queries(ent, rel, a, r, head=head, norm_flag=norm_flag)
+        return ops.transe_rank_filtered(q, en, b, p_norm, *filt)
+    return _rank_directions(ent, triplets, MAX_QUERY_ROWS, filter_index, 2, rank_chunk)
 
 
 def rank_transe_unfused(ent, rel, triplets, p_norm, norm_flag, filter_index=None, batch=32):
     """``rank_transe`` in plain torch on materialised distances: the reference's head_batch / tail scores of every entity,
     ``sort_and_rank(-distance)``'s rule, the filtered count over the entities the filter does not list."""
-    s, r, o = (triplets[:, i].to(ent.device).long() for i in range(3))
     v = ent.shape[0]
-    raws, filts = [], []
-    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
-        for lo in range(0, a.numel(), batch):
-            hi = min(a.numel(), lo + batch)
-            m = hi - lo
-            cand = ent.unsqueeze(0).expand(m, v, ent.shape[1])
-            fix = ent[a[lo:hi]].unsqueeze(1).expand_as(cand)
-            rr = rel[r[lo:hi]].unsqueeze(1).expand_as(cand)
-            if norm_flag:
-                cand, fix, rr = F.normalize(cand, 2, -1), F.normalize(fix, 2, -1), F.normalize(rr, 2, -1)
-            diff = cand + (rr - fix) if head else (fix + rr) - cand
-            dist = torch.norm(diff, p_norm, -1)
-            raws.append(sort_and_rank(-dist, b[lo:hi]))
-            if filter_index is not None:
-                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
-                listed = _listed_mask(f_lo, f_hi, filter_index.entities(d), m, v, dist.device)
-                score, tgt = -dist, -dist.gather(1, b[lo:hi].view(-1, 1))
-                keep = ~listed
-                keep[torch.arange(m, device=dist.device), b[lo:hi]] = False
-                filts.append(((~(score <= tgt)) & keep).sum(1).float() + 0.5 * ((score == tgt) & keep).sum(1).float())
-            else:
-                filts.append(raws[-1])
-    return torch.cat(raws), torch.cat(filts)
+
+    def rank_chunk(head, d, a, r, b, filt):
+        cand = ent.unsqueeze(0).expand(a.numel(), v, ent.shape[1])
+        fix = ent[a].unsqueeze(1).expand_as(cand)
+        rr = rel[r].unsqueeze(1).expand_as(cand)
+        if norm_flag:
+            cand, fix, rr = F.normalize(cand, 2, -1), F.normalize(fix, 2, -1), F.normalize(rr, 2, -1)
+        diff = cand + (rr - fix) if head else (fix + rr) - cand
+        dist = torch.norm(diff, p_norm, -1)
+        listed = None if filter_index is None else _listed_mask(*filt, a.numel(), v, dist.device)
+        return mid_ranks(-dist, b, listed)[:2]
+    return _rank_directions(ent, triplets, batch, filter_index, 2, rank_chunk)
 
 
 def rank_transe_constrained(ent, rel, triplets, p_norm, norm_flag, type_constraint, filter_index=None):
@@ -500,45 +496,26 @@ def rank_transe_constrained(ent, rel, triplets, p_norm, norm_flag, type_constrai
     triplet, then tail queries) from the fused ranker: the constrained ranks count the members of the relation's type set only
     (``ranking.TypeConstraint``: subjects of r for a head query, objects of r for a tail query).  Without a filter the two
     filtered ones equal their unfiltered twins, as ``rank_transe``'s do."""
-    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
     en = ops.transe_queries(ent, norm_flag=norm_flag)                     # the normalised table, once
     words = type_constraint.words.to(ent.device)
-    out = [[], [], [], []]
-    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
-        ent_f = filter_index.entities(d, ent.device) if filter_index is not None else None
-        for lo in range(0, a.numel(), MAX_QUERY_ROWS):
-            hi = min(a.numel(), lo + MAX_QUERY_ROWS)
-            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
-            f = (None, None, None)
-            if filter_index is not None:
-                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
-                f = (f_lo, f_hi, ent_f)
-            rr, rf, rc, rfc = ops.transe_rank_constrained(q, en, b[lo:hi], p_norm, words, type_constraint.set_ids(r[lo:hi], d), *f)
-            for acc, x in zip(out, (rr, rr if rf is None else rf, rc, rc if rfc is None else rfc)):
-                acc.append(x)
-    return tuple(torch.cat(x) for x in out)
+
+    def rank_chunk(head, d, a, r, b, filt):
+        q = ops.transe_queries(ent, rel, a, r, head=head, norm_flag=norm_flag)
+        return ops.transe_rank_constrained(q, en, b, p_norm, words, type_constraint.set_ids(r, d), *filt)
+    return _rank_directions(ent, triplets, MAX_QUERY_ROWS, filter_index, 4, rank_chunk)
 
 
 def rank_transe_constrained_unfused(ent, rel, triplets, p_norm, norm_flag, type_constraint, filter_index=None, batch=1024):
     """``rank_transe_constrained`` on materialised distances: ``ranking.rank_from_scores_constrained`` on
     ``-ops.transe_distances`` -- the bits the fused ranker compares -- chunk by chunk."""
-    s, r, o = (triplets[:, i].to(ent.device) for i in range(3))
     en = ops.transe_queries(ent, norm_flag=norm_flag)
-    v = ent.shape[0]
-    out = [[], [], [], []]
-    for head, a, b, d in ((True, o, s, 's'), (False, s, o, 'o')):
-        for lo in range(0, a.numel(), batch):
-            hi = min(a.numel(), lo + batch)
-            q = ops.transe_queries(ent, rel, a[lo:hi], r[lo:hi], head=head, norm_flag=norm_flag)
-            listed = None
-            if filter_index is not None:
-                f_lo, f_hi = filter_index.lookup(a[lo:hi], r[lo:hi], d)
-                listed = _listed_mask(f_lo, f_hi, filter_index.entities(d), hi - lo, v, ent.device)
-            cand = type_constraint.mask(type_constraint.set_ids(r[lo:hi], d), ent.device)
-            rr, rf, rc, rfc = rank_from_scores_constrained(-ops.transe_distances(q, en, p_norm), b[lo:hi].long(), cand, listed)
-            for acc, x in zip(out, (rr, rr if rf is None else rf, rc, rc if rfc is None else rfc)):
-                acc.append(x)
-    return tuple(torch.cat(x) for x in out)
+
+    def rank_chunk(head, d, a, r, b, filt):
+        q = ops.transe_queries(ent, rel, a, r, head=head, norm_flag=norm_flag)
+        listed = None if filter_index is None else _listed_mask(*filt, a.numel(), ent.shape[0], ent.device)
+        cand = type_constraint.mask(type_constraint.set_ids(r, d), ent.device)
+        return rank_from_scores_constrained(-ops.transe_distances(q, en, p_norm), b, cand, listed)
+    return _rank_directions(ent, triplets, batch, filter_index, 4, rank_chunk)
 
 
 def evaluate(model, triplets, filter_index=None, hits=(1, 3, 10), unfused=False, verbose=True, type_constraint=None):
