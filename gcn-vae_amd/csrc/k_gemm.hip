@@ -1940,6 +1940,177 @@ extern "C" int gv_entity_topk_scores_typed_mc(const int32_t* ents, int m, const 
                                          span_tiles, out_rel, out_ent, out_prob, workspace, workspace_bytes, n, num_rels, h, stream);
 }
 
+namespace gv {
+
+// ---- relation prediction (gv_pair_rel_scores): the query is an entity pair, the candidates are the relations ---------------------
+// logit[i, r] = (e[s_i] * e[o_i]) . w[r] + bias.  The product row is made while it is staged, as k_entity_topk_span makes
+// e[a] * w[r] -- a thread's four floats of e[s] times the same four of e[o], one f32 multiply each, the value gv_mul stores -- and
+// the relation rows go through load_b, so the tile is score_tile_with's and a logit is gv_gemm_f32(gv_mul(e[s], e[o]), w^T) + bias
+// bit for bit.  There are 11 .. 1 345 candidates, one to 22 column tiles: a workgroup owns a 64-pair row tile and walks ALL of them
+// itself, in ascending order -- no spans, no workspace, no merge, one launch for ranks and list together.  Per tile the logits go
+// through Ls; wave w then takes rows 16 w .. 16 w + 15, one lane per column (topk_pair_rel_tile of k_topk.h, shared with
+// k_transe_pair_rel): the row's filter window (the cursor is shared by the count and the list), two ballots against the target's
+// logit for the counts, and the key into the row's sorted list.  A row's counts and list sit in LDS for the whole walk and belong to one wave, so nothing is atomic and the
+// epilogue is that wave's plain stores.
+// The target's logit is a tile's own element.  With one column tile it is read back from Ls; with more, one extra tile is made
+// ahead of the walk with the relation rows GATHERED through the rows' targets (score_tile_gather: the same staging, the same chain,
+// so a gathered row's logits are the bits score_tile gives that row) and its element (j, j) is row j's -- the walk proper
+// recomputes it bit for bit, as k_rank_scores<1> recomputes what k_rank_scores<0> wrote.
+// (A later sample loop -- the posterior predictive -- goes around score_tile_with here as in k_entity_topk_span<.., MC>: the
+// parameters carry the table by pointer and leading dimension, so a sample stride beside them is all it needs.)
+struct PairRelParams {
+    GemmParams g;                 // b = w (stored [R, h]), m, n = R, k = h; a is not read
+    const float* e;               // [n_entities, ld_e]
+    int ld_e, vec_a;              // vec_a: four floats of a row of e may be read as one
+    const int* s;                 // [m] the pairs' entities, trusted to lie in [0, n_entities)
+    const int* o;
+    const int* target;            // NULL: no ranks
+    const float* bias;
+    const int* filt_lo;           // NULL: no filter
+    const int* filt_hi;
+    const int* filt_rel;
+    int n_filt;                   // length of filt_rel: every range is clamped into it
+    int topk;                     // 0: no list
+    float* tgt;
+    int* count_raw;               // may be NULL
+    int* count_filt;              // NULL without a filter
+    int* out_ids;
+    float* out_logits;
+};
+
+// rank_votes' predicates: greater, or either side NaN; the key of gv_topk_scores
+struct PairRelRule {
+    static __device__ __forceinline__ bool above(float v, float t) { return !(v <= t); }
+    static __device__ __forceinline__ unsigned long long key(float v, int col) { return topk_key(v, col); }
+};
+
+template <int NK>                 // keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
+__global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
+    constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256;
+    __shared__ float As[BK * SC_LDA];
+    __shared__ float Bs[BK * SC_LDB];
+    __shared__ float Ls[BM * LDL];                 // the tile's logits, row-major
+    __shared__ unsigned long long thr[BM];         // each row's k-th key
+    __shared__ int cur[BM], fhi[BM], nxt[BM];      // filter cursor (k_topk.h)
+    __shared__ int fl[4][64];
+    __shared__ int tcol_s[BM];                     // the rows' targets (-1: none)
+    __shared__ float tgt_s[BM];                    // ... and their logits
+    __shared__ int cnt_s[2][BM];                   // 2 #better + #equal: raw, filtered
+    extern __shared__ unsigned long long lists[];  // [BM][topk]
+    const GemmParams& p = pp.g;
+    const int k = pp.topk;
+    const int m0 = blockIdx.x * BM;
+    const int col_tiles = (p.n + BN - 1) / BN;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const bool filtered = pp.filt_lo != nullptr, ranked = pp.target != nullptr;
+    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, tgt_s, cnt_s};
+
+    // this thread's share of the query operand: row threadIdx.x / 4 of the tile, APT floats from column (threadIdx.x % 4) * APT on
+    const int a_row = m0 + threadIdx.x / (BK / APT), a_col = (threadIdx.x % (BK / APT)) * APT;
+    const bool a_ok = a_row < p.m;
+    const float* s_src = pp.e + (a_ok ? (size_t)pp.s[a_row] * pp.ld_e : 0) + a_col;
+    const float* o_src = pp.e + (a_ok ? (size_t)pp.o[a_row] * pp.ld_e : 0) + a_col;
+    auto load_q = [&](int k0, float (&r)[APT]) {
+        float ov[APT];
+        load_run<APT>(s_src + k0, a_col + k0, p.k, a_ok, pp.vec_a, r, 0);
+        load_run<APT>(o_src + k0, a_col + k0, p.k, a_ok, pp.vec_a, ov, 0);
+#pragma unroll
+        for (int i = 0; i < APT; ++i) r[i] *= ov[i];
+    };
+
+    if constexpr (NK > 0)
+        for (int i = threadIdx.x; i < BM * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (threadIdx.x < BM) {
+        const int rl = threadIdx.x, row = m0 + rl;
+        thr[rl] = 0ull;
+        cnt_s[0][rl] = 0; cnt_s[1][rl] = 0;
+        tcol_s[rl] = (ranked && row < p.m) ? pp.target[row] : -1;
+        tgt_s[rl] = __uint_as_float(0x7fc00000u);  // a target outside [0, R) ranks last
+        topk_filter_begin(pp.filt_lo, pp.filt_hi, pp.filt_rel, pp.n_filt, filtered && row < p.m, row, 0, &cur[rl], &fhi[rl], &nxt[rl]);
+    }
+    const float bv = pp.bias ? *pp.bias : 0.f;
+    float ra[APT], rb[BN * BK / 256];
+
+    if (ranked && col_tiles > 1) {                 // the targets' logits: ONE gathered tile whose column j is w[target of row j]
+        const int tc = a_ok ? pp.target[a_row] : -1;                      // (this thread's B slot is its A row: threadIdx.x / 4)
+        const bool t_ok = (unsigned)tc < (unsigned)p.n;
+        const float* t_src = p.b + (t_ok ? (size_t)tc * p.ldb : 0) + a_col;
+        auto load_t = [&](int k0, float (&r)[BN * BK / 256]) { load_run<BN * BK / 256>(t_src + k0, a_col + k0, p.k, t_ok, p.vec_b, r, 0); };
+        load_q(0, ra);
+        load_t(0, rb);
+        const f32x16 acc = score_tile_gather(p, load_q, load_t, ra, rb, As, Bs);      // (its barriers publish the set-up)
+        const int cl = wn + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {                                    // element (j, j) is row j's own
+            const int rl = wm + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+            if (rl == cl && (unsigned)tcol_s[rl] < (unsigned)p.n) tgt_s[rl] = acc[r] + bv;
+        }
+    }
+
+    load_q(0, ra);
+    load_b<true, BN, BK>(p, 0, 0, p.k, rb);
+    for (int t = 0; t < col_tiles; ++t) {
+        const int n0 = t * BN;
+        // score_tile_with's first barrier publishes the set-up (and the gathered tile's tgt_s) and ends the last tile's reads of Ls
+        const f32x16 acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
+        if (t + 1 < col_tiles) {                   // the next tile's first operands fly under the selection
+            load_q(0, ra);
+            load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ls[(wm + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDL + wn + l31] = acc[r] + bv;
+        __syncthreads();
+        if (ranked && col_tiles == 1) {            // the one tile holds every target
+            if (threadIdx.x < BM && (unsigned)tcol_s[threadIdx.x] < (unsigned)p.n)
+                tgt_s[threadIdx.x] = Ls[threadIdx.x * LDL + tcol_s[threadIdx.x]];
+            __syncthreads();
+        }
+        topk_pair_rel_tile<NK, PairRelRule>(st, m0, p.m, n0, p.n, t, k, ranked, pp.filt_rel, lane, wid,
+                                            [&](int rl) { return Ls[rl * LDL + lane]; });
+    }
+    topk_pair_rel_store<NK, int, topk_key_logit>(st, m0, p.m, k, ranked, pp.tgt, pp.count_raw, pp.count_filt, pp.out_ids, pp.out_logits,
+                                                 lane, wid);
+}
+
+}  // namespace gv
+
+extern "C" int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* w, int ld_w, int num_rels, const int32_t* s,
+                                  const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo, const int* filt_hi,
+                                  const int* filt_rel, int n_filt_rel, int k, float* tgt, int* count_raw, int* count_filt, int* out_ids,
+                                  float* out_logits, int m, int h, void* stream) {
+    const char* name = "gv_pair_rel_scores";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_rel >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_rel=%d", name,
+               m, n, num_rels, h, n_filt_rel);
+    GV_CHECK(pair_query_asks(name, k, target));
+    GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_rel, "filt_lo / filt_hi / filt_rel"));
+    if (m == 0) return GV_OK;
+    GV_CHECK(pair_query_given(name, e && w && s && o, target, tgt, k, out_ids, out_logits, filt_lo, count_filt));
+    PairRelParams pp{};
+    pp.g = score_gemm_params(nullptr, ld_e, w, ld_w, m, num_rels, h);
+    pp.e = e; pp.ld_e = ld_e;
+    pp.vec_a = aligned16(e) && (ld_e % 4 == 0);
+    pp.s = s; pp.o = o; pp.target = target; pp.bias = bias;
+    pp.filt_lo = filt_lo; pp.filt_hi = filt_hi; pp.filt_rel = filt_rel; pp.n_filt = n_filt_rel;
+    pp.topk = k;
+    pp.tgt = tgt; pp.count_raw = count_raw; pp.count_filt = filt_lo ? count_filt : nullptr;
+    pp.out_ids = out_ids; pp.out_logits = out_logits;
+    constexpr int KEY = (int)sizeof(unsigned long long);
+    const dim3 grid((unsigned)((m + 63) / 64)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    static unsigned long long raised = 0;          // (<= 64 KiB of lists beside 28 KiB static: only k > 64 needs the limit raised)
+    if (k == 0) hipLaunchKernelGGL(k_pair_rel<0>, grid, block, 0, st, pp);
+    else if (k <= 64) hipLaunchKernelGGL(k_pair_rel<1>, grid, block, 64 * k * KEY, st, pp);
+    else {
+        if (!raise_dynamic_lds((const void*)k_pair_rel<2>, 64 * TOPK_MAX * KEY, raised, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_pair_rel<2>, grid, block, 64 * k * KEY, st, pp);
+    }
+    return launch_status(name);
+}
+
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,
                                 int out_feat, int transpose_w, const int32_t* tiles, int n_tiles, float* msg, void* stream) {
     GV_REQUIRE(num_rels > 0 && in_feat > 0 && out_feat > 0 && n_tiles >= 0, GV_ERR_SHAPE, "gv_rel_rows_gemm: bad sizes");

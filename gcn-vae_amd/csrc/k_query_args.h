@@ -1,8 +1,9 @@
 // The argument checks the entity-query entries share (host only): gv_rank_scores* / gv_topk_scores* / gv_entity_topk_scores{,_typed}
-// (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk{,_typed} (k_transe.hip).  One function per group of arguments; each takes the entry's
+// / gv_pair_rel_scores (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk{,_typed} / gv_transe_pair_rel
+// (k_transe.hip).  One function per group of arguments; each takes the entry's
 // name, sets the library's error text and returns the code, GV_OK when the group is fine.  An entry lists its groups in the order
-// in which it reports them -- tests/test_query_entries_host.py pins every text and, with two faults at once, that order -- then
-// returns for m == 0, then asks for its own pointers.
+// in which it reports them -- tests/test_query_entries_host.py (the pair entries: tests/test_relation_host.py) pins every text
+// and, with two faults at once, that order -- then returns for m == 0, then asks for its own pointers.
 #pragma once
 #include "common.h"
 #include "k_topk.h"
@@ -60,6 +61,23 @@ inline int query_pointers(const char* name, bool all_given) {
 // what comes with a filter: somewhere to count what it leaves (`what`: count_filt, or both filtered counts)
 inline int query_filter_needs(const char* name, const void* filt_lo, bool given, const char* what) {
     GV_REQUIRE(!filt_lo || given, GV_ERR_NULL, "%s: a filter needs %s", name, what);
+    return GV_OK;
+}
+
+// ---- the pair queries (gv_pair_rel_scores, gv_transe_pair_rel): ranks, a top-k, or both from the one launch --------------------
+// k = 0 is "no top-k" there, and a call has to ask for something
+inline int pair_query_asks(const char* name, int k, const void* target) {
+    GV_REQUIRE(k >= 0 && k <= TOPK_MAX, GV_ERR_SHAPE, "%s: k=%d outside [0, %d]", name, k, TOPK_MAX);
+    GV_REQUIRE(k >= 1 || target, GV_ERR_SHAPE, "%s: neither ranks (target) nor a top-k (k >= 1) asked for", name);
+    return GV_OK;
+}
+
+// after m == 0: the tables and the pairs, then what each request writes to, then what comes with a filter
+inline int pair_query_given(const char* name, bool tables, const void* target, const void* tgt, int k, const void* out_ids,
+                            const void* out_values, const void* filt_lo, const void* count_filt) {
+    GV_CHECK(query_pointers(name, tables && (!target || tgt) && (k == 0 || (out_ids && out_values))));
+    GV_REQUIRE(!filt_lo || !target || count_filt, GV_ERR_NULL, "%s: a filter needs count_filt", name);
+    GV_REQUIRE(filt_lo || !count_filt, GV_ERR_NULL, "%s: count_filt needs a filter", name);
     return GV_OK;
 }
 

@@ -6,6 +6,9 @@
 // made, not in how the best k of a row are kept.
 // The two type-constrained per-entity kernels (k_entity_topk_typed_span, k_transe_entity_topk_typed_span) share all of it but the
 // filter window, and their columns -- tiles of the relations' member lists -- are the TopkTyped pieces below.
+// The two pair kernels (k_pair_rel, k_transe_pair_rel: the relations of an entity pair) take the key, the list update and the filter
+// cursor, and share their own row loop and stores (topk_pair_rel_*): a workgroup there walks all of a row's few column tiles itself,
+// so there are no spans, no hand-on and no merge.
 //
 // Candidates are ordered by a 64-bit key, larger = better:
 //   key = ordered_u32(value) << 32 | ~id      ordered_u32: the sign-flip map, -0 -> +0, NaN -> 0 (after -inf)
@@ -215,6 +218,72 @@ __device__ __forceinline__ void topk_span_hand_on(Idx row0, Idx m, const unsigne
         if (row >= m) break;
         unsigned long long* dst = part + ((size_t)row * n_spans + blockIdx.y) * k;
         for (int j = lane; j < k; j += 64) dst[j] = lists[rl * k + j];
+    }
+}
+
+// ---- the pair kernels' selection (k_pair_rel of k_gemm.hip, k_transe_pair_rel of k_transe.hip) -------------------------------------
+// A workgroup there owns a 64-row tile and walks ALL of its few column tiles, so a row's rank counts and its list stay in LDS from
+// the first tile to the stores and belong to one wave (wave w: rows 16 w .. 16 w + 15): no span, no hand-on, no merge, no atomics.
+// The kernel declares the state and hands it over by pointer; what differs between the two -- which value is better, and the key's
+// sign -- is a Rule: Rule::above(v, t) (v beats the target's t, or either is NaN) and Rule::key(v, col).  A tie is v == t in both.
+struct TopkPairRel {
+    unsigned long long* lists;    // [64][k]
+    unsigned long long* thr;      // [64] each row's k-th key
+    int* cur; int* fhi; int* nxt; // [64] the filter cursor
+    int (*fl)[64];                // [4][64] the waves' flag words
+    const int* tcol;              // [64] the rows' targets (-1: none)
+    const float* tgt;             // [64] ... and their values
+    int (*cnt)[64];               // [2][64] 2 #better + #equal: raw, filtered
+};
+
+// The wave's rows of the tile at n0 (the t-th), one lane per column: value(rl) is the lane's value of tile row rl.  One pass of the
+// row's filter window serves the counts and the list alike; the target itself and the columns from v on vote nowhere, a listed
+// column votes in the raw count only and is no candidate.
+template <int NK, class Rule, class Value>
+__device__ __forceinline__ void topk_pair_rel_tile(const TopkPairRel& st, int m0, int m, int n0, int v, int t, int k, bool ranked,
+                                                   const int* filt_ids, int lane, int wid, Value&& value) {
+    const int col = n0 + lane;
+    for (int i = 0; i < 16; ++i) {
+        const int rl = wid * 16 + i;
+        if (m0 + rl >= m) break;
+        const float x = value(rl);
+        bool listed = false;
+        if (filt_ids && st.nxt[rl] < n0 + 64)     // this row lists ids inside the tile: mark them, advance the cursor
+            listed = topk_filter_window(filt_ids, n0, t * 64 + rl + 1, lane, &st.cur[rl], &st.fhi[rl], &st.nxt[rl], st.fl[wid]);
+        if (ranked) {
+            const float tg = st.tgt[rl];
+            const bool other = col < v && col != st.tcol[rl];
+            const unsigned long long ma = __ballot(other && Rule::above(x, tg)), me = __ballot(other && x == tg);
+            const unsigned long long keep = __ballot(!listed);
+            if (lane == 0) {
+                st.cnt[0][rl] += 2 * __popcll(ma) + __popcll(me);
+                st.cnt[1][rl] += 2 * __popcll(ma & keep) + __popcll(me & keep);
+            }
+        }
+        if constexpr (NK > 0)
+            topk_list_update<NK>((col < v && !listed) ? Rule::key(x, col) : 0ull, st.lists + rl * k, &st.thr[rl], k, lane);
+    }
+}
+
+// Each wave hands out its own rows: what it reads it wrote itself (tgt: ahead of the last barrier).  count_raw / count_filt may be
+// NULL; Decode is the key's value back (topk_key_logit, or te_key_dist for a key made of -distance).
+template <int NK, class Id, float (*Decode)(unsigned long long)>
+__device__ __forceinline__ void topk_pair_rel_store(const TopkPairRel& st, int m0, int m, int k, bool ranked, float* tgt, int* count_raw,
+                                                    int* count_filt, Id* out_ids, float* out_values, int lane, int wid) {
+    for (int i = 0; i < 16; ++i) {
+        const int rl = wid * 16 + i, row = m0 + rl;
+        if (row >= m) break;
+        if (ranked && lane == 0) {
+            tgt[row] = st.tgt[rl];
+            if (count_raw) count_raw[row] = st.cnt[0][rl];
+            if (count_filt) count_filt[row] = st.cnt[1][rl];
+        }
+        if constexpr (NK > 0)
+            for (int j = lane; j < k; j += 64) {
+                const unsigned long long key = st.lists[rl * k + j];
+                out_ids[(size_t)row * k + j] = (Id)topk_key_id(key);
+                out_values[(size_t)row * k + j] = Decode(key);
+            }
     }
 }
 

@@ -940,6 +940,116 @@ __global__ __launch_bounds__(256) void k_transe_entity_topk_typed_span(const TeE
     topk_span_hand_on<TE_TQ>(m0, tp.m, lists, k, tp.part, tp.n_spans, lane, wid);
 }
 
+// ---- relation prediction (gv_transe_pair_rel): the query is an entity pair, the candidates are the relations ---------------------
+// d[i, r] = ||(en[o_i] - en[s_i]) - rn[r]||_p: k_pair_rel (k_gemm.hip) on distances.  The query row en[o] - en[s], one f32
+// subtraction per element, is formed while te_tile_with stages it, and the relation table is the tile's "entity" side, so a
+// distance is gv_transe_distances' bits for that row against rn.  In exact arithmetic this is ||n(s) + n(r) - n(o)||, the triplet's
+// distance; it is NOT the bit pattern k_transe_topk_span reports for the same triplet, whose query row is (n(s) + n(r)) and whose
+// difference is taken against n(o): the operands are associated differently, each form rounds once where the other does not.
+// Nothing compares the two.  L2 stays on the vector ALU like every distance here (no MFMA route: DESIGN.md 4c).
+// One workgroup owns 64 pairs and walks all ceil(R / 64) relation tiles in ascending order: no spans, no workspace, no merge.  The
+// target's distance is a tile's own element: with one relation tile it is read back from ds; with more, one extra tile is made ahead
+// of the walk with the relation rows GATHERED through the rows' targets (te_tile_gather: the same staging, the same column order,
+// the same per-pair chain) and its element (j, j) is row j's.  Counts and lists live in LDS and belong to the wave that owns the
+// row; nothing is atomic.
+struct TePairRelParams {
+    const float* en;              // [n, dim]
+    const float* rn;              // [num_rels, dim]
+    const int32_t* s;             // [m] the pairs' entities, trusted to lie in [0, n)
+    const int32_t* o;
+    const int32_t* target;        // NULL: no ranks
+    const int32_t* filt_lo;       // NULL: no filter
+    const int32_t* filt_hi;
+    const int32_t* filt_rel;
+    int m, num_rels, dim, p;
+    int n_filt;                   // length of filt_rel: every range is clamped into it
+    int topk;                     // 0: no list
+    float* tgt;
+    int32_t* count_raw;           // may be NULL
+    int32_t* count_filt;          // NULL without a filter
+    int64_t* out_ids;
+    float* out_dist;
+};
+
+// k_transe_rank's predicates: nearer, or either side NaN; the key of gv_transe_topk
+struct TePairRelRule {
+    static __device__ __forceinline__ bool above(float d, float t) { return !(d >= t); }
+    static __device__ __forceinline__ unsigned long long key(float d, int col) { return topk_key(-d, col); }
+};
+
+template <int NK>                 // keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
+__global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams tp) {
+    __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
+    __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
+    __shared__ __attribute__((aligned(16))) float ds[TE_TQ * TE_LDD];     // the tile's distances, row-major
+    __shared__ unsigned long long thr[TE_TQ];                             // each row's k-th key
+    __shared__ int cur[TE_TQ], fhi[TE_TQ], nxt[TE_TQ];                    // filter cursor (k_topk.h)
+    __shared__ int fl[4][64];
+    __shared__ int s_s[TE_TQ], o_s[TE_TQ];                                // the rows' pairs (-1: no such row)
+    __shared__ int tcol_s[TE_TQ];                                         // the rows' targets (-1: none)
+    __shared__ float dt_s[TE_TQ];                                         // ... and their distances
+    __shared__ int cnt_s[2][TE_TQ];                                       // 2 #better + #equal: raw, filtered
+    extern __shared__ unsigned long long lists[];                         // [TE_TQ][topk]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, tx = tid & 15, ty = tid >> 4;
+    const int k = tp.topk, dim = tp.dim;
+    const int m0 = blockIdx.x * TE_TQ;
+    const int col_tiles = (tp.num_rels + TE_TE - 1) / TE_TE;
+    const bool filtered = tp.filt_lo != nullptr, ranked = tp.target != nullptr;
+    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, dt_s, cnt_s};
+    if constexpr (NK > 0)
+        for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
+    fl[wid][lane] = 0;
+    if (tid < TE_TQ) {
+        const int row = m0 + tid;
+        const bool live = row < tp.m;
+        const int a = live ? tp.s[row] : -1, b = live ? tp.o[row] : -1;
+        const int tc = (ranked && live) ? tp.target[row] : -1;
+        s_s[tid] = a; o_s[tid] = b; tcol_s[tid] = tc;
+        thr[tid] = 0ull;
+        cnt_s[0][tid] = 0; cnt_s[1][tid] = 0;
+        dt_s[tid] = __uint_as_float(0x7fc00000u);                         // a target outside [0, R) ranks last
+        topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_rel, tp.n_filt, filtered && live, row, 0, &cur[tid], &fhi[tid], &nxt[tid]);
+    }
+    auto q_at = [&](int row, int c) {
+        const int a = s_s[row];
+        if (a < 0 || c >= dim) return 0.f;
+        return tp.en[(size_t)o_s[row] * dim + c] - tp.en[(size_t)a * dim + c];
+    };
+    if (ranked && col_tiles > 1) {                 // the targets' distances: ONE gathered tile whose column j is rn[target of row j]
+        float acc[4][4];
+        te_tile_gather(                            // (its first barrier publishes the set-up above)
+            q_at,
+            [&](int row, int c) {
+                const int tc = tcol_s[row];
+                return ((unsigned)tc < (unsigned)tp.num_rels && c < dim) ? tp.rn[(size_t)tc * dim + c] : 0.f;
+            },
+            dim, tp.p, qs, es, acc);
+        if (tx == ty) {                            // element (j, j) is row j's own
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                if ((unsigned)tcol_s[4 * ty + a] < (unsigned)tp.num_rels) dt_s[4 * ty + a] = acc[a][a];
+        }
+    }
+    for (int t = 0; t < col_tiles; ++t) {
+        const int e0 = t * TE_TE;
+        float acc[4][4];
+        // te_tile_with's first barrier publishes the set-up above (and the gathered tile's dt_s) and ends the last tile's reads of ds
+        te_tile_with(q_at, tp.rn, tp.num_rels, dim, tp.p, e0, qs, es, acc);
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+            *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
+        __syncthreads();
+        if (ranked && col_tiles == 1) {            // the one tile holds every target
+            if (tid < TE_TQ && (unsigned)tcol_s[tid] < (unsigned)tp.num_rels) dt_s[tid] = ds[tid * TE_LDD + tcol_s[tid]];
+            __syncthreads();
+        }
+        topk_pair_rel_tile<NK, TePairRelRule>(st, m0, tp.m, e0, tp.num_rels, t, k, ranked, tp.filt_rel, lane, wid,
+                                              [&](int rl) { return ds[rl * TE_LDD + lane]; });
+    }
+    topk_pair_rel_store<NK, int64_t, te_key_dist>(st, m0, tp.m, k, ranked, tp.tgt, tp.count_raw, tp.count_filt, tp.out_ids, tp.out_dist,
+                                                  lane, wid);
+}
+
 }  // namespace gv
 
 using namespace gv;
@@ -1205,4 +1315,34 @@ extern "C" int gv_transe_entity_topk_typed(const int32_t* ents, int m, const flo
     // (<= 64 KiB of lists beside 38 KiB static: the limit is raised for either NK)
     return topk_span_merge<k_transe_entity_topk_typed_span<1>, k_transe_entity_topk_typed_span<2>, true, TE_TQ>(
         name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), pp, tp.part, m, tp.n_spans, k, out, GV_ST);
+}
+
+// ---- relation prediction (gv_transe_pair_rel): one launch, the checks of gv_pair_rel_scores in its order -------------------------
+extern "C" int gv_transe_pair_rel(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
+                                  const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
+                                  const int32_t* filt_rel, int n_filt_rel, int k, float* tgt, int32_t* count_raw, int32_t* count_filt,
+                                  int64_t* out_ids, float* out_dist, int m, void* stream) {
+    const char* name = "gv_transe_pair_rel";
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) && n_filt_rel >= 0,
+               GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_rel=%d", name, m, n, num_rels, dim,
+               GV_TRANSE_MAX_DIM, p_norm, n_filt_rel);
+    GV_CHECK(pair_query_asks(name, k, target));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_rel, "filt_lo / filt_hi / filt_rel"));
+    if (m == 0) return GV_OK;
+    GV_CHECK(pair_query_given(name, en && rn && s && o, target, tgt, k, out_ids, out_dist, filt_lo, count_filt));
+    const TePairRelParams tp{en, rn, s, o, target, filt_lo, filt_hi, filt_rel, m, num_rels, dim, p_norm, n_filt_rel, k, tgt,
+                             count_raw, filt_lo ? count_filt : nullptr, out_ids, out_dist};
+    constexpr int KEY = (int)sizeof(unsigned long long);
+    const dim3 grid((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ)), block(256);
+    static unsigned long long raised1 = 0, raised2 = 0;      // (<= 64 KiB of lists beside 38 KiB static: the limit is raised for either NK)
+    if (k == 0) {
+        hipLaunchKernelGGL(k_transe_pair_rel<0>, grid, block, 0, GV_ST, tp);
+    } else if (k <= 64) {
+        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<1>, TE_TQ * 64 * KEY, raised1, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_transe_pair_rel<1>, grid, block, TE_TQ * k * KEY, GV_ST, tp);
+    } else {
+        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<2>, TE_TQ * TOPK_MAX * KEY, raised2, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL(k_transe_pair_rel<2>, grid, block, TE_TQ * k * KEY, GV_ST, tp);
+    }
+    return launch_status(name);
 }

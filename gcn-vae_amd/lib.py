@@ -118,6 +118,8 @@ SIGNATURES = {
     'gv_entity_topk_scores_mc': (_I, [_P, _I, _P, _I, _L, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     'gv_entity_topk_scores_typed_mc': (_I, [_P, _I, _P, _I, _L, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P,
                                             _P, _L, _I, _I, _I, _P]),
+    'gv_pair_rel_scores': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'gv_transe_pair_rel': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
     'gv_rank_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_topk_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_pair_prob_std_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _I, _P, _I, _I, _I, _P]),

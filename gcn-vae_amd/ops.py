@@ -624,11 +624,12 @@ def _ranks(counts, m, filt=True):
     return tuple(r[i] if filt or i % 2 == 0 else None for i in range(r.shape[0]))
 
 
-def _filter_args(filt_lo, filt_hi, filt_ent, m, v, device):
-    """The checks of ``rank_scores_filtered`` on an optional filter: (lo32, hi32, ent32, n_ent), all None / 0 without one."""
+def _filter_args(filt_lo, filt_hi, filt_ent, m, v, device, what='entity', last='filt_ent'):
+    """The checks of ``rank_scores_filtered`` on an optional filter: (lo32, hi32, ent32, n_ent), all None / 0 without one.
+    ``what`` / ``last``: what the listed ids are and how the caller names their array (the pair queries list relations)."""
     given = [t is not None for t in (filt_lo, filt_hi, filt_ent)]
     if any(given) and not all(given):
-        raise ValueError('filt_lo, filt_hi and filt_ent are given together or not at all')
+        raise ValueError(f'filt_lo, filt_hi and {last} are given together or not at all')
     if not all(given):
         return None, None, None, 0
     filt_lo, filt_hi, filt_ent = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_ent.reshape(-1)
@@ -636,11 +637,11 @@ def _filter_args(filt_lo, filt_hi, filt_ent, m, v, device):
         raise ValueError('one filter range (filt_lo, filt_hi) per query row')
     n_ent = filt_ent.numel()
     if n_ent >= 2 ** 31:
-        raise ValueError('filt_ent: more than 2**31 - 1 entries')
+        raise ValueError(f'{last}: more than 2**31 - 1 entries')
     if m and (int(filt_lo.min()) < 0 or int(filt_hi.max()) > n_ent or bool((filt_hi < filt_lo).any())):
         raise ValueError(f'filter ranges must satisfy 0 <= filt_lo <= filt_hi <= {n_ent}')
     if n_ent and (int(filt_ent.min()) < 0 or int(filt_ent.max()) >= v):
-        raise ValueError(f'filtered entity ids must lie in [0, {v})')
+        raise ValueError(f'filtered {what} ids must lie in [0, {v})')
     i32 = dict(device=device, dtype=torch.int32)
     ent32 = filt_ent.to(**i32).contiguous() if n_ent else torch.zeros(1, **i32)
     return filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous(), ent32, n_ent
@@ -836,6 +837,134 @@ def entity_topk_scores(ents, emb, w, k, bias=None, filt_lo=None, filt_hi=None, f
     rule -- the result does not depend on it.  Returns ``(rel int64 (m, k), ent int64 (m, k), logits float32 (m, k))``, padded
     with -1 / -1 / -inf past a row's last candidate; -0 is reported as +0 and every NaN as the one quiet NaN."""
     return _entity_topk('gv_entity_topk_scores', ents, emb, w, k, bias, (filt_lo, filt_hi, filt_ent), exclude_self, span)
+
+
+def _pair_args(table, rels, names, s, o, target, k, filt, p_norm=None, ids_checked=False):
+    """What the two pair queries check ahead of any look at a device, in their one order: the operands' shapes, the pairs, k
+    (0: no top-k), that something is asked for, the pairs' range, [the norm and the width,] the targets and the filter over the
+    relations.  ``ids_checked``: the caller vouches for every id's range (``pair_ids_check``), so the device-to-host reads behind
+    those checks are not made; the shapes are still checked.  Returns (m, n, num_rels, h, k, tgt32 or None, ``_filter_args``' tuple)."""
+    tname, rname = names
+    for name, t in ((tname, table), (rname, rels)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise TypeError(f'{name}: expected a 2-D tensor')
+    for name, t in (('s', s), ('o', o)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.is_floating_point() or t.dtype == torch.bool:
+            raise TypeError(f'{name}: expected a 1-D integer tensor of entity ids')
+    if table.shape[1] != rels.shape[1]:
+        raise ValueError(f'{tname} / {rname} width mismatch')
+    n, num_rels, h = table.shape[0], rels.shape[0], table.shape[1]
+    if n < 1 or num_rels < 1 or h < 1:
+        raise ValueError(f'need at least one entity, one relation and width >= 1 (n={n}, num_rels={num_rels}, h={h})')
+    m = s.numel()
+    if o.numel() != m:
+        raise ValueError('one object per subject: s and o are the two columns of the pairs')
+    k = int(k)
+    if not 0 <= k <= TOPK_MAX:
+        raise ValueError(f'k must lie in [0, {TOPK_MAX}] (0: no top-k), got {k}')
+    if target is None and k == 0:
+        raise ValueError('nothing asked for: give target (ranks), k >= 1 (top-k) or both')
+    if m and not ids_checked:
+        lo, hi = torch.aminmax(torch.stack((s.long(), o.to(s.device).long())))
+        lo, hi = torch.stack((lo, hi)).tolist()                     # (one host round trip for both columns)
+        if lo < 0 or hi >= n:
+            raise ValueError(f'pair entities must lie in [0, {n})')
+    if p_norm is not None:
+        _p_norm(p_norm)
+        if h > TRANSE_MAX_DIM:
+            raise ValueError(f'{tname} / {rname}: width {h} above {TRANSE_MAX_DIM}')
+    dev = table.device
+    if ids_checked:
+        return m, n, num_rels, h, k, _pair_target_unread(target, m, dev), _pair_filter_unread(*filt, m, dev)
+    tgt32 = None if target is None else _target_args(target, m, num_rels, dev)
+    return m, n, num_rels, h, k, tgt32, _filter_args(*filt, m, num_rels, dev, 'relation', 'filt_rel')
+
+
+def _pair_target_unread(target, m, device):
+    """``_target_args`` without its look at the values."""
+    if target is None:
+        return None
+    target = target.reshape(-1)
+    if target.numel() != m:
+        raise ValueError('one target per query row')
+    return target.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _pair_filter_unread(filt_lo, filt_hi, filt_rel, m, device):
+    """``_filter_args`` without its looks at the values (the kernels clamp every range into the list on their own)."""
+    given = [t is not None for t in (filt_lo, filt_hi, filt_rel)]
+    if any(given) and not all(given):
+        raise ValueError('filt_lo, filt_hi and filt_rel are given together or not at all')
+    if not all(given):
+        return None, None, None, 0
+    filt_lo, filt_hi, filt_rel = filt_lo.reshape(-1), filt_hi.reshape(-1), filt_rel.reshape(-1)
+    if filt_lo.numel() != m or filt_hi.numel() != m:
+        raise ValueError('one filter range (filt_lo, filt_hi) per query row')
+    n_rel = filt_rel.numel()
+    if n_rel >= 2 ** 31:
+        raise ValueError('filt_rel: more than 2**31 - 1 entries')
+    i32 = dict(device=device, dtype=torch.int32)
+    rel32 = filt_rel.to(**i32).contiguous() if n_rel else torch.zeros(1, **i32)
+    return filt_lo.to(**i32).contiguous(), filt_hi.to(**i32).contiguous(), rel32, n_rel
+
+
+def pair_ids_check(s, o, target, n, num_rels):
+    """The range checks of the pair queries on a whole query set, in ONE device-to-host read: every entity of ``s`` / ``o`` in
+    [0, n), every target (when given) in [0, num_rels).  A chunked driver makes it once and passes ``ids_checked=True`` with each
+    chunk; a filter built by ``ranking.PairFilterIndex`` for the same sizes is in range by construction."""
+    if not s.numel():
+        return
+    ends = [torch.aminmax(torch.stack((s.long(), o.to(s.device).long())))]
+    if target is not None:
+        ends.append(torch.aminmax(target.to(s.device).long()))
+    ends = torch.stack([x for pair in ends for x in pair]).tolist()
+    if ends[0] < 0 or ends[1] >= n:
+        raise ValueError(f'pair entities must lie in [0, {n})')
+    if target is not None and (ends[2] < 0 or ends[3] >= num_rels):
+        raise ValueError(f'targets must lie in [0, {num_rels})')
+
+
+def _pair_buffers(m, k, ranked, id_dtype, dev):
+    """The outputs of a pair query: (tgt, counts (2, m) or None, ids (m, k), values (m, k))."""
+    tgt = torch.empty(max(m, 1), dtype=torch.float32, device=dev) if ranked else None
+    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=dev) if ranked else None
+    return tgt, counts, torch.empty(m, k, dtype=id_dtype, device=dev), torch.empty(m, k, dtype=torch.float32, device=dev)
+
+
+def _pair_result(counts, m, given, k, ids, values):
+    """(ranks, topk): ``(raw, filtered or None)`` as ``rank_scores_filtered`` returns them, or None without targets; ``(ids int64
+    (m, k), values float32 (m, k))``, or None with k == 0."""
+    return (None if counts is None else _ranks(counts, m, given)), (None if k == 0 else (ids.long(), values))
+
+
+def pair_relation_scores(emb, w, s, o, *, target=None, k=0, bias=None, filt_lo=None, filt_hi=None, filt_rel=None, ids_checked=False):
+    """Relation prediction: for every entity pair ``(s[i], o[i])`` the relations under ``logit[i, r] = (emb[s_i] * emb[o_i]) . w[r]
+    (+ bias)`` -- bit for bit ``gemm(mul(emb[s], emb[o]), w^T, precision='f32') + bias`` -- from ONE launch without a workspace
+    (gv_pair_rel_scores): a workgroup owns 64 pairs and walks every 64-relation tile itself, and the (m, h) product matrix is
+    never stored.  With ``target`` (one relation per pair): the 0-based mid-ranks of the target among all relations, raw and --
+    with a filter -- with the relations ``filt_rel[filt_lo[i]:filt_hi[i]]`` left out of the count (sorted ascending and unique
+    inside each range, ``ranking.PairFilterIndex`` builds them; a listed target is allowed), by the definition, tie rule and NaN
+    rule of ``rank_scores_filtered``.  With ``k >= 1``: the k best relations in ``topk_scores``' order (logit descending, equal
+    logits by lower id, NaN last), the listed ones left out, padded with id -1 / logit -inf; -0 is reported as +0 and every NaN
+    as the one quiet NaN.  Returns ``(ranks, topk)``: ``(raw, filtered or None)`` or None without ``target``; ``(ids int64 (m, k),
+    logits float32 (m, k))`` or None with ``k == 0``.  Pair ids outside the table are refused here: the kernel trusts them.
+    ``ids_checked=True`` skips the reads behind the range checks of pairs, targets and filter for a caller that has made them
+    (``pair_ids_check``: the chunked drivers check a whole query set once)."""
+    m, n, num_rels, h, k, tgt32, (lo32, hi32, rel32, n_rel) = _pair_args(emb, w, ('emb', 'w'), s, o, target, k, (filt_lo, filt_hi, filt_rel),
+                                                                         ids_checked=ids_checked)
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev = emb.device
+    if w.device != dev:
+        raise ValueError(f'emb on {dev}, w on {w.device}')
+    tgt, counts, ids, values = _pair_buffers(m, k, tgt32 is not None, torch.int32, dev)
+    given = lo32 is not None
+    if m:
+        s32, o32 = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (s, o))
+        lib.call('gv_pair_rel_scores', ptr(emb), ld_e, n, ptr(w), ld_w, num_rels, ptr(s32), ptr(o32), ptr(tgt32), ptr(_bias_arg(bias)),
+                 ptr(lo32), ptr(hi32), ptr(rel32), n_rel, k, ptr(tgt), None if counts is None else ptr(counts[0]),
+                 ptr(counts[1]) if given and counts is not None else None, ptr(ids), ptr(values), m, h, lib.stream())
+    return _pair_result(counts, m, given, k, ids, values)
 
 
 def entity_typed_plan(set_ptr, num_rels, side='s'):
@@ -3875,6 +4004,29 @@ def _transe_entity_topk(entry, ents, en, rn, k, p_norm, head, filt, exclude_self
     lib.call(entry, ptr(ents32), m, ptr(en), ptr(rn), n, num_rels, dim, int(bool(head)), p_norm, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
              *lists, int(bool(exclude_self)), k, span_tiles, ptr(rel), ptr(other), ptr(dist), ptr(ws), ws_bytes, lib.stream())
     return rel, other, dist
+
+
+def transe_pair_relations(en, rn, s, o, p_norm, *, target=None, k=0, filt_lo=None, filt_hi=None, filt_rel=None, ids_checked=False):
+    """Relation prediction for TransE: ``pair_relation_scores`` on distances, smaller is better (gv_transe_pair_rel, one launch, no
+    workspace).  ``d[i, r] = ||(en[o_i] - en[s_i]) - rn[r]||_p`` on the dense tables ``transe_entity_topk`` takes -- bit for bit
+    ``transe_distances(en[o] - en[s], rn, p_norm)``; in exact arithmetic the triplet's ``||n(s) + n(r) - n(o)||``, but NOT the bit
+    pattern ``transe_topk`` reports for the same triplet, which associates the operands the other way.  Ranks follow
+    ``transe_rank_filtered``'s rule, the top-k ``transe_topk``'s order (distance ascending, equal distances by lower id, NaN after
+    +inf), padded with id -1 / distance +inf.  ``ids_checked`` and the returned ``(ranks, topk)`` are ``pair_relation_scores``'."""
+    m, n, num_rels, dim, k, tgt32, (lo32, hi32, rel32, n_rel) = _pair_args(en, rn, ('en', 'rn'), s, o, target, k,
+                                                                           (filt_lo, filt_hi, filt_rel), p_norm, ids_checked)
+    en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
+    dev = en.device
+    if rn.device != dev:
+        raise ValueError(f'en on {dev}, rn on {rn.device}')
+    tgt, counts, ids, dist = _pair_buffers(m, k, tgt32 is not None, torch.int64, dev)
+    given = lo32 is not None
+    if m:
+        s32, o32 = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (s, o))
+        lib.call('gv_transe_pair_rel', ptr(en), ptr(rn), n, num_rels, dim, int(p_norm), ptr(s32), ptr(o32), ptr(tgt32), ptr(lo32), ptr(hi32),
+                 ptr(rel32), n_rel, k, ptr(tgt), None if counts is None else ptr(counts[0]),
+                 ptr(counts[1]) if given and counts is not None else None, ptr(ids), ptr(dist), m, lib.stream())
+    return _pair_result(counts, m, given, k, ids, dist)
 
 
 def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,

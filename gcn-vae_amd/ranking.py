@@ -48,6 +48,13 @@ type-correct triplets on pbar, and ``complete_entities_mc`` is per-entity comple
 (``ops.entity_topk_scores_mc`` / ``ops.entity_topk_scores_typed_mc``: the sample loop inside each (relation, tile), one selection
 per tile), with the mean and the spread of every returned fact; ``complete_entities_mc_from_probs`` states its rule on
 materialised probabilities and ``complete_entities_mc_unfused`` is the cross-check.
+
+Relation prediction (how are two entities related? -- the query is a pair (s, ?, o), the candidates are the relations):
+``rank_relations`` / ``calc_relation_mrr`` rank the true relation among all relations, raw and -- with a ``PairFilterIndex`` of the
+pairs' known relations -- filtered, and ``predict_relations`` proposes the k best new ones, from ``ops.pair_relation_scores``
+(gv_pair_rel_scores: one launch, the product row e_s * e_o formed while it is staged, every relation tile walked by the workgroup
+that owns the pairs).  ``relation_ranks_from_scores`` / ``topk_from_scores`` state the rules on a materialised (m, R) matrix; the
+``*_unfused`` routes are the GEMM cross-check.
 """
 import torch
 
@@ -1192,3 +1199,158 @@ def calc_mrr(embedding, w, test_triplets, hits=[], eval_bz=100, all_batches=True
                                       (perturb_and_get_rank(embedding, w, a, r, b, n, eval_bz, all_batches, flow_log_prob),))
         # Hits@k are printed, never returned: not computed when nothing is printed
         return _report(by_s, by_o, CONSTRAINED_KINDS[:1], hits if verbose else (), verbose, MRR_LINES)['mrr_raw']
+
+
+# ---- relation prediction: the query is an entity pair (s, ?, o), the candidates are the relations -----------------------------
+RELATION_MRR_LINES = ("Relation MRR ({0}): {1:.6f}", "Relation Hits ({0}) @ {1}: {2:.6f}")
+
+
+class PairFilterIndex:
+    """The known relations of every entity pair, built once per dataset: key ``s * num_nodes + o`` (int64: num_nodes ** 2 passes
+    2**31 from 46 341 entities on) -> the sorted unique relations r with (s, r, o) known.  ``keys`` (int64) and ``rel`` (int32) are
+    parallel arrays sorted by (key, relation), duplicate triplets once: the relations of one pair are a contiguous run of ``rel``,
+    which is the (filt_lo, filt_hi, filt_rel) form ``ops.pair_relation_scores`` takes.  Built with torch ops on ``device``."""
+
+    def __init__(self, num_nodes, num_rels, *triplet_sets, device='cpu'):
+        self.num_nodes, self.num_rels, self.device = int(num_nodes), int(num_rels), torch.device(device)
+        parts = [torch.as_tensor(t).to(device=self.device, dtype=torch.long).reshape(-1, 3) for t in triplet_sets]
+        trip = torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.long, device=self.device)
+        if trip.numel() and (int(trip[:, [0, 2]].min()) < 0 or int(trip[:, [0, 2]].max()) >= self.num_nodes
+                             or int(trip[:, 1].min()) < 0 or int(trip[:, 1].max()) >= self.num_rels):
+            raise ValueError('triplets out of range of num_nodes / num_rels')
+        key, r = trip[:, 0] * self.num_nodes + trip[:, 2], trip[:, 1]
+        order = torch.argsort(r, stable=True)
+        order = order[torch.argsort(key[order], stable=True)]               # by (key, relation)
+        k, x = key[order], r[order]
+        keep = torch.ones_like(k, dtype=torch.bool)
+        if k.numel() > 1:
+            keep[1:] = (k[1:] != k[:-1]) | (x[1:] != x[:-1])                  # duplicate triplets once
+        self.keys, self.rel = k[keep].contiguous(), x[keep].to(torch.int32).contiguous()
+        if max(self.rel.numel(), 1) >= 2 ** 31:
+            raise ValueError('more than 2**31 - 1 distinct triplets')
+
+    def lookup(self, s, o):
+        """(lo, hi): the range of ``rel`` holding the known relations of each pair (s[i], o[i]), on ``s``'s device."""
+        q = s.to(device=self.device, dtype=torch.long) * self.num_nodes + o.to(device=self.device, dtype=torch.long)
+        lo = torch.searchsorted(self.keys, q, right=False)
+        hi = torch.searchsorted(self.keys, q, right=True)
+        return lo.to(s.device), hi.to(s.device)
+
+    def relations(self, device=None):
+        return self.rel if device is None else self.rel.to(device)
+
+
+def _pair_checked(s, o, target, n, num_rels, pair_filter):
+    """The id checks of a whole query set, once (``ops.pair_ids_check``: one device-to-host read), so that no chunk repeats them;
+    a ``pair_filter`` vouches for its ranges only when it was built for these sizes."""
+    if pair_filter is not None and (pair_filter.num_nodes != n or pair_filter.num_rels != num_rels):
+        raise ValueError(f'pair_filter was built for {pair_filter.num_nodes} entities / {pair_filter.num_rels} relations, the tables '
+                         f'hold {n} / {num_rels}')
+    ops.pair_ids_check(s, o, target, n, num_rels)
+
+
+def _pair_chunks(s, o, pair_filter, device, step):
+    """The chunk loop of the pair queries, once: ``(slice, filt_lo, filt_hi, filt_rel)`` for every ``step`` pairs, the filter's
+    three None without a ``pair_filter``."""
+    rel = pair_filter.relations(device) if pair_filter is not None else None
+    for lo in range(0, s.shape[0], step):
+        sl = slice(lo, min(s.shape[0], lo + step))
+        f_lo, f_hi = pair_filter.lookup(s[sl], o[sl]) if pair_filter is not None else (None, None)
+        yield sl, f_lo, f_hi, rel
+
+
+def pair_scores_unfused(emb, w, s, o, flow_log_prob=None):
+    """The materialised (m, R) logits of the pairs: one product of the gathered rows, one fp32 GEMM against the relation table."""
+    score = ops.gemm(ops.mul(emb[s].contiguous(), emb[o].contiguous()), w, trans_b=True, precision='f32')
+    return score if flow_log_prob is None else score + flow_log_prob
+
+
+def relation_ranks_from_scores(score, target, filt_lo=None, filt_hi=None, filt_rel=None):
+    """The rank rule of ``ops.pair_relation_scores`` on a materialised (m, R) matrix, higher is better, in plain torch (any
+    device): ``mid_ranks`` with the relations ``filt_rel[filt_lo[i]:filt_hi[i]]`` left out of the filtered count (a listed target
+    is allowed: the target is left out of every pool anyway).  Returns (raw, filtered or None)."""
+    listed = None if filt_lo is None else _listed_mask(filt_lo, filt_hi, filt_rel, score.shape[0], score.shape[1], score.device)
+    return mid_ranks(score, target.to(score.device), listed)[:2]
+
+
+def _pair_cat(parts, width, dtype, device):
+    return torch.cat(parts) if parts else torch.zeros((0,) + width, dtype=dtype, device=device)
+
+
+def _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, fused):
+    emb = embedding.detach().contiguous()
+    wd, flow_log_prob = _on_device(emb, w.detach(), flow_log_prob)
+    triplets = triplets.to(emb.device)
+    s, r, o = triplets[:, 0], triplets[:, 1], triplets[:, 2]
+    _pair_checked(s, o, r, emb.shape[0], wd.shape[0], pair_filter)
+    raw, filt = [], []
+    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, emb.device, MAX_QUERY_ROWS):
+        if fused:
+            a, b = ops.pair_relation_scores(emb, wd, s[sl], o[sl], target=r[sl], bias=flow_log_prob, filt_lo=f_lo, filt_hi=f_hi,
+                                            filt_rel=rel, ids_checked=True)[0]
+        else:
+            a, b = relation_ranks_from_scores(pair_scores_unfused(emb, wd, s[sl], o[sl], flow_log_prob), r[sl], f_lo, f_hi, rel)
+        raw.append(a)
+        filt.append(b)
+    return (_pair_cat(raw, (), torch.float32, emb.device),
+            None if pair_filter is None else _pair_cat(filt, (), torch.float32, emb.device))
+
+
+def rank_relations(embedding, w, triplets, pair_filter=None, flow_log_prob=None):
+    """Relation prediction, ranks: for every triplet (s, r, o) the 0-based mid-rank of r among ALL relations under ``logit =
+    (e_s * e_o) . w_r + flow_log_prob`` -- DistMult's score of the triplet, read as a function of the relation -- raw and, with a
+    ``PairFilterIndex``, with the other known relations of the pair left out.  One launch per ``MAX_QUERY_ROWS`` pairs
+    (ops.pair_relation_scores).  Returns ``(raw, filtered or None)``."""
+    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, True)
+
+
+def rank_relations_unfused(embedding, w, triplets, pair_filter=None, flow_log_prob=None):
+    """``rank_relations`` from materialised logits (``pair_scores_unfused`` + ``mid_ranks``): the in-repo cross-check and the
+    bench's comparator, never a fallback."""
+    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, False)
+
+
+def _calc_relation_mrr(rank, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose):
+    with torch.no_grad():
+        raw, filt = rank(embedding, w, test_triplets, pair_filter, flow_log_prob)
+        none = [raw.new_zeros(0), None if filt is None else raw.new_zeros(0)]       # one direction: nothing on _report's other side
+        return _report([raw, filt], none, CONSTRAINED_KINDS[:2], hits, verbose, RELATION_MRR_LINES)
+
+
+def calc_relation_mrr(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True):
+    """The relation-prediction report over the test triplets (one direction: there is one relation slot): ``mrr_raw`` and
+    ``hits_raw: {k: v}``, and with a ``PairFilterIndex`` ``mrr_filtered`` / ``hits_filtered``."""
+    return _calc_relation_mrr(rank_relations, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose)
+
+
+def calc_relation_mrr_unfused(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True):
+    return _calc_relation_mrr(rank_relations_unfused, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose)
+
+
+def _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, fused):
+    emb = embedding.detach().contiguous()
+    wd, flow_log_prob = _on_device(emb, w.detach(), flow_log_prob)
+    s, o = s.to(emb.device), o.to(emb.device)
+    _pair_checked(s, o, None, emb.shape[0], wd.shape[0], pair_filter)
+    ids, logits = [], []
+    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, emb.device, MAX_QUERY_ROWS):
+        if fused:
+            i, l = ops.pair_relation_scores(emb, wd, s[sl], o[sl], k=k, bias=flow_log_prob, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
+                                            ids_checked=True)[1]
+        else:
+            i, l = topk_from_scores(pair_scores_unfused(emb, wd, s[sl], o[sl], flow_log_prob), k, f_lo, f_hi, rel)
+        ids.append(i)
+        logits.append(l)
+    return _pair_cat(ids, (int(k),), torch.int64, emb.device), _pair_cat(logits, (int(k),), torch.float32, emb.device)
+
+
+def predict_relations(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None):
+    """Relation prediction, proposals: the ``k`` most plausible relations between ``s[i]`` and ``o[i]`` at ``rank_relations``'
+    logits, the pair's known relations (``pair_filter``) left out.  Returns ``(ids int64 (n, k), logits float32 (n, k))`` in the
+    order of ``topk_from_scores``, padded with -1 / -inf when fewer than k relations are left."""
+    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, True)
+
+
+def predict_relations_unfused(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None):
+    """``predict_relations`` from materialised logits (``pair_scores_unfused`` + ``topk_from_scores``): cross-check and comparator."""
+    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, False)

@@ -215,6 +215,30 @@ def write_profile_lines(path, entities, route, rows=PROFILE_ROWS):
     return n_lines
 
 
+def write_relation_lines(path, triplets, route, rows=PROFILE_ROWS):
+    """The loop of the relation-prediction writers (this file's and transe.py's): one block per triplet, in order, ``rows`` pairs per
+    call of ``route(s, o)`` -> ``(ids, values)`` (each (m, k), best first), as TSV ``subject  object  position  predicted_relation
+    value`` -- the formatting of the top-k prediction files (position from 0, the value as ``:.9g``, padding slots written with
+    their id -1).  Returns the number of lines written."""
+    n_lines = 0
+    with torch.no_grad(), open(path, 'w') as f:
+        for at in range(0, triplets.shape[0], rows):
+            s, o = triplets[at:at + rows, 0], triplets[at:at + rows, 2]
+            ids, values = route(s, o)
+            for a, b, row_ids, row_values in zip(s.tolist(), o.tolist(), ids.tolist(), values.tolist()):
+                head = f"{a}\t{b}\t"
+                f.writelines(f"{head}{p}\t{e}\t{x:.9g}\n" for p, (e, x) in enumerate(zip(row_ids, row_values)))
+                n_lines += len(row_ids)
+    return n_lines
+
+
+def write_relation_predictions(path, embed, w, triplets, k, pair_filter, flow_log_prob=None):
+    """The ``k`` most plausible NEW relations of every triplet's pair (ranking.predict_relations; ``pair_filter``: the pair's known
+    relations left out) as TSV: ``subject  object  position  predicted_relation  logit``, one block of k lines per triplet, in
+    order; a pair with fewer than k relations left ends in id -1, logit -inf.  Returns the number of lines written."""
+    return write_relation_lines(path, triplets, lambda s, o: ranking.predict_relations(embed, w, s, o, k, pair_filter, flow_log_prob))
+
+
 def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None, type_constraint=None):
     """Per-entity completion as TSV, ``entity  side  relation  other_entity  rank  logit  probability``: for every entity of
     ``entities`` its ``k`` most likely new facts over all relations (ranking.complete_entities; ``filter_index``: the known ones
@@ -303,7 +327,11 @@ def check_args(args):
         raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
     if getattr(args, 'profile_typed', False) and not getattr(args, 'profile_topk', 0) > 0:
         raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
-    wants = [f for f, on in (('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
+    if not 0 <= getattr(args, 'predict_relations', 0) <= ops.TOPK_MAX:
+        raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
+    wants = [f for f, on in (('--relation-eval', getattr(args, 'relation_eval', False)),
+                             ('--predict-relations', getattr(args, 'predict_relations', 0) > 0),
+                             ('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
                              ('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
                              ('--complete-threshold', getattr(args, 'complete_threshold', None) is not None),
                              ('--sample-graph', getattr(args, 'sample_graph', 0) > 0)) if on]
@@ -420,6 +448,16 @@ def main(args):
                                             model.encoder.get_flow_log_prob(), typed)
             print(f"wrote {n_lines} new {'type-correct ' if typed is not None else ''}facts around {len(who)} entities (top "
                   f"{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}")
+        if getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0:
+            pairs = ranking.PairFilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            if getattr(args, 'relation_eval', False):
+                ranking.calc_relation_mrr(embed, model.w_relation, test_t, pairs if filters is not None else None, hits=[1, 3, 10],
+                                          flow_log_prob=model.encoder.get_flow_log_prob())
+            if getattr(args, 'predict_relations', 0) > 0:
+                n_lines = write_relation_predictions(args.relations_out, embed, model.w_relation, test_t, args.predict_relations,
+                                                     pairs, model.encoder.get_flow_log_prob())
+                print(f"wrote {n_lines} relation predictions (top {args.predict_relations} per test pair, known relations filtered) "
+                      f"to {args.relations_out}")
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -673,6 +711,15 @@ def build_parser():
     p.add_argument("--mc-complete-out", type=str, default="mc_completions.tsv",
                    help="TSV of --mc-complete: subject, relation, object, rank (the columns of --complete-out), then the mean and "
                         "the standard deviation over the samples of the triplet's probability")
+    p.add_argument("--relation-eval", action="store_true",
+                   help="with --test-mode: also report relation prediction over the test triplets -- MRR / Hits@k of the true "
+                        "relation of (s, ?, o) among all relations; with --filtered-eval also with the pair's other known relations "
+                        "(train + valid + test) left out; not a reference flag")
+    p.add_argument("--predict-relations", type=int, default=0,
+                   help="with --test-mode: write the K (1..128) most plausible NEW relations between subject and object of every test "
+                        "triplet (the pair's train + valid + test relations left out) to --relations-out; 0 = off")
+    p.add_argument("--relations-out", type=str, default="relation_predictions.tsv",
+                   help="TSV of --predict-relations: subject, object, position, predicted relation, logit")
     p.add_argument("--profile-topk", type=int, default=0,
                    help="with --test-mode: for every entity of --profile-entities write its K most likely NEW facts over all "
                         "relations at once, the entity as subject and as object (train + valid + test triplets and loops left "

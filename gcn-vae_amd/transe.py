@@ -65,6 +65,15 @@ profile layout, the distance in place of the logit and probability.  With a ``ty
 type-correct facts are candidates, from ``ops.transe_entity_topk_typed`` (gv_transe_entity_topk_typed: the relations' candidate
 member lists are walked, rows gathered through the ids).
 
+Relation prediction: ``rank_relations`` / ``evaluate_relations`` rank the true relation of every pair (s, ?, o) among all relations
+at distance ``||(n(o) - n(s)) - n(r)||_p`` -- in exact arithmetic the triplet's distance, though not ``predict_topk``'s bit pattern
+for it: the operands are associated differently --, raw and with a ``ranking.PairFilterIndex`` filtered, and
+``predict_relations`` proposes the k nearest new relations of a pair, from ``ops.transe_pair_relations`` (gv_transe_pair_rel: one
+launch, the query row formed while it is staged, every relation tile walked by the workgroup that owns the pairs).  The
+``*_unfused`` twins (``ops.transe_distances`` + ``topk_from_distances``) are the cross-check.  ``--relation-eval`` adds the report
+(with ``--filtered-eval`` the filtered figures too), ``--predict-relations K --relations-out FILE`` write train.py's relation TSV
+layout, the distance in place of the logit.  Relation-corrupted training negatives (``--neg-rel``) stay refused.
+
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --filtered-eval
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --predict-topk 10 --predict-out transe.tsv
     python -m gcn_vae_amd.transe -d FB15k-237-synthetic --gpu 0 --train-times 5 --optimizer adam --alpha 0.001 --graph-step
@@ -80,8 +89,9 @@ import torch.nn.functional as F
 from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
                       UNCONSTRAINED, _complete_constraint, _complete_mask_args, _complete_queries, _complete_side, _complete_unfused,
-                      _mine_unfused, complete_entities_from_scores, mid_ranks, rank_from_scores_constrained, topk_from_scores)
-from .train import profile_entities_arg, write_profile_lines
+                      _mine_unfused, complete_entities_from_scores, mid_ranks, rank_from_scores_constrained, topk_from_scores,
+                      PairFilterIndex, _pair_cat, _pair_checked, _pair_chunks, relation_ranks_from_scores)
+from .train import profile_entities_arg, write_profile_lines, write_relation_lines
 
 
 # ------------------------------------------------------------------------------------------------
@@ -647,6 +657,110 @@ def _write_rows(f, direction, a, r, ids, values):
 
 
 # ------------------------------------------------------------------------------------------------
+# relation prediction: the query is an entity pair (s, ?, o), the candidates are the relations
+# ------------------------------------------------------------------------------------------------
+def _pair_tables(model_or_tables):
+    """(en, rn, p_norm): the two tables normalised by ``ops.transe_queries(table, norm_flag=)``, once per call."""
+    ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+    return (ops.transe_queries(ent.contiguous(), norm_flag=norm_flag), ops.transe_queries(rel.contiguous(), norm_flag=norm_flag),
+            p_norm)
+
+
+def pair_distances_unfused(en, rn, s, o, p_norm):
+    """The materialised (m, R) distances of the pairs: the query rows ``en[o] - en[s]`` (one fp32 subtraction per element, the
+    value the fused kernel stages) against the relation table."""
+    return ops.transe_distances((en[o] - en[s]).contiguous(), rn, p_norm)
+
+
+def _rank_relations(model_or_tables, triplets, pair_filter, fused):
+    with torch.no_grad():
+        en, rn, p_norm = _pair_tables(model_or_tables)
+        if not isinstance(triplets, torch.Tensor):
+            triplets = torch.as_tensor(np.asarray(triplets))
+        triplets = triplets.to(device=en.device, dtype=torch.long).reshape(-1, 3)
+        s, r, o = triplets[:, 0], triplets[:, 1], triplets[:, 2]
+        _pair_checked(s, o, r, en.shape[0], rn.shape[0], pair_filter)
+        raw, filt = [], []
+        for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, en.device, MAX_QUERY_ROWS):
+            if fused:
+                a, b = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, target=r[sl], filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
+                                                 ids_checked=True)[0]
+            else:
+                a, b = relation_ranks_from_scores(-pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), r[sl], f_lo, f_hi, rel)
+            raw.append(a)
+            filt.append(b)
+        return (_pair_cat(raw, (), torch.float32, en.device),
+                None if pair_filter is None else _pair_cat(filt, (), torch.float32, en.device))
+
+
+def rank_relations(model_or_tables, triplets, pair_filter=None):
+    """Relation prediction, ranks: for every triplet (s, r, o) the 0-based mid-rank of r among ALL relations at distance
+    ``||(n(o) - n(s)) - n(r)||_p`` -- in exact arithmetic the triplet's ``||n(s) + n(r) - n(o)||``, though not the bit pattern
+    ``predict_topk`` reports for it (the operands are associated differently) -- raw and, with a ``ranking.PairFilterIndex``,
+    with the pair's other known relations left out.  One launch per ``MAX_QUERY_ROWS`` pairs (ops.transe_pair_relations).
+    Returns ``(raw, filtered or None)``."""
+    return _rank_relations(model_or_tables, triplets, pair_filter, True)
+
+
+def rank_relations_unfused(model_or_tables, triplets, pair_filter=None):
+    """``rank_relations`` from materialised distances (``ops.transe_distances`` + ``ranking.mid_ranks``): the in-repo cross-check
+    and the bench's comparator, never a fallback."""
+    return _rank_relations(model_or_tables, triplets, pair_filter, False)
+
+
+def evaluate_relations(model_or_tables, triplets, pair_filter=None, hits=(1, 3, 10), unfused=False, verbose=True):
+    """The relation-prediction report (one direction: there is one relation slot): {'mrr_raw', 'mr_raw', 'hits_raw': {k: v}} plus
+    the same '_filtered' keys with a ``ranking.PairFilterIndex`` -- ``evaluate``'s key style."""
+    raw, filt = (rank_relations_unfused if unfused else rank_relations)(model_or_tables, triplets, pair_filter)
+    out = _summary(raw, raw if filt is None else filt, hits)
+    if filt is None:
+        out = {k: v for k, v in out.items() if '_filtered' not in k}
+    if verbose:
+        for kind in ('raw', 'filtered') if filt is not None else ('raw',):
+            print('Relation MRR ({}): {:.6f} | MR ({}): {:.3f}'.format(kind, out['mrr_' + kind], kind, out['mr_' + kind]))
+            for h in hits:
+                print('Relation Hits ({}) @ {}: {:.6f}'.format(kind, h, out['hits_' + kind][h]))
+    return out
+
+
+def _predict_relations(model_or_tables, s, o, k, pair_filter, fused):
+    with torch.no_grad():
+        en, rn, p_norm = _pair_tables(model_or_tables)
+        s, o = s.to(en.device), o.to(en.device)
+        _pair_checked(s, o, None, en.shape[0], rn.shape[0], pair_filter)
+        ids, dist = [], []
+        for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, en.device, MAX_QUERY_ROWS):
+            if fused:
+                i, d = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, k=k, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
+                                                 ids_checked=True)[1]
+            else:
+                i, d = topk_from_distances(pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), k, f_lo, f_hi, rel)
+            ids.append(i)
+            dist.append(d)
+        return _pair_cat(ids, (int(k),), torch.int64, en.device), _pair_cat(dist, (int(k),), torch.float32, en.device)
+
+
+def predict_relations(model_or_tables, s, o, k, pair_filter=None):
+    """Relation prediction, proposals: the ``k`` nearest relations between ``s[i]`` and ``o[i]`` at ``rank_relations``' distances,
+    the pair's known relations (``pair_filter``) left out.  Returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of
+    ``topk_from_distances``, padded with -1 / +inf when fewer than k relations are left."""
+    return _predict_relations(model_or_tables, s, o, k, pair_filter, True)
+
+
+def predict_relations_unfused(model_or_tables, s, o, k, pair_filter=None):
+    """``predict_relations`` from materialised distances (``ops.transe_distances`` + ``topk_from_distances``)."""
+    return _predict_relations(model_or_tables, s, o, k, pair_filter, False)
+
+
+def write_relation_predictions(path, model_or_tables, triplets, k, pair_filter):
+    """The ``k`` nearest NEW relations of every triplet's pair as TSV in train.py's layout: ``subject  object  position
+    predicted_relation  distance``, one block of k lines per triplet, in order; a pair with fewer than k relations left ends in
+    id -1, distance inf.  Returns the number of lines written."""
+    triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
+    return write_relation_lines(path, triplets, lambda s, o: predict_relations(model_or_tables, s, o, k, pair_filter))
+
+
+# ------------------------------------------------------------------------------------------------
 # completion: the whole graph's nearest new triplets
 # ------------------------------------------------------------------------------------------------
 def mine_from_distances(dist, *, k=None, threshold=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
@@ -877,6 +991,16 @@ def build_parser():
     p.add_argument('--complete-typed', action='store_true',
                    help='with --complete-topk / --complete-threshold: mine among type-correct triplets only (the subject seen as '
                         'subject, the object seen as object of the relation in train + valid + test); needs no --filtered-eval')
+    p.add_argument('--relation-eval', action='store_true',
+                   help='after the final evaluation also report relation prediction over the test triplets: MRR / MR / Hits@k of the '
+                        'true relation of (s, ?, o) among all relations; with --filtered-eval also with the pair\'s other known '
+                        'relations (train + valid + test) left out')
+    p.add_argument('--predict-relations', type=int, default=0,
+                   help='after the final evaluation write the K (1..128) nearest NEW relations between subject and object of every '
+                        'test triplet (the pair\'s train + valid + test relations left out) to --relations-out; 0 = off')
+    p.add_argument('--relations-out', type=str, default='transe_relation_predictions.tsv',
+                   help='TSV written by --predict-relations: subject, object, position, predicted relation, distance; the first four '
+                        'columns are those of train.py\'s --relations-out')
     p.add_argument('--profile-topk', type=int, default=0,
                    help='after the final evaluation write, for every entity of --profile-entities, its K nearest NEW facts over all '
                         'relations, as subject and as object (train + valid + test triplets and loops left out), to --profile-out; '
@@ -910,7 +1034,7 @@ def check_args(args):
     if (opt != 'sgd' or wd != 0) and not args.alpha >= 0:
         raise ValueError(f'--alpha must be >= 0 with --optimizer {opt} / --weight-decay, got {args.alpha}')
     if args.neg_rel != 0:
-        raise ValueError('--neg-rel: relation corruption is not supported')
+        raise ValueError('--neg-rel: relation corruption is not supported')       # (relation QUERIES exist: --relation-eval)
     if args.p_norm not in (1, 2):
         raise ValueError('--p-norm must be 1 or 2')
     if args.adv_temperature is not None and not args.adv_temperature > 0:
@@ -934,6 +1058,8 @@ def check_args(args):
         raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
     if getattr(args, 'profile_typed', False) and not getattr(args, 'profile_topk', 0) > 0:
         raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
+    if not 0 <= getattr(args, 'predict_relations', 0) <= ops.TOPK_MAX:
+        raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
 
 
 def main(args):
@@ -991,6 +1117,14 @@ def main(args):
         n_lines = write_completions(args.complete_out, model, known, args.complete_topk, args.complete_threshold, typed)
         print(f'wrote {n_lines} completions (nearest new {"type-correct " if typed is not None else ""}triplets of the whole graph, '
               f'known triplets filtered) to {args.complete_out}')
+    if getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0:
+        pairs = PairFilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        if getattr(args, 'relation_eval', False):
+            out['relations'] = evaluate_relations(model, data.test, pairs if args.filtered_eval else None)
+        if getattr(args, 'predict_relations', 0) > 0:
+            n_lines = write_relation_predictions(args.relations_out, model, data.test, args.predict_relations, pairs)
+            print(f'wrote {n_lines} relation predictions (nearest {args.predict_relations} per test pair, known relations filtered) to '
+                  f'{args.relations_out}')
     if who is not None:
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
         typed = None

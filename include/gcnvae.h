@@ -607,6 +607,27 @@ int gv_entity_topk_scores_typed(const int32_t* ents, int m, const float* e, int 
                                 int span_tiles, int32_t* out_rel, int32_t* out_ent, float* out_logits, void* workspace,
                                 int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
 
+/* Relation prediction (csrc/k_gemm.hip): the query is an entity PAIR (s_i, o_i), the candidates are the num_rels relations,
+ *   logit[i, r] = (e[s_i] * e[o_i]) . w[r] (+ *bias)
+ * bit for bit the element gv_gemm_f32(gv_mul(e[s], e[o]), w^T) + bias gives: the product row is formed while it is staged (one
+ * f32 multiply per element, the value gv_mul stores), so no (m, h) query matrix exists.  e (n, h) and w (num_rels, h) row-major
+ * fp32; s / o int32 [m], each in [0, n) (NOT checked on the device: the caller's wrapper refuses others).  ONE launch, no
+ * workspace: a workgroup owns 64 pairs and walks all ceil(num_rels / 64) column tiles itself, in ascending order.
+ *   target (int32 [m], each in [0, num_rels)) given: tgt[i] = logit[i, target[i]] -- the tile's own element -- and
+ *     count_raw[i] = 2 #{r != target: logit > tgt or either NaN} + #{r != target: logit == tgt}, count_filt[i] the same over the
+ *     relations not listed in filt_rel[filt_lo[i] .. filt_hi[i]) (a listed target is allowed): the definition, tie rule and NaN
+ *     rule of gv_rank_scores_filtered.  tgt is required with target, count_filt exactly with a filter, count_raw may be NULL.
+ *   k >= 1 (at most 128): out_ids int32 [m, k] / out_logits fp32 [m, k], the first k relations of the row under gv_topk_scores'
+ *     strict total order (logit descending, ties by lower id, NaN last), the listed relations left out; padded with id -1 / logit
+ *     -inf (k above num_rels only pads); -0 reported as +0, every NaN as the quiet NaN 0x7fc00000.  k = 0: no top-k.
+ * At least one of target and k must ask for something.  The filter's three arrays are all given or all NULL; the ranges are
+ * sorted ascending and unique, and clamped into [0, n_filt_rel] on the device.  m = 0 launches nothing.  No atomics: a row's
+ * counts and list live in LDS for the whole walk and are written by the wave that owns the row. */
+int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* w, int ld_w, int num_rels, const int32_t* s, const int32_t* o,
+                       const int32_t* target, const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_rel,
+                       int n_filt_rel, int k, float* tgt, int* count_raw, int* count_filt, int* out_ids, float* out_logits, int m,
+                       int h, void* stream);
+
 /* Monte-Carlo posterior-predictive ranking and top-k for a variational encoder: S posterior samples instead of one draw.
  * Sample s has a query matrix Q_s (m, h) at q + s * q_stride and an entity table E_s (v, h) at e + s * e_stride (strides in
  * elements; the leading dimensions ld_q / ld_e are shared by the samples) and an optional bias[s] (that draw's flow_log_prob;
@@ -891,6 +912,23 @@ int gv_transe_entity_topk_typed(const int32_t* ents, int m, const float* en, con
                                 const int64_t* set_ptr, const int32_t* set_ids, const int32_t* tile_ptr, int n_tiles, int cand_base,
                                 int exclude_self, int k, int span_tiles, int64_t* out_rel, int64_t* out_ent, float* out_dist,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Relation prediction for TransE (csrc/k_transe.hip): gv_pair_rel_scores' contract on distances, smaller is better.  en (n, dim)
+ * and rn (num_rels, dim) are the dense tables gv_transe_entity_topk takes; for the pair (s_i, o_i)
+ *   q[c] = en[o_i][c] - en[s_i][c]  (one f32 subtraction, formed while the row is staged)      d[i, r] = ||q - rn[r]||_p
+ * bit for bit gv_transe_distances on that row against rn.  In exact arithmetic this is ||n(s) + n(r) - n(o)||_p, the distance of
+ * the triplet (s, r, o); it is NOT the bit pattern gv_transe_topk reports for the same triplet, which associates the operands as
+ * (n(s) + n(r)) - n(o): the two differ by roundings, and nothing compares values across the two queries.
+ *   target given: tgt[i] = d[i, target[i]], count_raw[i] = 2 #{r != target: !(d_r >= d_target)} + #{r != target: d_r == d_target}
+ *     (gv_transe_rank_filtered's rule), count_filt[i] the same over the relations not listed; required / optional as above.
+ *   k >= 1: out_ids int64 [m, k] / out_dist fp32 [m, k] in gv_transe_topk's order (distance ascending, ties by lower id, NaN after
+ *     +inf), listed relations left out, padded with id -1 / distance +inf, a zero distance +0, every NaN the quiet NaN.
+ * 1 <= dim <= GV_TRANSE_MAX_DIM, p_norm 1 or 2, 0 <= k <= 128.  One launch, no workspace, no atomics; the L2 form runs on the
+ * vector ALU like every TransE distance (no MFMA route). */
+int gv_transe_pair_rel(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s, const int32_t* o,
+                       const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_rel, int n_filt_rel,
+                       int k, float* tgt, int32_t* count_raw, int32_t* count_filt, int64_t* out_ids, float* out_dist, int m,
+                       void* stream);
 
 /* Whole-graph triplet mining for TransE (csrc/k_transe_mine.hip): every (s, r, o) of the dense tables en (n, dim) and rn (num_rels,
  * dim), both as gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
