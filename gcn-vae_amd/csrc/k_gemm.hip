@@ -1956,8 +1956,17 @@ namespace gv {
 // ahead of the walk with the relation rows GATHERED through the rows' targets (score_tile_gather: the same staging, the same chain,
 // so a gathered row's logits are the bits score_tile gives that row) and its element (j, j) is row j's -- the walk proper
 // recomputes it bit for bit, as k_rank_scores<1> recomputes what k_rank_scores<0> wrote.
-// (A later sample loop -- the posterior predictive -- goes around score_tile_with here as in k_entity_topk_span<.., MC>: the
-// parameters carry the table by pointer and leading dimension, so a sample stride beside them is all it needs.)
+// CAND (gv_pair_rel_scores_constrained): the pair's type-correct relations -- the AND of two rows of the relation bitmask
+// (TopkPairCand, k_topk.h) -- add two counts per row and narrow the list; the raw and filtered counts, the target's value and
+// every logit are the unconstrained kernel's.  Thread rl < 64 fetches the row's two words per tile once the tile's MFMAs are
+// done (every wave is then past the previous tile's selection), the tile's barrier publishes them.
+// MC (gv_pair_rel_scores_mc): the value is pbar = (sum over s ascending of mc_sig(logit_s + bias[s])) * inv_s -- the sample loop of
+// k_entity_topk_span<.., MC> around score_tile_with, sample s reading the pair's rows at e + s * e_stride against the one w, pbar
+// in the 16 accumulator registers, written to Ls and selected ONCE per tile.  Under each sample's sigmoids the next sample's first
+// k-chunk is in flight, under the last one's the next tile's of sample 0.  The gathered tile of the targets runs the same loop
+// around score_tile_gather, so a target's pbar is the walk's own element bit for bit.
+// The default corner keeps the statements it had (the new corners' parameters come in a wrapper struct, their code under
+// if constexpr): its results and its code are the parent's.
 struct PairRelParams {
     GemmParams g;                 // b = w (stored [R, h]), m, n = R, k = h; a is not read
     const float* e;               // [n_entities, ld_e]
@@ -1978,15 +1987,28 @@ struct PairRelParams {
     float* out_logits;
 };
 
+// what the CAND / MC corners carry beside the parent's parameters (mc.n_samples == 0: not Monte-Carlo; cs.cand NULL: no sets)
+struct PairRelXParams {
+    PairRelParams p;              // p.bias: one value per sample with MC
+    McSamples mc;                 // e_stride: elements between consecutive samples' tables
+    TopkPairCand cs;
+    int* count_raw_c;             // may be NULL
+    int* count_filt_c;            // NULL without a filter
+};
+
+__device__ __forceinline__ const PairRelParams& pair_rel_params(const PairRelParams& pp) { return pp; }
+__device__ __forceinline__ const PairRelParams& pair_rel_params(const PairRelXParams& px) { return px.p; }
+
 // rank_votes' predicates: greater, or either side NaN; the key of gv_topk_scores
 struct PairRelRule {
     static __device__ __forceinline__ bool above(float v, float t) { return !(v <= t); }
     static __device__ __forceinline__ unsigned long long key(float v, int col) { return topk_key(v, col); }
 };
 
-template <int NK>                 // keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
-__global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
+template <int NK, bool CAND = false, bool MC = false>      // NK: keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
+__global__ __launch_bounds__(256) void k_pair_rel(const std::conditional_t<CAND || MC, PairRelXParams, PairRelParams> px) {
     constexpr int BM = SC_BM, BN = SC_BN, BK = SC_BK, LDL = BN + 1, APT = BM * BK / 256;
+    const PairRelParams& pp = pair_rel_params(px);
     __shared__ float As[BK * SC_LDA];
     __shared__ float Bs[BK * SC_LDB];
     __shared__ float Ls[BM * LDL];                 // the tile's logits, row-major
@@ -1995,7 +2017,9 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
     __shared__ int fl[4][64];
     __shared__ int tcol_s[BM];                     // the rows' targets (-1: none)
     __shared__ float tgt_s[BM];                    // ... and their logits
-    __shared__ int cnt_s[2][BM];                   // 2 #better + #equal: raw, filtered
+    __shared__ int cnt_s[CAND ? 4 : 2][BM];        // 2 #better + #equal: raw, filtered (CAND: and the two among the allowed)
+    __shared__ int so_s[CAND ? 2 : 1][CAND ? BM : 1];              // CAND: the rows' pairs (-1: no such row)
+    __shared__ unsigned long long allow_s[CAND ? BM : 1];          // ... and their allowed relations of the tile at hand
     extern __shared__ unsigned long long lists[];  // [BM][topk]
     const GemmParams& p = pp.g;
     const int k = pp.topk;
@@ -2005,12 +2029,12 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
     const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
     const int l31 = lane & 31, lhi = lane >> 5;
     const bool filtered = pp.filt_lo != nullptr, ranked = pp.target != nullptr;
-    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, tgt_s, cnt_s};
+    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, tgt_s, cnt_s, allow_s};
 
     // this thread's share of the query operand: row threadIdx.x / 4 of the tile, APT floats from column (threadIdx.x % 4) * APT on
     const int a_row = m0 + threadIdx.x / (BK / APT), a_col = (threadIdx.x % (BK / APT)) * APT;
     const bool a_ok = a_row < p.m;
-    const float* s_src = pp.e + (a_ok ? (size_t)pp.s[a_row] * pp.ld_e : 0) + a_col;
+    const float* s_src = pp.e + (a_ok ? (size_t)pp.s[a_row] * pp.ld_e : 0) + a_col;     // (MC: of the sample at hand)
     const float* o_src = pp.e + (a_ok ? (size_t)pp.o[a_row] * pp.ld_e : 0) + a_col;
     auto load_q = [&](int k0, float (&r)[APT]) {
         float ov[APT];
@@ -2027,12 +2051,45 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
         const int rl = threadIdx.x, row = m0 + rl;
         thr[rl] = 0ull;
         cnt_s[0][rl] = 0; cnt_s[1][rl] = 0;
+        if constexpr (CAND) {
+            cnt_s[2][rl] = 0; cnt_s[3][rl] = 0;
+            so_s[0][rl] = row < p.m ? pp.s[row] : -1;
+            so_s[1][rl] = row < p.m ? pp.o[row] : -1;
+        }
         tcol_s[rl] = (ranked && row < p.m) ? pp.target[row] : -1;
         tgt_s[rl] = __uint_as_float(0x7fc00000u);  // a target outside [0, R) ranks last
         topk_filter_begin(pp.filt_lo, pp.filt_hi, pp.filt_rel, pp.n_filt, filtered && row < p.m, row, 0, &cur[rl], &fhi[rl], &nxt[rl]);
     }
-    const float bv = pp.bias ? *pp.bias : 0.f;
+    const float bv = (!MC && pp.bias) ? *pp.bias : 0.f;
     float ra[APT], rb[BN * BK / 256];
+    // MC: pbar of one tile.  one_sample() is the tile's MFMA chain on the operands in ra / rb; load_sample() requests the first
+    // k-chunk of the sample s_src / o_src point at, load_next() what follows the tile (s_src / o_src are back at sample 0 then).
+    auto pbar_tile = [&](auto&& one_sample, auto&& load_sample, auto&& load_next) {
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        if constexpr (MC) {
+            const McSamples& mc = px.mc;
+            for (int s = 0; s < mc.n_samples; ++s) {
+                const f32x16 lg = one_sample();
+                const float bs = pp.bias ? pp.bias[s] : 0.f;
+                if (s + 1 < mc.n_samples) {                            // the next sample's first operands fly under the sigmoids
+                    s_src += mc.e_stride;
+                    o_src += mc.e_stride;
+                    load_sample();
+                } else {                                               // ... under the last one's, what follows the tile
+                    s_src -= (long long)s * mc.e_stride;
+                    o_src -= (long long)s * mc.e_stride;
+                    load_next();
+                }
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] += mc_sig(lg[i] + bs);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] *= mc.inv_s;
+        }
+        return acc;
+    };
 
     if (ranked && col_tiles > 1) {                 // the targets' logits: ONE gathered tile whose column j is w[target of row j]
         const int tc = a_ok ? pp.target[a_row] : -1;                      // (this thread's B slot is its A row: threadIdx.x / 4)
@@ -2041,7 +2098,12 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
         auto load_t = [&](int k0, float (&r)[BN * BK / 256]) { load_run<BN * BK / 256>(t_src + k0, a_col + k0, p.k, t_ok, p.vec_b, r, 0); };
         load_q(0, ra);
         load_t(0, rb);
-        const f32x16 acc = score_tile_gather(p, load_q, load_t, ra, rb, As, Bs);      // (its barriers publish the set-up)
+        f32x16 acc;
+        if constexpr (MC)
+            acc = pbar_tile([&] { return score_tile_gather(p, load_q, load_t, ra, rb, As, Bs); },
+                            [&] { load_q(0, ra); load_t(0, rb); }, [] {});
+        else
+            acc = score_tile_gather(p, load_q, load_t, ra, rb, As, Bs);              // (its barriers publish the set-up)
         const int cl = wn + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {                                    // element (j, j) is row j's own
@@ -2055,11 +2117,25 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
     for (int t = 0; t < col_tiles; ++t) {
         const int n0 = t * BN;
         // score_tile_with's first barrier publishes the set-up (and the gathered tile's tgt_s) and ends the last tile's reads of Ls
-        const f32x16 acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
-        if (t + 1 < col_tiles) {                   // the next tile's first operands fly under the selection
-            load_q(0, ra);
-            load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+        f32x16 acc;
+        if constexpr (MC) {
+            acc = pbar_tile([&] { return score_tile_with(p, load_q, n0, ra, rb, As, Bs); },
+                            [&] { load_q(0, ra); load_b<true, BN, BK>(p, n0, 0, p.k, rb); },
+                            [&] {
+                                if (t + 1 < col_tiles) {
+                                    load_q(0, ra);
+                                    load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+                                }
+                            });
+        } else {
+            acc = score_tile_with(p, load_q, n0, ra, rb, As, Bs);
+            if (t + 1 < col_tiles) {               // the next tile's first operands fly under the selection
+                load_q(0, ra);
+                load_b<true, BN, BK>(p, n0 + BN, 0, p.k, rb);
+            }
         }
+        if constexpr (CAND)                        // (every wave is past the tile's first barrier: nobody still reads the last tile's)
+            if (threadIdx.x < BM) allow_s[threadIdx.x] = topk_pair_rel_allow(px.cs, so_s[0][threadIdx.x], so_s[1][threadIdx.x], n0, p.n);
 #pragma unroll
         for (int r = 0; r < 16; ++r) Ls[(wm + (r & 3) + 8 * (r >> 2) + 4 * lhi) * LDL + wn + l31] = acc[r] + bv;
         __syncthreads();
@@ -2068,14 +2144,34 @@ __global__ __launch_bounds__(256) void k_pair_rel(const PairRelParams pp) {
                 tgt_s[threadIdx.x] = Ls[threadIdx.x * LDL + tcol_s[threadIdx.x]];
             __syncthreads();
         }
-        topk_pair_rel_tile<NK, PairRelRule>(st, m0, p.m, n0, p.n, t, k, ranked, pp.filt_rel, lane, wid,
-                                            [&](int rl) { return Ls[rl * LDL + lane]; });
+        topk_pair_rel_tile<NK, PairRelRule, CAND>(st, m0, p.m, n0, p.n, t, k, ranked, pp.filt_rel, lane, wid,
+                                                  [&](int rl) { return Ls[rl * LDL + lane]; });
     }
-    topk_pair_rel_store<NK, int, topk_key_logit>(st, m0, p.m, k, ranked, pp.tgt, pp.count_raw, pp.count_filt, pp.out_ids, pp.out_logits,
-                                                 lane, wid);
+    if constexpr (CAND)
+        topk_pair_rel_store<NK, int, topk_key_logit, true>(st, m0, p.m, k, ranked, pp.tgt, pp.count_raw, pp.count_filt, pp.out_ids,
+                                                           pp.out_logits, lane, wid, px.count_raw_c, px.count_filt_c);
+    else
+        topk_pair_rel_store<NK, int, topk_key_logit>(st, m0, p.m, k, ranked, pp.tgt, pp.count_raw, pp.count_filt, pp.out_ids,
+                                                     pp.out_logits, lane, wid);
 }
 
 }  // namespace gv
+
+// what every pair entry puts into PairRelParams (e_stride: of the MC forms, 0 otherwise: the 16-byte loads need every sample's
+// table aligned)
+static void pair_rel_fill(PairRelParams& pp, const float* e, int ld_e, long long e_stride, const float* w, int ld_w, int num_rels,
+                          const int32_t* s, const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo,
+                          const int* filt_hi, const int* filt_rel, int n_filt_rel, int k, float* tgt, int* count_raw, int* count_filt,
+                          int* out_ids, float* out_values, int m, int h) {
+    pp.g = score_gemm_params(nullptr, ld_e, w, ld_w, m, num_rels, h);
+    pp.e = e; pp.ld_e = ld_e;
+    pp.vec_a = aligned16(e) && (ld_e % 4 == 0) && (e_stride % 4 == 0);
+    pp.s = s; pp.o = o; pp.target = target; pp.bias = bias;
+    pp.filt_lo = filt_lo; pp.filt_hi = filt_hi; pp.filt_rel = filt_rel; pp.n_filt = n_filt_rel;
+    pp.topk = k;
+    pp.tgt = tgt; pp.count_raw = count_raw; pp.count_filt = filt_lo ? count_filt : nullptr;
+    pp.out_ids = out_ids; pp.out_logits = out_values;
+}
 
 extern "C" int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* w, int ld_w, int num_rels, const int32_t* s,
                                   const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo, const int* filt_hi,
@@ -2090,14 +2186,8 @@ extern "C" int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* 
     if (m == 0) return GV_OK;
     GV_CHECK(pair_query_given(name, e && w && s && o, target, tgt, k, out_ids, out_logits, filt_lo, count_filt));
     PairRelParams pp{};
-    pp.g = score_gemm_params(nullptr, ld_e, w, ld_w, m, num_rels, h);
-    pp.e = e; pp.ld_e = ld_e;
-    pp.vec_a = aligned16(e) && (ld_e % 4 == 0);
-    pp.s = s; pp.o = o; pp.target = target; pp.bias = bias;
-    pp.filt_lo = filt_lo; pp.filt_hi = filt_hi; pp.filt_rel = filt_rel; pp.n_filt = n_filt_rel;
-    pp.topk = k;
-    pp.tgt = tgt; pp.count_raw = count_raw; pp.count_filt = filt_lo ? count_filt : nullptr;
-    pp.out_ids = out_ids; pp.out_logits = out_logits;
+    pair_rel_fill(pp, e, ld_e, 0, w, ld_w, num_rels, s, o, target, bias, filt_lo, filt_hi, filt_rel, n_filt_rel, k, tgt, count_raw,
+                  count_filt, out_ids, out_logits, m, h);
     constexpr int KEY = (int)sizeof(unsigned long long);
     const dim3 grid((unsigned)((m + 63) / 64)), block(256);
     hipStream_t st = (hipStream_t)stream;
@@ -2109,6 +2199,75 @@ extern "C" int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* 
         hipLaunchKernelGGL(k_pair_rel<2>, grid, block, 64 * k * KEY, st, pp);
     }
     return launch_status(name);
+}
+
+// ---- the type-constrained and the posterior-predictive forms (gv_pair_rel_scores_constrained / _mc / _mc_constrained) -----------
+// gv_pair_rel_scores' checks in its order; the sample geometry stands where it reports its leading dimensions
+// (entity_mc_samples_args), the candidate group follows the filter group.  One launch, no workspace.
+template <bool CAND, bool MC>
+static int pair_rel_entry(const char* name, const float* e, int ld_e, int64_t e_stride, int n_samples, int n, const float* w, int ld_w,
+                          int num_rels, const int32_t* s, const int32_t* o, const int32_t* target, const float* bias,
+                          const int* filt_lo, const int* filt_hi, const int* filt_rel, int n_filt_rel, const uint32_t* cand,
+                          int ld_cand, int n_sets, int k, float* tgt, int* count_raw, int* count_filt, int* count_raw_c,
+                          int* count_filt_c, int* out_ids, float* out_values, int m, int h, void* stream) {
+    GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && h > 0 && n_filt_rel >= 0, GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d h=%d n_filt_rel=%d", name,
+               m, n, num_rels, h, n_filt_rel);
+    GV_CHECK(pair_query_asks(name, k, target));
+    PairRelXParams px{};
+    if constexpr (MC) GV_CHECK(entity_mc_samples_args(name, ld_e, ld_w, e_stride, n_samples, n, h, &px.mc));
+    else GV_CHECK(query_leading(name, ld_e, ld_w, h));
+    GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_rel, "filt_lo / filt_hi / filt_rel"));
+    if constexpr (CAND) GV_CHECK(pair_query_cand(name, cand, ld_cand, n_sets, n, num_rels));
+    if (m == 0) return GV_OK;
+    GV_CHECK(pair_query_given(name, e && w && s && o, target, tgt, k, out_ids, out_values, filt_lo, count_filt));
+    if constexpr (CAND) GV_CHECK(pair_query_given_cand(name, target, filt_lo, count_filt_c));
+    pair_rel_fill(px.p, e, ld_e, px.mc.e_stride, w, ld_w, num_rels, s, o, target, bias, filt_lo, filt_hi, filt_rel, n_filt_rel, k, tgt,
+                  count_raw, count_filt, out_ids, out_values, m, h);
+    if constexpr (CAND) {
+        px.cs = TopkPairCand{cand, ld_cand, n};
+        px.count_raw_c = count_raw_c; px.count_filt_c = filt_lo ? count_filt_c : nullptr;
+    }
+    constexpr int KEY = (int)sizeof(unsigned long long);
+    const dim3 grid((unsigned)((m + 63) / 64)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    static unsigned long long raised = 0;          // (one per instantiation of this template, i.e. per NK = 2 kernel)
+    if (k == 0) hipLaunchKernelGGL((k_pair_rel<0, CAND, MC>), grid, block, 0, st, px);
+    else if (k <= 64) hipLaunchKernelGGL((k_pair_rel<1, CAND, MC>), grid, block, 64 * k * KEY, st, px);
+    else {
+        if (!raise_dynamic_lds((const void*)k_pair_rel<2, CAND, MC>, 64 * TOPK_MAX * KEY, raised, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_pair_rel<2, CAND, MC>), grid, block, 64 * k * KEY, st, px);
+    }
+    return launch_status(name);
+}
+
+extern "C" int gv_pair_rel_scores_constrained(const float* e, int ld_e, int n, const float* w, int ld_w, int num_rels, const int32_t* s,
+                                              const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo,
+                                              const int* filt_hi, const int* filt_rel, int n_filt_rel, const uint32_t* cand, int ld_cand,
+                                              int n_sets, int k, float* tgt, int* count_raw, int* count_filt, int* count_raw_c,
+                                              int* count_filt_c, int* out_ids, float* out_logits, int m, int h, void* stream) {
+    return pair_rel_entry<true, false>("gv_pair_rel_scores_constrained", e, ld_e, 0, 0, n, w, ld_w, num_rels, s, o, target, bias, filt_lo,
+                                       filt_hi, filt_rel, n_filt_rel, cand, ld_cand, n_sets, k, tgt, count_raw, count_filt, count_raw_c,
+                                       count_filt_c, out_ids, out_logits, m, h, stream);
+}
+
+extern "C" int gv_pair_rel_scores_mc(const float* e, int ld_e, int64_t e_stride, int n_samples, int n, const float* w, int ld_w,
+                                     int num_rels, const int32_t* s, const int32_t* o, const int32_t* target, const float* bias,
+                                     const int* filt_lo, const int* filt_hi, const int* filt_rel, int n_filt_rel, int k, float* tgt,
+                                     int* count_raw, int* count_filt, int* out_ids, float* out_prob, int m, int h, void* stream) {
+    return pair_rel_entry<false, true>("gv_pair_rel_scores_mc", e, ld_e, e_stride, n_samples, n, w, ld_w, num_rels, s, o, target, bias,
+                                       filt_lo, filt_hi, filt_rel, n_filt_rel, nullptr, 0, 0, k, tgt, count_raw, count_filt, nullptr,
+                                       nullptr, out_ids, out_prob, m, h, stream);
+}
+
+extern "C" int gv_pair_rel_scores_mc_constrained(const float* e, int ld_e, int64_t e_stride, int n_samples, int n, const float* w, int ld_w,
+                                                 int num_rels, const int32_t* s, const int32_t* o, const int32_t* target,
+                                                 const float* bias, const int* filt_lo, const int* filt_hi, const int* filt_rel,
+                                                 int n_filt_rel, const uint32_t* cand, int ld_cand, int n_sets, int k, float* tgt,
+                                                 int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int* out_ids,
+                                                 float* out_prob, int m, int h, void* stream) {
+    return pair_rel_entry<true, true>("gv_pair_rel_scores_mc_constrained", e, ld_e, e_stride, n_samples, n, w, ld_w, num_rels, s, o, target,
+                                      bias, filt_lo, filt_hi, filt_rel, n_filt_rel, cand, ld_cand, n_sets, k, tgt, count_raw, count_filt,
+                                      count_raw_c, count_filt_c, out_ids, out_prob, m, h, stream);
 }
 
 extern "C" int gv_rel_rows_gemm(const float* feat, int ld_feat, const int32_t* rows, const float* w, int num_rels, int in_feat,

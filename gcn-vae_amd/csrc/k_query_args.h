@@ -2,8 +2,9 @@
 // / gv_pair_rel_scores (k_gemm.hip) and gv_transe_rank_* / gv_transe_topk* / gv_transe_entity_topk{,_typed} / gv_transe_pair_rel
 // (k_transe.hip).  One function per group of arguments; each takes the entry's
 // name, sets the library's error text and returns the code, GV_OK when the group is fine.  An entry lists its groups in the order
-// in which it reports them -- tests/test_query_entries_host.py (the pair entries: tests/test_relation_host.py) pins every text
-// and, with two faults at once, that order -- then returns for m == 0, then asks for its own pointers.
+// in which it reports them -- tests/test_query_entries_host.py (the pair entries: tests/test_relation_host.py and
+// tests/test_relation_typed_mc_host.py) pins every text and, with two faults at once, that order -- then returns for m == 0, then
+// asks for its own pointers.
 #pragma once
 #include "common.h"
 #include "k_topk.h"
@@ -64,7 +65,7 @@ inline int query_filter_needs(const char* name, const void* filt_lo, bool given,
     return GV_OK;
 }
 
-// ---- the pair queries (gv_pair_rel_scores, gv_transe_pair_rel): ranks, a top-k, or both from the one launch --------------------
+// ---- the pair queries (gv_pair_rel_scores, gv_transe_pair_rel and their _constrained / _mc forms): ranks, a top-k, or both ----------
 // k = 0 is "no top-k" there, and a call has to ask for something
 inline int pair_query_asks(const char* name, int k, const void* target) {
     GV_REQUIRE(k >= 0 && k <= TOPK_MAX, GV_ERR_SHAPE, "%s: k=%d outside [0, %d]", name, k, TOPK_MAX);
@@ -78,6 +79,22 @@ inline int pair_query_given(const char* name, bool tables, const void* target, c
     GV_CHECK(query_pointers(name, tables && (!target || tgt) && (k == 0 || (out_ids && out_values))));
     GV_REQUIRE(!filt_lo || !target || count_filt, GV_ERR_NULL, "%s: a filter needs count_filt", name);
     GV_REQUIRE(filt_lo || !count_filt, GV_ERR_NULL, "%s: count_filt needs a filter", name);
+    return GV_OK;
+}
+
+// the *_constrained pair entries, after the filter group: the relation bitmask's geometry (row e and row n + e of every entity:
+// n_sets >= 2 n; ld_cand spans the relations), then the array itself
+inline int pair_query_cand(const char* name, const void* cand, int ld_cand, int n_sets, int n, int num_rels) {
+    GV_REQUIRE(n_sets >= 2 * (long long)n && ld_cand >= (num_rels + 31) / 32, GV_ERR_SHAPE, "%s: n_sets=%d (>= 2 n = %lld) ld_cand=%d (>= %d)",
+               name, n_sets, 2 * (long long)n, ld_cand, (num_rels + 31) / 32);
+    GV_REQUIRE(cand, GV_ERR_NULL, "%s: NULL cand", name);
+    return GV_OK;
+}
+
+// ... and after pair_query_given: count_filt_c comes exactly with a filter and targets
+inline int pair_query_given_cand(const char* name, const void* target, const void* filt_lo, const void* count_filt_c) {
+    GV_REQUIRE(!filt_lo || !target || count_filt_c, GV_ERR_NULL, "%s: a filter needs count_filt_c", name);
+    GV_REQUIRE((filt_lo && target) || !count_filt_c, GV_ERR_NULL, "%s: count_filt_c needs a filter and targets", name);
     return GV_OK;
 }
 

@@ -233,13 +233,37 @@ struct TopkPairRel {
     int (*fl)[64];                // [4][64] the waves' flag words
     const int* tcol;              // [64] the rows' targets (-1: none)
     const float* tgt;             // [64] ... and their values
-    int (*cnt)[64];               // [2][64] 2 #better + #equal: raw, filtered
+    int (*cnt)[64];               // [2][64] 2 #better + #equal: raw, filtered; CAND: [4][64], + the two among the allowed
+    const unsigned long long* allow;      // CAND: [64] the rows' allowed columns of the tile at hand, bit j = column n0 + j
 };
+
+// ---- the pair kernels' candidate sets (the *_constrained entries): the type-correct relations of a pair -------------------------
+// `cand` is ranking.TypeConstraint.relation_words: [2 n_ent, ld_cand] words, relation r = bit r & 31 of word r >> 5, row e the
+// relations entity e was subject of, row n_ent + e those it was object of.  The set of pair (s, o) is the AND of rows s and
+// n_ent + o -- no set id per row -- and a 64-relation tile needs two words of each: thread rl < 64 reads them once per tile into
+// allow[rl], the wave that owns the row reads that back wave-uniform, and a lane's own bit is (mask >> lane) & 1.  The second word
+// is guarded by the used word count ceil(v / 32) (n0 < v, so the first lies inside it); bits from column v on may be set: every
+// use below is under col < v.
+struct TopkPairCand {
+    const uint32_t* cand;
+    int ld_cand, n_ent;
+};
+
+__device__ __forceinline__ unsigned long long topk_pair_rel_allow(const TopkPairCand& pc, int s, int o, int n0, int v) {
+    if (s < 0) return 0ull;                                              // no such row
+    const uint32_t* a = pc.cand + (size_t)s * pc.ld_cand;
+    const uint32_t* b = pc.cand + ((size_t)pc.n_ent + o) * pc.ld_cand;
+    const int w0 = n0 >> 5;
+    unsigned long long mask = a[w0] & b[w0];
+    if (w0 + 1 < (v + 31) >> 5) mask |= (unsigned long long)(a[w0 + 1] & b[w0 + 1]) << 32;
+    return mask;
+}
 
 // The wave's rows of the tile at n0 (the t-th), one lane per column: value(rl) is the lane's value of tile row rl.  One pass of the
 // row's filter window serves the counts and the list alike; the target itself and the columns from v on vote nowhere, a listed
-// column votes in the raw count only and is no candidate.
-template <int NK, class Rule, class Value>
+// column votes in the raw count only and is no candidate.  CAND: the row's allowed mask (st.allow) adds the two counts among the
+// allowed columns -- the target is never counted, allowed or not -- and only an allowed column is a candidate of the list.
+template <int NK, class Rule, bool CAND = false, class Value>
 __device__ __forceinline__ void topk_pair_rel_tile(const TopkPairRel& st, int m0, int m, int n0, int v, int t, int k, bool ranked,
                                                    const int* filt_ids, int lane, int wid, Value&& value) {
     const int col = n0 + lane;
@@ -250,6 +274,8 @@ __device__ __forceinline__ void topk_pair_rel_tile(const TopkPairRel& st, int m0
         bool listed = false;
         if (filt_ids && st.nxt[rl] < n0 + 64)     // this row lists ids inside the tile: mark them, advance the cursor
             listed = topk_filter_window(filt_ids, n0, t * 64 + rl + 1, lane, &st.cur[rl], &st.fhi[rl], &st.nxt[rl], st.fl[wid]);
+        unsigned long long am = ~0ull;
+        if constexpr (CAND) am = st.allow[rl];
         if (ranked) {
             const float tg = st.tgt[rl];
             const bool other = col < v && col != st.tcol[rl];
@@ -258,18 +284,27 @@ __device__ __forceinline__ void topk_pair_rel_tile(const TopkPairRel& st, int m0
             if (lane == 0) {
                 st.cnt[0][rl] += 2 * __popcll(ma) + __popcll(me);
                 st.cnt[1][rl] += 2 * __popcll(ma & keep) + __popcll(me & keep);
+                if constexpr (CAND) {
+                    st.cnt[2][rl] += 2 * __popcll(ma & am) + __popcll(me & am);
+                    st.cnt[3][rl] += 2 * __popcll(ma & keep & am) + __popcll(me & keep & am);
+                }
             }
         }
-        if constexpr (NK > 0)
+        if constexpr (NK > 0 && CAND)
+            topk_list_update<NK>((col < v && !listed && ((am >> lane) & 1ull)) ? Rule::key(x, col) : 0ull, st.lists + rl * k, &st.thr[rl],
+                                 k, lane);
+        else if constexpr (NK > 0)
             topk_list_update<NK>((col < v && !listed) ? Rule::key(x, col) : 0ull, st.lists + rl * k, &st.thr[rl], k, lane);
     }
 }
 
 // Each wave hands out its own rows: what it reads it wrote itself (tgt: ahead of the last barrier).  count_raw / count_filt may be
-// NULL; Decode is the key's value back (topk_key_logit, or te_key_dist for a key made of -distance).
-template <int NK, class Id, float (*Decode)(unsigned long long)>
+// NULL; Decode is the key's value back (topk_key_logit, or te_key_dist for a key made of -distance).  CAND: the two counts among
+// the allowed columns go out beside them (either may be NULL).
+template <int NK, class Id, float (*Decode)(unsigned long long), bool CAND = false>
 __device__ __forceinline__ void topk_pair_rel_store(const TopkPairRel& st, int m0, int m, int k, bool ranked, float* tgt, int* count_raw,
-                                                    int* count_filt, Id* out_ids, float* out_values, int lane, int wid) {
+                                                    int* count_filt, Id* out_ids, float* out_values, int lane, int wid,
+                                                    int* count_raw_c = nullptr, int* count_filt_c = nullptr) {
     for (int i = 0; i < 16; ++i) {
         const int rl = wid * 16 + i, row = m0 + rl;
         if (row >= m) break;
@@ -277,6 +312,10 @@ __device__ __forceinline__ void topk_pair_rel_store(const TopkPairRel& st, int m
             tgt[row] = st.tgt[rl];
             if (count_raw) count_raw[row] = st.cnt[0][rl];
             if (count_filt) count_filt[row] = st.cnt[1][rl];
+            if constexpr (CAND) {
+                if (count_raw_c) count_raw_c[row] = st.cnt[2][rl];
+                if (count_filt_c) count_filt_c[row] = st.cnt[3][rl];
+            }
         }
         if constexpr (NK > 0)
             for (int j = lane; j < k; j += 64) {

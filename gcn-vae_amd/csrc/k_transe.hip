@@ -952,6 +952,9 @@ __global__ __launch_bounds__(256) void k_transe_entity_topk_typed_span(const TeE
 // of the walk with the relation rows GATHERED through the rows' targets (te_tile_gather: the same staging, the same column order,
 // the same per-pair chain) and its element (j, j) is row j's.  Counts and lists live in LDS and belong to the wave that owns the
 // row; nothing is atomic.
+// CAND (gv_transe_pair_rel_constrained): k_pair_rel<., CAND>'s sets -- the AND of two rows of the relation bitmask, fetched by
+// thread rl < 64 once per tile after the tile's distances are made (TopkPairCand, k_topk.h) -- add the two counts among the
+// type-correct relations and narrow the list; distances, raw and filtered counts are the unconstrained kernel's, whose code stays.
 struct TePairRelParams {
     const float* en;              // [n, dim]
     const float* rn;              // [num_rels, dim]
@@ -971,14 +974,25 @@ struct TePairRelParams {
     float* out_dist;
 };
 
+struct TePairRelCParams {
+    TePairRelParams t;
+    TopkPairCand cs;
+    int32_t* count_raw_c;         // may be NULL
+    int32_t* count_filt_c;        // NULL without a filter
+};
+
+__device__ __forceinline__ const TePairRelParams& te_pair_rel_params(const TePairRelParams& tp) { return tp; }
+__device__ __forceinline__ const TePairRelParams& te_pair_rel_params(const TePairRelCParams& tc) { return tc.t; }
+
 // k_transe_rank's predicates: nearer, or either side NaN; the key of gv_transe_topk
 struct TePairRelRule {
     static __device__ __forceinline__ bool above(float d, float t) { return !(d >= t); }
     static __device__ __forceinline__ unsigned long long key(float d, int col) { return topk_key(-d, col); }
 };
 
-template <int NK>                 // keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
-__global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams tp) {
+template <int NK, bool CAND = false>      // NK: keys per lane of a row's list: 0 (ranks only), 1 (k <= 64), 2
+__global__ __launch_bounds__(256) void k_transe_pair_rel(const std::conditional_t<CAND, TePairRelCParams, TePairRelParams> tq) {
+    const TePairRelParams& tp = te_pair_rel_params(tq);
     __shared__ __attribute__((aligned(16))) float qs[TE_KC][TE_TQ + 4];
     __shared__ __attribute__((aligned(16))) float es[TE_KC][TE_TE + 4];
     __shared__ __attribute__((aligned(16))) float ds[TE_TQ * TE_LDD];     // the tile's distances, row-major
@@ -988,14 +1002,15 @@ __global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams t
     __shared__ int s_s[TE_TQ], o_s[TE_TQ];                                // the rows' pairs (-1: no such row)
     __shared__ int tcol_s[TE_TQ];                                         // the rows' targets (-1: none)
     __shared__ float dt_s[TE_TQ];                                         // ... and their distances
-    __shared__ int cnt_s[2][TE_TQ];                                       // 2 #better + #equal: raw, filtered
+    __shared__ int cnt_s[CAND ? 4 : 2][TE_TQ];                            // 2 #better + #equal: raw, filtered (CAND: + among the allowed)
+    __shared__ unsigned long long allow_s[CAND ? TE_TQ : 1];              // CAND: the rows' allowed relations of the tile at hand
     extern __shared__ unsigned long long lists[];                         // [TE_TQ][topk]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, tx = tid & 15, ty = tid >> 4;
     const int k = tp.topk, dim = tp.dim;
     const int m0 = blockIdx.x * TE_TQ;
     const int col_tiles = (tp.num_rels + TE_TE - 1) / TE_TE;
     const bool filtered = tp.filt_lo != nullptr, ranked = tp.target != nullptr;
-    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, dt_s, cnt_s};
+    const TopkPairRel st{lists, thr, cur, fhi, nxt, fl, tcol_s, dt_s, cnt_s, allow_s};
     if constexpr (NK > 0)
         for (int i = tid; i < TE_TQ * k; i += 256) lists[i] = 0ull;
     fl[wid][lane] = 0;
@@ -1007,6 +1022,7 @@ __global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams t
         s_s[tid] = a; o_s[tid] = b; tcol_s[tid] = tc;
         thr[tid] = 0ull;
         cnt_s[0][tid] = 0; cnt_s[1][tid] = 0;
+        if constexpr (CAND) { cnt_s[2][tid] = 0; cnt_s[3][tid] = 0; }
         dt_s[tid] = __uint_as_float(0x7fc00000u);                         // a target outside [0, R) ranks last
         topk_filter_begin(tp.filt_lo, tp.filt_hi, tp.filt_rel, tp.n_filt, filtered && live, row, 0, &cur[tid], &fhi[tid], &nxt[tid]);
     }
@@ -1035,6 +1051,8 @@ __global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams t
         float acc[4][4];
         // te_tile_with's first barrier publishes the set-up above (and the gathered tile's dt_s) and ends the last tile's reads of ds
         te_tile_with(q_at, tp.rn, tp.num_rels, dim, tp.p, e0, qs, es, acc);
+        if constexpr (CAND)                        // (every wave is past the tile's first barrier: nobody still reads the last tile's)
+            if (tid < TE_TQ) allow_s[tid] = topk_pair_rel_allow(tq.cs, s_s[tid], o_s[tid], e0, tp.num_rels);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
             *reinterpret_cast<float4*>(&ds[(4 * ty + a) * TE_LDD + 4 * tx]) = make_float4(acc[a][0], acc[a][1], acc[a][2], acc[a][3]);
@@ -1043,11 +1061,15 @@ __global__ __launch_bounds__(256) void k_transe_pair_rel(const TePairRelParams t
             if (tid < TE_TQ && (unsigned)tcol_s[tid] < (unsigned)tp.num_rels) dt_s[tid] = ds[tid * TE_LDD + tcol_s[tid]];
             __syncthreads();
         }
-        topk_pair_rel_tile<NK, TePairRelRule>(st, m0, tp.m, e0, tp.num_rels, t, k, ranked, tp.filt_rel, lane, wid,
-                                              [&](int rl) { return ds[rl * TE_LDD + lane]; });
+        topk_pair_rel_tile<NK, TePairRelRule, CAND>(st, m0, tp.m, e0, tp.num_rels, t, k, ranked, tp.filt_rel, lane, wid,
+                                                    [&](int rl) { return ds[rl * TE_LDD + lane]; });
     }
-    topk_pair_rel_store<NK, int64_t, te_key_dist>(st, m0, tp.m, k, ranked, tp.tgt, tp.count_raw, tp.count_filt, tp.out_ids, tp.out_dist,
-                                                  lane, wid);
+    if constexpr (CAND)
+        topk_pair_rel_store<NK, int64_t, te_key_dist, true>(st, m0, tp.m, k, ranked, tp.tgt, tp.count_raw, tp.count_filt, tp.out_ids,
+                                                            tp.out_dist, lane, wid, tq.count_raw_c, tq.count_filt_c);
+    else
+        topk_pair_rel_store<NK, int64_t, te_key_dist>(st, m0, tp.m, k, ranked, tp.tgt, tp.count_raw, tp.count_filt, tp.out_ids,
+                                                      tp.out_dist, lane, wid);
 }
 
 }  // namespace gv
@@ -1317,32 +1339,57 @@ extern "C" int gv_transe_entity_topk_typed(const int32_t* ents, int m, const flo
         name, dim3((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ), (unsigned)tp.n_spans), pp, tp.part, m, tp.n_spans, k, out, GV_ST);
 }
 
-// ---- relation prediction (gv_transe_pair_rel): one launch, the checks of gv_pair_rel_scores in its order -------------------------
-extern "C" int gv_transe_pair_rel(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
-                                  const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
-                                  const int32_t* filt_rel, int n_filt_rel, int k, float* tgt, int32_t* count_raw, int32_t* count_filt,
-                                  int64_t* out_ids, float* out_dist, int m, void* stream) {
-    const char* name = "gv_transe_pair_rel";
+// ---- relation prediction (gv_transe_pair_rel{,_constrained}): one launch, the checks of gv_pair_rel_scores{,_constrained} in
+// their order
+template <bool CAND>
+static int te_pair_rel_entry(const char* name, const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
+                             const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
+                             const int32_t* filt_rel, int n_filt_rel, const uint32_t* cand, int ld_cand, int n_sets, int k, float* tgt,
+                             int32_t* count_raw, int32_t* count_filt, int32_t* count_raw_c, int32_t* count_filt_c, int64_t* out_ids,
+                             float* out_dist, int m, void* stream) {
     GV_REQUIRE(m >= 0 && n > 0 && num_rels > 0 && dim > 0 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2) && n_filt_rel >= 0,
                GV_ERR_SHAPE, "%s: m=%d n=%d num_rels=%d dim=%d (1..%d) p_norm=%d (1 or 2) n_filt_rel=%d", name, m, n, num_rels, dim,
                GV_TRANSE_MAX_DIM, p_norm, n_filt_rel);
     GV_CHECK(pair_query_asks(name, k, target));
     GV_CHECK(query_filter(name, filt_lo, filt_hi, filt_rel, "filt_lo / filt_hi / filt_rel"));
+    if constexpr (CAND) GV_CHECK(pair_query_cand(name, cand, ld_cand, n_sets, n, num_rels));
     if (m == 0) return GV_OK;
     GV_CHECK(pair_query_given(name, en && rn && s && o, target, tgt, k, out_ids, out_dist, filt_lo, count_filt));
+    if constexpr (CAND) GV_CHECK(pair_query_given_cand(name, target, filt_lo, count_filt_c));
     const TePairRelParams tp{en, rn, s, o, target, filt_lo, filt_hi, filt_rel, m, num_rels, dim, p_norm, n_filt_rel, k, tgt,
                              count_raw, filt_lo ? count_filt : nullptr, out_ids, out_dist};
+    std::conditional_t<CAND, TePairRelCParams, TePairRelParams> tx;
+    if constexpr (CAND) tx = TePairRelCParams{tp, TopkPairCand{cand, ld_cand, n}, count_raw_c, filt_lo ? count_filt_c : nullptr};
+    else tx = tp;
     constexpr int KEY = (int)sizeof(unsigned long long);
     const dim3 grid((unsigned)(((long long)m + TE_TQ - 1) / TE_TQ)), block(256);
     static unsigned long long raised1 = 0, raised2 = 0;      // (<= 64 KiB of lists beside 38 KiB static: the limit is raised for either NK)
     if (k == 0) {
-        hipLaunchKernelGGL(k_transe_pair_rel<0>, grid, block, 0, GV_ST, tp);
+        hipLaunchKernelGGL((k_transe_pair_rel<0, CAND>), grid, block, 0, GV_ST, tx);
     } else if (k <= 64) {
-        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<1>, TE_TQ * 64 * KEY, raised1, name)) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_transe_pair_rel<1>, grid, block, TE_TQ * k * KEY, GV_ST, tp);
+        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<1, CAND>, TE_TQ * 64 * KEY, raised1, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_transe_pair_rel<1, CAND>), grid, block, TE_TQ * k * KEY, GV_ST, tx);
     } else {
-        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<2>, TE_TQ * TOPK_MAX * KEY, raised2, name)) return GV_ERR_SHAPE;
-        hipLaunchKernelGGL(k_transe_pair_rel<2>, grid, block, TE_TQ * k * KEY, GV_ST, tp);
+        if (!raise_dynamic_lds((const void*)k_transe_pair_rel<2, CAND>, TE_TQ * TOPK_MAX * KEY, raised2, name)) return GV_ERR_SHAPE;
+        hipLaunchKernelGGL((k_transe_pair_rel<2, CAND>), grid, block, TE_TQ * k * KEY, GV_ST, tx);
     }
     return launch_status(name);
+}
+
+extern "C" int gv_transe_pair_rel(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
+                                  const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
+                                  const int32_t* filt_rel, int n_filt_rel, int k, float* tgt, int32_t* count_raw, int32_t* count_filt,
+                                  int64_t* out_ids, float* out_dist, int m, void* stream) {
+    return te_pair_rel_entry<false>("gv_transe_pair_rel", en, rn, n, num_rels, dim, p_norm, s, o, target, filt_lo, filt_hi, filt_rel,
+                                    n_filt_rel, nullptr, 0, 0, k, tgt, count_raw, count_filt, nullptr, nullptr, out_ids, out_dist, m, stream);
+}
+
+extern "C" int gv_transe_pair_rel_constrained(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
+                                              const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
+                                              const int32_t* filt_rel, int n_filt_rel, const uint32_t* cand, int ld_cand, int n_sets,
+                                              int k, float* tgt, int32_t* count_raw, int32_t* count_filt, int32_t* count_raw_c,
+                                              int32_t* count_filt_c, int64_t* out_ids, float* out_dist, int m, void* stream) {
+    return te_pair_rel_entry<true>("gv_transe_pair_rel_constrained", en, rn, n, num_rels, dim, p_norm, s, o, target, filt_lo, filt_hi,
+                                   filt_rel, n_filt_rel, cand, ld_cand, n_sets, k, tgt, count_raw, count_filt, count_raw_c, count_filt_c,
+                                   out_ids, out_dist, m, stream);
 }

@@ -120,6 +120,13 @@ SIGNATURES = {
                                             _P, _L, _I, _I, _I, _P]),
     'gv_pair_rel_scores': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     'gv_transe_pair_rel': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P]),
+    'gv_pair_rel_scores_constrained': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                            _I, _I, _P]),
+    'gv_pair_rel_scores_mc': (_I, [_P, _I, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    'gv_pair_rel_scores_mc_constrained': (_I, [_P, _I, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P,
+                                               _P, _P, _P, _P, _I, _I, _P]),
+    'gv_transe_pair_rel_constrained': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P,
+                                            _I, _P]),
     'gv_rank_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_topk_scores_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     'gv_pair_prob_std_mc': (_I, [_P, _I, _L, _P, _I, _L, _I, _P, _P, _I, _P, _I, _I, _I, _P]),

@@ -924,11 +924,28 @@ def pair_ids_check(s, o, target, n, num_rels):
         raise ValueError(f'targets must lie in [0, {num_rels})')
 
 
-def _pair_buffers(m, k, ranked, id_dtype, dev):
-    """The outputs of a pair query: (tgt, counts (2, m) or None, ids (m, k), values (m, k))."""
+def _pair_buffers(m, k, ranked, id_dtype, dev, n_counts=2):
+    """The outputs of a pair query: (tgt, counts (2, m) -- (4, m) for a constrained one -- or None, ids (m, k), values (m, k))."""
     tgt = torch.empty(max(m, 1), dtype=torch.float32, device=dev) if ranked else None
-    counts = torch.empty(2, max(m, 1), dtype=torch.int32, device=dev) if ranked else None
+    counts = torch.empty(n_counts, max(m, 1), dtype=torch.int32, device=dev) if ranked else None
     return tgt, counts, torch.empty(m, k, dtype=id_dtype, device=dev), torch.empty(m, k, dtype=torch.float32, device=dev)
+
+
+def _pair_cand_args(cand, n, num_rels, device):
+    """The relation bitmask of a constrained pair query (``ranking.TypeConstraint.relation_words``: row e the relations entity e
+    was subject of, row n + e those it was object of) through ``_cand_args``' type, shape and device checks with v = num_rels;
+    the pairs index 2 n rows.  Returns the entries' (cand, ld_cand, n_sets)."""
+    words, ld_cand, n_sets, _ = _cand_args(cand, torch.zeros(0, dtype=torch.int32), 0, num_rels, device)
+    if n_sets < 2 * n:
+        raise ValueError(f'cand: need 2 n = {2 * n} rows (entity e as subject, then as object), got {n_sets}')
+    return words, ld_cand, n_sets
+
+
+def _pair_count_ptrs(counts, given):
+    """The count arguments of a pair entry from the (2 or 4, m) buffer: the filtered ones only with a filter and targets."""
+    if counts is None:
+        return (None,) * 4
+    return tuple(ptr(counts[i]) if i < counts.shape[0] and (given or i % 2 == 0) else None for i in range(4))
 
 
 def _pair_result(counts, m, given, k, ids, values):
@@ -937,7 +954,8 @@ def _pair_result(counts, m, given, k, ids, values):
     return (None if counts is None else _ranks(counts, m, given)), (None if k == 0 else (ids.long(), values))
 
 
-def pair_relation_scores(emb, w, s, o, *, target=None, k=0, bias=None, filt_lo=None, filt_hi=None, filt_rel=None, ids_checked=False):
+def pair_relation_scores(emb, w, s, o, *, target=None, k=0, bias=None, filt_lo=None, filt_hi=None, filt_rel=None, cand=None,
+                         ids_checked=False):
     """Relation prediction: for every entity pair ``(s[i], o[i])`` the relations under ``logit[i, r] = (emb[s_i] * emb[o_i]) . w[r]
     (+ bias)`` -- bit for bit ``gemm(mul(emb[s], emb[o]), w^T, precision='f32') + bias`` -- from ONE launch without a workspace
     (gv_pair_rel_scores): a workgroup owns 64 pairs and walks every 64-relation tile itself, and the (m, h) product matrix is
@@ -949,7 +967,13 @@ def pair_relation_scores(emb, w, s, o, *, target=None, k=0, bias=None, filt_lo=N
     as the one quiet NaN.  Returns ``(ranks, topk)``: ``(raw, filtered or None)`` or None without ``target``; ``(ids int64 (m, k),
     logits float32 (m, k))`` or None with ``k == 0``.  Pair ids outside the table are refused here: the kernel trusts them.
     ``ids_checked=True`` skips the reads behind the range checks of pairs, targets and filter for a caller that has made them
-    (``pair_ids_check``: the chunked drivers check a whole query set once)."""
+    (``pair_ids_check``: the chunked drivers check a whole query set once).
+    ``cand`` (gv_pair_rel_scores_constrained): the relation bitmask ``ranking.TypeConstraint.relation_words`` -- (>= 2 n, >=
+    ceil(R / 32)) int32, see ``_pair_cand_args`` -- whose rows ``s[i]`` and ``n + o[i]`` AND to the pair's TYPE-CORRECT relations.
+    The ranks become ``(raw, filtered, raw_constrained, filtered_constrained)`` by ``rank_scores_constrained``'s rules (the
+    constrained counts take type-correct relations only, the target is never counted, none besides the target gives 0; the first
+    two are the unconstrained call's bit for bit) and the list's candidates the type-correct relations less the listed ones.
+    Bits at columns >= R are ignored."""
     m, n, num_rels, h, k, tgt32, (lo32, hi32, rel32, n_rel) = _pair_args(emb, w, ('emb', 'w'), s, o, target, k, (filt_lo, filt_hi, filt_rel),
                                                                          ids_checked=ids_checked)
     emb, ld_e = _row_major(emb, 'emb')
@@ -957,14 +981,50 @@ def pair_relation_scores(emb, w, s, o, *, target=None, k=0, bias=None, filt_lo=N
     dev = emb.device
     if w.device != dev:
         raise ValueError(f'emb on {dev}, w on {w.device}')
-    tgt, counts, ids, values = _pair_buffers(m, k, tgt32 is not None, torch.int32, dev)
+    sets = () if cand is None else _pair_cand_args(cand, n, num_rels, dev)
+    tgt, counts, ids, values = _pair_buffers(m, k, tgt32 is not None, torch.int32, dev, 2 if cand is None else 4)
     given = lo32 is not None
     if m:
         s32, o32 = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (s, o))
-        lib.call('gv_pair_rel_scores', ptr(emb), ld_e, n, ptr(w), ld_w, num_rels, ptr(s32), ptr(o32), ptr(tgt32), ptr(_bias_arg(bias)),
-                 ptr(lo32), ptr(hi32), ptr(rel32), n_rel, k, ptr(tgt), None if counts is None else ptr(counts[0]),
-                 ptr(counts[1]) if given and counts is not None else None, ptr(ids), ptr(values), m, h, lib.stream())
+        c = _pair_count_ptrs(counts, given)
+        lib.call('gv_pair_rel_scores' if cand is None else 'gv_pair_rel_scores_constrained', ptr(emb), ld_e, n, ptr(w), ld_w, num_rels,
+                 ptr(s32), ptr(o32), ptr(tgt32), ptr(_bias_arg(bias)), ptr(lo32), ptr(hi32), ptr(rel32), n_rel,
+                 *((ptr(sets[0]),) + sets[1:] if sets else ()), k, ptr(tgt), *c[:4 if sets else 2], ptr(ids), ptr(values), m, h,
+                 lib.stream())
     return _pair_result(counts, m, given, k, ids, values)
+
+
+def pair_relation_scores_mc(z, w, s, o, *, target=None, k=0, bias=None, filt_lo=None, filt_hi=None, filt_rel=None, cand=None,
+                            ids_checked=False):
+    """``pair_relation_scores`` on the Monte-Carlo posterior predictive of S samples (gv_pair_rel_scores_mc{,_constrained}): ``z``
+    (S, N, h) holds one entity table per sample (``KGVAE.posterior_samples``; unit inner stride, row and sample strides are kept
+    when they span their rows / table), ``w`` the one relation table, ``bias`` (S,) optionally each draw's flow_log_prob (None: no
+    bias).  The value is ``pbar[i, r] = mean_s sigmoid((z_s[s_i] * z_s[o_i]) . w[r] + bias[s])``, summed in ascending sample order
+    in registers and ranked / selected once per 64-relation tile: bit for bit what ``rank_scores_mc`` / ``topk_scores_mc`` give
+    for ``q = mul(z[:, s], z[:, o])`` against ``w`` repeated per sample.  Ranks are mid-ranks -- pbar saturates, so ties are real
+    -- and NaN is never optimistic; the list is padded with -1 / -inf.  ``cand``, the filter and ``ids_checked`` are
+    ``pair_relation_scores``'.  Returns ``(ranks, topk, tgt)``: ``tgt`` (m,) the target's own pbar, None without ``target``."""
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] < 1:
+        raise TypeError('z: expected a 3-D (samples, entities, width) tensor with at least one sample')
+    n_samples = z.shape[0]
+    m, n, num_rels, h, k, tgt32, (lo32, hi32, rel32, n_rel) = _pair_args(z[0], w, ('z', 'w'), s, o, target, k, (filt_lo, filt_hi, filt_rel),
+                                                                         ids_checked=ids_checked)
+    z, ld_e, e_stride = _mine_sample_stack(z, 'z')
+    w, ld_w = _row_major(w, 'w')
+    dev = z.device
+    if w.device != dev:
+        raise ValueError(f'z on {dev}, w on {w.device}')
+    sets = () if cand is None else _pair_cand_args(cand, n, num_rels, dev)
+    tgt, counts, ids, values = _pair_buffers(m, k, tgt32 is not None, torch.int32, dev, 2 if cand is None else 4)
+    given = lo32 is not None
+    if m:
+        s32, o32 = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (s, o))
+        c = _pair_count_ptrs(counts, given)
+        lib.call('gv_pair_rel_scores_mc' if cand is None else 'gv_pair_rel_scores_mc_constrained', ptr(z), ld_e, e_stride, n_samples, n,
+                 ptr(w), ld_w, num_rels, ptr(s32), ptr(o32), ptr(tgt32), ptr(_mc_bias_arg(bias, n_samples, dev)), ptr(lo32), ptr(hi32),
+                 ptr(rel32), n_rel, *((ptr(sets[0]),) + sets[1:] if sets else ()), k, ptr(tgt), *c[:4 if sets else 2], ptr(ids),
+                 ptr(values), m, h, lib.stream())
+    return _pair_result(counts, m, given, k, ids, values) + (None if tgt is None else tgt[:m],)
 
 
 def entity_typed_plan(set_ptr, num_rels, side='s'):
@@ -4006,26 +4066,30 @@ def _transe_entity_topk(entry, ents, en, rn, k, p_norm, head, filt, exclude_self
     return rel, other, dist
 
 
-def transe_pair_relations(en, rn, s, o, p_norm, *, target=None, k=0, filt_lo=None, filt_hi=None, filt_rel=None, ids_checked=False):
+def transe_pair_relations(en, rn, s, o, p_norm, *, target=None, k=0, filt_lo=None, filt_hi=None, filt_rel=None, cand=None,
+                          ids_checked=False):
     """Relation prediction for TransE: ``pair_relation_scores`` on distances, smaller is better (gv_transe_pair_rel, one launch, no
     workspace).  ``d[i, r] = ||(en[o_i] - en[s_i]) - rn[r]||_p`` on the dense tables ``transe_entity_topk`` takes -- bit for bit
     ``transe_distances(en[o] - en[s], rn, p_norm)``; in exact arithmetic the triplet's ``||n(s) + n(r) - n(o)||``, but NOT the bit
     pattern ``transe_topk`` reports for the same triplet, which associates the operands the other way.  Ranks follow
     ``transe_rank_filtered``'s rule, the top-k ``transe_topk``'s order (distance ascending, equal distances by lower id, NaN after
-    +inf), padded with id -1 / distance +inf.  ``ids_checked`` and the returned ``(ranks, topk)`` are ``pair_relation_scores``'."""
+    +inf), padded with id -1 / distance +inf.  ``ids_checked``, ``cand`` (gv_transe_pair_rel_constrained: the type-correct
+    relations of each pair, four ranks, the narrowed list) and the returned ``(ranks, topk)`` are ``pair_relation_scores``'."""
     m, n, num_rels, dim, k, tgt32, (lo32, hi32, rel32, n_rel) = _pair_args(en, rn, ('en', 'rn'), s, o, target, k,
                                                                            (filt_lo, filt_hi, filt_rel), p_norm, ids_checked)
     en, rn = _table(en.contiguous(), 'en'), _table(rn.contiguous(), 'rn')
     dev = en.device
     if rn.device != dev:
         raise ValueError(f'en on {dev}, rn on {rn.device}')
-    tgt, counts, ids, dist = _pair_buffers(m, k, tgt32 is not None, torch.int64, dev)
+    sets = () if cand is None else _pair_cand_args(cand, n, num_rels, dev)
+    tgt, counts, ids, dist = _pair_buffers(m, k, tgt32 is not None, torch.int64, dev, 2 if cand is None else 4)
     given = lo32 is not None
     if m:
         s32, o32 = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (s, o))
-        lib.call('gv_transe_pair_rel', ptr(en), ptr(rn), n, num_rels, dim, int(p_norm), ptr(s32), ptr(o32), ptr(tgt32), ptr(lo32), ptr(hi32),
-                 ptr(rel32), n_rel, k, ptr(tgt), None if counts is None else ptr(counts[0]),
-                 ptr(counts[1]) if given and counts is not None else None, ptr(ids), ptr(dist), m, lib.stream())
+        c = _pair_count_ptrs(counts, given)
+        lib.call('gv_transe_pair_rel' if cand is None else 'gv_transe_pair_rel_constrained', ptr(en), ptr(rn), n, num_rels, dim, int(p_norm),
+                 ptr(s32), ptr(o32), ptr(tgt32), ptr(lo32), ptr(hi32), ptr(rel32), n_rel, *((ptr(sets[0]),) + sets[1:] if sets else ()), k,
+                 ptr(tgt), *c[:4 if sets else 2], ptr(ids), ptr(dist), m, lib.stream())
     return _pair_result(counts, m, given, k, ids, dist)
 
 

@@ -54,7 +54,11 @@ Relation prediction (how are two entities related? -- the query is a pair (s, ?,
 pairs' known relations -- filtered, and ``predict_relations`` proposes the k best new ones, from ``ops.pair_relation_scores``
 (gv_pair_rel_scores: one launch, the product row e_s * e_o formed while it is staged, every relation tile walked by the workgroup
 that owns the pairs).  ``relation_ranks_from_scores`` / ``topk_from_scores`` state the rules on a materialised (m, R) matrix; the
-``*_unfused`` routes are the GEMM cross-check.
+``*_unfused`` routes are the GEMM cross-check.  With a ``type_constraint`` the three also answer among the pair's TYPE-CORRECT
+relations (s seen as subject of r and o as its object: the AND of two rows of ``TypeConstraint.relation_words``; four rank kinds),
+and ``rank_relations_mc`` / ``calc_relation_mc_mrr`` / ``predict_relations_mc`` answer on the posterior predictive
+(``ops.pair_relation_scores_mc``: the sample loop around each relation tile; ``predict_relations_mc`` adds the spread), typed or
+not; ``pair_pbar_unfused`` is their materialised side.
 """
 import torch
 
@@ -216,11 +220,39 @@ class TypeConstraint:
         # distinct (set, entity) pairs: each is one bit, so summing the bits of a word is OR-ing them
         pair = torch.unique(torch.cat([r * self.num_nodes + o, (self.num_rels + r) * self.num_nodes + s]))
         set_id, ent = pair // max(self.num_nodes, 1), pair % max(self.num_nodes, 1)
+        self._pairs, self._relation_words = (set_id, ent), None              # (relation_words is built from them on first use)
         words = torch.zeros(n_sets * n_words, dtype=torch.long, device=self.device)
         words.index_add_(0, set_id * n_words + (ent >> 5), torch.ones_like(ent) << (ent & 31))
         words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)          # the uint32 bit pattern, held as int32
         self.words = words.to(torch.int32).view(n_sets, n_words).contiguous()
         self.sizes = torch.bincount(set_id, minlength=n_sets)
+
+    def relation_words(self, device=None):
+        """The sets seen from an entity: int32 (2 * num_nodes, ceil(num_rels / 32)), row e the relations entity e was SUBJECT of,
+        row num_nodes + e those it was OBJECT of; relation r is bit r & 31 of word r >> 5, bits from num_rels on are zero.  The
+        type-correct relations of a pair (s, o) are the AND of rows s and num_nodes + o -- what ``ops.pair_relation_scores(cand=)``
+        reads, two words per side per 64-relation tile.  Built once, with torch ops, from the distinct (set, entity) pairs
+        ``words`` is built from."""
+        if self._relation_words is None:
+            set_id, ent = self._pairs
+            n_words = (self.num_rels + 31) // 32
+            rel = set_id % max(self.num_rels, 1)
+            row = torch.where(set_id >= self.num_rels, ent, self.num_nodes + ent)      # set R + r: subjects of r; set r: its objects
+            words = torch.zeros(2 * self.num_nodes * n_words, dtype=torch.long, device=self.device)
+            words.index_add_(0, row * n_words + (rel >> 5), torch.ones_like(rel) << (rel & 31))
+            words = torch.where(words >= 2 ** 31, words - 2 ** 32, words)      # the uint32 bit pattern, held as int32
+            self._relation_words = words.to(torch.int32).view(2 * self.num_nodes, n_words).contiguous()
+        return self._relation_words if device is None else self._relation_words.to(device)
+
+    def pair_mask(self, s, o, device=None):
+        """Dense (m, num_rels) bool: relation r is type-correct for the pair (s[i], o[i]) -- s[i] was seen as subject of r and
+        o[i] as object of r.  Read off ``words`` (not ``relation_words``): the materialised twins' side of the cross-check."""
+        s, o = (torch.as_tensor(t).to(device=self.device, dtype=torch.long).reshape(-1) for t in (s, o))
+        rel = torch.arange(self.num_rels, device=self.device).view(1, -1)
+        subj = (self.words[self.num_rels + rel, (s >> 5).view(-1, 1)] >> (s & 31).view(-1, 1)) & 1
+        obj = (self.words[rel, (o >> 5).view(-1, 1)] >> (o & 31).view(-1, 1)) & 1
+        dense = (subj & obj).bool()
+        return dense if device is None else dense.to(device)
 
     def set_ids(self, r, direction):
         """int32 set id of each relation ``r[i]``: r for 'o' (object candidates), num_rels + r for 's' (subject candidates)."""
@@ -1265,92 +1297,199 @@ def pair_scores_unfused(emb, w, s, o, flow_log_prob=None):
     return score if flow_log_prob is None else score + flow_log_prob
 
 
-def relation_ranks_from_scores(score, target, filt_lo=None, filt_hi=None, filt_rel=None):
+def relation_ranks_from_scores(score, target, filt_lo=None, filt_hi=None, filt_rel=None, cand_mask=None):
     """The rank rule of ``ops.pair_relation_scores`` on a materialised (m, R) matrix, higher is better, in plain torch (any
     device): ``mid_ranks`` with the relations ``filt_rel[filt_lo[i]:filt_hi[i]]`` left out of the filtered count (a listed target
-    is allowed: the target is left out of every pool anyway).  Returns (raw, filtered or None)."""
+    is allowed: the target is left out of every pool anyway).  Returns (raw, filtered or None); with ``cand_mask`` (dense (m, R)
+    bool of the type-correct relations, ``TypeConstraint.pair_mask``) the four kinds of ``mid_ranks``."""
     listed = None if filt_lo is None else _listed_mask(filt_lo, filt_hi, filt_rel, score.shape[0], score.shape[1], score.device)
-    return mid_ranks(score, target.to(score.device), listed)[:2]
+    if cand_mask is None:
+        return mid_ranks(score, target.to(score.device), listed)[:2]
+    return mid_ranks(score, target.to(score.device), listed, cand_mask.to(score.device))
 
 
 def _pair_cat(parts, width, dtype, device):
     return torch.cat(parts) if parts else torch.zeros((0,) + width, dtype=dtype, device=device)
 
 
-def _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, fused):
-    emb = embedding.detach().contiguous()
-    wd, flow_log_prob = _on_device(emb, w.detach(), flow_log_prob)
-    triplets = triplets.to(emb.device)
+def pair_pbar_unfused(z, w, s, o, flow_log_probs=None):
+    """The materialised (m, R) posterior-predictive probabilities of the pairs: ``pair_scores_unfused`` per sample, a sigmoid and
+    a running sum in ascending sample order, times 1 / S."""
+    total = None
+    for i in range(z.shape[0]):
+        p = torch.sigmoid(pair_scores_unfused(z[i], w, s, o, None if flow_log_probs is None else flow_log_probs[i]))
+        total = p if total is None else total + p
+    return total * (1.0 / z.shape[0])
+
+
+def _pair_tables(table, w, flow, mc):
+    """The operands of a relation driver on the table's device: (table, w, bias) -- with ``mc`` the (S, N, h) samples and one
+    bias per sample (``_mc_args``), else the embedding and the scalar flow_log_prob."""
+    if mc:
+        return _mc_args(table, w, flow)
+    emb = table.detach().contiguous()
+    return (emb,) + _on_device(emb, w.detach(), flow)
+
+
+def _pair_type_checked(type_constraint, n, num_rels):
+    if type_constraint is not None and (type_constraint.num_nodes != n or type_constraint.num_rels != num_rels):
+        raise ValueError(f'type_constraint was built for {type_constraint.num_nodes} entities / {type_constraint.num_rels} relations, '
+                         f'the tables hold {n} / {num_rels}')
+
+
+def _rank_relations(table, w, triplets, pair_filter, flow, fused, type_constraint=None, mc=False):
+    """The relation rank driver, fused or materialised, single-draw or (``mc``) posterior-predictive: (raw, filtered or None), with
+    a ``type_constraint`` the four kinds (the filtered ones None without a ``pair_filter``)."""
+    tab, wd, flow = _pair_tables(table, w, flow, mc)
+    dev = tab.device
+    triplets = triplets.to(dev)
     s, r, o = triplets[:, 0], triplets[:, 1], triplets[:, 2]
-    _pair_checked(s, o, r, emb.shape[0], wd.shape[0], pair_filter)
-    raw, filt = [], []
-    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, emb.device, MAX_QUERY_ROWS):
+    _pair_checked(s, o, r, tab.shape[-2], wd.shape[0], pair_filter)
+    _pair_type_checked(type_constraint, tab.shape[-2], wd.shape[0])
+    cand = type_constraint.relation_words(dev) if fused and type_constraint is not None else None
+    n_kinds = 2 if type_constraint is None else 4
+    kinds = [[] for _ in range(n_kinds)]
+    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, dev, MAX_QUERY_ROWS):
         if fused:
-            a, b = ops.pair_relation_scores(emb, wd, s[sl], o[sl], target=r[sl], bias=flow_log_prob, filt_lo=f_lo, filt_hi=f_hi,
-                                            filt_rel=rel, ids_checked=True)[0]
+            score = ops.pair_relation_scores_mc if mc else ops.pair_relation_scores
+            ranks = score(tab, wd, s[sl], o[sl], target=r[sl], bias=flow, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel, cand=cand,
+                          ids_checked=True)[0]
         else:
-            a, b = relation_ranks_from_scores(pair_scores_unfused(emb, wd, s[sl], o[sl], flow_log_prob), r[sl], f_lo, f_hi, rel)
-        raw.append(a)
-        filt.append(b)
-    return (_pair_cat(raw, (), torch.float32, emb.device),
-            None if pair_filter is None else _pair_cat(filt, (), torch.float32, emb.device))
+            value = pair_pbar_unfused(tab, wd, s[sl], o[sl], flow) if mc else pair_scores_unfused(tab, wd, s[sl], o[sl], flow)
+            mask = None if type_constraint is None else type_constraint.pair_mask(s[sl], o[sl], dev)
+            ranks = relation_ranks_from_scores(value, r[sl], f_lo, f_hi, rel, mask)
+        for kind, part in zip(kinds, ranks):
+            kind.append(part)
+    return tuple(None if pair_filter is None and i % 2 else _pair_cat(kind, (), torch.float32, dev) for i, kind in enumerate(kinds))
 
 
-def rank_relations(embedding, w, triplets, pair_filter=None, flow_log_prob=None):
+def rank_relations(embedding, w, triplets, pair_filter=None, flow_log_prob=None, type_constraint=None):
     """Relation prediction, ranks: for every triplet (s, r, o) the 0-based mid-rank of r among ALL relations under ``logit =
     (e_s * e_o) . w_r + flow_log_prob`` -- DistMult's score of the triplet, read as a function of the relation -- raw and, with a
     ``PairFilterIndex``, with the other known relations of the pair left out.  One launch per ``MAX_QUERY_ROWS`` pairs
-    (ops.pair_relation_scores).  Returns ``(raw, filtered or None)``."""
-    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, True)
+    (ops.pair_relation_scores).  Returns ``(raw, filtered or None)``; with a ``TypeConstraint`` ``(raw, filtered, raw_constrained,
+    filtered_constrained)``, the last two among the pair's type-correct relations only (s seen as subject of r and o as object
+    of r), the first two unchanged."""
+    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, True, type_constraint)
 
 
-def rank_relations_unfused(embedding, w, triplets, pair_filter=None, flow_log_prob=None):
+def rank_relations_unfused(embedding, w, triplets, pair_filter=None, flow_log_prob=None, type_constraint=None):
     """``rank_relations`` from materialised logits (``pair_scores_unfused`` + ``mid_ranks``): the in-repo cross-check and the
     bench's comparator, never a fallback."""
-    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, False)
+    return _rank_relations(embedding, w, triplets, pair_filter, flow_log_prob, False, type_constraint)
 
 
-def _calc_relation_mrr(rank, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose):
+def rank_relations_mc(z, w, triplets, pair_filter=None, flow_log_probs=None, type_constraint=None):
+    """``rank_relations`` on the posterior predictive of the samples ``z`` (S, N, h) of ``KGVAE.posterior_samples``
+    (``flow_log_probs``: its second result): every triplet's relation is ranked on ``pbar[r] = mean_s sigmoid((z_s[s] * z_s[o]) .
+    w_r + flow_log_probs[s])`` (ops.pair_relation_scores_mc, one launch per ``MAX_QUERY_ROWS`` pairs).  Mid-ranks: pbar saturates,
+    so ties are real.  Reproducible for a seed of the samples."""
+    return _rank_relations(z, w, triplets, pair_filter, flow_log_probs, True, type_constraint, mc=True)
+
+
+def rank_relations_mc_unfused(z, w, triplets, pair_filter=None, flow_log_probs=None, type_constraint=None):
+    """``rank_relations_mc`` from materialised probabilities (``pair_pbar_unfused`` + ``mid_ranks``): cross-check and comparator."""
+    return _rank_relations(z, w, triplets, pair_filter, flow_log_probs, False, type_constraint, mc=True)
+
+
+RELATION_MC_MRR_LINES = ("MC relation MRR ({0}, {n_samples} samples): {1:.6f}", "MC relation Hits ({0}) @ {1}: {2:.6f}")
+
+
+def _calc_relation_mrr(rank, table, w, test_triplets, pair_filter, hits, flow, verbose, type_constraint=None, mc=False):
     with torch.no_grad():
-        raw, filt = rank(embedding, w, test_triplets, pair_filter, flow_log_prob)
-        none = [raw.new_zeros(0), None if filt is None else raw.new_zeros(0)]       # one direction: nothing on _report's other side
-        return _report([raw, filt], none, CONSTRAINED_KINDS[:2], hits, verbose, RELATION_MRR_LINES)
+        ranks = rank(table, w, test_triplets, pair_filter, flow, type_constraint)
+        none = [None if r is None else r.new_zeros(0) for r in ranks]      # one direction: nothing on _report's other side
+        if mc:
+            return _report(list(ranks), none, CONSTRAINED_KINDS, hits, verbose, RELATION_MC_MRR_LINES, {'n_samples': int(table.shape[0])})
+        return _report(list(ranks), none, CONSTRAINED_KINDS, hits, verbose, RELATION_MRR_LINES)
 
 
-def calc_relation_mrr(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True):
+def calc_relation_mrr(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True,
+                      type_constraint=None):
     """The relation-prediction report over the test triplets (one direction: there is one relation slot): ``mrr_raw`` and
-    ``hits_raw: {k: v}``, and with a ``PairFilterIndex`` ``mrr_filtered`` / ``hits_filtered``."""
-    return _calc_relation_mrr(rank_relations, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose)
+    ``hits_raw: {k: v}``, and with a ``PairFilterIndex`` ``mrr_filtered`` / ``hits_filtered``; with a ``TypeConstraint`` also the
+    ``_constrained`` kinds of ``CONSTRAINED_KINDS``."""
+    return _calc_relation_mrr(rank_relations, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose, type_constraint)
 
 
-def calc_relation_mrr_unfused(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True):
-    return _calc_relation_mrr(rank_relations_unfused, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose)
+def calc_relation_mrr_unfused(embedding, w, test_triplets, pair_filter=None, hits=[1, 3, 10], flow_log_prob=None, verbose=True,
+                              type_constraint=None):
+    return _calc_relation_mrr(rank_relations_unfused, embedding, w, test_triplets, pair_filter, hits, flow_log_prob, verbose,
+                              type_constraint)
 
 
-def _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, fused):
-    emb = embedding.detach().contiguous()
-    wd, flow_log_prob = _on_device(emb, w.detach(), flow_log_prob)
-    s, o = s.to(emb.device), o.to(emb.device)
-    _pair_checked(s, o, None, emb.shape[0], wd.shape[0], pair_filter)
-    ids, logits = [], []
-    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, emb.device, MAX_QUERY_ROWS):
+def calc_relation_mc_mrr(z, w, test_triplets, pair_filter=None, flow_log_probs=None, hits=[1, 3, 10], verbose=True, type_constraint=None):
+    """``calc_relation_mrr`` on the posterior predictive (``rank_relations_mc``): ``n_samples``, then the same keys."""
+    return _calc_relation_mrr(rank_relations_mc, z, w, test_triplets, pair_filter, hits, flow_log_probs, verbose, type_constraint, mc=True)
+
+
+def calc_relation_mc_mrr_unfused(z, w, test_triplets, pair_filter=None, flow_log_probs=None, hits=[1, 3, 10], verbose=True,
+                                 type_constraint=None):
+    return _calc_relation_mrr(rank_relations_mc_unfused, z, w, test_triplets, pair_filter, hits, flow_log_probs, verbose, type_constraint,
+                              mc=True)
+
+
+def _pair_prob_std(z, w, s, o, ids, flp, fused):
+    """The spread of each proposed relation's probability over the samples, (n, k): fused, ``ops.pair_prob_std_mc`` on the stacks
+    ``mul(z[:, s], z[:, o])`` and ``w`` repeated per sample (a real copy: the entry refuses a zero stride), ``MC_STACK_ROWS`` pairs
+    at a time; else from the materialised per-sample probabilities.  Padding ids give 0."""
+    if fused:
+        ws = w.unsqueeze(0).repeat(z.shape[0], 1, 1)
+        parts = [ops.pair_prob_std_mc(ops.mul(z[:, s[lo:lo + MC_STACK_ROWS]].contiguous(), z[:, o[lo:lo + MC_STACK_ROWS]].contiguous()), ws,
+                                      ids[lo:lo + MC_STACK_ROWS], flp) for lo in range(0, s.shape[0], MC_STACK_ROWS)]
+        return _pair_cat(parts, (ids.shape[1],), torch.float32, z.device)
+    pick = ids.clamp(min=0)
+    ps = [torch.sigmoid(pair_scores_unfused(z[i], w, s, o, None if flp is None else flp[i])).gather(1, pick) for i in range(z.shape[0])]
+    sd = torch.stack(ps).std(dim=0, unbiased=False)
+    sd[ids < 0] = 0.0
+    return sd
+
+
+def _predict_relations(table, w, s, o, k, pair_filter, flow, fused, type_constraint=None, mc=False):
+    tab, wd, flow = _pair_tables(table, w, flow, mc)
+    dev = tab.device
+    s, o = s.to(dev), o.to(dev)
+    _pair_checked(s, o, None, tab.shape[-2], wd.shape[0], pair_filter)
+    _pair_type_checked(type_constraint, tab.shape[-2], wd.shape[0])
+    cand = type_constraint.relation_words(dev) if fused and type_constraint is not None else None
+    ids, values, std = [], [], []
+    for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, dev, MAX_QUERY_ROWS):
         if fused:
-            i, l = ops.pair_relation_scores(emb, wd, s[sl], o[sl], k=k, bias=flow_log_prob, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
-                                            ids_checked=True)[1]
+            score = ops.pair_relation_scores_mc if mc else ops.pair_relation_scores
+            i, l = score(tab, wd, s[sl], o[sl], k=k, bias=flow, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel, cand=cand, ids_checked=True)[1]
         else:
-            i, l = topk_from_scores(pair_scores_unfused(emb, wd, s[sl], o[sl], flow_log_prob), k, f_lo, f_hi, rel)
+            value = pair_pbar_unfused(tab, wd, s[sl], o[sl], flow) if mc else pair_scores_unfused(tab, wd, s[sl], o[sl], flow)
+            mask = None if type_constraint is None else type_constraint.pair_mask(s[sl], o[sl], dev)
+            i, l = topk_from_scores(value, k, f_lo, f_hi, rel, cand=mask)
         ids.append(i)
-        logits.append(l)
-    return _pair_cat(ids, (int(k),), torch.int64, emb.device), _pair_cat(logits, (int(k),), torch.float32, emb.device)
+        values.append(l)
+        if mc:
+            std.append(_pair_prob_std(tab, wd, s[sl], o[sl], i, flow, fused))
+    out = _pair_cat(ids, (int(k),), torch.int64, dev), _pair_cat(values, (int(k),), torch.float32, dev)
+    return out + (_pair_cat(std, (int(k),), torch.float32, dev),) if mc else out
 
 
-def predict_relations(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None):
+def predict_relations(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None, type_constraint=None):
     """Relation prediction, proposals: the ``k`` most plausible relations between ``s[i]`` and ``o[i]`` at ``rank_relations``'
-    logits, the pair's known relations (``pair_filter``) left out.  Returns ``(ids int64 (n, k), logits float32 (n, k))`` in the
-    order of ``topk_from_scores``, padded with -1 / -inf when fewer than k relations are left."""
-    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, True)
+    logits, the pair's known relations (``pair_filter``) left out -- with a ``TypeConstraint`` among the pair's type-correct
+    relations only.  Returns ``(ids int64 (n, k), logits float32 (n, k))`` in the order of ``topk_from_scores``, padded with
+    -1 / -inf when fewer than k relations are left."""
+    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, True, type_constraint)
 
 
-def predict_relations_unfused(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None):
+def predict_relations_unfused(embedding, w, s, o, k, pair_filter=None, flow_log_prob=None, type_constraint=None):
     """``predict_relations`` from materialised logits (``pair_scores_unfused`` + ``topk_from_scores``): cross-check and comparator."""
-    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, False)
+    return _predict_relations(embedding, w, s, o, k, pair_filter, flow_log_prob, False, type_constraint)
+
+
+def predict_relations_mc(z, w, s, o, k, pair_filter=None, flow_log_probs=None, type_constraint=None):
+    """``predict_relations`` on the posterior predictive of the samples ``z`` (S, N, h): the ``k`` relations of highest ``pbar``
+    (``rank_relations_mc``'s value) and how sure the model is of each.  Returns ``(ids int64 (n, k), prob_mean float32 (n, k),
+    prob_std float32 (n, k))``, ``prob_std`` the population standard deviation of the relation's probability over the samples
+    (ops.pair_prob_std_mc on the proposed ids); padding is -1 / -inf / 0."""
+    return _predict_relations(z, w, s, o, k, pair_filter, flow_log_probs, True, type_constraint, mc=True)
+
+
+def predict_relations_mc_unfused(z, w, s, o, k, pair_filter=None, flow_log_probs=None, type_constraint=None):
+    """``predict_relations_mc`` from materialised probabilities (``pair_pbar_unfused`` + ``topk_from_scores``)."""
+    return _predict_relations(z, w, s, o, k, pair_filter, flow_log_probs, False, type_constraint, mc=True)

@@ -217,26 +217,39 @@ def write_profile_lines(path, entities, route, rows=PROFILE_ROWS):
 
 def write_relation_lines(path, triplets, route, rows=PROFILE_ROWS):
     """The loop of the relation-prediction writers (this file's and transe.py's): one block per triplet, in order, ``rows`` pairs per
-    call of ``route(s, o)`` -> ``(ids, values)`` (each (m, k), best first), as TSV ``subject  object  position  predicted_relation
-    value`` -- the formatting of the top-k prediction files (position from 0, the value as ``:.9g``, padding slots written with
-    their id -1).  Returns the number of lines written."""
+    call of ``route(s, o)`` -> ``(ids, *value_columns)`` (each (m, k), best first), as TSV ``subject  object  position
+    predicted_relation  value...`` -- the formatting of the top-k prediction files (position from 0, every value as ``:.9g``, padding
+    slots written with their id -1).  Returns the number of lines written."""
     n_lines = 0
     with torch.no_grad(), open(path, 'w') as f:
         for at in range(0, triplets.shape[0], rows):
             s, o = triplets[at:at + rows, 0], triplets[at:at + rows, 2]
-            ids, values = route(s, o)
-            for a, b, row_ids, row_values in zip(s.tolist(), o.tolist(), ids.tolist(), values.tolist()):
+            ids, *values = route(s, o)
+            for a, b, row_ids, *row_values in zip(s.tolist(), o.tolist(), ids.tolist(), *(v.tolist() for v in values)):
                 head = f"{a}\t{b}\t"
-                f.writelines(f"{head}{p}\t{e}\t{x:.9g}\n" for p, (e, x) in enumerate(zip(row_ids, row_values)))
+                f.writelines(f"{head}{p}\t{e}\t" + '\t'.join(f"{x:.9g}" for x in xs) + '\n'
+                             for p, (e, *xs) in enumerate(zip(row_ids, *row_values)))
                 n_lines += len(row_ids)
     return n_lines
 
 
-def write_relation_predictions(path, embed, w, triplets, k, pair_filter, flow_log_prob=None):
+def write_relation_predictions(path, embed, w, triplets, k, pair_filter, flow_log_prob=None, type_constraint=None):
     """The ``k`` most plausible NEW relations of every triplet's pair (ranking.predict_relations; ``pair_filter``: the pair's known
     relations left out) as TSV: ``subject  object  position  predicted_relation  logit``, one block of k lines per triplet, in
-    order; a pair with fewer than k relations left ends in id -1, logit -inf.  Returns the number of lines written."""
-    return write_relation_lines(path, triplets, lambda s, o: ranking.predict_relations(embed, w, s, o, k, pair_filter, flow_log_prob))
+    order; a pair with fewer than k relations left ends in id -1, logit -inf.  With a ``type_constraint`` (ranking.TypeConstraint)
+    only type-correct relations are written, in the same columns.  Returns the number of lines written."""
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    return write_relation_lines(path, triplets, lambda s, o: ranking.predict_relations(embed, w, s, o, k, pair_filter, flow_log_prob,
+                                                                                       **constrained))
+
+
+def write_mc_relation_predictions(path, z, w, triplets, k, pair_filter, flow_log_probs=None, type_constraint=None):
+    """``write_relation_predictions`` under the posterior predictive of the samples ``z`` (S, N, h) (ranking.predict_relations_mc), as
+    TSV: ``subject  object  position  predicted_relation  prob_mean  prob_std`` -- the first three columns join with the single-draw
+    file; a pair with fewer than k relations left ends in id -1, mean -inf, std 0.  Returns the number of lines written."""
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    return write_relation_lines(path, triplets, lambda s, o: ranking.predict_relations_mc(z, w, s, o, k, pair_filter, flow_log_probs,
+                                                                                          **constrained))
 
 
 def write_entity_profiles(path, embed, w, entities, k, filter_index, flow_log_prob=None, type_constraint=None):
@@ -329,6 +342,15 @@ def check_args(args):
         raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
     if not 0 <= getattr(args, 'predict_relations', 0) <= ops.TOPK_MAX:
         raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
+    relations = getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0
+    if getattr(args, 'relations_typed', False) and not relations:
+        raise ValueError('--relations-typed restricts the relation queries: it needs --relation-eval or --predict-relations')
+    if getattr(args, 'mc_relations', False):
+        if not getattr(args, 'mc_samples', 0) > 0:
+            raise ValueError('--mc-relations answers the relation queries on the posterior predictive: it needs --mc-samples S > 0')
+        if not relations:
+            raise ValueError('--mc-relations writes the posterior-predictive form of the relation queries: it needs --relation-eval '
+                             'or --predict-relations')
     wants = [f for f, on in (('--relation-eval', getattr(args, 'relation_eval', False)),
                              ('--predict-relations', getattr(args, 'predict_relations', 0) > 0),
                              ('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
@@ -450,14 +472,18 @@ def main(args):
                   f"{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}")
         if getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0:
             pairs = ranking.PairFilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            rel_types = None
+            if getattr(args, 'relations_typed', False):    # (--type-constrain's sets are the same ones, when it is given as well)
+                rel_types = types if types is not None else \
+                    ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             if getattr(args, 'relation_eval', False):
                 ranking.calc_relation_mrr(embed, model.w_relation, test_t, pairs if filters is not None else None, hits=[1, 3, 10],
-                                          flow_log_prob=model.encoder.get_flow_log_prob())
+                                          flow_log_prob=model.encoder.get_flow_log_prob(), type_constraint=rel_types)
             if getattr(args, 'predict_relations', 0) > 0:
                 n_lines = write_relation_predictions(args.relations_out, embed, model.w_relation, test_t, args.predict_relations,
-                                                     pairs, model.encoder.get_flow_log_prob())
-                print(f"wrote {n_lines} relation predictions (top {args.predict_relations} per test pair, known relations filtered) "
-                      f"to {args.relations_out}")
+                                                     pairs, model.encoder.get_flow_log_prob(), rel_types)
+                print(f"wrote {n_lines} relation predictions (top {args.predict_relations} {'type-correct ' if rel_types is not None else ''}"
+                      f"per test pair, known relations filtered) to {args.relations_out}")
         if getattr(args, 'complete_topk', 0) > 0 or getattr(args, 'complete_threshold', None) is not None:
             known = filters if filters is not None else \
                 ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -508,6 +534,16 @@ def main(args):
                 typed_note = ", type-correct entities only" if mc_types is not None else ""
                 print(f"wrote {n_lines} posterior-predictive predictions (top {args.predict_topk}, both directions, known "
                       f"triplets filtered{typed_note}, mean and spread over {args.mc_samples} samples) to {args.mc_predict_out}")
+            if getattr(args, 'mc_relations', False):
+                if getattr(args, 'relation_eval', False):
+                    ranking.calc_relation_mc_mrr(z, model.w_relation, test_t, pairs if filters is not None else None, flps,
+                                                 hits=[1, 3, 10], type_constraint=rel_types)
+                if getattr(args, 'predict_relations', 0) > 0:
+                    n_lines = write_mc_relation_predictions(args.mc_relations_out, z, model.w_relation, test_t, args.predict_relations,
+                                                            pairs, flps, rel_types)
+                    print(f"wrote {n_lines} posterior-predictive relation predictions (top {args.predict_relations} "
+                          f"{'type-correct ' if rel_types is not None else ''}per test pair, known relations filtered, mean and spread "
+                          f"over {args.mc_samples} samples) to {args.mc_relations_out}")
             if getattr(args, 'mc_complete', False):
                 known = filters if filters is not None else \
                     ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
@@ -718,6 +754,16 @@ def build_parser():
     p.add_argument("--predict-relations", type=int, default=0,
                    help="with --test-mode: write the K (1..128) most plausible NEW relations between subject and object of every test "
                         "triplet (the pair's train + valid + test relations left out) to --relations-out; 0 = off")
+    p.add_argument("--relations-typed", action="store_true",
+                   help="with --relation-eval / --predict-relations: also report the ranks among the TYPE-CORRECT relations of each "
+                        "pair (the subject seen as subject of the relation, the object as its object, in train + valid + test) and "
+                        "propose only those")
+    p.add_argument("--mc-relations", action="store_true",
+                   help="with --mc-samples S and --relation-eval / --predict-relations: the relation report and proposals on the "
+                        "posterior predictive as well (honours --relations-typed)")
+    p.add_argument("--mc-relations-out", type=str, default="mc_relation_predictions.tsv",
+                   help="TSV written by --mc-relations with --predict-relations: subject, object, position, predicted relation, "
+                        "prob_mean, prob_std; joins with --relations-out on the first three columns")
     p.add_argument("--relations-out", type=str, default="relation_predictions.tsv",
                    help="TSV of --predict-relations: subject, object, position, predicted relation, logit")
     p.add_argument("--profile-topk", type=int, default=0,

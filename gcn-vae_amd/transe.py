@@ -70,7 +70,9 @@ at distance ``||(n(o) - n(s)) - n(r)||_p`` -- in exact arithmetic the triplet's 
 for it: the operands are associated differently --, raw and with a ``ranking.PairFilterIndex`` filtered, and
 ``predict_relations`` proposes the k nearest new relations of a pair, from ``ops.transe_pair_relations`` (gv_transe_pair_rel: one
 launch, the query row formed while it is staged, every relation tile walked by the workgroup that owns the pairs).  The
-``*_unfused`` twins (``ops.transe_distances`` + ``topk_from_distances``) are the cross-check.  ``--relation-eval`` adds the report
+``*_unfused`` twins (``ops.transe_distances`` + ``topk_from_distances``) are the cross-check.  With a ``type_constraint``
+(``--relations-typed``) the three also answer among the pair's type-correct relations (gv_transe_pair_rel_constrained: the AND of two
+rows of ``TypeConstraint.relation_words``; the keys get ``_constrained``).  ``--relation-eval`` adds the report
 (with ``--filtered-eval`` the filtered figures too), ``--predict-relations K --relations-out FILE`` write train.py's relation TSV
 layout, the distance in place of the logit.  Relation-corrupted training negatives (``--neg-rel``) stay refused.
 
@@ -672,7 +674,13 @@ def pair_distances_unfused(en, rn, s, o, p_norm):
     return ops.transe_distances((en[o] - en[s]).contiguous(), rn, p_norm)
 
 
-def _rank_relations(model_or_tables, triplets, pair_filter, fused):
+def _pair_type_checked(type_constraint, n, num_rels):
+    if type_constraint is not None and (type_constraint.num_nodes != n or type_constraint.num_rels != num_rels):
+        raise ValueError(f'type_constraint was built for {type_constraint.num_nodes} entities / {type_constraint.num_rels} relations, '
+                         f'the tables hold {n} / {num_rels}')
+
+
+def _rank_relations(model_or_tables, triplets, pair_filter, fused, type_constraint=None):
     with torch.no_grad():
         en, rn, p_norm = _pair_tables(model_or_tables)
         if not isinstance(triplets, torch.Tensor):
@@ -680,84 +688,101 @@ def _rank_relations(model_or_tables, triplets, pair_filter, fused):
         triplets = triplets.to(device=en.device, dtype=torch.long).reshape(-1, 3)
         s, r, o = triplets[:, 0], triplets[:, 1], triplets[:, 2]
         _pair_checked(s, o, r, en.shape[0], rn.shape[0], pair_filter)
-        raw, filt = [], []
+        _pair_type_checked(type_constraint, en.shape[0], rn.shape[0])
+        cand = type_constraint.relation_words(en.device) if fused and type_constraint is not None else None
+        kinds = [[] for _ in range(2 if type_constraint is None else 4)]
         for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, en.device, MAX_QUERY_ROWS):
             if fused:
-                a, b = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, target=r[sl], filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
-                                                 ids_checked=True)[0]
+                ranks = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, target=r[sl], filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
+                                                  cand=cand, ids_checked=True)[0]
             else:
-                a, b = relation_ranks_from_scores(-pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), r[sl], f_lo, f_hi, rel)
-            raw.append(a)
-            filt.append(b)
-        return (_pair_cat(raw, (), torch.float32, en.device),
-                None if pair_filter is None else _pair_cat(filt, (), torch.float32, en.device))
+                mask = None if type_constraint is None else type_constraint.pair_mask(s[sl], o[sl], en.device)
+                ranks = relation_ranks_from_scores(-pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), r[sl], f_lo, f_hi, rel, mask)
+            for kind, part in zip(kinds, ranks):
+                kind.append(part)
+        return tuple(None if pair_filter is None and i % 2 else _pair_cat(kind, (), torch.float32, en.device)
+                     for i, kind in enumerate(kinds))
 
 
-def rank_relations(model_or_tables, triplets, pair_filter=None):
+def rank_relations(model_or_tables, triplets, pair_filter=None, type_constraint=None):
     """Relation prediction, ranks: for every triplet (s, r, o) the 0-based mid-rank of r among ALL relations at distance
     ``||(n(o) - n(s)) - n(r)||_p`` -- in exact arithmetic the triplet's ``||n(s) + n(r) - n(o)||``, though not the bit pattern
     ``predict_topk`` reports for it (the operands are associated differently) -- raw and, with a ``ranking.PairFilterIndex``,
     with the pair's other known relations left out.  One launch per ``MAX_QUERY_ROWS`` pairs (ops.transe_pair_relations).
-    Returns ``(raw, filtered or None)``."""
-    return _rank_relations(model_or_tables, triplets, pair_filter, True)
+    Returns ``(raw, filtered or None)``; with a ``ranking.TypeConstraint`` ``(raw, filtered, raw_constrained,
+    filtered_constrained)``, the last two among the pair's type-correct relations only, the first two unchanged."""
+    return _rank_relations(model_or_tables, triplets, pair_filter, True, type_constraint)
 
 
-def rank_relations_unfused(model_or_tables, triplets, pair_filter=None):
+def rank_relations_unfused(model_or_tables, triplets, pair_filter=None, type_constraint=None):
     """``rank_relations`` from materialised distances (``ops.transe_distances`` + ``ranking.mid_ranks``): the in-repo cross-check
     and the bench's comparator, never a fallback."""
-    return _rank_relations(model_or_tables, triplets, pair_filter, False)
+    return _rank_relations(model_or_tables, triplets, pair_filter, False, type_constraint)
 
 
-def evaluate_relations(model_or_tables, triplets, pair_filter=None, hits=(1, 3, 10), unfused=False, verbose=True):
+def evaluate_relations(model_or_tables, triplets, pair_filter=None, hits=(1, 3, 10), unfused=False, verbose=True, type_constraint=None):
     """The relation-prediction report (one direction: there is one relation slot): {'mrr_raw', 'mr_raw', 'hits_raw': {k: v}} plus
-    the same '_filtered' keys with a ``ranking.PairFilterIndex`` -- ``evaluate``'s key style."""
-    raw, filt = (rank_relations_unfused if unfused else rank_relations)(model_or_tables, triplets, pair_filter)
+    the same '_filtered' keys with a ``ranking.PairFilterIndex`` -- ``evaluate``'s key style; with a ``ranking.TypeConstraint``
+    also the '_raw_constrained' keys (and '_filtered_constrained' ones with a filter)."""
+    ranks = (rank_relations_unfused if unfused else rank_relations)(model_or_tables, triplets, pair_filter, type_constraint)
+    raw, filt = ranks[:2]
     out = _summary(raw, raw if filt is None else filt, hits)
+    kinds = ('raw', 'filtered')
+    if type_constraint is not None:
+        out.update(_summary(ranks[2], ranks[2] if filt is None else ranks[3], hits, '_constrained'))
+        kinds = kinds + tuple(k + '_constrained' for k in kinds)
     if filt is None:
         out = {k: v for k, v in out.items() if '_filtered' not in k}
+        kinds = tuple(k for k in kinds if not k.startswith('filtered'))
     if verbose:
-        for kind in ('raw', 'filtered') if filt is not None else ('raw',):
+        for kind in kinds:
             print('Relation MRR ({}): {:.6f} | MR ({}): {:.3f}'.format(kind, out['mrr_' + kind], kind, out['mr_' + kind]))
             for h in hits:
                 print('Relation Hits ({}) @ {}: {:.6f}'.format(kind, h, out['hits_' + kind][h]))
     return out
 
 
-def _predict_relations(model_or_tables, s, o, k, pair_filter, fused):
+def _predict_relations(model_or_tables, s, o, k, pair_filter, fused, type_constraint=None):
     with torch.no_grad():
         en, rn, p_norm = _pair_tables(model_or_tables)
         s, o = s.to(en.device), o.to(en.device)
         _pair_checked(s, o, None, en.shape[0], rn.shape[0], pair_filter)
+        _pair_type_checked(type_constraint, en.shape[0], rn.shape[0])
+        cand = type_constraint.relation_words(en.device) if fused and type_constraint is not None else None
         ids, dist = [], []
         for sl, f_lo, f_hi, rel in _pair_chunks(s, o, pair_filter, en.device, MAX_QUERY_ROWS):
             if fused:
-                i, d = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, k=k, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel,
+                i, d = ops.transe_pair_relations(en, rn, s[sl], o[sl], p_norm, k=k, filt_lo=f_lo, filt_hi=f_hi, filt_rel=rel, cand=cand,
                                                  ids_checked=True)[1]
             else:
-                i, d = topk_from_distances(pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), k, f_lo, f_hi, rel)
+                mask = None if type_constraint is None else type_constraint.pair_mask(s[sl], o[sl], en.device)
+                i, d = topk_from_distances(pair_distances_unfused(en, rn, s[sl], o[sl], p_norm), k, f_lo, f_hi, rel, cand=mask)
             ids.append(i)
             dist.append(d)
         return _pair_cat(ids, (int(k),), torch.int64, en.device), _pair_cat(dist, (int(k),), torch.float32, en.device)
 
 
-def predict_relations(model_or_tables, s, o, k, pair_filter=None):
+def predict_relations(model_or_tables, s, o, k, pair_filter=None, type_constraint=None):
     """Relation prediction, proposals: the ``k`` nearest relations between ``s[i]`` and ``o[i]`` at ``rank_relations``' distances,
-    the pair's known relations (``pair_filter``) left out.  Returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of
-    ``topk_from_distances``, padded with -1 / +inf when fewer than k relations are left."""
-    return _predict_relations(model_or_tables, s, o, k, pair_filter, True)
+    the pair's known relations (``pair_filter``) left out -- with a ``ranking.TypeConstraint`` among the pair's type-correct
+    relations only.  Returns ``(ids int64 (n, k), dist float32 (n, k))`` in the order of ``topk_from_distances``, padded with
+    -1 / +inf when fewer than k relations are left."""
+    return _predict_relations(model_or_tables, s, o, k, pair_filter, True, type_constraint)
 
 
-def predict_relations_unfused(model_or_tables, s, o, k, pair_filter=None):
+def predict_relations_unfused(model_or_tables, s, o, k, pair_filter=None, type_constraint=None):
     """``predict_relations`` from materialised distances (``ops.transe_distances`` + ``topk_from_distances``)."""
-    return _predict_relations(model_or_tables, s, o, k, pair_filter, False)
+    return _predict_relations(model_or_tables, s, o, k, pair_filter, False, type_constraint)
 
 
-def write_relation_predictions(path, model_or_tables, triplets, k, pair_filter):
+def write_relation_predictions(path, model_or_tables, triplets, k, pair_filter, type_constraint=None):
     """The ``k`` nearest NEW relations of every triplet's pair as TSV in train.py's layout: ``subject  object  position
     predicted_relation  distance``, one block of k lines per triplet, in order; a pair with fewer than k relations left ends in
-    id -1, distance inf.  Returns the number of lines written."""
+    id -1, distance inf.  With a ``type_constraint`` only type-correct relations are written.  Returns the number of lines
+    written."""
     triplets = torch.as_tensor(np.asarray(triplets), dtype=torch.long).reshape(-1, 3)
-    return write_relation_lines(path, triplets, lambda s, o: predict_relations(model_or_tables, s, o, k, pair_filter))
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    return write_relation_lines(path, triplets, lambda s, o: predict_relations(model_or_tables, s, o, k, pair_filter, **constrained))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -998,6 +1023,10 @@ def build_parser():
     p.add_argument('--predict-relations', type=int, default=0,
                    help='after the final evaluation write the K (1..128) nearest NEW relations between subject and object of every '
                         'test triplet (the pair\'s train + valid + test relations left out) to --relations-out; 0 = off')
+    p.add_argument('--relations-typed', action='store_true',
+                   help='with --relation-eval / --predict-relations: also report the ranks among the TYPE-CORRECT relations of each pair '
+                        '(the subject seen as subject of the relation, the object as its object, in train + valid + test) and propose '
+                        'only those')
     p.add_argument('--relations-out', type=str, default='transe_relation_predictions.tsv',
                    help='TSV written by --predict-relations: subject, object, position, predicted relation, distance; the first four '
                         'columns are those of train.py\'s --relations-out')
@@ -1060,6 +1089,8 @@ def check_args(args):
         raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
     if not 0 <= getattr(args, 'predict_relations', 0) <= ops.TOPK_MAX:
         raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
+    if getattr(args, 'relations_typed', False) and not (getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0):
+        raise ValueError('--relations-typed restricts the relation queries: it needs --relation-eval or --predict-relations')
 
 
 def main(args):
@@ -1119,12 +1150,16 @@ def main(args):
               f'known triplets filtered) to {args.complete_out}')
     if getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0:
         pairs = PairFilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        typed = None
+        if getattr(args, 'relations_typed', False):
+            typed = types if types is not None else \
+                TypeConstraint(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
         if getattr(args, 'relation_eval', False):
-            out['relations'] = evaluate_relations(model, data.test, pairs if args.filtered_eval else None)
+            out['relations'] = evaluate_relations(model, data.test, pairs if args.filtered_eval else None, type_constraint=typed)
         if getattr(args, 'predict_relations', 0) > 0:
-            n_lines = write_relation_predictions(args.relations_out, model, data.test, args.predict_relations, pairs)
-            print(f'wrote {n_lines} relation predictions (nearest {args.predict_relations} per test pair, known relations filtered) to '
-                  f'{args.relations_out}')
+            n_lines = write_relation_predictions(args.relations_out, model, data.test, args.predict_relations, pairs, typed)
+            print(f'wrote {n_lines} relation predictions (nearest {args.predict_relations} {"type-correct " if typed is not None else ""}'
+                  f'per test pair, known relations filtered) to {args.relations_out}')
     if who is not None:
         known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
         typed = None

@@ -628,6 +628,42 @@ int gv_pair_rel_scores(const float* e, int ld_e, int n, const float* w, int ld_w
                        int n_filt_rel, int k, float* tgt, int* count_raw, int* count_filt, int* out_ids, float* out_logits, int m,
                        int h, void* stream);
 
+/* gv_pair_rel_scores among the TYPE-CORRECT relations of each pair.  cand is a relation bitmask of n_sets >= 2 n rows of
+ * ld_cand >= ceil(num_rels / 32) 32-bit words (ranking.TypeConstraint.relation_words): relation r is bit r & 31 of word r >> 5,
+ * row e holds the relations entity e was seen as subject of, row n + e those it was seen as object of.  The set of pair i is the
+ * AND of rows s_i and n + o_i -- no set id per row; the kernel reads two words of each row per 64-relation tile, once, and never
+ * looks at a bit at a column >= num_rels.
+ *   target given: count_raw_c[i] / count_filt_c[i] are count_raw / count_filt taken over the type-correct relations only
+ *     (gv_rank_scores_constrained's rules: the target itself is never counted, type-correct or not; no type-correct relation
+ *     besides the target gives 0).  count_filt_c is required exactly when a filter and targets are given; count_raw_c may be NULL.
+ *     tgt, count_raw and count_filt equal gv_pair_rel_scores' bit for bit.
+ *   k >= 1: the candidates are the type-correct relations less the listed ones; order, ties, NaN and padding as above.
+ * The checks are gv_pair_rel_scores' in its order, the bitmask's (geometry: GV_ERR_SHAPE, then NULL cand: GV_ERR_NULL) after the
+ * filter's.  One launch, no workspace, no atomics. */
+int gv_pair_rel_scores_constrained(const float* e, int ld_e, int n, const float* w, int ld_w, int num_rels, const int32_t* s,
+                                   const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo, const int* filt_hi,
+                                   const int* filt_rel, int n_filt_rel, const uint32_t* cand, int ld_cand, int n_sets, int k, float* tgt,
+                                   int* count_raw, int* count_filt, int* count_raw_c, int* count_filt_c, int* out_ids,
+                                   float* out_logits, int m, int h, void* stream);
+
+/* gv_pair_rel_scores on the Monte-Carlo posterior predictive of n_samples entity tables: sample s reads e + s * e_stride (elements;
+ * ld_e shared; n_samples >= 1, and with more than one sample e_stride >= (n - 1) * ld_e + h), the one w, bias[s] (bias NULL: none;
+ * else n_samples values).  The value ranked and selected is
+ *   pbar[i, r] = (sum over s ascending of sig((e_s[s_i] * e_s[o_i]) . w[r] + bias[s])) * (1.0f / n_samples)
+ * with gv_rank_scores_mc's sig, kept in the accumulator registers and selected once per tile: bit for bit what gv_rank_scores_mc /
+ * gv_topk_scores_mc give for the query stack gv_mul(e_s[s], e_s[o]) against w repeated per sample.  tgt[i] is the target's pbar;
+ * ranks are mid-ranks (pbar saturates: ties are real), NaN never optimistic; out_prob is padded with -inf.  The _constrained form
+ * adds gv_pair_rel_scores_constrained's bitmask, counts and list rule.  One launch, no workspace, no atomics. */
+int gv_pair_rel_scores_mc(const float* e, int ld_e, int64_t e_stride, int n_samples, int n, const float* w, int ld_w, int num_rels,
+                          const int32_t* s, const int32_t* o, const int32_t* target, const float* bias, const int* filt_lo,
+                          const int* filt_hi, const int* filt_rel, int n_filt_rel, int k, float* tgt, int* count_raw, int* count_filt,
+                          int* out_ids, float* out_prob, int m, int h, void* stream);
+int gv_pair_rel_scores_mc_constrained(const float* e, int ld_e, int64_t e_stride, int n_samples, int n, const float* w, int ld_w,
+                                      int num_rels, const int32_t* s, const int32_t* o, const int32_t* target, const float* bias,
+                                      const int* filt_lo, const int* filt_hi, const int* filt_rel, int n_filt_rel, const uint32_t* cand,
+                                      int ld_cand, int n_sets, int k, float* tgt, int* count_raw, int* count_filt, int* count_raw_c,
+                                      int* count_filt_c, int* out_ids, float* out_prob, int m, int h, void* stream);
+
 /* Monte-Carlo posterior-predictive ranking and top-k for a variational encoder: S posterior samples instead of one draw.
  * Sample s has a query matrix Q_s (m, h) at q + s * q_stride and an entity table E_s (v, h) at e + s * e_stride (strides in
  * elements; the leading dimensions ld_q / ld_e are shared by the samples) and an optional bias[s] (that draw's flow_log_prob;
@@ -929,6 +965,14 @@ int gv_transe_pair_rel(const float* en, const float* rn, int n, int num_rels, in
                        const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_rel, int n_filt_rel,
                        int k, float* tgt, int32_t* count_raw, int32_t* count_filt, int64_t* out_ids, float* out_dist, int m,
                        void* stream);
+
+/* gv_transe_pair_rel among the type-correct relations of each pair: the bitmask, the two extra counts, the list rule and the checks
+ * of gv_pair_rel_scores_constrained; distances, tgt, count_raw and count_filt are gv_transe_pair_rel's bit for bit. */
+int gv_transe_pair_rel_constrained(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* s,
+                                   const int32_t* o, const int32_t* target, const int32_t* filt_lo, const int32_t* filt_hi,
+                                   const int32_t* filt_rel, int n_filt_rel, const uint32_t* cand, int ld_cand, int n_sets, int k,
+                                   float* tgt, int32_t* count_raw, int32_t* count_filt, int32_t* count_raw_c, int32_t* count_filt_c,
+                                   int64_t* out_ids, float* out_dist, int m, void* stream);
 
 /* Whole-graph triplet mining for TransE (csrc/k_transe_mine.hip): every (s, r, o) of the dense tables en (n, dim) and rn (num_rels,
  * dim), both as gv_transe_queries with rel == NULL writes them (the normalised tables; the raw ones without norm_flag):
