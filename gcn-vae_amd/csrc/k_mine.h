@@ -26,6 +26,9 @@
 // where a candidate's ids come from (the member lists, MineTyped) and the filter: gathered tiles do not fit the per-tile-pair
 // buckets, so a workgroup reads the (lo, hi, ent) ranges of its 64 subjects directly (mine_typed_filter).
 //
+// The by-relation sweeps keep all of this and give every relation its own selection: a MineSelect narrowed to the relation's slot
+// (MineSlots, mine_slot_select) is what mine_select16 then sees.
+//
 // Host side: an entry states its selection arguments once, as a MineCall; mine_prepare / mine_typed_prepare check them and queue
 // what precedes the sweep, mine_launch raises the kernel's LDS limit and launches it.
 #pragma once
@@ -76,6 +79,20 @@ struct MineTyped {
     int n_filt_ent;
 };
 
+// ---- selection state PER RELATION (gv_mine_scores_by_relation, gv_mine_scores_typed_by_relation) ------------------------------------
+// A slot i is one relation rels[i] with its own threshold, prefix, counter, histogram and output segment; the pass's MineSelect
+// carries what the slots share (sizes, level, the filter, the bases of out / counter / hist).  An id outside [0, num_rels): the slot
+// is empty this pass.
+constexpr int MINE_SLOT_HIST_BITS = 8;         // bins of the whole-graph form's per-relation LDS histogram (flushed per relation)
+
+struct MineSlots {
+    const int* rels;                   // [m]
+    int m;
+    const unsigned* key_min;           // [m], EMIT
+    const unsigned* prefix;            // [m], HIST (not read at prefix_bits 0)
+    const long long* out_base;         // [m + 1], EMIT: slot i's records go to out[out_base[i] .. out_base[i + 1])
+};
+
 // ---- host side, compiled once (k_mine.hip) -----------------------------------------------------------------------------------
 // bytes of the re-bucketed filter of an n-entity table with n_filt_ent listed objects (0 for an empty table)
 int64_t mine_filter_workspace_bytes(int n, int n_filt_ent);
@@ -104,10 +121,18 @@ struct MineCall {
 int mine_select_args(const MineCall& c, MineSelect* sel);
 
 // What the two type-constrained entries do before their launch: mine_select_args, the checks of the member lists and the unit list,
-// *ty filled, the counter (EMIT) or the histogram (HIST) cleared on the stream.  GV_OK: launch n_units workgroups, unless n == 0 or
-// n_units == 0.
+// *ty filled, the counter (EMIT) or the histogram (HIST) -- of each of `slots` selections -- cleared on the stream.  GV_OK: launch
+// n_units workgroups, unless n == 0 or n_units == 0.
 int mine_typed_prepare(const MineCall& c, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
-                       MineSelect* sel, MineTyped* ty);
+                       MineSelect* sel, MineTyped* ty, int slots = 1);
+
+// What the two by-relation entries check of their slots (after mine_select_args on the shared arguments): 1 <= m <= num_rels, HIST
+// levels of at most max_bin_bits bits whose m << bin_bits histogram words stay within MINE_SLOT_HIST_WORDS, and (n > 0) the
+// per-slot arrays of the mode; *sl filled.  The arrays' contents are device memory: an id outside [0, num_rels) is an empty slot,
+// a segment is clamped into out, a prefix that is no prefix matches nothing.
+constexpr long long MINE_SLOT_HIST_WORDS = 1LL << 24;
+int mine_slots_args(const MineCall& c, const int32_t* rels, int m, const uint32_t* key_min, const uint32_t* prefix,
+                    const int64_t* out_base, int max_bin_bits, MineSlots* sl);
 
 // What the two whole-graph entries do before their launch: mine_select_args, then
 // *sel completed (rel_span: about four workgroups per CU of the MI355X when the table has few tiles; the result does not depend on
@@ -271,6 +296,55 @@ __device__ __forceinline__ void mine_hist_flush(const unsigned* hist_s, const Mi
     for (int i = t; i < (1 << sel.bin_bits); i += 256) {
         const unsigned c = hist_s[i];
         if (c) atomicAdd(sel.hist + i, (unsigned long long)c);
+    }
+}
+
+// ---- device side: a slot's selection -----------------------------------------------------------------------------------------------
+// The per-slot arrays are uniform over the workgroup: one lane's load, broadcast, so that the values live in SGPRs.
+__device__ __forceinline__ unsigned mine_uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ long long mine_uniform(long long v) {
+    const unsigned lo = mine_uniform((unsigned)v), hi = mine_uniform((unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// relation of slot i, or -1 for an empty slot (i outside [0, m) or an id outside [0, num_rels))
+__device__ __forceinline__ int mine_slot_relation(const MineSlots& sl, int i, int num_rels) {
+    if ((unsigned)i >= (unsigned)sl.m) return -1;
+    const int r = (int)mine_uniform((unsigned)sl.rels[i]);
+    return (unsigned)r < (unsigned)num_rels ? r : -1;
+}
+
+// The pass's selection narrowed to slot i, read once per relation: its prefix and histogram (HIST) or its threshold, counter and
+// output segment (EMIT; the segment clamped into out [0, capacity), the counter keeps counting past it).  mine_select16 and what it
+// calls then run unchanged on the result.
+template <bool HIST>
+__device__ __forceinline__ MineSelect mine_slot_select(const MineSelect& pass, const MineSlots& sl, int i) {
+    MineSelect s = pass;
+    if (HIST) {
+        if (pass.prefix_bits) s.prefix = mine_uniform(sl.prefix[i]);
+        s.hist = pass.hist + ((size_t)i << pass.bin_bits);
+    } else {
+        s.key_min = mine_uniform(sl.key_min[i]);
+        const long long cap = pass.capacity;
+        long long b0 = mine_uniform(sl.out_base[i]), b1 = mine_uniform(sl.out_base[i + 1]);
+        b0 = b0 < 0 ? 0 : (b0 > cap ? cap : b0);
+        b1 = b1 < b0 ? b0 : (b1 > cap ? cap : b1);
+        s.out = pass.out + b0;
+        s.capacity = b1 - b0;
+        s.counter = pass.counter + i;
+    }
+    return s;
+}
+
+// HIST, per relation: a 1 << MINE_SLOT_HIST_BITS bin LDS histogram into the slot's global one and back to zero -- one LDS read per
+// thread, an atomic and a store only where something was counted (after a barrier; the bins are next written after another).
+__device__ __forceinline__ void mine_hist_flush_clear(unsigned* hist_s, unsigned long long* hist, int bin_bits, int t) {
+    if (t < (1 << bin_bits)) {
+        const unsigned c = hist_s[t];
+        if (c) {
+            atomicAdd(hist + t, (unsigned long long)c);
+            hist_s[t] = 0u;
+        }
     }
 }
 

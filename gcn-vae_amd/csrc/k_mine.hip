@@ -19,6 +19,10 @@
 // mine_key_logit of its key: -0 as +0) and, on the host, mine_params and mine_launch.  This file is also the one home of what every
 // mining entry does on the host before its launch (mine_select_args, mine_prepare, mine_typed_prepare on a MineCall) and of the
 // three small kernels that re-bucket the filter.
+//
+// gv_mine_scores_by_relation / gv_mine_scores_typed_by_relation (k_mine_rel, k_mine_typed_rel) are the two sweeps with the selection
+// state PER RELATION (k_mine.h: MineSlots, mine_slot_select): the loops, the staging and the arithmetic of k_mine / k_mine_typed over
+// the chosen relations, each relation selected against its own threshold, prefix, histogram, counter and output segment.
 #include <limits.h>
 
 #include <algorithm>
@@ -205,6 +209,105 @@ __global__ __launch_bounds__(256) void k_mine(const MineParams p) {
     }
 }
 
+// ---- the whole-graph sweep with selection state per relation (gv_mine_scores_by_relation) -----------------------------------------
+// k_mine's loop order, staging and arithmetic over the SLOTS' relations: a workgroup owns its tile pair and walks the live slots of
+// [blockIdx.z * rel_span, + rel_span), so a subset of the relations costs its share of a sweep and an empty slot costs one scalar
+// load.  Per relation the selection is narrowed to the slot (mine_slot_select) and handed to the same mine_epilogue.  HIST: the LDS
+// histogram is the slot's, 256 bins, two of them: relation `it` counts into buffer it & 1 while the buffer of the relation before
+// it -- complete since the barrier behind this relation's MFMA chain -- is flushed to that slot's global histogram and cleared
+// (mine_hist_flush_clear: one LDS read per thread).  No barrier is added to k_mine's one per relation.
+struct MineRelParams {
+    MineParams p;
+    MineSlots sl;
+};
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_mine_rel(const MineRelParams rp) {
+    extern __shared__ __attribute__((aligned(16))) float mine_smem[];
+    __shared__ unsigned long long fmask[3][64];          // the relation's listed objects per subject row, three relations in flight
+    __shared__ int fany[3];
+    __shared__ unsigned flist[MINE_FL_CAP];
+    __shared__ unsigned hist_s[HIST ? 2 : 1][HIST ? (1 << MINE_SLOT_HIST_BITS) : 1];
+    const MineParams& p = rp.p;
+    const MineSlots& sl = rp.sl;
+    const int kc = p.kc, pitch = kc + 4, half = kc >> 1;
+    float* As = mine_smem;
+    float* Bs = As + 64 * pitch;
+    float* Ws = Bs + 64 * pitch;                         // [2][kc + 4]
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const MineSelect& pass = p.sel;
+    const int i0 = blockIdx.z * pass.rel_span, i1 = min(i0 + pass.rel_span, sl.m);
+    const bool resident = p.n_chunks == 1;
+    const float bv = p.bias ? *p.bias : 0.f;
+    const auto s_row = [=](int rl) { return m0 + rl; };
+    const auto o_row = [=](int cl) { return n0 + cl; };
+    const auto live_from = [&](int i) {                  // the first live slot at or after i, i1 when there is none (uniform)
+        while (i < i1 && mine_slot_relation(sl, i, pass.num_rels) < 0) ++i;
+        return i;
+    };
+
+    int i = live_from(i0);
+    if (i >= i1) return;                                 // uniform: no live slot in this span
+    int f_base, f_cnt;
+    mine_filter_load(pass.tile_ptr, pass.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, t, &f_base, &f_cnt);
+    if (t < 64) { fmask[0][t] = 0ull; fmask[1][t] = 0ull; fmask[2][t] = 0ull; }
+    if (t < 3) fany[t] = 0;
+    if (HIST) { hist_s[0][t] = 0u; hist_s[1][t] = 0u; }  // 256 threads, 256 bins
+    if (resident) {
+        mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, pass.n, 0, p.h, kc);
+        mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, pass.n, 0, p.h, kc);
+        if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, mine_slot_relation(sl, i, pass.num_rels), 4 * t));
+    }
+    __syncthreads();
+
+    const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
+
+    int before = -1;                                     // the slot whose histogram waits in hist_s[(it - 1) & 1]
+    for (int it = 0; i < i1; ++it) {
+        const int r = mine_slot_relation(sl, i, pass.num_rels), i_next = live_from(i + 1);
+        const int fb = it % 3, wb = resident ? (it & 1) : 0;
+        if (t < 64) fmask[(it + 1) % 3][t] = 0ull;
+        if (t == 64) fany[(it + 1) % 3] = 0;
+        mine_filter_relation(flist, pass.tile_ent, f_base, f_cnt, r, t, fmask[fb], &fany[fb]);
+        float4 wnext = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool w_pre = resident && t < (kc >> 2) && i_next < i1;
+        if (w_pre) wnext = mine_load_w(p, mine_slot_relation(sl, i_next, pass.num_rels), 4 * t);
+
+        mine_f32x16 acc;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc;
+            if (!resident) {
+                __syncthreads();
+                mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, pass.n, k0, p.h, kc);
+                mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, pass.n, k0, p.h, kc);
+                if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
+                __syncthreads();
+            }
+            acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + wb * (kc + 4) + w_off, mine_groups(kc, p.h, k0));
+        }
+        if (w_pre) mine_store_w(Ws + ((it + 1) & 1) * (kc + 4), kc, t, wnext);
+        __syncthreads();
+
+        if (HIST && before >= 0)
+            mine_hist_flush_clear(hist_s[(it + 1) & 1], pass.hist + ((size_t)before << pass.bin_bits), pass.bin_bits, t);
+        const MineSelect sel = mine_slot_select<HIST>(pass, sl, i);
+        mine_epilogue<HIST>(acc, bv, wm, wn, lane, pass.exclude_self && m0 == n0,
+                            [&](int rl, int cl) { return make_int2(s_row(rl), o_row(cl)); }, r, fany[fb] != 0, fmask[fb],
+                            hist_s[HIST ? (it & 1) : 0], sel);
+        before = i;
+        i = i_next;
+        if (HIST && i >= i1) {                           // the last relation's histogram
+            __syncthreads();
+            mine_hist_flush_clear(hist_s[it & 1], pass.hist + ((size_t)before << pass.bin_bits), pass.bin_bits, t);
+        }
+    }
+}
+
 // ---- the filter, re-bucketed per (subject tile, object tile): count, scan, fill ------------------------------------------
 struct MineFiltParams {
     const int* lo;
@@ -332,18 +435,18 @@ static int mine_fill_status(const MineCall& c) {
     return launch_status(fill);
 }
 
-// the counter (EMIT) or the histogram (HIST) cleared on the stream
-static int mine_clear(const MineCall& c) {
+// the counters (EMIT) or the histograms (HIST) of `slots` selections cleared on the stream
+static int mine_clear(const MineCall& c, int slots = 1) {
     const bool emit = c.mode == GV_MINE_EMIT;
-    if (fill_words(emit ? (void*)c.counter : (void*)c.hist, 0u, emit ? 8 : (size_t)8 << c.bin_bits, c.st) != hipSuccess)
+    if (fill_words(emit ? (void*)c.counter : (void*)c.hist, 0u, (size_t)slots * (emit ? 8 : (size_t)8 << c.bin_bits), c.st) != hipSuccess)
         return mine_fill_status(c);
     return GV_OK;
 }
 
-int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid) {
-    const int rc = mine_select_args(c, sel);
-    const int n = c.n, num_rels = c.num_rels;
-    if (rc != GV_OK || n == 0) return rc;
+// A whole-graph sweep over `count` relations (or slots) of an n-entity table, n > 0: the workspace checked, sel->rel_span and *grid
+// set, the filter re-bucketed on the stream.
+static int mine_sweep_prepare(const MineCall& c, int count, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid) {
+    const int n = c.n;
     const bool filtered = c.filt_lo != nullptr;
     if (filtered) {
         GV_REQUIRE(workspace, GV_ERR_NULL, "%s: a filter needs the workspace", c.who);
@@ -354,18 +457,44 @@ int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, Mi
     const int tiles_1d = (n + 63) / 64;
     const int tiles = tiles_1d * tiles_1d;
     long long spans = (4LL * 256 + tiles - 1) / tiles;
-    spans = std::max(1LL, std::min(spans, (long long)num_rels));
-    sel->rel_span = (int)((num_rels + spans - 1) / spans);
-    *grid = dim3(tiles_1d, tiles_1d, (num_rels + sel->rel_span - 1) / sel->rel_span);
+    spans = std::max(1LL, std::min(spans, (long long)count));
+    sel->rel_span = (int)((count + spans - 1) / spans);
+    *grid = dim3(tiles_1d, tiles_1d, (count + sel->rel_span - 1) / sel->rel_span);
 
-    if (filtered && !mine_filter_rebucket(c.filt_lo, c.filt_hi, c.filt_ent, c.n_filt_ent, n, num_rels, workspace, c.st, &sel->tile_ptr,
+    if (filtered && !mine_filter_rebucket(c.filt_lo, c.filt_hi, c.filt_ent, c.n_filt_ent, n, c.num_rels, workspace, c.st, &sel->tile_ptr,
                                           &sel->tile_ent))
         return mine_fill_status(c);
-    return mine_clear(c);
+    return GV_OK;
+}
+
+int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid) {
+    int rc = mine_select_args(c, sel);
+    if (rc != GV_OK || c.n == 0) return rc;
+    rc = mine_sweep_prepare(c, c.num_rels, workspace, workspace_bytes, sel, grid);
+    return rc != GV_OK ? rc : mine_clear(c);
+}
+
+int mine_slots_args(const MineCall& c, const int32_t* rels, int m, const uint32_t* key_min, const uint32_t* prefix,
+                    const int64_t* out_base, int max_bin_bits, MineSlots* sl) {
+    GV_REQUIRE(m >= 1 && m <= c.num_rels, GV_ERR_SHAPE, "%s: m=%d slots outside [1, num_rels=%d]", c.who, m, c.num_rels);
+    if (c.mode == GV_MINE_HIST) {
+        GV_REQUIRE(c.bin_bits <= max_bin_bits, GV_ERR_SHAPE, "%s: bin_bits=%d above %d", c.who, c.bin_bits, max_bin_bits);
+        GV_REQUIRE(((long long)m << c.bin_bits) <= MINE_SLOT_HIST_WORDS, GV_ERR_SHAPE, "%s: m << bin_bits = %lld histogram words, more than %lld",
+                   c.who, (long long)m << c.bin_bits, MINE_SLOT_HIST_WORDS);
+    }
+    *sl = MineSlots{};
+    sl->rels = rels; sl->m = m; sl->key_min = key_min; sl->prefix = prefix; sl->out_base = (const long long*)out_base;
+    if (c.n == 0) return GV_OK;
+    GV_REQUIRE(rels, GV_ERR_NULL, "%s: NULL rels", c.who);
+    if (c.mode == GV_MINE_EMIT)
+        GV_REQUIRE(key_min && out_base, GV_ERR_NULL, "%s: NULL key_min / out_base", c.who);
+    else
+        GV_REQUIRE(prefix || c.prefix_bits == 0, GV_ERR_NULL, "%s: NULL prefix", c.who);
+    return GV_OK;
 }
 
 int mine_typed_prepare(const MineCall& c, const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
-                       MineSelect* sel, MineTyped* ty) {
+                       MineSelect* sel, MineTyped* ty, int slots) {
     const int rc = mine_select_args(c, sel);
     if (rc != GV_OK) return rc;
     GV_REQUIRE(n_units >= 0 && n_units <= INT_MAX, GV_ERR_SHAPE, "%s: n_units=%lld outside [0, 2^31)", c.who, (long long)n_units);
@@ -375,7 +504,7 @@ int mine_typed_prepare(const MineCall& c, const int64_t* set_ptr, const int32_t*
     *ty = MineTyped{};
     ty->set_ptr = (const long long*)set_ptr; ty->set_ids = set_ids; ty->units = (const int4*)units;
     ty->filt_lo = c.filt_lo; ty->filt_hi = c.filt_hi; ty->filt_ent = c.filt_ent; ty->n_filt_ent = c.n_filt_ent;
-    return mine_clear(c);
+    return mine_clear(c, slots);
 }
 
 // What both DistMult entries check of their tables; then *p filled but for the selection.
@@ -463,6 +592,83 @@ __global__ __launch_bounds__(256) void k_mine_typed(const MineTypedParams tp) {
         }
 
         // ids through the member lists, -1 past them; fmask is complete (a barrier followed the filter's atomics) and always read
+        const int o = oid_s[wn + l31];
+        mine_epilogue<HIST>(acc, bv, wm, wn, lane, sel.exclude_self != 0, [&](int rl, int) { return make_int2(sid_s[rl], o); }, r, true,
+                            fmask, hist_s, sel);
+    }
+    if (HIST) {
+        __syncthreads();
+        mine_hist_flush(hist_s, sel, t);
+    }
+}
+
+// ---- the type-constrained sweep with selection state per relation (gv_mine_scores_typed_by_relation) --------------------------------
+// k_mine_typed, a unit's first word being the SLOT whose relation it walks: the workgroup owns one relation already, so the
+// selection is narrowed to the slot once (mine_slot_select) and the LDS histogram, its 12 + 10 + 10 levels and its one flush stay
+// k_mine_typed's; only their destination is the slot's.
+struct MineTypedRelParams {
+    MineParams p;
+    MineTyped ty;
+    MineSlots sl;
+};
+
+template <bool HIST>
+__global__ __launch_bounds__(256) void k_mine_typed_rel(const MineTypedRelParams tp) {
+    extern __shared__ __attribute__((aligned(16))) float mine_smem[];
+    __shared__ unsigned long long fmask[64];             // the tile pair's listed objects per subject row
+    __shared__ int sid_s[64], oid_s[64];                 // the tiles' entity ids, -1 past the lists
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const MineParams& p = tp.p;
+    const MineTyped& ty = tp.ty;
+    const int kc = p.kc, pitch = kc + 4, half = kc >> 1;
+    float* As = mine_smem;
+    float* Bs = As + 64 * pitch;
+    float* Ws = Bs + 64 * pitch;                         // [kc + 4]
+    const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+    const int wm = (wid >> 1) * 32, wn = (wid & 1) * 32;
+    const int l31 = lane & 31, lhi = lane >> 5;
+    const auto s_row = [&](int rl) { return sid_s[rl]; };
+    const auto o_row = [&](int cl) { return oid_s[cl]; };
+    const int4 unit = ty.units[blockIdx.x];
+    const int slot = (int)mine_uniform((unsigned)unit.x);
+    const int r = mine_slot_relation(tp.sl, slot, p.sel.num_rels);
+    if (r < 0) return;                                   // uniform: not a unit, or an empty slot
+    const MineSelect sel = mine_slot_select<HIST>(p.sel, tp.sl, slot);
+    const bool resident = p.n_chunks == 1;
+    const float bv = p.bias ? *p.bias : 0.f;
+
+    mine_typed_ids(ty, sel.num_rels + r, unit.y, sel.n, t, sid_s);
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += 256) hist_s[i] = 0u;
+    __syncthreads();
+    if (resident) {
+        mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, 0, p.h, kc);
+        if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, 4 * t));
+    }
+    const int a_off = (wm + l31) * pitch + lhi * half, b_off = (wn + l31) * pitch + lhi * half, w_off = lhi * half;
+
+    for (int ot = unit.z; ot < unit.w; ++ot) {
+        __syncthreads();                                 // the last tile's reads of Bs, oid_s and fmask are over
+        mine_typed_ids(ty, r, ot, sel.n, t, oid_s);
+        if (t < 64) fmask[t] = 0ull;
+        __syncthreads();
+        mine_typed_filter(ty, sel.num_rels, r, sid_s, oid_s, t, fmask);
+
+        mine_f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc;
+            if (c > 0) __syncthreads();
+            if (!resident) {
+                mine_stage_rows(As, p.e, p.ld_e, p.vec_e, s_row, sel.n, k0, p.h, kc);
+                if (t < (kc >> 2)) mine_store_w(Ws, kc, t, mine_load_w(p, r, k0 + 4 * t));
+            }
+            mine_stage_rows(Bs, p.e, p.ld_e, p.vec_e, o_row, sel.n, k0, p.h, kc);
+            __syncthreads();
+            acc = mine_mfma_chunk(acc, As + a_off, Bs + b_off, Ws + w_off, mine_groups(kc, p.h, k0));
+        }
+
         const int o = oid_s[wn + l31];
         mine_epilogue<HIST>(acc, bv, wm, wn, lane, sel.exclude_self != 0, [&](int rl, int) { return make_int2(sid_s[rl], o); }, r, true,
                             fmask, hist_s, sel);
@@ -697,6 +903,52 @@ extern "C" int gv_mine_scores_typed(const float* e, int ld_e, const float* w, in
     const dim3 grid((unsigned)n_units);
     return mode == GV_MINE_EMIT ? mine_launch<k_mine_typed<false>>(tp, grid, 256, lds, lds_max, c)
                                 : mine_launch<k_mine_typed<true>>(tp, grid, 256, lds, lds_max, c);
+}
+
+extern "C" int gv_mine_scores_by_relation(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,
+                                          const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                                          const int32_t* rels, int m, const uint32_t* key_min, int prefix_bits, const uint32_t* prefix,
+                                          int bin_bits, int32_t* out, int64_t capacity, const int64_t* out_base, uint64_t* counter,
+                                          uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h,
+                                          void* stream) {
+    const MineCall c{"gv_mine_scores_by_relation", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, 0u,
+                     prefix_bits, 0u, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
+    MineRelParams rp{};
+    dim3 grid;
+    int rc = mine_params(c.who, e, ld_e, w, ld_w, bias, n, num_rels, h, n_filt_ent, &rp.p);
+    if (rc == GV_OK) rc = mine_select_args(c, &rp.p.sel);
+    if (rc == GV_OK) rc = mine_slots_args(c, rels, m, key_min, prefix, out_base, MINE_SLOT_HIST_BITS, &rp.sl);
+    if (rc != GV_OK || n == 0) return rc;
+    rc = mine_sweep_prepare(c, m, workspace, workspace_bytes, &rp.p.sel, &grid);
+    if (rc == GV_OK) rc = mine_clear(c, m);
+    if (rc != GV_OK) return rc;
+    const int lds = (2 * 64 * (rp.p.kc + 4) + 2 * (rp.p.kc + 4)) * (int)sizeof(float);
+    const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);
+    return mode == GV_MINE_EMIT ? mine_launch<k_mine_rel<false>>(rp, grid, 256, lds, lds_max, c)
+                                : mine_launch<k_mine_rel<true>>(rp, grid, 256, lds, lds_max, c);
+}
+
+extern "C" int gv_mine_scores_typed_by_relation(const float* e, int ld_e, const float* w, int ld_w, const float* bias,
+                                                const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                                                const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                                int exclude_self, int mode, const int32_t* rels, int m, const uint32_t* key_min,
+                                                int prefix_bits, const uint32_t* prefix, int bin_bits, int32_t* out, int64_t capacity,
+                                                const int64_t* out_base, uint64_t* counter, uint64_t* hist, int n, int num_rels, int h,
+                                                void* stream) {
+    const MineCall c{"gv_mine_scores_typed_by_relation", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, 0u,
+                     prefix_bits, 0u, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
+    MineTypedRelParams tp{};
+    MineSelect checked;
+    int rc = mine_params(c.who, e, ld_e, w, ld_w, bias, n, num_rels, h, n_filt_ent, &tp.p);
+    if (rc == GV_OK) rc = mine_select_args(c, &checked);
+    if (rc == GV_OK) rc = mine_slots_args(c, rels, m, key_min, prefix, out_base, MINE_HIST_BITS, &tp.sl);
+    if (rc == GV_OK) rc = mine_typed_prepare(c, set_ptr, set_ids, units, n_units, &tp.p.sel, &tp.ty, m);
+    if (rc != GV_OK || n == 0 || n_units == 0) return rc;
+    const int lds = (2 * 64 + 1) * (tp.p.kc + 4) * (int)sizeof(float);
+    const int lds_max = (2 * 64 + 1) * (MINE_KC_MAX + 4) * (int)sizeof(float);
+    const dim3 grid((unsigned)n_units);
+    return mode == GV_MINE_EMIT ? mine_launch<k_mine_typed_rel<false>>(tp, grid, 256, lds, lds_max, c)
+                                : mine_launch<k_mine_typed_rel<true>>(tp, grid, 256, lds, lds_max, c);
 }
 
 extern "C" int gv_mine_scores_typed_mc(const float* e, int ld_e, int64_t e_stride, int n_samples, const float* w, int ld_w,

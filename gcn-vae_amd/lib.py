@@ -139,6 +139,10 @@ SIGNATURES = {
                             _I, _I, _I, _P]),
     'gv_mine_scores_typed': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32, _I,
                                   _P, _L, _P, _P, _I, _I, _I, _P]),
+    'gv_mine_scores_by_relation': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _L, _P, _P, _P, _P, _L,
+                                        _I, _I, _I, _P]),
+    'gv_mine_scores_typed_by_relation': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _L,
+                                              _P, _P, _P, _I, _I, _I, _P]),
     'gv_mine_scores_typed_mc': (_I, [_P, _I, _L, _I, _P, _I, _P, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I,
                                      ctypes.c_uint32, _I, _P, _L, _P, _P, _I, _I, _I, _P]),
     'gv_ec_basis_rows_fwd': (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P]),

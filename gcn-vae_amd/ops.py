@@ -11,6 +11,7 @@ import os as _os
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import lib
@@ -1570,6 +1571,241 @@ def mine_scores_typed_mc(z, w, set_ptr, set_ids, *, threshold=None, k=None, bias
     count, as the rule says for any tie.  Returns ``(triplets int64 (n, 3), probs float32 (n,), info)``."""
     return _mine_scores('gv_mine_scores_typed_mc', z, w, (set_ptr, set_ids, span), threshold, k, bias, filt_lo, filt_hi, filt_ent,
                         exclude_self, max_results, mc=True)
+
+
+# ---- per-relation completion: every relation's own K best ---------------------------------------------------------------------------
+# (prefix bits, bin bits) of the histogram passes of the two by-relation sweeps.  The whole-graph form flushes its LDS histogram
+# after EVERY relation, so it keeps 256 bins (one LDS read per thread and flush: DESIGN.md 4d-3); a typed unit owns one relation and
+# keeps the miners' 12 + 10 + 10.
+MINE_RELATION_LEVELS = ((0, 8), (8, 8), (16, 8), (24, 8))
+MINE_RELATION_TYPED_LEVELS = MINE_LEVELS
+MINE_RELATION_HIST_WORDS = 1 << 24      # = MINE_SLOT_HIST_WORDS (csrc/k_mine.h): m << bin_bits histogram words at most
+
+
+def relation_ids_check(relations, num_rels, device=None):
+    """The ``relations`` of a per-relation query as int64 [m] on ``device`` (default: where they are): a 1-D integer list of unique
+    ids in [0, num_rels), any order; None: every relation.  Checked with ONE device-to-host read, as ``pair_ids_check``; a repeated
+    or out-of-range id is a ValueError, an empty list too."""
+    if relations is None:
+        return torch.arange(num_rels, dtype=torch.int64, device=device)
+    rels = torch.as_tensor(relations, device=device)
+    if not rels.numel():
+        raise ValueError('relations: expected at least one relation id')
+    if rels.dim() != 1 or rels.dtype not in (torch.int32, torch.int64):
+        raise TypeError('relations: expected a 1-D int32 / int64 list of relation ids')
+    rels = rels.long()
+    ordered = torch.sort(rels).values
+    lo, hi, repeated = torch.stack((ordered[0], ordered[-1], (ordered[1:] == ordered[:-1]).any().long())).tolist()
+    if lo < 0 or hi >= num_rels:
+        raise ValueError(f'relation ids must lie in [0, {num_rels})')
+    if repeated:
+        raise ValueError('relations: a relation id is repeated')
+    return rels
+
+
+def _relation_args(k, m, max_results):
+    """(k, max_results, the share of ``max_results`` one relation may return) of a per-relation call: k >= 1, m * k <= max_results."""
+    k, max_results = int(k), int(max_results)
+    if k < 1:
+        raise ValueError(f'k must be >= 1, got {k}')
+    if not 1 <= max_results < 2 ** 31:
+        raise ValueError(f'max_results must lie in [1, 2**31), got {max_results}')
+    if m * k > max_results:
+        raise ValueError(f'm * k = {m} * {k} = {m * k} results, more than max_results={max_results}')
+    return k, max_results, max_results // m
+
+
+def _relation_overflow(rel, count, share, m, k):
+    return MineOverflow(count, share, f'relation {rel} (one of {m}, each with an equal share of max_results), top-{k}: the candidates '
+                                      f'at or above the K-th logit')
+
+
+def relation_select(slot, s, o, logits, rels, k, n, share):
+    """The top-K end of every per-relation route: from candidates ``(slot, s, o, logit)`` that include, for every slot i < m (the
+    relation ``rels[i]``), everything at or above its K-th logit, the first K of each slot in ``mine_order``'s order restricted to
+    it -- logit descending (-0 as +0), then (s, o) ascending -- as ``(subj int64 (m, k), obj int64 (m, k), logits float32 (m, k),
+    count int64 [m])``, short rows padded with -1 / -1 / -inf; ``count[i]`` is the number of slot i's candidates at or above its
+    K-th logit's exact value (all of them when it has fewer than K).  A count above ``share`` raises ``MineOverflow`` naming the
+    relation.  Any device."""
+    m, dev = rels.numel(), logits.device
+    logits = logits.to(torch.float32) + 0.0
+    order = torch.argsort(s * max(n, 1) + o, stable=True)
+    order = order[torch.argsort(logits[order], descending=True, stable=True)]
+    order = order[torch.argsort(slot[order], stable=True)]
+    slot, s, o, logits = slot[order], s[order], o[order], logits[order]
+    sizes = torch.bincount(slot, minlength=m)
+    start = torch.cumsum(sizes, 0) - sizes
+    rank = torch.arange(slot.numel(), device=dev) - start[slot]
+    subj = torch.full((m, k), -1, dtype=torch.int64, device=dev)
+    obj = torch.full((m, k), -1, dtype=torch.int64, device=dev)
+    best = torch.full((m, k), float('-inf'), dtype=torch.float32, device=dev)
+    keep = rank < k
+    subj[slot[keep], rank[keep]], obj[slot[keep], rank[keep]], best[slot[keep], rank[keep]] = s[keep], o[keep], logits[keep]
+    kth = best[:, k - 1]                                 # -inf where the slot has fewer than K: everything counts
+    count = torch.zeros(m, dtype=torch.int64, device=dev).index_add_(0, slot, (logits >= kth[slot]).long())
+    over = torch.nonzero(count > share).reshape(-1)
+    if over.numel():
+        i = int(over[0])
+        raise _relation_overflow(int(rels[i]), int(count[i]), share, m, k)
+    return subj, obj, best, count
+
+
+def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name):
+    """``_mine_drive``'s top-K walk for ALL relations of ``rels`` (int64 [m], unique) at once: each has its own K-th key, found on
+    its own histogram.  ``launch(mode, rels32, key_min, prefix_bits, prefix, bin_bits, out, capacity, out_base, words)`` is one
+    sweep of the kernel over m slots -- int32 [m] relation ids (-1: the slot sits this pass out), per-slot ``key_min`` / ``prefix``
+    (uint32 bit patterns in int32 [m]), ``words`` the counters int64 [m] or the histograms int64 [m << bin_bits], ``out_base`` int64
+    [m + 1] the slots' segments of ``out`` (capacity, 4).  After each HIST sweep the (m, bins) histogram is read ONCE; every
+    unresolved slot takes the bin that holds its K-th candidate and extends its prefix; a slot is resolved once what an emission
+    at that bin's lower edge returns fits its ``share`` of the results (or the key is spent) and sits out the later sweeps.  One
+    EMIT sweep follows, the segments an exclusive scan of the edges, each counter checked against its edge; then
+    ``relation_select``.  ``levels``: the (prefix bits, bin bits) of the passes.  Returns (subj, obj, logits, info)."""
+    m = rels.numel()
+    rel_host = rels.cpu().numpy().astype(np.int64)
+    above, prefix = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    key_min, edge = np.zeros(m, np.int64), np.zeros(m, np.int64)
+    live = np.ones(m, bool)
+    info = {'count': torch.zeros(m, dtype=torch.int64, device=dev), 'passes': 0}
+
+    def i32(a, fill=None):                               # uint32 values / ids as the int32 [m] the kernel reads
+        a = a if fill is None else np.where(fill, a, -1)
+        return torch.from_numpy(a.astype(np.uint32).view(np.int32) if fill is None else a.astype(np.int32)).to(dev)
+
+    for prefix_bits, bin_bits in levels:
+        if not live.any():
+            break
+        bins, shift = 1 << bin_bits, 32 - prefix_bits - bin_bits
+        words = torch.zeros(m * bins, dtype=torch.int64, device=dev)
+        launch(1, i32(rel_host, live), None, prefix_bits, i32(prefix), bin_bits, None, 0, None, words)
+        info['passes'] += 1
+        hist = words.view(m, bins).cpu().numpy()
+        tail = hist[:, ::-1].cumsum(1)[:, ::-1]          # tail[i, b] = slot i's candidates of its range in bins >= b
+        few = live & (tail[:, 0] <= k) if prefix_bits == 0 else np.zeros(m, bool)      # fewer candidates than asked for: all
+        edge[few], key_min[few] = tail[few, 0], (tail[few, 0] > 0).astype(np.int64)
+        walk = np.nonzero(live & ~few)[0]
+        holds = tail[walk] >= (k - above[walk])[:, None]
+        if not holds[:, 0].all():
+            i = walk[np.argmin(holds[:, 0])]
+            raise RuntimeError(f'{name}: relation {rel_host[i]}: a refining pass counted fewer candidates than the level above it')
+        b = bins - 1 - np.argmax(holds[:, ::-1], axis=1)                                 # the last bin that still holds the K-th
+        prefix[walk] = (prefix[walk] << bin_bits) | b
+        above[walk] += tail[walk, b] - hist[walk, b]
+        edge[walk] = above[walk] + hist[walk, b]         # what an emission at this bin's lower edge returns
+        done = walk[(edge[walk] <= share) | (shift == 0)]
+        key_min[done] = prefix[done] << shift
+        live[few] = False
+        live[done] = False
+    over = np.nonzero(edge > share)[0]
+    if over.size:                     # one exact value of a relation holds more candidates than it may return
+        raise _relation_overflow(rel_host[over[0]], edge[over[0]], share, m, k)
+    out_base = np.concatenate([[0], np.cumsum(edge)])
+    total = int(out_base[-1])
+    if total == 0:
+        empty = torch.zeros(0, dtype=torch.int64, device=dev)
+        subj, obj, best, _ = relation_select(empty, empty, empty, torch.zeros(0, device=dev), rels, k, n, share)
+        return subj, obj, best, info
+    out = torch.empty(total, 4, dtype=torch.int32, device=dev)
+    counters = torch.zeros(m, dtype=torch.int64, device=dev)
+    launch(0, i32(rel_host, edge > 0), i32(key_min), 0, None, 1, out, total, torch.from_numpy(out_base).to(dev), counters)
+    info['passes'] += 1
+    found = counters.cpu().numpy()
+    if (found != edge).any():
+        i = int(np.nonzero(found != edge)[0][0])
+        raise RuntimeError(f'{name}: relation {rel_host[i]}: the emission pass found {found[i]} candidates where the histograms '
+                           f'counted {edge[i]}')
+    slot = torch.repeat_interleave(torch.arange(m, device=dev), torch.from_numpy(edge).to(dev))
+    subj, obj, best, info['count'] = relation_select(slot, out[:, 0].long(), out[:, 2].long(), out[:, 3].contiguous().view(torch.float32),
+                                                     rels, k, n, share)
+    return subj, obj, best, info
+
+
+def _relation_topk(entry, levels, emb, w, k, relations, members, bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
+    """``relation_topk_scores`` (``members`` None) and ``relation_topk_scores_typed`` (``members`` = (set_ptr, set_ids, span)):
+    ``_mine_scores``' checks and operands, the slots, one launch closure, ``_mine_drive_by_relation``."""
+    _mine_tables(emb, 'emb', w, 'w')
+    n, num_rels, h = emb.shape[0], w.shape[0], emb.shape[1]
+    if num_rels < 1 or h < 1:
+        raise ValueError(f'need at least one relation and width >= 1 (R={num_rels}, h={h})')
+    _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    rels = relation_ids_check(relations, num_rels)
+    m = rels.numel()
+    k, max_results, share = _relation_args(k, m, max_results)
+    if (m << max(b for _, b in levels)) > MINE_RELATION_HIST_WORDS:
+        raise ValueError(f'{m} relations: more than {MINE_RELATION_HIST_WORDS} histogram words; ask for them in several calls')
+    if members is not None:
+        members = _mine_typed_members(members[0], members[1], n, num_rels) + (members[2],)
+    emb, ld_e = _row_major(emb, 'emb')
+    w, ld_w = _row_major(w, 'w')
+    dev, nothing = _mine_device(emb, 'emb', w, 'w')
+    rels = rels.to(dev)
+    info = {'count': torch.zeros(m, dtype=torch.int64, device=dev), 'passes': 0}
+    padding = (torch.full((m, k), -1, dtype=torch.int64, device=dev), torch.full((m, k), -1, dtype=torch.int64, device=dev),
+               torch.full((m, k), float('-inf'), dtype=torch.float32, device=dev), info)
+    if nothing is not None:
+        return padding
+    if members is None:
+        lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
+                                                                   lib.load().gv_mine_scores_workspace_bytes)
+        sets, after = (), (ptr(ws), ws_bytes)
+    else:
+        set_ptr, set_ids = members[0].to(dev), members[1].to(dev)
+        units = relation_typed_plan(set_ptr, num_rels, rels, members[2])
+        if units.shape[0] == 0:
+            return padding
+        lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
+        sets, after = (ptr(set_ptr), ptr(set_ids), ptr(units), units.shape[0]), ()
+    if bias is not None:
+        bias = torch.as_tensor(bias, dtype=torch.float32, device=dev) if not isinstance(bias, torch.Tensor) else bias
+        bias = _chk(bias.detach().reshape(1).to(torch.float32).contiguous(), name='bias')
+
+    def launch(mode, rels32, key_min, prefix_bits, prefix, bin_bits, out, capacity, out_base, words):
+        lib.call(entry, ptr(emb), ld_e, ptr(w), ld_w, ptr(bias), *sets, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+                 1 if exclude_self else 0, mode, ptr(rels32), m, ptr(key_min), prefix_bits, ptr(prefix), bin_bits, ptr(out), capacity,
+                 ptr(out_base), ptr(words), ptr(words), *after, n, num_rels, h, lib.stream())
+
+    return _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, entry)
+
+
+def relation_topk_scores(emb, w, k, *, relations=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                         max_results=MINE_MAX_RESULTS):
+    """Every relation's OWN ``k`` best triplets of a DistMult decoder: for each relation r of ``relations`` (unique ids, any order;
+    None: all) the k candidates (s, o) of largest ``logit[s, r, o]``, ``mine_scores``' logit bit for bit and its candidates -- all
+    (s, o) less the filter's triplets of r, less s == o under ``exclude_self``, less NaN.  ``mine_scores`` walks to ONE key for
+    the whole graph, which compares relations by the scale of their ``w`` rows; here the thresholds, prefixes, histograms,
+    counters and output segments are per relation (gv_mine_scores_by_relation: the miner's loop order over the chosen relations
+    only, a 256-bin histogram flushed per relation), so all lists come out of the same three to five sweeps and a few relations
+    cost their share of a sweep.  Returns ``(subj int64 (m, k), obj int64 (m, k), logits float32 (m, k), info)``, row i for
+    ``relations[i]`` in ``relation_select``'s order, short rows padded with -1 / -1 / -inf; ``info['count']`` int64 [m] is each
+    relation's candidates at or above its K-th logit, ``info['passes']`` the sweeps.  ``m * k <= max_results``; a relation may
+    return ``max_results // m`` records, and one whose candidates at or above its K-th logit are more raises ``MineOverflow``
+    naming it."""
+    return _relation_topk('gv_mine_scores_by_relation', MINE_RELATION_LEVELS, emb, w, k, relations, None, bias, filt_lo, filt_hi,
+                          filt_ent, exclude_self, max_results)
+
+
+def relation_typed_plan(set_ptr, num_rels, rels, span=None):
+    """``mine_typed_plan`` for the relations ``rels`` (int64 [m], unique) only, a unit's first word being the SLOT (the index into
+    ``rels``) as gv_mine_scores_typed_by_relation reads it; the default span is chosen from the chosen relations' tile pairs."""
+    sizes = (set_ptr[1:] - set_ptr[:-1]).to(torch.int64)
+    chosen = torch.zeros(num_rels, dtype=torch.bool, device=set_ptr.device)
+    chosen[rels.to(set_ptr.device)] = True
+    sizes = sizes * torch.cat([chosen, chosen])
+    units = mine_typed_plan(torch.cat([sizes.new_zeros(1), torch.cumsum(sizes, 0)]), num_rels, span)
+    slot_of = torch.full((num_rels,), -1, dtype=torch.int32, device=set_ptr.device)
+    slot_of[rels.to(set_ptr.device)] = torch.arange(rels.numel(), dtype=torch.int32, device=set_ptr.device)
+    units[:, 0] = slot_of[units[:, 0].long()]
+    return units.contiguous()
+
+
+def relation_topk_scores_typed(emb, w, k, set_ptr, set_ids, *, relations=None, bias=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                               exclude_self=True, max_results=MINE_MAX_RESULTS, span=None):
+    """``relation_topk_scores`` among the TYPE-CORRECT pairs only: s a member of set ``R + r``, o a member of set ``r``
+    (``mine_scores_typed``'s member lists and rule, the same logits bit for bit).  gv_mine_scores_typed_by_relation walks
+    ``relation_typed_plan``'s units -- the chosen relations' tiles only; the result does not depend on ``span`` -- and keeps the typed
+    miner's 12 + 10 + 10 histogram levels, a unit's workgroup owning one relation.  A relation with an empty subject or object
+    list returns an all-padding row."""
+    return _relation_topk('gv_mine_scores_typed_by_relation', MINE_RELATION_TYPED_LEVELS, emb, w, k, relations,
+                          (set_ptr, set_ids, span), bias, filt_lo, filt_hi, filt_ent, exclude_self, max_results)
 
 
 def pick_split_k(m_out, n_out, k):

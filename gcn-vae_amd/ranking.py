@@ -1062,6 +1062,131 @@ def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_ind
     return _complete_unfused(chunk, ents, max(1, COMPLETE_UNFUSED_ELEMS // (n * num_rels)), k)
 
 
+# ---- per-relation completion: which pairs belong to this relation? -----------------------------------------------------------------
+def _relation_pairs(val, r, num_rels, k, filt, exclude_self, subj_ok=None, obj_ok=None):
+    """Relation r's candidates at or above its K-th logit, ``(s, o, logits)``, from its (N, N) logits ``val``: all pairs less NaN,
+    less the typed rule's misses (``subj_ok`` / ``obj_ok`` bool [N]), less s == o under ``exclude_self``, less the filter's
+    objects of (s, r) (``filt`` = the (lo, hi, ent) of ``_mine_filter``)."""
+    n = val.shape[0]
+    val = val.to(torch.float32) + 0.0
+    cand = ~torch.isnan(val)
+    if subj_ok is not None:
+        cand &= subj_ok.view(n, 1) & obj_ok.view(1, n)
+    if exclude_self:
+        cand &= ~torch.eye(n, dtype=torch.bool, device=val.device)
+    lo, hi, ent = filt
+    if lo is not None and n:
+        dev = val.device
+        cand &= ~_listed_mask(lo.reshape(-1).to(dev)[r::num_rels], hi.reshape(-1).to(dev)[r::num_rels], ent.to(dev), n, n, dev)
+    vals = val[cand]
+    if vals.numel() > k:
+        cand &= val >= torch.topk(vals, k).values[-1]
+    s, o = torch.nonzero(cand, as_tuple=True)
+    return s, o, val[cand]
+
+
+def _relation_rows(pairs_of, rels, k, n, share):
+    """The end of both host routes: ``pairs_of(i, r)`` is the ``_relation_pairs`` of slot i, ``ops.relation_select`` the rest."""
+    dev = rels.device
+    parts = [pairs_of(i, r) for i, r in enumerate(rels.tolist())]
+    slot = torch.cat([torch.full_like(p[0], i) for i, p in enumerate(parts)])
+    subj, obj, logits, count = ops.relation_select(slot, torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
+                                                   torch.cat([p[2] for p in parts]), rels, k, n, share)
+    return subj, obj, logits, {'count': count.to(dev), 'passes': len(parts)}
+
+
+def _relation_masks(cand_subj, cand_obj, num_rels, n, device):
+    """The typed rule's dense masks, bool (R, N) each, given together or not at all."""
+    if (cand_subj is None) != (cand_obj is None):
+        raise ValueError('cand_subj and cand_obj are given together or not at all')
+    if cand_subj is None:
+        return None, None
+    masks = tuple(torch.as_tensor(c, device=device) for c in (cand_subj, cand_obj))
+    for name, c in zip(('cand_subj', 'cand_obj'), masks):
+        if c.dtype != torch.bool or tuple(c.shape) != (num_rels, n):
+            raise ValueError(f'{name}: expected a bool ({num_rels}, {n}) mask')
+    return masks
+
+
+def complete_relations_from_scores(score, k, *, relations=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                                   cand_subj=None, cand_obj=None, max_results=ops.MINE_MAX_RESULTS):
+    """The rule of ``ops.relation_topk_scores`` on a materialised tensor ``score[r, s, o]`` (R, N, N), in plain torch (any device,
+    CPU included): for each relation r of ``relations`` (unique ids in [0, R), any order; None: all) the ``k`` candidates (s, o)
+    of largest logit.  Candidates: every (s, o), less ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r),
+    less s == o when ``exclude_self``, less NaN logits, and with ``cand_subj`` / ``cand_obj`` (bool (R, N), together) only s among
+    ``cand_subj[r]`` and o among ``cand_obj[r]``.  Order inside a relation: ``mine_from_scores``' restricted to it -- logit
+    descending with -0 == +0, then (s, o) ascending.  Returns ``(subj int64 (m, k), obj int64 (m, k), logits float32 (m, k),
+    info)``, row i for ``relations[i]``, rows with fewer than k candidates ending in -1 / -1 / -inf, -0 reported as +0;
+    ``info['count']`` int64 [m] is each relation's candidates at or above its K-th logit's exact value (all, when fewer than K
+    exist).  ``m * k <= max_results``; a relation whose count exceeds its share ``max_results // m`` raises ``MineOverflow``
+    naming it: nothing is truncated silently."""
+    num_rels, n = score.shape[0], score.shape[1]
+    rels = ops.relation_ids_check(relations, num_rels).to(score.device)
+    k, max_results, share = ops._relation_args(k, rels.numel(), max_results)
+    ops._mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    subj_ok, obj_ok = _relation_masks(cand_subj, cand_obj, num_rels, n, score.device)
+    filt = (filt_lo, filt_hi, filt_ent)
+
+    def pairs_of(i, r):
+        return _relation_pairs(score[r], r, num_rels, k, filt, exclude_self, *((subj_ok[r], obj_ok[r]) if subj_ok is not None else ()))
+
+    return _relation_rows(pairs_of, rels, k, n, share)
+
+
+def _relation_setup(embedding, w, filter_index, flow_log_prob, type_constraint):
+    """What the two routes of ``complete_relations`` prepare alike: (emb, w, (lo, hi, ent), bias, the constraint or None)."""
+    type_constraint = _complete_constraint(type_constraint)
+    emb = embedding.detach()
+    wd = w.detach().to(emb.device)
+    filt = _mine_filter(filter_index, emb.shape[0], wd.shape[0], emb.device)
+    if type_constraint is not None:
+        _mine_members_sizes(type_constraint, emb.shape[0], wd.shape[0])
+    return emb, wd, filt, _mine_bias(flow_log_prob, emb.device), type_constraint
+
+
+def complete_relations(embedding, w, k, *, relations=None, filter_index=None, flow_log_prob=None, exclude_self=True,
+                       type_constraint=UNCONSTRAINED, max_results=ops.MINE_MAX_RESULTS):
+    """Which pairs belong to this relation?  For every relation r of ``relations`` (unique ids, any order; default: every relation)
+    its OWN ``k`` most confident new facts (s, r, o), scored as every scorer here scores them (logit = (e_s * w_r) . e_o +
+    flow_log_prob); with a ``FilterIndex`` the known triplets are left out.  ``mine_triplets`` cannot answer this: its one
+    threshold for the whole graph compares relations by the scale of their ``w`` rows.  Here every relation has its own
+    threshold, found for all of them in the same few fused sweeps (ops.relation_topk_scores), and a handful of relations cost
+    their share of a sweep.  Returns ``(subj int64 (m, k), obj int64 (m, k), logits float32 (m, k), info)`` in the order of
+    ``complete_relations_from_scores``: row i for ``relations[i]``, best first, ties by (s, o), short rows padded with -1 / -1 /
+    -inf; ``info['count']`` int64 [m], ``info['passes']``.  ``k >= 1`` and ``m * k <= max_results``; ``MineOverflow`` (naming the
+    relation) rather than a truncated list.  With a ``type_constraint`` (TypeConstraint) only type-correct pairs are candidates --
+    ``mine_triplets(type_constraint=)``'s rule on the same member lists, at the same logits (ops.relation_topk_scores_typed).  The
+    unconstrained call leaves the argument out; an explicit None is a TypeError."""
+    emb, wd, (lo, hi, ent), bias, type_constraint = _relation_setup(embedding, w, filter_index, flow_log_prob, type_constraint)
+    rule = dict(relations=relations, bias=bias, filt_lo=lo, filt_hi=hi, filt_ent=ent, exclude_self=exclude_self, max_results=max_results)
+    if type_constraint is not None:
+        set_ptr, set_ids = type_constraint.members(emb.device)
+        return ops.relation_topk_scores_typed(emb, wd, k, set_ptr, set_ids, **rule)
+    return ops.relation_topk_scores(emb, wd, k, **rule)
+
+
+def complete_relations_unfused(embedding, w, k, *, relations=None, filter_index=None, flow_log_prob=None, exclude_self=True,
+                               type_constraint=UNCONSTRAINED, max_results=ops.MINE_MAX_RESULTS):
+    """``complete_relations`` from materialised logits, one relation at a time: ``ops.gemm(ops.mul(E, w[r]), E^T)`` (+ bias), then
+    the rule of ``complete_relations_from_scores``.  The in-repo cross-check and the bench's comparator, never a fallback."""
+    emb, wd, filt, bias, type_constraint = _relation_setup(embedding, w, filter_index, flow_log_prob, type_constraint)
+    emb, wd = emb.contiguous(), wd.contiguous()
+    n, num_rels = emb.shape[0], wd.shape[0]
+    rels = ops.relation_ids_check(relations, num_rels).to(emb.device)
+    k, max_results, share = ops._relation_args(k, rels.numel(), max_results)
+    masks = None
+    if type_constraint is not None:
+        masks = (type_constraint.mask(torch.arange(num_rels, 2 * num_rels), emb.device), type_constraint.mask(torch.arange(num_rels), emb.device))
+
+    def pairs_of(i, r):
+        val = ops.gemm(ops.mul(emb, wd[r].expand_as(emb).contiguous()), emb, trans_b=True, precision='f32')
+        if bias is not None:
+            val = val + bias
+        return _relation_pairs(val, r, num_rels, k, filt, exclude_self, *((masks[0][r], masks[1][r]) if masks else ()))
+
+    return _relation_rows(pairs_of, rels, k, n, share)
+
+
 # ---- type-correct completions on the Monte-Carlo posterior predictive ---------------------------------------------------------
 MC_MINE_STACK_BYTES = 64 << 20      # bytes of the (S, chunk, h) query stack behind the spread of the mined triplets
 

@@ -189,6 +189,50 @@ def profile_entities_arg(spec, num_nodes):
     return ids
 
 
+def relation_profile_ids_arg(spec, num_rels=None):
+    """The relations of ``--relation-profile-ids``: None is every relation (a list only once ``num_rels`` is known), else
+    comma-separated ids or the path of a file with one id per line (blank lines skipped), kept in the order given.  Refused: a field
+    that is no integer, a negative id, a repeated id and, once ``num_rels`` is known, one outside [0, num_rels)."""
+    if spec is None:
+        return None if num_rels is None else list(range(num_rels))
+    if os.path.isfile(spec):
+        with open(spec) as f:
+            fields = [line.strip() for line in f if line.strip()]
+    else:
+        fields = [x.strip() for x in spec.split(',') if x.strip()]
+    try:
+        ids = [int(x) for x in fields]
+    except ValueError:
+        raise ValueError(f'--relation-profile-ids takes comma-separated relation ids or a file with one id per line, got {spec!r}') from None
+    if not ids:
+        raise ValueError(f'--relation-profile-ids names no relation: {spec!r}')
+    bad = [i for i in ids if i < 0 or (num_rels is not None and i >= num_rels)]
+    if bad:
+        raise ValueError(f"--relation-profile-ids: relation {bad[0]} lies outside [0, {'R' if num_rels is None else num_rels})")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f'--relation-profile-ids: relation {[i for i in ids if ids.count(i) > 1][0]} is named twice')
+    return ids
+
+
+def write_relation_profiles(path, embed, w, relations, k, filter_index, flow_log_prob=None, type_constraint=None):
+    """Per-relation completion as TSV, ``s  r  o  rank  logit`` (the columns of ``write_completions``: the two files join on s, r,
+    o): for every relation of ``relations``, in the order given, its OWN ``k`` most confident new facts
+    (ranking.complete_relations; ``filter_index``: the known ones left out, as are loops), best first with the rank counted from
+    1 within the relation.  A relation with fewer than k candidates has fewer lines.  With a ``type_constraint``
+    (ranking.TypeConstraint) only type-correct facts are written.  Returns the number of lines written."""
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    with torch.no_grad():
+        subj, obj, logits, _ = ranking.complete_relations(embed, w, k, relations=torch.as_tensor(relations, dtype=torch.long),
+                                                          filter_index=filter_index, flow_log_prob=flow_log_prob, **constrained)
+    n_lines = 0
+    with open(path, 'w') as f:
+        for r, ss, os_, xs in zip(relations, subj.tolist(), obj.tolist(), logits.tolist()):
+            lines = [f"{a}\t{r}\t{b}\t{i}\t{x:.9g}\n" for i, (a, b, x) in enumerate(zip(ss, os_, xs), 1) if a >= 0]
+            f.writelines(lines)
+            n_lines += len(lines)
+    return n_lines
+
+
 def profile_lines(side, entities, rel, other, *value_columns):
     """The lines of a per-entity TSV for one side, ``entity  side  relation  other_entity  rank  value...``: one per returned fact
     of every entity of ``entities`` (``rel``, ``other`` and each value column are its (m, k) results, best first), the rank counted
@@ -340,6 +384,14 @@ def check_args(args):
         raise ValueError(f'--profile-topk keeps one list of at most {ops.TOPK_MAX} facts per entity (0 = off), got {args.profile_topk}')
     if getattr(args, 'profile_typed', False) and not getattr(args, 'profile_topk', 0) > 0:
         raise ValueError('--profile-typed restricts the profiles: it needs --profile-topk')
+    if getattr(args, 'relation_profile_topk', 0) < 0:
+        raise ValueError(f'--relation-profile-topk counts the facts kept per relation: 0 (off) or more, got {args.relation_profile_topk}')
+    if getattr(args, 'relation_profile_typed', False) and not getattr(args, 'relation_profile_topk', 0) > 0:
+        raise ValueError('--relation-profile-typed restricts the per-relation lists: it needs --relation-profile-topk')
+    if getattr(args, 'relation_profile_ids', None) is not None:
+        if not getattr(args, 'relation_profile_topk', 0) > 0:
+            raise ValueError('--relation-profile-ids chooses the relations of the per-relation lists: it needs --relation-profile-topk')
+        relation_profile_ids_arg(args.relation_profile_ids)
     if not 0 <= getattr(args, 'predict_relations', 0) <= ops.TOPK_MAX:
         raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
     relations = getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0
@@ -354,6 +406,7 @@ def check_args(args):
     wants = [f for f, on in (('--relation-eval', getattr(args, 'relation_eval', False)),
                              ('--predict-relations', getattr(args, 'predict_relations', 0) > 0),
                              ('--profile-topk', getattr(args, 'profile_topk', 0) > 0),
+                             ('--relation-profile-topk', getattr(args, 'relation_profile_topk', 0) > 0),
                              ('--complete-topk', getattr(args, 'complete_topk', 0) > 0),
                              ('--complete-threshold', getattr(args, 'complete_threshold', None) is not None),
                              ('--sample-graph', getattr(args, 'sample_graph', 0) > 0)) if on]
@@ -408,6 +461,8 @@ def main(args):
     data = load_data(args.dataset)
     num_nodes, num_rels = data.num_nodes, data.num_rels
     train_data, valid_data, test_data = data.train, data.valid, data.test
+    if getattr(args, 'relation_profile_topk', 0) > 0:
+        relation_profile_ids_arg(getattr(args, 'relation_profile_ids', None), num_rels)      # a bad id: before the model is built
 
     if args.gpu < 0 or not torch.cuda.is_available():
         raise RuntimeError('gcn_vae_amd runs on a ROCm device only (pass --gpu N on an MI355X box); '
@@ -470,6 +525,18 @@ def main(args):
                                             model.encoder.get_flow_log_prob(), typed)
             print(f"wrote {n_lines} new {'type-correct ' if typed is not None else ''}facts around {len(who)} entities (top "
                   f"{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}")
+        if getattr(args, 'relation_profile_topk', 0) > 0:
+            known = filters if filters is not None else \
+                ranking.FilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            which = relation_profile_ids_arg(getattr(args, 'relation_profile_ids', None), num_rels)
+            typed = None
+            if getattr(args, 'relation_profile_typed', False):      # (--type-constrain's sets are the same ones, when it is given as well)
+                typed = types if types is not None else \
+                    ranking.TypeConstraint(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
+            n_lines = write_relation_profiles(args.relation_profile_out, embed, model.w_relation, which, args.relation_profile_topk,
+                                              known, model.encoder.get_flow_log_prob(), typed)
+            print(f"wrote {n_lines} new {'type-correct ' if typed is not None else ''}facts of {len(which)} relations (each "
+                  f"relation's own top {args.relation_profile_topk}, known triplets filtered) to {args.relation_profile_out}")
         if getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0:
             pairs = ranking.PairFilterIndex(num_nodes, num_rels, train_data, valid_data, test_data, device=dev)
             rel_types = None
@@ -780,6 +847,19 @@ def build_parser():
                    help="with --profile-topk: write type-correct facts only (the entity seen on its side of the relation, the other "
                         "entity seen on the other side, in train + valid + test); the same columns; --type-constrain does not "
                         "constrain profiles")
+    p.add_argument("--relation-profile-topk", type=int, default=0,
+                   help="with --test-mode: for every relation of --relation-profile-ids write ITS OWN K most confident NEW facts "
+                        "(train + valid + test triplets and loops left out) to --relation-profile-out -- every relation has its own "
+                        "threshold, where --complete-topk has one for the whole graph; 0 = off; not a reference flag")
+    p.add_argument("--relation-profile-ids", type=str, default=None,
+                   help="the relations of --relation-profile-topk: comma-separated ids, or a file with one id per line, each at most "
+                        "once; default: every relation")
+    p.add_argument("--relation-profile-out", type=str, default="relation_profiles.tsv",
+                   help="TSV of --relation-profile-topk: s, r, o, rank from 1 within the relation, logit; relations in the order "
+                        "asked; joins with --complete-out on s, r, o")
+    p.add_argument("--relation-profile-typed", action="store_true",
+                   help="with --relation-profile-topk: write type-correct facts only (s seen as subject of r, o seen as its object, "
+                        "in train + valid + test); the same columns; --type-constrain and --complete-typed keep their meaning")
     p.add_argument("--mc-profile", action="store_true",
                    help="with --mc-samples and --profile-topk: also write the profiles on the posterior predictive (each entity's K "
                         "new facts of highest mean probability over the samples, with the spread) to --mc-profile-out; honours "

@@ -783,6 +783,38 @@ int gv_mine_scores_typed(const float* e, int ld_e, const float* w, int ld_w, con
                          uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                          uint64_t* counter, uint64_t* hist, int n, int num_rels, int h, void* stream);
 
+/* Per-relation completion (csrc/k_mine.hip): gv_mine_scores / gv_mine_scores_typed with the selection state PER RELATION, so that
+ * one sweep serves every relation's own top-K.  A slot i < m is the relation rels[i] (int32 [m], device memory) with its own
+ *   key_min [m] (uint32), counter [m] (uint64) and output segment out[out_base[i] .. out_base[i + 1]) (out_base int64 [m + 1],
+ *                 records of out [capacity][4]; a segment is clamped into [0, capacity])                        -- GV_MINE_EMIT
+ *   prefix [m] (uint32; not read at prefix_bits 0) and histogram hist [i << bin_bits .. (i + 1) << bin_bits)   -- GV_MINE_HIST
+ * while prefix_bits and bin_bits are the pass's.  Slot i's counter ends as the number of its candidates with key >= key_min[i] and
+ * keeps counting past its segment; all m counters (EMIT) or all m << bin_bits histogram words (HIST) are zeroed here.  An id
+ * outside [0, num_rels) makes the slot EMPTY for this pass -- nothing of it is scored, counted or written: this is how a slot whose
+ * threshold is already known sits out a later histogram pass -- and a relation that is in no slot costs nothing.  A record is
+ * (s, r, o, bits of the logit) with r the relation, not the slot; logits, keys, candidates, filter and exclude_self are those of
+ * gv_mine_scores (gv_mine_scores_typed) bit for bit.
+ * gv_mine_scores_by_relation walks gv_mine_scores' loop order over the slots (a workgroup owns a tile pair and a span of slots);
+ * its histogram levels have 1 <= bin_bits <= 8 (a 256-bin LDS histogram per relation, flushed after every relation).  The workspace
+ * is gv_mine_scores' (gv_mine_scores_workspace_bytes; only with a filter).
+ * gv_mine_scores_typed_by_relation takes gv_mine_scores_typed's member lists, filter and units, except that a unit's first word is
+ * the SLOT whose relation it walks (a unit of a slot outside [0, m) or of an empty slot does nothing); 1 <= bin_bits <= 12.
+ * Checked on the host before any launch, the message naming the entry: everything gv_mine_scores (gv_mine_scores_typed) checks,
+ * 1 <= m <= num_rels, m << bin_bits <= 2^24 histogram words, the per-slot arrays of the mode not NULL, out 16-byte aligned.
+ * n == 0: nothing is launched.  Integer atomics on the counters and the histograms only; the result does not depend on the spans
+ * or the launch geometry. */
+int gv_mine_scores_by_relation(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int32_t* filt_lo,
+                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                               const int32_t* rels, int m, const uint32_t* key_min, int prefix_bits, const uint32_t* prefix,
+                               int bin_bits, int32_t* out, int64_t capacity, const int64_t* out_base, uint64_t* counter,
+                               uint64_t* hist, void* workspace, int64_t workspace_bytes, int n, int num_rels, int h, void* stream);
+int gv_mine_scores_typed_by_relation(const float* e, int ld_e, const float* w, int ld_w, const float* bias, const int64_t* set_ptr,
+                                     const int32_t* set_ids, const int32_t* units, int64_t n_units, const int32_t* filt_lo,
+                                     const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                                     const int32_t* rels, int m, const uint32_t* key_min, int prefix_bits, const uint32_t* prefix,
+                                     int bin_bits, int32_t* out, int64_t capacity, const int64_t* out_base, uint64_t* counter,
+                                     uint64_t* hist, int n, int num_rels, int h, void* stream);
+
 /* Type-constrained mining on the Monte-Carlo posterior predictive (csrc/k_mine.hip): gv_mine_scores_typed with n_samples entity
  * tables.  Sample s reads e + s * e_stride (elements; the leading dimension ld_e is shared), the one w, and bias[s] when bias is
  * given (n_samples floats).  The value that is selected is
