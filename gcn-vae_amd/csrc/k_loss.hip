@@ -1220,6 +1220,172 @@ __global__ __launch_bounds__(64 * MMD_WAVES) void k_mmd_bwd_g(const float* x, co
     }
 }
 
+// ONE SWEEP FOR THE VALUE AND BOTH GRADIENTS (gv_mmd_fwd_grad; inside the DistMult forward launch: k_distmult_bce_fwd_grad_mmd).
+// d mmd / d a is linear in the upstream scalar, and the backward's loop over the row pairs computes every K(a, b) the value needs:
+// a workgroup of 256 threads (4 waves x 4 DPP rows: 16 partner rows a sweep, two sweeps in flight) owns one row and leaves its
+// value partial (gv_loss_combine's layout: x rows, then y rows) and its gradient row AT UPSTREAM 1 in the dense buffers gx_u
+// [sx][h], gy_u [sy][h]; k_mmd_grad_finish scales by the upstream scalar, which does not exist yet when this runs.
+// Per element the expressions of k_mmd_fwd_g / k_mmd_bwd_g (direct differences, expf(-d2 * inv), the coefficients at gg = 1).
+// Summation order: a lane chains its columns in ascending order, the row butterfly of row16_sum, a group's partner rows in
+// ascending order (same set, then the other set), the wave's four groups in group order, the four waves in wave order through
+// LDS.  No atomics.
+struct MmdSweepParams {
+    const float* x;
+    const float* y;
+    const int64_t* yidx;
+    int sx, sy, h;
+    float* part;         // [sx + sy]
+    float* gx_u;         // [sx][h]
+    float* gy_u;         // [sy][h]: row j belongs to y row yidx[j]
+};
+
+template <int G>
+__device__ __forceinline__ void mmd_row_sweep(const MmdSweepParams& a, int blk, float4* sm /*[4][16 G]*/, float* smv /*[4]*/) {
+    const int lane = threadIdx.x & 63, l16 = lane & 15, w = threadIdx.x >> 6;
+    const int grp = (int)(threadIdx.x >> 4);                  // 16 groups of 16 lanes
+    constexpr int NG = 16;
+    const int sx = a.sx, sy = a.sy, h = a.h;
+    const bool is_x = blk < sx;
+    const int row = is_x ? blk : blk - sx;
+    auto row_of = [&](bool from_y, int j) -> const float* {
+        return from_y ? a.y + (size_t)(a.yidx ? a.yidx[j] : j) * h : a.x + (size_t)j * h;
+    };
+    bool on[G];
+    int col[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) { col[g] = 4 * (l16 + 16 * g); on[g] = col[g] < h; }
+    float4 av[G], acc[G];
+    mmd_load_row4<G>(row_of(!is_x, row), on, col, av);
+#pragma unroll
+    for (int g = 0; g < G; ++g) acc[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float inv = 1.f / ((float)h * (float)h);
+    const int n_same = is_x ? sx : sy, n_other = is_x ? sy : sx;
+    const float c_same = (-2.f * inv) * 2.f / ((float)n_same * (float)n_same);
+    const float c_other = (-2.f * inv) * (-2.f) / ((float)sx * (float)sy);
+    float tot = 0.f;
+    // x rows: + Kxx/sx^2 - 2 Kxy/(sx sy);   y rows: + Kyy/sy^2 (their cross pass feeds the gradient only)
+    for (int pass = 0; pass < 2; ++pass) {
+        const bool b_is_y = pass == 0 ? !is_x : is_x;
+        const int nb = pass == 0 ? n_same : n_other;
+        const float cf = pass == 0 ? c_same : c_other;
+        const float wt = pass == 0 ? 1.f / ((float)nb * (float)nb) : (is_x ? -2.f / ((float)sx * (float)sy) : 0.f);
+        const bool counted = pass == 0 || is_x;
+        for (int j0 = 0; j0 < nb; j0 += 2 * NG) {               // (uniform trip count: the row reductions run in every lane)
+            const int j = j0 + grp, j1 = j + NG;
+            float4 b0[G], b1[G];
+            mmd_load_row4<G>(row_of(b_is_y, min(j, nb - 1)), on, col, b0);
+            mmd_load_row4<G>(row_of(b_is_y, min(j1, nb - 1)), on, col, b1);
+            const float d0 = row16_sum(mmd_d2_4<G>(av, b0)), d1 = row16_sum(mmd_d2_4<G>(av, b1));
+            const float e0 = expf(-d0 * inv), e1 = expf(-d1 * inv);
+            if (counted && j < nb) tot += wt * e0;
+            if (counted && j1 < nb) tot += wt * e1;
+            const float k0 = j < nb ? cf * e0 : 0.f, k1 = j1 < nb ? cf * e1 : 0.f;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                acc[g].x = fmaf(k0, av[g].x - b0[g].x, fmaf(k1, av[g].x - b1[g].x, acc[g].x));
+                acc[g].y = fmaf(k0, av[g].y - b0[g].y, fmaf(k1, av[g].y - b1[g].y, acc[g].y));
+                acc[g].z = fmaf(k0, av[g].z - b0[g].z, fmaf(k1, av[g].z - b1[g].z, acc[g].z));
+                acc[g].w = fmaf(k0, av[g].w - b0[g].w, fmaf(k1, av[g].w - b1[g].w, acc[g].w));
+            }
+        }
+    }
+    // a wave's four groups hold the same columns in lanes l16, 16 + l16, 32 + l16, 48 + l16
+    const float t = ((rl_bcast_f(tot, 0) + rl_bcast_f(tot, 16)) + rl_bcast_f(tot, 32)) + rl_bcast_f(tot, 48);
+    if (lane == 0) smv[w] = t;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float4 s;
+        s.x = ((rl_dyn(acc[g].x, l16) + rl_dyn(acc[g].x, 16 + l16)) + rl_dyn(acc[g].x, 32 + l16)) + rl_dyn(acc[g].x, 48 + l16);
+        s.y = ((rl_dyn(acc[g].y, l16) + rl_dyn(acc[g].y, 16 + l16)) + rl_dyn(acc[g].y, 32 + l16)) + rl_dyn(acc[g].y, 48 + l16);
+        s.z = ((rl_dyn(acc[g].z, l16) + rl_dyn(acc[g].z, 16 + l16)) + rl_dyn(acc[g].z, 32 + l16)) + rl_dyn(acc[g].z, 48 + l16);
+        s.w = ((rl_dyn(acc[g].w, l16) + rl_dyn(acc[g].w, 16 + l16)) + rl_dyn(acc[g].w, 32 + l16)) + rl_dyn(acc[g].w, 48 + l16);
+        if (lane < 16) sm[w * (16 * G) + l16 + 16 * g] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.part[blk] = ((smv[0] + smv[1]) + smv[2]) + smv[3];
+    float* o = (is_x ? a.gx_u : a.gy_u) + (size_t)row * h;
+    for (int q = threadIdx.x; q < (h >> 2); q += 256) {
+        float4 s4 = sm[q];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) { const float4 v = sm[i * (16 * G) + q]; s4.x += v.x; s4.y += v.y; s4.z += v.z; s4.w += v.w; }
+        *reinterpret_cast<float4*>(o + 4 * q) = s4;
+    }
+}
+
+// The sweep as a launch of its own (gv_mmd_fwd_grad): what the tests call; the loss head takes the combined launch (G = 4) only.
+template <int G>
+__global__ __launch_bounds__(256) void k_mmd_fwd_grad(const MmdSweepParams a) {
+    __shared__ float4 lds[4 * 16 * G + 1];
+    mmd_row_sweep<G>(a, (int)blockIdx.x, lds, reinterpret_cast<float*>(lds + 4 * 16 * G));
+}
+
+// The backward's one launch behind the sweep, the blocks dealt by range (gg = gscale * (gmmd ? *gmmd : 1)):
+//   [0, sy)                 gy[yidx[row]] += gg * gy_u[row]   (float atomics: an index may repeat; without yidx the row is stored)
+//   [sy, + ceil(k h / 256)) k_prior_sample_bwd's two rows of z_pre's gradient from g = gg * gx_u and eps, the same expressions,
+//                           stored or accumulated; g itself goes to g_pri (z_pri's gradient) where that is asked for
+struct MmdFinishParams {
+    const float* gmmd;
+    float gscale;
+    const float* gx_u;
+    const float* gy_u;
+    const int64_t* yidx;
+    int sx, sy, h;
+    float* gy;
+    float* g_pri;
+    const float* z_pre;
+    const float* eps;
+    float* gz_pre;
+    int accumulate, k;
+};
+
+__global__ __launch_bounds__(256) void k_mmd_grad_finish(const MmdFinishParams a) {
+    const float gg = a.gscale * (a.gmmd ? *a.gmmd : 1.f);
+    const int h = a.h;
+    if ((int)blockIdx.x < a.sy) {
+        const int row = blockIdx.x;
+        const float* src = a.gy_u + (size_t)row * h;
+        float* o = a.gy + (size_t)(a.yidx ? a.yidx[row] : row) * h;
+        for (int c = threadIdx.x; c < h; c += 256) {
+            const float v = gg * src[c];
+            if (a.yidx) atomicAdd(o + c, v);
+            else o[c] = v;
+        }
+        return;
+    }
+    const int total = a.k * h;
+    const int i = ((int)blockIdx.x - a.sy) * 256 + (int)threadIdx.x;
+    if (i >= total) return;
+    const int j = i / h, c = i - j * h;
+    const float raw = a.z_pre[(size_t)(a.k + j) * h + c];
+    const float v = softplus_t(raw) + 1e-8f;
+    float gm = 0.f, gs = 0.f;
+    // eight repeats' loads in flight (a loop of dependent round trips is what the launch costs); summed in ascending row order
+    constexpr int RU = 8;
+    const int last = a.sx - a.k + j;                    // this component's last row
+    for (int r0 = j; r0 < a.sx; r0 += RU * a.k) {
+        float gu[RU], ev[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            const size_t at = (size_t)min(r0 + u * a.k, last) * h + c;
+            gu[u] = a.gx_u[at];
+            ev[u] = a.eps[at];
+        }
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            const int r = r0 + u * a.k;
+            if (r < a.sx) {
+                const float g = gg * gu[u];
+                if (a.g_pri) a.g_pri[(size_t)r * h + c] = g;
+                gm += g;
+                gs += g * ev[u];
+            }
+        }
+    }
+    const float gr = gs * 0.5f / sqrtf(v) * (raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw)));
+    a.gz_pre[i] = a.accumulate ? a.gz_pre[i] + gm : gm;
+    a.gz_pre[total + i] = a.accumulate ? a.gz_pre[total + i] + gr : gr;
+}
+
 // prior samples of get_mmd: z_pri[i] = mu[i % k] + eps[i] * sqrt(softplus(raw[i % k]) + 1e-8)   (z_pre = [mu; raw], (2k, h))
 __global__ __launch_bounds__(256) void k_prior_sample_fwd(const float* z_pre, const float* eps, float* out, int s, int k, int h) {
     const int total = s * h;
@@ -1296,11 +1462,12 @@ __device__ __forceinline__ float dm_delta(float x, float y) { return 1.f / (1.f 
 // Steps in flight, on the MI355X at T = 220 000, h = 200: 1 / 2 / 3 -> 95 / 127 / 161 registers, 36.6 / 35.4 / 38.7 us (NOTES.md).
 constexpr int DM_U = 2;
 
-__global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedParams a) {
+// The body of workgroup `bid` of `nblk` (the launch's own index and grid, or those behind the MMD blocks of the combined launch).
+//   sm [4];  tb [4][64]: a wave's batch, (s, o, label, score) of batch lane j;  sums [2][256]: per thread, the BCE terms and deltas
+//   of the triplets whose scalars it finishes
+__device__ __forceinline__ void dm_fused_body(const DmFusedParams& a, const int bid, const int nblk, float* sm, int4 (*tb)[64],
+                                              float (*sums)[256]) {
     constexpr int U = DM_U;
-    __shared__ float sm[4];
-    __shared__ int4 tb[4][64];          // a wave's batch: (s, o, label, score) of batch lane j
-    __shared__ float sums[2][256];      // per thread: BCE terms and deltas of the triplets whose scalars it finishes
     constexpr int G = 4;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l16 = lane & 15, rw = lane >> 4;
@@ -1310,7 +1477,7 @@ __global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedPara
     const float bv = a.bias ? *a.bias : 0.f;
     const float* __restrict__ ebase = a.e + 4 * l16;
     sums[0][threadIdx.x] = sums[1][threadIdx.x] = 0.f;
-    for (int quad = blockIdx.x; quad * 4 < a.n_items; quad += gridDim.x) {
+    for (int quad = bid; quad * 4 < a.n_items; quad += nblk) {
         const int item = __builtin_amdgcn_readfirstlane(quad * 4 + wv);
         if (item >= a.n_items) continue;
         const int4 it = a.items[item];
@@ -1405,9 +1572,31 @@ __global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedPara
     const float lt = block_sum_256(sums[0][threadIdx.x], sm);
     const float dt = block_sum_256(sums[1][threadIdx.x], sm);
     if (threadIdx.x == 0) {
-        a.part[blockIdx.x] = lt;
-        a.part[DM_PART + blockIdx.x] = dt;
+        a.part[bid] = lt;
+        a.part[DM_PART + bid] = dt;
     }
+}
+
+__global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad(const DmFusedParams a) {
+    __shared__ float sm[4];
+    __shared__ int4 tb[4][64];
+    __shared__ float sums[2][256];
+    dm_fused_body(a, (int)blockIdx.x, (int)gridDim.x, sm, tb, sums);
+}
+
+// The same launch with the MMD sweep's sx + sy row workgroups in front (dispatched first; the branch is block-uniform).  The
+// DistMult sweep leaves more than half of its workgroup slots without an item at the default shape (1 856 items for 1 024
+// SIMDs), the MMD rows need z, z_pri and pick only, and extra workgroups in a launch cost no launch boundary.  One LDS array
+// for both bodies: [0, 256) tb or the MMD wave sums, [256, 384) sums, [384] sm or the MMD value sums.
+__global__ __launch_bounds__(256) void k_distmult_bce_fwd_grad_mmd(const DmFusedParams a, const MmdSweepParams m) {
+    __shared__ float4 lds[385];
+    const int n_mmd = m.sx + m.sy;
+    if ((int)blockIdx.x < n_mmd) {
+        mmd_row_sweep<4>(m, (int)blockIdx.x, lds, reinterpret_cast<float*>(lds + 384));
+        return;
+    }
+    dm_fused_body(a, (int)blockIdx.x - n_mmd, (int)gridDim.x - n_mmd, reinterpret_cast<float*>(lds + 384),
+                  reinterpret_cast<int4(*)[64]>(lds), reinterpret_cast<float(*)[256]>(lds + 256));
 }
 
 // The backward's one launch behind it, the blocks dealt by range:
@@ -1900,6 +2089,60 @@ extern "C" int gv_distmult_bce_fwd_grad(const int32_t* items, int n_items, const
                     score, delta, u, partial, workspace, h};
     hipLaunchKernelGGL(k_distmult_bce_fwd_grad, dim3(red_blocks(t, 16)), dim3(256), 0, GV_ST, p);
     return launch_status("gv_distmult_bce_fwd_grad");
+}
+
+// THE shape rule of the one-sweep MMD (restated by ops.mmd_sweep_ok)
+static int mmd_sweep_args(const char* who, const float* x, const float* y, int sx, int sy, int h, int h_max, const float* part,
+                          const float* gx_u, const float* gy_u) {
+    GV_REQUIRE(x && y && part && gx_u && gy_u, GV_ERR_NULL, "%s: NULL pointer", who);
+    GV_REQUIRE(sx > 0 && sy > 0 && sx + sy <= RED_BLOCKS && h > 0 && h <= h_max && h % 4 == 0, GV_ERR_SHAPE,
+               "%s: sx=%d sy=%d h=%d (need h %% 4 == 0, h <= %d, sx+sy <= %d)", who, sx, sy, h, h_max, RED_BLOCKS);
+    GV_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gx_u) && aligned16(gy_u), GV_ERR_ALIGN, "%s: 16-B alignment required",
+               who);
+    return GV_OK;
+}
+
+extern "C" int gv_mmd_fwd_grad(const float* x, const float* y, const int64_t* y_index, int sx, int sy, int h, float* part,
+                               float* gx_u, float* gy_u, void* stream) {
+    if (const int rc = mmd_sweep_args("gv_mmd_fwd_grad", x, y, sx, sy, h, 512, part, gx_u, gy_u)) return rc;
+    MmdSweepParams m{x, y, y_index, sx, sy, h, part, gx_u, gy_u};
+    if (h <= 256) hipLaunchKernelGGL(k_mmd_fwd_grad<4>, dim3(sx + sy), dim3(256), 0, GV_ST, m);
+    else hipLaunchKernelGGL(k_mmd_fwd_grad<8>, dim3(sx + sy), dim3(256), 0, GV_ST, m);
+    return launch_status("gv_mmd_fwd_grad");
+}
+
+extern "C" int gv_distmult_bce_fwd_grad_mmd(const int32_t* items, int n_items, const int32_t* rel_s, const int32_t* rel_o,
+                                            const int32_t* rel_tid, const float* embed, int ld_e, const float* w_rel, int ld_w,
+                                            const float* labels, const float* bias, const int32_t* pos3, float* score,
+                                            float* delta, float* u, float* partial, float* workspace, int64_t t, int h,
+                                            const float* mmd_x, const float* mmd_y, const int64_t* mmd_y_index, int sx, int sy,
+                                            int mmd_h, float* mmd_part, float* gx_u, float* gy_u, void* stream) {
+    GV_REQUIRE(items && rel_s && rel_o && rel_tid && embed && w_rel && labels && score && delta && u && workspace,
+               GV_ERR_NULL, "gv_distmult_bce_fwd_grad_mmd: NULL pointer");
+    GV_REQUIRE(t > 0 && t < (1ll << 30) && n_items > 0, GV_ERR_SHAPE, "gv_distmult_bce_fwd_grad_mmd: t=%lld n_items=%d",
+               (long long)t, n_items);
+    GV_REQUIRE(h > 0 && h <= 256 && h % 4 == 0 && ld_e >= h && ld_w >= h && ld_e % 4 == 0 && ld_w % 4 == 0, GV_ERR_SHAPE,
+               "gv_distmult_bce_fwd_grad_mmd: h=%d (ld %d, %d): the fused sweep covers h <= 256, h %% 4 == 0", h, ld_e, ld_w);
+    GV_REQUIRE(aligned16(embed) && aligned16(w_rel) && aligned16(u) && aligned16(partial), GV_ERR_ALIGN,
+               "gv_distmult_bce_fwd_grad_mmd: 16-B alignment required");
+    if (const int rc = mmd_sweep_args("gv_distmult_bce_fwd_grad_mmd", mmd_x, mmd_y, sx, sy, mmd_h, 256, mmd_part, gx_u, gy_u))
+        return rc;
+    DmFusedParams p{(const int4*)items, n_items, rel_s, rel_o, rel_tid, embed, ld_e, w_rel, ld_w, labels, bias, pos3,
+                    score, delta, u, partial, workspace, h};
+    MmdSweepParams m{mmd_x, mmd_y, mmd_y_index, sx, sy, mmd_h, mmd_part, gx_u, gy_u};
+    hipLaunchKernelGGL(k_distmult_bce_fwd_grad_mmd, dim3(sx + sy + red_blocks(t, 16)), dim3(256), 0, GV_ST, p, m);
+    return launch_status("gv_distmult_bce_fwd_grad_mmd");
+}
+
+extern "C" int gv_mmd_grad_finish(const float* gx_u, const float* gy_u, const int64_t* y_index, int sx, int sy, int h,
+                                  const float* gmmd, float gscale, float* gy, float* g_pri, const float* z_pre, const float* eps,
+                                  float* gz_pre, int accumulate, int k, void* stream) {
+    GV_REQUIRE(gx_u && gy_u && gy && z_pre && eps && gz_pre, GV_ERR_NULL, "gv_mmd_grad_finish: NULL pointer");
+    GV_REQUIRE(sx > 0 && sy > 0 && h > 0 && k > 0 && sx % k == 0, GV_ERR_SHAPE,
+               "gv_mmd_grad_finish: sx=%d sy=%d h=%d k=%d (the prior rows are whole repeats of the k components)", sx, sy, h, k);
+    MmdFinishParams p{gmmd, gscale, gx_u, gy_u, y_index, sx, sy, h, gy, g_pri, z_pre, eps, gz_pre, accumulate, k};
+    hipLaunchKernelGGL(k_mmd_grad_finish, dim3(sy + (k * h + 255) / 256), dim3(256), 0, GV_ST, p);
+    return launch_status("gv_mmd_grad_finish");
 }
 
 extern "C" int gv_distmult_grad_finish(const float* gloss, const float* u, const float* partial, const int32_t* fix,

@@ -201,6 +201,10 @@ SIGNATURES = {
     'gv_mmd_bwd': (_I, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P]),
     'gv_prior_sample_fwd': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'gv_prior_sample_bwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'gv_mmd_fwd_grad': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'gv_distmult_bce_fwd_grad_mmd': (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I,
+                                          _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'gv_mmd_grad_finish': (_I, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _I, _I, _P]),
     'gv_iaf_update_fwd': (_I, [_P, _P, _I, _P, _P, _P, _L, _I, _P]),
     'gv_iaf_update_bwd': (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     'gv_iaf_update_bwd_acc': (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _L, _I, _P]),

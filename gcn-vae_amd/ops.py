@@ -3290,17 +3290,23 @@ def distmult_fused_ok(embed, ld_e, w_rel, ld_w):
             and embed.data_ptr() % 16 == 0 and w_rel.data_ptr() % 16 == 0)
 
 
-def _distmult_fused_fwd(embed, ld_e, w_rel, ld_w, labels, bias, tidx, score, ws):
-    """Launch the fused forward; returns what the finishing launch needs: (delta, u, partial).  ``ws``: 2048 floats."""
+def _distmult_fused_fwd(embed, ld_e, w_rel, ld_w, labels, bias, tidx, score, ws, mmd=None):
+    """Launch the fused forward; returns what the finishing launch needs: (delta, u, partial).  ``ws``: 2048 floats.
+    ``mmd`` = (z_pri, z, pick, part, gx_u, gy_u): the MMD sweep's row workgroups ride in the same launch."""
     seg, T, h = tidx.rel, tidx.T, embed.shape[1]
     _check_items(seg)
     f32 = dict(dtype=torch.float32, device=embed.device)
     delta = torch.empty(2 * T if tidx.pos3 is not None else T, **f32)
     u = torch.empty(w_rel.shape[0], h, **f32)
     partial = torch.empty(seg.n_slots, h, **f32) if seg.n_fix > 0 else None
-    lib.call('gv_distmult_bce_fwd_grad', ptr(seg.items), seg.n_items, ptr(tidx.rel_s), ptr(tidx.rel_o), ptr(tidx.rel_tid),
-             ptr(embed), ld_e, ptr(w_rel), ld_w, ptr(labels), ptr(bias), ptr(tidx.pos3), ptr(score), ptr(delta), ptr(u),
-             ptr(partial), ptr(ws), T, h, lib.stream())
+    args = (ptr(seg.items), seg.n_items, ptr(tidx.rel_s), ptr(tidx.rel_o), ptr(tidx.rel_tid), ptr(embed), ld_e, ptr(w_rel), ld_w,
+            ptr(labels), ptr(bias), ptr(tidx.pos3), ptr(score), ptr(delta), ptr(u), ptr(partial), ptr(ws), T, h)
+    if mmd is None:
+        lib.call('gv_distmult_bce_fwd_grad', *args, lib.stream())
+    else:
+        x, y, pick, part, gx_u, gy_u = mmd
+        lib.call('gv_distmult_bce_fwd_grad_mmd', *args, ptr(x), ptr(y), ptr(pick), x.shape[0], pick.numel(), x.shape[1],
+                 ptr(part), ptr(gx_u), ptr(gy_u), lib.stream())
     return delta, u, partial
 
 
@@ -3649,34 +3655,100 @@ def mmd(x, y):
     return _MMD.apply(x, y)
 
 
+# The MMD term's value and gradients in one sweep, riding in the fused DistMult forward launch (gv_distmult_bce_fwd_grad_mmd), and
+# ONE finishing launch in the backward (gv_mmd_grad_finish) in place of gv_mmd_fwd + gv_mmd_bwd + gv_prior_sample_bwd.
+# GV_MMD_FUSED=0: the separate launches.
+MMD_FUSED = _os.environ.get('GV_MMD_FUSED', '1') == '1'
+
+
+def mmd_sweep_ok(z_pri, z, h_max=256):
+    """THE shape rule of the one-sweep MMD inside the DistMult launch: a partner row's 16 lanes hold up to four float4 columns each
+    (h <= 256, h % 4 == 0, 16-B aligned rows) and a workgroup per row leaves one of gv_loss_combine's 1024 partial slots."""
+    h = z_pri.shape[1]
+    return (MMD_FUSED and h % 4 == 0 and h <= h_max and z.shape[1] == h and z_pri.data_ptr() % 16 == 0
+            and z.data_ptr() % 16 == 0)
+
+
+class PriorLink:
+    """Hand-off between the prior sampler's node and the loss head that takes its output as z_pri: the sampler's forward leaves
+    z_pre and eps here; a loss head on the one-sweep MMD route claims the link (once) and its backward's finishing launch
+    (gv_mmd_grad_finish) produces z_pre's gradient from the unscaled MMD rows itself.  It records the z_pri gradient buffer it
+    returned in ``buf``; the sampler's backward skips its own launch only for that very buffer."""
+    __slots__ = ('z_pre', 'eps', 'out_ptr', 'out_version', 'out_shape', 'claimed', 'buf', 'buf_version', 'gz')
+
+    def __init__(self, z_pre, eps, out):
+        self.z_pre, self.eps = z_pre, eps
+        self.out_ptr, self.out_version, self.out_shape = out.data_ptr(), out._version, tuple(out.shape)
+        self.claimed = False          # ONE loss head may take the hand-off; a second one on the same z_pri runs the separate launches
+        self.buf = self.gz = None
+        self.buf_version = 0
+
+    def matches(self, z_pri):
+        return (z_pri is not None and z_pri.data_ptr() == self.out_ptr and z_pri._version == self.out_version
+                and tuple(z_pri.shape) == self.out_shape and z_pri.is_contiguous())
+
+    def record(self, buf, gz):
+        self.buf, self.buf_version, self.gz = buf, buf._version, gz
+
+    def take(self, grad_out):
+        """The sampler's backward: None when nothing was folded; (gz,) -- gz None when z_pre's gradient went straight into its
+        direct target -- when ``grad_out`` is the buffer the loss head returned, untouched; raises when the fold happened but
+        another gradient was added to z_pri's (z_pre's share of it would be lost)."""
+        buf, version, gz = self.buf, self.buf_version, self.gz
+        self.buf = self.gz = None
+        if buf is None:
+            return None
+        if (grad_out is None or grad_out.data_ptr() != buf.data_ptr() or tuple(grad_out.shape) != tuple(buf.shape)
+                or grad_out.dtype != buf.dtype or not grad_out.is_contiguous() or grad_out._version != version):
+            raise RuntimeError('the prior sampler\'s backward was folded into the loss head\'s MMD finishing launch (ops.PriorLink), '
+                               'but the gradient arriving at the sampler is not that buffer: something else consumed z_pri as well.  '
+                               'Only hand a linked z_pri to ops.loss_head when the head is its sole consumer (GV_MMD_FUSED=0 turns '
+                               'the fold off)')
+        return (gz,)
+
+
 class _PriorSample(torch.autograd.Function):
     """z_pri = cat([m]*repeat) + eps * cat([sqrt(softplus(raw)+1e-8)]*repeat) for z_pre = [m; raw] (2k, h)."""
 
     @staticmethod
-    def forward(ctx, z_pre, eps):
+    def forward(ctx, z_pre, eps, link_box=None):
         z_pre, eps = _chk(z_pre.contiguous(), name='z_pre'), _chk(eps.contiguous(), name='eps')
         k, h = z_pre.shape[0] // 2, z_pre.shape[1]
         out = torch.empty_like(eps)
         ctx.set_materialize_grads(False)
         lib.call('gv_prior_sample_fwd', ptr(z_pre), ptr(eps), ptr(out), eps.shape[0], k, h, lib.stream())
         ctx.save_for_backward(z_pre, eps)
+        ctx.link = None
+        if link_box is not None and eps.shape[0] % k == 0:
+            ctx.link = link_box[0] = PriorLink(z_pre, eps, out)
         return out
 
     @staticmethod
     def backward(ctx, g):
         z_pre, eps = ctx.saved_tensors
+        link = ctx.link
+        if link is not None and link.claimed:
+            folded = link.take(g)
+            if folded is not None:
+                return folded[0], None, None
         if g is None:
-            return None, None
+            return None, None, None
         g = _chk(g.contiguous(), name='g')
         d_zp = _direct_flat(z_pre)
         gz = d_zp if d_zp is not None else torch.empty_like(z_pre)
         lib.call('gv_prior_sample_bwd', ptr(z_pre), ptr(eps), ptr(g), ptr(gz), 1 if d_zp is not None else 0, eps.shape[0],
                  z_pre.shape[0] // 2, z_pre.shape[1], lib.stream())
-        return (None if d_zp is not None else gz), None
+        return (None if d_zp is not None else gz), None, None
 
 
 def prior_sample(z_pre, eps):
-    return _PriorSample.apply(z_pre, eps)
+    """The returned z_pri carries the hand-off to a loss head on the one-sweep MMD route (``z_pri._gv_prior_link``)."""
+    if not MMD_FUSED:
+        return _PriorSample.apply(z_pre, eps)
+    box = [None]
+    out = _PriorSample.apply(z_pre, eps, box)
+    out._gv_prior_link = box[0]
+    return out
 
 
 class _LossHead(torch.autograd.Function):
@@ -3694,7 +3766,7 @@ class _LossHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, reg_w, kl_w, mmd_w, score_bias,
-                embed_rows=None, rows_dev=None, kl_link=None, grad_mode=True):
+                embed_rows=None, rows_dev=None, kl_link=None, grad_mode=True, prior_link=None):
         z, ld_z = _row_major(z, 'embed')
         if rows_dev is not None:          # static-shape batch: rows [*rows_dev, n) of z are padding (include/gcnvae.h, rows_dev)
             rows_dev = _chk(rows_dev.reshape(-1), torch.int32, 'rows_dev')
@@ -3731,6 +3803,16 @@ class _LossHead(torch.autograd.Function):
             wsm = torch.empty(z_pri.shape[0] + pick.numel(), **f32)
         if ld_z != h or ld_w != h:
             raise ValueError('loss_head needs contiguous embeddings and relation table')
+        # (grad_mode: the caller's torch.is_grad_enabled() -- inside forward it is always off)
+        dm_fused = grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and distmult_fused_ok(z, ld_z, w_rel, ld_w)
+        # the MMD sweep rides in the fused DistMult launch when the sampler that made z_pri left its hand-off (its backward is
+        # then this node's finishing launch) and the shapes fit
+        plink = prior_link if (mmd_w > 0 and dm_fused and prior_link is not None and not prior_link.claimed
+                               and prior_link.matches(z_pri) and mmd_sweep_ok(z_pri, z)
+                               and z_pri.shape[0] + pick.numel() <= 1024) else None
+        if plink is not None:
+            plink.claimed = True
+        ctx.prior_link = plink
         st = lib.stream()
         # every term leaves its per-block partial sums in its workspace; ONE combine launch finishes the four sums
         if link is not None:
@@ -3738,7 +3820,7 @@ class _LossHead(torch.autograd.Function):
         elif kl_w > 0:
             lib.call('gv_kl_fwd', ptr(z), ptr(z_mean), h, ptr(z_sigma), ptr(z_pre), ptr(flp), ptr(resp), None, ptr(wsk),
                      n, h, k, ptr(rows_dev), st)
-        if mmd_w > 0:      # the posterior sample set is rows `pick` of z, read in place
+        if mmd_w > 0 and plink is None:      # the posterior sample set is rows `pick` of z, read in place
             lib.call('gv_mmd_fwd', ptr(z_pri), ptr(z), ptr(pick), z_pri.shape[0], pick.numel(), h, None, ptr(wsm), st)
         # embed_rows: the regulariser's mean runs over that many rows (the rest of z are all-zero padding rows of the
         # multi-GPU row partition)
@@ -3751,10 +3833,12 @@ class _LossHead(torch.autograd.Function):
                      ptr(ws2), ptr(rows_dev), n, st)
         # DistMult scorer + BCE (three 800-B row gathers per triplet: the bandwidth-bound part)
         # (with a backward to come and a width the fused sweep covers: in by-relation order, the relation gradient's sums with it)
-        ctx.fused = None
-        # (grad_mode: the caller's torch.is_grad_enabled() -- inside forward it is always off)
-        if grad_mode and (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and distmult_fused_ok(z, ld_z, w_rel, ld_w):
-            ctx.fused = _distmult_fused_fwd(z, ld_z, w_rel, ld_w, labels, bias, tidx, score, ws)
+        ctx.fused = ctx.mmd_u = None
+        if dm_fused:
+            if plink is not None:      # value partials and the gradient rows at upstream 1, for the backward's finishing launch
+                ctx.mmd_u = (torch.empty_like(z_pri), torch.empty(pick.numel(), h, **f32))
+            ctx.fused = _distmult_fused_fwd(z, ld_z, w_rel, ld_w, labels, bias, tidx, score, ws,
+                                            None if plink is None else (z_pri, z, pick, wsm) + ctx.mmd_u)
             ctx.ws = ws
         else:
             lib.call('gv_distmult_bce_fwd', ptr(z), ld_z, ptr(w_rel), ld_w, ptr(tidx.trip32), ptr(tidx.fwd_order), ptr(labels),
@@ -3783,7 +3867,7 @@ class _LossHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gp, _gk, _gm):
         if g is None:
-            return (None,) * 18
+            return (None,) * 19
         z, z_mean, z_sigma, w_rel, z_pre, resp, z_pri, z_post, pick, labels, score, wsk, rows_dev = ctx.saved_tensors
         z_count = ctx.z_count
         tidx, reg_w, kl_w, mmd_w, has_bias, flp_in_kl = ctx.meta
@@ -3808,13 +3892,30 @@ class _LossHead(torch.autograd.Function):
             d_zp = _direct_flat(z_pre)
             gm, gv = torch.empty_like(z), torch.empty_like(z)
             gzp = d_zp if d_zp is not None else torch.empty_like(z_pre)
+        plink, gzs, d_zs = ctx.prior_link, None, None
         if mmd_w > 0:
             g_pri = torch.empty_like(z_pri)
+        if plink is not None:      # the sampler's z_pre gradient is produced by the finishing launch
+            d_zs = _direct_flat(plink.z_pre)
+            gzs = d_zs if d_zs is not None else torch.empty_like(plink.z_pre)
         _verify_direct(ctx)
         d_w = ctx.direct_w
         g_w = d_w if d_w is not None else torch.empty_like(w_rel)
         g_flp = torch.empty((), **f32) if (has_bias or flp_in_kl) else None
         st = lib.stream()
+
+        def mmd_backward(target, stream):
+            """The MMD rows ADDED into rows `pick` of ``target``, z_pri's gradient into g_pri (and, on the one-sweep route, the
+            sampler's z_pre gradient)."""
+            if plink is None:
+                lib.call('gv_mmd_bwd', ptr(z_pri), ptr(z), ptr(pick), z_pri.shape[0], pick.numel(), h, ptr(g), mmd_w,
+                         ptr(g_pri), ptr(target), stream)
+                return
+            gx_u, gy_u = ctx.mmd_u
+            lib.call('gv_mmd_grad_finish', ptr(gx_u), ptr(gy_u), ptr(pick), z_pri.shape[0], pick.numel(), h, ptr(g), mmd_w,
+                     ptr(target), ptr(g_pri), ptr(plink.z_pre), ptr(plink.eps), ptr(gzs), 1 if d_zs is not None else 0,
+                     plink.z_pre.shape[0] // 2, stream)
+            plink.record(g_pri, None if d_zs is not None else gzs)
         # branch 1: KL backward (writes gz, gm, gv, gzp), then the regulariser folded into gz
         with fork(1):
             s1 = lib.stream()
@@ -3828,8 +3929,7 @@ class _LossHead(torch.autograd.Function):
             else:
                 lib.call('gv_axpby', z.numel(), ptr(g), 2.0 * reg_w / z_count, ptr(z), 0.0, ptr(gz), s1)
             if mmd_w > 0 and link is None:      # MMD backward: prior rows -> g_pri, posterior rows ADDED into rows `pick` of gz (now complete)
-                lib.call('gv_mmd_bwd', ptr(z_pri), ptr(z), ptr(pick), z_pri.shape[0], pick.numel(), h, ptr(g), mmd_w,
-                         ptr(g_pri), ptr(gz), s1)
+                mmd_backward(gz, s1)
         # main: dL/dscore, then the relation-side gradient (does not need gz)
         if fused is not None:          # the forward summed the relation rows: scale them, add the regulariser, scale delta
             d_inc = _distmult_fused_finish(fused, g, tidx, w_rel, h, 2.0 * reg_w / w_rel.numel(), g_w, d_w is not None, ctx.ws,
@@ -3850,20 +3950,19 @@ class _LossHead(torch.autograd.Function):
         g_z = bdd_aggregate(indices.largest_first(tidx.inc) if indices.K1_ITEMS_LARGEST_FIRST else tidx.inc, tidx.inc_other, tidx.inc_rel,
                             d_inc, idx_inc, z, w_rel, h, 1, 1, addend=gz)
         if link is not None and mmd_w > 0:       # no KL buffer to ride on: the MMD rows are added to the decoder's gradient
-            lib.call('gv_mmd_bwd', ptr(z_pri), ptr(z), ptr(pick), z_pri.shape[0], pick.numel(), h, ptr(g), mmd_w,
-                     ptr(g_pri), ptr(g_z), st)
+            mmd_backward(g_z, st)
         if g_flp is not None:
             lib.call('gv_lincomb4', ptr(dbias) if has_bias else None, 1.0, ptr(g) if flp_in_kl else None, kl_w, None, 0.0,
                      None, 0.0, ptr(g_flp), st)
         return (g_z, gm, gv, (None if d_w is not None else g_w), (None if d_zp is not None else gzp), g_flp, g_pri, None,
-                None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None)
 
 
 def loss_head(z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, reg_w, kl_w, mmd_w, score_bias,
               embed_rows=None, rows_dev=None):
     return _LossHead.apply(z, z_mean, z_sigma, w_rel, z_pre, flp, z_pri, pick, labels, tidx, float(reg_w), float(kl_w),
                            float(mmd_w), bool(score_bias), embed_rows, rows_dev, getattr(z, '_gv_kl_link', None),
-                           torch.is_grad_enabled())
+                           torch.is_grad_enabled(), getattr(z_pri, '_gv_prior_link', None))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1244,6 +1244,30 @@ int gv_mmd_bwd(const float* x, const float* y, const int64_t* y_index, int sx, i
 int gv_prior_sample_fwd(const float* z_pre, const float* eps, float* out, int s, int k, int h, void* stream);
 int gv_prior_sample_bwd(const float* z_pre, const float* eps, const float* g, float* gz_pre, int accumulate, int s, int k,
                         int h, void* stream);
+/* The MMD value and both gradients in ONE sweep over the row pairs (the gradient is linear in the upstream scalar):
+ *   gv_mmd_fwd_grad    part [sx + sy] = gv_mmd_fwd's partial sums (another fixed summation order);  gx_u [sx][h], gy_u [sy][h] =
+ *                      what gv_mmd_bwd computes at gscale * *gmmd = 1, gy_u dense (row j belongs to row y_index[j] of y).
+ *                      h % 4 == 0, h <= 512, sx + sy <= 1024, x / y / gx_u / gy_u 16-B aligned; anything else fails with
+ *                      GV_ERR_SHAPE / GV_ERR_ALIGN and launches nothing (the caller decides beforehand: ops.mmd_sweep_ok).
+ *                      The library's own route is the combined launch below (h <= 256); this entry, and with it the widths in
+ *                      (256, 512] (eight float4 columns a lane, 150 registers), has no caller but tests/test_gpu_mmd_fused.py.
+ *   gv_distmult_bce_fwd_grad_mmd = gv_distmult_bce_fwd_grad with that sweep's sx + sy workgroups in front of its own, ONE launch
+ *                      (mmd_h <= 256); score, delta, u, partial and workspace are bit for bit gv_distmult_bce_fwd_grad's.
+ *   gv_mmd_grad_finish the backward's one launch behind either, gg = gscale * (gmmd ? *gmmd : 1):
+ *                      gy[y_index[j]] += gg * gy_u[j] (float atomics; without y_index gy[j] is overwritten);
+ *                      g_pri (optional, [sx][h]) = gg * gx_u;  gz_pre (+)= gv_prior_sample_bwd(z_pre, eps, g = gg * gx_u) with
+ *                      s = sx rows (sx % k == 0). */
+int gv_mmd_fwd_grad(const float* x, const float* y, const int64_t* y_index, int sx, int sy, int h, float* part, float* gx_u,
+                    float* gy_u, void* stream);
+int gv_distmult_bce_fwd_grad_mmd(const int32_t* items, int n_items, const int32_t* rel_s, const int32_t* rel_o,
+                                 const int32_t* rel_tid, const float* embed, int ld_e, const float* w_rel, int ld_w,
+                                 const float* labels, const float* bias, const int32_t* pos3, float* score, float* delta,
+                                 float* u, float* partial, float* workspace, int64_t t, int h, const float* mmd_x,
+                                 const float* mmd_y, const int64_t* mmd_y_index, int sx, int sy, int mmd_h, float* mmd_part,
+                                 float* gx_u, float* gy_u, void* stream);
+int gv_mmd_grad_finish(const float* gx_u, const float* gy_u, const int64_t* y_index, int sx, int sy, int h, const float* gmmd,
+                       float gscale, float* gy, float* g_pri, const float* z_pre, const float* eps, float* gz_pre,
+                       int accumulate, int k, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K4  IAF / MADE update step (kgvae/flow_network.py:93-96); the masked linears are gv_gemm_f32.
