@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "k_riders.h"
 
 namespace gv {
 
@@ -486,16 +487,7 @@ __global__ __launch_bounds__(256) void k_pack_weight(const float* w, float* pack
                                                      int adj, float* packed2, int bpl2, int adj2) {
     // blockIdx.y = 1: the second layout of the same weights (a layer's forward and backward-x launches pack differently)
     if (blockIdx.y == 1) { packed = packed2; bpl = bpl2; adj = adj2; }
-    const int L = nb / bpl, nq = bpl * pq / 4, quads = L * nq;     // float4 per relation row
-    const int total = num_rels * quads;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int r = i / quads, rem = i - r * quads;
-        const int l = rem % L, jq = rem / L;               // quad jq of lane l's weight list
-        const int f = 4 * jq, sb = f / pq, within = f - sb * pq;
-        const int block = adj ? l * bpl + sb : l + sb * L;
-        reinterpret_cast<float4*>(packed)[i] =
-            *reinterpret_cast<const float4*>(w + (size_t)r * nb * pq + (size_t)block * pq + within);
-    }
+    pack_weight_body(w, packed, num_rels, nb, pq, bpl, adj, blockIdx.x, gridDim.x);
 }
 
 // Any (P, Q): lane <-> output column, 64 columns per sweep over the item's edges.
@@ -1006,6 +998,15 @@ bool pack_plan(int nb, int p_gather, int q_out, bool trans, PackPlan* plan) {
     return true;
 }
 }  // namespace
+
+// (k_riders.h) the lane-packed layout of one launch kind, for a pack job that rides on another launch
+bool gv::pack_job_plan(int num_bases, int blk_in, int blk_out, bool transpose_w, int* bpl, int* adj) {
+    PackPlan pl;
+    if (!pack_plan(num_bases, blk_in, blk_out, transpose_w, &pl)) return false;
+    *bpl = pl.bpl;
+    *adj = pl.adj;
+    return true;
+}
 
 extern "C" int gv_rgcn_bdd_pack_supported(int num_bases, int blk_in, int blk_out, int transpose_w) {
     PackPlan pl;

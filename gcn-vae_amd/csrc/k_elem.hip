@@ -2,6 +2,7 @@
 // reparameterisation (K3), IAF update (K4 glue), clip+Adam (a-11).  All HBM/cache-bound
 // streaming kernels: 16-B per lane where the shape allows, grid-stride, <= 2048 blocks.
 #include "common.h"
+#include "k_riders.h"
 
 namespace gv {
 
@@ -102,9 +103,7 @@ __global__ __launch_bounds__(256) void k_scatter_add_rows(const float* gout, con
     }
 }
 
-__device__ __forceinline__ float softplus_t(float x) {  // torch: beta=1, threshold=20
-    return x > 20.f ? x : log1pf(expf(x));
-}
+// (softplus_t -- torch: beta=1, threshold=20 -- is k_riders.h's)
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ __launch_bounds__(256) void k_reparam_fwd(const float* h2, const float* eps, float* z, float* v, float* mout,
@@ -304,65 +303,9 @@ __global__ __launch_bounds__(256) void k_reverse_cols(const float* x, float* out
     }
 }
 
-// ---- counter-based RNG: every random draw of one forward pass in ONE launch ---------------------------------
-// Philox4x32-10 (Salmon et al., SC'11): key = the 64-bit seed, counter = (group, stream, tick_lo, tick_hi); one call
-// yields the 4 outputs of elements 4*group .. 4*group+3 of a job.  `tick` is a device-side step counter (state[1]),
-// so a captured hipGraph draws fresh numbers on every replay; `stream` separates the jobs of one tick.
-//   kind 0: keep mask, byte = (u32 >= floor(p_drop * 2^32))            (nn.Dropout's Bernoulli(1-p) decision)
-//   kind 1: standard normals by Box-Muller, (u1, u2) = ((x0 + 1) * 2^-32, x1 * 2^-32)  (torch.randn_like)
-struct RngJobs {
-    void* ptr[GV_RNG_MAX_JOBS];
-    long long n[GV_RNG_MAX_JOBS];
-    long long group0[GV_RNG_MAX_JOBS + 1];     // prefix of ceil(n/4): job j owns global groups [group0[j], group0[j+1])
-    int kind[GV_RNG_MAX_JOBS];
-    uint32_t thresh[GV_RNG_MAX_JOBS];
-    uint32_t stream[GV_RNG_MAX_JOBS];
-    int n_jobs;
-};
-
+// ---- counter-based RNG: every random draw of one forward pass in ONE launch (the generator and its jobs: k_riders.h) ----
 __global__ __launch_bounds__(256) void k_rng_fill(const uint64_t* state, const RngJobs jobs) {
-    const uint64_t seed = state[0], tick = state[1];
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), t0 = (uint32_t)tick, t1 = (uint32_t)(tick >> 32);
-    const long long total = jobs.group0[jobs.n_jobs];
-    for (long long gg = (long long)blockIdx.x * 256 + threadIdx.x; gg < total; gg += (long long)gridDim.x * 256) {
-        int j = 0;
-#pragma unroll
-        for (int q = 1; q < GV_RNG_MAX_JOBS; ++q)
-            if (q < jobs.n_jobs && gg >= jobs.group0[q]) j = q;
-        const long long grp = gg - jobs.group0[j];
-        const uint4 x = philox4x32_10(k0, k1, (uint32_t)grp, jobs.stream[j], t0, t1);
-        const long long e0 = grp * 4, left = jobs.n[j] - e0;
-        if (jobs.kind[j] == 0) {
-            const uint32_t th = jobs.thresh[j];
-            uint8_t* o = (uint8_t*)jobs.ptr[j] + e0;
-            const uchar4 b = make_uchar4(x.x >= th, x.y >= th, x.z >= th, x.w >= th);
-            if (left >= 4) {
-                *reinterpret_cast<uchar4*>(o) = b;
-            } else {
-                o[0] = b.x;
-                if (left > 1) o[1] = b.y;
-                if (left > 2) o[2] = b.z;
-            }
-        } else {
-            // hardware transcendentals: v_log_f32 (base 2), v_sin/v_cos_f32 (argument in revolutions) -- ~1e-6 absolute
-            // on the result, far inside what noise needs; the precise libm sincosf tripled this kernel's time
-            const float s = 2.3283064365386963e-10f;       // 2^-32
-            const float r0 = sqrtf(-1.3862943611198906f * __log2f(((float)x.x + 1.f) * s));    // -2 ln u = -2 ln2 log2 u
-            const float r1 = sqrtf(-1.3862943611198906f * __log2f(((float)x.z + 1.f) * s));
-            const float a0 = (float)x.y * s, a1 = (float)x.w * s;                                 // revolutions in [0, 1]
-            const float s0 = __builtin_amdgcn_sinf(a0), c0 = __builtin_amdgcn_cosf(a0);
-            const float s1 = __builtin_amdgcn_sinf(a1), c1 = __builtin_amdgcn_cosf(a1);
-            const float4 nrm = make_float4(r0 * c0, r0 * s0, r1 * c1, r1 * s1);
-            float* o = (float*)jobs.ptr[j] + e0;
-            if (left >= 4) {
-                *reinterpret_cast<float4*>(o) = nrm;
-            } else {
-                o[0] = nrm.x;
-                if (left > 1) o[1] = nrm.y;
-                if (left > 2) o[2] = nrm.z;
-            }
-        }
-    }
+    rng_fill_body(state, jobs, blockIdx.x, gridDim.x);
 }
 
 __global__ void k_rng_tick(uint64_t* state) {

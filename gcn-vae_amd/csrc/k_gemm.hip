@@ -13,11 +13,13 @@
 // split-K (grid.z) writes raw partial tiles to a workspace that a second kernel sums in order.
 #include <limits.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
 
 #include "common.h"
+#include "k_riders.h"
 #include "k_mc.h"
 #include "k_query_args.h"
 #include "k_topk.h"
@@ -141,20 +143,22 @@ __device__ __forceinline__ void stage_b(float* Bs, const float (&r)[BN * BK / 25
     }
 }
 
-// MT / NT = 32-row / 32-column MFMA tiles per wave: block tile (64*MT) x (64*NT) x BK, four waves as 2 (M) x 2 (N).
+// The workgroup's body: (bx, by, bz) = its tile coordinates in dispatch order (x fastest), (ntn, ntm) = the product's OWN tile counts
+// along n and m -- not the launch's grid, which may hold workgroups that are no tiles (k_gemm_f32_riders).
 template <bool TA, bool TB, int MT, int NT, int BK>
-__global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
+__device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bx, const int by, const int bz, const int ntn,
+                                              const int ntm) {
     constexpr int BM = 64 * MT, BN = 64 * NT, LDA_S = BM + 1, LDB_S = BN + 1;
     __shared__ float As[BK * LDA_S];
     __shared__ float Bs[BK * LDB_S];
     // Workgroups are dealt round-robin to the 8 XCDs.  The n-tiles of one m-tile share the A rows: give them CONSECUTIVE slots of
     // the SAME XCD, so that a tall A (configs[4]: 800 MB, far beyond the Infinity Cache) crosses the fabric once instead of once
     // per n-tile.  (Whole groups of 8 m-tiles only; the ragged end keeps the plain order.)
-    int mt_i = blockIdx.y, nt_i = blockIdx.x;
+    int mt_i = by, nt_i = bx;
     if (p.tmask_wanted > 0) {
         // the x-th wanted 64 x 64 tile (MT = NT = 1): no block exists for the others -- with one block per tile, wanted or not, the CUs
         // that were dealt 4 wanted blocks set the launch's time whatever the others hold (2-4 per CU under a triangular mask)
-        int rank = blockIdx.x, bit = -1;
+        int rank = bx, bit = -1;
         for (int w = 0; bit < 0; ++w) {
             unsigned long long word = p.tmask[w];
             const int pc = __popcll(word);
@@ -165,8 +169,8 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
         mt_i = bit / p.tmask_ld;
         nt_i = bit - mt_i * p.tmask_ld;
     } else {
-        const int ntn = gridDim.x, lin = blockIdx.y * ntn + blockIdx.x;
-        const int full = (gridDim.y / 8) * 8 * ntn;
+        const int lin = by * ntn + bx;
+        const int full = (ntm / 8) * 8 * ntn;
         if (lin < full) {
             const int xcd = lin & 7, j = lin >> 3;
             // (rotated by the m-tile group: an XCD deals its slots to its 32 CUs in turn, so with 8 column tiles a CU would receive the
@@ -178,14 +182,14 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
             // tiles, and a CU -- dealt every 32nd slot of its XCD -- the SAME tile of every k-split.  Tiles with (row + column) % 8 = x
             // go to XCD x (4-5 wanted ones each under a triangular mask), the column rotated with the split so that a CU's blocks differ
             if (p.tmask) {
-                const int z = blockIdx.z;
+                const int z = bz;
                 nt_i = (nt_i + z + (z >> 2)) % ntn;
                 mt_i = (j / ntn) * 8 + ((xcd - nt_i) & 7);
             }
         }
     }
     const int m0 = mt_i * BM, n0 = nt_i * BN;
-    const int kbeg = blockIdx.z * p.k_chunk;
+    const int kbeg = bz * p.k_chunk;
     int kend = min(p.k, kbeg + p.k_chunk);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int wm = (wid >> 1) * 32 * MT, wn = (wid & 1) * 32 * NT;
@@ -317,11 +321,37 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                 if (row >= p.m) continue;
-                if (p.split_k > 1) p.ws[((size_t)blockIdx.z * p.m + row) * p.n + col] = val[r];
+                if (p.split_k > 1) p.ws[((size_t)bz * p.m + row) * p.n + col] = val[r];
                 else p.c[(size_t)row * p.ldc + col] = val[r];
             }
         }
     }
+}
+
+// MT / NT = 32-row / 32-column MFMA tiles per wave: block tile (64*MT) x (64*NT) x BK, four waves as 2 (M) x 2 (N).
+template <bool TA, bool TB, int MT, int NT, int BK>
+__global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
+    gemm_f32_body<TA, TB, MT, NT, BK>(p, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+}
+
+// The same product with RIDERS (k_riders.h): a 1-D launch of ntn * ntm tile workgroups, in the plain kernel's dispatch order, and
+// n_riders workgroups that run independent small jobs on the VALUs and the memory system the product leaves free.  The branch is
+// block-uniform.  riders_front: the rider workgroups are dispatched first (n_riders is then a multiple of 8, so that every tile
+// workgroup keeps the XCD it has in the plain launch); otherwise they follow the tiles.  No split-K, no k-chunk / tile words.
+template <bool TA, bool TB, int MT, int NT, int BK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 5 : 7))) void k_gemm_f32_riders(const GemmParams p, const RiderSet rs, const int ntn, const int ntm,
+                                                         const int n_riders, const int riders_front) {
+    const int tiles = ntn * ntm;
+    int b = blockIdx.x;
+    if (riders_front) {
+        if (b < n_riders) { rider_body(rs, b, n_riders); return; }
+        b -= n_riders;
+    } else if (b >= tiles) {
+        rider_body(rs, b - tiles, n_riders);
+        return;
+    }
+    const int by = b / ntn;
+    gemm_f32_body<TA, TB, MT, NT, BK>(p, b - by * ntn, by, 0, ntn, ntm);
 }
 
 // ---- the 64 x 64 score tile of the entity queries: acc = Q[m0 .., :] @ E[n0 .., :]^T -------------------------------------------
@@ -1524,6 +1554,139 @@ extern "C" int gv_gemm_f32(int trans_a, int trans_b, int m, int n, int k, const 
                            const float* a_relu_mask, void* workspace, int64_t workspace_bytes, void* stream) {
     return gemm_any(false, trans_a, trans_b, m, n, k, a, lda, b, ldb, c, ldc, bias, act, accumulate, split_k, a_relu_mask,
                     workspace, workspace_bytes, stream);
+}
+
+// ---- the product with riders (k_riders.h) ----------------------------------------------------------------------------------------
+namespace {
+struct Extent { const char* lo; const char* hi; };      // [lo, hi) in bytes; lo == NULL: nothing
+inline Extent extent_of(const void* p, int64_t bytes) {
+    return p && bytes > 0 ? Extent{(const char*)p, (const char*)p + bytes} : Extent{nullptr, nullptr};
+}
+inline bool overlaps(const Extent& a, const Extent& b) { return a.lo && b.lo && a.lo < b.hi && b.lo < a.hi; }
+inline int64_t matrix_bytes(int rows, int cols, int ld) { return rows > 0 && cols > 0 ? ((int64_t)(rows - 1) * ld + cols) * 4 : 0; }
+}  // namespace
+
+extern "C" int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
+                                  float* c, int ldc, const float* bias, int act, int accumulate, int split_k,
+                                  const float* a_relu_mask, void* workspace, int64_t workspace_bytes, const gv_riders* riders,
+                                  void* stream) {
+    const bool any = riders && (riders->rng_jobs > 0 || riders->pack_weight || riders->mix_z_pre);
+    if (!any)       // no riders: the plain kernel, exactly as gv_gemm_f32 launches it
+        return gemm_any(false, trans_a, trans_b, m, n, k, a, lda, b, ldb, c, ldc, bias, act, accumulate, split_k, a_relu_mask,
+                        workspace, workspace_bytes, stream);
+    GV_REQUIRE(split_k <= 1, GV_ERR_SHAPE, "gv_gemm_f32_riders: riders do not ride on a split-K product (split_k=%d)", split_k);
+    GV_REQUIRE(!trans_a && !trans_b, GV_ERR_SHAPE, "gv_gemm_f32_riders: riders ride on A @ B only (the forward self-loop product)");
+    GV_REQUIRE(m > 0 && n > 0 && k >= 0, GV_ERR_SHAPE, "gv_gemm_f32_riders: m=%d n=%d k=%d", m, n, k);
+    GV_REQUIRE(c && (k == 0 || (a && b)), GV_ERR_NULL, "gv_gemm_f32_riders: NULL matrix");
+    GV_REQUIRE(lda >= k && ldb >= n && ldc >= n, GV_ERR_SHAPE, "gv_gemm_f32_riders: leading dimension too small (lda=%d ldb=%d ldc=%d)",
+               lda, ldb, ldc);
+    GV_REQUIRE(act == GV_ACT_NONE || act == GV_ACT_RELU, GV_ERR_SHAPE, "gv_gemm_f32_riders: unknown act %d", act);
+    GemmParams p;
+    p.a = a; p.b = b; p.c = c; p.bias = bias; p.a_mask = a_relu_mask; p.ws = nullptr;
+    p.m = m; p.n = n; p.k = k; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.act = act; p.accumulate = accumulate;
+    p.k_chunk = k_chunk_for(k > 0 ? k : 1, 1);
+    p.split_k = 1;
+    p.vec_a = aligned16(a) && (lda % 4 == 0) && (!a_relu_mask || aligned16(a_relu_mask));
+    p.vec_b = aligned16(b) && (ldb % 4 == 0);
+    p.rows_dev = nullptr; p.kmask = nullptr; p.tmask = nullptr; p.tmask_ld = (n + 63) / 64; p.tmask_wanted = 0;
+    // the tile rule of gv_gemm_f32 for A @ B: 64-column tiles, 16-deep steps, 128-row tiles once they still give every CU >= 4 blocks
+    const int ntn = (n + 63) / 64;
+    const int mt = (long)ntn * ((m + 127) / 128) >= 1024 ? 2 : 1;
+    const int ntm = (m + 64 * mt - 1) / (64 * mt);
+    GV_REQUIRE((int64_t)ntn * ntm < (1ll << 30), GV_ERR_SHAPE, "gv_gemm_f32_riders: %d x %d tiles", ntn, ntm);
+
+    // what the product reads and writes, against what the riders read and write
+    const Extent ea = extent_of(a, matrix_bytes(m, k, lda)), eb = extent_of(b, matrix_bytes(k, n, ldb)),
+                 ec = extent_of(c, matrix_bytes(m, n, ldc)), ebias = extent_of(bias, (int64_t)n * 4),
+                 emask = extent_of(a_relu_mask, matrix_bytes(m, k, lda));
+    auto written_ok = [&](const Extent& w) { return !(overlaps(w, ea) || overlaps(w, eb) || overlaps(w, ec) || overlaps(w, ebias) || overlaps(w, emask)); };
+    auto read_ok = [&](const Extent& r) { return !overlaps(r, ec); };
+
+    RiderSet rs;
+    memset(&rs, 0, sizeof(rs));
+    // the measured defaults: see NOTES.md ("Riders on the forward self-loop products")
+    static const int per_thread = getenv("GV_RIDER_GROUPS") ? std::max(1, atoi(getenv("GV_RIDER_GROUPS"))) : 8;
+    static const int front = getenv("GV_RIDERS_FRONT") ? atoi(getenv("GV_RIDERS_FRONT")) : 1;
+    int nblk = 0;
+    rs.first[0] = 0;
+    if (riders->rng_jobs > 0) {
+        GV_REQUIRE(riders->rng_state, GV_ERR_NULL, "gv_gemm_f32_riders: NULL rng_state");
+        GV_REQUIRE(riders->rng_jobs <= GV_RNG_MAX_JOBS, GV_ERR_SHAPE, "gv_gemm_f32_riders: rng_jobs=%d (1..%d)", riders->rng_jobs,
+                   GV_RNG_MAX_JOBS);
+        GV_REQUIRE(read_ok(extent_of(riders->rng_state, 16)), GV_ERR_SHAPE, "gv_gemm_f32_riders: rng_state overlaps C");
+        rs.rng_state = riders->rng_state;
+        long long g = 0;
+        for (int j = 0; j < GV_RNG_MAX_JOBS; ++j) {
+            rs.rng.group0[j] = g;
+            if (j >= riders->rng_jobs) continue;
+            void* ptr = riders->rng_ptr[j];
+            const int64_t cnt = riders->rng_count[j];
+            const int kind = riders->rng_kind[j];
+            const float dp = riders->rng_drop_p[j];
+            GV_REQUIRE(ptr && cnt > 0 && cnt < (1ll << 34), GV_ERR_SHAPE, "gv_gemm_f32_riders: rng job %d: bad buffer/count", j);
+            GV_REQUIRE(kind == GV_RNG_KEEP_MASK || kind == GV_RNG_NORMAL, GV_ERR_SHAPE, "gv_gemm_f32_riders: rng job %d: kind %d", j, kind);
+            GV_REQUIRE((reinterpret_cast<uintptr_t>(ptr) & (kind == GV_RNG_NORMAL ? 15u : 3u)) == 0, GV_ERR_ALIGN,
+                       "gv_gemm_f32_riders: rng job %d: buffer alignment", j);
+            GV_REQUIRE(kind == GV_RNG_NORMAL || (dp >= 0.f && dp < 1.f), GV_ERR_SHAPE, "gv_gemm_f32_riders: rng job %d: p=%f", j, dp);
+            GV_REQUIRE(written_ok(extent_of(ptr, cnt * (kind == GV_RNG_NORMAL ? 4 : 1))), GV_ERR_SHAPE,
+                       "gv_gemm_f32_riders: rng job %d writes into an operand of the product", j);
+            rs.rng.ptr[j] = ptr; rs.rng.n[j] = cnt; rs.rng.kind[j] = kind; rs.rng.stream[j] = riders->rng_stream[j];
+            const double th = (double)dp * 4294967296.0;          // as gv_rng_fill
+            rs.rng.thresh[j] = th >= 4294967295.0 ? 4294967295u : (uint32_t)th;
+            g += (cnt + 3) / 4;
+        }
+        rs.rng.group0[GV_RNG_MAX_JOBS] = g;
+        for (int j = riders->rng_jobs; j <= GV_RNG_MAX_JOBS; ++j) rs.rng.group0[j] = g;
+        rs.rng.n_jobs = riders->rng_jobs;
+        const long long want = (g + 256ll * per_thread - 1) / (256ll * per_thread);
+        nblk += (int)std::min<long long>(std::max<long long>(want, 1), 1 << 16);
+    }
+    rs.first[1] = nblk;
+    if (riders->pack_weight) {
+        const int nb = riders->pack_bases, bi = riders->pack_blk_in, bo = riders->pack_blk_out, r = riders->pack_rels;
+        GV_REQUIRE(riders->packed, GV_ERR_NULL, "gv_gemm_f32_riders: NULL packed");
+        GV_REQUIRE(r > 0 && nb > 0 && bi > 0 && bo > 0 && (int64_t)r * nb * bi * bo < (1ll << 31), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders: pack shape R=%d nb=%d %dx%d", r, nb, bi, bo);
+        GV_REQUIRE(!riders->packed_pair || !riders->pack_transpose, GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders: the pair is (blk_in, blk_out, transpose 0) + its backward-x layout");
+        PackJob& pj = rs.pack;
+        GV_REQUIRE(pack_job_plan(nb, bi, bo, riders->pack_transpose != 0, &pj.bpl, &pj.adj) &&
+                       (!riders->packed_pair || pack_job_plan(nb, bo, bi, true, &pj.bpl2, &pj.adj2)),
+                   GV_ERR_SHAPE, "gv_gemm_f32_riders: no lane-packed kernel for num_bases=%d blocks %dx%d trans=%d", nb, bi, bo,
+                   riders->pack_transpose);
+        GV_REQUIRE(aligned16(riders->pack_weight) && aligned16(riders->packed) && aligned16(riders->packed_pair), GV_ERR_ALIGN,
+                   "gv_gemm_f32_riders: pack buffers need 16-B alignment");
+        const int64_t wbytes = (int64_t)r * nb * bi * bo * 4;
+        const Extent ew = extent_of(riders->pack_weight, wbytes), e1 = extent_of(riders->packed, wbytes),
+                     e2 = extent_of(riders->packed_pair, wbytes);
+        GV_REQUIRE(read_ok(ew) && written_ok(e1) && written_ok(e2) && !overlaps(ew, e1) && !overlaps(ew, e2) && !overlaps(e1, e2),
+                   GV_ERR_SHAPE, "gv_gemm_f32_riders: a pack buffer overlaps an operand of the product or another pack buffer");
+        pj.w = riders->pack_weight; pj.packed = riders->packed; pj.packed2 = riders->packed_pair;
+        pj.num_rels = r; pj.nb = nb; pj.pq = bi * bo;
+        const int total = r * nb * bi * bo / 4;
+        pj.blocks = std::min(2048, (total + 255) / 256);
+        nblk += pj.blocks * (riders->packed_pair ? 2 : 1);
+    }
+    rs.first[2] = nblk;
+    if (riders->mix_z_pre) {
+        const int mk = riders->mix_k, mh = riders->mix_h;
+        GV_REQUIRE(riders->mix, GV_ERR_NULL, "gv_gemm_f32_riders: NULL mix");
+        GV_REQUIRE(mk > 0 && mh > 0 && (int64_t)mk * mh < (1ll << 28), GV_ERR_SHAPE, "gv_gemm_f32_riders: mix k=%d h=%d", mk, mh);
+        const Extent ez = extent_of(riders->mix_z_pre, (int64_t)2 * mk * mh * 4), em = extent_of(riders->mix, (int64_t)3 * mk * mh * 4);
+        GV_REQUIRE(read_ok(ez) && written_ok(em) && !overlaps(ez, em), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders: a mix buffer overlaps an operand of the product or z_pre");
+        rs.mix.z_pre = riders->mix_z_pre; rs.mix.mix = riders->mix; rs.mix.k = mk; rs.mix.h = mh;
+        nblk += (mk * mh + 255) / 256;
+    }
+    rs.first[3] = nblk;
+    // riders in front: pad their count to a multiple of 8, so that tile workgroup i keeps XCD i % 8 (the padding blocks leave at once)
+    const int n_riders = front ? (nblk + 7) / 8 * 8 : nblk;
+    const dim3 grid((unsigned)(ntn * ntm + n_riders)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (mt == 2) hipLaunchKernelGGL((k_gemm_f32_riders<false, false, 2, 1, 16>), grid, block, 0, st, p, rs, ntn, ntm, n_riders, front ? 1 : 0);
+    else hipLaunchKernelGGL((k_gemm_f32_riders<false, false, 1, 1, 16>), grid, block, 0, st, p, rs, ntn, ntm, n_riders, front ? 1 : 0);
+    return launch_status("gv_gemm_f32_riders");
 }
 
 extern "C" int gv_gemm_f32_live_rows(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b,

@@ -2,6 +2,7 @@
 // All scalar results are produced by an ordered two-pass reduction (per-block partials, then one
 // block sums them in index order) -> bitwise reproducible, no float atomics.
 #include "common.h"
+#include "k_riders.h"
 
 namespace gv {
 
@@ -225,18 +226,9 @@ __global__ __launch_bounds__(256) void k_sumsq_part(const float* x, int64_t n, f
 
 // ---- KL -----------------------------------------------------------------------------------------
 // workspace layout (floats): mix[3][k*h] (mu_j, 1/(2 v_j), log sqrt v_j + log sqrt 2pi) | terms[n] | part[...]
-constexpr float LOG_SQRT_2PI = 0.9189385332046727f;
-
-__device__ __forceinline__ float softplus_t(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-
+// (LOG_SQRT_2PI, softplus_t and the table's body kl_mix_body: k_riders.h)
 __global__ __launch_bounds__(256) void k_kl_mix(const float* z_pre, int k, int h, float* mix) {
-    const int total = k * h;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const float v = softplus_t(z_pre[total + i]) + 1e-8f;
-        mix[i] = z_pre[i];
-        mix[total + i] = 1.f / (2.f * v);
-        mix[2 * total + i] = logf(sqrtf(v)) + LOG_SQRT_2PI;
-    }
+    kl_mix_body(z_pre, k, h, mix, blockIdx.x, gridDim.x);
 }
 
 constexpr int KL_KMAX = 64;   // mixture components (lane j keeps component j's log-density)
@@ -1897,12 +1889,20 @@ extern "C" int gv_kl_bwd(const float* z, const float* m, int ld_m, const float* 
     return launch_status("gv_kl_bwd");
 }
 
+// the mixture table alone (what gv_kl_fwd / gv_reparam_kl_fwd launch first): mix = the first 3 k h floats of a KL workspace
+extern "C" int gv_kl_mix(const float* z_pre, int k, int h, float* mix, void* stream) {
+    GV_REQUIRE(z_pre && mix, GV_ERR_NULL, "gv_kl_mix: NULL pointer");
+    GV_REQUIRE(h > 0 && k > 0 && k <= KL_KMAX && (int64_t)k * h < (1ll << 28), GV_ERR_SHAPE, "gv_kl_mix: h=%d k=%d", h, k);
+    hipLaunchKernelGGL(k_kl_mix, dim3((k * h + 255) / 256), dim3(256), 0, GV_ST, z_pre, k, h, mix);
+    return launch_status("gv_kl_mix");
+}
+
 // K3 fused into K6 (the reparameterisation and the KL term read the same node rows):
 //   fwd: (m, v, z) = reparameterise(h2, eps) AND the KL forward pass over them (resp, per-block partial sums) in one sweep;
 //   bwd: KL's node gradients, the regulariser's z_extra * z and the upstream dL/dz are chained through the reparameterisation
 //        in registers: gh2 is the only node-sized output (gz / gm / gv of gv_kl_bwd are never materialised).
-extern "C" int gv_reparam_kl_fwd(const float* h2, const float* eps, const float* z_pre, float* z, float* v, float* m_out,
-                                 float* resp, float* workspace, int64_t n, int h, int k, void* stream) {
+extern "C" int gv_reparam_kl_fwd_mix(const float* h2, const float* eps, const float* z_pre, float* z, float* v, float* m_out,
+                                     float* resp, float* workspace, int mix_ready, int64_t n, int h, int k, void* stream) {
     GV_REQUIRE(h2 && eps && z_pre && z && v && resp && workspace, GV_ERR_NULL, "gv_reparam_kl_fwd: NULL pointer");
     GV_REQUIRE(n > 0 && h > 0 && h <= 1024 && k > 0 && k <= KL_KMAX, GV_ERR_SHAPE, "gv_reparam_kl_fwd: n=%lld h=%d k=%d", (long long)n,
                h, k);
@@ -1911,7 +1911,8 @@ extern "C" int gv_reparam_kl_fwd(const float* h2, const float* eps, const float*
     float* mix = workspace;
     float* part = workspace + 3 * (size_t)k * h;
     float* zsq_part = workspace + kl_zsq_offset(h, k);      // sum z^2 per block, for gv_loss_combine_fold
-    hipLaunchKernelGGL(k_kl_mix, dim3((k * h + 255) / 256), dim3(256), 0, GV_ST, z_pre, k, h, mix);
+    // mix_ready: the table at the head of `workspace` was already made from this z_pre (gv_kl_mix, or a rider of gv_gemm_f32_riders)
+    if (!mix_ready) hipLaunchKernelGGL(k_kl_mix, dim3((k * h + 255) / 256), dim3(256), 0, GV_ST, z_pre, k, h, mix);
     const int nb = kl_blocks(n);
     const float* none = nullptr;
     const int* no_rows = nullptr;
@@ -1926,6 +1927,11 @@ extern "C" int gv_reparam_kl_fwd(const float* h2, const float* eps, const float*
     else GV_RKL_FWD(16);
 #undef GV_RKL_FWD
     return launch_status("gv_reparam_kl_fwd");
+}
+
+extern "C" int gv_reparam_kl_fwd(const float* h2, const float* eps, const float* z_pre, float* z, float* v, float* m_out,
+                                 float* resp, float* workspace, int64_t n, int h, int k, void* stream) {
+    return gv_reparam_kl_fwd_mix(h2, eps, z_pre, z, v, m_out, resp, workspace, 0, n, h, k, stream);
 }
 
 extern "C" int gv_reparam_kl_bwd(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,

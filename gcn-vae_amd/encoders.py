@@ -125,9 +125,11 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         num_sample = 200
         return (num_sample // self.k) * self.k if num_sample // self.k > 1 else self.k
 
-    def _draw_noise(self, n, device):
+    def _draw_noise(self, n, device, riders=None):
         """All random draws of one forward pass in ONE launch: both layers' dropout masks, the reparameterisation
-        noise and (when the head announced get_mmd) the prior noise.  Overrides (parity mode) are left alone."""
+        noise and (when the head announced get_mmd) the prior noise.  Overrides (parity mode) are left alone.
+        ``riders`` (ops.RiderBox): the launch is left to the box -- layer 1's self-loop product carries it; the generator's
+        host-side bookkeeping (seed, streams used in this tick) is done here, where the launch used to be."""
         jobs, eps = [], self.eps_override
         for layer in (self.rconv_layer_1, self.rconv_layer_2):
             if layer.wants_keep_mask():
@@ -139,7 +141,11 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         if self.batch_mmd_prior_with_forward and self.training and self.mmd_eps_override is None:
             self._prior_eps_next = torch.empty(self._prior_rows(), self.h_dim, dtype=torch.float32, device=device)
             jobs.append((self._prior_eps_next, ops.RNG_NORMAL, 0.0, self.rng_stream_prior))
-        if jobs:
+        if jobs and riders is not None:
+            rng = ops.device_rng(device)
+            rng.claim(jobs)
+            riders.rng = (rng, jobs)
+        elif jobs:
             ops.device_rng(device).fill(jobs)
         return eps
 
@@ -239,17 +245,30 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         if self.n_flows > 0:      # the flows' parameter-only work (mask folds, packed weights, pass 0's row) beside the encoder's layers
             ops.made_prepare([f.call_arguments() for f in self.nf if isinstance(f, MADE)])
         h = self.input_layer(g, h, r, norm)
-        eps = self._draw_noise(h.shape[0], h.device)
-        h = self.rconv_layer_1(g, h, r, norm)
+        # the forward's random draws ride on layer 1's self-loop product; layer 2's weight packing (left in the box by the layer)
+        # and the KL mixture table on layer 2's (ops.RiderBox: each layer call launches its box, as riders or stand-alone)
+        # (a static-shape mini-batch step counts live rows in its products: no combined form there, the launches stay where they were)
+        ride = ops.LIVE_ROWS is None
+        box1, box2 = self._rider_boxes = (ops.RiderBox(), ops.RiderBox()) if ride else (None, None)      # (kept for inspection)
+        eps = self._draw_noise(h.shape[0], h.device, box1)
+        h = self.rconv_layer_1(g, h, r, norm, riders=box1)
+        if box1 is not None and not box1.done:
+            raise RuntimeError('KGVAE.forward: layer 1 dropped its RiderBox (the random draws were never launched)')
         if self.grad_reducer is not None:     # layer 2 onwards is final once dL/dh1 exists: its arena suffix reduces under layer 1's backward
             h = self.grad_reducer.milestone(h, next(self.rconv_layer_2.parameters()))
         # no flow between z and the KL term: the KL forward pass rides on the reparameterisation's sweep over the rows, and
         # its backward is chained through the reparameterisation's (ops.reparam); with flows the two stay separate.  h2 has
         # exactly one consumer here, so layer 2's epilogue gradient may ride on that backward too (ops.EpilogueLink)
         fuse_kl = self.training and self.n_flows == 0 and self.fuse_kl_with_reparam
-        h = self.rconv_layer_2(g, h, r, norm, sole_consumer=fuse_kl)
+        kl_ws = None
+        if box2 is not None and fuse_kl and ops.FUSE_REPARAM_KL:      # the KL workspace ahead of layer 2: its mixture table depends on z_pre alone
+            kl_ws = ops.KLWorkspace(self.z_pre.squeeze(0), h.shape[0])
+            box2.mix = (kl_ws.z_pre, kl_ws.ws)
+        h = self.rconv_layer_2(g, h, r, norm, sole_consumer=fuse_kl, riders=box2)
+        if box2 is not None and not box2.done:
+            raise RuntimeError('KGVAE.forward: layer 2 dropped its RiderBox (weight packing / KL mixture table never launched)')
         z, self.z_mean, self.z_sigma = ops.reparam(h, eps, self.z_pre.squeeze(0) if fuse_kl else None,
-                                                   getattr(h, '_gv_epi_link', None) if fuse_kl else None)
+                                                   getattr(h, '_gv_epi_link', None) if fuse_kl else None, kl_ws)
         self._z_pri_flowed = None
         if self.n_flows > 0:
             # flow_log_prob = mean over the rows that exist (a static-shape batch: the device count) of the blocks' summed log-dets

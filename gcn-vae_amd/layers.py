@@ -112,11 +112,16 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
                                        part, act_id, keep, scale if keep is not None else 1.0, gather_input, pad_output,
                                        gather_output, x_gathered)
 
-    def forward(self, g, x, etypes, norm=None, sole_consumer=False):
+    def forward(self, g, x, etypes, norm=None, sole_consumer=False, riders=None):
         """``sole_consumer``: the caller passes the output to one node only and that node takes ``out._gv_epi_link``
-        (ops.EpilogueLink; KGVAE.forward -> ops.reparam): offered by the bdd layer without activation."""
+        (ops.EpilogueLink; KGVAE.forward -> ops.reparam): offered by the bdd layer without activation.
+        ``riders`` (ops.RiderBox): small independent jobs for this call's self-loop product to carry; launched in this call
+        either way -- stand-alone, up front, where the layer has no such product (``riders.done`` is set on return)."""
         x, etypes, norm = ops.to_module_device(self.weight, x, etypes, norm)
         int_ids = x.dtype == torch.int64 and x.dim() == 1
+        if riders is not None and (int_ids or self.regularizer != 'bdd'):
+            riders.flush()
+            riders = None
         if int_ids and self.regularizer == 'bdd':
             raise TypeError('Block decomposition does not allow integer ID feature.')
         gidx = graph_index_of(g, x.device)
@@ -148,7 +153,7 @@ class RelGraphConv(ops.StayOnDevice, nn.Module):
         elif self.regularizer == 'bdd':
             h = ops.rel_graph_conv_bdd(x, self.weight, h_bias, loop_w, norm, gidx, ridx, self.num_bases, act_id, keep,
                                        keep_scale, self.reduce_hook,
-                                       sole_consumer=sole_consumer and post_act is None and late_keep is None)
+                                       sole_consumer=sole_consumer and post_act is None and late_keep is None, riders=riders)
         else:
             # basis: W_r = sum_b w_comp[r, b] V_b (one MFMA GEMM), then a full (in x out) matrix per relation
             flat = self.weight.view(self.num_bases, self.in_feat * self.out_feat)

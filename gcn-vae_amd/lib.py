@@ -57,6 +57,7 @@ SIGNATURES = {
     'gv_colsum_finish': (_I, [_P, _I, _I, _P, _I, _P]),
     'gv_gemm_workspace_bytes': (_L, [_I, _I, _I, _I]),
     'gv_gemm_f32': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P]),
+    'gv_gemm_f32_riders': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P]),
     'gv_gemm_f32_live_rows': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P]),
     'gv_gemm_f32_sparse': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _I, _P]),
     'gv_gemm_bf16': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P]),
@@ -192,6 +193,8 @@ SIGNATURES = {
     'gv_kl_fwd': (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P]),
     'gv_kl_bwd': (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _I, _L, _I, _I, _P, _P]),
     'gv_reparam_kl_fwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
+    'gv_reparam_kl_fwd_mix': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _P]),
+    'gv_kl_mix': (_I, [_P, _I, _I, _P, _P]),
     'gv_reparam_kl_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _L, _I, _I, _P]),
     'gv_reparam_kl_bwd_fold': (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _P, _F, _P, _I, _P, _L, _I, _I, _P]),
     'gv_loss_combine_fold': (_I, [_P, _L, _P, _L, _L, _P, _L, _I, _I, _P, _I, _I, _F, _F, _F, _P, _P, _P]),

@@ -449,11 +449,95 @@ class live_rows:
         return False
 
 
+# Riders (csrc/k_riders.h, gv_gemm_f32_riders): the forward head's small launches whose inputs do not depend on a layer's self-loop
+# product -- the forward's random draws, layer 2's lane-packed weights, the KL mixture table -- run as extra workgroups of that
+# product's launch.  GV_GEMM_RIDERS=0: every one of them stand-alone, where it stood before.
+GEMM_RIDERS = _os.environ.get('GV_GEMM_RIDERS', '1') == '1'
+GEMM_RIDER_KINDS = set(_os.environ.get('GV_GEMM_RIDER_KINDS', 'rng,pack,mix').split(','))      # measurement: which kinds may ride
+
+
+class _Riders(_ct.Structure):
+    """ctypes mirror of gv_riders (include/gcnvae.h)."""
+    _fields_ = [('rng_state', _ct.c_void_p), ('rng_ptr', _ct.c_void_p * 8), ('rng_count', _ct.c_int64 * 8),
+                ('rng_kind', _ct.c_int32 * 8), ('rng_drop_p', _ct.c_float * 8), ('rng_stream', _ct.c_uint32 * 8),
+                ('rng_jobs', _ct.c_int32), ('pack_rels', _ct.c_int32), ('pack_bases', _ct.c_int32), ('pack_blk_in', _ct.c_int32),
+                ('pack_blk_out', _ct.c_int32), ('pack_transpose', _ct.c_int32), ('pack_weight', _ct.c_void_p),
+                ('packed', _ct.c_void_p), ('packed_pair', _ct.c_void_p), ('mix_z_pre', _ct.c_void_p), ('mix', _ct.c_void_p),
+                ('mix_k', _ct.c_int32), ('mix_h', _ct.c_int32)]
+
+
+class RiderBox:
+    """Explicit hand-off of independent small jobs to the NEXT self-loop product of one layer call (KGVAE.forward ->
+    RelGraphConv.forward -> _RelGraphConvBdd.forward -> _gemm_addend -> gemm(..., riders=box)): whoever holds the box either
+    launches its jobs as riders of that product (``ride``) or, where the combined launch does not apply, stand-alone on the
+    spot (``flush``) -- in both cases on the caller's stream and before anything reads what they write.  ``done`` says that
+    one of the two happened; the encoder checks it after the layer call, so a box cannot be dropped silently.
+      rng  : (DeviceRNG, [(tensor, kind, drop_p, stream)]) -- already claimed (DeviceRNG.claim), at most 8 jobs ride
+      pack : (weight, num_bases, blk_in, blk_out, transpose_w, packed, packed_pair or None)
+      mix  : (z_pre (2k, h) contiguous, KL workspace) -- the table at the head of the workspace"""
+    __slots__ = ('rng', 'pack', 'mix', 'done', 'rode')
+
+    def __init__(self):
+        self.rng = self.pack = self.mix = None
+        self.done = False
+        self.rode = ()          # the kinds that went out as riders (tests, profiles)
+
+    def empty(self):
+        return self.rng is None and self.pack is None and self.mix is None
+
+    def _launch_alone(self, kinds):
+        if 'rng' in kinds and self.rng is not None:
+            self.rng[0].launch(self.rng[1])
+        if 'pack' in kinds and self.pack is not None:
+            w, nb, bi, bo, trans, packed, pair = self.pack
+            if pair is not None:
+                lib.call('gv_rgcn_bdd_pack_weight_pair', ptr(w), w.shape[0], nb, bi, bo, ptr(packed), ptr(pair), lib.stream())
+            else:
+                lib.call('gv_rgcn_bdd_pack_weight', ptr(w), w.shape[0], nb, bi, bo, 1 if trans else 0, ptr(packed), lib.stream())
+        if 'mix' in kinds and self.mix is not None:
+            z_pre, ws = self.mix
+            lib.call('gv_kl_mix', ptr(z_pre), z_pre.shape[0] // 2, z_pre.shape[1], ptr(ws), lib.stream())
+
+    def flush(self):
+        """Every job stand-alone, here and now."""
+        if self.done:
+            raise RuntimeError('RiderBox: its jobs were already launched')
+        self._launch_alone(('rng', 'pack', 'mix'))
+        self.done = True
+
+    def ride(self, gemm_args):
+        """Launch the product ``gemm_args`` (gv_gemm_f32's arguments without the stream) with the jobs as its riders."""
+        if self.done:
+            raise RuntimeError('RiderBox: its jobs were already launched')
+        ride = {k for k in ('rng', 'pack', 'mix') if getattr(self, k) is not None and k in GEMM_RIDER_KINDS}
+        if 'rng' in ride and len(self.rng[1]) > 8:
+            ride.discard('rng')
+        self._launch_alone({'rng', 'pack', 'mix'} - ride)
+        d = _Riders()
+        if 'rng' in ride:
+            rng, jobs = self.rng
+            d.rng_state, d.rng_jobs = rng.state.data_ptr(), len(jobs)
+            for i, (t, kind, p, st) in enumerate(jobs):
+                d.rng_ptr[i], d.rng_count[i], d.rng_kind[i], d.rng_drop_p[i], d.rng_stream[i] = t.data_ptr(), t.numel(), kind, float(p), st
+        if 'pack' in ride:
+            w, nb, bi, bo, trans, packed, pair = self.pack
+            d.pack_weight, d.packed, d.packed_pair = w.data_ptr(), packed.data_ptr(), (pair.data_ptr() if pair is not None else None)
+            d.pack_rels, d.pack_bases, d.pack_blk_in, d.pack_blk_out, d.pack_transpose = w.shape[0], nb, bi, bo, 1 if trans else 0
+        if 'mix' in ride:
+            z_pre, ws = self.mix
+            d.mix_z_pre, d.mix, d.mix_k, d.mix_h = z_pre.data_ptr(), ws.data_ptr(), z_pre.shape[0] // 2, z_pre.shape[1]
+        lib.call('gv_gemm_f32_riders', *gemm_args, _ct.addressof(d), lib.stream())
+        self.rode = tuple(sorted(ride))
+        self.done = True
+
+
 def gemm(a, b, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, out=None, accumulate=False, split_k=1,
-         a_relu_mask=None, precision=None, b_k_chunks=None, c_tiles=None):
+         a_relu_mask=None, precision=None, b_k_chunks=None, c_tiles=None, riders=None):
     """out = act(op(a') @ op(b) + bias) (+ out);  a' = a * [a_relu_mask > 0] when a mask (same layout as a) is given.
     precision None = the global GEMM_PRECISION.  b_k_chunks / c_tiles (int64 device words, ops.block_words): blocks of op(b) / tiles
-    of the result known to be zero are skipped (gv_gemm_f32_sparse; fp32 only)."""
+    of the result known to be zero are skipped (gv_gemm_f32_sparse; fp32 only).  ``riders`` (RiderBox): its jobs ride on this
+    launch where that form exists (plain fp32 A @ B, no split-K, no zero-block words, no live-row count) and are launched
+    stand-alone in front of it everywhere else."""
     a, lda = _row_major(a, 'a')
     b, ldb = _row_major(b, 'b')
     m, k = (a.shape[1], a.shape[0]) if trans_a else a.shape
@@ -487,6 +571,14 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, out=None, 
             raise ValueError('a_relu_mask must have the shape and leading dimension of a')
     entry = 'gv_gemm_bf16' if (precision or GEMM_PRECISION) == 'bf16' else 'gv_gemm_f32'
     live = LIVE_ROWS
+    if riders is not None:
+        plain = (entry == 'gv_gemm_f32' and b_k_chunks is None and c_tiles is None and not trans_a and not trans_b and split_k <= 1
+                 and m > 0 and n > 0 and not (live is not None and a.shape[0] == live[1] and a.device == live[0].device))
+        if GEMM_RIDERS and plain and not riders.empty():
+            riders.ride((0, 0, m, n, k, ptr(a), lda, ptr(b), ldb, ptr(out), out.stride(0) if m > 1 else n, ptr(bias), act,
+                         1 if accumulate else 0, 1, ptr(a_relu_mask), None, 0))
+            return out
+        riders.flush()
     if (b_k_chunks is not None or c_tiles is not None) and entry == 'gv_gemm_f32':
         if b_k_chunks is not None and (b_k_chunks.dtype != torch.int64 or b_k_chunks.numel() < (n + 63) // 64 or k > 1024 or split_k != 1):
             raise ValueError('b_k_chunks: one int64 word per 64-column tile, k <= 1024, no split-K')
@@ -2003,25 +2095,34 @@ class DeviceRNG:
         self._used.clear()
         return self.state
 
-    def fill(self, jobs):
-        """jobs: [(tensor, kind, drop_p, stream)] -- uint8 tensors for RNG_KEEP_MASK, float32 for RNG_NORMAL."""
+    def claim(self, jobs):
+        """The host side of a fill whose launch comes later on this stream (a rider of the next self-loop product, ops.RiderBox):
+        the seed, the "same stream twice within one tick" rule and the buffer checks, at the place where fill would have run."""
         self._sync_seed()
         if any(j[3] in self._used for j in jobs):     # same stream twice within one tick would repeat its numbers
             self.tick()
+        for t, kind, _, _ in jobs:
+            want = torch.uint8 if kind == RNG_KEEP_MASK else torch.float32
+            if t.dtype != want or not t.is_contiguous() or t.device != self.device:
+                raise TypeError('rng fill: buffers must be contiguous uint8 (mask) / float32 (normal) on the RNG device')
+        self._used.update(j[3] for j in jobs)
+
+    def fill(self, jobs):
+        """jobs: [(tensor, kind, drop_p, stream)] -- uint8 tensors for RNG_KEEP_MASK, float32 for RNG_NORMAL."""
+        self.claim(jobs)
+        self.launch(jobs)
+
+    def launch(self, jobs):
+        """The launches of claimed jobs, stand-alone."""
         for i in range(0, len(jobs), 8):
             part = jobs[i:i + 8]
             n = len(part)
-            for t, kind, _, _ in part:
-                want = torch.uint8 if kind == RNG_KEEP_MASK else torch.float32
-                if t.dtype != want or not t.is_contiguous() or t.device != self.device:
-                    raise TypeError('rng fill: buffers must be contiguous uint8 (mask) / float32 (normal) on the RNG device')
             ptrs = (_ct.c_void_p * n)(*[t.data_ptr() for t, _, _, _ in part])
             counts = (_ct.c_int64 * n)(*[t.numel() for t, _, _, _ in part])
             kinds = (_ct.c_int32 * n)(*[k for _, k, _, _ in part])
             ps = (_ct.c_float * n)(*[float(p) for _, _, p, _ in part])
             streams = (_ct.c_uint32 * n)(*[s for _, _, _, s in part])
             lib.call('gv_rng_fill', ptr(self.state), n, ptrs, counts, kinds, ps, streams, lib.stream())
-        self._used.update(j[3] for j in jobs)
 
 
 def device_rng(device):
@@ -2138,13 +2239,17 @@ def _epilogue_grad(out, grad_out, act, keep, keep_scale, want_bias, d_b):
     return g, (None if d_b is not None else grad_bias)
 
 
-def _gemm_addend(x, loop_weight, h_bias, out_feat, loop_bf=None):
+def _gemm_addend(x, loop_weight, h_bias, out_feat, loop_bf=None, riders=None):
     """The forward epilogue's addend: x @ loop_weight + h_bias (on the bf16 dense forms ``loop_bf`` when the caller has them),
-    h_bias broadcast to x's rows without a self loop, or None."""
+    h_bias broadcast to x's rows without a self loop, or None.  ``riders`` (RiderBox): its jobs ride on the fp32 product, and
+    are launched stand-alone here on every other branch."""
+    if riders is not None and (loop_weight is None or loop_bf is not None):
+        riders.flush()
+        riders = None
     if loop_weight is not None and loop_bf is not None:
         return dense_bf16(x, loop_bf[0], loop_weight.shape[1], loop_weight.shape[0], bias=h_bias)
     if loop_weight is not None:
-        return gemm(x, loop_weight, bias=h_bias)
+        return gemm(x, loop_weight, bias=h_bias, riders=riders)
     if h_bias is not None:
         return h_bias.unsqueeze(0).expand(x.shape[0], out_feat).contiguous()
     return None
@@ -2195,11 +2300,18 @@ def _relation_weight_grad(gidx, ridx, coef, x, g, nb, si, so, d_w):
     return None if d_w is not None else grad_w
 
 
-def _bdd_weight_fwd(ctx, weight, nb, si, so, pk, pk_bwd):
+def _bdd_weight_fwd(ctx, weight, nb, si, so, pk, pk_bwd, riders=None):
     """The forward K1 launch's weight operand (lane-packed with ``pk``).  When the backward-x launch packs too (``pk_bwd``) one
-    launch writes both layouts and the backward's copy is kept on ctx for _bdd_weight_bwd."""
+    launch writes both layouts and the backward's copy is kept on ctx for _bdd_weight_bwd.  ``riders`` (RiderBox): the packing
+    is left in the box -- the layer's self-loop product, launched in front of the K1 launch, carries it."""
     ctx.w_bwd_packed = None
     ctx.w_version = weight._version
+    if pk and riders is not None:
+        w_fwd = torch.empty_like(weight)
+        if pk_bwd:
+            ctx.w_bwd_packed = torch.empty_like(weight)
+        riders.pack = (weight, nb, si, so, False, w_fwd, ctx.w_bwd_packed)
+        return w_fwd
     if pk and pk_bwd:
         w_fwd, ctx.w_bwd_packed = torch.empty_like(weight), torch.empty_like(weight)
         lib.call('gv_rgcn_bdd_pack_weight_pair', ptr(weight), weight.shape[0], nb, si, so, ptr(w_fwd), ptr(ctx.w_bwd_packed),
@@ -2278,9 +2390,12 @@ class _RelGraphConvBdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep, keep_scale,
-                reduce_hook, link_box=None):
+                reduce_hook, link_box=None, riders=None):
         x, _ = _row_major(x, 'x')
         n, in_feat = x.shape
+        if riders is not None and (reduce_hook is not None or loop_weight is None):
+            riders.flush()          # edge-sharded: the aggregation precedes the self-loop product; no self loop: no product
+            riders = None
         si = in_feat // num_bases
         so = weight.shape[1] // (num_bases * si)
         out_feat = num_bases * so
@@ -2294,11 +2409,11 @@ class _RelGraphConvBdd(torch.autograd.Function):
         pk = tl is None and si * so >= 8 and pack_supported(num_bases, si, so, False)
         bwd_phases = reduce_hook is None and use_phases(gidx, so, si, True, n, out_feat)
         pk_bwd = not bwd_phases and si * so >= 8 and pack_supported(num_bases, so, si, True)
-        w_fwd = _bdd_weight_fwd(ctx, weight, num_bases, si, so, pk, pk_bwd and ctx.needs_input_grad[0])
+        w_fwd = _bdd_weight_fwd(ctx, weight, num_bases, si, so, pk, pk_bwd and ctx.needs_input_grad[0], riders)
         ctx.loop_bf = dense_bf16_forms(loop_weight) if (loop_weight is not None and x.shape[0] >= 4096) else None
 
-        def addend():
-            return _gemm_addend(x, loop_weight, h_bias, out_feat, ctx.loop_bf)
+        def addend():       # (every K1 route calls it once, after its own weight packing and in front of its launch)
+            return _gemm_addend(x, loop_weight, h_bias, out_feat, ctx.loop_bf, riders)
 
         ctx.grouped = tl is None and reduce_hook is None and use_relation_groups(weight, gidx)
         ctx.k1_bf = False
@@ -2394,7 +2509,7 @@ class _RelGraphConvBdd(torch.autograd.Function):
         grad_w = None
         if ctx.needs_input_grad[1] and not side_w:
             grad_w = _relation_weight_grad(gidx, ridx, coef, x, g_agg, nb, si, so, d_w)
-        return grad_x, grad_w, grad_bias, grad_loop, None, None, None, None, None, None, None, None, None
+        return grad_x, grad_w, grad_bias, grad_loop, None, None, None, None, None, None, None, None, None, None
 
 
 K1_REL_RUNS = _os.environ.get('GV_K1_REL_RUNS', '1') == '1'     # static graphs: rows sorted by relation (weight reuse along runs)
@@ -2412,15 +2527,16 @@ def use_relation_groups(weight, gidx):
 
 
 def rel_graph_conv_bdd(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act=ACT_NONE, keep=None,
-                       keep_scale=1.0, reduce_hook=None, sole_consumer=False):
+                       keep_scale=1.0, reduce_hook=None, sole_consumer=False, riders=None):
     """``sole_consumer``: the caller hands the output to exactly one node that accepts an EpilogueLink (ops.reparam); the output
-    then carries the hand-off (``out._gv_epi_link``) when the layer can offer one."""
+    then carries the hand-off (``out._gv_epi_link``) when the layer can offer one.  ``riders``: a RiderBox for the layer's
+    self-loop product (launched in this call either way)."""
     if not (sole_consumer and KL_SEAM_FOLD):
         return _RelGraphConvBdd.apply(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep,
-                                      float(keep_scale), reduce_hook, None)
+                                      float(keep_scale), reduce_hook, None, riders)
     box = [None]
     out = _RelGraphConvBdd.apply(x, weight, h_bias, loop_weight, norm, gidx, ridx, num_bases, act, keep, float(keep_scale),
-                                 reduce_hook, box)
+                                 reduce_hook, box, riders)
     out._gv_epi_link = box[0]
     return out
 
@@ -3191,7 +3307,7 @@ class _Reparam(torch.autograd.Function):
     With ``z_pre`` (the mixture prior's parameters, (2k, h)) the KL forward pass over the same rows rides along."""
 
     @staticmethod
-    def forward(ctx, h2, eps, z_pre, link_box, epi_link=None):
+    def forward(ctx, h2, eps, z_pre, link_box, epi_link=None, kl_ws=None):
         ctx.set_materialize_grads(False)
         h2 = _chk(h2.contiguous(), name='h2')
         n, h = h2.shape[0], h2.shape[1] // 2
@@ -3204,10 +3320,15 @@ class _Reparam(torch.autograd.Function):
         if z_pre is not None:
             z_pre = _chk(z_pre.contiguous(), name='z_pre')
             k = z_pre.shape[0] // 2
-            ws = torch.empty(int(lib.load().gv_kl_workspace_bytes(n, h, k)) // 4, dtype=torch.float32, device=h2.device)
             resp = torch.empty(n, k, dtype=torch.float32, device=h2.device)
-            lib.call('gv_reparam_kl_fwd', ptr(h2), ptr(eps), ptr(z_pre), ptr(z), ptr(v), ptr(m), ptr(resp), ptr(ws), n, h, k,
-                     lib.stream())
+            if kl_ws is not None and kl_ws.matches(z_pre, n, h, k):     # the mixture table is already at the head of the workspace
+                ws = kl_ws.ws
+                lib.call('gv_reparam_kl_fwd_mix', ptr(h2), ptr(eps), ptr(z_pre), ptr(z), ptr(v), ptr(m), ptr(resp), ptr(ws), 1, n, h,
+                         k, lib.stream())
+            else:
+                ws = torch.empty(kl_workspace_floats(n, h, k), dtype=torch.float32, device=h2.device)
+                lib.call('gv_reparam_kl_fwd', ptr(h2), ptr(eps), ptr(z_pre), ptr(z), ptr(v), ptr(m), ptr(resp), ptr(ws), n, h, k,
+                         lib.stream())
             ctx.link = link_box[0] = KLLink(resp, ws, z_pre)
             ctx.save_for_backward(h2, eps, v, z, z_pre)
         else:
@@ -3242,7 +3363,7 @@ class _Reparam(torch.autograd.Function):
                          lib.stream())
                 link.gkl = None
                 epi.record(gh2, None if d_b is not None else g_bias)
-                return gh2, None, (None if d_zp is not None else gzp), None, None
+                return gh2, None, (None if d_zp is not None else gzp), None, None, None
             lib.call('gv_reparam_kl_bwd', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp), ptr(link.gkl),
                      float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), 1 if d_zp is not None else 0,
                      ptr(link.ws), n, h, k, lib.stream())
@@ -3253,7 +3374,7 @@ class _Reparam(torch.autograd.Function):
                 gv = None if gv is None else _chk(gv.contiguous(), name='gv')
                 lib.call('gv_reparam_bwd', ptr(h2), ptr(eps), ptr(v), None, ptr(gm), ptr(gv), ptr(extra), n, h, lib.stream())
                 gh2 += extra
-            return gh2, None, (None if d_zp is not None else gzp), None, None
+            return gh2, None, (None if d_zp is not None else gzp), None, None, None
         h2, eps, v = ctx.saved_tensors[:3]
         n, h = v.shape
         gz = None if gz is None else _chk(gz.contiguous(), name='gz')
@@ -3261,17 +3382,38 @@ class _Reparam(torch.autograd.Function):
         gv = None if gv is None else _chk(gv.contiguous(), name='gv')
         gh2 = torch.empty_like(h2)
         lib.call('gv_reparam_bwd', ptr(h2), ptr(eps), ptr(v), ptr(gz), ptr(gm), ptr(gv), ptr(gh2), n, h, lib.stream())
-        return gh2, None, None, None, None
+        return gh2, None, None, None, None, None
 
 
-def reparam(h2, eps, z_pre=None, epi_link=None):
+def kl_workspace_floats(n, h, k):
+    return int(lib.load().gv_kl_workspace_bytes(n, h, k)) // 4
+
+
+class KLWorkspace:
+    """A KL workspace allocated AHEAD of ops.reparam, so that its mixture table can be made early (the mix job of a RiderBox):
+    ``ws`` for (n, h, k) and the z_pre (address, version) the table is made from.  ops.reparam takes it only for that z_pre."""
+    __slots__ = ('ws', 'z_pre', 'key')
+
+    def __init__(self, z_pre, n):
+        z_pre = _chk(z_pre.detach().contiguous(), name='z_pre')
+        k, h = z_pre.shape[0] // 2, z_pre.shape[1]
+        self.z_pre = z_pre
+        self.ws = torch.empty(kl_workspace_floats(n, h, k), dtype=torch.float32, device=z_pre.device)
+        self.key = (z_pre.data_ptr(), z_pre._version, int(n), h, k)
+
+    def matches(self, z_pre, n, h, k):
+        return (z_pre.data_ptr(), z_pre._version, int(n), h, k) == self.key
+
+
+def reparam(h2, eps, z_pre=None, epi_link=None, kl_ws=None):
     """``z_pre``: when the caller knows that the loss head will evaluate KL(z) against this mixture with no flow in between,
     the KL forward pass is done in the same sweep; the returned z then carries the hand-off (``z._gv_kl_link``).
-    ``epi_link``: the EpilogueLink of the layer that made ``h2``, from a caller that knows this node is h2's ONLY consumer."""
+    ``epi_link``: the EpilogueLink of the layer that made ``h2``, from a caller that knows this node is h2's ONLY consumer.
+    ``kl_ws``: a KLWorkspace whose mixture table has been made from this z_pre (on this stream, before this call)."""
     if z_pre is None or not FUSE_REPARAM_KL:
-        return _Reparam.apply(h2, eps, None, None, None)
+        return _Reparam.apply(h2, eps, None, None, None, None)
     box = [None]
-    z, m, v = _Reparam.apply(h2, eps, z_pre, box, epi_link if KL_SEAM_FOLD else None)
+    z, m, v = _Reparam.apply(h2, eps, z_pre, box, epi_link if KL_SEAM_FOLD else None, kl_ws)
     z._gv_kl_link = box[0]
     return z, m, v
 

@@ -1042,6 +1042,37 @@ int64_t gv_gemm_workspace_bytes(int m, int n, int k, int split_k);
 int gv_gemm_f32(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
                 float* c, int ldc, const float* bias, int act, int accumulate, int split_k, const float* a_relu_mask,
                 void* workspace, int64_t workspace_bytes, void* stream);
+/* ... with RIDERS: small launches of the forward head whose inputs do not depend on this product -- the forward's random draws
+ * (gv_rng_fill), a layer's lane-packed weights (gv_rgcn_bdd_pack_weight / _pair) and the KL mixture table (gv_kl_mix) -- run as
+ * extra workgroups of the product's launch, on the VALUs and the memory system that the MFMA tile loop leaves free: no launch
+ * boundary, no fork, no join.  Every rider computes bit for bit what its stand-alone entry computes (the kernels share the bodies,
+ * csrc/k_riders.h); C is bit for bit gv_gemm_f32's.  A part of the description that is unused stays zero: rng_jobs = 0,
+ * pack_weight = NULL, mix_z_pre = NULL; with all three unused (or riders == NULL) the call IS gv_gemm_f32.  With riders: A @ B only
+ * (trans_a = trans_b = 0), split_k <= 1 (GV_ERR_SHAPE otherwise); a rider buffer that overlaps A, B, C, bias or the mask -- or a
+ * rider input that overlaps C -- is refused (GV_ERR_SHAPE), and nothing is launched.  The struct is a HOST object, read during the call.
+ *   rng_*  : as the arrays of gv_rng_fill (at most GV_RNG_MAX_JOBS jobs);
+ *   pack_* : packed <- weight for (pack_blk_in, pack_blk_out, pack_transpose); packed_pair (optional, pack_transpose = 0 only): the
+ *            backward-x layout as well, as gv_rgcn_bdd_pack_weight_pair writes it;
+ *   mix_*  : mix <- gv_kl_mix(mix_z_pre, mix_k, mix_h). */
+typedef struct gv_riders {
+    const uint64_t* rng_state;
+    void* rng_ptr[8];
+    int64_t rng_count[8];
+    int32_t rng_kind[8];
+    float rng_drop_p[8];
+    uint32_t rng_stream[8];
+    int32_t rng_jobs;
+    int32_t pack_rels, pack_bases, pack_blk_in, pack_blk_out, pack_transpose;
+    const float* pack_weight;
+    float* packed;
+    float* packed_pair;
+    const float* mix_z_pre;
+    float* mix;
+    int32_t mix_k, mix_h;
+} gv_riders;
+int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* c,
+                       int ldc, const float* bias, int act, int accumulate, int split_k, const float* a_relu_mask, void* workspace,
+                       int64_t workspace_bytes, const gv_riders* riders, void* stream);
 /* ... for a STATIC-SHAPE batch whose node arrays are padded: only the first *rows_dev (device int32) rows of the stored A exist.
  * Row-major A (trans_a == 0): 64-row tiles of padding rows are not computed, their C rows receive ZEROS (nothing when
  * accumulating); A stored [K, M] (trans_a != 0): the reduction ends at row *rows_dev.  The padding rows of A must be finite. */
@@ -1187,6 +1218,12 @@ int gv_kl_bwd(const float* z, const float* m, int ld_m, const float* v, const fl
  *                       gv_kl_bwd; `workspace` must be the one gv_reparam_kl_fwd (or gv_kl_fwd) filled for the same z_pre; k <= 16. */
 int gv_reparam_kl_fwd(const float* h2, const float* eps, const float* z_pre, float* z, float* v, float* m_out, float* resp,
                       float* workspace, int64_t n, int h, int k, void* stream);
+/* ... gv_reparam_kl_fwd with mix_ready, as gv_kl_bwd has it: 1 = the mixture table at the head of `workspace` was already made from
+ * this z_pre (gv_kl_mix, or the mix rider of gv_gemm_f32_riders) and is not made again; 0 = gv_reparam_kl_fwd.
+ * gv_kl_mix: that table alone, mix[3][k*h] = (mu_j, 1 / (2 v_j), log sqrt v_j + log sqrt 2 pi), v = softplus(z_pre[k:]) + 1e-8. */
+int gv_reparam_kl_fwd_mix(const float* h2, const float* eps, const float* z_pre, float* z, float* v, float* m_out, float* resp,
+                          float* workspace, int mix_ready, int64_t n, int h, int k, void* stream);
+int gv_kl_mix(const float* z_pre, int k, int h, float* mix, void* stream);
 int gv_reparam_kl_bwd(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre, const float* resp,
                       const float* gkl, float gscale, float z_extra, const float* gz_up, float* gh2, float* g_zpre,
                       int accumulate_zpre, float* workspace, int64_t n, int h, int k, void* stream);
