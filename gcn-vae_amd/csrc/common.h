@@ -146,8 +146,8 @@ __device__ __forceinline__ void store_vec(float* __restrict__ p, const float (&s
 // slice groups: group g adds its contiguous range of slices in order (4 independent chains, fixed combine), then the 64
 // group sums of a column are added in group order.  Returns the column total to the threads of group 0 (others: 0);
 // `sm` is a 64 x 16 float scratch.  Many small blocks instead of one wide one: the sum is latency-bound.
-__device__ __forceinline__ float sum_slices_16x64(const float* __restrict__ part, int ncols, int nsl, int col, float (*sm)[16]) {
-    const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
+// (slice group `grp` of 64: its contiguous range of slices of column `col`)
+__device__ __forceinline__ float slice_group_sum(const float* __restrict__ part, int ncols, int nsl, int col, int grp) {
     const int per = (nsl + 63) / 64;
     const int s0 = grp * per, s1 = min(nsl, s0 + per);
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -160,13 +160,41 @@ __device__ __forceinline__ float sum_slices_16x64(const float* __restrict__ part
         }
         for (; s < s1; ++s) a0 += part[(size_t)s * ncols + col];
     }
-    sm[grp][cl] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
+    return (a0 + a1) + (a2 + a3);
+}
+
+// (the 64 group sums of column threadIdx.x & 15 in group order, for the threads of group 0; behind the barrier that follows the stores)
+__device__ __forceinline__ float slice_groups_total(const float (*sm)[16]) {
+    const int cl = threadIdx.x & 15;
     float tot = 0.f;
-    if (grp == 0) {
+    if ((threadIdx.x >> 4) == 0) {
 #pragma unroll 8
         for (int g = 0; g < 64; ++g) tot += sm[g][cl];
     }
+    return tot;
+}
+
+__device__ __forceinline__ float sum_slices_16x64(const float* __restrict__ part, int ncols, int nsl, int col, float (*sm)[16]) {
+    const int cl = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    sm[grp][cl] = slice_group_sum(part, ncols, nsl, col, grp);
+    __syncthreads();
+    return slice_groups_total(sm);
+}
+
+// The same sum by a 256-thread workgroup (16 columns x 16 thread groups, a thread group takes the slice groups t, t + 16, t + 32,
+// t + 48): the same 64 group sums, added in the same order -- the same bits.  `sm` may be in use by the caller up to this call and
+// is free again behind it (barriers on both sides).
+__device__ __forceinline__ float sum_slices_16x64_wg256(const float* __restrict__ part, int ncols, int nsl, int col, float (*sm)[16]) {
+    const int cl = threadIdx.x & 15, t = threadIdx.x >> 4;
+    float g4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g4[q] = slice_group_sum(part, ncols, nsl, col, t + 16 * q);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sm[t + 16 * q][cl] = g4[q];
+    __syncthreads();
+    const float tot = slice_groups_total(sm);
+    __syncthreads();
     return tot;
 }
 

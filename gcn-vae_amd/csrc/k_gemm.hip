@@ -338,16 +338,19 @@ __global__ __launch_bounds__(256) void k_gemm_f32(const GemmParams p) {
 // n_riders workgroups that run independent small jobs on the VALUs and the memory system the product leaves free.  The branch is
 // block-uniform.  riders_front: the rider workgroups are dispatched first (n_riders is then a multiple of 8, so that every tile
 // workgroup keeps the XCD it has in the plain launch); otherwise they follow the tiles.  No split-K, no k-chunk / tile words.
+// <false, false>: the forward's x @ loop_weight; <false, true>: the backward's dL/dx = g @ loop_weight^T (_loop_grads), which
+// carries the gradient finishers.  A rider workgroup's 4 KiB scratch stands beside the tile's staging arrays (12.4 of 160 KiB).
 template <bool TA, bool TB, int MT, int NT, int BK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 5 : 7))) void k_gemm_f32_riders(const GemmParams p, const RiderSet rs, const int ntn, const int ntm,
                                                          const int n_riders, const int riders_front) {
+    __shared__ float rider_sm[64][16];
     const int tiles = ntn * ntm;
     int b = blockIdx.x;
     if (riders_front) {
-        if (b < n_riders) { rider_body(rs, b, n_riders); return; }
+        if (b < n_riders) { rider_body(rs, b, n_riders, rider_sm); return; }
         b -= n_riders;
     } else if (b >= tiles) {
-        rider_body(rs, b - tiles, n_riders);
+        rider_body(rs, b - tiles, n_riders, rider_sm);
         return;
     }
     const int by = b / ntn;
@@ -1437,7 +1440,7 @@ __global__ __launch_bounds__(1024) void k_colsum_final_wide(const float* part, i
     __shared__ float sm[64][16];
     const int c = blockIdx.x * 16 + (threadIdx.x & 15);
     const float acc = sum_slices_16x64(part, n, nsl, c, sm);
-    if ((threadIdx.x >> 4) == 0 && c < n) out[c] = accumulate ? out[c] + acc : acc;
+    if ((threadIdx.x >> 4) == 0 && c < n) colsum_final_store(acc, c, out, accumulate);      // (k_riders.h: a rider does the same)
 }
 
 }  // namespace gv
@@ -1566,20 +1569,27 @@ inline bool overlaps(const Extent& a, const Extent& b) { return a.lo && b.lo && 
 inline int64_t matrix_bytes(int rows, int cols, int ld) { return rows > 0 && cols > 0 ? ((int64_t)(rows - 1) * ld + cols) * 4 : 0; }
 }  // namespace
 
-extern "C" int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
-                                  float* c, int ldc, const float* bias, int act, int accumulate, int split_k,
-                                  const float* a_relu_mask, void* workspace, int64_t workspace_bytes, const gv_riders* riders,
-                                  void* stream) {
-    const bool any = riders && (riders->rng_jobs > 0 || riders->pack_weight || riders->mix_z_pre);
+static const gv_riders NO_RIDERS = {};
+
+// riders: the forward head's kinds; fin (gv_gemm_f32_riders_fin only): the prior sampler and the backward's gradient finishers
+static int gemm_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
+                       float* c, int ldc, const float* bias, int act, int accumulate, int split_k,
+                       const float* a_relu_mask, void* workspace, int64_t workspace_bytes, const gv_riders* riders,
+                       const gv_riders_fin* fin, void* stream) {
+    const bool any_fin = fin && (fin->prior_z_pre || fin->kl_part || fin->cs_part);
+    const bool any = (riders && (riders->rng_jobs > 0 || riders->pack_weight || riders->mix_z_pre)) || any_fin;
     if (!any)       // no riders: the plain kernel, exactly as gv_gemm_f32 launches it
         return gemm_any(false, trans_a, trans_b, m, n, k, a, lda, b, ldb, c, ldc, bias, act, accumulate, split_k, a_relu_mask,
                         workspace, workspace_bytes, stream);
+    if (!riders) riders = &NO_RIDERS;
     GV_REQUIRE(split_k <= 1, GV_ERR_SHAPE, "gv_gemm_f32_riders: riders do not ride on a split-K product (split_k=%d)", split_k);
-    GV_REQUIRE(!trans_a && !trans_b, GV_ERR_SHAPE, "gv_gemm_f32_riders: riders ride on A @ B only (the forward self-loop product)");
+    GV_REQUIRE(!trans_a && (!trans_b || fin), GV_ERR_SHAPE,
+               "gv_gemm_f32_riders: riders ride on A @ B (the forward self-loop product) and, through gv_gemm_f32_riders_fin, on "
+               "A @ B^T (the backward's) only");
     GV_REQUIRE(m > 0 && n > 0 && k >= 0, GV_ERR_SHAPE, "gv_gemm_f32_riders: m=%d n=%d k=%d", m, n, k);
     GV_REQUIRE(c && (k == 0 || (a && b)), GV_ERR_NULL, "gv_gemm_f32_riders: NULL matrix");
-    GV_REQUIRE(lda >= k && ldb >= n && ldc >= n, GV_ERR_SHAPE, "gv_gemm_f32_riders: leading dimension too small (lda=%d ldb=%d ldc=%d)",
-               lda, ldb, ldc);
+    GV_REQUIRE(lda >= k && ldb >= (trans_b ? k : n) && ldc >= n, GV_ERR_SHAPE,
+               "gv_gemm_f32_riders: leading dimension too small (lda=%d ldb=%d ldc=%d)", lda, ldb, ldc);
     GV_REQUIRE(act == GV_ACT_NONE || act == GV_ACT_RELU, GV_ERR_SHAPE, "gv_gemm_f32_riders: unknown act %d", act);
     GemmParams p;
     p.a = a; p.b = b; p.c = c; p.bias = bias; p.a_mask = a_relu_mask; p.ws = nullptr;
@@ -1597,7 +1607,7 @@ extern "C" int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k,
     GV_REQUIRE((int64_t)ntn * ntm < (1ll << 30), GV_ERR_SHAPE, "gv_gemm_f32_riders: %d x %d tiles", ntn, ntm);
 
     // what the product reads and writes, against what the riders read and write
-    const Extent ea = extent_of(a, matrix_bytes(m, k, lda)), eb = extent_of(b, matrix_bytes(k, n, ldb)),
+    const Extent ea = extent_of(a, matrix_bytes(m, k, lda)), eb = extent_of(b, trans_b ? matrix_bytes(n, k, ldb) : matrix_bytes(k, n, ldb)),
                  ec = extent_of(c, matrix_bytes(m, n, ldc)), ebias = extent_of(bias, (int64_t)n * 4),
                  emask = extent_of(a_relu_mask, matrix_bytes(m, k, lda));
     auto written_ok = [&](const Extent& w) { return !(overlaps(w, ea) || overlaps(w, eb) || overlaps(w, ec) || overlaps(w, ebias) || overlaps(w, emask)); };
@@ -1680,13 +1690,93 @@ extern "C" int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k,
         nblk += (mk * mh + 255) / 256;
     }
     rs.first[3] = nblk;
+    // what the finishers write, against each other
+    Extent fin_out[3] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    if (any_fin && fin->prior_z_pre) {
+        const int s = fin->prior_s, pk = fin->prior_k, ph = fin->prior_h;
+        GV_REQUIRE(fin->prior_eps && fin->prior_out, GV_ERR_NULL, "gv_gemm_f32_riders_fin: NULL prior buffer");
+        GV_REQUIRE(s > 0 && pk > 0 && ph > 0 && (int64_t)s * ph < (1ll << 28) && (int64_t)pk * ph < (1ll << 28), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders_fin: prior s=%d k=%d h=%d", s, pk, ph);
+        const Extent ez = extent_of(fin->prior_z_pre, (int64_t)2 * pk * ph * 4), ee = extent_of(fin->prior_eps, (int64_t)s * ph * 4),
+                     eo = extent_of(fin->prior_out, (int64_t)s * ph * 4);
+        GV_REQUIRE(read_ok(ez) && read_ok(ee) && written_ok(eo) && !overlaps(eo, ez) && !overlaps(eo, ee), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders_fin: a prior sampler buffer overlaps an operand of the product or its own input");
+        // its noise must be complete before this launch: a draw of the same launch is no such thing
+        for (int j = 0; j < riders->rng_jobs; ++j) {
+            const Extent ej = extent_of(riders->rng_ptr[j], riders->rng_count[j] * (riders->rng_kind[j] == GV_RNG_NORMAL ? 4 : 1));
+            GV_REQUIRE(!overlaps(ej, ee) && !overlaps(ej, ez) && !overlaps(ej, eo), GV_ERR_SHAPE,
+                       "gv_gemm_f32_riders_fin: the prior sampler reads or writes what rng job %d of the same launch writes", j);
+        }
+        GV_REQUIRE(!overlaps(eo, extent_of(riders->mix, (int64_t)3 * riders->mix_k * riders->mix_h * 4)), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders_fin: the prior samples overlap the mixture table");
+        rs.prior.z_pre = fin->prior_z_pre; rs.prior.eps = fin->prior_eps; rs.prior.out = fin->prior_out;
+        rs.prior.s = s; rs.prior.k = pk; rs.prior.h = ph;
+        fin_out[0] = eo;
+        nblk += (s * ph + 255) / 256;                  // as gv_prior_sample_fwd's grid
+    }
+    rs.first[4] = nblk;
+    if (any_fin && fin->kl_part) {
+        const int kh_ = fin->kl_h, kk = fin->kl_k, nsl = fin->kl_slices;
+        GV_REQUIRE(fin->kl_z_pre && fin->kl_g_zpre, GV_ERR_NULL, "gv_gemm_f32_riders_fin: NULL KL finisher buffer");
+        GV_REQUIRE(kh_ > 0 && kk > 0 && nsl > 0 && fin->kl_n > 0 && (int64_t)(2 * kk + 2) * kh_ < (1ll << 28), GV_ERR_SHAPE,
+                   "gv_gemm_f32_riders_fin: KL finisher n=%lld h=%d k=%d slices=%d", (long long)fin->kl_n, kh_, kk, nsl);
+        const int cols = (2 * kk + (fin->kl_g_bias ? 2 : 0)) * kh_;
+        const Extent ep = extent_of(fin->kl_part, (int64_t)nsl * cols * 4), ez = extent_of(fin->kl_z_pre, (int64_t)2 * kk * kh_ * 4),
+                     eg = extent_of(fin->kl_gkl, 4), eo = extent_of(fin->kl_g_zpre, (int64_t)2 * kk * kh_ * 4),
+                     ebo = extent_of(fin->kl_g_bias, (int64_t)2 * kh_ * 4);
+        GV_REQUIRE(read_ok(ep) && read_ok(ez) && read_ok(eg) && written_ok(eo) && written_ok(ebo) && !overlaps(eo, ebo) &&
+                       !overlaps(eo, ep) && !overlaps(eo, ez) && !overlaps(eo, eg) && !overlaps(ebo, ep) && !overlaps(ebo, ez) &&
+                       !overlaps(ebo, eg) && !overlaps(eo, fin_out[0]) && !overlaps(ebo, fin_out[0]),
+                   GV_ERR_SHAPE, "gv_gemm_f32_riders_fin: a KL finisher buffer overlaps an operand of the product or another rider buffer");
+        KlFinJob& kj = rs.klfin;
+        kj.part = fin->kl_part; kj.z_pre = fin->kl_z_pre; kj.gkl = fin->kl_gkl; kj.gscale = fin->kl_gscale;
+        kj.g_zpre = fin->kl_g_zpre; kj.g_bias = fin->kl_g_bias; kj.n = fin->kl_n; kj.accumulate = fin->kl_accumulate;
+        kj.accumulate_bias = fin->kl_accumulate_bias; kj.h = kh_; kj.k = kk; kj.nsl = nsl;
+        fin_out[1] = eo; fin_out[2] = ebo;
+        nblk += (cols + 15) / 16;                      // 16 columns per workgroup, as k_kl_bwd_mix_final's blocks
+    }
+    rs.first[5] = nblk;
+    if (any_fin && fin->cs_part) {
+        const int cn = fin->cs_n, nsl = fin->cs_slices;
+        GV_REQUIRE(fin->cs_out, GV_ERR_NULL, "gv_gemm_f32_riders_fin: NULL column-sum target");
+        GV_REQUIRE(cn > 0 && nsl > 0 && (int64_t)cn * nsl < (1ll << 28), GV_ERR_SHAPE, "gv_gemm_f32_riders_fin: column sums n=%d slices=%d",
+                   cn, nsl);
+        const Extent ep = extent_of(fin->cs_part, (int64_t)nsl * cn * 4), eo = extent_of(fin->cs_out, (int64_t)cn * 4);
+        GV_REQUIRE(read_ok(ep) && written_ok(eo) && !overlaps(eo, ep) && !overlaps(eo, fin_out[0]) && !overlaps(eo, fin_out[1]) &&
+                       !overlaps(eo, fin_out[2]) && !overlaps(ep, fin_out[0]) && !overlaps(ep, fin_out[1]) && !overlaps(ep, fin_out[2]),
+                   GV_ERR_SHAPE, "gv_gemm_f32_riders_fin: a column-sum buffer overlaps an operand of the product or another rider buffer");
+        rs.colsum.part = fin->cs_part; rs.colsum.out = fin->cs_out; rs.colsum.n = cn; rs.colsum.nsl = nsl;
+        rs.colsum.accumulate = fin->cs_accumulate;
+        nblk += (cn + 15) / 16;
+    }
+    rs.first[6] = nblk;
     // riders in front: pad their count to a multiple of 8, so that tile workgroup i keeps XCD i % 8 (the padding blocks leave at once)
     const int n_riders = front ? (nblk + 7) / 8 * 8 : nblk;
     const dim3 grid((unsigned)(ntn * ntm + n_riders)), block(256);
     hipStream_t st = (hipStream_t)stream;
-    if (mt == 2) hipLaunchKernelGGL((k_gemm_f32_riders<false, false, 2, 1, 16>), grid, block, 0, st, p, rs, ntn, ntm, n_riders, front ? 1 : 0);
-    else hipLaunchKernelGGL((k_gemm_f32_riders<false, false, 1, 1, 16>), grid, block, 0, st, p, rs, ntn, ntm, n_riders, front ? 1 : 0);
+#define GV_RIDERS_LAUNCH(TB_, MT_) \
+    hipLaunchKernelGGL((k_gemm_f32_riders<false, TB_, MT_, 1, 16>), grid, block, 0, st, p, rs, ntn, ntm, n_riders, front ? 1 : 0)
+    if (trans_b) { if (mt == 2) GV_RIDERS_LAUNCH(true, 2); else GV_RIDERS_LAUNCH(true, 1); }
+    else { if (mt == 2) GV_RIDERS_LAUNCH(false, 2); else GV_RIDERS_LAUNCH(false, 1); }
+#undef GV_RIDERS_LAUNCH
     return launch_status("gv_gemm_f32_riders");
+}
+
+extern "C" int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
+                                  float* c, int ldc, const float* bias, int act, int accumulate, int split_k,
+                                  const float* a_relu_mask, void* workspace, int64_t workspace_bytes, const gv_riders* riders,
+                                  void* stream) {
+    return gemm_riders(trans_a, trans_b, m, n, k, a, lda, b, ldb, c, ldc, bias, act, accumulate, split_k, a_relu_mask, workspace,
+                       workspace_bytes, riders, nullptr, stream);
+}
+
+extern "C" int gv_gemm_f32_riders_fin(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb,
+                                      float* c, int ldc, const float* bias, int act, int accumulate, int split_k,
+                                      const float* a_relu_mask, void* workspace, int64_t workspace_bytes, const gv_riders* riders,
+                                      const gv_riders_fin* fin, void* stream) {
+    static const gv_riders_fin none = {};
+    return gemm_riders(trans_a, trans_b, m, n, k, a, lda, b, ldb, c, ldc, bias, act, accumulate, split_k, a_relu_mask, workspace,
+                       workspace_bytes, riders, fin ? fin : &none, stream);
 }
 
 extern "C" int gv_gemm_f32_live_rows(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b,

@@ -947,16 +947,7 @@ __global__ __launch_bounds__(1024) void k_kl_bwd_mix_final(const float* part, co
     const int i = blockIdx.x * 16 + (threadIdx.x & 15);
     float acc = sum_slices_16x64(part, total, nsl, i, sm);     // slices added in a fixed order
     if ((threadIdx.x >> 4) != 0 || i >= total) return;
-    if (i >= 2 * kh) {
-        g_bias[i - 2 * kh] = accumulate_bias ? g_bias[i - 2 * kh] + acc : acc;
-        return;
-    }
-    const float cg = gscale * (gkl ? *gkl : 1.f) / (float)(rows_dev ? (int64_t)*rows_dev : n);
-    if (i >= kh) {  // chain through v_j = softplus(raw) + 1e-8
-        const float raw = z_pre[i];
-        acc *= raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw));
-    }
-    g_zpre[i] = accumulate ? g_zpre[i] + cg * acc : cg * acc;
+    kl_mix_final_store(acc, i, kh, z_pre, gkl, gscale, g_zpre, accumulate, n, rows_dev, g_bias, accumulate_bias);      // (k_riders.h)
 }
 
 // ---- MMD (KGVAE.get_mmd / compute_kernel, kgvae/model.py:71-80, :89-102) -------------------------------
@@ -1378,14 +1369,9 @@ __global__ __launch_bounds__(256) void k_mmd_grad_finish(const MmdFinishParams a
     a.gz_pre[total + i] = a.accumulate ? a.gz_pre[total + i] + gr : gr;
 }
 
-// prior samples of get_mmd: z_pri[i] = mu[i % k] + eps[i] * sqrt(softplus(raw[i % k]) + 1e-8)   (z_pre = [mu; raw], (2k, h))
+// prior samples of get_mmd (the body: k_riders.h, prior_sample_body -- layer 2's forward self-loop product may carry it)
 __global__ __launch_bounds__(256) void k_prior_sample_fwd(const float* z_pre, const float* eps, float* out, int s, int k, int h) {
-    const int total = s * h;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int r = i / h, c = i - r * h, j = r % k;
-        const float v = softplus_t(z_pre[(size_t)(k + j) * h + c]) + 1e-8f;
-        out[i] = z_pre[(size_t)j * h + c] + eps[i] * sqrtf(v);
-    }
+    prior_sample_body(z_pre, eps, out, s, k, h, (int)blockIdx.x, (int)gridDim.x);
 }
 
 __global__ __launch_bounds__(256) void k_prior_sample_bwd(const float* z_pre, const float* eps, const float* g, float* gz_pre,
@@ -1957,11 +1943,11 @@ extern "C" int gv_reparam_kl_bwd(const float* z, const float* h2, const float* v
 // gv_reparam_kl_bwd that also does the epilogue gradient of the layer that made h2 (no activation; k_kl_bwd_cols4): gh2 rows
 // masked by keep / keep_scale before they are stored, their column sums (that layer's bias gradient) finished by the launch
 // that finishes g_zpre.  Only the float4-column form takes the fold: where it refuses, this call fails and launches nothing.
-extern "C" int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
-                                      const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up,
-                                      float* gh2, float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale,
-                                      float* g_bias, int accumulate_bias, float* workspace, int64_t n, int h, int k,
-                                      void* stream) {
+static int reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                               const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up,
+                               float* gh2, float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale,
+                               float* g_bias, int accumulate_bias, float* workspace, int64_t n, int h, int k,
+                               void* stream, bool finish) {
     GV_REQUIRE(z && h2 && v && eps && z_pre && resp && gh2 && g_zpre && workspace, GV_ERR_NULL,
                "gv_reparam_kl_bwd_fold: NULL pointer");
     GV_REQUIRE(n > 0 && h > 0 && k > 0 && k <= KL_FUSED_KT, GV_ERR_SHAPE, "gv_reparam_kl_bwd_fold: n=%lld h=%d k=%d (k <= %d)",
@@ -1975,9 +1961,47 @@ extern "C" int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const flo
                             gz_up, gh2, keep, keep_scale, g_bias != nullptr),
                GV_ERR_SHAPE, "gv_reparam_kl_bwd_fold: h=%d k=%d or an unaligned operand: only the float4-column backward "
                "(h %% 4 == 0, k <= 10, 16-B rows) folds the epilogue gradient", h, k);
-    hipLaunchKernelGGL(k_kl_bwd_mix_final, dim3((cols + 15) / 16), dim3(1024), 0, GV_ST, (const float*)part, z_pre, gkl, gscale,
-                       g_zpre, accumulate_zpre, n, h, k, KL_SLICES, no_rows, g_bias, accumulate_bias);
+    if (finish)
+        hipLaunchKernelGGL(k_kl_bwd_mix_final, dim3((cols + 15) / 16), dim3(1024), 0, GV_ST, (const float*)part, z_pre, gkl, gscale,
+                           g_zpre, accumulate_zpre, n, h, k, KL_SLICES, no_rows, g_bias, accumulate_bias);
     return launch_status("gv_reparam_kl_bwd_fold");
+}
+
+extern "C" int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                                      const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up,
+                                      float* gh2, float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale,
+                                      float* g_bias, int accumulate_bias, float* workspace, int64_t n, int h, int k,
+                                      void* stream) {
+    return reparam_kl_bwd_fold(z, h2, v, eps, z_pre, resp, gkl, gscale, z_extra, gz_up, gh2, g_zpre, accumulate_zpre, keep, keep_scale,
+                               g_bias, accumulate_bias, workspace, n, h, k, stream, true);
+}
+
+// gv_reparam_kl_bwd_fold without its finishing launch: the slice sums stay in the workspace ([gv_kl_bwd_slices()][(2 k + 2) h]
+// floats, or 2 k h columns without g_bias, from float gv_kl_bwd_part_offset(h, k) on) for gv_kl_bwd_mix_final -- or for the KL
+// finisher among the riders of a later product on this stream (gv_gemm_f32_riders_fin).  g_zpre / g_bias are not written here.
+extern "C" int gv_reparam_kl_bwd_fold_sweep(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                                            const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up,
+                                            float* gh2, float* g_zpre, const uint8_t* keep, float keep_scale, float* g_bias,
+                                            float* workspace, int64_t n, int h, int k, void* stream) {
+    return reparam_kl_bwd_fold(z, h2, v, eps, z_pre, resp, gkl, gscale, z_extra, gz_up, gh2, g_zpre, 0, keep, keep_scale, g_bias, 0,
+                               workspace, n, h, k, stream, false);
+}
+
+extern "C" int64_t gv_kl_bwd_part_offset(int h, int k) { return 3 * (int64_t)k * h + RED_BLOCKS; }
+extern "C" int gv_kl_bwd_slices(void) { return KL_SLICES; }
+
+// The KL backward's finishing launch alone: z_pre's gradient (and, with g_bias, the 2 h bias sums behind the mixture columns)
+// from `n_slices` slices of partial sums, added in a fixed order.
+extern "C" int gv_kl_bwd_mix_final(const float* part, int n_slices, const float* z_pre, const float* gkl, float gscale, float* g_zpre,
+                                   int accumulate_zpre, float* g_bias, int accumulate_bias, int64_t n, int h, int k, void* stream) {
+    GV_REQUIRE(part && z_pre && g_zpre, GV_ERR_NULL, "gv_kl_bwd_mix_final: NULL pointer");
+    GV_REQUIRE(n > 0 && h > 0 && k > 0 && n_slices > 0 && (int64_t)(2 * k + 2) * h < (1ll << 28), GV_ERR_SHAPE,
+               "gv_kl_bwd_mix_final: n=%lld h=%d k=%d n_slices=%d", (long long)n, h, k, n_slices);
+    const int cols = (2 * k + (g_bias ? 2 : 0)) * h;
+    const int* no_rows = nullptr;
+    hipLaunchKernelGGL(k_kl_bwd_mix_final, dim3((cols + 15) / 16), dim3(1024), 0, GV_ST, part, z_pre, gkl, gscale, g_zpre,
+                       accumulate_zpre, n, h, k, n_slices, no_rows, g_bias, accumulate_bias);
+    return launch_status("gv_kl_bwd_mix_final");
 }
 
 __global__ void k_lincomb(const float* a0, float c0, const float* a1, float c1, const float* a2, float c2, const float* a3,

@@ -1,9 +1,14 @@
-// Riders: small launches of the forward head whose inputs do not depend on the product beside them, as bodies that take
-// (block index, block count) instead of blockIdx / gridDim.  The stand-alone kernels (k_rng_fill, k_pack_weight, k_kl_mix) call
-// the same bodies, and so do the extra workgroups of k_gemm_f32_riders (k_gemm.hip): every expression and every order is shared,
-// so a value does not depend on which launch wrote it.
-// Rules of a rider: no atomics, no LDS, no barrier, no waiting of one workgroup on another; it reads nothing the product writes
-// and writes nothing the product reads (gv_gemm_f32_riders refuses overlapping buffers on the host).
+// Riders: small launches of the forward head and of the backward's gradient finishers whose inputs do not depend on the product
+// beside them, as bodies that take (block index, block count) instead of blockIdx / gridDim.  The stand-alone kernels (k_rng_fill,
+// k_pack_weight, k_kl_mix, k_prior_sample_fwd) call the same bodies, and so do the extra workgroups of k_gemm_f32_riders
+// (k_gemm.hip): every expression and every order is shared, so a value does not depend on which launch wrote it.  The two slice-sum
+// finishers (k_kl_bwd_mix_final, k_colsum_final_wide) keep their 1024-thread launches; their rider bodies are 256-thread
+// workgroups that form the same 64 slice-group sums with the same function and add them in the same order (common.h:
+// slice_group_sum, slice_groups_total), and share the store expressions below.
+// Rules of a rider: no atomics, no waiting of one workgroup on another; it reads nothing the product writes and writes nothing
+// the product reads (gv_gemm_f32_riders / _fin refuse overlapping buffers on the host).  LDS and barriers: only inside ONE rider
+// workgroup -- the branch that selects a rider is block-uniform, so a __syncthreads() in a body is reached by all 256 threads --
+// and only through the 64 x 16 float scratch that the riders kernel hands to rider_body.
 #pragma once
 
 #include "common.h"
@@ -104,6 +109,69 @@ __device__ __forceinline__ void kl_mix_body(const float* z_pre, int k, int h, fl
     }
 }
 
+// ---- prior samples of get_mmd: z_pri[i] = mu[i % k] + eps[i] * sqrt(softplus(raw[i % k]) + 1e-8)   (z_pre = [mu; raw], (2k, h))
+__device__ __forceinline__ void prior_sample_body(const float* z_pre, const float* eps, float* out, int s, int k, int h, int bid, int nblk) {
+    const int total = s * h;
+    for (int i = bid * 256 + threadIdx.x; i < total; i += nblk * 256) {
+        const int r = i / h, c = i - r * h, j = r % k;
+        const float v = softplus_t(z_pre[(size_t)(k + j) * h + c]) + 1e-8f;
+        out[i] = z_pre[(size_t)j * h + c] + eps[i] * sqrtf(v);
+    }
+}
+
+// ---- the KL backward's finisher: column i of the slice sums -> z_pre's gradient (chained through v_j = softplus(raw) + 1e-8 in
+// the second half) or, behind the 2 k h mixture columns, the bias gradient of the layer that made h2 (no factor, no chain)
+__device__ __forceinline__ void kl_mix_final_store(float acc, int i, int kh, const float* z_pre, const float* gkl, float gscale,
+                                                   float* g_zpre, int accumulate, int64_t n, const int* rows_dev, float* g_bias,
+                                                   int accumulate_bias) {
+    if (i >= 2 * kh) {
+        g_bias[i - 2 * kh] = accumulate_bias ? g_bias[i - 2 * kh] + acc : acc;
+        return;
+    }
+    const float cg = gscale * (gkl ? *gkl : 1.f) / (float)(rows_dev ? (int64_t)*rows_dev : n);
+    if (i >= kh) {  // chain through v_j = softplus(raw) + 1e-8
+        const float raw = z_pre[i];
+        acc *= raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw));
+    }
+    g_zpre[i] = accumulate ? g_zpre[i] + cg * acc : cg * acc;
+}
+
+struct KlFinJob {
+    const float* part;     // [nsl][2 k h (+ 2 h)]
+    const float* z_pre;
+    const float* gkl;
+    float gscale;
+    float* g_zpre;
+    float* g_bias;         // or NULL
+    long long n;
+    int accumulate, accumulate_bias, h, k, nsl;
+};
+
+__device__ __forceinline__ void kl_mix_final_body(const KlFinJob& j, int bid, float (*sm)[16]) {
+    const int kh = j.k * j.h, total = 2 * kh + (j.g_bias ? 2 * j.h : 0);
+    const int i = bid * 16 + (threadIdx.x & 15);
+    const float acc = sum_slices_16x64_wg256(j.part, total, j.nsl, i, sm);
+    if ((threadIdx.x >> 4) != 0 || i >= total) return;
+    kl_mix_final_store(acc, i, kh, j.z_pre, j.gkl, j.gscale, j.g_zpre, j.accumulate, j.n, nullptr, j.g_bias, j.accumulate_bias);
+}
+
+// ---- a bias gradient from the column-sum partials of an epilogue backward: out[c] (+)= sum over the slices
+struct ColsumJob {
+    const float* part;     // [nsl][n]
+    float* out;
+    int n, nsl, accumulate;
+};
+
+__device__ __forceinline__ void colsum_final_store(float acc, int c, float* out, int accumulate) {
+    out[c] = accumulate ? out[c] + acc : acc;
+}
+
+__device__ __forceinline__ void colsum_final_body(const ColsumJob& j, int bid, float (*sm)[16]) {
+    const int c = bid * 16 + (threadIdx.x & 15);
+    const float acc = sum_slices_16x64_wg256(j.part, j.n, j.nsl, c, sm);
+    if ((threadIdx.x >> 4) == 0 && c < j.n) colsum_final_store(acc, c, j.out, j.accumulate);
+}
+
 // ---- what one launch carries: the jobs, and per rider kind the prefix of its workgroup count --------------------
 struct PackJob {
     const float* w;
@@ -119,16 +187,29 @@ struct MixJob {
     int k, h;
 };
 
+struct PriorJob {
+    const float* z_pre;
+    const float* eps;
+    float* out;
+    int s, k, h;
+};
+
 struct RiderSet {
     const uint64_t* rng_state;
     RngJobs rng;
     PackJob pack;
     MixJob mix;
-    int first[4];          // rider block b belongs to: RNG [first[0], first[1]), pack [first[1], first[2]), mix [first[2], first[3])
+    PriorJob prior;
+    KlFinJob klfin;
+    ColsumJob colsum;
+    // rider block b belongs to: RNG [first[0], first[1]), pack [first[1], first[2]), mix [first[2], first[3]), prior samples
+    // [first[3], first[4]), KL finisher [first[4], first[5]), column sums [first[5], first[6])
+    int first[7];
 };
 
-// rider block `b` of `n` (n >= first[3]: the blocks behind first[3] only pad the count and leave at once); block-uniform branches
-__device__ __forceinline__ void rider_body(const RiderSet& rs, int b, int n) {
+// rider block `b` of `n` (n >= first[6]: the blocks behind first[6] only pad the count and leave at once); block-uniform branches.
+// `sm`: the workgroup's 64 x 16 float scratch (the slice-sum finishers)
+__device__ __forceinline__ void rider_body(const RiderSet& rs, int b, int n, float (*sm)[16]) {
     (void)n;
     if (b < rs.first[1]) {
         rng_fill_body(rs.rng_state, rs.rng, b, rs.first[1]);
@@ -139,6 +220,13 @@ __device__ __forceinline__ void rider_body(const RiderSet& rs, int b, int n) {
                          second ? pj.adj2 : pj.adj, second ? i - pj.blocks : i, pj.blocks);
     } else if (b < rs.first[3]) {
         kl_mix_body(rs.mix.z_pre, rs.mix.k, rs.mix.h, rs.mix.mix, b - rs.first[2], rs.first[3] - rs.first[2]);
+    } else if (b < rs.first[4]) {
+        prior_sample_body(rs.prior.z_pre, rs.prior.eps, rs.prior.out, rs.prior.s, rs.prior.k, rs.prior.h, b - rs.first[3],
+                          rs.first[4] - rs.first[3]);
+    } else if (b < rs.first[5]) {
+        kl_mix_final_body(rs.klfin, b - rs.first[4], sm);
+    } else if (b < rs.first[6]) {
+        colsum_final_body(rs.colsum, b - rs.first[5], sm);
     }
 }
 

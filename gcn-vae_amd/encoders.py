@@ -109,7 +109,7 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         # (None + tensor, kgvae/model.py:86); None is read as "no flow term".
         return ops.kl_to_mixture(z, self.z_mean, self.z_sigma, self.z_pre.squeeze(0), self.flow_log_prob)
 
-    def _prior_draw(self, device, dtype):
+    def _prior_draw(self, device, dtype, riders=None):
         num_sample = 200
         rows = (num_sample // self.k) * self.k if num_sample // self.k > 1 else self.k
         if self.mmd_eps_override is not None:
@@ -119,7 +119,7 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         else:
             eps = torch.empty(rows, self.h_dim, device=device, dtype=dtype)
             ops.device_rng(device).fill([(eps, ops.RNG_NORMAL, 0.0, self.rng_stream_prior)])
-        return ops.prior_sample(self.z_pre.squeeze(0), eps)       # sample_gaussian(m_mix, s_mix, repeat)
+        return ops.prior_sample(self.z_pre.squeeze(0), eps, riders)       # sample_gaussian(m_mix, s_mix, repeat)
 
     def _prior_rows(self):
         num_sample = 200
@@ -264,12 +264,21 @@ class KGVAE(ops.StayOnDevice, nn.Module):
         if box2 is not None and fuse_kl and ops.FUSE_REPARAM_KL:      # the KL workspace ahead of layer 2: its mixture table depends on z_pre alone
             kl_ws = ops.KLWorkspace(self.z_pre.squeeze(0), h.shape[0])
             box2.mix = (kl_ws.z_pre, kl_ws.ws)
+        # get_mmd's prior samples (announced by the head, no flow to carry them through): they need z_pre and their noise alone,
+        # which layer 1's product drew -- layer 2's product carries the sampler, and mmd_inputs finds the samples waiting
+        # (only at a width the one-sweep MMD takes, ops.mmd_sweep_ok: there the sampler's backward is the loss head's finishing
+        # launch.  On the separate route it is a node of its own, and making that node this early moves its backward behind
+        # layer 2's: z_pre's gradient is then added up in another order -- the same sum, other roundings)
+        z_pri = None
+        if (box2 is not None and self.n_flows == 0 and self._prior_eps_next is not None and ops.rider_kind('prior')
+                and ops.MMD_FUSED and self.h_dim % 4 == 0 and self.h_dim <= 256):
+            z_pri = self._prior_draw(h.device, h.dtype, box2)
         h = self.rconv_layer_2(g, h, r, norm, sole_consumer=fuse_kl, riders=box2)
         if box2 is not None and not box2.done:
             raise RuntimeError('KGVAE.forward: layer 2 dropped its RiderBox (weight packing / KL mixture table never launched)')
         z, self.z_mean, self.z_sigma = ops.reparam(h, eps, self.z_pre.squeeze(0) if fuse_kl else None,
                                                    getattr(h, '_gv_epi_link', None) if fuse_kl else None, kl_ws)
-        self._z_pri_flowed = None
+        self._z_pri_flowed = z_pri
         if self.n_flows > 0:
             # flow_log_prob = mean over the rows that exist (a static-shape batch: the device count) of the blocks' summed log-dets
             z, self.flow_log_prob = self._apply_flows(z, want_mean=True)

@@ -58,6 +58,11 @@ SIGNATURES = {
     'gv_gemm_workspace_bytes': (_L, [_I, _I, _I, _I]),
     'gv_gemm_f32': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P]),
     'gv_gemm_f32_riders': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P]),
+    'gv_gemm_f32_riders_fin': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
+    'gv_reparam_kl_bwd_fold_sweep': (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _F, _P, _P, _L, _I, _I, _P]),
+    'gv_kl_bwd_part_offset': (_L, [_I, _I]),
+    'gv_kl_bwd_slices': (_I, []),
+    'gv_kl_bwd_mix_final': (_I, [_P, _I, _P, _P, _F, _P, _I, _P, _I, _L, _I, _I, _P]),
     'gv_gemm_f32_live_rows': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P]),
     'gv_gemm_f32_sparse': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _I, _P]),
     'gv_gemm_bf16': (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _L, _P]),

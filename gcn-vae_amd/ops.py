@@ -452,8 +452,22 @@ class live_rows:
 # Riders (csrc/k_riders.h, gv_gemm_f32_riders): the forward head's small launches whose inputs do not depend on a layer's self-loop
 # product -- the forward's random draws, layer 2's lane-packed weights, the KL mixture table -- run as extra workgroups of that
 # product's launch.  GV_GEMM_RIDERS=0: every one of them stand-alone, where it stood before.
+# The finisher kinds: the prior sampler of get_mmd on layer 2's forward product ('prior'); in the backward, on a layer's
+# dL/dx = g @ loop_weight^T, the KL backward's finishing launch ('klfin', layer 2) and the bias column sums of an epilogue
+# backward ('colsum', layer 1) -- their inputs are complete before that product and nothing reads their outputs (arena slices,
+# leaf gradients) before the optimiser.
 GEMM_RIDERS = _os.environ.get('GV_GEMM_RIDERS', '1') == '1'
-GEMM_RIDER_KINDS = set(_os.environ.get('GV_GEMM_RIDER_KINDS', 'rng,pack,mix').split(','))      # measurement: which kinds may ride
+RIDER_KINDS_ALL = ('rng', 'pack', 'mix', 'prior', 'klfin', 'colsum')
+GEMM_RIDER_KINDS = set(_os.environ.get('GV_GEMM_RIDER_KINDS', ','.join(RIDER_KINDS_ALL)).split(','))      # measurement: which kinds may ride
+
+
+def rider_kind(kind):
+    """Whether jobs of ``kind`` are handed to a RiderBox at all (off: the launch stays where it stood, nothing is deferred)."""
+    return GEMM_RIDERS and kind in GEMM_RIDER_KINDS
+
+
+def _dist_active():
+    return torch.distributed.is_available() and torch.distributed.is_initialized()
 
 
 class _Riders(_ct.Structure):
@@ -466,6 +480,16 @@ class _Riders(_ct.Structure):
                 ('mix_k', _ct.c_int32), ('mix_h', _ct.c_int32)]
 
 
+class _RidersFin(_ct.Structure):
+    """ctypes mirror of gv_riders_fin (include/gcnvae.h)."""
+    _fields_ = [('prior_z_pre', _ct.c_void_p), ('prior_eps', _ct.c_void_p), ('prior_out', _ct.c_void_p), ('kl_part', _ct.c_void_p),
+                ('kl_z_pre', _ct.c_void_p), ('kl_gkl', _ct.c_void_p), ('kl_g_zpre', _ct.c_void_p), ('kl_g_bias', _ct.c_void_p),
+                ('cs_part', _ct.c_void_p), ('cs_out', _ct.c_void_p), ('kl_n', _ct.c_int64), ('kl_gscale', _ct.c_float),
+                ('prior_s', _ct.c_int32), ('prior_k', _ct.c_int32), ('prior_h', _ct.c_int32), ('kl_slices', _ct.c_int32),
+                ('kl_h', _ct.c_int32), ('kl_k', _ct.c_int32), ('kl_accumulate', _ct.c_int32), ('kl_accumulate_bias', _ct.c_int32),
+                ('cs_n', _ct.c_int32), ('cs_slices', _ct.c_int32), ('cs_accumulate', _ct.c_int32)]
+
+
 class RiderBox:
     """Explicit hand-off of independent small jobs to the NEXT self-loop product of one layer call (KGVAE.forward ->
     RelGraphConv.forward -> _RelGraphConvBdd.forward -> _gemm_addend -> gemm(..., riders=box)): whoever holds the box either
@@ -474,16 +498,26 @@ class RiderBox:
     one of the two happened; the encoder checks it after the layer call, so a box cannot be dropped silently.
       rng  : (DeviceRNG, [(tensor, kind, drop_p, stream)]) -- already claimed (DeviceRNG.claim), at most 8 jobs ride
       pack : (weight, num_bases, blk_in, blk_out, transpose_w, packed, packed_pair or None)
-      mix  : (z_pre (2k, h) contiguous, KL workspace) -- the table at the head of the workspace"""
-    __slots__ = ('rng', 'pack', 'mix', 'done', 'rode')
+      mix  : (z_pre (2k, h) contiguous, KL workspace) -- the table at the head of the workspace
+      prior : (z_pre, eps (s, h), out) -- gv_prior_sample_fwd
+      klfin : (KL workspace, z_pre, gkl, gscale, g_zpre, accumulate, g_bias or None, accumulate_bias, n, h, k) -- the finisher of
+              gv_reparam_kl_bwd_fold_sweep's slice sums
+      colsum: (part, n, slices, out, accumulate) -- gv_colsum_finish
+    A box made in a backward pass (the last two kinds) is launched by the layer backward that made or received it."""
+    __slots__ = ('rng', 'pack', 'mix', 'prior', 'klfin', 'colsum', 'done', 'rode')
 
     def __init__(self):
-        self.rng = self.pack = self.mix = None
+        self.rng = self.pack = self.mix = self.prior = self.klfin = self.colsum = None
         self.done = False
         self.rode = ()          # the kinds that went out as riders (tests, profiles)
 
     def empty(self):
-        return self.rng is None and self.pack is None and self.mix is None
+        return all(getattr(self, k) is None for k in RIDER_KINDS_ALL)
+
+    def _kl_part(self):
+        ws, h, k = self.klfin[0], self.klfin[9], self.klfin[10]
+        l = lib.load()
+        return ws.data_ptr() + 4 * int(l.gv_kl_bwd_part_offset(h, k)), int(l.gv_kl_bwd_slices())
 
     def _launch_alone(self, kinds):
         if 'rng' in kinds and self.rng is not None:
@@ -497,22 +531,34 @@ class RiderBox:
         if 'mix' in kinds and self.mix is not None:
             z_pre, ws = self.mix
             lib.call('gv_kl_mix', ptr(z_pre), z_pre.shape[0] // 2, z_pre.shape[1], ptr(ws), lib.stream())
+        if 'prior' in kinds and self.prior is not None:
+            z_pre, eps, out = self.prior
+            lib.call('gv_prior_sample_fwd', ptr(z_pre), ptr(eps), ptr(out), eps.shape[0], z_pre.shape[0] // 2, z_pre.shape[1],
+                     lib.stream())
+        if 'klfin' in kinds and self.klfin is not None:
+            _, z_pre, gkl, gscale, gzp, acc, g_bias, acc_b, n, h, k = self.klfin
+            part, slices = self._kl_part()
+            lib.call('gv_kl_bwd_mix_final', part, slices, ptr(z_pre), ptr(gkl), float(gscale), ptr(gzp), 1 if acc else 0, ptr(g_bias),
+                     1 if acc_b else 0, n, h, k, lib.stream())
+        if 'colsum' in kinds and self.colsum is not None:
+            part, n, slices, out, acc = self.colsum
+            lib.call('gv_colsum_finish', ptr(part), n, slices, ptr(out), 1 if acc else 0, lib.stream())
 
     def flush(self):
         """Every job stand-alone, here and now."""
         if self.done:
             raise RuntimeError('RiderBox: its jobs were already launched')
-        self._launch_alone(('rng', 'pack', 'mix'))
+        self._launch_alone(RIDER_KINDS_ALL)
         self.done = True
 
     def ride(self, gemm_args):
         """Launch the product ``gemm_args`` (gv_gemm_f32's arguments without the stream) with the jobs as its riders."""
         if self.done:
             raise RuntimeError('RiderBox: its jobs were already launched')
-        ride = {k for k in ('rng', 'pack', 'mix') if getattr(self, k) is not None and k in GEMM_RIDER_KINDS}
+        ride = {k for k in RIDER_KINDS_ALL if getattr(self, k) is not None and k in GEMM_RIDER_KINDS}
         if 'rng' in ride and len(self.rng[1]) > 8:
             ride.discard('rng')
-        self._launch_alone({'rng', 'pack', 'mix'} - ride)
+        self._launch_alone(set(RIDER_KINDS_ALL) - ride)
         d = _Riders()
         if 'rng' in ride:
             rng, jobs = self.rng
@@ -526,7 +572,24 @@ class RiderBox:
         if 'mix' in ride:
             z_pre, ws = self.mix
             d.mix_z_pre, d.mix, d.mix_k, d.mix_h = z_pre.data_ptr(), ws.data_ptr(), z_pre.shape[0] // 2, z_pre.shape[1]
-        lib.call('gv_gemm_f32_riders', *gemm_args, _ct.addressof(d), lib.stream())
+        if gemm_args[1] or ride & {'prior', 'klfin', 'colsum'}:     # A @ B^T, or a finisher kind: the entry that knows them
+            f = _RidersFin()
+            if 'prior' in ride:
+                z_pre, eps, out = self.prior
+                f.prior_z_pre, f.prior_eps, f.prior_out = z_pre.data_ptr(), eps.data_ptr(), out.data_ptr()
+                f.prior_s, f.prior_k, f.prior_h = eps.shape[0], z_pre.shape[0] // 2, z_pre.shape[1]
+            if 'klfin' in ride:
+                _, z_pre, gkl, gscale, gzp, acc, g_bias, acc_b, n, h, k = self.klfin
+                f.kl_part, f.kl_slices = self._kl_part()
+                f.kl_z_pre, f.kl_gkl, f.kl_g_zpre, f.kl_g_bias = z_pre.data_ptr(), ptr(gkl), gzp.data_ptr(), ptr(g_bias)
+                f.kl_gscale, f.kl_n, f.kl_h, f.kl_k = float(gscale), n, h, k
+                f.kl_accumulate, f.kl_accumulate_bias = 1 if acc else 0, 1 if acc_b else 0
+            if 'colsum' in ride:
+                part, n, slices, out, acc = self.colsum
+                f.cs_part, f.cs_out, f.cs_n, f.cs_slices, f.cs_accumulate = part.data_ptr(), out.data_ptr(), n, slices, 1 if acc else 0
+            lib.call('gv_gemm_f32_riders_fin', *gemm_args, _ct.addressof(d), _ct.addressof(f), lib.stream())
+        else:
+            lib.call('gv_gemm_f32_riders', *gemm_args, _ct.addressof(d), lib.stream())
         self.rode = tuple(sorted(ride))
         self.done = True
 
@@ -536,7 +599,7 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, out=None, 
     """out = act(op(a') @ op(b) + bias) (+ out);  a' = a * [a_relu_mask > 0] when a mask (same layout as a) is given.
     precision None = the global GEMM_PRECISION.  b_k_chunks / c_tiles (int64 device words, ops.block_words): blocks of op(b) / tiles
     of the result known to be zero are skipped (gv_gemm_f32_sparse; fp32 only).  ``riders`` (RiderBox): its jobs ride on this
-    launch where that form exists (plain fp32 A @ B, no split-K, no zero-block words, no live-row count) and are launched
+    launch where that form exists (plain fp32 A @ B or A @ B^T, no split-K, no zero-block words, no live-row count) and are launched
     stand-alone in front of it everywhere else."""
     a, lda = _row_major(a, 'a')
     b, ldb = _row_major(b, 'b')
@@ -572,10 +635,10 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, out=None, 
     entry = 'gv_gemm_bf16' if (precision or GEMM_PRECISION) == 'bf16' else 'gv_gemm_f32'
     live = LIVE_ROWS
     if riders is not None:
-        plain = (entry == 'gv_gemm_f32' and b_k_chunks is None and c_tiles is None and not trans_a and not trans_b and split_k <= 1
+        plain = (entry == 'gv_gemm_f32' and b_k_chunks is None and c_tiles is None and not trans_a and split_k <= 1
                  and m > 0 and n > 0 and not (live is not None and a.shape[0] == live[1] and a.device == live[0].device))
         if GEMM_RIDERS and plain and not riders.empty():
-            riders.ride((0, 0, m, n, k, ptr(a), lda, ptr(b), ldb, ptr(out), out.stride(0) if m > 1 else n, ptr(bias), act,
+            riders.ride((0, 1 if trans_b else 0, m, n, k, ptr(a), lda, ptr(b), ldb, ptr(out), out.stride(0) if m > 1 else n, ptr(bias), act,
                          1 if accumulate else 0, 1, ptr(a_relu_mask), None, 0))
             return out
         riders.flush()
@@ -1935,8 +1998,9 @@ def epilogue_fwd(agg, addend, act, keep, keep_scale):
     return out
 
 
-def epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=None, colsum_accumulate=False):
-    """g = d(act/dropout epilogue); with ``colsum_out`` the same pass also yields the column sums of g (bias grad)."""
+def epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=None, colsum_accumulate=False, riders=None):
+    """g = d(act/dropout epilogue); with ``colsum_out`` the same pass also yields the column sums of g (bias grad).
+    ``riders`` (RiderBox): the finishing launch of the fused column sums is left in the box (the caller launches it)."""
     grad_out = _chk(grad_out.contiguous(), name='grad_out')
     g = torch.empty_like(grad_out)
     m, n = grad_out.shape
@@ -1944,7 +2008,9 @@ def epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=None, colsum_a
     part = torch.empty(EPILOGUE_COLSUM_SLICES * n, dtype=torch.float32, device=g.device) if fused else None
     lib.call('gv_rgcn_epilogue_bwd', ptr(out), ptr(grad_out), act, ptr(keep), float(keep_scale), ptr(g), m, n, ptr(part),
              lib.stream())
-    if fused:
+    if fused and riders is not None:
+        riders.colsum = (part, n, EPILOGUE_COLSUM_SLICES, colsum_out, bool(colsum_accumulate))
+    elif fused:
         lib.call('gv_colsum_finish', ptr(part), n, EPILOGUE_COLSUM_SLICES, ptr(colsum_out), 1 if colsum_accumulate else 0,
                  lib.stream())
     elif colsum_out is not None:
@@ -2229,13 +2295,13 @@ def embedding(table, ids, tick_rng=None, sole_consumer=False):
 
 # ---- the R-GCN layers' shared pieces: epilogue gradient, self-loop + bias addend, loop-weight and relation-weight gradients,
 # the edge norm in a launch's order, the packed bdd weights and the K1 choice of _RelGraphConvBdd
-def _epilogue_grad(out, grad_out, act, keep, keep_scale, want_bias, d_b):
+def _epilogue_grad(out, grad_out, act, keep, keep_scale, want_bias, d_b, riders=None):
     """(g, grad_bias): g = dL/d(pre-epilogue rows); with ``want_bias`` the same pass yields the bias gradient (the column sums of
     g), added into the optimiser's arena when the bias has a direct target ``d_b`` (grad_bias is then None)."""
     if not want_bias:
         return epilogue_bwd(out, grad_out, act, keep, keep_scale), None
     grad_bias = d_b if d_b is not None else torch.empty(grad_out.shape[1], dtype=torch.float32, device=grad_out.device)
-    g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None)
+    g = epilogue_bwd(out, grad_out, act, keep, keep_scale, colsum_out=grad_bias, colsum_accumulate=d_b is not None, riders=riders)
     return g, (None if d_b is not None else grad_bias)
 
 
@@ -2265,9 +2331,13 @@ def _row_addend(h_bias, loop_rows, n, out_feat):
     return addend
 
 
-def _loop_grads(x, g, loop_weight, d_l, want_loop, want_x, loop_bf=None):
+def _loop_grads(x, g, loop_weight, d_l, want_loop, want_x, loop_bf=None, riders=None):
     """(grad_loop, gx_loop) of the self-loop term x @ loop_weight: the loop weight's gradient x^T g (added into its direct target
-    ``d_l`` when there is one, grad_loop then None) and g @ loop_weight^T (on the bf16 form of ``loop_bf`` when given)."""
+    ``d_l`` when there is one, grad_loop then None) and g @ loop_weight^T (on the bf16 form of ``loop_bf`` when given).
+    ``riders`` (RiderBox): the backward's finishers ride on the fp32 dL/dx product; without one they are launched here, alone."""
+    if riders is not None and (loop_weight is None or not want_x or loop_bf is not None):
+        riders.flush()
+        riders = None
     if loop_weight is None:
         return None, None
     grad_loop = gx_loop = None
@@ -2280,7 +2350,7 @@ def _loop_grads(x, g, loop_weight, d_l, want_loop, want_x, loop_bf=None):
         if loop_bf is not None:
             gx_loop = dense_bf16(g, loop_bf[1], loop_weight.shape[0], loop_weight.shape[1])
         else:
-            gx_loop = gemm(g, loop_weight, trans_b=True)
+            gx_loop = gemm(g, loop_weight, trans_b=True, riders=riders)
     return grad_loop, gx_loop
 
 
@@ -2393,6 +2463,8 @@ class _RelGraphConvBdd(torch.autograd.Function):
                 reduce_hook, link_box=None, riders=None):
         x, _ = _row_major(x, 'x')
         n, in_feat = x.shape
+        # a caller that hands over a box runs the one-GPU dynamic-shape step: the backward's finishers may ride as well
+        ctx.bwd_riders = riders is not None and reduce_hook is None and not _dist_active()
         if riders is not None and (reduce_hook is not None or loop_weight is None):
             riders.flush()          # edge-sharded: the aggregation precedes the self-loop product; no self loop: no product
             riders = None
@@ -2446,6 +2518,7 @@ class _RelGraphConvBdd(torch.autograd.Function):
         if link_box is not None and act == ACT_NONE and reduce_hook is None:
             ctx.epi_link = link_box[0] = EpilogueLink(keep, keep_scale, h_bias is not None and ctx.needs_input_grad[2],
                                                       ctx.direct[1], out_feat)
+            ctx.epi_link.carries_fin = ctx.bwd_riders
         return out
 
     @staticmethod
@@ -2455,10 +2528,18 @@ class _RelGraphConvBdd(torch.autograd.Function):
         _verify_direct(ctx)
         d_w, d_b, d_l = ctx.direct
         folded = ctx.epi_link.take(grad_out) if ctx.epi_link is not None else None
+        # the finishers that this layer's dL/dx product carries (ops.RiderBox): the KL backward's, left on the link by the
+        # reparameterisation's backward, or this layer's own bias column sums; launched in this call either way
+        fin_box = ctx.epi_link.take_fin() if ctx.epi_link is not None else None
         if folded is not None:          # the consumer's backward wrote these rows masked and summed the bias gradient
             g, grad_bias = folded
         else:
-            g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b)
+            if fin_box is None and ctx.bwd_riders and rider_kind('colsum') and LIVE_ROWS is None and d_b is not None:
+                fin_box = RiderBox()      # (d_b: an arena slice; a buffer returned to autograd could be read before the product)
+            g, grad_bias = _epilogue_grad(out, grad_out, act, keep, keep_scale, has_bias and ctx.needs_input_grad[2], d_b, fin_box)
+        if fin_box is not None and fin_box.empty():
+            fin_box = None
+        ctx.fin_box = fin_box           # (kept for inspection)
         pending = None
         g_agg = g
         if reduce_hook is not None:      # gradient of this rank's partial aggregate = sum over ranks; overlapped below
@@ -2480,7 +2561,9 @@ class _RelGraphConvBdd(torch.autograd.Function):
         # slices, which no other node of the pass writes -- a wait here serialises the flows' weight-gradient products with the
         # R-GCN backward: WN18RR + 3 IAF 4.9 -> 5.2 ms when it was tried)
         grad_loop, gx_loop = _loop_grads(x, g, loop_weight, d_l, ctx.needs_input_grad[3] and not side_w, ctx.needs_input_grad[0],
-                                         ctx.loop_bf)
+                                         ctx.loop_bf, fin_box)
+        if fin_box is not None and not fin_box.done:
+            raise RuntimeError('_RelGraphConvBdd.backward: the finishers\' RiderBox was dropped (a gradient was never finished)')
         if pending is not None:
             pending.wait()
         grad_x = None
@@ -3257,7 +3340,8 @@ class EpilogueLink:
     reparameterisation's backward may then write dL/dh2 already masked and sum the bias gradient in the same sweep
     (gv_reparam_kl_bwd_fold).  It records the buffer it returned in ``buf``; the layer's backward skips its own epilogue
     gradient only for that very buffer."""
-    __slots__ = ('keep', 'keep_scale', 'want_bias', 'bias_target', 'n_bias', '_gv_direct_epoch', 'buf', 'buf_version', 'grad_bias')
+    __slots__ = ('keep', 'keep_scale', 'want_bias', 'bias_target', 'n_bias', '_gv_direct_epoch', 'buf', 'buf_version', 'grad_bias',
+                 'carries_fin', 'fin')
 
     def __init__(self, keep, keep_scale, want_bias, bias_target, n_bias):
         self.keep, self.keep_scale = keep, float(keep_scale)
@@ -3265,6 +3349,12 @@ class EpilogueLink:
         _stamp_direct(self)               # bias_target is a slice of the optimiser arena as it stood in the layer's forward
         self.buf = self.grad_bias = None
         self.buf_version = 0
+        # carries_fin: the layer promises that its backward launches a RiderBox left in ``fin`` (the KL backward's finisher)
+        self.carries_fin, self.fin = False, None
+
+    def take_fin(self):
+        box, self.fin = self.fin, None
+        return box
 
     def record(self, buf, grad_bias):
         self.buf, self.buf_version, self.grad_bias = buf, buf._version, grad_bias
@@ -3357,10 +3447,22 @@ class _Reparam(torch.autograd.Function):
                     if d_b is not None:
                         _verify_direct(epi)                # the arena slice resolved in the LAYER's forward
                     g_bias = d_b if d_b is not None else torch.empty(2 * h, dtype=torch.float32, device=h2.device)
-                lib.call('gv_reparam_kl_bwd_fold', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp), ptr(link.gkl),
-                         float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), 1 if d_zp is not None else 0,
-                         ptr(epi.keep), epi.keep_scale, ptr(g_bias), 1 if d_b is not None else 0, ptr(link.ws), n, h, k,
-                         lib.stream())
+                # the finishing launch (z_pre's gradient, the bias sums) rides on the layer's dL/dx product, which is next on this
+                # stream -- when its outputs are arena slices, which nothing reads before the optimiser (a buffer returned to
+                # autograd may be added to another gradient of z_pre at once)
+                if (epi.carries_fin and epi.fin is None and rider_kind('klfin') and LIVE_ROWS is None and d_zp is not None
+                        and (g_bias is None or d_b is not None)):
+                    lib.call('gv_reparam_kl_bwd_fold_sweep', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp),
+                             ptr(link.gkl), float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), ptr(epi.keep),
+                             epi.keep_scale, ptr(g_bias), ptr(link.ws), n, h, k, lib.stream())
+                    epi.fin = RiderBox()
+                    epi.fin.klfin = (link.ws, z_pre, link.gkl, float(link.gscale), gzp, d_zp is not None, g_bias, d_b is not None,
+                                     n, h, k)
+                else:
+                    lib.call('gv_reparam_kl_bwd_fold', ptr(z), ptr(h2), ptr(v), ptr(eps), ptr(z_pre), ptr(link.resp), ptr(link.gkl),
+                             float(link.gscale), float(link.z_extra), ptr(gz), ptr(gh2), ptr(gzp), 1 if d_zp is not None else 0,
+                             ptr(epi.keep), epi.keep_scale, ptr(g_bias), 1 if d_b is not None else 0, ptr(link.ws), n, h, k,
+                             lib.stream())
                 link.gkl = None
                 epi.record(gh2, None if d_b is not None else g_bias)
                 return gh2, None, (None if d_zp is not None else gzp), None, None, None
@@ -3853,12 +3955,15 @@ class _PriorSample(torch.autograd.Function):
     """z_pri = cat([m]*repeat) + eps * cat([sqrt(softplus(raw)+1e-8)]*repeat) for z_pre = [m; raw] (2k, h)."""
 
     @staticmethod
-    def forward(ctx, z_pre, eps, link_box=None):
+    def forward(ctx, z_pre, eps, link_box=None, riders=None):
         z_pre, eps = _chk(z_pre.contiguous(), name='z_pre'), _chk(eps.contiguous(), name='eps')
         k, h = z_pre.shape[0] // 2, z_pre.shape[1]
         out = torch.empty_like(eps)
         ctx.set_materialize_grads(False)
-        lib.call('gv_prior_sample_fwd', ptr(z_pre), ptr(eps), ptr(out), eps.shape[0], k, h, lib.stream())
+        if riders is not None and riders.prior is None and not riders.done and rider_kind('prior'):
+            riders.prior = (z_pre, eps, out)          # the box's product carries the launch (eps is complete on this stream)
+        else:
+            lib.call('gv_prior_sample_fwd', ptr(z_pre), ptr(eps), ptr(out), eps.shape[0], k, h, lib.stream())
         ctx.save_for_backward(z_pre, eps)
         ctx.link = None
         if link_box is not None and eps.shape[0] % k == 0:
@@ -3872,23 +3977,24 @@ class _PriorSample(torch.autograd.Function):
         if link is not None and link.claimed:
             folded = link.take(g)
             if folded is not None:
-                return folded[0], None, None
+                return folded[0], None, None, None
         if g is None:
-            return None, None, None
+            return None, None, None, None
         g = _chk(g.contiguous(), name='g')
         d_zp = _direct_flat(z_pre)
         gz = d_zp if d_zp is not None else torch.empty_like(z_pre)
         lib.call('gv_prior_sample_bwd', ptr(z_pre), ptr(eps), ptr(g), ptr(gz), 1 if d_zp is not None else 0, eps.shape[0],
                  z_pre.shape[0] // 2, z_pre.shape[1], lib.stream())
-        return (None if d_zp is not None else gz), None, None
+        return (None if d_zp is not None else gz), None, None, None
 
 
-def prior_sample(z_pre, eps):
-    """The returned z_pri carries the hand-off to a loss head on the one-sweep MMD route (``z_pri._gv_prior_link``)."""
+def prior_sample(z_pre, eps, riders=None):
+    """The returned z_pri carries the hand-off to a loss head on the one-sweep MMD route (``z_pri._gv_prior_link``).
+    ``riders`` (RiderBox): a box whose product is launched later on this stream and before anything reads z_pri carries the launch."""
     if not MMD_FUSED:
-        return _PriorSample.apply(z_pre, eps)
+        return _PriorSample.apply(z_pre, eps, None, riders)
     box = [None]
-    out = _PriorSample.apply(z_pre, eps, box)
+    out = _PriorSample.apply(z_pre, eps, box, riders)
     out._gv_prior_link = box[0]
     return out
 

@@ -1073,6 +1073,36 @@ typedef struct gv_riders {
 int gv_gemm_f32_riders(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* c,
                        int ldc, const float* bias, int act, int accumulate, int split_k, const float* a_relu_mask, void* workspace,
                        int64_t workspace_bytes, const gv_riders* riders, void* stream);
+/* ... with the FINISHER kinds as well, on A @ B or on A @ B^T (trans_b = 1: the backward's dL/dx = g @ loop_weight^T): launches
+ * whose inputs are complete before this call on this stream and whose outputs nothing reads before a later launch.  A rider
+ * workgroup has 256 threads; the two slice sums form the 64 slice-group sums of their 1024-thread stand-alone kernels with the
+ * same function and add them in the same order, so every output carries the stand-alone launch's bits.  Unused kinds stay zero
+ * (prior_z_pre = NULL, kl_part = NULL, cs_part = NULL); `riders` may be NULL.  Overlaps are refused as above -- also between two
+ * finishers' outputs, and between the prior sampler's buffers and an rng job of the same launch.
+ *   prior_* : prior_out <- gv_prior_sample_fwd(prior_z_pre, prior_eps, s, k, h);
+ *   kl_*    : gv_kl_bwd_mix_final(kl_part, kl_slices, ...): z_pre's gradient and, with kl_g_bias, the 2 h bias sums;
+ *   cs_*    : gv_colsum_finish(cs_part, cs_n, cs_slices, cs_out, cs_accumulate). */
+typedef struct gv_riders_fin {
+    const float* prior_z_pre;
+    const float* prior_eps;
+    float* prior_out;
+    const float* kl_part;
+    const float* kl_z_pre;
+    const float* kl_gkl;
+    float* kl_g_zpre;
+    float* kl_g_bias;
+    const float* cs_part;
+    float* cs_out;
+    int64_t kl_n;
+    float kl_gscale;
+    int32_t prior_s, prior_k, prior_h;
+    int32_t kl_slices, kl_h, kl_k, kl_accumulate, kl_accumulate_bias;
+    int32_t cs_n, cs_slices, cs_accumulate;
+} gv_riders_fin;
+int gv_gemm_f32_riders_fin(int trans_a, int trans_b, int m, int n, int k, const float* a, int lda, const float* b, int ldb, float* c,
+                           int ldc, const float* bias, int act, int accumulate, int split_k, const float* a_relu_mask,
+                           void* workspace, int64_t workspace_bytes, const gv_riders* riders, const gv_riders_fin* fin,
+                           void* stream);
 /* ... for a STATIC-SHAPE batch whose node arrays are padded: only the first *rows_dev (device int32) rows of the stored A exist.
  * Row-major A (trans_a == 0): 64-row tiles of padding rows are not computed, their C rows receive ZEROS (nothing when
  * accumulating); A stored [K, M] (trans_a != 0): the reduction ends at row *rows_dev.  The padding rows of A must be finite. */
@@ -1245,6 +1275,17 @@ int gv_reparam_kl_bwd_fold(const float* z, const float* h2, const float* v, cons
                            const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up, float* gh2,
                            float* g_zpre, int accumulate_zpre, const uint8_t* keep, float keep_scale, float* g_bias,
                            int accumulate_bias, float* workspace, int64_t n, int h, int k, void* stream);
+/* gv_reparam_kl_bwd_fold in two parts: the sweep (gh2, and the slice sums left in the workspace: gv_kl_bwd_slices() slices of
+ * (2 k + 2) h columns -- 2 k h without g_bias -- from float gv_kl_bwd_part_offset(h, k) on; g_zpre / g_bias only say what the
+ * finisher will be asked for) and the finisher, which is either this launch or the kl_* rider of gv_gemm_f32_riders_fin. */
+int gv_reparam_kl_bwd_fold_sweep(const float* z, const float* h2, const float* v, const float* eps, const float* z_pre,
+                                 const float* resp, const float* gkl, float gscale, float z_extra, const float* gz_up, float* gh2,
+                                 float* g_zpre, const uint8_t* keep, float keep_scale, float* g_bias, float* workspace, int64_t n,
+                                 int h, int k, void* stream);
+int64_t gv_kl_bwd_part_offset(int h, int k);
+int gv_kl_bwd_slices(void);
+int gv_kl_bwd_mix_final(const float* part, int n_slices, const float* z_pre, const float* gkl, float gscale, float* g_zpre,
+                        int accumulate_zpre, float* g_bias, int accumulate_bias, int64_t n, int h, int k, void* stream);
 int gv_loss_combine_fold(const float* ws_pred, int64_t t, const float* w_rel, int64_t n_embed, int64_t n_wrel,
                          const float* ws_kl, int64_t n_nodes, int h, int k, const float* ws_mmd, int sx, int sy, float reg_w,
                          float kl_w, float mmd_w, float* scal /* 4 floats, optional */, float* loss, void* stream);
