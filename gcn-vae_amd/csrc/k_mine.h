@@ -79,7 +79,8 @@ struct MineTyped {
     int n_filt_ent;
 };
 
-// ---- selection state PER RELATION (gv_mine_scores_by_relation, gv_mine_scores_typed_by_relation) ------------------------------------
+// ---- selection state PER RELATION (gv_mine_scores_by_relation, gv_mine_scores_typed_by_relation and their TransE twins
+// gv_transe_mine_by_relation, gv_transe_mine_typed_by_relation in k_transe_mine.hip) ------------------------------------------------
 // A slot i is one relation rels[i] with its own threshold, prefix, counter, histogram and output segment; the pass's MineSelect
 // carries what the slots share (sizes, level, the filter, the bases of out / counter / hist).  An id outside [0, num_rels): the slot
 // is empty this pass.
@@ -140,6 +141,11 @@ int mine_slots_args(const MineCall& c, const int32_t* rels, int m, const uint32_
 // counter or the histogram cleared, *grid = (object tiles, subject tiles, relation spans).  GV_OK: launch, unless n == 0 (nothing
 // was queued, nothing is to be done).
 int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid);
+
+// What the whole-graph by-relation entries (gv_mine_scores_by_relation, gv_transe_mine_by_relation) do before their launch, after
+// mine_select_args and mine_slots_args, n > 0: mine_prepare's geometry over the m SLOTS (sel->rel_span slots per blockIdx.z), the
+// filter re-bucketed, the m counters (EMIT) or the m << bin_bits histogram words (HIST) cleared.
+int mine_slots_prepare(const MineCall& c, int m, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid);
 
 // one sweep's launch: the kernel's dynamic-LDS limit raised to lds_max once per device (one flag per kernel instantiation)
 template <auto KERNEL, class Params>

@@ -474,6 +474,11 @@ int mine_prepare(const MineCall& c, void* workspace, int64_t workspace_bytes, Mi
     return rc != GV_OK ? rc : mine_clear(c);
 }
 
+int mine_slots_prepare(const MineCall& c, int m, void* workspace, int64_t workspace_bytes, MineSelect* sel, dim3* grid) {
+    const int rc = mine_sweep_prepare(c, m, workspace, workspace_bytes, sel, grid);
+    return rc != GV_OK ? rc : mine_clear(c, m);
+}
+
 int mine_slots_args(const MineCall& c, const int32_t* rels, int m, const uint32_t* key_min, const uint32_t* prefix,
                     const int64_t* out_base, int max_bin_bits, MineSlots* sl) {
     GV_REQUIRE(m >= 1 && m <= c.num_rels, GV_ERR_SHAPE, "%s: m=%d slots outside [1, num_rels=%d]", c.who, m, c.num_rels);
@@ -919,8 +924,7 @@ extern "C" int gv_mine_scores_by_relation(const float* e, int ld_e, const float*
     if (rc == GV_OK) rc = mine_select_args(c, &rp.p.sel);
     if (rc == GV_OK) rc = mine_slots_args(c, rels, m, key_min, prefix, out_base, MINE_SLOT_HIST_BITS, &rp.sl);
     if (rc != GV_OK || n == 0) return rc;
-    rc = mine_sweep_prepare(c, m, workspace, workspace_bytes, &rp.p.sel, &grid);
-    if (rc == GV_OK) rc = mine_clear(c, m);
+    rc = mine_slots_prepare(c, m, workspace, workspace_bytes, &rp.p.sel, &grid);
     if (rc != GV_OK) return rc;
     const int lds = (2 * 64 * (rp.p.kc + 4) + 2 * (rp.p.kc + 4)) * (int)sizeof(float);
     const int lds_max = (2 * 64 * (MINE_KC_MAX + 4) + 2 * (MINE_KC_MAX + 4)) * (int)sizeof(float);

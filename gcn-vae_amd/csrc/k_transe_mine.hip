@@ -222,6 +222,114 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine(const TeMineParams p
     }
 }
 
+// ---- the whole-graph sweep with selection state per relation (gv_transe_mine_by_relation) -------------------------------------------
+// k_transe_mine's loop order, staging and arithmetic over the SLOTS' relations (k_mine.h: MineSlots): a workgroup owns its tile pair
+// and the slots [blockIdx.z * rel_span, + rel_span), whose LIVE ones its four groups take in turn, four a round; an empty slot costs
+// one scalar load, so a subset of the relations costs its share of a sweep.  Four slots are in flight at once, so everything a slot
+// owns is the GROUP's: the select narrowed to the slot (mine_slot_select; all four waves of a group read the same slot, the values
+// stay wave-uniform), the early-exit bound taken from THAT select every round -- the slots' prefixes and thresholds differ, and a
+// bound shared between them would let the partial sums of the relation with the larger distances leave the column loop early and be
+// counted in the wrong bins --, and one 256-bin LDS histogram per group (levels 8 + 8 + 8 + 8).  A group's histogram is complete at
+// the next round's first barrier and is flushed into its slot's global histogram right behind it (mine_hist_flush_clear), two
+// barriers before the group counts into it again; the last one is flushed behind the barrier after the loop.  No barrier is added
+// to k_transe_mine's.
+struct TeMineRelParams {
+    TeMineParams p;
+    MineSlots sl;
+};
+
+template <int P, bool HIST>
+__global__ __launch_bounds__(TM_THREADS) void k_transe_mine_rel(const TeMineRelParams rp) {
+    extern __shared__ __attribute__((aligned(16))) float tm_smem[];
+    __shared__ unsigned long long fmask[TM_GROUPS][64];  // a group's relation: its listed objects per subject row
+    __shared__ int fany[TM_GROUPS];
+    __shared__ unsigned flist[MINE_FL_CAP];
+    __shared__ unsigned hist_s[HIST ? TM_GROUPS : 1][HIST ? (1 << MINE_SLOT_HIST_BITS) : 1];
+    const TeMineParams& p = rp.p;
+    const MineSlots& sl = rp.sl;
+    const int kc = p.kc;
+    float* As = tm_smem;                                 // [kc][TM_LD] subjects
+    float* Bs = As + kc * TM_LD;                         // [kc][TM_LD] objects
+    const int t = threadIdx.x, tl = t & 255, lane = t & 63, tx = tl & 15, ty = tl >> 4;
+    const int g = (int)mine_uniform((unsigned)(t >> 8));
+    float* Rs = Bs + kc * TM_LD + g * kc;                // [TM_GROUPS][kc] each group's relation row
+    unsigned* const hist_g = hist_s[HIST ? g : 0];       // and its histogram
+    const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+    const MineSelect& pass = p.sel;
+    const int n = pass.n;
+    const int i0 = blockIdx.z * pass.rel_span, i1 = min(i0 + pass.rel_span, sl.m);
+    const bool resident = p.n_chunks == 1;
+    const bool diag = pass.exclude_self && m0 == n0;
+    const auto s_row = [=](int rl) { return m0 + rl; };
+    const auto o_row = [=](int cl) { return n0 + cl; };
+    const auto live_from = [&](int i) {                  // the first live slot at or after i, i1 when there is none (uniform)
+        while (i < i1 && mine_slot_relation(sl, i, pass.num_rels) < 0) ++i;
+        return i;
+    };
+
+    int i = live_from(i0);
+    if (i >= i1) return;                                 // uniform: no live slot in this span
+    int f_base, f_cnt;
+    mine_filter_load(pass.tile_ptr, pass.tile_ent, blockIdx.y * gridDim.x + blockIdx.x, flist, tl, &f_base, &f_cnt);   // every group: the same words
+    if (HIST) hist_g[tl] = 0u;                           // 256 threads a group, 256 bins
+    if (resident) {
+        tm_stage_rows(As, p.en, s_row, n, p.dim, 0, p.dim, t, TM_THREADS);
+        tm_stage_rows(Bs, p.en, o_row, n, p.dim, 0, p.dim, t, TM_THREADS);
+    }
+    const float* a_ptr = As + 4 * ty;
+    const float* b_ptr = Bs + 4 * tx;
+
+    int before = -1;                                     // the slot whose histogram waits in hist_s[g]
+    while (i < i1) {
+        int mine = -1;                                   // this round's live slots, one a group; every group makes every round's barriers
+        for (int j = 0; j < TM_GROUPS && i < i1; ++j) {
+            if (j == g) mine = i;
+            i = live_from(i + 1);
+        }
+        const int r = mine_slot_relation(sl, mine, pass.num_rels);
+        const bool live = r >= 0;
+        const MineSelect sel = mine_slot_select<HIST>(pass, sl, live ? mine : i0);     // a group without a slot reads a valid one and uses nothing of it
+        const float bound = tm_bound<P, HIST>(sel);      // the slot's own: never the pass's
+        __syncthreads();                                 // the last round's reads of Rs and fmask and its counts into hist_s are over
+        if (HIST && before >= 0)
+            mine_hist_flush_clear(hist_g, pass.hist + ((size_t)before << pass.bin_bits), pass.bin_bits, tl);
+        if (tl < 64) fmask[g][tl] = 0ull;
+        if (tl == 64) fany[g] = 0;
+        if (resident && live)
+            for (int k = tl; k < p.dim; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k];
+        __syncthreads();
+        if (live) mine_filter_relation(flist, pass.tile_ent, f_base, f_cnt, r, tl, fmask[g], &fany[g]);
+
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        bool past = !live;                               // wave-uniform: every pair of the wave is beyond the slot's bound
+        for (int c = 0; c < p.n_chunks; ++c) {
+            const int k0 = c * kc, kn = min(kc, p.dim - k0);
+            if (!resident) {
+                __syncthreads();
+                tm_stage_rows(As, p.en, s_row, n, p.dim, k0, kn, t, TM_THREADS);
+                tm_stage_rows(Bs, p.en, o_row, n, p.dim, k0, kn, t, TM_THREADS);
+                if (live)
+                    for (int k = tl; k < kn; k += 256) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
+                __syncthreads();
+            }
+            tm_columns<P>(acc, a_ptr, b_ptr, Rs, kn, bound, past);
+        }
+        __syncthreads();                                 // fmask / fany of this round are complete
+
+        tm_epilogue<P, HIST>(acc, live, diag, tx, ty, lane, [&](int rl, int cl) { return make_int2(s_row(rl), o_row(cl)); }, r,
+                             fany[g] != 0, fmask[g], hist_g, sel);
+        before = live ? mine : -1;
+    }
+    if (HIST) {
+        __syncthreads();
+        if (before >= 0) mine_hist_flush_clear(hist_g, pass.hist + ((size_t)before << pass.bin_bits), pass.bin_bits, tl);
+    }
+}
+
 // ---- the type-constrained sweep (gv_transe_mine_typed) -----------------------------------------------------------------------------
 // Loop order, transposed (k_mine.h): a workgroup owns one unit = (relation r, one 64-row tile of r's subject members, a span of
 // 64-row tiles of r's object members), rows gathered through the member ids.  No second relation can reuse an object tile (its rows
@@ -299,6 +407,79 @@ __global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed(const TeMineTy
     }
 }
 
+// ---- the type-constrained sweep with selection state per relation (gv_transe_mine_typed_by_relation) -------------------------------
+// k_transe_mine_typed, a unit's first word being the SLOT whose relation it walks (as k_mine_typed_rel, k_mine.hip): the workgroup
+// owns one relation already, so the selection is narrowed to the slot once (mine_slot_select), the bound comes from that select, and
+// the 4 096-bin LDS histogram, its 12 + 10 + 10 levels and its one flush stay k_transe_mine_typed's; only their destination is the
+// slot's.
+struct TeMineTypedRelParams {
+    TeMineParams p;
+    MineTyped ty;
+    MineSlots sl;
+};
+
+template <int P, bool HIST>
+__global__ __launch_bounds__(TM_THREADS) void k_transe_mine_typed_rel(const TeMineTypedRelParams tp) {
+    extern __shared__ __attribute__((aligned(16))) float tm_smem[];
+    __shared__ unsigned long long fmask[TM_GROUPS][64];  // a group's object tile: its listed objects per subject row
+    __shared__ int sid_s[64], oid_s[TM_GROUPS][64];      // the tiles' entity ids, -1 past the lists
+    __shared__ unsigned hist_s[HIST ? (1 << MINE_HIST_BITS) : 1];
+    const TeMineParams& p = tp.p;
+    const MineTyped& ty = tp.ty;
+    const int kc = p.kc;
+    const int t = threadIdx.x, g = t >> 8, tl = t & 255, lane = t & 63, tx = tl & 15, ty4 = tl >> 4;
+    float* As = tm_smem;                                 // [kc][TM_LD] subjects
+    float* Bs = As + (1 + g) * kc * TM_LD;               // [TM_GROUPS][kc][TM_LD] each group's objects
+    float* Rs = As + (1 + TM_GROUPS) * kc * TM_LD;       // [kc] the relation's row
+    const int4 unit = ty.units[blockIdx.x];
+    const int slot = (int)mine_uniform((unsigned)unit.x);
+    const int r = mine_slot_relation(tp.sl, slot, p.sel.num_rels);
+    if (r < 0) return;                                   // uniform: not a unit, or an empty slot
+    const MineSelect sel = mine_slot_select<HIST>(p.sel, tp.sl, slot);
+    const float bound = tm_bound<P, HIST>(sel);          // the slot's
+
+    mine_typed_ids(ty, sel.num_rels + r, unit.y, sel.n, t, sid_s);
+    if (HIST)
+        for (int i = t; i < (1 << MINE_HIST_BITS); i += TM_THREADS) hist_s[i] = 0u;
+    const float* a_ptr = As + 4 * ty4;
+    const float* b_ptr = Bs + 4 * tx;
+
+    // group g takes object tiles unit.z + g, unit.z + g + TM_GROUPS, ...; every group makes every round's barriers
+    for (int ob = unit.z; ob < unit.w; ob += TM_GROUPS) {
+        const int ot = ob + g;
+        const bool live = ot < unit.w;
+        __syncthreads();                                 // the last round's reads of oid_s and fmask are over; sid_s is there
+        mine_typed_ids(ty, r, live ? ot : -1, sel.n, tl, oid_s[g]);
+        if (tl < 64) fmask[g][tl] = 0ull;
+        __syncthreads();
+        if (live) mine_typed_filter(ty, sel.num_rels, r, sid_s, oid_s[g], tl, fmask[g]);
+
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        bool past = !live;                               // wave-uniform: every pair of the wave is beyond the bound
+        for (int k0 = 0; k0 < p.dim; k0 += kc) {
+            const int kn = min(kc, p.dim - k0);
+            if (__syncthreads_and(past)) break;          // the last chunk's reads are over; nothing left to look at: uniform
+            tm_stage_rows(As, p.en, [&](int row) { return sid_s[row]; }, sel.n, p.dim, k0, kn, t, TM_THREADS);
+            if (live) tm_stage_rows(Bs, p.en, [&](int row) { return oid_s[g][row]; }, sel.n, p.dim, k0, kn, tl, 256);
+            for (int k = t; k < kn; k += TM_THREADS) Rs[k] = p.rn[(size_t)r * p.dim + k0 + k];
+            __syncthreads();
+            tm_columns<P>(acc, a_ptr, b_ptr, Rs, kn, bound, past);
+        }
+        __syncthreads();                                 // fmask of this round is complete
+
+        tm_epilogue<P, HIST>(acc, live, sel.exclude_self != 0, tx, ty4, lane,
+                             [&](int rl, int cl) { return make_int2(sid_s[rl], oid_s[g][cl]); }, r, true, fmask[g], hist_s, sel);
+    }
+    if (HIST) {
+        __syncthreads();
+        if (t < 256) mine_hist_flush(hist_s, sel, t);
+    }
+}
+
 // What both entries check of their tables and the norm; then *p filled but for the selection, in chunks of at most kc_max columns.
 static int tm_params(const char* who, const float* en, const float* rn, int n, int dim, int p_norm, int kc_max, TeMineParams* p) {
     GV_REQUIRE(dim >= 1 && dim <= GV_TRANSE_MAX_DIM && (p_norm == 1 || p_norm == 2), GV_ERR_SHAPE, "%s: dim=%d (1..%d) p_norm=%d (1 or 2)",
@@ -358,4 +539,54 @@ extern "C" int gv_transe_mine_typed(const float* en, const float* rn, int n, int
                            : mine_launch<k_transe_mine_typed<2, false>>(tp, grid, TM_THREADS, lds, lds_max, c);
     return p_norm == 1 ? mine_launch<k_transe_mine_typed<1, true>>(tp, grid, TM_THREADS, lds, lds_max, c)
                        : mine_launch<k_transe_mine_typed<2, true>>(tp, grid, TM_THREADS, lds, lds_max, c);
+}
+
+extern "C" int gv_transe_mine_by_relation(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm,
+                                          const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                          int exclude_self, int mode, const int32_t* rels, int m, const uint32_t* key_min,
+                                          int prefix_bits, const uint32_t* prefix, int bin_bits, int32_t* out, int64_t capacity,
+                                          const int64_t* out_base, uint64_t* counter, uint64_t* hist, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    const MineCall c{"gv_transe_mine_by_relation", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, 0u,
+                     prefix_bits, 0u, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
+    TeMineRelParams rp{};
+    dim3 grid;
+    int rc = tm_params(c.who, en, rn, n, dim, p_norm, TM_KC_MAX, &rp.p);
+    if (rc == GV_OK) rc = mine_select_args(c, &rp.p.sel);
+    if (rc == GV_OK) rc = mine_slots_args(c, rels, m, key_min, prefix, out_base, MINE_SLOT_HIST_BITS, &rp.sl);
+    if (rc != GV_OK || n == 0) return rc;
+    rc = mine_slots_prepare(c, m, workspace, workspace_bytes, &rp.p.sel, &grid);
+    if (rc != GV_OK) return rc;
+    const int lds = (2 * TM_LD + TM_GROUPS) * rp.p.kc * (int)sizeof(float);
+    const int lds_max = (2 * TM_LD + TM_GROUPS) * TM_KC_MAX * (int)sizeof(float);
+    if (mode == GV_MINE_EMIT)
+        return p_norm == 1 ? mine_launch<k_transe_mine_rel<1, false>>(rp, grid, TM_THREADS, lds, lds_max, c)
+                           : mine_launch<k_transe_mine_rel<2, false>>(rp, grid, TM_THREADS, lds, lds_max, c);
+    return p_norm == 1 ? mine_launch<k_transe_mine_rel<1, true>>(rp, grid, TM_THREADS, lds, lds_max, c)
+                       : mine_launch<k_transe_mine_rel<2, true>>(rp, grid, TM_THREADS, lds, lds_max, c);
+}
+
+extern "C" int gv_transe_mine_typed_by_relation(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm,
+                                                const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                                                const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                                int exclude_self, int mode, const int32_t* rels, int m, const uint32_t* key_min,
+                                                int prefix_bits, const uint32_t* prefix, int bin_bits, int32_t* out, int64_t capacity,
+                                                const int64_t* out_base, uint64_t* counter, uint64_t* hist, void* stream) {
+    const MineCall c{"gv_transe_mine_typed_by_relation", n, num_rels, filt_lo, filt_hi, filt_ent, n_filt_ent, exclude_self, mode, 0u,
+                     prefix_bits, 0u, bin_bits, out, capacity, counter, hist, (hipStream_t)stream};
+    TeMineTypedRelParams tp{};
+    MineSelect checked;
+    int rc = tm_params(c.who, en, rn, n, dim, p_norm, TMT_KC, &tp.p);
+    if (rc == GV_OK) rc = mine_select_args(c, &checked);
+    if (rc == GV_OK) rc = mine_slots_args(c, rels, m, key_min, prefix, out_base, MINE_HIST_BITS, &tp.sl);
+    if (rc == GV_OK) rc = mine_typed_prepare(c, set_ptr, set_ids, units, n_units, &tp.p.sel, &tp.ty, m);
+    if (rc != GV_OK || n == 0 || n_units == 0) return rc;
+    const int lds = ((1 + TM_GROUPS) * TM_LD + 1) * tp.p.kc * (int)sizeof(float);
+    const int lds_max = ((1 + TM_GROUPS) * TM_LD + 1) * TMT_KC * (int)sizeof(float);
+    const dim3 grid((unsigned)n_units);
+    if (mode == GV_MINE_EMIT)
+        return p_norm == 1 ? mine_launch<k_transe_mine_typed_rel<1, false>>(tp, grid, TM_THREADS, lds, lds_max, c)
+                           : mine_launch<k_transe_mine_typed_rel<2, false>>(tp, grid, TM_THREADS, lds, lds_max, c);
+    return p_norm == 1 ? mine_launch<k_transe_mine_typed_rel<1, true>>(tp, grid, TM_THREADS, lds, lds_max, c)
+                       : mine_launch<k_transe_mine_typed_rel<2, true>>(tp, grid, TM_THREADS, lds, lds_max, c);
 }

@@ -177,6 +177,10 @@ SIGNATURES = {
                             _P, _L, _P]),
     'gv_transe_mine_typed': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, ctypes.c_uint32,
                                   _I, _P, _L, _P, _P, _P]),
+    'gv_transe_mine_by_relation': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _L, _P, _P, _P,
+                                        _P, _L, _P]),
+    'gv_transe_mine_typed_by_relation': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I,
+                                              _P, _L, _P, _P, _P, _P]),
     'gv_colsum': (_I, [_P, _P, _L, _I, _I, _P, _P, _I, _P]),
     'gv_gather_rows': (_I, [_P, _P, _P, _L, _I, _P]),
     'gv_gather_rows_rng_tick': (_I, [_P, _P, _P, _L, _I, _P, _P]),

@@ -1770,22 +1770,24 @@ def _relation_args(k, m, max_results):
     return k, max_results, max_results // m
 
 
-def _relation_overflow(rel, count, share, m, k):
+def _relation_overflow(rel, count, share, m, k, ascending=False):
+    edge_of = 'at or below the K-th distance' if ascending else 'at or above the K-th logit'
     return MineOverflow(count, share, f'relation {rel} (one of {m}, each with an equal share of max_results), top-{k}: the candidates '
-                                      f'at or above the K-th logit')
+                                      f'{edge_of}')
 
 
-def relation_select(slot, s, o, logits, rels, k, n, share):
+def relation_select(slot, s, o, logits, rels, k, n, share, ascending=False):
     """The top-K end of every per-relation route: from candidates ``(slot, s, o, logit)`` that include, for every slot i < m (the
     relation ``rels[i]``), everything at or above its K-th logit, the first K of each slot in ``mine_order``'s order restricted to
     it -- logit descending (-0 as +0), then (s, o) ascending -- as ``(subj int64 (m, k), obj int64 (m, k), logits float32 (m, k),
     count int64 [m])``, short rows padded with -1 / -1 / -inf; ``count[i]`` is the number of slot i's candidates at or above its
     K-th logit's exact value (all of them when it has fewer than K).  A count above ``share`` raises ``MineOverflow`` naming the
-    relation.  Any device."""
+    relation.  ``ascending``: the values are distances (the TransE routes) -- smallest first, then (s, o); padding -1 / -1 / +inf;
+    ``count[i]`` the candidates at or below the K-th distance's exact value, and the overflow says so.  Any device."""
     m, dev = rels.numel(), logits.device
     logits = logits.to(torch.float32) + 0.0
     order = torch.argsort(s * max(n, 1) + o, stable=True)
-    order = order[torch.argsort(logits[order], descending=True, stable=True)]
+    order = order[torch.argsort(logits[order], descending=not ascending, stable=True)]
     order = order[torch.argsort(slot[order], stable=True)]
     slot, s, o, logits = slot[order], s[order], o[order], logits[order]
     sizes = torch.bincount(slot, minlength=m)
@@ -1793,19 +1795,20 @@ def relation_select(slot, s, o, logits, rels, k, n, share):
     rank = torch.arange(slot.numel(), device=dev) - start[slot]
     subj = torch.full((m, k), -1, dtype=torch.int64, device=dev)
     obj = torch.full((m, k), -1, dtype=torch.int64, device=dev)
-    best = torch.full((m, k), float('-inf'), dtype=torch.float32, device=dev)
+    best = torch.full((m, k), float('inf' if ascending else '-inf'), dtype=torch.float32, device=dev)
     keep = rank < k
     subj[slot[keep], rank[keep]], obj[slot[keep], rank[keep]], best[slot[keep], rank[keep]] = s[keep], o[keep], logits[keep]
-    kth = best[:, k - 1]                                 # -inf where the slot has fewer than K: everything counts
-    count = torch.zeros(m, dtype=torch.int64, device=dev).index_add_(0, slot, (logits >= kth[slot]).long())
+    kth = best[:, k - 1]                                 # the padding value where the slot has fewer than K: everything counts
+    within = logits <= kth[slot] if ascending else logits >= kth[slot]
+    count = torch.zeros(m, dtype=torch.int64, device=dev).index_add_(0, slot, within.long())
     over = torch.nonzero(count > share).reshape(-1)
     if over.numel():
         i = int(over[0])
-        raise _relation_overflow(int(rels[i]), int(count[i]), share, m, k)
+        raise _relation_overflow(int(rels[i]), int(count[i]), share, m, k, ascending)
     return subj, obj, best, count
 
 
-def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name):
+def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name, ascending=False):
     """``_mine_drive``'s top-K walk for ALL relations of ``rels`` (int64 [m], unique) at once: each has its own K-th key, found on
     its own histogram.  ``launch(mode, rels32, key_min, prefix_bits, prefix, bin_bits, out, capacity, out_base, words)`` is one
     sweep of the kernel over m slots -- int32 [m] relation ids (-1: the slot sits this pass out), per-slot ``key_min`` / ``prefix``
@@ -1814,7 +1817,9 @@ def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name):
     unresolved slot takes the bin that holds its K-th candidate and extends its prefix; a slot is resolved once what an emission
     at that bin's lower edge returns fits its ``share`` of the results (or the key is spent) and sits out the later sweeps.  One
     EMIT sweep follows, the segments an exclusive scan of the edges, each counter checked against its edge; then
-    ``relation_select``.  ``levels``: the (prefix bits, bin bits) of the passes.  Returns (subj, obj, logits, info)."""
+    ``relation_select``.  ``levels``: the (prefix bits, bin bits) of the passes.  ``ascending``: a record's fourth word is a distance
+    and the keys are those of -d (the TransE sweeps), so the walk is the same and only ``relation_select``'s order, padding and
+    count turn round.  Returns (subj, obj, logits, info)."""
     m = rels.numel()
     rel_host = rels.cpu().numpy().astype(np.int64)
     above, prefix = np.zeros(m, np.int64), np.zeros(m, np.int64)
@@ -1852,12 +1857,12 @@ def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name):
         live[done] = False
     over = np.nonzero(edge > share)[0]
     if over.size:                     # one exact value of a relation holds more candidates than it may return
-        raise _relation_overflow(rel_host[over[0]], edge[over[0]], share, m, k)
+        raise _relation_overflow(rel_host[over[0]], edge[over[0]], share, m, k, ascending)
     out_base = np.concatenate([[0], np.cumsum(edge)])
     total = int(out_base[-1])
     if total == 0:
         empty = torch.zeros(0, dtype=torch.int64, device=dev)
-        subj, obj, best, _ = relation_select(empty, empty, empty, torch.zeros(0, device=dev), rels, k, n, share)
+        subj, obj, best, _ = relation_select(empty, empty, empty, torch.zeros(0, device=dev), rels, k, n, share, ascending)
         return subj, obj, best, info
     out = torch.empty(total, 4, dtype=torch.int32, device=dev)
     counters = torch.zeros(m, dtype=torch.int64, device=dev)
@@ -1870,7 +1875,7 @@ def _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, name):
                            f'counted {edge[i]}')
     slot = torch.repeat_interleave(torch.arange(m, device=dev), torch.from_numpy(edge).to(dev))
     subj, obj, best, info['count'] = relation_select(slot, out[:, 0].long(), out[:, 2].long(), out[:, 3].contiguous().view(torch.float32),
-                                                     rels, k, n, share)
+                                                     rels, k, n, share, ascending)
     return subj, obj, best, info
 
 
@@ -1938,14 +1943,15 @@ def relation_topk_scores(emb, w, k, *, relations=None, bias=None, filt_lo=None, 
                           filt_ent, exclude_self, max_results)
 
 
-def relation_typed_plan(set_ptr, num_rels, rels, span=None):
+def relation_typed_plan(set_ptr, num_rels, rels, span=None, multiple=1):
     """``mine_typed_plan`` for the relations ``rels`` (int64 [m], unique) only, a unit's first word being the SLOT (the index into
-    ``rels``) as gv_mine_scores_typed_by_relation reads it; the default span is chosen from the chosen relations' tile pairs."""
+    ``rels``) as gv_mine_scores_typed_by_relation reads it; the default span is chosen from the chosen relations' tile pairs, a
+    multiple of ``multiple`` (4 for gv_transe_mine_typed_by_relation, which takes four object tiles at a time)."""
     sizes = (set_ptr[1:] - set_ptr[:-1]).to(torch.int64)
     chosen = torch.zeros(num_rels, dtype=torch.bool, device=set_ptr.device)
     chosen[rels.to(set_ptr.device)] = True
     sizes = sizes * torch.cat([chosen, chosen])
-    units = mine_typed_plan(torch.cat([sizes.new_zeros(1), torch.cumsum(sizes, 0)]), num_rels, span)
+    units = mine_typed_plan(torch.cat([sizes.new_zeros(1), torch.cumsum(sizes, 0)]), num_rels, span, multiple=multiple)
     slot_of = torch.full((num_rels,), -1, dtype=torch.int32, device=set_ptr.device)
     slot_of[rels.to(set_ptr.device)] = torch.arange(rels.numel(), dtype=torch.int32, device=set_ptr.device)
     units[:, 0] = slot_of[units[:, 0].long()]
@@ -4689,10 +4695,10 @@ def transe_mine(en, rn, p_norm, *, k=None, threshold=None, filt_lo=None, filt_hi
     return _transe_mine('gv_transe_mine', en, rn, p_norm, None, k, threshold, filt_lo, filt_hi, filt_ent, exclude_self, max_results)
 
 
-def _transe_mine(entry, en, rn, p_norm, members, k, threshold, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
-    """``transe_mine`` (``members`` None) and ``transe_mine_typed`` (``members`` = (set_ptr, set_ids, span)), as ``_mine_scores`` is
-    both DistMult miners; the member lists are checked before the tables are made contiguous."""
-    k, threshold, max_results = _mine_args(k, threshold, max_results)
+def _transe_mine_tables(en, rn, p_norm, members, filt_lo, filt_hi, filt_ent):
+    """What every TransE mining wrapper checks and prepares of its tables: the member lists (checked before the tables are made
+    contiguous), the two tables of one width, the norm, at least one relation, the sizes and the filter's shape.  Returns ``(en, rn,
+    p_norm, members, device, the empty mining result when there is no entity or else None)``."""
     if members is not None:
         for name, t in (('en', en), ('rn', rn)):
             if not isinstance(t, torch.Tensor) or t.dim() != 2:
@@ -4700,11 +4706,19 @@ def _transe_mine(entry, en, rn, p_norm, members, k, threshold, filt_lo, filt_hi,
         members = _mine_typed_members(members[0], members[1], en.shape[0], rn.shape[0]) + (members[2],)
     en, rn = _mine_tables(en, 'en', rn, 'rn', prepare=lambda t, name: _table(t.contiguous(), name))
     p_norm = _p_norm(p_norm)
-    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
-    if num_rels < 1:
+    if rn.shape[0] < 1:
         raise ValueError('need at least one relation')
-    _mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    _mine_sizes(en.shape[0], rn.shape[0], filt_lo, filt_hi, filt_ent)
     dev, nothing = _mine_device(en, 'en', rn, 'rn')
+    return en, rn, p_norm, members, dev, nothing
+
+
+def _transe_mine(entry, en, rn, p_norm, members, k, threshold, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
+    """``transe_mine`` (``members`` None) and ``transe_mine_typed`` (``members`` = (set_ptr, set_ids, span)), as ``_mine_scores`` is
+    both DistMult miners; the member lists are checked before the tables are made contiguous."""
+    k, threshold, max_results = _mine_args(k, threshold, max_results)
+    en, rn, p_norm, members, dev, nothing = _transe_mine_tables(en, rn, p_norm, members, filt_lo, filt_hi, filt_ent)
+    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
     if nothing is not None:
         return nothing
     lists = _mine_lists(members, 4, (filt_lo, filt_hi, filt_ent), n, num_rels, dev, lib.load().gv_transe_mine_workspace_bytes)
@@ -4731,3 +4745,73 @@ def transe_mine_typed(en, rn, p_norm, set_ptr, set_ids, *, k=None, threshold=Non
     a launch."""
     return _transe_mine('gv_transe_mine_typed', en, rn, p_norm, (set_ptr, set_ids, span), k, threshold, filt_lo, filt_hi, filt_ent,
                         exclude_self, max_results)
+
+
+# ---- per-relation completion for TransE: every relation's own K nearest -------------------------------------------------------------
+def _transe_relation_topk(entry, levels, en, rn, k, p_norm, relations, members, filt_lo, filt_hi, filt_ent, exclude_self, max_results):
+    """``transe_relation_topk`` (``members`` None) and ``transe_relation_topk_typed`` (``members`` = (set_ptr, set_ids, span)), as
+    ``_relation_topk`` is the DistMult pair: ``_transe_mine``'s checks and tables, the slots, one launch closure,
+    ``_mine_drive_by_relation`` on the keys of -d."""
+    _mine_tables(en, 'en', rn, 'rn')
+    if rn.shape[0] < 1:
+        raise ValueError('need at least one relation')
+    rels = relation_ids_check(relations, rn.shape[0])
+    m = rels.numel()
+    k, max_results, share = _relation_args(k, m, max_results)
+    if (m << max(b for _, b in levels)) > MINE_RELATION_HIST_WORDS:
+        raise ValueError(f'{m} relations: more than {MINE_RELATION_HIST_WORDS} histogram words; ask for them in several calls')
+    en, rn, p_norm, members, dev, nothing = _transe_mine_tables(en, rn, p_norm, members, filt_lo, filt_hi, filt_ent)
+    n, num_rels, dim = en.shape[0], rn.shape[0], en.shape[1]
+    rels = rels.to(dev)
+    info = {'count': torch.zeros(m, dtype=torch.int64, device=dev), 'passes': 0}
+    padding = (torch.full((m, k), -1, dtype=torch.int64, device=dev), torch.full((m, k), -1, dtype=torch.int64, device=dev),
+               torch.full((m, k), float('inf'), dtype=torch.float32, device=dev), info)
+    if nothing is not None:
+        return padding
+    if members is None:
+        lo32, hi32, ent32, n_ent, ws, ws_bytes = _mine_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev,
+                                                                   lib.load().gv_transe_mine_workspace_bytes)
+        sets, after = (), (ptr(ws), ws_bytes)
+    else:
+        set_ptr, set_ids = members[0].to(dev), members[1].to(dev)
+        units = relation_typed_plan(set_ptr, num_rels, rels, members[2], multiple=4)
+        if units.shape[0] == 0:
+            return padding
+        lo32, hi32, ent32, n_ent = _mine_typed_filter_args(filt_lo, filt_hi, filt_ent, n, num_rels, dev)
+        sets, after = (ptr(set_ptr), ptr(set_ids), ptr(units), units.shape[0]), ()
+
+    def launch(mode, rels32, key_min, prefix_bits, prefix, bin_bits, out, capacity, out_base, words):
+        lib.call(entry, ptr(en), ptr(rn), n, num_rels, dim, p_norm, *sets, ptr(lo32), ptr(hi32), ptr(ent32), n_ent,
+                 1 if exclude_self else 0, mode, ptr(rels32), m, ptr(key_min), prefix_bits, ptr(prefix), bin_bits, ptr(out), capacity,
+                 ptr(out_base), ptr(words), ptr(words), *after, lib.stream())
+
+    return _mine_drive_by_relation(launch, dev, n, rels, k, share, levels, entry, ascending=True)
+
+
+def transe_relation_topk(en, rn, k, p_norm, *, relations=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                         max_results=MINE_MAX_RESULTS):
+    """Every relation's OWN ``k`` nearest triplets of a TransE model: for each relation r of ``relations`` (unique ids, any order;
+    None: all) the k candidates (s, o) of smallest ``d[s, r, o] = ||(en[s] + rn[r]) - en[o]||_p``, ``transe_mine``'s distance bit
+    for bit and its candidates -- all (s, o) less the filter's triplets of r, less s == o under ``exclude_self``, less NaN (+inf is
+    a candidate); ``en`` / ``rn`` are the normalised tables.  ``transe_mine`` walks to ONE distance for the whole graph, which the
+    relations with short translation vectors fill; here thresholds, prefixes, histograms, counters and output segments are per
+    relation (gv_transe_mine_by_relation: the miner's loop order over the chosen relations only, four slots in flight, each with
+    its own early-exit bound and 256-bin histogram), so all lists come out of the same two to five sweeps and a few relations cost
+    their share of a sweep.  Returns ``(subj int64 (m, k), obj int64 (m, k), dist float32 (m, k), info)``, row i for
+    ``relations[i]`` in ``relation_select(ascending=True)``'s order -- distance ascending, then (s, o) --, short rows padded with
+    -1 / -1 / +inf; ``info['count']`` int64 [m] is each relation's candidates at or below its K-th distance, ``info['passes']`` the
+    sweeps.  ``m * k <= max_results``; a relation may return ``max_results // m`` records, and one whose candidates at or below its
+    K-th distance are more raises ``MineOverflow`` naming it."""
+    return _transe_relation_topk('gv_transe_mine_by_relation', MINE_RELATION_LEVELS, en, rn, k, p_norm, relations, None, filt_lo,
+                                 filt_hi, filt_ent, exclude_self, max_results)
+
+
+def transe_relation_topk_typed(en, rn, k, p_norm, set_ptr, set_ids, *, relations=None, filt_lo=None, filt_hi=None, filt_ent=None,
+                               exclude_self=True, max_results=MINE_MAX_RESULTS, span=None):
+    """``transe_relation_topk`` among the TYPE-CORRECT pairs only: s a member of set ``R + r``, o a member of set ``r``
+    (``transe_mine_typed``'s member lists and rule, the same distances bit for bit).  gv_transe_mine_typed_by_relation walks
+    ``relation_typed_plan``'s units -- the chosen relations' tiles only, four object tiles at a time; the result does not depend on
+    ``span`` -- and keeps the typed miner's 12 + 10 + 10 histogram levels, a unit's workgroup owning one relation.  A relation with
+    an empty subject or object list returns an all-padding row."""
+    return _transe_relation_topk('gv_transe_mine_typed_by_relation', MINE_RELATION_TYPED_LEVELS, en, rn, k, p_norm, relations,
+                                 (set_ptr, set_ids, span), filt_lo, filt_hi, filt_ent, exclude_self, max_results)

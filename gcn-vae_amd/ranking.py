@@ -1063,10 +1063,11 @@ def complete_entities_unfused(embedding, w, entities, k, *, side='s', filter_ind
 
 
 # ---- per-relation completion: which pairs belong to this relation? -----------------------------------------------------------------
-def _relation_pairs(val, r, num_rels, k, filt, exclude_self, subj_ok=None, obj_ok=None):
+def _relation_pairs(val, r, num_rels, k, filt, exclude_self, subj_ok=None, obj_ok=None, ascending=False):
     """Relation r's candidates at or above its K-th logit, ``(s, o, logits)``, from its (N, N) logits ``val``: all pairs less NaN,
     less the typed rule's misses (``subj_ok`` / ``obj_ok`` bool [N]), less s == o under ``exclude_self``, less the filter's
-    objects of (s, r) (``filt`` = the (lo, hi, ent) of ``_mine_filter``)."""
+    objects of (s, r) (``filt`` = the (lo, hi, ent) of ``_mine_filter``).  ``ascending``: ``val`` holds distances (transe.py) and
+    the candidates at or below the K-th smallest are kept."""
     n = val.shape[0]
     val = val.to(torch.float32) + 0.0
     cand = ~torch.isnan(val)
@@ -1080,18 +1081,20 @@ def _relation_pairs(val, r, num_rels, k, filt, exclude_self, subj_ok=None, obj_o
         cand &= ~_listed_mask(lo.reshape(-1).to(dev)[r::num_rels], hi.reshape(-1).to(dev)[r::num_rels], ent.to(dev), n, n, dev)
     vals = val[cand]
     if vals.numel() > k:
-        cand &= val >= torch.topk(vals, k).values[-1]
+        kth = torch.topk(vals, k, largest=not ascending).values[-1]
+        cand &= (val <= kth) if ascending else (val >= kth)
     s, o = torch.nonzero(cand, as_tuple=True)
     return s, o, val[cand]
 
 
-def _relation_rows(pairs_of, rels, k, n, share):
-    """The end of both host routes: ``pairs_of(i, r)`` is the ``_relation_pairs`` of slot i, ``ops.relation_select`` the rest."""
+def _relation_rows(pairs_of, rels, k, n, share, ascending=False):
+    """The end of the host routes (transe.py's with ``ascending``): ``pairs_of(i, r)`` is the ``_relation_pairs`` of slot i,
+    ``ops.relation_select`` the rest."""
     dev = rels.device
     parts = [pairs_of(i, r) for i, r in enumerate(rels.tolist())]
     slot = torch.cat([torch.full_like(p[0], i) for i, p in enumerate(parts)])
     subj, obj, logits, count = ops.relation_select(slot, torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]),
-                                                   torch.cat([p[2] for p in parts]), rels, k, n, share)
+                                                   torch.cat([p[2] for p in parts]), rels, k, n, share, ascending)
     return subj, obj, logits, {'count': count.to(dev), 'passes': len(parts)}
 
 

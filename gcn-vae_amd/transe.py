@@ -65,6 +65,15 @@ profile layout, the distance in place of the logit and probability.  With a ``ty
 type-correct facts are candidates, from ``ops.transe_entity_topk_typed`` (gv_transe_entity_topk_typed: the relations' candidate
 member lists are walked, rows gathered through the ids).
 
+Per-relation completion: ``complete_relations`` answers "which pairs belong to this relation?" -- every relation's OWN k nearest new
+facts, at ``predict_topk(direction='o')``'s distances, from ``ops.transe_relation_topk`` (gv_transe_mine_by_relation: the miner's
+loop order over the chosen relations, each with its own threshold, prefix, early-exit bound, histogram, counter and output segment,
+so all lists come from the same few sweeps).  ``complete_relations_from_distances`` states the rule on a materialised (R, N, N)
+tensor; ``complete_relations_unfused`` is the per-relation cross-check.  ``--relation-profile-topk K --relation-profile-ids IDS|FILE
+--relation-profile-out FILE`` write ``s r o rank distance`` in train.py's relation-profile layout; with a ``type_constraint``
+(``--relation-profile-typed``) only type-correct pairs are candidates (gv_transe_mine_typed_by_relation).  There is no Monte-Carlo
+form: TransE has no posterior.
+
 Relation prediction: ``rank_relations`` / ``evaluate_relations`` rank the true relation of every pair (s, ?, o) among all relations
 at distance ``||(n(o) - n(s)) - n(r)||_p`` -- in exact arithmetic the triplet's distance, though not ``predict_topk``'s bit pattern
 for it: the operands are associated differently --, raw and with a ``ranking.PairFilterIndex`` filtered, and
@@ -92,8 +101,9 @@ from . import ops
 from .ranking import (FilterIndex, MineOverflow, TypeConstraint, _listed_mask, _mine_args, _mine_filter, _mine_from_values, _mine_members,
                       UNCONSTRAINED, _complete_constraint, _complete_mask_args, _complete_queries, _complete_side, _complete_unfused,
                       _mine_unfused, complete_entities_from_scores, mid_ranks, rank_from_scores_constrained, topk_from_scores,
-                      PairFilterIndex, _pair_cat, _pair_checked, _pair_chunks, relation_ranks_from_scores)
-from .train import profile_entities_arg, write_profile_lines, write_relation_lines
+                      PairFilterIndex, _pair_cat, _pair_checked, _pair_chunks, relation_ranks_from_scores, _relation_masks,
+                      _relation_pairs, _relation_rows)
+from .train import profile_entities_arg, relation_profile_ids_arg, write_profile_lines, write_relation_lines
 
 
 # ------------------------------------------------------------------------------------------------
@@ -966,6 +976,122 @@ def write_entity_profiles(path, model_or_tables, entities, k, filter_index, type
 
 
 # ------------------------------------------------------------------------------------------------
+# per-relation completion: which pairs belong to this relation?
+# ------------------------------------------------------------------------------------------------
+def complete_relations_from_distances(dist, k, *, relations=None, filt_lo=None, filt_hi=None, filt_ent=None, exclude_self=True,
+                                      cand_subj=None, cand_obj=None, max_results=ops.MINE_MAX_RESULTS):
+    """The rule of ``ops.transe_relation_topk`` on a materialised tensor ``dist[r, s, o]`` (R, N, N), in plain torch (any device,
+    CPU included): the counterpart of ``ranking.complete_relations_from_scores``.  For each relation r of ``relations`` (unique
+    ids in [0, R), any order; None: all) the ``k`` candidates (s, o) of smallest distance.  Candidates: every (s, o), less
+    ``filt_ent[filt_lo[s * R + r]:filt_hi[s * R + r]]`` as objects of (s, r), less s == o when ``exclude_self``, less NaN
+    distances (+inf is a candidate, after every finite one), and with ``cand_subj`` / ``cand_obj`` (bool (R, N), together) only s
+    among ``cand_subj[r]`` and o among ``cand_obj[r]``.  Order inside a relation: ``mine_from_distances``' restricted to it --
+    distance ascending, then (s, o) ascending.  Returns ``(subj int64 (m, k), obj int64 (m, k), dist float32 (m, k), info)``, row i
+    for ``relations[i]``, rows with fewer than k candidates ending in -1 / -1 / +inf, a zero reported as +0; ``info['count']`` int64
+    [m] is each relation's candidates at or below its K-th distance's exact value (all, when fewer than K exist).  ``m * k <=
+    max_results``; a relation whose count exceeds its share ``max_results // m`` raises ``MineOverflow`` naming it."""
+    num_rels, n = dist.shape[0], dist.shape[1]
+    rels = ops.relation_ids_check(relations, num_rels).to(dist.device)
+    k, max_results, share = ops._relation_args(k, rels.numel(), max_results)
+    ops._mine_sizes(n, num_rels, filt_lo, filt_hi, filt_ent)
+    subj_ok, obj_ok = _relation_masks(cand_subj, cand_obj, num_rels, n, dist.device)
+    filt = (filt_lo, filt_hi, filt_ent)
+
+    def pairs_of(i, r):
+        typed = {} if subj_ok is None else dict(subj_ok=subj_ok[r], obj_ok=obj_ok[r])
+        return _relation_pairs(dist[r], r, num_rels, k, filt, exclude_self, ascending=True, **typed)
+
+    return _relation_rows(pairs_of, rels, k, n, share, ascending=True)
+
+
+def _relation_setup(model_or_tables, k, relations, max_results, filter_index, type_constraint):
+    """What the two routes of ``complete_relations`` check and prepare alike, before anything is asked of the device: (ent, rel,
+    p_norm, norm_flag, the relations int64 [m], k, a relation's share of ``max_results``, (lo, hi, ent), the constraint's member
+    lists or None, the constraint or None)."""
+    type_constraint = _complete_constraint(type_constraint)
+    ent, rel, p_norm, norm_flag = _tables(model_or_tables)
+    ent, rel = ent.contiguous(), rel.to(ent.device).contiguous()
+    rels = ops.relation_ids_check(relations, rel.shape[0]).to(ent.device)
+    k, _, share = ops._relation_args(k, rels.numel(), max_results)
+    filt = _mine_filter(filter_index, ent.shape[0], rel.shape[0], ent.device)
+    members = None if type_constraint is None else _mine_members(type_constraint, ent.shape[0], rel.shape[0], ent.device)
+    return ent, rel, ops._p_norm(p_norm), norm_flag, rels, k, share, filt, members, type_constraint
+
+
+def complete_relations(model_or_tables, k, *, relations=None, filter_index=None, exclude_self=True, type_constraint=UNCONSTRAINED,
+                       max_results=ops.MINE_MAX_RESULTS):
+    """Which pairs belong to this relation?  For every relation r of ``relations`` (unique ids, any order; default: every relation)
+    its OWN ``k`` nearest new facts (s, r, o), at the distance ``||n(E_s) + n(R_r) - n(E_o)||_p`` of ``predict_topk(direction='o')``
+    bit for bit; with a ``FilterIndex`` the known triplets are left out.  ``mine_triplets`` cannot answer this: its one distance
+    for the whole graph is filled by the relations with short translation vectors.  Here every relation has its own threshold,
+    found for all of them in the same few fused sweeps (ops.transe_relation_topk), and a handful of relations cost their share of
+    a sweep.  ``model_or_tables`` is a ``TransE`` or ``(ent, rel, p_norm, norm_flag)``; the normalised tables are built once.
+    Returns ``(subj int64 (m, k), obj int64 (m, k), dist float32 (m, k), info)`` in the order of
+    ``complete_relations_from_distances``: row i for ``relations[i]``, nearest first, ties by (s, o), short rows padded with -1 /
+    -1 / +inf; ``info['count']`` int64 [m], ``info['passes']``.  ``k >= 1`` and ``m * k <= max_results``; ``MineOverflow`` (naming
+    the relation) rather than a truncated list.  With a ``type_constraint`` (TypeConstraint) only type-correct pairs are
+    candidates -- ``mine_triplets(type_constraint=)``'s rule on the same member lists, at the same distances
+    (ops.transe_relation_topk_typed).  The unconstrained call leaves the argument out; an explicit None is a TypeError.  There is no
+    Monte-Carlo form: TransE has no posterior."""
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag, rels, k, _, (lo, hi, f_ent), members, _ = \
+            _relation_setup(model_or_tables, k, relations, max_results, filter_index, type_constraint)
+        if ent.shape[0] == 0:
+            en, rn = ent, rel
+        else:
+            en = ops.transe_queries(ent, norm_flag=norm_flag)             # the normalised tables, once
+            rn = ops.transe_queries(rel, norm_flag=norm_flag)
+        rule = dict(relations=rels, filt_lo=lo, filt_hi=hi, filt_ent=f_ent, exclude_self=exclude_self, max_results=max_results)
+        if members is not None:
+            return ops.transe_relation_topk_typed(en, rn, k, p_norm, members[0], members[1], **rule)
+        return ops.transe_relation_topk(en, rn, k, p_norm, **rule)
+
+
+def complete_relations_unfused(model_or_tables, k, *, relations=None, filter_index=None, exclude_self=True,
+                               type_constraint=UNCONSTRAINED, max_results=ops.MINE_MAX_RESULTS):
+    """``complete_relations`` from materialised distances, one relation at a time: ``ops.transe_queries`` +
+    ``ops.transe_distances`` into an (N, N) tensor, then the rule of ``complete_relations_from_distances``.  The in-repo
+    cross-check and the bench's comparator, never a fallback."""
+    with torch.no_grad():
+        ent, rel, p_norm, norm_flag, rels, k, share, filt, _, type_constraint = \
+            _relation_setup(model_or_tables, k, relations, max_results, filter_index, type_constraint)
+        n, num_rels = ent.shape[0], rel.shape[0]
+        masks = None
+        if type_constraint is not None:
+            masks = (type_constraint.mask(torch.arange(num_rels, 2 * num_rels), ent.device),
+                     type_constraint.mask(torch.arange(num_rels), ent.device))
+        subjects = torch.arange(n, device=ent.device)
+        en = ops.transe_queries(ent, norm_flag=norm_flag) if n else ent
+
+        def pairs_of(i, r):
+            q = ops.transe_queries(ent, rel, subjects, torch.full_like(subjects, r), head=False, norm_flag=norm_flag)
+            val = ops.transe_distances(q, en, p_norm)
+            typed = {} if masks is None else dict(subj_ok=masks[0][r], obj_ok=masks[1][r])
+            return _relation_pairs(val, r, num_rels, k, filt, exclude_self, ascending=True, **typed)
+
+        return _relation_rows(pairs_of, rels, k, n, share, ascending=True)
+
+
+def write_relation_profiles(path, model_or_tables, relations, k, filter_index, type_constraint=None):
+    """Per-relation completion as TSV, ``s  r  o  rank  distance`` (the columns of ``write_completions``, and of train.py's
+    ``relation_profiles.tsv`` with the distance in place of the logit: the files join on s, r, o): for every relation of
+    ``relations``, in the order given, its OWN ``k`` nearest new facts (``complete_relations``; ``filter_index``: the known ones
+    left out, as are loops), nearest first with the rank counted from 1 within the relation.  A relation with fewer than k
+    candidates has fewer lines: the padding is left out.  With a ``type_constraint`` (ranking.TypeConstraint) only type-correct
+    facts are written.  Returns the number of lines written."""
+    constrained = {} if type_constraint is None else {'type_constraint': type_constraint}
+    subj, obj, dist, _ = complete_relations(model_or_tables, k, relations=torch.as_tensor(relations, dtype=torch.long),
+                                            filter_index=filter_index, **constrained)
+    n_lines = 0
+    with open(path, 'w') as f:
+        for r, ss, os_, xs in zip(relations, subj.tolist(), obj.tolist(), dist.tolist()):
+            lines = [f"{a}\t{r}\t{b}\t{i}\t{x:.9g}\n" for i, (a, b, x) in enumerate(zip(ss, os_, xs), 1) if a >= 0]
+            f.writelines(lines)
+            n_lines += len(lines)
+    return n_lines
+
+
+# ------------------------------------------------------------------------------------------------
 # CLI (baselines/transe/main.py's hyperparameters as defaults)
 # ------------------------------------------------------------------------------------------------
 def build_parser():
@@ -1043,7 +1169,24 @@ def build_parser():
                    help='with --profile-topk: write type-correct facts only (the entity seen on its side of the relation, the other '
                         'entity seen on the other side, in train + valid + test); the same columns; --type-constrain does not '
                         'constrain profiles')
+    p.add_argument('--relation-profile-topk', type=int, default=None,
+                   help='after the final evaluation write, for every relation of --relation-profile-ids, ITS OWN K nearest NEW facts '
+                        '(train + valid + test triplets and loops left out) to --relation-profile-out -- every relation has its own '
+                        'distance threshold, where --complete-topk has one for the whole graph')
+    p.add_argument('--relation-profile-ids', type=str, default=None,
+                   help='the relations of --relation-profile-topk: comma-separated ids, or a file with one id per line, each at most '
+                        'once; default: every relation')
+    p.add_argument('--relation-profile-out', type=str, default=None,
+                   help='TSV written by --relation-profile-topk (default transe_relation_profiles.tsv): s, r, o, rank from 1 within '
+                        'the relation, distance; relations in the order asked; joins with --complete-out and with train.py\'s '
+                        '--relation-profile-out on s, r, o')
+    p.add_argument('--relation-profile-typed', action='store_true',
+                   help='with --relation-profile-topk: write type-correct facts only (s seen as subject of r, o seen as its object, '
+                        'in train + valid + test); the same columns; --type-constrain and --complete-typed keep their meaning')
     return p
+
+
+RELATION_PROFILE_OUT = 'transe_relation_profiles.tsv'      # --relation-profile-out when it is not given
 
 
 def check_args(args):
@@ -1091,6 +1234,17 @@ def check_args(args):
         raise ValueError(f'--predict-relations must lie in [1, {ops.TOPK_MAX}] (0 = off), got {args.predict_relations}')
     if getattr(args, 'relations_typed', False) and not (getattr(args, 'relation_eval', False) or getattr(args, 'predict_relations', 0) > 0):
         raise ValueError('--relations-typed restricts the relation queries: it needs --relation-eval or --predict-relations')
+    rk = getattr(args, 'relation_profile_topk', None)
+    if rk is not None and rk < 1:
+        raise ValueError(f'--relation-profile-topk counts the facts kept per relation: it must be >= 1, got {rk}')
+    if getattr(args, 'relation_profile_typed', False) and rk is None:
+        raise ValueError('--relation-profile-typed restricts the per-relation lists: it needs --relation-profile-topk')
+    if getattr(args, 'relation_profile_out', None) is not None and rk is None:
+        raise ValueError('--relation-profile-out names the file of the per-relation lists: it needs --relation-profile-topk')
+    if getattr(args, 'relation_profile_ids', None) is not None:
+        if rk is None:
+            raise ValueError('--relation-profile-ids chooses the relations of the per-relation lists: it needs --relation-profile-topk')
+        relation_profile_ids_arg(args.relation_profile_ids)
 
 
 def main(args):
@@ -1107,6 +1261,9 @@ def main(args):
     who = None
     if getattr(args, 'profile_topk', 0) > 0:         # a bad id is refused before any training
         who = profile_entities_arg(getattr(args, 'profile_entities', None), data.num_nodes)
+    which = None
+    if getattr(args, 'relation_profile_topk', None) is not None:
+        which = relation_profile_ids_arg(getattr(args, 'relation_profile_ids', None), data.num_rels)
     model = TransE(data.num_nodes, data.num_rels, dim=args.dim, p_norm=args.p_norm, norm_flag=bool(args.norm_flag))
     filt = None
     if args.filtered_eval:
@@ -1169,6 +1326,16 @@ def main(args):
         n_lines = write_entity_profiles(args.profile_out, model, who, args.profile_topk, known, typed)
         print(f'wrote {n_lines} new {"type-correct " if typed is not None else ""}facts around {len(who)} entities (nearest '
               f'{args.profile_topk} over all relations, as subject and as object, known triplets filtered) to {args.profile_out}')
+    if which is not None:
+        known = filt if filt is not None else FilterIndex(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        typed = None
+        if getattr(args, 'relation_profile_typed', False):
+            typed = types if types is not None else \
+                TypeConstraint(data.num_nodes, data.num_rels, data.train, data.valid, data.test, device=dev)
+        path = args.relation_profile_out if getattr(args, 'relation_profile_out', None) is not None else RELATION_PROFILE_OUT
+        n_lines = write_relation_profiles(path, model, which, args.relation_profile_topk, known, typed)
+        print(f'wrote {n_lines} new {"type-correct " if typed is not None else ""}facts of {len(which)} relations (each relation\'s own '
+              f'nearest {args.relation_profile_topk}, known triplets filtered) to {path}')
     return out
 
 

@@ -1032,6 +1032,39 @@ int gv_transe_mine_typed(const float* en, const float* rn, int n, int num_rels, 
                          uint32_t key_min, int prefix_bits, uint32_t prefix, int bin_bits, int32_t* out, int64_t capacity,
                          uint64_t* counter, uint64_t* hist, void* stream);
 
+/* Per-relation completion for TransE (csrc/k_transe_mine.hip): gv_transe_mine / gv_transe_mine_typed with the selection state PER
+ * RELATION, the slots of gv_mine_scores_by_relation / gv_mine_scores_typed_by_relation.  A slot i < m is the relation rels[i]
+ * (int32 [m], device memory) with its own
+ *   key_min [m] (uint32), counter [m] (uint64) and output segment out[out_base[i] .. out_base[i + 1]) (out_base int64 [m + 1],
+ *                 records of out [capacity][4]; a segment is clamped into [0, capacity])                        -- GV_MINE_EMIT
+ *   prefix [m] (uint32; not read at prefix_bits 0) and histogram hist [i << bin_bits .. (i + 1) << bin_bits)   -- GV_MINE_HIST
+ * while prefix_bits and bin_bits are the pass's.  Slot i's counter ends as the number of its candidates with key >= key_min[i] and
+ * keeps counting past its segment; all m counters (EMIT) or all m << bin_bits histogram words (HIST) are zeroed here.  An id
+ * outside [0, num_rels) makes the slot EMPTY for this pass -- nothing of it is computed, counted or written -- and a relation that
+ * is in no slot costs nothing.  A record is (s, r, o, bits of d) with r the relation, not the slot, d never -0; tables, distances,
+ * keys (ordered_u32(-d)), candidates, filter and exclude_self are those of gv_transe_mine (gv_transe_mine_typed) bit for bit.  The
+ * monotone early exit of the column loop is bounded by the SLOT's threshold or prefix, never by another slot's.
+ * gv_transe_mine_by_relation walks gv_transe_mine's loop order over the slots (a workgroup owns a tile pair and a span of slots,
+ * four live slots in flight at once); its histogram levels have 1 <= bin_bits <= 8 (one 256-bin LDS histogram per slot in flight,
+ * flushed per slot).  The workspace is gv_transe_mine's (gv_transe_mine_workspace_bytes; only with a filter).
+ * gv_transe_mine_typed_by_relation takes gv_transe_mine_typed's member lists, filter and units, except that a unit's first word is
+ * the SLOT whose relation it walks (a unit of a slot outside [0, m) or of an empty slot does nothing); 1 <= bin_bits <= 12.
+ * Checked on the host before any launch, the message naming the entry: everything gv_transe_mine (gv_transe_mine_typed) checks,
+ * 1 <= m <= num_rels, m << bin_bits <= 2^24 histogram words, the per-slot arrays of the mode not NULL, out 16-byte aligned.
+ * n == 0: nothing is launched.  Integer atomics on the counters and the histograms only; the result does not depend on the spans
+ * or the launch geometry. */
+int gv_transe_mine_by_relation(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm, const int32_t* filt_lo,
+                               const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent, int exclude_self, int mode,
+                               const int32_t* rels, int m, const uint32_t* key_min, int prefix_bits, const uint32_t* prefix,
+                               int bin_bits, int32_t* out, int64_t capacity, const int64_t* out_base, uint64_t* counter,
+                               uint64_t* hist, void* workspace, int64_t workspace_bytes, void* stream);
+int gv_transe_mine_typed_by_relation(const float* en, const float* rn, int n, int num_rels, int dim, int p_norm,
+                                     const int64_t* set_ptr, const int32_t* set_ids, const int32_t* units, int64_t n_units,
+                                     const int32_t* filt_lo, const int32_t* filt_hi, const int32_t* filt_ent, int n_filt_ent,
+                                     int exclude_self, int mode, const int32_t* rels, int m, const uint32_t* key_min, int prefix_bits,
+                                     const uint32_t* prefix, int bin_bits, int32_t* out, int64_t capacity, const int64_t* out_base,
+                                     uint64_t* counter, uint64_t* hist, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K2/K4  dense fp32 GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32; exact fp32 fma chain):
  *   C = act(op(A) @ op(B) + bias) (+ C if accumulate)      op(X) = X or X^T; bias (length N) optional.

@@ -9,6 +9,7 @@ process under a time limit and stops the bench at its first failure.
     python tools/transe_bench.py --topk [--out profiles/transe_topk/bench.json]
     python tools/transe_bench.py --mine [--out profiles/transe_mine/bench.json]
     python tools/transe_bench.py --profile [--profile-shapes fb,wn18rr,fb-dim500] [--out profiles/transe_profile/bench.json]
+    python tools/transe_bench.py --relation-profile [--relation-profile-shapes fb,wn18rr,fb-dim500,wn18rr-dim500]
 
 --topk runs the link-prediction leg alone: both directions of the test split (40 932 queries), filter = train + valid + test,
 L1 and L2, k = 10 and 100; per configuration predict_topk (fused), predict_topk_unfused (materialised distances + sort) and
@@ -26,6 +27,13 @@ test filtered, loops kept as predict_topk keeps them), FB15k-237 and WN18RR size
 entity and for a single one: complete_entities (fused) against predict_topk over all m x R queries + a torch merge, and against
 complete_entities_unfused -- on the all-entities set measured on 256 entities and scaled, which the JSON says.  All three in one
 process, each warmed up once, medians of --profile-repeats synchronised runs; the answers are asserted bit-equal.
+
+--relation-profile runs the per-relation completion leg alone: each relation's own K nearest new facts (train + valid + test filtered,
+loops left out), FB15k-237 and WN18RR sizes, dim 200 and 500, L1 and L2, typed and untyped, K = 10 and 1 000, for every relation
+and for three: complete_relations (fused) against one transe_mine(k = K) call per relation on that relation's row and filter
+slice, and against complete_relations_unfused.  All three in one process, each warmed up once, medians of
+--relation-profile-repeats synchronised runs; the answers are asserted bit-equal.  It also reports how many relations the graph's
+100 000 nearest new triplets (mine_triplets) touch.  Output: profiles/transe_relation_profile/bench.json.
 
 --opt runs the optimiser leg alone (python tools/transe_bench.py --opt [--out profiles/transe_opt/bench.json]): the whole step at
 the workload above with SGD, Adagrad, Adadelta and Adam, eager and captured, the four interleaved over --opt-rounds rounds of
@@ -290,6 +298,94 @@ def case_profile(steps, warmup, repeats=3, shapes='fb,wn18rr', chunk=2048, unfus
     return res
 
 
+RELATION_SHAPES = dict(PROFILE_SHAPES, **{'wn18rr-dim500': ('WN18RR-synthetic', 500)})
+
+
+def case_relation_profile(steps, warmup, repeats=3, shapes='fb,wn18rr,fb-dim500,wn18rr-dim500', cover_k=100000):
+    """The per-relation completion leg: transe.complete_relations (fused: every relation's own threshold from the same few sweeps)
+    against (a) one ops.transe_mine[_typed](k=K) call per relation on that relation's row of the normalised table and its slice of
+    the filter (and its two member lists), and (b) transe.complete_relations_unfused; L1 and L2, typed and untyped, K = 10 and
+    1 000, every relation and three relations.  The three answers are asserted bit-equal.  Per shape and norm it also counts the
+    relations that the graph's ``cover_k`` nearest new triplets (mine_triplets) touch."""
+    from gcn_vae_amd import ops, transe
+    from gcn_vae_amd.data import load_data
+    from gcn_vae_amd.ranking import FilterIndex, TypeConstraint, _mine_filter
+
+    def say(*a):
+        print(*a, file=sys.stderr, flush=True)
+
+    def same(a, b):
+        return (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2].view(torch.int32), b[2].view(torch.int32))
+                and torch.equal(a[3]['count'], b[3]['count']))
+
+    res = dict(unit='ms; each route warmed up once, then the median of synchronised timed runs, all in one process', repeats=repeats,
+               exclude_self=True, shapes={})
+    for shape in shapes.split(','):
+        name, dim = RELATION_SHAPES[shape]
+        data = load_data(name)
+        n, num_rels = data.num_nodes, data.num_rels
+        fi = FilterIndex(n, num_rels, data.train, data.valid, data.test, device='cuda')
+        tc = TypeConstraint(n, num_rels, data.train, data.valid, data.test, device='cuda')
+        set_ptr, set_ids = tc.members(torch.device('cuda'))
+        lo, hi, f_ent = _mine_filter(fi, n, num_rels, torch.device('cuda'))
+        torch.manual_seed(0)
+        model = transe.TransE(n, num_rels, dim=dim, p_norm=1, norm_flag=True).cuda()
+        ent, rel = model.ent_embeddings.weight.data, model.rel_embeddings.weight.data
+        en, rn = ops.transe_queries(ent, norm_flag=True), ops.transe_queries(rel, norm_flag=True)
+        cases, covered = [], {}
+        for p in (1, 2):
+            tables = (ent, rel, p, True)
+            trip = transe.mine_triplets(tables, k=cover_k, filter_index=fi)[0]
+            covered[f'p{p}'] = int(torch.unique(trip[:, 1]).numel())
+            say(f'{shape} L{p}: the graph\'s {cover_k} nearest new triplets touch {covered[f"p{p}"]} of {num_rels} relations')
+            for typed in (False, True):
+                constrained = dict(type_constraint=tc) if typed else {}
+                for which, rels in (('all', list(range(num_rels))), ('three', [num_rels - 1, 0, num_rels // 2])):
+                    for k in (10, 1000):
+                        def fused():
+                            return transe.complete_relations(tables, k, relations=rels, filter_index=fi, **constrained)
+
+                        def per_relation():
+                            rows = []
+                            for r in rels:
+                                f = dict(filt_lo=lo[r::num_rels], filt_hi=hi[r::num_rels], filt_ent=f_ent)
+                                if typed:
+                                    o_ids = set_ids[set_ptr[r]:set_ptr[r + 1]]
+                                    s_ids = set_ids[set_ptr[num_rels + r]:set_ptr[num_rels + r + 1]]
+                                    ptr_r = torch.tensor([0, o_ids.numel(), o_ids.numel() + s_ids.numel()], device='cuda')
+                                    rows.append(ops.transe_mine_typed(en, rn[r:r + 1], p, ptr_r, torch.cat([o_ids, s_ids]), k=k, **f))
+                                else:
+                                    rows.append(ops.transe_mine(en, rn[r:r + 1], p, k=k, **f))
+                            return rows
+
+                        def unfused():
+                            return transe.complete_relations_unfused(tables, k, relations=rels, filter_index=fi, **constrained)
+
+                        got = fused()
+                        eq_u = same(got, unfused())
+                        eq_r = all(torch.equal(t[:, 0], got[0][i][:t.shape[0]]) and torch.equal(t[:, 2], got[1][i][:t.shape[0]])
+                                   and torch.equal(d.view(torch.int32), got[2][i][:t.shape[0]].view(torch.int32))
+                                   and info['count'] == int(got[3]['count'][i]) and bool((got[0][i][t.shape[0]:] < 0).all())
+                                   for i, (t, d, info) in enumerate(per_relation()))
+                        t_f = _repeat_ms(fused, repeats)
+                        t_r = _repeat_ms(per_relation, max(1, repeats - 1))
+                        t_u = _repeat_ms(unfused, max(1, repeats - 1))
+                        case = dict(p_norm=p, typed=typed, relations=which, m=len(rels), k=k, passes=got[3]['passes'], fused=t_f,
+                                    per_relation_miner=t_r, per_relation_miner_over_fused=t_r['median_ms'] / t_f['median_ms'],
+                                    unfused=t_u, unfused_over_fused=t_u['median_ms'] / t_f['median_ms'], equal_per_relation=eq_r,
+                                    equal_unfused=eq_u)
+                        say(f"{shape} L{p} {'typed  ' if typed else 'untyped'} {which:5s} k={k:4d}: fused {t_f['median_ms']:9.2f} ms "
+                            f"({got[3]['passes']} sweeps) | miner per relation {t_r['median_ms']:9.2f} ms "
+                            f"({case['per_relation_miner_over_fused']:.2f}x) | unfused {t_u['median_ms']:9.2f} ms "
+                            f"({case['unfused_over_fused']:.2f}x) | equal: {eq_r} {eq_u}")
+                        if not (eq_r and eq_u):
+                            raise SystemExit('the fused route differs from a cross-check route')
+                        cases.append(case)
+        res['shapes'][shape] = dict(dataset=name, entities=n, relations=num_rels, dim=dim, filter_triplets=int(fi.ent['o'].numel()),
+                                    cover_k=cover_k, relations_covered_by_mine_triplets=covered, cases=cases)
+    return res
+
+
 OPT_ALPHA = {'sgd': 1.0, 'adagrad': 0.1, 'adadelta': 1.0, 'adam': 1e-3}
 
 
@@ -393,8 +489,12 @@ def main():
     ap.add_argument('--profile', action='store_true', help='run the per-entity completion leg alone')
     ap.add_argument('--profile-repeats', type=int, default=3)
     ap.add_argument('--profile-shapes', default='fb,wn18rr', help=f'comma list of {sorted(PROFILE_SHAPES)}')
-    ap.add_argument('--out', default=None, help='with --topk / --mine / --opt / --profile: also write the JSON result to this file '
-                                                '(--profile: profiles/transe_profile/bench.json unless given)')
+    ap.add_argument('--relation-profile', action='store_true', help='run the per-relation completion leg alone')
+    ap.add_argument('--relation-profile-repeats', type=int, default=3)
+    ap.add_argument('--relation-profile-shapes', default='fb,wn18rr,fb-dim500,wn18rr-dim500', help=f'comma list of {sorted(RELATION_SHAPES)}')
+    ap.add_argument('--out', default=None, help='with --topk / --mine / --opt / --profile / --relation-profile: also write the JSON '
+                                                'result to this file (--profile: profiles/transe_profile/bench.json, '
+                                                '--relation-profile: profiles/transe_relation_profile/bench.json unless given)')
     a = ap.parse_args()
     if a.case == 'mine':
         print('RESULT ' + json.dumps(case_mine(a.steps, a.warmup, a.mine_repeats)))
@@ -408,15 +508,23 @@ def main():
     if a.case == 'profile':
         print('RESULT ' + json.dumps(case_profile(a.steps, a.warmup, a.profile_repeats, a.profile_shapes)))
         return
+    if a.case == 'relation_profile':
+        print('RESULT ' + json.dumps(case_relation_profile(a.steps, a.warmup, a.relation_profile_repeats, a.relation_profile_shapes)))
+        return
     if a.profile and a.out is None:
         a.out = os.path.join(ROOT, 'profiles', 'transe_profile', 'bench.json')
-    if a.topk or a.mine or a.opt or a.profile:
+    if a.relation_profile and a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'transe_relation_profile', 'bench.json')
+    if a.topk or a.mine or a.opt or a.profile or a.relation_profile:
         leg = ['--case', 'topk', '--topk-repeats', str(a.topk_repeats)] if a.topk else ['--case', 'mine', '--mine-repeats',
                                                                                            str(a.mine_repeats)]
         if a.opt:
             leg = ['--case', 'opt', '--opt-rounds', str(a.opt_rounds), '--steps', str(a.steps), '--warmup', str(a.warmup)]
         if a.profile:
             leg = ['--case', 'profile', '--profile-repeats', str(a.profile_repeats), '--profile-shapes', a.profile_shapes]
+        if a.relation_profile:
+            leg = ['--case', 'relation_profile', '--relation-profile-repeats', str(a.relation_profile_repeats),
+                   '--relation-profile-shapes', a.relation_profile_shapes]
         # the mining and the profile legs report each configuration on stderr as it finishes
         r = subprocess.run(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__)] + leg,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE if a.topk else None, text=True, cwd=ROOT)
